@@ -1,14 +1,23 @@
 #!/usr/bin/env python3
 """bench.py — decode tokens/sec of the MI355X-native KuiperLLama decode path.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N>1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ...
   One JSON line on stdout (rank 0).
 
+* plain run: set up the workload, W warm-up steps, the K timed steps, the line (`metric`, `value`,
+             `unit`, `higher_is_better`, `dtype`, `ms_per_step` = ms of one timed step) - nothing
+             else.  Everything below that takes runs of its own (second workload, roofline kernel
+             timings, CPU baselines, other configs, latency / prefill / long-context / load probes)
+             runs only with --full.
+* --dump-outputs DIR : after the timed steps, what their last step handed the caller of generate():
+             DIR/words.npy (the K generated token ids, float64) and DIR/logits.npy (the logits of
+             the last step, float32).  Same arguments -> same seeded weights and prompt -> same
+             inputs in every run, so two builds can be compared output for output.
 * metric   : BASELINE.json "decode tokens/sec" (batch-1 greedy, the reference's generate()
-             loop, demo/main.cpp:5-47), workload = configs[1] Llama-3.2-1B fp32; the second half
-             of the metric (Llama-2-7B int8) is measured in the same run and reported under
-             "secondary".
+             loop, demo/main.cpp:5-47), workload = configs[1] Llama-3.2-1B fp32; with --full the
+             second half of the metric (Llama-2-7B int8) is measured in the same run and reported
+             under "secondary".
 * a "step" : one decode step = one forward pass of the whole model + greedy argmax for one
              token, all inside one hipGraph replay.  Weights, KV cache and activations are
              resident in HBM before the timed region starts.
@@ -35,7 +44,7 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
              --no-others for rocprofv3 runs (they launch the same kernel instantiations at other
              sizes and would blur the --stats average of the headline workload).
 * long_context : single-step latency of the headline workload deep in its 131072-row cache.
-* --no-extras  : only the contract's timed region + the roofline kernel (smoke runs).
+* --full --no-extras : only the contract's timed region + the roofline kernel.
 """
 from __future__ import annotations
 
@@ -506,6 +515,9 @@ def measure(spec, args, rank, world, local_rank, primary):
     dev = torch.device(f"cuda:{local_rank}")
     m, img = build_model(spec, local_rank)
     words, wall, ev_ms = timed_generate(m, args.steps, args.warmup, world, dev)
+    # what the last timed step handed its caller, read back before anything else runs on the model
+    outputs = ({"words": np.asarray(words, dtype=np.float64), "logits": m.logits()}
+               if primary and args.dump_outputs else None)
     tok_s = world * args.steps / wall
     mean_pos = (args.steps - 1) / 2.0
     bytes_tok = spec.algorithmic_bytes_per_token(mean_pos)
@@ -526,6 +538,11 @@ def measure(spec, args, rank, world, local_rank, primary):
         out["kv_cache"] = {"reserved_bytes": kv_res, "committed_bytes_after_timed_run": kv_com,
                            "what": "address range of the reference's [layer, seq_len, kv_dim] x 2 allocation vs the HBM "
                                    "mapped behind it after the timed run (8-MiB chunks, on demand)"}
+    if outputs is not None:
+        out["outputs"] = outputs
+    if not args.full:  # a plain run: the timed region is all it measures
+        m.close()
+        return out
     ref_words = words
     if args.extras:
         # SURVEY 8d extras, all outside the contract's timed region: repeated runs (median) and the
@@ -677,6 +694,50 @@ def _flat_first(d: dict) -> dict:
             **{k: v for k, v in d.items() if isinstance(v, (dict, list))}}
 
 
+DATA = ("synthetic via kuiperllama_amd.binfmt.synth_image (seeded torch RNG on the GPU, the "
+        "reference exporter's .bin byte layout and init std; not the reference exporter itself)")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _contract_head(spec, args, world, res) -> dict:
+    """The contract's scalar keys, in the contract's order: the head of every line."""
+    return {"metric": "decode tokens/sec",
+            "value": res["value"], "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "int8 weights x f32 activations" if spec.quant else "f32"}
+
+
+def _config_head(spec, args, world, timing_backend) -> dict:
+    return {"workload": f"{spec.name} greedy decode, batch 1, prompt {PROMPT}, "
+                        f"{args.steps} steps from pos 0 (demo/main.cpp generate)",
+            "parallelism": f"replicas{world} (no shard, no data-path collective; one process "
+                           f"per GPU, HIP_VISIBLE_DEVICES/LOCAL_RANK pinning)",
+            "timing_backend": timing_backend,
+            "exec": "hipGraph replay, 5L+2 fused HIP kernels per token",
+            "kv_cache_rows": spec.seq_len}
+
+
+def plain_line(spec, args, world, res, timing_backend) -> dict:
+    """The line of a plain run (no --full): the contract's keys and what the timed run itself reported."""
+    return {**_contract_head(spec, args, world, res),
+            "hip_event_ms": res["hip_event_ms"], "step_gbs": res["step_gbs"], "data": DATA,
+            "config": _config_head(spec, args, world, timing_backend),
+            "replicas": res["replicas"], "kv_cache": res.get("kv_cache"), "selftests": res.get("selftests"),
+            "words_head": res["words_head"]}
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """outputs {name: float32 / float64 array} -> out_dir/<name>.npy, at most DUMP_LIMIT_BYTES in all."""
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def assemble_line(spec, args, world, res, secondary, others, skipped, timing_backend) -> dict:
     """The ONE JSON line.  Both halves of BASELINE.json's metric (Llama-3.2-1B fp32 and Llama-2-7B int8 decode
     tok/s) and their roofline fractions are carried as SCALARS inside `roofline` and `config` (a record parser that
@@ -703,13 +764,7 @@ def assemble_line(spec, args, world, res, secondary, others, skipped, timing_bac
     roofline["secondary_achieved"] = sr.get("achieved")
     roofline["secondary_step_frac"] = summary["secondary_step_frac"]
     roofline["secondary_step_achieved"] = sr.get("step", {}).get("achieved")
-    config = {"workload": f"{spec.name} greedy decode, batch 1, prompt {PROMPT}, "
-                          f"{args.steps} steps from pos 0 (demo/main.cpp generate)",
-              "parallelism": f"replicas{world} (no shard, no data-path collective; one process "
-                             f"per GPU, HIP_VISIBLE_DEVICES/LOCAL_RANK pinning)",
-              "timing_backend": timing_backend,
-              "exec": "hipGraph replay, 5L+2 fused HIP kernels per token",
-              "kv_cache_rows": spec.seq_len,
+    config = {**_config_head(spec, args, world, timing_backend),
               "tok_s_128_steps": summary["tok_s_128_steps"],
               "secondary_workload": summary["secondary_workload"],
               "secondary_value": summary["secondary_value"],
@@ -722,17 +777,12 @@ def assemble_line(spec, args, world, res, secondary, others, skipped, timing_bac
               "secondary_selftest_ring": (secondary.get("selftests") or {}).get("ring") if sec_ok else None,
               "secondary_selftest_attn_merge": (secondary.get("selftests") or {}).get("attn_merge") if sec_ok else None}
     line = {
-        "metric": "decode tokens/sec",
-        "value": res["value"], "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None,
-        "dtype": "int8 weights x f32 activations" if spec.quant else "f32",
+        **_contract_head(spec, args, world, res),
         "tok_s_128_steps": summary["tok_s_128_steps"],
         "secondary_value": summary["secondary_value"],
         "secondary_ms_per_step": summary["secondary_ms_per_step"],
         "secondary_step_frac": summary["secondary_step_frac"],
-        "data": "synthetic via kuiperllama_amd.binfmt.synth_image (seeded torch RNG on the GPU, the "
-                "reference exporter's .bin byte layout and init std; not the reference exporter itself)",
+        "data": DATA,
         "config": config,
         "roofline": _flat_first(roofline),
     }
@@ -784,9 +834,9 @@ def main(argv=None):
     ap.add_argument("--prefill-secondary", action=argparse.BooleanOptionalAction, default=True,
                     help="also time the prompt phase of the secondary workload")
     ap.add_argument("--extras", action=argparse.BooleanOptionalAction, default=True,
-                    help="--no-extras: only the contract's timed region and the roofline kernel (no repeated "
-                         "runs, 128-step reference run, latency probes, prefill, long context, CPU baseline, "
-                         "other configs) - for smoke runs with a small --steps")
+                    help="--full --no-extras: only the contract's timed region and the roofline kernel (no "
+                         "repeated runs, 128-step reference run, latency probes, prefill, long context, CPU "
+                         "baseline, other configs)")
     ap.add_argument("--others", default=None,
                     help=f"comma-separated further BASELINE configs measured briefly into the same line "
                          f"(default on one GPU: {DEFAULT_OTHERS}; '' or --no-others: none)")
@@ -797,6 +847,12 @@ def main(argv=None):
     ap.add_argument("--no-others", action="store_true",
                     help="skip the other BASELINE configs (rocprofv3 runs: they launch the same kernel "
                          "instantiations at other sizes and would blur the --stats average)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the timed region: secondary workload, roofline kernel timings, CPU "
+                         "baselines, other configs, latency / prefill / long-context / load probes (the options "
+                         "above shape these sections; a plain run is set-up, warm-up, timed steps and the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the words and last-step logits of the timed run as DIR/<name>.npy")
     args = ap.parse_args(argv)
 
     if not torch.cuda.is_available():
@@ -812,6 +868,15 @@ def main(argv=None):
         log(f"[bench] note: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE")
     if args.workload is None:
         args.workload = replicas.default_workload(world)
+    spec = binfmt.PRESETS[args.workload]
+    if not args.full:
+        res = measure(spec, args, rank, world, local_rank, primary=True)
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, res["outputs"])
+            print(json.dumps(plain_line(spec, args, world, res, replicas.backend_in_use(world))), flush=True)
+        replicas.shutdown(world)
+        return
     if args.secondary is None:
         args.secondary = "llama2-7b-int8" if world == 1 else ""
     if args.others is None:
@@ -819,9 +884,10 @@ def main(argv=None):
     if args.no_others or not args.extras:
         args.others = ""
 
-    spec = binfmt.PRESETS[args.workload]
     skipped = []
     res = measure(spec, args, rank, world, local_rank, primary=True)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["outputs"])
     secondary = None
     if args.secondary and args.secondary != args.workload:
         try:

@@ -9,6 +9,7 @@ import os
 import socket
 import sys
 
+import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
@@ -47,23 +48,31 @@ class _StubModel:
         self.calls.append(("generate", steps))
         return (words * (steps // n + 1))[:steps], (self._time.perf_counter() - t0) * 1e3
 
+    def logits(self):
+        self.calls.append(("logits",))
+        return np.linspace(-1.0, 1.0, self.spec.vocab_size, dtype=np.float32)
+
     def time_step(self, pos, reps=9):
+        self.calls.append(("time_step", pos))
         return [100.0 + self.rank] * reps
 
     def time_prefill(self, tokens, pos0=0, mode="gemm"):
+        self.calls.append(("time_prefill", mode))
         return 1.0
 
     def profile_kernels(self, pos, reps=8):
+        self.calls.append(("profile_kernels", pos))
         return {"qkv": 6.0, "attn": 4.0, "wo": 5.0, "ffn13": 20.0, "w2": 12.0, "cls": 100.0, "sample": 3.0}
 
     def profile_step(self, start_pos, n_steps):
+        self.calls.append(("profile_step", start_pos))
         return {k: {"avg_us": v, "launches_per_step": 1} for k, v in self.profile_kernels(0).items()}
 
     def close(self):
         pass
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, argv):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
@@ -72,11 +81,12 @@ def _worker(rank, world, port, q):
     import io
     import torch
     import bench
-    seen = {}
+    seen = {"models": []}
 
     def fake_build_model(spec, device_index, seed=1234, max_seq_len=0):
         seen["workload"] = spec.name
-        return _StubModel(rank), torch.zeros(8, dtype=torch.uint8)
+        seen["models"].append(_StubModel(rank))
+        return seen["models"][-1], torch.zeros(8, dtype=torch.uint8)
 
     bench.build_model = fake_build_model
     torch.cuda.is_available = lambda: True          # main() refuses to run without a GPU
@@ -85,8 +95,8 @@ def _worker(rank, world, port, q):
     torch.cuda.empty_cache = lambda *a, **k: None
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "12", "--warmup", "2"])
-    q.put((rank, buf.getvalue(), seen.get("workload")))
+        bench.main(argv)
+    q.put((rank, buf.getvalue(), seen.get("workload"), [m.calls for m in seen["models"]]))
 
 
 @pytest.mark.timeout(180)
@@ -95,14 +105,15 @@ def test_bench_main_world2_gloo():
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    argv = ["--gpus", str(world), "--steps", "12", "--warmup", "2", "--full"]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, argv)) for r in range(world)]
     for p in procs:
         p.start()
     res = sorted(q.get(timeout=150) for _ in range(world))
     for p in procs:
         p.join(timeout=30)
         assert p.exitcode == 0
-    (_, out0, wl0), (_, out1, wl1) = res
+    (_, out0, wl0, _), (_, out1, wl1, _) = res
     assert wl0 == wl1 == "llama2-7b"                 # default workload for N > 1 = config 5
     assert out1.strip() == ""                        # only rank 0 prints
     lines = [ln for ln in out0.splitlines() if ln.strip()]
@@ -135,6 +146,41 @@ def test_bench_main_world2_gloo():
     spec.loader.exec_module(bm)
     assert rf["bytes_per_launch"] == bm.ffn13_bytes(binfmt.PRESETS["llama2-7b"])
     assert abs(rf["achieved"] - rf["bytes_per_launch"] / 20e-6 / 1e9) < 1e-6 * rf["achieved"]
+
+
+@pytest.mark.timeout(180)
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) sets up, warms up, times --steps steps and prints the line: no second workload, no
+    roofline kernel timings, no probes, no CPU baseline.  --dump-outputs writes what the last timed step handed its
+    caller (the words of the run and the last logits) as float64 / float32 .npy files."""
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    out_dir = str(tmp_path / "outputs")
+    argv = ["--gpus", "1", "--steps", "12", "--warmup", "3", "--dump-outputs", out_dir]
+    p = ctx.Process(target=_worker, args=(0, 1, port, q, argv))
+    p.start()
+    _, out, wl, calls = q.get(timeout=150)
+    p.join(timeout=30)
+    assert p.exitcode == 0
+    assert wl == "llama3.2-1b"
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1, out
+    j = json.loads(lines[0])
+    assert list(j)[:11] == ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                            "scaling", "vs_baseline", "dtype"]
+    assert j["metric"] == "decode tokens/sec" and j["unit"] == "tokens/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "f32" and j["steps"] == 12 and j["warmup"] == 3
+    assert abs(j["value"] - 12 / (j["ms_per_step"] * 12e-3)) < 1e-6 * j["value"]
+    for k in ("roofline", "secondary", "other_configs", "cpu_baseline", "prefill", "long_context", "load", "runs"):
+        assert k not in j, k
+    # one model, and on it only the warm-up, the timed run of --steps steps and the read-back of its logits
+    assert calls == [[("generate", 3), ("generate", 12), ("logits",)]]
+    words = np.load(os.path.join(out_dir, "words.npy"))
+    logits = np.load(os.path.join(out_dir, "logits.npy"))
+    assert words.dtype == np.float64 and words.shape == (12,) and words[:8].tolist() == j["words_head"]
+    assert logits.dtype == np.float32 and logits.ndim == 1 and logits[0] == -1.0 and logits[-1] == 1.0
+    assert sorted(os.listdir(out_dir)) == ["logits.npy", "words.npy"]
 
 
 def test_bench_flags_can_be_switched_off():

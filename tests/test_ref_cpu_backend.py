@@ -5,7 +5,9 @@ stand-in (tests/cpp/ref_stubs/armadillo over numpy's OpenBLAS).  Built in the bu
 `ref_cpu`), the binaries travel to the GPU box.
 
 CPU tests: the oracle (oracle/kuiper_oracle.c, the restatement every other parity test leans on) against that backend
-on the committed goldens - words and LOGITS.  GPU tests: the HIP path against it, mid-size and at full size."""
+on the committed goldens - words and LOGITS; what the backend computed there is stored in tests/golden/ref_cpu_backend.npz
+(tests/golden/make_ref_cpu_golden.py), so these need no build of it, and run it live as well where it is built.  GPU
+tests: the HIP path against it, mid-size and at full size."""
 import os
 import subprocess
 import tempfile
@@ -17,6 +19,18 @@ from conftest import GOLDEN, load_golden
 from kuiperllama_amd import binfmt, build
 
 TOK = os.path.join(GOLDEN, "spm_llama_like.model")
+REF_CPU_GOLDEN = os.path.join(GOLDEN, "ref_cpu_backend.npz")
+GOLDEN_NAMES = ["ref_llama_gqa_tied", "ref_llama_mha_untied", "hf_llama_half", "hf_qwen2_half"]
+GREEDY_PROMPT = [1, 7, 3]
+
+
+def greedy_steps(spec):
+    return min(24, spec.seq_len)
+
+
+def _built(spec):
+    flavor = build.ref_cpu_flavor(spec)
+    return bool(flavor) and os.path.exists(build.REF_CPU_BINS[flavor])
 
 
 def _exe(spec):
@@ -45,22 +59,30 @@ def run_ref_cpu(spec, img, steps, prompt, want_logits=False, threads=8, budget_s
     return words, lg, float(lines[2].split(" = ")[1].split(" tokens/s")[0])
 
 
-@pytest.mark.parametrize("name", ["ref_llama_gqa_tied", "ref_llama_mha_untied", "hf_llama_half", "hf_qwen2_half"])
+@pytest.mark.parametrize("name", GOLDEN_NAMES)
 def test_oracle_equals_reference_cpu_backend_on_goldens(oracle, name):
     """Pins the oracle against the reference's own C++ CPU code (not only its Python model): teacher-forced over the
     golden's tokens, the logits of LLama2Model / Qwen2Model::forward on kDeviceCPU agree with the oracle's to 1e-6
-    and with the reference-Python golden logits to 2e-6; a greedy run gives the same words."""
+    and with the reference-Python golden logits to 2e-6; a greedy run gives the same words.  Held against the stored
+    outputs of that backend always, and against a live run of it where it is built."""
     spec, img, toks, golden = load_golden(name)
     toks = [int(t) for t in toks]
-    words, lg, _ = run_ref_cpu(spec, img, len(toks), toks, want_logits=True, threads=2)
-    om = oracle.OracleModel.from_spec(img, spec)
-    for t, tok in enumerate(toks):
-        lo = om.forward(tok, t)
-        assert np.abs(lo - lg[t]).max() <= 1e-6, (name, t, float(np.abs(lo - lg[t]).max()))
-        assert np.abs(golden[t] - lg[t]).max() <= 2e-6, (name, t)
-    steps, prompt = min(24, spec.seq_len), [1, 7, 3]
-    w2, _, _ = run_ref_cpu(spec, img, steps, prompt, threads=2)
-    assert w2 == oracle.OracleModel.from_spec(img, spec).generate(prompt, steps)
+    steps = greedy_steps(spec)
+    z = np.load(REF_CPU_GOLDEN)
+    runs = [("stored", z[name + "__logits"], [int(w) for w in z[name + "__words"]])]
+    if _built(spec):
+        _, lg, _ = run_ref_cpu(spec, img, len(toks), toks, want_logits=True, threads=2)
+        w2, _, _ = run_ref_cpu(spec, img, steps, GREEDY_PROMPT, threads=2)
+        runs.append(("live", lg, w2))
+    want = oracle.OracleModel.from_spec(img, spec).generate(GREEDY_PROMPT, steps)
+    for how, lg, w2 in runs:
+        assert lg.shape == (len(toks), spec.vocab_size), (how, lg.shape)
+        om = oracle.OracleModel.from_spec(img, spec)
+        for t, tok in enumerate(toks):
+            lo = om.forward(tok, t)
+            assert np.abs(lo - lg[t]).max() <= 1e-6, (name, how, t, float(np.abs(lo - lg[t]).max()))
+            assert np.abs(golden[t] - lg[t]).max() <= 2e-6, (name, how, t)
+        assert w2 == want, (name, how)
 
 
 _MID = {

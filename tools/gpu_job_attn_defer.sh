@@ -11,6 +11,6 @@ tail -5 $O/r4_pytest_gpu_a.txt
   for tl in 8192 16384 32768; do KH_ATTN_TLONG=$tl timeout 300 python tools/attn_defer_ab.py llama3.2-1b; done
 } 2>&1 | grep -v amdgpu.ids > $O/r4_attn_defer_ab.txt
 tail -30 $O/r4_attn_defer_ab.txt
-timeout 900 python bench.py > $O/r4_bench_a.json 2> $O/r4_bench_a.err
+timeout 900 python bench.py --full > $O/r4_bench_a.json 2> $O/r4_bench_a.err
 echo "bench rc=$?" >> $O/r4_bench_a.err
 tail -3 $O/r4_bench_a.err; head -c 600 $O/r4_bench_a.json

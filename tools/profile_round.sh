@@ -9,7 +9,7 @@
 # (rounds 4 and 5: `git show 87acefa:tools/profile_round5.sh`)
 ROUND=${ROUND:-r6}
 R=$PWD; O=$R/gpurun_out; mkdir -p $O; export TMPDIR=/tmp; cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/pf_stats -o bench -- python $R/bench.py --steps 128 --warmup 16 --no-cpu-baseline --no-others > $O/${ROUND}_bench_under_rocprof.json 2> $O/${ROUND}_pf_stats.log || echo "stats pass exit $?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/pf_stats -o bench -- python $R/bench.py --full --steps 128 --warmup 16 --no-cpu-baseline --no-others > $O/${ROUND}_bench_under_rocprof.json 2> $O/${ROUND}_pf_stats.log || echo "stats pass exit $?"
 for w in llama3.2-1b llama2-7b-int8; do for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c --kernel-trace -d $O/pf_${c}_$w -o bench -- python $R/tools/pmc_workload.py $w --steps 8 > $O/pf_${c}_$w.log 2>&1 || echo "$c $w exit $?"
 done; done
