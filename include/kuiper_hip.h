@@ -342,13 +342,18 @@ int kh_plan_prefill_shape(int32_t epi, int32_t T, int32_t rows, int32_t K, int32
 /* Tuning / test hooks.  Every hook the library honours (KH_SHAPE_<QKV|WO|FFN|W2|CLS>, KH_RING, KH_ATTN_WG, KH_ATTN_FENCED,
  * KH_ATTN_TLONG, KH_ATTN_DEFER (0 = never merge time splits in the wo kernel), KH_ATTN_DEFER_MAX (active splits up to
  * which it does), KH_PREFILL, KH_PG_<CHUNK|SHAPE_*|SOLO|KZ|ATTN|ATTN_QT|ROPE_FUSE|DEBUG>,
- * KH_SHAPE_DEBUG) lives in ONE process-wide key -> value table, seeded once from the KH_* variables of
+ * KH_SHAPE_DEBUG, KH_LAUNCH_LOG) lives in ONE process-wide key -> value table, seeded once from the KH_* variables of
  * the environment when the library is first used and changed afterwards only through kh_debug_set
  * (value NULL = unset).  No launch path reads the environment.  Hooks that shape a model (KH_SHAPE_*,
  * KH_ATTN_*) are read by kh_model_create_*; the others by the call they affect.  Keys must start with "KH_". */
 int kh_debug_set(const char* key, const char* value);
 const char* kh_debug_get(const char* key); /* NULL when unset */
 int64_t kh_debug_list(char* buf, int64_t cap); /* '\n'-separated names; returns bytes needed */
+/* Launch log.  While hook KH_LAUNCH_LOG is set (to anything but "0"), every fused decode-step and B-token prefill
+ * launch adds the name of the kernel instantiation it launches ("k_gemv_res<true,3,6,2>") to a process-wide set;
+ * setting, resetting or unsetting the hook (kh_debug_set) empties it.  kh_debug_launch_log: the names,
+ * '\n'-separated and sorted, into buf (always NUL-terminated); returns the bytes needed. */
+int64_t kh_debug_launch_log(char* buf, int64_t cap);
 
 /* Duration (ms, HIP events on the model stream) of the prompt phase alone for n fed-only tokens:
  * KH_PREFILL_TOKEN = the reference's prompt phase, one forward pass per token (demo/main.cpp:20-22)

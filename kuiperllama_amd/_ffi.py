@@ -28,7 +28,7 @@ EXPORTS = [
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
     "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention",
-    "kh_debug_set", "kh_debug_get", "kh_debug_list",
+    "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
 ]
 
 KH_EXEC_GRAPH, KH_EXEC_FUSED, KH_EXEC_UNFUSED = 0, 1, 2
@@ -171,6 +171,8 @@ def lib() -> C.CDLL:
     L.kh_debug_get.restype = C.c_char_p
     L.kh_debug_list.argtypes = [C.c_char_p, _i64]
     L.kh_debug_list.restype = _i64
+    L.kh_debug_launch_log.argtypes = [C.c_char_p, _i64]
+    L.kh_debug_launch_log.restype = _i64
     for name in EXPORTS:  # fail at load time, not at first call, if a symbol is missing
         getattr(L, name)
     _lib = L
@@ -187,6 +189,16 @@ def debug_set(key: str, value: Optional[str]) -> None:
 def debug_get(key: str) -> Optional[str]:
     v = lib().kh_debug_get(key.encode())
     return None if v is None else v.decode()
+
+
+def launch_log() -> set:
+    """Kernel instantiations launched since the hook KH_LAUNCH_LOG was last set (kh_debug_launch_log), e.g.
+    {"k_qkv<false,8,4,2>", "k_pf_ffn13<true,4>"}.  debug_set("KH_LAUNCH_LOG", "1") starts an empty log, None ends it."""
+    L = lib()
+    n = L.kh_debug_launch_log(None, 0)
+    buf = C.create_string_buffer(int(n) + 1)
+    L.kh_debug_launch_log(buf, int(n) + 1)
+    return {k for k in buf.value.decode().split("\n") if k}
 
 
 _HOOK_PREFIXES = ("KH_SHAPE_", "KH_ATTN_", "KH_PG_", "KH_PREFILL", "KH_RING", "KH_SELFTEST", "KH_KV_")

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/kuiper_hip.h"
 
 #define KH_WAVE 64
@@ -41,6 +43,14 @@ const char* dbg(const char* key);
 inline bool dbg_off(const char* key) {  // hook present and starting with '0'
   const char* e = dbg(key);
   return e && e[0] == '0';
+}
+// Hook KH_LAUNCH_LOG (any value but "0"): every fused-step and prefill launch site adds the name of the kernel
+// instantiation it launches ("k_gemv_res<true,3,6,2>") to a process-wide set, read by kh_debug_launch_log.  Off, a
+// launch reads one flag (kept by kh_debug_set and the table seeding): no lock, no table lookup.
+extern std::atomic<bool> g_launch_log_on;
+void launch_log_add(const char* name);
+inline void launch_log(const char* name) {
+  if (g_launch_log_on.load(std::memory_order_relaxed)) launch_log_add(name);
 }
 }  // namespace khm
 

@@ -9,6 +9,7 @@
 // kuiperllama_amd/_ffi.py::sync_env, so `monkeypatch.setenv` in the test-suite still works.)
 #include <string.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <set>
@@ -17,6 +18,10 @@
 #include "../../include/kuiper_hip.h"
 
 extern char** environ;
+
+namespace khm {
+extern std::atomic<bool> g_launch_log_on;
+}
 
 namespace {
 std::mutex g_mu;
@@ -27,6 +32,9 @@ const std::string* intern(const std::string& v) {
   static std::set<std::string> pool;
   return &*pool.insert(v).first;
 }
+const char kLaunchLog[] = "KH_LAUNCH_LOG";
+std::set<std::string> g_launched;  // kernel instantiations launched while KH_LAUNCH_LOG was on (guarded by g_mu)
+bool log_value_on(const std::string* v) { return v && !(v->size() && (*v)[0] == '0'); }
 std::map<std::string, const std::string*>& table() {
   static std::map<std::string, const std::string*> t = [] {
     std::map<std::string, const std::string*> m;
@@ -36,6 +44,8 @@ std::map<std::string, const std::string*>& table() {
       if (!eq) continue;
       m.emplace(std::string(*e, (size_t)(eq - *e)), intern(std::string(eq + 1)));
     }
+    auto it = m.find(kLaunchLog);
+    khm::g_launch_log_on.store(it != m.end() && log_value_on(it->second));
     return m;
   }();
   return t;
@@ -43,6 +53,11 @@ std::map<std::string, const std::string*>& table() {
 }  // namespace
 
 namespace khm {
+std::atomic<bool> g_launch_log_on{false};
+void launch_log_add(const char* name) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  g_launched.insert(name);
+}
 // Value of a hook, or nullptr when it is not set.  The pointer stays valid for the life of the process (interned).
 const char* dbg(const char* key) {
   if (!key) return nullptr;
@@ -61,10 +76,25 @@ extern "C" int kh_debug_set(const char* key, const char* value) {
     t[key] = intern(value);
   else
     t.erase(key);
+  if (strcmp(key, kLaunchLog) == 0) {  // setting, resetting or unsetting the hook starts an empty log
+    g_launched.clear();
+    khm::g_launch_log_on.store(log_value_on(value ? t[key] : nullptr));
+  }
   return KH_OK;
 }
 
 extern "C" const char* kh_debug_get(const char* key) { return khm::dbg(key); }
+
+namespace {
+int64_t copy_out(const std::string& all, char* buf, int64_t cap) {
+  if (buf && cap > 0) {
+    const size_t n = all.size() < (size_t)cap - 1 ? all.size() : (size_t)cap - 1;
+    memcpy(buf, all.data(), n);
+    buf[n] = 0;
+  }
+  return (int64_t)all.size() + 1;
+}
+}  // namespace
 
 // Names currently set, '\n'-separated, into buf (always NUL-terminated); returns the number of bytes needed.
 extern "C" int64_t kh_debug_list(char* buf, int64_t cap) {
@@ -74,10 +104,17 @@ extern "C" int64_t kh_debug_list(char* buf, int64_t cap) {
     all += kv.first;
     all += '\n';
   }
-  if (buf && cap > 0) {
-    const size_t n = all.size() < (size_t)cap - 1 ? all.size() : (size_t)cap - 1;
-    memcpy(buf, all.data(), n);
-    buf[n] = 0;
+  return copy_out(all, buf, cap);
+}
+
+// Kernel instantiations launched since KH_LAUNCH_LOG was last set, '\n'-separated and sorted, into buf (always
+// NUL-terminated); returns the number of bytes needed.
+extern "C" int64_t kh_debug_launch_log(char* buf, int64_t cap) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  std::string all;
+  for (const auto& k : g_launched) {
+    all += k;
+    all += '\n';
   }
-  return (int64_t)all.size() + 1;
+  return copy_out(all, buf, cap);
 }

@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
+#include <string>
 #include <vector>
 
 #include "kh_gemm.h"
@@ -105,15 +107,27 @@ void pf_launch(K kernel, int grid, int wg, size_t lds, hipStream_t s, const A& a
   if (grid > resident) grid = resident;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(wg), lds, s, args);
 }
+// the launch log's name of a B-token kernel instantiation (hook KH_LAUNCH_LOG), e.g. "k_pf_gemv_res<true,4,2>"
+void pf_log(const char* stem, bool q, std::initializer_list<int> targs) {
+  if (!g_launch_log_on.load(std::memory_order_relaxed)) return;
+  std::string n = std::string(stem) + (q ? "<true" : "<false");
+  for (int t : targs) n += "," + std::to_string(t);
+  launch_log_add((n + ">").c_str());
+}
+template <bool Q, int SP, int B>
+void pf_launch_gemv_res_sp(kh_model* m, const kh_model::Shape& sh, const KhPfGemvResArgs& a, size_t lds) {
+  pf_log("k_pf_gemv_res", Q, {SP, B});
+  pf_launch(k_pf_gemv_res<Q, SP, B>, sh.grid, sh.wg, lds, m->stream, a);
+}
 template <bool Q, int B>
 void pf_launch_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhPfGemvResArgs& a) {
   const size_t lds = pf_lds_bytes(Q, a.M, B);
   if (sh.split == 4)
-    pf_launch(k_pf_gemv_res<Q, 4, B>, sh.grid, sh.wg, lds, m->stream, a);
+    pf_launch_gemv_res_sp<Q, 4, B>(m, sh, a, lds);
   else if (sh.split == 2)
-    pf_launch(k_pf_gemv_res<Q, 2, B>, sh.grid, sh.wg, lds, m->stream, a);
+    pf_launch_gemv_res_sp<Q, 2, B>(m, sh, a, lds);
   else
-    pf_launch(k_pf_gemv_res<Q, 1, B>, sh.grid, sh.wg, lds, m->stream, a);
+    pf_launch_gemv_res_sp<Q, 1, B>(m, sh, a, lds);
 }
 // y = W.v ; X += y for the nvalid tokens of the chunk, in sub-batches of the largest of 8/4/2
 // tokens (<= bmax) whose input vectors fit LDS
@@ -140,16 +154,21 @@ void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const f
     }
   }
 }
+template <bool Q, int SP, int B>
+void pf_launch_qkv_sp(kh_model* m, const KhPfQkvArgs& a) {
+  pf_log("k_pf_qkv", Q, {SP, B});
+  pf_launch(k_pf_qkv<Q, SP, B>, m->sh_qkv.grid, m->sh_qkv.wg, pf_lds_bytes(Q, a.dim, B), m->stream, a);
+}
 template <bool Q, int B>
 void pf_launch_qkv(kh_model* m, const KhPfQkvArgs& a) {
-  const size_t lds = pf_lds_bytes(Q, a.dim, B);
   if (m->sh_qkv.split == 2)
-    pf_launch(k_pf_qkv<Q, 2, B>, m->sh_qkv.grid, m->sh_qkv.wg, lds, m->stream, a);
+    pf_launch_qkv_sp<Q, 2, B>(m, a);
   else
-    pf_launch(k_pf_qkv<Q, 1, B>, m->sh_qkv.grid, m->sh_qkv.wg, lds, m->stream, a);
+    pf_launch_qkv_sp<Q, 1, B>(m, a);
 }
 template <bool Q, int B>
 void pf_launch_ffn13(kh_model* m, const KhPfFfn13Args& a) {
+  pf_log("k_pf_ffn13", Q, {B});
   pf_launch(k_pf_ffn13<Q, B>, m->sh_ffn.grid, m->sh_ffn.wg, pf_lds_bytes(Q, a.dim, B), m->stream, a);
 }
 // forward of nvalid (<= B) prompt tokens at positions pos0.. : fills their K/V cache rows

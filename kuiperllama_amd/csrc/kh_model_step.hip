@@ -38,6 +38,10 @@ kh_model::Shape pick_shape(bool quant, int pairs, int M, int max_split, const ch
       sh.wg = w;
       return sh;
     }
+    // not a launch this kernel has (e.g. split 4 for qkv, u 8 for int8, wg 512 where the kernel stays at 256):
+    // say so rather than let a test believe it forced a shape
+    fprintf(stderr, "[kh] %s=\"%s\" rejected (split <= %d, u 2/4%s%s, grid 1..4096, wg 256%s): heuristic shape\n",
+            env, ov, max_split, quant ? "" : "/8", quant && u3 ? "/3" : "", wg_max >= 512 ? "/512" : "");
   }
   const int elem = quant ? 1 : 4;
   const int min_bytes = quant ? 4096 : 8192;  // bytes one wave must still stream per pair
@@ -106,11 +110,24 @@ kh_model::Shape pick_shape(bool quant, int pairs, int M, int max_split, const ch
 // ---- fused launches -------------------------------------------------------------------------
 // Template dispatch.  U: 16-byte loads per row in flight per lane; MV: in-register staging depth
 // (kh_stage_maxv of the input length); SP: waves sharing one row pair.
-// The workgroup size comes from a variable `kh_launch_wg` in scope at the dispatch site.
-#define KH_L3(KERNEL, Q, UU, MV, GRID, LDS, STREAM, ARGS) \
-  hipLaunchKernelGGL((KERNEL<Q, UU, MV>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS)
-#define KH_L4(KERNEL, Q, UU, MV, SP, GRID, LDS, STREAM, ARGS) \
-  hipLaunchKernelGGL((KERNEL<Q, UU, MV, SP>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS)
+// The workgroup size comes from a variable `kh_launch_wg` in scope at the dispatch site.  Every launch macro names
+// its instantiation in the launch log (hook KH_LAUNCH_LOG, kh_common.h) from the literal template arguments it launches.
+#define KH_L3(KERNEL, Q, UU, MV, GRID, LDS, STREAM, ARGS)                                     \
+  do {                                                                                     \
+    launch_log(#KERNEL "<" #Q "," #UU "," #MV ">");                                        \
+    hipLaunchKernelGGL((KERNEL<Q, UU, MV>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS); \
+  } while (0)
+#define KH_L4(KERNEL, Q, UU, MV, SP, GRID, LDS, STREAM, ARGS)                                     \
+  do {                                                                                         \
+    launch_log(#KERNEL "<" #Q "," #UU "," #MV "," #SP ">");                                    \
+    hipLaunchKernelGGL((KERNEL<Q, UU, MV, SP>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS); \
+  } while (0)
+// the int8 LDS-DMA ring kernels (kh_fused_ring.h): R ring slots per wave, MAXV float4 staged per thread, plain layout
+#define KH_LRING(KERNEL, R, MV, GRID, LDS, STREAM, ARGS)                                   \
+  do {                                                                                  \
+    launch_log(#KERNEL "<" #R "," #MV ",false>");                                       \
+    hipLaunchKernelGGL((KERNEL<R, MV, false>), dim3(GRID), dim3(KH_WG), LDS, STREAM, ARGS); \
+  } while (0)
 #define KH_SEL_MV3(KERNEL, Q, UU, MV, ...)                  \
   do {                                                      \
     if ((MV) == 4)                                          \
@@ -131,17 +148,27 @@ kh_model::Shape pick_shape(bool quant, int pairs, int M, int max_split, const ch
     else                                                    \
       KH_L4(KERNEL, Q, UU, MV, 1, __VA_ARGS__);             \
   } while (0)
-#define KH_SEL_MV4(KERNEL, Q, UU, MV, SP, ...)              \
+// k_qkv: its shape is split at most twice (plan_decode_shapes: max_split 2), so SPLIT = 4 is not compiled
+#define KH_SEL_SP2(KERNEL, Q, UU, MV, SP, ...)              \
+  do {                                                      \
+    if ((SP) == 2)                                          \
+      KH_L4(KERNEL, Q, UU, MV, 2, __VA_ARGS__);             \
+    else                                                    \
+      KH_L4(KERNEL, Q, UU, MV, 1, __VA_ARGS__);             \
+  } while (0)
+#define KH_SEL_MV4S(SELSP, KERNEL, Q, UU, MV, SP, ...)      \
   do {                                                      \
     if ((MV) == 4)                                          \
-      KH_SEL_SP4(KERNEL, Q, UU, 4, SP, __VA_ARGS__);        \
+      SELSP(KERNEL, Q, UU, 4, SP, __VA_ARGS__);             \
     else if ((MV) == 2)                                     \
-      KH_SEL_SP4(KERNEL, Q, UU, 2, SP, __VA_ARGS__);        \
+      SELSP(KERNEL, Q, UU, 2, SP, __VA_ARGS__);             \
     else if ((MV) == 1)                                     \
-      KH_SEL_SP4(KERNEL, Q, UU, 1, SP, __VA_ARGS__);        \
+      SELSP(KERNEL, Q, UU, 1, SP, __VA_ARGS__);             \
     else                                                    \
-      KH_SEL_SP4(KERNEL, Q, UU, 0, SP, __VA_ARGS__);        \
+      SELSP(KERNEL, Q, UU, 0, SP, __VA_ARGS__);             \
   } while (0)
+#define KH_SEL_MV4(KERNEL, Q, UU, MV, SP, ...) KH_SEL_MV4S(KH_SEL_SP4, KERNEL, Q, UU, MV, SP, __VA_ARGS__)
+#define KH_SEL_MV4Q(KERNEL, Q, UU, MV, SP, ...) KH_SEL_MV4S(KH_SEL_SP2, KERNEL, Q, UU, MV, SP, __VA_ARGS__)
 // k_gemv_res only: the 6-deep in-register staging for hidden-sized inputs (kh_stage_maxv)
 #define KH_SEL_MV4X(KERNEL, Q, UU, MV, SP, ...)             \
   do {                                                      \
@@ -173,6 +200,8 @@ kh_model::Shape pick_shape(bool quant, int pairs, int M, int max_split, const ch
   KH_SEL_U(KH_SEL_MV4, KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS)
 #define KH_DISPATCH4X(KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS) \
   KH_SEL_U(KH_SEL_MV4X, KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS)
+#define KH_DISPATCH4Q(KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS) \
+  KH_SEL_U(KH_SEL_MV4Q, KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS)
 
 KhQkvArgs fill_qkv(kh_model* m, int l) {
   const kh_config& c = m->cfg;
@@ -202,7 +231,7 @@ void launch_qkv(kh_model* m, int l) {
   const KhQkvArgs a = fill_qkv(m, l);
   const bool qn = c.is_quant;
   const int kh_launch_wg = m->sh_qkv.wg;
-  KH_DISPATCH4(k_qkv, qn, m->sh_qkv.u, kh_stage_maxv(c.dim, kh_launch_wg), m->sh_qkv.split, m->sh_qkv.grid,
+  KH_DISPATCH4Q(k_qkv, qn, m->sh_qkv.u, kh_stage_maxv(c.dim, kh_launch_wg), m->sh_qkv.split, m->sh_qkv.grid,
                fused_lds_bytes(qn, c.dim), m->stream, a);
 }
 KhAttnArgs fill_attn(kh_model* m, int l) {
@@ -258,8 +287,11 @@ KhGemvResArgs fill_wo(kh_model* m, int l) {
   return a;
 }
 // wo behind a deferring attention launch (step variant 1): in-register staging of 2 or 4 float4
-#define KH_L5C(Q, UU, MV, SP, GRID, LDS, STREAM, ARGS) \
-  hipLaunchKernelGGL((k_wo_comb<Q, UU, MV, SP>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS)
+#define KH_L5C(Q, UU, MV, SP, GRID, LDS, STREAM, ARGS)                                            \
+  do {                                                                                          \
+    launch_log("k_wo_comb<" #Q "," #UU "," #MV "," #SP ">");                                    \
+    hipLaunchKernelGGL((k_wo_comb<Q, UU, MV, SP>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS); \
+  } while (0)
 #define KH_SEL_SP5C(Q, UU, MV, SP, ...)                     \
   do {                                                      \
     if ((SP) == 4)                                          \
@@ -316,8 +348,7 @@ void launch_ffn13(kh_model* m, int l) {
   a.eps = c.rms_eps;
   const bool qn = c.is_quant;
   if (m->ring.ffn_r == 2) {  // plan_ring: int8, dim a multiple of 256 floats and at most 16 per thread
-    hipLaunchKernelGGL((k_ffn13_ring<2, 4>), dim3(m->ring.ffn_grid), dim3(KH_WG),
-                       ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
+    KH_LRING(k_ffn13_ring, 2, 4, m->ring.ffn_grid, ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
   const int kh_launch_wg = m->sh_ffn.wg;
@@ -359,8 +390,7 @@ void launch_cls(kh_model* m) {
   // the classifier is int8 only when the model is quantised (untied; llama3.cpp:255-268)
   const bool qn = c.is_quant;
   if (m->ring.cls_r == 2) {
-    hipLaunchKernelGGL((k_cls_ring<2, 4>), dim3(m->ring.cls_grid), dim3(KH_WG),
-                       ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
+    KH_LRING(k_cls_ring, 2, 4, m->ring.cls_grid, ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
   const int kh_launch_wg = m->sh_cls.wg;

@@ -121,3 +121,35 @@ def test_debug_hooks_live_in_one_table_not_in_getenv(lib, monkeypatch):
     csrc = os.path.join(ROOT, "kuiperllama_amd", "csrc")
     for f in os.listdir(csrc):
         assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+
+
+def test_launch_log_hook_and_qkv_split_limit(lib):
+    """KH_LAUNCH_LOG: kh_debug_launch_log reads the set of launched kernel instantiations like kh_debug_list (bytes
+    needed, NUL-terminated, truncated to the buffer); setting, resetting and unsetting the hook leave it empty (no
+    launch here: no device).  Every decode-GEMV and B-token prefill launch in the step / prefill sources goes through
+    a site that logs it.  The qkv shape hook refuses split 4 (qkv's SPLIT = 4 kernels are not compiled)."""
+    import re
+    assert lib.kh_debug_launch_log(None, 0) == 1
+    _ffi.debug_set("KH_LAUNCH_LOG", "1")
+    assert _ffi.launch_log() == set()
+    buf = C.create_string_buffer(4)
+    buf.value = b"abc"
+    assert lib.kh_debug_launch_log(buf, 4) == 1 and buf.value == b""
+    _ffi.debug_set("KH_LAUNCH_LOG", "1")  # reset: a new, empty log
+    assert _ffi.launch_log() == set()
+    _ffi.debug_set("KH_LAUNCH_LOG", None)
+    assert _ffi.launch_log() == set() and _ffi.debug_get("KH_LAUNCH_LOG") is None
+    csrc = os.path.join(ROOT, "kuiperllama_amd", "csrc")
+    for f in ("kh_model_step.hip", "kh_model_prefill.hip"):
+        lines = open(os.path.join(csrc, f)).read().splitlines()
+        for i, ln in enumerate(lines):
+            if re.search(r"(hipLaunchKernelGGL\(\(|pf_launch\()(KERNEL|k_qkv|k_gemv_res|k_wo_comb|k_ffn13|k_cls|k_pf_)",
+                         ln):
+                near = "\n".join(lines[max(0, i - 2):i + 1])
+                assert "launch_log(" in near or "pf_log(" in near, f"{f}:{i + 1}: launch without a launch-log entry"
+    base = _ffi.plan_decode_shapes(2048, 8192, 512, 128256, False)["qkv"]
+    _ffi.debug_set("KH_SHAPE_QKV", "2,4,64,512")
+    assert _ffi.plan_decode_shapes(2048, 8192, 512, 128256, False)["qkv"] == {"split": 2, "u": 4, "grid": 64, "wg": 512}
+    _ffi.debug_set("KH_SHAPE_QKV", "4,4,64,512")
+    assert _ffi.plan_decode_shapes(2048, 8192, 512, 128256, False)["qkv"] == base
+    _ffi.debug_set("KH_SHAPE_QKV", None)

@@ -3,63 +3,36 @@ latency-bound decode kernel is a memory round trip per use), and the kernels the
 Reads the .hip_fatbin section of kuiperllama_amd/lib/libkuiper_hip.so with the LLVM tools of the ROCm install (no GPU).
 Round 6 found 20-24 bytes of scratch in six k_wo_comb instantiations after a branch had been removed from their
 merge loop (the compiler hoisted every factor read and crossed the 128-register cap): this test is the tripwire."""
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import pytest
 
+import code_objects as co
 from kuiperllama_amd import build
-
-LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
 def _code_object_notes():
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not all(os.path.exists(t) for t in tools):
+    if not co.tools_present():
         pytest.skip("LLVM tools of the ROCm install not found")
-    lib = build.build_lib()
-    td = tempfile.mkdtemp(prefix="kh_co_")
-    try:
-        fat = os.path.join(td, "fat.bin")
-        subprocess.check_call([tools[0], "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-        assert starts, "no offload bundle in .hip_fatbin"
-        notes = []
-        for i, s in enumerate(starts):
-            chunk = os.path.join(td, f"bundle{i}.bin")
-            with open(chunk, "wb") as f:
-                f.write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-            co = os.path.join(td, f"co{i}.elf")
-            subprocess.check_call([tools[1], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                                   f"--input={chunk}", f"--output={co}"], stderr=subprocess.DEVNULL)
-            if os.path.getsize(co) == 0:
-                continue  # a translation unit without device code
-            notes.append(subprocess.check_output([tools[2], "--notes", co], text=True))
-        return "\n".join(notes)
-    finally:
-        shutil.rmtree(td, ignore_errors=True)
+    return co.code_object_notes(build.build_lib())
 
 
 def test_no_kernel_uses_scratch_and_step_kernels_exist():
-    text = _code_object_notes()
-    kernels = {}
-    name = None
-    for line in text.splitlines():
-        m = re.search(r"\.name:\s+(\S+)", line)
-        if m and m.group(1).startswith("_Z"):
-            name = m.group(1)
-        m = re.search(r"\.private_segment_fixed_size:\s+(\d+)", line)
-        if m:
-            kernels.setdefault(name or f"?{len(kernels)}", int(m.group(1)))
-            name = None
+    kernels = co.kernel_scratch(_code_object_notes())
     assert len(kernels) > 100, f"only {len(kernels)} kernel descriptors parsed"
     spilled = {k: v for k, v in kernels.items() if v}
     assert not spilled, f"kernels with scratch (bytes): {spilled}"
     for stem in ("k_qkv", "k_attn_decode", "k_gemv_res", "k_wo_comb", "k_ffn13", "k_ffn13_ring", "k_cls", "k_cls_ring",
                  "k_sample", "k_pg_gemm", "k_pg_attn"):
         assert any(stem in k for k in kernels), f"no {stem} instantiation in the library"
+
+
+def test_qkv_is_compiled_for_its_reachable_splits_only():
+    """k_qkv's shape is never split more than twice (plan_decode_shapes: max_split 2; the KH_SHAPE_QKV hook rejects 4),
+    so the library compiles SPLIT 1 and 2 only: 40 instantiations = fp32 U 8/4/2 and int8 U 4/2, times MAXV 4/2/1/0,
+    times SPLIT 1/2.  The mangled-name reader of code_objects.py must also read the arguments back."""
+    assert co.template_name("_Z5k_qkvILb0ELi2ELi0ELi1EEv9KhQkvArgs") == "k_qkv<false,2,0,1>"
+    assert co.template_name("_Z12k_ffn13_ringILi2ELi4ELb0E9StagerAsmILb1ELi4ELi0EEEv11KhFfn13Args") == \
+        "k_ffn13_ring<2,4,false>"
+    qkv = co.instantiations(_code_object_notes(), {"k_qkv"})
+    want = {f"k_qkv<{q},{u},{mv},{sp}>" for q, us in (("false", (8, 4, 2)), ("true", (4, 2))) for u in us
+            for mv in (4, 2, 1, 0) for sp in (1, 2)}
+    assert qkv == want, (sorted(qkv - want), sorted(want - qkv))
