@@ -145,6 +145,36 @@ int kh_mha_decode_f32(const int32_t* d_pos, int32_t pos, int32_t head_num, int32
 int kh_argmax_f32(const float* logits, int64_t n, int32_t* d_out_index, void* stream);
 int kh_argmax_f32_host(const float* logits, int64_t n, int64_t* h_out_index, void* stream);
 
+/* Seeded sampling (the reference's sampler::Sampler interface, kuiper/include/sampler/sampler.h, has only the
+ * argmax; these are further samplers behind it).  With temperature T, top_k K, top_p P, seed and a 64-bit counter c:
+ *   1. T <= 0: greedy - exactly kh_argmax_f32 (ties -> lowest index), on the argmax kernels;
+ *   2. order the tokens by (logit descending, index ascending);
+ *   3. 0 < K < n: keep the first K of that order (K = 0 or K >= n: no top-k);
+ *   4. weights w_i = exp((l_i - l_max) / T) of the kept tokens;
+ *   5. P < 1: keep the shortest prefix of that order whose weight is >= P times the kept total (at least one
+ *      token; P = 1: no top-p) = the set S;
+ *   6. x = Philox4x32-10(counter = (c mod 2^32, 0, 0, 0), key = (seed & 0xffffffff, seed >> 32)) word 0,
+ *      u = ((x >> 8) + 0.5) * 2^-24;
+ *   7. the result is the smallest index j in S whose index-order prefix sum of w over S exceeds u * Z_S
+ *      (Z_S = the weight of S); the largest index of S if rounding leaves none.
+ * K = 1 is the argmax.  Logits must be finite or -inf.  KH_ERR_INVALID_ARG, before any device call, for a
+ * non-finite T, K < 0, or P NaN or outside (0, 1].  One 1024-thread workgroup per draw: a histogram pass of
+ * (l_max - l) / T, the candidates compacted into LDS when at most 4096 of them can be in S, exact radix descents
+ * over them (csrc/kh_sample.h; DESIGN.md "Sampling" has the measured cost). */
+typedef struct kh_sampling {
+  float temperature; /* <= 0: greedy */
+  int32_t top_k;     /* 0: off */
+  float top_p;       /* 1: off */
+  uint64_t seed;
+} kh_sampling;
+/* n_draws draws on one logit vector with counters counter0 .. counter0 + n_draws - 1 -> d_out[n_draws] (DEVICE;
+ * graph-capturable, asynchronous) */
+int kh_sample_f32(const float* logits, int64_t n, const kh_sampling* p, int64_t counter0, int32_t n_draws,
+                  int32_t* d_out, void* stream);
+/* one draw with the index in HOST memory: the twin of kh_argmax_f32_host (synchronises the stream) */
+int kh_sample_f32_host(const float* logits, int64_t n, const kh_sampling* p, int64_t counter, int64_t* h_out,
+                       void* stream);
+
 /* CPU-only helpers of the reference (kernels_interface.h:38-46), provided on device so the
  * op set is closed: softmax in place, x *= scale, out += sum_t scale[t]*value[t*stride..] */
 int kh_softmax_f32(float* x, int32_t n, void* stream);
@@ -231,7 +261,7 @@ enum {
 };
 
 /* Model::predict (llama3.cpp:642-650): embedding of `token` -> forward at `pos` ->
- * argmax unless is_prompt.  *h_next receives the token (or -1 when is_prompt).
+ * argmax (or the kh_model_set_sampling draw) unless is_prompt.  *h_next receives the token (or -1 when is_prompt).
  * Synchronises the stream. exec: KH_EXEC_FUSED or KH_EXEC_UNFUSED. */
 int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t is_prompt, int32_t exec,
                      int32_t* h_next);
@@ -317,6 +347,17 @@ typedef struct kh_first_sample {
   float top1, top2;      /* the two largest logits of that step; ties -> lowest index first, like the sampler */
 } kh_first_sample;
 int kh_model_first_sample(kh_model* m, kh_first_sample* out);
+
+/* The model's sampler (NULL = greedy, the default of every model).  Applies to kh_model_predict (fused and unfused),
+ * kh_model_generate and kh_model_generate_until; the semantics are kh_sample_f32's with the counter = the position
+ * whose logits are sampled, so the tokens depend only on (seed, prompt, parameters, logits): not on the exec mode,
+ * on how steps are cut into graph chunks, or on whether generate or a loop of predict calls produced them.  Prompt
+ * positions are never sampled.  The parameters live in a small device buffer written on the model stream, so a new
+ * seed or temperature needs no graph recapture; greedy and sampled steps are captured as separate graphs, and the
+ * sampled step replaces only the last launch (k_sample -> k_sample_topp: launches_per_token is unchanged).
+ * KH_ERR_INVALID_ARG as kh_sample_f32.  kh_model_first_sample keeps reporting the two largest logits. */
+int kh_model_set_sampling(kh_model* m, const kh_sampling* p);
+int kh_model_get_sampling(const kh_model* m, kh_sampling* out);
 
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,

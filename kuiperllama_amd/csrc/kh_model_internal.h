@@ -48,6 +48,7 @@ struct LayerW {
 using khm::LayerW;
 
 #define KH_STEP_VARIANTS 3  // kh_model_step.hip::step_variant
+struct KhSampParams;       // kh_sample.h
 struct kh_model {
   kh_config cfg{};
   kh_model_opts opts{};
@@ -145,7 +146,14 @@ struct kh_model {
     hipGraph_t g = nullptr;
     hipGraphExec_t e = nullptr;
   };
-  StepGraph sg[KH_STEP_VARIANTS][4];  // [variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps
+  // [sampler][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps, with the greedy k_sample (0) or
+  // the sampling k_sample_topp (1) as the last launch of every step
+  StepGraph sg[2][KH_STEP_VARIANTS][4];
+  // kh_model_set_sampling: the parameters (host copy), whether they sample (temperature > 0), and their device copy,
+  // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
+  kh_sampling samp{0.f, 0, 1.f, 0};
+  bool samp_on = false;
+  KhSampParams* d_samp = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -174,6 +182,7 @@ void launch_wo(kh_model* m, int l);  // follows m->step_var like launch_attn
 void launch_ffn13(kh_model* m, int l);
 void launch_w2(kh_model* m, int l);
 void launch_cls(kh_model* m);
+// the step's last launch: k_sample (argmax), or k_sample_topp while m->samp_on
 void launch_sample(kh_model* m, int advance, int n_forced);
 // variant (see kh_model::sg): which attention / wo pair the launches of a step use
 int step_variant(const kh_model* m, int pos_lo, int pos_hi);

@@ -653,6 +653,7 @@ extern "C" void kh_model_destroy(kh_model* m) {
   if (m->h_words_pin) (void)hipHostFree(m->h_words_pin);
   if (m->h_forced_pin) (void)hipHostFree(m->h_forced_pin);
   if (m->first_logits) (void)hipFree(m->first_logits);
+  if (m->d_samp) (void)hipFree(m->d_samp);
   void* bufs[] = {m->x,      m->rms,    m->q,         m->att,       m->h1,       m->h3,
                   m->w2o,    m->logits, m->score,     m->sin_cache,
                   m->cos_cache, m->part_val, m->part_idx, m->d_pos, m->d_token,  m->d_next,

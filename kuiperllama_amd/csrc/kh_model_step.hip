@@ -12,6 +12,7 @@
 
 #include "kh_fused.h"
 #include "kh_fused_ring.h"
+#include "kh_sample.h"
 #include "kh_model_internal.h"
 
 namespace khm {
@@ -415,6 +416,28 @@ void launch_sample(kh_model* m, int advance, int n_forced) {
   a.dim = c.dim;
   a.vocab = c.vocab_size;
   a.advance = advance;
+  if (m->samp_on) {
+    KhSampleTopArgs t;
+    t.logits = m->logits;
+    t.part_val = m->part_val;
+    t.nparts = m->nparts;
+    t.params = m->d_samp;
+    t.forced = a.forced;
+    t.n_forced = a.n_forced;
+    t.words = a.words;
+    t.words_cap = a.words_cap;
+    t.d_next = a.d_next;
+    t.d_token = a.d_token;
+    t.d_pos = a.d_pos;
+    t.tok_emb = a.tok_emb;
+    t.x = a.x;
+    t.dim = a.dim;
+    t.vocab = a.vocab;
+    t.advance = advance;
+    launch_log("k_sample_topp");
+    hipLaunchKernelGGL(k_sample_topp, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
+    return;
+  }
   hipLaunchKernelGGL(k_sample, dim3(1), dim3(KH_WG), 0, m->stream, a);
 }
 
@@ -501,7 +524,11 @@ int launch_step_unfused(kh_model* m, int pos) {
   }
   KH_TRY(kh_rmsnorm_f32(m->x, m->final_norm, m->x, c.dim, c.rms_eps, s));
   KH_TRY(lin(m->cls, m->x, m->logits, c.dim, c.vocab_size));
-  KH_TRY(kh_argmax_f32(m->logits, c.vocab_size, m->d_next, s));
+  if (m->samp_on) {  // the counter is the position whose logits are sampled, as in the fused step
+    KH_TRY(kh_sample_f32(m->logits, c.vocab_size, &m->samp, pos, 1, m->d_next, s));
+  } else {
+    KH_TRY(kh_argmax_f32(m->logits, c.vocab_size, m->d_next, s));
+  }
 #undef KH_TRY
   return KH_OK;
 }
@@ -548,13 +575,14 @@ int ensure_seq_cap(kh_model* m, int n) {
   return KH_OK;
 }
 void destroy_step_graphs(kh_model* m) {
-  for (int v = 0; v < KH_STEP_VARIANTS; ++v)
-    for (int k = 0; k < 4; ++k) {
-      kh_model::StepGraph& sg = m->sg[v][k];
-      if (sg.e) (void)hipGraphExecDestroy(sg.e);
-      if (sg.g) (void)hipGraphDestroy(sg.g);
-      sg = kh_model::StepGraph{};
-    }
+  for (auto& per_sampler : m->sg)
+    for (int v = 0; v < KH_STEP_VARIANTS; ++v)
+      for (int k = 0; k < 4; ++k) {
+        kh_model::StepGraph& sg = per_sampler[v][k];
+        if (sg.e) (void)hipGraphExecDestroy(sg.e);
+        if (sg.g) (void)hipGraphDestroy(sg.g);
+        sg = kh_model::StepGraph{};
+      }
 }
 
 int capture_steps(kh_model* m, int n_forced, int steps, int variant, hipGraph_t* g, hipGraphExec_t* ge) {
@@ -569,7 +597,7 @@ int step_graph_n(kh_model* m, int n_forced, int variant, int nsteps, hipGraphExe
   if (variant < 0 || variant >= KH_STEP_VARIANTS) return KH_ERR_INVALID_ARG;
   const int k = nsteps == 1 ? 0 : nsteps == 2 ? 1 : nsteps == 4 ? 2 : nsteps == KH_GRAPH_STEPS ? 3 : -1;
   if (k < 0) return KH_ERR_INVALID_ARG;
-  kh_model::StepGraph& sg = m->sg[variant][k];
+  kh_model::StepGraph& sg = m->sg[m->samp_on ? 1 : 0][variant][k];  // captured with the sampler now in use
   if (!sg.e) {
     const int rc = capture_steps(m, n_forced, nsteps, variant, &sg.g, &sg.e);
     if (rc != KH_OK) return rc;
@@ -704,6 +732,30 @@ extern "C" int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t
   return KH_OK;
 }
 
+extern "C" int kh_model_set_sampling(kh_model* m, const kh_sampling* p) {
+  if (p && !kh_sampling_valid(p)) return KH_ERR_INVALID_ARG;
+  if (!m) return KH_ERR_INVALID_ARG;
+  const kh_sampling greedy{0.f, 0, 1.f, 0};
+  const kh_sampling want = p ? *p : greedy;
+  const bool on = !kh_sampling_greedy(&want);
+  if (on) {
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    if (!m->d_samp) KH_CHECK_HIP(hipMalloc((void**)&m->d_samp, sizeof(KhSampParams)));
+    // written on the model stream behind whatever is queued; the sync keeps the host copy alive for the upload
+    const KhSampParams dp = kh_samp_params(&want);
+    KH_CHECK_HIP(hipMemcpyAsync(m->d_samp, &dp, sizeof(dp), hipMemcpyHostToDevice, m->stream));
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  }
+  m->samp = want;
+  m->samp_on = on;
+  return KH_OK;
+}
+extern "C" int kh_model_get_sampling(const kh_model* m, kh_sampling* out) {
+  if (!m || !out) return KH_ERR_INVALID_ARG;
+  *out = m->samp;
+  return KH_OK;
+}
+
 extern "C" int kh_model_generate(kh_model* m, const int32_t* h_prompt, int32_t n_prompt,
                                  int32_t total_steps, int32_t exec, int32_t* h_words,
                                  int32_t* n_words, float* h_elapsed_ms) {
@@ -799,7 +851,7 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
     bool fresh[4] = {false, false, false, false};
     hipGraphExec_t ge = nullptr;
     for (int n = 1, k = 0; n <= KH_GRAPH_STEPS; n *= 2, ++k) {
-      fresh[k] = m->sg[0][k].e == nullptr;
+      fresh[k] = m->sg[m->samp_on ? 1 : 0][0][k].e == nullptr;
       if ((rc = step_graph_n(m, n_forced, 0, n, &ge)) != KH_OK) return rc;
     }
     bool dry = false;
@@ -807,7 +859,7 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
       for (int k = 3; k >= 0; --k)
         if (fresh[k]) {
           set_state(m, h_prompt[0], 0);
-          KH_CHECK_HIP(hipGraphLaunch(m->sg[0][k].e, m->stream));
+          KH_CHECK_HIP(hipGraphLaunch(m->sg[m->samp_on ? 1 : 0][0][k].e, m->stream));
           dry = true;
         }
     if (dry) KH_CHECK_HIP(hipStreamSynchronize(m->stream));

@@ -11,6 +11,7 @@
 
 #include "kh_common.h"
 #include "kh_gemv.h"
+#include "kh_sample.h"
 
 // =============================================================================================
 // add / swiglu / scale : elementwise, HBM/L2-bound, float4 body + scalar tail
@@ -733,6 +734,41 @@ extern "C" int kh_argmax_f32_host(const float* logits, int64_t n, int64_t* h_out
     rc = e == hipSuccess ? KH_OK : (int)e;
   }
   *h_out_index = h;
+  return rc;
+}
+
+// =============================================================================================
+// seeded temperature / top-k / top-p sampling (kh_sample.h).  Greedy parameters run the argmax kernel above.
+extern "C" int kh_sample_f32(const float* logits, int64_t n, const kh_sampling* p, int64_t counter0,
+                             int32_t n_draws, int32_t* d_out, void* stream) {
+  if (!logits || !d_out || n <= 0 || n > 0x7fffffffLL || n_draws <= 0 || !kh_sampling_valid(p))
+    return KH_ERR_INVALID_ARG;
+  if (kh_sampling_greedy(p)) {
+    const int rc = kh_argmax_f32(logits, n, d_out, stream);
+    if (rc != KH_OK || n_draws == 1) return rc;
+    const int grid = (n_draws + KH_WG - 1) / KH_WG < 64 ? (n_draws + KH_WG - 1) / KH_WG : 64;
+    hipLaunchKernelGGL(k_sample_bcast, dim3(grid), dim3(KH_WG), 0, (hipStream_t)stream, d_out, (int)n_draws);
+    return kh_launch_status();
+  }
+  hipLaunchKernelGGL(k_sample_op, dim3(n_draws), dim3(KH_SAMP_THREADS), 0, (hipStream_t)stream, logits, (int)n,
+                     kh_samp_params(p), (uint32_t)(uint64_t)counter0, d_out);
+  return kh_launch_status();
+}
+extern "C" int kh_sample_f32_host(const float* logits, int64_t n, const kh_sampling* p, int64_t counter,
+                                  int64_t* h_out, void* stream) {
+  if (!h_out || !logits || n <= 0 || n > 0x7fffffffLL || !kh_sampling_valid(p)) return KH_ERR_INVALID_ARG;
+  ArgmaxSlot* slot = nullptr;
+  int rc = argmax_slot(stream, &slot);
+  if (rc != KH_OK) return rc;
+  std::lock_guard<std::mutex> busy(slot->busy);
+  rc = kh_sample_f32(logits, n, p, counter, 1, slot->d, stream);
+  int32_t h = -1;
+  if (rc == KH_OK) {
+    hipError_t e = hipMemcpyAsync(&h, slot->d, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    rc = e == hipSuccess ? KH_OK : (int)e;
+  }
+  *h_out = h;
   return rc;
 }
 

@@ -106,6 +106,19 @@ class KuiperModel:
                                                C.byref(nxt)), "kh_model_predict")
         return int(nxt.value)
 
+    def set_sampling(self, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+        """Sampler of predict / generate (kh_model_set_sampling): temperature <= 0 is greedy (the default), top_k 0
+        and top_p 1 are off; the draw at position p uses Philox counter p, so tokens do not depend on the exec mode
+        or on how the steps were run."""
+        _ffi.check(_ffi.lib().kh_model_set_sampling(self._h, _ffi.sampling(temperature, top_k, top_p, seed)),
+                   "kh_model_set_sampling")
+
+    @property
+    def sampling(self) -> dict:
+        s = _ffi.Sampling()
+        _ffi.check(_ffi.lib().kh_model_get_sampling(self._h, C.byref(s)), "kh_model_get_sampling")
+        return s.as_dict()
+
     def logits(self) -> np.ndarray:
         out = np.empty(self.cfg.vocab_size, np.float32)
         _ffi.check(_ffi.lib().kh_model_get_logits(self._h, out.ctypes.data), "kh_model_get_logits")

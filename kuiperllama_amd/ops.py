@@ -159,6 +159,30 @@ def argmax_host(logits) -> int:
     return int(r.value)
 
 
+def _sampling(params):
+    if isinstance(params, _ffi.Sampling):
+        return params
+    return _ffi.sampling(**params)
+
+
+def sample(logits, out, params, counter0: int = 0):
+    """out.numel() seeded draws from one logit vector (kh_sample_f32): draw d uses counter counter0 + d.
+    params: an _ffi.Sampling or a dict with temperature / top_k / top_p / seed (temperature <= 0: argmax)."""
+    p = _sampling(params)
+    _ffi.check(_ffi.lib().kh_sample_f32(_p(logits, torch.float32), logits.numel(), p, int(counter0), out.numel(),
+                                        _p(out, torch.int32), _stream()), "kh_sample_f32")
+    return out
+
+
+def sample_host(logits, params, counter: int = 0) -> int:
+    """One draw with the index returned to the host (kh_sample_f32_host; synchronises the stream)."""
+    import ctypes as C
+    r = C.c_int64(-1)
+    _ffi.check(_ffi.lib().kh_sample_f32_host(_p(logits, torch.float32), logits.numel(), _sampling(params),
+                                             int(counter), C.byref(r), _stream()), "kh_sample_f32_host")
+    return int(r.value)
+
+
 def softmax_(x):
     _ffi.check(_ffi.lib().kh_softmax_f32(_p(x, torch.float32), x.numel(), _stream()),
                "kh_softmax_f32")

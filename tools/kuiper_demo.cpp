@@ -13,10 +13,13 @@
 //               [--exec graph|fused|unfused] [--max-seq-len N] [--device 0]
 //               [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json [--hf-spaces]] [--text "a"]
 //               [--exact-prefill] [--fenced-merge]
+//               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
 // prompt tokens/s).  --fenced-merge = KH_FLAG_ATTN_MERGE_FENCED.  The self-checks of kh_model_create_* are printed.
+// --temperature / --top-k / --top-p / --seed: seeded sampling instead of the argmax (kh_model_set_sampling; the
+// reference's demo is greedy, which stays the default).
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <chrono>
 #include <cstdio>
@@ -32,7 +35,8 @@ static void usage() {
                "usage: kuiper_demo model.bin [--family llama|qwen2] [--quant] [--rope interleaved|half]\n"
                "       [--theta F] [--eps F] [--steps N] [--prompt id,id,...] [--stop id,id] [--exec graph|fused|unfused]\n"
                "       [--max-seq-len N] [--device D] [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json\n"
-               "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge]\n");
+               "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge]\n"
+               "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n");
 }
 
 int main(int argc, char** argv) {
@@ -42,6 +46,7 @@ int main(int argc, char** argv) {
   }
   const char* path = argv[1];
   kh_model_opts o{KH_FAMILY_LLAMA, 0, KH_ROPE_INTERLEAVED, 10000.f, 1e-5f, 0, 0, 0};
+  kh_sampling samp{0.f, 0, 1.f, 0};  // greedy unless --temperature > 0 (kh_model_set_sampling)
   int steps = 128, exec = KH_EXEC_GRAPH;
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
@@ -70,6 +75,10 @@ int main(int argc, char** argv) {
     else if (a == "--hf-spaces") bpe_flags = 0;
     else if (a == "--exact-prefill") o.flags |= KH_FLAG_PREFILL_EXACT;
     else if (a == "--fenced-merge") o.flags |= KH_FLAG_ATTN_MERGE_FENCED;
+    else if (a == "--temperature") samp.temperature = (float)std::atof(next());
+    else if (a == "--top-k") samp.top_k = std::atoi(next());
+    else if (a == "--top-p") samp.top_p = (float)std::atof(next());
+    else if (a == "--seed") samp.seed = std::strtoull(next(), nullptr, 0);
     else if (a == "--text") {
       text = next();
       have_text = true;
@@ -161,6 +170,15 @@ int main(int argc, char** argv) {
   std::fprintf(stderr, "self-checks: int8 ring kernels %d, attention split merge %d; prompt phase: %s\n", c.ring_selftest,
                c.attn_merge_selftest, (o.flags & KH_FLAG_PREFILL_EXACT) ? "exact (bit-identical to token-by-token)"
                                                                         : "GEMM for 17+ tokens (fp32 round-off)");
+  rc = kh_model_set_sampling(m, &samp);
+  if (rc != KH_OK) {
+    std::fprintf(stderr, "invalid sampling parameters: %d (%s)\n", rc, kh_error_string(rc));
+    kh_model_destroy(m);
+    return 1;
+  }
+  if (samp.temperature > 0.f)
+    std::fprintf(stderr, "sampling: temperature %g, top-k %d, top-p %g, seed %llu\n", samp.temperature, samp.top_k,
+                 samp.top_p, (unsigned long long)samp.seed);
   std::vector<int32_t> words((size_t)steps);
   int32_t n = 0;
   float gpu_ms = 0.f;
