@@ -390,8 +390,9 @@ int kh_plan_prefill_shape(int32_t epi, int32_t T, int32_t rows, int32_t K, int32
 int kh_debug_set(const char* key, const char* value);
 const char* kh_debug_get(const char* key); /* NULL when unset */
 int64_t kh_debug_list(char* buf, int64_t cap); /* '\n'-separated names; returns bytes needed */
-/* Launch log.  While hook KH_LAUNCH_LOG is set (to anything but "0"), every fused decode-step and B-token prefill
- * launch adds the name of the kernel instantiation it launches ("k_gemv_res<true,3,6,2>") to a process-wide set;
+/* Launch log.  While hook KH_LAUNCH_LOG is set (to anything but "0"), every fused decode-step, B-token prefill and
+ * GEMM prefill launch adds the name of the kernel instantiation it launches ("k_gemv_res<true,3,6,2>",
+ * "k_pg_gemm<false,2,8,1>", "k_pg_rope") to a process-wide set;
  * setting, resetting or unsetting the hook (kh_debug_set) empties it.  kh_debug_launch_log: the names,
  * '\n'-separated and sorted, into buf (always NUL-terminated); returns the bytes needed. */
 int64_t kh_debug_launch_log(char* buf, int64_t cap);

@@ -107,7 +107,8 @@ void pf_launch(K kernel, int grid, int wg, size_t lds, hipStream_t s, const A& a
   if (grid > resident) grid = resident;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(wg), lds, s, args);
 }
-// the launch log's name of a B-token kernel instantiation (hook KH_LAUNCH_LOG), e.g. "k_pf_gemv_res<true,4,2>"
+// the launch log's name of a prefill kernel instantiation (hook KH_LAUNCH_LOG), e.g. "k_pf_gemv_res<true,4,2>",
+// "k_pg_gemm<false,2,8,1>", "k_pg_rmsnorm<true>"
 void pf_log(const char* stem, bool q, std::initializer_list<int> targs) {
   if (!g_launch_log_on.load(std::memory_order_relaxed)) return;
   std::string n = std::string(stem) + (q ? "<true" : "<false");
@@ -397,10 +398,10 @@ bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const Kh
     hipLaunchKernelGGL(kern, dim3(tiles, sh.slices, sh.kz), dim3(wg), lds, s, a);
     return true;
   };
-  if (sh.R == 2 && sh.NT == 8) return go(k_pg_gemm<Q, 2, 8, EPI>);
-  if (sh.R == 2 && sh.NT == 4) return go(k_pg_gemm<Q, 2, 4, EPI>);
-  if (sh.R == 2) return go(k_pg_gemm<Q, 2, 2, EPI>);
-  return go(k_pg_gemm<Q, 1, 4, EPI>);
+  if (sh.R == 2 && sh.NT == 8) return pf_log("k_pg_gemm", Q, {2, 8, EPI}), go(k_pg_gemm<Q, 2, 8, EPI>);
+  if (sh.R == 2 && sh.NT == 4) return pf_log("k_pg_gemm", Q, {2, 4, EPI}), go(k_pg_gemm<Q, 2, 4, EPI>);
+  if (sh.R == 2) return pf_log("k_pg_gemm", Q, {2, 2, EPI}), go(k_pg_gemm<Q, 2, 2, EPI>);
+  return pf_log("k_pg_gemm", Q, {1, 4, EPI}), go(k_pg_gemm<Q, 1, 4, EPI>);
 }
 // returns whether the QKV epilogue rotates q / k itself (else k_pg_rope has to follow); RESID: the
 // number of K slices whose partial rows the next RMSNorm has to add (0 = the epilogue added itself)
@@ -409,7 +410,7 @@ int pg_launch(kh_model* m, int rows_total, bool r2_ok, KhPgGemmArgs a) {
   const bool q = m->cfg.is_quant;
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
   PgShape sh = pg_shape(a.T, rows_total, r2_ok, nm, a.K / (q ? 64 : 16), q ? 4 : 16, q, EPI == KH_PG_RESID);
-  {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU>="R,NT,ks" overrides the heuristic
+  {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU>="R,NT,ks[,kz]" overrides the heuristic
     static const char* const names[3] = {"KH_PG_SHAPE_QKV", "KH_PG_SHAPE_RESID", "KH_PG_SHAPE_SWIGLU"};
     const char* const ov = dbg(names[EPI]);
     if (ov) {
@@ -421,6 +422,12 @@ int pg_launch(kh_model* m, int rows_total, bool r2_ok, KhPgGemmArgs a) {
         const int slices = ((a.T + 15) / 16 + NT - 1) / NT;
         sh = PgShape{R, NT, ks, slices,
                      !q && (a.T > 128 || R * NT >= 16) && pg_solo_on() && (long)(rows_total / (16 * R)) * slices * kz > 256, kz};
+      } else {
+        // not a launch this GEMM has (e.g. R = 2 where 32 rows do not divide the matrices): say so rather than
+        // let a test believe it forced a shape
+        fprintf(stderr, "[kh] %s=\"%s\" rejected (R,NT 1,4%s, ks 1/2/4/8 up to %d waves%s): heuristic shape\n",
+                names[EPI], ov, r2_ok ? " or 2,2/4/8" : "", KH_PG_WG_MAX(q) / 64 / nm,
+                EPI == KH_PG_RESID ? ", kz 1/2/4" : "");
       }
     }
   }
@@ -445,6 +452,7 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
   (void)kh_embedding_f32_host(toks, T, m->tok_emb, m->pg_x, c.dim, c.vocab_size, (void*)m->stream);
   int pending_kz = 0;  // K slices of the last residual GEMM still to be added to pg_x (by the next RMSNorm)
   auto rmsnorm = [&](const float* w) {
+    pf_log("k_pg_rmsnorm", q, {});
     if (q) hipLaunchKernelGGL(k_pg_rmsnorm<true>, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_x, w, m->pg_xn, c.dim, c.rms_eps, tcap, (const float*)m->pg_part, pending_kz);
     else hipLaunchKernelGGL(k_pg_rmsnorm<false>, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_x, w, m->pg_xn, c.dim, c.rms_eps, tcap, (const float*)m->pg_part, pending_kz);
     pending_kz = 0;
@@ -472,9 +480,11 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
                                               : KH_PG_ROPE_PAIRS);
       rope_fused = pg_launch<KH_PG_QKV>(m, c.dim + 2 * c.kv_dim, c.dim % 32 == 0 && c.kv_dim % 32 == 0, a) != 0;
     }
-    if (!rope_fused)
+    if (!rope_fused) {
+      launch_log("k_pg_rope");
       hipLaunchKernelGGL(k_pg_rope, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_q, kc, m->sin_cache,
                          m->cos_cache, c.dim, c.kv_dim, c.head_size, pos0, c.rope_mode);
+    }
     // the prompt phase leaves K/V rows and nothing else (no logits): the last layer's K/V rows are
     // written, its attention, wo and FFN feed nothing (1/L of the pass minus one QKV GEMM)
     if (l == c.layer_num - 1) break;

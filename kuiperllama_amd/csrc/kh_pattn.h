@@ -253,7 +253,11 @@ static inline void launch_pg_attn(const KhPgAttnArgs& a, int head_size, hipStrea
   const int grid = a.kv_heads * a.kv_mul * ((a.T + 16 * qt - 1) / (16 * qt));
   // 8 waves (two per SIMD: one wave's softmax fills the other's MFMA shadow) where the registers
   // allow it; head size 128 keeps 4
-#define KH_PA_GO(HB, NW, QT) hipLaunchKernelGGL((k_pg_attn<HB, NW, QT>), dim3(grid), dim3(64 * NW), 0, s, a)
+#define KH_PA_GO(HB, NW, QT)                                                          \
+  do {                                                                                \
+    khm::launch_log("k_pg_attn<" #HB "," #NW "," #QT ">");                            \
+    hipLaunchKernelGGL((k_pg_attn<HB, NW, QT>), dim3(grid), dim3(64 * NW), 0, s, a);  \
+  } while (0)
   switch (head_size) {
     case 48: if (qt == 4) KH_PA_GO(3, 8, 4); else if (qt == 2) KH_PA_GO(3, 8, 2); else KH_PA_GO(3, 8, 1); break;
     case 64: if (qt == 4) KH_PA_GO(4, 8, 4); else if (qt == 2) KH_PA_GO(4, 8, 2); else KH_PA_GO(4, 8, 1); break;

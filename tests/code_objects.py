@@ -1,8 +1,9 @@
 """The gfx950 code objects inside a built library (no GPU): their kernel descriptors, and the template arguments of
-the decode GEMV kernels read straight from the Itanium-mangled kernel names.
+the decode GEMV and GEMM-prefill kernels read straight from the Itanium-mangled kernel names.
 
 Reads the .hip_fatbin section with the LLVM tools of the ROCm install.  Used by test_code_objects.py (no kernel may
-use scratch) and test_decode_instantiations_gpu.py (every compiled decode-step instantiation is launched)."""
+use scratch) and test_decode_instantiations_gpu.py / test_prefill_gemm_instantiations_gpu.py (every compiled
+instantiation is launched)."""
 import os
 import re
 import shutil
@@ -59,8 +60,10 @@ def kernel_scratch(notes):
 
 
 # _Z<len><name>I<args>E...: a kernel template instantiation.  Its leading literal arguments are Lb0E / Lb1E (bool)
-# and Li<n>E / Lin<n>E (int, n: negative); a class argument ends the literal run.
+# and Li<n>E / Lin<n>E (int, n: negative); a class argument ends the literal run.  _ZL<len><name>...: a kernel with
+# internal linkage (static).
 _MANGLED = re.compile(r"^_Z(\d+)")
+_PLAIN = re.compile(r"^_ZL?(\d+)")
 _LITERAL = re.compile(r"L([bi])(n?)(\d+)E")
 
 
@@ -87,6 +90,16 @@ def template_name(mangled):
     return f"{stem}<{','.join(args)}>"
 
 
+def plain_name(mangled):
+    """'_ZL9k_pg_ropePfS_PKfS1_iiiii' -> 'k_pg_rope' (a kernel that is not a template, static or not); None for a
+    template instantiation or a name that is not mangled."""
+    m = _PLAIN.match(mangled)
+    if not m:
+        return None
+    p = m.end() + int(m.group(1))
+    return None if mangled[p:p + 1] == "I" else mangled[m.end():p]
+
+
 def instantiations(notes, stems):
     """Distinct template_name()s of the kernels in code_object_notes() whose name is one of `stems`."""
     out = set()
@@ -94,4 +107,14 @@ def instantiations(notes, stems):
         t = template_name(k)
         if t and t.split("<")[0] in stems:
             out.add(t)
+    return out
+
+
+def kernels(notes, stems):
+    """instantiations() plus the plain_name()s of the non-template kernels whose name is one of `stems`."""
+    out = instantiations(notes, stems)
+    for k in kernel_scratch(notes):
+        n = plain_name(k)
+        if n in stems:
+            out.add(n)
     return out

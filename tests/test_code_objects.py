@@ -36,3 +36,14 @@ def test_qkv_is_compiled_for_its_reachable_splits_only():
     want = {f"k_qkv<{q},{u},{mv},{sp}>" for q, us in (("false", (8, 4, 2)), ("true", (4, 2))) for u in us
             for mv in (4, 2, 1, 0) for sp in (1, 2)}
     assert qkv == want, (sorted(qkv - want), sorted(want - qkv))
+
+
+def test_plain_kernel_names_are_read_back():
+    """k_pg_rope is a static, non-template kernel: template_name() has no name for it, plain_name() and kernels() do."""
+    assert co.plain_name("_ZL9k_pg_ropePfS_PKfS1_iiiii") == "k_pg_rope"
+    assert co.plain_name("_Z8k_samplePKfiPi") == "k_sample"
+    assert co.plain_name("_Z5k_qkvILb0ELi2ELi0ELi1EEv9KhQkvArgs") is None
+    assert co.plain_name("main") is None
+    assert co.template_name("_ZL9k_pg_ropePfS_PKfS1_iiiii") is None
+    got = co.kernels(_code_object_notes(), {"k_pg_rope", "k_pg_rmsnorm"})
+    assert got == {"k_pg_rope", "k_pg_rmsnorm<false>", "k_pg_rmsnorm<true>"}, sorted(got)
