@@ -216,6 +216,13 @@ typedef struct kh_model_opts {
  *    drop-in user who needs token identity with the reference's own prompt phase sets.
  * kh_first_sample.prefill_mode says which one the last generate took.  The test hook KH_PREFILL overrides both. */
 #define KH_FLAG_PREFILL_EXACT 4
+/* fp32 models keep a bf16 copy of the classifier (vocab x dim x 2 bytes of HBM, made at creation) with which the
+ * greedy steps of kh_model_generate* (graph and fused exec) find the argmax without streaming the fp32 classifier:
+ * the copy screens the rows, the rows that can still win are re-scored from their fp32 rows, the tokens are
+ * bit for bit those of the full classifier, and kh_model_get_logits behind such a run computes the last step's
+ * logits on demand (csrc/kh_cls_screen.h).  This flag - or hook KH_CLS_SCREEN=0 at creation - leaves the copy out;
+ * the hook set later turns screening off for the generates that follow.  kh_model_cls_screen_info reports. */
+#define KH_FLAG_NO_CLS_SCREEN 8
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -267,6 +274,11 @@ int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t is_prompt,
                      int32_t* h_next);
 /* copy the last logits (kForwardOutput) to host */
 int kh_model_get_logits(kh_model* m, float* h_logits);
+/* the screened classifier (KH_FLAG_NO_CLS_SCREEN): out[8] = on (0 / 1), creation-time self-test (0 not run, 1 passed,
+ * -1 failed: screening off), HBM bytes of the bf16 copy and its row table, microseconds its conversion took, screened
+ * steps so far, candidate rows re-scored in them, steps that overflowed into the full classifier, candidate
+ * capacity of a step */
+int kh_model_cls_screen_info(kh_model* m, int64_t* out8);
 /* device pointers of the KV cache [layer, cache_len, kv_dim] (tests) */
 int kh_model_get_kv(kh_model* m, float** d_kcache, float** d_vcache);
 /* bytes of the KV cache: *reserved = the address range of [layer, cache_len, kv_dim] floats x 2 (the reference's

@@ -1,0 +1,517 @@
+// kh_cls_screen.h — exact greedy argmax without streaming the fp32 classifier: a bf16 copy of the classifier
+// screens the rows, the few rows that can still be the argmax are re-scored from their fp32 rows.
+//
+// A greedy step uses one fact about its 128 k logits: which is largest.  k_cls streams vocab x dim fp32 weights to
+// find it; here
+//
+//   k_cls_bf16_build  (model creation) writes the classifier once more as bf16, round to nearest even, and per row
+//                     e[r] >= |w_r - bf16(w_r)|_2 + 2 gamma_n (|w_r|_2 + |bf16(w_r)|_2)            (fp64, rounded up)
+//   k_cls_screen      (k_cls's slot in the step) streams the bf16 rows - half the bytes - against the same staged
+//                     g = w_norm o x and leaves, per workgroup, the best LOWER bound of a logit and its few best
+//                     rows by UPPER bound
+//   k_sample_screen   (k_sample's slot) merges the partials, re-scores the candidate rows from the fp32 classifier
+//                     with k_cls's own per-lane order and reduction (the same device functions: Stager,
+//                     Gemv<false, U>::load / fma, wave_sum), and takes the argmax of those exact values.
+//
+// The interval.  Let g be the staged vector (fp32 words, the same in both kernels), rs the RMS scale, S and A the
+// exact sums  sum_i w_i g_i  and  sum_i bf16(w_i) g_i, S32 and A32 what the fp32 kernels accumulate for them.  k_cls
+// stores l = fl(rs S32); the screen forms a = fl(rs A32).
+//   |S - A|     <= |w - bf16(w)|_2 |g|_2                                          (Cauchy-Schwarz, exact reals)
+//   |S32 - S|   <= gamma_n sum_i |w_i g_i| <= gamma_n |w|_2 |g|_2 ,  gamma_n = n u / (1 - n u),  u = 2^-24
+//   |A32 - A|   <= gamma_n |bf16(w)|_2 |g|_2
+// n is the number of roundings a term passes through: a lane's chain of dim/64 FMAs (both kernels: 64 lanes, one
+// FMA per weight) plus six butterfly additions, n = ceil(dim / 64) + 8; e[r] carries 2 gamma_n, twice what the
+// analysis needs (at dim 2048 the rounding part is well under 1 % of e; the bf16 part is everything).  So
+//   |rs S32 - rs A32| <= rs |g|_2 e[r] .
+// What is left is relative to the values themselves: the two multiplications by rs (1 u each), an rs that a launch
+// of another workgroup width sums in another order (a few u), |g|_2 formed in fp32 (sum of non-negative terms,
+// < 32 u, and one square root), the products and the sums that form b, a - b and a + b.  They are covered by
+//   b = fl(rs |g|_2 (1 + 2^-17)) e[r] + |a| 2^-18 + 1e-30
+// (64 u on |a| against fewer than 8; 128 u on the main term against fewer than 40; 1e-30 stands for products that
+// underflow: dim x 2^-126 x rs stays below 1e-31 for every dim up to 64 k).  Claim: l lies in [a - b, a + b].  A
+// row whose a or b is not finite gets (-inf, +inf): always a candidate, never raises the lower bound.
+//
+// Exactness of the token.  L = max over rows of (a - b) is a lower bound of the largest logit, so a row with
+// a + b < L is not the argmax, nor tied with it.  Every other row is re-scored exactly; the argmax over them, ties to
+// the lowest index, is the argmax over all rows.  A workgroup hands over its KH_SCR_C best rows by upper bound and
+// the largest upper bound it dropped; if a dropped bound reaches L, or more than KH_SCR_CAND rows qualify, the step
+// OVERFLOWS: every workgroup of k_sample_screen (one per CU; all but the first leave at once otherwise) then runs
+// the full fp32 classifier and the last one to arrive merges - the arithmetic of k_cls + k_sample, inside the same
+// launch, no host decision.
+//
+// Replaces nothing in the reference (it streams the fp32 classifier and runs an argmax kernel,
+// kuiper/source/model/llama3.cpp:722-745).
+#pragma once
+#include "kh_fused.h"
+
+#define KH_SCR_C 4      // rows a workgroup of k_cls_screen hands over
+#define KH_SCR_CAND 32  // rows k_sample_screen re-scores before the step counts as an overflow
+#define KH_SCR_MERGE_WORDS (2 + 2 * KH_SCR_C)
+
+// LDS layout of the staged vector for the bf16 rows: a lane owns 8 consecutive weights (one dwordx4), i.e. the
+// float4 f = 2j and 2j + 1 of its 8-chunk j.  Two planes, slot(f) = (f & 1) * (M8 + 1) + (f >> 1): for either half
+// consecutive lanes read consecutive 16-byte slots (the int8 kernels' q8_slot with two planes instead of four).
+__device__ __forceinline__ int bf_slot(int f, int M8) { return (f & 1) * (M8 + 1) + (f >> 1); }
+static inline size_t kh_bf_lds_bytes(int M) { return (size_t)2 * (size_t)(M / 8 + 1) * 16; }
+// xs (two planes) | ss[KH_WAVES_MAX] | gg[KH_WAVES_MAX] | per-wave partials
+static inline size_t cls_screen_lds_bytes(int M) {
+  return kh_bf_lds_bytes(M) + (size_t)(2 * KH_WAVES_MAX + KH_WAVES_MAX * KH_SCR_MERGE_WORDS) * sizeof(float);
+}
+
+__device__ __forceinline__ float bf_lo(int d) { return __builtin_bit_cast(float, d << 16); }
+__device__ __forceinline__ float bf_hi(int d) { return __builtin_bit_cast(float, d & (int)0xffff0000u); }
+// 8 packed bf16 (one dwordx4, element 2k in the low half of dword k) . 8 floats
+__device__ __forceinline__ float dot8_bf16(i32x4 q, f32x4 xa, f32x4 xb, float acc) {
+  acc = __builtin_fmaf(bf_lo(q.x), xa.x, acc);
+  acc = __builtin_fmaf(bf_hi(q.x), xa.y, acc);
+  acc = __builtin_fmaf(bf_lo(q.y), xa.z, acc);
+  acc = __builtin_fmaf(bf_hi(q.y), xa.w, acc);
+  acc = __builtin_fmaf(bf_lo(q.z), xb.x, acc);
+  acc = __builtin_fmaf(bf_hi(q.z), xb.y, acc);
+  acc = __builtin_fmaf(bf_lo(q.w), xb.z, acc);
+  acc = __builtin_fmaf(bf_hi(q.w), xb.w, acc);
+  return acc;
+}
+
+// The matrix view gemv_pairs needs (kh_gemv.h: kU, Regs, Rows, Mc, load, fma), over bf16 rows of M weights.
+template <int U>
+struct RegsBf16 {
+  i32x4 v0[U], v1[U];
+};
+struct RowsBf16 {
+  const i32x4* w0;
+  const i32x4* w1;
+};
+template <int U>
+struct GemvBf16 {
+  static constexpr int kU = U;
+  using Regs = RegsBf16<U>;
+  using Rows = RowsBf16;
+  int Mc;  // 16-byte units per row: M / 8
+  __device__ __forceinline__ explicit GemvBf16(int M) : Mc(M >> 3) {}
+  __device__ __forceinline__ Rows rows(const uint16_t* base, int r0, int r1, int M) const {
+    return Rows{(const i32x4*)(base + (size_t)r0 * M), (const i32x4*)(base + (size_t)r1 * M)};
+  }
+  __device__ __forceinline__ void load(Regs& r, const Rows& rw, int c0, int lim, int lane) const {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = c0 + u * KH_WAVE + lane;
+      const int cidx = idx < lim ? idx : 0;  // clamped address; masked in fma (kh_gemv.h::fma_u)
+      r.v0[u] = ld_nt(rw.w0 + cidx);
+      r.v1[u] = ld_nt(rw.w1 + cidx);
+      __builtin_amdgcn_sched_barrier(0);  // slots stay in issue order (kh_gemv.h::load_u)
+    }
+  }
+  __device__ __forceinline__ void fma(const Regs& r, const f32x4* xs, int c0, int lim, int lane, float& a0,
+                                      float& a1) const {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = c0 + u * KH_WAVE + lane;
+      const bool in = idx < lim;
+      const int ci = in ? idx : 0;
+      f32x4 xa = xs[ci], xb = xs[Mc + 1 + ci];
+      xa.x = in ? xa.x : 0.f;
+      xa.y = in ? xa.y : 0.f;
+      xa.z = in ? xa.z : 0.f;
+      xa.w = in ? xa.w : 0.f;
+      xb.x = in ? xb.x : 0.f;
+      xb.y = in ? xb.y : 0.f;
+      xb.z = in ? xb.z : 0.f;
+      xb.w = in ? xb.w : 0.f;
+      a0 = dot8_bf16(r.v0[u], xa, xb, a0);
+      a1 = dot8_bf16(r.v1[u], xa, xb, a1);
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Model creation: bf16 copy of the classifier + per-row error norm.  One wave per row, fp64 accumulation.
+__device__ __forceinline__ uint32_t bf16_rne(float f) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // NaN stays a (quiet) NaN
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, KH_WAVE);
+  return v;
+}
+// gam2 = 2 gamma_n (see the head of this file).  dim is even (the caller requires a multiple of 8).
+static __global__ __launch_bounds__(KH_WG) void k_cls_bf16_build(const float* __restrict__ w, uint32_t* __restrict__ out,
+                                                                 float* __restrict__ err, int dim, int vocab,
+                                                                 double gam2) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int half = dim >> 1;
+  for (int row = blockIdx.x * KH_WAVES_PER_WG + wave; row < vocab; row += gridDim.x * KH_WAVES_PER_WG) {
+    const float2* src = (const float2*)(w + (size_t)row * dim);
+    uint32_t* dst = out + (size_t)row * half;
+    double d2 = 0.0, w2 = 0.0, b2 = 0.0;
+    for (int i = lane; i < half; i += KH_WAVE) {
+      const float2 v = src[i];
+      const uint32_t lo = bf16_rne(v.x), hi = bf16_rne(v.y);
+      dst[i] = lo | (hi << 16);
+      const float bx = __builtin_bit_cast(float, lo << 16), by = __builtin_bit_cast(float, hi << 16);
+      const double ex = (double)v.x - (double)bx, ey = (double)v.y - (double)by;
+      d2 += ex * ex + ey * ey;
+      w2 += (double)v.x * (double)v.x + (double)v.y * (double)v.y;
+      b2 += (double)bx * (double)bx + (double)by * (double)by;
+    }
+    d2 = wave_sum_f64(d2);
+    w2 = wave_sum_f64(w2);
+    b2 = wave_sum_f64(b2);
+    if (lane == 0) {
+      // the fp64 sums carry a relative error below dim x 2^-52: (1 + 1e-9) is far above it
+      const double e = (sqrt(d2) + gam2 * (sqrt(w2) + sqrt(b2))) * (1.0 + 1e-9);
+      float f = (float)e;
+      if ((double)f < e) f = nextafterf(f, INFINITY);
+      if (!(e < (double)INFINITY)) f = INFINITY;  // NaN / Inf weights: the row is always a candidate
+      err[row] = f;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// keep the KH_SCR_C largest upper bounds (descending) and the largest one that fell out
+struct ScrTop {
+  float lb, spill;
+  float u[KH_SCR_C];
+  int i[KH_SCR_C];
+  __device__ __forceinline__ void init() {
+    lb = -INFINITY;
+    spill = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < KH_SCR_C; ++k) {
+      u[k] = -INFINITY;
+      i[k] = -1;
+    }
+  }
+  __device__ __forceinline__ void insert(float ub, int idx) {
+#pragma unroll
+    for (int k = 0; k < KH_SCR_C; ++k) {
+      const bool sw = ub > u[k];
+      const float tu = sw ? u[k] : ub;
+      const int ti = sw ? i[k] : idx;
+      u[k] = sw ? ub : u[k];
+      i[k] = sw ? idx : i[k];
+      ub = tu;
+      idx = ti;
+    }
+    spill = fmaxf(spill, idx >= 0 ? ub : -INFINITY);  // an empty slot that fell out is not a row
+  }
+};
+
+struct KhClsScreenArgs {
+  const float* x;
+  const float* final_norm;
+  const uint16_t* wbf;  // [vocab, dim] bf16
+  const float* err;     // [vocab]
+  float* x_save;        // [dim]: the pre-norm input, for logits on demand and for the re-scoring
+  float* p_lb;          // [grid]
+  float* p_spill;       // [grid]
+  float* p_ub;          // [grid, KH_SCR_C]
+  int32_t* p_idx;       // [grid, KH_SCR_C], -1 = empty
+  float* dbg_lb;        // [vocab] or nullptr: every row's interval (creation-time self-test)
+  float* dbg_ub;
+  int dim, vocab;
+  float eps;
+};
+template <int U, int MAXV>
+__global__ __launch_bounds__(KH_WG_MAX, 4) void k_cls_screen(const KhClsScreenArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  f32x4* xs = (f32x4*)smem_raw;
+  const int dim = a.dim, vocab = a.vocab, M8 = dim >> 3;
+  float* red = (float*)(xs + 2 * (M8 + 1));
+  float* mg = red + 2 * KH_WAVES_MAX;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint16_t* const wbf = a.wbf;
+  const float* const err = a.err;
+  float* const dbg_lb = a.dbg_lb;
+  float* const dbg_ub = a.dbg_ub;
+  float* const x_save = a.x_save;
+  const float eps = a.eps;
+  const GemvBf16<U> g(dim);
+  Stager<true, false, MAXV> st(a.x, a.final_norm, dim);
+  ScrTop top;
+  top.init();
+  auto r1_of = [&](int p) __attribute__((always_inline)) { return 2 * p + 1 < vocab ? 2 * p + 1 : 2 * p; };
+  auto pair = [&](int p) __attribute__((always_inline)) { return g.rows(wbf, 2 * p, r1_of(p), dim); };
+  struct Aux {
+    float e0, e1;
+  };
+  auto pre = [&](int p) __attribute__((always_inline)) { return Aux{err[2 * p], err[r1_of(p)]}; };
+  float rs = 1.f, cb = 0.f;  // RMS scale; rs |g|_2 (1 + 2^-17)
+  auto track = [&](float s, float e, int r) __attribute__((always_inline)) {
+    const float av = s * rs;
+    const float b = __builtin_fmaf(cb, e, fabsf(av) * 0x1p-18f) + 1e-30f;
+    const bool ok = fabsf(av) < INFINITY && b < INFINITY;  // false for NaN as well
+    const float lb = ok ? av - b : -INFINITY, ub = ok ? av + b : INFINITY;
+    top.lb = fmaxf(top.lb, lb);
+    top.insert(ub, r);
+    if (dbg_lb && lane == 0) {
+      dbg_lb[r] = lb;
+      dbg_ub[r] = ub;
+    }
+  };
+  // every lane holds the same sums behind the butterfly: the bookkeeping runs unmasked, lane 0 hands it over
+  auto epi = [&](int p, float s0, float s1, const Aux& x) __attribute__((always_inline)) {
+    const int r0 = 2 * p, r1 = r1_of(p);
+    track(s0, x.e0, r0);
+    if (r1 != r0) track(s1, x.e1, r1);
+  };
+  auto finish = [&]() __attribute__((always_inline)) {
+    // Stager::finish with the two-plane layout, the sum of g^2 beside the sum of x^2, and the input put aside
+    const int M4 = dim >> 2;
+    float ss = 0.f, gg = 0.f;
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) {
+      const int i = threadIdx.x + v * kh_wg();
+      const bool in = i < M4;
+      const float t = fma4(st.xv[v], st.xv[v], 0.f);
+      ss += in ? t : 0.f;
+      f32x4 gv = st.xv[v];
+      gv.x = st.wv[v].x * gv.x;
+      gv.y = st.wv[v].y * gv.y;
+      gv.z = st.wv[v].z * gv.z;
+      gv.w = st.wv[v].w * gv.w;
+      const float t2 = fma4(gv, gv, 0.f);
+      gg += in ? t2 : 0.f;
+      if (in) {
+        xs[bf_slot(i, M8)] = gv;
+        if (blockIdx.x == 0) ((f32x4*)x_save)[i] = st.xv[v];
+      }
+    }
+    gg = wave_sum(gg);
+    if (lane == 0) red[KH_WAVES_MAX + wave] = gg;
+    rs = stage_rs(ss, dim, eps, red);  // its barrier publishes xs and both sets of wave sums
+    const int n = kh_nwaves();
+    float r = 0.f;
+#pragma unroll
+    for (int w = 0; w < KH_WAVES_MAX; ++w) r += w < n ? red[KH_WAVES_MAX + (w < n ? w : 0)] : 0.f;
+    cb = rs * sqrtf(r) * (1.f + 0x1p-17f);
+  };
+  gemv_pairs<1, /*ROLL=*/false>(g, xs, (vocab + 1) >> 1, lane, nullptr, pair, pre,
+                                [&]() __attribute__((always_inline)) { st.issue(); }, finish, epi);
+  // one partial per workgroup
+  if (lane == 0) {
+    float* q = mg + wave * KH_SCR_MERGE_WORDS;
+    q[0] = top.lb;
+    q[1] = top.spill;
+#pragma unroll
+    for (int k = 0; k < KH_SCR_C; ++k) {
+      q[2 + k] = top.u[k];
+      q[2 + KH_SCR_C + k] = __builtin_bit_cast(float, top.i[k]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1, nw = kh_nwaves(); w < nw; ++w) {
+      const float* q = mg + w * KH_SCR_MERGE_WORDS;
+      top.lb = fmaxf(top.lb, q[0]);
+      top.spill = fmaxf(top.spill, q[1]);
+#pragma unroll
+      for (int k = 0; k < KH_SCR_C; ++k) top.insert(q[2 + k], __builtin_bit_cast(int, q[2 + KH_SCR_C + k]));
+    }
+    a.p_lb[blockIdx.x] = top.lb;
+    a.p_spill[blockIdx.x] = top.spill;
+#pragma unroll
+    for (int k = 0; k < KH_SCR_C; ++k) {
+      a.p_ub[blockIdx.x * KH_SCR_C + k] = top.u[k];
+      a.p_idx[blockIdx.x * KH_SCR_C + k] = top.i[k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+struct KhSampleScreenArgs {
+  // the screen's partials
+  const float* p_lb;
+  const float* p_spill;
+  const float* p_ub;
+  const int32_t* p_idx;
+  int nsp;
+  // the exact classifier (re-scoring, overflow)
+  const float* x_save;
+  const float* final_norm;
+  const float* wcls;  // fp32 [vocab, dim]
+  float eps;
+  float* ov_val;      // [gridDim.x] argmax partials of an overflow step
+  int32_t* ov_idx;
+  uint32_t* ticket;   // 0 between launches
+  int32_t* stats;     // [0] steps, [1] candidate rows re-scored, [2] overflow steps
+  // k_sample's tail
+  const int32_t* forced;
+  int n_forced;
+  int32_t* words;
+  int words_cap;
+  int32_t* d_next;
+  int32_t* d_token;
+  int32_t* d_pos;
+  const float* tok_emb;
+  float* x;
+  int dim, vocab;
+  int advance;
+};
+// the tail of k_sample (kh_fused.h), word for word: thread 0 holds the argmax
+__device__ __forceinline__ void screen_tail(const KhSampleScreenArgs& a, int idx, int* s_next) {
+  if (threadIdx.x == 0) {
+    const int pos = *a.d_pos;
+    int feed = idx;
+    int reported = idx;
+    if (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) {
+      feed = a.forced[pos + 1];
+      reported = -1;
+    }
+    *a.d_next = reported;
+    if (a.advance) {
+      if (a.words && pos < a.words_cap) a.words[pos] = feed;
+      *a.d_token = feed;
+      *a.d_pos = pos + 1;
+    }
+    *s_next = a.advance ? feed : -1;
+  }
+  __syncthreads();
+  const int nxt = *s_next;
+  if (nxt >= 0 && nxt < a.vocab) {
+    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
+    f32x4* dst = (f32x4*)a.x;
+    for (int i = threadIdx.x; i < (a.dim >> 2); i += kh_wg()) dst[i] = src[i];
+  }
+}
+// U, MAXV and the workgroup width are those of the model's k_cls launch: the staging (and with it rs) and the
+// per-lane order of a row's sum are then k_cls's, bit for bit.  Dynamic LDS: cls_lds_bytes(false, dim).
+template <int U, int MAXV>
+__global__ __launch_bounds__(KH_WG_MAX, 4) void k_sample_screen(const KhSampleScreenArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  __shared__ float s_cv[KH_SCR_CAND];
+  __shared__ int s_ci[KH_SCR_CAND];
+  __shared__ int s_n, s_last, s_next;
+  f32x4* xs = (f32x4*)smem_raw;
+  const int dim = a.dim, vocab = a.vocab;
+  float* red = lds_red_ptr<false>(xs, dim);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const float* const wcls = a.wcls;
+  const float eps = a.eps;
+  // ---- merge the screen's partials: L, the largest dropped bound, the candidate rows (every workgroup: all of
+  // them must come to the same decision without talking to each other)
+  float l = -INFINITY, sp = -INFINITY;
+  for (int i = threadIdx.x; i < a.nsp; i += kh_wg()) {
+    l = fmaxf(l, a.p_lb[i]);
+    sp = fmaxf(sp, a.p_spill[i]);
+  }
+  if (threadIdx.x == 0) s_n = 0;
+  const float L = block_max(l, red);
+  const float S = block_max(sp, red);
+  for (int i = threadIdx.x; i < a.nsp * KH_SCR_C; i += kh_wg()) {
+    const int idx = a.p_idx[i];
+    if (idx >= 0 && a.p_ub[i] >= L) {
+      const int slot = atomicAdd(&s_n, 1);
+      if (slot < KH_SCR_CAND) s_ci[slot] = idx;  // order is free: the argmax below breaks ties by index
+    }
+  }
+  __syncthreads();
+  const int n = s_n;
+  const bool overflow = S >= L || n > KH_SCR_CAND || n == 0;
+  const Gemv<false, U> g(dim, 0);
+  Stager<true, false, MAXV> st(a.x_save, a.final_norm, dim);
+  if (!overflow) {
+    if (blockIdx.x != 0) return;
+    // ---- re-score: one wave per candidate row, the row requested before the vector is staged
+    typename Gemv<false, U>::Regs regs;
+    st.issue();
+    __builtin_amdgcn_sched_barrier(0);
+    const int step = KH_WAVE * U;
+    int r = s_ci[wave < n ? wave : 0];
+    typename Gemv<false, U>::Rows rw = g.rows(wcls, r, wcls, r, nullptr, nullptr, dim);
+    g.load(regs, rw, 0, g.Mc, lane);
+    const float rs = st.finish(xs, eps, red);
+    for (int j = wave; j < n; j += kh_nwaves()) {
+      if (j != wave) {
+        r = s_ci[j];
+        rw = g.rows(wcls, r, wcls, r, nullptr, nullptr, dim);
+        g.load(regs, rw, 0, g.Mc, lane);
+      }
+      float a0 = 0.f, a1 = 0.f;
+      for (int c0 = 0;;) {  // gemv_pairs' walk over a row's chunks (SPLIT = 1, no rolling refill)
+        g.fma(regs, xs, c0, g.Mc, lane, a0, a1);
+        c0 += step;
+        if (c0 >= g.Mc) break;
+        g.load(regs, rw, c0, g.Mc, lane);
+      }
+      float s0 = wave_sum(a0);
+      s0 *= rs;
+      if (lane == 0) s_cv[j] = s0;
+    }
+    __syncthreads();
+    int idx = 0x7fffffff;
+    if (threadIdx.x == 0) {
+      float v = -INFINITY;
+      for (int k = 0; k < n; ++k) amax_merge(v, idx, s_cv[k], s_ci[k]);
+      a.stats[0] += 1;
+      a.stats[1] += n;
+    }
+    screen_tail(a, idx, &s_next);
+    return;
+  }
+  // ---- overflow: k_cls's classifier in every workgroup, argmax partials, last arriver merges
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  auto r1_of = [&](int p) __attribute__((always_inline)) { return 2 * p + 1 < vocab ? 2 * p + 1 : 2 * p; };
+  auto pair = [&](int p) __attribute__((always_inline)) {
+    return g.rows(wcls, 2 * p, wcls, r1_of(p), nullptr, nullptr, dim);
+  };
+  float rs = 1.f;
+  auto epi = [&](int p, float s0, float s1, const NoAux&) __attribute__((always_inline)) {
+    if (lane != 0) return;
+    const int r0 = 2 * p, r1 = r1_of(p);
+    s0 *= rs;
+    s1 *= rs;
+    amax_merge(bv, bi, s0, r0);
+    if (r1 != r0) amax_merge(bv, bi, s1, r1);
+  };
+  gemv_pairs<1, /*ROLL=*/false>(g, xs, (vocab + 1) >> 1, lane, nullptr, pair,
+                                [](int) __attribute__((always_inline)) { return NoAux{}; },
+                                [&]() __attribute__((always_inline)) { st.issue(); },
+                                [&]() __attribute__((always_inline)) { rs = st.finish(xs, eps, red); }, epi);
+  int* redi = (int*)(red + 3 * KH_WAVES_MAX);
+  __syncthreads();
+  if (lane == 0) {
+    red[wave] = bv;
+    redi[wave] = bi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float v = red[0];
+    int i = redi[0];
+    for (int w = 1, nw = kh_nwaves(); w < nw; ++w) amax_merge(v, i, red[w], redi[w]);
+    // agent-scope stores + a release in front of the ticket: the partial is visible to whoever draws the last one
+    __hip_atomic_store(a.ov_val + blockIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.ov_idx + blockIdx.x, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = t == gridDim.x - 1 ? 1 : 0;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  float v = -INFINITY;
+  int idx = 0x7fffffff;
+  for (int i = threadIdx.x; i < (int)gridDim.x; i += kh_wg())
+    amax_merge(v, idx, __hip_atomic_load(a.ov_val + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+               __hip_atomic_load(a.ov_idx + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  wave_amax(v, idx);
+  __syncthreads();  // red / redi were read by thread 0 above
+  if (lane == 0) {
+    red[wave] = v;
+    redi[wave] = idx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v = red[0];
+    idx = redi[0];
+    for (int w = 1, nw = kh_nwaves(); w < nw; ++w) amax_merge(v, idx, red[w], redi[w]);
+    __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a.stats[0] += 1;
+    a.stats[2] += 1;
+  }
+  screen_tail(a, idx, &s_next);
+}

@@ -148,13 +148,35 @@ struct kh_model {
   };
   // [sampler][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps, with the greedy k_sample (0) or
   // the sampling k_sample_topp (1) as the last launch of every step
-  StepGraph sg[2][KH_STEP_VARIANTS][4];
+  // ... or (2) the screened classifier pair k_cls_screen + k_sample_screen (greedy steps of a generate, see scr)
+  StepGraph sg[3][KH_STEP_VARIANTS][4];
   // kh_model_set_sampling: the parameters (host copy), whether they sample (temperature > 0), and their device copy,
   // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
   kh_sampling samp{0.f, 0, 1.f, 0};
   bool samp_on = false;
   KhSampParams* d_samp = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // Screened classifier of the greedy generate loop (kh_cls_screen.h, kh_model_screen.hip): fp32 models only
+  struct ClsScreen {
+    bool on = false;        // the bf16 copy exists and the creation-time check passed (or was skipped)
+    int selftest = 0;       // 0 not applicable / skipped, 1 passed, -1 failed -> screening off
+    uint16_t* wbf = nullptr;   // [vocab, dim] bf16 copy of the classifier
+    float* err = nullptr;      // [vocab] per-row error norm
+    float* x_save = nullptr;   // [dim] input of the last screened step
+    float *p_lb = nullptr, *p_spill = nullptr, *p_ub = nullptr;  // partials of k_cls_screen
+    int32_t* p_idx = nullptr;
+    float* ov_val = nullptr;   // argmax partials of an overflow step [sgrid]
+    int32_t* ov_idx = nullptr;
+    uint32_t* ticket = nullptr;
+    int32_t* stats = nullptr;  // steps, candidate rows, overflow steps
+    float *dbg_lb = nullptr, *dbg_ub = nullptr;  // set by the self-test only
+    int u = 4, grid = 1, wg = KH_WG, sgrid = 1;  // launch of k_cls_screen; workgroups of k_sample_screen
+    size_t bytes = 0;          // HBM the copy and its tables take
+    float build_ms = 0.f;      // time of the conversion kernel
+    bool now = false;          // the launches being enqueued / captured use the screened pair
+    bool stale = false;        // the logits buffer is older than the last step: refresh from x_save on demand
+  };
+  ClsScreen scr;
 };
 
 #define KH_GRAPH_STEPS 8
@@ -196,6 +218,16 @@ void destroy_step_graphs(kh_model* m);
 int step_graph(kh_model* m, int n_forced, int variant, bool steps8, hipGraphExec_t* out);
 // the same for a graph of `nsteps` in {1, 2, 4, 8} steps (the tail of a run: 20 steps = 8 + 8 + 4)
 int step_graph_n(kh_model* m, int n_forced, int variant, int nsteps, hipGraphExec_t* out);
+// index of kh_model::sg the launches enqueued right now belong to
+static inline int sg_sampler(const kh_model* m) { return m->samp_on ? 1 : (m->scr.now ? 2 : 0); }
+// ---- kh_model_screen.hip --------------------------------------------------------------------
+int cls_screen_create(kh_model* m);   // bf16 copy + tables, once the weights are resident (no-op where it does not apply)
+void cls_screen_release(kh_model* m);
+bool cls_screen_wanted(const kh_model* m);  // may this generate screen? (sampler, hooks)
+void launch_cls_screen(kh_model* m);
+void launch_sample_screen(kh_model* m, int advance, int n_forced);
+int cls_refresh_logits(kh_model* m);  // k_cls on the saved input if the logits buffer is stale
+int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result);
 // ---- kh_model_load.hip ----------------------------------------------------------------------
 // Make rows [0, rows) of the K / V cache usable before anything that touches them is enqueued: every layer, or one
 // (layer >= 0).  No-op for rows that are mapped already and for caches that are plainly allocated.  Newly mapped

@@ -654,6 +654,7 @@ extern "C" void kh_model_destroy(kh_model* m) {
   if (m->h_forced_pin) (void)hipHostFree(m->h_forced_pin);
   if (m->first_logits) (void)hipFree(m->first_logits);
   if (m->d_samp) (void)hipFree(m->d_samp);
+  cls_screen_release(m);
   void* bufs[] = {m->x,      m->rms,    m->q,         m->att,       m->h1,       m->h3,
                   m->w2o,    m->logits, m->score,     m->sin_cache,
                   m->cos_cache, m->part_val, m->part_idx, m->d_pos, m->d_token,  m->d_next,
@@ -682,6 +683,7 @@ static int create_from_device_weights_impl(const int32_t* h_header, const void* 
   m->arena_bytes = weight_nbytes;
   m->cfg.weight_bytes = (int64_t)expected_weight_bytes(m->cfg);
   rc = finish_create(m);
+  if (rc == KH_OK) rc = cls_screen_create(m);
   if (rc == KH_OK) rc = run_selftests(m);  // the weights are resident: ring kernels / split merge against their fallbacks
   if (rc != KH_OK) {
     kh_model_destroy(m);
@@ -758,6 +760,8 @@ static int create_from_host_image_impl(const void* h_image, size_t nbytes, const
     if (es != hipSuccess) rc = (int)es;
   }
   pc.lap("upload || buffers, joined");
+  if (rc == KH_OK) rc = cls_screen_create(m);  // the arena is resident: bf16 copy of the classifier (fp32 models)
+  pc.lap("bf16 classifier copy");
   if (rc == KH_OK) rc = run_selftests(m);
   pc.lap("self-tests");
   if (rc != KH_OK) {
@@ -837,6 +841,10 @@ extern "C" void* kh_model_stream(kh_model* m) { return m ? (void*)m->stream : nu
 
 extern "C" int kh_model_get_logits(kh_model* m, float* h_logits) {
   if (!m || !h_logits) return KH_ERR_INVALID_ARG;
+  {  // behind a screened step the buffer is refreshed first: k_cls on the step's saved input (kh_cls_screen.h)
+    const int rc = cls_refresh_logits(m);
+    if (rc != KH_OK) return rc;
+  }
   KH_CHECK_HIP(hipMemcpyAsync(h_logits, m->logits, sizeof(float) * m->cfg.vocab_size,
                               hipMemcpyDeviceToHost, m->stream));
   KH_CHECK_HIP(hipStreamSynchronize(m->stream));

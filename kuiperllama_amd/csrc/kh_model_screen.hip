@@ -1,0 +1,303 @@
+// kh_model_screen.hip — host side of the screened classifier (kh_cls_screen.h): the bf16 copy made at model
+// creation, the two launches that take k_cls's and k_sample's slots in the greedy steps of kh_model_generate*,
+// logits on demand behind such steps, the creation-time check, kh_model_cls_screen_info.
+// Replaces nothing in the reference (kuiper/source/model/llama3.cpp:722-745 streams the fp32 classifier every step).
+// gfx950 only.  No CPU fallback: every path below launches HIP kernels.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "kh_cls_screen.h"
+#include "kh_model_internal.h"
+
+namespace khm {
+
+namespace {
+// k_sample_screen<U, MAXV>: U in {2, 4, 8} (k_cls's), MAXV in {1, 2, 4}; k_cls_screen<U, MAXV>: U in {2, 4} (a tile of
+// 8 loads per row, 64 registers of packed weights beside their unpacked halves, does not fit 128 registers)
+#define KH_LSCR(KERNEL, UU, MV, GRID, WG, LDS, STREAM, ARGS)                                \
+  do {                                                                                      \
+    launch_log(#KERNEL "<" #UU "," #MV ">");                                                \
+    hipLaunchKernelGGL((KERNEL<UU, MV>), dim3(GRID), dim3(WG), LDS, STREAM, ARGS);          \
+  } while (0)
+#define KH_LSCR_MV(KERNEL, UU, MV, ...)                    \
+  do {                                                     \
+    if ((MV) == 4)                                         \
+      KH_LSCR(KERNEL, UU, 4, __VA_ARGS__);                 \
+    else if ((MV) == 2)                                    \
+      KH_LSCR(KERNEL, UU, 2, __VA_ARGS__);                 \
+    else                                                   \
+      KH_LSCR(KERNEL, UU, 1, __VA_ARGS__);                 \
+  } while (0)
+#define KH_LSCR_U4(KERNEL, U, MV, ...)                     \
+  do {                                                     \
+    if ((U) >= 4)                                          \
+      KH_LSCR_MV(KERNEL, 4, MV, __VA_ARGS__);              \
+    else                                                   \
+      KH_LSCR_MV(KERNEL, 2, MV, __VA_ARGS__);              \
+  } while (0)
+#define KH_LSCR_U(KERNEL, U, MV, ...)                      \
+  do {                                                     \
+    if ((U) >= 8)                                          \
+      KH_LSCR_MV(KERNEL, 8, MV, __VA_ARGS__);              \
+    else if ((U) >= 4)                                     \
+      KH_LSCR_MV(KERNEL, 4, MV, __VA_ARGS__);              \
+    else                                                   \
+      KH_LSCR_MV(KERNEL, 2, MV, __VA_ARGS__);              \
+  } while (0)
+
+// Launch of k_cls_screen.  u: 16-byte loads per row and lane in flight, one tile per row where it fits (a lane
+// covers 8 weights per load: dim 2048 is 4 loads; longer rows walk several tiles of 4).  A bf16 row pair is half
+// the bytes of k_cls's, so twice the workgroups of k_cls's plan keep the same bytes in flight per CU (measured on
+// Llama-3.2-1B: 83.8 us for 525.8 MB, profiles/cls_screen_ab.txt).  Hook KH_SHAPE_SCREEN="u,grid,wg" overrides.
+void plan_screen(kh_model* m) {
+  const kh_config& c = m->cfg;
+  kh_model::ClsScreen& s = m->scr;
+  const int per_lane = (c.dim / 8 + KH_WAVE - 1) / KH_WAVE;
+  s.u = per_lane >= 3 ? 4 : 2;
+  s.wg = m->sh_cls.wg;
+  const int pairs = (c.vocab_size + 1) / 2, wpw = s.wg / KH_WAVE;
+  const int need = (pairs + wpw - 1) / wpw;
+  const int cap = 1024 * KH_WG / s.wg;  // 16 waves per CU
+  s.grid = 2 * m->sh_cls.grid;
+  if (s.grid > cap) s.grid = cap;
+  if (s.grid > need) s.grid = need;
+  if (const char* ov = dbg("KH_SHAPE_SCREEN")) {
+    int u = 0, g = 0, w = 0;
+    if (sscanf(ov, "%d,%d,%d", &u, &g, &w) == 3 && (u == 2 || u == 4) && g >= 1 && g <= 4096 &&
+        (w == 256 || w == 512) && kh_stage_maxv(c.dim, w) >= 1 && kh_stage_maxv(c.dim, w) <= 4) {
+      s.u = u;
+      s.grid = g;
+      s.wg = w;
+    } else {
+      fprintf(stderr, "[kh] KH_SHAPE_SCREEN=\"%s\" rejected (u 2/4, grid 1..4096, wg 256/512): planned shape\n", ov);
+    }
+  }
+}
+}  // namespace
+
+bool cls_screen_wanted(const kh_model* m) {
+  // the sampling kernel needs every logit; a KH_SHAPE_CLS hook asks for a specific k_cls launch (the rule of plan_ring)
+  return m->scr.on && !m->samp_on && !dbg_off("KH_CLS_SCREEN") && !dbg("KH_SHAPE_CLS");
+}
+
+void cls_screen_release(kh_model* m) {
+  kh_model::ClsScreen& s = m->scr;
+  for (void* q : {(void*)s.wbf, (void*)s.err, (void*)s.x_save, (void*)s.p_lb, (void*)s.p_spill, (void*)s.p_ub,
+                  (void*)s.p_idx, (void*)s.ov_val, (void*)s.ov_idx, (void*)s.ticket, (void*)s.stats})
+    if (q) (void)hipFree(q);
+  s = kh_model::ClsScreen();
+}
+
+int cls_screen_create(kh_model* m) {
+  const kh_config& c = m->cfg;
+  kh_model::ClsScreen& s = m->scr;
+  s = kh_model::ClsScreen();
+  // fp32 models whose rows keep 16-byte alignment as bf16 and whose vector k_cls stages in registers; int8
+  // classifiers are a fiftieth of their token and stay as they are
+  if (c.is_quant || (m->opts.flags & KH_FLAG_NO_CLS_SCREEN) || dbg_off("KH_CLS_SCREEN") || dbg("KH_SHAPE_CLS")) return KH_OK;
+  if (c.dim % 8 != 0 || c.vocab_size < 2) return KH_OK;
+  const int mv = kh_stage_maxv(c.dim, m->sh_cls.wg);
+  if (mv < 1 || mv > 4) return KH_OK;
+  plan_screen(m);
+  {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->opts.device) != hipSuccess || cus <= 0)
+      cus = 256;
+    const int wpw = m->sh_cls.wg / KH_WAVE, need = ((c.vocab_size + 1) / 2 + wpw - 1) / wpw;
+    s.sgrid = cus < need ? cus : need;
+  }
+  int rc;
+  const size_t V = (size_t)c.vocab_size;
+#define KH_ALLOC(ptr, n)                         \
+  if ((rc = dalloc(&(ptr), (n))) != KH_OK) {     \
+    cls_screen_release(m);                       \
+    return rc;                                   \
+  }
+  KH_ALLOC(s.wbf, V * (size_t)c.dim);
+  KH_ALLOC(s.err, V);
+  KH_ALLOC(s.x_save, (size_t)c.dim);
+  // sized for every grid a KH_SHAPE_SCREEN hook may ask for
+  KH_ALLOC(s.p_lb, 4096);
+  KH_ALLOC(s.p_spill, 4096);
+  KH_ALLOC(s.p_ub, 4096 * KH_SCR_C);
+  KH_ALLOC(s.p_idx, 4096 * KH_SCR_C);
+  KH_ALLOC(s.ov_val, (size_t)s.sgrid);
+  KH_ALLOC(s.ov_idx, (size_t)s.sgrid);
+  KH_ALLOC(s.ticket, 1);
+  KH_ALLOC(s.stats, 4);
+#undef KH_ALLOC
+  s.bytes = V * (size_t)c.dim * sizeof(uint16_t) + V * sizeof(float);
+  hipStream_t st = m->stream;
+  KH_CHECK_HIP(hipMemsetAsync(s.ticket, 0, sizeof(uint32_t), st));
+  KH_CHECK_HIP(hipMemsetAsync(s.stats, 0, 4 * sizeof(int32_t), st));
+  KH_CHECK_HIP(hipMemsetAsync(s.x_save, 0, sizeof(float) * (size_t)c.dim, st));
+  const int n = (c.dim + KH_WAVE - 1) / KH_WAVE + 8;  // roundings a term passes through (kh_cls_screen.h)
+  const double u = 1.0 / 16777216.0;
+  const double gam2 = 2.0 * (n * u) / (1.0 - n * u);
+  KH_CHECK_HIP(hipEventRecord(m->ev0, st));
+  hipLaunchKernelGGL(k_cls_bf16_build, dim3(2048), dim3(KH_WG), 0, st, (const float*)m->cls.w, (uint32_t*)s.wbf, s.err,
+                     c.dim, c.vocab_size, gam2);
+  KH_CHECK_HIP(hipEventRecord(m->ev1, st));
+  KH_CHECK_HIP(hipEventSynchronize(m->ev1));
+  if ((rc = kh_launch_status()) != KH_OK) return rc;
+  KH_CHECK_HIP(hipEventElapsedTime(&s.build_ms, m->ev0, m->ev1));
+  s.on = true;
+  if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
+    fprintf(stderr, "[kh] classifier screen: bf16 copy %.1f MB in %.2f ms; k_cls_screen u %d grid %d wg %d, "
+                    "k_sample_screen grid %d wg %d\n", (double)s.bytes / 1e6, s.build_ms, s.u, s.grid, s.wg, s.sgrid,
+            m->sh_cls.wg);
+  return KH_OK;
+}
+
+void launch_cls_screen(kh_model* m) {
+  const kh_config& c = m->cfg;
+  const kh_model::ClsScreen& s = m->scr;
+  KhClsScreenArgs a;
+  a.x = m->x;
+  a.final_norm = m->final_norm;
+  a.wbf = s.wbf;
+  a.err = s.err;
+  a.x_save = s.x_save;
+  a.p_lb = s.p_lb;
+  a.p_spill = s.p_spill;
+  a.p_ub = s.p_ub;
+  a.p_idx = s.p_idx;
+  a.dbg_lb = s.dbg_lb;
+  a.dbg_ub = s.dbg_ub;
+  a.dim = c.dim;
+  a.vocab = c.vocab_size;
+  a.eps = c.rms_eps;
+  KH_LSCR_U4(k_cls_screen, s.u, kh_stage_maxv(c.dim, s.wg), s.grid, s.wg, cls_screen_lds_bytes(c.dim), m->stream, a);
+}
+
+void launch_sample_screen(kh_model* m, int advance, int n_forced) {
+  const kh_config& c = m->cfg;
+  const kh_model::ClsScreen& s = m->scr;
+  KhSampleScreenArgs a;
+  a.p_lb = s.p_lb;
+  a.p_spill = s.p_spill;
+  a.p_ub = s.p_ub;
+  a.p_idx = s.p_idx;
+  a.nsp = s.grid;
+  a.x_save = s.x_save;
+  a.final_norm = m->final_norm;
+  a.wcls = (const float*)m->cls.w;
+  a.eps = c.rms_eps;
+  a.ov_val = s.ov_val;
+  a.ov_idx = s.ov_idx;
+  a.ticket = s.ticket;
+  a.stats = s.stats;
+  a.forced = n_forced > 0 ? m->d_forced : nullptr;
+  a.n_forced = n_forced;
+  a.words = m->d_words;
+  a.words_cap = m->seq_cap;
+  a.d_next = m->d_next;
+  a.d_token = m->d_token;
+  a.d_pos = m->d_pos;
+  a.tok_emb = m->tok_emb;
+  a.x = m->x;
+  a.dim = c.dim;
+  a.vocab = c.vocab_size;
+  a.advance = advance;
+  // k_cls's own U, staging depth and workgroup width: the re-scored values are then k_cls's, bit for bit
+  const int wg = m->sh_cls.wg;
+  KH_LSCR_U(k_sample_screen, m->sh_cls.u, kh_stage_maxv(c.dim, wg), s.sgrid, wg, cls_lds_bytes(false, c.dim), m->stream, a);
+}
+
+int cls_refresh_logits(kh_model* m) {
+  if (!m->scr.stale) return KH_OK;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  float* const x = m->x;
+  m->x = m->scr.x_save;  // the input the last screened step saw; today's k_cls instantiation on the same bytes
+  launch_cls(m);         // (clears scr.stale)
+  m->x = x;
+  return kh_launch_status();
+}
+
+namespace {
+// *flag |= some logit outside its interval (a NaN logit has the interval (-inf, +inf))
+__global__ __launch_bounds__(KH_WG) void k_st_interval(const float* lg, const float* lb, const float* ub, size_t n,
+                                                      int32_t* flag) {
+  bool d = false;
+  for (size_t i = (size_t)blockIdx.x * KH_WG + threadIdx.x; i < n; i += (size_t)gridDim.x * KH_WG) {
+    const float v = lg[i];
+    d |= v == v ? !(lb[i] <= v && v <= ub[i]) : !(lb[i] == -INFINITY && ub[i] == INFINITY);
+  }
+  if (d) *flag = 1;
+}
+}  // namespace
+
+// One screened step against one full step on a fixed vector (the embedding row of token 1): the same token, every
+// full logit inside the interval the screen gave its row.  *result: 0 not applicable, 1 passed, -1 failed ->
+// screening off for this model.
+int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
+  const kh_config& c = m->cfg;
+  kh_model::ClsScreen& s = m->scr;
+  *result = 0;
+  if (!s.on) return KH_OK;
+  hipStream_t st = m->stream;
+  const size_t V = (size_t)c.vocab_size;
+  int rc = KH_OK;
+  int32_t tok[2] = {-1, -2};
+  if ((rc = dalloc(&s.dbg_lb, V)) == KH_OK && (rc = dalloc(&s.dbg_ub, V)) == KH_OK) {
+    set_state(m, 1 % c.vocab_size, 0);
+    s.now = true;
+    launch_cls_screen(m);
+    launch_sample(m, /*advance=*/0, /*n_forced=*/0);
+    s.now = false;
+    hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    launch_cls(m);
+    launch_sample(m, 0, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    const size_t g = (V + KH_WG - 1) / KH_WG;
+    hipLaunchKernelGGL(k_st_interval, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(KH_WG), 0, st, m->logits, s.dbg_lb,
+                       s.dbg_ub, V, d_flag);
+    int32_t flag = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = (int)e;
+    if (rc == KH_OK) rc = kh_launch_status();
+    if (rc == KH_OK) *result = (flag || tok[0] != tok[1] || inject) ? -1 : 1;
+  }
+  if (s.dbg_lb) (void)hipFree(s.dbg_lb);
+  if (s.dbg_ub) (void)hipFree(s.dbg_ub);
+  s.dbg_lb = s.dbg_ub = nullptr;
+  if (rc != KH_OK) return rc;
+  KH_CHECK_HIP(hipMemsetAsync(s.stats, 0, 4 * sizeof(int32_t), st));  // the counters describe the user's steps
+  if (*result < 0) {
+    fprintf(stderr, "[kh] classifier screen self-test failed (tokens %d / %d): screening is off for this model\n",
+            tok[0], tok[1]);
+    cls_screen_release(m);  // the copy's HBM goes back
+    s.selftest = -1;
+  } else {
+    s.selftest = 1;
+  }
+  return KH_OK;
+}
+
+}  // namespace khm
+using namespace khm;
+
+// out[8]: 0 screening on | 1 self-test (0 / 1 / -1) | 2 HBM bytes of the bf16 copy and its row table |
+// 3 microseconds the conversion took | 4 screened steps so far | 5 candidate rows re-scored in them |
+// 6 steps that overflowed into the full classifier | 7 candidate capacity of a step
+extern "C" int kh_model_cls_screen_info(kh_model* m, int64_t* out) {
+  if (!m || !out) return KH_ERR_INVALID_ARG;
+  const kh_model::ClsScreen& s = m->scr;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = s.on ? 1 : 0;
+  out[1] = s.selftest;
+  out[2] = (int64_t)s.bytes;
+  out[3] = (int64_t)(s.build_ms * 1000.f);
+  out[7] = KH_SCR_CAND;
+  if (s.on) {
+    int32_t h[4] = {0, 0, 0, 0};
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    KH_CHECK_HIP(hipMemcpyAsync(h, s.stats, sizeof(h), hipMemcpyDeviceToHost, m->stream));
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    out[4] = h[0];
+    out[5] = h[1];
+    out[6] = h[2];
+  }
+  return KH_OK;
+}

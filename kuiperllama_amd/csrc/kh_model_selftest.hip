@@ -11,12 +11,16 @@
 //      reference, KH_SELFTEST_ATTN_LAUNCHES back-to-back fence-free launches of the same merge (per-head path and,
 //      where the geometry has one, the GQA group path) must reproduce it word for word.  A mismatch makes this
 //      model use the fenced form (kh_config.attn_merge_selftest = -1).
+//  (c) the screened classifier of the greedy generate loop (kh_cls_screen.h; kh_model_screen.hip::cls_screen_selftest):
+//      one screened step against one full step on a fixed vector - the same token, every full logit inside the
+//      interval the screen gave its row.  A failure turns screening off for this model, frees the bf16 copy and says
+//      so on stderr (kh_model_cls_screen_info reports -1).
 //
 // Both run on scratch state the model owns at that moment (activation buffers, rows of layer 0 of the still
 // empty KV cache, which are zeroed again) in about a millisecond.  This is a tripwire for a part, a compiler or a
 // partition mode on which the suite never ran - a race that shows once in a million launches will not trip it.
 // Hooks (kh_debug_set / KH_* environment at load): KH_SELFTEST=0 skips both; KH_SELFTEST_FAIL="ring", "attn" or
-// "ring,attn" reports the named comparison as failed (fault injection: tests/test_model_gpu.py checks that the
+// "ring,attn" (also "screen") reports the named comparison as failed (fault injection: tests/test_model_gpu.py checks that the
 // fallbacks engage and that decode still matches the oracle).
 // Replaces nothing in the reference (it has neither path); cf. kuiper/source/op/kernels/cuda/matmul_kernel.cu:56-87,
 // mha_kernel.cu:47-130 for the kernels these paths stand in for.
@@ -193,17 +197,18 @@ int run_selftests(kh_model* m) {
   const auto t0 = std::chrono::steady_clock::now();
   const char* inj = dbg("KH_SELFTEST_FAIL");
   int32_t* d_flag = nullptr;
-  KH_CHECK_HIP(hipMalloc((void**)&d_flag, 2 * sizeof(int32_t)));
-  int r = 0, a = 0;
-  const hipError_t e = hipMemsetAsync(d_flag, 0, 2 * sizeof(int32_t), m->stream);
+  KH_CHECK_HIP(hipMalloc((void**)&d_flag, 3 * sizeof(int32_t)));
+  int r = 0, a = 0, sc = 0;
+  const hipError_t e = hipMemsetAsync(d_flag, 0, 3 * sizeof(int32_t), m->stream);
   int rc = e == hipSuccess ? ring_selftest(m, d_flag, hook_has(inj, "ring"), &r) : (int)e;
   if (rc == KH_OK) rc = attn_selftest(m, d_flag + 1, hook_has(inj, "attn"), &a);
+  if (rc == KH_OK) rc = cls_screen_selftest(m, d_flag + 2, hook_has(inj, "screen"), &sc);
   (void)hipFree(d_flag);
   if (rc != KH_OK) return rc;
   m->cfg.ring_selftest = r;
   m->cfg.attn_merge_selftest = a;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
-    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d (%.2f ms)\n", r, a,
+    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d, classifier screen %d (%.2f ms)\n", r, a, sc,
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return KH_OK;
 }

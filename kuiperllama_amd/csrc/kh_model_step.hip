@@ -377,6 +377,7 @@ void launch_w2(kh_model* m, int l) {
 }
 void launch_cls(kh_model* m) {
   const kh_config& c = m->cfg;
+  m->scr.stale = false;  // (a generate that replays captured steps keeps this flag itself)
   KhClsArgs a;
   a.x = m->x;
   a.final_norm = m->final_norm;
@@ -400,6 +401,10 @@ void launch_cls(kh_model* m) {
 }
 void launch_sample(kh_model* m, int advance, int n_forced) {
   const kh_config& c = m->cfg;
+  if (m->scr.now && !m->samp_on) {
+    launch_sample_screen(m, advance, n_forced);
+    return;
+  }
   KhSampleArgs a;
   a.part_val = m->part_val;
   a.part_idx = m->part_idx;
@@ -480,7 +485,10 @@ void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, i
     launch_w2(m, l);
     mark();
   }
-  launch_cls(m);
+  if (m->scr.now && !m->samp_on)
+    launch_cls_screen(m);  // k_cls's slot: still 5L + 2 launches
+  else
+    launch_cls(m);
   mark();
   launch_sample(m, advance, n_forced);
   mark();
@@ -597,7 +605,7 @@ int step_graph_n(kh_model* m, int n_forced, int variant, int nsteps, hipGraphExe
   if (variant < 0 || variant >= KH_STEP_VARIANTS) return KH_ERR_INVALID_ARG;
   const int k = nsteps == 1 ? 0 : nsteps == 2 ? 1 : nsteps == 4 ? 2 : nsteps == KH_GRAPH_STEPS ? 3 : -1;
   if (k < 0) return KH_ERR_INVALID_ARG;
-  kh_model::StepGraph& sg = m->sg[m->samp_on ? 1 : 0][variant][k];  // captured with the sampler now in use
+  kh_model::StepGraph& sg = m->sg[sg_sampler(m)][variant][k];  // captured with the sampler now in use
   if (!sg.e) {
     const int rc = capture_steps(m, n_forced, nsteps, variant, &sg.g, &sg.e);
     if (rc != KH_OK) return rc;
@@ -606,6 +614,8 @@ int step_graph_n(kh_model* m, int n_forced, int variant, int nsteps, hipGraphExe
     // clock where repeated runs gave 1060)
     (void)hipGraphUpload(sg.e, m->stream);
   }
+  // every replay fetches its graph here: behind it the logits buffer is as old as the last full classifier launch
+  m->scr.stale = m->scr.now;
   *out = sg.e;
   return KH_OK;
 }
@@ -716,6 +726,7 @@ extern "C" int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t
   int rc = kv_ensure(m, pos + 1);  // cache rows 0 .. pos backed by HBM before the step is enqueued
   if (rc != KH_OK) return rc;
   set_state(m, token, pos);  // embedding() + fill_input (llama3.cpp:578-598, model.cpp:245-263)
+  m->scr.stale = false;      // a single step always runs the full classifier
   if (exec == KH_EXEC_UNFUSED) {
     rc = launch_step_unfused(m, pos);
   } else if (exec == KH_EXEC_FUSED || exec == KH_EXEC_GRAPH) {
@@ -809,6 +820,14 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
   }
   if (exec != KH_EXEC_GRAPH && exec != KH_EXEC_FUSED) return KH_ERR_INVALID_ARG;
 
+  // greedy steps run the screened classifier pair (kh_cls_screen.h) wherever the model has one; m->scr.now says
+  // which pair the launches enqueued or captured right now use, and is off again on every way out
+  const bool screen = cls_screen_wanted(m);
+  struct ScreenOff {
+    kh_model* m;
+    ~ScreenOff() { m->scr.now = false; }
+  } screen_off{m};
+  m->scr.now = screen;
   if ((rc = ensure_seq_cap(m, total_steps)) != KH_OK) return rc;
   // every cache row this call can reach is backed by HBM before its first launch (the dry launches of fresh graphs
   // below touch rows 0 .. 7); mapping happens here, on the host, outside the event bracket of the step loop
@@ -851,7 +870,7 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
     bool fresh[4] = {false, false, false, false};
     hipGraphExec_t ge = nullptr;
     for (int n = 1, k = 0; n <= KH_GRAPH_STEPS; n *= 2, ++k) {
-      fresh[k] = m->sg[m->samp_on ? 1 : 0][0][k].e == nullptr;
+      fresh[k] = m->sg[sg_sampler(m)][0][k].e == nullptr;
       if ((rc = step_graph_n(m, n_forced, 0, n, &ge)) != KH_OK) return rc;
     }
     bool dry = false;
@@ -859,11 +878,12 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
       for (int k = 3; k >= 0; --k)
         if (fresh[k]) {
           set_state(m, h_prompt[0], 0);
-          KH_CHECK_HIP(hipGraphLaunch(m->sg[m->samp_on ? 1 : 0][0][k].e, m->stream));
+          KH_CHECK_HIP(hipGraphLaunch(m->sg[sg_sampler(m)][0][k].e, m->stream));
           dry = true;
         }
     if (dry) KH_CHECK_HIP(hipStreamSynchronize(m->stream));
   }
+  m->scr.now = false;  // the prompt phase below launches the full classifier; launch_chunk decides per chunk
 
   // prompt phase: the tokens that are only fed (positions 0 .. n_prompt-2).  KH_PREFILL selects how:
   //   "0" / "token"  the reference's one forward pass per prompt token (demo/main.cpp:20-22)
@@ -910,6 +930,8 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
       while (n > total_steps - s) n >>= 1;
       const bool keep = s == start && start > 0;  // first sampled step behind a prefill: alone, logits kept
       if (keep) n = 1;
+      m->scr.now = screen && !keep;  // the kept step leaves its logits in the buffer: full classifier
+      m->scr.stale = m->scr.now;
       hipGraphExec_t ge = nullptr;
       if (step_graph_n(m, n_forced, step_variant(m, s, s + n - 1), n, &ge) != KH_OK) return -1;
       if (hipGraphLaunch(ge, m->stream) != hipSuccess) return -1;
@@ -918,7 +940,9 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
         return -1;
       return n;
     }
+    m->scr.now = screen && !(s == start && start > 0);
     launch_step_fused(m, 1, n_forced, nullptr, step_variant(m, s, s));
+    m->scr.stale = m->scr.now;
     if (s == start && start > 0 &&
         hipMemcpyAsync(m->first_logits, m->logits, sizeof(float) * (size_t)c.vocab_size, hipMemcpyDeviceToDevice,
                        m->stream) != hipSuccess)

@@ -124,6 +124,14 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_get_logits(self._h, out.ctypes.data), "kh_model_get_logits")
         return out
 
+    def cls_screen_info(self) -> dict:
+        """The screened classifier of the greedy generate loop (kh_model_cls_screen_info): whether it is on, its
+        creation-time self-test, the HBM bytes and creation time of the bf16 copy, and counters since creation."""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_cls_screen_info(self._h, out), "kh_model_cls_screen_info")
+        keys = ("on", "selftest", "bytes", "build_us", "steps", "candidates", "overflow_steps", "capacity")
+        return dict(zip(keys, (int(v) for v in out)))
+
     def kv_bytes(self) -> Tuple[int, int]:
         """(reserved, committed) bytes of the KV cache: the address range of the reference's up-front allocation and
         the HBM backing it right now (mapped on demand, kh_model_kv_bytes)."""
