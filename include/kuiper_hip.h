@@ -386,7 +386,7 @@ int kh_plan_decode_ring(int32_t dim, int32_t hidden_dim, int32_t vocab_size, int
 /* kh_plan_attention: the decode-attention geometry of kh_mha_decode_f32 / the fused step for a cache of seq_len rows:
  * out8 = {time splits per head, splits per KV group (0: no group path), workspace slot stride, first pos + 1 of the
  * group path, path taken at `pos` (0 per-head, 1 group), active splits at `pos`, timesteps per split at `pos`,
- * workgroups that own timesteps at `pos`} (KH_ATTN_TLONG honoured). */
+ * workgroups that own timesteps at `pos`} (KH_ATTN_TLONG, KH_ATTN_TS and KH_ATTN_WG honoured). */
 int kh_plan_attention(int32_t head_num, int32_t kv_mul, int32_t head_size, int32_t seq_len, int32_t pos,
                       int32_t* out8);
 int kh_plan_prefill_shape(int32_t epi, int32_t T, int32_t rows, int32_t K, int32_t is_quant,
@@ -404,7 +404,12 @@ const char* kh_debug_get(const char* key); /* NULL when unset */
 int64_t kh_debug_list(char* buf, int64_t cap); /* '\n'-separated names; returns bytes needed */
 /* Launch log.  While hook KH_LAUNCH_LOG is set (to anything but "0"), every fused decode-step, B-token prefill and
  * GEMM prefill launch adds the name of the kernel instantiation it launches ("k_gemv_res<true,3,6,2>",
- * "k_pg_gemm<false,2,8,1>", "k_pg_rope") to a process-wide set;
+ * "k_pg_gemm<false,2,8,1>", "k_pg_rope") to a process-wide set.  Decode attention adds "k_attn_decode<16,7>" (lanes
+ * per timestep, heads per KV-group workgroup; 0 = per-head only) and one record of the launch's host-side variant,
+ * "attn_launch<wg,ts_shift,defer,fenced,ntok>1?,group_grid?>" (workgroup width - hook KH_ATTN_WG = 256 | 512, which
+ * kh_mha_decode_f32, kh_mha_decode_workspace_bytes and kh_plan_attention honour like kh_model_create_* -, log2 of the
+ * split quantum, partials left to the wo kernel, fenced merge, several tokens per launch, grid carries the GQA group
+ * path); the small-head kernel and kh_mha_f32's score kernel add "k_attn_generic" / "k_mha";
  * setting, resetting or unsetting the hook (kh_debug_set) empties it.  kh_debug_launch_log: the names,
  * '\n'-separated and sorted, into buf (always NUL-terminated); returns the bytes needed. */
 int64_t kh_debug_launch_log(char* buf, int64_t cap);

@@ -14,6 +14,7 @@
 // the output over its timesteps, then timestep-groups are folded with shuffles + one LDS
 // exchange across the 4 waves.
 #pragma once
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "kh_common.h"
@@ -1027,6 +1028,17 @@ static inline int attn_tlong_hook() {
   const char* e = khm::dbg("KH_ATTN_TLONG");
   return e ? atoi(e) : -1;
 }
+// KH_ATTN_WG hook (256 | 512) -> threads per decode-attention workgroup; default KH_WG_MAX: 8 waves per (head, split)
+// shorten each lane's timestep loop.  The ONE reader (model level: finish_create; operator level: kh_mha_decode_f32,
+// its workspace size and kh_plan_attention), so that plan, workspace and launch agree - attn_group_supported depends
+// on the width.
+static inline int attn_wg_hook() {
+  if (const char* e = khm::dbg("KH_ATTN_WG")) {
+    const int v = atoi(e);
+    if (v == 256 || v == 512) return v;
+  }
+  return KH_WG_MAX;
+}
 
 // Launch.  a.nsplit_g == 0 disables the group path; head_size > 32 required (callers route
 // smaller heads to the generic LDS-score kernel).
@@ -1072,8 +1084,20 @@ static inline void launch_attn_decode(KhAttnArgs a, int host_pos, int wg, hipStr
     if (l2 > lds) lds = l2;
   }
   if (grid < 1) grid = 1;
-#define KH_ATTN_LAUNCH(GG, KK) \
-  hipLaunchKernelGGL((k_attn_decode<GG, KK>), dim3(grid, ntok), dim3(wg), lds, s, a, host_pos)
+  // launch log (hook KH_LAUNCH_LOG, kh_common.h): the literal instantiation, and one record of the host-side variant
+  // of the launch - "attn_launch<wg,ts_shift,defer,fenced,ntok>1?,group_grid?>" - built only while the log is on
+  const bool logging = khm::g_launch_log_on.load(std::memory_order_relaxed);
+  if (logging) {
+    char rec[96];
+    snprintf(rec, sizeof rec, "attn_launch<%d,%d,%d,%d,%d,%d>", wg, a.ts_shift, a.defer ? 1 : 0, a.fenced ? 1 : 0,
+             ntok > 1 ? 1 : 0, grp ? 1 : 0);
+    khm::launch_log_add(rec);
+  }
+#define KH_ATTN_LAUNCH(GG, KK)                                                                        \
+  do {                                                                                                \
+    if (logging) khm::launch_log_add("k_attn_decode<" #GG "," #KK ">");                               \
+    hipLaunchKernelGGL((k_attn_decode<GG, KK>), dim3(grid, ntok), dim3(wg), lds, s, a, host_pos);     \
+  } while (0)
   const int kvm = grp ? a.kv_mul : 0;
   if (G == 16) {
     switch (kvm) {

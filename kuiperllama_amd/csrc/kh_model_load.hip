@@ -538,9 +538,7 @@ int finish_create(kh_model* m, SinCosJob* sincos = nullptr) {
       fprintf(stderr, "[kh] shape %-5s split %d u %d grid %d wg %d\n", e.n, e.s->split, e.s->u, e.s->grid, e.s->wg);
   }
   // attention: 8 waves per (head, split) shorten each lane's timestep loop
-  m->attn_wg = KH_WG_MAX;
-  if (const char* e = dbg("KH_ATTN_WG"))
-    if (atoi(e) == 256 || atoi(e) == 512) m->attn_wg = atoi(e);
+  m->attn_wg = attn_wg_hook();
   {
     const AttnPlan ap = attn_plan(c.head_num, c.kv_mul, c.head_size, c.cache_len, m->attn_wg, attn_tlong_hook());
     m->attn_ns = ap.ns;

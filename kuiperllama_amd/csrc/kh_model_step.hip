@@ -272,9 +272,11 @@ void launch_attn(kh_model* m, int l) {
   const int wg = m->attn_wg;
   if (c.head_size > 32)
     launch_attn_decode(a, 0, wg, m->stream);
-  else  // head_size <= 32: generic LDS-score kernel (tiny test models)
+  else {  // head_size <= 32: generic LDS-score kernel (tiny test models)
+    launch_log("k_attn_generic");
     hipLaunchKernelGGL(k_attn_generic, dim3(c.head_num), dim3(wg),
                        attn_lds_bytes(c.head_size, wg), m->stream, a);
+  }
 }
 KhGemvResArgs fill_wo(kh_model* m, int l) {
   const kh_config& c = m->cfg;

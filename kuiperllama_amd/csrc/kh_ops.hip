@@ -477,7 +477,7 @@ static int launch_mha_fast(const int32_t* d_pos, int32_t pos, int32_t head_num,
                            int32_t layer_index, int32_t seq_len, int32_t kv_dim, int32_t kv_mul,
                            int32_t head_size, float* mha_out, const float* q, const float* kcache,
                            const float* vcache, int nsplit, int nsplit_g, int ws_stride,
-                           int t_long, void* ws, hipStream_t s) {
+                           int t_long, void* ws, int wg, hipStream_t s) {
   const size_t layer_off = (size_t)layer_index * (size_t)seq_len * (size_t)kv_dim;
   KhAttnArgs a;
   a.q = q;
@@ -502,7 +502,7 @@ static int launch_mha_fast(const int32_t* d_pos, int32_t pos, int32_t head_num,
   }
   a.tok_stride = 0;
   a.ws_tok_bytes = 0;
-  launch_attn_decode(a, pos, KH_WG_MAX, s);
+  launch_attn_decode(a, pos, wg, s);
   return kh_launch_status();
 }
 
@@ -521,17 +521,19 @@ extern "C" int kh_mha_f32(const int32_t* d_pos, int32_t pos, int32_t head_num,
     // no score tensor requested: the fused decode path's one-round-trip kernel (kh_attn.h),
     // one workgroup per head (kh_mha_decode_f32 adds the long-context time split)
     return launch_mha_fast(d_pos, pos, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size,
-                           mha_out, q, kcache, vcache, 1, 0, 1, 1 << 30, nullptr, s);
+                           mha_out, q, kcache, vcache, 1, 0, 1, 1 << 30, nullptr, KH_WG_MAX, s);
+  khm::launch_log("k_mha");
   hipLaunchKernelGGL(k_mha, dim3(head_num), dim3(KH_WG), attn_lds_bytes(head_size), s, d_pos,
                      pos, layer_index, seq_len, kv_dim, kv_mul, head_size, mha_out, q, score,
                      kcache, vcache);
   return kh_launch_status();
 }
 
-// Decode attention with the long-context time split (the kernel the fused step launches).
+// Decode attention with the long-context time split (the kernel the fused step launches).  Workgroup width: hook
+// KH_ATTN_WG (attn_wg_hook) - the plan, the workspace size and the launch all take it from here.
 static void mha_decode_geometry(int head_num, int kv_mul, int head_size, int seq_len, int* ns,
                                 int* ns_g, int* stride, int* t_long) {
-  const AttnPlan p = attn_plan(head_num, kv_mul, head_size, seq_len, KH_WG_MAX, attn_tlong_hook());
+  const AttnPlan p = attn_plan(head_num, kv_mul, head_size, seq_len, attn_wg_hook(), attn_tlong_hook());
   *ns = p.ns;
   *ns_g = p.ns_g;
   *stride = p.stride;
@@ -599,7 +601,7 @@ extern "C" int kh_mha_decode_f32(const int32_t* d_pos, int32_t pos, int32_t head
         !kh_aligned16(workspace))))
     return KH_ERR_INVALID_ARG;
   return launch_mha_fast(d_pos, pos, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size,
-                         mha_out, q, kcache, vcache, ns, ns_g, stride, tl, workspace,
+                         mha_out, q, kcache, vcache, ns, ns_g, stride, tl, workspace, attn_wg_hook(),
                          (hipStream_t)stream);
 }
 

@@ -40,6 +40,8 @@
 
 namespace khm {
 const char* dbg(const char*) { return nullptr; }
+std::atomic<bool> g_launch_log_on{false};  // the launch log of launch_attn_decode stays off here
+void launch_log_add(const char*) {}
 }  // namespace khm
 
 #define CK(x)                                                                       \
