@@ -221,7 +221,11 @@ typedef struct kh_model_opts {
  * the copy screens the rows, the rows that can still win are re-scored from their fp32 rows, the tokens are
  * bit for bit those of the full classifier, and kh_model_get_logits behind such a run computes the last step's
  * logits on demand (csrc/kh_cls_screen.h).  This flag - or hook KH_CLS_SCREEN=0 at creation - leaves the copy out;
- * the hook set later turns screening off for the generates that follow.  kh_model_cls_screen_info reports. */
+ * the hook set later turns screening off for the generates that follow.  A KH_SHAPE_CLS hook (a specific k_cls
+ * launch was asked for) does the same, unless KH_CLS_SCREEN=force is set beside it: screening stays on and
+ * re-scores with the hooked U, staging depth and workgroup width (tests reach every k_sample_screen instantiation
+ * this way).  kh_model_cls_screen_info reports; kh_model_cls_screen_probe / _read expose one screened step on a
+ * caller-supplied vector, every row's interval, the bf16 copy and its error table to the tests. */
 #define KH_FLAG_NO_CLS_SCREEN 8
 
 typedef struct kh_config {
@@ -279,6 +283,16 @@ int kh_model_get_logits(kh_model* m, float* h_logits);
  * steps so far, candidate rows re-scored in them, steps that overflowed into the full classifier, candidate
  * capacity of a step */
 int kh_model_cls_screen_info(kh_model* m, int64_t* out8);
+/* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
+ * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave
+ * every row.  out4 = screened token, full classifier's token, candidate rows re-scored, 1 if the step overflowed.
+ * Afterwards kh_model_get_logits returns k_cls's logits of h_x and the counters of kh_model_cls_screen_info are as
+ * before, also behind a failed copy or launch.  Clobbers the model's residual vector, the screen's saved input and
+ * the next-token word: the generate or step that follows sets its own.  KH_ERR_UNSUPPORTED where the model does
+ * not screen. */
+int kh_model_cls_screen_probe(kh_model* m, const float* h_x, float* h_lb, float* h_ub, int64_t* out4);
+/* tests: the bf16 copy of the classifier [vocab x dim] and its per-row error table [vocab] */
+int kh_model_cls_screen_read(kh_model* m, uint16_t* h_wbf, float* h_err);
 /* device pointers of the KV cache [layer, cache_len, kv_dim] (tests) */
 int kh_model_get_kv(kh_model* m, float** d_kcache, float** d_vcache);
 /* bytes of the KV cache: *reserved = the address range of [layer, cache_len, kv_dim] floats x 2 (the reference's

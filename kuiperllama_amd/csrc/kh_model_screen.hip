@@ -5,6 +5,7 @@
 // gfx950 only.  No CPU fallback: every path below launches HIP kernels.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "kh_cls_screen.h"
 #include "kh_model_internal.h"
@@ -75,9 +76,20 @@ void plan_screen(kh_model* m) {
 }
 }  // namespace
 
+namespace {
+// A KH_SHAPE_CLS hook asks for a specific k_cls launch (the rule of plan_ring): screening steps aside - unless
+// KH_CLS_SCREEN=force asks for both (tests: k_sample_screen re-scores with k_cls's U, staging depth and width, and
+// away from the heuristic those change only through that hook).
+bool cls_hook_bars_screen() {
+  if (!dbg("KH_SHAPE_CLS")) return false;
+  const char* v = dbg("KH_CLS_SCREEN");
+  return !(v && strcmp(v, "force") == 0);
+}
+}  // namespace
+
 bool cls_screen_wanted(const kh_model* m) {
-  // the sampling kernel needs every logit; a KH_SHAPE_CLS hook asks for a specific k_cls launch (the rule of plan_ring)
-  return m->scr.on && !m->samp_on && !dbg_off("KH_CLS_SCREEN") && !dbg("KH_SHAPE_CLS");
+  // the sampling kernel needs every logit
+  return m->scr.on && !m->samp_on && !dbg_off("KH_CLS_SCREEN") && !cls_hook_bars_screen();
 }
 
 void cls_screen_release(kh_model* m) {
@@ -94,7 +106,7 @@ int cls_screen_create(kh_model* m) {
   s = kh_model::ClsScreen();
   // fp32 models whose rows keep 16-byte alignment as bf16 and whose vector k_cls stages in registers; int8
   // classifiers are a fiftieth of their token and stay as they are
-  if (c.is_quant || (m->opts.flags & KH_FLAG_NO_CLS_SCREEN) || dbg_off("KH_CLS_SCREEN") || dbg("KH_SHAPE_CLS")) return KH_OK;
+  if (c.is_quant || (m->opts.flags & KH_FLAG_NO_CLS_SCREEN) || dbg_off("KH_CLS_SCREEN") || cls_hook_bars_screen()) return KH_OK;
   if (c.dim % 8 != 0 || c.vocab_size < 2) return KH_OK;
   const int mv = kh_stage_maxv(c.dim, m->sh_cls.wg);
   if (mv < 1 || mv > 4) return KH_OK;
@@ -277,6 +289,71 @@ int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) 
 
 }  // namespace khm
 using namespace khm;
+
+// One screened step and one full step on the caller's residual vector, without advancing (tests): the shape of
+// cls_screen_selftest above, through the same two launch functions a generate uses.  out[4]: screened token | full
+// classifier's token | candidate rows re-scored | 1 if the step overflowed.  h_lb / h_ub: every row's interval.  The
+// logits buffer is left holding k_cls's logits of that vector; the residual vector (m->x), the screen's saved input
+// and d_next are overwritten (the next generate or step sets its own state).  The counters of
+// kh_model_cls_screen_info are put back on every path that got as far as reading them.
+extern "C" int kh_model_cls_screen_probe(kh_model* m, const float* h_x, float* h_lb, float* h_ub, int64_t* out) {
+  if (!m || !h_x || !h_lb || !h_ub || !out) return KH_ERR_INVALID_ARG;
+  kh_model::ClsScreen& s = m->scr;
+  if (!s.on || m->samp_on) return KH_ERR_UNSUPPORTED;
+  const kh_config& c = m->cfg;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  hipStream_t st = m->stream;
+  const size_t V = (size_t)c.vocab_size;
+  int rc = KH_OK;
+  int32_t tok[2] = {-1, -2}, h0[4] = {0, 0, 0, 0}, h1[4] = {0, 0, 0, 0};
+  KH_CHECK_HIP(hipMemcpyAsync(h0, s.stats, sizeof(h0), hipMemcpyDeviceToHost, st));
+  KH_CHECK_HIP(hipStreamSynchronize(st));
+  if ((rc = dalloc(&s.dbg_lb, V)) == KH_OK && (rc = dalloc(&s.dbg_ub, V)) == KH_OK) {
+    hipError_t e = hipMemcpyAsync(m->x, h_x, sizeof(float) * (size_t)c.dim, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      s.now = true;
+      launch_cls_screen(m);
+      launch_sample(m, /*advance=*/0, /*n_forced=*/0);
+      s.now = false;
+      e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+      launch_cls(m);  // (clears scr.stale: kh_model_get_logits returns this launch's logits)
+      launch_sample(m, 0, 0);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_lb, s.dbg_lb, sizeof(float) * V, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_ub, s.dbg_ub, sizeof(float) * V, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h1, s.stats, sizeof(h1), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    // the user's steps: also behind a failed copy or launch (h0 is pageable, so the copy has left it on return)
+    const hipError_t e2 = hipMemcpyAsync(s.stats, h0, sizeof(h0), hipMemcpyHostToDevice, st);
+    const hipError_t e3 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2 != hipSuccess ? e2 : e3;
+    if (e != hipSuccess) rc = (int)e;
+    if (rc == KH_OK) rc = kh_launch_status();
+  }
+  if (s.dbg_lb) (void)hipFree(s.dbg_lb);
+  if (s.dbg_ub) (void)hipFree(s.dbg_ub);
+  s.dbg_lb = s.dbg_ub = nullptr;
+  if (rc != KH_OK) return rc;
+  out[0] = tok[0];
+  out[1] = tok[1];
+  out[2] = h1[1] - h0[1];
+  out[3] = h1[2] - h0[2];
+  return KH_OK;
+}
+
+// the bf16 copy [vocab x dim] and the per-row error table [vocab] (tests)
+extern "C" int kh_model_cls_screen_read(kh_model* m, uint16_t* h_wbf, float* h_err) {
+  if (!m || !h_wbf || !h_err) return KH_ERR_INVALID_ARG;
+  const kh_model::ClsScreen& s = m->scr;
+  if (!s.on) return KH_ERR_UNSUPPORTED;
+  const size_t V = (size_t)m->cfg.vocab_size;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemcpyAsync(h_wbf, s.wbf, sizeof(uint16_t) * V * (size_t)m->cfg.dim, hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipMemcpyAsync(h_err, s.err, sizeof(float) * V, hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
+}
 
 // out[8]: 0 screening on | 1 self-test (0 / 1 / -1) | 2 HBM bytes of the bf16 copy and its row table |
 // 3 microseconds the conversion took | 4 screened steps so far | 5 candidate rows re-scored in them |

@@ -132,6 +132,28 @@ class KuiperModel:
         keys = ("on", "selftest", "bytes", "build_us", "steps", "candidates", "overflow_steps", "capacity")
         return dict(zip(keys, (int(v) for v in out)))
 
+    def cls_screen_probe(self, x: np.ndarray) -> dict:
+        """One screened step and one full-classifier step on the residual vector x[dim], without advancing
+        (kh_model_cls_screen_probe, tests): the two tokens, the candidate rows re-scored, whether the step overflowed,
+        and the interval [lb, ub] the screen gave every row.  logits() afterwards returns k_cls's logits of x."""
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.shape == (self.cfg.dim,)
+        lb = np.empty(self.cfg.vocab_size, np.float32)
+        ub = np.empty(self.cfg.vocab_size, np.float32)
+        out = (C.c_int64 * 4)()
+        _ffi.check(_ffi.lib().kh_model_cls_screen_probe(self._h, x.ctypes.data, lb.ctypes.data, ub.ctypes.data, out),
+                   "kh_model_cls_screen_probe")
+        return {"token": int(out[0]), "full_token": int(out[1]), "candidates": int(out[2]), "overflow": int(out[3]),
+                "lb": lb, "ub": ub}
+
+    def cls_screen_read(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(bf16 copy of the classifier as uint16 [vocab, dim], per-row error table [vocab]): kh_model_cls_screen_read."""
+        wbf = np.empty((self.cfg.vocab_size, self.cfg.dim), np.uint16)
+        err = np.empty(self.cfg.vocab_size, np.float32)
+        _ffi.check(_ffi.lib().kh_model_cls_screen_read(self._h, wbf.ctypes.data, err.ctypes.data),
+                   "kh_model_cls_screen_read")
+        return wbf, err
+
     def kv_bytes(self) -> Tuple[int, int]:
         """(reserved, committed) bytes of the KV cache: the address range of the reference's up-front allocation and
         the HBM backing it right now (mapped on demand, kh_model_kv_bytes)."""

@@ -55,29 +55,45 @@ def _butterfly(v):
     return v[..., 0]
 
 
+class LaneDot:
+    """lane_dot for many vectors against one matrix: the matrix is padded, widened and laid out once."""
+
+    def __init__(self, W, per_load):
+        W = np.asarray(W, dtype=F32)
+        R, K = W.shape
+        assert K % per_load == 0
+        self.R, self.K, self.per_load = R, K, per_load
+        nload = K // per_load
+        self.rounds = (nload + WAVE - 1) // WAVE
+        self.pad = self.rounds * WAVE * per_load
+        Wp = np.zeros((R, self.pad), F32)
+        Wp[:, :K] = W
+        # [round, element of the load, row, lane], fp64: a product of two fp32 values is exact there
+        self.Wp = np.ascontiguousarray(Wp.reshape(R, self.rounds, WAVE, per_load).transpose(1, 3, 0, 2), dtype=np.float64)
+        self.valid = (np.arange(self.pad) < K).reshape(self.rounds, WAVE, per_load)
+
+    def dot(self, g):
+        gp = np.zeros(self.pad, np.float64)
+        gp[:self.K] = np.asarray(g, dtype=F32)
+        gp = gp.reshape(self.rounds, WAVE, self.per_load)
+        acc = np.zeros((self.R, WAVE), np.float64)  # fp32 values
+        for j in range(self.rounds):
+            for e in range(self.per_load):
+                with np.errstate(all="ignore"):
+                    nxt = (self.Wp[j, e] * gp[j, :, e][None, :] + acc).astype(F32)
+                v = self.valid[j, :, e]
+                if v.all():
+                    acc = nxt.astype(np.float64)
+                else:
+                    acc[:, v] = nxt[:, v]
+        return _butterfly(acc.astype(F32))
+
+
 def lane_dot(W, g, per_load):
     """The sum a wave forms for every row of W (fp32 values; bf16 rows are passed widened): lane l takes the loads
     l, l + 64, ... of `per_load` consecutive weights each (4: k_cls's float4, 8: k_cls_screen's eight bf16) and runs one
     FMA chain over them, then the butterfly.  Lanes past the end add exact zeros (skipped here)."""
-    W = np.asarray(W, dtype=F32)
-    R, K = W.shape
-    assert K % per_load == 0
-    nload = K // per_load
-    rounds = (nload + WAVE - 1) // WAVE
-    pad = rounds * WAVE * per_load
-    Wp = np.zeros((R, pad), F32)
-    Wp[:, :K] = W
-    gp = np.zeros(pad, F32)
-    gp[:K] = g
-    Wp = Wp.reshape(R, rounds, WAVE, per_load)
-    gp = gp.reshape(rounds, WAVE, per_load)
-    valid = (np.arange(pad) < K).reshape(rounds, WAVE, per_load)
-    acc = np.zeros((R, WAVE), F32)
-    for j in range(rounds):
-        for e in range(per_load):
-            nxt = _fma(Wp[:, j, :, e], np.broadcast_to(gp[j, :, e], (R, WAVE)), acc)
-            acc = np.where(valid[j, :, e][None, :], nxt, acc)
-    return _butterfly(acc)
+    return LaneDot(W, per_load).dot(g)
 
 
 def stage(x, wnorm, eps, wg):
@@ -144,3 +160,42 @@ def screened_argmax(logits, lb, ub, cap):
         return int(np.argmax(np.where(np.isnan(logits), -np.inf, logits))), cand.size, True
     v = np.where(np.isnan(logits[cand]), -np.inf, logits[cand])
     return int(cand[np.argmax(v)]), cand.size, False
+
+
+def bf16_bits(w):
+    """The 16 stored bits of bf16_rne(w), as k_cls_bf16_build writes them."""
+    return (bf16_rne(w).view(np.uint32) >> 16).astype(np.uint16)
+
+
+def err_exact64(W):
+    """|w - bf16(w)|_2 + 2 gamma_n (|w|_2 + |bf16(w)|_2) per row in fp64, without the (1 + 1e-9) factor and without the
+    rounding up to fp32: what every stored e[r] must reach.  inf for rows with a non-finite weight or bf16 weight."""
+    W = np.asarray(W, dtype=F32)
+    W64, B64 = W.astype(np.float64), bf16_rne(W).astype(np.float64)
+    with np.errstate(all="ignore"):
+        e = np.sqrt(((W64 - B64) ** 2).sum(1)) + gamma2(W.shape[1]) * (np.sqrt((W64 ** 2).sum(1)) + np.sqrt((B64 ** 2).sum(1)))
+    return np.where(e < np.inf, e, np.inf)
+
+
+def gold_logits64(W, x, wnorm, eps):
+    """The classifier in fp64 on the fp32 inputs: (W (wnorm o x)) / sqrt(mean(x^2) + eps)."""
+    x64 = np.asarray(x, dtype=F32).astype(np.float64)
+    g64 = np.asarray(wnorm, dtype=F32).astype(np.float64) * x64
+    with np.errstate(all="ignore"):
+        return (np.asarray(W, dtype=F32).astype(np.float64) @ g64) / np.sqrt((x64 * x64).mean() + float(eps))
+
+
+def bf16_row_norms(W):
+    """|bf16(w_r)|_2 per row, fp64."""
+    with np.errstate(all="ignore"):
+        return np.sqrt((bf16_rne(W).astype(np.float64) ** 2).sum(1))
+
+
+def twin_tolerance(nb, K, g, rs, b):
+    """tau_r = 2 gamma_n rs |bf16(w_r)|_2 |g|_2 + 2^-5 b_r (nb = bf16_row_norms, K the row length): how far the GPU's
+    lb / ub may lie from the twin's.  Both are fp32 sums of the same products in a valid order (first term: each within
+    gamma_n of the exact sum); lb / ub are fp32 roundings of a -+ b, and for a row that is exact in bf16 b can be as
+    small as 2^-18 |a| (second term)."""
+    with np.errstate(all="ignore"):
+        ng = np.sqrt((np.asarray(g, dtype=F32).astype(np.float64) ** 2).sum())
+        return gamma2(K) * float(rs) * nb * ng + 2.0 ** -5 * b.astype(np.float64)

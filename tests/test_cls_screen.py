@@ -110,3 +110,46 @@ def test_argmax_from_the_intervals_is_the_argmax_of_the_logits(K):
     logits, lb, ub, _ = R.screen_and_logits(W, x, np.zeros(K, F32))
     tok, n, over = R.screened_argmax(logits, lb, ub, cap=32)
     assert over and n == W.shape[0] and tok == 0 and np.all(logits == 0)
+
+
+def test_lane_dot_layout_cache_is_the_plain_formula():
+    """cls_screen_R.LaneDot lays the matrix out once for many vectors; its sums are those of the plain formula
+    (pad, one fp32 FMA per weight and lane with the lanes past the end skipped, the butterfly), bit for bit, on rows
+    with NaN, Inf and huge weights, at a row length that ends inside a round of loads, for both load widths."""
+    rng = np.random.default_rng(5)
+    K = 1152 + 64
+    W = rng.normal(0.0, 0.05, (9, K)).astype(F32)
+    W[1, 7] = np.nan
+    W[2, K - 1] = np.inf
+    W[3, 100] = -np.inf
+    W[4, 5] = F32(3.4e38)
+    W[5] = 0
+    g = rng.normal(0.0, 1.0, K).astype(F32)
+    g[::61] *= 50
+
+    def plain(W, g, per_load):
+        n, K = W.shape
+        rounds = (K // per_load + R.WAVE - 1) // R.WAVE
+        pad = rounds * R.WAVE * per_load
+        Wp = np.zeros((n, pad), F32)
+        Wp[:, :K] = W
+        gp = np.zeros(pad, F32)
+        gp[:K] = g
+        Wp = Wp.reshape(n, rounds, R.WAVE, per_load)
+        gp = gp.reshape(rounds, R.WAVE, per_load)
+        valid = (np.arange(pad) < K).reshape(rounds, R.WAVE, per_load)
+        acc = np.zeros((n, R.WAVE), F32)
+        for j in range(rounds):
+            for e in range(per_load):
+                nxt = R._fma(Wp[:, j, :, e], np.broadcast_to(gp[j, :, e], (n, R.WAVE)), acc)
+                acc = np.where(valid[j, :, e][None, :], nxt, acc)
+        return R._butterfly(acc)
+
+    for per_load in (4, 8):
+        for vec in (g, np.zeros(K, F32)):
+            got = R.LaneDot(W, per_load).dot(vec)
+            want = plain(W, vec, per_load)
+            assert got.dtype == F32
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (per_load, got, want)
+        assert np.array_equal(R.lane_dot(W, g, per_load).view(np.uint32), plain(W, g, per_load).view(np.uint32))
+
