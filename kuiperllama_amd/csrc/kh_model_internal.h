@@ -2,7 +2,8 @@
 // The model level is split into four translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
-//                         predict / generate (kh_fused.h kernels are instantiated here)
+//                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
+//                         template parameter, picked from and launched through kh_dispatch.h)
 //   kh_model_prefill.hip  B-token VALU prefill and the MFMA GEMM prefill (kh_prefill.h, kh_gemm.h,
 //                         kh_pattn.h kernels)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
@@ -98,7 +99,6 @@ struct kh_model {
   bool attn_fenced = false;  // KH_FLAG_ATTN_MERGE_FENCED / KH_ATTN_FENCED: fences around the in-launch split merge
   bool attn_defer = false;  // variant 1 exists: split partials combined by kh_fused.h::k_wo_comb
   int attn_defer_max = 0;   // ... up to this many active splits (more: the in-launch merge is as fast or faster)
-  int step_var = 0;         // variant the launch_* helpers use right now (set by launch_step_fused / profile)
   int32_t *d_pos = nullptr, *d_token = nullptr, *d_next = nullptr, *d_forced = nullptr,
           *d_words = nullptr;
   int seq_cap = 0;  // capacity of d_forced / d_words
@@ -197,16 +197,17 @@ void plan_decode_shapes(bool quant, int dim, int hidden_dim, int kv_dim, int voc
 // which int8 GEMVs of a decode step run on the LDS-DMA ring kernels, and their launch geometry (host-only)
 void plan_ring(bool quant, int dim, int hidden_dim, int vocab_size, int group_size, kh_model::RingPlan* out);
 int configure_step_kernels(kh_model* m);  // >64 KiB dynamic-LDS opt-in of the hidden-sized GEMVs
-KhAttnArgs fill_attn(kh_model* m, int l);
+// variant (see kh_model::sg, step_variant): which attention / wo pair is launched
+KhAttnArgs fill_attn(kh_model* m, int l, int variant);
 void launch_qkv(kh_model* m, int l);
-void launch_attn(kh_model* m, int l);
-void launch_wo(kh_model* m, int l);  // follows m->step_var like launch_attn
+void launch_attn(kh_model* m, int l, int variant);
+void launch_wo(kh_model* m, int l, int variant);
 void launch_ffn13(kh_model* m, int l);
 void launch_w2(kh_model* m, int l);
 void launch_cls(kh_model* m);
 // the step's last launch: k_sample (argmax), or k_sample_topp while m->samp_on
 void launch_sample(kh_model* m, int advance, int n_forced);
-// variant (see kh_model::sg): which attention / wo pair the launches of a step use
+// the variant of the steps at positions pos_lo .. pos_hi
 int step_variant(const kh_model* m, int pos_lo, int pos_hi);
 void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, int variant);
 int launch_step_unfused(kh_model* m, int pos);

@@ -6,10 +6,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <initializer_list>
-#include <string>
 #include <vector>
 
+#include "kh_dispatch.h"
 #include "kh_gemm.h"
 #include "kh_model_internal.h"
 #include "kh_pattn.h"
@@ -72,8 +71,8 @@ int ensure_prefill_buffers(kh_model* m) {
 // The B-token kernels are register- and LDS-heavy: a grid larger than what is resident at once
 // runs in rounds and every round re-stages the B activation vectors, so the decode shape's grid
 // is clipped to one resident round (the result does not depend on the grid).
-template <class K, class A>
-void pf_launch(K kernel, int grid, int wg, size_t lds, hipStream_t s, const A& args) {
+template <class K>
+void pf_clip_grid(K kernel, dim3& grid, int wg, size_t lds) {
   // resident-workgroup count and the >64 KiB LDS opt-in are per (device, kernel, shape): a thread
   // that drives models on several GPUs must not reuse device A's answer (or skip the attribute)
   // on device B
@@ -104,31 +103,30 @@ void pf_launch(K kernel, int grid, int wg, size_t lds, hipStream_t s, const A& a
     resident = per_cu * cus;
     cache.push_back({dev, (const void*)kernel, wg, lds, resident});
   }
-  if (grid > resident) grid = resident;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(wg), lds, s, args);
+  if ((int)grid.x > resident) grid.x = resident;
 }
-// the launch log's name of a prefill kernel instantiation (hook KH_LAUNCH_LOG), e.g. "k_pf_gemv_res<true,4,2>",
-// "k_pg_gemm<false,2,8,1>", "k_pg_rmsnorm<true>"
-void pf_log(const char* stem, bool q, std::initializer_list<int> targs) {
-  if (!g_launch_log_on.load(std::memory_order_relaxed)) return;
-  std::string n = std::string(stem) + (q ? "<true" : "<false");
-  for (int t : targs) n += "," + std::to_string(t);
-  launch_log_add((n + ">").c_str());
+// pf_launch(KH_KERNEL(k_pf_qkv, Q, SP, B), ...): the logged launch of kh_dispatch.h on the clipped grid
+template <class K, class A>
+void pf_launch(K kernel, const char* stem, std::initializer_list<KhTArg> targs, const kh_model::Shape& sh, size_t lds,
+               hipStream_t s, const A& args) {
+  (void)kh_launch_prep([&](K k, dim3& grid) { return pf_clip_grid(k, grid, sh.wg, lds), true; }, kernel, stem, targs,
+                       sh.grid, sh.wg, lds, s, args);
 }
-template <bool Q, int SP, int B>
-void pf_launch_gemv_res_sp(kh_model* m, const kh_model::Shape& sh, const KhPfGemvResArgs& a, size_t lds) {
-  pf_log("k_pf_gemv_res", Q, {SP, B});
-  pf_launch(k_pf_gemv_res<Q, SP, B>, sh.grid, sh.wg, lds, m->stream, a);
-}
-template <bool Q, int B>
-void pf_launch_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhPfGemvResArgs& a) {
-  const size_t lds = pf_lds_bytes(Q, a.M, B);
-  if (sh.split == 4)
-    pf_launch_gemv_res_sp<Q, 4, B>(m, sh, a, lds);
-  else if (sh.split == 2)
-    pf_launch_gemv_res_sp<Q, 2, B>(m, sh, a, lds);
-  else
-    pf_launch_gemv_res_sp<Q, 1, B>(m, sh, a, lds);
+// The instantiations of the B-token kernels: SP = the decode shape's split (prefill_supported: qkv's at most 2), B =
+// tokens per pass - 8, 4 or 2 by construction (prefill_batch, pf_gemv_res), int8 at most 4.
+template <bool Q>
+using PfB = std::conditional_t<Q, KhVals<4>, KhVals<8, 4>>;  // k_pf_qkv, k_pf_ffn13
+template <bool Q>
+using PfGemvResB = std::conditional_t<Q, KhVals<4, 2>, KhVals<8, 4, 2>>;
+using PfQkvSP = KhVals<2, 1>;
+using PfGemvResSP = KhVals<4, 2, 1>;
+using PfNoSP = KhVals<1>;  // k_pf_ffn13
+// f(Q, SP, B) with the compile-time values of a launch
+template <template <bool> class BS, class SPS, class F>
+void pick_pf(bool quant, int sp, int b, F&& f) {
+  kh_pick_bool(quant, [&](auto Q) {
+    kh_pick(SPS{}, sp, [&](auto SP) { kh_pick_ge(BS<decltype(Q)::value>{}, b, [&](auto B) { f(Q, SP, B); }); });
+  });
 }
 // y = W.v ; X += y for the nvalid tokens of the chunk, in sub-batches of the largest of 8/4/2
 // tokens (<= bmax) whose input vectors fit LDS
@@ -146,31 +144,10 @@ void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const f
     a.V = V + (size_t)t0 * M;
     a.X = X + (size_t)t0 * K;
     a.nvalid = nvalid - t0 < bs ? nvalid - t0 : bs;
-    if (q) {
-      if (bs >= 4) pf_launch_gemv_res<true, 4>(m, sh, a); else pf_launch_gemv_res<true, 2>(m, sh, a);
-    } else {
-      if (bs == 8) pf_launch_gemv_res<false, 8>(m, sh, a);
-      else if (bs == 4) pf_launch_gemv_res<false, 4>(m, sh, a);
-      else pf_launch_gemv_res<false, 2>(m, sh, a);
-    }
+    pick_pf<PfGemvResB, PfGemvResSP>(q, sh.split, bs, [&](auto Q, auto SP, auto B) {
+      pf_launch(KH_KERNEL(k_pf_gemv_res, Q, SP, B), sh, pf_lds_bytes(Q, M, B), m->stream, a);
+    });
   }
-}
-template <bool Q, int SP, int B>
-void pf_launch_qkv_sp(kh_model* m, const KhPfQkvArgs& a) {
-  pf_log("k_pf_qkv", Q, {SP, B});
-  pf_launch(k_pf_qkv<Q, SP, B>, m->sh_qkv.grid, m->sh_qkv.wg, pf_lds_bytes(Q, a.dim, B), m->stream, a);
-}
-template <bool Q, int B>
-void pf_launch_qkv(kh_model* m, const KhPfQkvArgs& a) {
-  if (m->sh_qkv.split == 2)
-    pf_launch_qkv_sp<Q, 2, B>(m, a);
-  else
-    pf_launch_qkv_sp<Q, 1, B>(m, a);
-}
-template <bool Q, int B>
-void pf_launch_ffn13(kh_model* m, const KhPfFfn13Args& a) {
-  pf_log("k_pf_ffn13", Q, {B});
-  pf_launch(k_pf_ffn13<Q, B>, m->sh_ffn.grid, m->sh_ffn.wg, pf_lds_bytes(Q, a.dim, B), m->stream, a);
 }
 // forward of nvalid (<= B) prompt tokens at positions pos0.. : fills their K/V cache rows
 void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0, int B) {
@@ -201,15 +178,15 @@ void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0
       a.pos0 = pos0;
       a.nvalid = nvalid;
       a.eps = c.rms_eps;
-      if (q) pf_launch_qkv<true, 4>(m, a);
-      else if (B == 8) pf_launch_qkv<false, 8>(m, a);
-      else pf_launch_qkv<false, 4>(m, a);
+      pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
+        pf_launch(KH_KERNEL(k_pf_qkv, Q, SP, BB), m->sh_qkv, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
+      });
     }
     // the prompt phase leaves K/V rows and nothing else (no logits): the last layer's K/V rows are
     // written, its attention, wo and FFN feed nothing
     if (l == c.layer_num - 1) break;
     {
-      KhAttnArgs a = fill_attn(m, l);
+      KhAttnArgs a = fill_attn(m, l, /*variant=*/0);
       a.defer = 0;  // multi-token slices merge in the launch
       a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: launch_attn_decode decides from the slice's positions
       a.q = m->pf_q;
@@ -233,9 +210,9 @@ void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0
       a.gshift = m->gshift;
       a.nvalid = nvalid;
       a.eps = c.rms_eps;
-      if (q) pf_launch_ffn13<true, 4>(m, a);
-      else if (B == 8) pf_launch_ffn13<false, 8>(m, a);
-      else pf_launch_ffn13<false, 4>(m, a);
+      pick_pf<PfB, PfNoSP>(q, 1, B, [&](auto Q, auto, auto BB) {
+        pf_launch(KH_KERNEL(k_pf_ffn13, Q, BB), m->sh_ffn, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
+      });
     }
     pf_gemv_res(m, m->sh_w2, W.w2, m->pf_h, m->pf_x, c.hidden_dim, c.dim, nvalid, B);
   }
@@ -285,6 +262,13 @@ int ensure_pg_ws(kh_model* m) {
   KH_CHECK_HIP(hipMemsetAsync(m->pg_ws, 0, m->pg_ws_tok_bytes * (size_t)KH_PG_TMAX, m->stream));
   return KH_OK;
 }
+// the (R, NT) register tiles k_pg_gemm is compiled for, and the waves per SIMD that fit with each
+constexpr int kPgTiles[4][3] = {{2, 8, 2}, {2, 4, 3}, {2, 2, 4}, {1, 4, 4}};
+constexpr int pg_tile(int R, int NT) {  // index in kPgTiles, -1: no such tile
+  for (int i = 0; i < 4; ++i)
+    if (kPgTiles[i][0] == R && kPgTiles[i][1] == NT) return i;
+  return -1;
+}
 // Launch shape of one prefill GEMM (kh_gemm.h): R 16-row tiles and NT 16-token tiles per wave,
 // ks waves splitting K per workgroup, grid.y token slices.  Picked by a small cost model of the
 // busiest SIMD, fitted to a sweep on Llama-3.2-1B (profiles/r2_gemm_shape_sweep.txt):
@@ -326,10 +310,9 @@ PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min
                  bool allow_kz = false) {
   const int nt_all = (T + 15) / 16;
   const bool wide = nt_all > 8;  // a pass of more than 128 tokens
-  static const int cand[4][3] = {{2, 8, 2}, {2, 4, 3}, {2, 2, 4}, {1, 4, 4}};  // R, NT, waves/SIMD that fit
   PgShape best{1, 4, 1, (nt_all + 3) / 4, false, 1};
   double best_cost = -1.0;
-  for (const auto& c : cand) {
+  for (const auto& c : kPgTiles) {
     const int R = c[0], NT = c[1], occ = c[2];
     if (R == 2 && !r2_ok) continue;
     if (R == 1 && quant && r2_ok) continue;  // int8: the 32-row tile measured better wherever it fits
@@ -377,7 +360,7 @@ template <bool Q, int EPI>
 bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const KhPgGemmArgs& a) {
   size_t lds = pg_lds_bytes(wg / 64, sh.NT);
   if (sh.solo && lds < KH_PG_SOLO_LDS) lds = KH_PG_SOLO_LDS;  // one workgroup per CU at a time
-  auto go = [&](auto kern) {
+  auto opt_in = [&](auto kern, dim3&) {
     if (lds > 48 * 1024) {
       // the >48 KiB dynamic-LDS opt-in is per (device, kernel): set once, not on every launch of
       // the prefill hot path; a refusal is reported here, not as a generic launch error later
@@ -395,13 +378,15 @@ bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const Kh
         done.push_back({dev, (const void*)kern, lds});
       }
     }
-    hipLaunchKernelGGL(kern, dim3(tiles, sh.slices, sh.kz), dim3(wg), lds, s, a);
     return true;
   };
-  if (sh.R == 2 && sh.NT == 8) return pf_log("k_pg_gemm", Q, {2, 8, EPI}), go(k_pg_gemm<Q, 2, 8, EPI>);
-  if (sh.R == 2 && sh.NT == 4) return pf_log("k_pg_gemm", Q, {2, 4, EPI}), go(k_pg_gemm<Q, 2, 4, EPI>);
-  if (sh.R == 2) return pf_log("k_pg_gemm", Q, {2, 2, EPI}), go(k_pg_gemm<Q, 2, 2, EPI>);
-  return pf_log("k_pg_gemm", Q, {1, 4, EPI}), go(k_pg_gemm<Q, 1, 4, EPI>);
+  const int tile = pg_tile(sh.R, sh.NT);  // one that is not listed runs as (2,2) where R is 2, else as (1,4)
+  bool ok = false;
+  kh_pick(KhVals<0, 1, 2, 3>{}, tile >= 0 ? tile : (sh.R == 2 ? 2 : 3), [&](auto I) {
+    constexpr int R = kPgTiles[I][0], NT = kPgTiles[I][1];
+    ok = kh_launch_prep(opt_in, KH_KERNEL(k_pg_gemm, Q, R, NT, EPI), dim3(tiles, sh.slices, sh.kz), wg, lds, s, a);
+  });
+  return ok;
 }
 // returns whether the QKV epilogue rotates q / k itself (else k_pg_rope has to follow); RESID: the
 // number of K slices whose partial rows the next RMSNorm has to add (0 = the epilogue added itself)
@@ -415,7 +400,7 @@ int pg_launch(kh_model* m, int rows_total, bool r2_ok, KhPgGemmArgs a) {
     const char* const ov = dbg(names[EPI]);
     if (ov) {
       int R = 0, NT = 0, ks = 0, kz = 1;
-      if (sscanf(ov, "%d,%d,%d,%d", &R, &NT, &ks, &kz) >= 3 && ((R == 2 && (NT == 2 || NT == 4 || NT == 8) && r2_ok) || (R == 1 && NT == 4)) &&
+      if (sscanf(ov, "%d,%d,%d,%d", &R, &NT, &ks, &kz) >= 3 && pg_tile(R, NT) >= 0 && (R != 2 || r2_ok) &&
           (ks == 1 || ks == 2 || ks == 4 || ks == 8) && ks * nm * 64 <= KH_PG_WG_MAX(q) &&
           (kz == 1 || (EPI == KH_PG_RESID && (kz == 2 || kz == 4))))
       {
@@ -452,9 +437,10 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
   (void)kh_embedding_f32_host(toks, T, m->tok_emb, m->pg_x, c.dim, c.vocab_size, (void*)m->stream);
   int pending_kz = 0;  // K slices of the last residual GEMM still to be added to pg_x (by the next RMSNorm)
   auto rmsnorm = [&](const float* w) {
-    pf_log("k_pg_rmsnorm", q, {});
-    if (q) hipLaunchKernelGGL(k_pg_rmsnorm<true>, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_x, w, m->pg_xn, c.dim, c.rms_eps, tcap, (const float*)m->pg_part, pending_kz);
-    else hipLaunchKernelGGL(k_pg_rmsnorm<false>, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_x, w, m->pg_xn, c.dim, c.rms_eps, tcap, (const float*)m->pg_part, pending_kz);
+    kh_pick_bool(q, [&](auto Q) {
+      kh_launch(KH_KERNEL(k_pg_rmsnorm, Q), T, KH_WG, 0, m->stream, m->pg_x, w, m->pg_xn, c.dim, c.rms_eps, tcap,
+                (const float*)m->pg_part, pending_kz);
+    });
     pending_kz = 0;
   };
   // attention of the slice: MFMA kernel (kh_pattn.h) unless KH_PG_ATTN=0 or an odd head size
@@ -495,7 +481,7 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
       a.T = T; a.pos0 = pos0; a.layout = q ? KH_PA_TILED_Q8 : KH_PA_TILED_F32; a.tcap = tcap;
       launch_pg_attn(a, c.head_size, m->stream);
     } else {
-      KhAttnArgs a = fill_attn(m, l);
+      KhAttnArgs a = fill_attn(m, l, /*variant=*/0);
       a.defer = 0;  // multi-token slices merge in the launch
       a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: launch_attn_decode decides from the slice's positions
       a.q = m->pg_q;

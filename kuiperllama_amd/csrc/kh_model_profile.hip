@@ -18,14 +18,14 @@ extern "C" int kh_model_profile_kernel(kh_model* m, int32_t kclass, int32_t pos,
     if (rc != KH_OK) return rc;
   }
   set_state(m, 1 % c.vocab_size, pos);
-  m->step_var = step_variant(m, pos, pos);  // the attention / wo pair a step at `pos` launches
+  const int variant = step_variant(m, pos, pos);  // the attention / wo pair a step at `pos` launches
   const bool per_layer = kclass < KH_K_CLS;
   const int n_inner = per_layer ? c.layer_num : 1;
   auto sweep = [&]() {
     for (int l = 0; l < n_inner; ++l) switch (kclass) {
         case KH_K_QKV: launch_qkv(m, l); break;
-        case KH_K_ATTN: launch_attn(m, l); break;
-        case KH_K_WO: launch_wo(m, l); break;
+        case KH_K_ATTN: launch_attn(m, l, variant); break;
+        case KH_K_WO: launch_wo(m, l, variant); break;
         case KH_K_FFN13: launch_ffn13(m, l); break;
         case KH_K_W2: launch_w2(m, l); break;
         case KH_K_CLS: launch_cls(m); break;

@@ -8,43 +8,23 @@
 #include <string.h>
 
 #include "kh_cls_screen.h"
+#include "kh_dispatch.h"
 #include "kh_model_internal.h"
 
 namespace khm {
 
 namespace {
-// k_sample_screen<U, MAXV>: U in {2, 4, 8} (k_cls's), MAXV in {1, 2, 4}; k_cls_screen<U, MAXV>: U in {2, 4} (a tile of
-// 8 loads per row, 64 registers of packed weights beside their unpacked halves, does not fit 128 registers)
-#define KH_LSCR(KERNEL, UU, MV, GRID, WG, LDS, STREAM, ARGS)                                \
-  do {                                                                                      \
-    launch_log(#KERNEL "<" #UU "," #MV ">");                                                \
-    hipLaunchKernelGGL((KERNEL<UU, MV>), dim3(GRID), dim3(WG), LDS, STREAM, ARGS);          \
-  } while (0)
-#define KH_LSCR_MV(KERNEL, UU, MV, ...)                    \
-  do {                                                     \
-    if ((MV) == 4)                                         \
-      KH_LSCR(KERNEL, UU, 4, __VA_ARGS__);                 \
-    else if ((MV) == 2)                                    \
-      KH_LSCR(KERNEL, UU, 2, __VA_ARGS__);                 \
-    else                                                   \
-      KH_LSCR(KERNEL, UU, 1, __VA_ARGS__);                 \
-  } while (0)
-#define KH_LSCR_U4(KERNEL, U, MV, ...)                     \
-  do {                                                     \
-    if ((U) >= 4)                                          \
-      KH_LSCR_MV(KERNEL, 4, MV, __VA_ARGS__);              \
-    else                                                   \
-      KH_LSCR_MV(KERNEL, 2, MV, __VA_ARGS__);              \
-  } while (0)
-#define KH_LSCR_U(KERNEL, U, MV, ...)                      \
-  do {                                                     \
-    if ((U) >= 8)                                          \
-      KH_LSCR_MV(KERNEL, 8, MV, __VA_ARGS__);              \
-    else if ((U) >= 4)                                     \
-      KH_LSCR_MV(KERNEL, 4, MV, __VA_ARGS__);              \
-    else                                                   \
-      KH_LSCR_MV(KERNEL, 2, MV, __VA_ARGS__);              \
-  } while (0)
+// The instantiations of the two kernels, <U, MAXV>.  k_cls_screen has no U 8: a tile of 8 loads per row, 64 registers
+// of packed weights beside their unpacked halves, does not fit 128 registers.  k_sample_screen takes k_cls's U.  A
+// vector staged deeper than 4 float4 per thread is not screened (cls_screen_create), so MAXV is one of these; the
+// lists end in the value an unlisted one takes (kh_dispatch.h).
+using ScreenU = KhVals<4, 2>;
+using SampleScreenU = KhVals<8, 4, 2>;
+using ScreenMV = KhVals<4, 2, 1>;
+template <class US, class F>
+void pick_screen(int u, int mv, F&& f) {
+  kh_pick_ge(US{}, u, [&](auto U) { kh_pick(ScreenMV{}, mv, [&](auto MV) { f(U, MV); }); });
+}
 
 // Launch of k_cls_screen.  u: 16-byte loads per row and lane in flight, one tile per row where it fits (a lane
 // covers 8 weights per load: dim 2048 is 4 loads; longer rows walk several tiles of 4).  A bf16 row pair is half
@@ -64,8 +44,8 @@ void plan_screen(kh_model* m) {
   if (s.grid > need) s.grid = need;
   if (const char* ov = dbg("KH_SHAPE_SCREEN")) {
     int u = 0, g = 0, w = 0;
-    if (sscanf(ov, "%d,%d,%d", &u, &g, &w) == 3 && (u == 2 || u == 4) && g >= 1 && g <= 4096 &&
-        (w == 256 || w == 512) && kh_stage_maxv(c.dim, w) >= 1 && kh_stage_maxv(c.dim, w) <= 4) {
+    if (sscanf(ov, "%d,%d,%d", &u, &g, &w) == 3 && ScreenU::has(u) && g >= 1 && g <= 4096 &&
+        (w == 256 || w == 512) && ScreenMV::has(kh_stage_maxv(c.dim, w))) {
       s.u = u;
       s.grid = g;
       s.wg = w;
@@ -108,8 +88,7 @@ int cls_screen_create(kh_model* m) {
   // classifiers are a fiftieth of their token and stay as they are
   if (c.is_quant || (m->opts.flags & KH_FLAG_NO_CLS_SCREEN) || dbg_off("KH_CLS_SCREEN") || cls_hook_bars_screen()) return KH_OK;
   if (c.dim % 8 != 0 || c.vocab_size < 2) return KH_OK;
-  const int mv = kh_stage_maxv(c.dim, m->sh_cls.wg);
-  if (mv < 1 || mv > 4) return KH_OK;
+  if (!ScreenMV::has(kh_stage_maxv(c.dim, m->sh_cls.wg))) return KH_OK;
   plan_screen(m);
   {
     int cus = 0;
@@ -179,7 +158,9 @@ void launch_cls_screen(kh_model* m) {
   a.dim = c.dim;
   a.vocab = c.vocab_size;
   a.eps = c.rms_eps;
-  KH_LSCR_U4(k_cls_screen, s.u, kh_stage_maxv(c.dim, s.wg), s.grid, s.wg, cls_screen_lds_bytes(c.dim), m->stream, a);
+  pick_screen<ScreenU>(s.u, kh_stage_maxv(c.dim, s.wg), [&](auto U, auto MV) {
+    kh_launch(KH_KERNEL(k_cls_screen, U, MV), s.grid, s.wg, cls_screen_lds_bytes(c.dim), m->stream, a);
+  });
 }
 
 void launch_sample_screen(kh_model* m, int advance, int n_forced) {
@@ -213,7 +194,9 @@ void launch_sample_screen(kh_model* m, int advance, int n_forced) {
   a.advance = advance;
   // k_cls's own U, staging depth and workgroup width: the re-scored values are then k_cls's, bit for bit
   const int wg = m->sh_cls.wg;
-  KH_LSCR_U(k_sample_screen, m->sh_cls.u, kh_stage_maxv(c.dim, wg), s.sgrid, wg, cls_lds_bytes(false, c.dim), m->stream, a);
+  pick_screen<SampleScreenU>(m->sh_cls.u, kh_stage_maxv(c.dim, wg), [&](auto U, auto MV) {
+    kh_launch(KH_KERNEL(k_sample_screen, U, MV), s.sgrid, wg, cls_lds_bytes(false, c.dim), m->stream, a);
+  });
 }
 
 int cls_refresh_logits(kh_model* m) {

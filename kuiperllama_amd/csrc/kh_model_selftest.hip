@@ -130,13 +130,12 @@ static int attn_merge_case(kh_model* m, int pos, int variant, int32_t* d_flag) {
   const kh_config& c = m->cfg;
   hipStream_t s = m->stream;
   set_state(m, 1 % c.vocab_size, pos);
-  m->step_var = variant;
   m->attn_fenced = true;
-  launch_attn(m, 0);
+  launch_attn(m, 0, variant);
   KH_CHECK_HIP(hipMemcpyAsync(m->rms, m->att, sizeof(float) * (size_t)c.dim, hipMemcpyDeviceToDevice, s));
   m->attn_fenced = false;
   for (int i = 0; i < KH_SELFTEST_ATTN_LAUNCHES; ++i) {
-    launch_attn(m, 0);
+    launch_attn(m, 0, variant);
     hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.dim)), dim3(KH_WG), 0, s, (const uint32_t*)m->att,
                        (const uint32_t*)m->rms, (size_t)c.dim, d_flag);
   }
@@ -171,7 +170,6 @@ static int attn_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
   hipLaunchKernelGGL(k_st_fill, dim3(grid_for((size_t)c.dim)), dim3(KH_WG), 0, s, m->q, (size_t)c.dim, 0xc2b2ae35u, 1.0f);
   if (head_case) rc = attn_merge_case(m, pos1, m->attn_ns_g > 0 ? 2 : 0, d_flag);
   if (rc == KH_OK && pos2 >= 0) rc = attn_merge_case(m, pos2, 0, d_flag);
-  m->step_var = 0;
   m->attn_fenced = false;
   int32_t flag = 0;
   hipError_t e = hipMemsetAsync(m->kcache, 0, n * sizeof(float), s);  // the cache is empty again

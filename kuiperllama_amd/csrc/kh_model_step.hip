@@ -10,12 +10,37 @@
 
 #include <vector>
 
+#include "kh_dispatch.h"
 #include "kh_fused.h"
 #include "kh_fused_ring.h"
 #include "kh_sample.h"
 #include "kh_model_internal.h"
 
 namespace khm {
+
+// The instantiations each kernel is compiled for, stated once: the dispatch below, the LDS opt-in of
+// configure_step_kernels and the KH_SHAPE_* validator of pick_shape all read these lists.  U: 16-byte loads per row in
+// flight per lane (kh_pick_ge: u >= 8 -> 8, >= 4 -> 4, else 2); MV: in-register staging depth (kh_stage_maxv of the
+// input length) and SP: waves sharing one row pair (kh_pick: an unlisted value takes the last one listed).
+template <bool Q>
+using FusedU = std::conditional_t<Q, KhVals<4, 2>, KhVals<8, 4, 2>>;  // k_qkv, k_gemv_res as wo, k_wo_comb, k_ffn13, k_cls
+template <bool Q>
+using GemvResU = std::conditional_t<Q, KhVals<4, 3, 2>, KhVals<8, 4, 2>>;  // k_gemv_res as w2 (pick_shape, u3)
+using FusedMV = KhVals<4, 2, 1, 0>;
+using GemvResMV = KhVals<6, 4, 2, 1, 0>;  // w2 only: the 6-deep staging for hidden-sized inputs (wo's 6 runs as 0)
+using WoCombMV = KhVals<2, 4>;
+using QkvSP = KhVals<2, 1>;  // k_qkv's shape is split at most twice (plan_decode_shapes: max_split 2)
+using GemvResSP = KhVals<4, 2, 1>;  // k_gemv_res, k_wo_comb
+using NoSP = KhVals<1>;             // k_ffn13, k_cls
+// f(Q, U, MV, SP) with the compile-time values a launch shape selects from a kernel's lists
+template <template <bool> class US, class MVS, class SPS, class F>
+void pick_fused(bool quant, int u, int mv, int sp, F&& f) {
+  kh_pick_bool(quant, [&](auto Q) {
+    kh_pick_ge(US<decltype(Q)::value>{}, u, [&](auto U) {
+      kh_pick(MVS{}, mv, [&](auto MV) { kh_pick(SPS{}, sp, [&](auto SP) { f(Q, U, MV, SP); }); });
+    });
+  });
+}
 
 // Launch shape of one GEMV: rows are processed as `pairs` work items of two M-long rows.
 //  split: waves sharing a pair (1/2/4) — raised while the launch has < 4096 waves and each wave
@@ -30,8 +55,9 @@ kh_model::Shape pick_shape(bool quant, int pairs, int M, int max_split, const ch
   if (const char* ov = env ? dbg(env) : nullptr) {
     int sp = 0, u = 0, g = 0, w = wg;
     const int nf = sscanf(ov, "%d,%d,%d,%d", &sp, &u, &g, &w);
-    if (nf >= 3 && (sp == 1 || sp == 2 || sp == 4) && sp <= max_split &&
-        (u == 2 || u == 4 || u == 8 || (quant && u3 && u == 3)) && !(quant && u == 8) && g >= 1 && g <= 4096 &&
+    const bool u_ok = u3 ? (quant ? GemvResU<true>::has(u) : GemvResU<false>::has(u))
+                         : (quant ? FusedU<true>::has(u) : FusedU<false>::has(u));
+    if (nf >= 3 && GemvResSP::has(sp) && sp <= max_split && u_ok && g >= 1 && g <= 4096 &&
         (w == 256 || (w == 512 && wg_max >= 512))) {
       sh.split = sp;
       sh.u = u;
@@ -109,101 +135,6 @@ kh_model::Shape pick_shape(bool quant, int pairs, int M, int max_split, const ch
 }
 
 // ---- fused launches -------------------------------------------------------------------------
-// Template dispatch.  U: 16-byte loads per row in flight per lane; MV: in-register staging depth
-// (kh_stage_maxv of the input length); SP: waves sharing one row pair.
-// The workgroup size comes from a variable `kh_launch_wg` in scope at the dispatch site.  Every launch macro names
-// its instantiation in the launch log (hook KH_LAUNCH_LOG, kh_common.h) from the literal template arguments it launches.
-#define KH_L3(KERNEL, Q, UU, MV, GRID, LDS, STREAM, ARGS)                                     \
-  do {                                                                                     \
-    launch_log(#KERNEL "<" #Q "," #UU "," #MV ">");                                        \
-    hipLaunchKernelGGL((KERNEL<Q, UU, MV>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS); \
-  } while (0)
-#define KH_L4(KERNEL, Q, UU, MV, SP, GRID, LDS, STREAM, ARGS)                                     \
-  do {                                                                                         \
-    launch_log(#KERNEL "<" #Q "," #UU "," #MV "," #SP ">");                                    \
-    hipLaunchKernelGGL((KERNEL<Q, UU, MV, SP>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS); \
-  } while (0)
-// the int8 LDS-DMA ring kernels (kh_fused_ring.h): R ring slots per wave, MAXV float4 staged per thread, plain layout
-#define KH_LRING(KERNEL, R, MV, GRID, LDS, STREAM, ARGS)                                   \
-  do {                                                                                  \
-    launch_log(#KERNEL "<" #R "," #MV ",false>");                                       \
-    hipLaunchKernelGGL((KERNEL<R, MV, false>), dim3(GRID), dim3(KH_WG), LDS, STREAM, ARGS); \
-  } while (0)
-#define KH_SEL_MV3(KERNEL, Q, UU, MV, ...)                  \
-  do {                                                      \
-    if ((MV) == 4)                                          \
-      KH_L3(KERNEL, Q, UU, 4, __VA_ARGS__);                 \
-    else if ((MV) == 2)                                     \
-      KH_L3(KERNEL, Q, UU, 2, __VA_ARGS__);                 \
-    else if ((MV) == 1)                                     \
-      KH_L3(KERNEL, Q, UU, 1, __VA_ARGS__);                 \
-    else                                                    \
-      KH_L3(KERNEL, Q, UU, 0, __VA_ARGS__);                 \
-  } while (0)
-#define KH_SEL_SP4(KERNEL, Q, UU, MV, SP, ...)              \
-  do {                                                      \
-    if ((SP) == 4)                                          \
-      KH_L4(KERNEL, Q, UU, MV, 4, __VA_ARGS__);             \
-    else if ((SP) == 2)                                     \
-      KH_L4(KERNEL, Q, UU, MV, 2, __VA_ARGS__);             \
-    else                                                    \
-      KH_L4(KERNEL, Q, UU, MV, 1, __VA_ARGS__);             \
-  } while (0)
-// k_qkv: its shape is split at most twice (plan_decode_shapes: max_split 2), so SPLIT = 4 is not compiled
-#define KH_SEL_SP2(KERNEL, Q, UU, MV, SP, ...)              \
-  do {                                                      \
-    if ((SP) == 2)                                          \
-      KH_L4(KERNEL, Q, UU, MV, 2, __VA_ARGS__);             \
-    else                                                    \
-      KH_L4(KERNEL, Q, UU, MV, 1, __VA_ARGS__);             \
-  } while (0)
-#define KH_SEL_MV4S(SELSP, KERNEL, Q, UU, MV, SP, ...)      \
-  do {                                                      \
-    if ((MV) == 4)                                          \
-      SELSP(KERNEL, Q, UU, 4, SP, __VA_ARGS__);             \
-    else if ((MV) == 2)                                     \
-      SELSP(KERNEL, Q, UU, 2, SP, __VA_ARGS__);             \
-    else if ((MV) == 1)                                     \
-      SELSP(KERNEL, Q, UU, 1, SP, __VA_ARGS__);             \
-    else                                                    \
-      SELSP(KERNEL, Q, UU, 0, SP, __VA_ARGS__);             \
-  } while (0)
-#define KH_SEL_MV4(KERNEL, Q, UU, MV, SP, ...) KH_SEL_MV4S(KH_SEL_SP4, KERNEL, Q, UU, MV, SP, __VA_ARGS__)
-#define KH_SEL_MV4Q(KERNEL, Q, UU, MV, SP, ...) KH_SEL_MV4S(KH_SEL_SP2, KERNEL, Q, UU, MV, SP, __VA_ARGS__)
-// k_gemv_res only: the 6-deep in-register staging for hidden-sized inputs (kh_stage_maxv)
-#define KH_SEL_MV4X(KERNEL, Q, UU, MV, SP, ...)             \
-  do {                                                      \
-    if ((MV) == 6)                                          \
-      KH_SEL_SP4(KERNEL, Q, UU, 6, SP, __VA_ARGS__);        \
-    else                                                    \
-      KH_SEL_MV4(KERNEL, Q, UU, MV, SP, __VA_ARGS__);       \
-  } while (0)
-#define KH_SEL_U(SEL, KERNEL, QUANT, U, ...)                \
-  do {                                                      \
-    if (QUANT) {                                            \
-      if ((U) >= 4)                                         \
-        SEL(KERNEL, true, 4, __VA_ARGS__);                  \
-      else                                                  \
-        SEL(KERNEL, true, 2, __VA_ARGS__);                  \
-    } else {                                                \
-      if ((U) >= 8)                                         \
-        SEL(KERNEL, false, 8, __VA_ARGS__);                 \
-      else if ((U) >= 4)                                    \
-        SEL(KERNEL, false, 4, __VA_ARGS__);                 \
-      else                                                  \
-        SEL(KERNEL, false, 2, __VA_ARGS__);                 \
-    }                                                       \
-  } while (0)
-// kernels without / with the SPLIT parameter
-#define KH_DISPATCH3(KERNEL, QUANT, U, MV, GRID, LDS, STREAM, ARGS) \
-  KH_SEL_U(KH_SEL_MV3, KERNEL, QUANT, U, MV, GRID, LDS, STREAM, ARGS)
-#define KH_DISPATCH4(KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS) \
-  KH_SEL_U(KH_SEL_MV4, KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS)
-#define KH_DISPATCH4X(KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS) \
-  KH_SEL_U(KH_SEL_MV4X, KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS)
-#define KH_DISPATCH4Q(KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS) \
-  KH_SEL_U(KH_SEL_MV4Q, KERNEL, QUANT, U, MV, SP, GRID, LDS, STREAM, ARGS)
-
 KhQkvArgs fill_qkv(kh_model* m, int l) {
   const kh_config& c = m->cfg;
   const LayerW& W = m->layers[l];
@@ -230,12 +161,13 @@ KhQkvArgs fill_qkv(kh_model* m, int l) {
 void launch_qkv(kh_model* m, int l) {
   const kh_config& c = m->cfg;
   const KhQkvArgs a = fill_qkv(m, l);
-  const bool qn = c.is_quant;
-  const int kh_launch_wg = m->sh_qkv.wg;
-  KH_DISPATCH4Q(k_qkv, qn, m->sh_qkv.u, kh_stage_maxv(c.dim, kh_launch_wg), m->sh_qkv.split, m->sh_qkv.grid,
-               fused_lds_bytes(qn, c.dim), m->stream, a);
+  const kh_model::Shape& sh = m->sh_qkv;
+  pick_fused<FusedU, FusedMV, QkvSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split,
+                                     [&](auto Q, auto U, auto MV, auto SP) {
+    kh_launch(KH_KERNEL(k_qkv, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
+  });
 }
-KhAttnArgs fill_attn(kh_model* m, int l) {
+KhAttnArgs fill_attn(kh_model* m, int l, int variant) {
   const kh_config& c = m->cfg;
   KhAttnArgs a;
   a.q = m->q;
@@ -252,10 +184,10 @@ KhAttnArgs fill_attn(kh_model* m, int l) {
   a.ws_stride = m->attn_ws_stride;
   // step variants 1 and 2 cover positions below the group path's threshold only (step_variant): launch the
   // per-head-only instantiation, whose register count leaves room for two 512-thread workgroups per CU
-  a.nsplit_g = m->step_var != 0 ? 0 : m->attn_ns_g;
+  a.nsplit_g = variant != 0 ? 0 : m->attn_ns_g;
   a.t_long = m->attn_t_long;
   a.ts_shift = m->attn_ts_shift;
-  a.defer = m->step_var == 1 ? 1 : 0;
+  a.defer = variant == 1 ? 1 : 0;
   a.fenced = m->attn_fenced ? 1 : 0;
   a.tok_stride = 0;
   a.ws_tok_bytes = 0;
@@ -266,9 +198,9 @@ int attn_group_lanes(const kh_config& c) {
   while (G < c.head_size / 4) G <<= 1;
   return G < 16 ? 16 : G;
 }
-void launch_attn(kh_model* m, int l) {
+void launch_attn(kh_model* m, int l, int variant) {
   const kh_config& c = m->cfg;
-  const KhAttnArgs a = fill_attn(m, l);
+  const KhAttnArgs a = fill_attn(m, l, variant);
   const int wg = m->attn_wg;
   if (c.head_size > 32)
     launch_attn_decode(a, 0, wg, m->stream);
@@ -289,33 +221,10 @@ KhGemvResArgs fill_wo(kh_model* m, int l) {
   a.gshift = m->gshift;
   return a;
 }
-// wo behind a deferring attention launch (step variant 1): in-register staging of 2 or 4 float4
-#define KH_L5C(Q, UU, MV, SP, GRID, LDS, STREAM, ARGS)                                            \
-  do {                                                                                          \
-    launch_log("k_wo_comb<" #Q "," #UU "," #MV "," #SP ">");                                    \
-    hipLaunchKernelGGL((k_wo_comb<Q, UU, MV, SP>), dim3(GRID), dim3(kh_launch_wg), LDS, STREAM, ARGS); \
-  } while (0)
-#define KH_SEL_SP5C(Q, UU, MV, SP, ...)                     \
-  do {                                                      \
-    if ((SP) == 4)                                          \
-      KH_L5C(Q, UU, MV, 4, __VA_ARGS__);                    \
-    else if ((SP) == 2)                                     \
-      KH_L5C(Q, UU, MV, 2, __VA_ARGS__);                    \
-    else                                                    \
-      KH_L5C(Q, UU, MV, 1, __VA_ARGS__);                    \
-  } while (0)
-#define KH_SEL_MV5C(KERNEL_UNUSED, Q, UU, MV, SP, ...)      \
-  do {                                                      \
-    if ((MV) == 2)                                          \
-      KH_SEL_SP5C(Q, UU, 2, SP, __VA_ARGS__);               \
-    else                                                    \
-      KH_SEL_SP5C(Q, UU, 4, SP, __VA_ARGS__);               \
-  } while (0)
-void launch_wo(kh_model* m, int l) {
+void launch_wo(kh_model* m, int l, int variant) {
   const kh_config& c = m->cfg;
-  const bool qn = c.is_quant;
-  const int kh_launch_wg = m->sh_wo.wg;
-  if (m->step_var == 1) {
+  const kh_model::Shape& sh = m->sh_wo;
+  if (variant == 1) {  // behind a deferring attention launch: in-register staging of 2 or 4 float4
     KhWoCombArgs a;
     a.g = fill_wo(m, l);
     const AttnSplitWs ws = attn_ws_carve(m->attn_ws, c.head_num, c.head_size, m->attn_ws_stride);
@@ -327,14 +236,17 @@ void launch_wo(kh_model* m, int l) {
     a.cb.nsw = m->attn_ws_stride;
     a.cb.heads = c.head_num;
     a.cb.hs = c.head_size;
-    const int mv = c.dim <= 2 * 4 * kh_launch_wg ? 2 : 4;
-    KH_SEL_U(KH_SEL_MV5C, k_wo_comb, qn, m->sh_wo.u, mv, m->sh_wo.split, m->sh_wo.grid,
-             comb_lds_bytes(qn, c.dim, c.head_num), m->stream, a);
+    pick_fused<FusedU, WoCombMV, GemvResSP>(c.is_quant, sh.u, c.dim <= 2 * 4 * sh.wg ? 2 : 4, sh.split,
+                                            [&](auto Q, auto U, auto MV, auto SP) {
+      kh_launch(KH_KERNEL(k_wo_comb, Q, U, MV, SP), sh.grid, sh.wg, comb_lds_bytes(Q, c.dim, c.head_num), m->stream, a);
+    });
     return;
   }
   const KhGemvResArgs a = fill_wo(m, l);
-  KH_DISPATCH4(k_gemv_res, qn, m->sh_wo.u, kh_stage_maxv(c.dim, kh_launch_wg), m->sh_wo.split, m->sh_wo.grid,
-               fused_lds_bytes(qn, c.dim), m->stream, a);
+  pick_fused<FusedU, FusedMV, GemvResSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split,
+                                         [&](auto Q, auto U, auto MV, auto SP) {
+    kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
+  });
 }
 void launch_ffn13(kh_model* m, int l) {
   const kh_config& c = m->cfg;
@@ -349,14 +261,16 @@ void launch_ffn13(kh_model* m, int l) {
   a.hidden = c.hidden_dim;
   a.gshift = m->gshift;
   a.eps = c.rms_eps;
-  const bool qn = c.is_quant;
+  // the int8 LDS-DMA ring kernels (kh_fused_ring.h): 2 ring slots per wave, 4 float4 staged per thread, plain layout
   if (m->ring.ffn_r == 2) {  // plan_ring: int8, dim a multiple of 256 floats and at most 16 per thread
-    KH_LRING(k_ffn13_ring, 2, 4, m->ring.ffn_grid, ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
+    kh_launch(KH_KERNEL(k_ffn13_ring, 2, 4, false), m->ring.ffn_grid, KH_WG,
+              ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
-  const int kh_launch_wg = m->sh_ffn.wg;
-  KH_DISPATCH3(k_ffn13, qn, m->sh_ffn.u, kh_stage_maxv(c.dim, kh_launch_wg), m->sh_ffn.grid,
-               fused_lds_bytes(qn, c.dim), m->stream, a);
+  const kh_model::Shape& sh = m->sh_ffn;
+  pick_fused<FusedU, FusedMV, NoSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto Q, auto U, auto MV, auto) {
+    kh_launch(KH_KERNEL(k_ffn13, Q, U, MV), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
+  });
 }
 void launch_w2(kh_model* m, int l) {
   const kh_config& c = m->cfg;
@@ -367,15 +281,11 @@ void launch_w2(kh_model* m, int l) {
   a.M = c.hidden_dim;
   a.K = c.dim;
   a.gshift = m->gshift;
-  const bool qn = c.is_quant;
-  const int kh_launch_wg = m->sh_w2.wg;
-  const int mv = kh_stage_maxv(c.hidden_dim, kh_launch_wg);
-  if (qn && m->sh_w2.u == 3) {  // two exact tiles of three loads per row (pick_shape, u3)
-    KH_SEL_MV4X(k_gemv_res, true, 3, mv, m->sh_w2.split, m->sh_w2.grid, fused_lds_bytes(qn, c.hidden_dim), m->stream, a);
-    return;
-  }
-  KH_DISPATCH4X(k_gemv_res, qn, m->sh_w2.u, mv, m->sh_w2.split, m->sh_w2.grid,
-                fused_lds_bytes(qn, c.hidden_dim), m->stream, a);
+  const kh_model::Shape& sh = m->sh_w2;  // int8 u 3: two exact tiles of three loads per row (pick_shape, u3)
+  pick_fused<GemvResU, GemvResMV, GemvResSP>(c.is_quant, sh.u, kh_stage_maxv(c.hidden_dim, sh.wg), sh.split,
+                                             [&](auto Q, auto U, auto MV, auto SP) {
+    kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.hidden_dim), m->stream, a);
+  });
 }
 void launch_cls(kh_model* m) {
   const kh_config& c = m->cfg;
@@ -392,14 +302,15 @@ void launch_cls(kh_model* m) {
   a.gshift = m->gshift;
   a.eps = c.rms_eps;
   // the classifier is int8 only when the model is quantised (untied; llama3.cpp:255-268)
-  const bool qn = c.is_quant;
   if (m->ring.cls_r == 2) {
-    KH_LRING(k_cls_ring, 2, 4, m->ring.cls_grid, ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
+    kh_launch(KH_KERNEL(k_cls_ring, 2, 4, false), m->ring.cls_grid, KH_WG,
+              ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
-  const int kh_launch_wg = m->sh_cls.wg;
-  KH_DISPATCH3(k_cls, qn, m->sh_cls.u, kh_stage_maxv(c.dim, kh_launch_wg), m->sh_cls.grid, cls_lds_bytes(qn, c.dim),
-               m->stream, a);
+  const kh_model::Shape& sh = m->sh_cls;
+  pick_fused<FusedU, FusedMV, NoSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto Q, auto U, auto MV, auto) {
+    kh_launch(KH_KERNEL(k_cls, Q, U, MV), sh.grid, sh.wg, cls_lds_bytes(Q, c.dim), m->stream, a);
+  });
 }
 void launch_sample(kh_model* m, int advance, int n_forced) {
   const kh_config& c = m->cfg;
@@ -469,7 +380,6 @@ int step_variant(const kh_model* m, int pos_lo, int pos_hi) {
 }
 // one fused decode step = 5L + 2 launches.  ev (optional) receives an event after each launch.
 void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, int variant) {
-  m->step_var = variant;
   int e = 0;
   auto mark = [&]() {
     if (ev) (void)hipEventRecord(ev[e++], m->stream);
@@ -478,9 +388,9 @@ void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, i
   for (int l = 0; l < m->cfg.layer_num; ++l) {
     launch_qkv(m, l);
     mark();
-    launch_attn(m, l);
+    launch_attn(m, l, variant);
     mark();
-    launch_wo(m, l);
+    launch_wo(m, l, variant);
     mark();
     launch_ffn13(m, l);
     mark();
@@ -699,19 +609,19 @@ int configure_step_kernels(kh_model* m) {
   const size_t lds_need = fused_lds_bytes(c.is_quant, c.hidden_dim);
   if (lds_need > 160 * 1024) return KH_ERR_UNSUPPORTED;
   if (lds_need > 64 * 1024) {
-    const int v = (int)lds_need;
-#define KH_ATTR(Q, UU, SP)                                                                     \
-  (void)hipFuncSetAttribute((const void*)k_gemv_res<Q, UU, 0, SP>,                             \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, v);                    \
-  (void)hipFuncSetAttribute((const void*)k_gemv_res<Q, UU, 6, SP>,                             \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, v)
-    KH_ATTR(false, 8, 1); KH_ATTR(false, 8, 2); KH_ATTR(false, 8, 4);
-    KH_ATTR(false, 4, 1); KH_ATTR(false, 4, 2); KH_ATTR(false, 4, 4);
-    KH_ATTR(false, 2, 1); KH_ATTR(false, 2, 2); KH_ATTR(false, 2, 4);
-    KH_ATTR(true, 4, 1); KH_ATTR(true, 4, 2); KH_ATTR(true, 4, 4);
-    KH_ATTR(true, 3, 1); KH_ATTR(true, 3, 2); KH_ATTR(true, 3, 4);
-    KH_ATTR(true, 2, 1); KH_ATTR(true, 2, 2); KH_ATTR(true, 2, 4);
-#undef KH_ATTR
+    auto opt_in = [&](auto Q) {  // every k_gemv_res that w2 can launch on such an input: MAXV 0 and 6
+      GemvResU<decltype(Q)::value>::each([&](auto U) {
+        GemvResSP::each([&](auto SP) {
+          KhVals<0, 6>::each([&](auto MV) {
+            (void)hipFuncSetAttribute(
+                (const void*)k_gemv_res<decltype(Q)::value, decltype(U)::value, decltype(MV)::value, decltype(SP)::value>,
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need);
+          });
+        });
+      });
+    };
+    opt_in(std::false_type{});
+    opt_in(std::true_type{});
   }
   return KH_OK;
 }

@@ -126,8 +126,10 @@ def test_debug_hooks_live_in_one_table_not_in_getenv(lib, monkeypatch):
 def test_launch_log_hook_and_qkv_split_limit(lib):
     """KH_LAUNCH_LOG: kh_debug_launch_log reads the set of launched kernel instantiations like kh_debug_list (bytes
     needed, NUL-terminated, truncated to the buffer); setting, resetting and unsetting the hook leave it empty (no
-    launch here: no device).  Every decode-GEMV and B-token prefill launch in the step / prefill sources goes through
-    a site that logs it.  The qkv shape hook refuses split 4 (qkv's SPLIT = 4 kernels are not compiled)."""
+    launch here: no device).  Every decode-GEMV, screened-classifier, B-token and GEMM prefill launch in the step /
+    prefill / screen sources goes through the helper that logs it (kh_dispatch.h: kh_launch(KH_KERNEL(...))): those
+    sources launch nothing but plain, non-template kernels themselves, and spell an instantiation of the logged
+    families nowhere else (but for an LDS opt-in).  The qkv shape hook refuses split 4 (qkv's SPLIT = 4 kernels are not compiled)."""
     import re
     assert lib.kh_debug_launch_log(None, 0) == 1
     _ffi.debug_set("KH_LAUNCH_LOG", "1")
@@ -140,13 +142,20 @@ def test_launch_log_hook_and_qkv_split_limit(lib):
     _ffi.debug_set("KH_LAUNCH_LOG", None)
     assert _ffi.launch_log() == set() and _ffi.debug_get("KH_LAUNCH_LOG") is None
     csrc = os.path.join(ROOT, "kuiperllama_amd", "csrc")
-    for f in ("kh_model_step.hip", "kh_model_prefill.hip"):
-        lines = open(os.path.join(csrc, f)).read().splitlines()
-        for i, ln in enumerate(lines):
-            if re.search(r"(hipLaunchKernelGGL\(\(|pf_launch\()(KERNEL|k_qkv|k_gemv_res|k_wo_comb|k_ffn13|k_cls|k_pf_)",
-                         ln):
-                near = "\n".join(lines[max(0, i - 2):i + 1])
-                assert "launch_log(" in near or "pf_log(" in near, f"{f}:{i + 1}: launch without a launch-log entry"
+    family = r"k_qkv|k_gemv_res|k_wo_comb|k_ffn13|k_cls|k_ffn13_ring|k_cls_ring|k_cls_screen|k_sample_screen|k_pf_gemv_res|k_pf_qkv|k_pf_ffn13|k_pg_gemm"
+    for f in ("kh_model_step.hip", "kh_model_prefill.hip", "kh_model_screen.hip"):
+        src = open(os.path.join(csrc, f)).read()
+        assert "<<<" not in src, f
+        # a direct launch names a plain kernel: not an instantiation (k<...>), not a kernel passed in as a value
+        for m in re.finditer(r"hipLaunchKernelGGL\(\s*([^,]*),", src):
+            where = f"{f}:{src.count(chr(10), 0, m.start()) + 1}"
+            assert re.fullmatch(r"k_[a-z0-9_]+", m.group(1)), f"{where}: launch outside kh_launch"
+        # an instantiation of the families is spelled by KH_KERNEL alone (which hands it to the logging helper)
+        for m in re.finditer(r"\b(%s)\s*<" % family, src):
+            where = f"{f}:{src.count(chr(10), 0, m.start()) + 1}"
+            assert "hipFuncSetAttribute(" in src[max(0, m.start() - 120):m.start()], f"{where}: instantiation outside KH_KERNEL"
+        sites = re.findall(r"(?:\b(?:kh_launch|pf_launch)\(|\bkh_launch_prep\(\w+, )KH_KERNEL\(", src)
+        assert len(sites) == src.count("KH_KERNEL(") > 0, f"{f}: KH_KERNEL outside a logging launch"
     base = _ffi.plan_decode_shapes(2048, 8192, 512, 128256, False)["qkv"]
     _ffi.debug_set("KH_SHAPE_QKV", "2,4,64,512")
     assert _ffi.plan_decode_shapes(2048, 8192, 512, 128256, False)["qkv"] == {"split": 2, "u": 4, "grid": 64, "wg": 512}

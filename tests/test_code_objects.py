@@ -28,7 +28,9 @@ def test_no_kernel_uses_scratch_and_step_kernels_exist():
 def test_qkv_is_compiled_for_its_reachable_splits_only():
     """k_qkv's shape is never split more than twice (plan_decode_shapes: max_split 2; the KH_SHAPE_QKV hook rejects 4),
     so the library compiles SPLIT 1 and 2 only: 40 instantiations = fp32 U 8/4/2 and int8 U 4/2, times MAXV 4/2/1/0,
-    times SPLIT 1/2.  The mangled-name reader of code_objects.py must also read the arguments back."""
+    times SPLIT 1/2.  The mangled-name reader of code_objects.py must also read the arguments back.
+    Every other kernel picked from per-parameter value lists (kh_dispatch.h) is pinned the same way: the lists of its
+    launch site compile exactly these products, 265 instantiations in all."""
     assert co.template_name("_Z5k_qkvILb0ELi2ELi0ELi1EEv9KhQkvArgs") == "k_qkv<false,2,0,1>"
     assert co.template_name("_Z12k_ffn13_ringILi2ELi4ELb0E9StagerAsmILb1ELi4ELi0EEEv11KhFfn13Args") == \
         "k_ffn13_ring<2,4,false>"
@@ -36,6 +38,29 @@ def test_qkv_is_compiled_for_its_reachable_splits_only():
     want = {f"k_qkv<{q},{u},{mv},{sp}>" for q, us in (("false", (8, 4, 2)), ("true", (4, 2))) for u in us
             for mv in (4, 2, 1, 0) for sp in (1, 2)}
     assert qkv == want, (sorted(qkv - want), sorted(want - qkv))
+    notes = _code_object_notes()
+    Q = (("false", (8, 4, 2)), ("true", (4, 2)))  # <QUANT, U ...>: U as k_qkv's
+    want = {
+        "k_gemv_res": {f"k_gemv_res<{q},{u},{mv},{sp}>" for q, us in (("false", (8, 4, 2)), ("true", (4, 3, 2)))
+                       for u in us for mv in (6, 4, 2, 1, 0) for sp in (1, 2, 4)},
+        "k_wo_comb": {f"k_wo_comb<{q},{u},{mv},{sp}>" for q, us in Q for u in us for mv in (2, 4) for sp in (1, 2, 4)},
+        "k_ffn13": {f"k_ffn13<{q},{u},{mv}>" for q, us in Q for u in us for mv in (4, 2, 1, 0)},
+        "k_cls": {f"k_cls<{q},{u},{mv}>" for q, us in Q for u in us for mv in (4, 2, 1, 0)},
+        "k_ffn13_ring": {"k_ffn13_ring<2,4,false>"},
+        "k_cls_ring": {"k_cls_ring<2,4,false>"},
+        "k_cls_screen": {f"k_cls_screen<{u},{mv}>" for u in (4, 2) for mv in (4, 2, 1)},
+        "k_sample_screen": {f"k_sample_screen<{u},{mv}>" for u in (8, 4, 2) for mv in (4, 2, 1)},
+        "k_pf_gemv_res": {f"k_pf_gemv_res<{q},{sp},{b}>" for q, bs in (("false", (8, 4, 2)), ("true", (4, 2)))
+                          for sp in (1, 2, 4) for b in bs},
+        "k_pf_qkv": {f"k_pf_qkv<{q},{sp},{b}>" for q, bs in (("false", (8, 4)), ("true", (4,))) for sp in (1, 2) for b in bs},
+        "k_pf_ffn13": {f"k_pf_ffn13<{q},{b}>" for q, bs in (("false", (8, 4)), ("true", (4,))) for b in bs},
+        "k_pg_gemm": {f"k_pg_gemm<{q},{r},{nt},{epi}>" for q in ("false", "true")
+                      for r, nt in ((2, 8), (2, 4), (2, 2), (1, 4)) for epi in (0, 1, 2)},
+    }
+    assert len(qkv) + sum(len(w) for w in want.values()) == 265
+    for stem, w in want.items():
+        got = co.instantiations(notes, {stem})
+        assert got == w, (stem, sorted(got - w), sorted(w - got))
 
 
 def test_plain_kernel_names_are_read_back():

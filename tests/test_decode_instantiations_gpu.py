@@ -1,8 +1,8 @@
 """Every decode-GEMV kernel instantiation the library compiles, launched and checked against an fp64 gold.
 
 The fused decode step picks one instantiation of k_qkv / k_gemv_res (wo, w2) / k_wo_comb / k_ffn13 / k_cls
-<QUANT, U, MAXV, SPLIT> per launch from the shape plan, the staging depth kh_stage_maxv(M, wg) and the KH_SEL_*
-macros; the int8 ffn13 / classifier launches may run on the LDS-DMA ring kernels, and the B-token prefill has its own
+<QUANT, U, MAXV, SPLIT> per launch from the shape plan, the staging depth kh_stage_maxv(M, wg) and the value lists
+of its launch site (kh_dispatch.h: kh_pick); the int8 ffn13 / classifier launches may run on the LDS-DMA ring kernels, and the B-token prefill has its own
 k_pf_* family.  The heuristic shapes of the model geometries elsewhere in the suite reach only a few of them.  Here a
 handful of seeded geometries - each 2 layers, a small odd vocabulary, 1024 cache rows - are run under forced shapes
 (hooks KH_SHAPE_<QKV|WO|FFN|W2|CLS> = "split,u,grid,wg", workgroups of 256 and 512 threads) so that every staging
