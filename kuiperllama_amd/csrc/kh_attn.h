@@ -1039,6 +1039,12 @@ static inline int attn_wg_hook() {
   }
   return KH_WG_MAX;
 }
+// KH_ATTN_FENCED=1 hook -> the fenced form of the in-launch split merge.  The ONE reader (model level: finish_create;
+// operator level: launch_mha_fast).
+static inline bool attn_fenced_hook() {
+  const char* e = khm::dbg("KH_ATTN_FENCED");
+  return e && e[0] == '1';
+}
 
 // Launch.  a.nsplit_g == 0 disables the group path; head_size > 32 required (callers route
 // smaller heads to the generic LDS-score kernel).

@@ -1,5 +1,5 @@
 // kh_model_internal.h — state and cross-unit helpers of the model level of the C-ABI.
-// The model level is split into four translation units:
+// The model level is split into six translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
@@ -7,6 +7,8 @@
 //   kh_model_prefill.hip  B-token VALU prefill and the MFMA GEMM prefill (kh_prefill.h, kh_gemm.h,
 //                         kh_pattn.h kernels)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
+//   kh_model_screen.hip   the screened classifier of the greedy generate loop (kh_cls_screen.h kernels)
+//   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge and the screen
 // gfx950 only.  No CPU fallback: every path launches HIP kernels.
 #pragma once
 #include <new>
@@ -146,9 +148,7 @@ struct kh_model {
     hipGraph_t g = nullptr;
     hipGraphExec_t e = nullptr;
   };
-  // [sampler][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps, with the greedy k_sample (0) or
-  // the sampling k_sample_topp (1) as the last launch of every step
-  // ... or (2) the screened classifier pair k_cls_screen + k_sample_screen (greedy steps of a generate, see scr)
+  // [StepTail][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps per tail of the step
   StepGraph sg[3][KH_STEP_VARIANTS][4];
   // kh_model_set_sampling: the parameters (host copy), whether they sample (temperature > 0), and their device copy,
   // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
@@ -169,11 +169,9 @@ struct kh_model {
     int32_t* ov_idx = nullptr;
     uint32_t* ticket = nullptr;
     int32_t* stats = nullptr;  // steps, candidate rows, overflow steps
-    float *dbg_lb = nullptr, *dbg_ub = nullptr;  // set by the self-test only
     int u = 4, grid = 1, wg = KH_WG, sgrid = 1;  // launch of k_cls_screen; workgroups of k_sample_screen
     size_t bytes = 0;          // HBM the copy and its tables take
     float build_ms = 0.f;      // time of the conversion kernel
-    bool now = false;          // the launches being enqueued / captured use the screened pair
     bool stale = false;        // the logits buffer is older than the last step: refresh from x_save on demand
   };
   ClsScreen scr;
@@ -197,35 +195,72 @@ void plan_decode_shapes(bool quant, int dim, int hidden_dim, int kv_dim, int voc
 // which int8 GEMVs of a decode step run on the LDS-DMA ring kernels, and their launch geometry (host-only)
 void plan_ring(bool quant, int dim, int hidden_dim, int vocab_size, int group_size, kh_model::RingPlan* out);
 int configure_step_kernels(kh_model* m);  // >64 KiB dynamic-LDS opt-in of the hidden-sized GEMVs
-// variant (see kh_model::sg, step_variant): which attention / wo pair is launched
-KhAttnArgs fill_attn(kh_model* m, int l, int variant);
+// What a launch helper does beyond the model's plan is an argument, never a field of *m changed around the call.
+// variant (see kh_model::sg, step_variant): which attention / wo pair is launched; fenced: the form of the in-launch
+// split merge (m->attn_fenced, but for the self-test that compares the two)
+KhAttnArgs fill_attn(kh_model* m, int l, int variant, bool fenced);
 void launch_qkv(kh_model* m, int l);
-void launch_attn(kh_model* m, int l, int variant);
+void launch_attn(kh_model* m, int l, int variant, bool fenced);
 void launch_wo(kh_model* m, int l, int variant);
-void launch_ffn13(kh_model* m, int l);
+void launch_ffn13(kh_model* m, int l, bool ring);  // ring: the LDS-DMA ring kernel (m->ring.ffn_r), else register tiles
 void launch_w2(kh_model* m, int l);
-void launch_cls(kh_model* m);
-// the step's last launch: k_sample (argmax), or k_sample_topp while m->samp_on
-void launch_sample(kh_model* m, int advance, int n_forced);
+// what a classifier launch reads and writes; the model's own buffers and plan: launch_cls(m)
+struct ClsIo {
+  const float* x;
+  float *logits, *part_val;
+  int32_t* part_idx;
+};
+void launch_cls(kh_model* m, const ClsIo& io, bool ring);
+static inline void launch_cls(kh_model* m) {
+  launch_cls(m, {m->x, m->logits, m->part_val, m->part_idx}, m->ring.cls_r == 2);
+}
+// a classifier launch has written the model's own logits buffer (kh_model_get_logits need not re-run k_cls)
+static inline void logits_fresh(kh_model* m) { m->scr.stale = false; }
+// The last two launches of a fused step, and the index of kh_model::sg its graphs live in: k_cls + k_sample (argmax),
+// k_cls + k_sample_topp, or the screened pair k_cls_screen + k_sample_screen (greedy steps of a generate, see scr)
+enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2 };
+// sampling needs every logit: it is stronger than a caller's wish to screen
+static inline StepTail step_tail(const kh_model* m, bool screen) {
+  return m->samp_on ? kSample : screen ? kScreen : kGreedy;
+}
+// the fields every step tail shares: KhSampleArgs, KhSampleTopArgs and KhSampleScreenArgs name them alike
+template <class A>
+void fill_step_tail(const kh_model* m, int advance, int n_forced, A* a) {
+  a->forced = n_forced > 0 ? m->d_forced : nullptr;
+  a->n_forced = n_forced;
+  a->words = m->d_words;
+  a->words_cap = m->seq_cap;
+  a->d_next = m->d_next;
+  a->d_token = m->d_token;
+  a->d_pos = m->d_pos;
+  a->tok_emb = m->tok_emb;
+  a->x = m->x;
+  a->dim = m->cfg.dim;
+  a->vocab = m->cfg.vocab_size;
+  a->advance = advance;
+}
+// the step's last launch
+void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail);
 // the variant of the steps at positions pos_lo .. pos_hi
 int step_variant(const kh_model* m, int pos_lo, int pos_hi);
-void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, int variant);
+void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, int variant, StepTail tail);
 int launch_step_unfused(kh_model* m, int pos);
 void set_state(kh_model* m, int token, int pos);
 int ensure_pinned_words(kh_model* m, int n);
 int ensure_seq_cap(kh_model* m, int n);
 void destroy_step_graphs(kh_model* m);
-// the captured graph of 1 (steps8 = false) or KH_GRAPH_STEPS decode steps in `variant`, captured on first use
-int step_graph(kh_model* m, int n_forced, int variant, bool steps8, hipGraphExec_t* out);
-// the same for a graph of `nsteps` in {1, 2, 4, 8} steps (the tail of a run: 20 steps = 8 + 8 + 4)
-int step_graph_n(kh_model* m, int n_forced, int variant, int nsteps, hipGraphExec_t* out);
-// index of kh_model::sg the launches enqueued right now belong to
-static inline int sg_sampler(const kh_model* m) { return m->samp_on ? 1 : (m->scr.now ? 2 : 0); }
+// the captured graph of `nsteps` in {1, 2, 4, 8} decode steps in `variant` ending in `tail`, captured on first use
+int step_graph(kh_model* m, int n_forced, int variant, int nsteps, StepTail tail, hipGraphExec_t* out);
+// Enqueue the steps at positions pos .. pos + nsteps - 1 behind whatever set the state: one replay of their captured
+// graph (exec KH_EXEC_GRAPH) or eager launches (KH_EXEC_FUSED).  Picks the variant; records whether the logits buffer
+// is left behind the steps (scr.stale).
+int enqueue_steps(kh_model* m, int pos, int nsteps, int n_forced, StepTail tail, int exec);
 // ---- kh_model_screen.hip --------------------------------------------------------------------
 int cls_screen_create(kh_model* m);   // bf16 copy + tables, once the weights are resident (no-op where it does not apply)
 void cls_screen_release(kh_model* m);
 bool cls_screen_wanted(const kh_model* m);  // may this generate screen? (sampler, hooks)
-void launch_cls_screen(kh_model* m);
+// dbg_lb / dbg_ub [vocab] (optional): receive every row's interval
+void launch_cls_screen(kh_model* m, float* dbg_lb = nullptr, float* dbg_ub = nullptr);
 void launch_sample_screen(kh_model* m, int advance, int n_forced);
 int cls_refresh_logits(kh_model* m);  // k_cls on the saved input if the logits buffer is stale
 int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result);

@@ -186,7 +186,7 @@ void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0
     // written, its attention, wo and FFN feed nothing
     if (l == c.layer_num - 1) break;
     {
-      KhAttnArgs a = fill_attn(m, l, /*variant=*/0);
+      KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
       a.defer = 0;  // multi-token slices merge in the launch
       a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: launch_attn_decode decides from the slice's positions
       a.q = m->pf_q;
@@ -481,7 +481,7 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
       a.T = T; a.pos0 = pos0; a.layout = q ? KH_PA_TILED_Q8 : KH_PA_TILED_F32; a.tcap = tcap;
       launch_pg_attn(a, c.head_size, m->stream);
     } else {
-      KhAttnArgs a = fill_attn(m, l, /*variant=*/0);
+      KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
       a.defer = 0;  // multi-token slices merge in the launch
       a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: launch_attn_decode decides from the slice's positions
       a.q = m->pg_q;
@@ -625,21 +625,19 @@ extern "C" int kh_model_time_prefill(kh_model* m, const int32_t* h_tokens, int32
                                 hipMemcpyHostToDevice, m->stream));
     KH_CHECK_HIP(hipStreamSynchronize(m->stream));
     const int n_forced = m->seq_cap + 1;
+    const StepTail tail = step_tail(m, false);
     // capture (first use) outside the timed region
     hipGraphExec_t ge = nullptr;
     for (int s = 0; s < n;) {
-      const bool n8 = n - s >= KH_GRAPH_STEPS;
-      const int k = n8 ? KH_GRAPH_STEPS : 1;
-      if ((rc = step_graph(m, n_forced, step_variant(m, pos0 + s, pos0 + s + k - 1), n8, &ge)) != KH_OK) return rc;
+      const int k = n - s >= KH_GRAPH_STEPS ? KH_GRAPH_STEPS : 1;
+      if ((rc = step_graph(m, n_forced, step_variant(m, pos0 + s, pos0 + s + k - 1), k, tail, &ge)) != KH_OK) return rc;
       s += k;
     }
     set_state(m, h_tokens[0], pos0);
     KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
     for (int s = 0; s < n;) {
-      const bool n8 = n - s >= KH_GRAPH_STEPS;
-      const int k = n8 ? KH_GRAPH_STEPS : 1;
-      if ((rc = step_graph(m, n_forced, step_variant(m, pos0 + s, pos0 + s + k - 1), n8, &ge)) != KH_OK) return rc;
-      KH_CHECK_HIP(hipGraphLaunch(ge, m->stream));
+      const int k = n - s >= KH_GRAPH_STEPS ? KH_GRAPH_STEPS : 1;
+      if ((rc = enqueue_steps(m, pos0 + s, k, n_forced, tail, KH_EXEC_GRAPH)) != KH_OK) return rc;
       s += k;
     }
     KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));

@@ -24,12 +24,12 @@ extern "C" int kh_model_profile_kernel(kh_model* m, int32_t kclass, int32_t pos,
   auto sweep = [&]() {
     for (int l = 0; l < n_inner; ++l) switch (kclass) {
         case KH_K_QKV: launch_qkv(m, l); break;
-        case KH_K_ATTN: launch_attn(m, l, variant); break;
+        case KH_K_ATTN: launch_attn(m, l, variant, m->attn_fenced); break;
         case KH_K_WO: launch_wo(m, l, variant); break;
-        case KH_K_FFN13: launch_ffn13(m, l); break;
+        case KH_K_FFN13: launch_ffn13(m, l, m->ring.ffn_r == 2); break;
         case KH_K_W2: launch_w2(m, l); break;
         case KH_K_CLS: launch_cls(m); break;
-        default: launch_sample(m, /*advance=*/0, /*n_forced=*/0); break;
+        default: launch_sample(m, /*advance=*/0, /*n_forced=*/0, step_tail(m, false)); break;
       }
   };
   // The sweeps are captured into a graph and replayed: a 3-4 us kernel finishes faster than the
@@ -71,12 +71,13 @@ extern "C" int kh_model_time_step(kh_model* m, int32_t pos, int32_t reps, float*
   int rc;
   if ((rc = kv_ensure(m, pos + 1)) != KH_OK) return rc;
   if ((rc = ensure_seq_cap(m, pos + 1)) != KH_OK) return rc;
-  hipGraphExec_t ge = nullptr;
-  if ((rc = step_graph(m, m->seq_cap + 1, step_variant(m, pos, pos), false, &ge)) != KH_OK) return rc;
+  const StepTail tail = step_tail(m, false);
+  hipGraphExec_t ge = nullptr;  // capture (first use) outside the timed region
+  if ((rc = step_graph(m, m->seq_cap + 1, step_variant(m, pos, pos), 1, tail, &ge)) != KH_OK) return rc;
   for (int r = 0; r < reps; ++r) {
     set_state(m, 1 % m->cfg.vocab_size, pos);
     KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
-    KH_CHECK_HIP(hipGraphLaunch(ge, m->stream));
+    if ((rc = enqueue_steps(m, pos, 1, m->seq_cap + 1, tail, KH_EXEC_GRAPH)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));
     KH_CHECK_HIP(hipEventSynchronize(m->ev1));
     float ms = 0.f;
@@ -105,13 +106,17 @@ extern "C" int kh_model_profile_step(kh_model* m, int32_t start_pos, int32_t n_s
   const int L = c.layer_num;
   const int nk = 5 * L + 2;
   std::vector<hipEvent_t> ev((size_t)nk + 1);
-  for (auto& e : ev) KH_CHECK_HIP(hipEventCreate(&e));
+  int rc = KH_OK;
+  for (auto& e : ev)
+    if (hipError_t he = hipEventCreate(&e); he != hipSuccess) {
+      rc = (int)he;
+      break;
+    }
   double acc[KH_NUM_KCLASS] = {0};
   int cnt[KH_NUM_KCLASS] = {0};
   set_state(m, 1 % c.vocab_size, start_pos);
-  int rc = KH_OK;
   for (int s = 0; s < n_steps && rc == KH_OK; ++s) {
-    launch_step_fused(m, 1, 0, ev.data(), step_variant(m, start_pos + s, start_pos + s));
+    launch_step_fused(m, 1, 0, ev.data(), step_variant(m, start_pos + s, start_pos + s), step_tail(m, false));
     hipError_t e = hipStreamSynchronize(m->stream);
     if (e != hipSuccess) {
       rc = (int)e;
@@ -129,7 +134,8 @@ extern "C" int kh_model_profile_step(kh_model* m, int32_t start_pos, int32_t n_s
       cnt[cls] += 1;
     }
   }
-  for (auto& e : ev) (void)hipEventDestroy(e);
+  for (auto& e : ev)
+    if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < KH_NUM_KCLASS; ++k) {
     h_avg_us[k] = cnt[k] ? (float)(acc[k] / cnt[k]) : 0.f;
     h_count[k] = cnt[k] / n_steps;

@@ -140,7 +140,7 @@ int cls_screen_create(kh_model* m) {
   return KH_OK;
 }
 
-void launch_cls_screen(kh_model* m) {
+void launch_cls_screen(kh_model* m, float* dbg_lb, float* dbg_ub) {
   const kh_config& c = m->cfg;
   const kh_model::ClsScreen& s = m->scr;
   KhClsScreenArgs a;
@@ -153,8 +153,8 @@ void launch_cls_screen(kh_model* m) {
   a.p_spill = s.p_spill;
   a.p_ub = s.p_ub;
   a.p_idx = s.p_idx;
-  a.dbg_lb = s.dbg_lb;
-  a.dbg_ub = s.dbg_ub;
+  a.dbg_lb = dbg_lb;
+  a.dbg_ub = dbg_ub;
   a.dim = c.dim;
   a.vocab = c.vocab_size;
   a.eps = c.rms_eps;
@@ -180,18 +180,7 @@ void launch_sample_screen(kh_model* m, int advance, int n_forced) {
   a.ov_idx = s.ov_idx;
   a.ticket = s.ticket;
   a.stats = s.stats;
-  a.forced = n_forced > 0 ? m->d_forced : nullptr;
-  a.n_forced = n_forced;
-  a.words = m->d_words;
-  a.words_cap = m->seq_cap;
-  a.d_next = m->d_next;
-  a.d_token = m->d_token;
-  a.d_pos = m->d_pos;
-  a.tok_emb = m->tok_emb;
-  a.x = m->x;
-  a.dim = c.dim;
-  a.vocab = c.vocab_size;
-  a.advance = advance;
+  fill_step_tail(m, advance, n_forced, &a);
   // k_cls's own U, staging depth and workgroup width: the re-scored values are then k_cls's, bit for bit
   const int wg = m->sh_cls.wg;
   pick_screen<SampleScreenU>(m->sh_cls.u, kh_stage_maxv(c.dim, wg), [&](auto U, auto MV) {
@@ -202,10 +191,8 @@ void launch_sample_screen(kh_model* m, int advance, int n_forced) {
 int cls_refresh_logits(kh_model* m) {
   if (!m->scr.stale) return KH_OK;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
-  float* const x = m->x;
-  m->x = m->scr.x_save;  // the input the last screened step saw; today's k_cls instantiation on the same bytes
-  launch_cls(m);         // (clears scr.stale)
-  m->x = x;
+  // the input the last screened step saw; today's k_cls instantiation on the same bytes (clears scr.stale)
+  launch_cls(m, {m->scr.x_save, m->logits, m->part_val, m->part_idx}, m->ring.cls_r == 2);
   return kh_launch_status();
 }
 
@@ -222,6 +209,32 @@ __global__ __launch_bounds__(KH_WG) void k_st_interval(const float* lg, const fl
 }
 }  // namespace
 
+// One screened pair, then one full pair, on the vector now in m->x, without advancing: tok[0] / tok[1] receive the two
+// tokens, and the model's logits buffer holds k_cls's logits of that vector afterwards.  Every row's interval goes to
+// two arrays that live for this call: then(lb, ub) enqueues the caller's reads of them behind the pairs and ahead of
+// the stream sync that ends the body.
+template <class F>
+static int cls_screen_pairs(kh_model* m, int32_t* tok, F&& then) {
+  hipStream_t st = m->stream;
+  const size_t V = (size_t)m->cfg.vocab_size;
+  float *lb = nullptr, *ub = nullptr;
+  int rc;
+  if ((rc = dalloc(&lb, V)) == KH_OK && (rc = dalloc(&ub, V)) == KH_OK) {
+    launch_cls_screen(m, lb, ub);
+    launch_sample(m, /*advance=*/0, /*n_forced=*/0, kScreen);
+    hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    launch_cls(m);
+    launch_sample(m, 0, 0, kGreedy);
+    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = then(lb, ub);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = (int)e;
+  }
+  if (lb) (void)hipFree(lb);
+  if (ub) (void)hipFree(ub);
+  return rc;
+}
+
 // One screened step against one full step on a fixed vector (the embedding row of token 1): the same token, every
 // full logit inside the interval the screen gave its row.  *result: 0 not applicable, 1 passed, -1 failed ->
 // screening off for this model.
@@ -232,32 +245,17 @@ int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) 
   if (!s.on) return KH_OK;
   hipStream_t st = m->stream;
   const size_t V = (size_t)c.vocab_size;
-  int rc = KH_OK;
-  int32_t tok[2] = {-1, -2};
-  if ((rc = dalloc(&s.dbg_lb, V)) == KH_OK && (rc = dalloc(&s.dbg_ub, V)) == KH_OK) {
-    set_state(m, 1 % c.vocab_size, 0);
-    s.now = true;
-    launch_cls_screen(m);
-    launch_sample(m, /*advance=*/0, /*n_forced=*/0);
-    s.now = false;
-    hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    launch_cls(m);
-    launch_sample(m, 0, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  int32_t tok[2] = {-1, -2}, flag = 0;
+  set_state(m, 1 % c.vocab_size, 0);
+  int rc = cls_screen_pairs(m, tok, [&](const float* lb, const float* ub) {
     const size_t g = (V + KH_WG - 1) / KH_WG;
-    hipLaunchKernelGGL(k_st_interval, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(KH_WG), 0, st, m->logits, s.dbg_lb,
-                       s.dbg_ub, V, d_flag);
-    int32_t flag = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = (int)e;
-    if (rc == KH_OK) rc = kh_launch_status();
-    if (rc == KH_OK) *result = (flag || tok[0] != tok[1] || inject) ? -1 : 1;
-  }
-  if (s.dbg_lb) (void)hipFree(s.dbg_lb);
-  if (s.dbg_ub) (void)hipFree(s.dbg_ub);
-  s.dbg_lb = s.dbg_ub = nullptr;
+    hipLaunchKernelGGL(k_st_interval, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(KH_WG), 0, st, m->logits, lb, ub, V,
+                       d_flag);
+    return hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st);
+  });
+  if (rc == KH_OK) rc = kh_launch_status();
   if (rc != KH_OK) return rc;
+  *result = (flag || tok[0] != tok[1] || inject) ? -1 : 1;
   KH_CHECK_HIP(hipMemsetAsync(s.stats, 0, 4 * sizeof(int32_t), st));  // the counters describe the user's steps
   if (*result < 0) {
     fprintf(stderr, "[kh] classifier screen self-test failed (tokens %d / %d): screening is off for this model\n",
@@ -273,7 +271,7 @@ int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) 
 }  // namespace khm
 using namespace khm;
 
-// One screened step and one full step on the caller's residual vector, without advancing (tests): the shape of
+// One screened step and one full step on the caller's residual vector, without advancing (tests): the body of
 // cls_screen_selftest above, through the same two launch functions a generate uses.  out[4]: screened token | full
 // classifier's token | candidate rows re-scored | 1 if the step overflowed.  h_lb / h_ub: every row's interval.  The
 // logits buffer is left holding k_cls's logits of that vector; the residual vector (m->x), the screen's saved input
@@ -281,42 +279,27 @@ using namespace khm;
 // kh_model_cls_screen_info are put back on every path that got as far as reading them.
 extern "C" int kh_model_cls_screen_probe(kh_model* m, const float* h_x, float* h_lb, float* h_ub, int64_t* out) {
   if (!m || !h_x || !h_lb || !h_ub || !out) return KH_ERR_INVALID_ARG;
-  kh_model::ClsScreen& s = m->scr;
+  const kh_model::ClsScreen& s = m->scr;
   if (!s.on || m->samp_on) return KH_ERR_UNSUPPORTED;
   const kh_config& c = m->cfg;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   hipStream_t st = m->stream;
   const size_t V = (size_t)c.vocab_size;
-  int rc = KH_OK;
   int32_t tok[2] = {-1, -2}, h0[4] = {0, 0, 0, 0}, h1[4] = {0, 0, 0, 0};
   KH_CHECK_HIP(hipMemcpyAsync(h0, s.stats, sizeof(h0), hipMemcpyDeviceToHost, st));
   KH_CHECK_HIP(hipStreamSynchronize(st));
-  if ((rc = dalloc(&s.dbg_lb, V)) == KH_OK && (rc = dalloc(&s.dbg_ub, V)) == KH_OK) {
-    hipError_t e = hipMemcpyAsync(m->x, h_x, sizeof(float) * (size_t)c.dim, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-      s.now = true;
-      launch_cls_screen(m);
-      launch_sample(m, /*advance=*/0, /*n_forced=*/0);
-      s.now = false;
-      e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-      launch_cls(m);  // (clears scr.stale: kh_model_get_logits returns this launch's logits)
-      launch_sample(m, 0, 0);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_lb, s.dbg_lb, sizeof(float) * V, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_ub, s.dbg_ub, sizeof(float) * V, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h1, s.stats, sizeof(h1), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    // the user's steps: also behind a failed copy or launch (h0 is pageable, so the copy has left it on return)
-    const hipError_t e2 = hipMemcpyAsync(s.stats, h0, sizeof(h0), hipMemcpyHostToDevice, st);
-    const hipError_t e3 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2 != hipSuccess ? e2 : e3;
-    if (e != hipSuccess) rc = (int)e;
-    if (rc == KH_OK) rc = kh_launch_status();
-  }
-  if (s.dbg_lb) (void)hipFree(s.dbg_lb);
-  if (s.dbg_ub) (void)hipFree(s.dbg_ub);
-  s.dbg_lb = s.dbg_ub = nullptr;
+  hipError_t e = hipMemcpyAsync(m->x, h_x, sizeof(float) * (size_t)c.dim, hipMemcpyHostToDevice, st);
+  int rc = e != hipSuccess ? (int)e : cls_screen_pairs(m, tok, [&](const float* lb, const float* ub) {
+    hipError_t r = hipMemcpyAsync(h_lb, lb, sizeof(float) * V, hipMemcpyDeviceToHost, st);
+    if (r == hipSuccess) r = hipMemcpyAsync(h_ub, ub, sizeof(float) * V, hipMemcpyDeviceToHost, st);
+    if (r == hipSuccess) r = hipMemcpyAsync(h1, s.stats, sizeof(h1), hipMemcpyDeviceToHost, st);
+    return r;
+  });
+  // the user's steps: also behind a failed copy or launch (h0 is pageable, so the copy has left it on return)
+  e = hipMemcpyAsync(s.stats, h0, sizeof(h0), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (rc == KH_OK && e != hipSuccess) rc = (int)e;
+  if (rc == KH_OK) rc = kh_launch_status();
   if (rc != KH_OK) return rc;
   out[0] = tok[0];
   out[1] = tok[1];

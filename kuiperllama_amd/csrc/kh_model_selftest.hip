@@ -68,11 +68,9 @@ static int ring_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
   int rc = KH_OK;
   set_state(m, 1 % c.vocab_size, 0);  // x = a real embedding row
   if (plan.ffn_r) {
-    launch_ffn13(m, 0);  // ring -> h1
+    launch_ffn13(m, 0, /*ring=*/true);  // -> h1
     KH_CHECK_HIP(hipMemcpyAsync(m->h3, m->h1, sizeof(float) * (size_t)c.hidden_dim, hipMemcpyDeviceToDevice, s));
-    m->ring.ffn_r = 0;
-    launch_ffn13(m, 0);  // register tiles -> h1
-    m->ring = plan;
+    launch_ffn13(m, 0, /*ring=*/false);  // register tiles -> h1
     hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.hidden_dim)), dim3(KH_WG), 0, s, (const uint32_t*)m->h1,
                        (const uint32_t*)m->h3, (size_t)c.hidden_dim, d_flag);
   }
@@ -84,19 +82,8 @@ static int ring_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
     if ((rc = dalloc(&tmp_logits, (size_t)c.vocab_size)) == KH_OK && (rc = dalloc(&tmp_pv, np)) == KH_OK &&
         (rc = dalloc(&tmp_pi, np)) == KH_OK) {
       launch_cls(m);  // ring -> logits
-      float* const lg = m->logits;
-      float* const pv = m->part_val;
-      int32_t* const pi = m->part_idx;
-      m->logits = tmp_logits;
-      m->part_val = tmp_pv;
-      m->part_idx = tmp_pi;
-      m->ring.cls_r = 0;
-      launch_cls(m);  // register tiles -> tmp
-      m->ring = plan;
-      m->logits = lg;
-      m->part_val = pv;
-      m->part_idx = pi;
-      hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.vocab_size)), dim3(KH_WG), 0, s, (const uint32_t*)lg,
+      launch_cls(m, {m->x, tmp_logits, tmp_pv, tmp_pi}, /*ring=*/false);  // register tiles -> tmp
+      hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.vocab_size)), dim3(KH_WG), 0, s, (const uint32_t*)m->logits,
                          (const uint32_t*)tmp_logits, (size_t)c.vocab_size, d_flag);
     }
   }
@@ -130,12 +117,10 @@ static int attn_merge_case(kh_model* m, int pos, int variant, int32_t* d_flag) {
   const kh_config& c = m->cfg;
   hipStream_t s = m->stream;
   set_state(m, 1 % c.vocab_size, pos);
-  m->attn_fenced = true;
-  launch_attn(m, 0, variant);
+  launch_attn(m, 0, variant, /*fenced=*/true);
   KH_CHECK_HIP(hipMemcpyAsync(m->rms, m->att, sizeof(float) * (size_t)c.dim, hipMemcpyDeviceToDevice, s));
-  m->attn_fenced = false;
   for (int i = 0; i < KH_SELFTEST_ATTN_LAUNCHES; ++i) {
-    launch_attn(m, 0, variant);
+    launch_attn(m, 0, variant, /*fenced=*/false);
     hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.dim)), dim3(KH_WG), 0, s, (const uint32_t*)m->att,
                        (const uint32_t*)m->rms, (size_t)c.dim, d_flag);
   }
@@ -170,7 +155,6 @@ static int attn_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
   hipLaunchKernelGGL(k_st_fill, dim3(grid_for((size_t)c.dim)), dim3(KH_WG), 0, s, m->q, (size_t)c.dim, 0xc2b2ae35u, 1.0f);
   if (head_case) rc = attn_merge_case(m, pos1, m->attn_ns_g > 0 ? 2 : 0, d_flag);
   if (rc == KH_OK && pos2 >= 0) rc = attn_merge_case(m, pos2, 0, d_flag);
-  m->attn_fenced = false;
   int32_t flag = 0;
   hipError_t e = hipMemsetAsync(m->kcache, 0, n * sizeof(float), s);  // the cache is empty again
   if (e == hipSuccess) e = hipMemsetAsync(m->vcache, 0, n * sizeof(float), s);

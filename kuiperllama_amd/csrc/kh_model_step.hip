@@ -167,7 +167,7 @@ void launch_qkv(kh_model* m, int l) {
     kh_launch(KH_KERNEL(k_qkv, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
   });
 }
-KhAttnArgs fill_attn(kh_model* m, int l, int variant) {
+KhAttnArgs fill_attn(kh_model* m, int l, int variant, bool fenced) {
   const kh_config& c = m->cfg;
   KhAttnArgs a;
   a.q = m->q;
@@ -188,7 +188,7 @@ KhAttnArgs fill_attn(kh_model* m, int l, int variant) {
   a.t_long = m->attn_t_long;
   a.ts_shift = m->attn_ts_shift;
   a.defer = variant == 1 ? 1 : 0;
-  a.fenced = m->attn_fenced ? 1 : 0;
+  a.fenced = fenced ? 1 : 0;
   a.tok_stride = 0;
   a.ws_tok_bytes = 0;
   return a;
@@ -198,9 +198,9 @@ int attn_group_lanes(const kh_config& c) {
   while (G < c.head_size / 4) G <<= 1;
   return G < 16 ? 16 : G;
 }
-void launch_attn(kh_model* m, int l, int variant) {
+void launch_attn(kh_model* m, int l, int variant, bool fenced) {
   const kh_config& c = m->cfg;
-  const KhAttnArgs a = fill_attn(m, l, variant);
+  const KhAttnArgs a = fill_attn(m, l, variant, fenced);
   const int wg = m->attn_wg;
   if (c.head_size > 32)
     launch_attn_decode(a, 0, wg, m->stream);
@@ -248,7 +248,7 @@ void launch_wo(kh_model* m, int l, int variant) {
     kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
   });
 }
-void launch_ffn13(kh_model* m, int l) {
+void launch_ffn13(kh_model* m, int l, bool ring) {
   const kh_config& c = m->cfg;
   const LayerW& W = m->layers[l];
   KhFfn13Args a;
@@ -262,7 +262,7 @@ void launch_ffn13(kh_model* m, int l) {
   a.gshift = m->gshift;
   a.eps = c.rms_eps;
   // the int8 LDS-DMA ring kernels (kh_fused_ring.h): 2 ring slots per wave, 4 float4 staged per thread, plain layout
-  if (m->ring.ffn_r == 2) {  // plan_ring: int8, dim a multiple of 256 floats and at most 16 per thread
+  if (ring) {  // plan_ring: int8, dim a multiple of 256 floats and at most 16 per thread
     kh_launch(KH_KERNEL(k_ffn13_ring, 2, 4, false), m->ring.ffn_grid, KH_WG,
               ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
@@ -287,22 +287,22 @@ void launch_w2(kh_model* m, int l) {
     kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.hidden_dim), m->stream, a);
   });
 }
-void launch_cls(kh_model* m) {
+void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
   const kh_config& c = m->cfg;
-  m->scr.stale = false;  // (a generate that replays captured steps keeps this flag itself)
+  if (io.logits == m->logits) logits_fresh(m);  // (enqueue_steps has the last word behind captured steps)
   KhClsArgs a;
-  a.x = m->x;
+  a.x = io.x;
   a.final_norm = m->final_norm;
   a.wcls = m->cls;
-  a.logits = m->logits;
-  a.part_val = m->part_val;
-  a.part_idx = m->part_idx;
+  a.logits = io.logits;
+  a.part_val = io.part_val;
+  a.part_idx = io.part_idx;
   a.dim = c.dim;
   a.vocab = c.vocab_size;
   a.gshift = m->gshift;
   a.eps = c.rms_eps;
   // the classifier is int8 only when the model is quantised (untied; llama3.cpp:255-268)
-  if (m->ring.cls_r == 2) {
+  if (ring) {
     kh_launch(KH_KERNEL(k_cls_ring, 2, 4, false), m->ring.cls_grid, KH_WG,
               ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
@@ -312,51 +312,27 @@ void launch_cls(kh_model* m) {
     kh_launch(KH_KERNEL(k_cls, Q, U, MV), sh.grid, sh.wg, cls_lds_bytes(Q, c.dim), m->stream, a);
   });
 }
-void launch_sample(kh_model* m, int advance, int n_forced) {
-  const kh_config& c = m->cfg;
-  if (m->scr.now && !m->samp_on) {
+void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
+  tail = step_tail(m, tail == kScreen);  // sampling on is stronger than "screen"
+  if (tail == kScreen) {
     launch_sample_screen(m, advance, n_forced);
-    return;
-  }
-  KhSampleArgs a;
-  a.part_val = m->part_val;
-  a.part_idx = m->part_idx;
-  a.nparts = m->nparts;
-  a.forced = n_forced > 0 ? m->d_forced : nullptr;
-  a.n_forced = n_forced;
-  a.words = m->d_words;
-  a.words_cap = m->seq_cap;
-  a.d_next = m->d_next;
-  a.d_token = m->d_token;
-  a.d_pos = m->d_pos;
-  a.tok_emb = m->tok_emb;
-  a.x = m->x;
-  a.dim = c.dim;
-  a.vocab = c.vocab_size;
-  a.advance = advance;
-  if (m->samp_on) {
+  } else if (tail == kSample) {
     KhSampleTopArgs t;
     t.logits = m->logits;
     t.part_val = m->part_val;
     t.nparts = m->nparts;
     t.params = m->d_samp;
-    t.forced = a.forced;
-    t.n_forced = a.n_forced;
-    t.words = a.words;
-    t.words_cap = a.words_cap;
-    t.d_next = a.d_next;
-    t.d_token = a.d_token;
-    t.d_pos = a.d_pos;
-    t.tok_emb = a.tok_emb;
-    t.x = a.x;
-    t.dim = a.dim;
-    t.vocab = a.vocab;
-    t.advance = advance;
+    fill_step_tail(m, advance, n_forced, &t);
     launch_log("k_sample_topp");
     hipLaunchKernelGGL(k_sample_topp, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
-    return;
+  } else {
+    KhSampleArgs a;
+    a.part_val = m->part_val;
+    a.part_idx = m->part_idx;
+    a.nparts = m->nparts;
+    fill_step_tail(m, advance, n_forced, &a);
+    hipLaunchKernelGGL(k_sample, dim3(1), dim3(KH_WG), 0, m->stream, a);
   }
-  hipLaunchKernelGGL(k_sample, dim3(1), dim3(KH_WG), 0, m->stream, a);
 }
 
 // Which attention / wo pair the steps at positions pos_lo .. pos_hi launch (host decision, per captured
@@ -379,7 +355,7 @@ int step_variant(const kh_model* m, int pos_lo, int pos_hi) {
   return m->attn_ns_g > 0 ? 2 : 0;
 }
 // one fused decode step = 5L + 2 launches.  ev (optional) receives an event after each launch.
-void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, int variant) {
+void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, int variant, StepTail tail) {
   int e = 0;
   auto mark = [&]() {
     if (ev) (void)hipEventRecord(ev[e++], m->stream);
@@ -388,21 +364,21 @@ void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, i
   for (int l = 0; l < m->cfg.layer_num; ++l) {
     launch_qkv(m, l);
     mark();
-    launch_attn(m, l, variant);
+    launch_attn(m, l, variant, m->attn_fenced);
     mark();
     launch_wo(m, l, variant);
     mark();
-    launch_ffn13(m, l);
+    launch_ffn13(m, l, m->ring.ffn_r == 2);
     mark();
     launch_w2(m, l);
     mark();
   }
-  if (m->scr.now && !m->samp_on)
+  if (tail == kScreen)
     launch_cls_screen(m);  // k_cls's slot: still 5L + 2 launches
   else
     launch_cls(m);
   mark();
-  launch_sample(m, advance, n_forced);
+  launch_sample(m, advance, n_forced, tail);
   mark();
 }
 
@@ -444,6 +420,7 @@ int launch_step_unfused(kh_model* m, int pos) {
   }
   KH_TRY(kh_rmsnorm_f32(m->x, m->final_norm, m->x, c.dim, c.rms_eps, s));
   KH_TRY(lin(m->cls, m->x, m->logits, c.dim, c.vocab_size));
+  logits_fresh(m);
   if (m->samp_on) {  // the counter is the position whose logits are sampled, as in the fused step
     KH_TRY(kh_sample_f32(m->logits, c.vocab_size, &m->samp, pos, 1, m->d_next, s));
   } else {
@@ -505,34 +482,43 @@ void destroy_step_graphs(kh_model* m) {
       }
 }
 
-int capture_steps(kh_model* m, int n_forced, int steps, int variant, hipGraph_t* g, hipGraphExec_t* ge) {
+int capture_steps(kh_model* m, int n_forced, int steps, int variant, StepTail tail, hipGraph_t* g, hipGraphExec_t* ge) {
   KH_CHECK_HIP(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-  for (int i = 0; i < steps; ++i) launch_step_fused(m, /*advance=*/1, n_forced, nullptr, variant);
+  for (int i = 0; i < steps; ++i) launch_step_fused(m, /*advance=*/1, n_forced, nullptr, variant, tail);
   hipError_t e = hipStreamEndCapture(m->stream, g);
   if (e != hipSuccess) return (int)e;
   KH_CHECK_HIP(hipGraphInstantiate(ge, *g, nullptr, nullptr, 0));
   return KH_OK;
 }
-int step_graph_n(kh_model* m, int n_forced, int variant, int nsteps, hipGraphExec_t* out) {
+int step_graph(kh_model* m, int n_forced, int variant, int nsteps, StepTail tail, hipGraphExec_t* out) {
   if (variant < 0 || variant >= KH_STEP_VARIANTS) return KH_ERR_INVALID_ARG;
   const int k = nsteps == 1 ? 0 : nsteps == 2 ? 1 : nsteps == 4 ? 2 : nsteps == KH_GRAPH_STEPS ? 3 : -1;
   if (k < 0) return KH_ERR_INVALID_ARG;
-  kh_model::StepGraph& sg = m->sg[sg_sampler(m)][variant][k];  // captured with the sampler now in use
+  kh_model::StepGraph& sg = m->sg[tail][variant][k];
   if (!sg.e) {
-    const int rc = capture_steps(m, n_forced, nsteps, variant, &sg.g, &sg.e);
+    const int rc = capture_steps(m, n_forced, nsteps, variant, tail, &sg.g, &sg.e);
     if (rc != KH_OK) return rc;
     // push the executable graph to the device now: otherwise its FIRST launch pays for it (a 20-step run behind a
     // 5-step warm-up launched its 8-step graph for the first time inside the timed region: 1037-1046 tok/s by wall
     // clock where repeated runs gave 1060)
     (void)hipGraphUpload(sg.e, m->stream);
   }
-  // every replay fetches its graph here: behind it the logits buffer is as old as the last full classifier launch
-  m->scr.stale = m->scr.now;
   *out = sg.e;
   return KH_OK;
 }
-int step_graph(kh_model* m, int n_forced, int variant, bool steps8, hipGraphExec_t* out) {
-  return step_graph_n(m, n_forced, variant, steps8 ? KH_GRAPH_STEPS : 1, out);
+int enqueue_steps(kh_model* m, int pos, int nsteps, int n_forced, StepTail tail, int exec) {
+  const int variant = step_variant(m, pos, pos + nsteps - 1);
+  if (exec == KH_EXEC_GRAPH) {
+    hipGraphExec_t ge = nullptr;
+    const int rc = step_graph(m, n_forced, variant, nsteps, tail, &ge);
+    if (rc != KH_OK) return rc;
+    KH_CHECK_HIP(hipGraphLaunch(ge, m->stream));
+  } else {
+    for (int i = 0; i < nsteps; ++i) launch_step_fused(m, /*advance=*/1, n_forced, nullptr, variant, tail);
+  }
+  // behind screened steps the logits buffer is as old as the last full classifier launch
+  m->scr.stale = tail == kScreen;
+  return KH_OK;
 }
 
 void plan_decode_shapes(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size,
@@ -638,11 +624,11 @@ extern "C" int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t
   int rc = kv_ensure(m, pos + 1);  // cache rows 0 .. pos backed by HBM before the step is enqueued
   if (rc != KH_OK) return rc;
   set_state(m, token, pos);  // embedding() + fill_input (llama3.cpp:578-598, model.cpp:245-263)
-  m->scr.stale = false;      // a single step always runs the full classifier
   if (exec == KH_EXEC_UNFUSED) {
     rc = launch_step_unfused(m, pos);
   } else if (exec == KH_EXEC_FUSED || exec == KH_EXEC_GRAPH) {
-    launch_step_fused(m, /*advance=*/0, /*n_forced=*/0, nullptr, step_variant(m, pos, pos));
+    // a single step always runs the full classifier
+    launch_step_fused(m, /*advance=*/0, /*n_forced=*/0, nullptr, step_variant(m, pos, pos), step_tail(m, false));
     rc = kh_launch_status();
   } else {
     return KH_ERR_INVALID_ARG;
@@ -732,14 +718,8 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
   }
   if (exec != KH_EXEC_GRAPH && exec != KH_EXEC_FUSED) return KH_ERR_INVALID_ARG;
 
-  // greedy steps run the screened classifier pair (kh_cls_screen.h) wherever the model has one; m->scr.now says
-  // which pair the launches enqueued or captured right now use, and is off again on every way out
+  // greedy steps run the screened classifier pair (kh_cls_screen.h) wherever the model has one
   const bool screen = cls_screen_wanted(m);
-  struct ScreenOff {
-    kh_model* m;
-    ~ScreenOff() { m->scr.now = false; }
-  } screen_off{m};
-  m->scr.now = screen;
   if ((rc = ensure_seq_cap(m, total_steps)) != KH_OK) return rc;
   // every cache row this call can reach is backed by HBM before its first launch (the dry launches of fresh graphs
   // below touch rows 0 .. 7); mapping happens here, on the host, outside the event bracket of the step loop
@@ -779,23 +759,23 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
     // a generate owns rows [0, max(total_steps, 8)) of the cache).  Skipped when the cache is shorter than that.
     // (Launching only the graphs of at most total_steps steps - the first r5 form - left the 8-step graph's first
     // launch inside the timed loop of a 20-step run behind a 5-step warm-up: 1018 instead of 1036-1042 tok/s.)
+    const StepTail tail = step_tail(m, screen);
     bool fresh[4] = {false, false, false, false};
     hipGraphExec_t ge = nullptr;
     for (int n = 1, k = 0; n <= KH_GRAPH_STEPS; n *= 2, ++k) {
-      fresh[k] = m->sg[sg_sampler(m)][0][k].e == nullptr;
-      if ((rc = step_graph_n(m, n_forced, 0, n, &ge)) != KH_OK) return rc;
+      fresh[k] = m->sg[tail][0][k].e == nullptr;
+      if ((rc = step_graph(m, n_forced, 0, n, tail, &ge)) != KH_OK) return rc;
     }
     bool dry = false;
     if (c.cache_len >= KH_GRAPH_STEPS && m->seq_cap >= KH_GRAPH_STEPS)
       for (int k = 3; k >= 0; --k)
         if (fresh[k]) {
           set_state(m, h_prompt[0], 0);
-          KH_CHECK_HIP(hipGraphLaunch(m->sg[sg_sampler(m)][0][k].e, m->stream));
+          if ((rc = enqueue_steps(m, 0, 1 << k, n_forced, tail, KH_EXEC_GRAPH)) != KH_OK) return rc;
           dry = true;
         }
     if (dry) KH_CHECK_HIP(hipStreamSynchronize(m->stream));
   }
-  m->scr.now = false;  // the prompt phase below launches the full classifier; launch_chunk decides per chunk
 
   // prompt phase: the tokens that are only fed (positions 0 .. n_prompt-2).  KH_PREFILL selects how:
   //   "0" / "token"  the reference's one forward pass per prompt token (demo/main.cpp:20-22)
@@ -834,32 +814,19 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
     m->first_pos = start;
   }
   set_state(m, h_prompt[start], start);
-  auto launch_chunk = [&](int s) -> int {  // enqueue the next 1 or KH_GRAPH_STEPS steps (positions s ..)
-    if (exec == KH_EXEC_GRAPH) {
-      // the largest of 8 / 4 / 2 / 1 steps that still fits (a single-step launch costs ~15 us of graph-launch gap:
-      // the 20-step form of the bench ran 8 + 8 + 1 + 1 + 1 + 1 and lost 0.3 % to it; now 8 + 8 + 4)
-      int n = KH_GRAPH_STEPS;
-      while (n > total_steps - s) n >>= 1;
-      const bool keep = s == start && start > 0;  // first sampled step behind a prefill: alone, logits kept
-      if (keep) n = 1;
-      m->scr.now = screen && !keep;  // the kept step leaves its logits in the buffer: full classifier
-      m->scr.stale = m->scr.now;
-      hipGraphExec_t ge = nullptr;
-      if (step_graph_n(m, n_forced, step_variant(m, s, s + n - 1), n, &ge) != KH_OK) return -1;
-      if (hipGraphLaunch(ge, m->stream) != hipSuccess) return -1;
-      if (keep && hipMemcpyAsync(m->first_logits, m->logits, sizeof(float) * (size_t)c.vocab_size,
-                                 hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
-        return -1;
-      return n;
-    }
-    m->scr.now = screen && !(s == start && start > 0);
-    launch_step_fused(m, 1, n_forced, nullptr, step_variant(m, s, s));
-    m->scr.stale = m->scr.now;
-    if (s == start && start > 0 &&
-        hipMemcpyAsync(m->first_logits, m->logits, sizeof(float) * (size_t)c.vocab_size, hipMemcpyDeviceToDevice,
-                       m->stream) != hipSuccess)
+  auto launch_chunk = [&](int s) -> int {  // enqueue the next 1 or up to KH_GRAPH_STEPS steps (positions s ..)
+    // graph exec: the largest of 8 / 4 / 2 / 1 steps that still fits (a single-step launch costs ~15 us of graph-launch
+    // gap: the 20-step form of the bench ran 8 + 8 + 1 + 1 + 1 + 1 and lost 0.3 % to it; now 8 + 8 + 4)
+    int n = exec == KH_EXEC_GRAPH ? KH_GRAPH_STEPS : 1;
+    while (n > total_steps - s) n >>= 1;
+    // first sampled step behind a prefill: alone, and it leaves its logits in the buffer (full classifier)
+    const bool keep = s == start && start > 0;
+    if (keep) n = 1;
+    if (enqueue_steps(m, s, n, n_forced, step_tail(m, screen && !keep), exec) != KH_OK) return -1;
+    if (keep && hipMemcpyAsync(m->first_logits, m->logits, sizeof(float) * (size_t)c.vocab_size,
+                               hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
       return -1;
-    return 1;
+    return n;
   };
   int n_out = total_steps;
   if (n_stop == 0) {

@@ -123,6 +123,31 @@ def test_debug_hooks_live_in_one_table_not_in_getenv(lib, monkeypatch):
         assert "getenv" not in open(os.path.join(csrc, f)).read(), f
 
 
+def test_launch_helpers_take_their_target_as_arguments_not_toggled_model_state():
+    """What a launch helper does beyond the model's plan travels as an argument: no source of the library
+    redirects a helper by editing kh_model around the call.  The step tail, the classifier's buffers, ring or register
+    tiles, the fenced merge and the screen's debug arrays have no field to toggle or none is assigned; scr.stale has
+    three writers at the most; KH_ATTN_FENCED is read in one helper."""
+    csrc = os.path.join(ROOT, "kuiperllama_amd", "csrc")
+    lines = [(f, n + 1, re.sub(r"//.*", "", ln)) for f in sorted(os.listdir(csrc))
+             for n, ln in enumerate(open(os.path.join(csrc, f)).read().split("\n"))]
+
+    def sites(pattern):
+        return [f"{f}:{n}" for f, n, ln in lines if re.search(pattern, ln)]
+    assert sites(r"\b(scr|s)\.now\b|\bbool\s+now\b") == []           # ClsScreen::now
+    assert sites(r"\b(scr|s)\.dbg_[lu]b\b") == []                    # ClsScreen::dbg_lb / dbg_ub
+    assert sites(r"\bScreenOff\b|\bsg_sampler\b|\bstep_graph_n\b") == []
+    assert sites(r"\bm->(x|logits|ring\.ffn_r|ring\.cls_r)\s*=[^=]") == []
+    fenced = sites(r"(->|\.)attn_fenced\s*=[^=]")
+    assert sorted(s.split(":")[0] for s in fenced) == ["kh_model_load.hip", "kh_model_selftest.hip"], fenced
+    assert sites(r"(->|\.)attn_fenced\s*=\s*true;") == [s for s in fenced if s.startswith("kh_model_selftest.hip")]
+    stale = sites(r"\.stale\s*=[^=]")  # the step enqueuer, the classifier launch into the model's buffer
+    assert 1 <= len(stale) <= 3, stale
+    assert {s.split(":")[0] for s in stale} <= {"kh_model_step.hip", "kh_model_internal.h"}, stale
+    hook = sites(r'"KH_ATTN_FENCED"')
+    assert len(hook) == 1 and hook[0].startswith("kh_attn.h:"), hook
+
+
 def test_launch_log_hook_and_qkv_split_limit(lib):
     """KH_LAUNCH_LOG: kh_debug_launch_log reads the set of launched kernel instantiations like kh_debug_list (bytes
     needed, NUL-terminated, truncated to the buffer); setting, resetting and unsetting the hook leave it empty (no

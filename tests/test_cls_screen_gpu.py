@@ -218,3 +218,56 @@ def test_failed_selftest_turns_screening_off(gpu):
         _same(_run(m, PROMPT, 32), want, "KH_FLAG_NO_CLS_SCREEN")
     finally:
         m.close()
+
+
+def test_entry_points_interleaved_on_one_model_match_an_unscreened_model(gpu):
+    """Which step tail is launched, where the classifier reads and writes and whether the logits buffer is behind the
+    last step travel as arguments between the entry points: greedy, sampled and greedy generates, time_step, predict,
+    the probe and a fused generate, one after the other on ONE model, give the words and logits() of a model created
+    without the screen.  The 300-step run crosses position 256, so the screened tail is captured for a second
+    attention / wo variant; logits() right behind the probe is k_cls's on the probe's vector."""
+    from kuiperllama_amd.model import KuiperModel
+    spec = dataclasses.replace(binfmt.PRESETS["tinyllama-1.1b"], n_layers=2, seq_len=512)
+    img = binfmt.synth_image(spec, seed=77, device=gpu, final_norm_std=1.0)
+    torch.cuda.synchronize()
+    x = np.random.default_rng(3).normal(0, 1, spec.dim).astype(np.float32)
+
+    def sequence(m, probe):
+        out = [("greedy 40",) + _run(m, PROMPT, 40)]
+        m.set_sampling(temperature=0.8, top_k=50, seed=7)
+        out.append(("sampled 40", m.generate(PROMPT, 40)[0], None))
+        m.set_sampling()
+        out.append(("greedy 300", m.generate(PROMPT, 300)[0], None))
+        m.time_step(5, reps=1)
+        out.append(("time_step", [], m.logits()))
+        out.append(("predict", [m.predict(out[0][1][3], 3)], m.logits()))
+        if probe:
+            p = m.cls_screen_probe(x)
+            assert p["token"] == p["full_token"] == int(np.argmax(m.logits())), p
+        out.append(("fused 40",) + _run(m, PROMPT, 40, exec="fused"))
+        return out
+
+    try:
+        _ffi.debug_set("KH_CLS_SCREEN", "0")
+        plain = KuiperModel.from_device_image(img, spec)
+    finally:
+        _ffi.debug_set("KH_CLS_SCREEN", None)
+    try:
+        assert plain.cls_screen_info()["on"] == 0
+        want = sequence(plain, probe=False)
+        assert plain.cls_screen_info()["steps"] == 0
+    finally:
+        plain.close()
+    m = KuiperModel.from_device_image(img, spec)
+    try:
+        assert m.cls_screen_info()["on"] == 1
+        got = sequence(m, probe=True)
+        assert m.cls_screen_info()["steps"] >= 40 + 300 + 40  # (+ the first launches of fresh graphs)
+    finally:
+        m.close()
+    for (what, wa, la), (_, wb, lb) in zip(got, want):
+        assert wa == wb, f"{what}: words differ first at {next(i for i, (p, q) in enumerate(zip(wa, wb)) if p != q)}"
+        assert (la is None) == (lb is None)
+        if la is not None:
+            assert np.array_equal(la.view(np.uint32), lb.view(np.uint32)), f"{what}: logits() differ"
+    assert len(set(got[2][1][2:])) > 8, "the sequence was meant to wander"
