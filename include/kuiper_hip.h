@@ -175,6 +175,38 @@ int kh_sample_f32(const float* logits, int64_t n, const kh_sampling* p, int64_t 
 int kh_sample_f32_host(const float* logits, int64_t n, const kh_sampling* p, int64_t counter, int64_t* h_out,
                        void* stream);
 
+/* Logit processors: repetition / presence / frequency penalties over a window of the fed tokens, and a logit bias,
+ * applied IN PLACE to a logit vector ahead of the pick (the controls of llama.cpp's repeat_penalty / repeat_last_n /
+ * presence_penalty / frequency_penalty / logit_bias and HF's repetition_penalty / bad_words_ids).  Let p be the
+ * position whose logits are processed, V = n, N = last_n:
+ *   1. the window is the positions j in [max(0, p + 1 - N), p]; N = 0: [0, p];
+ *   2. t_j = the token FED at position j (prompt tokens count, as in llama.cpp); c(v) = the number of window
+ *      positions with t_j == v; entries outside [0, V) are ignored (a never-written slot of a model's record is -1);
+ *   3. for every v with c(v) > 0, once, in fp32, each operation rounded once and never contracted, in this order:
+ *        l = l > 0 ? l / repetition : l * repetition            (skipped when repetition == 1)
+ *        l = l - (float(c) * frequency + presence)              (skipped when both are 0)
+ *   4. then for every bias entry (id, b): l[id] = l[id] + b.  A bias of -inf bans a token; -inf logits stay -inf
+ *      through all three steps.
+ * The caller keeps the processed logits finite or -inf with at least one finite entry (kh_sample_f32's
+ * precondition).  The processed logits are bit-identical to the numpy float32 twin tests/logit_proc_ref.py.
+ * KH_ERR_INVALID_ARG, before any device call, for repetition non-finite or <= 0, presence or frequency non-finite,
+ * last_n < 0.  One 1024-thread workgroup, time proportional to the window, not to V (csrc/kh_logit_proc.h; DESIGN.md
+ * 3.3c has the measured cost). */
+typedef struct kh_penalties {
+  float repetition;  /* 1: off; finite, > 0 */
+  float presence;    /* 0: off; finite */
+  float frequency;   /* 0: off; finite */
+  int32_t last_n;    /* window length in positions; 0: the whole sequence; >= 0 */
+} kh_penalties;
+/* bytes of the operator's workspace: n int32 counters, zeroed ONCE by the caller; the kernel re-arms them */
+int64_t kh_logit_process_workspace_bytes(int64_t n);
+/* d_tokens[j] = token fed at position j, j <= position (DEVICE); the position is *d_pos (DEVICE, graph-capturable
+ * form) or, when d_pos is NULL, pos; d_bias_ids / d_bias [n_bias] (DEVICE): distinct ids in [0, n), no NaN, no +inf -
+ * an id outside [0, n) is skipped.  p NULL or (1, 0, 0, *) with n_bias 0: nothing is launched.  Asynchronous. */
+int kh_logit_process_f32(float* logits, int64_t n, const int32_t* d_tokens, const int32_t* d_pos, int32_t pos,
+                         const kh_penalties* p, const int32_t* d_bias_ids, const float* d_bias, int32_t n_bias,
+                         void* workspace, void* stream);
+
 /* CPU-only helpers of the reference (kernels_interface.h:38-46), provided on device so the
  * op set is closed: softmax in place, x *= scale, out += sum_t scale[t]*value[t*stride..] */
 int kh_softmax_f32(float* x, int32_t n, void* stream);
@@ -276,7 +308,8 @@ enum {
  * Synchronises the stream. exec: KH_EXEC_FUSED or KH_EXEC_UNFUSED. */
 int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t is_prompt, int32_t exec,
                      int32_t* h_next);
-/* copy the last logits (kForwardOutput) to host */
+/* copy the last logits (kForwardOutput) to host; behind a step that ran the model's logit processors
+ * (kh_model_set_penalties / kh_model_set_logit_bias) these are the PROCESSED logits: processing is in place */
 int kh_model_get_logits(kh_model* m, float* h_logits);
 /* the screened classifier (KH_FLAG_NO_CLS_SCREEN): out[8] = on (0 / 1), creation-time self-test (0 not run, 1 passed,
  * -1 failed: screening off), HBM bytes of the bf16 copy and its row table, microseconds its conversion took, screened
@@ -384,6 +417,25 @@ int kh_model_first_sample(kh_model* m, kh_first_sample* out);
  * KH_ERR_INVALID_ARG as kh_sample_f32.  kh_model_first_sample keeps reporting the two largest logits. */
 int kh_model_set_sampling(kh_model* m, const kh_sampling* p);
 int kh_model_get_sampling(const kh_model* m, kh_sampling* out);
+
+/* The model's logit processors (NULL / n = 0 = off, the default of every model): kh_logit_process_f32's semantics
+ * on the logits of every SAMPLED position of kh_model_predict (fused and unfused), kh_model_generate and
+ * kh_model_generate_until, ahead of the pick - the first maximum (lowest index) of the processed logits, or, with a
+ * sampler set, kh_sample_f32's draw on them with counter = position.  Prompt positions are never processed.  The
+ * window runs over the model's record of the token fed at every position, which kh_model_predict, the generate
+ * loops, kh_model_prefill and kh_model_prefill_gemm keep; like the K/V rows, slots below the position of a call are
+ * whatever earlier calls left (generate steps that run with processors off do not record).  While anything is on, the
+ * step's last launch is k_sample_proc (processing, one max pass, the pick: launches_per_token is unchanged) and the
+ * screened classifier is not used; all-neutral penalties (1, 0, 0, *) and no bias entries are "off": the model then
+ * runs exactly the launches it runs without this feature.  Parameters and the bias list live in device buffers
+ * written on the model stream: new values need no graph recapture (a list longer than any before - 64 entries at
+ * least fit - rebuilds the graphs).  kh_model_get_logits and kh_model_first_sample report the processed logits, so
+ * top1_id stays the greedy pick.
+ * kh_model_set_logit_bias, before any device call: KH_ERR_INVALID_ARG for a NaN or +inf bias, a duplicate id, -inf on
+ * all vocab_size ids; KH_ERR_RANGE for an id outside [0, vocab_size). */
+int kh_model_set_penalties(kh_model* m, const kh_penalties* p);
+int kh_model_get_penalties(const kh_model* m, kh_penalties* out);
+int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const float* h_bias, int32_t n);
 
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,

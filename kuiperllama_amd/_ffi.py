@@ -18,7 +18,7 @@ EXPORTS = [
     "kh_add_f32", "kh_matmul_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
     "kh_mha_decode_workspace_bytes", "kh_argmax_f32",
-    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
+    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
     "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
@@ -26,7 +26,7 @@ EXPORTS = [
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
-    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
+    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
 ]
@@ -69,6 +69,19 @@ class Sampling(C.Structure):
 
 def sampling(temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> Sampling:
     return Sampling(float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+class Penalties(C.Structure):
+    """kh_penalties: repetition 1, presence 0 and frequency 0 are off; last_n 0 is the whole sequence."""
+    _fields_ = [("repetition", C.c_float), ("presence", C.c_float), ("frequency", C.c_float), ("last_n", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"repetition": float(self.repetition), "presence": float(self.presence),
+                "frequency": float(self.frequency), "last_n": int(self.last_n)}
+
+
+def penalties(repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0, last_n: int = 0) -> Penalties:
+    return Penalties(float(repetition), float(presence), float(frequency), int(last_n))
 
 
 class Config(C.Structure):
@@ -122,6 +135,9 @@ def lib() -> C.CDLL:
     L.kh_argmax_f32_host.argtypes = [_vp, _i64, C.POINTER(_i64), _vp]
     L.kh_sample_f32.argtypes = [_vp, _i64, C.POINTER(Sampling), _i64, _i32, _vp, _vp]
     L.kh_sample_f32_host.argtypes = [_vp, _i64, C.POINTER(Sampling), _i64, C.POINTER(_i64), _vp]
+    L.kh_logit_process_workspace_bytes.argtypes = [_i64]
+    L.kh_logit_process_workspace_bytes.restype = _i64
+    L.kh_logit_process_f32.argtypes = [_vp, _i64, _vp, _vp, _i32, C.POINTER(Penalties), _vp, _vp, _i32, _vp, _vp]
     L.kh_softmax_f32.argtypes = [_vp, _i32, _vp]
     L.kh_scale_f32.argtypes = [_f32, _vp, _i32, _vp]
     L.kh_scale_sum_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _vp]
@@ -153,6 +169,9 @@ def lib() -> C.CDLL:
     L.kh_model_first_sample.argtypes = [_vp, C.POINTER(FirstSample)]
     L.kh_model_set_sampling.argtypes = [_vp, C.POINTER(Sampling)]
     L.kh_model_get_sampling.argtypes = [_vp, C.POINTER(Sampling)]
+    L.kh_model_set_penalties.argtypes = [_vp, C.POINTER(Penalties)]
+    L.kh_model_get_penalties.argtypes = [_vp, C.POINTER(Penalties)]
+    L.kh_model_set_logit_bias.argtypes = [_vp, C.POINTER(_i32), C.POINTER(_f32), _i32]
     L.kh_model_time_step.argtypes = [_vp, _i32, _i32, C.POINTER(_f32)]
     L.kh_plan_decode_shapes.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]
     L.kh_plan_decode_ring.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]

@@ -544,12 +544,14 @@ static __global__ __launch_bounds__(KH_WG) void k_sample(const KhSampleArgs a) {
 }
 
 // set (token, pos) from the host and gather the embedding row: start of generate / predict
+// (and record it as the token fed at `pos`: hist, kh_logit_proc.h)
 static __global__ __launch_bounds__(KH_WG) void k_set_state(int token, int pos, int32_t* d_token,
                                                      int32_t* d_pos, const float* tok_emb,
-                                                     float* x, int dim) {
+                                                     float* x, int dim, int32_t* hist) {
   if (threadIdx.x == 0) {
     *d_token = token;
     *d_pos = pos;
+    hist[pos] = token;
   }
   const f32x4* src = (const f32x4*)(tok_emb + (size_t)token * dim);
   f32x4* dst = (f32x4*)x;

@@ -52,6 +52,7 @@ using khm::LayerW;
 
 #define KH_STEP_VARIANTS 3  // kh_model_step.hip::step_variant
 struct KhSampParams;       // kh_sample.h
+struct KhProcParams;       // kh_logit_proc.h
 struct kh_model {
   kh_config cfg{};
   kh_model_opts opts{};
@@ -149,12 +150,27 @@ struct kh_model {
     hipGraphExec_t e = nullptr;
   };
   // [StepTail][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps per tail of the step
-  StepGraph sg[3][KH_STEP_VARIANTS][4];
+  StepGraph sg[4][KH_STEP_VARIANTS][4];
   // kh_model_set_sampling: the parameters (host copy), whether they sample (temperature > 0), and their device copy,
   // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
   kh_sampling samp{0.f, 0, 1.f, 0};
   bool samp_on = false;
   KhSampParams* d_samp = nullptr;
+  // Logit processors (kh_logit_proc.h).  d_hist[hist_cap = cache_len + 1]: the token fed at every position, -1 where
+  // none was: written by set_state, by k_sample_proc for the token it feeds next, by the prompt upload of a generate
+  // with processors on and by kh_model_prefill / kh_model_prefill_gemm - like the K/V rows, slots below a call's
+  // position are whatever earlier calls left.  Sized by the cache, not by seq_cap: predict reaches every position.
+  // kh_model_set_penalties / kh_model_set_logit_bias: host copies, whether anything is on, and the device copies the
+  // captured k_sample_proc launches read (new values need no recapture; a bias list that outgrows bias_cap does).
+  int32_t* d_hist = nullptr;
+  int hist_cap = 0;
+  kh_penalties pen{1.f, 0.f, 0.f, 0};
+  int n_bias = 0, bias_cap = 0;
+  bool proc_on = false;
+  KhProcParams* d_proc = nullptr;
+  int32_t* d_bias_ids = nullptr;
+  float* d_bias = nullptr;
+  int32_t* d_cnt = nullptr;  // [vocab] counters of the processing core, zero between launches
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // Screened classifier of the greedy generate loop (kh_cls_screen.h, kh_model_screen.hip): fp32 models only
   struct ClsScreen {
@@ -217,11 +233,13 @@ static inline void launch_cls(kh_model* m) {
 // a classifier launch has written the model's own logits buffer (kh_model_get_logits need not re-run k_cls)
 static inline void logits_fresh(kh_model* m) { m->scr.stale = false; }
 // The last two launches of a fused step, and the index of kh_model::sg its graphs live in: k_cls + k_sample (argmax),
-// k_cls + k_sample_topp, or the screened pair k_cls_screen + k_sample_screen (greedy steps of a generate, see scr)
-enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2 };
-// sampling needs every logit: it is stronger than a caller's wish to screen
-static inline StepTail step_tail(const kh_model* m, bool screen) {
-  return m->samp_on ? kSample : screen ? kScreen : kGreedy;
+// k_cls + k_sample_topp, the screened pair k_cls_screen + k_sample_screen (greedy steps of a generate, see scr), or
+// k_cls + k_sample_proc (penalties or a logit bias set: processing, then the greedy or sampled pick)
+enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2, kProcess = 3 };
+// processing and sampling need every logit: they are stronger than a caller's wish to screen.  process = false: a
+// step whose pick is discarded (kh_model_predict at a prompt position) leaves its logits as the classifier wrote them
+static inline StepTail step_tail(const kh_model* m, bool screen, bool process = true) {
+  return m->proc_on && process ? kProcess : m->samp_on ? kSample : screen ? kScreen : kGreedy;
 }
 // the fields every step tail shares: KhSampleArgs, KhSampleTopArgs and KhSampleScreenArgs name them alike
 template <class A>
@@ -244,8 +262,10 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail);
 // the variant of the steps at positions pos_lo .. pos_hi
 int step_variant(const kh_model* m, int pos_lo, int pos_hi);
 void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, int variant, StepTail tail);
-int launch_step_unfused(kh_model* m, int pos);
+int launch_step_unfused(kh_model* m, int pos, bool process);  // process: apply the model's logit processors
 void set_state(kh_model* m, int token, int pos);
+// d_hist[pos0 .. pos0 + n) = h_tokens (the public prefill entry points; a generate uploads its prompt itself)
+int hist_write(kh_model* m, const int32_t* h_tokens, int n, int pos0);
 int ensure_pinned_words(kh_model* m, int n);
 int ensure_seq_cap(kh_model* m, int n);
 void destroy_step_graphs(kh_model* m);
@@ -275,4 +295,7 @@ int run_selftests(kh_model* m);
 // ---- kh_model_prefill.hip -------------------------------------------------------------------
 bool prefill_supported(const kh_model* m);  // B-token VALU path
 bool pg_supported(const kh_model* m);       // MFMA GEMM path
+// kh_model_prefill / kh_model_prefill_gemm without the token record (hist_write)
+int prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
+int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
 }  // namespace khm

@@ -573,6 +573,10 @@ int finish_create(kh_model* m, SinCosJob* sincos = nullptr) {
   }
   KH_CHECK_HIP(hipMemsetAsync(m->d_pos, 0, sizeof(int32_t), m->stream));
   KH_CHECK_HIP(hipMemsetAsync(m->d_token, 0, sizeof(int32_t), m->stream));
+  // the token fed at every position (kh_logit_proc.h): -1 = none yet
+  m->hist_cap = (int)CL + 1;
+  if ((rc = dalloc(&m->d_hist, (size_t)m->hist_cap)) != KH_OK) return rc;
+  KH_CHECK_HIP(hipMemsetAsync(m->d_hist, 0xFF, sizeof(int32_t) * (size_t)m->hist_cap, m->stream));
   // sin/cos table: computed on the host with libm exactly as the CPU backend does
   // (cpu/rope_kernel.cpp:4-16) so the fp32 table is bit-identical to the CPU reference's,
   // then uploaded once.  (kh_sincos_cache_f32 is the on-device twin of sin_cos_cache_calc_cu.)
@@ -649,6 +653,8 @@ extern "C" void kh_model_destroy(kh_model* m) {
   if (m->h_forced_pin) (void)hipHostFree(m->h_forced_pin);
   if (m->first_logits) (void)hipFree(m->first_logits);
   if (m->d_samp) (void)hipFree(m->d_samp);
+  for (void* q : {(void*)m->d_hist, (void*)m->d_proc, (void*)m->d_bias_ids, (void*)m->d_bias, (void*)m->d_cnt})
+    if (q) (void)hipFree(q);
   cls_screen_release(m);
   void* bufs[] = {m->x,      m->rms,    m->q,         m->att,       m->h1,       m->h3,
                   m->w2o,    m->logits, m->score,     m->sin_cache,

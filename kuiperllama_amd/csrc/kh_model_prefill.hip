@@ -538,6 +538,10 @@ extern "C" int kh_plan_prefill_shape(int32_t epi, int32_t T, int32_t rows, int32
 }
 
 extern "C" int kh_model_prefill_gemm(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
+  const int rc = khm::prefill_gemm_run(m, h_tokens, n, pos0);
+  return rc == KH_OK ? khm::hist_write(m, h_tokens, n, pos0) : rc;
+}
+int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
@@ -586,6 +590,10 @@ extern "C" int kh_mha_prefill_f32(int32_t pos0, int32_t n_tokens, int32_t head_n
 }
 
 extern "C" int kh_model_prefill(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
+  const int rc = khm::prefill_run(m, h_tokens, n, pos0);
+  return rc == KH_OK ? khm::hist_write(m, h_tokens, n, pos0) : rc;
+}
+int khm::prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
@@ -645,14 +653,14 @@ extern "C" int kh_model_time_prefill(kh_model* m, const int32_t* h_tokens, int32
     if (!prefill_supported(m)) return KH_ERR_UNSUPPORTED;
     if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
-    if ((rc = kh_model_prefill(m, h_tokens, n, pos0)) != KH_OK) return rc;
+    if ((rc = prefill_run(m, h_tokens, n, pos0)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));
   } else if (mode == KH_PREFILL_GEMM) {
     if (!pg_supported(m)) return KH_ERR_UNSUPPORTED;
     if ((rc = ensure_pg_buffers(m)) != KH_OK) return rc;
     if ((rc = ensure_pg_ws(m)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
-    if ((rc = kh_model_prefill_gemm(m, h_tokens, n, pos0)) != KH_OK) return rc;
+    if ((rc = prefill_gemm_run(m, h_tokens, n, pos0)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));
   } else {
     return KH_ERR_INVALID_ARG;

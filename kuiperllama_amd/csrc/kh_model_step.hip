@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "kh_dispatch.h"
@@ -313,9 +314,22 @@ void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
   });
 }
 void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
-  tail = step_tail(m, tail == kScreen);  // sampling on is stronger than "screen"
+  if (tail == kScreen) tail = step_tail(m, true);  // processors or sampling on are stronger than "screen"
   if (tail == kScreen) {
     launch_sample_screen(m, advance, n_forced);
+  } else if (tail == kProcess) {
+    KhSampleProcArgs t;
+    t.logits = m->logits;
+    t.params = m->d_samp;
+    t.proc = m->d_proc;
+    t.bias_ids = m->d_bias_ids;
+    t.bias = m->d_bias;
+    t.hist = m->d_hist;
+    t.hist_cap = m->hist_cap;
+    t.cnt = m->d_cnt;
+    fill_step_tail(m, advance, n_forced, &t);
+    launch_log("k_sample_proc");
+    hipLaunchKernelGGL(k_sample_proc, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
   } else if (tail == kSample) {
     KhSampleTopArgs t;
     t.logits = m->logits;
@@ -383,7 +397,7 @@ void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, i
 }
 
 // the reference's own launch sequence, one C-ABI op per reference kernel (llama3.cpp:147-167)
-int launch_step_unfused(kh_model* m, int pos) {
+int launch_step_unfused(kh_model* m, int pos, bool process) {
   const kh_config& c = m->cfg;
   void* s = (void*)m->stream;
   int rc;
@@ -421,6 +435,9 @@ int launch_step_unfused(kh_model* m, int pos) {
   KH_TRY(kh_rmsnorm_f32(m->x, m->final_norm, m->x, c.dim, c.rms_eps, s));
   KH_TRY(lin(m->cls, m->x, m->logits, c.dim, c.vocab_size));
   logits_fresh(m);
+  if (process && m->proc_on)  // d_hist[pos] is this step's own token (set_state)
+    KH_TRY(kh_logit_process_f32(m->logits, c.vocab_size, m->d_hist, nullptr, pos, &m->pen, m->d_bias_ids, m->d_bias,
+                                m->n_bias, m->d_cnt, s));
   if (m->samp_on) {  // the counter is the position whose logits are sampled, as in the fused step
     KH_TRY(kh_sample_f32(m->logits, c.vocab_size, &m->samp, pos, 1, m->d_next, s));
   } else {
@@ -432,7 +449,14 @@ int launch_step_unfused(kh_model* m, int pos) {
 
 void set_state(kh_model* m, int token, int pos) {
   hipLaunchKernelGGL(k_set_state, dim3(1), dim3(KH_WG), 0, m->stream, token, pos, m->d_token,
-                     m->d_pos, m->tok_emb, m->x, m->cfg.dim);
+                     m->d_pos, m->tok_emb, m->x, m->cfg.dim, m->d_hist);
+}
+int hist_write(kh_model* m, const int32_t* h_tokens, int n, int pos0) {
+  if (pos0 < 0 || n <= 0 || (int64_t)pos0 + n > m->hist_cap) return KH_ERR_RANGE;
+  // pageable source: the sync keeps the caller's array alive for the upload
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_hist + pos0, h_tokens, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+  KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
 }
 
 int ensure_pinned_words(kh_model* m, int n) {
@@ -624,11 +648,13 @@ extern "C" int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t
   int rc = kv_ensure(m, pos + 1);  // cache rows 0 .. pos backed by HBM before the step is enqueued
   if (rc != KH_OK) return rc;
   set_state(m, token, pos);  // embedding() + fill_input (llama3.cpp:578-598, model.cpp:245-263)
+  // logit processors apply to the calls whose pick is returned: prompt positions are never processed
   if (exec == KH_EXEC_UNFUSED) {
-    rc = launch_step_unfused(m, pos);
+    rc = launch_step_unfused(m, pos, !is_prompt);
   } else if (exec == KH_EXEC_FUSED || exec == KH_EXEC_GRAPH) {
     // a single step always runs the full classifier
-    launch_step_fused(m, /*advance=*/0, /*n_forced=*/0, nullptr, step_variant(m, pos, pos), step_tail(m, false));
+    launch_step_fused(m, /*advance=*/0, /*n_forced=*/0, nullptr, step_variant(m, pos, pos),
+                      step_tail(m, false, !is_prompt));
     rc = kh_launch_status();
   } else {
     return KH_ERR_INVALID_ARG;
@@ -647,7 +673,7 @@ extern "C" int kh_model_set_sampling(kh_model* m, const kh_sampling* p) {
   const kh_sampling greedy{0.f, 0, 1.f, 0};
   const kh_sampling want = p ? *p : greedy;
   const bool on = !kh_sampling_greedy(&want);
-  if (on) {
+  if (on || m->d_samp) {  // (k_sample_proc decides greedy or sampled from the device copy: it follows "off" too)
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     if (!m->d_samp) KH_CHECK_HIP(hipMalloc((void**)&m->d_samp, sizeof(KhSampParams)));
     // written on the model stream behind whatever is queued; the sync keeps the host copy alive for the upload
@@ -663,6 +689,91 @@ extern "C" int kh_model_get_sampling(const kh_model* m, kh_sampling* out) {
   if (!m || !out) return KH_ERR_INVALID_ARG;
   *out = m->samp;
   return KH_OK;
+}
+
+// ---- logit processors (kh_logit_proc.h)
+namespace {
+// after a change of m->pen / the bias list: whether anything is on, the buffers of the first "on", the device copy of
+// the parameters (on the model stream, behind whatever is queued)
+int proc_commit(kh_model* m) {
+  const bool on = !kh_penalties_neutral(&m->pen) || m->n_bias > 0;
+  if (on || m->d_proc) {
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    if (!m->d_proc) KH_CHECK_HIP(hipMalloc((void**)&m->d_proc, sizeof(KhProcParams)));
+    if (!m->d_cnt) {
+      KH_CHECK_HIP(hipMalloc((void**)&m->d_cnt, sizeof(int32_t) * (size_t)m->cfg.vocab_size));
+      KH_CHECK_HIP(hipMemsetAsync(m->d_cnt, 0, sizeof(int32_t) * (size_t)m->cfg.vocab_size, m->stream));  // once
+    }
+    if (!m->d_samp) {  // k_sample_proc reads the sampler's device copy: greedy until kh_model_set_sampling says more
+      KH_CHECK_HIP(hipMalloc((void**)&m->d_samp, sizeof(KhSampParams)));
+      const KhSampParams sp = kh_samp_params(&m->samp);
+      KH_CHECK_HIP(hipMemcpyAsync(m->d_samp, &sp, sizeof(sp), hipMemcpyHostToDevice, m->stream));
+      KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    }
+    const KhProcParams dp{m->pen.repetition, m->pen.presence, m->pen.frequency, m->pen.last_n, m->n_bias};
+    KH_CHECK_HIP(hipMemcpyAsync(m->d_proc, &dp, sizeof(dp), hipMemcpyHostToDevice, m->stream));
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  }
+  m->proc_on = on;
+  return KH_OK;
+}
+}  // namespace
+
+extern "C" int kh_model_set_penalties(kh_model* m, const kh_penalties* p) {
+  if (p && !kh_penalties_valid(p)) return KH_ERR_INVALID_ARG;
+  if (!m) return KH_ERR_INVALID_ARG;
+  const kh_penalties before = m->pen;
+  m->pen = p ? *p : kh_penalties{1.f, 0.f, 0.f, 0};
+  const int rc = proc_commit(m);
+  if (rc != KH_OK) m->pen = before;
+  return rc;
+}
+extern "C" int kh_model_get_penalties(const kh_model* m, kh_penalties* out) {
+  if (!m || !out) return KH_ERR_INVALID_ARG;
+  *out = m->pen;
+  return KH_OK;
+}
+extern "C" int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const float* h_bias, int32_t n) {
+  if (n < 0 || (n > 0 && (!h_ids || !h_bias))) return KH_ERR_INVALID_ARG;
+  return kh_api_guard([&]() -> int {
+    // every check before any device call: values, ids that no vocabulary has, duplicates; then what needs the model
+    for (int i = 0; i < n; ++i)
+      if (h_bias[i] != h_bias[i] || h_bias[i] == INFINITY) return KH_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i)
+      if (h_ids[i] < 0) return KH_ERR_RANGE;
+    std::vector<int32_t> ids(h_ids, h_ids + n);
+    std::sort(ids.begin(), ids.end());
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return KH_ERR_INVALID_ARG;
+    if (!m) return KH_ERR_INVALID_ARG;
+    const int V = m->cfg.vocab_size;
+    if (n > 0 && ids.back() >= V) return KH_ERR_RANGE;
+    int banned = 0;
+    for (int i = 0; i < n; ++i) banned += h_bias[i] == -INFINITY;
+    if (banned >= V) return KH_ERR_INVALID_ARG;  // (ids are distinct and in range) nothing left to pick
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    if (n > m->bias_cap) {
+      // the captured k_sample_proc launches hold the old pointers: drain, replace, rebuild the graphs on next use
+      KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+      if (m->d_bias_ids) (void)hipFree(m->d_bias_ids);
+      if (m->d_bias) (void)hipFree(m->d_bias);
+      m->d_bias_ids = nullptr;
+      m->d_bias = nullptr;
+      m->bias_cap = 0;
+      m->n_bias = 0;
+      const int cap = n < 64 ? 64 : n;
+      int rc;
+      if ((rc = dalloc(&m->d_bias_ids, (size_t)cap)) != KH_OK) return rc;
+      if ((rc = dalloc(&m->d_bias, (size_t)cap)) != KH_OK) return rc;
+      m->bias_cap = cap;
+      destroy_step_graphs(m);
+    }
+    if (n > 0) {
+      KH_CHECK_HIP(hipMemcpyAsync(m->d_bias_ids, h_ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+      KH_CHECK_HIP(hipMemcpyAsync(m->d_bias, h_bias, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    }
+    m->n_bias = n;
+    return proc_commit(m);  // (its sync keeps the caller's arrays alive for the uploads)
+  });
 }
 
 extern "C" int kh_model_generate(kh_model* m, const int32_t* h_prompt, int32_t n_prompt,
@@ -786,6 +897,11 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
   //                  on, "gemv" below that
   // any other value is an error (KH_ERR_INVALID_ARG), not a silent choice.
   int start = 0;
+  // the token record of the processors' window: the prompt, -1 behind it (the steps write what they feed; the dry
+  // launches above left a throw-away continuation in slots 1 .. 8)
+  if (m->proc_on)
+    KH_CHECK_HIP(hipMemcpyAsync(m->d_hist, m->d_forced, sizeof(int32_t) * (size_t)m->forced_hwm, hipMemcpyDeviceToDevice,
+                                m->stream));
   KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
   if (n_prompt - 1 >= 2 && n_prompt - 1 < total_steps) {
     const char* e = dbg("KH_PREFILL");
@@ -797,11 +913,11 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
       else return KH_ERR_INVALID_ARG;
     }
     if (want_gemm && pg_supported(m)) {
-      if ((rc = kh_model_prefill_gemm(m, h_prompt, n_prompt - 1, 0)) != KH_OK) return rc;
+      if ((rc = prefill_gemm_run(m, h_prompt, n_prompt - 1, 0)) != KH_OK) return rc;
       start = n_prompt - 1;
       m->first_mode = 2;
     } else if (want_gemv && prefill_supported(m)) {
-      if ((rc = kh_model_prefill(m, h_prompt, n_prompt - 1, 0)) != KH_OK) return rc;
+      if ((rc = prefill_run(m, h_prompt, n_prompt - 1, 0)) != KH_OK) return rc;
       start = n_prompt - 1;
       m->first_mode = 1;
     }

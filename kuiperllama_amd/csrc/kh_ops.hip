@@ -11,7 +11,7 @@
 
 #include "kh_common.h"
 #include "kh_gemv.h"
-#include "kh_sample.h"
+#include "kh_sample.h"  // (includes kh_logit_proc.h)
 
 // =============================================================================================
 // add / swiglu / scale : elementwise, HBM/L2-bound, float4 body + scalar tail
@@ -769,6 +769,28 @@ extern "C" int kh_sample_f32_host(const float* logits, int64_t n, const kh_sampl
   }
   *h_out = h;
   return rc;
+}
+
+// =============================================================================================
+// repetition / presence / frequency penalties and logit bias, in place (kh_logit_proc.h)
+extern "C" int64_t kh_logit_process_workspace_bytes(int64_t n) {
+  return n > 0 && n <= 0x7fffffffLL ? n * (int64_t)sizeof(int32_t) : KH_ERR_INVALID_ARG;
+}
+extern "C" int kh_logit_process_f32(float* logits, int64_t n, const int32_t* d_tokens, const int32_t* d_pos,
+                                    int32_t pos, const kh_penalties* p, const int32_t* d_bias_ids,
+                                    const float* d_bias, int32_t n_bias, void* workspace, void* stream) {
+  if (p && !kh_penalties_valid(p)) return KH_ERR_INVALID_ARG;
+  if (!logits || n <= 0 || n > 0x7fffffffLL || n_bias < 0 || (n_bias > 0 && (!d_bias_ids || !d_bias)) ||
+      (!d_pos && pos < 0))
+    return KH_ERR_INVALID_ARG;
+  const bool pen = !kh_penalties_neutral(p);
+  if (pen && (!d_tokens || !workspace)) return KH_ERR_INVALID_ARG;
+  if (!pen && n_bias == 0) return KH_OK;  // off: nothing to launch
+  const KhProcParams dp = pen ? KhProcParams{p->repetition, p->presence, p->frequency, p->last_n, n_bias}
+                              : KhProcParams{1.f, 0.f, 0.f, 0, n_bias};
+  hipLaunchKernelGGL(k_logit_process, dim3(1), dim3(KH_PROC_THREADS), 0, (hipStream_t)stream, logits, (int)n,
+                     d_tokens, d_pos, (int)pos, dp, d_bias_ids, d_bias, (int32_t*)workspace);
+  return kh_launch_status();
 }
 
 // =============================================================================================

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "kh_common.h"
+#include "kh_logit_proc.h"
 
 #define KH_SAMP_THREADS 1024
 #define KH_SAMP_NB 2048   // histogram bins = 2^11 (one 11-bit digit of a radix descent)
@@ -514,6 +515,83 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_topp(const Kh
     *a.d_next = reported;
     if (a.advance) {
       if (a.words && pos < a.words_cap) a.words[pos] = feed;
+      *a.d_token = feed;
+      *a.d_pos = pos + 1;
+    }
+  }
+  const int nxt = a.advance ? feed : -1;
+  if (nxt >= 0 && nxt < a.vocab) {
+    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
+    f32x4* dst = (f32x4*)a.x;
+    for (int i = threadIdx.x; i < (a.dim >> 2); i += KH_SAMP_THREADS) dst[i] = src[i];
+  }
+}
+
+// ---- the decode step's last launch while penalties or a logit bias are set (kh_logit_proc.h): k_sample_topp's duties
+// on the PROCESSED logits.  Forced steps leave before touching a logit; otherwise the processing core rewrites the
+// logits in place, one pass finds their maximum and its first index (k_cls's partials describe the raw logits), and
+// the pick is that index or, when the device copy of the sampling parameters has T > 0, the sampler core's draw with
+// counter = position.  Also records the token it feeds next in hist[pos + 1] (the window of the steps that follow).
+struct KhSampleProcArgs {
+  float* logits;
+  const KhSampParams* params;  // device copy (kh_model_set_sampling; T <= 0 while the model is greedy)
+  const KhProcParams* proc;    // device copy (kh_model_set_penalties / kh_model_set_logit_bias)
+  const int32_t* bias_ids;
+  const float* bias;
+  int32_t* hist;               // [hist_cap] token fed at every position
+  int hist_cap;
+  int32_t* cnt;                // [vocab] counters, zero between launches
+  const int32_t* forced;
+  int n_forced;
+  int32_t* words;
+  int words_cap;
+  int32_t* d_next;
+  int32_t* d_token;
+  int32_t* d_pos;
+  const float* tok_emb;
+  float* x;
+  int dim, vocab;
+  int advance;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_proc(const KhSampleProcArgs a) {
+  __shared__ KhSampSmem s;
+  __shared__ int s_pos, s_forced;
+  if (threadIdx.x == 0) {
+    const int pos = *a.d_pos;
+    s_pos = pos;
+    s_forced = (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) ? a.forced[pos + 1] : -1;
+  }
+  __syncthreads();
+  const int pos = s_pos, forced = s_forced;
+  int feed, reported;
+  if (forced >= 0) {
+    feed = forced;  // prompt phase: next = tokens[pos+1] (main.cpp:36-38)
+    reported = -1;
+  } else {
+    const KhProcParams pp = *a.proc;
+    kh_logit_process_core(a.logits, a.vocab, a.hist, pos, pp, a.bias_ids, a.bias, a.cnt);
+    float v = -INFINITY;
+    int idx = 0x7fffffff;
+    kh_samp_for_global(a.logits, a.vocab, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
+    wave_amax(v, idx);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+      s.red[wave] = v;
+      s.red_i[wave] = idx;
+    }
+    __syncthreads();
+    v = s.red[0];
+    idx = s.red_i[0];
+    for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) amax_merge(v, idx, s.red[w], s.red_i[w]);
+    __syncthreads();  // s.red is the sampler core's too
+    const KhSampParams p = *a.params;
+    feed = reported = p.temperature > 0.f ? kh_sample_core(s, a.logits, a.vocab, v, p, (uint32_t)pos) : idx;
+  }
+  if (threadIdx.x == 0) {
+    *a.d_next = reported;
+    if (a.advance) {
+      if (a.words && pos < a.words_cap) a.words[pos] = feed;
+      if (pos + 1 < a.hist_cap) a.hist[pos + 1] = feed;
       *a.d_token = feed;
       *a.d_pos = pos + 1;
     }

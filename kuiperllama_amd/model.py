@@ -119,6 +119,28 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_get_sampling(self._h, C.byref(s)), "kh_model_get_sampling")
         return s.as_dict()
 
+    def set_penalties(self, repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0,
+                      last_n: int = 0) -> None:
+        """Penalties of predict / generate over the last_n fed tokens (0: all of them), prompt included
+        (kh_model_set_penalties): l = l / repetition (l > 0) or l * repetition, then l -= count * frequency + presence,
+        for every token in the window, ahead of the greedy or sampled pick.  The defaults turn them off."""
+        _ffi.check(_ffi.lib().kh_model_set_penalties(self._h, _ffi.penalties(repetition, presence, frequency, last_n)),
+                   "kh_model_set_penalties")
+
+    @property
+    def penalties(self) -> dict:
+        p = _ffi.Penalties()
+        _ffi.check(_ffi.lib().kh_model_get_penalties(self._h, C.byref(p)), "kh_model_get_penalties")
+        return p.as_dict()
+
+    def set_logit_bias(self, bias: Optional[dict] = None) -> None:
+        """{token id: value} added to the logits after the penalties (kh_model_set_logit_bias); -inf bans a token,
+        None or {} clears the list."""
+        items = sorted((int(k), float(v)) for k, v in (bias or {}).items())
+        ids = (C.c_int32 * max(len(items), 1))(*[k for k, _ in items])
+        vals = (C.c_float * max(len(items), 1))(*[v for _, v in items])
+        _ffi.check(_ffi.lib().kh_model_set_logit_bias(self._h, ids, vals, len(items)), "kh_model_set_logit_bias")
+
     def logits(self) -> np.ndarray:
         out = np.empty(self.cfg.vocab_size, np.float32)
         _ffi.check(_ffi.lib().kh_model_get_logits(self._h, out.ctypes.data), "kh_model_get_logits")

@@ -183,6 +183,31 @@ def sample_host(logits, params, counter: int = 0) -> int:
     return int(r.value)
 
 
+def logit_process_workspace(n: int, device):
+    """Zeroed counter table for logit_process (zeroed once: the kernel leaves it zero)."""
+    nb = int(_ffi.lib().kh_logit_process_workspace_bytes(int(n)))
+    if nb < 0:
+        _ffi.check(nb, "kh_logit_process_workspace_bytes")
+    return torch.zeros(nb // 4, dtype=torch.int32, device=device)
+
+
+def logit_process(logits, tokens, pos, penalties=None, bias_ids=None, bias=None, workspace=None):
+    """Penalties and logit bias in place on `logits` (kh_logit_process_f32).  tokens: int32 GPU tensor, the token fed
+    at every position up to `pos` (a python int, or a 1-element int32 GPU tensor: graph-capturable form); penalties: an
+    _ffi.Penalties or a dict with repetition / presence / frequency / last_n; bias_ids / bias: int32 / float32 GPU
+    tensors of equal length; workspace: logit_process_workspace(logits.numel())."""
+    p = penalties if isinstance(penalties, _ffi.Penalties) or penalties is None else _ffi.penalties(**penalties)
+    d_pos, ipos = (None, int(pos)) if not torch.is_tensor(pos) else (_p(pos, torch.int32), 0)
+    nb = 0 if bias_ids is None else bias_ids.numel()
+    if nb and (bias is None or bias.numel() != nb):
+        raise ValueError("bias_ids and bias must have the same length")
+    _ffi.check(_ffi.lib().kh_logit_process_f32(_p(logits, torch.float32), logits.numel(), _p(tokens, torch.int32),
+                                               d_pos, ipos, p, _p(bias_ids, torch.int32) if nb else None,
+                                               _p(bias, torch.float32) if nb else None, nb,
+                                               _p(workspace, torch.int32), _stream()), "kh_logit_process_f32")
+    return logits
+
+
 def softmax_(x):
     _ffi.check(_ffi.lib().kh_softmax_f32(_p(x, torch.float32), x.numel(), _stream()),
                "kh_softmax_f32")

@@ -14,12 +14,17 @@
 //               [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json [--hf-spaces]] [--text "a"]
 //               [--exact-prefill] [--fenced-merge]
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
+//               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
+//               [--logit-bias id=value]...
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
 // prompt tokens/s).  --fenced-merge = KH_FLAG_ATTN_MERGE_FENCED.  The self-checks of kh_model_create_* are printed.
 // --temperature / --top-k / --top-p / --seed: seeded sampling instead of the argmax (kh_model_set_sampling; the
 // reference's demo is greedy, which stays the default).
+// --repeat-penalty / --presence-penalty / --frequency-penalty over the last --repeat-last-n fed tokens (0: all of
+// them; llama.cpp's flags of the same names) and --logit-bias id=value (repeatable; value -inf bans the token):
+// kh_model_set_penalties / kh_model_set_logit_bias, applied to the logits ahead of the greedy or sampled pick.
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <chrono>
 #include <cstdio>
@@ -36,7 +41,9 @@ static void usage() {
                "       [--theta F] [--eps F] [--steps N] [--prompt id,id,...] [--stop id,id] [--exec graph|fused|unfused]\n"
                "       [--max-seq-len N] [--device D] [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json\n"
                "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge]\n"
-               "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n");
+               "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
+               "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
+               "       [--logit-bias id=value]...\n");
 }
 
 int main(int argc, char** argv) {
@@ -47,6 +54,9 @@ int main(int argc, char** argv) {
   const char* path = argv[1];
   kh_model_opts o{KH_FAMILY_LLAMA, 0, KH_ROPE_INTERLEAVED, 10000.f, 1e-5f, 0, 0, 0};
   kh_sampling samp{0.f, 0, 1.f, 0};  // greedy unless --temperature > 0 (kh_model_set_sampling)
+  kh_penalties pen{1.f, 0.f, 0.f, 0};  // off unless one of the penalty flags says more (kh_model_set_penalties)
+  std::vector<int32_t> bias_ids;       // --logit-bias id=value (kh_model_set_logit_bias)
+  std::vector<float> bias_vals;
   int steps = 128, exec = KH_EXEC_GRAPH;
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
@@ -79,6 +89,20 @@ int main(int argc, char** argv) {
     else if (a == "--top-k") samp.top_k = std::atoi(next());
     else if (a == "--top-p") samp.top_p = (float)std::atof(next());
     else if (a == "--seed") samp.seed = std::strtoull(next(), nullptr, 0);
+    else if (a == "--repeat-penalty") pen.repetition = (float)std::atof(next());
+    else if (a == "--presence-penalty") pen.presence = (float)std::atof(next());
+    else if (a == "--frequency-penalty") pen.frequency = (float)std::atof(next());
+    else if (a == "--repeat-last-n") pen.last_n = std::atoi(next());
+    else if (a == "--logit-bias") {
+      const std::string e = next();
+      const size_t eq = e.find('=');
+      if (eq == std::string::npos || eq == 0 || eq + 1 >= e.size()) {
+        usage();
+        return 2;
+      }
+      bias_ids.push_back(std::atoi(e.substr(0, eq).c_str()));
+      bias_vals.push_back(std::strtof(e.c_str() + eq + 1, nullptr));  // "-inf" parses
+    }
     else if (a == "--text") {
       text = next();
       have_text = true;
@@ -179,6 +203,16 @@ int main(int argc, char** argv) {
   if (samp.temperature > 0.f)
     std::fprintf(stderr, "sampling: temperature %g, top-k %d, top-p %g, seed %llu\n", samp.temperature, samp.top_k,
                  samp.top_p, (unsigned long long)samp.seed);
+  rc = kh_model_set_penalties(m, &pen);
+  if (rc == KH_OK) rc = kh_model_set_logit_bias(m, bias_ids.data(), bias_vals.data(), (int32_t)bias_ids.size());
+  if (rc != KH_OK) {
+    std::fprintf(stderr, "invalid penalties or logit bias: %d (%s)\n", rc, kh_error_string(rc));
+    kh_model_destroy(m);
+    return 1;
+  }
+  if (pen.repetition != 1.f || pen.presence != 0.f || pen.frequency != 0.f || !bias_ids.empty())
+    std::fprintf(stderr, "logit processors: repeat %g, presence %g, frequency %g over the last %d tokens (0: all), %zu bias entries\n",
+                 pen.repetition, pen.presence, pen.frequency, pen.last_n, bias_ids.size());
   std::vector<int32_t> words((size_t)steps);
   int32_t n = 0;
   float gpu_ms = 0.f;
