@@ -207,6 +207,28 @@ int kh_logit_process_f32(float* logits, int64_t n, const int32_t* d_tokens, cons
                          const kh_penalties* p, const int32_t* d_bias_ids, const float* d_bias, int32_t n_bias,
                          void* workspace, void* stream);
 
+/* Log-probabilities: what a pick was worth and which tokens it beat (the logprobs / top_logprobs of the inference
+ * APIs).  The input is a logit vector l[0..V) with entries finite or -inf, at least one finite:
+ *   1. m = max l;  lse = m + log(sum_i exp(l_i - m));
+ *   2. lp(i) = l_i - lse;  lp(i) = -inf where l_i = -inf;
+ *   3. the top-N, 0 <= N <= KH_LOGPROBS_MAX_TOP, are the first N tokens of the sampler's order (logit descending, index
+ *      ascending): ties at the cut go to the lower index; if fewer than N logits are finite, -inf entries follow in
+ *      index order with lp = -inf.
+ * These are the log-probs of the softmax of l itself - inside a model, of the PROCESSED logits (after penalties and
+ * bias, before temperature, top-k and top-p).  The ids are exact (ordering fp32 values involves no arithmetic); lse
+ * and lp are fp32: the sum of exp is accumulated in fp32 (four strided partials per thread of a 1024-thread workgroup,
+ * then a tree), within 2^-24 (ceil(V / 1024) + 16) + 2^-23 (|lse| + |lp|) of the fp64 values
+ * (tests/logprobs_ref.py is the fp64 statement).  One 1024-thread workgroup per row; with the maximum known, one pass
+ * over the logits for the sum and the candidate histogram and one for the gather of the candidates (csrc/kh_logprobs.h;
+ * DESIGN.md 3.3d has the pass count and the cost). */
+#define KH_LOGPROBS_MAX_TOP 20
+/* logits [n_rows][n] row-major (DEVICE); d_ids[n_rows]: the token whose log-prob each row reports (an id outside
+ * [0, n), or d_ids NULL, gives NaN) -> d_lse[n_rows], d_lp[n_rows], d_top_ids[n_rows][top_n], d_top_lp[n_rows][top_n]
+ * (DEVICE; any of them may be NULL).  Asynchronous, graph-capturable, never allocates.  KH_ERR_INVALID_ARG, before any
+ * device call, for top_n < 0, top_n > KH_LOGPROBS_MAX_TOP, top_n > n, n_rows <= 0 or a NULL logits. */
+int kh_logprobs_f32(const float* logits, int64_t n, int32_t n_rows, const int32_t* d_ids, int32_t top_n, float* d_lse,
+                    float* d_lp, int32_t* d_top_ids, float* d_top_lp, void* stream);
+
 /* CPU-only helpers of the reference (kernels_interface.h:38-46), provided on device so the
  * op set is closed: softmax in place, x *= scale, out += sum_t scale[t]*value[t*stride..] */
 int kh_softmax_f32(float* x, int32_t n, void* stream);
@@ -436,6 +458,30 @@ int kh_model_get_sampling(const kh_model* m, kh_sampling* out);
 int kh_model_set_penalties(kh_model* m, const kh_penalties* p);
 int kh_model_get_penalties(const kh_model* m, kh_penalties* out);
 int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const float* h_bias, int32_t n);
+
+/* Per-token log-probabilities of the model's picks (top_n = -1: off, the default of every model; 0: the picked token
+ * only; 1 .. KH_LOGPROBS_MAX_TOP: and that many alternatives).  While on, every SAMPLED position p of kh_model_predict
+ * (fused and unfused), kh_model_generate and kh_model_generate_until leaves a record: the picked token (= words[p]),
+ * its log-prob, top_id[top_n] and top_lp[top_n] - kh_logprobs_f32's semantics on the logits the pick was made from
+ * (the processed logits when processors are on; never the tempered or truncated sampling distribution).  Asking for
+ * log-probs changes no token: the pick is the first maximum, or kh_sample_f32's draw with counter = position, exactly
+ * as without them.  A position that was fed but not sampled - prompt positions, rows a prefill covered - holds the
+ * "none" record: token -1, ids -1, NaN floats.  A generate resets the records of its prompt positions [0, n_prompt - 1)
+ * to "none"; like the K/V rows, records of other positions are whatever earlier calls left.  Records live in device
+ * buffers sized by the cache, allocated by the first call that turns the feature on.  While on, the step's last launch
+ * is k_sample_lp (k_sample_proc's duties, then the record: launches_per_token is unchanged) and the screened classifier
+ * is not used; while off the model runs exactly the launches it runs without this feature.  top_n lives in a device
+ * word written on the model stream and records have a fixed stride: a new top_n needs no graph recapture.
+ * kh_model_set_logprobs: KH_ERR_INVALID_ARG for top_n < -1, top_n > KH_LOGPROBS_MAX_TOP or top_n > vocab_size.
+ * kh_model_get_logprobs copies the records of positions [pos0, pos0 + n) to the host - h_token[n], h_lp[n],
+ * h_top_ids[n][top_n], h_top_lp[n][top_n] with top_n the setting in force at the call (none while off); any of them may
+ * be NULL - and synchronises the stream.  KH_ERR_UNSUPPORTED when log-probs were never turned on, KH_ERR_RANGE for a
+ * range outside [0, cache_len).  After kh_model_generate_until the records of positions n_prompt - 1 .. *n_words - 1
+ * are the returned words' records; records past the stop are whatever the discarded steps left. */
+int kh_model_set_logprobs(kh_model* m, int32_t top_n);
+int kh_model_get_logprobs_setting(const kh_model* m, int32_t* top_n);
+int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32_t* h_token, float* h_lp, int32_t* h_top_ids,
+                          float* h_top_lp);
 
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,

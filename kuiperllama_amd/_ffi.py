@@ -18,7 +18,7 @@ EXPORTS = [
     "kh_add_f32", "kh_matmul_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
     "kh_mha_decode_workspace_bytes", "kh_argmax_f32",
-    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
+    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
     "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
@@ -26,19 +26,22 @@ EXPORTS = [
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
-    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
+    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
 ]
 
 KH_EXEC_GRAPH, KH_EXEC_FUSED, KH_EXEC_UNFUSED = 0, 1, 2
 KH_NUM_KCLASS = 7
+KH_ERR_INVALID_ARG = -1
+KH_ERR_UNSUPPORTED = -2
 KH_ERR_RANGE = -6
 KH_ERR_INTERNAL = -7
 KH_FLAG_ATTN_MERGE_IN_LAUNCH = 1
 KH_FLAG_ATTN_MERGE_FENCED = 2
 KH_FLAG_PREFILL_EXACT = 4
 KH_FLAG_NO_CLS_SCREEN = 8
+KH_LOGPROBS_MAX_TOP = 20
 
 
 class KhError(RuntimeError):
@@ -138,6 +141,7 @@ def lib() -> C.CDLL:
     L.kh_logit_process_workspace_bytes.argtypes = [_i64]
     L.kh_logit_process_workspace_bytes.restype = _i64
     L.kh_logit_process_f32.argtypes = [_vp, _i64, _vp, _vp, _i32, C.POINTER(Penalties), _vp, _vp, _i32, _vp, _vp]
+    L.kh_logprobs_f32.argtypes = [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]
     L.kh_softmax_f32.argtypes = [_vp, _i32, _vp]
     L.kh_scale_f32.argtypes = [_f32, _vp, _i32, _vp]
     L.kh_scale_sum_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _vp]
@@ -172,6 +176,9 @@ def lib() -> C.CDLL:
     L.kh_model_set_penalties.argtypes = [_vp, C.POINTER(Penalties)]
     L.kh_model_get_penalties.argtypes = [_vp, C.POINTER(Penalties)]
     L.kh_model_set_logit_bias.argtypes = [_vp, C.POINTER(_i32), C.POINTER(_f32), _i32]
+    L.kh_model_set_logprobs.argtypes = [_vp, _i32]
+    L.kh_model_get_logprobs_setting.argtypes = [_vp, C.POINTER(_i32)]
+    L.kh_model_get_logprobs.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp]
     L.kh_model_time_step.argtypes = [_vp, _i32, _i32, C.POINTER(_f32)]
     L.kh_plan_decode_shapes.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]
     L.kh_plan_decode_ring.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]

@@ -1,0 +1,296 @@
+// kh_logprobs.h — log-probability of a token and the top-N alternatives of a logit vector on the device (gfx950).
+//
+// Semantics (include/kuiper_hip.h, "Log-probabilities"; tests/logprobs_ref.py is the fp64 statement of the same):
+//   m = max l, lse = m + log(sum exp(l_i - m)), lp(i) = l_i - lse (-inf where l_i = -inf); the top-N are the first N
+//   tokens of the sampler's order (logit descending, index ascending), 0 <= N <= KH_LOGPROBS_MAX_TOP.
+//
+// One workgroup of 1024 threads per vector, given l_max, on the sampler's shared memory and machinery (kh_sample.h):
+//   pass 1 (global)  every thread sums expf(l - l_max) of its float4 column (thread t owns float4 t, t + 1024, ...: four
+//                    fp32 partials of at most ceil(V / 4096) adds each, two adds to join them, then a ten-level tree
+//                    over the workgroup) and counts the token on the sampler's first-pass bins of l_max - l (32 per
+//                    unit).  The bins up to the one where the running count reaches N hold every token the top-N can
+//                    contain: the CANDIDATES.
+//   pass 2 (global)  the candidates are compacted into LDS (at most KH_SAMP_CAP of them; more - flat logits, or fewer
+//                    than N finite ones - leaves them in global memory and every step below re-reads the logits).
+//   then             on the candidates: the sampler's exact radix descent to the order key of the N-th token, its
+//                    index descent for the cut among equal logits at the boundary, the gather of the exactly N
+//                    survivors into LDS and their ranks (N threads, N comparisons each).
+// N = 0 stops after pass 1 and counts nothing.  The order involves no arithmetic, so the ids are exact; the floats
+// carry the fp32 roundings of the sum, logf, l_max + log Z and l - lse.
+// No scratch, no inline assembly; every result is written with plain C++ stores.
+#pragma once
+#include "kh_sample.h"
+
+#define KH_LOGPROBS_TOP KH_LOGPROBS_MAX_TOP  // (kuiper_hip.h) also the stride of a model's records
+
+struct KhLpSmem {
+  float l[KH_LOGPROBS_TOP];
+  int32_t i[KH_LOGPROBS_TOP];
+  int n;
+};
+
+// Called by all 1024 threads of the workgroup with uniform arguments.  id: the token whose log-prob goes to *o_lp
+// (outside [0, n): NaN).  Any output pointer may be null; o_top_ids / o_top_lp receive top_n entries.  Inlined into
+// each kernel: a call would save the callee's registers in scratch.
+__device__ __forceinline__ void kh_logprobs_core(KhSampSmem& s, KhLpSmem& t, const float* logits, int n, float lmax,
+                                                 int id, int top_n, float* o_lse, float* o_lp, int32_t* o_top_ids,
+                                                 float* o_top_lp) {
+  KhSampCtx c;
+  c.logits = logits;
+  c.n = n;
+  c.lmax = lmax;
+  c.T = 1.f;
+  c.fx_scale = 0.0;  // the descents below count, they weigh nothing
+  c.b_end = KH_SAMP_NB - 1;
+  c.in_lds = false;
+  const bool want_top = top_n > 0 && (o_top_ids || o_top_lp);
+  __syncthreads();  // whatever the caller did with s is over
+  for (int b = threadIdx.x; b < KH_SAMP_NB; b += KH_SAMP_THREADS) {
+    s.cnt[b] = 0;
+    s.wsum[b] = 0;
+  }
+  if (threadIdx.x == 0) {
+    s.ncand = 0;
+    t.n = 0;
+  }
+  __syncthreads();
+  // ---- pass 1: sum of exp and the candidate histogram
+  float z0 = 0.f, z1 = 0.f, z2 = 0.f, z3 = 0.f;
+  {
+    KhSampRun run;
+    auto one = [&](float l, float& z) __attribute__((always_inline)) {
+      const float e = c.expo(l);
+      z += expf(e);
+      if (want_top) run.add(s.cnt, s.wsum, c.bin_of(e), 0ull);
+    };
+    int done = 0;
+    if ((((uintptr_t)logits) & 15u) == 0) {
+      const int n4 = n >> 2;
+      const f32x4* l4 = (const f32x4*)logits;
+      auto four = [&](const f32x4& v) __attribute__((always_inline)) {
+        one(v.x, z0);
+        one(v.y, z1);
+        one(v.z, z2);
+        one(v.w, z3);
+      };
+      // four loads in flight per thread, each a contiguous kilobyte per wave
+      for (int q = threadIdx.x; q < n4; q += 4 * KH_SAMP_THREADS) {
+        const int q1 = q + KH_SAMP_THREADS, q2 = q + 2 * KH_SAMP_THREADS, q3 = q + 3 * KH_SAMP_THREADS;
+        const f32x4 v0 = l4[q];
+        f32x4 v1 = v0, v2 = v0, v3 = v0;
+        if (q1 < n4) v1 = l4[q1];
+        if (q2 < n4) v2 = l4[q2];
+        if (q3 < n4) v3 = l4[q3];
+        four(v0);
+        if (q1 < n4) four(v1);
+        if (q2 < n4) four(v2);
+        if (q3 < n4) four(v3);
+      }
+      done = 4 * n4;
+    }
+    for (int i = done + threadIdx.x; i < n; i += KH_SAMP_THREADS) one(logits[i], z0);
+    run.flush(s.cnt, s.wsum);
+  }
+  float z = (z0 + z1) + (z2 + z3);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off, KH_WAVE);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) s.red[wave] = z;
+  __syncthreads();
+  z = lane < KH_SAMP_THREADS / KH_WAVE ? s.red[lane] : 0.f;
+#pragma unroll
+  for (int off = KH_SAMP_THREADS / KH_WAVE / 2; off > 0; off >>= 1) z += __shfl_xor(z, off, KH_WAVE);
+  z = __shfl(z, 0, KH_WAVE);  // the same sixteen words in the same order in every wave
+  const float lse = __fadd_rn(lmax, logf(z));
+  if (threadIdx.x == 0) {
+    if (o_lse) *o_lse = lse;
+    if (o_lp) *o_lp = (unsigned)id < (unsigned)n ? __fsub_rn(logits[id], lse) : __uint_as_float(0x7fc00000u);
+  }
+  if (!want_top) return;  // uniform
+
+  // ---- the candidate bins, pass 2: compaction
+  kh_samp_walk(s, KH_SAMP_NB, false, false, false, (double)top_n, 0, 0);
+  __syncthreads();
+  c.b_end = s.r_digit >= 0 ? s.r_digit : KH_SAMP_NB - 1;
+  const unsigned long long ncand = s.r_digit >= 0 ? s.r_cb + s.cnt[s.r_digit] : (unsigned long long)n;
+  __syncthreads();
+  if (ncand <= KH_SAMP_CAP) {
+    kh_samp_for_global(logits, n, [&](float l, int i) __attribute__((always_inline)) {
+      if (c.bin_of(c.expo(l)) <= c.b_end) {
+        const int slot = atomicAdd(&s.ncand, 1);
+        if (slot < KH_SAMP_CAP) {
+          s.cl[slot] = l;
+          s.ci[slot] = i;
+        }
+      }
+    });
+    c.in_lds = true;
+    __syncthreads();
+  }
+  // ---- the key of the top_n-th token of the order, and the index cut among its equals
+  const KhSampDesc dk = kh_samp_descend(
+      c, s, [&](float l, int, uint32_t& v) __attribute__((always_inline)) { v = kh_okey(l); return true; }, 32,
+      /*desc=*/true, /*by_w=*/false, /*strict=*/false, (double)top_n);
+  const uint32_t t_key = dk.value;
+  const unsigned long long m_key = (unsigned long long)top_n - dk.c_before;
+  int i_cut = 0x7fffffff;
+  if (m_key < dk.c_at) {
+    const KhSampDesc di = kh_samp_descend(
+        c, s,
+        [&](float l, int i, uint32_t& v) __attribute__((always_inline)) {
+          v = (uint32_t)i;
+          return kh_okey(l) == t_key;
+        },
+        32 - __clz(n), /*desc=*/false, /*by_w=*/false, /*strict=*/false, (double)m_key, /*low8=*/true);
+    if (di.found) i_cut = (int)di.value;
+  }
+  // ---- the survivors, ranked
+  kh_samp_for_src(c, s, [&](float l, int i) __attribute__((always_inline)) {
+    const uint32_t k = kh_okey(l);
+    if (k > t_key || (k == t_key && i <= i_cut)) {
+      const int slot = atomicAdd(&t.n, 1);
+      if (slot < KH_LOGPROBS_TOP) {
+        t.l[slot] = l;
+        t.i[slot] = i;
+      }
+    }
+  });
+  __syncthreads();
+  const int got = min(t.n, min(top_n, KH_LOGPROBS_TOP));
+  if ((int)threadIdx.x < got) {
+    const float l = t.l[threadIdx.x];
+    const int i = t.i[threadIdx.x];
+    const uint32_t k = kh_okey(l);
+    int rank = 0;
+    for (int j = 0; j < got; ++j) {
+      const uint32_t kj = kh_okey(t.l[j]);
+      rank += kj > k || (kj == k && t.i[j] < i);
+    }
+    if (o_top_ids) o_top_ids[rank] = i;
+    if (o_top_lp) o_top_lp[rank] = __fsub_rn(l, lse);
+  }
+}
+
+// ---- operator: one workgroup per row of logits[n_rows][n]
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_logprobs_op(const float* logits, int n, const int32_t* ids,
+                                                                         int top_n, float* lse, float* lp,
+                                                                         int32_t* top_ids, float* top_lp) {
+  __shared__ KhSampSmem s;
+  __shared__ KhLpSmem t;
+  const size_t row = blockIdx.x;
+  const float* lg = logits + row * (size_t)n;
+  float m = -INFINITY;
+  kh_samp_for_global(lg, n, [&](float l, int) __attribute__((always_inline)) { m = fmaxf(m, l); });
+  const float lmax = kh_samp_block_max(s, m);
+  kh_logprobs_core(s, t, lg, n, lmax, ids ? ids[row] : -1, top_n, lse ? lse + row : nullptr, lp ? lp + row : nullptr,
+                   top_ids ? top_ids + row * (size_t)top_n : nullptr, top_lp ? top_lp + row * (size_t)top_n : nullptr);
+}
+
+// ---- the decode step's last launch while log-probs are on (kh_model_set_logprobs): k_sample_proc's duties - the
+// forced branch, the processing core when the device copy of the processors' parameters says anything is on, the
+// maximum and its first index (one pass over the processed logits; k_cls's partials when nothing was processed), the
+// greedy or sampled pick, d_next / words / hist / d_token / d_pos, the embedding gather - and then the record of the
+// position: the picked token, its log-prob and the top *top_n of the logits the pick was made from.  Records have a
+// fixed stride of KH_LOGPROBS_TOP; entries from *top_n on, and the whole record of a forced step, are "none" (-1, NaN).
+struct KhSampleLpArgs {
+  float* logits;
+  const float* part_val;       // k_cls's per-workgroup maxima of the raw logits
+  const int32_t* part_idx;
+  int nparts;
+  const KhSampParams* params;  // device copy (kh_model_set_sampling; T <= 0 while the model is greedy)
+  const KhProcParams* proc;    // device copy (kh_model_set_penalties / kh_model_set_logit_bias; neutral while off)
+  const int32_t* bias_ids;
+  const float* bias;
+  int32_t* hist;               // [hist_cap] token fed at every position
+  int hist_cap;
+  int32_t* cnt;                // [vocab] counters, zero between launches
+  const int32_t* top_n;        // device word (kh_model_set_logprobs)
+  int32_t* rec_token;          // [rec_cap]
+  float* rec_lp;               // [rec_cap]
+  int32_t* rec_top_ids;        // [rec_cap][KH_LOGPROBS_TOP]
+  float* rec_top_lp;           // [rec_cap][KH_LOGPROBS_TOP]
+  int rec_cap;
+  const int32_t* forced;
+  int n_forced;
+  int32_t* words;
+  int words_cap;
+  int32_t* d_next;
+  int32_t* d_token;
+  int32_t* d_pos;
+  const float* tok_emb;
+  float* x;
+  int dim, vocab;
+  int advance;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_lp(const KhSampleLpArgs a) {
+  __shared__ KhSampSmem s;
+  __shared__ KhLpSmem t;
+  __shared__ int s_pos, s_forced;
+  if (threadIdx.x == 0) {
+    const int pos = *a.d_pos;
+    s_pos = pos;
+    s_forced = (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) ? a.forced[pos + 1] : -1;
+  }
+  __syncthreads();
+  const int pos = s_pos, forced = s_forced;
+  const bool rec = pos >= 0 && pos < a.rec_cap;
+  const size_t r0 = (size_t)(rec ? pos : 0) * KH_LOGPROBS_TOP;
+  const float none = __uint_as_float(0xffffffffu);
+  int feed, reported, top_n = 0;
+  if (forced >= 0) {
+    feed = forced;  // prompt phase: next = tokens[pos+1] (main.cpp:36-38)
+    reported = -1;
+    if (rec && threadIdx.x == 0) {
+      a.rec_token[pos] = -1;
+      a.rec_lp[pos] = none;
+    }
+  } else {
+    const KhProcParams pp = *a.proc;
+    float v = -INFINITY;
+    int idx = 0x7fffffff;
+    if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0) {
+      kh_logit_process_core(a.logits, a.vocab, a.hist, pos, pp, a.bias_ids, a.bias, a.cnt);
+      kh_samp_for_global(a.logits, a.vocab, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
+    } else {
+      for (int i = threadIdx.x; i < a.nparts; i += KH_SAMP_THREADS) amax_merge(v, idx, a.part_val[i], a.part_idx[i]);
+    }
+    wave_amax(v, idx);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+      s.red[wave] = v;
+      s.red_i[wave] = idx;
+    }
+    __syncthreads();
+    v = s.red[0];
+    idx = s.red_i[0];
+    for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) amax_merge(v, idx, s.red[w], s.red_i[w]);
+    __syncthreads();  // s.red is the cores' too
+    const KhSampParams p = *a.params;
+    feed = reported = p.temperature > 0.f ? kh_sample_core(s, a.logits, a.vocab, v, p, (uint32_t)pos) : idx;
+    if (rec) {
+      top_n = min(max(*a.top_n, 0), min(KH_LOGPROBS_TOP, a.vocab));
+      kh_logprobs_core(s, t, a.logits, a.vocab, v, feed, top_n, nullptr, a.rec_lp + pos, a.rec_top_ids + r0,
+                       a.rec_top_lp + r0);
+      if (threadIdx.x == 0) a.rec_token[pos] = feed;
+    }
+  }
+  if (rec && (int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
+    a.rec_top_ids[r0 + threadIdx.x] = -1;
+    a.rec_top_lp[r0 + threadIdx.x] = none;
+  }
+  if (threadIdx.x == 0) {
+    *a.d_next = reported;
+    if (a.advance) {
+      if (a.words && pos < a.words_cap) a.words[pos] = feed;
+      if (pos + 1 < a.hist_cap) a.hist[pos + 1] = feed;
+      *a.d_token = feed;
+      *a.d_pos = pos + 1;
+    }
+  }
+  const int nxt = a.advance ? feed : -1;
+  if (nxt >= 0 && nxt < a.vocab) {
+    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
+    f32x4* dst = (f32x4*)a.x;
+    for (int i = threadIdx.x; i < (a.dim >> 2); i += KH_SAMP_THREADS) dst[i] = src[i];
+  }
+}

@@ -150,7 +150,7 @@ struct kh_model {
     hipGraphExec_t e = nullptr;
   };
   // [StepTail][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps per tail of the step
-  StepGraph sg[4][KH_STEP_VARIANTS][4];
+  StepGraph sg[5][KH_STEP_VARIANTS][4];
   // kh_model_set_sampling: the parameters (host copy), whether they sample (temperature > 0), and their device copy,
   // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
   kh_sampling samp{0.f, 0, 1.f, 0};
@@ -171,6 +171,18 @@ struct kh_model {
   int32_t* d_bias_ids = nullptr;
   float* d_bias = nullptr;
   int32_t* d_cnt = nullptr;  // [vocab] counters of the processing core, zero between launches
+  // Log-probs (kh_logprobs.h, kh_model_set_logprobs).  lp_top_n: -1 off, else the width of a record's top list; its
+  // device copy d_lp_top_n is what the captured k_sample_lp launches read (a new width needs no recapture).  Records of
+  // every position, [lp_cap = cache_len] with a fixed stride of KH_LOGPROBS_MAX_TOP like d_hist: predict reaches every
+  // position.  Allocated by the first call that turns the feature on, all bytes 0xff ("none": -1 / NaN) where no
+  // sampled step wrote.  While on, d_proc / d_samp / d_cnt exist too (neutral / greedy unless set): k_sample_lp reads them.
+  int lp_top_n = -1;
+  int lp_cap = 0;
+  int32_t* d_lp_top_n = nullptr;
+  int32_t* d_lp_token = nullptr;
+  float* d_lp_lp = nullptr;
+  int32_t* d_lp_top_ids = nullptr;
+  float* d_lp_top_lp = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // Screened classifier of the greedy generate loop (kh_cls_screen.h, kh_model_screen.hip): fp32 models only
   struct ClsScreen {
@@ -234,12 +246,18 @@ static inline void launch_cls(kh_model* m) {
 static inline void logits_fresh(kh_model* m) { m->scr.stale = false; }
 // The last two launches of a fused step, and the index of kh_model::sg its graphs live in: k_cls + k_sample (argmax),
 // k_cls + k_sample_topp, the screened pair k_cls_screen + k_sample_screen (greedy steps of a generate, see scr), or
-// k_cls + k_sample_proc (penalties or a logit bias set: processing, then the greedy or sampled pick)
-enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2, kProcess = 3 };
-// processing and sampling need every logit: they are stronger than a caller's wish to screen.  process = false: a
-// step whose pick is discarded (kh_model_predict at a prompt position) leaves its logits as the classifier wrote them
+// k_cls + k_sample_proc (penalties or a logit bias set: processing, then the greedy or sampled pick), or k_cls +
+// k_sample_lp (log-probs on: k_sample_proc's duties, then the record of the position)
+enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2, kProcess = 3, kLogprob = 4 };
+// log-probs, processing and sampling need every logit: they are stronger than a caller's wish to screen, and log-probs
+// are stronger than the rest.  process = false: a step whose pick is discarded (kh_model_predict at a prompt position)
+// leaves its logits as the classifier wrote them and writes no record
 static inline StepTail step_tail(const kh_model* m, bool screen, bool process = true) {
-  return m->proc_on && process ? kProcess : m->samp_on ? kSample : screen ? kScreen : kGreedy;
+  return m->lp_top_n >= 0 && process ? kLogprob
+         : m->proc_on && process     ? kProcess
+         : m->samp_on                ? kSample
+         : screen                    ? kScreen
+                                     : kGreedy;
 }
 // the fields every step tail shares: KhSampleArgs, KhSampleTopArgs and KhSampleScreenArgs name them alike
 template <class A>
@@ -266,6 +284,8 @@ int launch_step_unfused(kh_model* m, int pos, bool process);  // process: apply 
 void set_state(kh_model* m, int token, int pos);
 // d_hist[pos0 .. pos0 + n) = h_tokens (the public prefill entry points; a generate uploads its prompt itself)
 int hist_write(kh_model* m, const int32_t* h_tokens, int n, int pos0);
+// log-probs on: the records of positions [pos0, pos0 + n) become "none" (fed, not sampled), on the model stream
+int lp_none(kh_model* m, int pos0, int n);
 int ensure_pinned_words(kh_model* m, int n);
 int ensure_seq_cap(kh_model* m, int n);
 void destroy_step_graphs(kh_model* m);

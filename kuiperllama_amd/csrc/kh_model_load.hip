@@ -655,6 +655,8 @@ extern "C" void kh_model_destroy(kh_model* m) {
   if (m->d_samp) (void)hipFree(m->d_samp);
   for (void* q : {(void*)m->d_hist, (void*)m->d_proc, (void*)m->d_bias_ids, (void*)m->d_bias, (void*)m->d_cnt})
     if (q) (void)hipFree(q);
+  for (void* q : {(void*)m->d_lp_top_n, (void*)m->d_lp_token, (void*)m->d_lp_lp, (void*)m->d_lp_top_ids, (void*)m->d_lp_top_lp})
+    if (q) (void)hipFree(q);
   cls_screen_release(m);
   void* bufs[] = {m->x,      m->rms,    m->q,         m->att,       m->h1,       m->h3,
                   m->w2o,    m->logits, m->score,     m->sin_cache,

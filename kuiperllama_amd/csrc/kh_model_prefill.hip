@@ -538,7 +538,8 @@ extern "C" int kh_plan_prefill_shape(int32_t epi, int32_t T, int32_t rows, int32
 }
 
 extern "C" int kh_model_prefill_gemm(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
-  const int rc = khm::prefill_gemm_run(m, h_tokens, n, pos0);
+  int rc = khm::prefill_gemm_run(m, h_tokens, n, pos0);
+  if (rc == KH_OK) rc = khm::lp_none(m, pos0, n);
   return rc == KH_OK ? khm::hist_write(m, h_tokens, n, pos0) : rc;
 }
 int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
@@ -590,7 +591,8 @@ extern "C" int kh_mha_prefill_f32(int32_t pos0, int32_t n_tokens, int32_t head_n
 }
 
 extern "C" int kh_model_prefill(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
-  const int rc = khm::prefill_run(m, h_tokens, n, pos0);
+  int rc = khm::prefill_run(m, h_tokens, n, pos0);
+  if (rc == KH_OK) rc = khm::lp_none(m, pos0, n);
   return rc == KH_OK ? khm::hist_write(m, h_tokens, n, pos0) : rc;
 }
 int khm::prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {

@@ -15,6 +15,7 @@
 #include "kh_fused.h"
 #include "kh_fused_ring.h"
 #include "kh_sample.h"
+#include "kh_logprobs.h"
 #include "kh_model_internal.h"
 
 namespace khm {
@@ -317,6 +318,28 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
   if (tail == kScreen) tail = step_tail(m, true);  // processors or sampling on are stronger than "screen"
   if (tail == kScreen) {
     launch_sample_screen(m, advance, n_forced);
+  } else if (tail == kLogprob) {
+    KhSampleLpArgs t;
+    t.logits = m->logits;
+    t.part_val = m->part_val;
+    t.part_idx = m->part_idx;
+    t.nparts = m->nparts;
+    t.params = m->d_samp;
+    t.proc = m->d_proc;
+    t.bias_ids = m->d_bias_ids;
+    t.bias = m->d_bias;
+    t.hist = m->d_hist;
+    t.hist_cap = m->hist_cap;
+    t.cnt = m->d_cnt;
+    t.top_n = m->d_lp_top_n;
+    t.rec_token = m->d_lp_token;
+    t.rec_lp = m->d_lp_lp;
+    t.rec_top_ids = m->d_lp_top_ids;
+    t.rec_top_lp = m->d_lp_top_lp;
+    t.rec_cap = m->lp_cap;
+    fill_step_tail(m, advance, n_forced, &t);
+    launch_log("k_sample_lp");
+    hipLaunchKernelGGL(k_sample_lp, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
   } else if (tail == kProcess) {
     KhSampleProcArgs t;
     t.logits = m->logits;
@@ -443,6 +466,13 @@ int launch_step_unfused(kh_model* m, int pos, bool process) {
   } else {
     KH_TRY(kh_argmax_f32(m->logits, c.vocab_size, m->d_next, s));
   }
+  if (process && m->lp_top_n >= 0) {  // the record of the position, from the logits the pick was made from
+    KH_TRY(lp_none(m, pos, 1));       // (the entries behind top_n stay "none")
+    KH_CHECK_HIP(hipMemcpyAsync(m->d_lp_token + pos, m->d_next, sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream));
+    KH_TRY(kh_logprobs_f32(m->logits, c.vocab_size, 1, m->d_next, m->lp_top_n, nullptr, m->d_lp_lp + pos,
+                           m->d_lp_top_ids + (size_t)pos * KH_LOGPROBS_TOP, m->d_lp_top_lp + (size_t)pos * KH_LOGPROBS_TOP,
+                           s));
+  }
 #undef KH_TRY
   return KH_OK;
 }
@@ -456,6 +486,18 @@ int hist_write(kh_model* m, const int32_t* h_tokens, int n, int pos0) {
   // pageable source: the sync keeps the caller's array alive for the upload
   KH_CHECK_HIP(hipMemcpyAsync(m->d_hist + pos0, h_tokens, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, m->stream));
   KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
+}
+
+int lp_none(kh_model* m, int pos0, int n) {
+  if (m->lp_top_n < 0 || pos0 < 0 || pos0 >= m->lp_cap) return KH_OK;
+  if (n > m->lp_cap - pos0) n = m->lp_cap - pos0;
+  if (n <= 0) return KH_OK;
+  const size_t k = KH_LOGPROBS_TOP;
+  KH_CHECK_HIP(hipMemsetAsync(m->d_lp_token + pos0, 0xFF, sizeof(int32_t) * (size_t)n, m->stream));
+  KH_CHECK_HIP(hipMemsetAsync(m->d_lp_lp + pos0, 0xFF, sizeof(float) * (size_t)n, m->stream));
+  KH_CHECK_HIP(hipMemsetAsync(m->d_lp_top_ids + pos0 * k, 0xFF, sizeof(int32_t) * n * k, m->stream));
+  KH_CHECK_HIP(hipMemsetAsync(m->d_lp_top_lp + pos0 * k, 0xFF, sizeof(float) * n * k, m->stream));
   return KH_OK;
 }
 
@@ -648,6 +690,7 @@ extern "C" int kh_model_predict(kh_model* m, int32_t token, int32_t pos, int32_t
   int rc = kv_ensure(m, pos + 1);  // cache rows 0 .. pos backed by HBM before the step is enqueued
   if (rc != KH_OK) return rc;
   set_state(m, token, pos);  // embedding() + fill_input (llama3.cpp:578-598, model.cpp:245-263)
+  if (is_prompt && (rc = lp_none(m, pos, 1)) != KH_OK) return rc;  // fed, not sampled
   // logit processors apply to the calls whose pick is returned: prompt positions are never processed
   if (exec == KH_EXEC_UNFUSED) {
     rc = launch_step_unfused(m, pos, !is_prompt);
@@ -697,7 +740,7 @@ namespace {
 // the parameters (on the model stream, behind whatever is queued)
 int proc_commit(kh_model* m) {
   const bool on = !kh_penalties_neutral(&m->pen) || m->n_bias > 0;
-  if (on || m->d_proc) {
+  if (on || m->d_proc || m->lp_top_n >= 0) {  // (k_sample_lp reads the device copies while log-probs are on)
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     if (!m->d_proc) KH_CHECK_HIP(hipMalloc((void**)&m->d_proc, sizeof(KhProcParams)));
     if (!m->d_cnt) {
@@ -773,6 +816,86 @@ extern "C" int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const 
     }
     m->n_bias = n;
     return proc_commit(m);  // (its sync keeps the caller's arrays alive for the uploads)
+  });
+}
+
+// ---- log-probs (kh_logprobs.h)
+extern "C" int kh_model_set_logprobs(kh_model* m, int32_t top_n) {
+  if (top_n < -1 || top_n > KH_LOGPROBS_MAX_TOP || !m || top_n > m->cfg.vocab_size) return KH_ERR_INVALID_ARG;
+  if (top_n < 0) {
+    m->lp_top_n = -1;
+    return KH_OK;
+  }
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  const int before = m->lp_top_n;
+  if (!m->d_lp_token) {  // the first "on": the records of every position, all "none"
+    const size_t cap = (size_t)m->cfg.cache_len, k = KH_LOGPROBS_TOP;
+    int32_t *w = nullptr, *tok = nullptr, *ids = nullptr;
+    float *lp = nullptr, *tlp = nullptr;
+    int rc;
+    if ((rc = dalloc(&w, 1)) != KH_OK || (rc = dalloc(&tok, cap)) != KH_OK || (rc = dalloc(&lp, cap)) != KH_OK ||
+        (rc = dalloc(&ids, cap * k)) != KH_OK || (rc = dalloc(&tlp, cap * k)) != KH_OK) {
+      for (void* q : {(void*)w, (void*)tok, (void*)lp, (void*)ids, (void*)tlp})
+        if (q) (void)hipFree(q);
+      return rc;
+    }
+    m->d_lp_top_n = w;
+    m->d_lp_token = tok;
+    m->d_lp_lp = lp;
+    m->d_lp_top_ids = ids;
+    m->d_lp_top_lp = tlp;
+    m->lp_cap = (int)cap;
+    m->lp_top_n = 0;
+    if ((rc = lp_none(m, 0, m->lp_cap)) != KH_OK) {
+      m->lp_top_n = before;
+      return rc;
+    }
+  }
+  m->lp_top_n = top_n;
+  const int rc = proc_commit(m);  // the device copies of the processors' and the sampler's parameters exist
+  if (rc != KH_OK) {
+    m->lp_top_n = before;
+    return rc;
+  }
+  // written on the model stream behind whatever is queued; the sync keeps the host copy alive for the upload
+  const int32_t word = top_n;
+  hipError_t e = hipMemcpyAsync(m->d_lp_top_n, &word, sizeof(word), hipMemcpyHostToDevice, m->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+  if (e != hipSuccess) {
+    m->lp_top_n = -1;
+    return (int)e;
+  }
+  return KH_OK;
+}
+extern "C" int kh_model_get_logprobs_setting(const kh_model* m, int32_t* top_n) {
+  if (!m || !top_n) return KH_ERR_INVALID_ARG;
+  *top_n = m->lp_top_n;
+  return KH_OK;
+}
+extern "C" int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32_t* h_token, float* h_lp,
+                                     int32_t* h_top_ids, float* h_top_lp) {
+  if (!m || n <= 0) return KH_ERR_INVALID_ARG;
+  if (!m->d_lp_token) return KH_ERR_UNSUPPORTED;
+  if (pos0 < 0 || (int64_t)pos0 + n > m->lp_cap) return KH_ERR_RANGE;
+  return kh_api_guard([&]() -> int {
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    const size_t k = KH_LOGPROBS_TOP, w = m->lp_top_n > 0 ? (size_t)m->lp_top_n : 0;
+    std::vector<int32_t> ids(h_top_ids && w ? (size_t)n * k : 0);
+    std::vector<float> tlp(h_top_lp && w ? (size_t)n * k : 0);
+    if (h_token)
+      KH_CHECK_HIP(hipMemcpyAsync(h_token, m->d_lp_token + pos0, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (h_lp)
+      KH_CHECK_HIP(hipMemcpyAsync(h_lp, m->d_lp_lp + pos0, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (!ids.empty())
+      KH_CHECK_HIP(hipMemcpyAsync(ids.data(), m->d_lp_top_ids + pos0 * k, sizeof(int32_t) * ids.size(), hipMemcpyDeviceToHost, m->stream));
+    if (!tlp.empty())
+      KH_CHECK_HIP(hipMemcpyAsync(tlp.data(), m->d_lp_top_lp + pos0 * k, sizeof(float) * tlp.size(), hipMemcpyDeviceToHost, m->stream));
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    for (size_t r = 0; r < (size_t)n; ++r) {  // the records' stride -> the caller's
+      if (!ids.empty()) memcpy(h_top_ids + r * w, ids.data() + r * k, sizeof(int32_t) * w);
+      if (!tlp.empty()) memcpy(h_top_lp + r * w, tlp.data() + r * k, sizeof(float) * w);
+    }
+    return KH_OK;
   });
 }
 
@@ -902,6 +1025,9 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
   if (m->proc_on)
     KH_CHECK_HIP(hipMemcpyAsync(m->d_hist, m->d_forced, sizeof(int32_t) * (size_t)m->forced_hwm, hipMemcpyDeviceToDevice,
                                 m->stream));
+  // log-probs: the prompt positions are fed, not sampled (whatever path feeds them; the dry launches above wrote the
+  // records of a throw-away continuation at positions 0 .. 7)
+  if ((rc = lp_none(m, 0, n_prompt - 1)) != KH_OK) return rc;
   KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
   if (n_prompt - 1 >= 2 && n_prompt - 1 < total_steps) {
     const char* e = dbg("KH_PREFILL");

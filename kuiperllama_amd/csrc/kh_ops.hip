@@ -12,6 +12,7 @@
 #include "kh_common.h"
 #include "kh_gemv.h"
 #include "kh_sample.h"  // (includes kh_logit_proc.h)
+#include "kh_logprobs.h"
 
 // =============================================================================================
 // add / swiglu / scale : elementwise, HBM/L2-bound, float4 body + scalar tail
@@ -790,6 +791,17 @@ extern "C" int kh_logit_process_f32(float* logits, int64_t n, const int32_t* d_t
                               : KhProcParams{1.f, 0.f, 0.f, 0, n_bias};
   hipLaunchKernelGGL(k_logit_process, dim3(1), dim3(KH_PROC_THREADS), 0, (hipStream_t)stream, logits, (int)n,
                      d_tokens, d_pos, (int)pos, dp, d_bias_ids, d_bias, (int32_t*)workspace);
+  return kh_launch_status();
+}
+
+// =============================================================================================
+// log-probability of one token per row and the top-N alternatives (kh_logprobs.h): one workgroup per row
+extern "C" int kh_logprobs_f32(const float* logits, int64_t n, int32_t n_rows, const int32_t* d_ids, int32_t top_n,
+                               float* d_lse, float* d_lp, int32_t* d_top_ids, float* d_top_lp, void* stream) {
+  if (!logits || n <= 0 || n > 0x7fffffffLL || n_rows <= 0 || top_n < 0 || top_n > KH_LOGPROBS_MAX_TOP || top_n > n)
+    return KH_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(k_logprobs_op, dim3(n_rows), dim3(KH_SAMP_THREADS), 0, (hipStream_t)stream, logits, (int)n, d_ids,
+                     (int)top_n, d_lse, d_lp, d_top_ids, d_top_lp);
   return kh_launch_status();
 }
 

@@ -141,6 +141,30 @@ class KuiperModel:
         vals = (C.c_float * max(len(items), 1))(*[v for _, v in items])
         _ffi.check(_ffi.lib().kh_model_set_logit_bias(self._h, ids, vals, len(items)), "kh_model_set_logit_bias")
 
+    def set_logprobs(self, top_n: Optional[int] = None) -> None:
+        """Per-token log-probs of predict / generate (kh_model_set_logprobs): None turns them off (the default), 0
+        records the picked token's log-prob, 1 .. 20 also that many top alternatives.  No token changes."""
+        _ffi.check(_ffi.lib().kh_model_set_logprobs(self._h, -1 if top_n is None else int(top_n)),
+                   "kh_model_set_logprobs")
+
+    @property
+    def logprobs_setting(self) -> Optional[int]:
+        n = C.c_int32(-1)
+        _ffi.check(_ffi.lib().kh_model_get_logprobs_setting(self._h, C.byref(n)), "kh_model_get_logprobs_setting")
+        return None if n.value < 0 else int(n.value)
+
+    def logprobs(self, pos0: int, n: int) -> dict:
+        """Records of positions [pos0, pos0 + n) (kh_model_get_logprobs): {"token": [n], "logprob": [n], "top_ids":
+        [n, top_n], "top_logprobs": [n, top_n]} with top_n the current setting.  A position that was fed but not
+        sampled holds token -1, ids -1 and NaN."""
+        w = self.logprobs_setting or 0
+        out = {"token": np.empty(max(n, 0), np.int32), "logprob": np.empty(max(n, 0), np.float32),
+               "top_ids": np.empty((max(n, 0), w), np.int32), "top_logprobs": np.empty((max(n, 0), w), np.float32)}
+        _ffi.check(_ffi.lib().kh_model_get_logprobs(self._h, int(pos0), int(n), out["token"].ctypes.data,
+                                                    out["logprob"].ctypes.data, out["top_ids"].ctypes.data,
+                                                    out["top_logprobs"].ctypes.data), "kh_model_get_logprobs")
+        return out
+
     def logits(self) -> np.ndarray:
         out = np.empty(self.cfg.vocab_size, np.float32)
         _ffi.check(_ffi.lib().kh_model_get_logits(self._h, out.ctypes.data), "kh_model_get_logits")

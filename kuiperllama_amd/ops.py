@@ -208,6 +208,26 @@ def logit_process(logits, tokens, pos, penalties=None, bias_ids=None, bias=None,
     return logits
 
 
+def logprobs(logits, ids, top_n: int = 0) -> dict:
+    """Log-probability of ids[r] under the softmax of logits[r] and the top_n alternatives of every row
+    (kh_logprobs_f32).  logits: float32 GPU tensor [V] or [rows, V]; ids: int32 GPU tensor [rows] (an id outside [0, V)
+    reports NaN); 0 <= top_n <= 20.  Returns {"lse": [rows], "logprob": [rows], "top_ids": [rows, top_n],
+    "top_logprobs": [rows, top_n]} as GPU tensors, in the sampler's order (logit descending, index ascending)."""
+    rows = 1 if logits.dim() == 1 else logits.shape[0]
+    V = logits.shape[-1]
+    if ids.numel() != rows:
+        raise ValueError("one id per row of logits")
+    dev = logits.device
+    out = {"lse": torch.empty(rows, dtype=torch.float32, device=dev),
+           "logprob": torch.empty(rows, dtype=torch.float32, device=dev),
+           "top_ids": torch.empty((rows, max(int(top_n), 0)), dtype=torch.int32, device=dev),
+           "top_logprobs": torch.empty((rows, max(int(top_n), 0)), dtype=torch.float32, device=dev)}
+    _ffi.check(_ffi.lib().kh_logprobs_f32(_p(logits, torch.float32), V, rows, _p(ids, torch.int32), int(top_n),
+                                          _p(out["lse"]), _p(out["logprob"]), _p(out["top_ids"]),
+                                          _p(out["top_logprobs"]), _stream()), "kh_logprobs_f32")
+    return out
+
+
 def softmax_(x):
     _ffi.check(_ffi.lib().kh_softmax_f32(_p(x, torch.float32), x.numel(), _stream()),
                "kh_softmax_f32")

@@ -15,7 +15,7 @@
 //               [--exact-prefill] [--fenced-merge]
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
-//               [--logit-bias id=value]...
+//               [--logit-bias id=value]... [--logprobs N]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -25,6 +25,8 @@
 // --repeat-penalty / --presence-penalty / --frequency-penalty over the last --repeat-last-n fed tokens (0: all of
 // them; llama.cpp's flags of the same names) and --logit-bias id=value (repeatable; value -inf bans the token):
 // kh_model_set_penalties / kh_model_set_logit_bias, applied to the logits ahead of the greedy or sampled pick.
+// --logprobs N (0 .. 20): kh_model_set_logprobs; after the words and the timing, one line per generated token,
+// "pos token lp | id:lp ..." with the N most likely tokens of that position (no token changes).
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <chrono>
 #include <cstdio>
@@ -43,7 +45,7 @@ static void usage() {
                "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge]\n"
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
-               "       [--logit-bias id=value]...\n");
+               "       [--logit-bias id=value]... [--logprobs N]\n");
 }
 
 int main(int argc, char** argv) {
@@ -58,6 +60,7 @@ int main(int argc, char** argv) {
   std::vector<int32_t> bias_ids;       // --logit-bias id=value (kh_model_set_logit_bias)
   std::vector<float> bias_vals;
   int steps = 128, exec = KH_EXEC_GRAPH;
+  int logprobs = -1;  // --logprobs N (kh_model_set_logprobs)
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
   const char* tok_path = nullptr;
@@ -93,6 +96,7 @@ int main(int argc, char** argv) {
     else if (a == "--presence-penalty") pen.presence = (float)std::atof(next());
     else if (a == "--frequency-penalty") pen.frequency = (float)std::atof(next());
     else if (a == "--repeat-last-n") pen.last_n = std::atoi(next());
+    else if (a == "--logprobs") logprobs = std::atoi(next());
     else if (a == "--logit-bias") {
       const std::string e = next();
       const size_t eq = e.find('=');
@@ -213,6 +217,11 @@ int main(int argc, char** argv) {
   if (pen.repetition != 1.f || pen.presence != 0.f || pen.frequency != 0.f || !bias_ids.empty())
     std::fprintf(stderr, "logit processors: repeat %g, presence %g, frequency %g over the last %d tokens (0: all), %zu bias entries\n",
                  pen.repetition, pen.presence, pen.frequency, pen.last_n, bias_ids.size());
+  if (logprobs != -1 && (rc = kh_model_set_logprobs(m, logprobs)) != KH_OK) {
+    std::fprintf(stderr, "invalid --logprobs %d: %d (%s)\n", logprobs, rc, kh_error_string(rc));
+    kh_model_destroy(m);
+    return 1;
+  }
   std::vector<int32_t> words((size_t)steps);
   int32_t n = 0;
   float gpu_ms = 0.f;
@@ -226,6 +235,7 @@ int main(int argc, char** argv) {
     kh_model_destroy(m);
     return 1;
   }
+  const int n_gen = n;  // positions 0 .. n_gen - 1 produced words; those from prompt.size() - 1 on were sampled
   if (o.family == KH_FAMILY_QWEN2 && !prompt.empty()) {
     // demo/main_qwen.cpp:12,18 seeds `next` with the first prompt token and pushes it into `words`
     // before the loop (main.cpp starts from next = -1): the Qwen demo's output begins with it
@@ -251,6 +261,24 @@ int main(int argc, char** argv) {
   const int steps_done = n - (o.family == KH_FAMILY_QWEN2 && !prompt.empty() ? 1 : 0);
   std::printf("\nsteps/s:%lf\n", (double)steps_done / dur);
   if (o.family == KH_FAMILY_QWEN2) std::printf("\nsteps:%d\n\nduration:%lf\n", steps_done, dur);  // main_qwen.cpp:73-74
+  const int p0 = (int)prompt.size() - 1;
+  if (logprobs >= 0 && n_gen > p0) {
+    const int cnt = n_gen - p0;
+    std::vector<int32_t> tok_id((size_t)cnt), top_id((size_t)cnt * logprobs + 1);
+    std::vector<float> lp((size_t)cnt), top_lp((size_t)cnt * logprobs + 1);
+    rc = kh_model_get_logprobs(m, p0, cnt, tok_id.data(), lp.data(), top_id.data(), top_lp.data());
+    if (rc != KH_OK) {
+      std::fprintf(stderr, "kh_model_get_logprobs failed: %d (%s)\n", rc, kh_error_string(rc));
+      kh_model_destroy(m);
+      return 1;
+    }
+    for (int i = 0; i < cnt; ++i) {
+      std::printf("%d %d %.6f |", p0 + i, tok_id[i], lp[i]);
+      for (int k = 0; k < logprobs; ++k)
+        std::printf(" %d:%.6f", top_id[(size_t)i * logprobs + k], top_lp[(size_t)i * logprobs + k]);
+      std::printf("\n");
+    }
+  }
   std::fprintf(stderr, "(device time of the step loop: %.3f ms)\n", gpu_ms);
   kh_model_destroy(m);
   return 0;
