@@ -348,6 +348,25 @@ int kh_model_cls_screen_info(kh_model* m, int64_t* out8);
 int kh_model_cls_screen_probe(kh_model* m, const float* h_x, float* h_lb, float* h_ub, int64_t* out4);
 /* tests: the bf16 copy of the classifier [vocab x dim] and its per-row error table [vocab] */
 int kh_model_cls_screen_read(kh_model* m, uint16_t* h_wbf, float* h_err);
+/* The int8 tier ahead of the bf16 screen (csrc/kh_cls_screen.h): fp32 models with the bf16 screen on and dim a multiple
+ * of 64 also keep an int8 copy of the classifier with one fp32 scale per 64 weights (about 0.27 of the classifier's
+ * bytes).  Screened greedy steps then run three launches behind the layers (5 L + 3 in all): k_cls_screen_q8 thins the
+ * vocabulary to the few rows whose int8 interval reaches the best lower bound, k_cls_screen screens those from the
+ * bf16 copy, k_sample_screen re-scores.  Tokens and logits are unchanged.  The tier steps aside - the tail is the
+ * two-launch one - under hook KH_CLS_SCREEN_Q8=0 (at creation: no copy; later: for the generates that follow), under
+ * a KH_SHAPE_SCREEN or KH_SHAPE_CLS hook, and when its creation-time self-test fails (hook KH_SELFTEST_FAIL=screen8
+ * injects that).  Hook KH_SHAPE_SCREEN_Q8="u,grid,wg" shapes its launch.
+ * out8 = on, self-test (0 / 1 / -1), HBM bytes of the copy with its scales and row table, microseconds its conversion
+ * took, tier-1 steps so far, rows that survived tier 1 in them, steps in which tier 1 spilled (a workgroup dropped a
+ * row that could still win: the bf16 launch then scans every row), rows a tier-1 workgroup hands over */
+int kh_model_cls_screen_q8_info(kh_model* m, int64_t* out8);
+/* tests: one three-launch tail, tier 1 on `grid` workgroups (0: as planned), and one full step on h_x[dim], without
+ * advancing.  h_lb8 / h_ub8 [vocab]: tier 1's interval of every row.  out6 = the tail's token, the full classifier's
+ * token, rows that survived tier 1, 1 if tier 1 spilled, candidate rows re-scored, 1 if the step overflowed.  Counters
+ * and clobbered state as kh_model_cls_screen_probe.  KH_ERR_UNSUPPORTED where the tier is off. */
+int kh_model_cls_screen_q8_probe(kh_model* m, const float* h_x, int32_t grid, float* h_lb8, float* h_ub8, int64_t* out6);
+/* tests: the int8 copy [vocab x dim], its scales [vocab x dim / 64] and its per-row error table [vocab] */
+int kh_model_cls_screen_q8_read(kh_model* m, int8_t* h_q, float* h_sc, float* h_e8);
 /* device pointers of the KV cache [layer, cache_len, kv_dim] (tests) */
 int kh_model_get_kv(kh_model* m, float** d_kcache, float** d_vcache);
 /* bytes of the KV cache: *reserved = the address range of [layer, cache_len, kv_dim] floats x 2 (the reference's

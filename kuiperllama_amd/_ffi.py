@@ -21,7 +21,7 @@ EXPORTS = [
     "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
-    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
+    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
     "kh_spm_create_from_file", "kh_spm_create_from_memory", "kh_spm_destroy", "kh_spm_vocab_size",
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
@@ -162,6 +162,9 @@ def lib() -> C.CDLL:
     L.kh_model_cls_screen_info.argtypes = [_vp, C.POINTER(_i64)]
     L.kh_model_cls_screen_probe.argtypes = [_vp, _vp, _vp, _vp, C.POINTER(_i64)]
     L.kh_model_cls_screen_read.argtypes = [_vp, _vp, _vp]
+    L.kh_model_cls_screen_q8_info.argtypes = [_vp, C.POINTER(_i64)]
+    L.kh_model_cls_screen_q8_probe.argtypes = [_vp, _vp, _i32, _vp, _vp, C.POINTER(_i64)]
+    L.kh_model_cls_screen_q8_read.argtypes = [_vp, _vp, _vp, _vp]
     L.kh_model_get_kv.argtypes = [_vp, C.POINTER(_vp), C.POINTER(_vp)]
     L.kh_model_kv_bytes.argtypes = [_vp, C.POINTER(_i64), C.POINTER(_i64)]
     L.kh_model_read_kv.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp]

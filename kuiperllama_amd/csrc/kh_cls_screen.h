@@ -39,6 +39,45 @@
 // the full fp32 classifier and the last one to arrive merges - the arithmetic of k_cls + k_sample, inside the same
 // launch, no host decision.
 //
+// The int8 tier ahead of the bf16 screen.  The bf16 pass is at the stream ceiling, so only fewer bytes make the tail
+// shorter: an int8 copy with one fp32 scale per KH_SCR8_G = 64 weights is 0.53 of the bf16 copy's bytes.  Its interval
+// is 3-4 times wider, too wide to feed k_sample_screen's KH_SCR_CAND rows directly, so it only thins the vocabulary:
+//
+//   k_cls_q8_build     (model creation) per group G: sc_G = max |w_i| / 127, q_i = rint(w_i / sc_G) clamped to +-127
+//                      (an all-zero group, or one with a NaN / Inf weight: sc_G = 0, q = 0), and per row
+//                      e8[r] >= |w_r - sc o q_r|_2 + 2 gamma_n (|w_r|_2 + |sc o q_r|_2)               (fp64, rounded up)
+//                      with e8[r] = +inf for a row that holds a NaN or an Inf
+//   k_cls_screen_q8    (first launch of the tail) streams q and sc against g staged in the int8 kernels' four-plane
+//                      layout and leaves, per workgroup, the best lower bound, its KH_SCR8_C best rows by upper bound
+//                      and the largest upper bound it dropped.  No logits, no x_save.
+//   k_cls_screen       (survivor mode: KhClsScreenArgs::q_lb set) reads those partials: L8 = max lower bound, S8 = max
+//                      dropped bound.  S8 >= L8: tier 1 spilled, every workgroup runs the full bf16 scan as if there
+//                      were no tier 1.  Otherwise workgroup b re-screens the slots b, b + grid, ... of tier 1's partials
+//                      whose upper bound reaches L8 (neighbouring slots - the rows of one tier-1 workgroup - go to
+//                      different workgroups: each hands on KH_SCR_C rows, a tier-1 workgroup twice as many) - one wave
+//                      per row, the row's chunks in gemv_pairs' order, so the interval is the full scan's bit for bit -
+//                      and hands over the usual partials.
+//
+// Its interval.  A = sum_G sc_G sum_{i in G} q_i g_i in exact reals; A32 what the kernel accumulates: a lane owns 16
+// consecutive weights of one group per load, t = a chain of 16 FMAs q_i g_i from 0 (q_i exact in fp32), then
+// a = fma(sc_G, t, a) along the lane's ceil(dim / 1024) loads, then the six butterfly additions.
+//   |S - A|     <= |w - sc o q|_2 |g|_2                                          (Cauchy-Schwarz, exact reals)
+//   |A32 - A|   <= gamma_n8 sum |sc q_i g_i| <= gamma_n8 |sc o q|_2 |g|_2 ,  n8 = 16 + 1 + ceil(dim / 1024) + 6
+//   |S32 - S|   <= gamma_n' |w|_2 |g|_2 ,                                     n' = ceil(dim / 64) + 8  (k_cls, above)
+// e8[r] carries 2 gamma_n for both with the one n = ceil(dim / 64) + 24 >= max(n8, n') (at dim 2048 the rounding
+// part is 2e-3 of e8; the quantisation part is everything).  So |rs S32 - rs A32| <= rs |g|_2 e8[r], and with
+// a8 = fl(rs A32) the terms relative to the values are the bf16 interval's, covered by the same slack:
+//   b8 = fl(rs |g|_2 (1 + 2^-17)) e8[r] + |a8| 2^-18 + 1e-30 ,     l in [a8 - b8, a8 + b8].
+// (rs and |g|_2 are formed as in the bf16 kernel, thread for thread; a launch of another workgroup width sums them in
+// another order: a few u, inside the 128 u of the main term.)  A row whose a8 or b8 is not finite gets (-inf, +inf).
+// Exactness.  L8 = max (a8 - b8) is a lower bound of the largest logit: a row with a8 + b8 < L8 is neither the argmax
+// nor tied with it.  The bf16 screen of the remaining rows is the screen above on a smaller vocabulary that still
+// holds every row that can win: its L is a lower bound of the largest logit, its candidates hold the argmax.
+// Which workgroup re-screens which slot is a function of the slot's position alone: no scheduling order enters.
+// The survivor pass could raise its lower bounds to L8 and does not: the row that sets L8 is a survivor itself, and
+// its bf16 half-width is about a quarter of its int8 one, so L would hardly ever move; k_sample_screen sees the
+// partials it always saw.
+//
 // Replaces nothing in the reference (it streams the fp32 classifier and runs an argmax kernel,
 // kuiper/source/model/llama3.cpp:722-745).
 #pragma once
@@ -47,6 +86,10 @@
 #define KH_SCR_C 4      // rows a workgroup of k_cls_screen hands over
 #define KH_SCR_CAND 32  // rows k_sample_screen re-scores before the step counts as an overflow
 #define KH_SCR_MERGE_WORDS (2 + 2 * KH_SCR_C)
+#define KH_SCR8_C 8     // rows a workgroup of k_cls_screen_q8 hands over
+#define KH_SCR8_G 64    // weights per scale of the int8 copy
+#define KH_SCR8_GSHIFT 6
+#define KH_SCR8_MERGE_WORDS (2 + 2 * KH_SCR8_C)
 
 // LDS layout of the staged vector for the bf16 rows: a lane owns 8 consecutive weights (one dwordx4), i.e. the
 // float4 f = 2j and 2j + 1 of its 8-chunk j.  Two planes, slot(f) = (f & 1) * (M8 + 1) + (f >> 1): for either half
@@ -171,23 +214,24 @@ static __global__ __launch_bounds__(KH_WG) void k_cls_bf16_build(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// keep the KH_SCR_C largest upper bounds (descending) and the largest one that fell out
-struct ScrTop {
+// keep the C largest upper bounds (descending) and the largest one that fell out
+template <int C>
+struct ScrTopN {
   float lb, spill;
-  float u[KH_SCR_C];
-  int i[KH_SCR_C];
+  float u[C];
+  int i[C];
   __device__ __forceinline__ void init() {
     lb = -INFINITY;
     spill = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < KH_SCR_C; ++k) {
+    for (int k = 0; k < C; ++k) {
       u[k] = -INFINITY;
       i[k] = -1;
     }
   }
   __device__ __forceinline__ void insert(float ub, int idx) {
 #pragma unroll
-    for (int k = 0; k < KH_SCR_C; ++k) {
+    for (int k = 0; k < C; ++k) {
       const bool sw = ub > u[k];
       const float tu = sw ? u[k] : ub;
       const int ti = sw ? i[k] : idx;
@@ -198,7 +242,59 @@ struct ScrTop {
     }
     spill = fmaxf(spill, idx >= 0 ? ub : -INFINITY);  // an empty slot that fell out is not a row
   }
+  // insert() for a bound every lane of the wave holds alike: one that does not beat the last kept bound falls straight
+  // out (what the walk above comes to for it), decided by a scalar branch - most rows of a vocabulary take it
+  __device__ __forceinline__ void offer(float ub, int idx) {
+    if (__builtin_amdgcn_readfirstlane((int)(ub > u[C - 1])))
+      insert(ub, idx);
+    else
+      spill = fmaxf(spill, idx >= 0 ? ub : -INFINITY);
+  }
 };
+using ScrTop = ScrTopN<KH_SCR_C>;
+
+// The end of both screening kernels: the waves' lists merged by thread 0 (mg: nwaves x (2 + 2 C) words of LDS), one
+// partial per workgroup.
+template <int C>
+__device__ __forceinline__ void scr_handover(ScrTopN<C>& top, float* mg, int lane, int wave, float* p_lb, float* p_spill,
+                                             float* p_ub, int32_t* p_idx) {
+  constexpr int W = 2 + 2 * C;
+  if (lane == 0) {
+    float* q = mg + wave * W;
+    q[0] = top.lb;
+    q[1] = top.spill;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+      q[2 + k] = top.u[k];
+      q[2 + C + k] = __builtin_bit_cast(float, top.i[k]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1, nw = kh_nwaves(); w < nw; ++w) {
+      const float* q = mg + w * W;
+      top.lb = fmaxf(top.lb, q[0]);
+      top.spill = fmaxf(top.spill, q[1]);
+      // a wave's list is in descending order: behind the first bound that falls out, all of them do
+      for (int k = 0; k < C; ++k) {
+        const float ub = q[2 + k];
+        const int idx = __builtin_bit_cast(int, q[2 + C + k]);
+        if (!(ub > top.u[C - 1])) {
+          top.spill = fmaxf(top.spill, idx >= 0 ? ub : -INFINITY);
+          break;
+        }
+        top.insert(ub, idx);
+      }
+    }
+    p_lb[blockIdx.x] = top.lb;
+    p_spill[blockIdx.x] = top.spill;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+      p_ub[blockIdx.x * C + k] = top.u[k];
+      p_idx[blockIdx.x * C + k] = top.i[k];
+    }
+  }
+}
 
 struct KhClsScreenArgs {
   const float* x;
@@ -214,6 +310,13 @@ struct KhClsScreenArgs {
   float* dbg_ub;
   int dim, vocab;
   float eps;
+  // survivor mode (q_lb set): the partials of the k_cls_screen_q8 launch in front of this one, nq workgroups of it
+  const float* q_lb;
+  const float* q_spill;
+  const float* q_ub;     // [nq, KH_SCR8_C]
+  const int32_t* q_idx;  // [nq, KH_SCR8_C], -1 = empty
+  int32_t* q_stats;      // [0] tier-1 steps, [1] rows that survived tier 1, [2] steps in which tier 1 spilled
+  int nq;
 };
 template <int U, int MAXV>
 __global__ __launch_bounds__(KH_WG_MAX, 4) void k_cls_screen(const KhClsScreenArgs a) {
@@ -289,36 +392,244 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_cls_screen(const KhClsScreenAr
     for (int w = 0; w < KH_WAVES_MAX; ++w) r += w < n ? red[KH_WAVES_MAX + (w < n ? w : 0)] : 0.f;
     cb = rs * sqrtf(r) * (1.f + 0x1p-17f);
   };
+  // survivor mode: what tier 1 left.  Every workgroup comes to the same decision from the same words.
+  bool survivors = false;
+  float L8 = -INFINITY;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  // Slots of this workgroup: j = b, b + grid, ... of tier 1's nq x KH_SCR8_C slots, so the rows one tier-1 workgroup
+  // hands over go to as many workgroups here (each hands on KH_SCR_C rows only); wave w takes its slots w, w + nwaves, ...
+  const int mine = a.q_lb ? (a.nq * KH_SCR8_C - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+  auto slot_of = [&](int s) __attribute__((always_inline)) { return (int)blockIdx.x + s * (int)gridDim.x; };
+  int r_first = -1;
+  float ub_first = -INFINITY;
+  if (a.q_lb) {
+    // what does not depend on L8 leaves first: the vector and the wave's first slot.  (A spilled step requests the
+    // vector once more through gemv_pairs below: its ISSUE stays unconditional, the issue order of the full scan is
+    // the one every other step of the kernel has; a spill is rare and the words come from L2.)
+    st.issue();
+    if (wv < mine) {
+      r_first = a.q_idx[slot_of(wv)];
+      ub_first = a.q_ub[slot_of(wv)];
+    }
+    float l = -INFINITY, sp = -INFINITY;
+    for (int i = threadIdx.x; i < a.nq; i += kh_wg()) {
+      l = fmaxf(l, a.q_lb[i]);
+      sp = fmaxf(sp, a.q_spill[i]);
+    }
+    l = wave_max(l);
+    sp = wave_max(sp);
+    if (lane == 0) {
+      red[wave] = l;
+      red[KH_WAVES_MAX + wave] = sp;
+    }
+    __syncthreads();
+    float S8 = -INFINITY;
+    const int n = kh_nwaves();
+#pragma unroll
+    for (int w = 0; w < KH_WAVES_MAX; ++w) {
+      L8 = fmaxf(L8, red[w < n ? w : 0]);
+      S8 = fmaxf(S8, red[KH_WAVES_MAX + (w < n ? w : 0)]);
+    }
+    __syncthreads();  // red is the staging's from here on
+    survivors = !(S8 >= L8);  // a dropped bound that reaches L8 (or no finite bound at all): the full scan below
+    if (blockIdx.x == 0 && threadIdx.x == 0) {  // the tier's counters
+      atomicAdd(a.q_stats + 0, 1);
+      if (!survivors) atomicAdd(a.q_stats + 2, 1);
+    }
+  }
+  if (survivors) {
+    // One wave per surviving row, the chunks of the row in gemv_pairs' order (SPLIT 1: c0 = 0, step, ...; a row's sum
+    // does not depend on the row it is paired with), the same staging, reduction and interval as the full scan.  The
+    // first row's first tile is requested ahead of the staging barrier (row 0 where the wave has nothing to take).
+    typename GemvBf16<U>::Regs regs;
+    const int step = KH_WAVE * U;
+    int r = __builtin_amdgcn_readfirstlane(r_first);
+    bool take = r >= 0 && __builtin_amdgcn_readfirstlane((int)(ub_first >= L8));
+    r = take ? r : 0;
+    RowsBf16 rw = g.rows(wbf, r, r, dim);
+    g.load(regs, rw, 0, g.Mc, lane);
+    float e_r = err[r];
+    finish();
+    for (int s = wv; s < mine; s += kh_nwaves()) {
+      if (s != wv) {
+        r = __builtin_amdgcn_readfirstlane(a.q_idx[slot_of(s)]);
+        take = r >= 0 && __builtin_amdgcn_readfirstlane((int)(a.q_ub[slot_of(s)] >= L8));
+        if (take) {
+          rw = g.rows(wbf, r, r, dim);
+          g.load(regs, rw, 0, g.Mc, lane);
+          e_r = err[r];
+        }
+      }
+      if (!take) continue;
+      float a0 = 0.f, a1 = 0.f;
+      for (int c0 = 0;;) {
+        g.fma(regs, xs, c0, g.Mc, lane, a0, a1);
+        c0 += step;
+        if (c0 >= g.Mc) break;
+        g.load(regs, rw, c0, g.Mc, lane);
+      }
+      track(wave_sum(a0), e_r, r);
+    }
+    if (blockIdx.x == 0) {  // rows that survived tier 1, over all of its workgroups
+      int n = 0;
+      for (int i = threadIdx.x; i < a.nq * KH_SCR8_C; i += kh_wg()) n += a.q_idx[i] >= 0 && a.q_ub[i] >= L8 ? 1 : 0;
+      if (n) atomicAdd(a.q_stats + 1, n);
+    }
+  } else {
+    gemv_pairs<1, /*ROLL=*/false>(g, xs, (vocab + 1) >> 1, lane, nullptr, pair, pre,
+                                  [&]() __attribute__((always_inline)) { st.issue(); }, finish, epi);
+  }
+  // one partial per workgroup
+  scr_handover(top, mg, lane, wave, a.p_lb, a.p_spill, a.p_ub, a.p_idx);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Model creation: the int8 copy (see the head of this file).  One wave per row, a lane converts 4 consecutive weights
+// (16 lanes = one group of 64, four groups per pass), fp64 accumulation.  dim is a multiple of 64.
+static __global__ __launch_bounds__(KH_WG) void k_cls_q8_build(const float* __restrict__ w, uint32_t* __restrict__ q,
+                                                               float* __restrict__ sc, float* __restrict__ err, int dim,
+                                                               int vocab, double gam2) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int gpr = dim >> KH_SCR8_GSHIFT;
+  for (int row = blockIdx.x * KH_WAVES_PER_WG + wave; row < vocab; row += gridDim.x * KH_WAVES_PER_WG) {
+    const f32x4* src = (const f32x4*)(w + (size_t)row * dim);
+    uint32_t* dst = q + (size_t)row * (dim >> 2);
+    double d2 = 0.0, w2 = 0.0, q2 = 0.0;
+    for (int base = 0; base < dim; base += 4 * KH_WAVE) {
+      const int i4 = (base >> 2) + lane;  // float4 index in the row; a group's 16 lanes are inside the row together
+      const bool in = i4 < (dim >> 2);
+      const f32x4 v = src[in ? i4 : 0];
+      const float wv[4] = {v.x, v.y, v.z, v.w};
+      float am = fmaxf(fmaxf(fabsf(wv[0]), fabsf(wv[1])), fmaxf(fabsf(wv[2]), fabsf(wv[3])));
+      bool bad = !(fabsf(wv[0]) < INFINITY && fabsf(wv[1]) < INFINITY && fabsf(wv[2]) < INFINITY && fabsf(wv[3]) < INFINITY);
+      am = group_max<16>(am);  // fmaxf drops a NaN: `bad` carries it
+      bad = group_max<16>(bad ? 1.f : 0.f) != 0.f;
+      const float s = bad ? 0.f : am / 127.f;
+      uint32_t packed = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float t = s > 0.f ? rintf(wv[k] / s) : 0.f;
+        t = fminf(fmaxf(t, -127.f), 127.f);
+        if (!(t == t)) t = 0.f;
+        const int qi = (int)t;
+        packed |= (uint32_t)(qi & 0xff) << (8 * k);
+        const double dq = (double)s * (double)qi, e = (double)wv[k] - dq;  // fp32 x 8-bit integer: exact in fp64
+        if (in) {
+          d2 += e * e;
+          w2 += (double)wv[k] * (double)wv[k];
+          q2 += dq * dq;
+        }
+      }
+      if (in) {
+        dst[i4] = packed;
+        if ((lane & 15) == 0) sc[(size_t)row * gpr + (i4 >> 4)] = s;
+      }
+    }
+    d2 = wave_sum_f64(d2);
+    w2 = wave_sum_f64(w2);
+    q2 = wave_sum_f64(q2);
+    if (lane == 0) {
+      const double e = (sqrt(d2) + gam2 * (sqrt(w2) + sqrt(q2))) * (1.0 + 1e-9);
+      float f = (float)e;
+      if ((double)f < e) f = nextafterf(f, INFINITY);
+      if (!(e < (double)INFINITY)) f = INFINITY;  // NaN / Inf weights: the row always survives
+      err[row] = f;
+    }
+  }
+}
+
+// xs (four planes) | ss[KH_WAVES_MAX] | gg[KH_WAVES_MAX] | per-wave partials
+static inline size_t cls_screen_q8_lds_bytes(int M) {
+  return kh_q8_lds_bytes(M) + (size_t)(2 * KH_WAVES_MAX + KH_WAVES_MAX * KH_SCR8_MERGE_WORDS) * sizeof(float);
+}
+struct KhClsScreenQ8Args {
+  const float* x;
+  const float* final_norm;
+  const int8_t* q;   // [vocab, dim]
+  const float* sc;   // [vocab, dim / KH_SCR8_G]
+  const float* e8;   // [vocab]
+  float* p_lb;       // [grid]
+  float* p_spill;    // [grid]
+  float* p_ub;       // [grid, KH_SCR8_C]
+  int32_t* p_idx;    // [grid, KH_SCR8_C], -1 = empty
+  float* dbg_lb;     // [vocab] or nullptr: every row's interval (self-test, probe)
+  float* dbg_ub;
+  int dim, vocab;
+  float eps;
+};
+// Tier 1: k_cls_screen over the int8 copy - Gemv<true, U> with one scale per 64 weights as the matrix view, the
+// vector staged in its four-plane layout.  Writes neither logits nor x_save.
+template <int U, int MAXV>
+__global__ __launch_bounds__(KH_WG_MAX, 4) void k_cls_screen_q8(const KhClsScreenQ8Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  f32x4* xs = (f32x4*)smem_raw;
+  const int dim = a.dim, vocab = a.vocab, M16 = dim >> 4;
+  float* red = (float*)(xs + 4 * (M16 + 1));
+  float* mg = red + 2 * KH_WAVES_MAX;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* const e8 = a.e8;
+  float* const dbg_lb = a.dbg_lb;
+  float* const dbg_ub = a.dbg_ub;
+  const float eps = a.eps;
+  const Gemv<true, U> g(dim, KH_SCR8_GSHIFT);
+  Stager<true, true, MAXV> st(a.x, a.final_norm, dim);
+  ScrTopN<KH_SCR8_C> top;
+  top.init();
+  auto r1_of = [&](int p) __attribute__((always_inline)) { return 2 * p + 1 < vocab ? 2 * p + 1 : 2 * p; };
+  auto pair = [&](int p) __attribute__((always_inline)) { return g.rows(a.q, 2 * p, a.q, r1_of(p), a.sc, a.sc, dim); };
+  struct Aux {
+    float e0, e1;
+  };
+  auto pre = [&](int p) __attribute__((always_inline)) { return Aux{e8[2 * p], e8[r1_of(p)]}; };
+  float rs = 1.f, cb = 0.f;  // RMS scale; rs |g|_2 (1 + 2^-17)
+  auto track = [&](float s, float e, int r) __attribute__((always_inline)) {
+    const float av = s * rs;
+    const float b = __builtin_fmaf(cb, e, fabsf(av) * 0x1p-18f) + 1e-30f;
+    const bool ok = fabsf(av) < INFINITY && b < INFINITY;  // false for NaN as well
+    const float lb = ok ? av - b : -INFINITY, ub = ok ? av + b : INFINITY;
+    top.lb = fmaxf(top.lb, lb);
+    top.offer(ub, r);
+    if (dbg_lb && lane == 0) {
+      dbg_lb[r] = lb;
+      dbg_ub[r] = ub;
+    }
+  };
+  auto epi = [&](int p, float s0, float s1, const Aux& x) __attribute__((always_inline)) {
+    const int r0 = 2 * p, r1 = r1_of(p);
+    track(s0, x.e0, r0);
+    if (r1 != r0) track(s1, x.e1, r1);
+  };
+  auto finish = [&]() __attribute__((always_inline)) {
+    // k_cls_screen's staging with the four-plane layout; x_save is the bf16 kernel's to write
+    const int M4 = dim >> 2;
+    float ss = 0.f, gg = 0.f;
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) {
+      const int i = threadIdx.x + v * kh_wg();
+      const bool in = i < M4;
+      const float t = fma4(st.xv[v], st.xv[v], 0.f);
+      ss += in ? t : 0.f;
+      f32x4 gv = st.xv[v];
+      gv.x = st.wv[v].x * gv.x;
+      gv.y = st.wv[v].y * gv.y;
+      gv.z = st.wv[v].z * gv.z;
+      gv.w = st.wv[v].w * gv.w;
+      const float t2 = fma4(gv, gv, 0.f);
+      gg += in ? t2 : 0.f;
+      if (in) xs[q8_slot(i, M16)] = gv;
+    }
+    gg = wave_sum(gg);
+    if (lane == 0) red[KH_WAVES_MAX + wave] = gg;
+    rs = stage_rs(ss, dim, eps, red);  // its barrier publishes xs and both sets of wave sums
+    const int n = kh_nwaves();
+    float r = 0.f;
+#pragma unroll
+    for (int w = 0; w < KH_WAVES_MAX; ++w) r += w < n ? red[KH_WAVES_MAX + (w < n ? w : 0)] : 0.f;
+    cb = rs * sqrtf(r) * (1.f + 0x1p-17f);
+  };
   gemv_pairs<1, /*ROLL=*/false>(g, xs, (vocab + 1) >> 1, lane, nullptr, pair, pre,
                                 [&]() __attribute__((always_inline)) { st.issue(); }, finish, epi);
-  // one partial per workgroup
-  if (lane == 0) {
-    float* q = mg + wave * KH_SCR_MERGE_WORDS;
-    q[0] = top.lb;
-    q[1] = top.spill;
-#pragma unroll
-    for (int k = 0; k < KH_SCR_C; ++k) {
-      q[2 + k] = top.u[k];
-      q[2 + KH_SCR_C + k] = __builtin_bit_cast(float, top.i[k]);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1, nw = kh_nwaves(); w < nw; ++w) {
-      const float* q = mg + w * KH_SCR_MERGE_WORDS;
-      top.lb = fmaxf(top.lb, q[0]);
-      top.spill = fmaxf(top.spill, q[1]);
-#pragma unroll
-      for (int k = 0; k < KH_SCR_C; ++k) top.insert(q[2 + k], __builtin_bit_cast(int, q[2 + KH_SCR_C + k]));
-    }
-    a.p_lb[blockIdx.x] = top.lb;
-    a.p_spill[blockIdx.x] = top.spill;
-#pragma unroll
-    for (int k = 0; k < KH_SCR_C; ++k) {
-      a.p_ub[blockIdx.x * KH_SCR_C + k] = top.u[k];
-      a.p_idx[blockIdx.x * KH_SCR_C + k] = top.i[k];
-    }
-  }
+  scr_handover(top, mg, lane, wave, a.p_lb, a.p_spill, a.p_ub, a.p_idx);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -150,7 +150,7 @@ struct kh_model {
     hipGraphExec_t e = nullptr;
   };
   // [StepTail][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps per tail of the step
-  StepGraph sg[5][KH_STEP_VARIANTS][4];
+  StepGraph sg[6][KH_STEP_VARIANTS][4];
   // kh_model_set_sampling: the parameters (host copy), whether they sample (temperature > 0), and their device copy,
   // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
   kh_sampling samp{0.f, 0, 1.f, 0};
@@ -201,6 +201,21 @@ struct kh_model {
     size_t bytes = 0;          // HBM the copy and its tables take
     float build_ms = 0.f;      // time of the conversion kernel
     bool stale = false;        // the logits buffer is older than the last step: refresh from x_save on demand
+    // the int8 tier ahead of the bf16 screen (k_cls_q8_build, k_cls_screen_q8, k_cls_screen's survivor mode)
+    struct Q8 {
+      bool on = false;         // the int8 copy exists and its creation-time check passed (or was skipped)
+      int selftest = 0;        // 0 not applicable / skipped, 1 passed, -1 failed -> tier off, the bf16 screen goes on
+      int8_t* q = nullptr;     // [vocab, dim]
+      float* sc = nullptr;     // [vocab, dim / 64]
+      float* e8 = nullptr;     // [vocab]
+      float *p_lb = nullptr, *p_spill = nullptr, *p_ub = nullptr;  // partials of k_cls_screen_q8
+      int32_t* p_idx = nullptr;
+      int32_t* stats = nullptr;  // tier-1 steps, rows that survived it, steps in which it spilled
+      int u = 2, grid = 1, wg = KH_WG;  // launch of k_cls_screen_q8
+      size_t bytes = 0;
+      float build_ms = 0.f;
+    };
+    Q8 q8;
   };
   ClsScreen scr;
 };
@@ -247,15 +262,19 @@ static inline void logits_fresh(kh_model* m) { m->scr.stale = false; }
 // The last two launches of a fused step, and the index of kh_model::sg its graphs live in: k_cls + k_sample (argmax),
 // k_cls + k_sample_topp, the screened pair k_cls_screen + k_sample_screen (greedy steps of a generate, see scr), or
 // k_cls + k_sample_proc (penalties or a logit bias set: processing, then the greedy or sampled pick), or k_cls +
-// k_sample_lp (log-probs on: k_sample_proc's duties, then the record of the position)
-enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2, kProcess = 3, kLogprob = 4 };
+// k_sample_lp (log-probs on: k_sample_proc's duties, then the record of the position).  kScreenQ8: the screened pair
+// behind its int8 tier, k_cls_screen_q8 + k_cls_screen (survivor mode) + k_sample_screen: 5L + 3 launches
+enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2, kProcess = 3, kLogprob = 4, kScreenQ8 = 5 };
+static inline bool tail_screens(StepTail t) { return t == kScreen || t == kScreenQ8; }
 // log-probs, processing and sampling need every logit: they are stronger than a caller's wish to screen, and log-probs
 // are stronger than the rest.  process = false: a step whose pick is discarded (kh_model_predict at a prompt position)
 // leaves its logits as the classifier wrote them and writes no record
-static inline StepTail step_tail(const kh_model* m, bool screen, bool process = true) {
+// screen: 0 no, 1 the bf16 screen, 2 the bf16 screen behind its int8 tier (cls_screen_level)
+static inline StepTail step_tail(const kh_model* m, int screen, bool process = true) {
   return m->lp_top_n >= 0 && process ? kLogprob
          : m->proc_on && process     ? kProcess
          : m->samp_on                ? kSample
+         : screen == 2               ? kScreenQ8
          : screen                    ? kScreen
                                      : kGreedy;
 }
@@ -299,8 +318,12 @@ int enqueue_steps(kh_model* m, int pos, int nsteps, int n_forced, StepTail tail,
 int cls_screen_create(kh_model* m);   // bf16 copy + tables, once the weights are resident (no-op where it does not apply)
 void cls_screen_release(kh_model* m);
 bool cls_screen_wanted(const kh_model* m);  // may this generate screen? (sampler, hooks)
-// dbg_lb / dbg_ub [vocab] (optional): receive every row's interval
-void launch_cls_screen(kh_model* m, float* dbg_lb = nullptr, float* dbg_ub = nullptr);
+int cls_screen_level(const kh_model* m);    // 0 no screen, 1 the bf16 screen, 2 behind the int8 tier (hooks)
+// dbg_lb / dbg_ub [vocab] (optional): receive every row's interval.  survivors: re-screen what the k_cls_screen_q8
+// launch in front of this one left (kh_cls_screen.h) instead of scanning every row
+void launch_cls_screen(kh_model* m, float* dbg_lb = nullptr, float* dbg_ub = nullptr, bool survivors = false);
+void launch_cls_screen_q8(kh_model* m, float* dbg_lb = nullptr, float* dbg_ub = nullptr, int grid = 0);
+int cls_screen_q8_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result);
 void launch_sample_screen(kh_model* m, int advance, int n_forced);
 int cls_refresh_logits(kh_model* m);  // k_cls on the saved input if the logits buffer is stale
 int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result);

@@ -54,6 +54,44 @@ void plan_screen(kh_model* m) {
     }
   }
 }
+
+// Launch of k_cls_screen_q8: Gemv<true, U>, a lane covers 16 weights per load (dim 2048 is 2 loads).  256-thread
+// workgroups, three per CU: 12 waves per CU, all resident at once (the kernel's 85 registers would allow 20; more
+// workgroups measured slower), an int8 row pair is 4 KB and a wave streams about twenty of them behind one
+// staging of the vector.  The sweep of this shape on Llama-3.2-1B is the last section of
+// profiles/cls_screen_q8_ab.txt (tools/cls_screen_q8_ab.py --sweep): step loop per token against the two-launch
+// tail.  512-thread workgroups where the vector is too long to stage from 256.  Hook
+// KH_SHAPE_SCREEN_Q8="u,grid,wg" overrides (tests reach every instantiation and the one-workgroup spill this way).
+using ScreenQ8U = KhVals<4, 2>;
+void plan_screen_q8(kh_model* m) {
+  const kh_config& c = m->cfg;
+  kh_model::ClsScreen::Q8& t = m->scr.q8;
+  const int per_lane = (c.dim / 16 + KH_WAVE - 1) / KH_WAVE;
+  t.u = per_lane >= 3 ? 4 : 2;
+  t.wg = ScreenMV::has(kh_stage_maxv(c.dim, KH_WG)) ? KH_WG : KH_WG_MAX;
+  const int pairs = (c.vocab_size + 1) / 2, wpw = t.wg / KH_WAVE;
+  const int need = (pairs + wpw - 1) / wpw;
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->opts.device) != hipSuccess || cus <= 0)
+    cus = 256;
+  t.grid = 3 * cus * KH_WG / t.wg;
+  if (t.grid > 4096) t.grid = 4096;
+  if (t.grid > need) t.grid = need;
+  if (const char* ov = dbg("KH_SHAPE_SCREEN_Q8")) {
+    int u = 0, g = 0, w = 0;
+    if (sscanf(ov, "%d,%d,%d", &u, &g, &w) == 3 && ScreenQ8U::has(u) && g >= 1 && g <= 4096 &&
+        (w == 256 || w == 512) && ScreenMV::has(kh_stage_maxv(c.dim, w))) {
+      t.u = u;
+      t.grid = g;
+      t.wg = w;
+    } else {
+      fprintf(stderr, "[kh] KH_SHAPE_SCREEN_Q8=\"%s\" rejected (u 2/4, grid 1..4096, wg 256/512): planned shape\n", ov);
+    }
+  }
+}
+// The tier steps aside - the tail is the two-launch one - where a hook asks for a specific k_cls_screen or k_cls
+// launch, and under KH_CLS_SCREEN_Q8=0.
+bool q8_hooks_bar() { return dbg_off("KH_CLS_SCREEN_Q8") || dbg("KH_SHAPE_SCREEN") || dbg("KH_SHAPE_CLS"); }
 }  // namespace
 
 namespace {
@@ -72,8 +110,73 @@ bool cls_screen_wanted(const kh_model* m) {
   return m->scr.on && !m->samp_on && !dbg_off("KH_CLS_SCREEN") && !cls_hook_bars_screen();
 }
 
+int cls_screen_level(const kh_model* m) {
+  if (!cls_screen_wanted(m)) return 0;
+  return m->scr.q8.on && !q8_hooks_bar() ? 2 : 1;
+}
+
+static void cls_screen_q8_release(kh_model* m) {
+  kh_model::ClsScreen::Q8& t = m->scr.q8;
+  for (void* q : {(void*)t.q, (void*)t.sc, (void*)t.e8, (void*)t.p_lb, (void*)t.p_spill, (void*)t.p_ub, (void*)t.p_idx,
+                  (void*)t.stats})
+    if (q) (void)hipFree(q);
+  t = kh_model::ClsScreen::Q8();
+}
+
+// The int8 copy behind a bf16 screen that is on: fp32 model, dim a multiple of the group, no hook in the way.  Where
+// the copy cannot be had - no room for it - the tier is off and nothing else changes: KH_OK, the bf16 screen goes on.
+// A failing stream operation or launch is an error of the model (its stream is not usable); nothing stays allocated.
+static int cls_screen_q8_create(kh_model* m) {
+  const kh_config& c = m->cfg;
+  kh_model::ClsScreen::Q8& t = m->scr.q8;
+  if (!m->scr.on || c.dim % KH_SCR8_G != 0 || q8_hooks_bar()) return KH_OK;
+  plan_screen_q8(m);
+  if (!ScreenMV::has(kh_stage_maxv(c.dim, t.wg))) return KH_OK;
+  const size_t V = (size_t)c.vocab_size, gpr = (size_t)(c.dim / KH_SCR8_G);
+  // partials: every grid a KH_SHAPE_SCREEN_Q8 hook may ask for
+  if (dalloc(&t.q, V * (size_t)c.dim) != KH_OK || dalloc(&t.sc, V * gpr) != KH_OK || dalloc(&t.e8, V) != KH_OK ||
+      dalloc(&t.p_lb, 4096) != KH_OK || dalloc(&t.p_spill, 4096) != KH_OK || dalloc(&t.p_ub, 4096 * KH_SCR8_C) != KH_OK ||
+      dalloc(&t.p_idx, 4096 * KH_SCR8_C) != KH_OK || dalloc(&t.stats, 4) != KH_OK) {
+    (void)hipGetLastError();  // the failed allocation is not the model's error
+    cls_screen_q8_release(m);
+    if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
+      fprintf(stderr, "[kh] classifier screen, int8 tier: no room for the copy, the tier is off\n");
+    return KH_OK;
+  }
+  hipStream_t st = m->stream;
+  const int n = (c.dim + KH_WAVE - 1) / KH_WAVE + 24;  // roundings a term passes through (kh_cls_screen.h)
+  const double u = 1.0 / 16777216.0;
+  const double gam2 = 2.0 * (n * u) / (1.0 - n * u);
+  float ms = 0.f;
+  auto build = [&]() -> int {
+    KH_CHECK_HIP(hipMemsetAsync(t.stats, 0, 4 * sizeof(int32_t), st));
+    KH_CHECK_HIP(hipEventRecord(m->ev0, st));
+    hipLaunchKernelGGL(k_cls_q8_build, dim3(2048), dim3(KH_WG), 0, st, (const float*)m->cls.w, (uint32_t*)t.q, t.sc,
+                       t.e8, c.dim, c.vocab_size, gam2);
+    KH_CHECK_HIP(hipEventRecord(m->ev1, st));
+    KH_CHECK_HIP(hipEventSynchronize(m->ev1));
+    const int rc = kh_launch_status();
+    if (rc != KH_OK) return rc;
+    KH_CHECK_HIP(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+    return KH_OK;
+  };
+  const int rc = build();
+  if (rc != KH_OK) {
+    cls_screen_q8_release(m);
+    return rc;
+  }
+  t.bytes = V * (size_t)c.dim + V * gpr * sizeof(float) + V * sizeof(float);
+  t.build_ms = ms;
+  t.on = true;
+  if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
+    fprintf(stderr, "[kh] classifier screen, int8 tier: copy %.1f MB in %.2f ms; k_cls_screen_q8 u %d grid %d wg %d\n",
+            (double)t.bytes / 1e6, t.build_ms, t.u, t.grid, t.wg);
+  return KH_OK;
+}
+
 void cls_screen_release(kh_model* m) {
   kh_model::ClsScreen& s = m->scr;
+  cls_screen_q8_release(m);
   for (void* q : {(void*)s.wbf, (void*)s.err, (void*)s.x_save, (void*)s.p_lb, (void*)s.p_spill, (void*)s.p_ub,
                   (void*)s.p_idx, (void*)s.ov_val, (void*)s.ov_idx, (void*)s.ticket, (void*)s.stats})
     if (q) (void)hipFree(q);
@@ -133,6 +236,7 @@ int cls_screen_create(kh_model* m) {
   if ((rc = kh_launch_status()) != KH_OK) return rc;
   KH_CHECK_HIP(hipEventElapsedTime(&s.build_ms, m->ev0, m->ev1));
   s.on = true;
+  if ((rc = cls_screen_q8_create(m)) != KH_OK) return rc;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
     fprintf(stderr, "[kh] classifier screen: bf16 copy %.1f MB in %.2f ms; k_cls_screen u %d grid %d wg %d, "
                     "k_sample_screen grid %d wg %d\n", (double)s.bytes / 1e6, s.build_ms, s.u, s.grid, s.wg, s.sgrid,
@@ -140,10 +244,40 @@ int cls_screen_create(kh_model* m) {
   return KH_OK;
 }
 
-void launch_cls_screen(kh_model* m, float* dbg_lb, float* dbg_ub) {
+void launch_cls_screen_q8(kh_model* m, float* dbg_lb, float* dbg_ub, int grid) {
+  const kh_config& c = m->cfg;
+  const kh_model::ClsScreen::Q8& t = m->scr.q8;
+  KhClsScreenQ8Args a;
+  a.x = m->x;
+  a.final_norm = m->final_norm;
+  a.q = t.q;
+  a.sc = t.sc;
+  a.e8 = t.e8;
+  a.p_lb = t.p_lb;
+  a.p_spill = t.p_spill;
+  a.p_ub = t.p_ub;
+  a.p_idx = t.p_idx;
+  a.dbg_lb = dbg_lb;
+  a.dbg_ub = dbg_ub;
+  a.dim = c.dim;
+  a.vocab = c.vocab_size;
+  a.eps = c.rms_eps;
+  pick_screen<ScreenQ8U>(t.u, kh_stage_maxv(c.dim, t.wg), [&](auto U, auto MV) {
+    kh_launch(KH_KERNEL(k_cls_screen_q8, U, MV), grid > 0 ? grid : t.grid, t.wg, cls_screen_q8_lds_bytes(c.dim), m->stream, a);
+  });
+}
+
+// nq > 0: survivor mode behind a k_cls_screen_q8 launch of nq workgroups; 0: the full scan
+static void launch_cls_screen_behind(kh_model* m, float* dbg_lb, float* dbg_ub, int nq) {
   const kh_config& c = m->cfg;
   const kh_model::ClsScreen& s = m->scr;
   KhClsScreenArgs a;
+  a.q_lb = nq > 0 ? s.q8.p_lb : nullptr;
+  a.q_spill = s.q8.p_spill;
+  a.q_ub = s.q8.p_ub;
+  a.q_idx = s.q8.p_idx;
+  a.q_stats = s.q8.stats;
+  a.nq = nq;
   a.x = m->x;
   a.final_norm = m->final_norm;
   a.wbf = s.wbf;
@@ -161,6 +295,10 @@ void launch_cls_screen(kh_model* m, float* dbg_lb, float* dbg_ub) {
   pick_screen<ScreenU>(s.u, kh_stage_maxv(c.dim, s.wg), [&](auto U, auto MV) {
     kh_launch(KH_KERNEL(k_cls_screen, U, MV), s.grid, s.wg, cls_screen_lds_bytes(c.dim), m->stream, a);
   });
+}
+
+void launch_cls_screen(kh_model* m, float* dbg_lb, float* dbg_ub, bool survivors) {
+  launch_cls_screen_behind(m, dbg_lb, dbg_ub, survivors ? m->scr.q8.grid : 0);
 }
 
 void launch_sample_screen(kh_model* m, int advance, int n_forced) {
@@ -268,6 +406,66 @@ int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) 
   return KH_OK;
 }
 
+// One three-launch tail - tier 1 on grid1 workgroups (0: the planned grid), the bf16 screen of what it left, the
+// re-score - then one full pair, on the vector now in m->x, without advancing.  tok[0] / tok[1]: the two tokens; the
+// logits buffer holds k_cls's logits afterwards.  then(lb8, ub8): see cls_screen_pairs.
+template <class F>
+static int cls_screen_q8_pairs(kh_model* m, int grid1, int32_t* tok, F&& then) {
+  hipStream_t st = m->stream;
+  const size_t V = (size_t)m->cfg.vocab_size;
+  float *lb = nullptr, *ub = nullptr;
+  int rc;
+  if ((rc = dalloc(&lb, V)) == KH_OK && (rc = dalloc(&ub, V)) == KH_OK) {
+    launch_cls_screen_q8(m, lb, ub, grid1);
+    launch_cls_screen_behind(m, nullptr, nullptr, grid1 > 0 ? grid1 : m->scr.q8.grid);
+    launch_sample(m, /*advance=*/0, /*n_forced=*/0, kScreen);
+    hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    launch_cls(m);
+    launch_sample(m, 0, 0, kGreedy);
+    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = then(lb, ub);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = (int)e;
+  }
+  if (lb) (void)hipFree(lb);
+  if (ub) (void)hipFree(ub);
+  return rc;
+}
+
+// The tier's creation-time check: the embedding row of token 1 through the three-launch tail and through a full step.
+// *result: 0 not applicable, 1 passed, -1 failed -> the tier is off for this model, the bf16 screen goes on.
+int cls_screen_q8_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
+  const kh_config& c = m->cfg;
+  kh_model::ClsScreen& s = m->scr;
+  *result = 0;
+  if (!s.on || !s.q8.on) return KH_OK;
+  hipStream_t st = m->stream;
+  const size_t V = (size_t)c.vocab_size;
+  int32_t tok[2] = {-1, -2}, flag = 0;
+  set_state(m, 1 % c.vocab_size, 0);
+  int rc = cls_screen_q8_pairs(m, 0, tok, [&](const float* lb, const float* ub) {
+    const size_t g = (V + KH_WG - 1) / KH_WG;
+    hipLaunchKernelGGL(k_st_interval, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(KH_WG), 0, st, m->logits, lb, ub, V,
+                       d_flag);
+    return hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st);
+  });
+  if (rc == KH_OK) rc = kh_launch_status();
+  if (rc != KH_OK) return rc;
+  *result = (flag || tok[0] != tok[1] || inject) ? -1 : 1;
+  KH_CHECK_HIP(hipMemsetAsync(s.stats, 0, 4 * sizeof(int32_t), st));  // the counters describe the user's steps
+  KH_CHECK_HIP(hipMemsetAsync(s.q8.stats, 0, 4 * sizeof(int32_t), st));
+  if (*result < 0) {
+    fprintf(stderr, "[kh] classifier screen, int8 tier: self-test failed (tokens %d / %d): the tier is off for this "
+                    "model\n", tok[0], tok[1]);
+    KH_CHECK_HIP(hipStreamSynchronize(st));
+    cls_screen_q8_release(m);  // the copy's HBM goes back
+    s.q8.selftest = -1;
+  } else {
+    s.q8.selftest = 1;
+  }
+  return KH_OK;
+}
+
 }  // namespace khm
 using namespace khm;
 
@@ -337,6 +535,85 @@ extern "C" int kh_model_cls_screen_info(kh_model* m, int64_t* out) {
     int32_t h[4] = {0, 0, 0, 0};
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     KH_CHECK_HIP(hipMemcpyAsync(h, s.stats, sizeof(h), hipMemcpyDeviceToHost, m->stream));
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    out[4] = h[0];
+    out[5] = h[1];
+    out[6] = h[2];
+  }
+  return KH_OK;
+}
+
+// The int8 tier (tests).  One non-advancing three-launch tail - k_cls_screen_q8 on `grid` workgroups (0: the planned
+// grid), k_cls_screen in survivor mode, k_sample_screen - and one full step on the caller's residual vector.
+// h_lb8 / h_ub8 [vocab]: tier 1's interval of every row.  out[6]: the tail's token | the full classifier's token | rows
+// that survived tier 1 | 1 if tier 1 spilled (the bf16 launch then scanned every row) | candidate rows re-scored | 1 if
+// the step overflowed.  The counters of both info calls are put back; the logits buffer holds k_cls's logits of h_x.
+extern "C" int kh_model_cls_screen_q8_probe(kh_model* m, const float* h_x, int32_t grid, float* h_lb8, float* h_ub8,
+                                            int64_t* out) {
+  if (!m || !h_x || !h_lb8 || !h_ub8 || !out || grid < 0 || grid > 4096) return KH_ERR_INVALID_ARG;
+  const kh_model::ClsScreen& s = m->scr;
+  if (!s.on || !s.q8.on || m->samp_on) return KH_ERR_UNSUPPORTED;
+  const kh_config& c = m->cfg;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  hipStream_t st = m->stream;
+  const size_t V = (size_t)c.vocab_size;
+  int32_t tok[2] = {-1, -2}, h0[8] = {0}, h1[8] = {0};
+  KH_CHECK_HIP(hipMemcpyAsync(h0, s.stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  KH_CHECK_HIP(hipMemcpyAsync(h0 + 4, s.q8.stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  KH_CHECK_HIP(hipStreamSynchronize(st));
+  hipError_t e = hipMemcpyAsync(m->x, h_x, sizeof(float) * (size_t)c.dim, hipMemcpyHostToDevice, st);
+  int rc = e != hipSuccess ? (int)e : cls_screen_q8_pairs(m, grid, tok, [&](const float* lb, const float* ub) {
+    hipError_t r = hipMemcpyAsync(h_lb8, lb, sizeof(float) * V, hipMemcpyDeviceToHost, st);
+    if (r == hipSuccess) r = hipMemcpyAsync(h_ub8, ub, sizeof(float) * V, hipMemcpyDeviceToHost, st);
+    if (r == hipSuccess) r = hipMemcpyAsync(h1, s.stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (r == hipSuccess) r = hipMemcpyAsync(h1 + 4, s.q8.stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    return r;
+  });
+  e = hipMemcpyAsync(s.stats, h0, 4 * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.q8.stats, h0 + 4, 4 * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (rc == KH_OK && e != hipSuccess) rc = (int)e;
+  if (rc == KH_OK) rc = kh_launch_status();
+  if (rc != KH_OK) return rc;
+  out[0] = tok[0];
+  out[1] = tok[1];
+  out[2] = h1[5] - h0[5];
+  out[3] = h1[6] - h0[6];
+  out[4] = h1[1] - h0[1];
+  out[5] = h1[2] - h0[2];
+  return KH_OK;
+}
+
+// the int8 copy [vocab x dim], its scales [vocab x dim / 64] and its per-row error table [vocab] (tests)
+extern "C" int kh_model_cls_screen_q8_read(kh_model* m, int8_t* h_q, float* h_sc, float* h_e8) {
+  if (!m || !h_q || !h_sc || !h_e8) return KH_ERR_INVALID_ARG;
+  const kh_model::ClsScreen::Q8& t = m->scr.q8;
+  if (!t.on) return KH_ERR_UNSUPPORTED;
+  const size_t V = (size_t)m->cfg.vocab_size, D = (size_t)m->cfg.dim;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemcpyAsync(h_q, t.q, V * D, hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipMemcpyAsync(h_sc, t.sc, sizeof(float) * V * (D / KH_SCR8_G), hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipMemcpyAsync(h_e8, t.e8, sizeof(float) * V, hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
+}
+
+// out[8]: 0 the tier is on | 1 self-test (0 / 1 / -1) | 2 HBM bytes of the int8 copy, its scales and its row table |
+// 3 microseconds the conversion took | 4 tier-1 steps so far | 5 rows that survived tier 1 in them | 6 steps in which
+// tier 1 spilled (the bf16 launch scanned every row) | 7 rows a tier-1 workgroup hands over
+extern "C" int kh_model_cls_screen_q8_info(kh_model* m, int64_t* out) {
+  if (!m || !out) return KH_ERR_INVALID_ARG;
+  const kh_model::ClsScreen::Q8& t = m->scr.q8;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = t.on ? 1 : 0;
+  out[1] = t.selftest;
+  out[2] = (int64_t)t.bytes;
+  out[3] = (int64_t)(t.build_ms * 1000.f);
+  out[7] = KH_SCR8_C;
+  if (t.on) {
+    int32_t h[4] = {0, 0, 0, 0};
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    KH_CHECK_HIP(hipMemcpyAsync(h, t.stats, sizeof(h), hipMemcpyDeviceToHost, m->stream));
     KH_CHECK_HIP(hipStreamSynchronize(m->stream));
     out[4] = h[0];
     out[5] = h[1];

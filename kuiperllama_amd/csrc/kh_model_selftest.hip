@@ -15,6 +15,9 @@
 //      one screened step against one full step on a fixed vector - the same token, every full logit inside the
 //      interval the screen gave its row.  A failure turns screening off for this model, frees the bf16 copy and says
 //      so on stderr (kh_model_cls_screen_info reports -1).
+//  (d) the int8 tier ahead of that screen (kh_model_screen.hip::cls_screen_q8_selftest): one three-launch tail against
+//      one full step on the same vector - the same token, every full logit inside the interval tier 1 gave its row.
+//      A failure turns the tier off and frees the int8 copy; the bf16 screen goes on (kh_model_cls_screen_q8_info: -1).
 //
 // Both run on scratch state the model owns at that moment (activation buffers, rows of layer 0 of the still
 // empty KV cache, which are zeroed again) in about a millisecond.  This is a tripwire for a part, a compiler or a
@@ -53,6 +56,12 @@ inline int grid_for(size_t n) {
   return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
 }
 inline bool hook_has(const char* v, const char* word) { return v && strstr(v, word) != nullptr; }
+// "screen" names the bf16 screen, "screen8" its int8 tier: the shorter word does not match inside the longer one
+inline bool hook_has_screen(const char* v) {
+  for (const char* p = v; p && (p = strstr(p, "screen")) != nullptr; p += 6)
+    if (p[6] != '8') return true;
+  return false;
+}
 
 }  // namespace
 
@@ -179,18 +188,19 @@ int run_selftests(kh_model* m) {
   const auto t0 = std::chrono::steady_clock::now();
   const char* inj = dbg("KH_SELFTEST_FAIL");
   int32_t* d_flag = nullptr;
-  KH_CHECK_HIP(hipMalloc((void**)&d_flag, 3 * sizeof(int32_t)));
-  int r = 0, a = 0, sc = 0;
-  const hipError_t e = hipMemsetAsync(d_flag, 0, 3 * sizeof(int32_t), m->stream);
+  KH_CHECK_HIP(hipMalloc((void**)&d_flag, 4 * sizeof(int32_t)));
+  int r = 0, a = 0, sc = 0, s8 = 0;
+  const hipError_t e = hipMemsetAsync(d_flag, 0, 4 * sizeof(int32_t), m->stream);
   int rc = e == hipSuccess ? ring_selftest(m, d_flag, hook_has(inj, "ring"), &r) : (int)e;
   if (rc == KH_OK) rc = attn_selftest(m, d_flag + 1, hook_has(inj, "attn"), &a);
-  if (rc == KH_OK) rc = cls_screen_selftest(m, d_flag + 2, hook_has(inj, "screen"), &sc);
+  if (rc == KH_OK) rc = cls_screen_selftest(m, d_flag + 2, hook_has_screen(inj), &sc);
+  if (rc == KH_OK) rc = cls_screen_q8_selftest(m, d_flag + 3, hook_has(inj, "screen8"), &s8);
   (void)hipFree(d_flag);
   if (rc != KH_OK) return rc;
   m->cfg.ring_selftest = r;
   m->cfg.attn_merge_selftest = a;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
-    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d, classifier screen %d (%.2f ms)\n", r, a, sc,
+    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d, classifier screen %d, its int8 tier %d (%.2f ms)\n", r, a, sc, s8,
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return KH_OK;
 }

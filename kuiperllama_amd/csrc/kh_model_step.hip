@@ -315,8 +315,8 @@ void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
   });
 }
 void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
-  if (tail == kScreen) tail = step_tail(m, true);  // processors or sampling on are stronger than "screen"
-  if (tail == kScreen) {
+  if (tail_screens(tail) && step_tail(m, 1) != kScreen) tail = step_tail(m, 1);  // processors or sampling on are stronger than "screen"
+  if (tail_screens(tail)) {
     launch_sample_screen(m, advance, n_forced);
   } else if (tail == kLogprob) {
     KhSampleLpArgs t;
@@ -410,10 +410,14 @@ void launch_step_fused(kh_model* m, int advance, int n_forced, hipEvent_t* ev, i
     launch_w2(m, l);
     mark();
   }
-  if (tail == kScreen)
+  if (tail == kScreenQ8) {
+    launch_cls_screen_q8(m);  // the int8 tier, then the bf16 screen of what it left: 5L + 3 launches
+    launch_cls_screen(m, nullptr, nullptr, /*survivors=*/true);
+  } else if (tail == kScreen) {
     launch_cls_screen(m);  // k_cls's slot: still 5L + 2 launches
-  else
+  } else {
     launch_cls(m);
+  }
   mark();
   launch_sample(m, advance, n_forced, tail);
   mark();
@@ -583,7 +587,7 @@ int enqueue_steps(kh_model* m, int pos, int nsteps, int n_forced, StepTail tail,
     for (int i = 0; i < nsteps; ++i) launch_step_fused(m, /*advance=*/1, n_forced, nullptr, variant, tail);
   }
   // behind screened steps the logits buffer is as old as the last full classifier launch
-  m->scr.stale = tail == kScreen;
+  m->scr.stale = tail_screens(tail);
   return KH_OK;
 }
 
@@ -953,7 +957,7 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
   if (exec != KH_EXEC_GRAPH && exec != KH_EXEC_FUSED) return KH_ERR_INVALID_ARG;
 
   // greedy steps run the screened classifier pair (kh_cls_screen.h) wherever the model has one
-  const bool screen = cls_screen_wanted(m);
+  const int screen = cls_screen_level(m);
   if ((rc = ensure_seq_cap(m, total_steps)) != KH_OK) return rc;
   // every cache row this call can reach is backed by HBM before its first launch (the dry launches of fresh graphs
   // below touch rows 0 .. 7); mapping happens here, on the host, outside the event bracket of the step loop
@@ -1064,7 +1068,7 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
     // first sampled step behind a prefill: alone, and it leaves its logits in the buffer (full classifier)
     const bool keep = s == start && start > 0;
     if (keep) n = 1;
-    if (enqueue_steps(m, s, n, n_forced, step_tail(m, screen && !keep), exec) != KH_OK) return -1;
+    if (enqueue_steps(m, s, n, n_forced, step_tail(m, keep ? 0 : screen), exec) != KH_OK) return -1;
     if (keep && hipMemcpyAsync(m->first_logits, m->logits, sizeof(float) * (size_t)c.vocab_size,
                                hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
       return -1;

@@ -200,6 +200,39 @@ class KuiperModel:
                    "kh_model_cls_screen_read")
         return wbf, err
 
+    def cls_screen_q8_info(self) -> dict:
+        """The int8 tier ahead of the bf16 screen (kh_model_cls_screen_q8_info): whether it is on, its creation-time
+        self-test, the HBM bytes and creation time of the int8 copy, and counters since creation."""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_cls_screen_q8_info(self._h, out), "kh_model_cls_screen_q8_info")
+        keys = ("on", "selftest", "bytes", "build_us", "steps", "survivors", "spill_steps", "rows_per_workgroup")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def cls_screen_q8_probe(self, x: np.ndarray, grid: int = 0) -> dict:
+        """One three-launch screened tail (tier 1 on `grid` workgroups, 0 = as planned) and one full-classifier step on
+        the residual vector x[dim], without advancing (kh_model_cls_screen_q8_probe, tests): the two tokens, the rows
+        that survived tier 1, whether tier 1 spilled, the candidate rows re-scored, whether the step overflowed, and the
+        interval [lb, ub] tier 1 gave every row.  logits() afterwards returns k_cls's logits of x."""
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.shape == (self.cfg.dim,)
+        lb = np.empty(self.cfg.vocab_size, np.float32)
+        ub = np.empty(self.cfg.vocab_size, np.float32)
+        out = (C.c_int64 * 6)()
+        _ffi.check(_ffi.lib().kh_model_cls_screen_q8_probe(self._h, x.ctypes.data, int(grid), lb.ctypes.data,
+                                                           ub.ctypes.data, out), "kh_model_cls_screen_q8_probe")
+        return {"token": int(out[0]), "full_token": int(out[1]), "survivors": int(out[2]), "spill": int(out[3]),
+                "candidates": int(out[4]), "overflow": int(out[5]), "lb": lb, "ub": ub}
+
+    def cls_screen_q8_read(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(int8 copy [vocab, dim], scales [vocab, dim / 64], per-row error table [vocab]): kh_model_cls_screen_q8_read."""
+        V, D = self.cfg.vocab_size, self.cfg.dim
+        q = np.empty((V, D), np.int8)
+        sc = np.empty((V, D // 64), np.float32)
+        e8 = np.empty(V, np.float32)
+        _ffi.check(_ffi.lib().kh_model_cls_screen_q8_read(self._h, q.ctypes.data, sc.ctypes.data, e8.ctypes.data),
+                   "kh_model_cls_screen_q8_read")
+        return q, sc, e8
+
     def kv_bytes(self) -> Tuple[int, int]:
         """(reserved, committed) bytes of the KV cache: the address range of the reference's up-front allocation and
         the HBM backing it right now (mapped on demand, kh_model_kv_bytes)."""
