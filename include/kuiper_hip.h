@@ -484,8 +484,9 @@ int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const float* h_bi
  * its log-prob, top_id[top_n] and top_lp[top_n] - kh_logprobs_f32's semantics on the logits the pick was made from
  * (the processed logits when processors are on; never the tempered or truncated sampling distribution).  Asking for
  * log-probs changes no token: the pick is the first maximum, or kh_sample_f32's draw with counter = position, exactly
- * as without them.  A position that was fed but not sampled - prompt positions, rows a prefill covered - holds the
- * "none" record: token -1, ids -1, NaN floats.  A generate resets the records of its prompt positions [0, n_prompt - 1)
+ * as without them.  A position that predict, generate or a prefill fed but did not sample - prompt positions, rows a
+ * prefill covered - holds the "none" record: token -1, ids -1, NaN floats (kh_model_score, below, is the call that
+ * leaves records at fed positions).  A generate resets the records of its prompt positions [0, n_prompt - 1)
  * to "none"; like the K/V rows, records of other positions are whatever earlier calls left.  Records live in device
  * buffers sized by the cache, allocated by the first call that turns the feature on.  While on, the step's last launch
  * is k_sample_lp (k_sample_proc's duties, then the record: launches_per_token is unchanged) and the screened classifier
@@ -501,6 +502,27 @@ int kh_model_set_logprobs(kh_model* m, int32_t top_n);
 int kh_model_get_logprobs_setting(const kh_model* m, int32_t* top_n);
 int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32_t* h_token, float* h_lp, int32_t* h_top_ids,
                           float* h_top_lp);
+
+/* Sequence scoring: log P(token | prefix) at every FED position (perplexity, loglikelihood evaluation, reranking, the
+ * "echo" log-probs of a prompt).  Feeds h_tokens[0..n) at positions pos0 .. pos0 + n - 1 - rows below pos0 must exist,
+ * as for kh_model_prefill - and leaves what kh_model_prefill leaves: the K/V rows of those positions in every layer,
+ * bit-identical to the token-by-token path, and the fed-token record.  The decode state, the sampler and the
+ * processors are not touched.  In addition every position p of the range receives its log-prob record: token =
+ * h_tokens[p - pos0 + 1], the token that FOLLOWED; logprob = the log-softmax of the RAW logits of position p at that
+ * token; top_ids / top_logprobs = the first top_n tokens of the sampler's order - kh_logprobs_f32's semantics.  The
+ * last position, pos0 + n - 1, has no successor in the call: token -1, logprob NaN, and a FILLED top list (the
+ * next-token distribution).  Entries from top_n on are "none"; records outside the range are untouched.  Penalties,
+ * bias, temperature, top-k and top-p never enter: these are the model's own probabilities of given text.  Read the
+ * records with kh_model_get_logprobs (which synchronises).
+ * The records are BIT-IDENTICAL to kh_logprobs_f32 on the logits n calls of kh_model_predict(.., KH_EXEC_FUSED) leave:
+ * the logits come from k_pf_cls, the B-token twin of the decode classifier (8 tokens per pass over the weights for
+ * fp32, 4 for int8 and wide fp32 models), the records from the routine behind kh_logprobs_f32.  Eager launches on the
+ * model stream, no graph; a model that never calls this launches exactly what it launched before.
+ * Before any launch: KH_ERR_INVALID_ARG for NULL pointers, n <= 0, pos0 < 0; KH_ERR_RANGE for pos0 + n > cache_len or
+ * a token outside [0, vocab_size); KH_ERR_UNSUPPORTED while log-probs are off (kh_model_set_logprobs never called, or
+ * -1) and for geometries outside the mirrored kernels (kh_model_prefill's limits; dim > 16 x the classifier's
+ * workgroup width).  There is no token-by-token fallback and no MFMA variant. */
+int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
 
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,

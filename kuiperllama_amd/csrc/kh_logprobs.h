@@ -294,3 +294,42 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_lp(const KhSa
     for (int i = threadIdx.x; i < (a.dim >> 2); i += KH_SAMP_THREADS) dst[i] = src[i];
   }
 }
+
+// ---- sequence scoring (kh_model_score): the records of the fed positions of one B-token pass.  One workgroup per
+// valid token; the token at position pos0 + b reads row b of k_pf_cls's logits (kh_prefill.h) - the RAW logits: no
+// processor, no sampler - finds its maximum as k_logprobs_op does, and leaves the record of the position: the token
+// that FOLLOWED it (target[b]; -1 behind the last token of a call, whose log-prob is then NaN while its top list
+// is the next-token distribution), that token's log-prob and the top *top_n.  Entries from *top_n on are "none".
+#define KH_SCORE_BMAX 8  // tokens of one pass (kh_prefill.h: KH_PF_BMAX)
+struct KhScoreLpArgs {
+  const float* logits;         // [gridDim.x][vstride]
+  int vstride, vocab;
+  int32_t target[KH_SCORE_BMAX];
+  int pos0;
+  const int32_t* top_n;        // device word (kh_model_set_logprobs)
+  int32_t* rec_token;          // [rec_cap]
+  float* rec_lp;               // [rec_cap]
+  int32_t* rec_top_ids;        // [rec_cap][KH_LOGPROBS_TOP]
+  float* rec_top_lp;           // [rec_cap][KH_LOGPROBS_TOP]
+  int rec_cap;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_score_lp(const KhScoreLpArgs a) {
+  __shared__ KhSampSmem s;
+  __shared__ KhLpSmem t;
+  const int b = blockIdx.x;
+  const int pos = a.pos0 + b;
+  if (b >= KH_SCORE_BMAX || pos < 0 || pos >= a.rec_cap) return;  // uniform
+  const float* lg = a.logits + (size_t)b * a.vstride;
+  float m = -INFINITY;
+  kh_samp_for_global(lg, a.vocab, [&](float l, int) __attribute__((always_inline)) { m = fmaxf(m, l); });
+  const float lmax = kh_samp_block_max(s, m);
+  const int id = a.target[b];
+  const int top_n = min(max(*a.top_n, 0), min(KH_LOGPROBS_TOP, a.vocab));
+  const size_t r0 = (size_t)pos * KH_LOGPROBS_TOP;
+  kh_logprobs_core(s, t, lg, a.vocab, lmax, id, top_n, nullptr, a.rec_lp + pos, a.rec_top_ids + r0, a.rec_top_lp + r0);
+  if (threadIdx.x == 0) a.rec_token[pos] = id;
+  if ((int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
+    a.rec_top_ids[r0 + threadIdx.x] = -1;
+    a.rec_top_lp[r0 + threadIdx.x] = __uint_as_float(0xffffffffu);
+  }
+}

@@ -109,6 +109,10 @@ struct kh_model {
   float *pf_x = nullptr, *pf_q = nullptr, *pf_att = nullptr, *pf_h = nullptr;
   void* pf_ws = nullptr;        // KH_PF_BMAX attention split workspaces
   size_t pf_ws_tok_bytes = 0;
+  // sequence scoring (kh_model_score): k_pf_cls's logits of one pass, [KH_PF_BMAX][pf_vstride], pf_vstride = the
+  // vocabulary rounded up to 4 floats; allocated by the first score call
+  float* pf_logits = nullptr;
+  int pf_vstride = 0;
   // GEMM prefill (kh_gemm.h): slabs of KH_PG_TMAX token rows
   float *pg_x = nullptr, *pg_xn = nullptr, *pg_q = nullptr, *pg_att = nullptr, *pg_h = nullptr;
   float* pg_part = nullptr;     // partial rows of residual GEMMs that split K across workgroups

@@ -1,5 +1,6 @@
 // kh_model_prefill.hip — prompt phase of the model level: the B-token VALU prefill (kh_prefill.h,
-// bit-identical to token-by-token) and the fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h).  The
+// bit-identical to token-by-token), sequence scoring on top of it (kh_model_score: k_pf_cls, k_score_lp) and the
+// fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h).  The
 // reference feeds the prompt one token per forward pass (demo/main.cpp:20-22).
 // gfx950 only.
 #include <stdio.h>
@@ -10,9 +11,11 @@
 
 #include "kh_dispatch.h"
 #include "kh_gemm.h"
+#include "kh_logprobs.h"
 #include "kh_model_internal.h"
 #include "kh_pattn.h"
 #include "kh_prefill.h"
+#include "kh_score_plan.h"
 
 using namespace khm;
 
@@ -149,8 +152,9 @@ void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const f
     });
   }
 }
-// forward of nvalid (<= B) prompt tokens at positions pos0.. : fills their K/V cache rows
-void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0, int B) {
+// forward of nvalid (<= B) prompt tokens at positions pos0.. : fills their K/V cache rows.  full_depth (scoring): the
+// last layer's attention, wo and FFN run too and pf_x holds the tokens' final residual vectors
+void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0, int B, bool full_depth = false) {
   const kh_config& c = m->cfg;
   const bool q = c.is_quant;
   KhPfTokens tk;
@@ -183,8 +187,8 @@ void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0
       });
     }
     // the prompt phase leaves K/V rows and nothing else (no logits): the last layer's K/V rows are
-    // written, its attention, wo and FFN feed nothing
-    if (l == c.layer_num - 1) break;
+    // written, its attention, wo and FFN feed nothing - unless the classifier follows (full_depth)
+    if (l == c.layer_num - 1 && !full_depth) break;
     {
       KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
       a.defer = 0;  // multi-token slices merge in the launch
@@ -216,6 +220,47 @@ void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0
     }
     pf_gemv_res(m, m->sh_w2, W.w2, m->pf_h, m->pf_x, c.hidden_dim, c.dim, nvalid, B);
   }
+}
+// ---- sequence scoring: the classifier and the records behind a full-depth chunk -------------------
+int ensure_score_buffers(kh_model* m) {
+  if (m->pf_logits) return KH_OK;
+  m->pf_vstride = (m->cfg.vocab_size + 3) & ~3;
+  return dalloc(&m->pf_logits, (size_t)KH_PF_BMAX * m->pf_vstride);
+}
+// logits of the chunk's tokens (k_cls's arithmetic on pf_x, the decode classifier's workgroup width), then the record
+// of every position: target[b] = the token fed behind token b, -1 behind the last token of the call
+void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0, int B) {
+  const kh_config& c = m->cfg;
+  {
+    KhPfClsArgs a;
+    a.X = m->pf_x;
+    a.final_norm = m->final_norm;
+    a.wcls = m->cls;
+    a.logits = m->pf_logits;
+    a.dim = c.dim;
+    a.vocab = c.vocab_size;
+    a.vstride = m->pf_vstride;
+    a.gshift = m->gshift;
+    a.nvalid = nvalid;
+    a.eps = c.rms_eps;
+    pick_pf<PfB, PfNoSP>(c.is_quant, 1, B, [&](auto Q, auto, auto BB) {
+      pf_launch(KH_KERNEL(k_pf_cls, Q, BB), m->sh_cls, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
+    });
+  }
+  KhScoreLpArgs t;
+  t.logits = m->pf_logits;
+  t.vstride = m->pf_vstride;
+  t.vocab = c.vocab_size;
+  for (int b = 0; b < KH_SCORE_BMAX; ++b) t.target[b] = b < nvalid ? target[b] : -1;
+  t.pos0 = pos0;
+  t.top_n = m->d_lp_top_n;
+  t.rec_token = m->d_lp_token;
+  t.rec_lp = m->d_lp_lp;
+  t.rec_top_ids = m->d_lp_top_ids;
+  t.rec_top_lp = m->d_lp_top_lp;
+  t.rec_cap = m->lp_cap;
+  launch_log("k_score_lp");
+  hipLaunchKernelGGL(k_score_lp, dim3(nvalid), dim3(KH_SAMP_THREADS), 0, m->stream, t);
 }
 }  // namespace
 
@@ -610,6 +655,33 @@ int khm::prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t po
   for (int t0 = 0; t0 < n; t0 += B)
     launch_prefill_chunk(m, h_tokens + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B);
   return kh_launch_status();
+}
+
+// Sequence scoring: kh_model_prefill's pass at full depth, k_pf_cls and k_score_lp per chunk of B tokens.  Eager
+// launches on the model stream; every check before the first of them.
+static_assert(KH_SCORE_BMAX == KH_PF_BMAX, "k_score_lp takes one target per token of a prefill pass");
+extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
+  if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
+  for (int i = 0; i < n; ++i)
+    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (m->lp_top_n < 0 || !prefill_supported(m) || !kh_stage_fits4(c.dim, m->sh_cls.wg)) return KH_ERR_UNSUPPORTED;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  int rc;
+  if ((rc = kv_ensure(m, pos0 + n)) != KH_OK) return rc;
+  if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
+  if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
+  const int B = prefill_batch(m);
+  for (int t0 = 0; t0 < n; t0 += B) {
+    const int nv = n - t0 < B ? n - t0 : B;
+    int32_t target[KH_PF_BMAX];
+    kh_score_targets(h_tokens, n, t0, nv, target);
+    launch_prefill_chunk(m, h_tokens + t0, nv, pos0 + t0, B, /*full_depth=*/true);
+    launch_score_tail(m, target, nv, pos0 + t0, B);
+  }
+  if ((rc = kh_launch_status()) != KH_OK) return rc;
+  return khm::hist_write(m, h_tokens, n, pos0);
 }
 
 // Time the prompt phase alone: n fed-only tokens at positions pos0.., HIP events on the model

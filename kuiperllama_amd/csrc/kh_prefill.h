@@ -5,8 +5,9 @@
 // row-pair GEMV core keeps B (4 or 8) activation vectors in LDS and B accumulator pairs per wave, so the
 // weight bytes per prompt token drop by B while the kernels stay HBM-bound (B = 4: 4 FMA per
 // weight byte-quad, ~10 % of the VALU rate at the HBM rate).  No logits are produced for prompt
-// tokens (the reference computes and discards them); what the prompt phase leaves behind — the
-// K/V cache rows — is BIT-IDENTICAL to the token-by-token path:
+// tokens (the reference computes and discards them) unless the caller scores the sequence
+// (kh_model_score: the pass at full depth and k_pf_cls at the end of this file); what the prompt
+// phase leaves behind — the K/V cache rows, and those logits — is BIT-IDENTICAL to the token-by-token path:
 //   * per (row, token) the dot product visits the columns in the same order (lane l takes
 //     chunks l, l+64, l+128, ... of its column range whatever U is), with the same SPLIT
 //     partition and the same fixed-order combine;
@@ -514,5 +515,59 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_gemv_res(const KhPfGemvResArgs
   gemv_pairs_b<QUANT, U, SPLIT, B>(
       g, xs, xstride, K >> 1, lane, comb, pair, pre,
       [&]() __attribute__((always_inline)) { pf_stage_copy<QUANT, B>(V, (size_t)M, xs, xstride, M); },
+      epi);
+}
+
+// Sequence scoring (kh_model_score): the B-token twin of k_cls.  Launched with the classifier's decode shape
+// (workgroup width: the RMS statistics use k_cls's thread partition), rows 2p and r1_of(p) per pair with k_cls's
+// odd-vocabulary clamp, the scale applied as there (s *= rs); logits[b][r] for the valid tokens, rows of `vstride`
+// floats (a multiple of 4: every row 16-byte aligned for kh_logprobs_core).  No argmax partials: k_score_lp
+// (kh_logprobs.h) finds each row's maximum itself, as the operator k_logprobs_op does.
+struct KhPfClsArgs {
+  const float* X;  // [B][dim] residual streams after the last layer
+  const float* final_norm;
+  KhLin wcls;
+  float* logits;   // [B][vstride]
+  int dim, vocab, vstride, gshift, nvalid;
+  float eps;
+};
+template <bool QUANT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls(const KhPfClsArgs a) {
+  constexpr int U = KH_PF_U(QUANT);
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const void* const w = a.wcls.w;
+  const float* const sc = a.wcls.scales;
+  const float* const X = a.X;
+  const float* const final_norm = a.final_norm;
+  float* const logits = a.logits;
+  const int dim = a.dim, vocab = a.vocab, vstride = a.vstride, nvalid = a.nvalid;
+  const float eps = a.eps;
+  f32x4* xs = (f32x4*)smem_raw;
+  const int xstride = pf_xstride<QUANT>(dim);
+  float* red = (float*)(xs + (size_t)B * xstride);
+  const int lane = threadIdx.x & 63;
+  const Gemv<QUANT, U> g(dim, a.gshift);
+  auto r1_of = [&](int p) __attribute__((always_inline)) { return 2 * p + 1 < vocab ? 2 * p + 1 : 2 * p; };
+  auto pair = [&](int p) __attribute__((always_inline)) { return g.rows(w, 2 * p, w, r1_of(p), sc, sc, dim); };
+  float rs[B];  // RMS scale per token: set by the staging, applied in the epilogue (as k_cls)
+  auto epi = [&](int p, const float (&s0)[B], const float (&s1)[B], const NoAux&)
+      __attribute__((always_inline)) {
+    if (lane != 0) return;
+    const int r0 = 2 * p, r1 = r1_of(p);
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      if (b < nvalid) {
+        float* row = logits + (size_t)b * vstride;
+        row[r0] = s0[b] * rs[b];
+        if (r1 != r0) row[r1] = s1[b] * rs[b];
+      }
+    }
+  };
+  gemv_pairs_b<QUANT, U, 1, B>(
+      g, xs, xstride, (vocab + 1) >> 1, lane, nullptr, pair,
+      [](int) __attribute__((always_inline)) { return NoAux{}; },
+      [&]() __attribute__((always_inline)) {
+        pf_stage_norm<QUANT, B>(X, (size_t)dim, final_norm, xs, xstride, dim, eps, red, rs);
+      },
       epi);
 }

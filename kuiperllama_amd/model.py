@@ -308,6 +308,28 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_prefill(self._h, t, len(tokens), pos0), "kh_model_prefill")
         torch.cuda.synchronize()
 
+    @staticmethod
+    def score_totals(rec: dict) -> dict:
+        """`rec` (the four keys of .logprobs() for the n positions of a score call) plus "sum_logprob", the float64
+        sum of the n - 1 targets' log-probs (the last position has no target: token -1), and "perplexity" =
+        exp(-sum / (n - 1)) - NaN for a single token, which predicts nothing inside the call."""
+        lp = np.asarray(rec["logprob"], np.float64)[np.asarray(rec["token"]) >= 0]
+        total = float(lp.sum())
+        out = dict(rec)
+        out["sum_logprob"] = total
+        out["perplexity"] = float(np.exp(-total / len(lp))) if len(lp) else float("nan")
+        return out
+
+    def score(self, tokens: Sequence[int], pos0: int = 0) -> dict:
+        """log P(token | prefix) of given text (kh_model_score; needs set_logprobs(top_n)): feeds `tokens` at
+        positions pos0.. like prefill() and returns the records of those n positions - "token": the token that
+        followed (-1 at the last position), "logprob": its log-prob under the raw logits (NaN at the last),
+        "top_ids" / "top_logprobs": [n, top_n] - plus "sum_logprob" and "perplexity" (score_totals).  Bit-identical
+        to ops.logprobs on the logits a loop of predict() leaves."""
+        t = (C.c_int32 * len(tokens))(*[int(x) for x in tokens])
+        _ffi.check(_ffi.lib().kh_model_score(self._h, t, len(tokens), int(pos0)), "kh_model_score")
+        return self.score_totals(self.logprobs(int(pos0), len(tokens)))
+
     def prefill_gemm(self, tokens: Sequence[int], pos0: int = 0) -> None:
         """Forward of `tokens` at positions pos0.. as fp32-MFMA GEMMs (up to 128 tokens per weight
         pass); K/V rows equal the token-by-token ones to fp32 round-off."""

@@ -15,7 +15,7 @@
 //               [--exact-prefill] [--fenced-merge]
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
-//               [--logit-bias id=value]... [--logprobs N]
+//               [--logit-bias id=value]... [--logprobs N] [--score]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -27,7 +27,11 @@
 // kh_model_set_penalties / kh_model_set_logit_bias, applied to the logits ahead of the greedy or sampled pick.
 // --logprobs N (0 .. 20): kh_model_set_logprobs; after the words and the timing, one line per generated token,
 // "pos token lp | id:lp ..." with the N most likely tokens of that position (no token changes).
+// --score (needs --logprobs N): scores the prompt instead of generating (kh_model_score): one line per prompt
+// position in the same form - the token is the one that FOLLOWED, "-1 nan" at the last position, whose list is the
+// next-token distribution - then "sum_logprob:" and "perplexity:" over the prompt's n - 1 predicted tokens.
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +49,7 @@ static void usage() {
                "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge]\n"
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
-               "       [--logit-bias id=value]... [--logprobs N]\n");
+               "       [--logit-bias id=value]... [--logprobs N] [--score]\n");
 }
 
 int main(int argc, char** argv) {
@@ -61,6 +65,7 @@ int main(int argc, char** argv) {
   std::vector<float> bias_vals;
   int steps = 128, exec = KH_EXEC_GRAPH;
   int logprobs = -1;  // --logprobs N (kh_model_set_logprobs)
+  bool score = false;  // --score (kh_model_score)
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
   const char* tok_path = nullptr;
@@ -97,6 +102,7 @@ int main(int argc, char** argv) {
     else if (a == "--frequency-penalty") pen.frequency = (float)std::atof(next());
     else if (a == "--repeat-last-n") pen.last_n = std::atoi(next());
     else if (a == "--logprobs") logprobs = std::atoi(next());
+    else if (a == "--score") score = true;
     else if (a == "--logit-bias") {
       const std::string e = next();
       const size_t eq = e.find('=');
@@ -221,6 +227,39 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "invalid --logprobs %d: %d (%s)\n", logprobs, rc, kh_error_string(rc));
     kh_model_destroy(m);
     return 1;
+  }
+  if (score) {
+    if (logprobs < 0) {
+      std::fprintf(stderr, "--score needs --logprobs N\n");
+      kh_model_destroy(m);
+      return 2;
+    }
+    const int cnt = (int)prompt.size();
+    if ((rc = kh_model_score(m, prompt.data(), cnt, 0)) != KH_OK) {
+      std::fprintf(stderr, "kh_model_score failed: %d (%s)\n", rc, kh_error_string(rc));
+      kh_model_destroy(m);
+      return 1;
+    }
+    std::vector<int32_t> tok_id((size_t)cnt), top_id((size_t)cnt * logprobs + 1);
+    std::vector<float> lp((size_t)cnt), top_lp((size_t)cnt * logprobs + 1);
+    if ((rc = kh_model_get_logprobs(m, 0, cnt, tok_id.data(), lp.data(), top_id.data(), top_lp.data())) != KH_OK) {
+      std::fprintf(stderr, "kh_model_get_logprobs failed: %d (%s)\n", rc, kh_error_string(rc));
+      kh_model_destroy(m);
+      return 1;
+    }
+    double sum = 0.0;
+    for (int i = 0; i < cnt; ++i) {
+      if (tok_id[i] >= 0) sum += (double)lp[i];
+      std::printf("%d %d %.6f |", i, tok_id[i], lp[i]);
+      for (int k = 0; k < logprobs; ++k)
+        std::printf(" %d:%.6f", top_id[(size_t)i * logprobs + k], top_lp[(size_t)i * logprobs + k]);
+      std::printf("\n");
+    }
+    std::printf("sum_logprob:%.6f\nperplexity:%.6f\n", sum, cnt > 1 ? std::exp(-sum / (cnt - 1)) : std::nan(""));
+    if (tok) kh_spm_destroy(tok);
+    if (bpe) kh_bpe_destroy(bpe);
+    kh_model_destroy(m);
+    return 0;
   }
   std::vector<int32_t> words((size_t)steps);
   int32_t n = 0;
