@@ -144,6 +144,12 @@ int kh_mha_decode_f32(const int32_t* d_pos, int32_t pos, int32_t head_num, int32
  * stream, like the reference's D2H copy at argmax_kernel.cu:84). */
 int kh_argmax_f32(const float* logits, int64_t n, int32_t* d_out_index, void* stream);
 int kh_argmax_f32_host(const float* logits, int64_t n, int64_t* h_out_index, void* stream);
+/* The row form: d_out[r] = index of the first maximum of logits[r * row_stride .. + n), r < n_rows - the pick of a
+ * verify pass (kh_model_verify) as an operator.  One workgroup per row, grids of at most 8 rows; asynchronous and
+ * graph-capturable.  KH_ERR_INVALID_ARG for NULL pointers, n <= 0, n_rows <= 0, row_stride < n or row_stride not a
+ * multiple of 4 (rows of a 16-byte aligned buffer then take 16-byte loads). */
+int kh_argmax_rows_f32(const float* logits, int64_t n, int64_t row_stride, int32_t n_rows, int32_t* d_out,
+                       void* stream);
 
 /* Seeded sampling (the reference's sampler::Sampler interface, kuiper/include/sampler/sampler.h, has only the
  * argmax; these are further samplers behind it).  With temperature T, top_k K, top_p P, seed and a 64-bit counter c:
@@ -523,6 +529,67 @@ int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32_t* h_token
  * -1) and for geometries outside the mirrored kernels (kh_model_prefill's limits; dim > 16 x the classifier's
  * workgroup width).  There is no token-by-token fallback and no MFMA variant. */
 int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
+
+/* Speculative greedy decode: up to `width` consecutive positions verified by ONE pass over the weights (llama.cpp's
+ * lookup / --draft, vLLM's ngram speculator, the "predicted outputs" of hosted APIs, in their exact greedy form).
+ * kh_model_verify_width: tokens per verify pass of this model - 8 for fp32, 4 for int8 and wide fp32 models (the
+ * batch of kh_model_prefill); KH_ERR_UNSUPPORTED for the geometries kh_model_score refuses.
+ * kh_model_verify feeds h_tokens[0..n), 1 <= n <= width, at positions pos0 .. pos0 + n - 1 (rows below pos0 must exist)
+ * in one full-depth pass: h_tokens[0] is the token known to be fed at pos0, h_tokens[1..n) are drafts.  h_next[i] = the
+ * greedy pick - the first maximum of the RAW logits - at position pos0 + i given h_tokens[0..i]; *n_accept = a, the
+ * largest value in [0, n - 1] with h_next[i] == h_tokens[i + 1] for all i < a.  The caller owns a + 1 new tokens,
+ * h_next[0..a]; h_next[a + 1 .. n) are the picks behind a rejected draft (what the model would say after the wrong
+ * token), of use to tests only.
+ * The logits are those of kh_model_score's pass - bit-identical to n calls of kh_model_predict(.., KH_EXEC_FUSED) - and a
+ * maximum involves no arithmetic, so h_next[0..a] are exactly the tokens a loop of predict calls returns: a rejected
+ * draft costs time, never a different word.  Afterwards the K/V rows pos0 .. pos0 + a are bit-identical to the
+ * token-by-token path; the rows above hold the rejected drafts' K/V and are stale - no step reads a row above its own
+ * position, and the step that reaches one rewrites it first.  The decode state stands at (token h_next[a], position
+ * pos0 + a + 1), as behind an advancing step: graph steps may follow at once.  The fed-token record holds h_tokens[0..a]
+ * at pos0 .. pos0 + a and -1 above; the logits buffer of kh_model_get_logits is not written.  Sampler, processors and
+ * log-prob settings are neither consulted nor touched.  Eager launches on the model stream (the pass, k_pf_cls,
+ * k_spec_pick, k_spec_accept); synchronises.  A model that never calls this launches exactly what it launched before.
+ * Before any launch: KH_ERR_INVALID_ARG for NULL pointers, n <= 0, pos0 < 0; KH_ERR_UNSUPPORTED for the geometries
+ * kh_model_score refuses (the same predicate); KH_ERR_RANGE for n > width, pos0 + n > cache_len or a token outside
+ * [0, vocab_size). */
+int kh_model_verify_width(const kh_model* m, int32_t* width);
+int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next, int32_t* n_accept);
+
+/* Prompt-lookup generation.  kh_model_generate_until's contract in its graph form - the same prompt phase, the same
+ * words, the same *n_words, the same stop rule, *h_elapsed_ms around the loop - with the sampled part driven by
+ * draft + verify.  At position p with token t to feed, kh_lookup_draft proposes up to min(width - 1, total_steps - 1
+ * - p) tokens from the sequence so far (prompt, then words) and the optional hint; a draft of d >= 1 tokens costs one
+ * kh_model_verify pass of [t, draft] and advances by a + 1 positions; no draft runs min(miss_steps, remaining) steps on
+ * the step graphs, exactly as kh_model_generate enqueues them (screened classifier included).  The host reads the words
+ * behind either, so unlike generate there is one host round trip per pass or per miss_steps steps: on text without
+ * repeats that is the price of asking (DESIGN 3.3f has the figures).  The first sampled position behind a prefill
+ * takes a plain step with the full classifier, so kh_model_first_sample keeps working.  A stop token among the accepted
+ * picks ends the call there.  stats (may be NULL): verify passes, tokens drafted, drafts accepted, sampled steps run
+ * on the step graphs; without a stop, accepted + passes + plain_steps = total_steps - (n_prompt - 1).
+ * kh_lookup_opts (NULL = all defaults): ngram_max 0 -> 4, ngram_min 0 -> 1, miss_steps 0 -> 8 (the measured price of
+ * the round trip on text that never drafts: +2.3-2.5 % of the token loop at 1, +0.2-0.4 % at 8).
+ * Before any launch: KH_ERR_INVALID_ARG as kh_model_generate_until, and for negative options, ngram_max < ngram_min,
+ * miss_steps > 8 or a hint without a pointer; KH_ERR_RANGE as there, and for a hint token outside [0, vocab_size);
+ * KH_ERR_UNSUPPORTED while a sampler (temperature > 0), a penalty, a bias entry or log-probs are on, and for the
+ * geometries kh_model_verify refuses.  There is no silent fallback: kh_model_generate_until is the caller's to call. */
+typedef struct kh_lookup_opts {
+  int32_t ngram_max;   /* longest suffix searched, >= ngram_min; 0 -> 4 */
+  int32_t ngram_min;   /* >= 1; 0 -> 1 */
+  int32_t miss_steps;  /* decode steps run on the step graphs when nothing is drafted, 1..8; 0 -> 8 */
+  const int32_t* h_hint; int32_t n_hint;  /* optional expected text ("predicted output"), token ids in range */
+} kh_lookup_opts;
+typedef struct kh_lookup_stats { int32_t passes, drafted, accepted, plain_steps; } kh_lookup_stats;
+int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
+                             const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts,
+                             int32_t* h_words, int32_t* n_words, float* h_elapsed_ms, kh_lookup_stats* stats);
+/* The drafter itself (host only, no device; csrc/kh_lookup.h), stateless.  For g = min(ngram_max, n_seq) down to
+ * ngram_min, with key = the last g tokens of seq: (1) the EARLIEST j with hint[j .. j+g) == key and j + g < n_hint
+ * drafts hint[j+g ..]; (2) else the MOST RECENT j with j + g <= n_seq - 1 and seq[j .. j+g) == key drafts seq[j+g ..];
+ * the first g that matches wins, the draft is cut to cap, no match gives 0.  Returns the draft length written to
+ * out[0 .. cap), or KH_ERR_INVALID_ARG (negative sizes or options, ngram_max < ngram_min, a size without a pointer);
+ * ngram_max 0 -> 4, ngram_min 0 -> 1. */
+int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t* hint, int32_t n_hint,
+                    int32_t ngram_max, int32_t ngram_min, int32_t* out, int32_t cap);
 
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,

@@ -17,7 +17,7 @@ EXPORTS = [
     "kh_error_string", "kh_version", "kh_device_count",
     "kh_add_f32", "kh_matmul_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
-    "kh_mha_decode_workspace_bytes", "kh_argmax_f32",
+    "kh_mha_decode_workspace_bytes", "kh_argmax_f32", "kh_argmax_rows_f32",
     "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
@@ -26,7 +26,7 @@ EXPORTS = [
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
-    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
+    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_lookup_draft", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
 ]
@@ -87,6 +87,19 @@ def penalties(repetition: float = 1.0, presence: float = 0.0, frequency: float =
     return Penalties(float(repetition), float(presence), float(frequency), int(last_n))
 
 
+class LookupOpts(C.Structure):
+    """kh_lookup_opts: 0 = the default of a field (ngram_max 4, ngram_min 1, miss_steps 8); hint optional."""
+    _fields_ = [("ngram_max", C.c_int32), ("ngram_min", C.c_int32), ("miss_steps", C.c_int32),
+                ("h_hint", C.POINTER(C.c_int32)), ("n_hint", C.c_int32)]
+
+
+class LookupStats(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("drafted", C.c_int32), ("accepted", C.c_int32), ("plain_steps", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "dim", "hidden_dim", "layer_num", "head_num", "kv_head_num", "vocab_size", "seq_len",
@@ -135,6 +148,7 @@ def lib() -> C.CDLL:
     L.kh_mha_decode_f32.argtypes = [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                     _vp, _vp, _i64, _vp]
     L.kh_argmax_f32.argtypes = [_vp, _i64, _vp, _vp]
+    L.kh_argmax_rows_f32.argtypes = [_vp, _i64, _i64, _i32, _vp, _vp]
     L.kh_argmax_f32_host.argtypes = [_vp, _i64, C.POINTER(_i64), _vp]
     L.kh_sample_f32.argtypes = [_vp, _i64, C.POINTER(Sampling), _i64, _i32, _vp, _vp]
     L.kh_sample_f32_host.argtypes = [_vp, _i64, C.POINTER(Sampling), _i64, C.POINTER(_i64), _vp]
@@ -211,6 +225,12 @@ def lib() -> C.CDLL:
                                 C.POINTER(C.c_int64)]
     L.kh_model_prefill.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
     L.kh_model_score.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
+    L.kh_model_verify_width.argtypes = [_vp, C.POINTER(_i32)]
+    L.kh_model_verify.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]
+    L.kh_model_generate_lookup.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), _i32,
+                                           C.POINTER(LookupOpts), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f32),
+                                           C.POINTER(LookupStats)]
+    L.kh_lookup_draft.argtypes = [C.POINTER(_i32), _i32, C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32), _i32]
     L.kh_model_prefill_gemm.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
     L.kh_model_time_prefill.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_f32)]
     L.kh_model_profile_kernel.argtypes = [_vp, _i32, _i32, _i32, C.POINTER(_f32)]

@@ -113,6 +113,10 @@ struct kh_model {
   // vocabulary rounded up to 4 floats; allocated by the first score call
   float* pf_logits = nullptr;
   int pf_vstride = 0;
+  // speculative greedy decode (kh_model_verify, kh_spec.h): the result block of a verify pass {a, pick[0 .. 8)} on the
+  // device and its pinned mirror; allocated by the first verify pass
+  int32_t* d_spec = nullptr;
+  int32_t* h_spec_pin = nullptr;
   // GEMM prefill (kh_gemm.h): slabs of KH_PG_TMAX token rows
   float *pg_x = nullptr, *pg_xn = nullptr, *pg_q = nullptr, *pg_att = nullptr, *pg_h = nullptr;
   float* pg_part = nullptr;     // partial rows of residual GEMMs that split K across workgroups
@@ -345,4 +349,13 @@ bool pg_supported(const kh_model* m);       // MFMA GEMM path
 // kh_model_prefill / kh_model_prefill_gemm without the token record (hist_write)
 int prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
 int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
+// Full-depth passes (kh_model_score, kh_model_verify): the geometries they run on, and the tokens of one pass
+bool full_depth_supported(const kh_model* m);
+int verify_width(const kh_model* m);
+// the buffers of a verify pass that reaches cache rows [0, rows): before the first verify_enqueue of a call
+int verify_prepare(kh_model* m, int rows);
+// One verify pass of toks[0 .. n), 1 <= n <= verify_width, at positions pos0 ..: the full-depth pass, k_pf_cls,
+// k_spec_pick, k_spec_accept and the copy of the result block into m->h_spec_pin {a, pick[0 .. n)}, all enqueued on the
+// model stream; the caller synchronises before it reads the block.  Arguments are the caller's to check.
+int verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0);
 }  // namespace khm

@@ -652,6 +652,8 @@ extern "C" void kh_model_destroy(kh_model* m) {
   if (m->h_words_pin) (void)hipHostFree(m->h_words_pin);
   if (m->h_forced_pin) (void)hipHostFree(m->h_forced_pin);
   if (m->first_logits) (void)hipFree(m->first_logits);
+  if (m->d_spec) (void)hipFree(m->d_spec);
+  if (m->h_spec_pin) (void)hipHostFree(m->h_spec_pin);
   if (m->d_samp) (void)hipFree(m->d_samp);
   for (void* q : {(void*)m->d_hist, (void*)m->d_proc, (void*)m->d_bias_ids, (void*)m->d_bias, (void*)m->d_cnt})
     if (q) (void)hipFree(q);

@@ -1,5 +1,6 @@
 // kh_model_prefill.hip — prompt phase of the model level: the B-token VALU prefill (kh_prefill.h,
-// bit-identical to token-by-token), sequence scoring on top of it (kh_model_score: k_pf_cls, k_score_lp) and the
+// bit-identical to token-by-token), sequence scoring on top of it (kh_model_score: k_pf_cls, k_score_lp), the verify
+// pass of speculative greedy decode (kh_model_verify: k_pf_cls, kh_spec.h) and the
 // fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h).  The
 // reference feeds the prompt one token per forward pass (demo/main.cpp:20-22).
 // gfx950 only.
@@ -16,6 +17,7 @@
 #include "kh_pattn.h"
 #include "kh_prefill.h"
 #include "kh_score_plan.h"
+#include "kh_spec.h"
 
 using namespace khm;
 
@@ -30,6 +32,10 @@ bool prefill_supported(const kh_model* m) {
   if (pf_lds_bytes(c.is_quant, c.dim, 4) > 160 * 1024) return false;
   if (pf_lds_bytes(c.is_quant, c.hidden_dim, 2) > 160 * 1024) return false;
   return true;
+}
+// the full-depth pass ends in k_pf_cls, which stages like k_cls at the classifier's workgroup width
+bool full_depth_supported(const kh_model* m) {
+  return prefill_supported(m) && kh_stage_fits4(m->cfg.dim, m->sh_cls.wg);
 }
 bool pg_supported(const kh_model* m) {
   const kh_config& c = m->cfg;
@@ -227,26 +233,30 @@ int ensure_score_buffers(kh_model* m) {
   m->pf_vstride = (m->cfg.vocab_size + 3) & ~3;
   return dalloc(&m->pf_logits, (size_t)KH_PF_BMAX * m->pf_vstride);
 }
-// logits of the chunk's tokens (k_cls's arithmetic on pf_x, the decode classifier's workgroup width), then the record
-// of every position: target[b] = the token fed behind token b, -1 behind the last token of the call
+// logits of the chunk's tokens behind a full-depth pass (k_cls's arithmetic on pf_x, the decode classifier's workgroup
+// width): rows 0 .. nvalid - 1 of pf_logits
+void launch_pf_cls(kh_model* m, int nvalid, int B) {
+  const kh_config& c = m->cfg;
+  KhPfClsArgs a;
+  a.X = m->pf_x;
+  a.final_norm = m->final_norm;
+  a.wcls = m->cls;
+  a.logits = m->pf_logits;
+  a.dim = c.dim;
+  a.vocab = c.vocab_size;
+  a.vstride = m->pf_vstride;
+  a.gshift = m->gshift;
+  a.nvalid = nvalid;
+  a.eps = c.rms_eps;
+  pick_pf<PfB, PfNoSP>(c.is_quant, 1, B, [&](auto Q, auto, auto BB) {
+    pf_launch(KH_KERNEL(k_pf_cls, Q, BB), m->sh_cls, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
+  });
+}
+// the classifier, then the record of every position: target[b] = the token fed behind token b, -1 behind the last
+// token of the call
 void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0, int B) {
   const kh_config& c = m->cfg;
-  {
-    KhPfClsArgs a;
-    a.X = m->pf_x;
-    a.final_norm = m->final_norm;
-    a.wcls = m->cls;
-    a.logits = m->pf_logits;
-    a.dim = c.dim;
-    a.vocab = c.vocab_size;
-    a.vstride = m->pf_vstride;
-    a.gshift = m->gshift;
-    a.nvalid = nvalid;
-    a.eps = c.rms_eps;
-    pick_pf<PfB, PfNoSP>(c.is_quant, 1, B, [&](auto Q, auto, auto BB) {
-      pf_launch(KH_KERNEL(k_pf_cls, Q, BB), m->sh_cls, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
-    });
-  }
+  launch_pf_cls(m, nvalid, B);
   KhScoreLpArgs t;
   t.logits = m->pf_logits;
   t.vstride = m->pf_vstride;
@@ -666,7 +676,7 @@ extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, i
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
   for (int i = 0; i < n; ++i)
     if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
-  if (m->lp_top_n < 0 || !prefill_supported(m) || !kh_stage_fits4(c.dim, m->sh_cls.wg)) return KH_ERR_UNSUPPORTED;
+  if (m->lp_top_n < 0 || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
   if ((rc = kv_ensure(m, pos0 + n)) != KH_OK) return rc;
@@ -682,6 +692,77 @@ extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, i
   }
   if ((rc = kh_launch_status()) != KH_OK) return rc;
   return khm::hist_write(m, h_tokens, n, pos0);
+}
+
+// ---- speculative greedy decode: the verify pass (kh_spec.h) ---------------------------------------------------------
+static_assert(KH_SPEC_BMAX == KH_PF_BMAX, "k_spec_accept takes one fed token per token of a prefill pass");
+int khm::verify_width(const kh_model* m) { return prefill_batch(m); }
+int khm::verify_prepare(kh_model* m, int rows) {
+  int rc;
+  if ((rc = kv_ensure(m, rows)) != KH_OK) return rc;
+  if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
+  if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
+  if (!m->d_spec && (rc = dalloc(&m->d_spec, (size_t)1 + KH_SPEC_BMAX)) != KH_OK) return rc;
+  if (!m->h_spec_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_spec_pin, sizeof(int32_t) * (1 + KH_SPEC_BMAX), hipHostMallocDefault));
+  return KH_OK;
+}
+int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0) {
+  const kh_config& c = m->cfg;
+  const int B = prefill_batch(m);
+  launch_prefill_chunk(m, toks, n, pos0, B, /*full_depth=*/true);
+  launch_pf_cls(m, n, B);
+  launch_log("k_spec_pick");
+  hipLaunchKernelGGL(k_spec_pick, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, (const float*)m->pf_logits,
+                     c.vocab_size, (long long)m->pf_vstride, m->d_spec + 1);
+  KhSpecAcceptArgs t;
+  t.res = m->d_spec;
+  for (int b = 0; b < KH_SPEC_BMAX; ++b) t.fed[b] = b < n ? toks[b] : -1;
+  t.pos0 = pos0;
+  t.n = n;
+  t.words = m->d_words;
+  t.words_cap = m->seq_cap;
+  t.hist = m->d_hist;
+  t.hist_cap = m->hist_cap;
+  t.d_next = m->d_next;
+  t.d_token = m->d_token;
+  t.d_pos = m->d_pos;
+  t.tok_emb = m->tok_emb;
+  t.x = m->x;
+  t.dim = c.dim;
+  t.vocab = c.vocab_size;
+  launch_log("k_spec_accept");
+  hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(KH_WG), 0, m->stream, t);
+  KH_CHECK_HIP(hipMemcpyAsync(m->h_spec_pin, m->d_spec, sizeof(int32_t) * (size_t)(1 + n), hipMemcpyDeviceToHost,
+                              m->stream));
+  return kh_launch_status();
+}
+
+extern "C" int kh_model_verify_width(const kh_model* m, int32_t* width) {
+  if (!m || !width) return KH_ERR_INVALID_ARG;
+  if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  *width = verify_width(m);
+  return KH_OK;
+}
+// One verify pass.  Eager launches on the model stream; every check before the first of them.
+extern "C" int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
+                               int32_t* n_accept) {
+  if (!m || !h_tokens || !h_next || !n_accept || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  if (n > verify_width(m) || (int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
+  for (int i = 0; i < n; ++i)
+    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  int rc;
+  if ((rc = verify_prepare(m, pos0 + n)) != KH_OK) return rc;
+  rc = verify_enqueue(m, h_tokens, n, pos0);
+  const hipError_t e = hipStreamSynchronize(m->stream);  // drained on every way out
+  if (rc != KH_OK) return rc;
+  if (e != hipSuccess) return (int)e;
+  *n_accept = m->h_spec_pin[0];
+  memcpy(h_next, m->h_spec_pin + 1, sizeof(int32_t) * (size_t)n);
+  return KH_OK;
 }
 
 // Time the prompt phase alone: n fed-only tokens at positions pos0.., HIP events on the model

@@ -16,6 +16,7 @@
 #include "kh_fused_ring.h"
 #include "kh_sample.h"
 #include "kh_logprobs.h"
+#include "kh_lookup.h"
 #include "kh_model_internal.h"
 
 namespace khm {
@@ -916,46 +917,21 @@ inline bool is_stop(int32_t t, const int32_t* stop, int n_stop) {
     if (stop[i] == t) return true;
   return false;
 }
-}  // namespace
-
-extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int32_t n_prompt,
-                                       int32_t total_steps, int32_t exec, const int32_t* h_stop,
-                                       int32_t n_stop, int32_t* h_words, int32_t* n_words,
-                                       float* h_elapsed_ms) {
-  if (!m || !h_prompt || n_prompt <= 0 || total_steps <= 0 || !h_words || !n_words ||
-      n_stop < 0 || (n_stop > 0 && !h_stop))
-    return KH_ERR_INVALID_ARG;
+// What the graph / fused forms of kh_model_generate_until and kh_model_generate_lookup share: the setup and the
+// prompt phase of a run (generate_begin), and the enqueue of its next steps (generate_chunk)
+struct GenRun {
+  int exec = KH_EXEC_GRAPH;
+  int screen = 0;      // cls_screen_level: the tail of the greedy steps
+  int n_forced = 0;
+  int start = 0;       // first position the step loop feeds: n_prompt - 1 behind a prefill, else 0
+  int total_steps = 0;
+};
+// Forced-token upload, step buffers, cache rows, step graphs and their dry launches, the event that opens the timed
+// loop, the prompt phase by the model's mode, and the decode state at (h_prompt[start], start).  Arguments checked by
+// the caller.
+int generate_begin(kh_model* m, const int32_t* h_prompt, int n_prompt, int total_steps, int exec, GenRun* g) {
   const kh_config& c = m->cfg;
-  if (total_steps > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n_prompt; ++i)
-    if (h_prompt[i] < 0 || h_prompt[i] >= c.vocab_size) return KH_ERR_RANGE;
-  KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
-  *n_words = 0;
-
-  if (exec == KH_EXEC_UNFUSED) {
-    // the reference loop verbatim: host drives every step and reads `next` back each time
-    KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
-    int pos = 0, next = -1, nw = 0;
-    while (pos < total_steps) {
-      const bool is_prompt = pos < n_prompt - 1;
-      const int tok = pos <= n_prompt - 1 ? h_prompt[pos] : next;
-      int got = -1;
-      if ((rc = kh_model_predict(m, tok, pos, is_prompt, KH_EXEC_UNFUSED, &got)) != KH_OK) return rc;
-      // demo/main.cpp:30-32: only a sampled token can end the sentence (next == -1 in the prompt)
-      if (!is_prompt && is_stop(got, h_stop, n_stop)) break;
-      next = is_prompt ? h_prompt[pos + 1] : got;
-      h_words[nw++] = next;
-      pos += 1;
-    }
-    KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));
-    KH_CHECK_HIP(hipEventSynchronize(m->ev1));
-    if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
-    *n_words = nw;
-    return KH_OK;
-  }
-  if (exec != KH_EXEC_GRAPH && exec != KH_EXEC_FUSED) return KH_ERR_INVALID_ARG;
-
   // greedy steps run the screened classifier pair (kh_cls_screen.h) wherever the model has one
   const int screen = cls_screen_level(m);
   if ((rc = ensure_seq_cap(m, total_steps)) != KH_OK) return rc;
@@ -1060,20 +1036,73 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
     m->first_pos = start;
   }
   set_state(m, h_prompt[start], start);
-  auto launch_chunk = [&](int s) -> int {  // enqueue the next 1 or up to KH_GRAPH_STEPS steps (positions s ..)
-    // graph exec: the largest of 8 / 4 / 2 / 1 steps that still fits (a single-step launch costs ~15 us of graph-launch
-    // gap: the 20-step form of the bench ran 8 + 8 + 1 + 1 + 1 + 1 and lost 0.3 % to it; now 8 + 8 + 4)
-    int n = exec == KH_EXEC_GRAPH ? KH_GRAPH_STEPS : 1;
-    while (n > total_steps - s) n >>= 1;
-    // first sampled step behind a prefill: alone, and it leaves its logits in the buffer (full classifier)
-    const bool keep = s == start && start > 0;
-    if (keep) n = 1;
-    if (enqueue_steps(m, s, n, n_forced, step_tail(m, keep ? 0 : screen), exec) != KH_OK) return -1;
-    if (keep && hipMemcpyAsync(m->first_logits, m->logits, sizeof(float) * (size_t)c.vocab_size,
-                               hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
-      return -1;
-    return n;
-  };
+  g->exec = exec;
+  g->screen = screen;
+  g->n_forced = n_forced;
+  g->start = start;
+  g->total_steps = total_steps;
+  return KH_OK;
+}
+// enqueue the next 1 or up to KH_GRAPH_STEPS steps (positions s ..), at most `limit` of them; returns how many, -1 on
+// an error
+int generate_chunk(kh_model* m, const GenRun& g, int s, int limit) {
+  // graph exec: the largest of 8 / 4 / 2 / 1 steps that still fits (a single-step launch costs ~15 us of graph-launch
+  // gap: the 20-step form of the bench ran 8 + 8 + 1 + 1 + 1 + 1 and lost 0.3 % to it; now 8 + 8 + 4)
+  int n = g.exec == KH_EXEC_GRAPH ? KH_GRAPH_STEPS : 1;
+  while (n > limit) n >>= 1;
+  // first sampled step behind a prefill: alone, and it leaves its logits in the buffer (full classifier)
+  const bool keep = s == g.start && g.start > 0;
+  if (keep) n = 1;
+  if (enqueue_steps(m, s, n, g.n_forced, step_tail(m, keep ? 0 : g.screen), g.exec) != KH_OK) return -1;
+  if (keep && hipMemcpyAsync(m->first_logits, m->logits, sizeof(float) * (size_t)m->cfg.vocab_size,
+                             hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
+    return -1;
+  return n;
+}
+}  // namespace
+
+extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int32_t n_prompt,
+                                       int32_t total_steps, int32_t exec, const int32_t* h_stop,
+                                       int32_t n_stop, int32_t* h_words, int32_t* n_words,
+                                       float* h_elapsed_ms) {
+  if (!m || !h_prompt || n_prompt <= 0 || total_steps <= 0 || !h_words || !n_words ||
+      n_stop < 0 || (n_stop > 0 && !h_stop))
+    return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  if (total_steps > c.cache_len) return KH_ERR_RANGE;
+  for (int i = 0; i < n_prompt; ++i)
+    if (h_prompt[i] < 0 || h_prompt[i] >= c.vocab_size) return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  int rc;
+  *n_words = 0;
+
+  if (exec == KH_EXEC_UNFUSED) {
+    // the reference loop verbatim: host drives every step and reads `next` back each time
+    KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
+    int pos = 0, next = -1, nw = 0;
+    while (pos < total_steps) {
+      const bool is_prompt = pos < n_prompt - 1;
+      const int tok = pos <= n_prompt - 1 ? h_prompt[pos] : next;
+      int got = -1;
+      if ((rc = kh_model_predict(m, tok, pos, is_prompt, KH_EXEC_UNFUSED, &got)) != KH_OK) return rc;
+      // demo/main.cpp:30-32: only a sampled token can end the sentence (next == -1 in the prompt)
+      if (!is_prompt && is_stop(got, h_stop, n_stop)) break;
+      next = is_prompt ? h_prompt[pos + 1] : got;
+      h_words[nw++] = next;
+      pos += 1;
+    }
+    KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));
+    KH_CHECK_HIP(hipEventSynchronize(m->ev1));
+    if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
+    *n_words = nw;
+    return KH_OK;
+  }
+  if (exec != KH_EXEC_GRAPH && exec != KH_EXEC_FUSED) return KH_ERR_INVALID_ARG;
+
+  GenRun g;
+  if ((rc = generate_begin(m, h_prompt, n_prompt, total_steps, exec, &g)) != KH_OK) return rc;
+  const int start = g.start;
+  auto launch_chunk = [&](int s) -> int { return generate_chunk(m, g, s, total_steps - s); };
   int n_out = total_steps;
   if (n_stop == 0) {
     for (int s = start; s < total_steps;) {
@@ -1149,4 +1178,123 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
   if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
   *n_words = n_out;
   return KH_OK;
+}
+
+// ---- speculative greedy decode (kh_lookup.h: the drafter; kh_model_prefill.hip: the verify pass) -------------------
+extern "C" int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t* hint, int32_t n_hint, int32_t ngram_max,
+                               int32_t ngram_min, int32_t* out, int32_t cap) {
+  KhLookupCfg cfg;
+  if (n_seq < 0 || n_hint < 0 || cap < 0 || (n_seq > 0 && !seq) || (n_hint > 0 && !hint) || (cap > 0 && !out) ||
+      !kh_lookup_resolve(ngram_max, ngram_min, 0, &cfg))
+    return KH_ERR_INVALID_ARG;
+  return kh_lookup_draft_core(seq, n_seq, hint, n_hint, cfg.ngram_max, cfg.ngram_min, out, cap);
+}
+
+// kh_model_generate_until's graph form with the sampled part driven by draft + verify: at position p a draft of d >= 1
+// tokens costs one verify pass and yields a + 1 words, no draft costs miss_steps steps on the step graphs.  The host
+// reads the words behind either (the next draft needs them), so every iteration ends in a stream sync.
+extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
+                                        const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts,
+                                        int32_t* h_words, int32_t* n_words, float* h_elapsed_ms,
+                                        kh_lookup_stats* stats) {
+  if (!m || !h_prompt || n_prompt <= 0 || total_steps <= 0 || !h_words || !n_words || n_stop < 0 ||
+      (n_stop > 0 && !h_stop))
+    return KH_ERR_INVALID_ARG;
+  const kh_lookup_opts o = opts ? *opts : kh_lookup_opts{0, 0, 0, nullptr, 0};
+  KhLookupCfg cfg;
+  if (!kh_lookup_resolve(o.ngram_max, o.ngram_min, o.miss_steps, &cfg) || o.n_hint < 0 || (o.n_hint > 0 && !o.h_hint))
+    return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  if (total_steps > c.cache_len) return KH_ERR_RANGE;
+  for (int i = 0; i < n_prompt; ++i)
+    if (h_prompt[i] < 0 || h_prompt[i] >= c.vocab_size) return KH_ERR_RANGE;
+  for (int i = 0; i < o.n_hint; ++i)
+    if (o.h_hint[i] < 0 || o.h_hint[i] >= c.vocab_size) return KH_ERR_RANGE;
+  // greedy on the raw logits only, and only where the verify pass runs: no silent fallback to generate_until
+  if (m->samp_on || m->proc_on || m->lp_top_n >= 0 || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  return kh_api_guard([&]() -> int {
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    *n_words = 0;
+    int rc;
+    // every early return below may leave launches and copies into pinned memory in flight: drain first
+    auto fail = [&](int code) -> int {
+      (void)hipStreamSynchronize(m->stream);
+      return code;
+    };
+    std::vector<int32_t> seq(h_prompt, h_prompt + n_prompt);  // seq[i] = the token of position i, as far as known
+    seq.reserve((size_t)total_steps + KH_GRAPH_STEPS + 1);
+    if ((rc = verify_prepare(m, total_steps)) != KH_OK) return rc;
+    GenRun g;
+    if ((rc = generate_begin(m, h_prompt, n_prompt, total_steps, KH_EXEC_GRAPH, &g)) != KH_OK) return fail(rc);
+    const int width = verify_width(m);
+    int32_t* const pin = m->h_words_pin;
+    for (int i = 0; i < g.start; ++i) pin[i] = h_prompt[i + 1];  // forced, main.cpp:36-38
+    kh_lookup_stats st{0, 0, 0, 0};
+    int p = g.start, stop_at = -1;
+    while (p < total_steps && stop_at < 0) {
+      const bool sampled = p >= n_prompt - 1;
+      // the first sampled position behind a prefill takes a plain step with the full classifier (kh_model_first_sample)
+      const bool first = p == g.start && g.start > 0;
+      int32_t fed[KH_GRAPH_STEPS];
+      int d = 0;
+      if (sampled && !first) {
+        const int room = total_steps - 1 - p;
+        d = kh_lookup_draft_core(seq.data(), p + 1, o.h_hint, o.n_hint, cfg.ngram_max, cfg.ngram_min, fed + 1,
+                                 width - 1 < room ? width - 1 : room);
+      }
+      if (d > 0) {
+        fed[0] = seq[(size_t)p];
+        if ((rc = verify_enqueue(m, fed, d + 1, p)) != KH_OK) return fail(rc);
+        if (hipStreamSynchronize(m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
+        const int a = m->h_spec_pin[0];
+        for (int i = 0; i <= a && stop_at < 0; ++i) {
+          const int32_t w = m->h_spec_pin[1 + i];
+          if (is_stop(w, h_stop, n_stop)) {
+            stop_at = p + i;
+          } else {
+            pin[p + i] = w;
+            seq.push_back(w);
+          }
+        }
+        st.passes += 1;
+        st.drafted += d;
+        st.accepted += a;
+        p += a + 1;
+      } else {
+        // nothing drafted: steps on the step graphs, exactly as generate enqueues them (prompt positions that no
+        // prefill covered run here too, up to the last fed-only one)
+        int k = sampled ? cfg.miss_steps : n_prompt - 1 - p;
+        if (k > total_steps - p) k = total_steps - p;
+        if (k > KH_GRAPH_STEPS) k = KH_GRAPH_STEPS;
+        if (first) k = 1;
+        for (int s = p; s < p + k;) {
+          const int n = generate_chunk(m, g, s, p + k - s);
+          if (n < 0) return fail((int)hipErrorUnknown);
+          s += n;
+        }
+        if (hipMemcpyAsync(pin + p, m->d_words + p, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, m->stream) !=
+                hipSuccess ||
+            hipStreamSynchronize(m->stream) != hipSuccess)
+          return fail((int)hipErrorUnknown);
+        for (int s = p; s < p + k && stop_at < 0; ++s) {
+          if (s >= n_prompt - 1 && is_stop(pin[s], h_stop, n_stop))
+            stop_at = s;
+          else if (s + 1 >= (int)seq.size())
+            seq.push_back(pin[s]);
+        }
+        if (sampled) st.plain_steps += k;
+        p += k;
+      }
+    }
+    if (hipEventRecord(m->ev1, m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
+    if ((rc = kh_launch_status()) != KH_OK) return fail(rc);
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    m->forced_in_flight = false;
+    const int n_out = stop_at >= 0 ? stop_at : total_steps;
+    memcpy(h_words, pin, sizeof(int32_t) * (size_t)n_out);
+    if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
+    if (stats) *stats = st;
+    *n_words = n_out;
+    return KH_OK;
+  });
 }

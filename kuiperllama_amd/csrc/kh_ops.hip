@@ -13,6 +13,7 @@
 #include "kh_gemv.h"
 #include "kh_sample.h"  // (includes kh_logit_proc.h)
 #include "kh_logprobs.h"
+#include "kh_spec.h"
 
 // =============================================================================================
 // add / swiglu / scale : elementwise, HBM/L2-bound, float4 body + scalar tail
@@ -683,6 +684,19 @@ extern "C" int kh_argmax_f32(const float* logits, int64_t n, int32_t* d_out_inde
   if (!logits || !d_out_index || n <= 0 || n > 0x7fffffffLL) return KH_ERR_INVALID_ARG;
   hipLaunchKernelGGL(k_argmax, dim3(1), dim3(KH_ARGMAX_THREADS), 0, (hipStream_t)stream, logits,
                      (long long)n, d_out_index);
+  return kh_launch_status();
+}
+// The row form (kh_spec.h::k_spec_pick, the pick of a verify pass): d_out[r] = first maximum of row r, one workgroup
+// per row, grids of at most 8 rows.  Asynchronous, capturable.
+extern "C" int kh_argmax_rows_f32(const float* logits, int64_t n, int64_t row_stride, int32_t n_rows, int32_t* d_out,
+                                  void* stream) {
+  if (!logits || !d_out || n <= 0 || n > 0x7fffffffLL || n_rows <= 0 || row_stride < n || (row_stride & 3))
+    return KH_ERR_INVALID_ARG;
+  for (int32_t r0 = 0; r0 < n_rows; r0 += KH_SPEC_BMAX) {
+    const int rows = n_rows - r0 < KH_SPEC_BMAX ? n_rows - r0 : KH_SPEC_BMAX;
+    hipLaunchKernelGGL(k_spec_pick, dim3(rows), dim3(KH_SAMP_THREADS), 0, (hipStream_t)stream,
+                       logits + (size_t)r0 * (size_t)row_stride, (int)n, (long long)row_stride, d_out + r0);
+  }
   return kh_launch_status();
 }
 // The reference's sampler path (ArgmaxSampler::sample -> argmax_kernel_cu, argmax_kernel.cu:53-77) allocates 8 bytes

@@ -22,6 +22,24 @@ def _opts(spec: binfmt.ModelSpec, max_seq_len: int, device: int, flags: int = 0)
                           spec.rms_eps, max_seq_len, device, flags)
 
 
+def _i32_array(tokens):
+    return (C.c_int32 * max(len(tokens), 1))(*[int(t) for t in tokens])
+
+
+def lookup_draft(seq: Sequence[int], hint: Optional[Sequence[int]] = None, ngram_max: int = 4, ngram_min: int = 1,
+                 cap: int = 7) -> List[int]:
+    """The drafter of generate_lookup (kh_lookup_draft; host only, no device): up to `cap` tokens that followed the
+    longest suffix of `seq` (ngram_max .. ngram_min tokens) at its earliest occurrence in `hint`, else at its most
+    recent earlier occurrence in `seq` itself; [] when nothing matches."""
+    seq, hint = list(seq), list(hint or [])
+    out = (C.c_int32 * max(int(cap), 1))()
+    n = _ffi.lib().kh_lookup_draft(_i32_array(seq), len(seq), _i32_array(hint), len(hint), int(ngram_max),
+                                   int(ngram_min), out, int(cap))
+    if n < 0:
+        raise _ffi.KhError(n, "kh_lookup_draft")
+    return list(out[:n])
+
+
 class KuiperModel:
     """Owns a kh_model handle.  Construct with one of the from_* classmethods."""
 
@@ -329,6 +347,45 @@ class KuiperModel:
         t = (C.c_int32 * len(tokens))(*[int(x) for x in tokens])
         _ffi.check(_ffi.lib().kh_model_score(self._h, t, len(tokens), int(pos0)), "kh_model_score")
         return self.score_totals(self.logprobs(int(pos0), len(tokens)))
+
+    def verify_width(self) -> int:
+        """Tokens per verify pass of this model (kh_model_verify_width): 8 for fp32, 4 for int8 and wide fp32."""
+        w = C.c_int32(0)
+        _ffi.check(_ffi.lib().kh_model_verify_width(self._h, C.byref(w)), "kh_model_verify_width")
+        return int(w.value)
+
+    def verify(self, tokens: Sequence[int], pos0: int) -> Tuple[np.ndarray, int]:
+        """One verify pass (kh_model_verify): feeds tokens[0] - known - and the drafts tokens[1:] at positions pos0 ..
+        in one sweep of the weights.  Returns (next, n_accept): next[i] is the greedy pick at position pos0 + i given
+        tokens[:i + 1]; the caller owns next[:n_accept + 1], exactly the tokens a loop of predict() returns, and the
+        decode state stands behind them."""
+        n = len(tokens)
+        nxt = np.full(max(n, 1), -1, np.int32)
+        a = C.c_int32(-1)
+        _ffi.check(_ffi.lib().kh_model_verify(self._h, _i32_array(tokens), n, int(pos0),
+                                              nxt.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(a)), "kh_model_verify")
+        return nxt[:n], int(a.value)
+
+    def generate_lookup(self, prompt: Sequence[int], total_steps: int, stop: Sequence[int] = (), ngram_max: int = 4,
+                        ngram_min: int = 1, miss_steps: int = 8,
+                        hint: Optional[Sequence[int]] = None) -> Tuple[List[int], float, dict]:
+        """generate(exec="graph") with the sampled part driven by draft + verify (kh_model_generate_lookup): the same
+        words, several per sweep of the weights wherever lookup_draft's guess - from the text so far and the optional
+        `hint`, the expected output - is right.  Greedy only.  Returns (words, elapsed_ms, stats) with stats =
+        {"passes", "drafted", "accepted", "plain_steps"}."""
+        _ffi.sync_env()  # KH_PREFILL, KH_PG_*
+        st, hn = list(stop or []), list(hint or [])
+        hint_arr = _i32_array(hn)
+        opts = _ffi.LookupOpts(int(ngram_max), int(ngram_min), int(miss_steps),
+                               C.cast(hint_arr, C.POINTER(C.c_int32)) if hn else None, len(hn))
+        words = (C.c_int32 * max(total_steps, 1))()
+        n = C.c_int32(0)
+        ms = C.c_float(0.0)
+        stats = _ffi.LookupStats()
+        _ffi.check(_ffi.lib().kh_model_generate_lookup(self._h, _i32_array(prompt), len(prompt), total_steps,
+                                                       _i32_array(st), len(st), C.byref(opts), words, C.byref(n),
+                                                       C.byref(ms), C.byref(stats)), "kh_model_generate_lookup")
+        return list(words[: n.value]), float(ms.value), stats.as_dict()
 
     def prefill_gemm(self, tokens: Sequence[int], pos0: int = 0) -> None:
         """Forward of `tokens` at positions pos0.. as fp32-MFMA GEMMs (up to 128 tokens per weight

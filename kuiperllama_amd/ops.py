@@ -151,6 +151,16 @@ def argmax(logits, out_index):
     return out_index
 
 
+def argmax_rows(logits, n: int, out_index):
+    """out_index[r] = first maximum of logits[r, :n] for every row of the contiguous 2-d fp32 tensor `logits`, whose
+    row stride - logits.shape[1] - is at least n and a multiple of 4 (kh_argmax_rows_f32; asynchronous)."""
+    rows, stride = logits.shape
+    assert out_index.numel() >= rows
+    _ffi.check(_ffi.lib().kh_argmax_rows_f32(_p(logits, torch.float32), int(n), int(stride), int(rows),
+                                             _p(out_index, torch.int32), _stream()), "kh_argmax_rows_f32")
+    return out_index
+
+
 def argmax_host(logits) -> int:
     import ctypes as C
     r = C.c_int64(-1)

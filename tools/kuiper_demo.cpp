@@ -16,6 +16,7 @@
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
+//               [--lookup [ngram_max]] [--hint id,id,...]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -30,6 +31,10 @@
 // --score (needs --logprobs N): scores the prompt instead of generating (kh_model_score): one line per prompt
 // position in the same form - the token is the one that FOLLOWED, "-1 nan" at the last position, whose list is the
 // next-token distribution - then "sum_logprob:" and "perplexity:" over the prompt's n - 1 predicted tokens.
+// --lookup [ngram_max]: speculative greedy decode (kh_model_generate_lookup): the same words, several per pass over
+// the weights wherever the text so far - or --hint id,id,..., the expected output - predicts the next tokens (n-grams
+// of up to ngram_max tokens, default 4).  Greedy only.  A line "lookup: passes P drafted D accepted A plain_steps S"
+// follows the words.
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <cmath>
 #include <chrono>
@@ -49,7 +54,8 @@ static void usage() {
                "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge]\n"
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
-               "       [--logit-bias id=value]... [--logprobs N] [--score]\n");
+               "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
+               "       [--lookup [ngram_max]] [--hint id,id,...]\n");
 }
 
 int main(int argc, char** argv) {
@@ -66,6 +72,9 @@ int main(int argc, char** argv) {
   int steps = 128, exec = KH_EXEC_GRAPH;
   int logprobs = -1;  // --logprobs N (kh_model_set_logprobs)
   bool score = false;  // --score (kh_model_score)
+  bool lookup = false;  // --lookup [ngram_max] (kh_model_generate_lookup)
+  kh_lookup_opts lk{0, 0, 0, nullptr, 0};
+  std::vector<int32_t> hint;  // --hint
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
   const char* tok_path = nullptr;
@@ -103,6 +112,10 @@ int main(int argc, char** argv) {
     else if (a == "--repeat-last-n") pen.last_n = std::atoi(next());
     else if (a == "--logprobs") logprobs = std::atoi(next());
     else if (a == "--score") score = true;
+    else if (a == "--lookup") {
+      lookup = true;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') lk.ngram_max = std::atoi(argv[++i]);
+    }
     else if (a == "--logit-bias") {
       const std::string e = next();
       const size_t eq = e.find('=');
@@ -122,8 +135,8 @@ int main(int argc, char** argv) {
     else if (a == "--exec") {
       std::string e = next();
       exec = e == "unfused" ? KH_EXEC_UNFUSED : (e == "fused" ? KH_EXEC_FUSED : KH_EXEC_GRAPH);
-    } else if (a == "--prompt" || a == "--stop") {
-      std::vector<int32_t>& dst = a == "--prompt" ? prompt : stop;
+    } else if (a == "--prompt" || a == "--stop" || a == "--hint") {
+      std::vector<int32_t>& dst = a == "--prompt" ? prompt : (a == "--stop" ? stop : hint);
       dst.clear();
       std::string s = next();
       size_t p = 0;
@@ -266,8 +279,16 @@ int main(int argc, char** argv) {
   float gpu_ms = 0.f;
   std::printf("Generating...\n");
   const auto t0 = std::chrono::steady_clock::now();  // timer excludes init (main.cpp:66)
-  rc = kh_model_generate_until(m, prompt.data(), (int32_t)prompt.size(), steps, exec, stop.data(),
-                               (int32_t)stop.size(), words.data(), &n, &gpu_ms);
+  kh_lookup_stats lks{0, 0, 0, 0};
+  if (lookup) {
+    lk.h_hint = hint.empty() ? nullptr : hint.data();
+    lk.n_hint = (int32_t)hint.size();
+    rc = kh_model_generate_lookup(m, prompt.data(), (int32_t)prompt.size(), steps, stop.data(), (int32_t)stop.size(),
+                                  &lk, words.data(), &n, &gpu_ms, &lks);
+  } else {
+    rc = kh_model_generate_until(m, prompt.data(), (int32_t)prompt.size(), steps, exec, stop.data(),
+                                 (int32_t)stop.size(), words.data(), &n, &gpu_ms);
+  }
   const auto t1 = std::chrono::steady_clock::now();
   if (rc != KH_OK) {
     std::fprintf(stderr, "generate failed: %d (%s)\n", rc, kh_error_string(rc));
@@ -298,6 +319,9 @@ int main(int argc, char** argv) {
   for (int i = 0; i < n; ++i) std::printf("%d ", words[i]);
   const double dur = std::chrono::duration<double>(t1 - t0).count();
   const int steps_done = n - (o.family == KH_FAMILY_QWEN2 && !prompt.empty() ? 1 : 0);
+  if (lookup)
+    std::printf("\nlookup: passes %d drafted %d accepted %d plain_steps %d", lks.passes, lks.drafted, lks.accepted,
+                lks.plain_steps);
   std::printf("\nsteps/s:%lf\n", (double)steps_done / dur);
   if (o.family == KH_FAMILY_QWEN2) std::printf("\nsteps:%d\n\nduration:%lf\n", steps_done, dur);  // main_qwen.cpp:73-74
   const int p0 = (int)prompt.size() - 1;
