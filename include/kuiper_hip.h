@@ -591,6 +591,73 @@ int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, int32_t n_pro
 int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t* hint, int32_t n_hint,
                     int32_t ngram_max, int32_t ngram_min, int32_t* out, int32_t cap);
 
+/* Sequence slots: several independent sequences in one model, decoded `width` per pass over the weights (best-of-n,
+ * self-consistency, a handful of prompts at once).  The reference runs one sequence per process (demo/main.cpp).
+ * kh_model_seq_slots cuts the cache rows into n_slots equal regions: *slot_len (may be NULL) = cache_len / n_slots,
+ * rounded down; slot s is rows [s * slot_len, (s + 1) * slot_len) of every layer, position p of its sequence is row
+ * s * slot_len + p of the unchanged [layer, cache_len, kv_dim] layout (kh_model_read_kv reads it there).  One slot is
+ * the state at creation.  Bookkeeping only: no kernel reads it, nothing is moved, and every batch-1 entry point keeps
+ * addressing rows from 0 - slot 0 IS the batch-1 sequence's rows.  KH_ERR_INVALID_ARG unless 1 <= n_slots <= 64 and
+ * slot_len >= 8.  kh_plan_seq_slots is the host-only twin.
+ * kh_model_seq_width: lanes per pass - kh_model_verify_width's value, refused alike.
+ * kh_model_seq_prefill: kh_model_prefill on the rows of `slot` - n tokens at positions pos0 .. of that sequence, rows
+ * bit-identical to the token-by-token path; the fed-token and log-prob records, which describe the batch-1 sequence,
+ * are not written.  KH_ERR_RANGE for a slot outside [0, n_slots), pos0 + n > slot_len or a token outside the
+ * vocabulary, otherwise kh_model_prefill's codes.  Does not synchronise.
+ * kh_model_seq_fork copies K/V rows [0, n_rows) of every layer from src_slot to dst_slot on the model stream: with the
+ * prefill call, how n samples share one prefilled prompt (they hold copies; nothing reads a shared prefix once).
+ * KH_ERR_INVALID_ARG for src == dst or n_rows <= 0, KH_ERR_RANGE for a slot outside the partition or n_rows >
+ * slot_len.  Does not synchronise.
+ * kh_model_seq_step: ONE full-depth pass over n <= width lanes in distinct slots.  Lane i feeds h_tokens[i] at
+ * position pos[i] of slot slots[i] (rows below pos[i] of that slot must exist); h_next[i] = the pick at that position:
+ * the first maximum of the raw logits, or, with samplings != NULL and samplings[i].temperature > 0, kh_sample_f32's
+ * draw with counter = pos[i] and the lane's own seed.  The logits are kh_model_score's - bit-identical to
+ * kh_model_predict(.., KH_EXEC_FUSED) after the same history - so h_next[i] is exactly what a predict loop on a batch-1
+ * model with kh_model_set_sampling(samplings[i]) returns, and row slot * slot_len + pos[i] of every layer is
+ * bit-identical to that loop's row pos[i]; no other row is written.  The model's own sampler setting is not
+ * consulted; the decode state, the logits buffer of kh_model_get_logits and the fed-token record are not touched.
+ * Eager launches (k_seq_embed, per layer k_seq_qkv, k_seq_attn and the prefill pass's kernels, k_pf_cls, k_seq_pick);
+ * synchronises.  Before any launch: KH_ERR_INVALID_ARG for NULL pointers, n <= 0, two lanes in one slot or invalid
+ * sampling parameters; KH_ERR_UNSUPPORTED while a penalty, a bias entry or log-probs are on and for the geometries
+ * kh_model_score refuses; KH_ERR_RANGE for n > width, a slot outside the partition, pos[i] outside [0, slot_len) or a
+ * token outside the vocabulary.
+ * kh_model_generate_batch: kh_model_generate_until for n_seq <= n_slots sequences at once, sequence s in slot s.
+ * h_prompts holds the prompts back to back (n_prompt[s] tokens each); row s of h_words ([n_seq][words_stride],
+ * words_stride >= every total_steps[s]) and n_words[s] are EXACTLY what kh_model_generate_until returns for prompt s,
+ * total_steps[s], the stop list and kh_model_set_sampling(samplings[s]) (NULL: greedy) on a batch-1 model whose
+ * prompt phase is bit-identical (KH_FLAG_PREFILL_EXACT, or fewer than 17 prompt tokens), and rows [0, n_words[s]) of
+ * slot s are that model's rows.  The fed-only part of each prompt runs as kh_model_seq_prefill's passes, then passes of
+ * up to `width` lanes: more live sequences than that take several passes per step, lanes grouped in slot order
+ * (kh_plan_seq_batch is the grouping, host-only: out_lanes[pass * width + i] = the sequence in lane i or -1; first_pos[s]
+ * = n_prompt[s] - 1; KH_ERR_RANGE with *n_passes set when cap_passes is too small).  Passes are enqueued eagerly, the
+ * picks feed the next pass on the device; with a stop list the host reads the words of every 8 passes from pinned
+ * memory while the next 8 are queued, and a sequence that stopped or reached its total leaves the lane table there -
+ * what ran past a stop is discarded, as in kh_model_generate_until.  *h_elapsed_ms (may be NULL) spans the prompt passes
+ * and the loop.  Leaves the decode state, the logits buffer and the records alone.  Before any launch:
+ * KH_ERR_INVALID_ARG for NULL pointers, n_seq <= 0, a prompt or total of no tokens, words_stride below a total, invalid
+ * sampling parameters; KH_ERR_RANGE for n_seq > n_slots, total_steps[s] > slot_len or a token outside the vocabulary;
+ * KH_ERR_UNSUPPORTED as kh_model_seq_step.  There is no fallback to a token loop.
+ * kh_model_generate_batch_from is the same call for prompts whose first n_cached[s] positions already sit in slot s
+ * (kh_model_seq_prefill, kh_model_seq_fork; NULL = none): it feeds the rest and returns the words of the WHOLE prompt's
+ * kh_model_generate_until.  KH_ERR_INVALID_ARG unless 0 <= n_cached[s] <= min(n_prompt[s] - 1, total_steps[s]). */
+int kh_model_seq_slots(kh_model* m, int32_t n_slots, int32_t* slot_len);
+int kh_plan_seq_slots(int32_t cache_len, int32_t n_slots, int32_t* slot_len);
+int kh_model_seq_width(const kh_model* m, int32_t* width);
+int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_tokens, int32_t n, int32_t pos0);
+int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot, int32_t n_rows);
+int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens, const int32_t* pos,
+                      const kh_sampling* samplings, int32_t* h_next);
+int kh_model_generate_batch(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                            const int32_t* total_steps, const kh_sampling* samplings, const int32_t* h_stop,
+                            int32_t n_stop, int32_t* h_words, int32_t words_stride, int32_t* n_words,
+                            float* h_elapsed_ms);
+int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                                 const int32_t* n_cached, const int32_t* total_steps, const kh_sampling* samplings,
+                                 const int32_t* h_stop, int32_t n_stop, int32_t* h_words, int32_t words_stride,
+                                 int32_t* n_words, float* h_elapsed_ms);
+int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
+                      int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes);
+
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,
  * cls) for a geometry - what kh_model_create_* configures (env KH_SHAPE_* overrides included).
@@ -629,7 +696,8 @@ int64_t kh_debug_list(char* buf, int64_t cap); /* '\n'-separated names; returns 
  * "attn_launch<wg,ts_shift,defer,fenced,ntok>1?,group_grid?>" (workgroup width - hook KH_ATTN_WG = 256 | 512, which
  * kh_mha_decode_f32, kh_mha_decode_workspace_bytes and kh_plan_attention honour like kh_model_create_* -, log2 of the
  * split quantum, partials left to the wo kernel, fenced merge, several tokens per launch, grid carries the GQA group
- * path); the small-head kernel and kh_mha_f32's score kernel add "k_attn_generic" / "k_mha";
+ * path); a pass over sequence slots adds "k_seq_attn<16,2>" and "seq_attn_launch<wg,ts_shift,fenced,group_grid?>"
+ * instead; the small-head kernel and kh_mha_f32's score kernel add "k_attn_generic" / "k_mha";
  * setting, resetting or unsetting the hook (kh_debug_set) empties it.  kh_debug_launch_log: the names,
  * '\n'-separated and sorted, into buf (always NUL-terminated); returns the bytes needed. */
 int64_t kh_debug_launch_log(char* buf, int64_t cap);

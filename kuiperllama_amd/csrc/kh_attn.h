@@ -1124,3 +1124,115 @@ static inline void launch_attn_decode(KhAttnArgs a, int host_pos, int wg, hipStr
   }
 #undef KH_ATTN_LAUNCH
 }
+
+// =============================================================================================
+// Decode attention over lanes that belong to DIFFERENT sequences (kh_seq.h, kh_model_seq_step): slice blockIdx.y = b
+// is the token of lane b, at position pos[b] of a sequence whose position 0 is cache row row[b] - pos[b] (a sequence
+// slot of the model's cache).  The host knows both, so they travel by value.
+#define KH_SEQ_BMAX 8  // lanes of one pass (kh_prefill.h: KH_PF_BMAX)
+struct KhSeqLanes {
+  int32_t pos[KH_SEQ_BMAX];  // position of the lane's token in its sequence
+  int32_t row[KH_SEQ_BMAX];  // its cache row: the slot's first row + pos
+  int32_t slot[KH_SEQ_BMAX]; // its sequence slot: the entry of the per-slot device tables (token to feed, sampler)
+};
+// k_attn_decode's multi-token slice with the slice's position and K/V base taken from the lane table: the same device
+// functions under the same choice of path, which is per slice (lanes sit at unrelated positions).
+template <int G, int KVM>
+__global__ __launch_bounds__(KH_WG_MAX) void k_seq_attn(KhAttnArgs a, const KhSeqLanes lanes) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int t = (int)blockIdx.y;
+  const int pos = lanes.pos[t];
+  {
+    const size_t row0 = (size_t)(lanes.row[t] - pos) * a.kv_dim;  // the slot's row 0
+    a.kcache_layer += row0;
+    a.vcache_layer += row0;
+    a.q += (size_t)t * a.tok_stride;
+    a.out += (size_t)t * a.tok_stride;
+    a.ws = (char*)a.ws + (size_t)t * a.ws_tok_bytes;
+  }
+  const int b = (int)blockIdx.x;
+  if (KVM == 0 || pos + 1 < a.t_long) {
+    if (b < a.kv_heads * a.kv_mul * a.nsplit) attn_head_block<G>(a, (float*)smem_raw, b, pos);
+    return;
+  }
+  if constexpr (KVM > 0) {
+    if (b >= a.kv_heads * a.nsplit_g) return;
+    const int g = b % a.kv_heads, s = b / a.kv_heads;
+    const size_t head_off = (size_t)g * a.head_size;
+    attn_group_decode<G, KVM>(a.q + (size_t)g * KVM * a.head_size, a.kcache_layer + head_off,
+                              a.vcache_layer + head_off, a.kv_dim, a.head_size, pos,
+                              a.out + (size_t)g * KVM * a.head_size, (float*)smem_raw, g, s,
+                              a.nsplit_g, a.ws_stride,
+                              attn_ws_carve(a.ws, a.kv_heads * KVM, a.head_size, a.ws_stride), a.fenced != 0);
+  }
+}
+// Launch of lanes [0, n): in-launch merge (defer = 0), a.fenced as the caller set it; the grid carries the splits that
+// own timesteps at the HIGHEST lane position of each path, as launch_attn_decode does with pos_hi.  Logs the literal
+// instantiation and "seq_attn_launch<wg,ts_shift,fenced,group_grid?>".
+static inline void launch_seq_attn(KhAttnArgs a, const KhSeqLanes& lanes, int n, int wg, hipStream_t s) {
+  const int G = attn_lanes(a.head_size);
+  auto log2_or_neg = [](int v) {
+    int sh = 0;
+    while ((1 << sh) < v) ++sh;
+    return (1 << sh) == v ? sh : -1;
+  };
+  a.kvh_shift = log2_or_neg(a.kv_heads);
+  a.kvm_shift = log2_or_neg(a.kv_mul);
+  a.d_pos = nullptr;
+  a.defer = 0;
+  int pos_hi = 0;
+  for (int b = 0; b < n; ++b)
+    if (lanes.pos[b] > pos_hi) pos_hi = lanes.pos[b];
+  if (pos_hi + 1 < a.t_long) a.nsplit_g = 0;  // every lane below the group path: the per-head-only instantiation
+  const bool grp = a.nsplit_g > 0 && attn_group_supported(a.head_size, a.kv_mul, wg);
+  if (!grp) a.nsplit_g = 0;
+  int head_splits = 0, group_splits = 0;
+  for (int b = 0; b < n; ++b) {
+    const int p = lanes.pos[b];
+    if (grp && p + 1 >= a.t_long) {
+      const int k = attn_active_splits(p, a.nsplit_g, KH_ATTN_TSG_SHIFT);
+      if (k > group_splits) group_splits = k;
+    } else {
+      const int k = attn_active_splits(p, a.nsplit, a.ts_shift);
+      if (k > head_splits) head_splits = k;
+    }
+  }
+  int grid = a.kv_heads * a.kv_mul * head_splits;
+  size_t lds = attn_fast_lds_bytes(a.head_size, wg);
+  if (grp) {
+    if (a.kv_heads * group_splits > grid) grid = a.kv_heads * group_splits;
+    const size_t l2 = attn_group_lds_bytes(a.head_size, a.kv_mul);
+    if (l2 > lds) lds = l2;
+  }
+  if (grid < 1) grid = 1;
+  const bool logging = khm::g_launch_log_on.load(std::memory_order_relaxed);
+  if (logging) {
+    char rec[96];
+    snprintf(rec, sizeof rec, "seq_attn_launch<%d,%d,%d,%d>", wg, a.ts_shift, a.fenced ? 1 : 0, grp ? 1 : 0);
+    khm::launch_log_add(rec);
+  }
+#define KH_SEQ_ATTN_LAUNCH(GG, KK)                                                               \
+  do {                                                                                           \
+    if (logging) khm::launch_log_add("k_seq_attn<" #GG "," #KK ">");                             \
+    hipLaunchKernelGGL((k_seq_attn<GG, KK>), dim3(grid, n), dim3(wg), lds, s, a, lanes);         \
+  } while (0)
+  const int kvm = grp ? a.kv_mul : 0;
+  if (G == 16) {
+    switch (kvm) {
+      case 2: KH_SEQ_ATTN_LAUNCH(16, 2); break;
+      case 4: KH_SEQ_ATTN_LAUNCH(16, 4); break;
+      case 7: KH_SEQ_ATTN_LAUNCH(16, 7); break;
+      case 8: KH_SEQ_ATTN_LAUNCH(16, 8); break;
+      default: KH_SEQ_ATTN_LAUNCH(16, 0); break;
+    }
+  } else if (G == 32) {
+    switch (kvm) {
+      case 2: KH_SEQ_ATTN_LAUNCH(32, 2); break;
+      case 4: KH_SEQ_ATTN_LAUNCH(32, 4); break;
+      default: KH_SEQ_ATTN_LAUNCH(32, 0); break;
+    }
+  } else {
+    KH_SEQ_ATTN_LAUNCH(64, 0);
+  }
+#undef KH_SEQ_ATTN_LAUNCH
+}

@@ -1,11 +1,12 @@
 // kh_model_internal.h — state and cross-unit helpers of the model level of the C-ABI.
-// The model level is split into six translation units:
+// The model level is split into seven translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
 //                         template parameter, picked from and launched through kh_dispatch.h)
 //   kh_model_prefill.hip  B-token VALU prefill and the MFMA GEMM prefill (kh_prefill.h, kh_gemm.h,
-//                         kh_pattn.h kernels)
+//                         kh_pattn.h kernels), and the B-lane pass over different sequences (kh_seq.h kernels)
+//   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
 //   kh_model_screen.hip   the screened classifier of the greedy generate loop (kh_cls_screen.h kernels)
 //   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge and the screen
@@ -117,6 +118,17 @@ struct kh_model {
   // device and its pinned mirror; allocated by the first verify pass
   int32_t* d_spec = nullptr;
   int32_t* h_spec_pin = nullptr;
+  // Sequence slots (kh_model_seq_slots, kh_model_seq.hip): the cache rows cut into seq_slots equal regions of
+  // cache_len / seq_slots rows - bookkeeping, no kernel reads it.  Device tables with one entry per slot, allocated
+  // by the first seq pass: the token the slot's sequence feeds next and its sampling parameters; the words of every
+  // sequence at its slot's rows ([cache_len]); pinned mirrors / staging of the three.
+  int seq_slots = 1;
+  int32_t* d_seq_tok = nullptr;
+  KhSampParams* d_seq_samp = nullptr;
+  int32_t* d_seq_words = nullptr;
+  int32_t* h_seq_tok_pin = nullptr;
+  KhSampParams* h_seq_samp_pin = nullptr;
+  int32_t* h_seq_words_pin = nullptr;
   // GEMM prefill (kh_gemm.h): slabs of KH_PG_TMAX token rows
   float *pg_x = nullptr, *pg_xn = nullptr, *pg_q = nullptr, *pg_att = nullptr, *pg_h = nullptr;
   float* pg_part = nullptr;     // partial rows of residual GEMMs that split K across workgroups
@@ -340,6 +352,7 @@ int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result);
 // (layer >= 0).  No-op for rows that are mapped already and for caches that are plainly allocated.  Newly mapped
 // memory is zeroed on the model's stream.
 int kv_ensure(kh_model* m, int rows, int layer = -1);
+int kv_ensure_rows(kh_model* m, int row0, int row_end);  // rows [row0, row_end) of every layer (a sequence slot's)
 // ---- kh_model_selftest.hip ------------------------------------------------------------------
 // ring kernels vs register tiles, fence-free vs fenced split merge: once at the end of kh_model_create_*
 int run_selftests(kh_model* m);
@@ -358,4 +371,12 @@ int verify_prepare(kh_model* m, int rows);
 // k_spec_pick, k_spec_accept and the copy of the result block into m->h_spec_pin {a, pick[0 .. n)}, all enqueued on the
 // model stream; the caller synchronises before it reads the block.  Arguments are the caller's to check.
 int verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0);
+// Sequence slots (kh_model_seq.hip drives these; arguments are the caller's to check).  seq_prepare: the buffers of
+// a pass, before the first enqueue of a call.  seq_prefill_enqueue: kh_model_prefill's passes for n tokens at
+// positions pos0 .. of the sequence whose position 0 is cache row row0.  seq_pass_enqueue: one full-depth pass over
+// lanes [0, n) (entries >= n are padded here) - k_seq_embed from d_seq_tok, k_seq_qkv, k_seq_attn, the prefill
+// kernels, k_pf_cls, k_seq_pick; picks land in d_seq_tok[slot] and, with words, in d_seq_words[row].
+int seq_prepare(kh_model* m);
+int seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0);
+int seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words);
 }  // namespace khm

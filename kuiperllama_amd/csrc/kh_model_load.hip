@@ -633,6 +633,7 @@ int new_model(const int32_t* h_header, const kh_model_opts* opts, kh_model** out
 
 namespace khm {
 int kv_ensure(kh_model* m, int rows, int layer) { return kv_ensure_impl(m, 0, rows, layer); }
+int kv_ensure_rows(kh_model* m, int row0, int row_end) { return kv_ensure_impl(m, row0, row_end, -1); }
 }  // namespace khm
 
 // =============================================================================================
@@ -654,6 +655,10 @@ extern "C" void kh_model_destroy(kh_model* m) {
   if (m->first_logits) (void)hipFree(m->first_logits);
   if (m->d_spec) (void)hipFree(m->d_spec);
   if (m->h_spec_pin) (void)hipHostFree(m->h_spec_pin);
+  for (void* q : {(void*)m->d_seq_tok, (void*)m->d_seq_samp, (void*)m->d_seq_words})
+    if (q) (void)hipFree(q);
+  for (void* q : {(void*)m->h_seq_tok_pin, (void*)m->h_seq_samp_pin, (void*)m->h_seq_words_pin})
+    if (q) (void)hipHostFree(q);
   if (m->d_samp) (void)hipFree(m->d_samp);
   for (void* q : {(void*)m->d_hist, (void*)m->d_proc, (void*)m->d_bias_ids, (void*)m->d_bias, (void*)m->d_cnt})
     if (q) (void)hipFree(q);

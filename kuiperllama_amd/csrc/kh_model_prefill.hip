@@ -1,6 +1,7 @@
 // kh_model_prefill.hip — prompt phase of the model level: the B-token VALU prefill (kh_prefill.h,
 // bit-identical to token-by-token), sequence scoring on top of it (kh_model_score: k_pf_cls, k_score_lp), the verify
-// pass of speculative greedy decode (kh_model_verify: k_pf_cls, kh_spec.h) and the
+// pass of speculative greedy decode (kh_model_verify: k_pf_cls, kh_spec.h), the pass over lanes of different
+// sequences (kh_seq.h; kh_model_seq.hip drives it) and the
 // fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h).  The
 // reference feeds the prompt one token per forward pass (demo/main.cpp:20-22).
 // gfx950 only.
@@ -17,6 +18,7 @@
 #include "kh_pattn.h"
 #include "kh_prefill.h"
 #include "kh_score_plan.h"
+#include "kh_seq.h"
 #include "kh_spec.h"
 
 using namespace khm;
@@ -159,8 +161,10 @@ void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const f
   }
 }
 // forward of nvalid (<= B) prompt tokens at positions pos0.. : fills their K/V cache rows.  full_depth (scoring): the
-// last layer's attention, wo and FFN run too and pf_x holds the tokens' final residual vectors
-void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0, int B, bool full_depth = false) {
+// last layer's attention, wo and FFN run too and pf_x holds the tokens' final residual vectors.  row0: the cache row
+// of the sequence's position 0 (a sequence slot's first row; 0 for the batch-1 entry points)
+void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0, int B, bool full_depth = false,
+                          int row0 = 0) {
   const kh_config& c = m->cfg;
   const bool q = c.is_quant;
   KhPfTokens tk;
@@ -176,8 +180,8 @@ void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0
       a.wk = W.wk;
       a.wv = W.wv;
       a.Q = m->pf_q;
-      a.kcache_layer = m->kcache + (size_t)l * c.cache_len * c.kv_dim;
-      a.vcache_layer = m->vcache + (size_t)l * c.cache_len * c.kv_dim;
+      a.kcache_layer = m->kcache + ((size_t)l * c.cache_len + row0) * c.kv_dim;
+      a.vcache_layer = m->vcache + ((size_t)l * c.cache_len + row0) * c.kv_dim;
       a.sin_cache = m->sin_cache;
       a.cos_cache = m->cos_cache;
       a.dim = c.dim;
@@ -205,6 +209,8 @@ void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0
       a.ws = m->pf_ws;
       a.tok_stride = c.dim;
       a.ws_tok_bytes = m->pf_ws_tok_bytes;
+      a.kcache_layer += (size_t)row0 * c.kv_dim;
+      a.vcache_layer += (size_t)row0 * c.kv_dim;
       launch_attn_decode(a, pos0, m->attn_wg, m->stream, nvalid, pos0 + nvalid - 1);
     }
     pf_gemv_res(m, m->sh_wo, W.wo, m->pf_att, m->pf_x, c.dim, c.dim, nvalid, B);
@@ -271,6 +277,74 @@ void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0,
   t.rec_cap = m->lp_cap;
   launch_log("k_score_lp");
   hipLaunchKernelGGL(k_score_lp, dim3(nvalid), dim3(KH_SAMP_THREADS), 0, m->stream, t);
+}
+// ---- the pass over lanes of different sequences (kh_seq.h) --------------------------------------------------------
+// launch_prefill_chunk at full depth with the token, the RoPE row and the cache row of every lane taken from the lane
+// table: k_seq_embed, then per layer k_seq_qkv, k_seq_attn and the prefill kernels as they are.  The instantiations of
+// k_seq_qkv are k_pf_qkv's (PfB x PfQkvSP).
+void launch_seq_chunk(kh_model* m, const KhSeqLanes& lanes, int nvalid, int B) {
+  const kh_config& c = m->cfg;
+  const bool q = c.is_quant;
+  launch_log("k_seq_embed");
+  hipLaunchKernelGGL(k_seq_embed, dim3(B), dim3(KH_WG), 0, m->stream, (const int32_t*)m->d_seq_tok, lanes, nvalid,
+                     c.vocab_size, m->tok_emb, m->pf_x, c.dim);
+  for (int l = 0; l < c.layer_num; ++l) {
+    const LayerW& W = m->layers[l];
+    {
+      KhSeqQkvArgs sa;
+      KhPfQkvArgs& a = sa.a;
+      a.X = m->pf_x;
+      a.att_norm = W.att_norm;
+      a.wq = W.wq;
+      a.wk = W.wk;
+      a.wv = W.wv;
+      a.Q = m->pf_q;
+      a.kcache_layer = m->kcache + (size_t)l * c.cache_len * c.kv_dim;
+      a.vcache_layer = m->vcache + (size_t)l * c.cache_len * c.kv_dim;
+      a.sin_cache = m->sin_cache;
+      a.cos_cache = m->cos_cache;
+      a.dim = c.dim;
+      a.kv_dim = c.kv_dim;
+      a.head_size = c.head_size;
+      a.rope_mode = c.rope_mode;
+      a.gshift = m->gshift;
+      a.pos0 = 0;
+      a.nvalid = nvalid;
+      a.eps = c.rms_eps;
+      sa.lanes = lanes;
+      pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
+        pf_launch(KH_KERNEL(k_seq_qkv, Q, SP, BB), m->sh_qkv, pf_lds_bytes(Q, c.dim, BB), m->stream, sa);
+      });
+    }
+    {
+      KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
+      a.nsplit_g = m->attn_ns_g;  // launch_seq_attn decides from the lanes' positions
+      a.q = m->pf_q;
+      a.out = m->pf_att;
+      a.ws = m->pf_ws;
+      a.tok_stride = c.dim;
+      a.ws_tok_bytes = m->pf_ws_tok_bytes;
+      launch_seq_attn(a, lanes, nvalid, m->attn_wg, m->stream);
+    }
+    pf_gemv_res(m, m->sh_wo, W.wo, m->pf_att, m->pf_x, c.dim, c.dim, nvalid, B);
+    {
+      KhPfFfn13Args a;
+      a.X = m->pf_x;
+      a.ffn_norm = W.ffn_norm;
+      a.w1 = W.w1;
+      a.w3 = W.w3;
+      a.H = m->pf_h;
+      a.dim = c.dim;
+      a.hidden = c.hidden_dim;
+      a.gshift = m->gshift;
+      a.nvalid = nvalid;
+      a.eps = c.rms_eps;
+      pick_pf<PfB, PfNoSP>(q, 1, B, [&](auto Q, auto, auto BB) {
+        pf_launch(KH_KERNEL(k_pf_ffn13, Q, BB), m->sh_ffn, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
+      });
+    }
+    pf_gemv_res(m, m->sh_w2, W.w2, m->pf_h, m->pf_x, c.hidden_dim, c.dim, nvalid, B);
+  }
 }
 }  // namespace
 
@@ -735,6 +809,54 @@ int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0) {
   hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(KH_WG), 0, m->stream, t);
   KH_CHECK_HIP(hipMemcpyAsync(m->h_spec_pin, m->d_spec, sizeof(int32_t) * (size_t)(1 + n), hipMemcpyDeviceToHost,
                               m->stream));
+  return kh_launch_status();
+}
+
+// ---- sequence slots: what kh_model_seq.hip enqueues (kh_seq.h) -----------------------------------------------------
+int khm::seq_prepare(kh_model* m) {
+  int rc;
+  if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
+  if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
+  const size_t rows = (size_t)m->cfg.cache_len;
+  if (!m->d_seq_tok && (rc = dalloc(&m->d_seq_tok, (size_t)KH_SEQ_MAX_SLOTS)) != KH_OK) return rc;
+  if (!m->d_seq_samp && (rc = dalloc(&m->d_seq_samp, (size_t)KH_SEQ_MAX_SLOTS)) != KH_OK) return rc;
+  if (!m->d_seq_words && (rc = dalloc(&m->d_seq_words, rows)) != KH_OK) return rc;
+  if (!m->h_seq_tok_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_tok_pin, sizeof(int32_t) * KH_SEQ_MAX_SLOTS, hipHostMallocDefault));
+  if (!m->h_seq_samp_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_samp_pin, sizeof(KhSampParams) * KH_SEQ_MAX_SLOTS, hipHostMallocDefault));
+  if (!m->h_seq_words_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_words_pin, sizeof(int32_t) * rows, hipHostMallocDefault));
+  for (auto& e : m->ev_chunk)  // the stop check's events (ensure_pinned_words makes them for the batch-1 loops)
+    if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return (int)hipErrorUnknown;
+  return KH_OK;
+}
+int khm::seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0) {
+  const int B = prefill_batch(m);
+  for (int t0 = 0; t0 < n; t0 += B)
+    launch_prefill_chunk(m, toks + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B, /*full_depth=*/false, row0);
+  return kh_launch_status();
+}
+int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words) {
+  const kh_config& c = m->cfg;
+  const int B = prefill_batch(m);
+  for (int b = n; b < KH_SEQ_BMAX; ++b) {  // padding lanes rotate by the last valid lane's row; nothing of them is kept
+    lanes.pos[b] = lanes.pos[n - 1];
+    lanes.row[b] = lanes.row[n - 1];
+    lanes.slot[b] = lanes.slot[n - 1];
+  }
+  launch_seq_chunk(m, lanes, n, B);
+  launch_pf_cls(m, n, B);
+  KhSeqPickArgs t;
+  t.logits = m->pf_logits;
+  t.vocab = c.vocab_size;
+  t.vstride = m->pf_vstride;
+  t.lanes = lanes;
+  t.params = m->d_seq_samp;
+  t.tok = m->d_seq_tok;
+  t.words = words ? m->d_seq_words : nullptr;
+  launch_log("k_seq_pick");
+  hipLaunchKernelGGL(k_seq_pick, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, t);
   return kh_launch_status();
 }
 

@@ -1,0 +1,314 @@
+// kh_model_seq.hip — several independent sequences in one model: sequence slots of the K/V cache, the pass over lanes
+// of different sequences as an entry point (kh_model_seq_step) and the batched generate loop on top of it
+// (kh_model_generate_batch).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
+// seq_pass_enqueue; kernels in kh_seq.h, kh_attn.h).  The reference decodes one sequence per process
+// (demo/main.cpp:16-50); n samples of a prompt are n runs of that loop there.
+// gfx950 only.
+#include <limits.h>
+#include <string.h>
+
+#include <vector>
+
+#include "kh_model_internal.h"
+#include "kh_sample.h"
+#include "kh_seq_plan.h"
+
+using namespace khm;
+
+static_assert(KH_SEQ_SLOTS_MAX >= KH_SEQ_BMAX, "a pass never has more lanes than there can be slots");
+
+namespace {
+inline int slot_len(const kh_model* m) { return m->cfg.cache_len / m->seq_slots; }
+inline bool is_stop(int32_t t, const int32_t* stop, int n_stop) {
+  for (int i = 0; i < n_stop; ++i)
+    if (stop[i] == t) return true;
+  return false;
+}
+// what the seq entry points do not cover, as kh_model_generate_lookup: refused, never rerouted
+inline bool seq_unsupported(const kh_model* m) { return m->proc_on || m->lp_top_n >= 0 || !full_depth_supported(m); }
+// the per-slot tables of a call: token to feed and sampling parameters (NULL / temperature <= 0: greedy), staged in
+// pinned memory and uploaded on the model stream
+int upload_slot_tables(kh_model* m) {
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_seq_tok, m->h_seq_tok_pin, sizeof(int32_t) * KH_SEQ_SLOTS_MAX, hipMemcpyHostToDevice,
+                              m->stream));
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_seq_samp, m->h_seq_samp_pin, sizeof(KhSampParams) * KH_SEQ_SLOTS_MAX,
+                              hipMemcpyHostToDevice, m->stream));
+  return KH_OK;
+}
+void clear_slot_tables(kh_model* m) {
+  for (int s = 0; s < KH_SEQ_SLOTS_MAX; ++s) {
+    m->h_seq_tok_pin[s] = 0;
+    m->h_seq_samp_pin[s] = KhSampParams{0.f, 0, 1.f, 0u, 0u};
+  }
+}
+}  // namespace
+
+extern "C" int kh_plan_seq_slots(int32_t cache_len, int32_t n_slots, int32_t* slot_len_out) {
+  const int len = kh_seq_slot_len(cache_len, n_slots);
+  if (!len) return KH_ERR_INVALID_ARG;
+  if (slot_len_out) *slot_len_out = len;
+  return KH_OK;
+}
+
+extern "C" int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
+                                 int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes) {
+  if (n_seq <= 0 || n_seq > KH_SEQ_SLOTS_MAX || width <= 0 || width > KH_SEQ_BMAX || !first_pos || !total_steps ||
+      !n_passes || cap_passes < 0 || (cap_passes > 0 && !out_lanes))
+    return KH_ERR_INVALID_ARG;
+  for (int s = 0; s < n_seq; ++s)
+    if (first_pos[s] < 0 || total_steps[s] <= 0) return KH_ERR_INVALID_ARG;
+  int32_t pos[KH_SEQ_SLOTS_MAX], lanes[KH_SEQ_BMAX];
+  memcpy(pos, first_pos, sizeof(int32_t) * (size_t)n_seq);
+  int cursor = 0, passes = 0;
+  for (int n; (n = kh_seq_next_pass(n_seq, width, pos, total_steps, nullptr, &cursor, lanes)) > 0; ++passes) {
+    for (int i = 0; i < width; ++i) {
+      if (passes < cap_passes) out_lanes[(size_t)passes * width + i] = i < n ? lanes[i] : -1;
+      if (i < n) pos[lanes[i]] += 1;
+    }
+  }
+  *n_passes = passes;
+  return passes <= cap_passes ? KH_OK : KH_ERR_RANGE;
+}
+
+extern "C" int kh_model_seq_slots(kh_model* m, int32_t n_slots, int32_t* slot_len_out) {
+  if (!m) return KH_ERR_INVALID_ARG;
+  const int len = kh_seq_slot_len(m->cfg.cache_len, n_slots);
+  if (!len) return KH_ERR_INVALID_ARG;
+  m->seq_slots = n_slots;
+  if (slot_len_out) *slot_len_out = len;
+  return KH_OK;
+}
+
+extern "C" int kh_model_seq_width(const kh_model* m, int32_t* width) {
+  if (!m || !width) return KH_ERR_INVALID_ARG;
+  if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  *width = verify_width(m);
+  return KH_OK;
+}
+
+extern "C" int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_tokens, int32_t n, int32_t pos0) {
+  if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  const int len = slot_len(m);
+  if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > len) return KH_ERR_RANGE;
+  for (int i = 0; i < n; ++i)
+    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!prefill_supported(m)) return KH_ERR_UNSUPPORTED;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  int rc;
+  const int row0 = slot * len;
+  if ((rc = kv_ensure_rows(m, row0, row0 + pos0 + n)) != KH_OK) return rc;
+  if ((rc = seq_prepare(m)) != KH_OK) return rc;
+  return seq_prefill_enqueue(m, row0, h_tokens, n, pos0);
+}
+
+extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot, int32_t n_rows) {
+  if (!m || n_rows <= 0 || src_slot == dst_slot) return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  const int len = slot_len(m);
+  if (src_slot < 0 || src_slot >= m->seq_slots || dst_slot < 0 || dst_slot >= m->seq_slots || n_rows > len)
+    return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  int rc;
+  if ((rc = kv_ensure_rows(m, src_slot * len, src_slot * len + n_rows)) != KH_OK) return rc;
+  if ((rc = kv_ensure_rows(m, dst_slot * len, dst_slot * len + n_rows)) != KH_OK) return rc;
+  const size_t nb = (size_t)n_rows * c.kv_dim * sizeof(float);
+  for (int l = 0; l < c.layer_num; ++l) {
+    const size_t so = ((size_t)l * c.cache_len + (size_t)src_slot * len) * c.kv_dim;
+    const size_t dof = ((size_t)l * c.cache_len + (size_t)dst_slot * len) * c.kv_dim;
+    KH_CHECK_HIP(hipMemcpyAsync(m->kcache + dof, m->kcache + so, nb, hipMemcpyDeviceToDevice, m->stream));
+    KH_CHECK_HIP(hipMemcpyAsync(m->vcache + dof, m->vcache + so, nb, hipMemcpyDeviceToDevice, m->stream));
+  }
+  return KH_OK;
+}
+
+// One pass.  Eager launches on the model stream; every check before the first of them.
+extern "C" int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens,
+                                 const int32_t* pos, const kh_sampling* samplings, int32_t* h_next) {
+  if (!m || !slots || !h_tokens || !pos || !h_next || n <= 0) return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  if (seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
+  if (n > verify_width(m)) return KH_ERR_RANGE;
+  const int len = slot_len(m);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= m->seq_slots || pos[i] < 0 || pos[i] >= len || h_tokens[i] < 0 ||
+        h_tokens[i] >= c.vocab_size)
+      return KH_ERR_RANGE;
+    for (int j = 0; j < i; ++j)
+      if (slots[j] == slots[i]) return KH_ERR_INVALID_ARG;  // two lanes of one sequence cannot share a pass
+    if (samplings && !kh_sampling_valid(&samplings[i])) return KH_ERR_INVALID_ARG;
+  }
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  int rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = kv_ensure_rows(m, slots[i] * len, slots[i] * len + pos[i] + 1)) != KH_OK) return rc;
+  if ((rc = seq_prepare(m)) != KH_OK) return rc;
+  clear_slot_tables(m);
+  KhSeqLanes lanes;
+  for (int i = 0; i < n; ++i) {
+    lanes.pos[i] = pos[i];
+    lanes.row[i] = slots[i] * len + pos[i];
+    lanes.slot[i] = slots[i];
+    m->h_seq_tok_pin[slots[i]] = h_tokens[i];
+    if (samplings && !kh_sampling_greedy(&samplings[i])) m->h_seq_samp_pin[slots[i]] = kh_samp_params(&samplings[i]);
+  }
+  rc = upload_slot_tables(m);
+  if (rc == KH_OK) rc = seq_pass_enqueue(m, lanes, n, /*words=*/false);
+  if (rc == KH_OK)
+    rc = (int)hipMemcpyAsync(m->h_seq_tok_pin, m->d_seq_tok, sizeof(int32_t) * KH_SEQ_SLOTS_MAX, hipMemcpyDeviceToHost,
+                             m->stream);
+  const hipError_t e = hipStreamSynchronize(m->stream);  // drained on every way out
+  if (rc != KH_OK) return rc;
+  if (e != hipSuccess) return (int)e;
+  for (int i = 0; i < n; ++i) h_next[i] = m->h_seq_tok_pin[slots[i]];
+  return KH_OK;
+}
+
+// kh_model_generate_until for n_seq sequences at once, sequence s in slot s.  The fed-only part of every prompt runs
+// as kh_model_seq_prefill's passes; the sampled part as passes of up to `width` lanes, enqueued eagerly (the picks
+// feed the next pass on the device).  With a stop list the words of every 8 passes are mirrored into pinned memory
+// behind them and inspected while the next 8 are queued: generate_until's check, with its contract that what ran
+// past a stop is discarded.
+extern "C" int kh_model_generate_batch(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                                       const int32_t* total_steps, const kh_sampling* samplings, const int32_t* h_stop,
+                                       int32_t n_stop, int32_t* h_words, int32_t words_stride, int32_t* n_words,
+                                       float* h_elapsed_ms) {
+  return kh_model_generate_batch_from(m, n_seq, h_prompts, n_prompt, nullptr, total_steps, samplings, h_stop, n_stop,
+                                      h_words, words_stride, n_words, h_elapsed_ms);
+}
+// ... with the first n_cached[s] positions of sequence s already in its slot's rows (kh_model_seq_prefill,
+// kh_model_seq_fork): the call feeds the rest of the prompt
+extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const int32_t* h_prompts,
+                                            const int32_t* n_prompt, const int32_t* n_cached,
+                                            const int32_t* total_steps, const kh_sampling* samplings,
+                                            const int32_t* h_stop, int32_t n_stop, int32_t* h_words,
+                                            int32_t words_stride, int32_t* n_words, float* h_elapsed_ms) {
+  if (!m || !h_prompts || !n_prompt || !total_steps || !h_words || !n_words || n_seq <= 0 || words_stride <= 0 ||
+      n_stop < 0 || (n_stop > 0 && !h_stop))
+    return KH_ERR_INVALID_ARG;
+  const kh_config& c = m->cfg;
+  const int len = slot_len(m);
+  if (n_seq > m->seq_slots) return KH_ERR_RANGE;
+  size_t n_tok = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    if (n_prompt[s] <= 0 || total_steps[s] <= 0 || total_steps[s] > words_stride) return KH_ERR_INVALID_ARG;
+    if (total_steps[s] > len) return KH_ERR_RANGE;
+    if (samplings && !kh_sampling_valid(&samplings[s])) return KH_ERR_INVALID_ARG;
+    // only fed-only positions can be cached: the last prompt token's logits are the first pick's
+    if (n_cached && (n_cached[s] < 0 || n_cached[s] > n_prompt[s] - 1 || n_cached[s] > total_steps[s]))
+      return KH_ERR_INVALID_ARG;
+    n_tok += (size_t)n_prompt[s];
+  }
+  for (size_t i = 0; i < n_tok; ++i)
+    if (h_prompts[i] < 0 || h_prompts[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
+  return kh_api_guard([&]() -> int {
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    int rc;
+    for (int s = 0; s < n_seq; ++s) {
+      n_words[s] = 0;
+      if ((rc = kv_ensure_rows(m, s * len, s * len + total_steps[s])) != KH_OK) return rc;
+    }
+    if ((rc = seq_prepare(m)) != KH_OK) return rc;
+    // every early return below may leave launches and copies into pinned memory in flight: drain first
+    auto fail = [&](int code) -> int {
+      (void)hipStreamSynchronize(m->stream);
+      return code;
+    };
+    const int width = verify_width(m);
+    std::vector<const int32_t*> prompt((size_t)n_seq);
+    // pos[s]: the next position sequence s feeds in a pass; copied / checked: how far its words were mirrored / read
+    std::vector<int32_t> pos((size_t)n_seq), copied((size_t)n_seq), checked((size_t)n_seq), stop_at((size_t)n_seq, -1);
+    std::vector<uint8_t> stopped((size_t)n_seq, 0);
+    clear_slot_tables(m);
+    {
+      const int32_t* p = h_prompts;
+      for (int s = 0; s < n_seq; ++s) {
+        prompt[s] = p;
+        p += n_prompt[s];
+        const int fed = n_prompt[s] - 1 < total_steps[s] ? n_prompt[s] - 1 : total_steps[s];  // fed-only positions
+        pos[s] = copied[s] = checked[s] = fed;
+        m->h_seq_tok_pin[s] = prompt[s][fed];  // fed <= n_prompt - 1
+        if (samplings && !kh_sampling_greedy(&samplings[s])) m->h_seq_samp_pin[s] = kh_samp_params(&samplings[s]);
+      }
+    }
+    if ((rc = upload_slot_tables(m)) != KH_OK) return fail(rc);
+    if (hipEventRecord(m->ev0, m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
+    for (int s = 0; s < n_seq; ++s) {
+      const int have = n_cached ? n_cached[s] : 0;
+      if (pos[s] > have && (rc = seq_prefill_enqueue(m, s * len, prompt[s] + have, pos[s] - have, have)) != KH_OK)
+        return fail(rc);
+    }
+    int32_t* const pin = m->h_seq_words_pin;
+    struct Chunk {
+      std::vector<int32_t> upto;
+    };
+    Chunk infl[2];
+    int n_infl = 0, head = 0, cursor = 0;
+    // the words the passes so far have written, into the pinned mirror; an event behind the copies
+    auto mirror = [&]() -> int {
+      for (int s = 0; s < n_seq; ++s)
+        if (pos[s] > copied[s]) {
+          const size_t at = (size_t)s * len + copied[s];
+          if (hipMemcpyAsync(pin + at, m->d_seq_words + at, sizeof(int32_t) * (size_t)(pos[s] - copied[s]),
+                             hipMemcpyDeviceToHost, m->stream) != hipSuccess)
+            return (int)hipErrorUnknown;
+          copied[s] = pos[s];
+        }
+      const int slot = (head + n_infl) & 1;
+      if (hipEventRecord(m->ev_chunk[slot], m->stream) != hipSuccess) return (int)hipErrorUnknown;
+      infl[slot].upto = pos;
+      ++n_infl;
+      return KH_OK;
+    };
+    // wait for the oldest mirror and read it: a sequence whose word is a stop token leaves the lane table here
+    auto retire = [&]() -> int {
+      if (hipEventSynchronize(m->ev_chunk[head]) != hipSuccess) return (int)hipErrorUnknown;
+      for (int s = 0; s < n_seq; ++s) {
+        for (int p = checked[s]; p < infl[head].upto[s] && !stopped[s]; ++p)
+          if (is_stop(pin[(size_t)s * len + p], h_stop, n_stop)) {
+            stop_at[s] = p;
+            stopped[s] = 1;
+          }
+        checked[s] = infl[head].upto[s];
+      }
+      head ^= 1;
+      --n_infl;
+      return KH_OK;
+    };
+    const int per_check = n_stop > 0 ? KH_GRAPH_STEPS : INT_MAX;
+    for (;;) {
+      int k = 0;
+      while (k < per_check) {
+        int32_t who[KH_SEQ_BMAX];
+        const int n = kh_seq_next_pass(n_seq, width, pos.data(), total_steps, stopped.data(), &cursor, who);
+        if (n == 0) break;
+        KhSeqLanes lanes;
+        for (int i = 0; i < n; ++i) {
+          lanes.pos[i] = pos[who[i]];
+          lanes.row[i] = who[i] * len + pos[who[i]];
+          lanes.slot[i] = who[i];
+          pos[who[i]] += 1;
+        }
+        if ((rc = seq_pass_enqueue(m, lanes, n, /*words=*/true)) != KH_OK) return fail(rc);
+        ++k;
+      }
+      if (k > 0 && (rc = mirror()) != KH_OK) return fail(rc);
+      if (n_infl == 2 || (k == 0 && n_infl > 0))
+        if ((rc = retire()) != KH_OK) return fail(rc);
+      if (k == 0 && n_infl == 0) break;
+    }
+    if (hipEventRecord(m->ev1, m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
+    if ((rc = kh_launch_status()) != KH_OK) return fail(rc);
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    for (int s = 0; s < n_seq; ++s) {
+      const int n_out = stop_at[s] >= 0 ? stop_at[s] : total_steps[s];
+      int32_t* w = h_words + (size_t)s * words_stride;
+      for (int p = 0; p < n_out; ++p)
+        w[p] = p < n_prompt[s] - 1 ? prompt[s][p + 1] : pin[(size_t)s * len + p];  // forced, main.cpp:36-38
+      n_words[s] = n_out;
+    }
+    if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
+    return KH_OK;
+  });
+}

@@ -17,6 +17,8 @@
 //   * epilogues (bias, RoPE, SwiGLU, residual) are the same expressions;
 //   * attention is the decode kernel itself, one grid slice per token.
 // tests/test_model_gpu.py::test_prefill_* compares cache rows and the following logits bit for bit.
+// The B tokens of a pass need not be consecutive positions of one sequence: kh_seq.h runs the same pass over lanes
+// that belong to different sequences (k_seq_qkv instantiates pf_qkv_body below with its own addressing).
 #pragma once
 #include "kh_fused.h"
 
@@ -322,10 +324,19 @@ struct KhPfQkvArgs {
   int pos0, nvalid;       // token b sits at position pos0 + b; tokens >= nvalid are padding
   float eps;
 };
-template <bool QUANT, int SPLIT, int B>
-__global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv(const KhPfQkvArgs a) {
+// Where token b of a pass sits: pos(b) = its position (the RoPE row), row(b) = its K/V cache row.  PfRunAddr: the B
+// consecutive positions of one sequence whose position p is cache row p (prefill, scoring, verify); kh_seq.h has the
+// policy of lanes that belong to different sequences.  pos() is asked for every b < B (padding tokens rotate by the
+// last valid token's row, their results are dropped), row() for valid tokens only.
+struct PfRunAddr {
+  int pos0, nvalid;
+  __device__ __forceinline__ int pos(int b) const { return pos0 + (b < nvalid ? b : nvalid - 1); }
+  __device__ __forceinline__ int row(int b) const { return pos0 + b; }
+};
+// the body of k_pf_qkv, shared with k_seq_qkv (kh_seq.h)
+template <bool QUANT, int SPLIT, int B, class Addr>
+__device__ __forceinline__ void pf_qkv_body(const KhPfQkvArgs& a, const Addr& addr, char* smem_raw) {
   constexpr int U = KH_PF_U(QUANT);
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const void *wq_w = a.wq.w, *wk_w = a.wk.w, *wv_w = a.wv.w;
   const float *wq_s = a.wq.scales, *wk_s = a.wk.scales, *wv_s = a.wv.scales;
   const float *wq_b = a.wq.bias, *wk_b = a.wk.bias, *wv_b = a.wv.bias;
@@ -337,7 +348,7 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv(const KhPfQkvArgs a) {
   const float* const X = a.X;
   const float* const att_norm = a.att_norm;
   const int dim = a.dim, kv_dim = a.kv_dim, rope_mode = a.rope_mode;
-  const int pos0 = a.pos0, nvalid = a.nvalid;
+  const int nvalid = a.nvalid;
   const float eps = a.eps;
   f32x4* xs = (f32x4*)smem_raw;
   const int xstride = pf_xstride<QUANT>(dim);
@@ -388,7 +399,7 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv(const KhPfQkvArgs a) {
     Aux x;
 #pragma unroll
     for (int b = 0; b < B; ++b) {
-      const int pos = pos0 + (b < nvalid ? b : nvalid - 1);
+      const int pos = addr.pos(b);
       x.fci[b] = sin_cache[(size_t)pos * hs + cidx];
       x.fcr[b] = cos_cache[(size_t)pos * hs + cidx];
     }
@@ -406,7 +417,7 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv(const KhPfQkvArgs a) {
     for (int b = 0; b < B; ++b) {
       if (b >= nvalid) break;
       float v0 = rs[b] * s0[b] + x.b0, v1 = rs[b] * s1[b] + x.b1;
-      const size_t row = (size_t)(pos0 + b) * kv_dim;
+      const size_t row = (size_t)addr.row(b) * kv_dim;
       float* dst = sel3(which, Qo + (size_t)b * dim, kc + row, vc + row);
       if (which < 2) {
         const float t0 = v0, t1 = v1;
@@ -423,6 +434,11 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv(const KhPfQkvArgs a) {
         pf_stage_norm<QUANT, B>(X, (size_t)dim, att_norm, xs, xstride, dim, eps, red, rs);
       },
       epi);
+}
+template <bool QUANT, int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv(const KhPfQkvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_qkv_body<QUANT, SPLIT, B>(a, PfRunAddr{a.pos0, a.nvalid}, smem_raw);
 }
 
 struct KhPfFfn13Args {

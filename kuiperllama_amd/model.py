@@ -26,6 +26,44 @@ def _i32_array(tokens):
     return (C.c_int32 * max(len(tokens), 1))(*[int(t) for t in tokens])
 
 
+def _sampling_array(samplings, n: int, what: str):
+    """[n] kh_sampling from a list of None (greedy) | dict of _ffi.sampling()'s fields | _ffi.Sampling; None stays None"""
+    if samplings is None:
+        return None
+    samplings = list(samplings)
+    if len(samplings) != n:
+        raise ValueError(f"{what}: {len(samplings)} sampling entries for {n} sequences")
+    arr = (_ffi.Sampling * max(n, 1))()
+    for i, sp in enumerate(samplings):
+        v = _ffi.sampling() if sp is None else sp if isinstance(sp, _ffi.Sampling) else _ffi.sampling(**sp)
+        arr[i] = _ffi.Sampling(v.temperature, v.top_k, v.top_p, v.seed)
+    return arr
+
+
+def plan_seq_slots(cache_len: int, n_slots: int) -> int:
+    """slot_len of a cache of cache_len rows cut into n_slots sequence slots (kh_plan_seq_slots; host only)."""
+    out = C.c_int32(0)
+    _ffi.check(_ffi.lib().kh_plan_seq_slots(int(cache_len), int(n_slots), C.byref(out)), "kh_plan_seq_slots")
+    return int(out.value)
+
+
+def plan_seq_batch(first_pos: Sequence[int], total_steps: Sequence[int], width: int) -> List[List[int]]:
+    """The passes generate_batch runs while no sequence stops early (kh_plan_seq_batch; host only): per pass the
+    sequences in its lanes.  first_pos[s] = len(prompt s) - 1, the first position a pass feeds."""
+    first_pos, total_steps = list(first_pos), list(total_steps)
+    if len(first_pos) != len(total_steps):
+        raise ValueError(f"plan_seq_batch: {len(first_pos)} positions for {len(total_steps)} totals")
+    n, L = C.c_int32(0), _ffi.lib()
+    rc = L.kh_plan_seq_batch(len(first_pos), int(width), _i32_array(first_pos), _i32_array(total_steps), None, 0,
+                             C.byref(n))
+    if rc not in (0, _ffi.KH_ERR_RANGE):
+        raise _ffi.KhError(rc, "kh_plan_seq_batch")
+    out = (C.c_int32 * max(n.value * int(width), 1))()
+    _ffi.check(L.kh_plan_seq_batch(len(first_pos), int(width), _i32_array(first_pos), _i32_array(total_steps), out,
+                                   n.value, C.byref(n)), "kh_plan_seq_batch")
+    return [[int(x) for x in out[p * width:(p + 1) * width] if x >= 0] for p in range(n.value)]
+
+
 def lookup_draft(seq: Sequence[int], hint: Optional[Sequence[int]] = None, ngram_max: int = 4, ngram_min: int = 1,
                  cap: int = 7) -> List[int]:
     """The drafter of generate_lookup (kh_lookup_draft; host only, no device): up to `cap` tokens that followed the
@@ -386,6 +424,77 @@ class KuiperModel:
                                                        _i32_array(st), len(st), C.byref(opts), words, C.byref(n),
                                                        C.byref(ms), C.byref(stats)), "kh_model_generate_lookup")
         return list(words[: n.value]), float(ms.value), stats.as_dict()
+
+    # ---- sequence slots: several independent sequences per pass over the weights ---------------------------------
+    def seq_slots(self, n_slots: int) -> int:
+        """Cut the cache rows into n_slots equal sequence slots (kh_model_seq_slots); returns slot_len.  Slot s is
+        rows [s * slot_len, (s + 1) * slot_len): read_kv(layer, s * slot_len + p, ..) is position p of its sequence."""
+        out = C.c_int32(0)
+        _ffi.check(_ffi.lib().kh_model_seq_slots(self._h, int(n_slots), C.byref(out)), "kh_model_seq_slots")
+        return int(out.value)
+
+    def seq_width(self) -> int:
+        """Lanes (sequences) per pass of this model (kh_model_seq_width): 8 for fp32, 4 for int8 and wide fp32."""
+        w = C.c_int32(0)
+        _ffi.check(_ffi.lib().kh_model_seq_width(self._h, C.byref(w)), "kh_model_seq_width")
+        return int(w.value)
+
+    def seq_prefill(self, slot: int, tokens: Sequence[int], pos0: int = 0) -> None:
+        """prefill() on the rows of sequence slot `slot` (kh_model_seq_prefill)."""
+        _ffi.check(_ffi.lib().kh_model_seq_prefill(self._h, int(slot), _i32_array(tokens), len(tokens), int(pos0)),
+                   "kh_model_seq_prefill")
+        torch.cuda.synchronize()
+
+    def seq_fork(self, src_slot: int, dst_slot: int, n_rows: int) -> None:
+        """Copy K/V rows [0, n_rows) of every layer from one slot to another (kh_model_seq_fork)."""
+        _ffi.check(_ffi.lib().kh_model_seq_fork(self._h, int(src_slot), int(dst_slot), int(n_rows)),
+                   "kh_model_seq_fork")
+        torch.cuda.synchronize()
+
+    def seq_step(self, slots: Sequence[int], tokens: Sequence[int], pos: Sequence[int],
+                 samplings: Optional[Sequence] = None) -> List[int]:
+        """One pass over len(slots) <= seq_width() lanes in distinct slots (kh_model_seq_step): lane i feeds tokens[i]
+        at position pos[i] of slot slots[i]; returns the picks - greedy, or sampled where samplings[i] (None | dict of
+        temperature / top_k / top_p / seed) has a temperature > 0 - exactly a predict loop's on a batch-1 model."""
+        slots, tokens, pos = list(slots), list(tokens), list(pos)
+        n = len(slots)
+        if len(tokens) != n or len(pos) != n:
+            raise ValueError(f"seq_step: {n} slots, {len(tokens)} tokens, {len(pos)} positions")
+        sp = _sampling_array(samplings, n, "seq_step")
+        nxt = (C.c_int32 * max(n, 1))()
+        _ffi.check(_ffi.lib().kh_model_seq_step(self._h, n, _i32_array(slots), _i32_array(tokens), _i32_array(pos), sp,
+                                                nxt), "kh_model_seq_step")
+        return list(nxt[:n])
+
+    def generate_batch(self, prompts: Sequence[Sequence[int]], total_steps, samplings: Optional[Sequence] = None,
+                       stop: Sequence[int] = (), cached: Optional[Sequence[int]] = None) -> Tuple[List[List[int]], float]:
+        """generate() for len(prompts) <= n_slots sequences at once, sequence s in slot s (kh_model_generate_batch):
+        seq_width() sequences share every pass over the weights.  total_steps: one int for all or one per sequence;
+        samplings: None (all greedy) or one entry per sequence (None | dict of temperature / top_k / top_p / seed).
+        cached: None, or per sequence how many leading prompt positions seq_prefill / seq_fork already left in its
+        slot (kh_model_generate_batch_from).  Returns (words per sequence, elapsed_ms); every word list is exactly
+        generate(prompt, total, stop=stop)'s on a batch-1 model with that entry set through set_sampling()."""
+        prompts = [list(p) for p in prompts]
+        n = len(prompts)
+        totals = [int(total_steps)] * n if isinstance(total_steps, (int, np.integer)) else [int(t) for t in total_steps]
+        if len(totals) != n:
+            raise ValueError(f"generate_batch: {len(totals)} totals for {n} prompts")
+        if n == 0 or any(len(p) == 0 for p in prompts):
+            raise ValueError("generate_batch: no prompt, or an empty one")
+        sp = _sampling_array(samplings, n, "generate_batch")
+        if cached is not None and len(cached) != n:
+            raise ValueError(f"generate_batch: {len(cached)} cached counts for {n} prompts")
+        st = list(stop or [])
+        stride = max(max(totals), 1)
+        words = (C.c_int32 * (n * stride))()
+        nw = (C.c_int32 * n)()
+        ms = C.c_float(0.0)
+        flat = [t for p in prompts for t in p]
+        _ffi.check(_ffi.lib().kh_model_generate_batch_from(
+            self._h, n, _i32_array(flat), _i32_array([len(p) for p in prompts]),
+            None if cached is None else _i32_array(cached), _i32_array(totals), sp, _i32_array(st), len(st), words,
+            stride, nw, C.byref(ms)), "kh_model_generate_batch")
+        return [list(words[s * stride:s * stride + nw[s]]) for s in range(n)], float(ms.value)
 
     def prefill_gemm(self, tokens: Sequence[int], pos0: int = 0) -> None:
         """Forward of `tokens` at positions pos0.. as fp32-MFMA GEMMs (up to 128 tokens per weight

@@ -16,7 +16,7 @@
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
-//               [--lookup [ngram_max]] [--hint id,id,...]
+//               [--lookup [ngram_max]] [--hint id,id,...] [--parallel N]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -35,6 +35,10 @@
 // the weights wherever the text so far - or --hint id,id,..., the expected output - predicts the next tokens (n-grams
 // of up to ngram_max tokens, default 4).  Greedy only.  A line "lookup: passes P drafted D accepted A plain_steps S"
 // follows the words.
+// --parallel N: N samples of the one prompt, decoded together (kh_model_seq_slots / _seq_prefill / _seq_fork /
+// kh_model_generate_batch_from): the cache is cut into N slots, the prompt is prefilled once and forked, the seeds are
+// --seed, --seed + 1, ...; each sequence's ids are printed on a line of their own, then the aggregate "steps/s".
+// Greedy without --temperature (N equal lines).  Penalties, bias and log-probs are refused, as by the library.
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <cmath>
 #include <chrono>
@@ -55,7 +59,7 @@ static void usage() {
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
-               "       [--lookup [ngram_max]] [--hint id,id,...]\n");
+               "       [--lookup [ngram_max]] [--hint id,id,...] [--parallel N]\n");
 }
 
 int main(int argc, char** argv) {
@@ -74,6 +78,7 @@ int main(int argc, char** argv) {
   bool score = false;  // --score (kh_model_score)
   bool lookup = false;  // --lookup [ngram_max] (kh_model_generate_lookup)
   kh_lookup_opts lk{0, 0, 0, nullptr, 0};
+  int parallel = 0;  // --parallel N (kh_model_generate_batch)
   std::vector<int32_t> hint;  // --hint
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
@@ -112,6 +117,7 @@ int main(int argc, char** argv) {
     else if (a == "--repeat-last-n") pen.last_n = std::atoi(next());
     else if (a == "--logprobs") logprobs = std::atoi(next());
     else if (a == "--score") score = true;
+    else if (a == "--parallel") parallel = std::atoi(next());
     else if (a == "--lookup") {
       lookup = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') lk.ngram_max = std::atoi(argv[++i]);
@@ -269,6 +275,49 @@ int main(int argc, char** argv) {
       std::printf("\n");
     }
     std::printf("sum_logprob:%.6f\nperplexity:%.6f\n", sum, cnt > 1 ? std::exp(-sum / (cnt - 1)) : std::nan(""));
+    if (tok) kh_spm_destroy(tok);
+    if (bpe) kh_bpe_destroy(bpe);
+    kh_model_destroy(m);
+    return 0;
+  }
+  if (parallel > 0) {
+    // N samples of the prompt: one prefill, N - 1 forks, then all sequences share every pass over the weights
+    int32_t slot_len = 0, width = 0;
+    const int32_t np = (int32_t)prompt.size();
+    const int32_t have = np - 1 < steps ? np - 1 : steps;  // fed-only positions: prefilled once, forked
+    std::vector<int32_t> prompts, n_prompt((size_t)parallel, np), cached((size_t)parallel, have),
+        totals((size_t)parallel, steps), n_out((size_t)parallel, 0), out((size_t)parallel * (size_t)(steps > 0 ? steps : 1));
+    std::vector<kh_sampling> samps((size_t)parallel, samp);
+    for (int s = 0; s < parallel; ++s) {
+      prompts.insert(prompts.end(), prompt.begin(), prompt.end());
+      samps[(size_t)s].seed = samp.seed + (uint64_t)s;
+    }
+    float ms = 0.f;
+    std::printf("Generating...\n");
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = kh_model_seq_slots(m, parallel, &slot_len);
+    if (rc == KH_OK) rc = kh_model_seq_width(m, &width);
+    if (rc == KH_OK && have > 0) rc = kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
+    for (int s = 1; s < parallel && rc == KH_OK && have > 0; ++s) rc = kh_model_seq_fork(m, 0, s, have);
+    if (rc == KH_OK)
+      rc = kh_model_generate_batch_from(m, parallel, prompts.data(), n_prompt.data(), cached.data(), totals.data(),
+                                        samps.data(), stop.data(), (int32_t)stop.size(), out.data(), steps,
+                                        n_out.data(), &ms);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (rc != KH_OK) {
+      std::fprintf(stderr, "--parallel %d failed: %d (%s)\n", parallel, rc, kh_error_string(rc));
+      kh_model_destroy(m);
+      return 1;
+    }
+    std::fprintf(stderr, "parallel: %d slots of %d rows, %d lanes per pass\n", parallel, slot_len, width);
+    long total = 0;
+    for (int s = 0; s < parallel; ++s) {
+      for (int i = 0; i < n_out[(size_t)s]; ++i) std::printf("%d ", out[(size_t)s * steps + i]);
+      std::printf("\n");
+      total += n_out[(size_t)s];
+    }
+    std::printf("steps/s:%lf\n", (double)total / std::chrono::duration<double>(t1 - t0).count());
+    std::fprintf(stderr, "(device time of the passes: %.3f ms)\n", ms);
     if (tok) kh_spm_destroy(tok);
     if (bpe) kh_bpe_destroy(bpe);
     kh_model_destroy(m);
