@@ -676,6 +676,12 @@ int kh_plan_decode_ring(int32_t dim, int32_t hidden_dim, int32_t vocab_size, int
  * workgroups that own timesteps at `pos`} (KH_ATTN_TLONG, KH_ATTN_TS and KH_ATTN_WG honoured). */
 int kh_plan_attention(int32_t head_num, int32_t kv_mul, int32_t head_size, int32_t seq_len, int32_t pos,
                       int32_t* out8);
+/* kh_plan_attention_launch: ONE decode-attention launch over the tokens at positions pos[0 .. n) of that geometry (a
+ * prefill slice, the lanes of a pass over sequence slots); n = 0: the position is a device word (a decode step).
+ * out6 = {lanes per timestep G, heads per KV-group workgroup KVM (0 = per-head only) of the kernel instantiation,
+ * grid.x, dynamic LDS bytes, per-head splits, group splits the grid carries} (same hooks). */
+int kh_plan_attention_launch(int32_t head_num, int32_t kv_mul, int32_t head_size, int32_t seq_len,
+                             const int32_t* pos, int32_t n, int32_t* out6);
 int kh_plan_prefill_shape(int32_t epi, int32_t T, int32_t rows, int32_t K, int32_t is_quant,
                           int32_t r2_ok, int32_t* out7);
 

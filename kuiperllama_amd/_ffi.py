@@ -27,7 +27,7 @@ EXPORTS = [
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
     "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
-    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_seq_slots", "kh_plan_seq_batch",
+    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
 ]
 
@@ -201,6 +201,7 @@ def lib() -> C.CDLL:
     L.kh_plan_decode_ring.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]
     L.kh_plan_prefill_shape.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]
     L.kh_plan_attention.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]
+    L.kh_plan_attention_launch.argtypes = [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32)]
     L.kh_spm_create_from_file.argtypes = [C.c_char_p, C.POINTER(_vp)]
     L.kh_spm_create_from_memory.argtypes = [_vp, C.c_int64, C.POINTER(_vp)]
     L.kh_spm_destroy.argtypes = [_vp]
@@ -376,6 +377,19 @@ def plan_attention(head_num: int, kv_mul: int, head_size: int, seq_len: int, pos
         raise KhError(rc, "kh_plan_attention")
     return dict(zip(("ns", "ns_g", "stride", "t_long", "group_path", "active_splits", "split_len", "workgroups"),
                     list(out)))
+
+
+def plan_attention_launch(head_num: int, kv_mul: int, head_size: int, seq_len: int, positions) -> dict:
+    """One decode-attention launch over the tokens at `positions` (empty: a device-positioned launch) of the geometry
+    of plan_attention (host-only, kh_plan_attention_launch)."""
+    sync_env()
+    n = len(positions)
+    pos = (_i32 * max(n, 1))(*positions)
+    out = (_i32 * 6)()
+    rc = lib().kh_plan_attention_launch(head_num, kv_mul, head_size, seq_len, pos, n, out)
+    if rc != 0:
+        raise KhError(rc, "kh_plan_attention_launch")
+    return dict(zip(("G", "KVM", "grid", "lds", "head_splits", "group_splits"), list(out)))
 
 
 def plan_prefill_shape(epi: str, T: int, rows: int, K: int, quant: bool, r2_ok: bool = True) -> dict:

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "kh_common.h"
+#include "kh_dispatch.h"
 
 #define KH_ATTN_TC 2048  // timesteps per LDS score chunk (8 KiB)
 
@@ -880,8 +881,10 @@ __device__ __forceinline__ void attn_group_decode(const float* q_g, const float*
 }
 
 // =============================================================================================
-// The decode-attention launch shared by the fused step (kh_model_step.hip) and the operator-level
-// entry point kh_mha_decode_f32 (kh_ops.hip).
+// The decode-attention launch shared by the fused step (kh_model_step.hip), the operator-level entry point
+// kh_mha_decode_f32 (kh_ops.hip) and the B-token pass (kh_model_prefill.hip): two kernels that differ in where a
+// slice's position and cache rows come from (k_attn_decode, k_seq_attn) over one slice body, one launch plan
+// (attn_launch_plan) and one instantiation table (attn_pick).
 struct KhAttnArgs {
   const float* q;          // [dim]
   const float* kcache_layer;
@@ -901,7 +904,7 @@ struct KhAttnArgs {
   // out rows tok_stride floats apart, its split workspace ws_tok_bytes apart (decode: y = 1)
   int tok_stride;
   size_t ws_tok_bytes;
-  int kvh_shift, kvm_shift;  // log2 of kv_heads / kv_mul when they are powers of two, else -1 (set by launch_attn_decode)
+  int kvh_shift, kvm_shift;  // log2 of kv_heads / kv_mul when they are powers of two, else -1 (attn_launch_plan)
 };
 
 // per-head path: block -> (kv group g, head-in-group j, split s).  Blocks are placed on XCD
@@ -929,11 +932,43 @@ __device__ __forceinline__ void attn_head_block(const KhAttnArgs& a, float* smem
       a.fenced != 0, a.ts_shift);
 }
 
+// The lanes of a B-token pass that belong to DIFFERENT sequences (kh_seq.h, kh_model_seq_step): lane b is a token at
+// position pos[b] of a sequence whose position 0 is cache row row[b] - pos[b] (a sequence slot of the model's cache).
+// The host knows both, so they travel by value.
+struct KhSeqLanes {
+  int32_t pos[KH_PF_BMAX];  // position of the lane's token in its sequence
+  int32_t row[KH_PF_BMAX];  // its cache row: the slot's first row + pos
+  int32_t slot[KH_PF_BMAX]; // its sequence slot: the entry of the per-slot device tables (token to feed, sampler)
+};
+
+// One slice (one token at position pos, a.q / a.out / a.ws / the cache bases already its own) of a decode-attention
+// launch: the body of k_attn_decode and k_seq_attn behind their address prologues.
 // KVM = 0: per-head workgroups only.  KVM = kv_mul > 1: per-head workgroups at short contexts,
 // one workgroup per (kv group, split) computing the group's KVM heads from one pass over K/V
-// once pos + 1 >= t_long.  The choice is uniform over the grid (it depends on the position
+// once pos + 1 >= t_long.  The choice is uniform over the slice (it depends on the position
 // only), so one captured launch serves every position; workgroups beyond the active path's
 // count leave immediately.
+template <int G, int KVM>
+__device__ __forceinline__ void attn_slice_body(const KhAttnArgs& a, int pos, char* smem_raw) {
+  const int b = (int)blockIdx.x;
+  if (KVM == 0 || pos + 1 < a.t_long) {
+    if (b < a.kv_heads * a.kv_mul * a.nsplit) attn_head_block<G>(a, (float*)smem_raw, b, pos);
+    return;
+  }
+  if constexpr (KVM > 0) {
+    if (b >= a.kv_heads * a.nsplit_g) return;
+    const int g = b % a.kv_heads, s = b / a.kv_heads;
+    const size_t head_off = (size_t)g * a.head_size;
+    attn_group_decode<G, KVM>(a.q + (size_t)g * KVM * a.head_size, a.kcache_layer + head_off,
+                              a.vcache_layer + head_off, a.kv_dim, a.head_size, pos,
+                              a.out + (size_t)g * KVM * a.head_size, (float*)smem_raw, g, s,
+                              a.nsplit_g, a.ws_stride,
+                              attn_ws_carve(a.ws, a.kv_heads * KVM, a.head_size, a.ws_stride), a.fenced != 0);
+  }
+}
+
+// The decode step's launch and the multi-token slices of ONE sequence: position from the device word or the host,
+// gridDim.y consecutive tokens.
 // (Measured and not kept, profiles/r4_attn_pipe_ab.txt: the split-0 workgroups requesting q and their first batch -
 // rows tg + u * TPI whatever the position is - BEFORE the device scalar *d_pos has arrived.  The position then has to
 // come through a vector load (scalar loads return out of order, so the kernel-argument waits would wait for it), the
@@ -951,21 +986,24 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_attn_decode(KhAttnArgs a, int hos
     a.out += (size_t)t * a.tok_stride;
     a.ws = (char*)a.ws + (size_t)t * a.ws_tok_bytes;
   }
-  const int b = (int)blockIdx.x;
-  if (KVM == 0 || pos + 1 < a.t_long) {
-    if (b < a.kv_heads * a.kv_mul * a.nsplit) attn_head_block<G>(a, (float*)smem_raw, b, pos);
-    return;
+  attn_slice_body<G, KVM>(a, pos, smem_raw);
+}
+// The slices of a lane table: slice blockIdx.y = b is the token of lane b, its position and K/V base taken from the
+// table.  The choice of path is per slice (lanes sit at unrelated positions).
+template <int G, int KVM>
+__global__ __launch_bounds__(KH_WG_MAX) void k_seq_attn(KhAttnArgs a, const KhSeqLanes lanes) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int t = (int)blockIdx.y;
+  const int pos = lanes.pos[t];
+  {
+    const size_t row0 = (size_t)(lanes.row[t] - pos) * a.kv_dim;  // the slot's row 0
+    a.kcache_layer += row0;
+    a.vcache_layer += row0;
+    a.q += (size_t)t * a.tok_stride;
+    a.out += (size_t)t * a.tok_stride;
+    a.ws = (char*)a.ws + (size_t)t * a.ws_tok_bytes;
   }
-  if constexpr (KVM > 0) {
-    if (b >= a.kv_heads * a.nsplit_g) return;
-    const int g = b % a.kv_heads, s = b / a.kv_heads;
-    const size_t head_off = (size_t)g * a.head_size;
-    attn_group_decode<G, KVM>(a.q + (size_t)g * KVM * a.head_size, a.kcache_layer + head_off,
-                              a.vcache_layer + head_off, a.kv_dim, a.head_size, pos,
-                              a.out + (size_t)g * KVM * a.head_size, (float*)smem_raw, g, s,
-                              a.nsplit_g, a.ws_stride,
-                              attn_ws_carve(a.ws, a.kv_heads * KVM, a.head_size, a.ws_stride), a.fenced != 0);
-  }
+  attn_slice_body<G, KVM>(a, pos, smem_raw);
 }
 
 // lanes cooperating on one timestep for this head size
@@ -1030,8 +1068,8 @@ static inline int attn_tlong_hook() {
 }
 // KH_ATTN_WG hook (256 | 512) -> threads per decode-attention workgroup; default KH_WG_MAX: 8 waves per (head, split)
 // shorten each lane's timestep loop.  The ONE reader (model level: finish_create; operator level: kh_mha_decode_f32,
-// its workspace size and kh_plan_attention), so that plan, workspace and launch agree - attn_group_supported depends
-// on the width.
+// its workspace size, kh_plan_attention and kh_plan_attention_launch), so that plan, workspace and launch agree -
+// attn_group_supported depends on the width.
 static inline int attn_wg_hook() {
   if (const char* e = khm::dbg("KH_ATTN_WG")) {
     const int v = atoi(e);
@@ -1046,193 +1084,117 @@ static inline bool attn_fenced_hook() {
   return e && e[0] == '1';
 }
 
-// Launch.  a.nsplit_g == 0 disables the group path; head_size > 32 required (callers route
-// smaller heads to the generic LDS-score kernel).
-// pos_hi >= 0 (host-positioned launches only): the highest position among the ntok tokens; the grid
-// then carries only the splits that own timesteps at those positions instead of all cache_len / 256
-// of them (a 128-token prefill slice at the start of a 131072-row cache launched 16x too many
-// workgroups, all of which left immediately - measured 129 us per layer of dispatch).
-static inline void launch_attn_decode(KhAttnArgs a, int host_pos, int wg, hipStream_t s,
-                                      int ntok = 1, int pos_hi = -1) {
-  const int G = attn_lanes(a.head_size);
-  auto log2_or_neg = [](int v) {
-    int sh = 0;
-    while ((1 << sh) < v) ++sh;
-    return (1 << sh) == v ? sh : -1;
-  };
-  a.kvh_shift = log2_or_neg(a.kv_heads);
-  a.kvm_shift = log2_or_neg(a.kv_mul);
-  // host-positioned launch whose positions all stay below the group path's threshold: the per-head-only
-  // instantiation (fewer registers: two 512-thread workgroups per CU instead of one, which matters when 16 splits
-  // x 32 heads are in flight).  Device-positioned callers clear nsplit_g themselves when they know the range.
-  if (!a.d_pos && (pos_hi >= 0 ? pos_hi : host_pos) + 1 < a.t_long) a.nsplit_g = 0;
-  const bool grp = a.nsplit_g > 0 && attn_group_supported(a.head_size, a.kv_mul, wg);
-  if (!grp) a.nsplit_g = 0;
-  int head_splits = a.nsplit, group_splits = grp ? a.nsplit_g : 0;
-  if (pos_hi >= 0 && !a.d_pos) {
-    head_splits = 0;
-    group_splits = 0;
-    for (int p = host_pos; p <= pos_hi; ++p) {
-      if (grp && p + 1 >= a.t_long) {
-        const int n = attn_active_splits(p, a.nsplit_g, KH_ATTN_TSG_SHIFT);
-        if (n > group_splits) group_splits = n;
+// What the host decides about one decode-attention launch (k_attn_decode or k_seq_attn), in ONE place - the
+// launchers below and the host-only kh_plan_attention_launch (kh_ops.hip) read it.
+struct AttnLaunch {
+  int G, kvm;                      // the instantiation <G, KVM>; kvm = 0: per-head workgroups only
+  bool grp;                        // the grid carries the group path (kvm = kv_mul)
+  int kvh_shift, kvm_shift;        // log2 of kv_heads / kv_mul when they are powers of two, else -1
+  int head_splits, group_splits;   // splits that own timesteps at the launch's positions, per path
+  int grid;                        // grid.x
+  size_t lds;                      // dynamic LDS bytes
+};
+static inline int attn_log2_or_neg(int v) {
+  int sh = 0;
+  while ((1 << sh) < v) ++sh;
+  return (1 << sh) == v ? sh : -1;
+}
+// a: the geometry fields (kv_heads, kv_mul, head_size, nsplit, nsplit_g, t_long, ts_shift); a.nsplit_g == 0 disables
+// the group path.  The launch's positions: pos[0 .. n), or the run lo .. lo + n - 1 (pos = null); n = 0: the position
+// is a device word, every split may own timesteps.  With positions the grid carries only the splits that own
+// timesteps at them, as the maximum over the positions on the path each takes, instead of all cache_len / 256 of them
+// (a 128-token prefill slice at the start of a 131072-row cache launched 16x too many workgroups, all of which left
+// immediately - measured 129 us per layer of dispatch); and positions that all stay below the group path's threshold
+// take the per-head-only instantiation (fewer registers: two 512-thread workgroups per CU instead of one, which
+// matters when 16 splits x 32 heads are in flight).
+static inline AttnLaunch attn_launch_plan(const KhAttnArgs& a, int wg, const int32_t* pos, int lo, int n) {
+  AttnLaunch L;
+  L.G = attn_lanes(a.head_size);
+  L.kvh_shift = attn_log2_or_neg(a.kv_heads);
+  L.kvm_shift = attn_log2_or_neg(a.kv_mul);
+  L.grp = a.nsplit_g > 0 && attn_group_supported(a.head_size, a.kv_mul, wg);
+  L.head_splits = a.nsplit;
+  L.group_splits = L.grp ? a.nsplit_g : 0;
+  if (n > 0) {
+    L.head_splits = 0;
+    L.group_splits = 0;
+    for (int i = 0; i < n; ++i) {
+      const int p = pos ? pos[i] : lo + i;
+      if (L.grp && p + 1 >= a.t_long) {
+        const int k = attn_active_splits(p, a.nsplit_g, KH_ATTN_TSG_SHIFT);
+        if (k > L.group_splits) L.group_splits = k;
       } else {
-        const int n = attn_active_splits(p, a.nsplit, a.ts_shift);
-        if (n > head_splits) head_splits = n;
+        const int k = attn_active_splits(p, a.nsplit, a.ts_shift);
+        if (k > L.head_splits) L.head_splits = k;
       }
     }
+    if (!L.group_splits) L.grp = false;
   }
-  int grid = a.kv_heads * a.kv_mul * head_splits;
-  size_t lds = attn_fast_lds_bytes(a.head_size, wg);
-  if (grp) {
-    if (a.kv_heads * group_splits > grid) grid = a.kv_heads * group_splits;
+  L.kvm = L.grp ? a.kv_mul : 0;
+  L.grid = a.kv_heads * a.kv_mul * L.head_splits;
+  L.lds = attn_fast_lds_bytes(a.head_size, wg);
+  if (L.grp) {
+    if (a.kv_heads * L.group_splits > L.grid) L.grid = a.kv_heads * L.group_splits;
     const size_t l2 = attn_group_lds_bytes(a.head_size, a.kv_mul);
-    if (l2 > lds) lds = l2;
+    if (l2 > L.lds) L.lds = l2;
   }
-  if (grid < 1) grid = 1;
-  // launch log (hook KH_LAUNCH_LOG, kh_common.h): the literal instantiation, and one record of the host-side variant
-  // of the launch - "attn_launch<wg,ts_shift,defer,fenced,ntok>1?,group_grid?>" - built only while the log is on
-  const bool logging = khm::g_launch_log_on.load(std::memory_order_relaxed);
-  if (logging) {
-    char rec[96];
-    snprintf(rec, sizeof rec, "attn_launch<%d,%d,%d,%d,%d,%d>", wg, a.ts_shift, a.defer ? 1 : 0, a.fenced ? 1 : 0,
-             ntok > 1 ? 1 : 0, grp ? 1 : 0);
-    khm::launch_log_add(rec);
-  }
-#define KH_ATTN_LAUNCH(GG, KK)                                                                        \
-  do {                                                                                                \
-    if (logging) khm::launch_log_add("k_attn_decode<" #GG "," #KK ">");                               \
-    hipLaunchKernelGGL((k_attn_decode<GG, KK>), dim3(grid, ntok), dim3(wg), lds, s, a, host_pos);     \
-  } while (0)
-  const int kvm = grp ? a.kv_mul : 0;
-  if (G == 16) {
-    switch (kvm) {
-      case 2: KH_ATTN_LAUNCH(16, 2); break;
-      case 4: KH_ATTN_LAUNCH(16, 4); break;
-      case 7: KH_ATTN_LAUNCH(16, 7); break;
-      case 8: KH_ATTN_LAUNCH(16, 8); break;
-      default: KH_ATTN_LAUNCH(16, 0); break;
-    }
-  } else if (G == 32) {
-    switch (kvm) {
-      case 2: KH_ATTN_LAUNCH(32, 2); break;
-      case 4: KH_ATTN_LAUNCH(32, 4); break;
-      default: KH_ATTN_LAUNCH(32, 0); break;
-    }
-  } else {
-    KH_ATTN_LAUNCH(64, 0);
-  }
-#undef KH_ATTN_LAUNCH
+  if (L.grid < 1) L.grid = 1;
+  return L;
+}
+// The instantiations of k_attn_decode and k_seq_attn (attn_group_supported names the same KVM per G; 0, per-head only,
+// is what anything else runs as): f(G, KVM) with the compile-time values of the plan.
+template <int G>
+using AttnKvms = std::conditional_t<G == 16, khm::KhVals<2, 4, 7, 8, 0>,
+                                    std::conditional_t<G == 32, khm::KhVals<2, 4, 0>, khm::KhVals<0>>>;
+template <class F>
+void attn_pick(const AttnLaunch& L, F&& f) {
+  khm::kh_pick(khm::KhVals<16, 32, 64>{}, L.G, [&](auto G) {
+    khm::kh_pick(AttnKvms<decltype(G)::value>{}, L.kvm, [&](auto KVM) { f(G, KVM); });
+  });
+}
+// what the kernels read of the plan
+static inline void attn_launch_apply(const AttnLaunch& L, KhAttnArgs& a) {
+  a.kvh_shift = L.kvh_shift;
+  a.kvm_shift = L.kvm_shift;
+  if (!L.grp) a.nsplit_g = 0;
 }
 
-// =============================================================================================
-// Decode attention over lanes that belong to DIFFERENT sequences (kh_seq.h, kh_model_seq_step): slice blockIdx.y = b
-// is the token of lane b, at position pos[b] of a sequence whose position 0 is cache row row[b] - pos[b] (a sequence
-// slot of the model's cache).  The host knows both, so they travel by value.
-#define KH_SEQ_BMAX 8  // lanes of one pass (kh_prefill.h: KH_PF_BMAX)
-struct KhSeqLanes {
-  int32_t pos[KH_SEQ_BMAX];  // position of the lane's token in its sequence
-  int32_t row[KH_SEQ_BMAX];  // its cache row: the slot's first row + pos
-  int32_t slot[KH_SEQ_BMAX]; // its sequence slot: the entry of the per-slot device tables (token to feed, sampler)
-};
-// k_attn_decode's multi-token slice with the slice's position and K/V base taken from the lane table: the same device
-// functions under the same choice of path, which is per slice (lanes sit at unrelated positions).
-template <int G, int KVM>
-__global__ __launch_bounds__(KH_WG_MAX) void k_seq_attn(KhAttnArgs a, const KhSeqLanes lanes) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int t = (int)blockIdx.y;
-  const int pos = lanes.pos[t];
-  {
-    const size_t row0 = (size_t)(lanes.row[t] - pos) * a.kv_dim;  // the slot's row 0
-    a.kcache_layer += row0;
-    a.vcache_layer += row0;
-    a.q += (size_t)t * a.tok_stride;
-    a.out += (size_t)t * a.tok_stride;
-    a.ws = (char*)a.ws + (size_t)t * a.ws_tok_bytes;
-  }
-  const int b = (int)blockIdx.x;
-  if (KVM == 0 || pos + 1 < a.t_long) {
-    if (b < a.kv_heads * a.kv_mul * a.nsplit) attn_head_block<G>(a, (float*)smem_raw, b, pos);
-    return;
-  }
-  if constexpr (KVM > 0) {
-    if (b >= a.kv_heads * a.nsplit_g) return;
-    const int g = b % a.kv_heads, s = b / a.kv_heads;
-    const size_t head_off = (size_t)g * a.head_size;
-    attn_group_decode<G, KVM>(a.q + (size_t)g * KVM * a.head_size, a.kcache_layer + head_off,
-                              a.vcache_layer + head_off, a.kv_dim, a.head_size, pos,
-                              a.out + (size_t)g * KVM * a.head_size, (float*)smem_raw, g, s,
-                              a.nsplit_g, a.ws_stride,
-                              attn_ws_carve(a.ws, a.kv_heads * KVM, a.head_size, a.ws_stride), a.fenced != 0);
-  }
-}
-// Launch of lanes [0, n): in-launch merge (defer = 0), a.fenced as the caller set it; the grid carries the splits that
-// own timesteps at the HIGHEST lane position of each path, as launch_attn_decode does with pos_hi.  Logs the literal
-// instantiation and "seq_attn_launch<wg,ts_shift,fenced,group_grid?>".
-static inline void launch_seq_attn(KhAttnArgs a, const KhSeqLanes& lanes, int n, int wg, hipStream_t s) {
-  const int G = attn_lanes(a.head_size);
-  auto log2_or_neg = [](int v) {
-    int sh = 0;
-    while ((1 << sh) < v) ++sh;
-    return (1 << sh) == v ? sh : -1;
-  };
-  a.kvh_shift = log2_or_neg(a.kv_heads);
-  a.kvm_shift = log2_or_neg(a.kv_mul);
-  a.d_pos = nullptr;
-  a.defer = 0;
-  int pos_hi = 0;
-  for (int b = 0; b < n; ++b)
-    if (lanes.pos[b] > pos_hi) pos_hi = lanes.pos[b];
-  if (pos_hi + 1 < a.t_long) a.nsplit_g = 0;  // every lane below the group path: the per-head-only instantiation
-  const bool grp = a.nsplit_g > 0 && attn_group_supported(a.head_size, a.kv_mul, wg);
-  if (!grp) a.nsplit_g = 0;
-  int head_splits = 0, group_splits = 0;
-  for (int b = 0; b < n; ++b) {
-    const int p = lanes.pos[b];
-    if (grp && p + 1 >= a.t_long) {
-      const int k = attn_active_splits(p, a.nsplit_g, KH_ATTN_TSG_SHIFT);
-      if (k > group_splits) group_splits = k;
-    } else {
-      const int k = attn_active_splits(p, a.nsplit, a.ts_shift);
-      if (k > head_splits) head_splits = k;
-    }
-  }
-  int grid = a.kv_heads * a.kv_mul * head_splits;
-  size_t lds = attn_fast_lds_bytes(a.head_size, wg);
-  if (grp) {
-    if (a.kv_heads * group_splits > grid) grid = a.kv_heads * group_splits;
-    const size_t l2 = attn_group_lds_bytes(a.head_size, a.kv_mul);
-    if (l2 > lds) lds = l2;
-  }
-  if (grid < 1) grid = 1;
-  const bool logging = khm::g_launch_log_on.load(std::memory_order_relaxed);
-  if (logging) {
+// Launch of the decode step (ntok = 1) or of ntok consecutive tokens of one sequence from host_pos on; head_size > 32
+// required (callers route smaller heads to the generic LDS-score kernel).  pos_hi >= 0 (host-positioned launches
+// only): the highest position among the ntok tokens, which lets the plan cut the grid.  A host position without it
+// keeps every split and picks the instantiation by the position; device-positioned callers clear nsplit_g themselves
+// when they know the range.
+// Launch log (hook KH_LAUNCH_LOG, kh_common.h): the literal instantiation, and one record of the host-side variant
+// of the launch - "attn_launch<wg,ts_shift,defer,fenced,ntok>1?,group_grid?>" - built only while the log is on.
+static inline void launch_attn_decode(KhAttnArgs a, int host_pos, int wg, hipStream_t s,
+                                      int ntok = 1, int pos_hi = -1) {
+  const bool host_run = !a.d_pos && pos_hi >= 0;
+  if (!a.d_pos && !host_run && host_pos + 1 < a.t_long) a.nsplit_g = 0;
+  const AttnLaunch L = attn_launch_plan(a, wg, nullptr, host_pos, host_run ? pos_hi - host_pos + 1 : 0);
+  attn_launch_apply(L, a);
+  if (khm::g_launch_log_on.load(std::memory_order_relaxed)) {
     char rec[96];
-    snprintf(rec, sizeof rec, "seq_attn_launch<%d,%d,%d,%d>", wg, a.ts_shift, a.fenced ? 1 : 0, grp ? 1 : 0);
+    snprintf(rec, sizeof rec, "attn_launch<%d,%d,%d,%d,%d,%d>", wg, a.ts_shift, a.defer ? 1 : 0, a.fenced ? 1 : 0,
+             ntok > 1 ? 1 : 0, L.grp ? 1 : 0);
     khm::launch_log_add(rec);
   }
-#define KH_SEQ_ATTN_LAUNCH(GG, KK)                                                               \
-  do {                                                                                           \
-    if (logging) khm::launch_log_add("k_seq_attn<" #GG "," #KK ">");                             \
-    hipLaunchKernelGGL((k_seq_attn<GG, KK>), dim3(grid, n), dim3(wg), lds, s, a, lanes);         \
-  } while (0)
-  const int kvm = grp ? a.kv_mul : 0;
-  if (G == 16) {
-    switch (kvm) {
-      case 2: KH_SEQ_ATTN_LAUNCH(16, 2); break;
-      case 4: KH_SEQ_ATTN_LAUNCH(16, 4); break;
-      case 7: KH_SEQ_ATTN_LAUNCH(16, 7); break;
-      case 8: KH_SEQ_ATTN_LAUNCH(16, 8); break;
-      default: KH_SEQ_ATTN_LAUNCH(16, 0); break;
-    }
-  } else if (G == 32) {
-    switch (kvm) {
-      case 2: KH_SEQ_ATTN_LAUNCH(32, 2); break;
-      case 4: KH_SEQ_ATTN_LAUNCH(32, 4); break;
-      default: KH_SEQ_ATTN_LAUNCH(32, 0); break;
-    }
-  } else {
-    KH_SEQ_ATTN_LAUNCH(64, 0);
+  attn_pick(L, [&](auto G, auto KVM) {
+    khm::kh_launch(KH_KERNEL(k_attn_decode, G, KVM), dim3(L.grid, ntok), wg, L.lds, s, a, host_pos);
+  });
+}
+// Launch of lanes [0, n): in-launch merge (defer = 0), a.fenced as the caller set it.  Logs the literal instantiation
+// and "seq_attn_launch<wg,ts_shift,fenced,group_grid?>".
+static inline void launch_seq_attn(KhAttnArgs a, const KhSeqLanes& lanes, int n, int wg, hipStream_t s) {
+  a.d_pos = nullptr;
+  a.defer = 0;
+  const AttnLaunch L = attn_launch_plan(a, wg, lanes.pos, 0, n);
+  attn_launch_apply(L, a);
+  if (khm::g_launch_log_on.load(std::memory_order_relaxed)) {
+    char rec[96];
+    snprintf(rec, sizeof rec, "seq_attn_launch<%d,%d,%d,%d>", wg, a.ts_shift, a.fenced ? 1 : 0, L.grp ? 1 : 0);
+    khm::launch_log_add(rec);
   }
-#undef KH_SEQ_ATTN_LAUNCH
+  attn_pick(L, [&](auto G, auto KVM) {
+    khm::kh_launch(KH_KERNEL(k_seq_attn, G, KVM), dim3(L.grid, n), wg, L.lds, s, a, lanes);
+  });
 }

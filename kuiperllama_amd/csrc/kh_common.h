@@ -18,6 +18,9 @@
 // pick_shape); KH_WG is the default and the size every op-level kernel uses.
 #define KH_WG_MAX 512
 #define KH_WAVES_MAX (KH_WG_MAX / KH_WAVE)
+// Tokens of one B-token pass over the weights (kh_prefill.h), at most: the rows of its logits, the lanes of a lane
+// table (kh_attn.h), the targets of k_score_lp (kh_logprobs.h) and the fed tokens of k_spec_accept (kh_spec.h).
+#define KH_PF_BMAX 8
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));

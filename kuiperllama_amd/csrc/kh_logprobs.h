@@ -300,11 +300,10 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_lp(const KhSa
 // processor, no sampler - finds its maximum as k_logprobs_op does, and leaves the record of the position: the token
 // that FOLLOWED it (target[b]; -1 behind the last token of a call, whose log-prob is then NaN while its top list
 // is the next-token distribution), that token's log-prob and the top *top_n.  Entries from *top_n on are "none".
-#define KH_SCORE_BMAX 8  // tokens of one pass (kh_prefill.h: KH_PF_BMAX)
 struct KhScoreLpArgs {
   const float* logits;         // [gridDim.x][vstride]
   int vstride, vocab;
-  int32_t target[KH_SCORE_BMAX];
+  int32_t target[KH_PF_BMAX];
   int pos0;
   const int32_t* top_n;        // device word (kh_model_set_logprobs)
   int32_t* rec_token;          // [rec_cap]
@@ -318,7 +317,7 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_score_lp(const KhSco
   __shared__ KhLpSmem t;
   const int b = blockIdx.x;
   const int pos = a.pos0 + b;
-  if (b >= KH_SCORE_BMAX || pos < 0 || pos >= a.rec_cap) return;  // uniform
+  if (b >= KH_PF_BMAX || pos < 0 || pos >= a.rec_cap) return;  // uniform
   const float* lg = a.logits + (size_t)b * a.vstride;
   float m = -INFINITY;
   kh_samp_for_global(lg, a.vocab, [&](float l, int) __attribute__((always_inline)) { m = fmaxf(m, l); });

@@ -244,6 +244,12 @@ struct kh_model {
 #define KH_PG_MIN_TOKENS 16  // prompts with fewer fed-only tokens stay on the bit-identical path
 
 namespace khm {
+// every token of a caller's array is a row of the embedding table (the entry points answer KH_ERR_RANGE otherwise)
+inline bool tokens_in_vocab(const kh_model* m, const int32_t* toks, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (toks[i] < 0 || toks[i] >= m->cfg.vocab_size) return false;
+  return true;
+}
 template <typename T>
 int dalloc(T** p, size_t n) {
   hipError_t e = hipMalloc((void**)p, n * sizeof(T));

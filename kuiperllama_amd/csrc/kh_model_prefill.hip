@@ -1,7 +1,7 @@
-// kh_model_prefill.hip — prompt phase of the model level: the B-token VALU prefill (kh_prefill.h,
-// bit-identical to token-by-token), sequence scoring on top of it (kh_model_score: k_pf_cls, k_score_lp), the verify
-// pass of speculative greedy decode (kh_model_verify: k_pf_cls, kh_spec.h), the pass over lanes of different
-// sequences (kh_seq.h; kh_model_seq.hip drives it) and the
+// kh_model_prefill.hip — prompt phase of the model level: the B-token VALU pass (kh_prefill.h, bit-identical to
+// token-by-token; ONE layer driver, launch_pf_pass) and what runs on it - the prompt prefill, sequence scoring
+// (kh_model_score: k_pf_cls, k_score_lp), the verify pass of speculative greedy decode (kh_model_verify: k_pf_cls,
+// kh_spec.h) and the pass over lanes of different sequences (kh_seq.h; kh_model_seq.hip drives it) - and the
 // fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h).  The
 // reference feeds the prompt one token per forward pass (demo/main.cpp:20-22).
 // gfx950 only.
@@ -160,58 +160,97 @@ void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const f
     });
   }
 }
-// forward of nvalid (<= B) prompt tokens at positions pos0.. : fills their K/V cache rows.  full_depth (scoring): the
-// last layer's attention, wo and FFN run too and pf_x holds the tokens' final residual vectors.  row0: the cache row
-// of the sequence's position 0 (a sequence slot's first row; 0 for the batch-1 entry points)
-void launch_prefill_chunk(kh_model* m, const int32_t* toks, int nvalid, int pos0, int B, bool full_depth = false,
-                          int row0 = 0) {
+// One pass of nvalid (<= B) tokens through the B-token kernels.  Where a token's id, its RoPE row and its cache row
+// come from is the only thing the callers differ in:
+//   a run (lanes = null)  toks[b] sits at position pos0 + b of the sequence whose position 0 is cache row row0 (a
+//                         sequence slot's first row; 0 for the batch-1 entry points): k_pf_embed, k_pf_qkv,
+//                         k_attn_decode.  Without full_depth the pass fills the tokens' K/V cache rows and stops
+//                         behind the last layer's; with it (scoring, verify) the last layer's attention, wo and FFN
+//                         run too and pf_x holds the tokens' final residual vectors
+//   a lane table          lane b feeds d_seq_tok[slot[b]] at position pos[b], cache row row[b] (kh_seq.h): k_seq_embed,
+//                         k_seq_qkv, k_seq_attn.  Always full depth
+// wo, ffn13 and w2 do not care where a token sits.
+struct PfPass {
+  int nvalid, B;
+  bool full_depth;
+  const int32_t* toks;
+  int pos0, row0;
+  const KhSeqLanes* lanes;
+};
+PfPass pf_run(const int32_t* toks, int nvalid, int pos0, int B, bool full_depth, int row0 = 0) {
+  return PfPass{nvalid, B, full_depth, toks, pos0, row0, nullptr};
+}
+PfPass pf_lanes(const KhSeqLanes& lanes, int nvalid, int B) { return PfPass{nvalid, B, true, nullptr, 0, 0, &lanes}; }
+// layer l's k_pf_qkv / k_seq_qkv arguments: cache rows counted from row0, RoPE rows from pos0 (a lane table brings
+// its own of both: 0, 0)
+KhPfQkvArgs pf_qkv_args(const kh_model* m, int l, const PfPass& p) {
+  const kh_config& c = m->cfg;
+  const LayerW& W = m->layers[l];
+  KhPfQkvArgs a;
+  a.X = m->pf_x;
+  a.att_norm = W.att_norm;
+  a.wq = W.wq;
+  a.wk = W.wk;
+  a.wv = W.wv;
+  a.Q = m->pf_q;
+  a.kcache_layer = m->kcache + ((size_t)l * c.cache_len + p.row0) * c.kv_dim;
+  a.vcache_layer = m->vcache + ((size_t)l * c.cache_len + p.row0) * c.kv_dim;
+  a.sin_cache = m->sin_cache;
+  a.cos_cache = m->cos_cache;
+  a.dim = c.dim;
+  a.kv_dim = c.kv_dim;
+  a.head_size = c.head_size;
+  a.rope_mode = c.rope_mode;
+  a.gshift = m->gshift;
+  a.pos0 = p.pos0;
+  a.nvalid = p.nvalid;
+  a.eps = c.rms_eps;
+  return a;
+}
+void launch_pf_pass(kh_model* m, const PfPass& p) {
   const kh_config& c = m->cfg;
   const bool q = c.is_quant;
-  KhPfTokens tk;
-  for (int b = 0; b < KH_PF_BMAX; ++b) tk.t[b] = toks[b < nvalid ? b : nvalid - 1];
-  hipLaunchKernelGGL(k_pf_embed, dim3(B), dim3(KH_WG), 0, m->stream, tk, m->tok_emb, m->pf_x, c.dim);
+  const int nvalid = p.nvalid, B = p.B;
+  if (p.lanes) {
+    launch_log("k_seq_embed");
+    hipLaunchKernelGGL(k_seq_embed, dim3(B), dim3(KH_WG), 0, m->stream, (const int32_t*)m->d_seq_tok, *p.lanes, nvalid,
+                       c.vocab_size, m->tok_emb, m->pf_x, c.dim);
+  } else {
+    KhPfTokens tk;
+    for (int b = 0; b < KH_PF_BMAX; ++b) tk.t[b] = p.toks[b < nvalid ? b : nvalid - 1];
+    hipLaunchKernelGGL(k_pf_embed, dim3(B), dim3(KH_WG), 0, m->stream, tk, m->tok_emb, m->pf_x, c.dim);
+  }
   for (int l = 0; l < c.layer_num; ++l) {
     const LayerW& W = m->layers[l];
-    {
-      KhPfQkvArgs a;
-      a.X = m->pf_x;
-      a.att_norm = W.att_norm;
-      a.wq = W.wq;
-      a.wk = W.wk;
-      a.wv = W.wv;
-      a.Q = m->pf_q;
-      a.kcache_layer = m->kcache + ((size_t)l * c.cache_len + row0) * c.kv_dim;
-      a.vcache_layer = m->vcache + ((size_t)l * c.cache_len + row0) * c.kv_dim;
-      a.sin_cache = m->sin_cache;
-      a.cos_cache = m->cos_cache;
-      a.dim = c.dim;
-      a.kv_dim = c.kv_dim;
-      a.head_size = c.head_size;
-      a.rope_mode = c.rope_mode;
-      a.gshift = m->gshift;
-      a.pos0 = pos0;
-      a.nvalid = nvalid;
-      a.eps = c.rms_eps;
-      pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
-        pf_launch(KH_KERNEL(k_pf_qkv, Q, SP, BB), m->sh_qkv, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
-      });
-    }
+    // the instantiations of k_seq_qkv are k_pf_qkv's (PfB x PfQkvSP)
+    pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
+      const size_t lds = pf_lds_bytes(Q, c.dim, BB);
+      if (p.lanes)
+        pf_launch(KH_KERNEL(k_seq_qkv, Q, SP, BB), m->sh_qkv, lds, m->stream,
+                  KhSeqQkvArgs{pf_qkv_args(m, l, p), *p.lanes});
+      else
+        pf_launch(KH_KERNEL(k_pf_qkv, Q, SP, BB), m->sh_qkv, lds, m->stream, pf_qkv_args(m, l, p));
+    });
     // the prompt phase leaves K/V rows and nothing else (no logits): the last layer's K/V rows are
     // written, its attention, wo and FFN feed nothing - unless the classifier follows (full_depth)
-    if (l == c.layer_num - 1 && !full_depth) break;
+    if (l == c.layer_num - 1 && !p.full_depth) break;
     {
       KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
       a.defer = 0;  // multi-token slices merge in the launch
-      a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: launch_attn_decode decides from the slice's positions
+      a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: the launch plan decides from the slices' positions
       a.q = m->pf_q;
       a.out = m->pf_att;
       a.d_pos = nullptr;
       a.ws = m->pf_ws;
       a.tok_stride = c.dim;
       a.ws_tok_bytes = m->pf_ws_tok_bytes;
-      a.kcache_layer += (size_t)row0 * c.kv_dim;
-      a.vcache_layer += (size_t)row0 * c.kv_dim;
-      launch_attn_decode(a, pos0, m->attn_wg, m->stream, nvalid, pos0 + nvalid - 1);
+      if (p.lanes) {
+        launch_seq_attn(a, *p.lanes, nvalid, m->attn_wg, m->stream);
+      } else {
+        a.kcache_layer += (size_t)p.row0 * c.kv_dim;
+        a.vcache_layer += (size_t)p.row0 * c.kv_dim;
+        launch_attn_decode(a, p.pos0, m->attn_wg, m->stream, nvalid, p.pos0 + nvalid - 1);
+      }
     }
     pf_gemv_res(m, m->sh_wo, W.wo, m->pf_att, m->pf_x, c.dim, c.dim, nvalid, B);
     {
@@ -267,7 +306,7 @@ void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0,
   t.logits = m->pf_logits;
   t.vstride = m->pf_vstride;
   t.vocab = c.vocab_size;
-  for (int b = 0; b < KH_SCORE_BMAX; ++b) t.target[b] = b < nvalid ? target[b] : -1;
+  for (int b = 0; b < KH_PF_BMAX; ++b) t.target[b] = b < nvalid ? target[b] : -1;
   t.pos0 = pos0;
   t.top_n = m->d_lp_top_n;
   t.rec_token = m->d_lp_token;
@@ -277,74 +316,6 @@ void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0,
   t.rec_cap = m->lp_cap;
   launch_log("k_score_lp");
   hipLaunchKernelGGL(k_score_lp, dim3(nvalid), dim3(KH_SAMP_THREADS), 0, m->stream, t);
-}
-// ---- the pass over lanes of different sequences (kh_seq.h) --------------------------------------------------------
-// launch_prefill_chunk at full depth with the token, the RoPE row and the cache row of every lane taken from the lane
-// table: k_seq_embed, then per layer k_seq_qkv, k_seq_attn and the prefill kernels as they are.  The instantiations of
-// k_seq_qkv are k_pf_qkv's (PfB x PfQkvSP).
-void launch_seq_chunk(kh_model* m, const KhSeqLanes& lanes, int nvalid, int B) {
-  const kh_config& c = m->cfg;
-  const bool q = c.is_quant;
-  launch_log("k_seq_embed");
-  hipLaunchKernelGGL(k_seq_embed, dim3(B), dim3(KH_WG), 0, m->stream, (const int32_t*)m->d_seq_tok, lanes, nvalid,
-                     c.vocab_size, m->tok_emb, m->pf_x, c.dim);
-  for (int l = 0; l < c.layer_num; ++l) {
-    const LayerW& W = m->layers[l];
-    {
-      KhSeqQkvArgs sa;
-      KhPfQkvArgs& a = sa.a;
-      a.X = m->pf_x;
-      a.att_norm = W.att_norm;
-      a.wq = W.wq;
-      a.wk = W.wk;
-      a.wv = W.wv;
-      a.Q = m->pf_q;
-      a.kcache_layer = m->kcache + (size_t)l * c.cache_len * c.kv_dim;
-      a.vcache_layer = m->vcache + (size_t)l * c.cache_len * c.kv_dim;
-      a.sin_cache = m->sin_cache;
-      a.cos_cache = m->cos_cache;
-      a.dim = c.dim;
-      a.kv_dim = c.kv_dim;
-      a.head_size = c.head_size;
-      a.rope_mode = c.rope_mode;
-      a.gshift = m->gshift;
-      a.pos0 = 0;
-      a.nvalid = nvalid;
-      a.eps = c.rms_eps;
-      sa.lanes = lanes;
-      pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
-        pf_launch(KH_KERNEL(k_seq_qkv, Q, SP, BB), m->sh_qkv, pf_lds_bytes(Q, c.dim, BB), m->stream, sa);
-      });
-    }
-    {
-      KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
-      a.nsplit_g = m->attn_ns_g;  // launch_seq_attn decides from the lanes' positions
-      a.q = m->pf_q;
-      a.out = m->pf_att;
-      a.ws = m->pf_ws;
-      a.tok_stride = c.dim;
-      a.ws_tok_bytes = m->pf_ws_tok_bytes;
-      launch_seq_attn(a, lanes, nvalid, m->attn_wg, m->stream);
-    }
-    pf_gemv_res(m, m->sh_wo, W.wo, m->pf_att, m->pf_x, c.dim, c.dim, nvalid, B);
-    {
-      KhPfFfn13Args a;
-      a.X = m->pf_x;
-      a.ffn_norm = W.ffn_norm;
-      a.w1 = W.w1;
-      a.w3 = W.w3;
-      a.H = m->pf_h;
-      a.dim = c.dim;
-      a.hidden = c.hidden_dim;
-      a.gshift = m->gshift;
-      a.nvalid = nvalid;
-      a.eps = c.rms_eps;
-      pick_pf<PfB, PfNoSP>(q, 1, B, [&](auto Q, auto, auto BB) {
-        pf_launch(KH_KERNEL(k_pf_ffn13, Q, BB), m->sh_ffn, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
-      });
-    }
-    pf_gemv_res(m, m->sh_w2, W.w2, m->pf_h, m->pf_x, c.hidden_dim, c.dim, nvalid, B);
-  }
 }
 }  // namespace
 
@@ -612,7 +583,7 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
     } else {
       KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
       a.defer = 0;  // multi-token slices merge in the launch
-      a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: launch_attn_decode decides from the slice's positions
+      a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: the launch plan decides from the slice's positions
       a.q = m->pg_q;
       a.out = m->pg_att;
       a.d_pos = nullptr;
@@ -675,8 +646,7 @@ int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n; ++i)
-    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   if (!pg_supported(m)) return KH_ERR_UNSUPPORTED;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
@@ -728,8 +698,7 @@ int khm::prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t po
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n; ++i)
-    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   if (!prefill_supported(m)) return KH_ERR_UNSUPPORTED;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
@@ -737,19 +706,17 @@ int khm::prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t po
   if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
   const int B = prefill_batch(m);
   for (int t0 = 0; t0 < n; t0 += B)
-    launch_prefill_chunk(m, h_tokens + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B);
+    launch_pf_pass(m, pf_run(h_tokens + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B, /*full_depth=*/false));
   return kh_launch_status();
 }
 
 // Sequence scoring: kh_model_prefill's pass at full depth, k_pf_cls and k_score_lp per chunk of B tokens.  Eager
 // launches on the model stream; every check before the first of them.
-static_assert(KH_SCORE_BMAX == KH_PF_BMAX, "k_score_lp takes one target per token of a prefill pass");
 extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n; ++i)
-    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   if (m->lp_top_n < 0 || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
@@ -761,7 +728,7 @@ extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, i
     const int nv = n - t0 < B ? n - t0 : B;
     int32_t target[KH_PF_BMAX];
     kh_score_targets(h_tokens, n, t0, nv, target);
-    launch_prefill_chunk(m, h_tokens + t0, nv, pos0 + t0, B, /*full_depth=*/true);
+    launch_pf_pass(m, pf_run(h_tokens + t0, nv, pos0 + t0, B, /*full_depth=*/true));
     launch_score_tail(m, target, nv, pos0 + t0, B);
   }
   if ((rc = kh_launch_status()) != KH_OK) return rc;
@@ -769,29 +736,28 @@ extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, i
 }
 
 // ---- speculative greedy decode: the verify pass (kh_spec.h) ---------------------------------------------------------
-static_assert(KH_SPEC_BMAX == KH_PF_BMAX, "k_spec_accept takes one fed token per token of a prefill pass");
 int khm::verify_width(const kh_model* m) { return prefill_batch(m); }
 int khm::verify_prepare(kh_model* m, int rows) {
   int rc;
   if ((rc = kv_ensure(m, rows)) != KH_OK) return rc;
   if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
   if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
-  if (!m->d_spec && (rc = dalloc(&m->d_spec, (size_t)1 + KH_SPEC_BMAX)) != KH_OK) return rc;
+  if (!m->d_spec && (rc = dalloc(&m->d_spec, (size_t)1 + KH_PF_BMAX)) != KH_OK) return rc;
   if (!m->h_spec_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_spec_pin, sizeof(int32_t) * (1 + KH_SPEC_BMAX), hipHostMallocDefault));
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_spec_pin, sizeof(int32_t) * (1 + KH_PF_BMAX), hipHostMallocDefault));
   return KH_OK;
 }
 int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0) {
   const kh_config& c = m->cfg;
   const int B = prefill_batch(m);
-  launch_prefill_chunk(m, toks, n, pos0, B, /*full_depth=*/true);
+  launch_pf_pass(m, pf_run(toks, n, pos0, B, /*full_depth=*/true));
   launch_pf_cls(m, n, B);
   launch_log("k_spec_pick");
   hipLaunchKernelGGL(k_spec_pick, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, (const float*)m->pf_logits,
                      c.vocab_size, (long long)m->pf_vstride, m->d_spec + 1);
   KhSpecAcceptArgs t;
   t.res = m->d_spec;
-  for (int b = 0; b < KH_SPEC_BMAX; ++b) t.fed[b] = b < n ? toks[b] : -1;
+  for (int b = 0; b < KH_PF_BMAX; ++b) t.fed[b] = b < n ? toks[b] : -1;
   t.pos0 = pos0;
   t.n = n;
   t.words = m->d_words;
@@ -818,13 +784,13 @@ int khm::seq_prepare(kh_model* m) {
   if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
   if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
   const size_t rows = (size_t)m->cfg.cache_len;
-  if (!m->d_seq_tok && (rc = dalloc(&m->d_seq_tok, (size_t)KH_SEQ_MAX_SLOTS)) != KH_OK) return rc;
-  if (!m->d_seq_samp && (rc = dalloc(&m->d_seq_samp, (size_t)KH_SEQ_MAX_SLOTS)) != KH_OK) return rc;
+  if (!m->d_seq_tok && (rc = dalloc(&m->d_seq_tok, (size_t)KH_SEQ_SLOTS_MAX)) != KH_OK) return rc;
+  if (!m->d_seq_samp && (rc = dalloc(&m->d_seq_samp, (size_t)KH_SEQ_SLOTS_MAX)) != KH_OK) return rc;
   if (!m->d_seq_words && (rc = dalloc(&m->d_seq_words, rows)) != KH_OK) return rc;
   if (!m->h_seq_tok_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_tok_pin, sizeof(int32_t) * KH_SEQ_MAX_SLOTS, hipHostMallocDefault));
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_tok_pin, sizeof(int32_t) * KH_SEQ_SLOTS_MAX, hipHostMallocDefault));
   if (!m->h_seq_samp_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_samp_pin, sizeof(KhSampParams) * KH_SEQ_MAX_SLOTS, hipHostMallocDefault));
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_samp_pin, sizeof(KhSampParams) * KH_SEQ_SLOTS_MAX, hipHostMallocDefault));
   if (!m->h_seq_words_pin)
     KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_words_pin, sizeof(int32_t) * rows, hipHostMallocDefault));
   for (auto& e : m->ev_chunk)  // the stop check's events (ensure_pinned_words makes them for the batch-1 loops)
@@ -834,18 +800,18 @@ int khm::seq_prepare(kh_model* m) {
 int khm::seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0) {
   const int B = prefill_batch(m);
   for (int t0 = 0; t0 < n; t0 += B)
-    launch_prefill_chunk(m, toks + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B, /*full_depth=*/false, row0);
+    launch_pf_pass(m, pf_run(toks + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B, /*full_depth=*/false, row0));
   return kh_launch_status();
 }
 int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words) {
   const kh_config& c = m->cfg;
   const int B = prefill_batch(m);
-  for (int b = n; b < KH_SEQ_BMAX; ++b) {  // padding lanes rotate by the last valid lane's row; nothing of them is kept
+  for (int b = n; b < KH_PF_BMAX; ++b) {  // padding lanes rotate by the last valid lane's row; nothing of them is kept
     lanes.pos[b] = lanes.pos[n - 1];
     lanes.row[b] = lanes.row[n - 1];
     lanes.slot[b] = lanes.slot[n - 1];
   }
-  launch_seq_chunk(m, lanes, n, B);
+  launch_pf_pass(m, pf_lanes(lanes, n, B));
   launch_pf_cls(m, n, B);
   KhSeqPickArgs t;
   t.logits = m->pf_logits;
@@ -873,8 +839,7 @@ extern "C" int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, 
   const kh_config& c = m->cfg;
   if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
   if (n > verify_width(m) || (int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n; ++i)
-    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
   if ((rc = verify_prepare(m, pos0 + n)) != KH_OK) return rc;
@@ -896,8 +861,7 @@ extern "C" int kh_model_time_prefill(kh_model* m, const int32_t* h_tokens, int32
   if (!m || !h_tokens || !h_ms || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n; ++i)
-    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
   if ((rc = kv_ensure(m, pos0 + n + 1)) != KH_OK) return rc;

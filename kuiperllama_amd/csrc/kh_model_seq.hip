@@ -15,7 +15,7 @@
 
 using namespace khm;
 
-static_assert(KH_SEQ_SLOTS_MAX >= KH_SEQ_BMAX, "a pass never has more lanes than there can be slots");
+static_assert(KH_SEQ_SLOTS_MAX >= KH_PF_BMAX, "a pass never has more lanes than there can be slots");
 
 namespace {
 inline int slot_len(const kh_model* m) { return m->cfg.cache_len / m->seq_slots; }
@@ -52,12 +52,12 @@ extern "C" int kh_plan_seq_slots(int32_t cache_len, int32_t n_slots, int32_t* sl
 
 extern "C" int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
                                  int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes) {
-  if (n_seq <= 0 || n_seq > KH_SEQ_SLOTS_MAX || width <= 0 || width > KH_SEQ_BMAX || !first_pos || !total_steps ||
+  if (n_seq <= 0 || n_seq > KH_SEQ_SLOTS_MAX || width <= 0 || width > KH_PF_BMAX || !first_pos || !total_steps ||
       !n_passes || cap_passes < 0 || (cap_passes > 0 && !out_lanes))
     return KH_ERR_INVALID_ARG;
   for (int s = 0; s < n_seq; ++s)
     if (first_pos[s] < 0 || total_steps[s] <= 0) return KH_ERR_INVALID_ARG;
-  int32_t pos[KH_SEQ_SLOTS_MAX], lanes[KH_SEQ_BMAX];
+  int32_t pos[KH_SEQ_SLOTS_MAX], lanes[KH_PF_BMAX];
   memcpy(pos, first_pos, sizeof(int32_t) * (size_t)n_seq);
   int cursor = 0, passes = 0;
   for (int n; (n = kh_seq_next_pass(n_seq, width, pos, total_steps, nullptr, &cursor, lanes)) > 0; ++passes) {
@@ -88,11 +88,9 @@ extern "C" int kh_model_seq_width(const kh_model* m, int32_t* width) {
 
 extern "C" int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_tokens, int32_t n, int32_t pos0) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
-  const kh_config& c = m->cfg;
   const int len = slot_len(m);
   if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > len) return KH_ERR_RANGE;
-  for (int i = 0; i < n; ++i)
-    if (h_tokens[i] < 0 || h_tokens[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   if (!prefill_supported(m)) return KH_ERR_UNSUPPORTED;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
@@ -186,7 +184,6 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
   if (!m || !h_prompts || !n_prompt || !total_steps || !h_words || !n_words || n_seq <= 0 || words_stride <= 0 ||
       n_stop < 0 || (n_stop > 0 && !h_stop))
     return KH_ERR_INVALID_ARG;
-  const kh_config& c = m->cfg;
   const int len = slot_len(m);
   if (n_seq > m->seq_slots) return KH_ERR_RANGE;
   size_t n_tok = 0;
@@ -199,8 +196,7 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
       return KH_ERR_INVALID_ARG;
     n_tok += (size_t)n_prompt[s];
   }
-  for (size_t i = 0; i < n_tok; ++i)
-    if (h_prompts[i] < 0 || h_prompts[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_prompts, n_tok)) return KH_ERR_RANGE;
   if (seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
   return kh_api_guard([&]() -> int {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
@@ -280,7 +276,7 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
     for (;;) {
       int k = 0;
       while (k < per_check) {
-        int32_t who[KH_SEQ_BMAX];
+        int32_t who[KH_PF_BMAX];
         const int n = kh_seq_next_pass(n_seq, width, pos.data(), total_steps, stopped.data(), &cursor, who);
         if (n == 0) break;
         KhSeqLanes lanes;

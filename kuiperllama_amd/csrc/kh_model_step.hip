@@ -1070,8 +1070,7 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
     return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if (total_steps > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n_prompt; ++i)
-    if (h_prompt[i] < 0 || h_prompt[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_prompt, n_prompt)) return KH_ERR_RANGE;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
   *n_words = 0;
@@ -1206,10 +1205,8 @@ extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, in
     return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if (total_steps > c.cache_len) return KH_ERR_RANGE;
-  for (int i = 0; i < n_prompt; ++i)
-    if (h_prompt[i] < 0 || h_prompt[i] >= c.vocab_size) return KH_ERR_RANGE;
-  for (int i = 0; i < o.n_hint; ++i)
-    if (o.h_hint[i] < 0 || o.h_hint[i] >= c.vocab_size) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, h_prompt, n_prompt)) return KH_ERR_RANGE;
+  if (!tokens_in_vocab(m, o.h_hint, o.n_hint)) return KH_ERR_RANGE;
   // greedy on the raw logits only, and only where the verify pass runs: no silent fallback to generate_until
   if (m->samp_on || m->proc_on || m->lp_top_n >= 0 || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
   return kh_api_guard([&]() -> int {

@@ -581,6 +581,35 @@ extern "C" int kh_plan_attention(int32_t head_num, int32_t kv_mul, int32_t head_
   out8[7] = (grp ? head_num / kv_mul : head_num) * nact;
   return KH_OK;
 }
+// Host-only view of what ONE launch over the positions pos[0 .. n) is (attn_launch_plan, the planner of
+// launch_attn_decode / launch_seq_attn, on the same geometry and hooks as kh_plan_attention); n = 0: a
+// device-positioned launch.  out6 = {G, KVM of the instantiation, grid.x, dynamic LDS bytes, per-head splits, group splits in the grid}.
+extern "C" int kh_plan_attention_launch(int32_t head_num, int32_t kv_mul, int32_t head_size, int32_t seq_len,
+                                        const int32_t* pos, int32_t n, int32_t* out6) {
+  if (!out6 || head_num <= 0 || kv_mul <= 0 || head_num % kv_mul || head_size <= 0 || seq_len <= 0 || n < 0 ||
+      (n > 0 && !pos))
+    return KH_ERR_INVALID_ARG;
+  for (int i = 0; i < n; ++i)
+    if (pos[i] < 0 || pos[i] >= seq_len) return KH_ERR_INVALID_ARG;
+  const int wg = attn_wg_hook();
+  const AttnPlan p = attn_plan(head_num, kv_mul, head_size, seq_len, wg, attn_tlong_hook());
+  KhAttnArgs a{};
+  a.kv_heads = head_num / kv_mul;
+  a.kv_mul = kv_mul;
+  a.head_size = head_size;
+  a.nsplit = p.ns;
+  a.nsplit_g = p.ns_g;
+  a.t_long = p.t_long;
+  a.ts_shift = p.ts_shift;
+  const AttnLaunch L = attn_launch_plan(a, wg, pos, 0, n);
+  out6[0] = L.G;
+  out6[1] = L.kvm;
+  out6[2] = L.grid;
+  out6[3] = (int32_t)L.lds;
+  out6[4] = L.head_splits;
+  out6[5] = L.group_splits;
+  return KH_OK;
+}
 extern "C" int kh_mha_decode_f32(const int32_t* d_pos, int32_t pos, int32_t head_num,
                                  int32_t layer_index, int32_t seq_len, int32_t kv_dim,
                                  int32_t kv_mul, int32_t head_size, float* mha_out, const float* q,
@@ -692,8 +721,8 @@ extern "C" int kh_argmax_rows_f32(const float* logits, int64_t n, int64_t row_st
                                   void* stream) {
   if (!logits || !d_out || n <= 0 || n > 0x7fffffffLL || n_rows <= 0 || row_stride < n || (row_stride & 3))
     return KH_ERR_INVALID_ARG;
-  for (int32_t r0 = 0; r0 < n_rows; r0 += KH_SPEC_BMAX) {
-    const int rows = n_rows - r0 < KH_SPEC_BMAX ? n_rows - r0 : KH_SPEC_BMAX;
+  for (int32_t r0 = 0; r0 < n_rows; r0 += KH_PF_BMAX) {
+    const int rows = n_rows - r0 < KH_PF_BMAX ? n_rows - r0 : KH_PF_BMAX;
     hipLaunchKernelGGL(k_spec_pick, dim3(rows), dim3(KH_SAMP_THREADS), 0, (hipStream_t)stream,
                        logits + (size_t)r0 * (size_t)row_stride, (int)n, (long long)row_stride, d_out + r0);
   }

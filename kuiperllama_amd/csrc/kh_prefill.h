@@ -24,8 +24,8 @@
 
 // Tokens per weight pass: up to 8 for the dim-input matrices of fp32 models when 8 vectors leave
 // room for two workgroups per CU, else 4; w2 (hidden-sized input) takes the largest of 8/4/2 whose
-// vectors fit LDS; int8 stays at 4 (its converted-weight tile already fills the register file).
-#define KH_PF_BMAX 8
+// vectors fit LDS; int8 stays at 4 (its converted-weight tile already fills the register file).  KH_PF_BMAX
+// (kh_common.h) is the most a pass takes.
 // 16-byte loads per row in flight per lane: int8 converts the whole tile to floats once per
 // chunk (16 floats per load), so its tile is kept to 2 loads per row
 #define KH_PF_U(QUANT) ((QUANT) ? 2 : 4)

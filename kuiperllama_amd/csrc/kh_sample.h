@@ -302,6 +302,28 @@ __device__ inline int kh_samp_block_max_i(KhSampSmem& s, int v) {
   for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) m = max(m, s.red_i[w]);
   return m;
 }
+// The FIRST maximum of the row lg[0 .. n) and its index (ties -> lowest index: amax_merge; a row without a maximum,
+// every entry NaN, gives 0x7fffffff).  Called by all threads with one slot per wave in red / red_i; THREAD 0 returns
+// with the row's (v, idx), the other threads with partial results.  Rows on 16-byte boundaries take the walker's
+// vector path.  No arithmetic enters a maximum, so the index is k_sample's pick on the same logits.
+__device__ __forceinline__ void kh_samp_row_amax(const float* lg, int n, float* red, int* red_i, float& v, int& idx) {
+  v = -INFINITY;
+  idx = 0x7fffffff;
+  kh_samp_for_global(lg, n, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
+  wave_amax(v, idx);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[wave] = v;
+    red_i[wave] = idx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v = red[0];
+    idx = red_i[0];
+#pragma unroll
+    for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) amax_merge(v, idx, red[w], red_i[w]);
+  }
+}
 
 // The sampler core: one draw from logits[0..n) with temperature T > 0, given l_max.  Called by all 1024 threads of
 // the workgroup; every thread returns the sampled index.

@@ -1,21 +1,20 @@
 // kh_seq.h — one full-depth B-token pass (kh_prefill.h) over lanes that belong to DIFFERENT sequences
 // (kh_model_seq_step, kh_model_generate_batch).  The reference decodes one sequence per process; here up to 8 (fp32) or
 // 4 (int8, wide fp32) independent sequences share every sweep of the weights.  wo, ffn13, w2 and the classifier do not
-// care where a token sits and are the prefill kernels themselves; four kernels do:
+// care where a token sits and are the prefill kernels themselves, and the layer loop is the prefill pass's own
+// (kh_model_prefill.hip::launch_pf_pass with a lane table); four kernels do:
 //   k_seq_embed   k_pf_embed with the lanes' tokens read from a device array (one entry per sequence slot), so that
 //                 the picks of one pass feed a later one without a host round trip, whichever lanes share it
 //   k_seq_qkv     k_pf_qkv's body (pf_qkv_body) under the lane table's addressing: RoPE row pos[b], cache row row[b]
-//   k_seq_attn    kh_attn.h: k_attn_decode's multi-token slice with position and K/V base per lane
-//   k_seq_pick    one workgroup per lane: the first maximum of the lane's logits row or, with the lane's temperature
-//                 > 0, the sampler core's draw with counter = position and the lane's own seed - what k_sample /
-//                 k_sample_topp pick from the same logits
+//   k_seq_attn    kh_attn.h: k_attn_decode's slice body (attn_slice_body) with position and K/V base per lane
+//   k_seq_pick    one workgroup per lane: the first maximum of the lane's logits row (kh_samp_row_amax) or, with the
+//                 lane's temperature > 0, the sampler core's draw with counter = position and the lane's own seed -
+//                 what k_sample / k_sample_topp pick from the same logits
 // gfx950 only.
 #pragma once
 #include "kh_prefill.h"
 #include "kh_sample.h"
-
-static_assert(KH_SEQ_BMAX == KH_PF_BMAX, "a lane table holds one entry per token of a prefill pass");
-#define KH_SEQ_MAX_SLOTS 64  // sequence slots of a model's cache (kh_model_seq_slots)
+#include "kh_seq_plan.h"  // KH_SEQ_SLOTS_MAX
 
 // embedding rows of the lanes' tokens -> X[B][dim]; lanes >= nvalid repeat the last valid lane (as k_pf_embed's
 // caller pads).  A token outside the vocabulary (the pick of a row without a maximum) copies nothing.
@@ -46,16 +45,16 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_seq_qkv(const KhSeqQkvArgs a) {
   pf_qkv_body<QUANT, SPLIT, B>(a.a, PfLaneAddr{a.lanes}, smem_raw);
 }
 
-// The tail of a pass.  Workgroup b: the maximum of row b of the logits and its first index (ties -> lowest index:
-// amax_merge, as k_spec_pick); the sampling parameters of the lane's slot from the device table; the pick;
+// The tail of a pass.  Workgroup b: the maximum of row b of the logits and its first index (kh_samp_row_amax, as
+// k_spec_pick); the sampling parameters of the lane's slot from the device table; the pick;
 // tok[slot[b]] = pick (the sequence's next pass reads it in k_seq_embed) and words[row[b]] = pick (may be null), the
 // sequence's word of position pos[b] - a sequence's words sit at its slot's rows, like its K/V.
 struct KhSeqPickArgs {
   const float* logits;  // [B][vstride]
   int vocab, vstride;
   KhSeqLanes lanes;
-  const KhSampParams* params;  // [KH_SEQ_MAX_SLOTS] device table, temperature <= 0: greedy
-  int32_t* tok;                // [KH_SEQ_MAX_SLOTS]
+  const KhSampParams* params;  // [KH_SEQ_SLOTS_MAX] device table, temperature <= 0: greedy
+  int32_t* tok;                // [KH_SEQ_SLOTS_MAX]
   int32_t* words;              // [cache_len] or null
 };
 static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_pick(const KhSeqPickArgs a) {
@@ -64,21 +63,10 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_pick(const KhSeq
   __shared__ int s_idx;
   const int b = blockIdx.x;
   const float* lg = a.logits + (size_t)b * (size_t)a.vstride;
-  float v = -INFINITY;
-  int idx = 0x7fffffff;
-  kh_samp_for_global(lg, a.vocab, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
-  wave_amax(v, idx);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    s.red[wave] = v;
-    s.red_i[wave] = idx;
-  }
-  __syncthreads();
+  float v;
+  int idx;
+  kh_samp_row_amax(lg, a.vocab, s.red, s.red_i, v, idx);
   if (threadIdx.x == 0) {
-    v = s.red[0];
-    idx = s.red_i[0];
-#pragma unroll
-    for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) amax_merge(v, idx, s.red[w], s.red_i[w]);
     s_max = v;
     s_idx = idx;
   }

@@ -4,7 +4,7 @@
 #pragma once
 #include <stdint.h>
 
-#define KH_SEQ_SLOTS_MAX 64    // kh_seq.h: KH_SEQ_MAX_SLOTS
+#define KH_SEQ_SLOTS_MAX 64    // sequence slots of a model's cache (kh_model_seq_slots), entries of the per-slot tables
 #define KH_SEQ_SLOT_MIN_ROWS 8
 
 // slot s = rows [s * slot_len, (s + 1) * slot_len); 0 = not a partition this library makes

@@ -175,3 +175,67 @@ def test_attention_plan_and_split_geometry(monkeypatch):
     assert _ffi.plan_attention(32, 4, 64, 131072, 255)["active_splits"] == 1
     monkeypatch.delenv("KH_ATTN_TS")
 
+
+
+# (head_num, kv_mul, head_size, seq_len): the four geometries of the test above and a kv_mul 7 one with enough KV
+# heads for the group path (28 heads in 4 groups; Qwen2.5-0.5B's 2 groups stay per-head)
+LAUNCH_GEOMETRIES = [(32, 4, 64, 131072), (14, 7, 64, 32768), (32, 1, 128, 2048), (6, 1, 32, 256), (28, 7, 64, 16384)]
+
+
+@pytest.mark.parametrize("wg", [256, 512])
+@pytest.mark.parametrize("geom", LAUNCH_GEOMETRIES)
+def test_attention_launch_plan_matches_the_per_position_plan(geom, wg, monkeypatch):
+    """kh_plan_attention_launch - the ONE planner behind launch_attn_decode and launch_seq_attn (kh_attn.h::
+    attn_launch_plan) - against kh_plan_attention, which is per position and checked against the documented rule
+    above: the grid carries exactly the workgroups that own timesteps at the launch's positions (the maximum over
+    them, on the path each takes), the instantiation carries the group path exactly when a position takes it, and a
+    device-positioned launch (no positions) keeps every split.  Both workgroup widths: at 256 threads the kv_mul 7
+    group path does not fit and the per-head kernel must be planned.  Exact integers."""
+    from kuiperllama_amd import _ffi
+    heads, kvm, hs, seq = geom
+    monkeypatch.delenv("KH_ATTN_TLONG", raising=False)
+    monkeypatch.delenv("KH_ATTN_TS", raising=False)
+    monkeypatch.setenv("KH_ATTN_WG", str(wg))
+    base = _ffi.plan_attention(heads, kvm, hs, seq, 0)
+    ns, ns_g = base["ns"], base["ns_g"]
+    assert (ns_g > 0) == (geom in ((32, 4, 64, 131072), (28, 7, 64, 16384)) and (kvm, wg) != (7, 256)), (geom, wg, base)
+    # the pivot of the position sets: the group path's threshold where there is one, else the middle of the cache
+    tl = base["t_long"] if ns_g > 0 else seq // 2
+    G = 1
+    while G < hs // 4:
+        G <<= 1
+    G = max(G, 16)
+    sets = [[0], [255, 256], [tl - 2, tl - 1], [tl + 40, 3, tl - 2, tl - 1], [seq - 1],
+            list(range(tl - 4, tl + 4)), list(range(1000, 1008)), []]
+    for positions in sets:
+        positions = [p for p in positions if 0 <= p < seq]  # a 256-row cache has no position 256 (or 1000)
+        got = _ffi.plan_attention_launch(heads, kvm, hs, seq, positions)
+        per = [_ffi.plan_attention(heads, kvm, hs, seq, p) for p in positions]
+        assert got["G"] == G, (geom, wg, positions, got)
+        if positions:
+            want_grid = max(1, max(p["workgroups"] for p in per))
+            want_group = ns_g > 0 and any(p["group_path"] == 1 for p in per)
+            want_hs = max([p["active_splits"] for p in per if not p["group_path"]], default=0)
+            want_gs = max([p["active_splits"] for p in per if p["group_path"]], default=0)
+        else:
+            want_grid = max(heads * ns, heads // kvm * ns_g)
+            want_group = ns_g > 0
+            want_hs, want_gs = ns, ns_g
+        assert got["grid"] == want_grid, (geom, wg, positions, got)
+        assert got["KVM"] == (kvm if want_group else 0), (geom, wg, positions, got)
+        assert (got["head_splits"], got["group_splits"]) == (want_hs, want_gs), (geom, wg, positions, got)
+        assert got["lds"] > 0
+
+
+def test_attention_launch_plan_refuses_bad_arguments():
+    import ctypes as C
+    from kuiperllama_amd import _ffi
+    L = _ffi.lib()
+    out, pos = (C.c_int32 * 6)(), (C.c_int32 * 2)(5, 6)
+    assert L.kh_plan_attention_launch(32, 4, 64, 4096, pos, 2, out) == 0
+    bad = [(32, 4, 64, 4096, pos, 2, None), (0, 4, 64, 4096, pos, 2, out), (32, 0, 64, 4096, pos, 2, out),
+           (30, 4, 64, 4096, pos, 2, out), (32, 4, 0, 4096, pos, 2, out), (32, 4, 64, 0, pos, 2, out),
+           (32, 4, 64, 4096, pos, -1, out), (32, 4, 64, 4096, None, 2, out), (32, 4, 64, 6, pos, 2, out),
+           (32, 4, 64, 4096, (C.c_int32 * 2)(5, -1), 2, out)]
+    for args in bad:
+        assert L.kh_plan_attention_launch(*args) == _ffi.KH_ERR_INVALID_ARG, args[:4] + args[5:6]
