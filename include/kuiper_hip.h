@@ -601,10 +601,11 @@ int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t* hint, int3
  * slot_len >= 8.  kh_plan_seq_slots is the host-only twin.
  * kh_model_seq_width: lanes per pass - kh_model_verify_width's value, refused alike.
  * kh_model_seq_prefill: kh_model_prefill on the rows of `slot` - n tokens at positions pos0 .. of that sequence, rows
- * bit-identical to the token-by-token path; the fed-token and log-prob records, which describe the batch-1 sequence,
- * are not written.  KH_ERR_RANGE for a slot outside [0, n_slots), pos0 + n > slot_len or a token outside the
- * vocabulary, otherwise kh_model_prefill's codes.  Does not synchronise.
- * kh_model_seq_fork copies K/V rows [0, n_rows) of every layer from src_slot to dst_slot on the model stream: with the
+ * bit-identical to the token-by-token path; the fed tokens are recorded at the slot's entries of the fed-token
+ * history (see kh_seq_opts below), the log-prob records are not written.  KH_ERR_RANGE for a slot outside [0, n_slots), pos0 + n > slot_len or a token outside the
+ * vocabulary, otherwise kh_model_prefill's codes.  Synchronises (the record is uploaded from the caller's array).
+ * kh_model_seq_fork copies K/V rows [0, n_rows) of every layer, and the n_rows entries of the fed-token history, from
+ * src_slot to dst_slot on the model stream: with the
  * prefill call, how n samples share one prefilled prompt (they hold copies; nothing reads a shared prefix once).
  * KH_ERR_INVALID_ARG for src == dst or n_rows <= 0, KH_ERR_RANGE for a slot outside the partition or n_rows >
  * slot_len.  Does not synchronise.
@@ -657,6 +658,66 @@ int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const int32_t* h_pr
                                  int32_t* n_words, float* h_elapsed_ms);
 int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
                       int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes);
+
+/* Sequence slots with per-sequence penalties, logit bias and log-probs: the `_ex` forms of kh_model_seq_step and
+ * kh_model_generate_batch_from.  Everything is stated per sequence IN THE CALL, as `samplings` already is: the model's
+ * own kh_model_set_sampling / _penalties / _logit_bias / _logprobs values are NOT consulted by the _ex calls (the plain
+ * entry points keep refusing while those are on).  kh_seq_opts, entry i for lane i (seq_step_ex) or sequence i
+ * (generate_batch_ex); a NULL array is the neutral value for everyone:
+ *   samplings       kh_sampling per sequence (temperature <= 0: greedy);
+ *   penalties       kh_penalties per sequence, kh_model_set_penalties' semantics over the SLOT's fed-token history;
+ *   n_bias          entries of sequence i's logit-bias list, 0 .. KH_SEQ_BIAS_MAX; the entries of sequence i follow
+ *                   those of sequence i - 1 in bias_ids / bias (kh_model_set_logit_bias' semantics);
+ *   logprobs_top_n  -1 off, else 0 .. KH_LOGPROBS_MAX_TOP for every sequence of the call: kh_model_set_logprobs'
+ *                   records, kept per CACHE ROW - the record of position p of slot s is entry s * slot_len + p.
+ * o == NULL, or everything in it neutral / off, is exactly the plain call: the same launches ending in k_seq_pick,
+ * nothing allocated, no history or record written.  Otherwise the pass ends in k_seq_tail (csrc/kh_seq.h), one
+ * workgroup per lane that chains the bit-exact cores of the batch-1 tail in its order - processing, maximum, greedy or
+ * sampled pick (counter = position), record - so lane i's pick and record are EXACTLY those of a batch-1 model with
+ * kh_model_set_penalties / _logit_bias / _sampling / _logprobs set to sequence i's values after the same history.
+ * The fed-token history is addressed by cache row like K/V (position p of slot s is entry s * slot_len + p; slot 0's
+ * is the batch-1 record).  It is written by kh_model_seq_prefill (the fed tokens; that call now synchronises), copied
+ * by kh_model_seq_fork (n_rows entries), set by kh_model_seq_set_history (any int32; entries outside the vocabulary
+ * count for nothing), and by the _ex calls while anything is on: seq_step_ex records each lane's fed token at its row
+ * ahead of the pass - entries below it are whatever earlier calls left, the contract of the K/V rows - and
+ * generate_batch_ex uploads every sequence's WHOLE prompt (also its n_cached part) to its slot's entries; k_seq_tail
+ * records each pick as the token fed next, except behind a slot's last position.  generate_batch_ex also resets the
+ * records of every sequence's fed-only positions to "none", as kh_model_generate_until does.
+ * Tables (per-slot parameters and bias lists, KH_PF_BMAX x vocab_size counters, pinned staging) and the records are
+ * allocated by the first call that needs them; a model that never asks allocates and launches nothing new.
+ * Before any launch or copy: the plain calls' codes (KH_ERR_UNSUPPORTED only for the geometries kh_model_score
+ * refuses), and KH_ERR_INVALID_ARG for invalid penalties (kh_model_set_penalties), a NaN or +inf bias, a duplicate id
+ * within one sequence's list, a negative n_bias, n_bias without bias_ids / bias, logprobs_top_n outside
+ * [-1, min(KH_LOGPROBS_MAX_TOP, vocab_size)]; KH_ERR_RANGE for a bias id outside the vocabulary or more than
+ * KH_SEQ_BIAS_MAX entries for one sequence.
+ * kh_model_seq_get_logprobs: kh_model_get_logprobs on the rows of `slot` - positions [pos0, pos0 + n) of its sequence;
+ * h_top_ids / h_top_lp are [n][w] with w = the logprobs_top_n of the last _ex call that had log-probs on.
+ * KH_ERR_UNSUPPORTED before any such call, KH_ERR_RANGE for a slot outside the partition or pos0 + n > slot_len.
+ * kh_seq_rank (host only, stateless; the ONE definition of "best" of best-of-n): sequence s's log-probs are
+ * h_lp[s * stride + p] for p in [first[s], n_words[s]); mean_lp[s] (may be NULL) = their sum in fp64, in index order,
+ * over their number - NaN where the range is empty or an entry is NaN; order[0 .. n_seq) = the sequences by that mean,
+ * descending, ties by ascending index, NaN last (by ascending index).  KH_ERR_INVALID_ARG for NULL pointers, n_seq <= 0,
+ * first[s] < 0 or n_words[s] > stride. */
+#define KH_SEQ_BIAS_MAX 64
+typedef struct kh_seq_opts {
+  const kh_sampling* samplings;   /* [n] or NULL: greedy */
+  const kh_penalties* penalties;  /* [n] or NULL: neutral */
+  const int32_t* n_bias;          /* [n] or NULL: none; entries of sequence i follow those of i - 1 in bias_ids / bias */
+  const int32_t* bias_ids;
+  const float* bias;
+  int32_t logprobs_top_n;         /* -1 off, 0 .. KH_LOGPROBS_MAX_TOP */
+} kh_seq_opts;
+int kh_model_seq_step_ex(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens, const int32_t* pos,
+                         const kh_seq_opts* o, int32_t* h_next);
+int kh_model_generate_batch_ex(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                               const int32_t* n_cached, const int32_t* total_steps, const kh_seq_opts* o,
+                               const int32_t* h_stop, int32_t n_stop, int32_t* h_words, int32_t words_stride,
+                               int32_t* n_words, float* h_elapsed_ms);
+int kh_model_seq_set_history(kh_model* m, int32_t slot, int32_t pos0, const int32_t* h_tokens, int32_t n);
+int kh_model_seq_get_logprobs(kh_model* m, int32_t slot, int32_t pos0, int32_t n, int32_t* h_token, float* h_lp,
+                              int32_t* h_top_ids, float* h_top_lp);
+int kh_seq_rank(int32_t n_seq, const float* h_lp, int32_t stride, const int32_t* first, const int32_t* n_words,
+                int32_t* order, double* mean_lp);
 
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,

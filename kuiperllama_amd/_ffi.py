@@ -26,7 +26,7 @@ EXPORTS = [
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
-    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
+    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
 ]
@@ -42,6 +42,7 @@ KH_FLAG_ATTN_MERGE_FENCED = 2
 KH_FLAG_PREFILL_EXACT = 4
 KH_FLAG_NO_CLS_SCREEN = 8
 KH_LOGPROBS_MAX_TOP = 20
+KH_SEQ_BIAS_MAX = 64
 
 
 class KhError(RuntimeError):
@@ -85,6 +86,12 @@ class Penalties(C.Structure):
 
 def penalties(repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0, last_n: int = 0) -> Penalties:
     return Penalties(float(repetition), float(presence), float(frequency), int(last_n))
+
+
+class SeqOpts(C.Structure):
+    """kh_seq_opts: per-sequence arrays of an _ex call (NULL: the neutral value for everyone); logprobs_top_n -1 off."""
+    _fields_ = [("samplings", C.POINTER(Sampling)), ("penalties", C.POINTER(Penalties)), ("n_bias", C.POINTER(C.c_int32)),
+                ("bias_ids", C.POINTER(C.c_int32)), ("bias", C.POINTER(C.c_float)), ("logprobs_top_n", C.c_int32)]
 
 
 class LookupOpts(C.Structure):
@@ -245,6 +252,15 @@ def lib() -> C.CDLL:
     L.kh_model_generate_batch_from.argtypes = [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
                                                C.POINTER(_i32), C.POINTER(Sampling), C.POINTER(_i32), _i32,
                                                C.POINTER(_i32), _i32, C.POINTER(_i32), C.POINTER(_f32)]
+    L.kh_model_seq_step_ex.argtypes = [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(SeqOpts),
+                                       C.POINTER(_i32)]
+    L.kh_model_generate_batch_ex.argtypes = [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                                             C.POINTER(_i32), C.POINTER(SeqOpts), C.POINTER(_i32), _i32,
+                                             C.POINTER(_i32), _i32, C.POINTER(_i32), C.POINTER(_f32)]
+    L.kh_model_seq_set_history.argtypes = [_vp, _i32, _i32, C.POINTER(_i32), _i32]
+    L.kh_model_seq_get_logprobs.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]
+    L.kh_seq_rank.argtypes = [_i32, C.POINTER(_f32), _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                              C.POINTER(C.c_double)]
     L.kh_plan_seq_batch.argtypes = [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32)]
     L.kh_model_prefill_gemm.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
     L.kh_model_time_prefill.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_f32)]

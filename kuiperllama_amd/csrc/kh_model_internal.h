@@ -6,7 +6,8 @@
 //                         template parameter, picked from and launched through kh_dispatch.h)
 //   kh_model_prefill.hip  B-token VALU prefill and the MFMA GEMM prefill (kh_prefill.h, kh_gemm.h,
 //                         kh_pattn.h kernels), and the B-lane pass over different sequences (kh_seq.h kernels)
-//   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch (host side)
+//   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
+//                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
 //   kh_model_screen.hip   the screened classifier of the greedy generate loop (kh_cls_screen.h kernels)
 //   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge and the screen
@@ -129,6 +130,20 @@ struct kh_model {
   int32_t* h_seq_tok_pin = nullptr;
   KhSampParams* h_seq_samp_pin = nullptr;
   int32_t* h_seq_words_pin = nullptr;
+  // ... with per-sequence processors or log-probs (kh_model_seq_step_ex, kh_model_generate_batch_ex; k_seq_tail):
+  // per-slot KhProcParams and bias lists [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX], the processing core's counters per LANE
+  // [KH_PF_BMAX][vocab] (zeroed once, the core re-arms them), pinned staging of the tables and of the history uploads
+  // [cache_len]; allocated by the first call that asks (seq_prepare_ex).  The history is d_hist and the records are
+  // d_lp_* below, both addressed by cache row.  seq_lp_top_n: the record width of the last such call (-1: none yet)
+  KhProcParams* d_seq_proc = nullptr;
+  int32_t* d_seq_bias_ids = nullptr;
+  float* d_seq_bias = nullptr;
+  int32_t* d_seq_cnt = nullptr;
+  KhProcParams* h_seq_proc_pin = nullptr;
+  int32_t* h_seq_bias_ids_pin = nullptr;
+  float* h_seq_bias_pin = nullptr;
+  int32_t* h_seq_hist_pin = nullptr;
+  int seq_lp_top_n = -1;
   // GEMM prefill (kh_gemm.h): slabs of KH_PG_TMAX token rows
   float *pg_x = nullptr, *pg_xn = nullptr, *pg_q = nullptr, *pg_att = nullptr, *pg_h = nullptr;
   float* pg_part = nullptr;     // partial rows of residual GEMMs that split K across workgroups
@@ -331,6 +346,13 @@ void set_state(kh_model* m, int token, int pos);
 int hist_write(kh_model* m, const int32_t* h_tokens, int n, int pos0);
 // log-probs on: the records of positions [pos0, pos0 + n) become "none" (fed, not sampled), on the model stream
 int lp_none(kh_model* m, int pos0, int n);
+// the record buffers (d_lp_*, lp_cap), all "none", allocated by whoever needs them first: kh_model_set_logprobs and
+// the sequence passes with log-probs (seq_prepare_ex); lp_top_n is the caller's to set
+int lp_ensure_records(kh_model* m);
+// records [pos0, pos0 + n) become "none" whatever the model's own setting says
+int lp_fill_none(kh_model* m, int pos0, int n);
+// records [pos0, pos0 + n) to the host with top lists of width w (kh_model_get_logprobs); synchronises
+int lp_read(kh_model* m, int pos0, int n, int w, int32_t* h_token, float* h_lp, int32_t* h_top_ids, float* h_top_lp);
 int ensure_pinned_words(kh_model* m, int n);
 int ensure_seq_cap(kh_model* m, int n);
 void destroy_step_graphs(kh_model* m);
@@ -381,8 +403,18 @@ int verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0);
 // a pass, before the first enqueue of a call.  seq_prefill_enqueue: kh_model_prefill's passes for n tokens at
 // positions pos0 .. of the sequence whose position 0 is cache row row0.  seq_pass_enqueue: one full-depth pass over
 // lanes [0, n) (entries >= n are padded here) - k_seq_embed from d_seq_tok, k_seq_qkv, k_seq_attn, the prefill
-// kernels, k_pf_cls, k_seq_pick; picks land in d_seq_tok[slot] and, with words, in d_seq_words[row].
+// kernels, k_pf_cls, k_seq_pick; picks land in d_seq_tok[slot] and, with words, in d_seq_words[row].  With a tail
+// description the pass ends in k_seq_tail instead of k_seq_pick: per-slot processing on the tables seq_prepare_ex
+// made (uploaded by the caller), the pick, and with top_n >= 0 the record of every lane's row.
+struct KhSeqTail {
+  int top_n;                 // -1: no records
+  const KhProcParams* proc;  // [KH_SEQ_SLOTS_MAX]
+  const int32_t* bias_ids;   // [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX]
+  const float* bias;
+  int32_t* cnt;              // [KH_PF_BMAX][vocab]
+};
 int seq_prepare(kh_model* m);
+int seq_prepare_ex(kh_model* m, bool records);  // behind seq_prepare: the tables of k_seq_tail, the record buffers
 int seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0);
-int seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words);
+int seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, const KhSeqTail* tail = nullptr);
 }  // namespace khm

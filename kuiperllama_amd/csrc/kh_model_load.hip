@@ -659,6 +659,10 @@ extern "C" void kh_model_destroy(kh_model* m) {
     if (q) (void)hipFree(q);
   for (void* q : {(void*)m->h_seq_tok_pin, (void*)m->h_seq_samp_pin, (void*)m->h_seq_words_pin})
     if (q) (void)hipHostFree(q);
+  for (void* q : {(void*)m->d_seq_proc, (void*)m->d_seq_bias_ids, (void*)m->d_seq_bias, (void*)m->d_seq_cnt})
+    if (q) (void)hipFree(q);
+  for (void* q : {(void*)m->h_seq_proc_pin, (void*)m->h_seq_bias_ids_pin, (void*)m->h_seq_bias_pin, (void*)m->h_seq_hist_pin})
+    if (q) (void)hipHostFree(q);
   if (m->d_samp) (void)hipFree(m->d_samp);
   for (void* q : {(void*)m->d_hist, (void*)m->d_proc, (void*)m->d_bias_ids, (void*)m->d_bias, (void*)m->d_cnt})
     if (q) (void)hipFree(q);

@@ -797,13 +797,39 @@ int khm::seq_prepare(kh_model* m) {
     if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return (int)hipErrorUnknown;
   return KH_OK;
 }
+int khm::seq_prepare_ex(kh_model* m, bool records) {
+  int rc;
+  const size_t slots = KH_SEQ_SLOTS_MAX, nb = (size_t)KH_SEQ_SLOTS_MAX * KH_SEQ_BIAS_MAX;
+  if (!m->d_seq_proc && (rc = dalloc(&m->d_seq_proc, slots)) != KH_OK) return rc;
+  if (!m->d_seq_bias_ids && (rc = dalloc(&m->d_seq_bias_ids, nb)) != KH_OK) return rc;
+  if (!m->d_seq_bias && (rc = dalloc(&m->d_seq_bias, nb)) != KH_OK) return rc;
+  if (!m->d_seq_cnt) {
+    const size_t n = (size_t)KH_PF_BMAX * (size_t)m->cfg.vocab_size;
+    int32_t* cnt = nullptr;
+    if ((rc = dalloc(&cnt, n)) != KH_OK) return rc;
+    if (hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, m->stream) != hipSuccess) {  // once: the core re-arms them
+      (void)hipFree(cnt);
+      return (int)hipErrorUnknown;
+    }
+    m->d_seq_cnt = cnt;
+  }
+  if (!m->h_seq_proc_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_proc_pin, sizeof(KhProcParams) * slots, hipHostMallocDefault));
+  if (!m->h_seq_bias_ids_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_bias_ids_pin, sizeof(int32_t) * nb, hipHostMallocDefault));
+  if (!m->h_seq_bias_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_bias_pin, sizeof(float) * nb, hipHostMallocDefault));
+  if (!m->h_seq_hist_pin)
+    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_hist_pin, sizeof(int32_t) * (size_t)m->cfg.cache_len, hipHostMallocDefault));
+  return records ? lp_ensure_records(m) : KH_OK;
+}
 int khm::seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0) {
   const int B = prefill_batch(m);
   for (int t0 = 0; t0 < n; t0 += B)
     launch_pf_pass(m, pf_run(toks + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B, /*full_depth=*/false, row0));
   return kh_launch_status();
 }
-int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words) {
+int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, const KhSeqTail* tail) {
   const kh_config& c = m->cfg;
   const int B = prefill_batch(m);
   for (int b = n; b < KH_PF_BMAX; ++b) {  // padding lanes rotate by the last valid lane's row; nothing of them is kept
@@ -813,6 +839,30 @@ int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words) {
   }
   launch_pf_pass(m, pf_lanes(lanes, n, B));
   launch_pf_cls(m, n, B);
+  if (tail) {
+    KhSeqTailArgs t;
+    t.logits = m->pf_logits;
+    t.vocab = c.vocab_size;
+    t.vstride = m->pf_vstride;
+    t.lanes = lanes;
+    t.params = m->d_seq_samp;
+    t.proc = tail->proc;
+    t.bias_ids = tail->bias_ids;
+    t.bias = tail->bias;
+    t.hist = m->d_hist;
+    t.slot_len = c.cache_len / m->seq_slots;
+    t.cnt = tail->cnt;
+    t.top_n = tail->top_n;
+    t.rec_token = m->d_lp_token;
+    t.rec_lp = m->d_lp_lp;
+    t.rec_top_ids = m->d_lp_top_ids;
+    t.rec_top_lp = m->d_lp_top_lp;
+    t.tok = m->d_seq_tok;
+    t.words = words ? m->d_seq_words : nullptr;
+    launch_log("k_seq_tail");
+    hipLaunchKernelGGL(k_seq_tail, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, t);
+    return kh_launch_status();
+  }
   KhSeqPickArgs t;
   t.logits = m->pf_logits;
   t.vocab = c.vocab_size;

@@ -1,14 +1,18 @@
 // kh_model_seq.hip — several independent sequences in one model: sequence slots of the K/V cache, the pass over lanes
 // of different sequences as an entry point (kh_model_seq_step) and the batched generate loop on top of it
-// (kh_model_generate_batch).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
+// (kh_model_generate_batch), and their _ex forms with per-sequence penalties, logit bias and log-probs (the pass then
+// ends in k_seq_tail).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
 // seq_pass_enqueue; kernels in kh_seq.h, kh_attn.h).  The reference decodes one sequence per process
 // (demo/main.cpp:16-50); n samples of a prompt are n runs of that loop there.
 // gfx950 only.
 #include <limits.h>
 #include <string.h>
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
+#include "kh_logit_proc.h"
 #include "kh_model_internal.h"
 #include "kh_sample.h"
 #include "kh_seq_plan.h"
@@ -40,6 +44,74 @@ void clear_slot_tables(kh_model* m) {
     m->h_seq_tok_pin[s] = 0;
     m->h_seq_samp_pin[s] = KhSampParams{0.f, 0, 1.f, 0u, 0u};
   }
+}
+// What an _ex call asks of the tail of its passes, checked: on = k_seq_tail runs instead of k_seq_pick (a processor
+// on at least one sequence, or log-probs); off[i] = where sequence i's bias entries start in the caller's arrays.
+struct SeqEx {
+  bool on = false;
+  int top_n = -1;
+  const kh_seq_opts* o = nullptr;
+  int32_t off[KH_SEQ_SLOTS_MAX + 1] = {0};
+};
+// the checks of kh_model_set_penalties / kh_model_set_logit_bias / kh_model_set_logprobs per sequence; no device call
+int seq_ex_parse(const kh_model* m, int n, const kh_seq_opts* o, SeqEx* out) {
+  out->o = o;
+  if (!o) return KH_OK;
+  const int V = m->cfg.vocab_size;
+  if (o->logprobs_top_n < -1 || o->logprobs_top_n > KH_LOGPROBS_MAX_TOP || o->logprobs_top_n > V)
+    return KH_ERR_INVALID_ARG;
+  out->top_n = o->logprobs_top_n;
+  out->on = out->top_n >= 0;
+  for (int i = 0; i < n; ++i) {
+    if (o->penalties) {
+      if (!kh_penalties_valid(&o->penalties[i])) return KH_ERR_INVALID_ARG;
+      out->on = out->on || !kh_penalties_neutral(&o->penalties[i]);
+    }
+    const int nb = o->n_bias ? o->n_bias[i] : 0;
+    if (nb < 0 || (nb > 0 && (!o->bias_ids || !o->bias))) return KH_ERR_INVALID_ARG;
+    if (nb > KH_SEQ_BIAS_MAX) return KH_ERR_RANGE;
+    const int32_t* ids = o->bias_ids + out->off[i];
+    const float* bias = o->bias + out->off[i];
+    int banned = 0;
+    for (int j = 0; j < nb; ++j) {
+      if (bias[j] != bias[j] || bias[j] == INFINITY) return KH_ERR_INVALID_ARG;
+      banned += bias[j] == -INFINITY;
+    }
+    for (int j = 0; j < nb; ++j)
+      if (ids[j] < 0 || ids[j] >= V) return KH_ERR_RANGE;
+    for (int j = 0; j < nb; ++j)
+      for (int k = 0; k < j; ++k)
+        if (ids[k] == ids[j]) return KH_ERR_INVALID_ARG;
+    if (nb > 0 && banned >= V) return KH_ERR_INVALID_ARG;  // nothing left to pick
+    out->off[i + 1] = out->off[i] + nb;
+    out->on = out->on || nb > 0;
+  }
+  return KH_OK;
+}
+// the per-slot processor tables of a call into pinned staging (entry i of the call is slot slot_of(i)), then uploaded
+template <class SlotOf>
+int upload_proc_tables(kh_model* m, int n, const SeqEx& ex, SlotOf slot_of) {
+  for (int s = 0; s < KH_SEQ_SLOTS_MAX; ++s) m->h_seq_proc_pin[s] = KhProcParams{1.f, 0.f, 0.f, 0, 0};
+  const kh_seq_opts* o = ex.o;
+  for (int i = 0; i < n; ++i) {
+    const int s = slot_of(i), nb = ex.off[i + 1] - ex.off[i];
+    KhProcParams& pp = m->h_seq_proc_pin[s];
+    if (o->penalties) pp = KhProcParams{o->penalties[i].repetition, o->penalties[i].presence, o->penalties[i].frequency,
+                                        o->penalties[i].last_n, 0};
+    pp.n_bias = nb;
+    for (int j = 0; j < nb; ++j) {
+      m->h_seq_bias_ids_pin[(size_t)s * KH_SEQ_BIAS_MAX + j] = o->bias_ids[ex.off[i] + j];
+      m->h_seq_bias_pin[(size_t)s * KH_SEQ_BIAS_MAX + j] = o->bias[ex.off[i] + j];
+    }
+  }
+  const size_t nb_all = (size_t)KH_SEQ_SLOTS_MAX * KH_SEQ_BIAS_MAX;
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_seq_proc, m->h_seq_proc_pin, sizeof(KhProcParams) * KH_SEQ_SLOTS_MAX,
+                              hipMemcpyHostToDevice, m->stream));
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_seq_bias_ids, m->h_seq_bias_ids_pin, sizeof(int32_t) * nb_all, hipMemcpyHostToDevice,
+                              m->stream));
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_seq_bias, m->h_seq_bias_pin, sizeof(float) * nb_all, hipMemcpyHostToDevice,
+                              m->stream));
+  return KH_OK;
 }
 }  // namespace
 
@@ -97,7 +169,8 @@ extern "C" int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_
   const int row0 = slot * len;
   if ((rc = kv_ensure_rows(m, row0, row0 + pos0 + n)) != KH_OK) return rc;
   if ((rc = seq_prepare(m)) != KH_OK) return rc;
-  return seq_prefill_enqueue(m, row0, h_tokens, n, pos0);
+  if ((rc = seq_prefill_enqueue(m, row0, h_tokens, n, pos0)) != KH_OK) return rc;
+  return hist_write(m, h_tokens, n, row0 + pos0);  // the slot's fed-token record, as kh_model_prefill from row 0
 }
 
 extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot, int32_t n_rows) {
@@ -117,15 +190,19 @@ extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot
     KH_CHECK_HIP(hipMemcpyAsync(m->kcache + dof, m->kcache + so, nb, hipMemcpyDeviceToDevice, m->stream));
     KH_CHECK_HIP(hipMemcpyAsync(m->vcache + dof, m->vcache + so, nb, hipMemcpyDeviceToDevice, m->stream));
   }
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_hist + (size_t)dst_slot * len, m->d_hist + (size_t)src_slot * len,
+                              sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToDevice, m->stream));
   return KH_OK;
 }
 
-// One pass.  Eager launches on the model stream; every check before the first of them.
-extern "C" int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens,
-                                 const int32_t* pos, const kh_sampling* samplings, int32_t* h_next) {
+// One pass.  Eager launches on the model stream; every check before the first of them.  o: the _ex call's options
+// (its samplings are `samplings` here), which replace the model's own settings - those refuse the plain call.
+namespace {
+int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens, const int32_t* pos,
+                 const kh_sampling* samplings, const kh_seq_opts* o, bool ex_call, int32_t* h_next) {
   if (!m || !slots || !h_tokens || !pos || !h_next || n <= 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
-  if (seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
+  if (ex_call ? !full_depth_supported(m) : seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
   if (n > verify_width(m)) return KH_ERR_RANGE;
   const int len = slot_len(m);
   for (int i = 0; i < n; ++i) {
@@ -136,11 +213,14 @@ extern "C" int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, c
       if (slots[j] == slots[i]) return KH_ERR_INVALID_ARG;  // two lanes of one sequence cannot share a pass
     if (samplings && !kh_sampling_valid(&samplings[i])) return KH_ERR_INVALID_ARG;
   }
-  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  SeqEx ex;
   int rc;
+  if ((rc = seq_ex_parse(m, n, o, &ex)) != KH_OK) return rc;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
   for (int i = 0; i < n; ++i)
     if ((rc = kv_ensure_rows(m, slots[i] * len, slots[i] * len + pos[i] + 1)) != KH_OK) return rc;
   if ((rc = seq_prepare(m)) != KH_OK) return rc;
+  if (ex.on && (rc = seq_prepare_ex(m, ex.top_n >= 0)) != KH_OK) return rc;
   clear_slot_tables(m);
   KhSeqLanes lanes;
   for (int i = 0; i < n; ++i) {
@@ -151,7 +231,17 @@ extern "C" int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, c
     if (samplings && !kh_sampling_greedy(&samplings[i])) m->h_seq_samp_pin[slots[i]] = kh_samp_params(&samplings[i]);
   }
   rc = upload_slot_tables(m);
-  if (rc == KH_OK) rc = seq_pass_enqueue(m, lanes, n, /*words=*/false);
+  const KhSeqTail tail{ex.top_n, m->d_seq_proc, m->d_seq_bias_ids, m->d_seq_bias, m->d_seq_cnt};
+  if (rc == KH_OK && ex.on) {
+    rc = upload_proc_tables(m, n, ex, [&](int i) { return slots[i]; });
+    for (int i = 0; i < n && rc == KH_OK; ++i) {  // the lanes' fed tokens at their rows of the history
+      m->h_seq_hist_pin[i] = h_tokens[i];
+      rc = (int)hipMemcpyAsync(m->d_hist + lanes.row[i], m->h_seq_hist_pin + i, sizeof(int32_t), hipMemcpyHostToDevice,
+                               m->stream);
+    }
+    if (rc == KH_OK && ex.top_n >= 0) m->seq_lp_top_n = ex.top_n;
+  }
+  if (rc == KH_OK) rc = seq_pass_enqueue(m, lanes, n, /*words=*/false, ex.on ? &tail : nullptr);
   if (rc == KH_OK)
     rc = (int)hipMemcpyAsync(m->h_seq_tok_pin, m->d_seq_tok, sizeof(int32_t) * KH_SEQ_SLOTS_MAX, hipMemcpyDeviceToHost,
                              m->stream);
@@ -160,6 +250,15 @@ extern "C" int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, c
   if (e != hipSuccess) return (int)e;
   for (int i = 0; i < n; ++i) h_next[i] = m->h_seq_tok_pin[slots[i]];
   return KH_OK;
+}
+}  // namespace
+extern "C" int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens,
+                                 const int32_t* pos, const kh_sampling* samplings, int32_t* h_next) {
+  return seq_step_run(m, n, slots, h_tokens, pos, samplings, nullptr, /*ex_call=*/false, h_next);
+}
+extern "C" int kh_model_seq_step_ex(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens,
+                                    const int32_t* pos, const kh_seq_opts* o, int32_t* h_next) {
+  return seq_step_run(m, n, slots, h_tokens, pos, o ? o->samplings : nullptr, o, /*ex_call=*/true, h_next);
 }
 
 // kh_model_generate_until for n_seq sequences at once, sequence s in slot s.  The fed-only part of every prompt runs
@@ -176,11 +275,33 @@ extern "C" int kh_model_generate_batch(kh_model* m, int32_t n_seq, const int32_t
 }
 // ... with the first n_cached[s] positions of sequence s already in its slot's rows (kh_model_seq_prefill,
 // kh_model_seq_fork): the call feeds the rest of the prompt
+namespace {
+int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                       const int32_t* n_cached, const int32_t* total_steps, const kh_sampling* samplings,
+                       const kh_seq_opts* o, bool ex_call, const int32_t* h_stop, int32_t n_stop, int32_t* h_words,
+                       int32_t words_stride, int32_t* n_words, float* h_elapsed_ms);
+}
 extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const int32_t* h_prompts,
                                             const int32_t* n_prompt, const int32_t* n_cached,
                                             const int32_t* total_steps, const kh_sampling* samplings,
                                             const int32_t* h_stop, int32_t n_stop, int32_t* h_words,
                                             int32_t words_stride, int32_t* n_words, float* h_elapsed_ms) {
+  return generate_batch_run(m, n_seq, h_prompts, n_prompt, n_cached, total_steps, samplings, nullptr, /*ex_call=*/false,
+                            h_stop, n_stop, h_words, words_stride, n_words, h_elapsed_ms);
+}
+// ... with per-sequence options in place of the model's own settings (see seq_step_run)
+extern "C" int kh_model_generate_batch_ex(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                                          const int32_t* n_cached, const int32_t* total_steps, const kh_seq_opts* o,
+                                          const int32_t* h_stop, int32_t n_stop, int32_t* h_words,
+                                          int32_t words_stride, int32_t* n_words, float* h_elapsed_ms) {
+  return generate_batch_run(m, n_seq, h_prompts, n_prompt, n_cached, total_steps, o ? o->samplings : nullptr, o,
+                            /*ex_call=*/true, h_stop, n_stop, h_words, words_stride, n_words, h_elapsed_ms);
+}
+namespace {
+int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                       const int32_t* n_cached, const int32_t* total_steps, const kh_sampling* samplings,
+                       const kh_seq_opts* o, bool ex_call, const int32_t* h_stop, int32_t n_stop, int32_t* h_words,
+                       int32_t words_stride, int32_t* n_words, float* h_elapsed_ms) {
   if (!m || !h_prompts || !n_prompt || !total_steps || !h_words || !n_words || n_seq <= 0 || words_stride <= 0 ||
       n_stop < 0 || (n_stop > 0 && !h_stop))
     return KH_ERR_INVALID_ARG;
@@ -197,7 +318,12 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
     n_tok += (size_t)n_prompt[s];
   }
   if (!tokens_in_vocab(m, h_prompts, n_tok)) return KH_ERR_RANGE;
-  if (seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
+  if (ex_call ? !full_depth_supported(m) : seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
+  SeqEx ex;
+  {
+    const int rc = seq_ex_parse(m, n_seq, o, &ex);
+    if (rc != KH_OK) return rc;
+  }
   return kh_api_guard([&]() -> int {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     int rc;
@@ -206,6 +332,8 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
       if ((rc = kv_ensure_rows(m, s * len, s * len + total_steps[s])) != KH_OK) return rc;
     }
     if ((rc = seq_prepare(m)) != KH_OK) return rc;
+    if (ex.on && (rc = seq_prepare_ex(m, ex.top_n >= 0)) != KH_OK) return rc;
+    const KhSeqTail tail{ex.top_n, m->d_seq_proc, m->d_seq_bias_ids, m->d_seq_bias, m->d_seq_cnt};
     // every early return below may leave launches and copies into pinned memory in flight: drain first
     auto fail = [&](int code) -> int {
       (void)hipStreamSynchronize(m->stream);
@@ -229,6 +357,20 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
       }
     }
     if ((rc = upload_slot_tables(m)) != KH_OK) return fail(rc);
+    if (ex.on) {
+      if ((rc = upload_proc_tables(m, n_seq, ex, [](int i) { return i; })) != KH_OK) return fail(rc);
+      // every sequence's whole prompt at its slot's entries of the history (its cached part too: the prompt is here
+      // whoever fed it), staged in pinned memory; the records of its fed-only positions become "none"
+      for (int s = 0; s < n_seq; ++s) {
+        const int np = n_prompt[s] < len ? n_prompt[s] : len;
+        memcpy(m->h_seq_hist_pin + (size_t)s * len, prompt[s], sizeof(int32_t) * (size_t)np);
+        if (hipMemcpyAsync(m->d_hist + (size_t)s * len, m->h_seq_hist_pin + (size_t)s * len,
+                           sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice, m->stream) != hipSuccess)
+          return fail((int)hipErrorUnknown);
+        if (ex.top_n >= 0 && pos[s] > 0 && (rc = lp_fill_none(m, s * len, pos[s])) != KH_OK) return fail(rc);
+      }
+      if (ex.top_n >= 0) m->seq_lp_top_n = ex.top_n;
+    }
     if (hipEventRecord(m->ev0, m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
     for (int s = 0; s < n_seq; ++s) {
       const int have = n_cached ? n_cached[s] : 0;
@@ -286,7 +428,7 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
           lanes.slot[i] = who[i];
           pos[who[i]] += 1;
         }
-        if ((rc = seq_pass_enqueue(m, lanes, n, /*words=*/true)) != KH_OK) return fail(rc);
+        if ((rc = seq_pass_enqueue(m, lanes, n, /*words=*/true, ex.on ? &tail : nullptr)) != KH_OK) return fail(rc);
         ++k;
       }
       if (k > 0 && (rc = mirror()) != KH_OK) return fail(rc);
@@ -305,6 +447,47 @@ extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const in
       n_words[s] = n_out;
     }
     if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
+    return KH_OK;
+  });
+}
+}  // namespace
+
+extern "C" int kh_model_seq_set_history(kh_model* m, int32_t slot, int32_t pos0, const int32_t* h_tokens, int32_t n) {
+  if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
+  const int len = slot_len(m);
+  if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > len) return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  return hist_write(m, h_tokens, n, slot * len + pos0);
+}
+
+extern "C" int kh_model_seq_get_logprobs(kh_model* m, int32_t slot, int32_t pos0, int32_t n, int32_t* h_token,
+                                         float* h_lp, int32_t* h_top_ids, float* h_top_lp) {
+  if (!m || n <= 0) return KH_ERR_INVALID_ARG;
+  if (!m->d_lp_token || m->seq_lp_top_n < 0) return KH_ERR_UNSUPPORTED;
+  const int len = slot_len(m);
+  if (slot < 0 || slot >= m->seq_slots || pos0 < 0 || (int64_t)pos0 + n > len) return KH_ERR_RANGE;
+  return lp_read(m, slot * len + pos0, n, m->seq_lp_top_n, h_token, h_lp, h_top_ids, h_top_lp);
+}
+
+extern "C" int kh_seq_rank(int32_t n_seq, const float* h_lp, int32_t stride, const int32_t* first,
+                           const int32_t* n_words, int32_t* order, double* mean_lp) {
+  if (n_seq <= 0 || !h_lp || !first || !n_words || !order || stride < 0) return KH_ERR_INVALID_ARG;
+  for (int s = 0; s < n_seq; ++s)
+    if (first[s] < 0 || n_words[s] > stride) return KH_ERR_INVALID_ARG;
+  return kh_api_guard([&]() -> int {
+    std::vector<double> mean((size_t)n_seq);
+    for (int s = 0; s < n_seq; ++s) {
+      double sum = 0.0;
+      for (int p = first[s]; p < n_words[s]; ++p) sum += (double)h_lp[(size_t)s * stride + p];
+      mean[s] = n_words[s] > first[s] ? sum / (double)(n_words[s] - first[s]) : (double)NAN;
+      if (mean_lp) mean_lp[s] = mean[s];
+      order[s] = s;
+    }
+    std::stable_sort(order, order + n_seq, [&](int32_t a, int32_t b) {
+      const bool na = std::isnan(mean[a]), nb = std::isnan(mean[b]);
+      if (na || nb) return !na && nb;
+      return mean[a] > mean[b];
+    });
     return KH_OK;
   });
 }

@@ -494,8 +494,9 @@ int hist_write(kh_model* m, const int32_t* h_tokens, int n, int pos0) {
   return KH_OK;
 }
 
-int lp_none(kh_model* m, int pos0, int n) {
-  if (m->lp_top_n < 0 || pos0 < 0 || pos0 >= m->lp_cap) return KH_OK;
+int lp_none(kh_model* m, int pos0, int n) { return m->lp_top_n < 0 ? KH_OK : lp_fill_none(m, pos0, n); }
+int lp_fill_none(kh_model* m, int pos0, int n) {
+  if (!m->d_lp_token || pos0 < 0 || pos0 >= m->lp_cap) return KH_OK;
   if (n > m->lp_cap - pos0) n = m->lp_cap - pos0;
   if (n <= 0) return KH_OK;
   const size_t k = KH_LOGPROBS_TOP;
@@ -504,6 +505,49 @@ int lp_none(kh_model* m, int pos0, int n) {
   KH_CHECK_HIP(hipMemsetAsync(m->d_lp_top_ids + pos0 * k, 0xFF, sizeof(int32_t) * n * k, m->stream));
   KH_CHECK_HIP(hipMemsetAsync(m->d_lp_top_lp + pos0 * k, 0xFF, sizeof(float) * n * k, m->stream));
   return KH_OK;
+}
+int lp_ensure_records(kh_model* m) {
+  if (m->d_lp_token) return KH_OK;
+  const size_t cap = (size_t)m->cfg.cache_len, k = KH_LOGPROBS_TOP;
+  int32_t *w = nullptr, *tok = nullptr, *ids = nullptr;
+  float *lp = nullptr, *tlp = nullptr;
+  int rc;
+  if ((rc = dalloc(&w, 1)) != KH_OK || (rc = dalloc(&tok, cap)) != KH_OK || (rc = dalloc(&lp, cap)) != KH_OK ||
+      (rc = dalloc(&ids, cap * k)) != KH_OK || (rc = dalloc(&tlp, cap * k)) != KH_OK) {
+    for (void* q : {(void*)w, (void*)tok, (void*)lp, (void*)ids, (void*)tlp})
+      if (q) (void)hipFree(q);
+    return rc;
+  }
+  m->d_lp_top_n = w;
+  m->d_lp_token = tok;
+  m->d_lp_lp = lp;
+  m->d_lp_top_ids = ids;
+  m->d_lp_top_lp = tlp;
+  m->lp_cap = (int)cap;
+  return lp_fill_none(m, 0, m->lp_cap);
+}
+int lp_read(kh_model* m, int pos0, int n, int top_w, int32_t* h_token, float* h_lp, int32_t* h_top_ids,
+            float* h_top_lp) {
+  return kh_api_guard([&]() -> int {
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    const size_t k = KH_LOGPROBS_TOP, w = top_w > 0 ? (size_t)top_w : 0;
+    std::vector<int32_t> ids(h_top_ids && w ? (size_t)n * k : 0);
+    std::vector<float> tlp(h_top_lp && w ? (size_t)n * k : 0);
+    if (h_token)
+      KH_CHECK_HIP(hipMemcpyAsync(h_token, m->d_lp_token + pos0, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (h_lp)
+      KH_CHECK_HIP(hipMemcpyAsync(h_lp, m->d_lp_lp + pos0, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (!ids.empty())
+      KH_CHECK_HIP(hipMemcpyAsync(ids.data(), m->d_lp_top_ids + pos0 * k, sizeof(int32_t) * ids.size(), hipMemcpyDeviceToHost, m->stream));
+    if (!tlp.empty())
+      KH_CHECK_HIP(hipMemcpyAsync(tlp.data(), m->d_lp_top_lp + pos0 * k, sizeof(float) * tlp.size(), hipMemcpyDeviceToHost, m->stream));
+    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    for (size_t r = 0; r < (size_t)n; ++r) {  // the records' stride -> the caller's
+      if (!ids.empty()) memcpy(h_top_ids + r * w, ids.data() + r * k, sizeof(int32_t) * w);
+      if (!tlp.empty()) memcpy(h_top_lp + r * w, tlp.data() + r * k, sizeof(float) * w);
+    }
+    return KH_OK;
+  });
 }
 
 int ensure_pinned_words(kh_model* m, int n) {
@@ -833,28 +877,9 @@ extern "C" int kh_model_set_logprobs(kh_model* m, int32_t top_n) {
   }
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   const int before = m->lp_top_n;
-  if (!m->d_lp_token) {  // the first "on": the records of every position, all "none"
-    const size_t cap = (size_t)m->cfg.cache_len, k = KH_LOGPROBS_TOP;
-    int32_t *w = nullptr, *tok = nullptr, *ids = nullptr;
-    float *lp = nullptr, *tlp = nullptr;
-    int rc;
-    if ((rc = dalloc(&w, 1)) != KH_OK || (rc = dalloc(&tok, cap)) != KH_OK || (rc = dalloc(&lp, cap)) != KH_OK ||
-        (rc = dalloc(&ids, cap * k)) != KH_OK || (rc = dalloc(&tlp, cap * k)) != KH_OK) {
-      for (void* q : {(void*)w, (void*)tok, (void*)lp, (void*)ids, (void*)tlp})
-        if (q) (void)hipFree(q);
-      return rc;
-    }
-    m->d_lp_top_n = w;
-    m->d_lp_token = tok;
-    m->d_lp_lp = lp;
-    m->d_lp_top_ids = ids;
-    m->d_lp_top_lp = tlp;
-    m->lp_cap = (int)cap;
-    m->lp_top_n = 0;
-    if ((rc = lp_none(m, 0, m->lp_cap)) != KH_OK) {
-      m->lp_top_n = before;
-      return rc;
-    }
+  {  // the first "on": the records of every position, all "none"
+    const int rc = lp_ensure_records(m);
+    if (rc != KH_OK) return rc;
   }
   m->lp_top_n = top_n;
   const int rc = proc_commit(m);  // the device copies of the processors' and the sampler's parameters exist
@@ -882,26 +907,7 @@ extern "C" int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32
   if (!m || n <= 0) return KH_ERR_INVALID_ARG;
   if (!m->d_lp_token) return KH_ERR_UNSUPPORTED;
   if (pos0 < 0 || (int64_t)pos0 + n > m->lp_cap) return KH_ERR_RANGE;
-  return kh_api_guard([&]() -> int {
-    KH_CHECK_HIP(hipSetDevice(m->opts.device));
-    const size_t k = KH_LOGPROBS_TOP, w = m->lp_top_n > 0 ? (size_t)m->lp_top_n : 0;
-    std::vector<int32_t> ids(h_top_ids && w ? (size_t)n * k : 0);
-    std::vector<float> tlp(h_top_lp && w ? (size_t)n * k : 0);
-    if (h_token)
-      KH_CHECK_HIP(hipMemcpyAsync(h_token, m->d_lp_token + pos0, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
-    if (h_lp)
-      KH_CHECK_HIP(hipMemcpyAsync(h_lp, m->d_lp_lp + pos0, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
-    if (!ids.empty())
-      KH_CHECK_HIP(hipMemcpyAsync(ids.data(), m->d_lp_top_ids + pos0 * k, sizeof(int32_t) * ids.size(), hipMemcpyDeviceToHost, m->stream));
-    if (!tlp.empty())
-      KH_CHECK_HIP(hipMemcpyAsync(tlp.data(), m->d_lp_top_lp + pos0 * k, sizeof(float) * tlp.size(), hipMemcpyDeviceToHost, m->stream));
-    KH_CHECK_HIP(hipStreamSynchronize(m->stream));
-    for (size_t r = 0; r < (size_t)n; ++r) {  // the records' stride -> the caller's
-      if (!ids.empty()) memcpy(h_top_ids + r * w, ids.data() + r * k, sizeof(int32_t) * w);
-      if (!tlp.empty()) memcpy(h_top_lp + r * w, tlp.data() + r * k, sizeof(float) * w);
-    }
-    return KH_OK;
-  });
+  return lp_read(m, pos0, n, m->lp_top_n, h_token, h_lp, h_top_ids, h_top_lp);
 }
 
 extern "C" int kh_model_generate(kh_model* m, const int32_t* h_prompt, int32_t n_prompt,

@@ -10,8 +10,13 @@
 //   k_seq_pick    one workgroup per lane: the first maximum of the lane's logits row (kh_samp_row_amax) or, with the
 //                 lane's temperature > 0, the sampler core's draw with counter = position and the lane's own seed -
 //                 what k_sample / k_sample_topp pick from the same logits
+// and, in place of k_seq_pick when a call states penalties, a logit bias or log-probs per sequence
+// (kh_model_seq_step_ex, kh_model_generate_batch_ex):
+//   k_seq_tail    one workgroup per lane: k_sample_lp's chain on the lane's row - the processing core on the slot's
+//                 parameters and history, the maximum, the greedy or sampled pick, the record of the lane's cache row
 // gfx950 only.
 #pragma once
+#include "kh_logprobs.h"
 #include "kh_prefill.h"
 #include "kh_sample.h"
 #include "kh_seq_plan.h"  // KH_SEQ_SLOTS_MAX
@@ -77,5 +82,78 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_pick(const KhSeq
   if (threadIdx.x == 0) {
     a.tok[a.lanes.slot[b]] = pick;
     if (a.words) a.words[a.lanes.row[b]] = pick;
+  }
+}
+
+// The tail of a pass with per-sequence processors or log-probs: k_sample_lp's steps in its order, one workgroup per
+// lane on per-slot state.  Workgroup b, slot = slot[b], pos = pos[b], row = row[b]:
+//   1. proc[slot] says anything: kh_logit_process_core in place on row b of the logits, over the slot's history -
+//      hist is addressed by cache row like K/V, position p of the slot is hist[row - pos + p] - with the slot's bias
+//      list and the LANE's counters (lanes run side by side; cnt is zero before and after);
+//   2. the first maximum of the processed row; 3. the pick: the sampler core (counter = pos) where the slot's
+//   temperature > 0, else that maximum;
+//   4. top_n >= 0: the record of cache row `row` - the pick, its log-prob and the top top_n of the logits the pick was
+//      made from; entries from top_n on are "none" (-1, NaN), as k_sample_lp leaves them;
+//   5. tok[slot] = words[row] = pick, and hist[row + 1] = pick unless pos is the slot's last position: row + 1 is then
+//      position 0 of the next slot.
+// LDS: KhSampSmem + KhLpSmem, as k_sample_lp.  No scratch, plain vector stores.
+struct KhSeqTailArgs {
+  float* logits;  // [B][vstride], processed in place
+  int vocab, vstride;
+  KhSeqLanes lanes;
+  const KhSampParams* params;  // [KH_SEQ_SLOTS_MAX] device table, temperature <= 0: greedy
+  const KhProcParams* proc;    // [KH_SEQ_SLOTS_MAX] device table, neutral: nothing is processed
+  const int32_t* bias_ids;     // [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX]
+  const float* bias;           // [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX]
+  int32_t* hist;               // [cache_len + 1] token fed at every cache row
+  int slot_len;
+  int32_t* cnt;                // [KH_PF_BMAX][vocab] counters, zero between launches
+  int top_n;                   // -1: no record
+  int32_t* rec_token;          // [cache_len]
+  float* rec_lp;               // [cache_len]
+  int32_t* rec_top_ids;        // [cache_len][KH_LOGPROBS_TOP]
+  float* rec_top_lp;           // [cache_len][KH_LOGPROBS_TOP]
+  int32_t* tok;                // [KH_SEQ_SLOTS_MAX]
+  int32_t* words;              // [cache_len] or null
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_tail(const KhSeqTailArgs a) {
+  __shared__ KhSampSmem s;
+  __shared__ KhLpSmem t;
+  __shared__ float s_max;
+  __shared__ int s_idx;
+  const int b = blockIdx.x;
+  const int slot = a.lanes.slot[b], pos = a.lanes.pos[b], row = a.lanes.row[b];
+  float* lg = a.logits + (size_t)b * (size_t)a.vstride;
+  const KhProcParams pp = a.proc[slot];
+  if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0)  // uniform
+    kh_logit_process_core(lg, a.vocab, a.hist + (row - pos), pos, pp, a.bias_ids + (size_t)slot * KH_SEQ_BIAS_MAX,
+                          a.bias + (size_t)slot * KH_SEQ_BIAS_MAX, a.cnt + (size_t)b * (size_t)a.vocab);
+  float v;
+  int idx;
+  kh_samp_row_amax(lg, a.vocab, s.red, s.red_i, v, idx);
+  if (threadIdx.x == 0) {
+    s_max = v;
+    s_idx = idx;
+  }
+  __syncthreads();
+  const KhSampParams p = a.params[slot];
+  const float lmax = s_max;
+  int pick = s_idx;
+  if (p.temperature > 0.f) pick = kh_sample_core(s, lg, a.vocab, lmax, p, (uint32_t)pos);  // uniform
+  if (a.top_n >= 0) {
+    const int top_n = min(a.top_n, min(KH_LOGPROBS_TOP, a.vocab));
+    const size_t r0 = (size_t)row * KH_LOGPROBS_TOP;
+    kh_logprobs_core(s, t, lg, a.vocab, lmax, pick, top_n, nullptr, a.rec_lp + row, a.rec_top_ids + r0,
+                     a.rec_top_lp + r0);
+    if (threadIdx.x == 0) a.rec_token[row] = pick;
+    if ((int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
+      a.rec_top_ids[r0 + threadIdx.x] = -1;
+      a.rec_top_lp[r0 + threadIdx.x] = __uint_as_float(0xffffffffu);
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.tok[slot] = pick;
+    if (a.words) a.words[row] = pick;
+    if (pos + 1 < a.slot_len) a.hist[row + 1] = pick;
   }
 }

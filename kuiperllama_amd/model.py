@@ -47,6 +47,61 @@ def plan_seq_slots(cache_len: int, n_slots: int) -> int:
     return int(out.value)
 
 
+def _seq_opts(n: int, sp, penalties, logit_bias, logprobs, what: str):
+    """kh_seq_opts of an _ex call and the arrays it points to (keep both alive across the call): penalties = None | [n]
+    of None | dict of set_penalties()'s keys | _ffi.Penalties; logit_bias = None | [n] of None | {id: value};
+    logprobs = None | top_n.  Wrong lengths are refused here, before the library is called."""
+    keep = [sp]
+    o = _ffi.SeqOpts()
+    o.samplings = sp if sp is not None else None
+    if penalties is not None:
+        penalties = list(penalties)
+        if len(penalties) != n:
+            raise ValueError(f"{what}: {len(penalties)} penalty entries for {n} sequences")
+        pa = (_ffi.Penalties * max(n, 1))()
+        for i, p in enumerate(penalties):
+            v = _ffi.penalties() if p is None else p if isinstance(p, _ffi.Penalties) else _ffi.penalties(**p)
+            pa[i] = _ffi.Penalties(v.repetition, v.presence, v.frequency, v.last_n)
+        keep.append(pa)
+        o.penalties = pa
+    if logit_bias is not None:
+        logit_bias = list(logit_bias)
+        if len(logit_bias) != n:
+            raise ValueError(f"{what}: {len(logit_bias)} logit-bias entries for {n} sequences")
+        items = [sorted((int(k), float(v)) for k, v in (b or {}).items()) for b in logit_bias]
+        nb = _i32_array([len(it) for it in items])
+        flat = [kv for it in items for kv in it]
+        ids = _i32_array([k for k, _ in flat])
+        vals = (C.c_float * max(len(flat), 1))(*[v for _, v in flat])
+        keep += [nb, ids, vals]
+        o.n_bias, o.bias_ids, o.bias = nb, ids, vals
+    o.logprobs_top_n = -1 if logprobs is None else int(logprobs)
+    return o, keep
+
+
+def seq_rank(lp_rows, first: Sequence[int], n_words: Sequence[int]) -> Tuple[List[int], np.ndarray]:
+    """The ranking of best-of-n (kh_seq_rank; host only): lp_rows[s] holds sequence s's per-position log-probs, of which
+    positions [first[s], n_words[s]) count.  Returns (order, mean): mean[s] the float64 mean of those log-probs (NaN
+    where there are none), order the sequences by it - descending, ties by index, NaN last."""
+    rows = [np.asarray(r, np.float32).ravel() for r in lp_rows]
+    n = len(rows)
+    first, n_words = list(first), list(n_words)
+    if len(first) != n or len(n_words) != n:
+        raise ValueError(f"seq_rank: {n} rows, {len(first)} first positions, {len(n_words)} word counts")
+    stride = max([len(r) for r in rows] + [1])
+    lp = np.full((max(n, 1), stride), np.nan, np.float32)
+    for s, r in enumerate(rows):
+        if int(n_words[s]) > len(r):
+            raise ValueError(f"seq_rank: row {s} holds {len(r)} log-probs, n_words says {n_words[s]}")
+        lp[s, :len(r)] = r
+    order = (C.c_int32 * max(n, 1))()
+    mean = np.empty(max(n, 1), np.float64)
+    _ffi.check(_ffi.lib().kh_seq_rank(n, lp.ctypes.data_as(C.POINTER(C.c_float)), stride, _i32_array(first),
+                                      _i32_array(n_words), order, mean.ctypes.data_as(C.POINTER(C.c_double))),
+               "kh_seq_rank")
+    return list(order[:n]), mean[:n]
+
+
 def plan_seq_batch(first_pos: Sequence[int], total_steps: Sequence[int], width: int) -> List[List[int]]:
     """The passes generate_batch runs while no sequence stops early (kh_plan_seq_batch; host only): per pass the
     sequences in its lanes.  first_pos[s] = len(prompt s) - 1, the first position a pass feeds."""
@@ -85,6 +140,8 @@ class KuiperModel:
         self._h = C.c_void_p(handle)
         self.spec = spec
         self._keep = keepalive
+        self._seq_slots = 1      # seq_slots(): the partition best_of() widens when it is too small
+        self._seq_top_n = None   # the logprobs= of the last seq_step / generate_batch that had one: seq_logprobs' width
         cfg = _ffi.Config()
         _ffi.check(_ffi.lib().kh_model_get_config(self._h, C.byref(cfg)), "kh_model_get_config")
         self.cfg = cfg
@@ -431,6 +488,7 @@ class KuiperModel:
         rows [s * slot_len, (s + 1) * slot_len): read_kv(layer, s * slot_len + p, ..) is position p of its sequence."""
         out = C.c_int32(0)
         _ffi.check(_ffi.lib().kh_model_seq_slots(self._h, int(n_slots), C.byref(out)), "kh_model_seq_slots")
+        self._seq_slots = int(n_slots)
         return int(out.value)
 
     def seq_width(self) -> int:
@@ -452,28 +510,48 @@ class KuiperModel:
         torch.cuda.synchronize()
 
     def seq_step(self, slots: Sequence[int], tokens: Sequence[int], pos: Sequence[int],
-                 samplings: Optional[Sequence] = None) -> List[int]:
+                 samplings: Optional[Sequence] = None, penalties: Optional[Sequence] = None,
+                 logit_bias: Optional[Sequence] = None, logprobs: Optional[int] = None) -> List[int]:
         """One pass over len(slots) <= seq_width() lanes in distinct slots (kh_model_seq_step): lane i feeds tokens[i]
         at position pos[i] of slot slots[i]; returns the picks - greedy, or sampled where samplings[i] (None | dict of
-        temperature / top_k / top_p / seed) has a temperature > 0 - exactly a predict loop's on a batch-1 model."""
+        temperature / top_k / top_p / seed) has a temperature > 0 - exactly a predict loop's on a batch-1 model.
+        penalties (per lane None | dict of set_penalties()'s keys), logit_bias (per lane None | {id: value}) and
+        logprobs (None | top_n for every lane) go through kh_model_seq_step_ex: the pick is then the batch-1 model's
+        under those settings over the slot's fed-token history (seq_prefill, seq_fork, seq_set_history, earlier
+        passes), the record of the lane's position is read with seq_logprobs(); the model's own set_* values are not
+        consulted.  With all three None this is the plain call."""
         slots, tokens, pos = list(slots), list(tokens), list(pos)
         n = len(slots)
         if len(tokens) != n or len(pos) != n:
             raise ValueError(f"seq_step: {n} slots, {len(tokens)} tokens, {len(pos)} positions")
         sp = _sampling_array(samplings, n, "seq_step")
         nxt = (C.c_int32 * max(n, 1))()
+        if penalties is not None or logit_bias is not None or logprobs is not None:
+            o, keep = _seq_opts(n, sp, penalties, logit_bias, logprobs, "seq_step")
+            _ffi.check(_ffi.lib().kh_model_seq_step_ex(self._h, n, _i32_array(slots), _i32_array(tokens),
+                                                       _i32_array(pos), C.byref(o), nxt), "kh_model_seq_step_ex")
+            del keep
+            if logprobs is not None:
+                self._seq_top_n = int(logprobs)
+            return list(nxt[:n])
         _ffi.check(_ffi.lib().kh_model_seq_step(self._h, n, _i32_array(slots), _i32_array(tokens), _i32_array(pos), sp,
                                                 nxt), "kh_model_seq_step")
         return list(nxt[:n])
 
     def generate_batch(self, prompts: Sequence[Sequence[int]], total_steps, samplings: Optional[Sequence] = None,
-                       stop: Sequence[int] = (), cached: Optional[Sequence[int]] = None) -> Tuple[List[List[int]], float]:
+                       stop: Sequence[int] = (), cached: Optional[Sequence[int]] = None,
+                       penalties: Optional[Sequence] = None, logit_bias: Optional[Sequence] = None,
+                       logprobs: Optional[int] = None) -> Tuple[List[List[int]], float]:
         """generate() for len(prompts) <= n_slots sequences at once, sequence s in slot s (kh_model_generate_batch):
         seq_width() sequences share every pass over the weights.  total_steps: one int for all or one per sequence;
         samplings: None (all greedy) or one entry per sequence (None | dict of temperature / top_k / top_p / seed).
         cached: None, or per sequence how many leading prompt positions seq_prefill / seq_fork already left in its
         slot (kh_model_generate_batch_from).  Returns (words per sequence, elapsed_ms); every word list is exactly
-        generate(prompt, total, stop=stop)'s on a batch-1 model with that entry set through set_sampling()."""
+        generate(prompt, total, stop=stop)'s on a batch-1 model with that entry set through set_sampling().
+        penalties / logit_bias (one entry per sequence: None | dict of set_penalties()'s keys, None | {id: value}) and
+        logprobs (None | top_n) go through kh_model_generate_batch_ex: the words are then that model's under
+        set_penalties / set_logit_bias / set_logprobs too, and seq_logprobs(s, 0, len(words[s])) its records.  The
+        model's own set_* values are not consulted.  With all three None this is the plain call."""
         prompts = [list(p) for p in prompts]
         n = len(prompts)
         totals = [int(total_steps)] * n if isinstance(total_steps, (int, np.integer)) else [int(t) for t in total_steps]
@@ -490,11 +568,69 @@ class KuiperModel:
         nw = (C.c_int32 * n)()
         ms = C.c_float(0.0)
         flat = [t for p in prompts for t in p]
+        if penalties is not None or logit_bias is not None or logprobs is not None:
+            o, keep = _seq_opts(n, sp, penalties, logit_bias, logprobs, "generate_batch")
+            _ffi.check(_ffi.lib().kh_model_generate_batch_ex(
+                self._h, n, _i32_array(flat), _i32_array([len(p) for p in prompts]),
+                None if cached is None else _i32_array(cached), _i32_array(totals), C.byref(o), _i32_array(st), len(st),
+                words, stride, nw, C.byref(ms)), "kh_model_generate_batch_ex")
+            del keep
+            if logprobs is not None:
+                self._seq_top_n = int(logprobs)
+            return [list(words[s * stride:s * stride + nw[s]]) for s in range(n)], float(ms.value)
         _ffi.check(_ffi.lib().kh_model_generate_batch_from(
             self._h, n, _i32_array(flat), _i32_array([len(p) for p in prompts]),
             None if cached is None else _i32_array(cached), _i32_array(totals), sp, _i32_array(st), len(st), words,
             stride, nw, C.byref(ms)), "kh_model_generate_batch")
         return [list(words[s * stride:s * stride + nw[s]]) for s in range(n)], float(ms.value)
+
+    def seq_set_history(self, slot: int, tokens: Sequence[int], pos0: int = 0) -> None:
+        """The fed-token history of positions pos0 .. of sequence slot `slot` (kh_model_seq_set_history): what the
+        penalties of a later seq_step / generate_batch on that slot count, for rows that were not fed through
+        seq_prefill (write_kv, a restored cache)."""
+        _ffi.check(_ffi.lib().kh_model_seq_set_history(self._h, int(slot), int(pos0), _i32_array(tokens), len(tokens)),
+                   "kh_model_seq_set_history")
+
+    def seq_logprobs(self, slot: int, pos0: int, n: int, top_n: Optional[int] = None) -> dict:
+        """logprobs() on the rows of sequence slot `slot` (kh_model_seq_get_logprobs): the records of positions
+        [pos0, pos0 + n) that seq_step / generate_batch with logprobs= left.  The width of the top lists is that of
+        the last such call (top_n, when given, must state the same)."""
+        w = self._seq_top_n if top_n is None else int(top_n)
+        if w is None or w != self._seq_top_n:
+            raise ValueError(f"seq_logprobs: the last call with logprobs= on this model said {self._seq_top_n}")
+        out = {"token": np.empty(max(n, 0), np.int32), "logprob": np.empty(max(n, 0), np.float32),
+               "top_ids": np.empty((max(n, 0), w), np.int32), "top_logprobs": np.empty((max(n, 0), w), np.float32)}
+        _ffi.check(_ffi.lib().kh_model_seq_get_logprobs(self._h, int(slot), int(pos0), int(n), out["token"].ctypes.data,
+                                                        out["logprob"].ctypes.data, out["top_ids"].ctypes.data,
+                                                        out["top_logprobs"].ctypes.data), "kh_model_seq_get_logprobs")
+        return out
+
+    seq_rank = staticmethod(seq_rank)
+
+    def best_of(self, prompt: Sequence[int], n: int, total_steps: int, sampling: dict, stop: Sequence[int] = (),
+                penalties: Optional[dict] = None, logit_bias: Optional[dict] = None, top_n: int = 0) -> List[dict]:
+        """n samples of one prompt, best first: one seq_prefill of the prompt's fed-only part into slot 0, n - 1
+        seq_forks, one generate_batch(cached=..) with seeds seed, seed + 1, .. of `sampling` (and the shared penalties
+        / logit_bias), then seq_rank on the sampled positions' log-probs.  Returns [{"words", "mean_logprob", "seed"}]
+        in rank order; sample i is exactly generate() of a batch-1 model under seed + i.  Cuts the cache into n slots
+        when the model has fewer."""
+        prompt, n, total_steps = [int(t) for t in prompt], int(n), int(total_steps)
+        if n <= 0 or not prompt:
+            raise ValueError("best_of: no sample, or an empty prompt")
+        if self._seq_slots < n:
+            self.seq_slots(n)
+        seed0 = int(sampling.get("seed", 0))
+        fed = min(len(prompt) - 1, total_steps)
+        if fed > 0:
+            self.seq_prefill(0, prompt[:fed])
+            for s in range(1, n):
+                self.seq_fork(0, s, fed)
+        words, _ = self.generate_batch([prompt] * n, total_steps, [dict(sampling, seed=seed0 + s) for s in range(n)],
+                                       stop=stop, cached=[fed] * n, penalties=[penalties] * n,
+                                       logit_bias=[logit_bias] * n, logprobs=int(top_n))
+        rows = [self.seq_logprobs(s, 0, len(w))["logprob"] if w else np.empty(0, np.float32) for s, w in enumerate(words)]
+        order, mean = seq_rank(rows, [min(fed, len(w)) for w in words], [len(w) for w in words])
+        return [{"words": words[s], "mean_logprob": float(mean[s]), "seed": seed0 + s} for s in order]
 
     def prefill_gemm(self, tokens: Sequence[int], pos0: int = 0) -> None:
         """Forward of `tokens` at positions pos0.. as fp32-MFMA GEMMs (up to 128 tokens per weight

@@ -16,7 +16,7 @@
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
-//               [--lookup [ngram_max]] [--hint id,id,...] [--parallel N]
+//               [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -39,6 +39,10 @@
 // kh_model_generate_batch_from): the cache is cut into N slots, the prompt is prefilled once and forked, the seeds are
 // --seed, --seed + 1, ...; each sequence's ids are printed on a line of their own, then the aggregate "steps/s".
 // Greedy without --temperature (N equal lines).  Penalties, bias and log-probs are refused, as by the library.
+// --best-of N: --parallel's N samples (seeds --seed, --seed + 1, ...) through kh_model_generate_batch_ex, which takes
+// the sampler, penalty, bias and --logprobs flags per sequence (the model's own settings are not consulted), ranked by
+// kh_seq_rank on the mean log-prob of each sample's generated tokens: one line per sample, best first,
+// "mean_logprob seed | id id ...", then the aggregate "steps/s".  --logprobs defaults to 0 here.
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <cmath>
 #include <chrono>
@@ -59,7 +63,7 @@ static void usage() {
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
-               "       [--lookup [ngram_max]] [--hint id,id,...] [--parallel N]\n");
+               "       [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N]\n");
 }
 
 int main(int argc, char** argv) {
@@ -79,6 +83,7 @@ int main(int argc, char** argv) {
   bool lookup = false;  // --lookup [ngram_max] (kh_model_generate_lookup)
   kh_lookup_opts lk{0, 0, 0, nullptr, 0};
   int parallel = 0;  // --parallel N (kh_model_generate_batch)
+  int best_of = 0;   // --best-of N (kh_model_generate_batch_ex, kh_seq_rank)
   std::vector<int32_t> hint;  // --hint
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
@@ -118,6 +123,7 @@ int main(int argc, char** argv) {
     else if (a == "--logprobs") logprobs = std::atoi(next());
     else if (a == "--score") score = true;
     else if (a == "--parallel") parallel = std::atoi(next());
+    else if (a == "--best-of") best_of = std::atoi(next());
     else if (a == "--lookup") {
       lookup = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') lk.ngram_max = std::atoi(argv[++i]);
@@ -275,6 +281,65 @@ int main(int argc, char** argv) {
       std::printf("\n");
     }
     std::printf("sum_logprob:%.6f\nperplexity:%.6f\n", sum, cnt > 1 ? std::exp(-sum / (cnt - 1)) : std::nan(""));
+    if (tok) kh_spm_destroy(tok);
+    if (bpe) kh_bpe_destroy(bpe);
+    kh_model_destroy(m);
+    return 0;
+  }
+  if (best_of > 0) {
+    // --parallel's samples with everything stated per sequence, then ranked
+    const int N = best_of, top_n = logprobs < 0 ? 0 : logprobs;
+    int32_t slot_len = 0;
+    const int32_t np = (int32_t)prompt.size();
+    const int32_t have = np - 1 < steps ? np - 1 : steps;
+    const size_t stride = (size_t)(steps > 0 ? steps : 1);
+    std::vector<int32_t> prompts, n_prompt((size_t)N, np), cached((size_t)N, have), totals((size_t)N, steps),
+        n_out((size_t)N, 0), out((size_t)N * stride), nb((size_t)N, (int32_t)bias_ids.size()), ids, first((size_t)N, 0),
+        order((size_t)N, 0);
+    std::vector<float> vals, lp((size_t)N * stride, std::nanf(""));
+    std::vector<double> mean((size_t)N, 0.0);
+    std::vector<kh_sampling> samps((size_t)N, samp);
+    std::vector<kh_penalties> pens((size_t)N, pen);
+    for (int s = 0; s < N; ++s) {
+      prompts.insert(prompts.end(), prompt.begin(), prompt.end());
+      ids.insert(ids.end(), bias_ids.begin(), bias_ids.end());
+      vals.insert(vals.end(), bias_vals.begin(), bias_vals.end());
+      samps[(size_t)s].seed = samp.seed + (uint64_t)s;
+    }
+    const kh_seq_opts so{samps.data(), pens.data(), nb.data(), ids.data(), vals.data(), top_n};
+    float ms = 0.f;
+    std::printf("Generating...\n");
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = kh_model_seq_slots(m, N, &slot_len);
+    if (rc == KH_OK && have > 0) rc = kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
+    for (int s = 1; s < N && rc == KH_OK && have > 0; ++s) rc = kh_model_seq_fork(m, 0, s, have);
+    if (rc == KH_OK)
+      rc = kh_model_generate_batch_ex(m, N, prompts.data(), n_prompt.data(), cached.data(), totals.data(), &so,
+                                      stop.data(), (int32_t)stop.size(), out.data(), steps, n_out.data(), &ms);
+    const auto t1 = std::chrono::steady_clock::now();
+    for (int s = 0; s < N && rc == KH_OK; ++s) {
+      first[(size_t)s] = have < n_out[(size_t)s] ? have : n_out[(size_t)s];
+      if (n_out[(size_t)s] > 0)
+        rc = kh_model_seq_get_logprobs(m, s, 0, n_out[(size_t)s], nullptr, lp.data() + (size_t)s * stride, nullptr, nullptr);
+    }
+    if (rc == KH_OK)
+      rc = kh_seq_rank(N, lp.data(), (int32_t)stride, first.data(), n_out.data(), order.data(), mean.data());
+    if (rc != KH_OK) {
+      std::fprintf(stderr, "--best-of %d failed: %d (%s)\n", N, rc, kh_error_string(rc));
+      kh_model_destroy(m);
+      return 1;
+    }
+    std::fprintf(stderr, "best-of: %d slots of %d rows\n", N, slot_len);
+    long total = 0;
+    for (int r = 0; r < N; ++r) {
+      const size_t s = (size_t)order[(size_t)r];
+      std::printf("%.6f %llu |", mean[s], (unsigned long long)samps[s].seed);
+      for (int i = 0; i < n_out[s]; ++i) std::printf(" %d", out[s * stride + i]);
+      std::printf("\n");
+      total += n_out[s];
+    }
+    std::printf("steps/s:%lf\n", (double)total / std::chrono::duration<double>(t1 - t0).count());
+    std::fprintf(stderr, "(device time of the passes: %.3f ms)\n", ms);
     if (tok) kh_spm_destroy(tok);
     if (bpe) kh_bpe_destroy(bpe);
     kh_model_destroy(m);
