@@ -640,8 +640,42 @@ int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t* hint, int3
  * KH_ERR_UNSUPPORTED as kh_model_seq_step.  There is no fallback to a token loop.
  * kh_model_generate_batch_from is the same call for prompts whose first n_cached[s] positions already sit in slot s
  * (kh_model_seq_prefill, kh_model_seq_fork; NULL = none): it feeds the rest and returns the words of the WHOLE prompt's
- * kh_model_generate_until.  KH_ERR_INVALID_ARG unless 0 <= n_cached[s] <= min(n_prompt[s] - 1, total_steps[s]). */
+ * kh_model_generate_until.  KH_ERR_INVALID_ARG unless 0 <= n_cached[s] <= min(n_prompt[s] - 1, total_steps[s]).
+ *
+ * Slots of unequal length and a shared prompt prefix (n samples of one long prompt, one system prompt for several
+ * users: ONE copy of the prompt's K/V rows).
+ * kh_model_seq_slots_var: slot s owns h_len[s] consecutive rows, slot 0 from row 0 (it stays the batch-1 sequence's
+ * rows), the others behind it without gaps.  KH_ERR_INVALID_ARG unless 1 <= n_slots <= 64, every h_len[s] >= 8 and
+ * their sum <= cache_len.  kh_plan_seq_slots_var is the host-only twin (row0_out[s] = slot s's first row, may be NULL).
+ * kh_model_seq_slots is the equal layout in the same tables; both calls reset every sharing relation.  Wherever the
+ * text above says slot_len, read "the positions the slot holds" (its capacity), and row s * slot_len + p is
+ * kh_model_seq_row(s, p).
+ * kh_model_seq_share(src, dst, n_rows): from now on positions [0, n_rows) of dst ARE src's rows [0, n_rows); position
+ * p >= n_rows of dst lives at dst's own row (p - n_rows), so dst holds n_rows + h_len[dst] positions.  Bookkeeping:
+ * nothing is copied or launched, dst's previous content is discarded, n_rows == 0 detaches dst.  A sharer's words,
+ * K/V rows and log-prob records are bit for bit those of a forked copy and of a batch-1 model: the attention of its
+ * lanes is k_seq_attn's with the row of a timestep below n_rows taken from the parent (k_seq_attn_pfx, launched only
+ * by a pass that has such a lane).  KH_ERR_INVALID_ARG for src == dst, n_rows < 0 or dst == 0 (slot 0 is what the
+ * batch-1 entry points address: a parent, never a sharer); KH_ERR_RANGE for a slot outside the partition or n_rows >
+ * h_len[src]; KH_ERR_UNSUPPORTED when src is itself a sharer (one level only) or dst has dependants.
+ * While shared, a parent's rows below Pmax (the largest n_rows a dependant holds) are immutable: kh_model_seq_prefill,
+ * kh_model_seq_step[_ex], kh_model_generate_batch* (by n_cached[s]) and kh_model_seq_set_history that would write
+ * such a position, and kh_model_seq_fork INTO the parent, return KH_ERR_INVALID_ARG before any launch; the parent
+ * keeps decoding at positions >= Pmax.  The batch-1 entry points ignore the bookkeeping, as ever: a caller that
+ * shares slot 0's rows does not run them below Pmax.
+ * A sharer is fed from its shared length on: kh_model_seq_prefill with pos0 below it, a lane position below it and
+ * n_cached[s] below it are KH_ERR_INVALID_ARG; lanes of sharers and non-sharers mix in one pass.  It never writes
+ * K/V, history or records at rows it does not own: kh_model_seq_get_logprobs returns "none" records below its shared
+ * length, kh_model_generate_batch_ex resets and uploads only from there on.  Penalties on a sharer are refused
+ * (KH_ERR_UNSUPPORTED from the _ex calls: its fed-token history would lie in two row ranges); sampling, logit bias and
+ * log-probs work.  kh_model_seq_fork: the source may be a parent; KH_ERR_UNSUPPORTED if either side is a sharer.
+ * kh_model_seq_row: the cache row that holds position pos of slot (the parent's below the shared length), for
+ * kh_model_read_kv; KH_ERR_RANGE outside the slot's capacity. */
 int kh_model_seq_slots(kh_model* m, int32_t n_slots, int32_t* slot_len);
+int kh_model_seq_slots_var(kh_model* m, int32_t n_slots, const int32_t* h_len);
+int kh_plan_seq_slots_var(int32_t cache_len, int32_t n_slots, const int32_t* h_len, int32_t* row0_out);
+int kh_model_seq_share(kh_model* m, int32_t src_slot, int32_t dst_slot, int32_t n_rows);
+int kh_model_seq_row(const kh_model* m, int32_t slot, int32_t pos, int32_t* row);
 int kh_plan_seq_slots(int32_t cache_len, int32_t n_slots, int32_t* slot_len);
 int kh_model_seq_width(const kh_model* m, int32_t* width);
 int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_tokens, int32_t n, int32_t pos0);

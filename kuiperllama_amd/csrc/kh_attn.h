@@ -299,13 +299,31 @@ __host__ __device__ static inline AttnSplitWs attn_ws_carve(void* ws, int heads,
   return w;
 }
 
+// Shared prompt prefix (kh_model_seq_share): a slice whose sequence reads its positions [0, P) from another slot's
+// rows.  An address translation and nothing else - which thread takes which timestep, the split geometry and every
+// arithmetic expression are those of the plain slice, so a sharer computes bit for bit what a copy of the rows gives.
+// Timestep t (the CLAMPED index, see load_batch) is row par + t below P and row own + t from P on, both as signed
+// element offsets from the layer's cache base (+ head column): own = (row - pos) * kv_dim is negative for a sharer
+// whose own rows start less than P rows into the cache, and rows below P of `own` belong to somebody else - they are
+// never addressed.  PFX is a compile-time parameter of the whole chain up to attn_slice_body; with it off the struct
+// is not read and the instantiations are what they were.
+struct AttnPfx {
+  int P = 0;
+  long long own = 0, par = 0;
+};
+template <bool PFX>
+__device__ __forceinline__ long long attn_pfx_row4(const AttnPfx& x, int tt, int stride4) {
+  if constexpr (PFX) return ((tt < x.P ? x.par : x.own) >> 2) + (long long)tt * stride4;  // offsets are multiples of 4
+  return 0;
+}
+
 // Attention of head h over timesteps [t_begin, t_end): leaves, for threads tid < hs, the
 // unnormalised output r = sum_t exp(s_t - M) v_t[tid] and L = sum_t exp(s_t - M); returns M.
-template <int G>
+template <int G, bool PFX = false>
 __device__ __forceinline__ float attn_fast_partial(const float* q_h, const float* k_base,
                                                    const float* v_base, int kv_stride, int hs,
                                                    int t_begin, int t_end, float* smem,
-                                                   float& r_out, float& L_out) {
+                                                   float& r_out, float& L_out, const AttnPfx& pfx = AttnPfx{}) {
   static_assert(G == 16 || G == 32 || G == 64, "G must be 16, 32 or 64");
   const int TPI = kh_wg() / G;
   float* red = smem;          // [8]
@@ -332,8 +350,14 @@ __device__ __forceinline__ float attn_fast_partial(const float* q_h, const float
       const int tt = t < t_end ? t : t_end - 1;  // clamped address, masked in use_batch
       // unconditional (lanes past the head vector read element 0 and are dropped in use_batch): a load behind an
       // exec-mask branch is a CFG join, and the s_waitcnt at the loop header then degrades to vmcnt(0)
-      kv[u] = K4[(size_t)tt * stride4 + dlc];
-      vv[u] = V4[(size_t)tt * stride4 + dlc];
+      if constexpr (PFX) {
+        const long long r4 = attn_pfx_row4<PFX>(pfx, tt, stride4) + dlc;
+        kv[u] = K4[r4];
+        vv[u] = V4[r4];
+      } else {
+        kv[u] = K4[(size_t)tt * stride4 + dlc];
+        vv[u] = V4[(size_t)tt * stride4 + dlc];
+      }
     }
   };
   auto use_batch = [&](const f32x4 (&kv)[KH_ATTN_UB], const f32x4 (&vv)[KH_ATTN_UB], int tb)
@@ -592,13 +616,14 @@ __device__ __forceinline__ void attn_acquire(bool fenced) {  // in the last arri
 // One workgroup = (head h, split s) of a grid of heads*NS workgroups.  ws may be null iff NS==1.
 // defer: leave the partial in the workspace and return, whatever nact is (the consumer combines).
 // Returns true in the workgroup that wrote the head's final output.
-template <int G>
+template <int G, bool PFX = false>
 __device__ __forceinline__ bool attn_head_decode_fast(const float* q_h, const float* k_base,
                                                       const float* v_base, int kv_stride, int hs,
                                                       int pos, float* out_h, float* smem, int h,
                                                       int s, int NS, AttnSplitWs ws, int NSW = 0,
                                                       bool defer = false, bool fenced = false,
-                                                      int ts_shift = KH_ATTN_TS_SHIFT_MAX) {
+                                                      int ts_shift = KH_ATTN_TS_SHIFT_MAX,
+                                                      const AttnPfx& pfx = AttnPfx{}) {
   if (NSW <= 0) NSW = NS;  // slot stride of the workspace (>= NS)
   const int tid = threadIdx.x;
   const int nT = pos + 1;
@@ -609,7 +634,7 @@ __device__ __forceinline__ bool attn_head_decode_fast(const float* q_h, const fl
   const int t_begin = s * TS;
   const int t_end = t_begin + TS < nT ? t_begin + TS : nT;
   float r, L;
-  const float M = attn_fast_partial<G>(q_h, k_base, v_base, kv_stride, hs, t_begin, t_end, smem, r, L);
+  const float M = attn_fast_partial<G, PFX>(q_h, k_base, v_base, kv_stride, hs, t_begin, t_end, smem, r, L, pfx);
   KH_ATTN_STAMP(4);
   const size_t slot = (size_t)h * NSW + s;
   if (defer) {  // plain stores (also with ONE active split); the next kernel on the stream reads them
@@ -674,11 +699,12 @@ static inline int attn_group_splits(int cache_len, int kv_heads) {
   return ns < 1 ? 1 : ns;
 }
 
-template <int G, int KVM>
+template <int G, int KVM, bool PFX = false>
 __device__ __forceinline__ void attn_group_partial(const float* q_g, const float* k_base,
                                                    const float* v_base, int kv_stride, int hs,
                                                    int t_begin, int t_end, float* smem,
-                                                   float& r_out, float& L_out, float& M_out) {
+                                                   float& r_out, float& L_out, float& M_out,
+                                                   const AttnPfx& pfx = AttnPfx{}) {
   static_assert(G == 16 || G == 32 || G == 64, "G must be 16, 32 or 64");
   const int TPI = kh_wg() / G;
   const int nw = kh_nwaves();
@@ -709,8 +735,14 @@ __device__ __forceinline__ void attn_group_partial(const float* q_g, const float
     for (int u = 0; u < KH_ATTN_UB; ++u) {
       const int t = tb + u * TPI;
       const int tt = t < t_end ? t : t_end - 1;
-      kv[u] = ld_nt(K4 + (size_t)tt * stride4 + dlc);  // unconditional, see attn_fast_partial
-      vv[u] = ld_nt(V4 + (size_t)tt * stride4 + dlc);
+      if constexpr (PFX) {
+        const long long r4 = attn_pfx_row4<PFX>(pfx, tt, stride4) + dlc;
+        kv[u] = ld_nt(K4 + r4);
+        vv[u] = ld_nt(V4 + r4);
+      } else {
+        kv[u] = ld_nt(K4 + (size_t)tt * stride4 + dlc);  // unconditional, see attn_fast_partial
+        vv[u] = ld_nt(V4 + (size_t)tt * stride4 + dlc);
+      }
     }
   };
   // tb < t_end required (u = 0 valid): a batch without any timestep would form exp2(-inf - -inf)
@@ -831,11 +863,12 @@ __device__ __forceinline__ void attn_group_partial(const float* q_g, const float
 // One workgroup = (kv group g, split s); heads g*KVM .. g*KVM+KVM-1.  Workspace slots and the
 // merge are those of the per-head path (slot = h*NSW + s); the arrival ticket of the group is
 // the ticket of its first head.  Requires KVM*hs <= blockDim.x.
-template <int G, int KVM>
+template <int G, int KVM, bool PFX = false>
 __device__ __forceinline__ void attn_group_decode(const float* q_g, const float* k_base,
                                                   const float* v_base, int kv_stride, int hs,
                                                   int pos, float* out_g, float* smem, int g, int s,
-                                                  int NS, int NSW, AttnSplitWs ws, bool fenced) {
+                                                  int NS, int NSW, AttnSplitWs ws, bool fenced,
+                                                  const AttnPfx& pfx = AttnPfx{}) {
   const int tid = threadIdx.x;
   const int nT = pos + 1;
   int TS, nact;
@@ -845,7 +878,7 @@ __device__ __forceinline__ void attn_group_decode(const float* q_g, const float*
   const int t_begin = s * TS;
   const int t_end = t_begin + TS < nT ? t_begin + TS : nT;
   float r, L, M;
-  attn_group_partial<G, KVM>(q_g, k_base, v_base, kv_stride, hs, t_begin, t_end, smem, r, L, M);
+  attn_group_partial<G, KVM, PFX>(q_g, k_base, v_base, kv_stride, hs, t_begin, t_end, smem, r, L, M, pfx);
   const bool mine = tid < KVM * hs;
   const int j = mine ? tid / hs : 0, e = tid - j * hs;
   const int h = g * KVM + j;
@@ -882,9 +915,10 @@ __device__ __forceinline__ void attn_group_decode(const float* q_g, const float*
 
 // =============================================================================================
 // The decode-attention launch shared by the fused step (kh_model_step.hip), the operator-level entry point
-// kh_mha_decode_f32 (kh_ops.hip) and the B-token pass (kh_model_prefill.hip): two kernels that differ in where a
-// slice's position and cache rows come from (k_attn_decode, k_seq_attn) over one slice body, one launch plan
-// (attn_launch_plan) and one instantiation table (attn_pick).
+// kh_mha_decode_f32 (kh_ops.hip) and the B-token pass (kh_model_prefill.hip): kernels that differ in where a
+// slice's position and cache rows come from (k_attn_decode, k_seq_attn, and k_seq_attn_pfx for lanes that read a shared
+// prompt prefix from another slot's rows) over one slice body, one launch plan (attn_launch_plan) and one instantiation
+// table (attn_pick).
 struct KhAttnArgs {
   const float* q;          // [dim]
   const float* kcache_layer;
@@ -909,8 +943,9 @@ struct KhAttnArgs {
 
 // per-head path: block -> (kv group g, head-in-group j, split s).  Blocks are placed on XCD
 // b % 8, so with g = b % kv_heads the kv_mul heads that share K/V rows share an XCD's L2.
-template <int G>
-__device__ __forceinline__ void attn_head_block(const KhAttnArgs& a, float* smem, int b, int pos) {
+template <int G, bool PFX = false>
+__device__ __forceinline__ void attn_head_block(const KhAttnArgs& a, float* smem, int b, int pos,
+                                                const AttnPfx& pfx = AttnPfx{}) {
   // power-of-two head counts (every Llama-family config): shifts instead of three integer divisions (~40
   // instructions each, in front of the first address of a launch whose whole body is ~2 us)
   int g, j, s;
@@ -925,11 +960,11 @@ __device__ __forceinline__ void attn_head_block(const KhAttnArgs& a, float* smem
   }
   const int h = g * a.kv_mul + j;
   const size_t head_off = (size_t)g * a.head_size;
-  attn_head_decode_fast<G>(
+  attn_head_decode_fast<G, PFX>(
       a.q + (size_t)h * a.head_size, a.kcache_layer + head_off, a.vcache_layer + head_off,
       a.kv_dim, a.head_size, pos, a.out + (size_t)h * a.head_size, smem, h, s, a.nsplit,
       attn_ws_carve(a.ws, a.kv_heads * a.kv_mul, a.head_size, a.ws_stride), a.ws_stride, a.defer != 0,
-      a.fenced != 0, a.ts_shift);
+      a.fenced != 0, a.ts_shift, pfx);
 }
 
 // The lanes of a B-token pass that belong to DIFFERENT sequences (kh_seq.h, kh_model_seq_step): lane b is a token at
@@ -939,6 +974,11 @@ struct KhSeqLanes {
   int32_t pos[KH_PF_BMAX];  // position of the lane's token in its sequence
   int32_t row[KH_PF_BMAX];  // its cache row: the slot's first row + pos
   int32_t slot[KH_PF_BMAX]; // its sequence slot: the entry of the per-slot device tables (token to feed, sampler)
+  // a lane whose slot shares a prefix (kh_model_seq_share) reads positions [0, pfx_len) from the parent's rows
+  // pfx_row0 .. and owns the rows from position pfx_len on (row - pos may then be negative); only k_seq_attn_pfx
+  // reads these two, and a pass launches it only when one of them is not 0
+  int32_t pfx_len[KH_PF_BMAX] = {0};
+  int32_t pfx_row0[KH_PF_BMAX] = {0};
 };
 
 // One slice (one token at position pos, a.q / a.out / a.ws / the cache bases already its own) of a decode-attention
@@ -948,22 +988,24 @@ struct KhSeqLanes {
 // once pos + 1 >= t_long.  The choice is uniform over the slice (it depends on the position
 // only), so one captured launch serves every position; workgroups beyond the active path's
 // count leave immediately.
-template <int G, int KVM>
-__device__ __forceinline__ void attn_slice_body(const KhAttnArgs& a, int pos, char* smem_raw) {
+template <int G, int KVM, bool PFX = false>
+__device__ __forceinline__ void attn_slice_body(const KhAttnArgs& a, int pos, char* smem_raw,
+                                                const AttnPfx& pfx = AttnPfx{}) {
   const int b = (int)blockIdx.x;
   if (KVM == 0 || pos + 1 < a.t_long) {
-    if (b < a.kv_heads * a.kv_mul * a.nsplit) attn_head_block<G>(a, (float*)smem_raw, b, pos);
+    if (b < a.kv_heads * a.kv_mul * a.nsplit) attn_head_block<G, PFX>(a, (float*)smem_raw, b, pos, pfx);
     return;
   }
   if constexpr (KVM > 0) {
     if (b >= a.kv_heads * a.nsplit_g) return;
     const int g = b % a.kv_heads, s = b / a.kv_heads;
     const size_t head_off = (size_t)g * a.head_size;
-    attn_group_decode<G, KVM>(a.q + (size_t)g * KVM * a.head_size, a.kcache_layer + head_off,
-                              a.vcache_layer + head_off, a.kv_dim, a.head_size, pos,
-                              a.out + (size_t)g * KVM * a.head_size, (float*)smem_raw, g, s,
-                              a.nsplit_g, a.ws_stride,
-                              attn_ws_carve(a.ws, a.kv_heads * KVM, a.head_size, a.ws_stride), a.fenced != 0);
+    attn_group_decode<G, KVM, PFX>(a.q + (size_t)g * KVM * a.head_size, a.kcache_layer + head_off,
+                                   a.vcache_layer + head_off, a.kv_dim, a.head_size, pos,
+                                   a.out + (size_t)g * KVM * a.head_size, (float*)smem_raw, g, s,
+                                   a.nsplit_g, a.ws_stride,
+                                   attn_ws_carve(a.ws, a.kv_heads * KVM, a.head_size, a.ws_stride), a.fenced != 0,
+                                   pfx);
   }
 }
 
@@ -1004,6 +1046,24 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_seq_attn(KhAttnArgs a, const KhSe
     a.ws = (char*)a.ws + (size_t)t * a.ws_tok_bytes;
   }
   attn_slice_body<G, KVM>(a, pos, smem_raw);
+}
+
+// ... of a pass in which at least one lane shares a prompt prefix: the cache bases stay the layer's, every slice
+// brings its two row offsets (AttnPfx); a lane that shares nothing has P = 0 and reads its own rows throughout.
+// gridDim.x may be padded (launch_seq_attn_pfx): the slice body's own bounds send the extra workgroups away.
+template <int G, int KVM>
+__global__ __launch_bounds__(KH_WG_MAX) void k_seq_attn_pfx(KhAttnArgs a, const KhSeqLanes lanes) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int t = (int)blockIdx.y;
+  const int pos = lanes.pos[t];
+  AttnPfx x;
+  x.P = lanes.pfx_len[t];
+  x.own = (long long)(lanes.row[t] - pos) * a.kv_dim;
+  x.par = (long long)lanes.pfx_row0[t] * a.kv_dim;
+  a.q += (size_t)t * a.tok_stride;
+  a.out += (size_t)t * a.tok_stride;
+  a.ws = (char*)a.ws + (size_t)t * a.ws_tok_bytes;
+  attn_slice_body<G, KVM, true>(a, pos, smem_raw, x);
 }
 
 // lanes cooperating on one timestep for this head size
@@ -1197,4 +1257,30 @@ static inline void launch_seq_attn(KhAttnArgs a, const KhSeqLanes& lanes, int n,
   attn_pick(L, [&](auto G, auto KVM) {
     khm::kh_launch(KH_KERNEL(k_seq_attn, G, KVM), dim3(L.grid, n), wg, L.lds, s, a, lanes);
   });
+}
+// ... when a lane of the pass shares a prompt prefix (lanes.pfx_len): the same plan, workspace and merge under
+// k_seq_attn_pfx.  pad8: grid.x rounded up to a multiple of 8 so that, where workgroups go to the 8 XCDs round-robin
+// by linear id (observed, not a contract - nothing depends on it), the workgroups of different lanes for one (head,
+// split) meet in one L2; the extra workgroups leave at once.  Logs "k_seq_attn_pfx<G,KVM>" and
+// "seq_attn_pfx_launch<wg,ts_shift,fenced,group_grid?>".
+static inline void launch_seq_attn_pfx(KhAttnArgs a, const KhSeqLanes& lanes, int n, int wg, hipStream_t s,
+                                       bool pad8) {
+  a.d_pos = nullptr;
+  a.defer = 0;
+  const AttnLaunch L = attn_launch_plan(a, wg, lanes.pos, 0, n);
+  attn_launch_apply(L, a);
+  if (khm::g_launch_log_on.load(std::memory_order_relaxed)) {
+    char rec[96];
+    snprintf(rec, sizeof rec, "seq_attn_pfx_launch<%d,%d,%d,%d>", wg, a.ts_shift, a.fenced ? 1 : 0, L.grp ? 1 : 0);
+    khm::launch_log_add(rec);
+  }
+  const int grid = pad8 ? (L.grid + 7) & ~7 : L.grid;
+  attn_pick(L, [&](auto G, auto KVM) {
+    khm::kh_launch(KH_KERNEL(k_seq_attn_pfx, G, KVM), dim3(grid, n), wg, L.lds, s, a, lanes);
+  });
+}
+static inline bool seq_lanes_share(const KhSeqLanes& lanes, int n) {
+  for (int i = 0; i < n; ++i)
+    if (lanes.pfx_len[i] > 0) return true;
+  return false;
 }

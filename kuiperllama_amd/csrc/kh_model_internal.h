@@ -21,6 +21,7 @@
 
 #include "kh_attn.h"
 #include "kh_common.h"
+#include "kh_seq_plan.h"
 
 namespace khm {
 // No C++ exception crosses the C ABI: the entry points that allocate host containers or start threads run their
@@ -124,6 +125,10 @@ struct kh_model {
   // by the first seq pass: the token the slot's sequence feeds next and its sampling parameters; the words of every
   // sequence at its slot's rows ([cache_len]); pinned mirrors / staging of the three.
   int seq_slots = 1;
+  // ... or into slots of unequal length (kh_model_seq_slots_var), some of which read a prompt prefix from another
+  // slot's rows (kh_model_seq_share): row0 / len / sharing of every slot; the equal partition is the same table
+  KhSeqSlot seq_tab[KH_SEQ_SLOTS_MAX];
+  bool seq_pfx_pad8 = false;  // hook KH_SEQ_PFX_PAD=1: k_seq_attn_pfx's grid.x padded to a multiple of 8
   int32_t* d_seq_tok = nullptr;
   KhSampParams* d_seq_samp = nullptr;
   int32_t* d_seq_words = nullptr;
@@ -415,6 +420,6 @@ struct KhSeqTail {
 };
 int seq_prepare(kh_model* m);
 int seq_prepare_ex(kh_model* m, bool records);  // behind seq_prepare: the tables of k_seq_tail, the record buffers
-int seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0);
+int seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0, int pfx_len = 0, int pfx_row0 = 0);
 int seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, const KhSeqTail* tail = nullptr);
 }  // namespace khm

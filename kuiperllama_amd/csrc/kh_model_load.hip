@@ -548,6 +548,11 @@ int finish_create(kh_model* m, SinCosJob* sincos = nullptr) {
     m->attn_t_long = ap.t_long;
   }
   m->attn_fenced = (m->opts.flags & KH_FLAG_ATTN_MERGE_FENCED) != 0 || attn_fenced_hook();
+  m->seq_tab[0].len = c.cache_len;  // one slot: the batch-1 sequence's rows
+  {
+    const char* e = khm::dbg("KH_SEQ_PFX_PAD");
+    m->seq_pfx_pad8 = e && e[0] == '1';
+  }
   // step variant 1 - time splits merged by k_wo_comb instead of a last arriver (kh_attn.h, kh_fused.h) -
   // needs wo's in-register staging (dim <= 16 floats per thread) and heads * 16 factor slots per pass
   m->attn_defer = m->attn_ns > 1 && !(m->opts.flags & KH_FLAG_ATTN_MERGE_IN_LAUNCH) && !dbg_off("KH_ATTN_DEFER") &&

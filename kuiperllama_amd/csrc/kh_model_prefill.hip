@@ -169,6 +169,11 @@ void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const f
 //                         run too and pf_x holds the tokens' final residual vectors
 //   a lane table          lane b feeds d_seq_tok[slot[b]] at position pos[b], cache row row[b] (kh_seq.h): k_seq_embed,
 //                         k_seq_qkv, k_seq_attn.  Always full depth
+//   a run into a slot that shares a prefix (pfx_len > 0, kh_model_seq_share): row0 is the slot's own base (the row of
+//                         its first own position minus pfx_len; it may be negative, rows below pos0 >= pfx_len are
+//                         never touched through it), positions [0, pfx_len) are the parent's rows pfx_row0 ..:
+//                         k_pf_embed and k_pf_qkv as any run, the attention as k_seq_attn_pfx over a lane table of
+//                         the run's positions - the same slices in the same launch order
 // wo, ffn13 and w2 do not care where a token sits.
 struct PfPass {
   int nvalid, B;
@@ -176,9 +181,11 @@ struct PfPass {
   const int32_t* toks;
   int pos0, row0;
   const KhSeqLanes* lanes;
+  int pfx_len = 0, pfx_row0 = 0;
 };
-PfPass pf_run(const int32_t* toks, int nvalid, int pos0, int B, bool full_depth, int row0 = 0) {
-  return PfPass{nvalid, B, full_depth, toks, pos0, row0, nullptr};
+PfPass pf_run(const int32_t* toks, int nvalid, int pos0, int B, bool full_depth, int row0 = 0, int pfx_len = 0,
+              int pfx_row0 = 0) {
+  return PfPass{nvalid, B, full_depth, toks, pos0, row0, nullptr, pfx_len, pfx_row0};
 }
 PfPass pf_lanes(const KhSeqLanes& lanes, int nvalid, int B) { return PfPass{nvalid, B, true, nullptr, 0, 0, &lanes}; }
 // layer l's k_pf_qkv / k_seq_qkv arguments: cache rows counted from row0, RoPE rows from pos0 (a lane table brings
@@ -193,8 +200,9 @@ KhPfQkvArgs pf_qkv_args(const kh_model* m, int l, const PfPass& p) {
   a.wk = W.wk;
   a.wv = W.wv;
   a.Q = m->pf_q;
-  a.kcache_layer = m->kcache + ((size_t)l * c.cache_len + p.row0) * c.kv_dim;
-  a.vcache_layer = m->vcache + ((size_t)l * c.cache_len + p.row0) * c.kv_dim;
+  const ptrdiff_t row = (ptrdiff_t)l * c.cache_len + p.row0;  // signed: a sharer's own base may lie below row 0
+  a.kcache_layer = m->kcache + row * c.kv_dim;
+  a.vcache_layer = m->vcache + row * c.kv_dim;
   a.sin_cache = m->sin_cache;
   a.cos_cache = m->cos_cache;
   a.dim = c.dim;
@@ -245,7 +253,21 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
       a.tok_stride = c.dim;
       a.ws_tok_bytes = m->pf_ws_tok_bytes;
       if (p.lanes) {
-        launch_seq_attn(a, *p.lanes, nvalid, m->attn_wg, m->stream);
+        if (seq_lanes_share(*p.lanes, nvalid))
+          launch_seq_attn_pfx(a, *p.lanes, nvalid, m->attn_wg, m->stream, m->seq_pfx_pad8);
+        else
+          launch_seq_attn(a, *p.lanes, nvalid, m->attn_wg, m->stream);
+      } else if (p.pfx_len > 0) {
+        KhSeqLanes run;
+        for (int b = 0; b < KH_PF_BMAX; ++b) {
+          const int bb = b < nvalid ? b : nvalid - 1;
+          run.pos[b] = p.pos0 + bb;
+          run.row[b] = p.row0 + p.pos0 + bb;
+          run.slot[b] = 0;
+          run.pfx_len[b] = p.pfx_len;
+          run.pfx_row0[b] = p.pfx_row0;
+        }
+        launch_seq_attn_pfx(a, run, nvalid, m->attn_wg, m->stream, m->seq_pfx_pad8);
       } else {
         a.kcache_layer += (size_t)p.row0 * c.kv_dim;
         a.vcache_layer += (size_t)p.row0 * c.kv_dim;
@@ -823,10 +845,11 @@ int khm::seq_prepare_ex(kh_model* m, bool records) {
     KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_hist_pin, sizeof(int32_t) * (size_t)m->cfg.cache_len, hipHostMallocDefault));
   return records ? lp_ensure_records(m) : KH_OK;
 }
-int khm::seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0) {
+int khm::seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0, int pfx_len, int pfx_row0) {
   const int B = prefill_batch(m);
   for (int t0 = 0; t0 < n; t0 += B)
-    launch_pf_pass(m, pf_run(toks + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B, /*full_depth=*/false, row0));
+    launch_pf_pass(m, pf_run(toks + t0, n - t0 < B ? n - t0 : B, pos0 + t0, B, /*full_depth=*/false, row0, pfx_len,
+                             pfx_row0));
   return kh_launch_status();
 }
 int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, const KhSeqTail* tail) {
@@ -836,6 +859,8 @@ int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, cons
     lanes.pos[b] = lanes.pos[n - 1];
     lanes.row[b] = lanes.row[n - 1];
     lanes.slot[b] = lanes.slot[n - 1];
+    lanes.pfx_len[b] = lanes.pfx_len[n - 1];
+    lanes.pfx_row0[b] = lanes.pfx_row0[n - 1];
   }
   launch_pf_pass(m, pf_lanes(lanes, n, B));
   launch_pf_cls(m, n, B);
@@ -850,7 +875,7 @@ int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, cons
     t.bias_ids = tail->bias_ids;
     t.bias = tail->bias;
     t.hist = m->d_hist;
-    t.slot_len = c.cache_len / m->seq_slots;
+    for (int b = 0; b < KH_PF_BMAX; ++b) t.cap[b] = kh_seq_capacity(m->seq_tab[lanes.slot[b]]);
     t.cnt = tail->cnt;
     t.top_n = tail->top_n;
     t.rec_token = m->d_lp_token;

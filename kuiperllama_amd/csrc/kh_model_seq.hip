@@ -22,7 +22,46 @@ using namespace khm;
 static_assert(KH_SEQ_SLOTS_MAX >= KH_PF_BMAX, "a pass never has more lanes than there can be slots");
 
 namespace {
-inline int slot_len(const kh_model* m) { return m->cfg.cache_len / m->seq_slots; }
+// The slot table (kh_seq_plan.h): slot s owns rows [row0, row0 + len) and, as a sharer, reads its positions [0, pfx)
+// from its parent's rows.  cap: the positions it holds; own_base + p: the row of position p >= pfx (the base itself
+// may be negative); seq_row: the row of any position.
+inline const KhSeqSlot& slot_of(const kh_model* m, int s) { return m->seq_tab[s]; }
+inline int cap(const kh_model* m, int s) { return kh_seq_capacity(m->seq_tab[s]); }
+inline int own_base(const kh_model* m, int s) { return kh_seq_own_base(m->seq_tab[s]); }
+inline int pfx_row0(const kh_model* m, int s) {
+  return m->seq_tab[s].pfx > 0 ? m->seq_tab[m->seq_tab[s].parent].row0 : 0;
+}
+inline int seq_row(const kh_model* m, int s, int p) {
+  return p < m->seq_tab[s].pfx ? pfx_row0(m, s) + p : own_base(m, s) + p;
+}
+// would feeding position p of slot s write a row it may not write: a shared row of a parent, or (a sharer) a row of
+// its parent's?
+inline bool writes_shared(const kh_model* m, int s, int p) { return p < m->seq_tab[s].pmax || p < m->seq_tab[s].pfx; }
+// the rows positions [p0, p1) of slot s touch, read or written: its own up to p1 and its parent's shared ones
+int ensure_slot_rows(kh_model* m, int s, int p1) {
+  const KhSeqSlot& t = m->seq_tab[s];
+  int rc;
+  if (t.pfx > 0 && (rc = kv_ensure_rows(m, pfx_row0(m, s), pfx_row0(m, s) + t.pfx)) != KH_OK) return rc;
+  return p1 > t.pfx ? kv_ensure_rows(m, t.row0, t.row0 + p1 - t.pfx) : KH_OK;
+}
+void lane_set(const kh_model* m, KhSeqLanes& l, int i, int s, int p) {
+  l.pos[i] = p;
+  l.row[i] = own_base(m, s) + p;
+  l.slot[i] = s;
+  l.pfx_len[i] = m->seq_tab[s].pfx;
+  l.pfx_row0[i] = pfx_row0(m, s);
+}
+void set_layout(kh_model* m, int n, const int32_t* len, const int32_t* row0) {
+  m->seq_slots = n;
+  for (int s = 0; s < KH_SEQ_SLOTS_MAX; ++s) m->seq_tab[s] = KhSeqSlot{};
+  for (int s = 0; s < n; ++s) {
+    m->seq_tab[s].row0 = row0[s];
+    m->seq_tab[s].len = len[s];
+  }
+}
+bool penalties_on_sharer(const kh_model* m, const kh_seq_opts* o, int i, int s) {
+  return o && o->penalties && m->seq_tab[s].pfx > 0 && !kh_penalties_neutral(&o->penalties[i]);
+}
 inline bool is_stop(int32_t t, const int32_t* stop, int n_stop) {
   for (int i = 0; i < n_stop; ++i)
     if (stop[i] == t) return true;
@@ -142,12 +181,56 @@ extern "C" int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* fi
   return passes <= cap_passes ? KH_OK : KH_ERR_RANGE;
 }
 
+extern "C" int kh_plan_seq_slots_var(int32_t cache_len, int32_t n_slots, const int32_t* h_len, int32_t* row0_out) {
+  return kh_seq_slots_var(cache_len, n_slots, h_len, row0_out) ? KH_OK : KH_ERR_INVALID_ARG;
+}
+
 extern "C" int kh_model_seq_slots(kh_model* m, int32_t n_slots, int32_t* slot_len_out) {
   if (!m) return KH_ERR_INVALID_ARG;
   const int len = kh_seq_slot_len(m->cfg.cache_len, n_slots);
   if (!len) return KH_ERR_INVALID_ARG;
-  m->seq_slots = n_slots;
+  int32_t lens[KH_SEQ_SLOTS_MAX], row0[KH_SEQ_SLOTS_MAX];
+  for (int s = 0; s < n_slots; ++s) {
+    lens[s] = len;
+    row0[s] = s * len;
+  }
+  set_layout(m, n_slots, lens, row0);
   if (slot_len_out) *slot_len_out = len;
+  return KH_OK;
+}
+
+extern "C" int kh_model_seq_slots_var(kh_model* m, int32_t n_slots, const int32_t* h_len) {
+  if (!m) return KH_ERR_INVALID_ARG;
+  int32_t row0[KH_SEQ_SLOTS_MAX];
+  if (!kh_seq_slots_var(m->cfg.cache_len, n_slots, h_len, row0)) return KH_ERR_INVALID_ARG;
+  set_layout(m, n_slots, h_len, row0);
+  return KH_OK;
+}
+
+// Bookkeeping only: nothing is copied, nothing is launched.
+extern "C" int kh_model_seq_share(kh_model* m, int32_t src_slot, int32_t dst_slot, int32_t n_rows) {
+  if (!m || src_slot == dst_slot || n_rows < 0 || dst_slot == 0) return KH_ERR_INVALID_ARG;
+  if (src_slot < 0 || src_slot >= m->seq_slots || dst_slot < 0 || dst_slot >= m->seq_slots ||
+      n_rows > m->seq_tab[src_slot].len)
+    return KH_ERR_RANGE;
+  if (n_rows > 0 && m->seq_tab[src_slot].pfx > 0) return KH_ERR_UNSUPPORTED;  // one level only
+  for (int s = 0; s < m->seq_slots; ++s)
+    if (m->seq_tab[s].pfx > 0 && m->seq_tab[s].parent == dst_slot) return KH_ERR_UNSUPPORTED;  // dst has dependants
+  KhSeqSlot& d = m->seq_tab[dst_slot];
+  d.parent = n_rows > 0 ? src_slot : -1;
+  d.pfx = n_rows;
+  for (int s = 0; s < m->seq_slots; ++s) m->seq_tab[s].pmax = 0;
+  for (int s = 0; s < m->seq_slots; ++s) {
+    const KhSeqSlot& t = m->seq_tab[s];
+    if (t.pfx > 0 && t.pfx > m->seq_tab[t.parent].pmax) m->seq_tab[t.parent].pmax = t.pfx;
+  }
+  return KH_OK;
+}
+
+extern "C" int kh_model_seq_row(const kh_model* m, int32_t slot, int32_t pos, int32_t* row) {
+  if (!m || !row) return KH_ERR_INVALID_ARG;
+  if (slot < 0 || slot >= m->seq_slots || pos < 0 || pos >= cap(m, slot)) return KH_ERR_RANGE;
+  *row = seq_row(m, slot, pos);
   return KH_OK;
 }
 
@@ -160,37 +243,41 @@ extern "C" int kh_model_seq_width(const kh_model* m, int32_t* width) {
 
 extern "C" int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_tokens, int32_t n, int32_t pos0) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
-  const int len = slot_len(m);
-  if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > len) return KH_ERR_RANGE;
+  if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > cap(m, slot)) return KH_ERR_RANGE;
   if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
+  if (writes_shared(m, slot, pos0)) return KH_ERR_INVALID_ARG;  // a sharer below its shared length, a parent's shared rows
   if (!prefill_supported(m)) return KH_ERR_UNSUPPORTED;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
-  const int row0 = slot * len;
-  if ((rc = kv_ensure_rows(m, row0, row0 + pos0 + n)) != KH_OK) return rc;
+  const int row0 = own_base(m, slot);
+  if ((rc = ensure_slot_rows(m, slot, pos0 + n)) != KH_OK) return rc;
   if ((rc = seq_prepare(m)) != KH_OK) return rc;
-  if ((rc = seq_prefill_enqueue(m, row0, h_tokens, n, pos0)) != KH_OK) return rc;
+  if ((rc = seq_prefill_enqueue(m, row0, h_tokens, n, pos0, slot_of(m, slot).pfx, pfx_row0(m, slot))) != KH_OK)
+    return rc;
   return hist_write(m, h_tokens, n, row0 + pos0);  // the slot's fed-token record, as kh_model_prefill from row 0
 }
 
 extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot, int32_t n_rows) {
   if (!m || n_rows <= 0 || src_slot == dst_slot) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
-  const int len = slot_len(m);
-  if (src_slot < 0 || src_slot >= m->seq_slots || dst_slot < 0 || dst_slot >= m->seq_slots || n_rows > len)
+  if (src_slot < 0 || src_slot >= m->seq_slots || dst_slot < 0 || dst_slot >= m->seq_slots ||
+      n_rows > slot_of(m, src_slot).len || n_rows > slot_of(m, dst_slot).len)
     return KH_ERR_RANGE;
+  if (slot_of(m, src_slot).pfx > 0 || slot_of(m, dst_slot).pfx > 0) return KH_ERR_UNSUPPORTED;  // a sharer's rows are not one run
+  if (slot_of(m, dst_slot).pmax > 0) return KH_ERR_INVALID_ARG;  // a parent's shared rows are immutable
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
-  if ((rc = kv_ensure_rows(m, src_slot * len, src_slot * len + n_rows)) != KH_OK) return rc;
-  if ((rc = kv_ensure_rows(m, dst_slot * len, dst_slot * len + n_rows)) != KH_OK) return rc;
+  const size_t srow = (size_t)slot_of(m, src_slot).row0, drow = (size_t)slot_of(m, dst_slot).row0;
+  if ((rc = kv_ensure_rows(m, (int)srow, (int)srow + n_rows)) != KH_OK) return rc;
+  if ((rc = kv_ensure_rows(m, (int)drow, (int)drow + n_rows)) != KH_OK) return rc;
   const size_t nb = (size_t)n_rows * c.kv_dim * sizeof(float);
   for (int l = 0; l < c.layer_num; ++l) {
-    const size_t so = ((size_t)l * c.cache_len + (size_t)src_slot * len) * c.kv_dim;
-    const size_t dof = ((size_t)l * c.cache_len + (size_t)dst_slot * len) * c.kv_dim;
+    const size_t so = ((size_t)l * c.cache_len + srow) * c.kv_dim;
+    const size_t dof = ((size_t)l * c.cache_len + drow) * c.kv_dim;
     KH_CHECK_HIP(hipMemcpyAsync(m->kcache + dof, m->kcache + so, nb, hipMemcpyDeviceToDevice, m->stream));
     KH_CHECK_HIP(hipMemcpyAsync(m->vcache + dof, m->vcache + so, nb, hipMemcpyDeviceToDevice, m->stream));
   }
-  KH_CHECK_HIP(hipMemcpyAsync(m->d_hist + (size_t)dst_slot * len, m->d_hist + (size_t)src_slot * len,
+  KH_CHECK_HIP(hipMemcpyAsync(m->d_hist + drow, m->d_hist + srow,
                               sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToDevice, m->stream));
   return KH_OK;
 }
@@ -204,9 +291,8 @@ int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_
   const kh_config& c = m->cfg;
   if (ex_call ? !full_depth_supported(m) : seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
   if (n > verify_width(m)) return KH_ERR_RANGE;
-  const int len = slot_len(m);
   for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= m->seq_slots || pos[i] < 0 || pos[i] >= len || h_tokens[i] < 0 ||
+    if (slots[i] < 0 || slots[i] >= m->seq_slots || pos[i] < 0 || pos[i] >= cap(m, slots[i]) || h_tokens[i] < 0 ||
         h_tokens[i] >= c.vocab_size)
       return KH_ERR_RANGE;
     for (int j = 0; j < i; ++j)
@@ -216,17 +302,19 @@ int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_
   SeqEx ex;
   int rc;
   if ((rc = seq_ex_parse(m, n, o, &ex)) != KH_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    if (writes_shared(m, slots[i], pos[i])) return KH_ERR_INVALID_ARG;
+    if (penalties_on_sharer(m, o, i, slots[i])) return KH_ERR_UNSUPPORTED;  // its history lies in two row ranges
+  }
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   for (int i = 0; i < n; ++i)
-    if ((rc = kv_ensure_rows(m, slots[i] * len, slots[i] * len + pos[i] + 1)) != KH_OK) return rc;
+    if ((rc = ensure_slot_rows(m, slots[i], pos[i] + 1)) != KH_OK) return rc;
   if ((rc = seq_prepare(m)) != KH_OK) return rc;
   if (ex.on && (rc = seq_prepare_ex(m, ex.top_n >= 0)) != KH_OK) return rc;
   clear_slot_tables(m);
   KhSeqLanes lanes;
   for (int i = 0; i < n; ++i) {
-    lanes.pos[i] = pos[i];
-    lanes.row[i] = slots[i] * len + pos[i];
-    lanes.slot[i] = slots[i];
+    lane_set(m, lanes, i, slots[i], pos[i]);
     m->h_seq_tok_pin[slots[i]] = h_tokens[i];
     if (samplings && !kh_sampling_greedy(&samplings[i])) m->h_seq_samp_pin[slots[i]] = kh_samp_params(&samplings[i]);
   }
@@ -305,12 +393,11 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
   if (!m || !h_prompts || !n_prompt || !total_steps || !h_words || !n_words || n_seq <= 0 || words_stride <= 0 ||
       n_stop < 0 || (n_stop > 0 && !h_stop))
     return KH_ERR_INVALID_ARG;
-  const int len = slot_len(m);
   if (n_seq > m->seq_slots) return KH_ERR_RANGE;
   size_t n_tok = 0;
   for (int s = 0; s < n_seq; ++s) {
     if (n_prompt[s] <= 0 || total_steps[s] <= 0 || total_steps[s] > words_stride) return KH_ERR_INVALID_ARG;
-    if (total_steps[s] > len) return KH_ERR_RANGE;
+    if (total_steps[s] > cap(m, s)) return KH_ERR_RANGE;
     if (samplings && !kh_sampling_valid(&samplings[s])) return KH_ERR_INVALID_ARG;
     // only fed-only positions can be cached: the last prompt token's logits are the first pick's
     if (n_cached && (n_cached[s] < 0 || n_cached[s] > n_prompt[s] - 1 || n_cached[s] > total_steps[s]))
@@ -324,12 +411,17 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
     const int rc = seq_ex_parse(m, n_seq, o, &ex);
     if (rc != KH_OK) return rc;
   }
+  for (int s = 0; s < n_seq; ++s) {
+    // the first position the call feeds: what is cached must cover a sharer's shared length and a parent's shared rows
+    if (writes_shared(m, s, n_cached ? n_cached[s] : 0)) return KH_ERR_INVALID_ARG;
+    if (penalties_on_sharer(m, o, s, s)) return KH_ERR_UNSUPPORTED;  // its history lies in two row ranges
+  }
   return kh_api_guard([&]() -> int {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     int rc;
     for (int s = 0; s < n_seq; ++s) {
       n_words[s] = 0;
-      if ((rc = kv_ensure_rows(m, s * len, s * len + total_steps[s])) != KH_OK) return rc;
+      if ((rc = ensure_slot_rows(m, s, total_steps[s])) != KH_OK) return rc;
     }
     if ((rc = seq_prepare(m)) != KH_OK) return rc;
     if (ex.on && (rc = seq_prepare_ex(m, ex.top_n >= 0)) != KH_OK) return rc;
@@ -361,20 +453,27 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
       if ((rc = upload_proc_tables(m, n_seq, ex, [](int i) { return i; })) != KH_OK) return fail(rc);
       // every sequence's whole prompt at its slot's entries of the history (its cached part too: the prompt is here
       // whoever fed it), staged in pinned memory; the records of its fed-only positions become "none"
+      // (a sharer: from its shared length on - the rows below are its parent's, with the parent's history and records)
       for (int s = 0; s < n_seq; ++s) {
-        const int np = n_prompt[s] < len ? n_prompt[s] : len;
-        memcpy(m->h_seq_hist_pin + (size_t)s * len, prompt[s], sizeof(int32_t) * (size_t)np);
-        if (hipMemcpyAsync(m->d_hist + (size_t)s * len, m->h_seq_hist_pin + (size_t)s * len,
-                           sizeof(int32_t) * (size_t)np, hipMemcpyHostToDevice, m->stream) != hipSuccess)
-          return fail((int)hipErrorUnknown);
-        if (ex.top_n >= 0 && pos[s] > 0 && (rc = lp_fill_none(m, s * len, pos[s])) != KH_OK) return fail(rc);
+        const int np = n_prompt[s] < cap(m, s) ? n_prompt[s] : cap(m, s);
+        const int p0 = slot_of(m, s).pfx;
+        if (np > p0) {
+          const size_t at = (size_t)(own_base(m, s) + p0);
+          memcpy(m->h_seq_hist_pin + at, prompt[s] + p0, sizeof(int32_t) * (size_t)(np - p0));
+          if (hipMemcpyAsync(m->d_hist + at, m->h_seq_hist_pin + at, sizeof(int32_t) * (size_t)(np - p0),
+                             hipMemcpyHostToDevice, m->stream) != hipSuccess)
+            return fail((int)hipErrorUnknown);
+        }
+        if (ex.top_n >= 0 && pos[s] > p0 && (rc = lp_fill_none(m, own_base(m, s) + p0, pos[s] - p0)) != KH_OK)
+          return fail(rc);
       }
       if (ex.top_n >= 0) m->seq_lp_top_n = ex.top_n;
     }
     if (hipEventRecord(m->ev0, m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
     for (int s = 0; s < n_seq; ++s) {
       const int have = n_cached ? n_cached[s] : 0;
-      if (pos[s] > have && (rc = seq_prefill_enqueue(m, s * len, prompt[s] + have, pos[s] - have, have)) != KH_OK)
+      if (pos[s] > have && (rc = seq_prefill_enqueue(m, own_base(m, s), prompt[s] + have, pos[s] - have, have,
+                                                     slot_of(m, s).pfx, pfx_row0(m, s))) != KH_OK)
         return fail(rc);
     }
     int32_t* const pin = m->h_seq_words_pin;
@@ -387,7 +486,7 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
     auto mirror = [&]() -> int {
       for (int s = 0; s < n_seq; ++s)
         if (pos[s] > copied[s]) {
-          const size_t at = (size_t)s * len + copied[s];
+          const size_t at = (size_t)(own_base(m, s) + copied[s]);  // copied[s] >= the slot's shared length
           if (hipMemcpyAsync(pin + at, m->d_seq_words + at, sizeof(int32_t) * (size_t)(pos[s] - copied[s]),
                              hipMemcpyDeviceToHost, m->stream) != hipSuccess)
             return (int)hipErrorUnknown;
@@ -404,7 +503,7 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
       if (hipEventSynchronize(m->ev_chunk[head]) != hipSuccess) return (int)hipErrorUnknown;
       for (int s = 0; s < n_seq; ++s) {
         for (int p = checked[s]; p < infl[head].upto[s] && !stopped[s]; ++p)
-          if (is_stop(pin[(size_t)s * len + p], h_stop, n_stop)) {
+          if (is_stop(pin[(size_t)(own_base(m, s) + p)], h_stop, n_stop)) {
             stop_at[s] = p;
             stopped[s] = 1;
           }
@@ -423,9 +522,7 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
         if (n == 0) break;
         KhSeqLanes lanes;
         for (int i = 0; i < n; ++i) {
-          lanes.pos[i] = pos[who[i]];
-          lanes.row[i] = who[i] * len + pos[who[i]];
-          lanes.slot[i] = who[i];
+          lane_set(m, lanes, i, who[i], pos[who[i]]);
           pos[who[i]] += 1;
         }
         if ((rc = seq_pass_enqueue(m, lanes, n, /*words=*/true, ex.on ? &tail : nullptr)) != KH_OK) return fail(rc);
@@ -443,7 +540,7 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
       const int n_out = stop_at[s] >= 0 ? stop_at[s] : total_steps[s];
       int32_t* w = h_words + (size_t)s * words_stride;
       for (int p = 0; p < n_out; ++p)
-        w[p] = p < n_prompt[s] - 1 ? prompt[s][p + 1] : pin[(size_t)s * len + p];  // forced, main.cpp:36-38
+        w[p] = p < n_prompt[s] - 1 ? prompt[s][p + 1] : pin[(size_t)(own_base(m, s) + p)];  // forced, main.cpp:36-38
       n_words[s] = n_out;
     }
     if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
@@ -454,19 +551,30 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
 
 extern "C" int kh_model_seq_set_history(kh_model* m, int32_t slot, int32_t pos0, const int32_t* h_tokens, int32_t n) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
-  const int len = slot_len(m);
-  if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > len) return KH_ERR_RANGE;
+  if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > cap(m, slot)) return KH_ERR_RANGE;
+  if (writes_shared(m, slot, pos0)) return KH_ERR_INVALID_ARG;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
-  return hist_write(m, h_tokens, n, slot * len + pos0);
+  return hist_write(m, h_tokens, n, own_base(m, slot) + pos0);
 }
 
 extern "C" int kh_model_seq_get_logprobs(kh_model* m, int32_t slot, int32_t pos0, int32_t n, int32_t* h_token,
                                          float* h_lp, int32_t* h_top_ids, float* h_top_lp) {
   if (!m || n <= 0) return KH_ERR_INVALID_ARG;
   if (!m->d_lp_token || m->seq_lp_top_n < 0) return KH_ERR_UNSUPPORTED;
-  const int len = slot_len(m);
-  if (slot < 0 || slot >= m->seq_slots || pos0 < 0 || (int64_t)pos0 + n > len) return KH_ERR_RANGE;
-  return lp_read(m, slot * len + pos0, n, m->seq_lp_top_n, h_token, h_lp, h_top_ids, h_top_lp);
+  if (slot < 0 || slot >= m->seq_slots || pos0 < 0 || (int64_t)pos0 + n > cap(m, slot)) return KH_ERR_RANGE;
+  // a sharer has no records below its shared length (the rows there are its parent's, and so are the records): "none"
+  const int w = m->seq_lp_top_n > 0 ? m->seq_lp_top_n : 0;
+  const int skip = pos0 < slot_of(m, slot).pfx ? std::min(n, slot_of(m, slot).pfx - pos0) : 0;
+  if (skip > 0) {
+    if (h_token) memset(h_token, 0xFF, sizeof(int32_t) * (size_t)skip);
+    if (h_lp) memset(h_lp, 0xFF, sizeof(float) * (size_t)skip);
+    if (h_top_ids && w) memset(h_top_ids, 0xFF, sizeof(int32_t) * (size_t)skip * w);
+    if (h_top_lp && w) memset(h_top_lp, 0xFF, sizeof(float) * (size_t)skip * w);
+  }
+  if (skip == n) return KH_OK;
+  return lp_read(m, own_base(m, slot) + pos0 + skip, n - skip, m->seq_lp_top_n, h_token ? h_token + skip : nullptr,
+                 h_lp ? h_lp + skip : nullptr, h_top_ids ? h_top_ids + (size_t)skip * w : nullptr,
+                 h_top_lp ? h_top_lp + (size_t)skip * w : nullptr);
 }
 
 extern "C" int kh_seq_rank(int32_t n_seq, const float* h_lp, int32_t stride, const int32_t* first,

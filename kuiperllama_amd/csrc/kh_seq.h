@@ -94,8 +94,8 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_pick(const KhSeq
 //   temperature > 0, else that maximum;
 //   4. top_n >= 0: the record of cache row `row` - the pick, its log-prob and the top top_n of the logits the pick was
 //      made from; entries from top_n on are "none" (-1, NaN), as k_sample_lp leaves them;
-//   5. tok[slot] = words[row] = pick, and hist[row + 1] = pick unless pos is the slot's last position: row + 1 is then
-//      position 0 of the next slot.
+//   5. tok[slot] = words[row] = pick, and hist[row + 1] = pick unless pos is the slot's last position (cap[b] = the
+//      positions the lane's slot holds; slots differ in length): row + 1 is then a row of the next slot.
 // LDS: KhSampSmem + KhLpSmem, as k_sample_lp.  No scratch, plain vector stores.
 struct KhSeqTailArgs {
   float* logits;  // [B][vstride], processed in place
@@ -106,7 +106,7 @@ struct KhSeqTailArgs {
   const int32_t* bias_ids;     // [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX]
   const float* bias;           // [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX]
   int32_t* hist;               // [cache_len + 1] token fed at every cache row
-  int slot_len;
+  int32_t cap[KH_PF_BMAX];     // positions the lane's slot holds
   int32_t* cnt;                // [KH_PF_BMAX][vocab] counters, zero between launches
   int top_n;                   // -1: no record
   int32_t* rec_token;          // [cache_len]
@@ -154,6 +154,6 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_tail(const KhSeq
   if (threadIdx.x == 0) {
     a.tok[slot] = pick;
     if (a.words) a.words[row] = pick;
-    if (pos + 1 < a.slot_len) a.hist[row + 1] = pick;
+    if (pos + 1 < a.cap[b]) a.hist[row + 1] = pick;
   }
 }

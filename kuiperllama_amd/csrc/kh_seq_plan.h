@@ -14,6 +14,37 @@ static inline int kh_seq_slot_len(int cache_len, int n_slots) {
   return len >= KH_SEQ_SLOT_MIN_ROWS ? len : 0;
 }
 
+// slots of unequal length: slot s = rows [row0[s], row0[s] + len[s]), slot 0 from row 0 (the batch-1 sequence's rows),
+// the others behind it without gaps.  Returns false for what is not such a partition of the cache (fewer than
+// KH_SEQ_SLOT_MIN_ROWS rows in a slot, more rows than the cache holds); row0 may be null.
+static inline bool kh_seq_slots_var(int cache_len, int n_slots, const int32_t* len, int32_t* row0) {
+  if (cache_len <= 0 || n_slots < 1 || n_slots > KH_SEQ_SLOTS_MAX || !len) return false;
+  int64_t at = 0;
+  for (int s = 0; s < n_slots; ++s) {
+    if (len[s] < KH_SEQ_SLOT_MIN_ROWS) return false;
+    at += len[s];
+  }
+  if (at > cache_len) return false;
+  at = 0;
+  for (int s = 0; s < n_slots; ++s) {
+    if (row0) row0[s] = (int32_t)at;
+    at += len[s];
+  }
+  return true;
+}
+
+// A slot may read its positions [0, pfx) from the rows of another slot, its parent (kh_model_seq_share); it then owns
+// only what follows them: position p >= pfx lives at row0 + (p - pfx), and the slot holds pfx + len positions.
+struct KhSeqSlot {
+  int32_t row0 = 0, len = 0;  // the rows the slot owns
+  int32_t parent = -1;        // the slot whose rows [0, pfx) hold this slot's positions [0, pfx); -1: none
+  int32_t pfx = 0;            // shared positions (0: the slot shares nothing)
+  int32_t pmax = 0;           // as a parent: the largest pfx one of its dependants holds (rows below are immutable)
+};
+static inline int kh_seq_capacity(const KhSeqSlot& t) { return t.pfx + t.len; }
+// the row of position p >= t.pfx is kh_seq_own_base(t) + p; negative for a sharer near the start of the cache
+static inline int kh_seq_own_base(const KhSeqSlot& t) { return t.row0 - t.pfx; }
+
 // The lanes of the next pass.  Sequence s is live while pos[s] < total[s] and it has not been seen to stop.  Rounds
 // walk the sequences in slot order; a pass takes the next up to `width` live ones from the cursor on and never wraps
 // (a sequence sits in at most one lane of a pass), the cursor goes back to 0 behind the last sequence.  More than

@@ -47,6 +47,30 @@ def plan_seq_slots(cache_len: int, n_slots: int) -> int:
     return int(out.value)
 
 
+def plan_seq_slots_var(cache_len: int, lens: Sequence[int]) -> List[int]:
+    """First row of every slot of a cache of cache_len rows cut into slots of lens[s] rows (kh_plan_seq_slots_var;
+    host only)."""
+    out = (C.c_int32 * max(len(lens), 1))()
+    _ffi.check(_ffi.lib().kh_plan_seq_slots_var(int(cache_len), len(lens), _i32_array(lens), out),
+               "kh_plan_seq_slots_var")
+    return [int(out[s]) for s in range(len(lens))]
+
+
+def plan_shared_layout(cache_len: int, n_seq: int, n_prefix: int, total_steps) -> List[int]:
+    """Slot lengths for n_seq sequences of which slot 0 holds a prompt prefix of n_prefix positions and the others read
+    it from there (seq_share): the parent owns all of its total_steps positions, a sharer only those from n_prefix on,
+    every slot at least 8 rows.  total_steps: one int for all or one per sequence.  Raises ValueError where the
+    lengths do not fit cache_len rows (host only)."""
+    n_seq, n_prefix = int(n_seq), int(n_prefix)
+    totals = [int(total_steps)] * n_seq if isinstance(total_steps, (int, np.integer)) else [int(t) for t in total_steps]
+    if n_seq < 1 or len(totals) != n_seq or n_prefix < 0 or any(t < n_prefix for t in totals):
+        raise ValueError(f"plan_shared_layout: {n_seq} sequences, prefix {n_prefix}, totals {totals}")
+    lens = [max(8, totals[0])] + [max(8, t - n_prefix) for t in totals[1:]]
+    if n_seq > 64 or sum(lens) > int(cache_len):
+        raise ValueError(f"plan_shared_layout: {sum(lens)} rows in {n_seq} slots do not fit a cache of {cache_len}")
+    return lens
+
+
 def _seq_opts(n: int, sp, penalties, logit_bias, logprobs, what: str):
     """kh_seq_opts of an _ex call and the arrays it points to (keep both alive across the call): penalties = None | [n]
     of None | dict of set_penalties()'s keys | _ffi.Penalties; logit_bias = None | [n] of None | {id: value};
@@ -491,6 +515,24 @@ class KuiperModel:
         self._seq_slots = int(n_slots)
         return int(out.value)
 
+    def seq_slots_var(self, lens: Sequence[int]) -> None:
+        """Cut the cache rows into len(lens) slots of lens[s] rows, slot 0 from row 0 (kh_model_seq_slots_var).  Resets
+        every sharing relation, as seq_slots() does."""
+        _ffi.check(_ffi.lib().kh_model_seq_slots_var(self._h, len(lens), _i32_array(lens)), "kh_model_seq_slots_var")
+        self._seq_slots = len(lens)
+
+    def seq_share(self, src_slot: int, dst_slot: int, n_rows: int) -> None:
+        """Positions [0, n_rows) of dst_slot become src_slot's rows [0, n_rows) (kh_model_seq_share): nothing is
+        copied, dst_slot stores only what follows them and holds n_rows + its own length positions.  0 detaches."""
+        _ffi.check(_ffi.lib().kh_model_seq_share(self._h, int(src_slot), int(dst_slot), int(n_rows)),
+                   "kh_model_seq_share")
+
+    def seq_row(self, slot: int, pos: int) -> int:
+        """The cache row that holds position pos of sequence slot `slot` (kh_model_seq_row): read_kv's row."""
+        out = C.c_int32(0)
+        _ffi.check(_ffi.lib().kh_model_seq_row(self._h, int(slot), int(pos), C.byref(out)), "kh_model_seq_row")
+        return int(out.value)
+
     def seq_width(self) -> int:
         """Lanes (sequences) per pass of this model (kh_model_seq_width): 8 for fp32, 4 for int8 and wide fp32."""
         w = C.c_int32(0)
@@ -608,23 +650,35 @@ class KuiperModel:
     seq_rank = staticmethod(seq_rank)
 
     def best_of(self, prompt: Sequence[int], n: int, total_steps: int, sampling: dict, stop: Sequence[int] = (),
-                penalties: Optional[dict] = None, logit_bias: Optional[dict] = None, top_n: int = 0) -> List[dict]:
+                penalties: Optional[dict] = None, logit_bias: Optional[dict] = None, top_n: int = 0,
+                share: bool = False) -> List[dict]:
         """n samples of one prompt, best first: one seq_prefill of the prompt's fed-only part into slot 0, n - 1
         seq_forks, one generate_batch(cached=..) with seeds seed, seed + 1, .. of `sampling` (and the shared penalties
         / logit_bias), then seq_rank on the sampled positions' log-probs.  Returns [{"words", "mean_logprob", "seed"}]
         in rank order; sample i is exactly generate() of a batch-1 model under seed + i.  Cuts the cache into n slots
-        when the model has fewer."""
+        when the model has fewer.
+        share=True: the samples read the prompt's rows from slot 0 instead of holding copies - one prefill, n - 1
+        seq_share calls on plan_shared_layout(cfg.cache_len, ..) - so n samples need prompt + n * generated rows, not
+        n * (prompt + generated).  Same words and records; penalties are refused on sharing slots."""
         prompt, n, total_steps = [int(t) for t in prompt], int(n), int(total_steps)
         if n <= 0 or not prompt:
             raise ValueError("best_of: no sample, or an empty prompt")
-        if self._seq_slots < n:
-            self.seq_slots(n)
         seed0 = int(sampling.get("seed", 0))
         fed = min(len(prompt) - 1, total_steps)
+        share = bool(share) and fed > 0 and n > 1
+        if share:
+            if penalties is not None:
+                raise ValueError("best_of: penalties on slots that share a prefix are not supported")
+            self.seq_slots_var(plan_shared_layout(int(self.cfg.cache_len), n, fed, total_steps))
+        elif self._seq_slots < n:
+            self.seq_slots(n)
         if fed > 0:
             self.seq_prefill(0, prompt[:fed])
             for s in range(1, n):
-                self.seq_fork(0, s, fed)
+                if share:
+                    self.seq_share(0, s, fed)
+                else:
+                    self.seq_fork(0, s, fed)
         words, _ = self.generate_batch([prompt] * n, total_steps, [dict(sampling, seed=seed0 + s) for s in range(n)],
                                        stop=stop, cached=[fed] * n, penalties=[penalties] * n,
                                        logit_bias=[logit_bias] * n, logprobs=int(top_n))

@@ -16,7 +16,7 @@
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
-//               [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N]
+//               [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N] [--share-prefix]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -43,6 +43,9 @@
 // the sampler, penalty, bias and --logprobs flags per sequence (the model's own settings are not consulted), ranked by
 // kh_seq_rank on the mean log-prob of each sample's generated tokens: one line per sample, best first,
 // "mean_logprob seed | id id ...", then the aggregate "steps/s".  --logprobs defaults to 0 here.
+// --share-prefix (beside --parallel / --best-of): the samples read the prompt's rows from slot 0 instead of holding
+// copies (kh_model_seq_slots_var / kh_model_seq_share): prompt + N x generated rows of cache, not N x (prompt +
+// generated).  Same ids; penalties are refused on the sharing slots, as by the library.
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <cmath>
 #include <chrono>
@@ -54,6 +57,20 @@
 
 #include "kuiper_hip.h"
 
+// The slots of --parallel / --best-of: N equal ones whose samples hold copies of the prompt's rows (kh_model_seq_fork),
+// or with --share-prefix one parent that owns all `steps` positions and N - 1 slots that read the prompt's `have` rows
+// from it and own only what follows (kh_model_seq_slots_var, kh_model_seq_share).  *rows: rows of a sample's slot.
+static int seq_layout(kh_model* m, int n, int have, int steps, bool share, int32_t* rows) {
+  if (!share || have <= 0 || n < 2) return kh_model_seq_slots(m, n, rows);
+  std::vector<int32_t> len((size_t)n, steps - have > 8 ? steps - have : 8);
+  len[0] = steps > 8 ? steps : 8;
+  *rows = len[1];
+  return kh_model_seq_slots_var(m, n, len.data());
+}
+static int seq_attach(kh_model* m, int s, int have, bool share) {
+  return share ? kh_model_seq_share(m, 0, s, have) : kh_model_seq_fork(m, 0, s, have);
+}
+
 static void usage() {
   std::fprintf(stderr,
                "usage: kuiper_demo model.bin [--family llama|qwen2] [--quant] [--rope interleaved|half]\n"
@@ -63,7 +80,7 @@ static void usage() {
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
-               "       [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N]\n");
+               "       [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N] [--share-prefix]\n");
 }
 
 int main(int argc, char** argv) {
@@ -84,6 +101,7 @@ int main(int argc, char** argv) {
   kh_lookup_opts lk{0, 0, 0, nullptr, 0};
   int parallel = 0;  // --parallel N (kh_model_generate_batch)
   int best_of = 0;   // --best-of N (kh_model_generate_batch_ex, kh_seq_rank)
+  bool share_prefix = false;  // --share-prefix: the samples read the prompt's rows from slot 0 (kh_model_seq_share)
   std::vector<int32_t> hint;  // --hint
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
@@ -124,6 +142,7 @@ int main(int argc, char** argv) {
     else if (a == "--score") score = true;
     else if (a == "--parallel") parallel = std::atoi(next());
     else if (a == "--best-of") best_of = std::atoi(next());
+    else if (a == "--share-prefix") share_prefix = true;
     else if (a == "--lookup") {
       lookup = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') lk.ngram_max = std::atoi(argv[++i]);
@@ -310,9 +329,9 @@ int main(int argc, char** argv) {
     float ms = 0.f;
     std::printf("Generating...\n");
     const auto t0 = std::chrono::steady_clock::now();
-    rc = kh_model_seq_slots(m, N, &slot_len);
+    rc = seq_layout(m, N, have, steps, share_prefix, &slot_len);
     if (rc == KH_OK && have > 0) rc = kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
-    for (int s = 1; s < N && rc == KH_OK && have > 0; ++s) rc = kh_model_seq_fork(m, 0, s, have);
+    for (int s = 1; s < N && rc == KH_OK && have > 0; ++s) rc = seq_attach(m, s, have, share_prefix);
     if (rc == KH_OK)
       rc = kh_model_generate_batch_ex(m, N, prompts.data(), n_prompt.data(), cached.data(), totals.data(), &so,
                                       stop.data(), (int32_t)stop.size(), out.data(), steps, n_out.data(), &ms);
@@ -360,10 +379,10 @@ int main(int argc, char** argv) {
     float ms = 0.f;
     std::printf("Generating...\n");
     const auto t0 = std::chrono::steady_clock::now();
-    rc = kh_model_seq_slots(m, parallel, &slot_len);
+    rc = seq_layout(m, parallel, have, steps, share_prefix, &slot_len);
     if (rc == KH_OK) rc = kh_model_seq_width(m, &width);
     if (rc == KH_OK && have > 0) rc = kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
-    for (int s = 1; s < parallel && rc == KH_OK && have > 0; ++s) rc = kh_model_seq_fork(m, 0, s, have);
+    for (int s = 1; s < parallel && rc == KH_OK && have > 0; ++s) rc = seq_attach(m, s, have, share_prefix);
     if (rc == KH_OK)
       rc = kh_model_generate_batch_from(m, parallel, prompts.data(), n_prompt.data(), cached.data(), totals.data(),
                                         samps.data(), stop.data(), (int32_t)stop.size(), out.data(), steps,
