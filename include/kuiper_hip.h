@@ -287,6 +287,15 @@ typedef struct kh_model_opts {
  * this way).  kh_model_cls_screen_info reports; kh_model_cls_screen_probe / _read expose one screened step on a
  * caller-supplied vector, every row's interval, the bf16 copy and its error table to the tests. */
 #define KH_FLAG_NO_CLS_SCREEN 8
+/* W16: batch-1 decode of a bf16-exact fp32 model from a 16-bit copy of its matrices, bit for bit.  An fp32 .bin that was
+ * exported from a bf16 checkpoint holds zeros in the low 16 bits of every matrix word; with this flag the model keeps a
+ * second arena with the upper halves of wq, wk, wv, wo, w1, w2, w3 of every layer and of the classifier matrix (half
+ * their bytes on top of the fp32 image, which the B-token passes, the operator level and the embedding keep reading),
+ * and the decode GEMVs stream that copy: the same tokens, logits, K/V rows and log-prob records as without the flag,
+ * compared as raw bits, from half the weight bytes per token.  Nothing is ever rounded: if one matrix word of the
+ * image has a non-zero low half the copy is freed and the model behaves as if the flag were not set; likewise on int8
+ * images.  Hook KH_W16=1 / 0 at creation overrides the flag.  kh_model_w16_info reports. */
+#define KH_FLAG_W16 16
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -344,6 +353,11 @@ int kh_model_get_logits(kh_model* m, float* h_logits);
  * steps so far, candidate rows re-scored in them, steps that overflowed into the full classifier, candidate
  * capacity of a step */
 int kh_model_cls_screen_info(kh_model* m, int64_t* out8);
+/* W16 (KH_FLAG_W16): out[8] = state (0 off or not applicable, 1 on, -1 a matrix is not bf16-exact, -2 the creation-time
+ * self-check failed - in both cases the model streams fp32), bytes of the 16-bit copy, its build time in us, bit mask of
+ * the launch classes that run on it (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), index of the first inexact tensor (7 * layer
+ * + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: the classifier; -1 none), 0, 0, 0. */
+int kh_model_w16_info(kh_model* m, int64_t* out8);
 /* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
  * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave
  * every row.  out4 = screened token, full classifier's token, candidate rows re-scored, 1 if the step overflowed.
@@ -765,6 +779,10 @@ int kh_plan_decode_shapes(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32
  * kernel of kh_plan_decode_shapes) and with how many 256-thread workgroups.  Hook KH_RING=0 turns them off. */
 int kh_plan_decode_ring(int32_t dim, int32_t hidden_dim, int32_t vocab_size, int32_t is_quant, int32_t group_size,
                         int32_t* out4);
+/* kh_plan_w16: out2 = {bit mask of the decode launch classes that run on the 16-bit copy of KH_FLAG_W16 for this
+ * geometry (kh_model_w16_info; 0: not applicable - int8, or dims that are no multiple of 4), bytes of the copy}. */
+int kh_plan_w16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t layer_num, int32_t is_quant,
+                int64_t* out2);
 /* kh_plan_attention: the decode-attention geometry of kh_mha_decode_f32 / the fused step for a cache of seq_len rows:
  * out8 = {time splits per head, splits per KV group (0: no group path), workspace slot stride, first pos + 1 of the
  * group path, path taken at `pos` (0 per-head, 1 group), active splits at `pos`, timesteps per split at `pos`,

@@ -21,13 +21,13 @@ EXPORTS = [
     "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
-    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
+    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
     "kh_spm_create_from_file", "kh_spm_create_from_memory", "kh_spm_destroy", "kh_spm_vocab_size",
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
     "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
-    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
+    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
 ]
@@ -42,6 +42,8 @@ KH_FLAG_ATTN_MERGE_IN_LAUNCH = 1
 KH_FLAG_ATTN_MERGE_FENCED = 2
 KH_FLAG_PREFILL_EXACT = 4
 KH_FLAG_NO_CLS_SCREEN = 8
+KH_FLAG_W16 = 16
+KH_W16_CLASSES = ("qkv", "wo", "ffn13", "w2", "cls")  # bit i of a class mask (kh_model_w16_info, kh_plan_w16)
 KH_LOGPROBS_MAX_TOP = 20
 KH_SEQ_BIAS_MAX = 64
 
@@ -187,6 +189,8 @@ def lib() -> C.CDLL:
     L.kh_model_cls_screen_q8_info.argtypes = [_vp, C.POINTER(_i64)]
     L.kh_model_cls_screen_q8_probe.argtypes = [_vp, _vp, _i32, _vp, _vp, C.POINTER(_i64)]
     L.kh_model_cls_screen_q8_read.argtypes = [_vp, _vp, _vp, _vp]
+    L.kh_model_w16_info.argtypes = [_vp, C.POINTER(_i64)]
+    L.kh_plan_w16.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
     L.kh_model_get_kv.argtypes = [_vp, C.POINTER(_vp), C.POINTER(_vp)]
     L.kh_model_kv_bytes.argtypes = [_vp, C.POINTER(_i64), C.POINTER(_i64)]
     L.kh_model_read_kv.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp]
@@ -308,7 +312,7 @@ def launch_log() -> set:
     return {k for k in buf.value.decode().split("\n") if k}
 
 
-_HOOK_PREFIXES = ("KH_SHAPE_", "KH_ATTN_", "KH_PG_", "KH_PREFILL", "KH_RING", "KH_SELFTEST", "KH_KV_")
+_HOOK_PREFIXES = ("KH_SHAPE_", "KH_ATTN_", "KH_PG_", "KH_PREFILL", "KH_RING", "KH_SELFTEST", "KH_KV_", "KH_W16")
 _ENV_MIRRORED = {}  # hook -> value, as last written into the table FROM os.environ by sync_env()
 _ENV_SEEDED = False
 
@@ -387,6 +391,16 @@ def plan_decode_ring(dim: int, hidden_dim: int, vocab_size: int, quant: bool, gr
     if rc != 0:
         raise KhError(rc, "kh_plan_decode_ring")
     return {"ffn13": {"slots": out[0], "grid": out[1]}, "cls": {"slots": out[2], "grid": out[3]}}
+
+
+def plan_w16(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, n_layers: int, quant: bool) -> dict:
+    """The 16-bit weight copy of KH_FLAG_W16 for a geometry (host-only, kh_plan_w16): {"classes": the decode launch
+    classes that run on it ([]: not applicable, e.g. int8), "bytes": HBM the copy takes}."""
+    out = (_i64 * 2)()
+    rc = lib().kh_plan_w16(dim, hidden_dim, kv_dim, vocab_size, n_layers, int(quant), out)
+    if rc != 0:
+        raise KhError(rc, "kh_plan_w16")
+    return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "bytes": int(out[1])}
 
 
 def plan_attention(head_num: int, kv_mul: int, head_size: int, seq_len: int, pos: int) -> dict:

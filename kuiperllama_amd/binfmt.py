@@ -321,5 +321,41 @@ def tensor_from_image(img: torch.Tensor, e: TensorEntry) -> torch.Tensor:
     return t.reshape(e.shape)
 
 
+def w16_tensors(spec: ModelSpec) -> List[TensorEntry]:
+    """The matrices the 16-bit weight copy of KH_FLAG_W16 covers: wq, wk, wv, wo, w1, w2, w3 of every layer and the
+    classifier matrix - wcls, or tok_emb when the classifier is tied.  [] for an int8 image."""
+    if spec.quant:
+        return []
+    cls = "tok_emb" if spec.shared_classifier else "wcls"
+    mats = ("wq", "wk", "wv", "wo", "w1", "w2", "w3")
+    return [e for e in layout(spec)[0] if e.name == cls or (e.name.split(".")[0] in mats and len(e.shape) == 2)]
+
+
+def _words(image, e: TensorEntry) -> torch.Tensor:
+    """int32 view of one fp32 tensor of a host (numpy uint8) or device / host (torch uint8) image."""
+    t = torch.from_numpy(image) if isinstance(image, np.ndarray) else image
+    return t[e.offset: e.offset + e.nbytes].view(torch.int32)
+
+
+def round_matrices_bf16(image, spec: ModelSpec):
+    """Round the tensors of w16_tensors(spec) to the nearest bf16 value (ties to even), in place, and leave them as
+    fp32 words whose low 16 bits are zero: the image is then bf16-exact, what KH_FLAG_W16 needs.  Integer arithmetic on
+    the words; NaN stays NaN (quiet, payload truncated), a value that rounds past the largest finite one becomes Inf
+    as in IEEE.  image: numpy uint8 array or torch uint8 tensor on any device.  Returns image."""
+    for e in w16_tensors(spec):
+        w = _words(image, e)
+        nan = (w & 0x7FFFFFFF) > 0x7F800000
+        r = w + (0x7FFF + ((w >> 16) & 1))  # two's complement wrap-around = unsigned addition on the word
+        r = torch.where(nan, w | 0x00400000, r)
+        w.copy_(r & -65536)
+    return image
+
+
+def matrices_bf16_exact(image, spec: ModelSpec) -> bool:
+    """Is every matrix word of w16_tensors(spec) free of low-half bits, i.e. would KH_FLAG_W16 adopt the image?"""
+    ents = w16_tensors(spec)
+    return bool(ents) and all(not bool((_words(image, e) & 0xFFFF).any()) for e in ents)
+
+
 def spec_to_dict(spec: ModelSpec) -> dict:
     return dataclasses.asdict(spec)

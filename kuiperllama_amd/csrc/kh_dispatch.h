@@ -53,6 +53,31 @@ void kh_pick_bool(bool b, F&& f) {
     f(std::false_type{});
 }
 
+// The instantiations each decode GEMV kernel is compiled for, stated once: the dispatch of kh_model_step.hip and
+// kh_model_w16.hip, the LDS opt-in of configure_step_kernels and the KH_SHAPE_* validator of pick_shape all read these
+// lists.  U: 16-byte loads per row in flight per lane (kh_pick_ge: u >= 8 -> 8, >= 4 -> 4, else 2); MV: in-register
+// staging depth (kh_stage_maxv of the input length) and SP: waves sharing one row pair (kh_pick: an unlisted value
+// takes the last one listed).
+template <bool Q>
+using FusedU = std::conditional_t<Q, KhVals<4, 2>, KhVals<8, 4, 2>>;  // k_qkv, k_gemv_res as wo, k_wo_comb, k_ffn13, k_cls
+template <bool Q>
+using GemvResU = std::conditional_t<Q, KhVals<4, 3, 2>, KhVals<8, 4, 2>>;  // k_gemv_res as w2 (pick_shape, u3)
+using FusedMV = KhVals<4, 2, 1, 0>;
+using GemvResMV = KhVals<6, 4, 2, 1, 0>;  // w2 only: the 6-deep staging for hidden-sized inputs (wo's 6 runs as 0)
+using WoCombMV = KhVals<2, 4>;
+using QkvSP = KhVals<2, 1>;  // k_qkv's shape is split at most twice (plan_decode_shapes: max_split 2)
+using GemvResSP = KhVals<4, 2, 1>;  // k_gemv_res, k_wo_comb
+using NoSP = KhVals<1>;             // k_ffn13, k_cls
+// f(Q, U, MV, SP) with the compile-time values a launch shape selects from a kernel's lists
+template <template <bool> class US, class MVS, class SPS, class F>
+void pick_fused(bool quant, int u, int mv, int sp, F&& f) {
+  kh_pick_bool(quant, [&](auto Q) {
+    kh_pick_ge(US<decltype(Q)::value>{}, u, [&](auto U) {
+      kh_pick(MVS{}, mv, [&](auto MV) { kh_pick(SPS{}, sp, [&](auto SP) { f(Q, U, MV, SP); }); });
+    });
+  });
+}
+
 // one template argument of a launched kernel as the launch log spells it: "true" / "false" or a decimal number
 struct KhTArg {
   int v;

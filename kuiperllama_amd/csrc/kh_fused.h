@@ -64,10 +64,10 @@ struct KhQkvArgs {
 // __launch_bounds__(512, 4): at least 4 waves per SIMD, i.e. at most 128 VGPRs.  The long-row shapes run
 // two 512-thread workgroups per CU (16 waves); the fp32 U = 8 kernels sit at 120-130 registers and a
 // build that crossed 128 lost the second workgroup (w2 fp32 11.8 -> 12.5 us, profiles/r3_aux_first_ab.txt).
-template <bool QUANT, int U, int MAXV, int SPLIT>
-__global__ __launch_bounds__(KH_WG_MAX, 4) void k_qkv(const KhQkvArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  KH_STAMP_INIT();
+// The kernel's text, over the matrix view G (Gemv<QUANT, U>; kh_w16.h: GemvW16<U>) and the LDS layout of the staged
+// vector (LQ8: the q8_slot arrangement of the int8 view).  xs: the kernel's dynamic LDS.
+template <class G, bool LQ8, int MAXV, int SPLIT>
+__device__ __forceinline__ void qkv_body(const KhQkvArgs& a, f32x4* xs) {
   // Every kernel argument used inside the lambdas is first copied into a scalar local: a
   // lambda that captures the argument STRUCT by reference keeps the whole struct addressable
   // and the compiler then parks it in scratch memory (seen as 168 B/lane of scratch traffic).
@@ -81,8 +81,7 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_qkv(const KhQkvArgs a) {
   const float* const cos_cache = a.cos_cache;
   const int dim = a.dim, kv_dim = a.kv_dim, rope_mode = a.rope_mode;
   const float eps = a.eps;
-  f32x4* xs = (f32x4*)smem_raw;
-  float* red = lds_red_ptr<QUANT>(xs, dim);
+  float* red = lds_red_ptr<LQ8>(xs, dim);
   const int lane = threadIdx.x & 63;
   const int hs = a.head_size, half = hs >> 1;
   // head sizes are powers of two in every BASELINE config: shifts instead of the ~25-instruction
@@ -91,8 +90,8 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_qkv(const KhQkvArgs a) {
   const int half_sh = __builtin_ctz((unsigned)half | 0x40000000u);
   const int npq = dim >> 1, npk = kv_dim >> 1;
   const int total = npq + 2 * npk;
-  const Gemv<QUANT, U> g(dim, a.gshift);
-  Stager<true, QUANT, MAXV> st(a.x, a.att_norm, dim);
+  const G g(dim, a.gshift);
+  Stager<true, LQ8, MAXV> st(a.x, a.att_norm, dim);
   const int pos = *a.d_pos;
 
   // work item p -> (which projection, row pair, sin/cos column)
@@ -160,9 +159,15 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_qkv(const KhQkvArgs a) {
     dst[r0] = s0;
     dst[r1] = s1;
   };
-  gemv_pairs<SPLIT, /*ROLL=*/QUANT>(g, xs, total, lane, red + KH_WAVES_MAX, pair, pre,
+  gemv_pairs<SPLIT, /*ROLL=*/LQ8>(g, xs, total, lane, red + KH_WAVES_MAX, pair, pre,
                               [&]() __attribute__((always_inline)) { st.issue(); },
                               [&]() __attribute__((always_inline)) { rs = st.finish(xs, eps, red); }, epi);
+}
+template <bool QUANT, int U, int MAXV, int SPLIT>
+__global__ __launch_bounds__(KH_WG_MAX, 4) void k_qkv(const KhQkvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  KH_STAMP_INIT();
+  qkv_body<Gemv<QUANT, U>, QUANT, MAXV, SPLIT>(a, (f32x4*)smem_raw);
   KH_STAMP_FLUSH();
 }
 
@@ -188,7 +193,8 @@ struct KhGemvResArgs {
 };
 // STAGER(a, M): the staging of the input vector - Stager<false, ...> over a.vec, or CombStager over the
 // split partials of a deferring attention launch (k_wo_comb below).
-template <bool QUANT, int U, int SPLIT, class St>
+// G: the matrix view (Gemv<QUANT, U>; kh_w16.h: GemvW16<U>)
+template <class G, int SPLIT, class St>
 __device__ __forceinline__ void gemv_res_body(const KhGemvResArgs& a, St& st, f32x4* xs, float* red) {
   // scalar locals for everything the lambdas touch (see qkv_body)
   const void* const w = a.w.w;
@@ -196,7 +202,7 @@ __device__ __forceinline__ void gemv_res_body(const KhGemvResArgs& a, St& st, f3
   float* const x = a.x;
   const int M = a.M;
   const int lane = threadIdx.x & 63;
-  const Gemv<QUANT, U> g(M, a.gshift);
+  const G g(M, a.gshift);
   auto pair = [&](int p) __attribute__((always_inline)) { return g.rows(w, 2 * p, w, 2 * p + 1, scales, scales, M); };
   struct Aux {
     float x0, x1;
@@ -218,7 +224,7 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_gemv_res(const KhGemvResArgs a
   KH_STAMP_INIT();
   f32x4* xs = (f32x4*)smem_raw;
   Stager<false, QUANT, MAXV> st(a.vec, nullptr, a.M);
-  gemv_res_body<QUANT, U, SPLIT>(a, st, xs, lds_red_ptr<QUANT>(xs, a.M));
+  gemv_res_body<Gemv<QUANT, U>, SPLIT>(a, st, xs, lds_red_ptr<QUANT>(xs, a.M));
   KH_STAMP_FLUSH();
 }
 
@@ -363,10 +369,12 @@ struct KhWoCombArgs {
   KhCombArgs cb;
 };
 // wo behind a deferring attention launch.  MAXV in {2, 4} float4 of the dim-long vector per thread.
-template <bool QUANT, int U, int MAXV, int SPLIT>
-__global__ __launch_bounds__(KH_WG_MAX, 4) void k_wo_comb(const KhWoCombArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  f32x4* xs = (f32x4*)smem_raw;
+// (G, LQ8: as qkv_body; U is the view's tile depth, also for a view whose tile is narrower than the fp32 one, so that
+// a kernel on such a view batches its o loads like its fp32 twin)
+template <class G, bool LQ8, int MAXV, int SPLIT>
+__device__ __forceinline__ void wo_comb_body(const KhWoCombArgs& a, f32x4* xs) {
+  constexpr int U = G::kU;
+  constexpr bool QUANT = LQ8;
   float* red = lds_red_ptr<QUANT>(xs, a.g.M);
   const int nact = attn_active_splits(*a.cb.d_pos, a.cb.ns, a.cb.ts_shift);
   float* fl = red + 3 * KH_WAVES_MAX;
@@ -377,7 +385,7 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_wo_comb(const KhWoCombArgs a) 
   constexpr bool OVERLAP = !(U >= 8 || (QUANT && U >= 4 && MAXV >= 4));
   if constexpr (OVERLAP) {
     CombStager<QUANT, MAXV, (MAXV >= 4 ? 2 : 4)> st(a.cb, a.g.M, nact, fl);
-    gemv_res_body<QUANT, U, SPLIT>(a.g, st, xs, red);
+    gemv_res_body<G, SPLIT>(a.g, st, xs, red);
   } else {
     CombStager<QUANT, MAXV, 16 / MAXV> st(a.cb, a.g.M, nact, fl);
     st.issue();
@@ -386,8 +394,13 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_wo_comb(const KhWoCombArgs a) 
       __device__ __forceinline__ void issue() {}
       __device__ __forceinline__ void finish(f32x4*, float, float*) {}
     } none;
-    gemv_res_body<QUANT, U, SPLIT>(a.g, none, xs, red);
+    gemv_res_body<G, SPLIT>(a.g, none, xs, red);
   }
+}
+template <bool QUANT, int U, int MAXV, int SPLIT>
+__global__ __launch_bounds__(KH_WG_MAX, 4) void k_wo_comb(const KhWoCombArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  wo_comb_body<Gemv<QUANT, U>, QUANT, MAXV, SPLIT>(a, (f32x4*)smem_raw);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -399,15 +412,12 @@ struct KhFfn13Args {
   int dim, hidden, gshift;
   float eps;
 };
-template <bool QUANT, int U, int MAXV>
-__global__ __launch_bounds__(KH_WG_MAX, 4) void k_ffn13(const KhFfn13Args a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  KH_STAMP_INIT();
-  f32x4* xs = (f32x4*)smem_raw;
-  float* red = lds_red_ptr<QUANT>(xs, a.dim);
+template <class G, bool LQ8, int MAXV>  // as qkv_body
+__device__ __forceinline__ void ffn13_body(const KhFfn13Args& a, f32x4* xs) {
+  float* red = lds_red_ptr<LQ8>(xs, a.dim);
   const int lane = threadIdx.x & 63;
-  const Gemv<QUANT, U> g(a.dim, a.gshift);
-  Stager<true, QUANT, MAXV> st(a.x, a.ffn_norm, a.dim);
+  const G g(a.dim, a.gshift);
+  Stager<true, LQ8, MAXV> st(a.x, a.ffn_norm, a.dim);
   auto pair = [&](int r) __attribute__((always_inline)) { return g.rows(a.w1.w, r, a.w3.w, r, a.w1.scales, a.w3.scales, a.dim); };
   float rs = 1.f;  // RMS scale of x: set by the staging, applied in the epilogue
   auto epi = [&](int r, float s0, float s1, const NoAux&) __attribute__((always_inline)) {
@@ -416,6 +426,12 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_ffn13(const KhFfn13Args a) {
   gemv_pairs<1, /*ROLL=*/false>(g, xs, a.hidden, lane, nullptr, pair, [](int) __attribute__((always_inline)) { return NoAux{}; },
                        [&]() __attribute__((always_inline)) { st.issue(); },
                        [&]() __attribute__((always_inline)) { rs = st.finish(xs, a.eps, red); }, epi);
+}
+template <bool QUANT, int U, int MAXV>
+__global__ __launch_bounds__(KH_WG_MAX, 4) void k_ffn13(const KhFfn13Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  KH_STAMP_INIT();
+  ffn13_body<Gemv<QUANT, U>, QUANT, MAXV>(a, (f32x4*)smem_raw);
   KH_STAMP_FLUSH();
 }
 
@@ -430,15 +446,12 @@ struct KhClsArgs {
   int dim, vocab, gshift;
   float eps;
 };
-template <bool QUANT, int U, int MAXV>
-__global__ __launch_bounds__(KH_WG_MAX, 4) void k_cls(const KhClsArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  KH_STAMP_INIT();
-  f32x4* xs = (f32x4*)smem_raw;
-  float* red = lds_red_ptr<QUANT>(xs, a.dim);
+template <class G, bool LQ8, int MAXV>  // as qkv_body
+__device__ __forceinline__ void cls_body(const KhClsArgs& a, f32x4* xs) {
+  float* red = lds_red_ptr<LQ8>(xs, a.dim);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const Gemv<QUANT, U> g(a.dim, a.gshift);
-  Stager<true, QUANT, MAXV> st(a.x, a.final_norm, a.dim);
+  const G g(a.dim, a.gshift);
+  Stager<true, LQ8, MAXV> st(a.x, a.final_norm, a.dim);
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   auto r1_of = [&](int p) __attribute__((always_inline)) { return 2 * p + 1 < a.vocab ? 2 * p + 1 : 2 * p; };
@@ -477,6 +490,12 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_cls(const KhClsArgs a) {
     a.part_val[blockIdx.x] = v;
     a.part_idx[blockIdx.x] = i;
   }
+}
+template <bool QUANT, int U, int MAXV>
+__global__ __launch_bounds__(KH_WG_MAX, 4) void k_cls(const KhClsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  KH_STAMP_INIT();
+  cls_body<Gemv<QUANT, U>, QUANT, MAXV>(a, (f32x4*)smem_raw);
   KH_STAMP_FLUSH();
 }
 static inline size_t cls_lds_bytes(bool quant, int M) {

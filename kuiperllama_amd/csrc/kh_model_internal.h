@@ -1,5 +1,5 @@
 // kh_model_internal.h — state and cross-unit helpers of the model level of the C-ABI.
-// The model level is split into seven translation units:
+// The model level is split into eight translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
@@ -10,7 +10,9 @@
 //                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
 //   kh_model_screen.hip   the screened classifier of the greedy generate loop (kh_cls_screen.h kernels)
-//   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge and the screen
+//   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge, the screen and W16
+//   kh_model_w16.hip      the 16-bit copy of a bf16-exact fp32 model's matrices and the decode GEMV launches that read
+//                         it (kh_w16.h kernels are instantiated here)
 // gfx950 only.  No CPU fallback: every path launches HIP kernels.
 #pragma once
 #include <new>
@@ -55,6 +57,11 @@ using khm::LayerW;
 
 #define KH_STEP_VARIANTS 3  // kh_model_step.hip::step_variant
 struct KhSampParams;       // kh_sample.h
+struct KhQkvArgs;          // kh_fused.h
+struct KhGemvResArgs;
+struct KhWoCombArgs;
+struct KhFfn13Args;
+struct KhClsArgs;
 struct KhProcParams;       // kh_logit_proc.h
 struct kh_model {
   kh_config cfg{};
@@ -258,6 +265,23 @@ struct kh_model {
     Q8 q8;
   };
   ClsScreen scr;
+  // W16 (kh_w16.h, kh_model_w16.hip; KH_FLAG_W16 / hook KH_W16): a second arena with the upper halves of every matrix
+  // word of a bf16-exact fp32 model, read by the batch-1 decode GEMVs of the adopted launch classes
+  struct W16 {
+    int state = 0;          // 0 off or not applicable, 1 on, -1 some matrix is not bf16-exact, -2 the self-check failed
+    void* alloc = nullptr;  // what hipMalloc returned; arena = its first 4-KiB boundary
+    char* arena = nullptr;
+    size_t bytes = 0;       // of the copy (every matrix padded to 256 bytes)
+    float build_us = 0.f;   // k_w16_build over all matrices
+    int classes = 0;        // KH_W16_* bits: launch classes that run on the copy (plan_w16)
+    int first_inexact = -1; // tensor index 7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers = classifier
+    struct Layer {
+      const void *wq, *wk, *wv, *wo, *w1, *w2, *w3;
+    };
+    std::vector<Layer> layers;
+    const void* cls = nullptr;
+  };
+  W16 w16;
 };
 
 #define KH_GRAPH_STEPS 8
@@ -288,18 +312,30 @@ int configure_step_kernels(kh_model* m);  // >64 KiB dynamic-LDS opt-in of the h
 // variant (see kh_model::sg, step_variant): which attention / wo pair is launched; fenced: the form of the in-launch
 // split merge (m->attn_fenced, but for the self-test that compares the two)
 KhAttnArgs fill_attn(kh_model* m, int l, int variant, bool fenced);
-void launch_qkv(kh_model* m, int l);
+// w16: the launch reads the 16-bit copy (kh_model::w16; its kernel has the bits of the fp32 one); the forms without
+// the argument follow the model's plan
+enum { KH_W16_QKV = 1, KH_W16_WO = 2, KH_W16_FFN13 = 4, KH_W16_W2 = 8, KH_W16_CLS = 16, KH_W16_ALL = 31 };
+static inline bool w16_runs(const kh_model* m, int cls) { return (m->w16.classes & cls) != 0; }
+void launch_qkv(kh_model* m, int l, bool w16);
 void launch_attn(kh_model* m, int l, int variant, bool fenced);
-void launch_wo(kh_model* m, int l, int variant);
-void launch_ffn13(kh_model* m, int l, bool ring);  // ring: the LDS-DMA ring kernel (m->ring.ffn_r), else register tiles
-void launch_w2(kh_model* m, int l);
+void launch_wo(kh_model* m, int l, int variant, bool w16);
+// ring: the LDS-DMA ring kernel (m->ring.ffn_r), else register tiles
+void launch_ffn13(kh_model* m, int l, bool ring, bool w16);
+void launch_w2(kh_model* m, int l, bool w16);
+static inline void launch_qkv(kh_model* m, int l) { launch_qkv(m, l, w16_runs(m, KH_W16_QKV)); }
+static inline void launch_wo(kh_model* m, int l, int variant) { launch_wo(m, l, variant, w16_runs(m, KH_W16_WO)); }
+static inline void launch_ffn13(kh_model* m, int l, bool ring) { launch_ffn13(m, l, ring, w16_runs(m, KH_W16_FFN13)); }
+static inline void launch_w2(kh_model* m, int l) { launch_w2(m, l, w16_runs(m, KH_W16_W2)); }
 // what a classifier launch reads and writes; the model's own buffers and plan: launch_cls(m)
 struct ClsIo {
   const float* x;
   float *logits, *part_val;
   int32_t* part_idx;
 };
-void launch_cls(kh_model* m, const ClsIo& io, bool ring);
+void launch_cls(kh_model* m, const ClsIo& io, bool ring, bool w16);
+static inline void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
+  launch_cls(m, io, ring, w16_runs(m, KH_W16_CLS));
+}
 static inline void launch_cls(kh_model* m) {
   launch_cls(m, {m->x, m->logits, m->part_val, m->part_idx}, m->ring.cls_r == 2);
 }
@@ -380,6 +416,19 @@ int cls_screen_q8_selftest(kh_model* m, int32_t* d_flag, bool inject, int* resul
 void launch_sample_screen(kh_model* m, int advance, int n_forced);
 int cls_refresh_logits(kh_model* m);  // k_cls on the saved input if the logits buffer is stale
 int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result);
+// ---- kh_model_w16.hip -----------------------------------------------------------------------
+// Launch classes that run on the copy for a geometry (KH_W16_* bits, 0: not applicable) and the copy's bytes (host-only)
+int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, int layer_num, size_t* bytes);
+// the copy, once the weights are resident and ahead of the self-tests (no-op unless KH_FLAG_W16 / KH_W16=1 asks)
+int w16_create(kh_model* m);
+void w16_release(kh_model* m);  // frees the copy; no class runs on it afterwards
+// the W16 twins of the fp32 launches: `a` as the fp32 launch fills it, the matrices replaced by their copies here
+void w16_launch_qkv(kh_model* m, int l, const KhQkvArgs& a);
+void w16_launch_wo(kh_model* m, int l, const KhGemvResArgs& a);
+void w16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
+void w16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
+void w16_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
+void w16_launch_cls(kh_model* m, const KhClsArgs& a);
 // ---- kh_model_load.hip ----------------------------------------------------------------------
 // Make rows [0, rows) of the K / V cache usable before anything that touches them is enqueued: every layer, or one
 // (layer >= 0).  No-op for rows that are mapped already and for caches that are plainly allocated.  Newly mapped

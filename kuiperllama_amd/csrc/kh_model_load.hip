@@ -674,6 +674,7 @@ extern "C" void kh_model_destroy(kh_model* m) {
   for (void* q : {(void*)m->d_lp_top_n, (void*)m->d_lp_token, (void*)m->d_lp_lp, (void*)m->d_lp_top_ids, (void*)m->d_lp_top_lp})
     if (q) (void)hipFree(q);
   cls_screen_release(m);
+  w16_release(m);
   void* bufs[] = {m->x,      m->rms,    m->q,         m->att,       m->h1,       m->h3,
                   m->w2o,    m->logits, m->score,     m->sin_cache,
                   m->cos_cache, m->part_val, m->part_idx, m->d_pos, m->d_token,  m->d_next,
@@ -702,6 +703,7 @@ static int create_from_device_weights_impl(const int32_t* h_header, const void* 
   m->arena_bytes = weight_nbytes;
   m->cfg.weight_bytes = (int64_t)expected_weight_bytes(m->cfg);
   rc = finish_create(m);
+  if (rc == KH_OK) rc = w16_create(m);  // KH_FLAG_W16: the 16-bit copy of a bf16-exact model's matrices
   if (rc == KH_OK) rc = cls_screen_create(m);
   if (rc == KH_OK) rc = run_selftests(m);  // the weights are resident: ring kernels / split merge against their fallbacks
   if (rc != KH_OK) {
@@ -779,6 +781,8 @@ static int create_from_host_image_impl(const void* h_image, size_t nbytes, const
     if (es != hipSuccess) rc = (int)es;
   }
   pc.lap("upload || buffers, joined");
+  if (rc == KH_OK) rc = w16_create(m);  // the arena is resident: the 16-bit copy of a bf16-exact model's matrices (KH_FLAG_W16)
+  pc.lap("W16 copy");
   if (rc == KH_OK) rc = cls_screen_create(m);  // the arena is resident: bf16 copy of the classifier (fp32 models)
   pc.lap("bf16 classifier copy");
   if (rc == KH_OK) rc = run_selftests(m);

@@ -18,12 +18,15 @@
 //  (d) the int8 tier ahead of that screen (kh_model_screen.hip::cls_screen_q8_selftest): one three-launch tail against
 //      one full step on the same vector - the same token, every full logit inside the interval tier 1 gave its row.
 //      A failure turns the tier off and frees the int8 copy; the bf16 screen goes on (kh_model_cls_screen_q8_info: -1).
+//  (e) W16 (kh_w16.h, kh_model_w16.hip): every launch class that runs on the 16-bit copy, once against the fp32 kernel
+//      of the same launch - layer 0 or the classifier, a real embedding row as the residual stream - outputs compared
+//      word for word.  A mismatch frees the copy and the model streams fp32 (kh_model_w16_info: state -2).
 //
 // Both run on scratch state the model owns at that moment (activation buffers, rows of layer 0 of the still
 // empty KV cache, which are zeroed again) in about a millisecond.  This is a tripwire for a part, a compiler or a
 // partition mode on which the suite never ran - a race that shows once in a million launches will not trip it.
 // Hooks (kh_debug_set / KH_* environment at load): KH_SELFTEST=0 skips both; KH_SELFTEST_FAIL="ring", "attn" or
-// "ring,attn" (also "screen") reports the named comparison as failed (fault injection: tests/test_model_gpu.py checks that the
+// "ring,attn" (also "screen", "w16") reports the named comparison as failed (fault injection: tests/test_model_gpu.py checks that the
 // fallbacks engage and that decode still matches the oracle).
 // Replaces nothing in the reference (it has neither path); cf. kuiper/source/op/kernels/cuda/matmul_kernel.cu:56-87,
 // mha_kernel.cu:47-130 for the kernels these paths stand in for.
@@ -178,6 +181,96 @@ static int attn_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
   return KH_OK;
 }
 
+// *result: 0 not applicable, 1 passed, -1 failed (the copy is freed, every class back on its fp32 kernel)
+static int w16_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
+  const kh_config& c = m->cfg;
+  *result = 0;
+  if (m->w16.state != 1) return KH_OK;
+  hipStream_t s = m->stream;
+  const size_t dim = (size_t)c.dim, kv = (size_t)c.kv_dim, hid = (size_t)c.hidden_dim, voc = (size_t)c.vocab_size;
+  const size_t np = (size_t)m->nparts;
+  // scratch: x as the check found it | outputs of the W16 launch (q, K row, V row | x | h | logits)
+  size_t tmp_n = dim + 2 * kv;
+  if (hid > tmp_n) tmp_n = hid;
+  if (voc > tmp_n) tmp_n = voc;
+  float *x0 = nullptr, *tmp = nullptr, *tmp_pv = nullptr;
+  int32_t* tmp_pi = nullptr;
+  int rc = kv_ensure(m, 1, /*layer=*/0);  // the qkv launch writes row 0 of layer 0
+  if (rc == KH_OK) rc = dalloc(&x0, dim);
+  if (rc == KH_OK) rc = dalloc(&tmp, tmp_n);
+  if (rc == KH_OK) rc = dalloc(&tmp_pv, np);
+  if (rc == KH_OK) rc = dalloc(&tmp_pi, np);
+  auto diff = [&](const float* a, const float* b, size_t n) {
+    hipLaunchKernelGGL(k_st_diff, dim3(grid_for(n)), dim3(KH_WG), 0, s, (const uint32_t*)a, (const uint32_t*)b, n, d_flag);
+  };
+  auto copy = [&](float* dst, const float* src, size_t n) {
+    return hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, s);
+  };
+  hipError_t e = hipSuccess;
+  if (rc == KH_OK) {
+    set_state(m, 1 % c.vocab_size, 0);  // x = a real embedding row
+    e = copy(x0, m->x, dim);
+    if (w16_runs(m, KH_W16_QKV) && e == hipSuccess) {
+      launch_qkv(m, 0, /*w16=*/true);  // -> q, row 0 of layer 0's K and V
+      e = copy(tmp, m->q, dim);
+      if (e == hipSuccess) e = copy(tmp + dim, m->kcache, kv);
+      if (e == hipSuccess) e = copy(tmp + dim + kv, m->vcache, kv);
+      launch_qkv(m, 0, /*w16=*/false);
+      diff(m->q, tmp, dim);
+      diff(m->kcache, tmp + dim, kv);
+      diff(m->vcache, tmp + dim + kv, kv);
+      if (e == hipSuccess) e = hipMemsetAsync(m->kcache, 0, sizeof(float) * kv, s);  // the cache is empty again
+      if (e == hipSuccess) e = hipMemsetAsync(m->vcache, 0, sizeof(float) * kv, s);
+    }
+    if (w16_runs(m, KH_W16_WO) && e == hipSuccess) {  // x += wo . att, on the projected query as the vector
+      e = copy(m->att, m->q, dim);
+      launch_wo(m, 0, /*variant=*/0, /*w16=*/true);
+      if (e == hipSuccess) e = copy(tmp, m->x, dim);
+      if (e == hipSuccess) e = copy(m->x, x0, dim);
+      launch_wo(m, 0, /*variant=*/0, /*w16=*/false);
+      diff(m->x, tmp, dim);
+    }
+    if (w16_runs(m, KH_W16_FFN13) && e == hipSuccess) {
+      launch_ffn13(m, 0, /*ring=*/false, /*w16=*/true);  // -> h1
+      e = copy(tmp, m->h1, hid);
+      launch_ffn13(m, 0, /*ring=*/false, /*w16=*/false);
+      diff(m->h1, tmp, hid);
+    }
+    if (w16_runs(m, KH_W16_W2) && e == hipSuccess) {  // x += w2 . h1 (h1: what ffn13 left, or an earlier check)
+      if (!w16_runs(m, KH_W16_FFN13)) launch_ffn13(m, 0, /*ring=*/false, /*w16=*/false);
+      e = copy(x0, m->x, dim);
+      launch_w2(m, 0, /*w16=*/true);
+      if (e == hipSuccess) e = copy(tmp, m->x, dim);
+      if (e == hipSuccess) e = copy(m->x, x0, dim);
+      launch_w2(m, 0, /*w16=*/false);
+      diff(m->x, tmp, dim);
+    }
+    if (w16_runs(m, KH_W16_CLS) && e == hipSuccess) {
+      launch_cls(m, {m->x, tmp, tmp_pv, tmp_pi}, /*ring=*/false, /*w16=*/true);
+      launch_cls(m, {m->x, m->logits, m->part_val, m->part_idx}, /*ring=*/false, /*w16=*/false);
+      diff(m->logits, tmp, voc);
+      diff(m->part_val, tmp_pv, np);
+      diff((const float*)m->part_idx, (const float*)tmp_pi, np);
+    }
+  }
+  int32_t flag = 0;
+  if (rc == KH_OK && e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s);
+  if (rc == KH_OK && e == hipSuccess) e = hipStreamSynchronize(s);
+  for (void* q : {(void*)x0, (void*)tmp, (void*)tmp_pv, (void*)tmp_pi})
+    if (q) (void)hipFree(q);
+  if (rc != KH_OK) return rc;
+  if (e != hipSuccess) return (int)e;
+  if ((rc = kh_launch_status()) != KH_OK) return rc;
+  *result = 1;
+  if (!flag && !inject) return KH_OK;
+  *result = -1;
+  w16_release(m);
+  m->w16.state = -2;
+  m->w16.bytes = 0;
+  fprintf(stderr, "[kh] W16 self-check %s: the model streams its fp32 matrices\n", inject ? "reported as failed (hook)" : "FAILED");
+  return KH_OK;
+}
+
 // -> KH_OK, or a HIP / KH error when a launch itself failed (the model is then not usable).  Results in
 // m->cfg.ring_selftest / attn_merge_selftest: 0 not applicable (or skipped), 1 passed, -1 failed -> fallback
 // engaged, 2 (attention only) the fenced form was requested.
@@ -188,10 +281,12 @@ int run_selftests(kh_model* m) {
   const auto t0 = std::chrono::steady_clock::now();
   const char* inj = dbg("KH_SELFTEST_FAIL");
   int32_t* d_flag = nullptr;
-  KH_CHECK_HIP(hipMalloc((void**)&d_flag, 4 * sizeof(int32_t)));
-  int r = 0, a = 0, sc = 0, s8 = 0;
-  const hipError_t e = hipMemsetAsync(d_flag, 0, 4 * sizeof(int32_t), m->stream);
-  int rc = e == hipSuccess ? ring_selftest(m, d_flag, hook_has(inj, "ring"), &r) : (int)e;
+  KH_CHECK_HIP(hipMalloc((void**)&d_flag, 5 * sizeof(int32_t)));
+  int r = 0, a = 0, sc = 0, s8 = 0, w = 0;
+  const hipError_t e = hipMemsetAsync(d_flag, 0, 5 * sizeof(int32_t), m->stream);
+  // W16 first: the checks behind it then run on the kernels the model will launch
+  int rc = e == hipSuccess ? w16_selftest(m, d_flag + 4, hook_has(inj, "w16"), &w) : (int)e;
+  if (rc == KH_OK) rc = ring_selftest(m, d_flag, hook_has(inj, "ring"), &r);
   if (rc == KH_OK) rc = attn_selftest(m, d_flag + 1, hook_has(inj, "attn"), &a);
   if (rc == KH_OK) rc = cls_screen_selftest(m, d_flag + 2, hook_has_screen(inj), &sc);
   if (rc == KH_OK) rc = cls_screen_q8_selftest(m, d_flag + 3, hook_has(inj, "screen8"), &s8);
@@ -200,7 +295,7 @@ int run_selftests(kh_model* m) {
   m->cfg.ring_selftest = r;
   m->cfg.attn_merge_selftest = a;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
-    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d, classifier screen %d, its int8 tier %d (%.2f ms)\n", r, a, sc, s8,
+    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d, classifier screen %d, its int8 tier %d, W16 %d (%.2f ms)\n", r, a, sc, s8, w,
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return KH_OK;
 }

@@ -21,29 +21,8 @@
 
 namespace khm {
 
-// The instantiations each kernel is compiled for, stated once: the dispatch below, the LDS opt-in of
-// configure_step_kernels and the KH_SHAPE_* validator of pick_shape all read these lists.  U: 16-byte loads per row in
-// flight per lane (kh_pick_ge: u >= 8 -> 8, >= 4 -> 4, else 2); MV: in-register staging depth (kh_stage_maxv of the
-// input length) and SP: waves sharing one row pair (kh_pick: an unlisted value takes the last one listed).
-template <bool Q>
-using FusedU = std::conditional_t<Q, KhVals<4, 2>, KhVals<8, 4, 2>>;  // k_qkv, k_gemv_res as wo, k_wo_comb, k_ffn13, k_cls
-template <bool Q>
-using GemvResU = std::conditional_t<Q, KhVals<4, 3, 2>, KhVals<8, 4, 2>>;  // k_gemv_res as w2 (pick_shape, u3)
-using FusedMV = KhVals<4, 2, 1, 0>;
-using GemvResMV = KhVals<6, 4, 2, 1, 0>;  // w2 only: the 6-deep staging for hidden-sized inputs (wo's 6 runs as 0)
-using WoCombMV = KhVals<2, 4>;
-using QkvSP = KhVals<2, 1>;  // k_qkv's shape is split at most twice (plan_decode_shapes: max_split 2)
-using GemvResSP = KhVals<4, 2, 1>;  // k_gemv_res, k_wo_comb
-using NoSP = KhVals<1>;             // k_ffn13, k_cls
-// f(Q, U, MV, SP) with the compile-time values a launch shape selects from a kernel's lists
-template <template <bool> class US, class MVS, class SPS, class F>
-void pick_fused(bool quant, int u, int mv, int sp, F&& f) {
-  kh_pick_bool(quant, [&](auto Q) {
-    kh_pick_ge(US<decltype(Q)::value>{}, u, [&](auto U) {
-      kh_pick(MVS{}, mv, [&](auto MV) { kh_pick(SPS{}, sp, [&](auto SP) { f(Q, U, MV, SP); }); });
-    });
-  });
-}
+// (The instantiation lists of the kernels launched below - FusedU, GemvResU, FusedMV, ... - and pick_fused are in
+// kh_dispatch.h: kh_model_w16.hip launches the W16 twins of these kernels from the same lists.)
 
 // Launch shape of one GEMV: rows are processed as `pairs` work items of two M-long rows.
 //  split: waves sharing a pair (1/2/4) — raised while the launch has < 4096 waves and each wave
@@ -161,9 +140,10 @@ KhQkvArgs fill_qkv(kh_model* m, int l) {
   a.eps = c.rms_eps;
   return a;
 }
-void launch_qkv(kh_model* m, int l) {
+void launch_qkv(kh_model* m, int l, bool w16) {
   const kh_config& c = m->cfg;
   const KhQkvArgs a = fill_qkv(m, l);
+  if (w16) return w16_launch_qkv(m, l, a);  // the same shape on the 16-bit copy (kh_model_w16.hip)
   const kh_model::Shape& sh = m->sh_qkv;
   pick_fused<FusedU, FusedMV, QkvSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split,
                                      [&](auto Q, auto U, auto MV, auto SP) {
@@ -224,7 +204,7 @@ KhGemvResArgs fill_wo(kh_model* m, int l) {
   a.gshift = m->gshift;
   return a;
 }
-void launch_wo(kh_model* m, int l, int variant) {
+void launch_wo(kh_model* m, int l, int variant, bool w16) {
   const kh_config& c = m->cfg;
   const kh_model::Shape& sh = m->sh_wo;
   if (variant == 1) {  // behind a deferring attention launch: in-register staging of 2 or 4 float4
@@ -239,6 +219,7 @@ void launch_wo(kh_model* m, int l, int variant) {
     a.cb.nsw = m->attn_ws_stride;
     a.cb.heads = c.head_num;
     a.cb.hs = c.head_size;
+    if (w16) return w16_launch_wo_comb(m, l, a);
     pick_fused<FusedU, WoCombMV, GemvResSP>(c.is_quant, sh.u, c.dim <= 2 * 4 * sh.wg ? 2 : 4, sh.split,
                                             [&](auto Q, auto U, auto MV, auto SP) {
       kh_launch(KH_KERNEL(k_wo_comb, Q, U, MV, SP), sh.grid, sh.wg, comb_lds_bytes(Q, c.dim, c.head_num), m->stream, a);
@@ -246,12 +227,13 @@ void launch_wo(kh_model* m, int l, int variant) {
     return;
   }
   const KhGemvResArgs a = fill_wo(m, l);
+  if (w16) return w16_launch_wo(m, l, a);
   pick_fused<FusedU, FusedMV, GemvResSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split,
                                          [&](auto Q, auto U, auto MV, auto SP) {
     kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
   });
 }
-void launch_ffn13(kh_model* m, int l, bool ring) {
+void launch_ffn13(kh_model* m, int l, bool ring, bool w16) {
   const kh_config& c = m->cfg;
   const LayerW& W = m->layers[l];
   KhFfn13Args a;
@@ -270,12 +252,13 @@ void launch_ffn13(kh_model* m, int l, bool ring) {
               ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
+  if (w16) return w16_launch_ffn13(m, l, a);
   const kh_model::Shape& sh = m->sh_ffn;
   pick_fused<FusedU, FusedMV, NoSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto Q, auto U, auto MV, auto) {
     kh_launch(KH_KERNEL(k_ffn13, Q, U, MV), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
   });
 }
-void launch_w2(kh_model* m, int l) {
+void launch_w2(kh_model* m, int l, bool w16) {
   const kh_config& c = m->cfg;
   KhGemvResArgs a;
   a.vec = m->h1;
@@ -284,13 +267,14 @@ void launch_w2(kh_model* m, int l) {
   a.M = c.hidden_dim;
   a.K = c.dim;
   a.gshift = m->gshift;
+  if (w16) return w16_launch_w2(m, l, a);
   const kh_model::Shape& sh = m->sh_w2;  // int8 u 3: two exact tiles of three loads per row (pick_shape, u3)
   pick_fused<GemvResU, GemvResMV, GemvResSP>(c.is_quant, sh.u, kh_stage_maxv(c.hidden_dim, sh.wg), sh.split,
                                              [&](auto Q, auto U, auto MV, auto SP) {
     kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.hidden_dim), m->stream, a);
   });
 }
-void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
+void launch_cls(kh_model* m, const ClsIo& io, bool ring, bool w16) {
   const kh_config& c = m->cfg;
   if (io.logits == m->logits) logits_fresh(m);  // (enqueue_steps has the last word behind captured steps)
   KhClsArgs a;
@@ -310,6 +294,7 @@ void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
               ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
+  if (w16) return w16_launch_cls(m, a);
   const kh_model::Shape& sh = m->sh_cls;
   pick_fused<FusedU, FusedMV, NoSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto Q, auto U, auto MV, auto) {
     kh_launch(KH_KERNEL(k_cls, Q, U, MV), sh.grid, sh.wg, cls_lds_bytes(Q, c.dim), m->stream, a);

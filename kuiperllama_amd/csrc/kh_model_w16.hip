@@ -1,0 +1,235 @@
+// kh_model_w16.hip — W16 at the model level: the 16-bit copy of a bf16-exact fp32 model's matrices (plan, build,
+// exactness check, release), the decode GEMV launches that read it and kh_model_w16_info.  The kernels are kh_w16.h's;
+// each launch below is the fp32 launch of kh_model_step.hip with the same shape (split, u, grid, wg - a shape forced
+// through KH_SHAPE_* included) on the W16 twin of its kernel, so the bits do not change.
+// Replaces nothing in the reference (it streams fp32 weights: kuiper/source/op/kernels/cuda/matmul_kernel.cu:8-44).
+// gfx950 only.  No CPU fallback: every path below launches HIP kernels.
+#include <stdio.h>
+#include <string.h>
+
+#include "kh_dispatch.h"
+#include "kh_w16.h"
+#include "kh_model_internal.h"
+
+namespace khm {
+
+namespace {
+inline size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
+// the matrices the copy covers, in tensor-index order: {rows K, columns M} of wq, wk, wv, wo, w1, w2, w3
+inline void layer_dims(int dim, int hidden, int kv_dim, size_t (&K)[7], size_t (&M)[7]) {
+  const size_t d = (size_t)dim, h = (size_t)hidden, kv = (size_t)kv_dim;
+  const size_t k[7] = {d, kv, kv, d, h, d, h}, mm[7] = {d, d, d, d, d, h, d};
+  for (int i = 0; i < 7; ++i) {
+    K[i] = k[i];
+    M[i] = mm[i];
+  }
+}
+}  // namespace
+
+// Which launch classes run on the copy.  Every class does: in the same-box A/B (tools/w16_ab.py, profiles/w16_ab.txt)
+// each class's W16 median lies below its fp32 median by more than the range of the fp32 runs on all four geometries
+// (smallest margin: Qwen2.5-0.5B's qkv, 2.90 -> 2.85 us).  A class that one takes out here keeps its fp32 kernel and
+// costs nothing but its bytes in the copy.
+int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, int layer_num, size_t* bytes) {
+  if (bytes) *bytes = 0;
+  if (quant || dim <= 0 || hidden_dim <= 0 || kv_dim <= 0 || vocab_size <= 0 || layer_num <= 0) return 0;
+  if (dim % 4 != 0 || hidden_dim % 4 != 0) return 0;  // a lane's unit is four columns
+  size_t K[7], M[7], total = 0;
+  layer_dims(dim, hidden_dim, kv_dim, K, M);
+  for (int i = 0; i < 7; ++i) total += pad256(2 * K[i] * M[i]);
+  total *= (size_t)layer_num;
+  total += pad256(2 * (size_t)vocab_size * (size_t)dim);
+  if (bytes) *bytes = total;
+  return KH_W16_ALL;
+}
+
+void w16_release(kh_model* m) {
+  kh_model::W16& w = m->w16;
+  if (w.alloc) (void)hipFree(w.alloc);
+  w.alloc = nullptr;
+  w.arena = nullptr;
+  w.classes = 0;
+  w.layers.clear();
+  w.cls = nullptr;
+}
+
+// >64 KiB dynamic-LDS opt-in of k_gemv_res_w16 as w2 (configure_step_kernels does it for k_gemv_res)
+static void w16_configure(const kh_model* m) {
+  const size_t lds_need = fused_lds_bytes(false, m->cfg.hidden_dim);
+  if (lds_need <= 64 * 1024) return;
+  GemvResU<false>::each([&](auto U) {
+    GemvResSP::each([&](auto SP) {
+      KhVals<0, 6>::each([&](auto MV) {
+        (void)hipFuncSetAttribute((const void*)k_gemv_res_w16<decltype(U)::value, decltype(MV)::value, decltype(SP)::value>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need);
+      });
+    });
+  });
+}
+
+int w16_create(kh_model* m) {
+  const kh_config& c = m->cfg;
+  kh_model::W16& w = m->w16;
+  w = kh_model::W16();
+  const char* hook = dbg("KH_W16");
+  const bool want = hook ? hook[0] == '1' : (m->opts.flags & KH_FLAG_W16) != 0;
+  if (!want) return KH_OK;
+  size_t bytes = 0;
+  const int classes = plan_w16(c.is_quant != 0, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size, c.layer_num, &bytes);
+  if (!classes) return KH_OK;  // int8, or a geometry the view does not cover: nothing changes
+  const int nt = 7 * c.layer_num + 1;
+  uint32_t* d_flags = nullptr;
+  KH_CHECK_HIP(hipMalloc(&w.alloc, bytes + 4096));
+  if (hipMalloc((void**)&d_flags, sizeof(uint32_t) * (size_t)nt) != hipSuccess) {
+    w16_release(m);
+    return (int)hipErrorOutOfMemory;
+  }
+  w.arena = (char*)(((uintptr_t)w.alloc + 4095) & ~(uintptr_t)4095);
+  w.layers.resize((size_t)c.layer_num);
+  hipStream_t s = m->stream;
+  hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * (size_t)nt, s);
+  if (e == hipSuccess) e = hipEventRecord(m->ev0, s);
+  size_t K[7], M[7], off = 0;
+  layer_dims(c.dim, c.hidden_dim, c.kv_dim, K, M);
+  auto build = [&](const void* src, size_t elems, int tensor) -> const void* {
+    char* dst = w.arena + off;
+    off += pad256(2 * elems);
+    const size_t n4 = elems / 4, need = (n4 + KH_WG - 1) / KH_WG;
+    hipLaunchKernelGGL(k_w16_build, dim3((unsigned)(need < 4096 ? (need ? need : 1) : 4096)), dim3(KH_WG), 0, s,
+                       (const u32x4*)src, (u32x2*)dst, n4, d_flags + tensor);
+    return dst;
+  };
+  for (int l = 0; l < c.layer_num && e == hipSuccess; ++l) {
+    const LayerW& W = m->layers[(size_t)l];
+    const void* src[7] = {W.wq.w, W.wk.w, W.wv.w, W.wo.w, W.w1.w, W.w2.w, W.w3.w};
+    const void* dst[7];
+    for (int i = 0; i < 7; ++i) dst[i] = build(src[i], K[i] * M[i], 7 * l + i);
+    w.layers[(size_t)l] = kh_model::W16::Layer{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5], dst[6]};
+  }
+  w.cls = build(m->cls.w, (size_t)c.vocab_size * (size_t)c.dim, nt - 1);  // tok_emb when the classifier is tied
+  std::vector<uint32_t> flags((size_t)nt, 0);
+  if (e == hipSuccess) e = hipEventRecord(m->ev1, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d_flags);
+  int rc = e == hipSuccess ? kh_launch_status() : (int)e;
+  if (rc == KH_OK && off != bytes) rc = KH_ERR_INTERNAL;
+  if (rc != KH_OK) {
+    w16_release(m);
+    return rc;
+  }
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, m->ev0, m->ev1) == hipSuccess) w.build_us = ms * 1000.f;
+  w.bytes = bytes;
+  for (int t = 0; t < nt; ++t)
+    if (flags[(size_t)t]) {
+      w.first_inexact = t;
+      break;
+    }
+  if (w.first_inexact >= 0) {  // all or nothing: the model streams fp32 as if the flag were not set
+    w16_release(m);
+    w.state = -1;
+    w.bytes = 0;
+    return KH_OK;
+  }
+  w16_configure(m);
+  w.classes = classes;
+  w.state = 1;
+  if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
+    fprintf(stderr, "[kh] W16: %.1f MiB copy of %d matrices in %.0f us, classes 0x%x\n", (double)bytes / (1 << 20), nt,
+            (double)w.build_us, (unsigned)classes);
+  return KH_OK;
+}
+
+// ---- the launches ---------------------------------------------------------------------------
+// f(U, MV, SP) from the fp32 lists of a kernel (pick_fused without its QUANT level: a W16 kernel has no int8 form, and
+// walking both levels would compile it for the int8 values of U as well)
+template <class US, class MVS, class SPS, class F>
+static void pick_w16(int u, int mv, int sp, F&& f) {
+  kh_pick_ge(US{}, u, [&](auto U) {
+    kh_pick(MVS{}, mv, [&](auto MV) { kh_pick(SPS{}, sp, [&](auto SP) { f(U, MV, SP); }); });
+  });
+}
+void w16_launch_qkv(kh_model* m, int l, const KhQkvArgs& fp32) {
+  const kh_config& c = m->cfg;
+  KhQkvArgs a = fp32;
+  const kh_model::W16::Layer& W = m->w16.layers[(size_t)l];
+  a.wq.w = W.wq;
+  a.wk.w = W.wk;
+  a.wv.w = W.wv;
+  const kh_model::Shape& sh = m->sh_qkv;
+  pick_w16<FusedU<false>, FusedMV, QkvSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split, [&](auto U, auto MV, auto SP) {
+    kh_launch(KH_KERNEL(k_qkv_w16, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(false, c.dim), m->stream, a);
+  });
+}
+void w16_launch_wo(kh_model* m, int l, const KhGemvResArgs& fp32) {
+  const kh_config& c = m->cfg;
+  KhGemvResArgs a = fp32;
+  a.w.w = m->w16.layers[(size_t)l].wo;
+  const kh_model::Shape& sh = m->sh_wo;
+  pick_w16<FusedU<false>, FusedMV, GemvResSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split, [&](auto U, auto MV, auto SP) {
+    kh_launch(KH_KERNEL(k_gemv_res_w16, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(false, c.dim), m->stream, a);
+  });
+}
+void w16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& fp32) {
+  const kh_config& c = m->cfg;
+  KhWoCombArgs a = fp32;
+  a.g.w.w = m->w16.layers[(size_t)l].wo;
+  const kh_model::Shape& sh = m->sh_wo;
+  pick_w16<FusedU<false>, WoCombMV, GemvResSP>(sh.u, c.dim <= 2 * 4 * sh.wg ? 2 : 4, sh.split, [&](auto U, auto MV, auto SP) {
+    kh_launch(KH_KERNEL(k_wo_comb_w16, U, MV, SP), sh.grid, sh.wg, comb_lds_bytes(false, c.dim, c.head_num), m->stream, a);
+  });
+}
+void w16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& fp32) {
+  const kh_config& c = m->cfg;
+  KhFfn13Args a = fp32;
+  a.w1.w = m->w16.layers[(size_t)l].w1;
+  a.w3.w = m->w16.layers[(size_t)l].w3;
+  const kh_model::Shape& sh = m->sh_ffn;
+  pick_w16<FusedU<false>, FusedMV, NoSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto U, auto MV, auto) {
+    kh_launch(KH_KERNEL(k_ffn13_w16, U, MV), sh.grid, sh.wg, fused_lds_bytes(false, c.dim), m->stream, a);
+  });
+}
+void w16_launch_w2(kh_model* m, int l, const KhGemvResArgs& fp32) {
+  const kh_config& c = m->cfg;
+  KhGemvResArgs a = fp32;
+  a.w.w = m->w16.layers[(size_t)l].w2;
+  const kh_model::Shape& sh = m->sh_w2;
+  pick_w16<GemvResU<false>, GemvResMV, GemvResSP>(sh.u, kh_stage_maxv(c.hidden_dim, sh.wg), sh.split,
+                                             [&](auto U, auto MV, auto SP) {
+    kh_launch(KH_KERNEL(k_gemv_res_w16, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(false, c.hidden_dim), m->stream, a);
+  });
+}
+void w16_launch_cls(kh_model* m, const KhClsArgs& fp32) {
+  const kh_config& c = m->cfg;
+  KhClsArgs a = fp32;
+  a.wcls.w = m->w16.cls;
+  const kh_model::Shape& sh = m->sh_cls;
+  pick_w16<FusedU<false>, FusedMV, NoSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto U, auto MV, auto) {
+    kh_launch(KH_KERNEL(k_cls_w16, U, MV), sh.grid, sh.wg, cls_lds_bytes(false, c.dim), m->stream, a);
+  });
+}
+
+}  // namespace khm
+using namespace khm;
+
+// out2 = {KH_W16_* bits of the launch classes that run on the copy (0: not applicable), bytes of the copy}
+extern "C" int kh_plan_w16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t layer_num,
+                           int32_t is_quant, int64_t* out2) {
+  if (!out2 || dim <= 0 || hidden_dim <= 0 || kv_dim <= 0 || vocab_size <= 0 || layer_num <= 0) return KH_ERR_INVALID_ARG;
+  size_t bytes = 0;
+  out2[0] = plan_w16(is_quant != 0, dim, hidden_dim, kv_dim, vocab_size, layer_num, &bytes);
+  out2[1] = (int64_t)bytes;
+  return KH_OK;
+}
+
+extern "C" int kh_model_w16_info(kh_model* m, int64_t* out) {
+  if (!m || !out) return KH_ERR_INVALID_ARG;
+  memset(out, 0, 8 * sizeof(int64_t));
+  out[0] = m->w16.state;
+  out[1] = (int64_t)m->w16.bytes;
+  out[2] = (int64_t)m->w16.build_us;
+  out[3] = m->w16.classes;
+  out[4] = m->w16.first_inexact;
+  return KH_OK;
+}

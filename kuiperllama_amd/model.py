@@ -315,6 +315,17 @@ class KuiperModel:
         keys = ("on", "selftest", "bytes", "build_us", "steps", "candidates", "overflow_steps", "capacity")
         return dict(zip(keys, (int(v) for v in out)))
 
+    def w16_info(self) -> dict:
+        """The 16-bit weight copy of _ffi.KH_FLAG_W16 (kh_model_w16_info): state (0 off or not applicable, 1 on, -1 some
+        matrix is not bf16-exact, -2 the creation-time self-check failed), the copy's HBM bytes and build time, the
+        decode launch classes that stream it, and the first inexact tensor (7 * layer + index into wq, wk, wv, wo, w1,
+        w2, w3; 7 * n_layers: the classifier matrix; -1: none)."""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_w16_info(self._h, out), "kh_model_w16_info")
+        return {"state": int(out[0]), "bytes": int(out[1]), "build_us": int(out[2]),
+                "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1],
+                "first_inexact": int(out[4])}
+
     def cls_screen_probe(self, x: np.ndarray) -> dict:
         """One screened step and one full-classifier step on the residual vector x[dim], without advancing
         (kh_model_cls_screen_probe, tests): the two tokens, the candidate rows re-scored, whether the step overflowed,
