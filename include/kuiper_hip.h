@@ -820,6 +820,12 @@ int64_t kh_debug_list(char* buf, int64_t cap); /* '\n'-separated names; returns 
  * setting, resetting or unsetting the hook (kh_debug_set) empties it.  kh_debug_launch_log: the names,
  * '\n'-separated and sorted, into buf (always NUL-terminated); returns the bytes needed. */
 int64_t kh_debug_launch_log(char* buf, int64_t cap);
+/* Allocation accounting.  Every device and pinned-host buffer the library allocates is counted, process-wide.
+ * out4 = {live buffers, live bytes, allocations since hook KH_ALLOC_FAIL was last set or cleared, failures injected
+ * since then}.  Test hook KH_ALLOC_FAIL=k: the k-th such allocation after the hook was set answers
+ * hipErrorOutOfMemory (2) without reaching the runtime; setting, resetting or unsetting it restarts the count.  (Not
+ * counted: the weight arena and the mapped-on-demand KV cache.) */
+int kh_debug_alloc_stats(int64_t* out4);
 
 /* Duration (ms, HIP events on the model stream) of the prompt phase alone for n fed-only tokens:
  * KH_PREFILL_TOKEN = the reference's prompt phase, one forward pass per token (demo/main.cpp:20-22)

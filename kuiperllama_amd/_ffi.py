@@ -29,7 +29,7 @@ EXPORTS = [
     "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
-    "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log",
+    "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log", "kh_debug_alloc_stats",
 ]
 
 KH_EXEC_GRAPH, KH_EXEC_FUSED, KH_EXEC_UNFUSED = 0, 1, 2
@@ -284,6 +284,7 @@ def lib() -> C.CDLL:
     L.kh_debug_list.restype = _i64
     L.kh_debug_launch_log.argtypes = [C.c_char_p, _i64]
     L.kh_debug_launch_log.restype = _i64
+    L.kh_debug_alloc_stats.argtypes = [C.POINTER(_i64)]
     for name in EXPORTS:  # fail at load time, not at first call, if a symbol is missing
         getattr(L, name)
     _lib = L
@@ -310,6 +311,14 @@ def launch_log() -> set:
     buf = C.create_string_buffer(int(n) + 1)
     L.kh_debug_launch_log(buf, int(n) + 1)
     return {k for k in buf.value.decode().split("\n") if k}
+
+
+def alloc_stats() -> dict:
+    """The library's allocation accounting (kh_debug_alloc_stats): device and pinned-host buffers alive and their
+    bytes, process-wide; allocations made and failures injected since debug_set("KH_ALLOC_FAIL", k | None)."""
+    out = (_i64 * 4)()
+    check(lib().kh_debug_alloc_stats(out), "kh_debug_alloc_stats")
+    return {"live": int(out[0]), "live_bytes": int(out[1]), "allocs": int(out[2]), "injected": int(out[3])}
 
 
 _HOOK_PREFIXES = ("KH_SHAPE_", "KH_ATTN_", "KH_PG_", "KH_PREFILL", "KH_RING", "KH_SELFTEST", "KH_KV_", "KH_W16")

@@ -16,6 +16,7 @@
 #include <string>
 
 #include "../../include/kuiper_hip.h"
+#include "kh_buf.h"
 
 extern char** environ;
 
@@ -33,6 +34,7 @@ const std::string* intern(const std::string& v) {
   return &*pool.insert(v).first;
 }
 const char kLaunchLog[] = "KH_LAUNCH_LOG";
+const char kAllocFail[] = "KH_ALLOC_FAIL";  // kh_buf.h
 std::set<std::string> g_launched;  // kernel instantiations launched while KH_LAUNCH_LOG was on (guarded by g_mu)
 bool log_value_on(const std::string* v) { return v && !(v->size() && (*v)[0] == '0'); }
 std::map<std::string, const std::string*>& table() {
@@ -46,6 +48,8 @@ std::map<std::string, const std::string*>& table() {
     }
     auto it = m.find(kLaunchLog);
     khm::g_launch_log_on.store(it != m.end() && log_value_on(it->second));
+    it = m.find(kAllocFail);
+    if (it != m.end()) khm::alloc_fail_set(it->second->c_str());
     return m;
   }();
   return t;
@@ -80,10 +84,22 @@ extern "C" int kh_debug_set(const char* key, const char* value) {
     g_launched.clear();
     khm::g_launch_log_on.store(log_value_on(value ? t[key] : nullptr));
   }
+  if (strcmp(key, kAllocFail) == 0) khm::alloc_fail_set(value);  // ... and this one restarts the allocation count
   return KH_OK;
 }
 
 extern "C" const char* kh_debug_get(const char* key) { return khm::dbg(key); }
+
+extern "C" int kh_debug_alloc_stats(int64_t* out4) {
+  if (!out4) return KH_ERR_INVALID_ARG;
+  (void)khm::dbg(kAllocFail);  // the table is seeded: a hook that came with the environment holds from here on
+  const khm::KhAllocStats& s = khm::alloc_stats();
+  out4[0] = s.live.load(std::memory_order_relaxed);
+  out4[1] = s.live_bytes.load(std::memory_order_relaxed);
+  out4[2] = s.allocs.load(std::memory_order_relaxed);
+  out4[3] = s.injected.load(std::memory_order_relaxed);
+  return KH_OK;
+}
 
 namespace {
 int64_t copy_out(const std::string& all, char* buf, int64_t cap) {

@@ -14,18 +14,41 @@
 //   kh_model_w16.hip      the 16-bit copy of a bf16-exact fp32 model's matrices and the decode GEMV launches that read
 //                         it (kh_w16.h kernels are instantiated here)
 // gfx950 only.  No CPU fallback: every path launches HIP kernels.
+//
+// Ownership: every device or pinned-host buffer the library allocates is a KhDev<T> / KhPin<T> (kh_buf.h) - a field of
+// kh_model or a local - and frees itself; kh_model_destroy has no list of them.  A function that needs several buffers
+// together allocates into locals and moves them into the model once all of it succeeded, so a failed call leaves the
+// model as it found it and emptiness of one member of a group says whether the group exists.  Not owned this way, and
+// released by hand: the VMM-mapped KV cache (KvVmm, kv_release), the weight arena (borrowed in
+// kh_model_create_from_device_weights), the stream, events and graphs.
 #pragma once
 #include <new>
 #include <thread>
 #include <stdint.h>
 
+#include <utility>
 #include <vector>
 
 #include "kh_attn.h"
+#include "kh_buf.h"
 #include "kh_common.h"
 #include "kh_seq_plan.h"
 
 namespace khm {
+// the two places memory comes from (alloc: KH_OK or the HIP error code)
+struct KhDevMem {
+  static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static void free(void* p) { (void)hipFree(p); }
+};
+struct KhPinMem {
+  static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+static_assert(KH_BUF_OK == KH_OK && KH_BUF_OOM == (int)hipErrorOutOfMemory, "kh_buf.h speaks HIP's codes");
+template <class T>
+using KhDev = KhBuf<T, KhDevMem>;
+template <class T>
+using KhPin = KhBuf<T, KhPinMem>;
 // No C++ exception crosses the C ABI: the entry points that allocate host containers or start threads run their
 // body through this (std::bad_alloc -> hipErrorOutOfMemory, anything else -> KH_ERR_INTERNAL).
 template <class F>
@@ -53,6 +76,8 @@ struct LayerW {
 };
 
 }  // namespace khm
+using khm::KhDev;
+using khm::KhPin;
 using khm::LayerW;
 
 #define KH_STEP_VARIANTS 3  // kh_model_step.hip::step_variant
@@ -67,7 +92,8 @@ struct kh_model {
   kh_config cfg{};
   kh_model_opts opts{};
   hipStream_t stream = nullptr;
-  // weights: one arena holding the .bin bytes after the header, in file order
+  // weights: one arena holding the .bin bytes after the header, in file order (a raw pointer: borrowed from the
+  // caller by kh_model_create_from_device_weights, else freed by kh_model_destroy)
   char* arena = nullptr;
   bool owns_arena = false;
   size_t arena_bytes = 0;
@@ -77,11 +103,12 @@ struct kh_model {
   KhLin cls{};
   int gshift = 0;
   // activations / caches (llama3.cpp:425-500)
-  float *x = nullptr, *rms = nullptr, *q = nullptr, *att = nullptr, *h1 = nullptr,
-        *h3 = nullptr, *w2o = nullptr, *logits = nullptr, *score = nullptr, *kcache = nullptr,
-        *vcache = nullptr, *sin_cache = nullptr, *cos_cache = nullptr;
-  float* part_val = nullptr;
-  int32_t* part_idx = nullptr;
+  KhDev<float> x, rms, q, att, h1, h3, w2o, logits, score, sin_cache, cos_cache;
+  // the cache's addresses: reserved ranges of KvVmm (not owned here: kv_release), or kv_plain's two halves
+  float *kcache = nullptr, *vcache = nullptr;
+  KhDev<float> kv_plain[2];
+  KhDev<float> part_val;
+  KhDev<int32_t> part_idx;
   int nparts = 0;
   // KV cache on reserved addresses, physical memory mapped on demand (kh_model_load.hip::kv_ensure): the contiguous
   // [layer, cache_len, kv_dim] addressing of llama3.cpp:469-472 with HBM committed only for the rows a sequence reached
@@ -102,7 +129,7 @@ struct kh_model {
   KvVmm kv;
   float load_ms = 0.f;      // host image -> HBM upload time (kh_model_get_load_ms)
   std::thread unmap_thread;  // kh_model_create_from_file: munmap of the file off the critical path, joined by destroy
-  void* attn_ws = nullptr;  // split-T attention partials + tickets (kh_attn.h)
+  KhDev<char> attn_ws;  // split-T attention partials + tickets (kh_attn.h)
   int attn_ns = 1;
   int attn_ns_g = 0;        // GQA long-context path: splits per KV group (0 = path off)
   int attn_ws_stride = 1;   // split slots per head in attn_ws
@@ -112,66 +139,64 @@ struct kh_model {
   bool attn_fenced = false;  // KH_FLAG_ATTN_MERGE_FENCED / KH_ATTN_FENCED: fences around the in-launch split merge
   bool attn_defer = false;  // variant 1 exists: split partials combined by kh_fused.h::k_wo_comb
   int attn_defer_max = 0;   // ... up to this many active splits (more: the in-launch merge is as fast or faster)
-  int32_t *d_pos = nullptr, *d_token = nullptr, *d_next = nullptr, *d_forced = nullptr,
-          *d_words = nullptr;
+  KhDev<int32_t> d_pos, d_token, d_next, d_forced, d_words;
   int seq_cap = 0;  // capacity of d_forced / d_words
   // prefill (kh_prefill.h): residual / q / attention / hidden rows of up to KH_PF_BMAX prompt tokens
-  float *pf_x = nullptr, *pf_q = nullptr, *pf_att = nullptr, *pf_h = nullptr;
-  void* pf_ws = nullptr;        // KH_PF_BMAX attention split workspaces
+  // (one group, made by the first call that needs it: pf_x says whether it exists)
+  KhDev<float> pf_x, pf_q, pf_att, pf_h;
+  KhDev<char> pf_ws;            // KH_PF_BMAX attention split workspaces
   size_t pf_ws_tok_bytes = 0;
   // sequence scoring (kh_model_score): k_pf_cls's logits of one pass, [KH_PF_BMAX][pf_vstride], pf_vstride = the
-  // vocabulary rounded up to 4 floats; allocated by the first score call
-  float* pf_logits = nullptr;
+  // vocabulary rounded up to 4 floats; made by the first call that needs it
+  KhDev<float> pf_logits;
   int pf_vstride = 0;
   // speculative greedy decode (kh_model_verify, kh_spec.h): the result block of a verify pass {a, pick[0 .. 8)} on the
-  // device and its pinned mirror; allocated by the first verify pass
-  int32_t* d_spec = nullptr;
-  int32_t* h_spec_pin = nullptr;
+  // device and its pinned mirror; one group, made by the first verify pass
+  KhDev<int32_t> d_spec;
+  KhPin<int32_t> h_spec_pin;
   // Sequence slots (kh_model_seq_slots, kh_model_seq.hip): the cache rows cut into seq_slots equal regions of
-  // cache_len / seq_slots rows - bookkeeping, no kernel reads it.  Device tables with one entry per slot, allocated
-  // by the first seq pass: the token the slot's sequence feeds next and its sampling parameters; the words of every
+  // cache_len / seq_slots rows - bookkeeping, no kernel reads it.  Device tables with one entry per slot, one group
+  // made by the first seq pass: the token the slot's sequence feeds next and its sampling parameters; the words of every
   // sequence at its slot's rows ([cache_len]); pinned mirrors / staging of the three.
   int seq_slots = 1;
   // ... or into slots of unequal length (kh_model_seq_slots_var), some of which read a prompt prefix from another
   // slot's rows (kh_model_seq_share): row0 / len / sharing of every slot; the equal partition is the same table
   KhSeqSlot seq_tab[KH_SEQ_SLOTS_MAX];
   bool seq_pfx_pad8 = false;  // hook KH_SEQ_PFX_PAD=1: k_seq_attn_pfx's grid.x padded to a multiple of 8
-  int32_t* d_seq_tok = nullptr;
-  KhSampParams* d_seq_samp = nullptr;
-  int32_t* d_seq_words = nullptr;
-  int32_t* h_seq_tok_pin = nullptr;
-  KhSampParams* h_seq_samp_pin = nullptr;
-  int32_t* h_seq_words_pin = nullptr;
+  KhDev<int32_t> d_seq_tok;
+  KhDev<KhSampParams> d_seq_samp;
+  KhDev<int32_t> d_seq_words;
+  KhPin<int32_t> h_seq_tok_pin;
+  KhPin<KhSampParams> h_seq_samp_pin;
+  KhPin<int32_t> h_seq_words_pin;
   // ... with per-sequence processors or log-probs (kh_model_seq_step_ex, kh_model_generate_batch_ex; k_seq_tail):
   // per-slot KhProcParams and bias lists [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX], the processing core's counters per LANE
   // [KH_PF_BMAX][vocab] (zeroed once, the core re-arms them), pinned staging of the tables and of the history uploads
-  // [cache_len]; allocated by the first call that asks (seq_prepare_ex).  The history is d_hist and the records are
+  // [cache_len]; one group, made by the first call that asks (seq_prepare_ex).  The history is d_hist and the records are
   // d_lp_* below, both addressed by cache row.  seq_lp_top_n: the record width of the last such call (-1: none yet)
-  KhProcParams* d_seq_proc = nullptr;
-  int32_t* d_seq_bias_ids = nullptr;
-  float* d_seq_bias = nullptr;
-  int32_t* d_seq_cnt = nullptr;
-  KhProcParams* h_seq_proc_pin = nullptr;
-  int32_t* h_seq_bias_ids_pin = nullptr;
-  float* h_seq_bias_pin = nullptr;
-  int32_t* h_seq_hist_pin = nullptr;
+  KhDev<KhProcParams> d_seq_proc;
+  KhDev<int32_t> d_seq_bias_ids;
+  KhDev<float> d_seq_bias;
+  KhDev<int32_t> d_seq_cnt;
+  KhPin<KhProcParams> h_seq_proc_pin;
+  KhPin<int32_t> h_seq_bias_ids_pin;
+  KhPin<float> h_seq_bias_pin;
+  KhPin<int32_t> h_seq_hist_pin;
   int seq_lp_top_n = -1;
-  // GEMM prefill (kh_gemm.h): slabs of KH_PG_TMAX token rows
-  float *pg_x = nullptr, *pg_xn = nullptr, *pg_q = nullptr, *pg_att = nullptr, *pg_h = nullptr;
-  float* pg_part = nullptr;     // partial rows of residual GEMMs that split K across workgroups
-  void* pg_ws = nullptr;        // KH_PG_TMAX attention split workspaces
+  // GEMM prefill (kh_gemm.h): slabs of KH_PG_TMAX token rows (one group: pg_x says whether it exists)
+  KhDev<float> pg_x, pg_xn, pg_q, pg_att, pg_h;
+  KhDev<float> pg_part;         // partial rows of residual GEMMs that split K across workgroups
+  KhDev<char> pg_ws;            // KH_PG_TMAX attention split workspaces (the first pass that takes the fallback)
   size_t pg_ws_tok_bytes = 0;
-  bool pf_ready = false, pg_ready = false;  // set when ALL prefill slabs exist (allocation can fail half-way)
   bool pg_launch_failed = false;
-  int32_t* h_words_pin = nullptr;  // pinned mirror of d_words (stop-token check, final copy-out)
-  int32_t* h_forced_pin = nullptr; // pinned staging of d_forced [seq_cap + 1]: the upload needs no host sync
+  KhPin<int32_t> h_words_pin;   // pinned mirror of d_words (stop-token check, final copy-out)
+  KhPin<int32_t> h_forced_pin;  // pinned staging of d_forced [seq_cap + 1]: the upload needs no host sync
   int forced_hwm = 0;              // entries of d_forced that may differ from -1 (the last generate's upload)
   bool forced_in_flight = false;   // a generate returned before its final stream sync: h_forced_pin may be under DMA
   // near-tie report (kh_model_first_sample): logits of the first sampled step of the last generate with a prefill
-  float* first_logits = nullptr;  // [vocab], allocated on first use
+  KhDev<float> first_logits;      // [vocab], made on first use
   int first_pos = -1;             // -1: the last generate had no prefill phase
   int first_mode = 0;             // 1 = kh_model_prefill, 2 = kh_model_prefill_gemm
-  int pin_cap = 0;
   hipEvent_t ev_chunk[2] = {nullptr, nullptr};
   // launch geometry
   struct Shape {
@@ -202,48 +227,48 @@ struct kh_model {
   // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
   kh_sampling samp{0.f, 0, 1.f, 0};
   bool samp_on = false;
-  KhSampParams* d_samp = nullptr;
+  KhDev<KhSampParams> d_samp;
   // Logit processors (kh_logit_proc.h).  d_hist[hist_cap = cache_len + 1]: the token fed at every position, -1 where
   // none was: written by set_state, by k_sample_proc for the token it feeds next, by the prompt upload of a generate
   // with processors on and by kh_model_prefill / kh_model_prefill_gemm - like the K/V rows, slots below a call's
   // position are whatever earlier calls left.  Sized by the cache, not by seq_cap: predict reaches every position.
   // kh_model_set_penalties / kh_model_set_logit_bias: host copies, whether anything is on, and the device copies the
-  // captured k_sample_proc launches read (new values need no recapture; a bias list that outgrows bias_cap does).
-  int32_t* d_hist = nullptr;
+  // captured k_sample_proc launches read (new values need no recapture; a bias list that outgrows d_bias does).
+  KhDev<int32_t> d_hist;
   int hist_cap = 0;
   kh_penalties pen{1.f, 0.f, 0.f, 0};
-  int n_bias = 0, bias_cap = 0;
+  int n_bias = 0;
   bool proc_on = false;
-  KhProcParams* d_proc = nullptr;
-  int32_t* d_bias_ids = nullptr;
-  float* d_bias = nullptr;
-  int32_t* d_cnt = nullptr;  // [vocab] counters of the processing core, zero between launches
+  KhDev<KhProcParams> d_proc;
+  KhDev<int32_t> d_bias_ids;
+  KhDev<float> d_bias;
+  KhDev<int32_t> d_cnt;  // [vocab] counters of the processing core, zero between launches
   // Log-probs (kh_logprobs.h, kh_model_set_logprobs).  lp_top_n: -1 off, else the width of a record's top list; its
   // device copy d_lp_top_n is what the captured k_sample_lp launches read (a new width needs no recapture).  Records of
   // every position, [lp_cap = cache_len] with a fixed stride of KH_LOGPROBS_MAX_TOP like d_hist: predict reaches every
-  // position.  Allocated by the first call that turns the feature on, all bytes 0xff ("none": -1 / NaN) where no
+  // position.  One group, made by the first call that needs records (lp_ensure_records), all bytes 0xff ("none": -1 / NaN) where no
   // sampled step wrote.  While on, d_proc / d_samp / d_cnt exist too (neutral / greedy unless set): k_sample_lp reads them.
   int lp_top_n = -1;
   int lp_cap = 0;
-  int32_t* d_lp_top_n = nullptr;
-  int32_t* d_lp_token = nullptr;
-  float* d_lp_lp = nullptr;
-  int32_t* d_lp_top_ids = nullptr;
-  float* d_lp_top_lp = nullptr;
+  KhDev<int32_t> d_lp_top_n;
+  KhDev<int32_t> d_lp_token;
+  KhDev<float> d_lp_lp;
+  KhDev<int32_t> d_lp_top_ids;
+  KhDev<float> d_lp_top_lp;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // Screened classifier of the greedy generate loop (kh_cls_screen.h, kh_model_screen.hip): fp32 models only
   struct ClsScreen {
     bool on = false;        // the bf16 copy exists and the creation-time check passed (or was skipped)
     int selftest = 0;       // 0 not applicable / skipped, 1 passed, -1 failed -> screening off
-    uint16_t* wbf = nullptr;   // [vocab, dim] bf16 copy of the classifier
-    float* err = nullptr;      // [vocab] per-row error norm
-    float* x_save = nullptr;   // [dim] input of the last screened step
-    float *p_lb = nullptr, *p_spill = nullptr, *p_ub = nullptr;  // partials of k_cls_screen
-    int32_t* p_idx = nullptr;
-    float* ov_val = nullptr;   // argmax partials of an overflow step [sgrid]
-    int32_t* ov_idx = nullptr;
-    uint32_t* ticket = nullptr;
-    int32_t* stats = nullptr;  // steps, candidate rows, overflow steps
+    KhDev<uint16_t> wbf;       // [vocab, dim] bf16 copy of the classifier
+    KhDev<float> err;          // [vocab] per-row error norm
+    KhDev<float> x_save;       // [dim] input of the last screened step
+    KhDev<float> p_lb, p_spill, p_ub;  // partials of k_cls_screen
+    KhDev<int32_t> p_idx;
+    KhDev<float> ov_val;       // argmax partials of an overflow step [sgrid]
+    KhDev<int32_t> ov_idx;
+    KhDev<uint32_t> ticket;
+    KhDev<int32_t> stats;      // steps, candidate rows, overflow steps
     int u = 4, grid = 1, wg = KH_WG, sgrid = 1;  // launch of k_cls_screen; workgroups of k_sample_screen
     size_t bytes = 0;          // HBM the copy and its tables take
     float build_ms = 0.f;      // time of the conversion kernel
@@ -252,12 +277,12 @@ struct kh_model {
     struct Q8 {
       bool on = false;         // the int8 copy exists and its creation-time check passed (or was skipped)
       int selftest = 0;        // 0 not applicable / skipped, 1 passed, -1 failed -> tier off, the bf16 screen goes on
-      int8_t* q = nullptr;     // [vocab, dim]
-      float* sc = nullptr;     // [vocab, dim / 64]
-      float* e8 = nullptr;     // [vocab]
-      float *p_lb = nullptr, *p_spill = nullptr, *p_ub = nullptr;  // partials of k_cls_screen_q8
-      int32_t* p_idx = nullptr;
-      int32_t* stats = nullptr;  // tier-1 steps, rows that survived it, steps in which it spilled
+      KhDev<int8_t> q;         // [vocab, dim]
+      KhDev<float> sc;         // [vocab, dim / 64]
+      KhDev<float> e8;         // [vocab]
+      KhDev<float> p_lb, p_spill, p_ub;  // partials of k_cls_screen_q8
+      KhDev<int32_t> p_idx;
+      KhDev<int32_t> stats;    // tier-1 steps, rows that survived it, steps in which it spilled
       int u = 2, grid = 1, wg = KH_WG;  // launch of k_cls_screen_q8
       size_t bytes = 0;
       float build_ms = 0.f;
@@ -269,7 +294,7 @@ struct kh_model {
   // word of a bf16-exact fp32 model, read by the batch-1 decode GEMVs of the adopted launch classes
   struct W16 {
     int state = 0;          // 0 off or not applicable, 1 on, -1 some matrix is not bf16-exact, -2 the self-check failed
-    void* alloc = nullptr;  // what hipMalloc returned; arena = its first 4-KiB boundary
+    KhDev<char> alloc;      // the allocation; arena = its first 4-KiB boundary
     char* arena = nullptr;
     size_t bytes = 0;       // of the copy (every matrix padded to 256 bytes)
     float build_us = 0.f;   // k_w16_build over all matrices
@@ -293,11 +318,6 @@ inline bool tokens_in_vocab(const kh_model* m, const int32_t* toks, size_t n) {
   for (size_t i = 0; i < n; ++i)
     if (toks[i] < 0 || toks[i] >= m->cfg.vocab_size) return false;
   return true;
-}
-template <typename T>
-int dalloc(T** p, size_t n) {
-  hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-  return e == hipSuccess ? KH_OK : (int)e;
 }
 
 // ---- kh_model_step.hip ----------------------------------------------------------------------
@@ -395,6 +415,7 @@ int lp_fill_none(kh_model* m, int pos0, int n);
 // records [pos0, pos0 + n) to the host with top lists of width w (kh_model_get_logprobs); synchronises
 int lp_read(kh_model* m, int pos0, int n, int w, int32_t* h_token, float* h_lp, int32_t* h_top_ids, float* h_top_lp);
 int ensure_pinned_words(kh_model* m, int n);
+int ensure_chunk_events(kh_model* m);  // ev_chunk, made by whoever needs them first
 int ensure_seq_cap(kh_model* m, int n);
 void destroy_step_graphs(kh_model* m);
 // the captured graph of `nsteps` in {1, 2, 4, 8} decode steps in `variant` ending in `tail`, captured on first use
@@ -405,7 +426,7 @@ int step_graph(kh_model* m, int n_forced, int variant, int nsteps, StepTail tail
 int enqueue_steps(kh_model* m, int pos, int nsteps, int n_forced, StepTail tail, int exec);
 // ---- kh_model_screen.hip --------------------------------------------------------------------
 int cls_screen_create(kh_model* m);   // bf16 copy + tables, once the weights are resident (no-op where it does not apply)
-void cls_screen_release(kh_model* m);
+void cls_screen_release(kh_model* m);  // frees the copies and tables; screening is off afterwards
 bool cls_screen_wanted(const kh_model* m);  // may this generate screen? (sampler, hooks)
 int cls_screen_level(const kh_model* m);    // 0 no screen, 1 the bf16 screen, 2 behind the int8 tier (hooks)
 // dbg_lb / dbg_ub [vocab] (optional): receive every row's interval.  survivors: re-screen what the k_cls_screen_q8

@@ -80,12 +80,12 @@ hipError_t upload_chunked(char* d_dst, const char* h_src, size_t n, hipStream_t 
       *ms_out = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return e;
   }
-  char* pin[NB] = {nullptr, nullptr, nullptr, nullptr};
+  KhPin<char> pin[NB];
   hipEvent_t done[NB] = {nullptr, nullptr, nullptr, nullptr};
   hipError_t e = hipSuccess;
   PhaseClock pc;
   for (int i = 0; i < NB && e == hipSuccess; ++i) {
-    e = hipHostMalloc((void**)&pin[i], CH, hipHostMallocDefault);
+    e = (hipError_t)pin[i].alloc(CH);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
   }
   pc.lap("pinned staging ring");
@@ -136,10 +136,9 @@ hipError_t upload_chunked(char* d_dst, const char* h_src, size_t n, hipStream_t 
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     pc.lap("staged upload");
   }
-  for (int i = 0; i < NB; ++i) {
-    if (done[i]) (void)hipEventDestroy(done[i]);
-    if (pin[i]) (void)hipHostFree(pin[i]);
-  }
+  for (hipEvent_t ev : done)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& p : pin) p.reset();  // here, not at the closing brace: the time below covers the ring's release
   if (ms_out)
     *ms_out = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return e;
@@ -403,15 +402,20 @@ static int kv_allocate(kh_model* m) {
     }
     (void)hipGetLastError();  // no virtual-memory API on this runtime / device: plain allocation
   }
+  KhDev<float> k, v;  // the plain allocation: both halves or none
   int rc;
-  if ((rc = dalloc(&m->kcache, total / sizeof(float))) != KH_OK) return rc;
-  return dalloc(&m->vcache, total / sizeof(float));
+  if ((rc = k.alloc(total / sizeof(float))) != KH_OK || (rc = v.alloc(total / sizeof(float))) != KH_OK) return rc;
+  m->kv_plain[0] = std::move(k);
+  m->kv_plain[1] = std::move(v);
+  m->kcache = m->kv_plain[0];
+  m->vcache = m->kv_plain[1];
+  return KH_OK;
 }
 static void kv_release(kh_model* m) {
   kh_model::KvVmm& kv = m->kv;
   if (!kv.on) {
-    if (m->kcache) (void)hipFree(m->kcache);
-    if (m->vcache) (void)hipFree(m->vcache);
+    m->kv_plain[0].reset();
+    m->kv_plain[1].reset();
   } else {
     for (const auto& r : kv.runs) {
       (void)hipMemUnmap(r.va, r.len);
@@ -502,24 +506,23 @@ int finish_create(kh_model* m, SinCosJob* sincos = nullptr) {
   if ((rc = build_weight_table(m)) != KH_OK) return rc;
   m->gshift = c.is_quant ? ilog2_exact(c.group_size) : 0;
   const size_t CL = (size_t)c.cache_len;
-#define KH_ALLOC(ptr, n) \
-  if ((rc = dalloc(&(ptr), (n))) != KH_OK) return rc
-  KH_ALLOC(m->x, (size_t)c.dim);
-  KH_ALLOC(m->rms, (size_t)c.dim);
-  KH_ALLOC(m->q, (size_t)c.dim);
-  KH_ALLOC(m->att, (size_t)c.dim);
-  KH_ALLOC(m->w2o, (size_t)c.dim);
-  KH_ALLOC(m->h1, (size_t)c.hidden_dim);
-  KH_ALLOC(m->h3, (size_t)c.hidden_dim);
-  KH_ALLOC(m->logits, (size_t)c.vocab_size);
-  KH_ALLOC(m->score, (size_t)c.head_num * CL);
+  // (a creation that fails on the way is destroyed by its caller: whatever exists by then frees itself)
+  if ((rc = m->x.alloc((size_t)c.dim)) != KH_OK) return rc;
+  if ((rc = m->rms.alloc((size_t)c.dim)) != KH_OK) return rc;
+  if ((rc = m->q.alloc((size_t)c.dim)) != KH_OK) return rc;
+  if ((rc = m->att.alloc((size_t)c.dim)) != KH_OK) return rc;
+  if ((rc = m->w2o.alloc((size_t)c.dim)) != KH_OK) return rc;
+  if ((rc = m->h1.alloc((size_t)c.hidden_dim)) != KH_OK) return rc;
+  if ((rc = m->h3.alloc((size_t)c.hidden_dim)) != KH_OK) return rc;
+  if ((rc = m->logits.alloc((size_t)c.vocab_size)) != KH_OK) return rc;
+  if ((rc = m->score.alloc((size_t)c.head_num * CL)) != KH_OK) return rc;
   pc.lap("weight table + small buffers");
   if ((rc = kv_allocate(m)) != KH_OK) return rc;
-  KH_ALLOC(m->sin_cache, CL * c.head_size);
-  KH_ALLOC(m->cos_cache, CL * c.head_size);
-  KH_ALLOC(m->d_pos, 1);
-  KH_ALLOC(m->d_token, 1);
-  KH_ALLOC(m->d_next, 1);
+  if ((rc = m->sin_cache.alloc(CL * c.head_size)) != KH_OK) return rc;
+  if ((rc = m->cos_cache.alloc(CL * c.head_size)) != KH_OK) return rc;
+  if ((rc = m->d_pos.alloc(1)) != KH_OK) return rc;
+  if ((rc = m->d_token.alloc(1)) != KH_OK) return rc;
+  if ((rc = m->d_next.alloc(1)) != KH_OK) return rc;
   // launch geometry
   {
     kh_model::Shape sh[5];
@@ -565,12 +568,11 @@ int finish_create(kh_model* m, SinCosJob* sincos = nullptr) {
     if (const char* e = dbg("KH_ATTN_DEFER_MAX")) m->attn_defer_max = atoi(e);
   }
   if (const size_t wsb = attn_ws_bytes(c.head_num, c.head_size, m->attn_ws_stride)) {
-    KH_CHECK_HIP(hipMalloc(&m->attn_ws, wsb));
+    if ((rc = m->attn_ws.alloc(wsb)) != KH_OK) return rc;
     KH_CHECK_HIP(hipMemsetAsync(m->attn_ws, 0, wsb, m->stream));
   }
-  KH_ALLOC(m->part_val, (size_t)m->nparts);
-  KH_ALLOC(m->part_idx, (size_t)m->nparts);
-#undef KH_ALLOC
+  if ((rc = m->part_val.alloc((size_t)m->nparts)) != KH_OK) return rc;
+  if ((rc = m->part_idx.alloc((size_t)m->nparts)) != KH_OK) return rc;
   pc.lap("caches, tables, plans, workspace");
   if (!m->kv.on) {  // a mapped-on-demand cache zeroes what it maps (kv_ensure)
     KH_CHECK_HIP(hipMemsetAsync(m->kcache, 0, sizeof(float) * c.layer_num * CL * c.kv_dim, m->stream));
@@ -580,7 +582,7 @@ int finish_create(kh_model* m, SinCosJob* sincos = nullptr) {
   KH_CHECK_HIP(hipMemsetAsync(m->d_token, 0, sizeof(int32_t), m->stream));
   // the token fed at every position (kh_logit_proc.h): -1 = none yet
   m->hist_cap = (int)CL + 1;
-  if ((rc = dalloc(&m->d_hist, (size_t)m->hist_cap)) != KH_OK) return rc;
+  if ((rc = m->d_hist.alloc((size_t)m->hist_cap)) != KH_OK) return rc;
   KH_CHECK_HIP(hipMemsetAsync(m->d_hist, 0xFF, sizeof(int32_t) * (size_t)m->hist_cap, m->stream));
   // sin/cos table: computed on the host with libm exactly as the CPU backend does
   // (cpu/rope_kernel.cpp:4-16) so the fp32 table is bit-identical to the CPU reference's,
@@ -649,42 +651,12 @@ extern "C" void kh_model_destroy(kh_model* m) {
   destroy_step_graphs(m);
   if (m->ev0) (void)hipEventDestroy(m->ev0);
   if (m->ev1) (void)hipEventDestroy(m->ev1);
-  for (void* q : {(void*)m->pf_x, (void*)m->pf_q, (void*)m->pf_att, (void*)m->pf_h, m->pf_ws, (void*)m->pf_logits,
-                  (void*)m->pg_x, (void*)m->pg_xn, (void*)m->pg_q, (void*)m->pg_att, (void*)m->pg_h, (void*)m->pg_part,
-                  m->pg_ws})
-    if (q) (void)hipFree(q);
   for (auto e : m->ev_chunk)
     if (e) (void)hipEventDestroy(e);
-  if (m->h_words_pin) (void)hipHostFree(m->h_words_pin);
-  if (m->h_forced_pin) (void)hipHostFree(m->h_forced_pin);
-  if (m->first_logits) (void)hipFree(m->first_logits);
-  if (m->d_spec) (void)hipFree(m->d_spec);
-  if (m->h_spec_pin) (void)hipHostFree(m->h_spec_pin);
-  for (void* q : {(void*)m->d_seq_tok, (void*)m->d_seq_samp, (void*)m->d_seq_words})
-    if (q) (void)hipFree(q);
-  for (void* q : {(void*)m->h_seq_tok_pin, (void*)m->h_seq_samp_pin, (void*)m->h_seq_words_pin})
-    if (q) (void)hipHostFree(q);
-  for (void* q : {(void*)m->d_seq_proc, (void*)m->d_seq_bias_ids, (void*)m->d_seq_bias, (void*)m->d_seq_cnt})
-    if (q) (void)hipFree(q);
-  for (void* q : {(void*)m->h_seq_proc_pin, (void*)m->h_seq_bias_ids_pin, (void*)m->h_seq_bias_pin, (void*)m->h_seq_hist_pin})
-    if (q) (void)hipHostFree(q);
-  if (m->d_samp) (void)hipFree(m->d_samp);
-  for (void* q : {(void*)m->d_hist, (void*)m->d_proc, (void*)m->d_bias_ids, (void*)m->d_bias, (void*)m->d_cnt})
-    if (q) (void)hipFree(q);
-  for (void* q : {(void*)m->d_lp_top_n, (void*)m->d_lp_token, (void*)m->d_lp_lp, (void*)m->d_lp_top_ids, (void*)m->d_lp_top_lp})
-    if (q) (void)hipFree(q);
-  cls_screen_release(m);
-  w16_release(m);
-  void* bufs[] = {m->x,      m->rms,    m->q,         m->att,       m->h1,       m->h3,
-                  m->w2o,    m->logits, m->score,     m->sin_cache,
-                  m->cos_cache, m->part_val, m->part_idx, m->d_pos, m->d_token,  m->d_next,
-                  m->d_forced, m->d_words, m->attn_ws};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  kv_release(m);
-  if (m->owns_arena && m->arena) (void)hipFree(m->arena);
+  kv_release(m);  // mapped chunks and reserved ranges are not KhBufs
+  if (m->owns_arena && m->arena) (void)hipFree(m->arena);  // nor is the arena: it may be the caller's
   if (m->stream) (void)hipStreamDestroy(m->stream);
-  delete m;
+  delete m;  // every buffer of the model frees itself here
 }
 
 static int create_from_device_weights_impl(const int32_t* h_header, const void* d_weight_data, size_t weight_nbytes,
@@ -750,7 +722,7 @@ static int create_from_host_image_impl(const void* h_image, size_t nbytes, const
   SinCosJob sincos;  // the RoPE table is computed on host threads while the weights travel
   sincos.start((size_t)m->cfg.cache_len, m->cfg.head_size, m->cfg.rope_theta);
   PhaseClock pc;
-  hipError_t e = hipMalloc((void**)&m->arena, need);
+  hipError_t e = hipMalloc((void**)&m->arena, need);  // raw like the borrowed arena: owns_arena says who frees it
   pc.lap("arena hipMalloc");
   if (e != hipSuccess) {
     sincos.join();

@@ -58,25 +58,25 @@ int prefill_batch(const kh_model* m) {
   return 4;
 }
 int ensure_prefill_buffers(kh_model* m) {
-  if (m->pf_ready) return KH_OK;
-  for (float** p : {&m->pf_x, &m->pf_q, &m->pf_att, &m->pf_h}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (m->pf_ws) (void)hipFree(m->pf_ws);
-  m->pf_ws = nullptr;
+  if (m->pf_x) return KH_OK;
   const kh_config& c = m->cfg;
+  KhDev<float> x, q, att, h;
+  KhDev<char> ws;
   int rc;
-  if ((rc = dalloc(&m->pf_x, (size_t)KH_PF_BMAX * c.dim)) != KH_OK) return rc;
-  if ((rc = dalloc(&m->pf_q, (size_t)KH_PF_BMAX * c.dim)) != KH_OK) return rc;
-  if ((rc = dalloc(&m->pf_att, (size_t)KH_PF_BMAX * c.dim)) != KH_OK) return rc;
-  if ((rc = dalloc(&m->pf_h, (size_t)KH_PF_BMAX * c.hidden_dim)) != KH_OK) return rc;
-  m->pf_ws_tok_bytes = (attn_ws_bytes(c.head_num, c.head_size, m->attn_ws_stride) + 255) & ~(size_t)255;
-  if (m->pf_ws_tok_bytes) {
-    KH_CHECK_HIP(hipMalloc(&m->pf_ws, m->pf_ws_tok_bytes * KH_PF_BMAX));
-    KH_CHECK_HIP(hipMemsetAsync(m->pf_ws, 0, m->pf_ws_tok_bytes * KH_PF_BMAX, m->stream));
+  if ((rc = x.alloc((size_t)KH_PF_BMAX * c.dim)) != KH_OK || (rc = q.alloc((size_t)KH_PF_BMAX * c.dim)) != KH_OK ||
+      (rc = att.alloc((size_t)KH_PF_BMAX * c.dim)) != KH_OK || (rc = h.alloc((size_t)KH_PF_BMAX * c.hidden_dim)) != KH_OK)
+    return rc;
+  const size_t tok_bytes = (attn_ws_bytes(c.head_num, c.head_size, m->attn_ws_stride) + 255) & ~(size_t)255;
+  if (tok_bytes) {
+    if ((rc = ws.alloc(tok_bytes * KH_PF_BMAX)) != KH_OK) return rc;
+    KH_CHECK_HIP(hipMemsetAsync(ws, 0, tok_bytes * KH_PF_BMAX, m->stream));
   }
-  m->pf_ready = true;
+  m->pf_ws_tok_bytes = tok_bytes;
+  m->pf_x = std::move(x);
+  m->pf_q = std::move(q);
+  m->pf_att = std::move(att);
+  m->pf_h = std::move(h);
+  m->pf_ws = std::move(ws);
   return KH_OK;
 }
 // The B-token kernels are register- and LDS-heavy: a grid larger than what is resident at once
@@ -298,7 +298,7 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
 int ensure_score_buffers(kh_model* m) {
   if (m->pf_logits) return KH_OK;
   m->pf_vstride = (m->cfg.vocab_size + 3) & ~3;
-  return dalloc(&m->pf_logits, (size_t)KH_PF_BMAX * m->pf_vstride);
+  return m->pf_logits.alloc((size_t)KH_PF_BMAX * m->pf_vstride);
 }
 // logits of the chunk's tokens behind a full-depth pass (k_cls's arithmetic on pf_x, the decode classifier's workgroup
 // width): rows 0 .. nvalid - 1 of pf_logits
@@ -344,31 +344,29 @@ void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0,
 // ---- GEMM prefill (kh_gemm.h) ------------------------------------------------------------------
 namespace {
 int ensure_pg_buffers(kh_model* m) {
-  if (m->pg_ready) return KH_OK;
-  // a previous attempt may have failed half-way (out of memory): start from a clean slate so a
-  // later call never launches GEMMs on null slabs
-  for (float** p : {&m->pg_x, &m->pg_xn, &m->pg_q, &m->pg_att, &m->pg_h, &m->pg_part}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (m->pg_ws) (void)hipFree(m->pg_ws);
-  m->pg_ws = nullptr;
+  if (m->pg_x) return KH_OK;
   const kh_config& c = m->cfg;
   const size_t T = KH_PG_TMAX;
   int rc;
-  auto zalloc = [&](float** p, size_t n) -> int {
-    if ((rc = dalloc(p, n)) != KH_OK) return rc;
+  auto zalloc = [&](KhDev<float>& b, size_t n) -> int {
+    if ((rc = b.alloc(n)) != KH_OK) return rc;
     // rows beyond the valid tokens are read as MFMA operands (their columns are discarded):
     // they must hold finite numbers
-    return (int)hipMemsetAsync(*p, 0, n * sizeof(float), m->stream);
+    return (int)hipMemsetAsync(b, 0, n * sizeof(float), m->stream);
   };
-  if ((rc = zalloc(&m->pg_x, T * c.dim)) != KH_OK) return rc;
-  if ((rc = zalloc(&m->pg_xn, T * c.dim)) != KH_OK) return rc;
-  if ((rc = zalloc(&m->pg_q, T * c.dim)) != KH_OK) return rc;
-  if ((rc = zalloc(&m->pg_att, T * c.dim)) != KH_OK) return rc;
-  if ((rc = zalloc(&m->pg_h, T * c.hidden_dim)) != KH_OK) return rc;
-  if ((rc = zalloc(&m->pg_part, (size_t)KH_PG_KZ_MAX * T * c.dim)) != KH_OK) return rc;  // K-slice partial rows
-  m->pg_ready = true;
+  // a failure half-way leaves the model without any slab: a later call starts over
+  KhDev<float> x, xn, q, att, h, part;
+  if ((rc = zalloc(x, T * c.dim)) != KH_OK || (rc = zalloc(xn, T * c.dim)) != KH_OK ||
+      (rc = zalloc(q, T * c.dim)) != KH_OK || (rc = zalloc(att, T * c.dim)) != KH_OK ||
+      (rc = zalloc(h, T * c.hidden_dim)) != KH_OK ||
+      (rc = zalloc(part, (size_t)KH_PG_KZ_MAX * T * c.dim)) != KH_OK)  // K-slice partial rows
+    return rc;
+  m->pg_x = std::move(x);
+  m->pg_xn = std::move(xn);
+  m->pg_q = std::move(q);
+  m->pg_att = std::move(att);
+  m->pg_h = std::move(h);
+  m->pg_part = std::move(part);
   return KH_OK;
 }
 // does the prompt-slice attention run on the MFMA kernel (kh_pattn.h)?  KH_PG_ATTN=0 forces the fallback.
@@ -380,8 +378,11 @@ int ensure_pg_ws(kh_model* m) {
   if (m->pg_ws || pg_mfma_attn(m)) return KH_OK;
   m->pg_ws_tok_bytes = (attn_ws_bytes(m->cfg.head_num, m->cfg.head_size, m->attn_ws_stride) + 255) & ~(size_t)255;
   if (!m->pg_ws_tok_bytes) return KH_OK;
-  KH_CHECK_HIP(hipMalloc(&m->pg_ws, m->pg_ws_tok_bytes * (size_t)KH_PG_TMAX));
-  KH_CHECK_HIP(hipMemsetAsync(m->pg_ws, 0, m->pg_ws_tok_bytes * (size_t)KH_PG_TMAX, m->stream));
+  KhDev<char> ws;
+  int rc;
+  if ((rc = ws.alloc(m->pg_ws_tok_bytes * (size_t)KH_PG_TMAX)) != KH_OK) return rc;
+  KH_CHECK_HIP(hipMemsetAsync(ws, 0, m->pg_ws_tok_bytes * (size_t)KH_PG_TMAX, m->stream));
+  m->pg_ws = std::move(ws);
   return KH_OK;
 }
 // the (R, NT) register tiles k_pg_gemm is compiled for, and the waves per SIMD that fit with each
@@ -764,9 +765,12 @@ int khm::verify_prepare(kh_model* m, int rows) {
   if ((rc = kv_ensure(m, rows)) != KH_OK) return rc;
   if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
   if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
-  if (!m->d_spec && (rc = dalloc(&m->d_spec, (size_t)1 + KH_PF_BMAX)) != KH_OK) return rc;
-  if (!m->h_spec_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_spec_pin, sizeof(int32_t) * (1 + KH_PF_BMAX), hipHostMallocDefault));
+  if (m->d_spec) return KH_OK;
+  KhDev<int32_t> spec;
+  KhPin<int32_t> pin;
+  if ((rc = spec.alloc((size_t)1 + KH_PF_BMAX)) != KH_OK || (rc = pin.alloc((size_t)1 + KH_PF_BMAX)) != KH_OK) return rc;
+  m->d_spec = std::move(spec);
+  m->h_spec_pin = std::move(pin);
   return KH_OK;
 }
 int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0) {
@@ -805,44 +809,50 @@ int khm::seq_prepare(kh_model* m) {
   int rc;
   if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
   if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
-  const size_t rows = (size_t)m->cfg.cache_len;
-  if (!m->d_seq_tok && (rc = dalloc(&m->d_seq_tok, (size_t)KH_SEQ_SLOTS_MAX)) != KH_OK) return rc;
-  if (!m->d_seq_samp && (rc = dalloc(&m->d_seq_samp, (size_t)KH_SEQ_SLOTS_MAX)) != KH_OK) return rc;
-  if (!m->d_seq_words && (rc = dalloc(&m->d_seq_words, rows)) != KH_OK) return rc;
-  if (!m->h_seq_tok_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_tok_pin, sizeof(int32_t) * KH_SEQ_SLOTS_MAX, hipHostMallocDefault));
-  if (!m->h_seq_samp_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_samp_pin, sizeof(KhSampParams) * KH_SEQ_SLOTS_MAX, hipHostMallocDefault));
-  if (!m->h_seq_words_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_words_pin, sizeof(int32_t) * rows, hipHostMallocDefault));
-  for (auto& e : m->ev_chunk)  // the stop check's events (ensure_pinned_words makes them for the batch-1 loops)
-    if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return (int)hipErrorUnknown;
+  if ((rc = ensure_chunk_events(m)) != KH_OK) return rc;  // the stop check's events
+  if (m->d_seq_tok) return KH_OK;
+  const size_t rows = (size_t)m->cfg.cache_len, slots = KH_SEQ_SLOTS_MAX;
+  KhDev<int32_t> tok, words;
+  KhDev<KhSampParams> samp;
+  KhPin<int32_t> tok_pin, words_pin;
+  KhPin<KhSampParams> samp_pin;
+  if ((rc = tok.alloc(slots)) != KH_OK || (rc = samp.alloc(slots)) != KH_OK || (rc = words.alloc(rows)) != KH_OK ||
+      (rc = tok_pin.alloc(slots)) != KH_OK || (rc = samp_pin.alloc(slots)) != KH_OK ||
+      (rc = words_pin.alloc(rows)) != KH_OK)
+    return rc;
+  m->d_seq_tok = std::move(tok);
+  m->d_seq_samp = std::move(samp);
+  m->d_seq_words = std::move(words);
+  m->h_seq_tok_pin = std::move(tok_pin);
+  m->h_seq_samp_pin = std::move(samp_pin);
+  m->h_seq_words_pin = std::move(words_pin);
   return KH_OK;
 }
 int khm::seq_prepare_ex(kh_model* m, bool records) {
   int rc;
-  const size_t slots = KH_SEQ_SLOTS_MAX, nb = (size_t)KH_SEQ_SLOTS_MAX * KH_SEQ_BIAS_MAX;
-  if (!m->d_seq_proc && (rc = dalloc(&m->d_seq_proc, slots)) != KH_OK) return rc;
-  if (!m->d_seq_bias_ids && (rc = dalloc(&m->d_seq_bias_ids, nb)) != KH_OK) return rc;
-  if (!m->d_seq_bias && (rc = dalloc(&m->d_seq_bias, nb)) != KH_OK) return rc;
-  if (!m->d_seq_cnt) {
+  if (!m->d_seq_proc) {
+    const size_t slots = KH_SEQ_SLOTS_MAX, nb = (size_t)KH_SEQ_SLOTS_MAX * KH_SEQ_BIAS_MAX;
     const size_t n = (size_t)KH_PF_BMAX * (size_t)m->cfg.vocab_size;
-    int32_t* cnt = nullptr;
-    if ((rc = dalloc(&cnt, n)) != KH_OK) return rc;
-    if (hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, m->stream) != hipSuccess) {  // once: the core re-arms them
-      (void)hipFree(cnt);
-      return (int)hipErrorUnknown;
-    }
-    m->d_seq_cnt = cnt;
+    KhDev<KhProcParams> proc;
+    KhDev<int32_t> bias_ids, cnt;
+    KhDev<float> bias;
+    KhPin<KhProcParams> proc_pin;
+    KhPin<int32_t> bias_ids_pin, hist_pin;
+    KhPin<float> bias_pin;
+    if ((rc = proc.alloc(slots)) != KH_OK || (rc = bias_ids.alloc(nb)) != KH_OK || (rc = bias.alloc(nb)) != KH_OK ||
+        (rc = cnt.alloc(n)) != KH_OK || (rc = proc_pin.alloc(slots)) != KH_OK || (rc = bias_ids_pin.alloc(nb)) != KH_OK ||
+        (rc = bias_pin.alloc(nb)) != KH_OK || (rc = hist_pin.alloc((size_t)m->cfg.cache_len)) != KH_OK)
+      return rc;
+    KH_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, m->stream));  // once: the core re-arms them
+    m->d_seq_proc = std::move(proc);
+    m->d_seq_bias_ids = std::move(bias_ids);
+    m->d_seq_bias = std::move(bias);
+    m->d_seq_cnt = std::move(cnt);
+    m->h_seq_proc_pin = std::move(proc_pin);
+    m->h_seq_bias_ids_pin = std::move(bias_ids_pin);
+    m->h_seq_bias_pin = std::move(bias_pin);
+    m->h_seq_hist_pin = std::move(hist_pin);
   }
-  if (!m->h_seq_proc_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_proc_pin, sizeof(KhProcParams) * slots, hipHostMallocDefault));
-  if (!m->h_seq_bias_ids_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_bias_ids_pin, sizeof(int32_t) * nb, hipHostMallocDefault));
-  if (!m->h_seq_bias_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_bias_pin, sizeof(float) * nb, hipHostMallocDefault));
-  if (!m->h_seq_hist_pin)
-    KH_CHECK_HIP(hipHostMalloc((void**)&m->h_seq_hist_pin, sizeof(int32_t) * (size_t)m->cfg.cache_len, hipHostMallocDefault));
   return records ? lp_ensure_records(m) : KH_OK;
 }
 int khm::seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0, int pfx_len, int pfx_row0) {

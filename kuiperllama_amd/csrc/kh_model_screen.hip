@@ -115,13 +115,7 @@ int cls_screen_level(const kh_model* m) {
   return m->scr.q8.on && !q8_hooks_bar() ? 2 : 1;
 }
 
-static void cls_screen_q8_release(kh_model* m) {
-  kh_model::ClsScreen::Q8& t = m->scr.q8;
-  for (void* q : {(void*)t.q, (void*)t.sc, (void*)t.e8, (void*)t.p_lb, (void*)t.p_spill, (void*)t.p_ub, (void*)t.p_idx,
-                  (void*)t.stats})
-    if (q) (void)hipFree(q);
-  t = kh_model::ClsScreen::Q8();
-}
+static void cls_screen_q8_release(kh_model* m) { m->scr.q8 = kh_model::ClsScreen::Q8(); }
 
 // The int8 copy behind a bf16 screen that is on: fp32 model, dim a multiple of the group, no hook in the way.  Where
 // the copy cannot be had - no room for it - the tier is off and nothing else changes: KH_OK, the bf16 screen goes on.
@@ -134,9 +128,10 @@ static int cls_screen_q8_create(kh_model* m) {
   if (!ScreenMV::has(kh_stage_maxv(c.dim, t.wg))) return KH_OK;
   const size_t V = (size_t)c.vocab_size, gpr = (size_t)(c.dim / KH_SCR8_G);
   // partials: every grid a KH_SHAPE_SCREEN_Q8 hook may ask for
-  if (dalloc(&t.q, V * (size_t)c.dim) != KH_OK || dalloc(&t.sc, V * gpr) != KH_OK || dalloc(&t.e8, V) != KH_OK ||
-      dalloc(&t.p_lb, 4096) != KH_OK || dalloc(&t.p_spill, 4096) != KH_OK || dalloc(&t.p_ub, 4096 * KH_SCR8_C) != KH_OK ||
-      dalloc(&t.p_idx, 4096 * KH_SCR8_C) != KH_OK || dalloc(&t.stats, 4) != KH_OK) {
+  // (eight allocations: the ones whose failure a creation survives)
+  if (t.q.alloc(V * (size_t)c.dim) != KH_OK || t.sc.alloc(V * gpr) != KH_OK || t.e8.alloc(V) != KH_OK ||
+      t.p_lb.alloc(4096) != KH_OK || t.p_spill.alloc(4096) != KH_OK || t.p_ub.alloc(4096 * KH_SCR8_C) != KH_OK ||
+      t.p_idx.alloc(4096 * KH_SCR8_C) != KH_OK || t.stats.alloc(4) != KH_OK) {
     (void)hipGetLastError();  // the failed allocation is not the model's error
     cls_screen_q8_release(m);
     if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
@@ -151,8 +146,8 @@ static int cls_screen_q8_create(kh_model* m) {
   auto build = [&]() -> int {
     KH_CHECK_HIP(hipMemsetAsync(t.stats, 0, 4 * sizeof(int32_t), st));
     KH_CHECK_HIP(hipEventRecord(m->ev0, st));
-    hipLaunchKernelGGL(k_cls_q8_build, dim3(2048), dim3(KH_WG), 0, st, (const float*)m->cls.w, (uint32_t*)t.q, t.sc,
-                       t.e8, c.dim, c.vocab_size, gam2);
+    hipLaunchKernelGGL(k_cls_q8_build, dim3(2048), dim3(KH_WG), 0, st, (const float*)m->cls.w, (uint32_t*)t.q.get(),
+                       t.sc.get(), t.e8.get(), c.dim, c.vocab_size, gam2);
     KH_CHECK_HIP(hipEventRecord(m->ev1, st));
     KH_CHECK_HIP(hipEventSynchronize(m->ev1));
     const int rc = kh_launch_status();
@@ -174,14 +169,7 @@ static int cls_screen_q8_create(kh_model* m) {
   return KH_OK;
 }
 
-void cls_screen_release(kh_model* m) {
-  kh_model::ClsScreen& s = m->scr;
-  cls_screen_q8_release(m);
-  for (void* q : {(void*)s.wbf, (void*)s.err, (void*)s.x_save, (void*)s.p_lb, (void*)s.p_spill, (void*)s.p_ub,
-                  (void*)s.p_idx, (void*)s.ov_val, (void*)s.ov_idx, (void*)s.ticket, (void*)s.stats})
-    if (q) (void)hipFree(q);
-  s = kh_model::ClsScreen();
-}
+void cls_screen_release(kh_model* m) { m->scr = kh_model::ClsScreen(); }
 
 int cls_screen_create(kh_model* m) {
   const kh_config& c = m->cfg;
@@ -202,24 +190,16 @@ int cls_screen_create(kh_model* m) {
   }
   int rc;
   const size_t V = (size_t)c.vocab_size;
-#define KH_ALLOC(ptr, n)                         \
-  if ((rc = dalloc(&(ptr), (n))) != KH_OK) {     \
-    cls_screen_release(m);                       \
-    return rc;                                   \
+  // (partials: sized for every grid a KH_SHAPE_SCREEN hook may ask for)
+  if ((rc = s.wbf.alloc(V * (size_t)c.dim)) != KH_OK || (rc = s.err.alloc(V)) != KH_OK ||
+      (rc = s.x_save.alloc((size_t)c.dim)) != KH_OK || (rc = s.p_lb.alloc(4096)) != KH_OK ||
+      (rc = s.p_spill.alloc(4096)) != KH_OK || (rc = s.p_ub.alloc(4096 * KH_SCR_C)) != KH_OK ||
+      (rc = s.p_idx.alloc(4096 * KH_SCR_C)) != KH_OK || (rc = s.ov_val.alloc((size_t)s.sgrid)) != KH_OK ||
+      (rc = s.ov_idx.alloc((size_t)s.sgrid)) != KH_OK || (rc = s.ticket.alloc(1)) != KH_OK ||
+      (rc = s.stats.alloc(4)) != KH_OK) {
+    cls_screen_release(m);
+    return rc;
   }
-  KH_ALLOC(s.wbf, V * (size_t)c.dim);
-  KH_ALLOC(s.err, V);
-  KH_ALLOC(s.x_save, (size_t)c.dim);
-  // sized for every grid a KH_SHAPE_SCREEN hook may ask for
-  KH_ALLOC(s.p_lb, 4096);
-  KH_ALLOC(s.p_spill, 4096);
-  KH_ALLOC(s.p_ub, 4096 * KH_SCR_C);
-  KH_ALLOC(s.p_idx, 4096 * KH_SCR_C);
-  KH_ALLOC(s.ov_val, (size_t)s.sgrid);
-  KH_ALLOC(s.ov_idx, (size_t)s.sgrid);
-  KH_ALLOC(s.ticket, 1);
-  KH_ALLOC(s.stats, 4);
-#undef KH_ALLOC
   s.bytes = V * (size_t)c.dim * sizeof(uint16_t) + V * sizeof(float);
   hipStream_t st = m->stream;
   KH_CHECK_HIP(hipMemsetAsync(s.ticket, 0, sizeof(uint32_t), st));
@@ -229,8 +209,8 @@ int cls_screen_create(kh_model* m) {
   const double u = 1.0 / 16777216.0;
   const double gam2 = 2.0 * (n * u) / (1.0 - n * u);
   KH_CHECK_HIP(hipEventRecord(m->ev0, st));
-  hipLaunchKernelGGL(k_cls_bf16_build, dim3(2048), dim3(KH_WG), 0, st, (const float*)m->cls.w, (uint32_t*)s.wbf, s.err,
-                     c.dim, c.vocab_size, gam2);
+  hipLaunchKernelGGL(k_cls_bf16_build, dim3(2048), dim3(KH_WG), 0, st, (const float*)m->cls.w, (uint32_t*)s.wbf.get(),
+                     s.err.get(), c.dim, c.vocab_size, gam2);
   KH_CHECK_HIP(hipEventRecord(m->ev1, st));
   KH_CHECK_HIP(hipEventSynchronize(m->ev1));
   if ((rc = kh_launch_status()) != KH_OK) return rc;
@@ -355,22 +335,20 @@ template <class F>
 static int cls_screen_pairs(kh_model* m, int32_t* tok, F&& then) {
   hipStream_t st = m->stream;
   const size_t V = (size_t)m->cfg.vocab_size;
-  float *lb = nullptr, *ub = nullptr;
+  KhDev<float> lb, ub;
   int rc;
-  if ((rc = dalloc(&lb, V)) == KH_OK && (rc = dalloc(&ub, V)) == KH_OK) {
-    launch_cls_screen(m, lb, ub);
-    launch_sample(m, /*advance=*/0, /*n_forced=*/0, kScreen);
-    hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    launch_cls(m);
-    launch_sample(m, 0, 0, kGreedy);
-    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = then(lb, ub);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = (int)e;
-  }
-  if (lb) (void)hipFree(lb);
-  if (ub) (void)hipFree(ub);
-  return rc;
+  if ((rc = lb.alloc(V)) != KH_OK || (rc = ub.alloc(V)) != KH_OK) return rc;
+  launch_cls_screen(m, lb, ub);
+  launch_sample(m, /*advance=*/0, /*n_forced=*/0, kScreen);
+  hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  launch_cls(m);
+  launch_sample(m, 0, 0, kGreedy);
+  if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = then(lb.get(), ub.get());
+  // whatever was enqueued reads lb / ub: the stream drains before they go, on the failure paths too
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  return e == hipSuccess ? KH_OK : (int)e;
 }
 
 // One screened step against one full step on a fixed vector (the embedding row of token 1): the same token, every
@@ -413,23 +391,21 @@ template <class F>
 static int cls_screen_q8_pairs(kh_model* m, int grid1, int32_t* tok, F&& then) {
   hipStream_t st = m->stream;
   const size_t V = (size_t)m->cfg.vocab_size;
-  float *lb = nullptr, *ub = nullptr;
+  KhDev<float> lb, ub;
   int rc;
-  if ((rc = dalloc(&lb, V)) == KH_OK && (rc = dalloc(&ub, V)) == KH_OK) {
-    launch_cls_screen_q8(m, lb, ub, grid1);
-    launch_cls_screen_behind(m, nullptr, nullptr, grid1 > 0 ? grid1 : m->scr.q8.grid);
-    launch_sample(m, /*advance=*/0, /*n_forced=*/0, kScreen);
-    hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    launch_cls(m);
-    launch_sample(m, 0, 0, kGreedy);
-    if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = then(lb, ub);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = (int)e;
-  }
-  if (lb) (void)hipFree(lb);
-  if (ub) (void)hipFree(ub);
-  return rc;
+  if ((rc = lb.alloc(V)) != KH_OK || (rc = ub.alloc(V)) != KH_OK) return rc;
+  launch_cls_screen_q8(m, lb, ub, grid1);
+  launch_cls_screen_behind(m, nullptr, nullptr, grid1 > 0 ? grid1 : m->scr.q8.grid);
+  launch_sample(m, /*advance=*/0, /*n_forced=*/0, kScreen);
+  hipError_t e = hipMemcpyAsync(&tok[0], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  launch_cls(m);
+  launch_sample(m, 0, 0, kGreedy);
+  if (e == hipSuccess) e = hipMemcpyAsync(&tok[1], m->d_next, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = then(lb.get(), ub.get());
+  // whatever was enqueued reads lb / ub: the stream drains before they go, on the failure paths too
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  return e == hipSuccess ? KH_OK : (int)e;
 }
 
 // The tier's creation-time check: the embedding row of token 1 through the three-launch tail and through a full step.

@@ -83,44 +83,40 @@ static int ring_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
     launch_ffn13(m, 0, /*ring=*/true);  // -> h1
     KH_CHECK_HIP(hipMemcpyAsync(m->h3, m->h1, sizeof(float) * (size_t)c.hidden_dim, hipMemcpyDeviceToDevice, s));
     launch_ffn13(m, 0, /*ring=*/false);  // register tiles -> h1
-    hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.hidden_dim)), dim3(KH_WG), 0, s, (const uint32_t*)m->h1,
-                       (const uint32_t*)m->h3, (size_t)c.hidden_dim, d_flag);
+    hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.hidden_dim)), dim3(KH_WG), 0, s, (const uint32_t*)m->h1.get(),
+                       (const uint32_t*)m->h3.get(), (size_t)c.hidden_dim, d_flag);
   }
-  float* tmp_logits = nullptr;
-  float* tmp_pv = nullptr;
-  int32_t* tmp_pi = nullptr;
+  // scratch of the register-tile classifier; whatever is enqueued on it has run when a return below frees it (the
+  // returns behind a launch follow a stream sync, and a device free waits for the device)
+  KhDev<float> tmp_logits, tmp_pv;
+  KhDev<int32_t> tmp_pi;
   if (plan.cls_r) {
     const size_t np = (size_t)(m->sh_cls.grid > plan.cls_grid ? m->sh_cls.grid : plan.cls_grid);
-    if ((rc = dalloc(&tmp_logits, (size_t)c.vocab_size)) == KH_OK && (rc = dalloc(&tmp_pv, np)) == KH_OK &&
-        (rc = dalloc(&tmp_pi, np)) == KH_OK) {
-      launch_cls(m);  // ring -> logits
-      launch_cls(m, {m->x, tmp_logits, tmp_pv, tmp_pi}, /*ring=*/false);  // register tiles -> tmp
-      hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.vocab_size)), dim3(KH_WG), 0, s, (const uint32_t*)m->logits,
-                         (const uint32_t*)tmp_logits, (size_t)c.vocab_size, d_flag);
-    }
+    if ((rc = tmp_logits.alloc((size_t)c.vocab_size)) != KH_OK || (rc = tmp_pv.alloc(np)) != KH_OK ||
+        (rc = tmp_pi.alloc(np)) != KH_OK)
+      return rc;
+    launch_cls(m);  // ring -> logits
+    launch_cls(m, {m->x, tmp_logits, tmp_pv, tmp_pi}, /*ring=*/false);  // register tiles -> tmp
+    hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.vocab_size)), dim3(KH_WG), 0, s,
+                       (const uint32_t*)m->logits.get(), (const uint32_t*)tmp_logits.get(), (size_t)c.vocab_size, d_flag);
   }
   int32_t flag = 0;
-  hipError_t e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  for (void* q : {(void*)tmp_logits, (void*)tmp_pv, (void*)tmp_pi})
-    if (q) (void)hipFree(q);
-  if (rc != KH_OK) return rc;
-  if (e != hipSuccess) return (int)e;
+  KH_CHECK_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
+  KH_CHECK_HIP(hipStreamSynchronize(s));
   if ((rc = kh_launch_status()) != KH_OK) return rc;
   *result = 1;
   if (!flag && !inject) return KH_OK;
   // fall back: register-tile kernels for this model; the argmax partials follow the register-tile grid
+  if (m->sh_cls.grid != m->nparts) {
+    KhDev<float> pv;
+    KhDev<int32_t> pi;
+    if ((rc = pv.alloc((size_t)m->sh_cls.grid)) != KH_OK || (rc = pi.alloc((size_t)m->sh_cls.grid)) != KH_OK) return rc;
+    m->part_val = std::move(pv);
+    m->part_idx = std::move(pi);
+    m->nparts = m->sh_cls.grid;
+  }
   *result = -1;
   m->ring = kh_model::RingPlan();
-  if (m->sh_cls.grid != m->nparts) {
-    (void)hipFree(m->part_val);
-    (void)hipFree(m->part_idx);
-    m->part_val = nullptr;
-    m->part_idx = nullptr;
-    m->nparts = m->sh_cls.grid;
-    if ((rc = dalloc(&m->part_val, (size_t)m->nparts)) != KH_OK) return rc;
-    if ((rc = dalloc(&m->part_idx, (size_t)m->nparts)) != KH_OK) return rc;
-  }
   return KH_OK;
 }
 
@@ -133,8 +129,8 @@ static int attn_merge_case(kh_model* m, int pos, int variant, int32_t* d_flag) {
   KH_CHECK_HIP(hipMemcpyAsync(m->rms, m->att, sizeof(float) * (size_t)c.dim, hipMemcpyDeviceToDevice, s));
   for (int i = 0; i < KH_SELFTEST_ATTN_LAUNCHES; ++i) {
     launch_attn(m, 0, variant, /*fenced=*/false);
-    hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.dim)), dim3(KH_WG), 0, s, (const uint32_t*)m->att,
-                       (const uint32_t*)m->rms, (size_t)c.dim, d_flag);
+    hipLaunchKernelGGL(k_st_diff, dim3(grid_for((size_t)c.dim)), dim3(KH_WG), 0, s, (const uint32_t*)m->att.get(),
+                       (const uint32_t*)m->rms.get(), (size_t)c.dim, d_flag);
   }
   return kh_launch_status();
 }
@@ -193,21 +189,20 @@ static int w16_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) 
   size_t tmp_n = dim + 2 * kv;
   if (hid > tmp_n) tmp_n = hid;
   if (voc > tmp_n) tmp_n = voc;
-  float *x0 = nullptr, *tmp = nullptr, *tmp_pv = nullptr;
-  int32_t* tmp_pi = nullptr;
+  KhDev<float> x0, tmp, tmp_pv;
+  KhDev<int32_t> tmp_pi;
   int rc = kv_ensure(m, 1, /*layer=*/0);  // the qkv launch writes row 0 of layer 0
-  if (rc == KH_OK) rc = dalloc(&x0, dim);
-  if (rc == KH_OK) rc = dalloc(&tmp, tmp_n);
-  if (rc == KH_OK) rc = dalloc(&tmp_pv, np);
-  if (rc == KH_OK) rc = dalloc(&tmp_pi, np);
-  auto diff = [&](const float* a, const float* b, size_t n) {
+  if (rc != KH_OK || (rc = x0.alloc(dim)) != KH_OK || (rc = tmp.alloc(tmp_n)) != KH_OK ||
+      (rc = tmp_pv.alloc(np)) != KH_OK || (rc = tmp_pi.alloc(np)) != KH_OK)
+    return rc;
+  auto diff = [&](const void* a, const void* b, size_t n) {  // words, whatever they hold
     hipLaunchKernelGGL(k_st_diff, dim3(grid_for(n)), dim3(KH_WG), 0, s, (const uint32_t*)a, (const uint32_t*)b, n, d_flag);
   };
   auto copy = [&](float* dst, const float* src, size_t n) {
     return hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, s);
   };
   hipError_t e = hipSuccess;
-  if (rc == KH_OK) {
+  {
     set_state(m, 1 % c.vocab_size, 0);  // x = a real embedding row
     e = copy(x0, m->x, dim);
     if (w16_runs(m, KH_W16_QKV) && e == hipSuccess) {
@@ -250,15 +245,12 @@ static int w16_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) 
       launch_cls(m, {m->x, m->logits, m->part_val, m->part_idx}, /*ring=*/false, /*w16=*/false);
       diff(m->logits, tmp, voc);
       diff(m->part_val, tmp_pv, np);
-      diff((const float*)m->part_idx, (const float*)tmp_pi, np);
+      diff(m->part_idx, tmp_pi, np);
     }
   }
   int32_t flag = 0;
-  if (rc == KH_OK && e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s);
-  if (rc == KH_OK && e == hipSuccess) e = hipStreamSynchronize(s);
-  for (void* q : {(void*)x0, (void*)tmp, (void*)tmp_pv, (void*)tmp_pi})
-    if (q) (void)hipFree(q);
-  if (rc != KH_OK) return rc;
+  if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return (int)e;
   if ((rc = kh_launch_status()) != KH_OK) return rc;
   *result = 1;
@@ -280,18 +272,17 @@ int run_selftests(kh_model* m) {
   if (dbg_off("KH_SELFTEST")) return KH_OK;
   const auto t0 = std::chrono::steady_clock::now();
   const char* inj = dbg("KH_SELFTEST_FAIL");
-  int32_t* d_flag = nullptr;
-  KH_CHECK_HIP(hipMalloc((void**)&d_flag, 5 * sizeof(int32_t)));
+  KhDev<int32_t> d_flag;
+  int rc;
+  if ((rc = d_flag.alloc(5)) != KH_OK) return rc;
   int r = 0, a = 0, sc = 0, s8 = 0, w = 0;
-  const hipError_t e = hipMemsetAsync(d_flag, 0, 5 * sizeof(int32_t), m->stream);
+  KH_CHECK_HIP(hipMemsetAsync(d_flag, 0, 5 * sizeof(int32_t), m->stream));
   // W16 first: the checks behind it then run on the kernels the model will launch
-  int rc = e == hipSuccess ? w16_selftest(m, d_flag + 4, hook_has(inj, "w16"), &w) : (int)e;
-  if (rc == KH_OK) rc = ring_selftest(m, d_flag, hook_has(inj, "ring"), &r);
-  if (rc == KH_OK) rc = attn_selftest(m, d_flag + 1, hook_has(inj, "attn"), &a);
-  if (rc == KH_OK) rc = cls_screen_selftest(m, d_flag + 2, hook_has_screen(inj), &sc);
-  if (rc == KH_OK) rc = cls_screen_q8_selftest(m, d_flag + 3, hook_has(inj, "screen8"), &s8);
-  (void)hipFree(d_flag);
-  if (rc != KH_OK) return rc;
+  if ((rc = w16_selftest(m, d_flag + 4, hook_has(inj, "w16"), &w)) != KH_OK) return rc;
+  if ((rc = ring_selftest(m, d_flag, hook_has(inj, "ring"), &r)) != KH_OK) return rc;
+  if ((rc = attn_selftest(m, d_flag + 1, hook_has(inj, "attn"), &a)) != KH_OK) return rc;
+  if ((rc = cls_screen_selftest(m, d_flag + 2, hook_has_screen(inj), &sc)) != KH_OK) return rc;
+  if ((rc = cls_screen_q8_selftest(m, d_flag + 3, hook_has(inj, "screen8"), &s8)) != KH_OK) return rc;
   m->cfg.ring_selftest = r;
   m->cfg.attn_merge_selftest = a;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))

@@ -494,22 +494,24 @@ int lp_fill_none(kh_model* m, int pos0, int n) {
 int lp_ensure_records(kh_model* m) {
   if (m->d_lp_token) return KH_OK;
   const size_t cap = (size_t)m->cfg.cache_len, k = KH_LOGPROBS_TOP;
-  int32_t *w = nullptr, *tok = nullptr, *ids = nullptr;
-  float *lp = nullptr, *tlp = nullptr;
+  KhDev<int32_t> w, tok, ids;
+  KhDev<float> lp, tlp;
   int rc;
-  if ((rc = dalloc(&w, 1)) != KH_OK || (rc = dalloc(&tok, cap)) != KH_OK || (rc = dalloc(&lp, cap)) != KH_OK ||
-      (rc = dalloc(&ids, cap * k)) != KH_OK || (rc = dalloc(&tlp, cap * k)) != KH_OK) {
-    for (void* q : {(void*)w, (void*)tok, (void*)lp, (void*)ids, (void*)tlp})
-      if (q) (void)hipFree(q);
+  if ((rc = w.alloc(1)) != KH_OK || (rc = tok.alloc(cap)) != KH_OK || (rc = lp.alloc(cap)) != KH_OK ||
+      (rc = ids.alloc(cap * k)) != KH_OK || (rc = tlp.alloc(cap * k)) != KH_OK)
     return rc;
-  }
-  m->d_lp_top_n = w;
-  m->d_lp_token = tok;
-  m->d_lp_lp = lp;
-  m->d_lp_top_ids = ids;
-  m->d_lp_top_lp = tlp;
+  // every record "none"
+  KH_CHECK_HIP(hipMemsetAsync(tok, 0xFF, sizeof(int32_t) * cap, m->stream));
+  KH_CHECK_HIP(hipMemsetAsync(lp, 0xFF, sizeof(float) * cap, m->stream));
+  KH_CHECK_HIP(hipMemsetAsync(ids, 0xFF, sizeof(int32_t) * cap * k, m->stream));
+  KH_CHECK_HIP(hipMemsetAsync(tlp, 0xFF, sizeof(float) * cap * k, m->stream));
+  m->d_lp_top_n = std::move(w);
+  m->d_lp_token = std::move(tok);
+  m->d_lp_lp = std::move(lp);
+  m->d_lp_top_ids = std::move(ids);
+  m->d_lp_top_lp = std::move(tlp);
   m->lp_cap = (int)cap;
-  return lp_fill_none(m, 0, m->lp_cap);
+  return KH_OK;
 }
 int lp_read(kh_model* m, int pos0, int n, int top_w, int32_t* h_token, float* h_lp, int32_t* h_top_ids,
             float* h_top_lp) {
@@ -535,40 +537,40 @@ int lp_read(kh_model* m, int pos0, int n, int top_w, int32_t* h_token, float* h_
   });
 }
 
-int ensure_pinned_words(kh_model* m, int n) {
+int ensure_chunk_events(kh_model* m) {
   for (auto& e : m->ev_chunk)
     if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return (int)hipErrorUnknown;
-  if (n <= m->pin_cap) return KH_OK;
-  if (m->h_words_pin) (void)hipHostFree(m->h_words_pin);
-  m->h_words_pin = nullptr;
-  m->pin_cap = 0;
-  if (hipHostMalloc((void**)&m->h_words_pin, sizeof(int32_t) * (size_t)n, hipHostMallocDefault) !=
-      hipSuccess)
-    return (int)hipErrorUnknown;
-  m->pin_cap = n;
+  return KH_OK;
+}
+int ensure_pinned_words(kh_model* m, int n) {
+  int rc;
+  if ((rc = ensure_chunk_events(m)) != KH_OK) return rc;
+  if (n <= (int)m->h_words_pin.size()) return KH_OK;
+  KhPin<int32_t> pin;  // the old mirror stays until the new one exists
+  if ((rc = pin.alloc((size_t)n)) != KH_OK) return rc;
+  m->h_words_pin = std::move(pin);
   return KH_OK;
 }
 
 int ensure_seq_cap(kh_model* m, int n) {
   if (n <= m->seq_cap) return KH_OK;
-  if (m->d_forced) (void)hipFree(m->d_forced);
-  if (m->d_words) (void)hipFree(m->d_words);
-  if (m->h_forced_pin) (void)hipHostFree(m->h_forced_pin);
-  m->d_forced = m->d_words = nullptr;
-  m->h_forced_pin = nullptr;
-  m->seq_cap = 0;
+  KhPin<int32_t> pin;
+  KhDev<int32_t> forced, words;
   int rc;
-  if (hipHostMalloc((void**)&m->h_forced_pin, sizeof(int32_t) * ((size_t)n + 1), hipHostMallocDefault) != hipSuccess)
-    return (int)hipErrorUnknown;
-  if ((rc = dalloc(&m->d_forced, (size_t)n + 1)) != KH_OK) return rc;
-  if ((rc = dalloc(&m->d_words, (size_t)n + 1)) != KH_OK) return rc;
+  if ((rc = pin.alloc((size_t)n + 1)) != KH_OK || (rc = forced.alloc((size_t)n + 1)) != KH_OK ||
+      (rc = words.alloc((size_t)n + 1)) != KH_OK)
+    return rc;
   // forced[i] = -1 (0xFFFFFFFF): every position sampled, until a generate uploads its prompt
-  KH_CHECK_HIP(hipMemsetAsync(m->d_forced, 0xFF, sizeof(int32_t) * ((size_t)n + 1), m->stream));
+  KH_CHECK_HIP(hipMemsetAsync(forced, 0xFF, sizeof(int32_t) * ((size_t)n + 1), m->stream));
+  // the graphs captured the old pointers and capacity: they go first, then the buffers they read (nothing of the
+  // model has changed on any way out above)
+  destroy_step_graphs(m);
+  m->h_forced_pin = std::move(pin);
+  m->d_forced = std::move(forced);
+  m->d_words = std::move(words);
   m->forced_hwm = 0;
   m->forced_in_flight = false;
   m->seq_cap = n;
-  // the graph captured pointers/capacity: rebuild
-  destroy_step_graphs(m);
   return KH_OK;
 }
 void destroy_step_graphs(kh_model* m) {
@@ -752,7 +754,8 @@ extern "C" int kh_model_set_sampling(kh_model* m, const kh_sampling* p) {
   const bool on = !kh_sampling_greedy(&want);
   if (on || m->d_samp) {  // (k_sample_proc decides greedy or sampled from the device copy: it follows "off" too)
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
-    if (!m->d_samp) KH_CHECK_HIP(hipMalloc((void**)&m->d_samp, sizeof(KhSampParams)));
+    int rc;
+    if ((rc = m->d_samp.ensure(1)) != KH_OK) return rc;
     // written on the model stream behind whatever is queued; the sync keeps the host copy alive for the upload
     const KhSampParams dp = kh_samp_params(&want);
     KH_CHECK_HIP(hipMemcpyAsync(m->d_samp, &dp, sizeof(dp), hipMemcpyHostToDevice, m->stream));
@@ -776,16 +779,23 @@ int proc_commit(kh_model* m) {
   const bool on = !kh_penalties_neutral(&m->pen) || m->n_bias > 0;
   if (on || m->d_proc || m->lp_top_n >= 0) {  // (k_sample_lp reads the device copies while log-probs are on)
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
-    if (!m->d_proc) KH_CHECK_HIP(hipMalloc((void**)&m->d_proc, sizeof(KhProcParams)));
-    if (!m->d_cnt) {
-      KH_CHECK_HIP(hipMalloc((void**)&m->d_cnt, sizeof(int32_t) * (size_t)m->cfg.vocab_size));
-      KH_CHECK_HIP(hipMemsetAsync(m->d_cnt, 0, sizeof(int32_t) * (size_t)m->cfg.vocab_size, m->stream));  // once
-    }
-    if (!m->d_samp) {  // k_sample_proc reads the sampler's device copy: greedy until kh_model_set_sampling says more
-      KH_CHECK_HIP(hipMalloc((void**)&m->d_samp, sizeof(KhSampParams)));
-      const KhSampParams sp = kh_samp_params(&m->samp);
-      KH_CHECK_HIP(hipMemcpyAsync(m->d_samp, &sp, sizeof(sp), hipMemcpyHostToDevice, m->stream));
-      KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+    if (!m->d_proc) {  // the first "on": d_proc and d_cnt together, and d_samp where no sampler call made it yet
+      KhDev<KhProcParams> proc;
+      KhDev<int32_t> cnt;
+      KhDev<KhSampParams> samp;
+      const size_t V = (size_t)m->cfg.vocab_size;
+      int rc;
+      if ((rc = proc.alloc(1)) != KH_OK || (rc = cnt.alloc(V)) != KH_OK || (!m->d_samp && (rc = samp.alloc(1)) != KH_OK))
+        return rc;
+      KH_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * V, m->stream));  // once
+      if (samp) {  // k_sample_proc reads the sampler's device copy: greedy until kh_model_set_sampling says more
+        const KhSampParams sp = kh_samp_params(&m->samp);
+        KH_CHECK_HIP(hipMemcpyAsync(samp, &sp, sizeof(sp), hipMemcpyHostToDevice, m->stream));
+        KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+        m->d_samp = std::move(samp);
+      }
+      m->d_proc = std::move(proc);
+      m->d_cnt = std::move(cnt);
     }
     const KhProcParams dp{m->pen.repetition, m->pen.presence, m->pen.frequency, m->pen.last_n, m->n_bias};
     KH_CHECK_HIP(hipMemcpyAsync(m->d_proc, &dp, sizeof(dp), hipMemcpyHostToDevice, m->stream));
@@ -828,21 +838,19 @@ extern "C" int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const 
     for (int i = 0; i < n; ++i) banned += h_bias[i] == -INFINITY;
     if (banned >= V) return KH_ERR_INVALID_ARG;  // (ids are distinct and in range) nothing left to pick
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
-    if (n > m->bias_cap) {
-      // the captured k_sample_proc launches hold the old pointers: drain, replace, rebuild the graphs on next use
-      KH_CHECK_HIP(hipStreamSynchronize(m->stream));
-      if (m->d_bias_ids) (void)hipFree(m->d_bias_ids);
-      if (m->d_bias) (void)hipFree(m->d_bias);
-      m->d_bias_ids = nullptr;
-      m->d_bias = nullptr;
-      m->bias_cap = 0;
-      m->n_bias = 0;
+    if (n > (int)m->d_bias.size()) {
+      // the captured k_sample_proc launches hold the old pointers: drain, drop the graphs (rebuilt on next use), then
+      // replace the lists - once both new ones exist; until then the model and its graphs are as they were
       const int cap = n < 64 ? 64 : n;
+      KhDev<int32_t> ids_new;
+      KhDev<float> bias_new;
       int rc;
-      if ((rc = dalloc(&m->d_bias_ids, (size_t)cap)) != KH_OK) return rc;
-      if ((rc = dalloc(&m->d_bias, (size_t)cap)) != KH_OK) return rc;
-      m->bias_cap = cap;
+      if ((rc = ids_new.alloc((size_t)cap)) != KH_OK || (rc = bias_new.alloc((size_t)cap)) != KH_OK) return rc;
+      KH_CHECK_HIP(hipStreamSynchronize(m->stream));
       destroy_step_graphs(m);
+      m->d_bias_ids = std::move(ids_new);
+      m->d_bias = std::move(bias_new);
+      m->n_bias = 0;
     }
     if (n > 0) {
       KH_CHECK_HIP(hipMemcpyAsync(m->d_bias_ids, h_ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, m->stream));
@@ -1023,7 +1031,7 @@ int generate_begin(kh_model* m, const int32_t* h_prompt, int n_prompt, int total
   // are put aside before the next step overwrites them
   m->first_pos = -1;
   if (start > 0) {
-    if (!m->first_logits) KH_CHECK_HIP(hipMalloc(&m->first_logits, sizeof(float) * (size_t)c.vocab_size));
+    if ((rc = m->first_logits.ensure((size_t)c.vocab_size)) != KH_OK) return rc;
     m->first_pos = start;
   }
   set_state(m, h_prompt[start], start);

@@ -45,8 +45,7 @@ int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, in
 
 void w16_release(kh_model* m) {
   kh_model::W16& w = m->w16;
-  if (w.alloc) (void)hipFree(w.alloc);
-  w.alloc = nullptr;
+  w.alloc.reset();
   w.arena = nullptr;
   w.classes = 0;
   w.layers.clear();
@@ -78,13 +77,13 @@ int w16_create(kh_model* m) {
   const int classes = plan_w16(c.is_quant != 0, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size, c.layer_num, &bytes);
   if (!classes) return KH_OK;  // int8, or a geometry the view does not cover: nothing changes
   const int nt = 7 * c.layer_num + 1;
-  uint32_t* d_flags = nullptr;
-  KH_CHECK_HIP(hipMalloc(&w.alloc, bytes + 4096));
-  if (hipMalloc((void**)&d_flags, sizeof(uint32_t) * (size_t)nt) != hipSuccess) {
+  KhDev<uint32_t> d_flags;  // per tensor: some word is not bf16-exact
+  int rc;
+  if ((rc = w.alloc.alloc(bytes + 4096)) != KH_OK || (rc = d_flags.alloc((size_t)nt)) != KH_OK) {
     w16_release(m);
-    return (int)hipErrorOutOfMemory;
+    return rc;
   }
-  w.arena = (char*)(((uintptr_t)w.alloc + 4095) & ~(uintptr_t)4095);
+  w.arena = (char*)(((uintptr_t)w.alloc.get() + 4095) & ~(uintptr_t)4095);
   w.layers.resize((size_t)c.layer_num);
   hipStream_t s = m->stream;
   hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * (size_t)nt, s);
@@ -111,8 +110,7 @@ int w16_create(kh_model* m) {
   if (e == hipSuccess) e = hipEventRecord(m->ev1, s);
   if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(d_flags);
-  int rc = e == hipSuccess ? kh_launch_status() : (int)e;
+  rc = e == hipSuccess ? kh_launch_status() : (int)e;
   if (rc == KH_OK && off != bytes) rc = KH_ERR_INTERNAL;
   if (rc != KH_OK) {
     w16_release(m);

@@ -754,7 +754,7 @@ int argmax_slot(void* stream, ArgmaxSlot** out) {
       *out = &s;
       return KH_OK;
     }
-  int32_t* d = nullptr;
+  int32_t* d = nullptr;  // process-wide and never freed: no owner, not a KhBuf (kh_buf.h)
   KH_CHECK_HIP(hipMalloc((void**)&d, sizeof(int32_t)));
   g_argmax_slots.emplace_back(dev, stream, d);
   *out = &g_argmax_slots.back();
