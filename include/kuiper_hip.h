@@ -287,14 +287,20 @@ typedef struct kh_model_opts {
  * this way).  kh_model_cls_screen_info reports; kh_model_cls_screen_probe / _read expose one screened step on a
  * caller-supplied vector, every row's interval, the bf16 copy and its error table to the tests. */
 #define KH_FLAG_NO_CLS_SCREEN 8
-/* W16: batch-1 decode of a bf16-exact fp32 model from a 16-bit copy of its matrices, bit for bit.  An fp32 .bin that was
+/* W16: a bf16-exact fp32 model runs from a 16-bit copy of its matrices, bit for bit.  An fp32 .bin that was
  * exported from a bf16 checkpoint holds zeros in the low 16 bits of every matrix word; with this flag the model keeps a
  * second arena with the upper halves of wq, wk, wv, wo, w1, w2, w3 of every layer and of the classifier matrix (half
- * their bytes on top of the fp32 image, which the B-token passes, the operator level and the embedding keep reading),
- * and the decode GEMVs stream that copy: the same tokens, logits, K/V rows and log-prob records as without the flag,
- * compared as raw bits, from half the weight bytes per token.  Nothing is ever rounded: if one matrix word of the
- * image has a non-zero low half the copy is freed and the model behaves as if the flag were not set; likewise on int8
- * images.  Hook KH_W16=1 / 0 at creation overrides the flag.  kh_model_w16_info reports. */
+ * their bytes on top of the fp32 image) and the decode GEMVs stream that copy: the same tokens, logits, K/V rows and
+ * log-prob records as without the flag, compared as raw bits, from half the weight bytes per token.  The B-token
+ * passes - kh_model_prefill, kh_model_score, kh_model_verify / kh_model_generate_lookup, kh_model_seq_prefill,
+ * kh_model_seq_step[_ex], kh_model_generate_batch[_ex] - read the copy too, with the same bits, for the launch classes
+ * of the pass mask: by default ffn13 and w2, the two that gain on every measured geometry; hook KH_W16_PASS at
+ * creation: 0 none (the passes stream fp32), 0x1f all five, any other number a mask of the class bits below, 1 or
+ * unset the default.  Still reading the fp32 image whatever the masks say: the MFMA GEMM prefill
+ * (kh_model_prefill_gemm, long prompts of kh_model_generate without KH_FLAG_PREFILL_EXACT), the operator level, the
+ * exact re-score of the screened greedy tails and the embedding gather.  Nothing is ever rounded: if one matrix word
+ * of the image has a non-zero low half the copy is freed and the model behaves as if the flag were not set; likewise
+ * on int8 images.  Hook KH_W16=1 / 0 at creation overrides the flag.  kh_model_w16_info reports. */
 #define KH_FLAG_W16 16
 
 typedef struct kh_config {
@@ -356,7 +362,9 @@ int kh_model_cls_screen_info(kh_model* m, int64_t* out8);
 /* W16 (KH_FLAG_W16): out[8] = state (0 off or not applicable, 1 on, -1 a matrix is not bf16-exact, -2 the creation-time
  * self-check failed - in both cases the model streams fp32), bytes of the 16-bit copy, its build time in us, bit mask of
  * the launch classes that run on it (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), index of the first inexact tensor (7 * layer
- * + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: the classifier; -1 none), 0, 0, 0. */
+ * + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: the classifier; -1 none), bit mask of the launch classes whose B-token
+ * passes (prefill, score, verify, sequence slots) run on it as well - a subset of the first mask, 0 unless state is 1 -
+ * then 0, 0. */
 int kh_model_w16_info(kh_model* m, int64_t* out8);
 /* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
  * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave

@@ -5,7 +5,8 @@
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
 //                         template parameter, picked from and launched through kh_dispatch.h)
 //   kh_model_prefill.hip  B-token VALU prefill and the MFMA GEMM prefill (kh_prefill.h, kh_gemm.h,
-//                         kh_pattn.h kernels), and the B-lane pass over different sequences (kh_seq.h kernels)
+//                         kh_pattn.h kernels), the B-lane pass over different sequences (kh_seq.h kernels) and the
+//                         twins of the B-token kernels on the 16-bit copy (kh_w16_pass.h)
 //   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
 //                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
@@ -291,7 +292,7 @@ struct kh_model {
   };
   ClsScreen scr;
   // W16 (kh_w16.h, kh_model_w16.hip; KH_FLAG_W16 / hook KH_W16): a second arena with the upper halves of every matrix
-  // word of a bf16-exact fp32 model, read by the batch-1 decode GEMVs of the adopted launch classes
+  // word of a bf16-exact fp32 model, read by the batch-1 decode GEMVs and the B-token passes of the adopted launch classes
   struct W16 {
     int state = 0;          // 0 off or not applicable, 1 on, -1 some matrix is not bf16-exact, -2 the self-check failed
     KhDev<char> alloc;      // the allocation; arena = its first 4-KiB boundary
@@ -299,6 +300,7 @@ struct kh_model {
     size_t bytes = 0;       // of the copy (every matrix padded to 256 bytes)
     float build_us = 0.f;   // k_w16_build over all matrices
     int classes = 0;        // KH_W16_* bits: launch classes that run on the copy (plan_w16)
+    int pass_classes = 0;   // ... whose B-token pass does too (kh_w16_pass.h; hook KH_W16_PASS): a subset of classes
     int first_inexact = -1; // tensor index 7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers = classifier
     struct Layer {
       const void *wq, *wk, *wv, *wo, *w1, *w2, *w3;
@@ -335,7 +337,12 @@ KhAttnArgs fill_attn(kh_model* m, int l, int variant, bool fenced);
 // w16: the launch reads the 16-bit copy (kh_model::w16; its kernel has the bits of the fp32 one); the forms without
 // the argument follow the model's plan
 enum { KH_W16_QKV = 1, KH_W16_WO = 2, KH_W16_FFN13 = 4, KH_W16_W2 = 8, KH_W16_CLS = 16, KH_W16_ALL = 31 };
+// classes whose B-token pass reads the copy unless KH_W16_PASS says otherwise: the ones 3.1c's adoption rule keeps on
+// every geometry (profiles/w16_pass_ab.txt; qkv and wo fail it on Qwen2.5-0.5B, cls on TinyLlama)
+enum { KH_W16_PASS_DEFAULT = KH_W16_FFN13 | KH_W16_W2 };
 static inline bool w16_runs(const kh_model* m, int cls) { return (m->w16.classes & cls) != 0; }
+// the B-token pass of the class (kh_model_prefill.hip: launch_pf_pass, pf_gemv_res, launch_pf_cls)
+static inline bool w16_pass_runs(const kh_model* m, int cls) { return (m->w16.pass_classes & cls) != 0; }
 void launch_qkv(kh_model* m, int l, bool w16);
 void launch_attn(kh_model* m, int l, int variant, bool fenced);
 void launch_wo(kh_model* m, int l, int variant, bool w16);

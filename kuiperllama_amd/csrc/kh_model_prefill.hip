@@ -1,8 +1,9 @@
 // kh_model_prefill.hip — prompt phase of the model level: the B-token VALU pass (kh_prefill.h, bit-identical to
 // token-by-token; ONE layer driver, launch_pf_pass) and what runs on it - the prompt prefill, sequence scoring
 // (kh_model_score: k_pf_cls, k_score_lp), the verify pass of speculative greedy decode (kh_model_verify: k_pf_cls,
-// kh_spec.h) and the pass over lanes of different sequences (kh_seq.h; kh_model_seq.hip drives it) - and the
-// fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h).  The
+// kh_spec.h) and the pass over lanes of different sequences (kh_seq.h; kh_model_seq.hip drives it); for a W16 model
+// the launch classes of its pass mask run on the 16-bit copy (kh_w16_pass.h, the w16_pf_* launchers) - and the
+// fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h), which always reads fp32.  The
 // reference feeds the prompt one token per forward pass (demo/main.cpp:20-22).
 // gfx950 only.
 #include <stdio.h>
@@ -20,6 +21,7 @@
 #include "kh_score_plan.h"
 #include "kh_seq.h"
 #include "kh_spec.h"
+#include "kh_w16_pass.h"
 
 using namespace khm;
 
@@ -139,9 +141,53 @@ void pick_pf(bool quant, int sp, int b, F&& f) {
     kh_pick(SPS{}, sp, [&](auto SP) { kh_pick_ge(BS<decltype(Q)::value>{}, b, [&](auto B) { f(Q, SP, B); }); });
   });
 }
+// ---- the W16 twins (kh_w16_pass.h): `fp32` as the fp32 launch fills it, the matrices of layer l replaced by their
+// 16-bit copies, on the fp32 launch's shape, LDS bytes (the plain layout) and clipped grid - the fp32 lists without
+// their int8 level, as pick_w16 of kh_model_w16.hip
+template <class SPS, class BS, class F>
+void pick_pf_w16(int sp, int b, F&& f) {
+  kh_pick(SPS{}, sp, [&](auto SP) { kh_pick_ge(BS{}, b, [&](auto B) { f(SP, B); }); });
+}
+void w16_pf_qkv(kh_model* m, int l, const KhPfQkvArgs& fp32, const KhSeqLanes* lanes, int B) {
+  KhPfQkvArgs a = fp32;
+  const kh_model::W16::Layer& W = m->w16.layers[(size_t)l];
+  a.wq.w = W.wq;
+  a.wk.w = W.wk;
+  a.wv.w = W.wv;
+  pick_pf_w16<PfQkvSP, PfB<false>>(m->sh_qkv.split, B, [&](auto SP, auto BB) {
+    const size_t lds = pf_lds_bytes(false, a.dim, BB);
+    if (lanes)
+      pf_launch(KH_KERNEL(k_seq_qkv_w16, SP, BB), m->sh_qkv, lds, m->stream, KhSeqQkvArgs{a, *lanes});
+    else
+      pf_launch(KH_KERNEL(k_pf_qkv_w16, SP, BB), m->sh_qkv, lds, m->stream, a);
+  });
+}
+void w16_pf_ffn13(kh_model* m, int l, const KhPfFfn13Args& fp32, int B) {
+  KhPfFfn13Args a = fp32;
+  a.w1.w = m->w16.layers[(size_t)l].w1;
+  a.w3.w = m->w16.layers[(size_t)l].w3;
+  pick_pf_w16<PfNoSP, PfB<false>>(1, B, [&](auto, auto BB) {
+    pf_launch(KH_KERNEL(k_pf_ffn13_w16, BB), m->sh_ffn, pf_lds_bytes(false, a.dim, BB), m->stream, a);
+  });
+}
+// cls: KH_W16_WO or KH_W16_W2; bs: the sub-batch pf_gemv_res chose
+void w16_pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& fp32, int bs) {
+  KhPfGemvResArgs a = fp32;
+  a.w.w = cls == KH_W16_WO ? m->w16.layers[(size_t)l].wo : m->w16.layers[(size_t)l].w2;
+  pick_pf_w16<PfGemvResSP, PfGemvResB<false>>(sh.split, bs, [&](auto SP, auto B) {
+    pf_launch(KH_KERNEL(k_pf_gemv_res_w16, SP, B), sh, pf_lds_bytes(false, a.M, B), m->stream, a);
+  });
+}
+void w16_pf_cls(kh_model* m, const KhPfClsArgs& fp32, int B) {
+  KhPfClsArgs a = fp32;
+  a.wcls.w = m->w16.cls;
+  pick_pf_w16<PfNoSP, PfB<false>>(1, B, [&](auto, auto BB) {
+    pf_launch(KH_KERNEL(k_pf_cls_w16, BB), m->sh_cls, pf_lds_bytes(false, a.dim, BB), m->stream, a);
+  });
+}
 // y = W.v ; X += y for the nvalid tokens of the chunk, in sub-batches of the largest of 8/4/2
-// tokens (<= bmax) whose input vectors fit LDS
-void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const float* V, float* X,
+// tokens (<= bmax) whose input vectors fit LDS.  w: layer l's wo (cls = KH_W16_WO) or w2 (KH_W16_W2)
+void pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhLin& w, const float* V, float* X,
                  int M, int K, int nvalid, int bmax) {
   const bool q = m->cfg.is_quant;
   int bs = bmax;
@@ -155,6 +201,10 @@ void pf_gemv_res(kh_model* m, const kh_model::Shape& sh, const KhLin& w, const f
     a.V = V + (size_t)t0 * M;
     a.X = X + (size_t)t0 * K;
     a.nvalid = nvalid - t0 < bs ? nvalid - t0 : bs;
+    if (w16_pass_runs(m, cls)) {  // the same shape on the 16-bit copy
+      w16_pf_gemv_res(m, l, cls, sh, a, bs);
+      continue;
+    }
     pick_pf<PfGemvResB, PfGemvResSP>(q, sh.split, bs, [&](auto Q, auto SP, auto B) {
       pf_launch(KH_KERNEL(k_pf_gemv_res, Q, SP, B), sh, pf_lds_bytes(Q, M, B), m->stream, a);
     });
@@ -231,14 +281,18 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
   for (int l = 0; l < c.layer_num; ++l) {
     const LayerW& W = m->layers[l];
     // the instantiations of k_seq_qkv are k_pf_qkv's (PfB x PfQkvSP)
-    pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
-      const size_t lds = pf_lds_bytes(Q, c.dim, BB);
-      if (p.lanes)
-        pf_launch(KH_KERNEL(k_seq_qkv, Q, SP, BB), m->sh_qkv, lds, m->stream,
-                  KhSeqQkvArgs{pf_qkv_args(m, l, p), *p.lanes});
-      else
-        pf_launch(KH_KERNEL(k_pf_qkv, Q, SP, BB), m->sh_qkv, lds, m->stream, pf_qkv_args(m, l, p));
-    });
+    if (w16_pass_runs(m, KH_W16_QKV)) {  // the same shape on the 16-bit copy
+      w16_pf_qkv(m, l, pf_qkv_args(m, l, p), p.lanes, B);
+    } else {
+      pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
+        const size_t lds = pf_lds_bytes(Q, c.dim, BB);
+        if (p.lanes)
+          pf_launch(KH_KERNEL(k_seq_qkv, Q, SP, BB), m->sh_qkv, lds, m->stream,
+                    KhSeqQkvArgs{pf_qkv_args(m, l, p), *p.lanes});
+        else
+          pf_launch(KH_KERNEL(k_pf_qkv, Q, SP, BB), m->sh_qkv, lds, m->stream, pf_qkv_args(m, l, p));
+      });
+    }
     // the prompt phase leaves K/V rows and nothing else (no logits): the last layer's K/V rows are
     // written, its attention, wo and FFN feed nothing - unless the classifier follows (full_depth)
     if (l == c.layer_num - 1 && !p.full_depth) break;
@@ -274,7 +328,7 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
         launch_attn_decode(a, p.pos0, m->attn_wg, m->stream, nvalid, p.pos0 + nvalid - 1);
       }
     }
-    pf_gemv_res(m, m->sh_wo, W.wo, m->pf_att, m->pf_x, c.dim, c.dim, nvalid, B);
+    pf_gemv_res(m, l, KH_W16_WO, m->sh_wo, W.wo, m->pf_att, m->pf_x, c.dim, c.dim, nvalid, B);
     {
       KhPfFfn13Args a;
       a.X = m->pf_x;
@@ -287,11 +341,14 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
       a.gshift = m->gshift;
       a.nvalid = nvalid;
       a.eps = c.rms_eps;
-      pick_pf<PfB, PfNoSP>(q, 1, B, [&](auto Q, auto, auto BB) {
-        pf_launch(KH_KERNEL(k_pf_ffn13, Q, BB), m->sh_ffn, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
-      });
+      if (w16_pass_runs(m, KH_W16_FFN13))
+        w16_pf_ffn13(m, l, a, B);
+      else
+        pick_pf<PfB, PfNoSP>(q, 1, B, [&](auto Q, auto, auto BB) {
+          pf_launch(KH_KERNEL(k_pf_ffn13, Q, BB), m->sh_ffn, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
+        });
     }
-    pf_gemv_res(m, m->sh_w2, W.w2, m->pf_h, m->pf_x, c.hidden_dim, c.dim, nvalid, B);
+    pf_gemv_res(m, l, KH_W16_W2, m->sh_w2, W.w2, m->pf_h, m->pf_x, c.hidden_dim, c.dim, nvalid, B);
   }
 }
 // ---- sequence scoring: the classifier and the records behind a full-depth chunk -------------------
@@ -315,6 +372,7 @@ void launch_pf_cls(kh_model* m, int nvalid, int B) {
   a.gshift = m->gshift;
   a.nvalid = nvalid;
   a.eps = c.rms_eps;
+  if (w16_pass_runs(m, KH_W16_CLS)) return w16_pf_cls(m, a, B);
   pick_pf<PfB, PfNoSP>(c.is_quant, 1, B, [&](auto Q, auto, auto BB) {
     pf_launch(KH_KERNEL(k_pf_cls, Q, BB), m->sh_cls, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
   });

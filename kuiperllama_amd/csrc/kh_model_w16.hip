@@ -1,10 +1,12 @@
 // kh_model_w16.hip — W16 at the model level: the 16-bit copy of a bf16-exact fp32 model's matrices (plan, build,
-// exactness check, release), the decode GEMV launches that read it and kh_model_w16_info.  The kernels are kh_w16.h's;
+// exactness check, release, the class masks of decode and of the B-token passes), the decode GEMV launches that read it
+// and kh_model_w16_info (the passes' launches: kh_model_prefill.hip).  The kernels are kh_w16.h's;
 // each launch below is the fp32 launch of kh_model_step.hip with the same shape (split, u, grid, wg - a shape forced
 // through KH_SHAPE_* included) on the W16 twin of its kernel, so the bits do not change.
 // Replaces nothing in the reference (it streams fp32 weights: kuiper/source/op/kernels/cuda/matmul_kernel.cu:8-44).
 // gfx950 only.  No CPU fallback: every path below launches HIP kernels.
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "kh_dispatch.h"
@@ -48,6 +50,7 @@ void w16_release(kh_model* m) {
   w.alloc.reset();
   w.arena = nullptr;
   w.classes = 0;
+  w.pass_classes = 0;
   w.layers.clear();
   w.cls = nullptr;
 }
@@ -64,6 +67,15 @@ static void w16_configure(const kh_model* m) {
       });
     });
   });
+}
+
+// Which classes run their B-token pass (kh_w16_pass.h) on the copy as well: those of KH_W16_PASS_DEFAULT that decode
+// adopted.  Hook KH_W16_PASS, read at creation: unset or 1 - that default; 0 - none (the passes stream fp32 while decode
+// reads the copy); any other number (strtol, base 0: 0x1f, 12, 0x1 for qkv alone) - a mask of KH_W16_* bits.
+static int w16_pass_mask() {
+  const char* hook = dbg("KH_W16_PASS");
+  if (!hook || strcmp(hook, "1") == 0) return KH_W16_PASS_DEFAULT;
+  return (int)strtol(hook, nullptr, 0) & KH_W16_ALL;
 }
 
 int w16_create(kh_model* m) {
@@ -132,10 +144,11 @@ int w16_create(kh_model* m) {
   }
   w16_configure(m);
   w.classes = classes;
+  w.pass_classes = classes & w16_pass_mask();
   w.state = 1;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
-    fprintf(stderr, "[kh] W16: %.1f MiB copy of %d matrices in %.0f us, classes 0x%x\n", (double)bytes / (1 << 20), nt,
-            (double)w.build_us, (unsigned)classes);
+    fprintf(stderr, "[kh] W16: %.1f MiB copy of %d matrices in %.0f us, classes 0x%x, passes 0x%x\n",
+            (double)bytes / (1 << 20), nt, (double)w.build_us, (unsigned)classes, (unsigned)w.pass_classes);
   return KH_OK;
 }
 
@@ -229,5 +242,6 @@ extern "C" int kh_model_w16_info(kh_model* m, int64_t* out) {
   out[2] = (int64_t)m->w16.build_us;
   out[3] = m->w16.classes;
   out[4] = m->w16.first_inexact;
+  out[5] = m->w16.pass_classes;
   return KH_OK;
 }

@@ -20,6 +20,8 @@
 // The B tokens of a pass need not be consecutive positions of one sequence: kh_seq.h runs the same pass over lanes
 // that belong to different sequences (k_seq_qkv instantiates pf_qkv_body below with its own addressing).
 #pragma once
+#include <type_traits>
+
 #include "kh_fused.h"
 
 // Tokens per weight pass: up to 8 for the dim-input matrices of fp32 models when 8 vectors leave
@@ -29,6 +31,12 @@
 // 16-byte loads per row in flight per lane: int8 converts the whole tile to floats once per
 // chunk (16 floats per load), so its tile is kept to 2 loads per row
 #define KH_PF_U(QUANT) ((QUANT) ? 2 : 4)
+// The kernels below are written over the matrix view G (kh_gemv.h: Gemv<QUANT, U>; kh_w16_pass.h runs the same text
+// on GemvW16<U>).  Only the LDS layout of the staged vectors asks "int8 or not": every other view stages plain fp32.
+template <class G>
+constexpr bool pf_layout_q8() {
+  return std::is_same<typename G::Regs, RegsQ8<G::kU>>::value;
+}
 
 // ---- B-token FMA of one register chunk --------------------------------------------------------
 template <int U, int B>
@@ -107,15 +115,14 @@ __device__ __forceinline__ void fma_chunk_b(const RegsQ8<U>& r, const f32x4* xs,
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-template <bool QUANT, int U, int B>
-__device__ __forceinline__ void gemv_fma_b(const Gemv<QUANT, U>& g,
-                                           const typename Gemv<QUANT, U>::Regs& r,
-                                           const f32x4* xs, int xstride, int c0, int lim, int lane,
-                                           float (&a0)[B], float (&a1)[B]) {
-  if constexpr (QUANT)
-    fma_chunk_b<U, B>(r, xs, xstride, c0, lim, g.Mc + 1, lane, a0, a1);
+// the overload of the view's register tile (found at instantiation: kh_w16_pass.h adds RegsW16's)
+template <class G, int B>
+__device__ __forceinline__ void gemv_fma_b(const G& g, const typename G::Regs& r, const f32x4* xs, int xstride, int c0,
+                                           int lim, int lane, float (&a0)[B], float (&a1)[B]) {
+  if constexpr (pf_layout_q8<G>())
+    fma_chunk_b<G::kU, B>(r, xs, xstride, c0, lim, g.Mc + 1, lane, a0, a1);
   else
-    fma_chunk_b<U, B>(r, xs, xstride, c0, lim, lane, a0, a1);
+    fma_chunk_b<G::kU, B>(r, xs, xstride, c0, lim, lane, a0, a1);
 }
 
 // LDS of a B-token GEMV stage: xs[B] | red[KH_WAVES_MAX*B] | comb[2*KH_WAVES_MAX*B]
@@ -132,11 +139,11 @@ static inline size_t pf_lds_bytes(bool quant, int M, int B) {
 //   EPI(p, s0[B], s1[B], aux) called by every lane of the owning wave.
 // (A double-buffered register tile — loads of chunk i+1 issued before the FMAs of chunk i — was
 // measured: no gain, and the int8 kernels ran out of VGPRs; other waves already cover the FMAs.)
-template <bool QUANT, int U, int SPLIT, int B, class PairFn, class PreFn, class StageFn,
-          class EpiFn>
-__device__ __forceinline__ void gemv_pairs_b(const Gemv<QUANT, U>& g, const f32x4* xs, int xstride,
+template <class G, int SPLIT, int B, class PairFn, class PreFn, class StageFn, class EpiFn>
+__device__ __forceinline__ void gemv_pairs_b(const G& g, const f32x4* xs, int xstride,
                                              int total, int lane, float* comb, PairFn&& PAIR,
                                              PreFn&& PRE, StageFn&& STAGE, EpiFn&& EPI) {
+  constexpr int U = G::kU;
   static_assert(SPLIT == 1 || SPLIT == 2 || SPLIT == 4, "SPLIT must be 1, 2 or 4");
   const int PPW = kh_nwaves() / SPLIT;
   const int wave = threadIdx.x >> 6;
@@ -148,8 +155,8 @@ __device__ __forceinline__ void gemv_pairs_b(const Gemv<QUANT, U>& g, const f32x
   const int cb = part * Q;
   const int ce = cb + Q < g.Mc ? cb + Q : g.Mc;
   const int p0 = gp < total ? gp : 0;
-  typename Gemv<QUANT, U>::Regs regs;
-  typename Gemv<QUANT, U>::Rows cur = PAIR(p0);
+  typename G::Regs regs;
+  typename G::Rows cur = PAIR(p0);
   g.load(regs, cur, cb, ce, lane);  // first weight chunk in flight while the vectors are staged
   auto aux = PRE(p0);
   STAGE();
@@ -162,7 +169,7 @@ __device__ __forceinline__ void gemv_pairs_b(const Gemv<QUANT, U>& g, const f32x
     for (int b = 0; b < B; ++b) a0[b] = a1[b] = 0.f;
     if (valid) {
       for (int c0 = cb;;) {
-        gemv_fma_b<QUANT, U, B>(g, regs, xs, xstride, c0, ce, lane, a0, a1);
+        gemv_fma_b<G, B>(g, regs, xs, xstride, c0, ce, lane, a0, a1);
         c0 += step;
         if (c0 >= ce) break;
         g.load(regs, cur, c0, ce, lane);
@@ -334,9 +341,9 @@ struct PfRunAddr {
   __device__ __forceinline__ int row(int b) const { return pos0 + b; }
 };
 // the body of k_pf_qkv, shared with k_seq_qkv (kh_seq.h)
-template <bool QUANT, int SPLIT, int B, class Addr>
+template <class G, int SPLIT, int B, class Addr>
 __device__ __forceinline__ void pf_qkv_body(const KhPfQkvArgs& a, const Addr& addr, char* smem_raw) {
-  constexpr int U = KH_PF_U(QUANT);
+  constexpr bool Q8 = pf_layout_q8<G>();
   const void *wq_w = a.wq.w, *wk_w = a.wk.w, *wv_w = a.wv.w;
   const float *wq_s = a.wq.scales, *wk_s = a.wk.scales, *wv_s = a.wv.scales;
   const float *wq_b = a.wq.bias, *wk_b = a.wk.bias, *wv_b = a.wv.bias;
@@ -351,14 +358,14 @@ __device__ __forceinline__ void pf_qkv_body(const KhPfQkvArgs& a, const Addr& ad
   const int nvalid = a.nvalid;
   const float eps = a.eps;
   f32x4* xs = (f32x4*)smem_raw;
-  const int xstride = pf_xstride<QUANT>(dim);
+  const int xstride = pf_xstride<Q8>(dim);
   float* red = (float*)(xs + (size_t)B * xstride);
   float* comb = red + KH_WAVES_MAX * B;
   const int lane = threadIdx.x & 63;
   const int hs = a.head_size, half = hs >> 1;
   const int npq = dim >> 1, npk = kv_dim >> 1;
   const int total = npq + 2 * npk;
-  const Gemv<QUANT, U> g(dim, a.gshift);
+  const G g(dim, a.gshift);
   auto decode = [&](int p, int& which, int& r0, int& r1, int& cidx) __attribute__((always_inline)) {
     int pp;
     if (p < npq) {
@@ -428,17 +435,17 @@ __device__ __forceinline__ void pf_qkv_body(const KhPfQkvArgs& a, const Addr& ad
       dst[r1] = v1;
     }
   };
-  gemv_pairs_b<QUANT, U, SPLIT, B>(
+  gemv_pairs_b<G, SPLIT, B>(
       g, xs, xstride, total, lane, comb, pair, pre,
       [&]() __attribute__((always_inline)) {
-        pf_stage_norm<QUANT, B>(X, (size_t)dim, att_norm, xs, xstride, dim, eps, red, rs);
+        pf_stage_norm<Q8, B>(X, (size_t)dim, att_norm, xs, xstride, dim, eps, red, rs);
       },
       epi);
 }
 template <bool QUANT, int SPLIT, int B>
 __global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv(const KhPfQkvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  pf_qkv_body<QUANT, SPLIT, B>(a, PfRunAddr{a.pos0, a.nvalid}, smem_raw);
+  pf_qkv_body<Gemv<QUANT, KH_PF_U(QUANT)>, SPLIT, B>(a, PfRunAddr{a.pos0, a.nvalid}, smem_raw);
 }
 
 struct KhPfFfn13Args {
@@ -449,10 +456,9 @@ struct KhPfFfn13Args {
   int dim, hidden, gshift, nvalid;
   float eps;
 };
-template <bool QUANT, int B>
-__global__ __launch_bounds__(KH_WG_MAX) void k_pf_ffn13(const KhPfFfn13Args a) {
-  constexpr int U = KH_PF_U(QUANT);
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+template <class G, int B>
+__device__ __forceinline__ void pf_ffn13_body(const KhPfFfn13Args& a, char* smem_raw) {
+  constexpr bool Q8 = pf_layout_q8<G>();
   const void *w1 = a.w1.w, *w3 = a.w3.w;
   const float *s1p = a.w1.scales, *s3p = a.w3.scales;
   const float* const X = a.X;
@@ -461,10 +467,10 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_ffn13(const KhPfFfn13Args a) {
   const int dim = a.dim, hidden = a.hidden, nvalid = a.nvalid;
   const float eps = a.eps;
   f32x4* xs = (f32x4*)smem_raw;
-  const int xstride = pf_xstride<QUANT>(dim);
+  const int xstride = pf_xstride<Q8>(dim);
   float* red = (float*)(xs + (size_t)B * xstride);
   const int lane = threadIdx.x & 63;
-  const Gemv<QUANT, U> g(dim, a.gshift);
+  const G g(dim, a.gshift);
   auto pair = [&](int r) __attribute__((always_inline)) { return g.rows(w1, r, w3, r, s1p, s3p, dim); };
   float rs[B];  // RMS scale per token: set by the staging, applied in the epilogue (as k_ffn13)
   auto epi = [&](int r, const float (&s0)[B], const float (&s1)[B], const NoAux&)
@@ -474,13 +480,18 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_ffn13(const KhPfFfn13Args a) {
     for (int b = 0; b < B; ++b)
       if (b < nvalid) H[(size_t)b * hidden + r] = swiglu1(rs[b] * s0[b], rs[b] * s1[b]);
   };
-  gemv_pairs_b<QUANT, U, 1, B>(
+  gemv_pairs_b<G, 1, B>(
       g, xs, xstride, hidden, lane, nullptr, pair,
       [](int) __attribute__((always_inline)) { return NoAux{}; },
       [&]() __attribute__((always_inline)) {
-        pf_stage_norm<QUANT, B>(X, (size_t)dim, ffn_norm, xs, xstride, dim, eps, red, rs);
+        pf_stage_norm<Q8, B>(X, (size_t)dim, ffn_norm, xs, xstride, dim, eps, red, rs);
       },
       epi);
+}
+template <bool QUANT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_ffn13(const KhPfFfn13Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_ffn13_body<Gemv<QUANT, KH_PF_U(QUANT)>, B>(a, smem_raw);
 }
 
 struct KhPfGemvResArgs {
@@ -489,21 +500,20 @@ struct KhPfGemvResArgs {
   float* X;        // [B][K] residual streams, updated in place
   int M, K, gshift, nvalid;
 };
-template <bool QUANT, int SPLIT, int B>
-__global__ __launch_bounds__(KH_WG_MAX) void k_pf_gemv_res(const KhPfGemvResArgs a) {
-  constexpr int U = KH_PF_U(QUANT);
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+template <class G, int SPLIT, int B>
+__device__ __forceinline__ void pf_gemv_res_body(const KhPfGemvResArgs& a, char* smem_raw) {
+  constexpr bool Q8 = pf_layout_q8<G>();
   const void* const w = a.w.w;
   const float* const scales = a.w.scales;
   const float* const V = a.V;
   float* const X = a.X;
   const int M = a.M, K = a.K, nvalid = a.nvalid;
   f32x4* xs = (f32x4*)smem_raw;
-  const int xstride = pf_xstride<QUANT>(M);
+  const int xstride = pf_xstride<Q8>(M);
   float* red = (float*)(xs + (size_t)B * xstride);
   float* comb = red + KH_WAVES_MAX * B;
   const int lane = threadIdx.x & 63;
-  const Gemv<QUANT, U> g(M, a.gshift);
+  const G g(M, a.gshift);
   auto pair = [&](int p) __attribute__((always_inline)) { return g.rows(w, 2 * p, w, 2 * p + 1, scales, scales, M); };
   struct Aux {
     float x0[B], x1[B];
@@ -528,10 +538,15 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_gemv_res(const KhPfGemvResArgs
       }
     }
   };
-  gemv_pairs_b<QUANT, U, SPLIT, B>(
+  gemv_pairs_b<G, SPLIT, B>(
       g, xs, xstride, K >> 1, lane, comb, pair, pre,
-      [&]() __attribute__((always_inline)) { pf_stage_copy<QUANT, B>(V, (size_t)M, xs, xstride, M); },
+      [&]() __attribute__((always_inline)) { pf_stage_copy<Q8, B>(V, (size_t)M, xs, xstride, M); },
       epi);
+}
+template <bool QUANT, int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_gemv_res(const KhPfGemvResArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_gemv_res_body<Gemv<QUANT, KH_PF_U(QUANT)>, SPLIT, B>(a, smem_raw);
 }
 
 // Sequence scoring (kh_model_score): the B-token twin of k_cls.  Launched with the classifier's decode shape
@@ -547,10 +562,9 @@ struct KhPfClsArgs {
   int dim, vocab, vstride, gshift, nvalid;
   float eps;
 };
-template <bool QUANT, int B>
-__global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls(const KhPfClsArgs a) {
-  constexpr int U = KH_PF_U(QUANT);
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+template <class G, int B>
+__device__ __forceinline__ void pf_cls_body(const KhPfClsArgs& a, char* smem_raw) {
+  constexpr bool Q8 = pf_layout_q8<G>();
   const void* const w = a.wcls.w;
   const float* const sc = a.wcls.scales;
   const float* const X = a.X;
@@ -559,10 +573,10 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls(const KhPfClsArgs a) {
   const int dim = a.dim, vocab = a.vocab, vstride = a.vstride, nvalid = a.nvalid;
   const float eps = a.eps;
   f32x4* xs = (f32x4*)smem_raw;
-  const int xstride = pf_xstride<QUANT>(dim);
+  const int xstride = pf_xstride<Q8>(dim);
   float* red = (float*)(xs + (size_t)B * xstride);
   const int lane = threadIdx.x & 63;
-  const Gemv<QUANT, U> g(dim, a.gshift);
+  const G g(dim, a.gshift);
   auto r1_of = [&](int p) __attribute__((always_inline)) { return 2 * p + 1 < vocab ? 2 * p + 1 : 2 * p; };
   auto pair = [&](int p) __attribute__((always_inline)) { return g.rows(w, 2 * p, w, r1_of(p), sc, sc, dim); };
   float rs[B];  // RMS scale per token: set by the staging, applied in the epilogue (as k_cls)
@@ -579,11 +593,16 @@ __global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls(const KhPfClsArgs a) {
       }
     }
   };
-  gemv_pairs_b<QUANT, U, 1, B>(
+  gemv_pairs_b<G, 1, B>(
       g, xs, xstride, (vocab + 1) >> 1, lane, nullptr, pair,
       [](int) __attribute__((always_inline)) { return NoAux{}; },
       [&]() __attribute__((always_inline)) {
-        pf_stage_norm<QUANT, B>(X, (size_t)dim, final_norm, xs, xstride, dim, eps, red, rs);
+        pf_stage_norm<Q8, B>(X, (size_t)dim, final_norm, xs, xstride, dim, eps, red, rs);
       },
       epi);
+}
+template <bool QUANT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls(const KhPfClsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_cls_body<Gemv<QUANT, KH_PF_U(QUANT)>, B>(a, smem_raw);
 }

@@ -47,7 +47,7 @@ struct PfLaneAddr {
 template <bool QUANT, int SPLIT, int B>
 __global__ __launch_bounds__(KH_WG_MAX) void k_seq_qkv(const KhSeqQkvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  pf_qkv_body<QUANT, SPLIT, B>(a.a, PfLaneAddr{a.lanes}, smem_raw);
+  pf_qkv_body<Gemv<QUANT, KH_PF_U(QUANT)>, SPLIT, B>(a.a, PfLaneAddr{a.lanes}, smem_raw);
 }
 
 // The tail of a pass.  Workgroup b: the maximum of row b of the logits and its first index (kh_samp_row_amax, as

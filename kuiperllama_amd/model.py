@@ -326,6 +326,14 @@ class KuiperModel:
                 "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1],
                 "first_inexact": int(out[4])}
 
+    def w16_pass_info(self) -> dict:
+        """The B-token passes of a KH_FLAG_W16 model (kh_model_w16_info, slot 5): {"classes": the launch classes whose
+        passes - prefill, score, verify / generate_lookup, seq_* and generate_batch* - stream the 16-bit copy}, a
+        subset of w16_info()["classes"] (hook KH_W16_PASS at creation); [] when the passes stream the fp32 matrices."""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_w16_info(self._h, out), "kh_model_w16_info")
+        return {"classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[5] >> i & 1]}
+
     def cls_screen_probe(self, x: np.ndarray) -> dict:
         """One screened step and one full-classifier step on the residual vector x[dim], without advancing
         (kh_model_cls_screen_probe, tests): the two tokens, the candidate rows re-scored, whether the step overflowed,

@@ -22,7 +22,7 @@
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
 // prompt tokens/s).  --fenced-merge = KH_FLAG_ATTN_MERGE_FENCED.  The self-checks of kh_model_create_* are printed.
 // --w16 = KH_FLAG_W16: decode a bf16-exact fp32 image from a 16-bit copy of its matrices, bit for bit (an image that is
-// not bf16-exact decodes as without the flag); prints kh_model_w16_info.
+// not bf16-exact decodes as without the flag); prints kh_model_w16_info, the pass class mask included.
 // --temperature / --top-k / --top-p / --seed: seeded sampling instead of the argmax (kh_model_set_sampling; the
 // reference's demo is greedy, which stays the default).
 // --repeat-penalty / --presence-penalty / --frequency-penalty over the last --repeat-last-n fed tokens (0: all of
@@ -255,8 +255,11 @@ int main(int argc, char** argv) {
     int64_t w[8] = {0};
     kh_model_w16_info(m, w);
     // state: 0 not applicable (int8), 1 on, -1 the image is not bf16-exact, -2 self-check failed (both: fp32 decode)
-    std::fprintf(stderr, "W16: state %lld, copy %.2f GB built in %.2f ms, launch classes 0x%llx, first inexact tensor %lld\n",
-                 (long long)w[0], (double)w[1] / 1e9, (double)w[2] / 1e3, (unsigned long long)w[3], (long long)w[4]);
+    // pass classes: whose B-token passes (prefill, score, verify, sequence slots) read the copy too (hook KH_W16_PASS)
+    std::fprintf(stderr, "W16: state %lld, copy %.2f GB built in %.2f ms, launch classes 0x%llx, pass classes 0x%llx, "
+                 "first inexact tensor %lld\n",
+                 (long long)w[0], (double)w[1] / 1e9, (double)w[2] / 1e3, (unsigned long long)w[3],
+                 (unsigned long long)w[5], (long long)w[4]);
   }
   rc = kh_model_set_sampling(m, &samp);
   if (rc != KH_OK) {
