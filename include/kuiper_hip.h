@@ -302,6 +302,16 @@ typedef struct kh_model_opts {
  * of the image has a non-zero low half the copy is freed and the model behaves as if the flag were not set; likewise
  * on int8 images.  Hook KH_W16=1 / 0 at creation overrides the flag.  kh_model_w16_info reports. */
 #define KH_FLAG_W16 16
+/* W16 for fp16-origin checkpoints (Llama-2): keep the 16-bit copy in whichever format the image is exact in.  First
+ * bf16, exactly as KH_FLAG_W16 (its kernels, all or nothing); if some matrix word is not bf16-exact, fp16: a word
+ * qualifies when it is +-0, an fp16 normal (2^-14 .. 65504, low 13 mantissa bits zero) or an fp16 subnormal (a multiple
+ * of 2^-24 below 2^-14); Inf and NaN do not.  The copy then holds the IEEE binary16 value of every matrix word (same
+ * layout and bytes), the kernels convert each back - exactly - and run the FMAs of the fp32 kernels in their order, so
+ * the bits are again those of the fp32 run; the creation-time self-check covers this copy as it covers a bf16 one.  If
+ * the image is exact in neither format there is no copy (state -1).  Implies KH_FLAG_W16; everything said there about
+ * the passes, KH_W16_PASS and what still reads fp32 holds.  Hook KH_W16_F16=1 / 0 at creation overrides this bit;
+ * KH_W16=0 still means no copy at all.  kh_model_w16_info slots 6 and 7 report. */
+#define KH_FLAG_W16_F16 32
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -364,7 +374,9 @@ int kh_model_cls_screen_info(kh_model* m, int64_t* out8);
  * the launch classes that run on it (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), index of the first inexact tensor (7 * layer
  * + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: the classifier; -1 none), bit mask of the launch classes whose B-token
  * passes (prefill, score, verify, sequence slots) run on it as well - a subset of the first mask, 0 unless state is 1 -
- * then 0, 0. */
+ * then the format of the live copy (0 bf16 or no copy, 1 fp16: KH_FLAG_W16_F16) and 1 + the index of the first tensor
+ * that is not fp16-exact (0: fp16 was not tried, or every tensor passed).  With KH_FLAG_W16_F16 state -1 means exact
+ * in neither format, and slot 4 keeps the first tensor that is not bf16-exact. */
 int kh_model_w16_info(kh_model* m, int64_t* out8);
 /* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
  * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave

@@ -43,6 +43,7 @@ KH_FLAG_ATTN_MERGE_FENCED = 2
 KH_FLAG_PREFILL_EXACT = 4
 KH_FLAG_NO_CLS_SCREEN = 8
 KH_FLAG_W16 = 16
+KH_FLAG_W16_F16 = 32  # the copy in whichever of bf16 / fp16 the image is exact in (KuiperModel.w16_format)
 KH_W16_CLASSES = ("qkv", "wo", "ffn13", "w2", "cls")  # bit i of a class mask (kh_model_w16_info, kh_plan_w16)
 KH_LOGPROBS_MAX_TOP = 20
 KH_SEQ_BIAS_MAX = 64

@@ -357,5 +357,49 @@ def matrices_bf16_exact(image, spec: ModelSpec) -> bool:
     return bool(ents) and all(not bool((_words(image, e) & 0xFFFF).any()) for e in ents)
 
 
+def round_matrices_fp16(image, spec: ModelSpec):
+    """Round the tensors of w16_tensors(spec) to the nearest fp16 (IEEE binary16) value, ties to even, in place, and
+    leave them as the fp32 words of those values: the image is then fp16-exact, what KH_FLAG_W16_F16 needs.  Integer
+    arithmetic on the words.  Below 2^-14 the result is an fp16 subnormal (a multiple of 2^-24; 2^-25 and less go to
+    zero, anything above 2^-25 to at least 2^-24); a value that rounds past 65504 becomes Inf as in IEEE; NaN stays NaN
+    with the ten payload bits fp16 keeps (quiet bit included; an empty payload becomes the lowest of them).
+    image: numpy uint8 array or torch uint8 tensor on any device.  Returns image."""
+    for e in w16_tensors(spec):
+        w = _words(image, e)
+        a = w & 0x7FFFFFFF
+        ex = a >> 23
+        # low bits of the word below the last fp16 place: 13 for fp16 normals, 126 - e for subnormals (103 <= e <= 112)
+        drop = torch.where(ex >= 113, torch.full_like(ex, 13), (126 - ex).clamp(min=14, max=23))
+        one = torch.ones_like(a)
+        odd = ((a | 0x00800000) >> drop) & 1  # of the kept part; the leading one is its last place when drop is 23
+        r = a + ((one << (drop - 1)) - 1) + odd
+        r = r & -(one << drop)
+        r = torch.where(r >= 0x47800000, torch.full_like(r, 0x7F800000), r)  # 65520 and above (Inf too): Inf
+        tiny = torch.where(a > (102 << 23), torch.full_like(a, 103 << 23), torch.zeros_like(a))
+        r = torch.where(ex >= 103, r, tiny)
+        nan = a & -0x2000
+        nan = torch.where(nan == 0x7F800000, nan | 0x2000, nan)
+        r = torch.where(a > 0x7F800000, nan, r)
+        w.copy_((w & -0x80000000) | r)
+    return image
+
+
+def _fp16_exact_words(w: torch.Tensor) -> torch.Tensor:
+    """The exactness rule of KH_FLAG_W16_F16 on int32 words (kh_w16.h: h16_field), elementwise."""
+    a = w & 0x7FFFFFFF
+    ex = a >> 23
+    norm = (ex >= 113) & (ex <= 142) & ((a & 0x1FFF) == 0)
+    low = a & ((torch.ones_like(a) << (126 - ex).clamp(min=0, max=23)) - 1)
+    sub = (ex >= 103) & (ex <= 112) & (low == 0)
+    return (a == 0) | norm | sub
+
+
+def matrices_fp16_exact(image, spec: ModelSpec) -> bool:
+    """Is every matrix word of w16_tensors(spec) an fp16 value (+-0, an fp16 normal or subnormal; Inf and NaN are
+    not), i.e. would KH_FLAG_W16_F16 keep an fp16 copy of an image that is not bf16-exact?"""
+    ents = w16_tensors(spec)
+    return bool(ents) and all(bool(_fp16_exact_words(_words(image, e)).all()) for e in ents)
+
+
 def spec_to_dict(spec: ModelSpec) -> dict:
     return dataclasses.asdict(spec)

@@ -1,5 +1,5 @@
 // kh_model_internal.h — state and cross-unit helpers of the model level of the C-ABI.
-// The model level is split into eight translation units:
+// The model level is split into ten translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
@@ -14,6 +14,8 @@
 //   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge, the screen and W16
 //   kh_model_w16.hip      the 16-bit copy of a bf16-exact fp32 model's matrices and the decode GEMV launches that read
 //                         it (kh_w16.h kernels are instantiated here)
+//   kh_model_h16.hip      the same launches for a copy in fp16 format (KH_FLAG_W16_F16; the _h16 kernels of kh_w16.h)
+//   kh_model_h16_pass.hip ... and its B-token passes (the _h16 kernels of kh_w16_pass.h)
 // gfx950 only.  No CPU fallback: every path launches HIP kernels.
 //
 // Ownership: every device or pinned-host buffer the library allocates is a KhDev<T> / KhPin<T> (kh_buf.h) - a field of
@@ -292,9 +294,12 @@ struct kh_model {
   };
   ClsScreen scr;
   // W16 (kh_w16.h, kh_model_w16.hip; KH_FLAG_W16 / hook KH_W16): a second arena with the upper halves of every matrix
-  // word of a bf16-exact fp32 model, read by the batch-1 decode GEMVs and the B-token passes of the adopted launch classes
+  // word of a bf16-exact fp32 model, read by the batch-1 decode GEMVs and the B-token passes of the adopted launch classes.
+  // With KH_FLAG_W16_F16 / hook KH_W16_F16 an image that is not bf16-exact but fp16-exact gets the fp16 values instead.
   struct W16 {
-    int state = 0;          // 0 off or not applicable, 1 on, -1 some matrix is not bf16-exact, -2 the self-check failed
+    int state = 0;          // 0 off or not applicable, 1 on, -1 some matrix is not exact in a format asked for, -2 the self-check failed
+    int format = 0;         // of the live copy: KH_W16_BF16 (also: no copy) or KH_W16_F16 (kh_w16.h)
+    int first_inexact_f16 = -1;  // as first_inexact, for the fp16 format (-1: not tried, or every tensor passed)
     KhDev<char> alloc;      // the allocation; arena = its first 4-KiB boundary
     char* arena = nullptr;
     size_t bytes = 0;       // of the copy (every matrix padded to 256 bytes)
@@ -457,6 +462,15 @@ void w16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
 void w16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
 void w16_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
 void w16_launch_cls(kh_model* m, const KhClsArgs& a);
+// ---- kh_model_h16.hip: the same launches on an fp16-format copy (the w16_launch_* above hand over by w16.format;
+// one text, kh_w16_launch.h), the LDS opt-in of their w2 kernel ------------------------------------
+void h16_configure(const kh_model* m);
+void h16_launch_qkv(kh_model* m, int l, const KhQkvArgs& a);
+void h16_launch_wo(kh_model* m, int l, const KhGemvResArgs& a);
+void h16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
+void h16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
+void h16_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
+void h16_launch_cls(kh_model* m, const KhClsArgs& a);
 // ---- kh_model_load.hip ----------------------------------------------------------------------
 // Make rows [0, rows) of the K / V cache usable before anything that touches them is enqueued: every layer, or one
 // (layer >= 0).  No-op for rows that are mapped already and for caches that are plainly allocated.  Newly mapped

@@ -20,7 +20,8 @@
 //      A failure turns the tier off and frees the int8 copy; the bf16 screen goes on (kh_model_cls_screen_q8_info: -1).
 //  (e) W16 (kh_w16.h, kh_model_w16.hip): every launch class that runs on the 16-bit copy, once against the fp32 kernel
 //      of the same launch - layer 0 or the classifier, a real embedding row as the residual stream - outputs compared
-//      word for word.  A mismatch frees the copy and the model streams fp32 (kh_model_w16_info: state -2).
+//      word for word.  A mismatch frees the copy and the model streams fp32 (kh_model_w16_info: state -2).  The
+//      launches go by the copy's format, so an fp16-format copy (KH_FLAG_W16_F16) is checked through its _h16 kernels.
 //
 // Both run on scratch state the model owns at that moment (activation buffers, rows of layer 0 of the still
 // empty KV cache, which are zeroed again) in about a millisecond.  This is a tripwire for a part, a compiler or a

@@ -1,7 +1,8 @@
-// kh_model_w16.hip — W16 at the model level: the 16-bit copy of a bf16-exact fp32 model's matrices (plan, build,
-// exactness check, release, the class masks of decode and of the B-token passes), the decode GEMV launches that read it
-// and kh_model_w16_info (the passes' launches: kh_model_prefill.hip).  The kernels are kh_w16.h's;
-// each launch below is the fp32 launch of kh_model_step.hip with the same shape (split, u, grid, wg - a shape forced
+// kh_model_w16.hip — W16 at the model level: the 16-bit copy of a bf16-exact (or, with KH_FLAG_W16_F16, fp16-exact)
+// fp32 model's matrices (plan, build, exactness check, release, the class masks of decode and of the B-token passes),
+// the decode GEMV launches that read it and kh_model_w16_info (the passes' launches: kh_model_prefill.hip; the
+// launches of an fp16-format copy: kh_model_h16.hip, kh_model_h16_pass.hip).  The kernels are kh_w16.h's;
+// each launch is the fp32 launch of kh_model_step.hip with the same shape (split, u, grid, wg - a shape forced
 // through KH_SHAPE_* included) on the W16 twin of its kernel, so the bits do not change.
 // Replaces nothing in the reference (it streams fp32 weights: kuiper/source/op/kernels/cuda/matmul_kernel.cu:8-44).
 // gfx950 only.  No CPU fallback: every path below launches HIP kernels.
@@ -9,9 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "kh_dispatch.h"
-#include "kh_w16.h"
-#include "kh_model_internal.h"
+#include "kh_w16_launch.h"
 
 namespace khm {
 
@@ -51,22 +50,9 @@ void w16_release(kh_model* m) {
   w.arena = nullptr;
   w.classes = 0;
   w.pass_classes = 0;
+  w.format = KH_W16_BF16;
   w.layers.clear();
   w.cls = nullptr;
-}
-
-// >64 KiB dynamic-LDS opt-in of k_gemv_res_w16 as w2 (configure_step_kernels does it for k_gemv_res)
-static void w16_configure(const kh_model* m) {
-  const size_t lds_need = fused_lds_bytes(false, m->cfg.hidden_dim);
-  if (lds_need <= 64 * 1024) return;
-  GemvResU<false>::each([&](auto U) {
-    GemvResSP::each([&](auto SP) {
-      KhVals<0, 6>::each([&](auto MV) {
-        (void)hipFuncSetAttribute((const void*)k_gemv_res_w16<decltype(U)::value, decltype(MV)::value, decltype(SP)::value>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need);
-      });
-    });
-  });
 }
 
 // Which classes run their B-token pass (kh_w16_pass.h) on the copy as well: those of KH_W16_PASS_DEFAULT that decode
@@ -78,18 +64,22 @@ static int w16_pass_mask() {
   return (int)strtol(hook, nullptr, 0) & KH_W16_ALL;
 }
 
+// The copy in the first format the image is exact in: bf16 (KH_FLAG_W16 or KH_FLAG_W16_F16), else fp16 (only
+// KH_FLAG_W16_F16; into the same arena - plan_w16's layout holds for both), else none.  All or nothing per format.
 int w16_create(kh_model* m) {
   const kh_config& c = m->cfg;
   kh_model::W16& w = m->w16;
   w = kh_model::W16();
   const char* hook = dbg("KH_W16");
-  const bool want = hook ? hook[0] == '1' : (m->opts.flags & KH_FLAG_W16) != 0;
+  const char* hook_f16 = dbg("KH_W16_F16");
+  const bool try_f16 = hook_f16 ? hook_f16[0] == '1' : (m->opts.flags & KH_FLAG_W16_F16) != 0;
+  const bool want = hook ? hook[0] == '1' : (m->opts.flags & KH_FLAG_W16) != 0 || try_f16;
   if (!want) return KH_OK;
   size_t bytes = 0;
   const int classes = plan_w16(c.is_quant != 0, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size, c.layer_num, &bytes);
   if (!classes) return KH_OK;  // int8, or a geometry the view does not cover: nothing changes
   const int nt = 7 * c.layer_num + 1;
-  KhDev<uint32_t> d_flags;  // per tensor: some word is not bf16-exact
+  KhDev<uint32_t> d_flags;  // per tensor: some word is not exact in the format being built
   int rc;
   if ((rc = w.alloc.alloc(bytes + 4096)) != KH_OK || (rc = d_flags.alloc((size_t)nt)) != KH_OK) {
     w16_release(m);
@@ -98,127 +88,97 @@ int w16_create(kh_model* m) {
   w.arena = (char*)(((uintptr_t)w.alloc.get() + 4095) & ~(uintptr_t)4095);
   w.layers.resize((size_t)c.layer_num);
   hipStream_t s = m->stream;
-  hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * (size_t)nt, s);
-  if (e == hipSuccess) e = hipEventRecord(m->ev0, s);
-  size_t K[7], M[7], off = 0;
+  size_t K[7], M[7];
   layer_dims(c.dim, c.hidden_dim, c.kv_dim, K, M);
-  auto build = [&](const void* src, size_t elems, int tensor) -> const void* {
-    char* dst = w.arena + off;
-    off += pad256(2 * elems);
-    const size_t n4 = elems / 4, need = (n4 + KH_WG - 1) / KH_WG;
-    hipLaunchKernelGGL(k_w16_build, dim3((unsigned)(need < 4096 ? (need ? need : 1) : 4096)), dim3(KH_WG), 0, s,
-                       (const u32x4*)src, (u32x2*)dst, n4, d_flags + tensor);
-    return dst;
+  // one pass of a build kernel over every matrix -> KH_OK and *first = the first inexact tensor (-1: none)
+  auto build_all = [&](auto kernel, int* first) -> int {
+    size_t off = 0;
+    hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * (size_t)nt, s);
+    if (e == hipSuccess) e = hipEventRecord(m->ev0, s);
+    auto build = [&](const void* src, size_t elems, int tensor) -> const void* {
+      char* dst = w.arena + off;
+      off += pad256(2 * elems);
+      const size_t n4 = elems / 4, need = (n4 + KH_WG - 1) / KH_WG;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)(need < 4096 ? (need ? need : 1) : 4096)), dim3(KH_WG), 0, s,
+                         (const u32x4*)src, (u32x2*)dst, n4, d_flags + tensor);
+      return dst;
+    };
+    for (int l = 0; l < c.layer_num && e == hipSuccess; ++l) {
+      const LayerW& W = m->layers[(size_t)l];
+      const void* src[7] = {W.wq.w, W.wk.w, W.wv.w, W.wo.w, W.w1.w, W.w2.w, W.w3.w};
+      const void* dst[7];
+      for (int i = 0; i < 7; ++i) dst[i] = build(src[i], K[i] * M[i], 7 * l + i);
+      w.layers[(size_t)l] = kh_model::W16::Layer{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5], dst[6]};
+    }
+    w.cls = build(m->cls.w, (size_t)c.vocab_size * (size_t)c.dim, nt - 1);  // tok_emb when the classifier is tied
+    std::vector<uint32_t> flags((size_t)nt, 0);
+    if (e == hipSuccess) e = hipEventRecord(m->ev1, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    int r = e == hipSuccess ? kh_launch_status() : (int)e;
+    if (r == KH_OK && off != bytes) r = KH_ERR_INTERNAL;
+    if (r != KH_OK) return r;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, m->ev0, m->ev1) == hipSuccess) w.build_us += ms * 1000.f;
+    *first = -1;
+    for (int t = 0; t < nt && *first < 0; ++t)
+      if (flags[(size_t)t]) *first = t;
+    return KH_OK;
   };
-  for (int l = 0; l < c.layer_num && e == hipSuccess; ++l) {
-    const LayerW& W = m->layers[(size_t)l];
-    const void* src[7] = {W.wq.w, W.wk.w, W.wv.w, W.wo.w, W.w1.w, W.w2.w, W.w3.w};
-    const void* dst[7];
-    for (int i = 0; i < 7; ++i) dst[i] = build(src[i], K[i] * M[i], 7 * l + i);
-    w.layers[(size_t)l] = kh_model::W16::Layer{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5], dst[6]};
+  int first = -1, first_f16 = -1, format = KH_W16_BF16;
+  rc = build_all(k_w16_build, &first);
+  if (rc == KH_OK && first >= 0 && try_f16) {
+    format = KH_W16_F16;
+    rc = build_all(k_h16_build, &first_f16);
   }
-  w.cls = build(m->cls.w, (size_t)c.vocab_size * (size_t)c.dim, nt - 1);  // tok_emb when the classifier is tied
-  std::vector<uint32_t> flags((size_t)nt, 0);
-  if (e == hipSuccess) e = hipEventRecord(m->ev1, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  rc = e == hipSuccess ? kh_launch_status() : (int)e;
-  if (rc == KH_OK && off != bytes) rc = KH_ERR_INTERNAL;
   if (rc != KH_OK) {
     w16_release(m);
     return rc;
   }
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, m->ev0, m->ev1) == hipSuccess) w.build_us = ms * 1000.f;
-  w.bytes = bytes;
-  for (int t = 0; t < nt; ++t)
-    if (flags[(size_t)t]) {
-      w.first_inexact = t;
-      break;
-    }
-  if (w.first_inexact >= 0) {  // all or nothing: the model streams fp32 as if the flag were not set
+  w.first_inexact = first;
+  w.first_inexact_f16 = first_f16;
+  if (format == KH_W16_BF16 ? first >= 0 : first_f16 >= 0) {  // all or nothing: the model streams fp32 as if no flag were set
     w16_release(m);
     w.state = -1;
-    w.bytes = 0;
     return KH_OK;
   }
-  w16_configure(m);
+  w.bytes = bytes;
+  w.format = format;
+  if (format == KH_W16_F16)
+    h16_configure(m);
+  else
+    w16_configure_fmt<KH_W16_BF16>(m);
   w.classes = classes;
   w.pass_classes = classes & w16_pass_mask();
   w.state = 1;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
-    fprintf(stderr, "[kh] W16: %.1f MiB copy of %d matrices in %.0f us, classes 0x%x, passes 0x%x\n",
-            (double)bytes / (1 << 20), nt, (double)w.build_us, (unsigned)classes, (unsigned)w.pass_classes);
+    fprintf(stderr, "[kh] W16: %.1f MiB %s copy of %d matrices in %.0f us, classes 0x%x, passes 0x%x\n",
+            (double)bytes / (1 << 20), format == KH_W16_F16 ? "fp16" : "bf16", nt, (double)w.build_us,
+            (unsigned)classes, (unsigned)w.pass_classes);
   return KH_OK;
 }
 
-// ---- the launches ---------------------------------------------------------------------------
-// f(U, MV, SP) from the fp32 lists of a kernel (pick_fused without its QUANT level: a W16 kernel has no int8 form, and
-// walking both levels would compile it for the int8 values of U as well)
-template <class US, class MVS, class SPS, class F>
-static void pick_w16(int u, int mv, int sp, F&& f) {
-  kh_pick_ge(US{}, u, [&](auto U) {
-    kh_pick(MVS{}, mv, [&](auto MV) { kh_pick(SPS{}, sp, [&](auto SP) { f(U, MV, SP); }); });
-  });
-}
+// ---- the launches (kh_w16_launch.h) ------------------------------------------------------------
+// This translation unit compiles the _w16 kernels; an fp16-format copy goes to kh_model_h16.hip, which compiles the
+// _h16 kernels from the same launch text.
+static inline bool f16_copy(const kh_model* m) { return m->w16.format == KH_W16_F16; }
 void w16_launch_qkv(kh_model* m, int l, const KhQkvArgs& fp32) {
-  const kh_config& c = m->cfg;
-  KhQkvArgs a = fp32;
-  const kh_model::W16::Layer& W = m->w16.layers[(size_t)l];
-  a.wq.w = W.wq;
-  a.wk.w = W.wk;
-  a.wv.w = W.wv;
-  const kh_model::Shape& sh = m->sh_qkv;
-  pick_w16<FusedU<false>, FusedMV, QkvSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split, [&](auto U, auto MV, auto SP) {
-    kh_launch(KH_KERNEL(k_qkv_w16, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(false, c.dim), m->stream, a);
-  });
+  f16_copy(m) ? h16_launch_qkv(m, l, fp32) : w16_qkv_fmt<KH_W16_BF16>(m, l, fp32);
 }
 void w16_launch_wo(kh_model* m, int l, const KhGemvResArgs& fp32) {
-  const kh_config& c = m->cfg;
-  KhGemvResArgs a = fp32;
-  a.w.w = m->w16.layers[(size_t)l].wo;
-  const kh_model::Shape& sh = m->sh_wo;
-  pick_w16<FusedU<false>, FusedMV, GemvResSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split, [&](auto U, auto MV, auto SP) {
-    kh_launch(KH_KERNEL(k_gemv_res_w16, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(false, c.dim), m->stream, a);
-  });
+  f16_copy(m) ? h16_launch_wo(m, l, fp32) : w16_wo_fmt<KH_W16_BF16>(m, l, fp32);
 }
 void w16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& fp32) {
-  const kh_config& c = m->cfg;
-  KhWoCombArgs a = fp32;
-  a.g.w.w = m->w16.layers[(size_t)l].wo;
-  const kh_model::Shape& sh = m->sh_wo;
-  pick_w16<FusedU<false>, WoCombMV, GemvResSP>(sh.u, c.dim <= 2 * 4 * sh.wg ? 2 : 4, sh.split, [&](auto U, auto MV, auto SP) {
-    kh_launch(KH_KERNEL(k_wo_comb_w16, U, MV, SP), sh.grid, sh.wg, comb_lds_bytes(false, c.dim, c.head_num), m->stream, a);
-  });
+  f16_copy(m) ? h16_launch_wo_comb(m, l, fp32) : w16_wo_comb_fmt<KH_W16_BF16>(m, l, fp32);
 }
 void w16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& fp32) {
-  const kh_config& c = m->cfg;
-  KhFfn13Args a = fp32;
-  a.w1.w = m->w16.layers[(size_t)l].w1;
-  a.w3.w = m->w16.layers[(size_t)l].w3;
-  const kh_model::Shape& sh = m->sh_ffn;
-  pick_w16<FusedU<false>, FusedMV, NoSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto U, auto MV, auto) {
-    kh_launch(KH_KERNEL(k_ffn13_w16, U, MV), sh.grid, sh.wg, fused_lds_bytes(false, c.dim), m->stream, a);
-  });
+  f16_copy(m) ? h16_launch_ffn13(m, l, fp32) : w16_ffn13_fmt<KH_W16_BF16>(m, l, fp32);
 }
 void w16_launch_w2(kh_model* m, int l, const KhGemvResArgs& fp32) {
-  const kh_config& c = m->cfg;
-  KhGemvResArgs a = fp32;
-  a.w.w = m->w16.layers[(size_t)l].w2;
-  const kh_model::Shape& sh = m->sh_w2;
-  pick_w16<GemvResU<false>, GemvResMV, GemvResSP>(sh.u, kh_stage_maxv(c.hidden_dim, sh.wg), sh.split,
-                                             [&](auto U, auto MV, auto SP) {
-    kh_launch(KH_KERNEL(k_gemv_res_w16, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(false, c.hidden_dim), m->stream, a);
-  });
+  f16_copy(m) ? h16_launch_w2(m, l, fp32) : w16_w2_fmt<KH_W16_BF16>(m, l, fp32);
 }
 void w16_launch_cls(kh_model* m, const KhClsArgs& fp32) {
-  const kh_config& c = m->cfg;
-  KhClsArgs a = fp32;
-  a.wcls.w = m->w16.cls;
-  const kh_model::Shape& sh = m->sh_cls;
-  pick_w16<FusedU<false>, FusedMV, NoSP>(sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto U, auto MV, auto) {
-    kh_launch(KH_KERNEL(k_cls_w16, U, MV), sh.grid, sh.wg, cls_lds_bytes(false, c.dim), m->stream, a);
-  });
+  f16_copy(m) ? h16_launch_cls(m, fp32) : w16_cls_fmt<KH_W16_BF16>(m, fp32);
 }
 
 }  // namespace khm
@@ -243,5 +203,7 @@ extern "C" int kh_model_w16_info(kh_model* m, int64_t* out) {
   out[3] = m->w16.classes;
   out[4] = m->w16.first_inexact;
   out[5] = m->w16.pass_classes;
+  out[6] = m->w16.format == KH_W16_F16;
+  out[7] = m->w16.first_inexact_f16 + 1;
   return KH_OK;
 }

@@ -19,15 +19,16 @@
 // B-token FMA of one W16 register chunk: the two rows' words of a slot are widened ONCE (bit operations, no convert
 // instruction) and reused by all B tokens, as the int8 overload reuses its converted tile; per token the two fma4 of
 // the fp32 overload, in its order and under its guard (GemvW16::load clamps the address of the lanes it skips).
-template <int U, int B>
-__device__ __forceinline__ void fma_chunk_b(const RegsW16<U>& r, const f32x4* xs, int xstride, int c0, int M4,
+// (FMT is deduced from the tile; for KH_W16_F16 the widening is four exact conversions per row, once per slot as well.)
+template <int U, int B, int FMT>
+__device__ __forceinline__ void fma_chunk_b(const RegsW16<U, FMT>& r, const f32x4* xs, int xstride, int c0, int M4,
                                             int lane, float (&a0)[B], float (&a1)[B]) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int idx = c0 + u * KH_WAVE + lane;
     if (idx < M4) {
-      const f32x4 w0 = GemvW16<U>::widen(r.v0[u]);
-      const f32x4 w1 = GemvW16<U>::widen(r.v1[u]);
+      const f32x4 w0 = GemvW16<U, FMT>::widen(r.v0[u]);
+      const f32x4 w1 = GemvW16<U, FMT>::widen(r.v1[u]);
 #pragma unroll
       for (int b = 0; b < B; ++b) {
         const f32x4 xv = xs[(size_t)b * xstride + idx];
@@ -64,4 +65,32 @@ template <int B>
 __global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls_w16(const KhPfClsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   pf_cls_body<GemvW16<KH_PF_U_W16>, B>(a, smem_raw);
+}
+
+// The same five on an fp16-format copy (KH_FLAG_W16_F16): the bodies and instantiation lists of the twins above on
+// GemvW16<KH_PF_U_W16, KH_W16_F16>.  Stems of their own, so the _w16 names and sets stay what they were.
+template <int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv_h16(const KhPfQkvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_qkv_body<GemvW16<KH_PF_U_W16, KH_W16_F16>, SPLIT, B>(a, PfRunAddr{a.pos0, a.nvalid}, smem_raw);
+}
+template <int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_seq_qkv_h16(const KhSeqQkvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_qkv_body<GemvW16<KH_PF_U_W16, KH_W16_F16>, SPLIT, B>(a.a, PfLaneAddr{a.lanes}, smem_raw);
+}
+template <int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_ffn13_h16(const KhPfFfn13Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_ffn13_body<GemvW16<KH_PF_U_W16, KH_W16_F16>, B>(a, smem_raw);
+}
+template <int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_gemv_res_h16(const KhPfGemvResArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_gemv_res_body<GemvW16<KH_PF_U_W16, KH_W16_F16>, SPLIT, B>(a, smem_raw);
+}
+template <int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls_h16(const KhPfClsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  pf_cls_body<GemvW16<KH_PF_U_W16, KH_W16_F16>, B>(a, smem_raw);
 }

@@ -334,6 +334,15 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_w16_info(self._h, out), "kh_model_w16_info")
         return {"classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[5] >> i & 1]}
 
+    def w16_format(self) -> dict:
+        """The format of the 16-bit weight copy (kh_model_w16_info, slots 6 and 7): {"format": None (no live copy),
+        "bf16" or "fp16" (_ffi.KH_FLAG_W16_F16 on an image that is fp16-exact but not bf16-exact),
+        "first_inexact_fp16": the first tensor that is not fp16-exact, indexed as w16_info()["first_inexact"]; -1 when
+        fp16 was not tried or every tensor passed}."""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_w16_info(self._h, out), "kh_model_w16_info")
+        return {"format": None if out[0] != 1 else ("fp16" if out[6] else "bf16"), "first_inexact_fp16": int(out[7]) - 1}
+
     def cls_screen_probe(self, x: np.ndarray) -> dict:
         """One screened step and one full-classifier step on the residual vector x[dim], without advancing
         (kh_model_cls_screen_probe, tests): the two tokens, the candidate rows re-scored, whether the step overflowed,

@@ -12,7 +12,7 @@
 //               [--theta 10000] [--eps 1e-5] [--steps 128] [--prompt 1,263] [--stop 2]
 //               [--exec graph|fused|unfused] [--max-seq-len N] [--device 0]
 //               [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json [--hf-spaces]] [--text "a"]
-//               [--exact-prefill] [--fenced-merge] [--w16]
+//               [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16]
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
@@ -23,6 +23,8 @@
 // prompt tokens/s).  --fenced-merge = KH_FLAG_ATTN_MERGE_FENCED.  The self-checks of kh_model_create_* are printed.
 // --w16 = KH_FLAG_W16: decode a bf16-exact fp32 image from a 16-bit copy of its matrices, bit for bit (an image that is
 // not bf16-exact decodes as without the flag); prints kh_model_w16_info, the pass class mask included.
+// --w16-f16 = KH_FLAG_W16_F16: the same for an image that is bf16-exact OR fp16-exact (Llama-2's fp16 checkpoints); the
+// format of the copy is printed.
 // --temperature / --top-k / --top-p / --seed: seeded sampling instead of the argmax (kh_model_set_sampling; the
 // reference's demo is greedy, which stays the default).
 // --repeat-penalty / --presence-penalty / --frequency-penalty over the last --repeat-last-n fed tokens (0: all of
@@ -78,7 +80,7 @@ static void usage() {
                "usage: kuiper_demo model.bin [--family llama|qwen2] [--quant] [--rope interleaved|half]\n"
                "       [--theta F] [--eps F] [--steps N] [--prompt id,id,...] [--stop id,id] [--exec graph|fused|unfused]\n"
                "       [--max-seq-len N] [--device D] [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json\n"
-               "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge] [--w16]\n"
+               "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16]\n"
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
@@ -133,6 +135,7 @@ int main(int argc, char** argv) {
     else if (a == "--exact-prefill") o.flags |= KH_FLAG_PREFILL_EXACT;
     else if (a == "--fenced-merge") o.flags |= KH_FLAG_ATTN_MERGE_FENCED;
     else if (a == "--w16") o.flags |= KH_FLAG_W16;
+    else if (a == "--w16-f16") o.flags |= KH_FLAG_W16_F16;
     else if (a == "--temperature") samp.temperature = (float)std::atof(next());
     else if (a == "--top-k") samp.top_k = std::atoi(next());
     else if (a == "--top-p") samp.top_p = (float)std::atof(next());
@@ -251,15 +254,16 @@ int main(int argc, char** argv) {
   std::fprintf(stderr, "self-checks: int8 ring kernels %d, attention split merge %d; prompt phase: %s\n", c.ring_selftest,
                c.attn_merge_selftest, (o.flags & KH_FLAG_PREFILL_EXACT) ? "exact (bit-identical to token-by-token)"
                                                                         : "GEMM for 17+ tokens (fp32 round-off)");
-  if (o.flags & KH_FLAG_W16) {
+  if (o.flags & (KH_FLAG_W16 | KH_FLAG_W16_F16)) {
     int64_t w[8] = {0};
     kh_model_w16_info(m, w);
-    // state: 0 not applicable (int8), 1 on, -1 the image is not bf16-exact, -2 self-check failed (both: fp32 decode)
+    // state: 0 not applicable (int8), 1 on, -1 the image is not exact in a format asked for, -2 self-check failed (both:
+    // fp32 decode); format: of the live copy; w[7]: 1 + the first tensor that is not fp16-exact (0: not tried / none)
     // pass classes: whose B-token passes (prefill, score, verify, sequence slots) read the copy too (hook KH_W16_PASS)
-    std::fprintf(stderr, "W16: state %lld, copy %.2f GB built in %.2f ms, launch classes 0x%llx, pass classes 0x%llx, "
-                 "first inexact tensor %lld\n",
-                 (long long)w[0], (double)w[1] / 1e9, (double)w[2] / 1e3, (unsigned long long)w[3],
-                 (unsigned long long)w[5], (long long)w[4]);
+    std::fprintf(stderr, "W16: state %lld, format %s, copy %.2f GB built in %.2f ms, launch classes 0x%llx, pass classes "
+                 "0x%llx, first inexact tensor %lld (bf16) %lld (fp16)\n",
+                 (long long)w[0], w[0] != 1 ? "none" : (w[6] ? "fp16" : "bf16"), (double)w[1] / 1e9, (double)w[2] / 1e3,
+                 (unsigned long long)w[3], (unsigned long long)w[5], (long long)w[4], (long long)w[7] - 1);
   }
   rc = kh_model_set_sampling(m, &samp);
   if (rc != KH_OK) {
