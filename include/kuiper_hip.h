@@ -616,6 +616,31 @@ typedef struct kh_lookup_stats { int32_t passes, drafted, accepted, plain_steps;
 int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
                              const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts,
                              int32_t* h_words, int32_t* n_words, float* h_elapsed_ms, kh_lookup_stats* stats);
+
+/* The two calls above under the model's own settings: kh_model_set_sampling, _penalties, _logit_bias and _logprobs.
+ * kh_model_verify_as_set is kh_model_verify's pass with h_next[i] = what a loop of kh_model_predict(.., KH_EXEC_FUSED)
+ * under the same settings returns at position pos0 + i after feeding h_tokens[0..i]: row i of the pass's logits is
+ * processed (penalties, bias) over the fed-token record up to pos0 + i, with this pass's own tokens at pos0 .. pos0 + i;
+ * then the first maximum of the processed row; then, where temperature > 0, the draw with counter pos0 + i.  *n_accept
+ * is defined as above, on these picks: a draft is accepted where it EQUALS the pick.  The draw depends on (seed,
+ * position) and the logits only, and the logits are bit-identical to the token loop's, so h_next[0..a] are exactly that
+ * loop's tokens - no rejection sampling, no tolerance; a wrong draft costs time, never a word.
+ * Afterwards: K/V rows and decode state as behind kh_model_verify.  The fed-token record holds h_tokens[0..a] at pos0 ..
+ * pos0 + a, h_next[a] at pos0 + a + 1 (the next step's penalty window reads it, as behind a batch-1 step) and -1 above.
+ * With log-probs on, the records of pos0 .. pos0 + a are bit for bit those of the token loop - the pick, its log-prob
+ * under the processed logits, the top-N - and those of pos0 + a + 1 .. pos0 + n - 1 are "none".  The logits buffer of
+ * kh_model_get_logits is not written.  Launches: the pass, k_pf_cls, then k_spec_tail and k_spec_accept_set (behind
+ * k_spec_hist with a penalty or bias on); with NOTHING on - greedy, neutral penalties, no bias, log-probs off - exactly
+ * kh_model_verify's launches and results, and nothing more is allocated.  Error codes: kh_model_verify's.
+ * kh_model_generate_lookup_as_set is kh_model_generate_lookup's loop and contract with that pass in place of
+ * kh_model_verify's and without the greedy-only refusal (KH_ERR_UNSUPPORTED is left for the geometries): the words, the
+ * log-prob records of the sampled positions and the K/V rows are kh_model_generate_until's under the same settings.  The
+ * plain steps of a miss run on the step graphs with the tail the settings select. */
+int kh_model_verify_as_set(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
+                           int32_t* n_accept);
+int kh_model_generate_lookup_as_set(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
+                                    const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts,
+                                    int32_t* h_words, int32_t* n_words, float* h_elapsed_ms, kh_lookup_stats* stats);
 /* The drafter itself (host only, no device; csrc/kh_lookup.h), stateless.  For g = min(ngram_max, n_seq) down to
  * ngram_min, with key = the last g tokens of seq: (1) the EARLIEST j with hint[j .. j+g) == key and j + g < n_hint
  * drafts hint[j+g ..]; (2) else the MOST RECENT j with j + g <= n_seq - 1 and seq[j .. j+g) == key drafts seq[j+g ..];

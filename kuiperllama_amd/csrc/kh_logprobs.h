@@ -171,6 +171,54 @@ __device__ __forceinline__ void kh_logprobs_core(KhSampSmem& s, KhLpSmem& t, con
   }
 }
 
+// ---- the tail of one row of a B-token pass (kh_seq.h: k_seq_tail, kh_spec.h: k_spec_tail): k_sample_lp's chain in its
+// order, one workgroup of KH_SAMP_THREADS threads per row, every argument uniform.
+//   1. pp says anything: kh_logit_process_core in place on lg[0 .. vocab) over hist[.. pos] (hist[j] = the token fed at
+//      the sequence's position j) with the bias list and cnt[vocab] (zero before and after);
+//   2. the first maximum of the processed row (kh_samp_row_amax);
+//   3. the pick: the sampler core with counter pos where p.temperature > 0, else that maximum;
+//   4. top_n >= 0: the record at index `rec` of the record arrays - the pick, its log-prob and the top top_n of the
+//      logits the pick was made from; entries from top_n on are "none" (-1, NaN), as k_sample_lp leaves them.
+// Returns the pick in every thread.  LDS: KhSampSmem + KhLpSmem, as k_sample_lp.  Inlined, like the cores.
+struct KhTailRecs {
+  int32_t* token;    // [rows]
+  float* lp;         // [rows]
+  int32_t* top_ids;  // [rows][KH_LOGPROBS_TOP]
+  float* top_lp;     // [rows][KH_LOGPROBS_TOP]
+};
+__device__ __forceinline__ int kh_tail_chain(float* lg, int vocab, const int32_t* hist, int pos, const KhProcParams pp,
+                                             const int32_t* bias_ids, const float* bias, int32_t* cnt,
+                                             const KhSampParams p, int top_n, const KhTailRecs r, int rec) {
+  __shared__ KhSampSmem s;
+  __shared__ KhLpSmem t;
+  __shared__ float s_max;
+  __shared__ int s_idx;
+  if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0)  // uniform
+    kh_logit_process_core(lg, vocab, hist, pos, pp, bias_ids, bias, cnt);
+  float v;
+  int idx;
+  kh_samp_row_amax(lg, vocab, s.red, s.red_i, v, idx);
+  if (threadIdx.x == 0) {
+    s_max = v;
+    s_idx = idx;
+  }
+  __syncthreads();
+  const float lmax = s_max;
+  int pick = s_idx;
+  if (p.temperature > 0.f) pick = kh_sample_core(s, lg, vocab, lmax, p, (uint32_t)pos);  // uniform
+  if (top_n >= 0) {
+    top_n = min(top_n, min(KH_LOGPROBS_TOP, vocab));
+    const size_t r0 = (size_t)rec * KH_LOGPROBS_TOP;
+    kh_logprobs_core(s, t, lg, vocab, lmax, pick, top_n, nullptr, r.lp + rec, r.top_ids + r0, r.top_lp + r0);
+    if (threadIdx.x == 0) r.token[rec] = pick;
+    if ((int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
+      r.top_ids[r0 + threadIdx.x] = -1;
+      r.top_lp[r0 + threadIdx.x] = __uint_as_float(0xffffffffu);
+    }
+  }
+  return pick;
+}
+
 // ---- operator: one workgroup per row of logits[n_rows][n]
 static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_logprobs_op(const float* logits, int n, const int32_t* ids,
                                                                          int top_n, float* lse, float* lp,

@@ -157,6 +157,9 @@ struct kh_model {
   // device and its pinned mirror; one group, made by the first verify pass
   KhDev<int32_t> d_spec;
   KhPin<int32_t> h_spec_pin;
+  // ... under the model's settings (kh_model_verify_as_set; k_spec_tail): the processing core's counters per ROW of the
+  // pass, [KH_PF_BMAX][vocab], zeroed once (the core re-arms them); made by the first such pass with processors on
+  KhDev<int32_t> d_spec_cnt;
   // Sequence slots (kh_model_seq_slots, kh_model_seq.hip): the cache rows cut into seq_slots equal regions of
   // cache_len / seq_slots rows - bookkeeping, no kernel reads it.  Device tables with one entry per slot, one group
   // made by the first seq pass: the token the slot's sequence feeds next and its sampling parameters; the words of every
@@ -489,12 +492,15 @@ int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t po
 // Full-depth passes (kh_model_score, kh_model_verify): the geometries they run on, and the tokens of one pass
 bool full_depth_supported(const kh_model* m);
 int verify_width(const kh_model* m);
-// the buffers of a verify pass that reaches cache rows [0, rows): before the first verify_enqueue of a call
-int verify_prepare(kh_model* m, int rows);
+// the buffers of a verify pass that reaches cache rows [0, rows): before the first verify_enqueue of a call.  as_set:
+// of a pass under the model's settings - the row counters too, where the settings need them
+int verify_prepare(kh_model* m, int rows, bool as_set = false);
 // One verify pass of toks[0 .. n), 1 <= n <= verify_width, at positions pos0 ..: the full-depth pass, k_pf_cls,
 // k_spec_pick, k_spec_accept and the copy of the result block into m->h_spec_pin {a, pick[0 .. n)}, all enqueued on the
 // model stream; the caller synchronises before it reads the block.  Arguments are the caller's to check.
-int verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0);
+// as_set: the picks are made under the model's sampler, penalties, logit bias and log-probs - where any of them is on,
+// k_spec_hist, k_spec_tail and k_spec_accept_set take the place of the last two launches; where none is, nothing changes.
+int verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool as_set = false);
 // Sequence slots (kh_model_seq.hip drives these; arguments are the caller's to check).  seq_prepare: the buffers of
 // a pass, before the first enqueue of a call.  seq_prefill_enqueue: kh_model_prefill's passes for n tokens at
 // positions pos0 .. of the sequence whose position 0 is cache row row0.  seq_pass_enqueue: one full-depth pass over

@@ -1,6 +1,6 @@
 // kh_model_prefill.hip — prompt phase of the model level: the B-token VALU pass (kh_prefill.h, bit-identical to
 // token-by-token; ONE layer driver, launch_pf_pass) and what runs on it - the prompt prefill, sequence scoring
-// (kh_model_score: k_pf_cls, k_score_lp), the verify pass of speculative greedy decode (kh_model_verify: k_pf_cls,
+// (kh_model_score: k_pf_cls, k_score_lp), the verify pass of speculative decode (kh_model_verify[_as_set]: k_pf_cls,
 // kh_spec.h) and the pass over lanes of different sequences (kh_seq.h; kh_model_seq.hip drives it); for a W16 model
 // the launch classes of its pass mask run on the 16-bit copy (kh_w16_pass.h, the w16_pf_* launchers) - and the
 // fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h), which always reads fp32.  The
@@ -730,11 +730,18 @@ extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, i
 
 // ---- speculative greedy decode: the verify pass (kh_spec.h) ---------------------------------------------------------
 int khm::verify_width(const kh_model* m) { return prefill_batch(m); }
-int khm::verify_prepare(kh_model* m, int rows) {
+int khm::verify_prepare(kh_model* m, int rows, bool as_set) {
   int rc;
   if ((rc = kv_ensure(m, rows)) != KH_OK) return rc;
   if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
   if ((rc = ensure_score_buffers(m)) != KH_OK) return rc;
+  if (as_set && m->proc_on && !m->d_spec_cnt) {
+    const size_t n = (size_t)KH_PF_BMAX * (size_t)m->cfg.vocab_size;
+    KhDev<int32_t> cnt;
+    if ((rc = cnt.alloc(n)) != KH_OK) return rc;
+    KH_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, m->stream));  // once: the core re-arms them
+    m->d_spec_cnt = std::move(cnt);
+  }
   if (m->d_spec) return KH_OK;
   KhDev<int32_t> spec;
   KhPin<int32_t> pin;
@@ -743,23 +750,50 @@ int khm::verify_prepare(kh_model* m, int rows) {
   m->h_spec_pin = std::move(pin);
   return KH_OK;
 }
-int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0) {
+int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool as_set) {
   const kh_config& c = m->cfg;
   const int B = prefill_batch(m);
-  launch_pf_pass(m, pf_run(toks, n, pos0, B, /*full_depth=*/true));
-  launch_pf_cls(m, n, B);
-  launch_log("k_spec_pick");
-  hipLaunchKernelGGL(k_spec_pick, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, (const float*)m->pf_logits,
-                     c.vocab_size, (long long)m->pf_vstride, m->d_spec + 1);
+  // the tail of the pass under the settings; with none of them on the greedy pair below is that tail
+  const bool tail = as_set && (m->samp_on || m->proc_on || m->lp_top_n >= 0);
   KhSpecAcceptArgs t;
-  t.res = m->d_spec;
+  t.hist = m->d_hist;
+  t.hist_cap = m->hist_cap;
   for (int b = 0; b < KH_PF_BMAX; ++b) t.fed[b] = b < n ? toks[b] : -1;
   t.pos0 = pos0;
   t.n = n;
+  if (tail && m->proc_on) {  // the record the rows' windows read, ahead of them on the stream
+    launch_log("k_spec_hist");
+    hipLaunchKernelGGL(k_spec_hist, dim3(1), dim3(KH_WAVE), 0, m->stream, t);
+  }
+  launch_pf_pass(m, pf_run(toks, n, pos0, B, /*full_depth=*/true));
+  launch_pf_cls(m, n, B);
+  const bool records = tail && m->lp_top_n >= 0;
+  const KhTailRecs recs{m->d_lp_token, m->d_lp_lp, m->d_lp_top_ids, m->d_lp_top_lp};
+  if (tail) {
+    KhSpecTailArgs a;
+    a.logits = m->pf_logits;
+    a.vocab = c.vocab_size;
+    a.vstride = m->pf_vstride;
+    a.pos0 = pos0;
+    a.params = m->d_samp;
+    a.proc = m->proc_on ? (const KhProcParams*)m->d_proc : nullptr;
+    a.bias_ids = m->d_bias_ids;
+    a.bias = m->d_bias;
+    a.hist = m->d_hist;
+    a.cnt = m->d_spec_cnt;
+    a.top_n = records ? (const int32_t*)m->d_lp_top_n : nullptr;
+    a.recs = recs;
+    a.res = m->d_spec;
+    launch_log("k_spec_tail");
+    hipLaunchKernelGGL(k_spec_tail, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, a);
+  } else {
+    launch_log("k_spec_pick");
+    hipLaunchKernelGGL(k_spec_pick, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, (const float*)m->pf_logits,
+                       c.vocab_size, (long long)m->pf_vstride, m->d_spec + 1);
+  }
+  t.res = m->d_spec;
   t.words = m->d_words;
   t.words_cap = m->seq_cap;
-  t.hist = m->d_hist;
-  t.hist_cap = m->hist_cap;
   t.d_next = m->d_next;
   t.d_token = m->d_token;
   t.d_pos = m->d_pos;
@@ -767,8 +801,14 @@ int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0) {
   t.x = m->x;
   t.dim = c.dim;
   t.vocab = c.vocab_size;
-  launch_log("k_spec_accept");
-  hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(KH_WG), 0, m->stream, t);
+  if (tail) {
+    launch_log("k_spec_accept_set");
+    hipLaunchKernelGGL(k_spec_accept_set, dim3(1), dim3(KH_WG), 0, m->stream,
+                       KhSpecAcceptSetArgs{t, records ? recs : KhTailRecs{nullptr, nullptr, nullptr, nullptr}, m->lp_cap});
+  } else {
+    launch_log("k_spec_accept");
+    hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(KH_WG), 0, m->stream, t);
+  }
   KH_CHECK_HIP(hipMemcpyAsync(m->h_spec_pin, m->d_spec, sizeof(int32_t) * (size_t)(1 + n), hipMemcpyDeviceToHost,
                               m->stream));
   return kh_launch_status();
@@ -888,8 +928,8 @@ extern "C" int kh_model_verify_width(const kh_model* m, int32_t* width) {
   return KH_OK;
 }
 // One verify pass.  Eager launches on the model stream; every check before the first of them.
-extern "C" int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
-                               int32_t* n_accept) {
+static int verify_call(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
+                       int32_t* n_accept, bool as_set) {
   if (!m || !h_tokens || !h_next || !n_accept || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
@@ -897,14 +937,22 @@ extern "C" int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, 
   if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
-  if ((rc = verify_prepare(m, pos0 + n)) != KH_OK) return rc;
-  rc = verify_enqueue(m, h_tokens, n, pos0);
+  if ((rc = verify_prepare(m, pos0 + n, as_set)) != KH_OK) return rc;
+  rc = verify_enqueue(m, h_tokens, n, pos0, as_set);
   const hipError_t e = hipStreamSynchronize(m->stream);  // drained on every way out
   if (rc != KH_OK) return rc;
   if (e != hipSuccess) return (int)e;
   *n_accept = m->h_spec_pin[0];
   memcpy(h_next, m->h_spec_pin + 1, sizeof(int32_t) * (size_t)n);
   return KH_OK;
+}
+extern "C" int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
+                               int32_t* n_accept) {
+  return verify_call(m, h_tokens, n, pos0, h_next, n_accept, /*as_set=*/false);
+}
+extern "C" int kh_model_verify_as_set(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
+                                      int32_t* n_accept) {
+  return verify_call(m, h_tokens, n, pos0, h_next, n_accept, /*as_set=*/true);
 }
 
 // Time the prompt phase alone: n fed-only tokens at positions pos0.., HIP events on the model

@@ -1191,10 +1191,12 @@ extern "C" int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t*
 // kh_model_generate_until's graph form with the sampled part driven by draft + verify: at position p a draft of d >= 1
 // tokens costs one verify pass and yields a + 1 words, no draft costs miss_steps steps on the step graphs.  The host
 // reads the words behind either (the next draft needs them), so every iteration ends in a stream sync.
-extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
-                                        const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts,
-                                        int32_t* h_words, int32_t* n_words, float* h_elapsed_ms,
-                                        kh_lookup_stats* stats) {
+// as_set = false: greedy on the raw logits, any setting is refused.  as_set = true: the pass picks under the model's
+// settings (verify_enqueue) as the plain steps do (step_tail); a draft is accepted where it EQUALS that pick - the
+// seeded draw depends on (seed, position) and the logits alone - so the words are generate_until's either way.
+static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
+                               const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts, int32_t* h_words,
+                               int32_t* n_words, float* h_elapsed_ms, kh_lookup_stats* stats, bool as_set) {
   if (!m || !h_prompt || n_prompt <= 0 || total_steps <= 0 || !h_words || !n_words || n_stop < 0 ||
       (n_stop > 0 && !h_stop))
     return KH_ERR_INVALID_ARG;
@@ -1206,8 +1208,10 @@ extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, in
   if (total_steps > c.cache_len) return KH_ERR_RANGE;
   if (!tokens_in_vocab(m, h_prompt, n_prompt)) return KH_ERR_RANGE;
   if (!tokens_in_vocab(m, o.h_hint, o.n_hint)) return KH_ERR_RANGE;
-  // greedy on the raw logits only, and only where the verify pass runs: no silent fallback to generate_until
-  if (m->samp_on || m->proc_on || m->lp_top_n >= 0 || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  // only where the verify pass runs and, unless as_set, greedy on the raw logits only: no silent fallback to
+  // generate_until
+  if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  if (!as_set && (m->samp_on || m->proc_on || m->lp_top_n >= 0)) return KH_ERR_UNSUPPORTED;
   return kh_api_guard([&]() -> int {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     *n_words = 0;
@@ -1219,7 +1223,7 @@ extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, in
     };
     std::vector<int32_t> seq(h_prompt, h_prompt + n_prompt);  // seq[i] = the token of position i, as far as known
     seq.reserve((size_t)total_steps + KH_GRAPH_STEPS + 1);
-    if ((rc = verify_prepare(m, total_steps)) != KH_OK) return rc;
+    if ((rc = verify_prepare(m, total_steps, as_set)) != KH_OK) return rc;
     GenRun g;
     if ((rc = generate_begin(m, h_prompt, n_prompt, total_steps, KH_EXEC_GRAPH, &g)) != KH_OK) return fail(rc);
     const int width = verify_width(m);
@@ -1240,7 +1244,7 @@ extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, in
       }
       if (d > 0) {
         fed[0] = seq[(size_t)p];
-        if ((rc = verify_enqueue(m, fed, d + 1, p)) != KH_OK) return fail(rc);
+        if ((rc = verify_enqueue(m, fed, d + 1, p, as_set)) != KH_OK) return fail(rc);
         if (hipStreamSynchronize(m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
         const int a = m->h_spec_pin[0];
         for (int i = 0; i <= a && stop_at < 0; ++i) {
@@ -1293,4 +1297,18 @@ extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, in
     *n_words = n_out;
     return KH_OK;
   });
+}
+extern "C" int kh_model_generate_lookup(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
+                                        const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts,
+                                        int32_t* h_words, int32_t* n_words, float* h_elapsed_ms,
+                                        kh_lookup_stats* stats) {
+  return generate_lookup_run(m, h_prompt, n_prompt, total_steps, h_stop, n_stop, opts, h_words, n_words, h_elapsed_ms,
+                             stats, /*as_set=*/false);
+}
+extern "C" int kh_model_generate_lookup_as_set(kh_model* m, const int32_t* h_prompt, int32_t n_prompt,
+                                               int32_t total_steps, const int32_t* h_stop, int32_t n_stop,
+                                               const kh_lookup_opts* opts, int32_t* h_words, int32_t* n_words,
+                                               float* h_elapsed_ms, kh_lookup_stats* stats) {
+  return generate_lookup_run(m, h_prompt, n_prompt, total_steps, h_stop, n_stop, opts, h_words, n_words, h_elapsed_ms,
+                             stats, /*as_set=*/true);
 }

@@ -85,8 +85,9 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_pick(const KhSeq
   }
 }
 
-// The tail of a pass with per-sequence processors or log-probs: k_sample_lp's steps in its order, one workgroup per
-// lane on per-slot state.  Workgroup b, slot = slot[b], pos = pos[b], row = row[b]:
+// The tail of a pass with per-sequence processors or log-probs: k_sample_lp's steps in its order (steps 1 - 4 are
+// kh_logprobs.h: kh_tail_chain, which kh_spec.h: k_spec_tail runs too), one workgroup per lane on per-slot state.
+// Workgroup b, slot = slot[b], pos = pos[b], row = row[b]:
 //   1. proc[slot] says anything: kh_logit_process_core in place on row b of the logits, over the slot's history -
 //      hist is addressed by cache row like K/V, position p of the slot is hist[row - pos + p] - with the slot's bias
 //      list and the LANE's counters (lanes run side by side; cnt is zero before and after);
@@ -117,40 +118,14 @@ struct KhSeqTailArgs {
   int32_t* words;              // [cache_len] or null
 };
 static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_tail(const KhSeqTailArgs a) {
-  __shared__ KhSampSmem s;
-  __shared__ KhLpSmem t;
-  __shared__ float s_max;
-  __shared__ int s_idx;
   const int b = blockIdx.x;
   const int slot = a.lanes.slot[b], pos = a.lanes.pos[b], row = a.lanes.row[b];
-  float* lg = a.logits + (size_t)b * (size_t)a.vstride;
   const KhProcParams pp = a.proc[slot];
-  if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0)  // uniform
-    kh_logit_process_core(lg, a.vocab, a.hist + (row - pos), pos, pp, a.bias_ids + (size_t)slot * KH_SEQ_BIAS_MAX,
-                          a.bias + (size_t)slot * KH_SEQ_BIAS_MAX, a.cnt + (size_t)b * (size_t)a.vocab);
-  float v;
-  int idx;
-  kh_samp_row_amax(lg, a.vocab, s.red, s.red_i, v, idx);
-  if (threadIdx.x == 0) {
-    s_max = v;
-    s_idx = idx;
-  }
-  __syncthreads();
   const KhSampParams p = a.params[slot];
-  const float lmax = s_max;
-  int pick = s_idx;
-  if (p.temperature > 0.f) pick = kh_sample_core(s, lg, a.vocab, lmax, p, (uint32_t)pos);  // uniform
-  if (a.top_n >= 0) {
-    const int top_n = min(a.top_n, min(KH_LOGPROBS_TOP, a.vocab));
-    const size_t r0 = (size_t)row * KH_LOGPROBS_TOP;
-    kh_logprobs_core(s, t, lg, a.vocab, lmax, pick, top_n, nullptr, a.rec_lp + row, a.rec_top_ids + r0,
-                     a.rec_top_lp + r0);
-    if (threadIdx.x == 0) a.rec_token[row] = pick;
-    if ((int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
-      a.rec_top_ids[r0 + threadIdx.x] = -1;
-      a.rec_top_lp[r0 + threadIdx.x] = __uint_as_float(0xffffffffu);
-    }
-  }
+  const int pick = kh_tail_chain(a.logits + (size_t)b * (size_t)a.vstride, a.vocab, a.hist + (row - pos), pos, pp,
+                                 a.bias_ids + (size_t)slot * KH_SEQ_BIAS_MAX, a.bias + (size_t)slot * KH_SEQ_BIAS_MAX,
+                                 a.cnt + (size_t)b * (size_t)a.vocab, p, a.top_n,
+                                 {a.rec_token, a.rec_lp, a.rec_top_ids, a.rec_top_lp}, row);
   if (threadIdx.x == 0) {
     a.tok[slot] = pick;
     if (a.words) a.words[row] = pick;

@@ -6,9 +6,18 @@
 //   k_spec_accept  one workgroup: how many drafts the picks confirm, the words, the fed-token record and the decode
 //                  state of the step that follows - what k_sample leaves behind an advancing step.
 // A dependent launch, not a ticket and a last arriver: 1.55 us against a hand-over inside a launch.
+// Under the model's settings (kh_model_verify_as_set, kh_model_generate_lookup_as_set: a sampler, penalties, a logit
+// bias or log-probs on) three launches take their place:
+//   k_spec_hist        the pass's fed tokens into the fed-token record, ahead of the rows that read them
+//   k_spec_tail        one workgroup per position: k_sample_lp's chain on its row (kh_logprobs.h: kh_tail_chain) - the
+//                      processors over the record up to its own position, the maximum, the greedy pick or the seeded
+//                      draw with counter = position, the log-prob record.  What a batch-1 step picks on the same logits.
+//   k_spec_accept_set  k_spec_accept's duties on those picks, the record entry the next step's window reads and "none"
+//                      over the log-prob records of the rejected positions
 // gfx950 only.
 #pragma once
-#include "kh_sample.h"  // KH_SAMP_THREADS, kh_samp_row_amax
+#include "kh_logprobs.h"  // kh_tail_chain
+#include "kh_sample.h"    // KH_SAMP_THREADS, kh_samp_row_amax
 
 // pick[b] = first maximum of logits[b * stride .. + n), b = blockIdx.x (kh_samp_row_amax).  A row without a maximum
 // (every entry NaN) leaves 0x7fffffff, as k_sample does.
@@ -38,12 +47,13 @@ struct KhSpecAcceptArgs {
   float* x;                // residual stream: receives the embedding row of pick[a]
   int dim, vocab;
 };
-static __global__ __launch_bounds__(KH_WG) void k_spec_accept(const KhSpecAcceptArgs t) {
+// returns a in thread 0 (every other thread: 0); the embedding gather is the whole workgroup's
+static __device__ __forceinline__ int kh_spec_accept_body(const KhSpecAcceptArgs& t) {
   __shared__ int s_next;
+  int a = 0;
   if (threadIdx.x == 0) {
     const int n = t.n < KH_PF_BMAX ? t.n : KH_PF_BMAX;
     const int32_t* pick = t.res + 1;
-    int a = 0;
     while (a < n - 1 && pick[a] == t.fed[a + 1]) ++a;
     t.res[0] = a;
     for (int i = 0; i < n; ++i) {
@@ -63,5 +73,78 @@ static __global__ __launch_bounds__(KH_WG) void k_spec_accept(const KhSpecAccept
     const f32x4* src = (const f32x4*)(t.tok_emb + (size_t)nxt * t.dim);
     f32x4* dst = (f32x4*)t.x;
     for (int i = threadIdx.x; i < (t.dim >> 2); i += KH_WG) dst[i] = src[i];
+  }
+  return a;
+}
+static __global__ __launch_bounds__(KH_WG) void k_spec_accept(const KhSpecAcceptArgs t) { kh_spec_accept_body(t); }
+
+// ---- the same pass under the model's settings ------------------------------------------------------------------------
+// hist[pos0 + i] = fed[i], i < n: every row of k_spec_tail reads the record up to its own position, and one workgroup
+// cannot wait for another, so the entries are there before that launch
+static __global__ __launch_bounds__(KH_WAVE) void k_spec_hist(const KhSpecAcceptArgs t) {
+  const int i = threadIdx.x, pos = t.pos0 + i;
+  if (i < t.n && i < KH_PF_BMAX && pos >= 0 && pos < t.hist_cap) t.hist[pos] = t.fed[i];
+}
+
+// Workgroup b: kh_tail_chain on row b of the pass's logits, in place, as the batch-1 step at position pos0 + b runs it
+// on its own logits - history = the fed-token record (k_spec_hist wrote this pass's entries), counter = pos0 + b,
+// counters cnt[b][vocab] (rows run side by side; zero before and after), record = position pos0 + b.  The parameters
+// are the model's device copies (a null pointer: that setting was never made - neutral / greedy / no record).
+struct KhSpecTailArgs {
+  float* logits;               // [n][vstride], processed in place
+  int vocab, vstride;
+  int pos0;
+  const KhSampParams* params;  // kh_model_set_sampling's device copy, or null
+  const KhProcParams* proc;    // kh_model_set_penalties / _logit_bias's device copy, or null
+  const int32_t* bias_ids;
+  const float* bias;
+  const int32_t* hist;         // [hist_cap >= pos0 + n]
+  int32_t* cnt;                // [KH_PF_BMAX][vocab] (null while proc is)
+  const int32_t* top_n;        // kh_model_set_logprobs's device word, or null while log-probs are off
+  KhTailRecs recs;             // [rec_cap >= pos0 + n]
+  int32_t* res;                // res[1 + b] = pick
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_spec_tail(const KhSpecTailArgs a) {
+  const int b = blockIdx.x;
+  if (b >= KH_PF_BMAX) return;  // uniform
+  const int pos = a.pos0 + b;
+  const KhProcParams pp = a.proc ? *a.proc : KhProcParams{1.f, 0.f, 0.f, 0, 0};
+  const KhSampParams p = a.params ? *a.params : KhSampParams{};
+  const int top_n = a.top_n ? max(*a.top_n, 0) : -1;
+  const int pick = kh_tail_chain(a.logits + (size_t)b * (size_t)a.vstride, a.vocab, a.hist, pos, pp, a.bias_ids, a.bias,
+                                 a.cnt + (size_t)b * (size_t)a.vocab, p, top_n, a.recs, pos);
+  if (threadIdx.x == 0) a.res[1 + b] = pick;
+}
+
+// k_spec_accept, then what a batch-1 step leaves besides: hist[pos0 + a + 1] = pick[a] (the token the next step feeds;
+// its penalty window reads it) and the records of the rejected positions pos0 + a + 1 .. pos0 + n - 1 back to "none"
+struct KhSpecAcceptSetArgs {
+  KhSpecAcceptArgs t;
+  KhTailRecs recs;  // token == null: log-probs are off
+  int rec_cap;
+};
+static __global__ __launch_bounds__(KH_WG) void k_spec_accept_set(const KhSpecAcceptSetArgs s) {
+  __shared__ int s_a;
+  const int a0 = kh_spec_accept_body(s.t);
+  if (threadIdx.x == 0) {
+    const int at = s.t.pos0 + a0 + 1;
+    if (at < s.t.hist_cap) s.t.hist[at] = s.t.res[1 + a0];
+    s_a = a0;
+  }
+  __syncthreads();
+  if (!s.recs.token) return;  // uniform
+  const int n = s.t.n < KH_PF_BMAX ? s.t.n : KH_PF_BMAX;
+  const float none = __uint_as_float(0xffffffffu);
+  for (int i = s_a + 1; i < n; ++i) {
+    const int pos = s.t.pos0 + i;
+    if (pos >= s.rec_cap) break;
+    if (threadIdx.x == 0) {
+      s.recs.token[pos] = -1;
+      s.recs.lp[pos] = none;
+    }
+    if (threadIdx.x < KH_LOGPROBS_TOP) {
+      s.recs.top_ids[(size_t)pos * KH_LOGPROBS_TOP + threadIdx.x] = -1;
+      s.recs.top_lp[(size_t)pos * KH_LOGPROBS_TOP + threadIdx.x] = none;
+    }
   }
 }

@@ -501,25 +501,31 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_verify_width(self._h, C.byref(w)), "kh_model_verify_width")
         return int(w.value)
 
-    def verify(self, tokens: Sequence[int], pos0: int) -> Tuple[np.ndarray, int]:
+    def verify(self, tokens: Sequence[int], pos0: int, as_set: bool = False) -> Tuple[np.ndarray, int]:
         """One verify pass (kh_model_verify): feeds tokens[0] - known - and the drafts tokens[1:] at positions pos0 ..
         in one sweep of the weights.  Returns (next, n_accept): next[i] is the greedy pick at position pos0 + i given
         tokens[:i + 1]; the caller owns next[:n_accept + 1], exactly the tokens a loop of predict() returns, and the
-        decode state stands behind them."""
+        decode state stands behind them.  as_set (kh_model_verify_as_set): the picks are made under the model's
+        sampler, penalties, logit bias and log-probs - what a loop of predict() returns under the same settings -
+        and with log-probs on the records of the accepted positions are written."""
         n = len(tokens)
         nxt = np.full(max(n, 1), -1, np.int32)
         a = C.c_int32(-1)
-        _ffi.check(_ffi.lib().kh_model_verify(self._h, _i32_array(tokens), n, int(pos0),
-                                              nxt.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(a)), "kh_model_verify")
+        name = "kh_model_verify_as_set" if as_set else "kh_model_verify"
+        _ffi.check(getattr(_ffi.lib(), name)(self._h, _i32_array(tokens), n, int(pos0),
+                                             nxt.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(a)), name)
         return nxt[:n], int(a.value)
 
     def generate_lookup(self, prompt: Sequence[int], total_steps: int, stop: Sequence[int] = (), ngram_max: int = 4,
                         ngram_min: int = 1, miss_steps: int = 8,
-                        hint: Optional[Sequence[int]] = None) -> Tuple[List[int], float, dict]:
+                        hint: Optional[Sequence[int]] = None,
+                        as_set: bool = False) -> Tuple[List[int], float, dict]:
         """generate(exec="graph") with the sampled part driven by draft + verify (kh_model_generate_lookup): the same
         words, several per sweep of the weights wherever lookup_draft's guess - from the text so far and the optional
-        `hint`, the expected output - is right.  Greedy only.  Returns (words, elapsed_ms, stats) with stats =
-        {"passes", "drafted", "accepted", "plain_steps"}."""
+        `hint`, the expected output - is right.  Greedy only, unless as_set (kh_model_generate_lookup_as_set): then the
+        passes pick under the model's sampler, penalties, logit bias and log-probs, and the words and records are
+        generate()'s under the same settings.  Returns (words, elapsed_ms, stats) with stats = {"passes", "drafted",
+        "accepted", "plain_steps"}."""
         _ffi.sync_env()  # KH_PREFILL, KH_PG_*
         st, hn = list(stop or []), list(hint or [])
         hint_arr = _i32_array(hn)
@@ -529,9 +535,10 @@ class KuiperModel:
         n = C.c_int32(0)
         ms = C.c_float(0.0)
         stats = _ffi.LookupStats()
-        _ffi.check(_ffi.lib().kh_model_generate_lookup(self._h, _i32_array(prompt), len(prompt), total_steps,
-                                                       _i32_array(st), len(st), C.byref(opts), words, C.byref(n),
-                                                       C.byref(ms), C.byref(stats)), "kh_model_generate_lookup")
+        name = "kh_model_generate_lookup_as_set" if as_set else "kh_model_generate_lookup"
+        _ffi.check(getattr(_ffi.lib(), name)(self._h, _i32_array(prompt), len(prompt), total_steps, _i32_array(st),
+                                             len(st), C.byref(opts), words, C.byref(n), C.byref(ms), C.byref(stats)),
+                   name)
         return list(words[: n.value]), float(ms.value), stats.as_dict()
 
     # ---- sequence slots: several independent sequences per pass over the weights ---------------------------------

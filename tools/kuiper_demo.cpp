@@ -16,7 +16,8 @@
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
-//               [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N] [--share-prefix]
+//               [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]
+//               [--parallel N] [--best-of N] [--share-prefix]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -39,6 +40,9 @@
 // the weights wherever the text so far - or --hint id,id,..., the expected output - predicts the next tokens (n-grams
 // of up to ngram_max tokens, default 4).  Greedy only.  A line "lookup: passes P drafted D accepted A plain_steps S"
 // follows the words.
+// --lookup-as-set [ngram_max]: the same loop under --temperature / --seed, the penalties, --logit-bias and --logprobs
+// (kh_model_generate_lookup_as_set): a draft is accepted where it equals the pick the settings make, so the words and
+// the log-prob lines are those of the same run without lookup.
 // --parallel N: N samples of the one prompt, decoded together (kh_model_seq_slots / _seq_prefill / _seq_fork /
 // kh_model_generate_batch_from): the cache is cut into N slots, the prompt is prefilled once and forked, the seeds are
 // --seed, --seed + 1, ...; each sequence's ids are printed on a line of their own, then the aggregate "steps/s".
@@ -84,7 +88,8 @@ static void usage() {
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
-               "       [--lookup [ngram_max]] [--hint id,id,...] [--parallel N] [--best-of N] [--share-prefix]\n");
+               "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]\n"
+               "       [--parallel N] [--best-of N] [--share-prefix]\n");
 }
 
 int main(int argc, char** argv) {
@@ -102,6 +107,7 @@ int main(int argc, char** argv) {
   int logprobs = -1;  // --logprobs N (kh_model_set_logprobs)
   bool score = false;  // --score (kh_model_score)
   bool lookup = false;  // --lookup [ngram_max] (kh_model_generate_lookup)
+  bool lookup_as_set = false;  // --lookup-as-set [ngram_max] (kh_model_generate_lookup_as_set)
   kh_lookup_opts lk{0, 0, 0, nullptr, 0};
   int parallel = 0;  // --parallel N (kh_model_generate_batch)
   int best_of = 0;   // --best-of N (kh_model_generate_batch_ex, kh_seq_rank)
@@ -149,8 +155,9 @@ int main(int argc, char** argv) {
     else if (a == "--parallel") parallel = std::atoi(next());
     else if (a == "--best-of") best_of = std::atoi(next());
     else if (a == "--share-prefix") share_prefix = true;
-    else if (a == "--lookup") {
+    else if (a == "--lookup" || a == "--lookup-as-set") {
       lookup = true;
+      if (a == "--lookup-as-set") lookup_as_set = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') lk.ngram_max = std::atoi(argv[++i]);
     }
     else if (a == "--logit-bias") {
@@ -433,8 +440,9 @@ int main(int argc, char** argv) {
   if (lookup) {
     lk.h_hint = hint.empty() ? nullptr : hint.data();
     lk.n_hint = (int32_t)hint.size();
-    rc = kh_model_generate_lookup(m, prompt.data(), (int32_t)prompt.size(), steps, stop.data(), (int32_t)stop.size(),
-                                  &lk, words.data(), &n, &gpu_ms, &lks);
+    rc = (lookup_as_set ? kh_model_generate_lookup_as_set : kh_model_generate_lookup)(
+        m, prompt.data(), (int32_t)prompt.size(), steps, stop.data(), (int32_t)stop.size(), &lk, words.data(), &n,
+        &gpu_ms, &lks);
   } else {
     rc = kh_model_generate_until(m, prompt.data(), (int32_t)prompt.size(), steps, exec, stop.data(),
                                  (int32_t)stop.size(), words.data(), &n, &gpu_ms);
