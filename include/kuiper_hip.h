@@ -812,6 +812,41 @@ int kh_model_seq_get_logprobs(kh_model* m, int32_t slot, int32_t pos0, int32_t n
 int kh_seq_rank(int32_t n_seq, const float* h_lp, int32_t stride, const int32_t* first, const int32_t* n_words,
                 int32_t* order, double* mean_lp);
 
+/* Batched decode on the matrix cores: up to 64 sequences per weight pass (csrc/kh_seq_gemm.h).  The passes above share
+ * a sweep of the weights between 8 (4) lanes on the VALU; the `_gemm` forms put the lanes on the MFMA token dimension
+ * of kh_model_prefill_gemm's GEMMs - QKV with the lane's RoPE row and cache row, wo, the SwiGLU pair, w2 and the
+ * classifier - and run the attention and the tail of the 8-lane pass once per group of 8 lanes.  Opt-in: no other
+ * entry point routes here, and a model that never calls these allocates and launches nothing new.
+ * Contract: kh_model_prefill_gemm's, NOT the bit-exact one of the calls above - fp32 round-off from another summation
+ * order.  K/V rows and logits agree with the token-by-token path within the project's tolerances; every pick is an
+ * exact function of the pass's own logits (kh_model_seq_gemm_logits): the first maximum, kh_sample_f32's draw with
+ * counter = position, or the k_seq_tail chain; greedy words can differ from the batch-1 loop at near-ties only.
+ * kh_model_seq_width_gemm: *width = 64, or KH_ERR_UNSUPPORTED: a geometry kh_model_seq_width or kh_model_prefill_gemm
+ * refuses, or vocab_size % 16 != 0.  There is no fallback to the 8-lane pass.
+ * kh_model_seq_step_gemm: kh_model_seq_step_ex with n <= 64 lanes; o == NULL: greedy and neutral.  The same refusals in
+ * the same order, all before any launch, and the same rules for sharers and parents.  Eager launches (k_sg_embed, per
+ * layer k_pg_rmsnorm, k_sg_gemm, k_sg_rope where the epilogue cannot rotate, k_seq_attn / k_seq_attn_pfx per group,
+ * k_sg_gemm x 3 with k_pg_rmsnorm between; k_pg_rmsnorm, the classifier k_sg_gemm, k_seq_pick / k_seq_tail per group);
+ * synchronises.
+ * kh_model_generate_batch_gemm: kh_model_generate_batch_ex's parameters and host loop - lanes grouped in slot order
+ * (kh_plan_seq_batch_wide is kh_plan_seq_batch for width <= 64), picks fed on the device, the stop check every 8
+ * passes - at width 64 over the wide pass.  The fed-only part of every prompt runs as kh_model_seq_prefill's passes,
+ * bit-exact as ever.
+ * kh_model_seq_gemm_logits: the logits row [vocab_size] of lane `lane` of the last wide pass - after the tail's
+ * in-place processing when the call had an option on; the near-tie probe of a caller that compares against the
+ * batch-1 loop.  KH_ERR_UNSUPPORTED before any wide pass, KH_ERR_RANGE for a lane that pass did not have.
+ * Synchronises. */
+int kh_model_seq_width_gemm(const kh_model* m, int32_t* width);
+int kh_model_seq_step_gemm(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens, const int32_t* pos,
+                           const kh_seq_opts* o, int32_t* h_next);
+int kh_model_generate_batch_gemm(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
+                                 const int32_t* n_cached, const int32_t* total_steps, const kh_seq_opts* o,
+                                 const int32_t* h_stop, int32_t n_stop, int32_t* h_words, int32_t words_stride,
+                                 int32_t* n_words, float* h_elapsed_ms);
+int kh_model_seq_gemm_logits(kh_model* m, int32_t lane, float* h_logits);
+int kh_plan_seq_batch_wide(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
+                           int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes);
+
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,
  * cls) for a geometry - what kh_model_create_* configures (env KH_SHAPE_* overrides included).

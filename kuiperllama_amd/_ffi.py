@@ -29,6 +29,7 @@ EXPORTS = [
     "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_model_verify_as_set", "kh_model_generate_lookup_as_set", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
+    "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log", "kh_debug_alloc_stats",
 ]
 
@@ -274,6 +275,11 @@ def lib() -> C.CDLL:
     L.kh_seq_rank.argtypes = [_i32, C.POINTER(_f32), _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
                               C.POINTER(C.c_double)]
     L.kh_plan_seq_batch.argtypes = [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32)]
+    L.kh_plan_seq_batch_wide.argtypes = L.kh_plan_seq_batch.argtypes
+    L.kh_model_seq_width_gemm.argtypes = [_vp, C.POINTER(_i32)]
+    L.kh_model_seq_step_gemm.argtypes = L.kh_model_seq_step_ex.argtypes
+    L.kh_model_generate_batch_gemm.argtypes = L.kh_model_generate_batch_ex.argtypes
+    L.kh_model_seq_gemm_logits.argtypes = [_vp, _i32, C.POINTER(_f32)]
     L.kh_model_prefill_gemm.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
     L.kh_model_time_prefill.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_f32)]
     L.kh_model_profile_kernel.argtypes = [_vp, _i32, _i32, _i32, C.POINTER(_f32)]

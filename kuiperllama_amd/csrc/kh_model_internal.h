@@ -195,6 +195,10 @@ struct kh_model {
   KhDev<char> pg_ws;            // KH_PG_TMAX attention split workspaces (the first pass that takes the fallback)
   size_t pg_ws_tok_bytes = 0;
   bool pg_launch_failed = false;
+  // the wide sequence pass (kh_seq_gemm.h): logits rows [KH_SEQ_SLOTS_MAX][pf_vstride] of its classifier GEMM, made by
+  // the first wide call; sg_lanes: the lane count of the last wide pass (0: none yet)
+  KhDev<float> sg_logits;
+  int sg_lanes = 0;
   KhPin<int32_t> h_words_pin;   // pinned mirror of d_words (stop-token check, final copy-out)
   KhPin<int32_t> h_forced_pin;  // pinned staging of d_forced [seq_cap + 1]: the upload needs no host sync
   int forced_hwm = 0;              // entries of d_forced that may differ from -1 (the last generate's upload)
@@ -519,4 +523,31 @@ int seq_prepare(kh_model* m);
 int seq_prepare_ex(kh_model* m, bool records);  // behind seq_prepare: the tables of k_seq_tail, the record buffers
 int seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0, int pfx_len = 0, int pfx_row0 = 0);
 int seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, const KhSeqTail* tail = nullptr);
+// the two ends of a pass that do not care how its logits and q rows were made, for lanes [0, n) of a full table: the
+// attention of layer l on q / out rows of dim floats per lane (k_seq_attn, k_seq_attn_pfx where a lane shares a
+// prefix; the B-token pass's workspace), and the tail on logits rows [n][pf_vstride] (k_seq_pick, or k_seq_tail)
+void seq_attn_enqueue(kh_model* m, int l, const float* q, float* out, const KhSeqLanes& lanes, int n);
+int seq_tail_enqueue(kh_model* m, float* logits, const KhSeqLanes& lanes, int n, bool words, const KhSeqTail* tail);
+// GEMM prefill machinery shared with the wide sequence pass (kh_model_seq_gemm.hip): the slabs, the launch shape of
+// one GEMM (cost model pg_shape; pg_plan adds the KH_PG_SHAPE_* hooks, epi = KH_PG_*) and the per-(device, kernel)
+// opt-in for more than 48 KiB of dynamic LDS
+struct PgShape {
+  int R, NT, ks, slices;
+  bool solo;
+  int kz;
+};
+int ensure_pg_buffers(kh_model* m);
+PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant,
+                 bool allow_kz = false);
+PgShape pg_plan(const kh_model* m, int epi, int T, int rows_total, bool r2_ok, int K);
+bool pg_lds_opt_in(const void* kern, size_t lds);
+// ---- kh_model_seq_gemm.hip ------------------------------------------------------------------
+// The wide sequence pass (kh_seq_gemm.h): up to KH_SEQ_SLOTS_MAX lanes of distinct slots at full depth with the four
+// weight GEMMs and the classifier on the matrix cores; lane i feeds d_seq_tok[slots[i]] at position pos[i].  Picks
+// land as seq_pass_enqueue's.  seq_gemm_supported: the geometries it runs on; seq_gemm_prepare: its buffers, behind
+// seq_prepare and before the first enqueue of a call.
+bool seq_gemm_supported(const kh_model* m);
+int seq_gemm_prepare(kh_model* m);
+int seq_pass_enqueue_gemm(kh_model* m, const int32_t* slots, const int32_t* pos, int n, bool words,
+                          const KhSeqTail* tail = nullptr);
 }  // namespace khm

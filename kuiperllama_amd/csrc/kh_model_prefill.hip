@@ -312,8 +312,7 @@ void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0,
 }  // namespace
 
 // ---- GEMM prefill (kh_gemm.h) ------------------------------------------------------------------
-namespace {
-int ensure_pg_buffers(kh_model* m) {
+int khm::ensure_pg_buffers(kh_model* m) {
   if (m->pg_x) return KH_OK;
   const kh_config& c = m->cfg;
   const size_t T = KH_PG_TMAX;
@@ -339,6 +338,7 @@ int ensure_pg_buffers(kh_model* m) {
   m->pg_part = std::move(part);
   return KH_OK;
 }
+namespace {
 // does the prompt-slice attention run on the MFMA kernel (kh_pattn.h)?  KH_PG_ATTN=0 forces the fallback.
 bool pg_mfma_attn(const kh_model* m) { return !dbg_off("KH_PG_ATTN") && pg_attn_supported(m->cfg.head_size); }
 // The split workspace of the decode-attention FALLBACK (one per token of a pass, ~270 KB per token at
@@ -391,16 +391,12 @@ constexpr int pg_tile(int R, int NT) {  // index in kPgTiles, -1: no such tile
 //     rows x 128 tokens there are only 64 (2,8) tiles, so a chip-filling launch either takes small
 //     tiles or more K slices than a workgroup has waves.  The slices store partial rows and the
 //     RMSNorm kernel that follows adds them in fixed order (kh_gemm.h) - no ticket, no second launch.
-struct PgShape {
-  int R, NT, ks, slices;
-  bool solo;
-  int kz;
-};
 // hooks read per call (kh_debug_set takes effect on the next launch plan)
 static inline bool pg_solo_on() { return !dbg_off("KH_PG_SOLO"); }
 static inline bool pg_kz_on() { return !dbg_off("KH_PG_KZ"); }
-PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant,
-                 bool allow_kz = false) {
+}  // namespace
+PgShape khm::pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant,
+                      bool allow_kz) {
   const int nt_all = (T + 15) / 16;
   const bool wide = nt_all > 8;  // a pass of more than 128 tokens
   PgShape best{1, 4, 1, (nt_all + 3) / 4, false, 1};
@@ -449,30 +445,67 @@ PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min
   }
   return best;
 }
+bool khm::pg_lds_opt_in(const void* kern, size_t lds) {
+  if (lds > 48 * 1024) {
+    // the >48 KiB dynamic-LDS opt-in is per (device, kernel): set once, not on every launch of
+    // the prefill hot path; a refusal is reported here, not as a generic launch error later
+    struct Done { int dev; const void* fn; size_t lds; };
+    static thread_local std::vector<Done> done;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    bool hit = false;
+    for (const auto& d : done) hit = hit || (d.dev == dev && d.fn == kern && d.lds >= lds);
+    if (!hit) {
+      if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+      }
+      done.push_back({dev, kern, lds});
+    }
+  }
+  return true;
+}
+// The launch shape of one GEMM of a pass: the cost model, the KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE> hook, KH_PG_DEBUG.
+// epi: KH_PG_*; STORE (the classifier GEMM of the wide sequence pass) plans as a residual GEMM without a K split
+// across workgroups.
+PgShape khm::pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K) {
+  const bool q = m->cfg.is_quant;
+  const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
+  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / (q ? 64 : 16), q ? 4 : 16, q, EPI == KH_PG_RESID);
+  {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE>="R,NT,ks[,kz]" overrides the heuristic
+    static const char* const names[4] = {"KH_PG_SHAPE_QKV", "KH_PG_SHAPE_RESID", "KH_PG_SHAPE_SWIGLU",
+                                         "KH_PG_SHAPE_STORE"};
+    const char* const ov = dbg(names[EPI]);
+    if (ov) {
+      int R = 0, NT = 0, ks = 0, kz = 1;
+      if (sscanf(ov, "%d,%d,%d,%d", &R, &NT, &ks, &kz) >= 3 && pg_tile(R, NT) >= 0 && (R != 2 || r2_ok) &&
+          (ks == 1 || ks == 2 || ks == 4 || ks == 8) && ks * nm * 64 <= KH_PG_WG_MAX(q) &&
+          (kz == 1 || (EPI == KH_PG_RESID && (kz == 2 || kz == 4))))
+      {
+        const int slices = ((T + 15) / 16 + NT - 1) / NT;
+        sh = PgShape{R, NT, ks, slices,
+                     !q && (T > 128 || R * NT >= 16) && pg_solo_on() && (long)(rows_total / (16 * R)) * slices * kz > 256, kz};
+      } else {
+        // not a launch this GEMM has (e.g. R = 2 where 32 rows do not divide the matrices): say so rather than
+        // let a test believe it forced a shape
+        fprintf(stderr, "[kh] %s=\"%s\" rejected (R,NT 1,4%s, ks 1/2/4/8 up to %d waves%s): heuristic shape\n",
+                names[EPI], ov, r2_ok ? " or 2,2/4/8" : "", KH_PG_WG_MAX(q) / 64 / nm,
+                EPI == KH_PG_RESID ? ", kz 1/2/4" : "");
+      }
+    }
+  }
+  if (dbg("KH_PG_DEBUG"))
+    fprintf(stderr, "[pg] epi %d rows %d K %d T %d -> R %d NT %d slices %d ks %d kz %d (%d wgs x %d waves%s)\n", EPI,
+            rows_total, K, T, sh.R, sh.NT, sh.slices, sh.ks, sh.kz, rows_total / (16 * sh.R) * sh.slices * sh.kz,
+            nm * sh.ks, sh.solo ? ", solo" : "");
+  return sh;
+}
+namespace {
 template <bool Q, int EPI>
 bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const KhPgGemmArgs& a) {
   size_t lds = pg_lds_bytes(wg / 64, sh.NT);
   if (sh.solo && lds < KH_PG_SOLO_LDS) lds = KH_PG_SOLO_LDS;  // one workgroup per CU at a time
-  auto opt_in = [&](auto kern, dim3&) {
-    if (lds > 48 * 1024) {
-      // the >48 KiB dynamic-LDS opt-in is per (device, kernel): set once, not on every launch of
-      // the prefill hot path; a refusal is reported here, not as a generic launch error later
-      struct Done { int dev; const void* fn; size_t lds; };
-      static thread_local std::vector<Done> done;
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      bool hit = false;
-      for (const auto& d : done) hit = hit || (d.dev == dev && d.fn == (const void*)kern && d.lds >= lds);
-      if (!hit) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-          (void)hipGetLastError();
-          return false;
-        }
-        done.push_back({dev, (const void*)kern, lds});
-      }
-    }
-    return true;
-  };
+  auto opt_in = [&](auto kern, dim3&) { return pg_lds_opt_in((const void*)kern, lds); };
   const int tile = pg_tile(sh.R, sh.NT);  // one that is not listed runs as (2,2) where R is 2, else as (1,4)
   bool ok = false;
   kh_pick(KhVals<0, 1, 2, 3>{}, tile >= 0 ? tile : (sh.R == 2 ? 2 : 3), [&](auto I) {
@@ -487,32 +520,7 @@ template <int EPI>
 int pg_launch(kh_model* m, int rows_total, bool r2_ok, KhPgGemmArgs a) {
   const bool q = m->cfg.is_quant;
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
-  PgShape sh = pg_shape(a.T, rows_total, r2_ok, nm, a.K / (q ? 64 : 16), q ? 4 : 16, q, EPI == KH_PG_RESID);
-  {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU>="R,NT,ks[,kz]" overrides the heuristic
-    static const char* const names[3] = {"KH_PG_SHAPE_QKV", "KH_PG_SHAPE_RESID", "KH_PG_SHAPE_SWIGLU"};
-    const char* const ov = dbg(names[EPI]);
-    if (ov) {
-      int R = 0, NT = 0, ks = 0, kz = 1;
-      if (sscanf(ov, "%d,%d,%d,%d", &R, &NT, &ks, &kz) >= 3 && pg_tile(R, NT) >= 0 && (R != 2 || r2_ok) &&
-          (ks == 1 || ks == 2 || ks == 4 || ks == 8) && ks * nm * 64 <= KH_PG_WG_MAX(q) &&
-          (kz == 1 || (EPI == KH_PG_RESID && (kz == 2 || kz == 4))))
-      {
-        const int slices = ((a.T + 15) / 16 + NT - 1) / NT;
-        sh = PgShape{R, NT, ks, slices,
-                     !q && (a.T > 128 || R * NT >= 16) && pg_solo_on() && (long)(rows_total / (16 * R)) * slices * kz > 256, kz};
-      } else {
-        // not a launch this GEMM has (e.g. R = 2 where 32 rows do not divide the matrices): say so rather than
-        // let a test believe it forced a shape
-        fprintf(stderr, "[kh] %s=\"%s\" rejected (R,NT 1,4%s, ks 1/2/4/8 up to %d waves%s): heuristic shape\n",
-                names[EPI], ov, r2_ok ? " or 2,2/4/8" : "", KH_PG_WG_MAX(q) / 64 / nm,
-                EPI == KH_PG_RESID ? ", kz 1/2/4" : "");
-      }
-    }
-  }
-  if (dbg("KH_PG_DEBUG"))
-    fprintf(stderr, "[pg] epi %d rows %d K %d T %d -> R %d NT %d slices %d ks %d kz %d (%d wgs x %d waves%s)\n", EPI,
-            rows_total, a.K, a.T, sh.R, sh.NT, sh.slices, sh.ks, sh.kz, rows_total / (16 * sh.R) * sh.slices * sh.kz,
-            nm * sh.ks, sh.solo ? ", solo" : "");
+  const PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K);
   if (EPI == KH_PG_QKV && a.rope == KH_PG_ROPE_TILES && (sh.R != 2 || sh.NT > 4))
     a.rope = KH_PG_ROPE_OFF;  // no partner tile in the wave / no registers to hold it: k_pg_rope follows
   const int tiles = rows_total / (16 * sh.R);
@@ -873,7 +881,6 @@ int khm::seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, 
   return kh_launch_status();
 }
 int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, const KhSeqTail* tail) {
-  const kh_config& c = m->cfg;
   const int B = prefill_batch(m);
   for (int b = n; b < KH_PF_BMAX; ++b) {  // padding lanes rotate by the last valid lane's row; nothing of them is kept
     lanes.pos[b] = lanes.pos[n - 1];
@@ -884,9 +891,31 @@ int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, cons
   }
   launch_pf_pass(m, pf_lanes(lanes, n, B));
   launch_pf_cls(m, n, B);
+  return seq_tail_enqueue(m, m->pf_logits, lanes, n, words, tail);
+}
+// the attention of lanes [0, n) of layer l (entries >= n padded by the caller): q / out rows of c.dim floats per lane
+void khm::seq_attn_enqueue(kh_model* m, int l, const float* q, float* out, const KhSeqLanes& lanes, int n) {
+  KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
+  a.defer = 0;  // multi-token slices merge in the launch
+  a.nsplit_g = m->attn_ns_g;
+  a.q = q;
+  a.out = out;
+  a.d_pos = nullptr;
+  a.ws = m->pf_ws;
+  a.tok_stride = m->cfg.dim;
+  a.ws_tok_bytes = m->pf_ws_tok_bytes;
+  if (seq_lanes_share(lanes, n))
+    launch_seq_attn_pfx(a, lanes, n, m->attn_wg, m->stream, m->seq_pfx_pad8);
+  else
+    launch_seq_attn(a, lanes, n, m->attn_wg, m->stream);
+}
+// the tail of lanes [0, n) on their logits rows [n][pf_vstride]: k_seq_pick, or k_seq_tail with a tail description
+int khm::seq_tail_enqueue(kh_model* m, float* logits, const KhSeqLanes& lanes, int n, bool words,
+                          const KhSeqTail* tail) {
+  const kh_config& c = m->cfg;
   if (tail) {
     KhSeqTailArgs t;
-    t.logits = m->pf_logits;
+    t.logits = logits;
     t.vocab = c.vocab_size;
     t.vstride = m->pf_vstride;
     t.lanes = lanes;
@@ -909,7 +938,7 @@ int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, cons
     return kh_launch_status();
   }
   KhSeqPickArgs t;
-  t.logits = m->pf_logits;
+  t.logits = logits;
   t.vocab = c.vocab_size;
   t.vstride = m->pf_vstride;
   t.lanes = lanes;

@@ -1,7 +1,8 @@
 // kh_model_seq.hip — several independent sequences in one model: sequence slots of the K/V cache, the pass over lanes
 // of different sequences as an entry point (kh_model_seq_step) and the batched generate loop on top of it
 // (kh_model_generate_batch), and their _ex forms with per-sequence penalties, logit bias and log-probs (the pass then
-// ends in k_seq_tail).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
+// ends in k_seq_tail), and their _gemm forms: the same host text over the wide pass of up to KH_SEQ_SLOTS_MAX lanes
+// (kh_model_seq_gemm.hip: seq_pass_enqueue_gemm).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
 // seq_pass_enqueue; kernels in kh_seq.h, kh_attn.h).  The reference decodes one sequence per process
 // (demo/main.cpp:16-50); n samples of a prompt are n runs of that loop there.
 // gfx950 only.
@@ -161,14 +162,15 @@ extern "C" int kh_plan_seq_slots(int32_t cache_len, int32_t n_slots, int32_t* sl
   return KH_OK;
 }
 
-extern "C" int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
-                                 int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes) {
-  if (n_seq <= 0 || n_seq > KH_SEQ_SLOTS_MAX || width <= 0 || width > KH_PF_BMAX || !first_pos || !total_steps ||
+namespace {
+int plan_seq_batch(int32_t n_seq, int32_t width, int32_t width_max, const int32_t* first_pos,
+                   const int32_t* total_steps, int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes) {
+  if (n_seq <= 0 || n_seq > KH_SEQ_SLOTS_MAX || width <= 0 || width > width_max || !first_pos || !total_steps ||
       !n_passes || cap_passes < 0 || (cap_passes > 0 && !out_lanes))
     return KH_ERR_INVALID_ARG;
   for (int s = 0; s < n_seq; ++s)
     if (first_pos[s] < 0 || total_steps[s] <= 0) return KH_ERR_INVALID_ARG;
-  int32_t pos[KH_SEQ_SLOTS_MAX], lanes[KH_PF_BMAX];
+  int32_t pos[KH_SEQ_SLOTS_MAX], lanes[KH_SEQ_SLOTS_MAX];
   memcpy(pos, first_pos, sizeof(int32_t) * (size_t)n_seq);
   int cursor = 0, passes = 0;
   for (int n; (n = kh_seq_next_pass(n_seq, width, pos, total_steps, nullptr, &cursor, lanes)) > 0; ++passes) {
@@ -179,6 +181,17 @@ extern "C" int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* fi
   }
   *n_passes = passes;
   return passes <= cap_passes ? KH_OK : KH_ERR_RANGE;
+}
+}  // namespace
+extern "C" int kh_plan_seq_batch(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
+                                 int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes) {
+  return plan_seq_batch(n_seq, width, KH_PF_BMAX, first_pos, total_steps, out_lanes, cap_passes, n_passes);
+}
+// ... for the passes of kh_model_generate_batch_gemm: width up to KH_SEQ_SLOTS_MAX
+extern "C" int kh_plan_seq_batch_wide(int32_t n_seq, int32_t width, const int32_t* first_pos,
+                                      const int32_t* total_steps, int32_t* out_lanes, int32_t cap_passes,
+                                      int32_t* n_passes) {
+  return plan_seq_batch(n_seq, width, KH_SEQ_SLOTS_MAX, first_pos, total_steps, out_lanes, cap_passes, n_passes);
 }
 
 extern "C" int kh_plan_seq_slots_var(int32_t cache_len, int32_t n_slots, const int32_t* h_len, int32_t* row0_out) {
@@ -241,6 +254,13 @@ extern "C" int kh_model_seq_width(const kh_model* m, int32_t* width) {
   return KH_OK;
 }
 
+extern "C" int kh_model_seq_width_gemm(const kh_model* m, int32_t* width) {
+  if (!m || !width) return KH_ERR_INVALID_ARG;
+  if (!seq_gemm_supported(m)) return KH_ERR_UNSUPPORTED;
+  *width = KH_SEQ_SLOTS_MAX;
+  return KH_OK;
+}
+
 extern "C" int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_tokens, int32_t n, int32_t pos0) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > cap(m, slot)) return KH_ERR_RANGE;
@@ -284,13 +304,15 @@ extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot
 
 // One pass.  Eager launches on the model stream; every check before the first of them.  o: the _ex call's options
 // (its samplings are `samplings` here), which replace the model's own settings - those refuse the plain call.
+// wide: the pass is the wide one (kh_seq_gemm.h: up to KH_SEQ_SLOTS_MAX lanes, seq_pass_enqueue_gemm); an _ex call.
 namespace {
 int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens, const int32_t* pos,
-                 const kh_sampling* samplings, const kh_seq_opts* o, bool ex_call, int32_t* h_next) {
+                 const kh_sampling* samplings, const kh_seq_opts* o, bool ex_call, int32_t* h_next, bool wide = false) {
   if (!m || !slots || !h_tokens || !pos || !h_next || n <= 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
-  if (ex_call ? !full_depth_supported(m) : seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
-  if (n > verify_width(m)) return KH_ERR_RANGE;
+  if (wide ? !seq_gemm_supported(m) : (ex_call ? !full_depth_supported(m) : seq_unsupported(m)))
+    return KH_ERR_UNSUPPORTED;
+  if (n > (wide ? KH_SEQ_SLOTS_MAX : verify_width(m))) return KH_ERR_RANGE;
   for (int i = 0; i < n; ++i) {
     if (slots[i] < 0 || slots[i] >= m->seq_slots || pos[i] < 0 || pos[i] >= cap(m, slots[i]) || h_tokens[i] < 0 ||
         h_tokens[i] >= c.vocab_size)
@@ -311,10 +333,11 @@ int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_
     if ((rc = ensure_slot_rows(m, slots[i], pos[i] + 1)) != KH_OK) return rc;
   if ((rc = seq_prepare(m)) != KH_OK) return rc;
   if (ex.on && (rc = seq_prepare_ex(m, ex.top_n >= 0)) != KH_OK) return rc;
+  if (wide && (rc = seq_gemm_prepare(m)) != KH_OK) return rc;
   clear_slot_tables(m);
   KhSeqLanes lanes;
   for (int i = 0; i < n; ++i) {
-    lane_set(m, lanes, i, slots[i], pos[i]);
+    if (!wide) lane_set(m, lanes, i, slots[i], pos[i]);
     m->h_seq_tok_pin[slots[i]] = h_tokens[i];
     if (samplings && !kh_sampling_greedy(&samplings[i])) m->h_seq_samp_pin[slots[i]] = kh_samp_params(&samplings[i]);
   }
@@ -324,12 +347,14 @@ int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_
     rc = upload_proc_tables(m, n, ex, [&](int i) { return slots[i]; });
     for (int i = 0; i < n && rc == KH_OK; ++i) {  // the lanes' fed tokens at their rows of the history
       m->h_seq_hist_pin[i] = h_tokens[i];
-      rc = (int)hipMemcpyAsync(m->d_hist + lanes.row[i], m->h_seq_hist_pin + i, sizeof(int32_t), hipMemcpyHostToDevice,
+      rc = (int)hipMemcpyAsync(m->d_hist + own_base(m, slots[i]) + pos[i], m->h_seq_hist_pin + i, sizeof(int32_t), hipMemcpyHostToDevice,
                                m->stream);
     }
     if (rc == KH_OK && ex.top_n >= 0) m->seq_lp_top_n = ex.top_n;
   }
-  if (rc == KH_OK) rc = seq_pass_enqueue(m, lanes, n, /*words=*/false, ex.on ? &tail : nullptr);
+  if (rc == KH_OK)
+    rc = wide ? seq_pass_enqueue_gemm(m, slots, pos, n, /*words=*/false, ex.on ? &tail : nullptr)
+              : seq_pass_enqueue(m, lanes, n, /*words=*/false, ex.on ? &tail : nullptr);
   if (rc == KH_OK)
     rc = (int)hipMemcpyAsync(m->h_seq_tok_pin, m->d_seq_tok, sizeof(int32_t) * KH_SEQ_SLOTS_MAX, hipMemcpyDeviceToHost,
                              m->stream);
@@ -347,6 +372,21 @@ extern "C" int kh_model_seq_step(kh_model* m, int32_t n, const int32_t* slots, c
 extern "C" int kh_model_seq_step_ex(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens,
                                     const int32_t* pos, const kh_seq_opts* o, int32_t* h_next) {
   return seq_step_run(m, n, slots, h_tokens, pos, o ? o->samplings : nullptr, o, /*ex_call=*/true, h_next);
+}
+extern "C" int kh_model_seq_step_gemm(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_tokens,
+                                      const int32_t* pos, const kh_seq_opts* o, int32_t* h_next) {
+  return seq_step_run(m, n, slots, h_tokens, pos, o ? o->samplings : nullptr, o, /*ex_call=*/true, h_next,
+                      /*wide=*/true);
+}
+extern "C" int kh_model_seq_gemm_logits(kh_model* m, int32_t lane, float* h_logits) {
+  if (!m || !h_logits) return KH_ERR_INVALID_ARG;
+  if (!m->sg_logits || m->sg_lanes == 0) return KH_ERR_UNSUPPORTED;  // no wide pass yet
+  if (lane < 0 || lane >= m->sg_lanes) return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemcpyAsync(h_logits, m->sg_logits + (size_t)lane * m->pf_vstride,
+                              sizeof(float) * (size_t)m->cfg.vocab_size, hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
 }
 
 // kh_model_generate_until for n_seq sequences at once, sequence s in slot s.  The fed-only part of every prompt runs
@@ -367,7 +407,7 @@ namespace {
 int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
                        const int32_t* n_cached, const int32_t* total_steps, const kh_sampling* samplings,
                        const kh_seq_opts* o, bool ex_call, const int32_t* h_stop, int32_t n_stop, int32_t* h_words,
-                       int32_t words_stride, int32_t* n_words, float* h_elapsed_ms);
+                       int32_t words_stride, int32_t* n_words, float* h_elapsed_ms, bool wide = false);
 }
 extern "C" int kh_model_generate_batch_from(kh_model* m, int32_t n_seq, const int32_t* h_prompts,
                                             const int32_t* n_prompt, const int32_t* n_cached,
@@ -385,11 +425,21 @@ extern "C" int kh_model_generate_batch_ex(kh_model* m, int32_t n_seq, const int3
   return generate_batch_run(m, n_seq, h_prompts, n_prompt, n_cached, total_steps, o ? o->samplings : nullptr, o,
                             /*ex_call=*/true, h_stop, n_stop, h_words, words_stride, n_words, h_elapsed_ms);
 }
+// ... with the sampled part as wide passes (kh_seq_gemm.h): the same loop at width KH_SEQ_SLOTS_MAX
+extern "C" int kh_model_generate_batch_gemm(kh_model* m, int32_t n_seq, const int32_t* h_prompts,
+                                            const int32_t* n_prompt, const int32_t* n_cached,
+                                            const int32_t* total_steps, const kh_seq_opts* o, const int32_t* h_stop,
+                                            int32_t n_stop, int32_t* h_words, int32_t words_stride, int32_t* n_words,
+                                            float* h_elapsed_ms) {
+  return generate_batch_run(m, n_seq, h_prompts, n_prompt, n_cached, total_steps, o ? o->samplings : nullptr, o,
+                            /*ex_call=*/true, h_stop, n_stop, h_words, words_stride, n_words, h_elapsed_ms,
+                            /*wide=*/true);
+}
 namespace {
 int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, const int32_t* n_prompt,
                        const int32_t* n_cached, const int32_t* total_steps, const kh_sampling* samplings,
                        const kh_seq_opts* o, bool ex_call, const int32_t* h_stop, int32_t n_stop, int32_t* h_words,
-                       int32_t words_stride, int32_t* n_words, float* h_elapsed_ms) {
+                       int32_t words_stride, int32_t* n_words, float* h_elapsed_ms, bool wide) {
   if (!m || !h_prompts || !n_prompt || !total_steps || !h_words || !n_words || n_seq <= 0 || words_stride <= 0 ||
       n_stop < 0 || (n_stop > 0 && !h_stop))
     return KH_ERR_INVALID_ARG;
@@ -405,7 +455,8 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
     n_tok += (size_t)n_prompt[s];
   }
   if (!tokens_in_vocab(m, h_prompts, n_tok)) return KH_ERR_RANGE;
-  if (ex_call ? !full_depth_supported(m) : seq_unsupported(m)) return KH_ERR_UNSUPPORTED;
+  if (wide ? !seq_gemm_supported(m) : (ex_call ? !full_depth_supported(m) : seq_unsupported(m)))
+    return KH_ERR_UNSUPPORTED;
   SeqEx ex;
   {
     const int rc = seq_ex_parse(m, n_seq, o, &ex);
@@ -425,13 +476,14 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
     }
     if ((rc = seq_prepare(m)) != KH_OK) return rc;
     if (ex.on && (rc = seq_prepare_ex(m, ex.top_n >= 0)) != KH_OK) return rc;
+    if (wide && (rc = seq_gemm_prepare(m)) != KH_OK) return rc;
     const KhSeqTail tail{ex.top_n, m->d_seq_proc, m->d_seq_bias_ids, m->d_seq_bias, m->d_seq_cnt};
     // every early return below may leave launches and copies into pinned memory in flight: drain first
     auto fail = [&](int code) -> int {
       (void)hipStreamSynchronize(m->stream);
       return code;
     };
-    const int width = verify_width(m);
+    const int width = wide ? KH_SEQ_SLOTS_MAX : verify_width(m);
     std::vector<const int32_t*> prompt((size_t)n_seq);
     // pos[s]: the next position sequence s feeds in a pass; copied / checked: how far its words were mirrored / read
     std::vector<int32_t> pos((size_t)n_seq), copied((size_t)n_seq), checked((size_t)n_seq), stop_at((size_t)n_seq, -1);
@@ -517,15 +569,18 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
     for (;;) {
       int k = 0;
       while (k < per_check) {
-        int32_t who[KH_PF_BMAX];
+        int32_t who[KH_SEQ_SLOTS_MAX], at[KH_SEQ_SLOTS_MAX];
         const int n = kh_seq_next_pass(n_seq, width, pos.data(), total_steps, stopped.data(), &cursor, who);
         if (n == 0) break;
         KhSeqLanes lanes;
         for (int i = 0; i < n; ++i) {
-          lane_set(m, lanes, i, who[i], pos[who[i]]);
+          if (!wide) lane_set(m, lanes, i, who[i], pos[who[i]]);
+          at[i] = pos[who[i]];
           pos[who[i]] += 1;
         }
-        if ((rc = seq_pass_enqueue(m, lanes, n, /*words=*/true, ex.on ? &tail : nullptr)) != KH_OK) return fail(rc);
+        rc = wide ? seq_pass_enqueue_gemm(m, who, at, n, /*words=*/true, ex.on ? &tail : nullptr)
+                  : seq_pass_enqueue(m, lanes, n, /*words=*/true, ex.on ? &tail : nullptr);
+        if (rc != KH_OK) return fail(rc);
         ++k;
       }
       if (k > 0 && (rc = mirror()) != KH_OK) return fail(rc);

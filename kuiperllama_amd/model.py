@@ -126,20 +126,23 @@ def seq_rank(lp_rows, first: Sequence[int], n_words: Sequence[int]) -> Tuple[Lis
     return list(order[:n]), mean[:n]
 
 
-def plan_seq_batch(first_pos: Sequence[int], total_steps: Sequence[int], width: int) -> List[List[int]]:
+def plan_seq_batch(first_pos: Sequence[int], total_steps: Sequence[int], width: int,
+                   wide: bool = False) -> List[List[int]]:
     """The passes generate_batch runs while no sequence stops early (kh_plan_seq_batch; host only): per pass the
-    sequences in its lanes.  first_pos[s] = len(prompt s) - 1, the first position a pass feeds."""
+    sequences in its lanes.  first_pos[s] = len(prompt s) - 1, the first position a pass feeds.  wide: the passes of
+    generate_batch(gemm=True), width up to 64 (kh_plan_seq_batch_wide)."""
     first_pos, total_steps = list(first_pos), list(total_steps)
     if len(first_pos) != len(total_steps):
         raise ValueError(f"plan_seq_batch: {len(first_pos)} positions for {len(total_steps)} totals")
     n, L = C.c_int32(0), _ffi.lib()
-    rc = L.kh_plan_seq_batch(len(first_pos), int(width), _i32_array(first_pos), _i32_array(total_steps), None, 0,
-                             C.byref(n))
+    name = "kh_plan_seq_batch_wide" if wide else "kh_plan_seq_batch"
+    plan = getattr(L, name)
+    rc = plan(len(first_pos), int(width), _i32_array(first_pos), _i32_array(total_steps), None, 0, C.byref(n))
     if rc not in (0, _ffi.KH_ERR_RANGE):
-        raise _ffi.KhError(rc, "kh_plan_seq_batch")
+        raise _ffi.KhError(rc, name)
     out = (C.c_int32 * max(n.value * int(width), 1))()
-    _ffi.check(L.kh_plan_seq_batch(len(first_pos), int(width), _i32_array(first_pos), _i32_array(total_steps), out,
-                                   n.value, C.byref(n)), "kh_plan_seq_batch")
+    _ffi.check(plan(len(first_pos), int(width), _i32_array(first_pos), _i32_array(total_steps), out, n.value,
+                    C.byref(n)), name)
     return [[int(x) for x in out[p * width:(p + 1) * width] if x >= 0] for p in range(n.value)]
 
 
@@ -568,11 +571,22 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_seq_row(self._h, int(slot), int(pos), C.byref(out)), "kh_model_seq_row")
         return int(out.value)
 
-    def seq_width(self) -> int:
-        """Lanes (sequences) per pass of this model (kh_model_seq_width): 8 for fp32, 4 for int8 and wide fp32."""
+    def seq_width(self, gemm: bool = False) -> int:
+        """Lanes (sequences) per pass of this model (kh_model_seq_width): 8 for fp32, 4 for int8 and wide fp32.
+        gemm=True: of the wide pass on the matrix cores (kh_model_seq_width_gemm): 64, or KhError where it does not
+        run."""
         w = C.c_int32(0)
-        _ffi.check(_ffi.lib().kh_model_seq_width(self._h, C.byref(w)), "kh_model_seq_width")
+        name = "kh_model_seq_width_gemm" if gemm else "kh_model_seq_width"
+        _ffi.check(getattr(_ffi.lib(), name)(self._h, C.byref(w)), name)
         return int(w.value)
+
+    def seq_gemm_logits(self, lane: int) -> np.ndarray:
+        """The logits row of lane `lane` of the last seq_step(gemm=True) / generate_batch(gemm=True) pass
+        (kh_model_seq_gemm_logits): what its pick was made from - after penalties and bias where the call had any."""
+        out = np.empty(int(self.cfg.vocab_size), np.float32)
+        _ffi.check(_ffi.lib().kh_model_seq_gemm_logits(self._h, int(lane), out.ctypes.data_as(C.POINTER(C.c_float))),
+                   "kh_model_seq_gemm_logits")
+        return out
 
     def seq_prefill(self, slot: int, tokens: Sequence[int], pos0: int = 0) -> None:
         """prefill() on the rows of sequence slot `slot` (kh_model_seq_prefill)."""
@@ -588,7 +602,8 @@ class KuiperModel:
 
     def seq_step(self, slots: Sequence[int], tokens: Sequence[int], pos: Sequence[int],
                  samplings: Optional[Sequence] = None, penalties: Optional[Sequence] = None,
-                 logit_bias: Optional[Sequence] = None, logprobs: Optional[int] = None) -> List[int]:
+                 logit_bias: Optional[Sequence] = None, logprobs: Optional[int] = None,
+                 gemm: bool = False) -> List[int]:
         """One pass over len(slots) <= seq_width() lanes in distinct slots (kh_model_seq_step): lane i feeds tokens[i]
         at position pos[i] of slot slots[i]; returns the picks - greedy, or sampled where samplings[i] (None | dict of
         temperature / top_k / top_p / seed) has a temperature > 0 - exactly a predict loop's on a batch-1 model.
@@ -596,17 +611,23 @@ class KuiperModel:
         logprobs (None | top_n for every lane) go through kh_model_seq_step_ex: the pick is then the batch-1 model's
         under those settings over the slot's fed-token history (seq_prefill, seq_fork, seq_set_history, earlier
         passes), the record of the lane's position is read with seq_logprobs(); the model's own set_* values are not
-        consulted.  With all three None this is the plain call."""
+        consulted.  With all three None this is the plain call.
+        gemm=True: the wide pass on the matrix cores (kh_model_seq_step_gemm), up to seq_width(gemm=True) = 64 lanes.
+        Not bit-identical to the batch-1 loop: logits and K/V rows agree to fp32 round-off, every pick is exact on the
+        pass's own logits (seq_gemm_logits)."""
         slots, tokens, pos = list(slots), list(tokens), list(pos)
         n = len(slots)
         if len(tokens) != n or len(pos) != n:
             raise ValueError(f"seq_step: {n} slots, {len(tokens)} tokens, {len(pos)} positions")
         sp = _sampling_array(samplings, n, "seq_step")
         nxt = (C.c_int32 * max(n, 1))()
-        if penalties is not None or logit_bias is not None or logprobs is not None:
+        if gemm:
+            _ffi.sync_env()  # KH_PG_*
+        if gemm or penalties is not None or logit_bias is not None or logprobs is not None:
             o, keep = _seq_opts(n, sp, penalties, logit_bias, logprobs, "seq_step")
-            _ffi.check(_ffi.lib().kh_model_seq_step_ex(self._h, n, _i32_array(slots), _i32_array(tokens),
-                                                       _i32_array(pos), C.byref(o), nxt), "kh_model_seq_step_ex")
+            name = "kh_model_seq_step_gemm" if gemm else "kh_model_seq_step_ex"
+            _ffi.check(getattr(_ffi.lib(), name)(self._h, n, _i32_array(slots), _i32_array(tokens), _i32_array(pos),
+                                                 C.byref(o), nxt), name)
             del keep
             if logprobs is not None:
                 self._seq_top_n = int(logprobs)
@@ -618,7 +639,7 @@ class KuiperModel:
     def generate_batch(self, prompts: Sequence[Sequence[int]], total_steps, samplings: Optional[Sequence] = None,
                        stop: Sequence[int] = (), cached: Optional[Sequence[int]] = None,
                        penalties: Optional[Sequence] = None, logit_bias: Optional[Sequence] = None,
-                       logprobs: Optional[int] = None) -> Tuple[List[List[int]], float]:
+                       logprobs: Optional[int] = None, gemm: bool = False) -> Tuple[List[List[int]], float]:
         """generate() for len(prompts) <= n_slots sequences at once, sequence s in slot s (kh_model_generate_batch):
         seq_width() sequences share every pass over the weights.  total_steps: one int for all or one per sequence;
         samplings: None (all greedy) or one entry per sequence (None | dict of temperature / top_k / top_p / seed).
@@ -628,7 +649,10 @@ class KuiperModel:
         penalties / logit_bias (one entry per sequence: None | dict of set_penalties()'s keys, None | {id: value}) and
         logprobs (None | top_n) go through kh_model_generate_batch_ex: the words are then that model's under
         set_penalties / set_logit_bias / set_logprobs too, and seq_logprobs(s, 0, len(words[s])) its records.  The
-        model's own set_* values are not consulted.  With all three None this is the plain call."""
+        model's own set_* values are not consulted.  With all three None this is the plain call.
+        gemm=True: the sampled part runs as wide passes on the matrix cores (kh_model_generate_batch_gemm), up to 64
+        sequences per pass over the weights.  Not bit-identical: greedy words can differ from generate()'s at
+        near-ties, sampled words are the sampler's on the pass's own logits."""
         prompts = [list(p) for p in prompts]
         n = len(prompts)
         totals = [int(total_steps)] * n if isinstance(total_steps, (int, np.integer)) else [int(t) for t in total_steps]
@@ -645,12 +669,15 @@ class KuiperModel:
         nw = (C.c_int32 * n)()
         ms = C.c_float(0.0)
         flat = [t for p in prompts for t in p]
-        if penalties is not None or logit_bias is not None or logprobs is not None:
+        if gemm:
+            _ffi.sync_env()  # KH_PG_*
+        if gemm or penalties is not None or logit_bias is not None or logprobs is not None:
             o, keep = _seq_opts(n, sp, penalties, logit_bias, logprobs, "generate_batch")
-            _ffi.check(_ffi.lib().kh_model_generate_batch_ex(
+            name = "kh_model_generate_batch_gemm" if gemm else "kh_model_generate_batch_ex"
+            _ffi.check(getattr(_ffi.lib(), name)(
                 self._h, n, _i32_array(flat), _i32_array([len(p) for p in prompts]),
                 None if cached is None else _i32_array(cached), _i32_array(totals), C.byref(o), _i32_array(st), len(st),
-                words, stride, nw, C.byref(ms)), "kh_model_generate_batch_ex")
+                words, stride, nw, C.byref(ms)), name)
             del keep
             if logprobs is not None:
                 self._seq_top_n = int(logprobs)
@@ -686,7 +713,7 @@ class KuiperModel:
 
     def best_of(self, prompt: Sequence[int], n: int, total_steps: int, sampling: dict, stop: Sequence[int] = (),
                 penalties: Optional[dict] = None, logit_bias: Optional[dict] = None, top_n: int = 0,
-                share: bool = False) -> List[dict]:
+                share: bool = False, gemm: bool = False) -> List[dict]:
         """n samples of one prompt, best first: one seq_prefill of the prompt's fed-only part into slot 0, n - 1
         seq_forks, one generate_batch(cached=..) with seeds seed, seed + 1, .. of `sampling` (and the shared penalties
         / logit_bias), then seq_rank on the sampled positions' log-probs.  Returns [{"words", "mean_logprob", "seed"}]
@@ -694,7 +721,9 @@ class KuiperModel:
         when the model has fewer.
         share=True: the samples read the prompt's rows from slot 0 instead of holding copies - one prefill, n - 1
         seq_share calls on plan_shared_layout(cfg.cache_len, ..) - so n samples need prompt + n * generated rows, not
-        n * (prompt + generated).  Same words and records; penalties are refused on sharing slots."""
+        n * (prompt + generated).  Same words and records; penalties are refused on sharing slots.
+        gemm=True: the samples decode as wide passes (generate_batch(gemm=True)), up to 64 per pass over the weights;
+        sample i is then the sampler's on the wide pass's logits, equal to generate()'s to fp32 round-off."""
         prompt, n, total_steps = [int(t) for t in prompt], int(n), int(total_steps)
         if n <= 0 or not prompt:
             raise ValueError("best_of: no sample, or an empty prompt")
@@ -716,7 +745,7 @@ class KuiperModel:
                     self.seq_fork(0, s, fed)
         words, _ = self.generate_batch([prompt] * n, total_steps, [dict(sampling, seed=seed0 + s) for s in range(n)],
                                        stop=stop, cached=[fed] * n, penalties=[penalties] * n,
-                                       logit_bias=[logit_bias] * n, logprobs=int(top_n))
+                                       logit_bias=[logit_bias] * n, logprobs=int(top_n), gemm=gemm)
         rows = [self.seq_logprobs(s, 0, len(w))["logprob"] if w else np.empty(0, np.float32) for s, w in enumerate(words)]
         order, mean = seq_rank(rows, [min(fed, len(w)) for w in words], [len(w) for w in words])
         return [{"words": words[s], "mean_logprob": float(mean[s]), "seed": seed0 + s} for s in order]

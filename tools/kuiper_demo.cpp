@@ -17,7 +17,7 @@
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
 //               [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]
-//               [--parallel N] [--best-of N] [--share-prefix]
+//               [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -47,6 +47,9 @@
 // kh_model_generate_batch_from): the cache is cut into N slots, the prompt is prefilled once and forked, the seeds are
 // --seed, --seed + 1, ...; each sequence's ids are printed on a line of their own, then the aggregate "steps/s".
 // Greedy without --temperature (N equal lines).  Penalties, bias and log-probs are refused, as by the library.
+// --gemm-batch (beside --parallel): the samples decode as wide passes on the matrix cores, up to 64 per pass over the
+// weights (kh_model_seq_width_gemm / kh_model_generate_batch_gemm): equal to the plain run to fp32 round-off, greedy ids
+// can differ at near-ties.  Refused where the library refuses it; there is no fallback.
 // --best-of N: --parallel's N samples (seeds --seed, --seed + 1, ...) through kh_model_generate_batch_ex, which takes
 // the sampler, penalty, bias and --logprobs flags per sequence (the model's own settings are not consulted), ranked by
 // kh_seq_rank on the mean log-prob of each sample's generated tokens: one line per sample, best first,
@@ -89,7 +92,7 @@ static void usage() {
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
                "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]\n"
-               "       [--parallel N] [--best-of N] [--share-prefix]\n");
+               "       [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix]\n");
 }
 
 int main(int argc, char** argv) {
@@ -110,6 +113,7 @@ int main(int argc, char** argv) {
   bool lookup_as_set = false;  // --lookup-as-set [ngram_max] (kh_model_generate_lookup_as_set)
   kh_lookup_opts lk{0, 0, 0, nullptr, 0};
   int parallel = 0;  // --parallel N (kh_model_generate_batch)
+  bool gemm_batch = false;  // --gemm-batch (kh_model_generate_batch_gemm)
   int best_of = 0;   // --best-of N (kh_model_generate_batch_ex, kh_seq_rank)
   bool share_prefix = false;  // --share-prefix: the samples read the prompt's rows from slot 0 (kh_model_seq_share)
   std::vector<int32_t> hint;  // --hint
@@ -153,6 +157,7 @@ int main(int argc, char** argv) {
     else if (a == "--logprobs") logprobs = std::atoi(next());
     else if (a == "--score") score = true;
     else if (a == "--parallel") parallel = std::atoi(next());
+    else if (a == "--gemm-batch") gemm_batch = true;
     else if (a == "--best-of") best_of = std::atoi(next());
     else if (a == "--share-prefix") share_prefix = true;
     else if (a == "--lookup" || a == "--lookup-as-set") {
@@ -404,13 +409,20 @@ int main(int argc, char** argv) {
     std::printf("Generating...\n");
     const auto t0 = std::chrono::steady_clock::now();
     rc = seq_layout(m, parallel, have, steps, share_prefix, &slot_len);
-    if (rc == KH_OK) rc = kh_model_seq_width(m, &width);
+    if (rc == KH_OK) rc = gemm_batch ? kh_model_seq_width_gemm(m, &width) : kh_model_seq_width(m, &width);
     if (rc == KH_OK && have > 0) rc = kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
     for (int s = 1; s < parallel && rc == KH_OK && have > 0; ++s) rc = seq_attach(m, s, have, share_prefix);
-    if (rc == KH_OK)
+    if (rc == KH_OK && gemm_batch) {
+      kh_seq_opts so{};
+      so.samplings = samps.data();
+      so.logprobs_top_n = -1;
+      rc = kh_model_generate_batch_gemm(m, parallel, prompts.data(), n_prompt.data(), cached.data(), totals.data(), &so,
+                                        stop.data(), (int32_t)stop.size(), out.data(), steps, n_out.data(), &ms);
+    } else if (rc == KH_OK) {
       rc = kh_model_generate_batch_from(m, parallel, prompts.data(), n_prompt.data(), cached.data(), totals.data(),
                                         samps.data(), stop.data(), (int32_t)stop.size(), out.data(), steps,
                                         n_out.data(), &ms);
+    }
     const auto t1 = std::chrono::steady_clock::now();
     if (rc != KH_OK) {
       std::fprintf(stderr, "--parallel %d failed: %d (%s)\n", parallel, rc, kh_error_string(rc));
