@@ -847,6 +847,34 @@ int kh_model_seq_gemm_logits(kh_model* m, int32_t lane, float* h_logits);
 int kh_plan_seq_batch_wide(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
                            int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes);
 
+/* MFMA prompt prefill into sequence slots: many prompts per weight pass (csrc/kh_seq_prefill.h).  kh_model_seq_prefill
+ * is the bit-exact VALU pass, 8 (fp32) or 4 (int8) tokens per sweep of the weights; kh_model_prefill_gemm writes rows
+ * pos0 + t of the batch-1 layout only.  Here prompt SEGMENTS of several slots - segment i = n_tokens[i] tokens of the
+ * concatenated h_tokens at positions pos0[i] .. of slot slots[i] - are packed into GEMM passes of 32 token tiles of 16
+ * (a tile belongs to one segment; the padding tokens of a segment's last tile repeat its last valid token).  One prompt
+ * into one slot is the one-segment call.  Opt-in: no other entry point routes here, and a model that never calls it
+ * allocates and launches nothing new.  It reads the fp32 weights, also under KH_FLAG_W16.
+ * Contract: kh_model_prefill_gemm's, NOT the bit-exact one of kh_model_seq_prefill - the call leaves K/V rows (and the
+ * slots' fed-token record, as kh_model_seq_prefill) and no logits.  A lone segment leaves the very bytes
+ * kh_model_prefill_gemm(tokens, n, pos0) leaves in rows [pos0, pos0 + n) of a batch-1 model below position 2048 (from
+ * there on that call may share K/V fragments between query tiles, which regroups nothing but is not promised here).
+ * kh_plan_seq_prefill_gemm: host only.  Segments are walked in call order; one that fits in what is left of the pass is
+ * placed whole, else its first 16 x free tokens fill the pass and the rest continues in the next.  out_runs[r] = {pass,
+ * segment, first token offset, count}; *n_runs = the runs there are (KH_ERR_RANGE when cap_runs holds fewer: call with
+ * cap_runs 0 to size the array), *n_passes (optional) the passes.
+ * kh_model_seq_prefill_gemm: every check before the first launch - per segment kh_model_seq_prefill's (the slot and its
+ * capacity: KH_ERR_RANGE; the vocabulary: KH_ERR_RANGE; a sharer below its shared length or a parent's shared rows:
+ * KH_ERR_INVALID_ARG); n_seq > 64: KH_ERR_RANGE; a slot twice, or a sharer together with its parent (feed the parent in
+ * an earlier call): KH_ERR_INVALID_ARG; a geometry kh_model_prefill_gemm refuses, a head size other than 48 / 64 / 128,
+ * or KH_PG_ATTN=0: KH_ERR_UNSUPPORTED - there is no fallback to the VALU pass or to the decode attention.  Launches per
+ * pass: the embedding, per layer k_pg_rmsnorm, k_rg_gemm (QKV under the tile address), k_rg_rope where the epilogue
+ * cannot rotate, k_rg_attn, k_pg_gemm x 3 with k_pg_rmsnorm between; the last layer stops behind its QKV GEMM.  The
+ * KH_PG_SHAPE_* hooks apply, KH_PG_CHUNK does not.  Synchronises. */
+int kh_plan_seq_prefill_gemm(int32_t n_seq, const int32_t* n_tokens, int32_t* out_runs, int32_t cap_runs,
+                             int32_t* n_runs, int32_t* n_passes);
+int kh_model_seq_prefill_gemm(kh_model* m, int32_t n_seq, const int32_t* slots, const int32_t* h_tokens,
+                              const int32_t* n_tokens, const int32_t* pos0);
+
 /* Launch plans, host-only (no device is touched; for tools and the CPU test-suite).
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,
  * cls) for a geometry - what kh_model_create_* configures (env KH_SHAPE_* overrides included).

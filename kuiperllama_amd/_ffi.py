@@ -30,6 +30,7 @@ EXPORTS = [
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
+    "kh_plan_seq_prefill_gemm", "kh_model_seq_prefill_gemm",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log", "kh_debug_alloc_stats",
 ]
 
@@ -280,6 +281,8 @@ def lib() -> C.CDLL:
     L.kh_model_seq_step_gemm.argtypes = L.kh_model_seq_step_ex.argtypes
     L.kh_model_generate_batch_gemm.argtypes = L.kh_model_generate_batch_ex.argtypes
     L.kh_model_seq_gemm_logits.argtypes = [_vp, _i32, C.POINTER(_f32)]
+    L.kh_plan_seq_prefill_gemm.argtypes = [_i32, C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32), C.POINTER(_i32)]
+    L.kh_model_seq_prefill_gemm.argtypes = [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]
     L.kh_model_prefill_gemm.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
     L.kh_model_time_prefill.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_f32)]
     L.kh_model_profile_kernel.argtypes = [_vp, _i32, _i32, _i32, C.POINTER(_f32)]

@@ -541,6 +541,14 @@ PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min
                  bool allow_kz = false);
 PgShape pg_plan(const kh_model* m, int epi, int T, int rows_total, bool r2_ok, int K);
 bool pg_lds_opt_in(const void* kern, size_t lds);
+// The GEMM prefill into sequence slots (kh_seq_prefill.h; kh_model_seq_prefill_gemm).  _check: KH_OK where the pass
+// runs - the GEMM prefill's geometries with an MFMA attention instantiation for the head size and KH_PG_ATTN not 0 -,
+// else KH_ERR_UNSUPPORTED.  _enqueue: the planned passes (kh_rg_plan) for segment s = n_tokens[s] tokens of the
+// concatenated toks at positions pos0[s] .. of slot slots[s]; the slabs are ensure_pg_buffers'.  Arguments and the
+// slots' rows (ensure_slot_rows) are the caller's to check.
+int seq_prefill_gemm_check(const kh_model* m);
+int seq_prefill_gemm_enqueue(kh_model* m, int n_seq, const int32_t* slots, const int32_t* toks, const int32_t* n_tokens,
+                             const int32_t* pos0);
 // ---- kh_model_seq_gemm.hip ------------------------------------------------------------------
 // The wide sequence pass (kh_seq_gemm.h): up to KH_SEQ_SLOTS_MAX lanes of distinct slots at full depth with the four
 // weight GEMMs and the classifier on the matrix cores; lane i feeds d_seq_tok[slots[i]] at position pos[i].  Picks

@@ -21,6 +21,7 @@
 #include "kh_prefill.h"
 #include "kh_score_plan.h"
 #include "kh_seq.h"
+#include "kh_seq_prefill.h"
 #include "kh_spec.h"
 #include "kh_w16_pass.h"
 
@@ -501,8 +502,10 @@ PgShape khm::pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_
   return sh;
 }
 namespace {
+// rg: the tokens are the tiles of a pass into sequence slots (kh_seq_prefill.h) - the QKV GEMM is then k_rg_gemm, the
+// same statements under the tile address, in the same launch geometry
 template <bool Q, int EPI>
-bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const KhPgGemmArgs& a) {
+bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const KhPgGemmArgs& a, const KhRgTiles* rg) {
   size_t lds = pg_lds_bytes(wg / 64, sh.NT);
   if (sh.solo && lds < KH_PG_SOLO_LDS) lds = KH_PG_SOLO_LDS;  // one workgroup per CU at a time
   auto opt_in = [&](auto kern, dim3&) { return pg_lds_opt_in((const void*)kern, lds); };
@@ -510,6 +513,12 @@ bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const Kh
   bool ok = false;
   kh_pick(KhVals<0, 1, 2, 3>{}, tile >= 0 ? tile : (sh.R == 2 ? 2 : 3), [&](auto I) {
     constexpr int R = kPgTiles[I][0], NT = kPgTiles[I][1];
+    if constexpr (EPI == KH_PG_QKV) {
+      if (rg) {
+        ok = kh_launch_prep(opt_in, KH_KERNEL(k_rg_gemm, Q, R, NT, EPI), dim3(tiles, sh.slices, sh.kz), wg, lds, s, a, *rg);
+        return;
+      }
+    }
     ok = kh_launch_prep(opt_in, KH_KERNEL(k_pg_gemm, Q, R, NT, EPI), dim3(tiles, sh.slices, sh.kz), wg, lds, s, a);
   });
   return ok;
@@ -517,21 +526,35 @@ bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const Kh
 // returns whether the QKV epilogue rotates q / k itself (else k_pg_rope has to follow); RESID: the
 // number of K slices whose partial rows the next RMSNorm has to add (0 = the epilogue added itself)
 template <int EPI>
-int pg_launch(kh_model* m, int rows_total, bool r2_ok, KhPgGemmArgs a) {
+int pg_launch(kh_model* m, int rows_total, bool r2_ok, KhPgGemmArgs a, const KhRgTiles* rg = nullptr) {
   const bool q = m->cfg.is_quant;
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
   const PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K);
   if (EPI == KH_PG_QKV && a.rope == KH_PG_ROPE_TILES && (sh.R != 2 || sh.NT > 4))
     a.rope = KH_PG_ROPE_OFF;  // no partner tile in the wave / no registers to hold it: k_pg_rope follows
   const int tiles = rows_total / (16 * sh.R);
-  const bool ok = q ? pg_launch_cfg<true, EPI>(sh, tiles, nm * sh.ks * 64, m->stream, a)
-                    : pg_launch_cfg<false, EPI>(sh, tiles, nm * sh.ks * 64, m->stream, a);
+  const bool ok = q ? pg_launch_cfg<true, EPI>(sh, tiles, nm * sh.ks * 64, m->stream, a, rg)
+                    : pg_launch_cfg<false, EPI>(sh, tiles, nm * sh.ks * 64, m->stream, a, rg);
   if (!ok) m->pg_launch_failed = true;  // reported by kh_model_prefill_gemm
   if (EPI == KH_PG_RESID) return sh.kz > 1 ? sh.kz : 0;
   return EPI == KH_PG_QKV && a.rope != KH_PG_ROPE_OFF;
 }
-// forward of T (<= KH_PG_TMAX) prompt tokens at positions pos0..: fills their K/V cache rows
-void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0) {
+// k_rg_attn (kh_seq_prefill.h) in k_pg_attn's launch geometry at one query tile per workgroup, with k_pg_attn's waves
+// per head size; pg_attn_supported(head_size) is the caller's to check
+void launch_rg_attn(const KhPgAttnArgs& a, const KhRgTiles& tiles, int head_size, hipStream_t s) {
+  const int grid = a.kv_heads * a.kv_mul * (a.T / 16);
+  switch (head_size) {
+    case 48: kh_launch(KH_KERNEL(k_rg_attn, 3, 8), grid, 64 * 8, 0, s, a, tiles); break;
+    case 64: kh_launch(KH_KERNEL(k_rg_attn, 4, 8), grid, 64 * 8, 0, s, a, tiles); break;
+    case 128: kh_launch(KH_KERNEL(k_rg_attn, 8, 4), grid, 64 * 4, 0, s, a, tiles); break;
+    default: break;
+  }
+}
+// forward of T (<= KH_PG_TMAX) prompt tokens at positions pos0..: fills their K/V cache rows.
+// rg (kh_seq_prefill.h): the T = 16 x tiles slab tokens are the tiles of a pass into sequence slots instead - toks is
+// the padded token list, pos0 is not read; the QKV GEMM, the RoPE fallback and the attention take the tile table
+// (k_rg_gemm, k_rg_rope, k_rg_attn: MFMA attention only, the caller checked), every other launch is the run's own
+void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0, const KhRgTiles* rg = nullptr) {
   const kh_config& c = m->cfg;
   const bool q = c.is_quant;
   const int tcap = pg_tcap(T);  // token stride of this chunk's tiled slabs
@@ -565,9 +588,13 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
       a.rope = !rope_fuse_env ? KH_PG_ROPE_OFF
                : (c.rope_mode == KH_ROPE_HALF ? (c.head_size % 32 == 0 ? KH_PG_ROPE_TILES : KH_PG_ROPE_OFF)
                                               : KH_PG_ROPE_PAIRS);
-      rope_fused = pg_launch<KH_PG_QKV>(m, c.dim + 2 * c.kv_dim, c.dim % 32 == 0 && c.kv_dim % 32 == 0, a) != 0;
+      rope_fused = pg_launch<KH_PG_QKV>(m, c.dim + 2 * c.kv_dim, c.dim % 32 == 0 && c.kv_dim % 32 == 0, a, rg) != 0;
     }
-    if (!rope_fused) {
+    if (!rope_fused && rg) {
+      launch_log("k_rg_rope");
+      hipLaunchKernelGGL(k_rg_rope, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_q, kc, m->sin_cache,
+                         m->cos_cache, c.dim, c.kv_dim, c.head_size, *rg, c.rope_mode);
+    } else if (!rope_fused) {
       launch_log("k_pg_rope");
       hipLaunchKernelGGL(k_pg_rope, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_q, kc, m->sin_cache,
                          m->cos_cache, c.dim, c.kv_dim, c.head_size, pos0, c.rope_mode);
@@ -580,7 +607,10 @@ void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0
       a.q = m->pg_q; a.kc = kc; a.vc = vc; a.out = m->pg_att;
       a.dim = c.dim; a.kv_dim = c.kv_dim; a.kv_heads = c.kv_head_num; a.kv_mul = c.kv_mul;
       a.T = T; a.pos0 = pos0; a.layout = q ? KH_PA_TILED_Q8 : KH_PA_TILED_F32; a.tcap = tcap;
-      launch_pg_attn(a, c.head_size, m->stream);
+      if (rg)
+        launch_rg_attn(a, *rg, c.head_size, m->stream);
+      else
+        launch_pg_attn(a, c.head_size, m->stream);
     } else {
       KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
       a.defer = 0;  // multi-token slices merge in the launch
@@ -663,6 +693,59 @@ int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32
   }
   for (int t0 = 0; t0 < n; t0 += chunk)
     launch_prefill_gemm_chunk(m, h_tokens + t0, n - t0 < chunk ? n - t0 : chunk, pos0 + t0);
+  if (m->pg_launch_failed) return KH_ERR_UNSUPPORTED;  // a GEMM shape's LDS opt-in was refused
+  return kh_launch_status();
+}
+
+// ---- the GEMM prefill into sequence slots (kh_seq_prefill.h; kh_model_seq.hip checks the call and drives this) -------
+int khm::seq_prefill_gemm_check(const kh_model* m) {
+  // no fallback to the VALU pass, none to the decode-attention slices (KH_PG_ATTN=0 refuses the call)
+  return pg_supported(m) && pg_mfma_attn(m) ? KH_OK : KH_ERR_UNSUPPORTED;
+}
+int khm::seq_prefill_gemm_enqueue(kh_model* m, int n_seq, const int32_t* slots, const int32_t* toks,
+                                  const int32_t* n_tokens, const int32_t* pos0) {
+  int rc;
+  if ((rc = ensure_pg_buffers(m)) != KH_OK) return rc;
+  m->pg_launch_failed = false;
+  std::vector<size_t> seg_at((size_t)n_seq);  // where segment s starts in toks
+  size_t at = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    seg_at[s] = at;
+    at += (size_t)n_tokens[s];
+  }
+  KhRgTiles tiles;
+  int32_t slab_tok[KH_PG_TMAX];
+  int ntiles = 0, cur_pass = 0;
+  auto flush = [&]() {
+    if (ntiles == 0) return;
+    for (int k = ntiles; k < KH_RG_TILES; ++k) {  // entries no slab token reads: the last tile's, as the lane tables pad
+      tiles.pos0[k] = tiles.pos0[ntiles - 1];
+      tiles.nvalid[k] = tiles.nvalid[ntiles - 1];
+      tiles.base[k] = tiles.base[ntiles - 1];
+      tiles.pfx_len[k] = tiles.pfx_len[ntiles - 1];
+      tiles.pfx_row0[k] = tiles.pfx_row0[ntiles - 1];
+    }
+    launch_prefill_gemm_chunk(m, slab_tok, 16 * ntiles, 0, &tiles);
+    ntiles = 0;
+  };
+  kh_rg_plan(n_seq, n_tokens, [&](int pass, int s, int off, int n) {
+    if (pass != cur_pass) {
+      flush();
+      cur_pass = pass;
+    }
+    const KhSeqSlot& t = m->seq_tab[slots[s]];
+    for (int o = 0; o < n; o += 16) {
+      const int k = ntiles++, nv = n - o < 16 ? n - o : 16;
+      tiles.pos0[k] = pos0[s] + off + o;
+      tiles.nvalid[k] = nv;
+      tiles.base[k] = kh_seq_own_base(t);
+      tiles.pfx_len[k] = t.pfx;
+      tiles.pfx_row0[k] = t.pfx > 0 ? m->seq_tab[t.parent].row0 : 0;
+      // the padding tokens of a segment's last tile repeat its last valid token
+      for (int i = 0; i < 16; ++i) slab_tok[16 * k + i] = toks[seg_at[s] + (size_t)(off + o + (i < nv ? i : nv - 1))];
+    }
+  });
+  flush();
   if (m->pg_launch_failed) return KH_ERR_UNSUPPORTED;  // a GEMM shape's LDS opt-in was refused
   return kh_launch_status();
 }

@@ -277,6 +277,71 @@ extern "C" int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_
   return hist_write(m, h_tokens, n, row0 + pos0);  // the slot's fed-token record, as kh_model_prefill from row 0
 }
 
+// Host only: the runs kh_model_seq_prefill_gemm's passes are made of (kh_seq_plan.h: kh_rg_plan)
+extern "C" int kh_plan_seq_prefill_gemm(int32_t n_seq, const int32_t* n_tokens, int32_t* out_runs, int32_t cap_runs,
+                                        int32_t* n_runs, int32_t* n_passes) {
+  if (n_seq <= 0 || !n_tokens || !n_runs || cap_runs < 0 || (cap_runs > 0 && !out_runs)) return KH_ERR_INVALID_ARG;
+  for (int s = 0; s < n_seq; ++s)
+    if (n_tokens[s] <= 0) return KH_ERR_INVALID_ARG;
+  int runs = 0;
+  const int passes = kh_rg_plan(n_seq, n_tokens, [&](int pass, int s, int off, int n) {
+    if (runs < cap_runs) {
+      int32_t* r = out_runs + (size_t)4 * runs;
+      r[0] = pass; r[1] = s; r[2] = off; r[3] = n;
+    }
+    ++runs;
+  });
+  *n_runs = runs;
+  if (n_passes) *n_passes = passes;
+  return runs <= cap_runs ? KH_OK : KH_ERR_RANGE;
+}
+
+// The GEMM prefill into slots (kh_seq_prefill.h).  Every check before the first launch.
+extern "C" int kh_model_seq_prefill_gemm(kh_model* m, int32_t n_seq, const int32_t* slots, const int32_t* h_tokens,
+                                         const int32_t* n_tokens, const int32_t* pos0) {
+  if (!m || !slots || !h_tokens || !n_tokens || !pos0 || n_seq <= 0) return KH_ERR_INVALID_ARG;
+  if (n_seq > KH_SEQ_SLOTS_MAX) return KH_ERR_RANGE;
+  size_t total = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    if (n_tokens[i] <= 0 || pos0[i] < 0) return KH_ERR_INVALID_ARG;
+    if (slots[i] < 0 || slots[i] >= m->seq_slots || (int64_t)pos0[i] + n_tokens[i] > cap(m, slots[i])) return KH_ERR_RANGE;
+    total += (size_t)n_tokens[i];
+  }
+  if (!tokens_in_vocab(m, h_tokens, total)) return KH_ERR_RANGE;
+  for (int i = 0; i < n_seq; ++i) {
+    // a sharer below its shared length, a parent's shared rows
+    if (writes_shared(m, slots[i], pos0[i])) return KH_ERR_INVALID_ARG;
+    for (int j = 0; j < n_seq; ++j) {
+      if (j < i && slots[j] == slots[i]) return KH_ERR_INVALID_ARG;  // two segments of one slot cannot share a call
+      // a sharer with its parent: the parent is fed by an earlier call
+      if (slot_of(m, slots[i]).pfx > 0 && slot_of(m, slots[i]).parent == slots[j]) return KH_ERR_INVALID_ARG;
+    }
+  }
+  int rc;
+  if ((rc = seq_prefill_gemm_check(m)) != KH_OK) return rc;
+  return kh_api_guard([&]() -> int {
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    for (int i = 0; i < n_seq; ++i)
+      if ((rc = ensure_slot_rows(m, slots[i], pos0[i] + n_tokens[i])) != KH_OK) return rc;
+    rc = seq_prefill_gemm_enqueue(m, n_seq, slots, h_tokens, n_tokens, pos0);
+    // every segment's fed tokens at its slot's rows of the history, as kh_model_seq_prefill's hist_write; pageable
+    // source: the sync keeps the caller's array alive for the uploads (and drains the passes on every way out)
+    const int32_t* seg = h_tokens;
+    for (int i = 0; i < n_seq && rc == KH_OK; ++i) {
+      const int64_t at = (int64_t)own_base(m, slots[i]) + pos0[i];
+      if (at < 0 || at + n_tokens[i] > m->hist_cap)
+        rc = KH_ERR_RANGE;
+      else
+        rc = (int)hipMemcpyAsync(m->d_hist + at, seg, sizeof(int32_t) * (size_t)n_tokens[i], hipMemcpyHostToDevice,
+                                 m->stream);
+      seg += n_tokens[i];
+    }
+    const hipError_t e = hipStreamSynchronize(m->stream);
+    if (rc != KH_OK) return rc;
+    return e == hipSuccess ? KH_OK : (int)e;
+  });
+}
+
 extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot, int32_t n_rows) {
   if (!m || n_rows <= 0 || src_slot == dst_slot) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;

@@ -45,6 +45,33 @@ static inline int kh_seq_capacity(const KhSeqSlot& t) { return t.pfx + t.len; }
 // the row of position p >= t.pfx is kh_seq_own_base(t) + p; negative for a sharer near the start of the cache
 static inline int kh_seq_own_base(const KhSeqSlot& t) { return t.row0 - t.pfx; }
 
+// The passes of the GEMM prefill into slots (kh_seq_prefill.h; kh_plan_seq_prefill_gemm).  A pass has KH_RG_TILES token
+// tiles of 16; a segment of n tokens takes ceil(n / 16) of them.  Segments are walked in call order: one that fits in
+// what is left of the pass is placed whole, else its first 16 x free tokens fill the pass (if a tile is free) and the
+// rest continues in the next - the split of the batch-1 GEMM prefill's 512-token chunks.
+// f(pass, segment, first token offset, count) per placed run; returns the number of passes.
+#define KH_RG_TILES 32
+template <class F>
+static inline int kh_rg_plan(int n_seq, const int32_t* n_tokens, F&& f) {
+  int pass = 0, used = 0;  // tiles taken in the current pass
+  for (int s = 0; s < n_seq; ++s) {
+    int off = 0, left = n_tokens[s];
+    while (left > 0) {
+      if (used == KH_RG_TILES) {
+        ++pass;
+        used = 0;
+      }
+      const int room = 16 * (KH_RG_TILES - used);
+      const int n = left <= room ? left : room;
+      f(pass, s, off, n);
+      used += (n + 15) / 16;
+      off += n;
+      left -= n;
+    }
+  }
+  return used > 0 ? pass + 1 : pass;
+}
+
 // The lanes of the next pass.  Sequence s is live while pos[s] < total[s] and it has not been seen to stop.  Rounds
 // walk the sequences in slot order; a pass takes the next up to `width` live ones from the cursor on and never wraps
 // (a sequence sits in at most one lane of a pass), the cursor goes back to 0 behind the last sequence.  More than

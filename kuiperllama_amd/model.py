@@ -146,6 +146,21 @@ def plan_seq_batch(first_pos: Sequence[int], total_steps: Sequence[int], width: 
     return [[int(x) for x in out[p * width:(p + 1) * width] if x >= 0] for p in range(n.value)]
 
 
+def plan_seq_prefill_gemm(n_tokens: Sequence[int]) -> List[Tuple[int, int, int, int]]:
+    """The runs seq_prefill_many's passes are made of (kh_plan_seq_prefill_gemm; host only): per placed run (pass,
+    segment, first token offset, count).  A pass has 32 token tiles of 16; a segment that fits in what is left of the
+    pass is placed whole, else its first 16 x free tokens fill the pass and the rest continues in the next."""
+    n_tokens = [int(n) for n in n_tokens]
+    n, L = C.c_int32(0), _ffi.lib()
+    rc = L.kh_plan_seq_prefill_gemm(len(n_tokens), _i32_array(n_tokens), None, 0, C.byref(n), None)
+    if rc not in (0, _ffi.KH_ERR_RANGE):
+        raise _ffi.KhError(rc, "kh_plan_seq_prefill_gemm")
+    out = (C.c_int32 * max(4 * n.value, 1))()
+    _ffi.check(L.kh_plan_seq_prefill_gemm(len(n_tokens), _i32_array(n_tokens), out, n.value, C.byref(n), None),
+               "kh_plan_seq_prefill_gemm")
+    return [tuple(int(x) for x in out[4 * r:4 * r + 4]) for r in range(n.value)]
+
+
 def lookup_draft(seq: Sequence[int], hint: Optional[Sequence[int]] = None, ngram_max: int = 4, ngram_min: int = 1,
                  cap: int = 7) -> List[int]:
     """The drafter of generate_lookup (kh_lookup_draft; host only, no device): up to `cap` tokens that followed the
@@ -588,11 +603,35 @@ class KuiperModel:
                    "kh_model_seq_gemm_logits")
         return out
 
-    def seq_prefill(self, slot: int, tokens: Sequence[int], pos0: int = 0) -> None:
-        """prefill() on the rows of sequence slot `slot` (kh_model_seq_prefill)."""
+    def seq_prefill(self, slot: int, tokens: Sequence[int], pos0: int = 0, gemm: bool = False) -> None:
+        """prefill() on the rows of sequence slot `slot` (kh_model_seq_prefill).
+        gemm=True: as one segment of seq_prefill_many - the MFMA GEMM pass, prefill_gemm()'s contract, not bit-exact."""
+        if gemm:
+            return self.seq_prefill_many([slot], [tokens], [pos0])
         _ffi.check(_ffi.lib().kh_model_seq_prefill(self._h, int(slot), _i32_array(tokens), len(tokens), int(pos0)),
                    "kh_model_seq_prefill")
         torch.cuda.synchronize()
+
+    def seq_prefill_many(self, slots: Sequence[int], prompts: Sequence[Sequence[int]],
+                         pos0: Optional[Sequence[int]] = None) -> None:
+        """Prompt segments of several slots in shared GEMM passes on the matrix cores (kh_model_seq_prefill_gemm):
+        prompts[i] is fed at positions pos0[i] .. (None: 0) of slot slots[i], up to 512 slab tokens - 32 tiles of 16,
+        a tile belongs to one segment - per sweep of the weights (plan_seq_prefill_gemm shows the passes).  Distinct
+        slots; a sharer is fed from its shared length on and not together with its parent.  prefill_gemm()'s contract:
+        K/V rows equal the token-by-token ones to fp32 round-off; no logits.  KhError where the pass does not run
+        (there is no fallback to seq_prefill)."""
+        slots, prompts = [int(s) for s in slots], [list(p) for p in prompts]
+        pos0 = [0] * len(slots) if pos0 is None else [int(p) for p in pos0]
+        if len(prompts) != len(slots) or len(pos0) != len(slots):
+            raise ValueError(f"seq_prefill_many: {len(slots)} slots, {len(prompts)} prompts, {len(pos0)} positions")
+        if not slots or any(len(p) == 0 for p in prompts):
+            raise ValueError("seq_prefill_many: no segment, or an empty one")
+        _ffi.sync_env()  # KH_PG_*
+        _ffi.check(_ffi.lib().kh_model_seq_prefill_gemm(
+            self._h, len(slots), _i32_array(slots), _i32_array([t for p in prompts for t in p]),
+            _i32_array([len(p) for p in prompts]), _i32_array(pos0)), "kh_model_seq_prefill_gemm")
+
+    plan_seq_prefill_gemm = staticmethod(plan_seq_prefill_gemm)
 
     def seq_fork(self, src_slot: int, dst_slot: int, n_rows: int) -> None:
         """Copy K/V rows [0, n_rows) of every layer from one slot to another (kh_model_seq_fork)."""
@@ -639,7 +678,8 @@ class KuiperModel:
     def generate_batch(self, prompts: Sequence[Sequence[int]], total_steps, samplings: Optional[Sequence] = None,
                        stop: Sequence[int] = (), cached: Optional[Sequence[int]] = None,
                        penalties: Optional[Sequence] = None, logit_bias: Optional[Sequence] = None,
-                       logprobs: Optional[int] = None, gemm: bool = False) -> Tuple[List[List[int]], float]:
+                       logprobs: Optional[int] = None, gemm: bool = False,
+                       gemm_prefill: bool = False) -> Tuple[List[List[int]], float]:
         """generate() for len(prompts) <= n_slots sequences at once, sequence s in slot s (kh_model_generate_batch):
         seq_width() sequences share every pass over the weights.  total_steps: one int for all or one per sequence;
         samplings: None (all greedy) or one entry per sequence (None | dict of temperature / top_k / top_p / seed).
@@ -652,7 +692,10 @@ class KuiperModel:
         model's own set_* values are not consulted.  With all three None this is the plain call.
         gemm=True: the sampled part runs as wide passes on the matrix cores (kh_model_generate_batch_gemm), up to 64
         sequences per pass over the weights.  Not bit-identical: greedy words can differ from generate()'s at
-        near-ties, sampled words are the sampler's on the pass's own logits."""
+        near-ties, sampled words are the sampler's on the pass's own logits.
+        gemm_prefill=True (orthogonal to gemm=): the fed-only part of every prompt that is not cached yet goes through
+        one seq_prefill_many first - GEMM passes shared between the sequences instead of seq_prefill's passes per
+        sequence - and the call then runs with cached = len(prompt) - 1.  prefill_gemm()'s contract for those rows."""
         prompts = [list(p) for p in prompts]
         n = len(prompts)
         totals = [int(total_steps)] * n if isinstance(total_steps, (int, np.integer)) else [int(t) for t in total_steps]
@@ -664,6 +707,13 @@ class KuiperModel:
         if cached is not None and len(cached) != n:
             raise ValueError(f"generate_batch: {len(cached)} cached counts for {n} prompts")
         st = list(stop or [])
+        if gemm_prefill:
+            have = [0] * n if cached is None else [int(c) for c in cached]
+            fed = [min(len(p) - 1, t) for p, t in zip(prompts, totals)]
+            todo = [s for s in range(n) if fed[s] > have[s]]
+            if todo:
+                self.seq_prefill_many(todo, [prompts[s][have[s]:fed[s]] for s in todo], [have[s] for s in todo])
+            cached = [max(f, h) for f, h in zip(fed, have)]
         stride = max(max(totals), 1)
         words = (C.c_int32 * (n * stride))()
         nw = (C.c_int32 * n)()
@@ -713,7 +763,7 @@ class KuiperModel:
 
     def best_of(self, prompt: Sequence[int], n: int, total_steps: int, sampling: dict, stop: Sequence[int] = (),
                 penalties: Optional[dict] = None, logit_bias: Optional[dict] = None, top_n: int = 0,
-                share: bool = False, gemm: bool = False) -> List[dict]:
+                share: bool = False, gemm: bool = False, gemm_prefill: bool = False) -> List[dict]:
         """n samples of one prompt, best first: one seq_prefill of the prompt's fed-only part into slot 0, n - 1
         seq_forks, one generate_batch(cached=..) with seeds seed, seed + 1, .. of `sampling` (and the shared penalties
         / logit_bias), then seq_rank on the sampled positions' log-probs.  Returns [{"words", "mean_logprob", "seed"}]
@@ -723,7 +773,8 @@ class KuiperModel:
         seq_share calls on plan_shared_layout(cfg.cache_len, ..) - so n samples need prompt + n * generated rows, not
         n * (prompt + generated).  Same words and records; penalties are refused on sharing slots.
         gemm=True: the samples decode as wide passes (generate_batch(gemm=True)), up to 64 per pass over the weights;
-        sample i is then the sampler's on the wide pass's logits, equal to generate()'s to fp32 round-off."""
+        sample i is then the sampler's on the wide pass's logits, equal to generate()'s to fp32 round-off.
+        gemm_prefill=True: the one prefill is seq_prefill(.., gemm=True), the GEMM pass on the matrix cores."""
         prompt, n, total_steps = [int(t) for t in prompt], int(n), int(total_steps)
         if n <= 0 or not prompt:
             raise ValueError("best_of: no sample, or an empty prompt")
@@ -737,7 +788,7 @@ class KuiperModel:
         elif self._seq_slots < n:
             self.seq_slots(n)
         if fed > 0:
-            self.seq_prefill(0, prompt[:fed])
+            self.seq_prefill(0, prompt[:fed], gemm=bool(gemm_prefill))
             for s in range(1, n):
                 if share:
                     self.seq_share(0, s, fed)

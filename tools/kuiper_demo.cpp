@@ -17,7 +17,7 @@
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
 //               [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]
-//               [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix]
+//               [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -57,6 +57,9 @@
 // --share-prefix (beside --parallel / --best-of): the samples read the prompt's rows from slot 0 instead of holding
 // copies (kh_model_seq_slots_var / kh_model_seq_share): prompt + N x generated rows of cache, not N x (prompt +
 // generated).  Same ids; penalties are refused on the sharing slots, as by the library.
+// --gemm-prefill (beside --parallel / --best-of): the one prefill of the prompt into slot 0 is the GEMM pass on the
+// matrix cores (kh_model_seq_prefill_gemm, one segment): its rows equal the plain run's to fp32 round-off.  Refused
+// where the library refuses it; there is no fallback.
 // Prints the generated ids and "steps/s" like demo/main.cpp:70-72.
 #include <cmath>
 #include <chrono>
@@ -82,6 +85,13 @@ static int seq_attach(kh_model* m, int s, int have, bool share) {
   return share ? kh_model_seq_share(m, 0, s, have) : kh_model_seq_fork(m, 0, s, have);
 }
 
+// the prompt's fed-only part into slot 0: kh_model_seq_prefill, or with --gemm-prefill the one-segment GEMM call
+static int seq_feed_prompt(kh_model* m, const std::vector<int32_t>& prompt, int have, bool gemm) {
+  if (!gemm) return kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
+  const int32_t slot = 0, n = have, pos0 = 0;
+  return kh_model_seq_prefill_gemm(m, 1, &slot, prompt.data(), &n, &pos0);
+}
+
 static void usage() {
   std::fprintf(stderr,
                "usage: kuiper_demo model.bin [--family llama|qwen2] [--quant] [--rope interleaved|half]\n"
@@ -92,7 +102,7 @@ static void usage() {
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
                "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]\n"
-               "       [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix]\n");
+               "       [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]\n");
 }
 
 int main(int argc, char** argv) {
@@ -114,6 +124,7 @@ int main(int argc, char** argv) {
   kh_lookup_opts lk{0, 0, 0, nullptr, 0};
   int parallel = 0;  // --parallel N (kh_model_generate_batch)
   bool gemm_batch = false;  // --gemm-batch (kh_model_generate_batch_gemm)
+  bool gemm_prefill = false;  // --gemm-prefill (kh_model_seq_prefill_gemm)
   int best_of = 0;   // --best-of N (kh_model_generate_batch_ex, kh_seq_rank)
   bool share_prefix = false;  // --share-prefix: the samples read the prompt's rows from slot 0 (kh_model_seq_share)
   std::vector<int32_t> hint;  // --hint
@@ -158,6 +169,7 @@ int main(int argc, char** argv) {
     else if (a == "--score") score = true;
     else if (a == "--parallel") parallel = std::atoi(next());
     else if (a == "--gemm-batch") gemm_batch = true;
+    else if (a == "--gemm-prefill") gemm_prefill = true;
     else if (a == "--best-of") best_of = std::atoi(next());
     else if (a == "--share-prefix") share_prefix = true;
     else if (a == "--lookup" || a == "--lookup-as-set") {
@@ -199,6 +211,11 @@ int main(int argc, char** argv) {
       usage();
       return 2;
     }
+  }
+  if (gemm_prefill && parallel <= 0 && best_of <= 0) {  // it is the prefill of the slots of those two runs
+    std::fprintf(stderr, "--gemm-prefill goes beside --parallel N or --best-of N\n");
+    usage();
+    return 2;
   }
   kh_spm* tok = nullptr;
   if (tok_path) {
@@ -359,7 +376,7 @@ int main(int argc, char** argv) {
     std::printf("Generating...\n");
     const auto t0 = std::chrono::steady_clock::now();
     rc = seq_layout(m, N, have, steps, share_prefix, &slot_len);
-    if (rc == KH_OK && have > 0) rc = kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
+    if (rc == KH_OK && have > 0) rc = seq_feed_prompt(m, prompt, have, gemm_prefill);
     for (int s = 1; s < N && rc == KH_OK && have > 0; ++s) rc = seq_attach(m, s, have, share_prefix);
     if (rc == KH_OK)
       rc = kh_model_generate_batch_ex(m, N, prompts.data(), n_prompt.data(), cached.data(), totals.data(), &so,
@@ -410,7 +427,7 @@ int main(int argc, char** argv) {
     const auto t0 = std::chrono::steady_clock::now();
     rc = seq_layout(m, parallel, have, steps, share_prefix, &slot_len);
     if (rc == KH_OK) rc = gemm_batch ? kh_model_seq_width_gemm(m, &width) : kh_model_seq_width(m, &width);
-    if (rc == KH_OK && have > 0) rc = kh_model_seq_prefill(m, 0, prompt.data(), have, 0);
+    if (rc == KH_OK && have > 0) rc = seq_feed_prompt(m, prompt, have, gemm_prefill);
     for (int s = 1; s < parallel && rc == KH_OK && have > 0; ++s) rc = seq_attach(m, s, have, share_prefix);
     if (rc == KH_OK && gemm_batch) {
       kh_seq_opts so{};
