@@ -879,7 +879,7 @@ int kh_model_seq_prefill_gemm(kh_model* m, int32_t n_seq, const int32_t* slots, 
  * kh_plan_decode_shapes: {split, u, grid, wg} of the five GEMV kernels of a decode step (qkv, wo, ffn13, w2,
  * cls) for a geometry - what kh_model_create_* configures (env KH_SHAPE_* overrides included).
  * kh_plan_prefill_shape: {R, NT, ks, token slices, solo, kz, workgroups} of one GEMM of a T-token prefill
- * pass (epi 0 = QKV, 1 = residual GEMM wo / w2, 2 = SwiGLU pair; csrc/kh_model_prefill.hip::pg_shape). */
+ * pass (epi 0 = QKV, 1 = residual GEMM wo / w2, 2 = SwiGLU pair; csrc/kh_model_gemm.hip::pg_shape). */
 int kh_plan_decode_shapes(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size,
                           int32_t is_quant, int32_t* out20);
 /* kh_plan_decode_ring: out4 = {ffn13 ring slots per wave, ffn13 workgroups, cls ring slots, cls workgroups} - which

@@ -28,7 +28,7 @@
 //     consecutive output rows of one token, which is exactly what the epilogues store.
 //   * a workgroup = ks waves that split K (fixed-order LDS reduction, deterministic), times two
 //     for the (w1, w3) SwiGLU pair; blockIdx.y selects a slice of 16*NT tokens.  (R, NT, ks, kz) are
-//     chosen per GEMM by the cost model of kh_model_prefill.hip::pg_shape (one wave per SIMD for
+//     chosen per GEMM by the cost model of kh_model_gemm.hip::pg_shape (one wave per SIMD for
 //     fp32, two or three for int8; launches above 256 workgroups one workgroup per CU at a time).
 //   * operand feeding: the fp32 loops request weights AND activations of block b + D together when
 //     block b has been consumed (pg_kloop_f32_ring, D = 8 for the small tiles, 2 for the (2,8) tile);
@@ -383,17 +383,11 @@ __global__ __launch_bounds__(KH_WG) void k_pg_rmsnorm(float* __restrict__ X,
   for (int k = (int)threadIdx.x + KEEP * KH_WG; k < n4; k += KH_WG) emit(k, x4[k]);
 }
 
-// RoPE of the T query rows and of the T fresh key rows, in place (cpu/rope_kernel.cpp:18-42 half,
-// :98-121 interleaved); token t sits at position pos0 + t.  blockIdx.x = token.
-static __global__ __launch_bounds__(KH_WG) void k_pg_rope(float* __restrict__ Q, float* __restrict__ kc,
-                                                   const float* __restrict__ sin_cache,
-                                                   const float* __restrict__ cos_cache, int dim,
-                                                   int kv_dim, int hs, int pos0, int mode) {
-  const int t = blockIdx.x, pos = pos0 + t;
-  float* q = Q + (size_t)t * dim;
-  float* k = kc + (size_t)pos * kv_dim;
-  const float* sn = sin_cache + (size_t)pos * hs;
-  const float* cs = cos_cache + (size_t)pos * hs;
+// One token's RoPE (cpu/rope_kernel.cpp:18-42 half, :98-121 interleaved): its query row q[dim] and its fresh key row
+// k[kv_dim] rotated in place by the sin / cos rows sn / cs [hs] of its position, the pairs spread over the workgroup.
+// The body of k_pg_rope and of its twins over a lane table (kh_seq_gemm.h) and a tile table (kh_seq_prefill.h).
+static __device__ __forceinline__ void pg_rope_token(float* q, float* k, const float* sn, const float* cs, int dim,
+                                                     int kv_dim, int hs, int mode) {
   const int npq = dim >> 1, npk = kv_dim >> 1, half = hs >> 1;
   for (int p = threadIdx.x; p < npq + npk; p += KH_WG) {
     float* v = p < npq ? q : k;
@@ -414,4 +408,14 @@ static __global__ __launch_bounds__(KH_WG) void k_pg_rope(float* __restrict__ Q,
     v[r0] = v0 * fcr - v1 * fci;
     v[r1] = v0 * fci + v1 * fcr;
   }
+}
+// RoPE of the T query rows and of the T fresh key rows, in place; token t sits at position pos0 + t.
+// blockIdx.x = token.
+static __global__ __launch_bounds__(KH_WG) void k_pg_rope(float* __restrict__ Q, float* __restrict__ kc,
+                                                   const float* __restrict__ sin_cache,
+                                                   const float* __restrict__ cos_cache, int dim,
+                                                   int kv_dim, int hs, int pos0, int mode) {
+  const int t = blockIdx.x, pos = pos0 + t;
+  pg_rope_token(Q + (size_t)t * dim, kc + (size_t)pos * kv_dim, sin_cache + (size_t)pos * hs,
+                cos_cache + (size_t)pos * hs, dim, kv_dim, hs, mode);
 }

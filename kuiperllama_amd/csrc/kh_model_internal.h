@@ -1,12 +1,14 @@
 // kh_model_internal.h — state and cross-unit helpers of the model level of the C-ABI.
-// The model level is split into ten translation units:
+// The model level is split into eleven translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
 //                         template parameter, picked from and launched through kh_dispatch.h)
-//   kh_model_prefill.hip  B-token VALU prefill and the MFMA GEMM prefill (kh_prefill.h, kh_gemm.h,
-//                         kh_pattn.h kernels), the B-lane pass over different sequences (kh_seq.h kernels) and the
-//                         twins of the B-token kernels on the 16-bit copy (kh_w16_pass.h)
+//   kh_model_prefill.hip  the B-token VALU pass (kh_prefill.h kernels) and what runs on it: prefill, scoring, verify,
+//                         the B-lane pass over different sequences (kh_seq.h kernels) and the twins of the B-token
+//                         kernels on the 16-bit copy (kh_w16_pass.h)
+//   kh_model_gemm.hip     what runs on the GEMM slabs (kh_gemm.h, kh_pattn.h, kh_seq_prefill.h, kh_seq_gemm.h kernels):
+//                         the MFMA prompt prefill, its form into sequence slots and the wide sequence pass
 //   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
 //                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
@@ -194,7 +196,6 @@ struct kh_model {
   KhDev<float> pg_part;         // partial rows of residual GEMMs that split K across workgroups
   KhDev<char> pg_ws;            // KH_PG_TMAX attention split workspaces (the first pass that takes the fallback)
   size_t pg_ws_tok_bytes = 0;
-  bool pg_launch_failed = false;
   // the wide sequence pass (kh_seq_gemm.h): logits rows [KH_SEQ_SLOTS_MAX][pf_vstride] of its classifier GEMM, made by
   // the first wide call; sg_lanes: the lane count of the last wide pass (0: none yet)
   KhDev<float> sg_logits;
@@ -489,10 +490,8 @@ int kv_ensure_rows(kh_model* m, int row0, int row_end);  // rows [row0, row_end)
 int run_selftests(kh_model* m);
 // ---- kh_model_prefill.hip -------------------------------------------------------------------
 bool prefill_supported(const kh_model* m);  // B-token VALU path
-bool pg_supported(const kh_model* m);       // MFMA GEMM path
-// kh_model_prefill / kh_model_prefill_gemm without the token record (hist_write)
+// kh_model_prefill without the token record (hist_write)
 int prefill_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
-int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
 // Full-depth passes (kh_model_score, kh_model_verify): the geometries they run on, and the tokens of one pass
 bool full_depth_supported(const kh_model* m);
 int verify_width(const kh_model* m);
@@ -528,28 +527,23 @@ int seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, const KhS
 // prefix; the B-token pass's workspace), and the tail on logits rows [n][pf_vstride] (k_seq_pick, or k_seq_tail)
 void seq_attn_enqueue(kh_model* m, int l, const float* q, float* out, const KhSeqLanes& lanes, int n);
 int seq_tail_enqueue(kh_model* m, float* logits, const KhSeqLanes& lanes, int n, bool words, const KhSeqTail* tail);
-// GEMM prefill machinery shared with the wide sequence pass (kh_model_seq_gemm.hip): the slabs, the launch shape of
-// one GEMM (cost model pg_shape; pg_plan adds the KH_PG_SHAPE_* hooks, epi = KH_PG_*) and the per-(device, kernel)
-// opt-in for more than 48 KiB of dynamic LDS
-struct PgShape {
-  int R, NT, ks, slices;
-  bool solo;
-  int kz;
-};
-int ensure_pg_buffers(kh_model* m);
-PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant,
-                 bool allow_kz = false);
-PgShape pg_plan(const kh_model* m, int epi, int T, int rows_total, bool r2_ok, int K);
-bool pg_lds_opt_in(const void* kern, size_t lds);
+// fill_attn(m, l, 0, m->attn_fenced) as the arguments of a multi-token slice (launch_attn_decode with tokens > 1,
+// launch_seq_attn[_pfx]): token t's q / out rows at q / out + t * dim, its split workspace at ws + t * ws_tok_bytes
+KhAttnArgs attn_slice_args(kh_model* m, int l, const float* q, float* out, void* ws, size_t ws_tok_bytes);
+// ---- kh_model_gemm.hip ----------------------------------------------------------------------
+bool pg_supported(const kh_model* m);  // MFMA GEMM path
+// kh_model_prefill_gemm without the token record (hist_write); prefill_gemm_prepare: its slabs, made by the call
+// itself or ahead of it by whoever times it
+int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
+int prefill_gemm_prepare(kh_model* m);
 // The GEMM prefill into sequence slots (kh_seq_prefill.h; kh_model_seq_prefill_gemm).  _check: KH_OK where the pass
 // runs - the GEMM prefill's geometries with an MFMA attention instantiation for the head size and KH_PG_ATTN not 0 -,
 // else KH_ERR_UNSUPPORTED.  _enqueue: the planned passes (kh_rg_plan) for segment s = n_tokens[s] tokens of the
-// concatenated toks at positions pos0[s] .. of slot slots[s]; the slabs are ensure_pg_buffers'.  Arguments and the
-// slots' rows (ensure_slot_rows) are the caller's to check.
+// concatenated toks at positions pos0[s] .. of slot slots[s]; it makes the slabs.  Arguments and the slots' rows
+// (ensure_slot_rows) are the caller's to check.
 int seq_prefill_gemm_check(const kh_model* m);
 int seq_prefill_gemm_enqueue(kh_model* m, int n_seq, const int32_t* slots, const int32_t* toks, const int32_t* n_tokens,
                              const int32_t* pos0);
-// ---- kh_model_seq_gemm.hip ------------------------------------------------------------------
 // The wide sequence pass (kh_seq_gemm.h): up to KH_SEQ_SLOTS_MAX lanes of distinct slots at full depth with the four
 // weight GEMMs and the classifier on the matrix cores; lane i feeds d_seq_tok[slots[i]] at position pos[i].  Picks
 // land as seq_pass_enqueue's.  seq_gemm_supported: the geometries it runs on; seq_gemm_prepare: its buffers, behind

@@ -2,9 +2,9 @@
 // token-by-token; ONE layer driver, launch_pf_pass) and what runs on it - the prompt prefill, sequence scoring
 // (kh_model_score: k_pf_cls, k_score_lp), the verify pass of speculative decode (kh_model_verify[_as_set]: k_pf_cls,
 // kh_spec.h) and the pass over lanes of different sequences (kh_seq.h; kh_model_seq.hip drives it); for a W16 model
-// the launch classes of its pass mask run on the 16-bit copy (kh_w16_pass.h, the w16_pf_* launchers) - and the
-// fp32-MFMA GEMM prefill (kh_gemm.h, kh_pattn.h), which always reads fp32.  The
-// reference feeds the prompt one token per forward pass (demo/main.cpp:20-22).
+// the launch classes of its pass mask run on the 16-bit copy (kh_w16_pass.h, the w16_pf_* launchers).  What runs on
+// the GEMM slabs lives in kh_model_gemm.hip.  The reference feeds the prompt one token per forward pass
+// (demo/main.cpp:20-22).
 // gfx950 only.
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,15 +13,12 @@
 #include <vector>
 
 #include "kh_dispatch.h"
-#include "kh_gemm.h"
 #include "kh_logprobs.h"
 #include "kh_model_internal.h"
-#include "kh_pattn.h"
 #include "kh_pf_launch.h"
 #include "kh_prefill.h"
 #include "kh_score_plan.h"
 #include "kh_seq.h"
-#include "kh_seq_prefill.h"
 #include "kh_spec.h"
 #include "kh_w16_pass.h"
 
@@ -43,13 +40,19 @@ bool prefill_supported(const kh_model* m) {
 bool full_depth_supported(const kh_model* m) {
   return prefill_supported(m) && kh_stage_fits4(m->cfg.dim, m->sh_cls.wg);
 }
-bool pg_supported(const kh_model* m) {
-  const kh_config& c = m->cfg;
-  if (c.head_size <= 32) return false;  // attention: the fast multi-token decode kernel
-  const int kq = c.is_quant ? 64 : 16;  // K granule of one MFMA operand load
-  if (c.dim % kq || c.hidden_dim % kq || c.dim % 16 || c.kv_dim % 16 || c.hidden_dim % 16) return false;
-  if (c.is_quant && m->gshift != 6) return false;
-  return true;
+// fill_attn's decode arguments as those of a multi-token slice: q / out rows of dim floats per token, one split
+// workspace of ws_tok_bytes per token
+KhAttnArgs attn_slice_args(kh_model* m, int l, const float* q, float* out, void* ws, size_t ws_tok_bytes) {
+  KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
+  a.defer = 0;  // multi-token slices merge in the launch
+  a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: the launch plan decides from the slices' positions
+  a.q = q;
+  a.out = out;
+  a.d_pos = nullptr;
+  a.ws = ws;
+  a.tok_stride = m->cfg.dim;
+  a.ws_tok_bytes = ws_tok_bytes;
+  return a;
 }
 }  // namespace khm
 
@@ -209,22 +212,11 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
     // the prompt phase leaves K/V rows and nothing else (no logits): the last layer's K/V rows are
     // written, its attention, wo and FFN feed nothing - unless the classifier follows (full_depth)
     if (l == c.layer_num - 1 && !p.full_depth) break;
-    {
-      KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
-      a.defer = 0;  // multi-token slices merge in the launch
-      a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: the launch plan decides from the slices' positions
-      a.q = m->pf_q;
-      a.out = m->pf_att;
-      a.d_pos = nullptr;
-      a.ws = m->pf_ws;
-      a.tok_stride = c.dim;
-      a.ws_tok_bytes = m->pf_ws_tok_bytes;
-      if (p.lanes) {
-        if (seq_lanes_share(*p.lanes, nvalid))
-          launch_seq_attn_pfx(a, *p.lanes, nvalid, m->attn_wg, m->stream, m->seq_pfx_pad8);
-        else
-          launch_seq_attn(a, *p.lanes, nvalid, m->attn_wg, m->stream);
-      } else if (p.pfx_len > 0) {
+    if (p.lanes) {
+      seq_attn_enqueue(m, l, m->pf_q, m->pf_att, *p.lanes, nvalid);
+    } else {
+      KhAttnArgs a = attn_slice_args(m, l, m->pf_q, m->pf_att, m->pf_ws, m->pf_ws_tok_bytes);
+      if (p.pfx_len > 0) {
         KhSeqLanes run;
         for (int b = 0; b < KH_PF_BMAX; ++b) {
           const int bb = b < nvalid ? b : nvalid - 1;
@@ -311,467 +303,6 @@ void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0,
   hipLaunchKernelGGL(k_score_lp, dim3(nvalid), dim3(KH_SAMP_THREADS), 0, m->stream, t);
 }
 }  // namespace
-
-// ---- GEMM prefill (kh_gemm.h) ------------------------------------------------------------------
-int khm::ensure_pg_buffers(kh_model* m) {
-  if (m->pg_x) return KH_OK;
-  const kh_config& c = m->cfg;
-  const size_t T = KH_PG_TMAX;
-  int rc;
-  auto zalloc = [&](KhDev<float>& b, size_t n) -> int {
-    if ((rc = b.alloc(n)) != KH_OK) return rc;
-    // rows beyond the valid tokens are read as MFMA operands (their columns are discarded):
-    // they must hold finite numbers
-    return (int)hipMemsetAsync(b, 0, n * sizeof(float), m->stream);
-  };
-  // a failure half-way leaves the model without any slab: a later call starts over
-  KhDev<float> x, xn, q, att, h, part;
-  if ((rc = zalloc(x, T * c.dim)) != KH_OK || (rc = zalloc(xn, T * c.dim)) != KH_OK ||
-      (rc = zalloc(q, T * c.dim)) != KH_OK || (rc = zalloc(att, T * c.dim)) != KH_OK ||
-      (rc = zalloc(h, T * c.hidden_dim)) != KH_OK ||
-      (rc = zalloc(part, (size_t)KH_PG_KZ_MAX * T * c.dim)) != KH_OK)  // K-slice partial rows
-    return rc;
-  m->pg_x = std::move(x);
-  m->pg_xn = std::move(xn);
-  m->pg_q = std::move(q);
-  m->pg_att = std::move(att);
-  m->pg_h = std::move(h);
-  m->pg_part = std::move(part);
-  return KH_OK;
-}
-namespace {
-// does the prompt-slice attention run on the MFMA kernel (kh_pattn.h)?  KH_PG_ATTN=0 forces the fallback.
-bool pg_mfma_attn(const kh_model* m) { return !dbg_off("KH_PG_ATTN") && pg_attn_supported(m->cfg.head_size); }
-// The split workspace of the decode-attention FALLBACK (one per token of a pass, ~270 KB per token at
-// Llama-3.2-1B geometry: 136 MB for a 512-token pass).  Every BASELINE head size has an MFMA
-// instantiation, so it is allocated on the first pass that actually takes the fallback.
-int ensure_pg_ws(kh_model* m) {
-  if (m->pg_ws || pg_mfma_attn(m)) return KH_OK;
-  m->pg_ws_tok_bytes = (attn_ws_bytes(m->cfg.head_num, m->cfg.head_size, m->attn_ws_stride) + 255) & ~(size_t)255;
-  if (!m->pg_ws_tok_bytes) return KH_OK;
-  KhDev<char> ws;
-  int rc;
-  if ((rc = ws.alloc(m->pg_ws_tok_bytes * (size_t)KH_PG_TMAX)) != KH_OK) return rc;
-  KH_CHECK_HIP(hipMemsetAsync(ws, 0, m->pg_ws_tok_bytes * (size_t)KH_PG_TMAX, m->stream));
-  m->pg_ws = std::move(ws);
-  return KH_OK;
-}
-// the (R, NT) register tiles k_pg_gemm is compiled for, and the waves per SIMD that fit with each
-constexpr int kPgTiles[4][3] = {{2, 8, 2}, {2, 4, 3}, {2, 2, 4}, {1, 4, 4}};
-constexpr int pg_tile(int R, int NT) {  // index in kPgTiles, -1: no such tile
-  for (int i = 0; i < 4; ++i)
-    if (kPgTiles[i][0] == R && kPgTiles[i][1] == NT) return i;
-  return -1;
-}
-// Launch shape of one prefill GEMM (kh_gemm.h): R 16-row tiles and NT 16-token tiles per wave,
-// ks waves splitting K per workgroup, grid.y token slices.  Picked by a small cost model of the
-// busiest SIMD, fitted to a sweep on Llama-3.2-1B (profiles/r2_gemm_shape_sweep.txt):
-//   * a workgroup lives on ONE CU: fewer than 256 workgroups leave CUs idle (the model prices the
-//     busiest CU, so such shapes simply show their long per-wave work);
-//   * fp32: ONE wave per SIMD is the sweet spot: two MFMA-bound waves on a SIMD cost ~1.6x the
-//     time of the same work in one wave (the (w1,w3) GEMM went 140 -> 84 us per launch from 8 to 4
-//     waves per CU), three or more ~1.8x;  int8: the opposite - its waves spend VALU time on the
-//     dequant between MFMAs, so a second and third wave per SIMD fill the matrix pipe
-//     (profiles/r2_gemm_shape_sweep_7b.txt: (w1,w3) 2 -> 4 waves per workgroup 30.4 -> 23.3 ms per
-//     prefill), up to what the register file admits;
-//     (these penalties were fitted with the phase scheme in every fp32 loop; since the uniform
-//     operand rings of kh_gemm.h a second wave per SIMD costs less - (w1,w3) with 8 instead of 4
-//     waves per workgroup: 3.01 vs 2.75 ms per 128-token pass - but still loses, and a re-sweep of
-//     13 forced shapes leaves every choice of the model in place, profiles/r3_prefill_shapes512.txt);
-//   * bigger register tiles need fewer operand bytes per MFMA (small factor), more token slices
-//     re-read the weights from L2 (small factor), padding tokens are wasted MFMAs;
-//   * fp32 passes of more than 128 tokens launch several times 256 workgroups, which would sit two
-//     or more to a CU - two or more MFMA-bound waves per SIMD.  `solo` keeps ONE workgroup per CU at
-//     a time (a dynamic-LDS request above half the CU's 160 KiB; the workgroups of a CU then run back
-//     to back at the one-wave-per-SIMD rate) and is priced as such: Llama-3.2-1B, 512-token pass,
-//     56.4 k prompt tok/s with it, 38.0 k without (profiles/r3_prefill_wide.txt).  Passes of <= 128
-//     tokens use it for the MFMA-bound (2,8) tile only (Llama-2-7B fp32: 344 / 384 workgroups); their
-//     small latency-bound tiles gain from a partner wave, and whole rounds of 256 cost more than
-//     they save (Qwen2.5, (1,4) tile in 608 workgroups: 45.9 k shared, 41.8 k solo).
-//   * the residual GEMMs (wo, w2) may split K across `kz` workgroups as well (blockIdx.z): with 2048
-//     rows x 128 tokens there are only 64 (2,8) tiles, so a chip-filling launch either takes small
-//     tiles or more K slices than a workgroup has waves.  The slices store partial rows and the
-//     RMSNorm kernel that follows adds them in fixed order (kh_gemm.h) - no ticket, no second launch.
-// hooks read per call (kh_debug_set takes effect on the next launch plan)
-static inline bool pg_solo_on() { return !dbg_off("KH_PG_SOLO"); }
-static inline bool pg_kz_on() { return !dbg_off("KH_PG_KZ"); }
-}  // namespace
-PgShape khm::pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant,
-                      bool allow_kz) {
-  const int nt_all = (T + 15) / 16;
-  const bool wide = nt_all > 8;  // a pass of more than 128 tokens
-  PgShape best{1, 4, 1, (nt_all + 3) / 4, false, 1};
-  double best_cost = -1.0;
-  for (const auto& c : kPgTiles) {
-    const int R = c[0], NT = c[1], occ = c[2];
-    if (R == 2 && !r2_ok) continue;
-    if (R == 1 && quant && r2_ok) continue;  // int8: the 32-row tile measured better wherever it fits
-    if (NT > 4 && nt_all <= 4) continue;     // no 128-token tile for <= 64 tokens
-    const int slices = (nt_all + NT - 1) / NT;
-    for (int kz = 1; kz <= (allow_kz && pg_kz_on() ? KH_PG_KZ_MAX : 1); kz *= 2)
-    for (int ks = 1; ks * nm * 64 <= KH_PG_WG_MAX(quant); ks *= 2) {
-      const long wgs = (long)(rows_total / (16 * R)) * slices * kz;
-      if (ks * kz > 1 && kblocks / (ks * kz) < min_blocks) break;  // keep a useful K range per wave
-      // waves per SIMD on the busiest CU.  A workgroup counts as one wave on EACH SIMD it touches:
-      // two 2-wave workgroups on a CU were measured on the same two SIMDs (Llama-3.2-1B, 256 tokens:
-      // the (2,8) SwiGLU tile with 2-wave workgroups 255 us against 2 x 83 us for two 128-token
-      // launches of 4-wave workgroups)
-      const long cu_wgs = (wgs + 255) / 256;
-      long wps = cu_wgs * ((nm * ks + 3) / 4);
-      const long rounds = (wps + occ - 1) / occ;                    // beyond the register file: queued
-      if (wps > occ) wps = occ;
-      const double pen = quant ? (wps <= 1 ? 1.0 : (wps == 2 ? 0.72 : 0.62))
-                               : (wps <= 1 ? 1.0 : (wps == 2 ? 1.6 : 1.8));
-      const double per_wave = (double)((kblocks + ks * kz - 1) / (ks * kz)) * R * NT;
-      double cost = per_wave * (double)(wps * rounds) * pen;
-      cost *= 1.0 + 0.04 * (double)(kz - 1);  // partial rows written, and read back by the RMSNorm
-      cost *= 1.0 + 0.15 * (double)(R + NT) / (double)(R * NT);
-      // every token slice re-reads the weights from L2 - and, int8, dequantises them again
-      cost *= 1.0 + (quant ? 0.15 : 0.05) * (double)(slices - 1);
-      cost *= (double)(slices * NT) / (double)nt_all;
-      bool solo = false;
-      if (!quant && (wide || R * NT >= 16) && pg_solo_on() && wgs > 256) {
-        const long wg_wps = (nm * ks + 3) / 4;
-        const double c1 = per_wave * (double)(((wgs + 255) / 256) * wg_wps) * (wg_wps <= 1 ? 1.0 : (wg_wps == 2 ? 1.6 : 1.8));
-        if (c1 < per_wave * (double)(wps * rounds) * pen) {
-          cost *= c1 / (per_wave * (double)(wps * rounds) * pen);
-          solo = true;
-        }
-      }
-      if (best_cost < 0 || cost < best_cost) {
-        best_cost = cost;
-        best = PgShape{R, NT, ks, slices, solo, kz};
-      }
-    }
-  }
-  return best;
-}
-bool khm::pg_lds_opt_in(const void* kern, size_t lds) {
-  if (lds > 48 * 1024) {
-    // the >48 KiB dynamic-LDS opt-in is per (device, kernel): set once, not on every launch of
-    // the prefill hot path; a refusal is reported here, not as a generic launch error later
-    struct Done { int dev; const void* fn; size_t lds; };
-    static thread_local std::vector<Done> done;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool hit = false;
-    for (const auto& d : done) hit = hit || (d.dev == dev && d.fn == kern && d.lds >= lds);
-    if (!hit) {
-      if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-      }
-      done.push_back({dev, kern, lds});
-    }
-  }
-  return true;
-}
-// The launch shape of one GEMM of a pass: the cost model, the KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE> hook, KH_PG_DEBUG.
-// epi: KH_PG_*; STORE (the classifier GEMM of the wide sequence pass) plans as a residual GEMM without a K split
-// across workgroups.
-PgShape khm::pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K) {
-  const bool q = m->cfg.is_quant;
-  const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
-  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / (q ? 64 : 16), q ? 4 : 16, q, EPI == KH_PG_RESID);
-  {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE>="R,NT,ks[,kz]" overrides the heuristic
-    static const char* const names[4] = {"KH_PG_SHAPE_QKV", "KH_PG_SHAPE_RESID", "KH_PG_SHAPE_SWIGLU",
-                                         "KH_PG_SHAPE_STORE"};
-    const char* const ov = dbg(names[EPI]);
-    if (ov) {
-      int R = 0, NT = 0, ks = 0, kz = 1;
-      if (sscanf(ov, "%d,%d,%d,%d", &R, &NT, &ks, &kz) >= 3 && pg_tile(R, NT) >= 0 && (R != 2 || r2_ok) &&
-          (ks == 1 || ks == 2 || ks == 4 || ks == 8) && ks * nm * 64 <= KH_PG_WG_MAX(q) &&
-          (kz == 1 || (EPI == KH_PG_RESID && (kz == 2 || kz == 4))))
-      {
-        const int slices = ((T + 15) / 16 + NT - 1) / NT;
-        sh = PgShape{R, NT, ks, slices,
-                     !q && (T > 128 || R * NT >= 16) && pg_solo_on() && (long)(rows_total / (16 * R)) * slices * kz > 256, kz};
-      } else {
-        // not a launch this GEMM has (e.g. R = 2 where 32 rows do not divide the matrices): say so rather than
-        // let a test believe it forced a shape
-        fprintf(stderr, "[kh] %s=\"%s\" rejected (R,NT 1,4%s, ks 1/2/4/8 up to %d waves%s): heuristic shape\n",
-                names[EPI], ov, r2_ok ? " or 2,2/4/8" : "", KH_PG_WG_MAX(q) / 64 / nm,
-                EPI == KH_PG_RESID ? ", kz 1/2/4" : "");
-      }
-    }
-  }
-  if (dbg("KH_PG_DEBUG"))
-    fprintf(stderr, "[pg] epi %d rows %d K %d T %d -> R %d NT %d slices %d ks %d kz %d (%d wgs x %d waves%s)\n", EPI,
-            rows_total, K, T, sh.R, sh.NT, sh.slices, sh.ks, sh.kz, rows_total / (16 * sh.R) * sh.slices * sh.kz,
-            nm * sh.ks, sh.solo ? ", solo" : "");
-  return sh;
-}
-namespace {
-// rg: the tokens are the tiles of a pass into sequence slots (kh_seq_prefill.h) - the QKV GEMM is then k_rg_gemm, the
-// same statements under the tile address, in the same launch geometry
-template <bool Q, int EPI>
-bool pg_launch_cfg(const PgShape& sh, int tiles, int wg, hipStream_t s, const KhPgGemmArgs& a, const KhRgTiles* rg) {
-  size_t lds = pg_lds_bytes(wg / 64, sh.NT);
-  if (sh.solo && lds < KH_PG_SOLO_LDS) lds = KH_PG_SOLO_LDS;  // one workgroup per CU at a time
-  auto opt_in = [&](auto kern, dim3&) { return pg_lds_opt_in((const void*)kern, lds); };
-  const int tile = pg_tile(sh.R, sh.NT);  // one that is not listed runs as (2,2) where R is 2, else as (1,4)
-  bool ok = false;
-  kh_pick(KhVals<0, 1, 2, 3>{}, tile >= 0 ? tile : (sh.R == 2 ? 2 : 3), [&](auto I) {
-    constexpr int R = kPgTiles[I][0], NT = kPgTiles[I][1];
-    if constexpr (EPI == KH_PG_QKV) {
-      if (rg) {
-        ok = kh_launch_prep(opt_in, KH_KERNEL(k_rg_gemm, Q, R, NT, EPI), dim3(tiles, sh.slices, sh.kz), wg, lds, s, a, *rg);
-        return;
-      }
-    }
-    ok = kh_launch_prep(opt_in, KH_KERNEL(k_pg_gemm, Q, R, NT, EPI), dim3(tiles, sh.slices, sh.kz), wg, lds, s, a);
-  });
-  return ok;
-}
-// returns whether the QKV epilogue rotates q / k itself (else k_pg_rope has to follow); RESID: the
-// number of K slices whose partial rows the next RMSNorm has to add (0 = the epilogue added itself)
-template <int EPI>
-int pg_launch(kh_model* m, int rows_total, bool r2_ok, KhPgGemmArgs a, const KhRgTiles* rg = nullptr) {
-  const bool q = m->cfg.is_quant;
-  const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
-  const PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K);
-  if (EPI == KH_PG_QKV && a.rope == KH_PG_ROPE_TILES && (sh.R != 2 || sh.NT > 4))
-    a.rope = KH_PG_ROPE_OFF;  // no partner tile in the wave / no registers to hold it: k_pg_rope follows
-  const int tiles = rows_total / (16 * sh.R);
-  const bool ok = q ? pg_launch_cfg<true, EPI>(sh, tiles, nm * sh.ks * 64, m->stream, a, rg)
-                    : pg_launch_cfg<false, EPI>(sh, tiles, nm * sh.ks * 64, m->stream, a, rg);
-  if (!ok) m->pg_launch_failed = true;  // reported by kh_model_prefill_gemm
-  if (EPI == KH_PG_RESID) return sh.kz > 1 ? sh.kz : 0;
-  return EPI == KH_PG_QKV && a.rope != KH_PG_ROPE_OFF;
-}
-// k_rg_attn (kh_seq_prefill.h) in k_pg_attn's launch geometry at one query tile per workgroup, with k_pg_attn's waves
-// per head size; pg_attn_supported(head_size) is the caller's to check
-void launch_rg_attn(const KhPgAttnArgs& a, const KhRgTiles& tiles, int head_size, hipStream_t s) {
-  const int grid = a.kv_heads * a.kv_mul * (a.T / 16);
-  switch (head_size) {
-    case 48: kh_launch(KH_KERNEL(k_rg_attn, 3, 8), grid, 64 * 8, 0, s, a, tiles); break;
-    case 64: kh_launch(KH_KERNEL(k_rg_attn, 4, 8), grid, 64 * 8, 0, s, a, tiles); break;
-    case 128: kh_launch(KH_KERNEL(k_rg_attn, 8, 4), grid, 64 * 4, 0, s, a, tiles); break;
-    default: break;
-  }
-}
-// forward of T (<= KH_PG_TMAX) prompt tokens at positions pos0..: fills their K/V cache rows.
-// rg (kh_seq_prefill.h): the T = 16 x tiles slab tokens are the tiles of a pass into sequence slots instead - toks is
-// the padded token list, pos0 is not read; the QKV GEMM, the RoPE fallback and the attention take the tile table
-// (k_rg_gemm, k_rg_rope, k_rg_attn: MFMA attention only, the caller checked), every other launch is the run's own
-void launch_prefill_gemm_chunk(kh_model* m, const int32_t* toks, int T, int pos0, const KhRgTiles* rg = nullptr) {
-  const kh_config& c = m->cfg;
-  const bool q = c.is_quant;
-  const int tcap = pg_tcap(T);  // token stride of this chunk's tiled slabs
-  (void)kh_embedding_f32_host(toks, T, m->tok_emb, m->pg_x, c.dim, c.vocab_size, (void*)m->stream);
-  int pending_kz = 0;  // K slices of the last residual GEMM still to be added to pg_x (by the next RMSNorm)
-  auto rmsnorm = [&](const float* w) {
-    kh_pick_bool(q, [&](auto Q) {
-      kh_launch(KH_KERNEL(k_pg_rmsnorm, Q), T, KH_WG, 0, m->stream, m->pg_x, w, m->pg_xn, c.dim, c.rms_eps, tcap,
-                (const float*)m->pg_part, pending_kz);
-    });
-    pending_kz = 0;
-  };
-  // attention of the slice: MFMA kernel (kh_pattn.h) unless KH_PG_ATTN=0 or an odd head size
-  const bool mfma_attn = pg_mfma_attn(m);
-  const bool rope_fuse_env = !dbg_off("KH_PG_ROPE_FUSE");
-  for (int l = 0; l < c.layer_num; ++l) {
-    const LayerW& W = m->layers[l];
-    float* kc = m->kcache + (size_t)l * c.cache_len * c.kv_dim;
-    float* vc = m->vcache + (size_t)l * c.cache_len * c.kv_dim;
-    rmsnorm(W.att_norm);
-    bool rope_fused = false;
-    {
-      KhPgGemmArgs a{};
-      a.w[0] = W.wq; a.w[1] = W.wk; a.w[2] = W.wv;
-      a.B = m->pg_xn; a.b_tiled = 1; a.tcap = tcap; a.out = m->pg_q; a.kc = kc; a.vc = vc;
-      a.rows0 = c.dim; a.rows1 = c.kv_dim; a.ldo = c.dim; a.K = c.dim; a.T = T; a.pos0 = pos0;
-      a.gshift = m->gshift;
-      // RoPE in the epilogue: interleaved pairs sit in one lane's float4; half-mode partners need the
-      // paired-tile mapping (R = 2, head size a multiple of 32).  KH_PG_ROPE_FUSE=0: separate kernel.
-      a.head_size = c.head_size; a.sin_cache = m->sin_cache; a.cos_cache = m->cos_cache;
-      a.rope = !rope_fuse_env ? KH_PG_ROPE_OFF
-               : (c.rope_mode == KH_ROPE_HALF ? (c.head_size % 32 == 0 ? KH_PG_ROPE_TILES : KH_PG_ROPE_OFF)
-                                              : KH_PG_ROPE_PAIRS);
-      rope_fused = pg_launch<KH_PG_QKV>(m, c.dim + 2 * c.kv_dim, c.dim % 32 == 0 && c.kv_dim % 32 == 0, a, rg) != 0;
-    }
-    if (!rope_fused && rg) {
-      launch_log("k_rg_rope");
-      hipLaunchKernelGGL(k_rg_rope, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_q, kc, m->sin_cache,
-                         m->cos_cache, c.dim, c.kv_dim, c.head_size, *rg, c.rope_mode);
-    } else if (!rope_fused) {
-      launch_log("k_pg_rope");
-      hipLaunchKernelGGL(k_pg_rope, dim3(T), dim3(KH_WG), 0, m->stream, m->pg_q, kc, m->sin_cache,
-                         m->cos_cache, c.dim, c.kv_dim, c.head_size, pos0, c.rope_mode);
-    }
-    // the prompt phase leaves K/V rows and nothing else (no logits): the last layer's K/V rows are
-    // written, its attention, wo and FFN feed nothing (1/L of the pass minus one QKV GEMM)
-    if (l == c.layer_num - 1) break;
-    if (mfma_attn) {
-      KhPgAttnArgs a{};
-      a.q = m->pg_q; a.kc = kc; a.vc = vc; a.out = m->pg_att;
-      a.dim = c.dim; a.kv_dim = c.kv_dim; a.kv_heads = c.kv_head_num; a.kv_mul = c.kv_mul;
-      a.T = T; a.pos0 = pos0; a.layout = q ? KH_PA_TILED_Q8 : KH_PA_TILED_F32; a.tcap = tcap;
-      if (rg)
-        launch_rg_attn(a, *rg, c.head_size, m->stream);
-      else
-        launch_pg_attn(a, c.head_size, m->stream);
-    } else {
-      KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
-      a.defer = 0;  // multi-token slices merge in the launch
-      a.nsplit_g = m->attn_ns_g;  // not the decode step's variant: the launch plan decides from the slice's positions
-      a.q = m->pg_q;
-      a.out = m->pg_att;
-      a.d_pos = nullptr;
-      a.ws = m->pg_ws;
-      a.tok_stride = c.dim;
-      a.ws_tok_bytes = m->pg_ws_tok_bytes;
-      // head sizes without an MFMA instantiation (and KH_PG_ATTN=0): the decode kernel, one grid
-      // slice per token, 256-thread workgroups (4096 latency-bound (head, token) workgroups: twice
-      // as many fit a CU as with the decode width, 28.7 -> 19.6 us per layer)
-      launch_attn_decode(a, pos0, KH_WG, m->stream, T, pos0 + T - 1);
-    }
-    {
-      KhPgGemmArgs a{};
-      a.w[0] = W.wo;
-      a.B = m->pg_att; a.b_tiled = mfma_attn ? 1 : 0; a.tcap = tcap; a.out = m->pg_x;  // decode kernel: row-major rows
-      a.rows0 = c.dim; a.ldo = c.dim; a.K = c.dim; a.T = T; a.gshift = m->gshift; a.part = m->pg_part;
-      pending_kz = pg_launch<KH_PG_RESID>(m, c.dim, c.dim % 32 == 0, a);
-    }
-    rmsnorm(W.ffn_norm);
-    {
-      KhPgGemmArgs a{};
-      a.w[0] = W.w1; a.w[1] = W.w3;
-      a.B = m->pg_xn; a.b_tiled = 1; a.tcap = tcap; a.out = m->pg_h;
-      a.rows0 = c.hidden_dim; a.ldo = c.hidden_dim; a.K = c.dim; a.T = T; a.gshift = m->gshift;
-      pg_launch<KH_PG_SWIGLU>(m, c.hidden_dim, c.hidden_dim % 32 == 0, a);
-    }
-    {
-      KhPgGemmArgs a{};
-      a.w[0] = W.w2;
-      a.B = m->pg_h; a.b_tiled = 1; a.tcap = tcap; a.out = m->pg_x;
-      a.rows0 = c.dim; a.ldo = c.dim; a.K = c.hidden_dim; a.T = T; a.gshift = m->gshift; a.part = m->pg_part;
-      pending_kz = pg_launch<KH_PG_RESID>(m, c.dim, c.dim % 32 == 0, a);  // (the next layer's RMSNorm adds them)
-    }
-  }
-}
-}  // namespace
-
-// Host-only view of the prefill GEMM launch plan (pg_shape) for tools and the CPU test-suite: epi 0 = QKV
-// (rows = dim + 2 kv_dim), 1 = residual GEMM (wo / w2: rows = dim), 2 = SwiGLU pair (rows = hidden_dim); K =
-// contraction length; r2_ok = the 32-row register tile divides the row blocks.  out[7] = {R, NT, ks, token
-// slices, solo, kz, workgroups}.  No device is touched; the KH_PG_SHAPE_* overrides are not applied.
-extern "C" int kh_plan_prefill_shape(int32_t epi, int32_t T, int32_t rows, int32_t K, int32_t is_quant,
-                                     int32_t r2_ok, int32_t* out7) {
-  if (!out7 || epi < 0 || epi > 2 || T <= 0 || T > KH_PG_TMAX || rows <= 0 || K <= 0) return KH_ERR_INVALID_ARG;
-  const bool q = is_quant != 0;
-  if (rows % 16 || K % (q ? 64 : 16)) return KH_ERR_UNSUPPORTED;
-  const PgShape sh = pg_shape(T, rows, r2_ok != 0, epi == KH_PG_SWIGLU ? 2 : 1, K / (q ? 64 : 16), q ? 4 : 16, q,
-                              epi == KH_PG_RESID);
-  out7[0] = sh.R; out7[1] = sh.NT; out7[2] = sh.ks; out7[3] = sh.slices; out7[4] = sh.solo ? 1 : 0; out7[5] = sh.kz;
-  out7[6] = rows / (16 * sh.R) * sh.slices * sh.kz;
-  return KH_OK;
-}
-
-extern "C" int kh_model_prefill_gemm(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
-  int rc = khm::prefill_gemm_run(m, h_tokens, n, pos0);
-  if (rc == KH_OK) rc = khm::lp_none(m, pos0, n);
-  return rc == KH_OK ? khm::hist_write(m, h_tokens, n, pos0) : rc;
-}
-int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
-  if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
-  const kh_config& c = m->cfg;
-  if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
-  if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
-  if (!pg_supported(m)) return KH_ERR_UNSUPPORTED;
-  KH_CHECK_HIP(hipSetDevice(m->opts.device));
-  int rc;
-  if ((rc = kv_ensure(m, pos0 + n)) != KH_OK) return rc;
-  if ((rc = ensure_pg_buffers(m)) != KH_OK) return rc;
-  if ((rc = ensure_pg_ws(m)) != KH_OK) return rc;
-  m->pg_launch_failed = false;
-  // tuning / test hook: KH_PG_CHUNK=<tokens per weight pass> (16 .. KH_PG_TMAX), read per call
-  int chunk = KH_PG_TMAX;
-  if (const char* e = dbg("KH_PG_CHUNK")) {
-    const int v = atoi(e);
-    chunk = v < 16 ? 16 : (v > KH_PG_TMAX ? KH_PG_TMAX : v);
-  }
-  for (int t0 = 0; t0 < n; t0 += chunk)
-    launch_prefill_gemm_chunk(m, h_tokens + t0, n - t0 < chunk ? n - t0 : chunk, pos0 + t0);
-  if (m->pg_launch_failed) return KH_ERR_UNSUPPORTED;  // a GEMM shape's LDS opt-in was refused
-  return kh_launch_status();
-}
-
-// ---- the GEMM prefill into sequence slots (kh_seq_prefill.h; kh_model_seq.hip checks the call and drives this) -------
-int khm::seq_prefill_gemm_check(const kh_model* m) {
-  // no fallback to the VALU pass, none to the decode-attention slices (KH_PG_ATTN=0 refuses the call)
-  return pg_supported(m) && pg_mfma_attn(m) ? KH_OK : KH_ERR_UNSUPPORTED;
-}
-int khm::seq_prefill_gemm_enqueue(kh_model* m, int n_seq, const int32_t* slots, const int32_t* toks,
-                                  const int32_t* n_tokens, const int32_t* pos0) {
-  int rc;
-  if ((rc = ensure_pg_buffers(m)) != KH_OK) return rc;
-  m->pg_launch_failed = false;
-  std::vector<size_t> seg_at((size_t)n_seq);  // where segment s starts in toks
-  size_t at = 0;
-  for (int s = 0; s < n_seq; ++s) {
-    seg_at[s] = at;
-    at += (size_t)n_tokens[s];
-  }
-  KhRgTiles tiles;
-  int32_t slab_tok[KH_PG_TMAX];
-  int ntiles = 0, cur_pass = 0;
-  auto flush = [&]() {
-    if (ntiles == 0) return;
-    for (int k = ntiles; k < KH_RG_TILES; ++k) {  // entries no slab token reads: the last tile's, as the lane tables pad
-      tiles.pos0[k] = tiles.pos0[ntiles - 1];
-      tiles.nvalid[k] = tiles.nvalid[ntiles - 1];
-      tiles.base[k] = tiles.base[ntiles - 1];
-      tiles.pfx_len[k] = tiles.pfx_len[ntiles - 1];
-      tiles.pfx_row0[k] = tiles.pfx_row0[ntiles - 1];
-    }
-    launch_prefill_gemm_chunk(m, slab_tok, 16 * ntiles, 0, &tiles);
-    ntiles = 0;
-  };
-  kh_rg_plan(n_seq, n_tokens, [&](int pass, int s, int off, int n) {
-    if (pass != cur_pass) {
-      flush();
-      cur_pass = pass;
-    }
-    const KhSeqSlot& t = m->seq_tab[slots[s]];
-    for (int o = 0; o < n; o += 16) {
-      const int k = ntiles++, nv = n - o < 16 ? n - o : 16;
-      tiles.pos0[k] = pos0[s] + off + o;
-      tiles.nvalid[k] = nv;
-      tiles.base[k] = kh_seq_own_base(t);
-      tiles.pfx_len[k] = t.pfx;
-      tiles.pfx_row0[k] = t.pfx > 0 ? m->seq_tab[t.parent].row0 : 0;
-      // the padding tokens of a segment's last tile repeat its last valid token
-      for (int i = 0; i < 16; ++i) slab_tok[16 * k + i] = toks[seg_at[s] + (size_t)(off + o + (i < nv ? i : nv - 1))];
-    }
-  });
-  flush();
-  if (m->pg_launch_failed) return KH_ERR_UNSUPPORTED;  // a GEMM shape's LDS opt-in was refused
-  return kh_launch_status();
-}
-
-// Operator-level entry of the MFMA slice attention (kh_pattn.h): the multi-token form of MHAKernel.
-extern "C" int kh_mha_prefill_f32(int32_t pos0, int32_t n_tokens, int32_t head_num, int32_t layer_index,
-                                  int32_t seq_len, int32_t kv_dim, int32_t kv_mul, int32_t head_size,
-                                  float* mha_out, const float* q, const float* key_cache,
-                                  const float* value_cache, void* stream) {
-  if (!mha_out || !q || !key_cache || !value_cache) return KH_ERR_INVALID_ARG;
-  if (n_tokens <= 0 || pos0 < 0 || head_num <= 0 || layer_index < 0 || seq_len <= 0 || kv_mul <= 0 ||
-      head_size <= 0 || kv_dim <= 0)
-    return KH_ERR_INVALID_ARG;
-  if (head_num % kv_mul || kv_dim != (head_num / kv_mul) * head_size) return KH_ERR_INVALID_ARG;
-  if ((int64_t)pos0 + n_tokens > seq_len) return KH_ERR_RANGE;
-  if (!pg_attn_supported(head_size)) return KH_ERR_UNSUPPORTED;
-  if (((uintptr_t)mha_out | (uintptr_t)q | (uintptr_t)key_cache | (uintptr_t)value_cache) & 15)
-    return KH_ERR_INVALID_ARG;  // 16-byte loads / stores
-  KhPgAttnArgs a{};
-  const size_t layer_off = (size_t)layer_index * seq_len * kv_dim;
-  a.q = q; a.kc = key_cache + layer_off; a.vc = value_cache + layer_off; a.out = mha_out;
-  a.dim = head_num * head_size; a.kv_dim = kv_dim; a.kv_heads = head_num / kv_mul; a.kv_mul = kv_mul;
-  a.T = n_tokens; a.pos0 = pos0; a.layout = KH_PA_ROWS;
-  launch_pg_attn(a, head_size, (hipStream_t)stream);
-  return kh_launch_status();
-}
 
 extern "C" int kh_model_prefill(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
   int rc = khm::prefill_run(m, h_tokens, n, pos0);
@@ -978,15 +509,7 @@ int khm::seq_pass_enqueue(kh_model* m, KhSeqLanes lanes, int n, bool words, cons
 }
 // the attention of lanes [0, n) of layer l (entries >= n padded by the caller): q / out rows of c.dim floats per lane
 void khm::seq_attn_enqueue(kh_model* m, int l, const float* q, float* out, const KhSeqLanes& lanes, int n) {
-  KhAttnArgs a = fill_attn(m, l, /*variant=*/0, m->attn_fenced);
-  a.defer = 0;  // multi-token slices merge in the launch
-  a.nsplit_g = m->attn_ns_g;
-  a.q = q;
-  a.out = out;
-  a.d_pos = nullptr;
-  a.ws = m->pf_ws;
-  a.tok_stride = m->cfg.dim;
-  a.ws_tok_bytes = m->pf_ws_tok_bytes;
+  const KhAttnArgs a = attn_slice_args(m, l, q, out, m->pf_ws, m->pf_ws_tok_bytes);
   if (seq_lanes_share(lanes, n))
     launch_seq_attn_pfx(a, lanes, n, m->attn_wg, m->stream, m->seq_pfx_pad8);
   else
@@ -1113,8 +636,7 @@ extern "C" int kh_model_time_prefill(kh_model* m, const int32_t* h_tokens, int32
     KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));
   } else if (mode == KH_PREFILL_GEMM) {
     if (!pg_supported(m)) return KH_ERR_UNSUPPORTED;
-    if ((rc = ensure_pg_buffers(m)) != KH_OK) return rc;
-    if ((rc = ensure_pg_ws(m)) != KH_OK) return rc;
+    if ((rc = prefill_gemm_prepare(m)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
     if ((rc = prefill_gemm_run(m, h_tokens, n, pos0)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev1, m->stream));

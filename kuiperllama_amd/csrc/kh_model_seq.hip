@@ -2,7 +2,7 @@
 // of different sequences as an entry point (kh_model_seq_step) and the batched generate loop on top of it
 // (kh_model_generate_batch), and their _ex forms with per-sequence penalties, logit bias and log-probs (the pass then
 // ends in k_seq_tail), and their _gemm forms: the same host text over the wide pass of up to KH_SEQ_SLOTS_MAX lanes
-// (kh_model_seq_gemm.hip: seq_pass_enqueue_gemm).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
+// (kh_model_gemm.hip: seq_pass_enqueue_gemm).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
 // seq_pass_enqueue; kernels in kh_seq.h, kh_attn.h).  The reference decodes one sequence per process
 // (demo/main.cpp:16-50); n samples of a prompt are n runs of that loop there.
 // gfx950 only.

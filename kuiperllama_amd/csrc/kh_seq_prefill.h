@@ -63,30 +63,8 @@ static __global__ __launch_bounds__(KH_WG) void k_rg_rope(float* __restrict__ Q,
   const int t = blockIdx.x, tk = t >> 4, i = t & 15;
   if (i >= tiles.nvalid[tk]) return;
   const int pos = tiles.pos0[tk] + i;
-  float* q = Q + (size_t)t * dim;
-  float* k = kc + (size_t)(tiles.base[tk] + pos) * kv_dim;
-  const float* sn = sin_cache + (size_t)pos * hs;
-  const float* cs = cos_cache + (size_t)pos * hs;
-  const int npq = dim >> 1, npk = kv_dim >> 1, half = hs >> 1;
-  for (int p = threadIdx.x; p < npq + npk; p += KH_WG) {
-    float* v = p < npq ? q : k;
-    const int pp = p < npq ? p : p - npq;
-    int r0, r1, cidx;
-    if (mode == KH_ROPE_HALF) {
-      const int head = pp / half, j = pp - head * half;
-      r0 = head * hs + j;
-      r1 = r0 + half;
-      cidx = 2 * j;
-    } else {
-      r0 = 2 * pp;
-      r1 = r0 + 1;
-      cidx = r0 % hs;
-    }
-    const float fci = sn[cidx], fcr = cs[cidx];
-    const float v0 = v[r0], v1 = v[r1];
-    v[r0] = v0 * fcr - v1 * fci;
-    v[r1] = v0 * fci + v1 * fcr;
-  }
+  pg_rope_token(Q + (size_t)t * dim, kc + (size_t)(tiles.base[tk] + pos) * kv_dim, sin_cache + (size_t)pos * hs,
+                cos_cache + (size_t)pos * hs, dim, kv_dim, hs, mode);
 }
 
 // Query columns by tile (QT = 1: a workgroup's columns are one tile, of one slot).  Every column's output is kept: a

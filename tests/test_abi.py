@@ -167,8 +167,8 @@ def test_launch_log_hook_and_qkv_split_limit(lib):
     _ffi.debug_set("KH_LAUNCH_LOG", None)
     assert _ffi.launch_log() == set() and _ffi.debug_get("KH_LAUNCH_LOG") is None
     csrc = os.path.join(ROOT, "kuiperllama_amd", "csrc")
-    family = r"k_qkv|k_gemv_res|k_wo_comb|k_ffn13|k_cls|k_ffn13_ring|k_cls_ring|k_cls_screen|k_sample_screen|k_pf_gemv_res|k_pf_qkv|k_pf_ffn13|k_pg_gemm"
-    for f in ("kh_model_step.hip", "kh_model_prefill.hip", "kh_model_screen.hip"):
+    family = r"k_qkv|k_gemv_res|k_wo_comb|k_ffn13|k_cls|k_ffn13_ring|k_cls_ring|k_cls_screen|k_sample_screen|k_pf_gemv_res|k_pf_qkv|k_pf_ffn13|k_pg_gemm|k_sg_gemm|k_rg_gemm"
+    for f in ("kh_model_step.hip", "kh_model_prefill.hip", "kh_model_gemm.hip", "kh_model_screen.hip"):
         src = open(os.path.join(csrc, f)).read()
         assert "<<<" not in src, f
         # a direct launch names a plain kernel: not an instantiation (k<...>), not a kernel passed in as a value

@@ -1,5 +1,5 @@
 """Host-side launch planning (no GPU): the decode GEMV shapes (csrc/kh_model_step.hip::pick_shape) and the
-prefill GEMM shapes (csrc/kh_model_prefill.hip::pg_shape) through the host-only C-ABI entries
+prefill GEMM shapes (csrc/kh_model_gemm.hip::pg_shape) through the host-only C-ABI entries
 kh_plan_decode_shapes / kh_plan_prefill_shape.  Invariants every plan must satisfy for every BASELINE
 geometry, plus the plans DESIGN.md documents (so that a change of the heuristics shows up here and not
 only as a slower GPU run)."""

@@ -1,4 +1,4 @@
-"""The wide sequence pass without a GPU (csrc/kh_seq_gemm.h, kh_model_seq_gemm.hip): the C-ABI symbols and their
+"""The wide sequence pass without a GPU (csrc/kh_seq_gemm.h, kh_model_gemm.hip): the C-ABI symbols and their
 ctypes signatures, kh_plan_seq_batch_wide against the Python twin of the grouping rule, the refusals that need no
 device, the new kernel stems in the gfx950 code objects (zero scratch, exactly the instantiations the launch site
 reaches), and the CPU oracle's margins on the batched-loop case of test_seq_gemm_gpu.py."""
@@ -71,7 +71,7 @@ def _notes():
 
 
 def sg_gemm_set():
-    """what kh_model_seq_gemm.hip: sg_launch can reach: fp32 and int8, the tiles pg_shape picks or a KH_PG_SHAPE_* hook
+    """what kh_model_gemm.hip: pg_gemm can reach on a lane table: fp32 and int8, the tiles pg_shape picks or a KH_PG_SHAPE_* hook
     forces at <= 64 tokens (no 128-token tile), the three epilogues of the layer and KH_PG_STORE = 3"""
     return {f"k_sg_gemm<{q},{r},{nt},{epi}>" for q in ("false", "true") for r, nt in ((2, 4), (2, 2), (1, 4))
             for epi in (0, 1, 2, 3)}

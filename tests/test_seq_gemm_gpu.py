@@ -1,5 +1,5 @@
 """The wide sequence pass on the GPU: kh_model_seq_step_gemm / kh_model_generate_batch_gemm / kh_model_seq_gemm_logits
-(csrc/kh_seq_gemm.h: k_sg_embed, k_sg_gemm, k_sg_rope; csrc/kh_model_seq_gemm.hip).
+(csrc/kh_seq_gemm.h: k_sg_embed, k_sg_gemm, k_sg_rope; csrc/kh_model_gemm.hip).
 
 The contract is kh_model_prefill_gemm's, not the bit-exact one of the 8-lane pass: K/V rows and logits are held to the
 project's tolerances against the CPU ORACLE fed the same tokens one by one (KV_ATOL_GEMM 5e-6, int8 4x; LOGIT_ATOL

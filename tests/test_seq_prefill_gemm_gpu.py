@@ -1,5 +1,5 @@
 """The GEMM prefill into sequence slots on the GPU: kh_model_seq_prefill_gemm (csrc/kh_seq_prefill.h: k_rg_gemm,
-k_rg_rope, k_rg_attn; the passes of csrc/kh_model_prefill.hip) and the Python calls on top of it.
+k_rg_rope, k_rg_attn; the passes of csrc/kh_model_gemm.hip) and the Python calls on top of it.
 
 The contract is kh_model_prefill_gemm's, not the bit-exact one of seq_prefill: K/V rows are held to the project's
 tolerances against the CPU ORACLE fed the same tokens one by one (seq_gemm_cases.kv_atol: 5e-6, int8 4x), and so are
