@@ -11,7 +11,8 @@
 //                     rows by UPPER bound
 //   k_sample_screen   (k_sample's slot) merges the partials, re-scores the candidate rows from the fp32 classifier
 //                     with k_cls's own per-lane order and reduction (the same device functions: Stager,
-//                     Gemv<false, U>::load / fma, wave_sum), and takes the argmax of those exact values.
+//                     Gemv<false, U>::load / fma, wave_sum), and takes the argmax of those exact values; what it
+//                     then leaves behind is k_sample's, through the same helpers (kh_step_tail.h).
 //
 // The interval.  Let g be the staged vector (fp32 words, the same in both kernels), rs the RMS scale, S and A the
 // exact sums  sum_i w_i g_i  and  sum_i bf16(w_i) g_i, S32 and A32 what the fp32 kernels accumulate for them.  k_cls
@@ -649,44 +650,14 @@ struct KhSampleScreenArgs {
   int32_t* ov_idx;
   uint32_t* ticket;   // 0 between launches
   int32_t* stats;     // [0] steps, [1] candidate rows re-scored, [2] overflow steps
-  // k_sample's tail
-  const int32_t* forced;
-  int n_forced;
-  int32_t* words;
-  int words_cap;
-  int32_t* d_next;
-  int32_t* d_token;
-  int32_t* d_pos;
-  const float* tok_emb;
-  float* x;
-  int dim, vocab;
-  int advance;
+  KhStepState st;     // what the step leaves behind (kh_step_tail.h)
 };
-// the tail of k_sample (kh_fused.h), word for word: thread 0 holds the argmax
-__device__ __forceinline__ void screen_tail(const KhSampleScreenArgs& a, int idx, int* s_next) {
-  if (threadIdx.x == 0) {
-    const int pos = *a.d_pos;
-    int feed = idx;
-    int reported = idx;
-    if (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) {
-      feed = a.forced[pos + 1];
-      reported = -1;
-    }
-    *a.d_next = reported;
-    if (a.advance) {
-      if (a.words && pos < a.words_cap) a.words[pos] = feed;
-      *a.d_token = feed;
-      *a.d_pos = pos + 1;
-    }
-    *s_next = a.advance ? feed : -1;
-  }
+// k_sample's last steps on the helpers of kh_step_tail.h: thread 0 holds the argmax and evaluates the forced-token rule
+// behind it, commits, and the workgroup (k_cls's width) gathers the row of the token fed next
+__device__ __forceinline__ void screen_tail(const KhStepState& st, int idx, int* s_next) {
+  if (threadIdx.x == 0) *s_next = kh_step_commit_pick(st, idx);
   __syncthreads();
-  const int nxt = *s_next;
-  if (nxt >= 0 && nxt < a.vocab) {
-    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
-    f32x4* dst = (f32x4*)a.x;
-    for (int i = threadIdx.x; i < (a.dim >> 2); i += kh_wg()) dst[i] = src[i];
-  }
+  kh_embed_gather(st.tok_emb, st.x, st.dim, st.vocab, *s_next, kh_wg());
 }
 // U, MAXV and the workgroup width are those of the model's k_cls launch: the staging (and with it rs) and the
 // per-lane order of a row's sum are then k_cls's, bit for bit.  Dynamic LDS: cls_lds_bytes(false, dim).
@@ -697,7 +668,7 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_sample_screen(const KhSampleSc
   __shared__ int s_ci[KH_SCR_CAND];
   __shared__ int s_n, s_last, s_next;
   f32x4* xs = (f32x4*)smem_raw;
-  const int dim = a.dim, vocab = a.vocab;
+  const int dim = a.st.dim, vocab = a.st.vocab;
   float* red = lds_red_ptr<false>(xs, dim);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -761,7 +732,7 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_sample_screen(const KhSampleSc
       a.stats[0] += 1;
       a.stats[1] += n;
     }
-    screen_tail(a, idx, &s_next);
+    screen_tail(a.st, idx, &s_next);
     return;
   }
   // ---- overflow: k_cls's classifier in every workgroup, argmax partials, last arriver merges
@@ -824,5 +795,5 @@ __global__ __launch_bounds__(KH_WG_MAX, 4) void k_sample_screen(const KhSampleSc
     a.stats[0] += 1;
     a.stats[2] += 1;
   }
-  screen_tail(a, idx, &s_next);
+  screen_tail(a.st, idx, &s_next);
 }

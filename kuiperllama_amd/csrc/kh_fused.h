@@ -12,7 +12,8 @@
 //   k_w2     w2 . h + residual add into x                 (llama3.cpp:710-719)
 //   k_cls    rmsnorm(x) -> LDS ; classifier rows -> logits + per-WG argmax partials (:722-731)
 //   k_sample merge partials -> next token (or forced prompt token), append to words,
-//            gather its embedding row into x, ++*d_pos    (llama3.cpp:733-745, main.cpp:20-41)
+//            gather its embedding row into x, ++*d_pos    (llama3.cpp:733-745, main.cpp:20-41): the forced-token
+//            rule, the commit and the gather are kh_step_tail.h's, shared with the four other step tails
 //
 // All GEMV kernels share kh_gemv.h::gemv_pairs: a wave streams one ROW PAIR, and the pair is
 // chosen so the epilogue has both operands in registers (RoPE partner rows, (w1,w3) rows,
@@ -21,6 +22,7 @@
 #include "kh_attn.h"
 #include "kh_common.h"
 #include "kh_gemv.h"
+#include "kh_step_tail.h"
 
 // Refill policy of gemv_pairs per kernel (same-box A/B of all four combinations on four models,
 // profiles/r3_roll_vs_bulk_ab.txt): the slot-by-slot ROLLING refill pays only in the int8 QKV kernel
@@ -507,17 +509,7 @@ struct KhSampleArgs {
   const float* part_val;
   const int32_t* part_idx;
   int nparts;
-  const int32_t* forced;  // [n_forced] token to feed at position i, or -1 => sampled
-  int n_forced;
-  int32_t* words;         // [>= steps] the reference's `words` vector (main.cpp:14,36-41)
-  int words_cap;
-  int32_t* d_next;        // argmax result (-1 while in the prompt, like post_processing)
-  int32_t* d_token;       // token fed at the NEXT position
-  int32_t* d_pos;
-  const float* tok_emb;   // [vocab, dim]
-  float* x;               // residual stream: receives the next token's embedding row
-  int dim, vocab;
-  int advance;            // 1: generate loop (feed next token, ++pos); 0: predict() only
+  KhStepState st;
 };
 static __global__ __launch_bounds__(KH_WG) void k_sample(const KhSampleArgs a) {
   __shared__ float sv[KH_WAVES_PER_WG];
@@ -538,28 +530,10 @@ static __global__ __launch_bounds__(KH_WG) void k_sample(const KhSampleArgs a) {
     idx = si[0];
 #pragma unroll
     for (int w = 1; w < KH_WAVES_PER_WG; ++w) amax_merge(v, idx, sv[w], si[w]);
-    const int pos = *a.d_pos;
-    int feed = idx;
-    int reported = idx;
-    if (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) {
-      feed = a.forced[pos + 1];  // prompt phase: next = tokens[pos+1] (main.cpp:36-38)
-      reported = -1;             // post_processing returns -1 while is_prompt (llama3.cpp:738)
-    }
-    *a.d_next = reported;
-    if (a.advance) {
-      if (a.words && pos < a.words_cap) a.words[pos] = feed;
-      *a.d_token = feed;
-      *a.d_pos = pos + 1;
-    }
-    s_next = a.advance ? feed : -1;
+    s_next = kh_step_commit_pick(a.st, idx);
   }
   __syncthreads();
-  const int nxt = s_next;
-  if (nxt >= 0 && nxt < a.vocab) {
-    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
-    f32x4* dst = (f32x4*)a.x;
-    for (int i = threadIdx.x; i < (a.dim >> 2); i += KH_WG) dst[i] = src[i];
-  }
+  kh_embed_gather(a.st.tok_emb, a.st.x, a.st.dim, a.st.vocab, s_next, KH_WG);
 }
 
 // set (token, pos) from the host and gather the embedding row: start of generate / predict
@@ -572,7 +546,5 @@ static __global__ __launch_bounds__(KH_WG) void k_set_state(int token, int pos, 
     *d_pos = pos;
     hist[pos] = token;
   }
-  const f32x4* src = (const f32x4*)(tok_emb + (size_t)token * dim);
-  f32x4* dst = (f32x4*)x;
-  for (int i = threadIdx.x; i < (dim >> 2); i += KH_WG) dst[i] = src[i];
+  kh_embed_row(tok_emb, x, dim, token, KH_WG);
 }

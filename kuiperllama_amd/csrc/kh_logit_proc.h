@@ -14,7 +14,7 @@
 //            logits[t] with the full count - which thread that is does not matter, and the table is re-armed
 //   barrier, then the bias entries (ids are distinct: one thread each).
 // __syncthreads() is the workgroup-scope fence that orders the global atomics and stores of one phase before the
-// reads of the next.  The core needs no LDS of its own, so the step's last launch (kh_sample.h: k_sample_proc) calls
+// reads of the next.  The core needs no LDS of its own, so the step's last launch (kh_logprobs.h: k_sample_proc) calls
 // it ahead of the pick on whatever shared memory it has.  No scratch, no inline assembly, plain vector stores.
 #pragma once
 #include <cmath>

@@ -18,6 +18,8 @@
 // N = 0 stops after pass 1 and counts nothing.  The order involves no arithmetic, so the ids are exact; the floats
 // carry the fp32 roundings of the sum, logf, l_max + log Z and l - lse.
 // No scratch, no inline assembly; every result is written with plain C++ stores.
+// Also here: kh_tail_chain, the one chain process -> first maximum -> pick -> record, and the two step tails that run it
+// between kh_step_tail.h's begin and end (k_sample_proc, k_sample_lp); the rows of kh_seq.h and kh_spec.h run it too.
 #pragma once
 #include "kh_sample.h"
 
@@ -171,33 +173,32 @@ __device__ __forceinline__ void kh_logprobs_core(KhSampSmem& s, KhLpSmem& t, con
   }
 }
 
-// ---- the tail of one row of a B-token pass (kh_seq.h: k_seq_tail, kh_spec.h: k_spec_tail): k_sample_lp's chain in its
-// order, one workgroup of KH_SAMP_THREADS threads per row, every argument uniform.
+// ---- the pick chain of one row of logits: the batch-1 step's (k_sample_proc, k_sample_lp below) and that of one row of
+// a B-token pass (kh_seq.h: k_seq_tail, kh_spec.h: k_spec_tail).  One workgroup of KH_SAMP_THREADS threads per row,
+// every argument uniform.
 //   1. pp says anything: kh_logit_process_core in place on lg[0 .. vocab) over hist[.. pos] (hist[j] = the token fed at
 //      the sequence's position j) with the bias list and cnt[vocab] (zero before and after);
-//   2. the first maximum of the processed row (kh_samp_row_amax);
+//   2. the first maximum of the row (kh_samp_row_amax) - from `parts`, the maxima a launch left of the RAW row, where
+//      there are any and step 1 changed nothing;
 //   3. the pick: the sampler core with counter pos where p.temperature > 0, else that maximum;
 //   4. top_n >= 0: the record at index `rec` of the record arrays - the pick, its log-prob and the top top_n of the
-//      logits the pick was made from; entries from top_n on are "none" (-1, NaN), as k_sample_lp leaves them.
-// Returns the pick in every thread.  LDS: KhSampSmem + KhLpSmem, as k_sample_lp.  Inlined, like the cores.
-struct KhTailRecs {
-  int32_t* token;    // [rows]
-  float* lp;         // [rows]
-  int32_t* top_ids;  // [rows][KH_LOGPROBS_TOP]
-  float* top_lp;     // [rows][KH_LOGPROBS_TOP]
-};
+//      logits the pick was made from (KhTailRecs, kh_step_tail.h); entries from top_n on are "none" (kh_rec_none).
+// Returns the pick in every thread.  LDS: KhSampSmem + KhLpSmem.  Inlined, like the cores.
 __device__ __forceinline__ int kh_tail_chain(float* lg, int vocab, const int32_t* hist, int pos, const KhProcParams pp,
                                              const int32_t* bias_ids, const float* bias, int32_t* cnt,
-                                             const KhSampParams p, int top_n, const KhTailRecs r, int rec) {
+                                             const KhSampParams p, int top_n, const KhTailRecs r, int rec,
+                                             KhAmaxParts parts = {nullptr, nullptr, 0}) {
   __shared__ KhSampSmem s;
   __shared__ KhLpSmem t;
   __shared__ float s_max;
   __shared__ int s_idx;
-  if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0)  // uniform
+  if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0) {  // uniform
     kh_logit_process_core(lg, vocab, hist, pos, pp, bias_ids, bias, cnt);
+    parts.val = nullptr;
+  }
   float v;
   int idx;
-  kh_samp_row_amax(lg, vocab, s.red, s.red_i, v, idx);
+  kh_samp_row_amax(lg, vocab, s.red, s.red_i, v, idx, parts);
   if (threadIdx.x == 0) {
     s_max = v;
     s_idx = idx;
@@ -211,10 +212,7 @@ __device__ __forceinline__ int kh_tail_chain(float* lg, int vocab, const int32_t
     const size_t r0 = (size_t)rec * KH_LOGPROBS_TOP;
     kh_logprobs_core(s, t, lg, vocab, lmax, pick, top_n, nullptr, r.lp + rec, r.top_ids + r0, r.top_lp + r0);
     if (threadIdx.x == 0) r.token[rec] = pick;
-    if ((int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
-      r.top_ids[r0 + threadIdx.x] = -1;
-      r.top_lp[r0 + threadIdx.x] = __uint_as_float(0xffffffffu);
-    }
+    kh_rec_none(r, rec, top_n);
   }
   return pick;
 }
@@ -234,12 +232,33 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_logprobs_op(const fl
                    top_ids ? top_ids + row * (size_t)top_n : nullptr, top_lp ? top_lp + row * (size_t)top_n : nullptr);
 }
 
-// ---- the decode step's last launch while log-probs are on (kh_model_set_logprobs): k_sample_proc's duties - the
-// forced branch, the processing core when the device copy of the processors' parameters says anything is on, the
-// maximum and its first index (one pass over the processed logits; k_cls's partials when nothing was processed), the
-// greedy or sampled pick, d_next / words / hist / d_token / d_pos, the embedding gather - and then the record of the
-// position: the picked token, its log-prob and the top *top_n of the logits the pick was made from.  Records have a
-// fixed stride of KH_LOGPROBS_TOP; entries from *top_n on, and the whole record of a forced step, are "none" (-1, NaN).
+// ---- the decode step's last launch while penalties or a logit bias are set (kh_logit_proc.h; k_sample_proc) or
+// log-probs are on (kh_model_set_logprobs; k_sample_lp): kh_tail_chain on the step's logits between the begin and the end
+// of kh_step_tail.h.  Forced steps leave before touching a logit.  Both record the token they feed next in hist[pos + 1]
+// (the window of the steps that follow); the parameters are the model's device copies.
+//   k_sample_proc  top_n = -1: no record.  k_cls's partials describe the raw logits and the processors are on: no parts.
+//   k_sample_lp    the record of position pos < rec_cap with the top *top_n (fixed stride KH_LOGPROBS_TOP); the whole
+//                  record of a forced step is "none".  k_cls's partials give the maximum while no processor is on,
+//                  which saves the pass over the vocabulary.
+struct KhSampleProcArgs {
+  float* logits;
+  const KhSampParams* params;  // device copy (kh_model_set_sampling; T <= 0 while the model is greedy)
+  const KhProcParams* proc;    // device copy (kh_model_set_penalties / kh_model_set_logit_bias)
+  const int32_t* bias_ids;
+  const float* bias;
+  int32_t* hist;               // [hist_cap] token fed at every position
+  int hist_cap;
+  int32_t* cnt;                // [vocab] counters, zero between launches
+  KhStepState st;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_proc(const KhSampleProcArgs a) {
+  int pos, forced, pick = -1;
+  kh_step_begin(a.st, pos, forced);
+  if (forced < 0)
+    pick = kh_tail_chain(a.logits, a.st.vocab, a.hist, pos, *a.proc, a.bias_ids, a.bias, a.cnt, *a.params,
+                         /*top_n=*/-1, KhTailRecs{nullptr, nullptr, nullptr, nullptr}, 0);
+  kh_step_end(a.st, pos, forced, pick, a.hist, a.hist_cap, KH_SAMP_THREADS);
+}
 struct KhSampleLpArgs {
   float* logits;
   const float* part_val;       // k_cls's per-workgroup maxima of the raw logits
@@ -253,111 +272,34 @@ struct KhSampleLpArgs {
   int hist_cap;
   int32_t* cnt;                // [vocab] counters, zero between launches
   const int32_t* top_n;        // device word (kh_model_set_logprobs)
-  int32_t* rec_token;          // [rec_cap]
-  float* rec_lp;               // [rec_cap]
-  int32_t* rec_top_ids;        // [rec_cap][KH_LOGPROBS_TOP]
-  float* rec_top_lp;           // [rec_cap][KH_LOGPROBS_TOP]
+  KhTailRecs recs;             // [rec_cap]
   int rec_cap;
-  const int32_t* forced;
-  int n_forced;
-  int32_t* words;
-  int words_cap;
-  int32_t* d_next;
-  int32_t* d_token;
-  int32_t* d_pos;
-  const float* tok_emb;
-  float* x;
-  int dim, vocab;
-  int advance;
+  KhStepState st;
 };
 static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_lp(const KhSampleLpArgs a) {
-  __shared__ KhSampSmem s;
-  __shared__ KhLpSmem t;
-  __shared__ int s_pos, s_forced;
-  if (threadIdx.x == 0) {
-    const int pos = *a.d_pos;
-    s_pos = pos;
-    s_forced = (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) ? a.forced[pos + 1] : -1;
-  }
-  __syncthreads();
-  const int pos = s_pos, forced = s_forced;
+  int pos, forced, pick = -1;
+  kh_step_begin(a.st, pos, forced);
   const bool rec = pos >= 0 && pos < a.rec_cap;
-  const size_t r0 = (size_t)(rec ? pos : 0) * KH_LOGPROBS_TOP;
-  const float none = __uint_as_float(0xffffffffu);
-  int feed, reported, top_n = 0;
-  if (forced >= 0) {
-    feed = forced;  // prompt phase: next = tokens[pos+1] (main.cpp:36-38)
-    reported = -1;
-    if (rec && threadIdx.x == 0) {
-      a.rec_token[pos] = -1;
-      a.rec_lp[pos] = none;
-    }
-  } else {
-    const KhProcParams pp = *a.proc;
-    float v = -INFINITY;
-    int idx = 0x7fffffff;
-    if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0) {
-      kh_logit_process_core(a.logits, a.vocab, a.hist, pos, pp, a.bias_ids, a.bias, a.cnt);
-      kh_samp_for_global(a.logits, a.vocab, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
-    } else {
-      for (int i = threadIdx.x; i < a.nparts; i += KH_SAMP_THREADS) amax_merge(v, idx, a.part_val[i], a.part_idx[i]);
-    }
-    wave_amax(v, idx);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-      s.red[wave] = v;
-      s.red_i[wave] = idx;
-    }
-    __syncthreads();
-    v = s.red[0];
-    idx = s.red_i[0];
-    for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) amax_merge(v, idx, s.red[w], s.red_i[w]);
-    __syncthreads();  // s.red is the cores' too
-    const KhSampParams p = *a.params;
-    feed = reported = p.temperature > 0.f ? kh_sample_core(s, a.logits, a.vocab, v, p, (uint32_t)pos) : idx;
-    if (rec) {
-      top_n = min(max(*a.top_n, 0), min(KH_LOGPROBS_TOP, a.vocab));
-      kh_logprobs_core(s, t, a.logits, a.vocab, v, feed, top_n, nullptr, a.rec_lp + pos, a.rec_top_ids + r0,
-                       a.rec_top_lp + r0);
-      if (threadIdx.x == 0) a.rec_token[pos] = feed;
-    }
-  }
-  if (rec && (int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
-    a.rec_top_ids[r0 + threadIdx.x] = -1;
-    a.rec_top_lp[r0 + threadIdx.x] = none;
-  }
-  if (threadIdx.x == 0) {
-    *a.d_next = reported;
-    if (a.advance) {
-      if (a.words && pos < a.words_cap) a.words[pos] = feed;
-      if (pos + 1 < a.hist_cap) a.hist[pos + 1] = feed;
-      *a.d_token = feed;
-      *a.d_pos = pos + 1;
-    }
-  }
-  const int nxt = a.advance ? feed : -1;
-  if (nxt >= 0 && nxt < a.vocab) {
-    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
-    f32x4* dst = (f32x4*)a.x;
-    for (int i = threadIdx.x; i < (a.dim >> 2); i += KH_SAMP_THREADS) dst[i] = src[i];
-  }
+  if (forced < 0)
+    pick = kh_tail_chain(a.logits, a.st.vocab, a.hist, pos, *a.proc, a.bias_ids, a.bias, a.cnt, *a.params,
+                         rec ? max(*a.top_n, 0) : -1, a.recs, pos, KhAmaxParts{a.part_val, a.part_idx, a.nparts});
+  else if (rec)
+    kh_rec_none(a.recs, pos, -1);
+  kh_step_end(a.st, pos, forced, pick, a.hist, a.hist_cap, KH_SAMP_THREADS);
 }
 
 // ---- sequence scoring (kh_model_score): the records of the fed positions of one B-token pass.  One workgroup per
 // valid token; the token at position pos0 + b reads row b of k_pf_cls's logits (kh_prefill.h) - the RAW logits: no
 // processor, no sampler - finds its maximum as k_logprobs_op does, and leaves the record of the position: the token
 // that FOLLOWED it (target[b]; -1 behind the last token of a call, whose log-prob is then NaN while its top list
-// is the next-token distribution), that token's log-prob and the top *top_n.  Entries from *top_n on are "none".
+// is the next-token distribution), that token's log-prob and the top *top_n.  Entries from *top_n on are "none" (kh_rec_none).
 struct KhScoreLpArgs {
   const float* logits;         // [gridDim.x][vstride]
   int vstride, vocab;
   int32_t target[KH_PF_BMAX];
   int pos0;
   const int32_t* top_n;        // device word (kh_model_set_logprobs)
-  int32_t* rec_token;          // [rec_cap]
-  float* rec_lp;               // [rec_cap]
-  int32_t* rec_top_ids;        // [rec_cap][KH_LOGPROBS_TOP]
-  float* rec_top_lp;           // [rec_cap][KH_LOGPROBS_TOP]
+  KhTailRecs recs;             // [rec_cap]
   int rec_cap;
 };
 static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_score_lp(const KhScoreLpArgs a) {
@@ -373,10 +315,7 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_score_lp(const KhSco
   const int id = a.target[b];
   const int top_n = min(max(*a.top_n, 0), min(KH_LOGPROBS_TOP, a.vocab));
   const size_t r0 = (size_t)pos * KH_LOGPROBS_TOP;
-  kh_logprobs_core(s, t, lg, a.vocab, lmax, id, top_n, nullptr, a.rec_lp + pos, a.rec_top_ids + r0, a.rec_top_lp + r0);
-  if (threadIdx.x == 0) a.rec_token[pos] = id;
-  if ((int)threadIdx.x >= top_n && threadIdx.x < KH_LOGPROBS_TOP) {
-    a.rec_top_ids[r0 + threadIdx.x] = -1;
-    a.rec_top_lp[r0 + threadIdx.x] = __uint_as_float(0xffffffffu);
-  }
+  kh_logprobs_core(s, t, lg, a.vocab, lmax, id, top_n, nullptr, a.recs.lp + pos, a.recs.top_ids + r0, a.recs.top_lp + r0);
+  if (threadIdx.x == 0) a.recs.token[pos] = id;
+  kh_rec_none(a.recs, pos, top_n);
 }

@@ -38,6 +38,7 @@
 #include "kh_buf.h"
 #include "kh_common.h"
 #include "kh_seq_plan.h"
+#include "kh_step_tail.h"
 
 namespace khm {
 // the two places memory comes from (alloc: KH_OK or the HIP error code)
@@ -400,21 +401,26 @@ static inline StepTail step_tail(const kh_model* m, int screen, bool process = t
          : screen                    ? kScreen
                                      : kGreedy;
 }
-// the fields every step tail shares: KhSampleArgs, KhSampleTopArgs and KhSampleScreenArgs name them alike
-template <class A>
-void fill_step_tail(const kh_model* m, int advance, int n_forced, A* a) {
-  a->forced = n_forced > 0 ? m->d_forced : nullptr;
-  a->n_forced = n_forced;
-  a->words = m->d_words;
-  a->words_cap = m->seq_cap;
-  a->d_next = m->d_next;
-  a->d_token = m->d_token;
-  a->d_pos = m->d_pos;
-  a->tok_emb = m->tok_emb;
-  a->x = m->x;
-  a->dim = m->cfg.dim;
-  a->vocab = m->cfg.vocab_size;
-  a->advance = advance;
+// what every step tail leaves behind (kh_step_tail.h): the last member of the five tails' arguments
+static inline KhStepState fill_step_tail(const kh_model* m, int advance, int n_forced) {
+  KhStepState st;
+  st.forced = n_forced > 0 ? (const int32_t*)m->d_forced : nullptr;
+  st.n_forced = n_forced;
+  st.words = m->d_words;
+  st.words_cap = m->seq_cap;
+  st.d_next = m->d_next;
+  st.d_token = m->d_token;
+  st.d_pos = m->d_pos;
+  st.tok_emb = m->tok_emb;
+  st.x = m->x;
+  st.dim = m->cfg.dim;
+  st.vocab = m->cfg.vocab_size;
+  st.advance = advance;
+  return st;
+}
+// the model's log-prob record buffers as the kernels take them
+static inline KhTailRecs lp_records(const kh_model* m) {
+  return {m->d_lp_token, m->d_lp_lp, m->d_lp_top_ids, m->d_lp_top_lp};
 }
 // the step's last launch
 void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail);

@@ -294,10 +294,7 @@ void launch_score_tail(kh_model* m, const int32_t* target, int nvalid, int pos0,
   for (int b = 0; b < KH_PF_BMAX; ++b) t.target[b] = b < nvalid ? target[b] : -1;
   t.pos0 = pos0;
   t.top_n = m->d_lp_top_n;
-  t.rec_token = m->d_lp_token;
-  t.rec_lp = m->d_lp_lp;
-  t.rec_top_ids = m->d_lp_top_ids;
-  t.rec_top_lp = m->d_lp_top_lp;
+  t.recs = lp_records(m);
   t.rec_cap = m->lp_cap;
   launch_log("k_score_lp");
   hipLaunchKernelGGL(k_score_lp, dim3(nvalid), dim3(KH_SAMP_THREADS), 0, m->stream, t);
@@ -390,7 +387,7 @@ int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool 
   launch_pf_pass(m, pf_run(toks, n, pos0, B, /*full_depth=*/true));
   launch_pf_cls(m, n, B);
   const bool records = tail && m->lp_top_n >= 0;
-  const KhTailRecs recs{m->d_lp_token, m->d_lp_lp, m->d_lp_top_ids, m->d_lp_top_lp};
+  const KhTailRecs recs = lp_records(m);
   if (tail) {
     KhSpecTailArgs a;
     a.logits = m->pf_logits;
@@ -533,10 +530,7 @@ int khm::seq_tail_enqueue(kh_model* m, float* logits, const KhSeqLanes& lanes, i
     for (int b = 0; b < KH_PF_BMAX; ++b) t.cap[b] = kh_seq_capacity(m->seq_tab[lanes.slot[b]]);
     t.cnt = tail->cnt;
     t.top_n = tail->top_n;
-    t.rec_token = m->d_lp_token;
-    t.rec_lp = m->d_lp_lp;
-    t.rec_top_ids = m->d_lp_top_ids;
-    t.rec_top_lp = m->d_lp_top_lp;
+    t.recs = lp_records(m);
     t.tok = m->d_seq_tok;
     t.words = words ? m->d_seq_words : nullptr;
     launch_log("k_seq_tail");

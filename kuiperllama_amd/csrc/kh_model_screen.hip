@@ -298,7 +298,7 @@ void launch_sample_screen(kh_model* m, int advance, int n_forced) {
   a.ov_idx = s.ov_idx;
   a.ticket = s.ticket;
   a.stats = s.stats;
-  fill_step_tail(m, advance, n_forced, &a);
+  a.st = fill_step_tail(m, advance, n_forced);
   // k_cls's own U, staging depth and workgroup width: the re-scored values are then k_cls's, bit for bit
   const int wg = m->sh_cls.wg;
   pick_screen<SampleScreenU>(m->sh_cls.u, kh_stage_maxv(c.dim, wg), [&](auto U, auto MV) {

@@ -318,12 +318,9 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
     t.hist_cap = m->hist_cap;
     t.cnt = m->d_cnt;
     t.top_n = m->d_lp_top_n;
-    t.rec_token = m->d_lp_token;
-    t.rec_lp = m->d_lp_lp;
-    t.rec_top_ids = m->d_lp_top_ids;
-    t.rec_top_lp = m->d_lp_top_lp;
+    t.recs = lp_records(m);
     t.rec_cap = m->lp_cap;
-    fill_step_tail(m, advance, n_forced, &t);
+    t.st = fill_step_tail(m, advance, n_forced);
     launch_log("k_sample_lp");
     hipLaunchKernelGGL(k_sample_lp, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
   } else if (tail == kProcess) {
@@ -336,7 +333,7 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
     t.hist = m->d_hist;
     t.hist_cap = m->hist_cap;
     t.cnt = m->d_cnt;
-    fill_step_tail(m, advance, n_forced, &t);
+    t.st = fill_step_tail(m, advance, n_forced);
     launch_log("k_sample_proc");
     hipLaunchKernelGGL(k_sample_proc, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
   } else if (tail == kSample) {
@@ -345,7 +342,7 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
     t.part_val = m->part_val;
     t.nparts = m->nparts;
     t.params = m->d_samp;
-    fill_step_tail(m, advance, n_forced, &t);
+    t.st = fill_step_tail(m, advance, n_forced);
     launch_log("k_sample_topp");
     hipLaunchKernelGGL(k_sample_topp, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
   } else {
@@ -353,7 +350,7 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
     a.part_val = m->part_val;
     a.part_idx = m->part_idx;
     a.nparts = m->nparts;
-    fill_step_tail(m, advance, n_forced, &a);
+    a.st = fill_step_tail(m, advance, n_forced);
     hipLaunchKernelGGL(k_sample, dim3(1), dim3(KH_WG), 0, m->stream, a);
   }
 }

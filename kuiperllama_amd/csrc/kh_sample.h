@@ -21,11 +21,14 @@
 // any order give the same totals, so draws are bit-reproducible.  The fixed point costs at most V * 2^-sb-1 of
 // absolute weight against Z >= 1 (the top token has w = 1): below 1e-8 relative for V < 2^20.
 // No scratch, no inline assembly; every result is written with plain C++ stores.
+// The step tail built on it, k_sample_topp (end of this file), shares the forced-token rule, the commit and the
+// embedding gather with the other step tails: kh_step_tail.h (kh_step_begin / kh_step_end).
 #pragma once
 #include <cmath>
 
 #include "kh_common.h"
 #include "kh_logit_proc.h"
+#include "kh_step_tail.h"
 
 #define KH_SAMP_THREADS 1024
 #define KH_SAMP_NB 2048   // histogram bins = 2^11 (one 11-bit digit of a radix descent)
@@ -302,14 +305,26 @@ __device__ inline int kh_samp_block_max_i(KhSampSmem& s, int v) {
   for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) m = max(m, s.red_i[w]);
   return m;
 }
+// Per-workgroup first maxima of a row that another launch left (k_cls: part_val / part_idx); val == null: none
+struct KhAmaxParts {
+  const float* val;
+  const int32_t* idx;
+  int n;
+};
 // The FIRST maximum of the row lg[0 .. n) and its index (ties -> lowest index: amax_merge; a row without a maximum,
 // every entry NaN, gives 0x7fffffff).  Called by all threads with one slot per wave in red / red_i; THREAD 0 returns
 // with the row's (v, idx), the other threads with partial results.  Rows on 16-byte boundaries take the walker's
-// vector path.  No arithmetic enters a maximum, so the index is k_sample's pick on the same logits.
-__device__ __forceinline__ void kh_samp_row_amax(const float* lg, int n, float* red, int* red_i, float& v, int& idx) {
+// vector path.  No arithmetic enters a maximum, so the index is k_sample's pick on the same logits - and `parts`, where
+// a launch left them for this row, give the same (v, idx) without the pass over the row.
+__device__ __forceinline__ void kh_samp_row_amax(const float* lg, int n, float* red, int* red_i, float& v, int& idx,
+                                                 const KhAmaxParts parts = {nullptr, nullptr, 0}) {
   v = -INFINITY;
   idx = 0x7fffffff;
-  kh_samp_for_global(lg, n, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
+  if (parts.val) {  // uniform
+    for (int i = threadIdx.x; i < parts.n; i += KH_SAMP_THREADS) amax_merge(v, idx, parts.val[i], parts.idx[i]);
+  } else {
+    kh_samp_for_global(lg, n, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
+  }
   wave_amax(v, idx);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
@@ -492,136 +507,29 @@ static __global__ __launch_bounds__(KH_WG) void k_sample_bcast(int32_t* out, int
   for (int i = 1 + blockIdx.x * KH_WG + threadIdx.x; i < n; i += gridDim.x * KH_WG) out[i] = v;
 }
 
-// ---- the decode step's sampler: k_sample's duties (forced prompt token, d_next / words / d_token / d_pos, the
-// embedding gather of the next token) with a sampled token instead of the argmax merge.  l_max comes from k_cls's
-// per-workgroup partials; the counter is the step's position.  Forced steps leave before reading any logit.
+// ---- the decode step's sampler: k_sample's duties on the helpers of kh_step_tail.h (the forced-token rule, the commit,
+// the embedding gather of the token fed next) with a sampled token instead of the argmax merge.  l_max comes from
+// k_cls's per-workgroup partials; the counter is the step's position.  The rule is evaluated first and broadcast:
+// forced steps leave before reading any logit.
+// (The step's last launch while penalties, a logit bias or log-probs are on - k_sample_proc, k_sample_lp - runs
+// kh_tail_chain between the same begin and commit: kh_logprobs.h.)
 struct KhSampleTopArgs {
   const float* logits;
   const float* part_val;
   int nparts;
   const KhSampParams* params;  // device copy (kh_model_set_sampling)
-  const int32_t* forced;
-  int n_forced;
-  int32_t* words;
-  int words_cap;
-  int32_t* d_next;
-  int32_t* d_token;
-  int32_t* d_pos;
-  const float* tok_emb;
-  float* x;
-  int dim, vocab;
-  int advance;
+  KhStepState st;
 };
 static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_topp(const KhSampleTopArgs a) {
   __shared__ KhSampSmem s;
-  __shared__ int s_pos, s_forced;
-  if (threadIdx.x == 0) {
-    const int pos = *a.d_pos;
-    s_pos = pos;
-    s_forced = (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) ? a.forced[pos + 1] : -1;
-  }
-  __syncthreads();
-  const int pos = s_pos, forced = s_forced;
-  int feed, reported;
-  if (forced >= 0) {
-    feed = forced;  // prompt phase: next = tokens[pos+1] (main.cpp:36-38)
-    reported = -1;
-  } else {
+  int pos, forced, pick = -1;
+  kh_step_begin(a.st, pos, forced);
+  if (forced < 0) {
     float m = -INFINITY;
     for (int i = threadIdx.x; i < a.nparts; i += KH_SAMP_THREADS) m = fmaxf(m, a.part_val[i]);
     const float lmax = kh_samp_block_max(s, m);
     const KhSampParams p = *a.params;
-    feed = reported = kh_sample_core(s, a.logits, a.vocab, lmax, p, (uint32_t)pos);
+    pick = kh_sample_core(s, a.logits, a.st.vocab, lmax, p, (uint32_t)pos);
   }
-  if (threadIdx.x == 0) {
-    *a.d_next = reported;
-    if (a.advance) {
-      if (a.words && pos < a.words_cap) a.words[pos] = feed;
-      *a.d_token = feed;
-      *a.d_pos = pos + 1;
-    }
-  }
-  const int nxt = a.advance ? feed : -1;
-  if (nxt >= 0 && nxt < a.vocab) {
-    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
-    f32x4* dst = (f32x4*)a.x;
-    for (int i = threadIdx.x; i < (a.dim >> 2); i += KH_SAMP_THREADS) dst[i] = src[i];
-  }
-}
-
-// ---- the decode step's last launch while penalties or a logit bias are set (kh_logit_proc.h): k_sample_topp's duties
-// on the PROCESSED logits.  Forced steps leave before touching a logit; otherwise the processing core rewrites the
-// logits in place, one pass finds their maximum and its first index (k_cls's partials describe the raw logits), and
-// the pick is that index or, when the device copy of the sampling parameters has T > 0, the sampler core's draw with
-// counter = position.  Also records the token it feeds next in hist[pos + 1] (the window of the steps that follow).
-struct KhSampleProcArgs {
-  float* logits;
-  const KhSampParams* params;  // device copy (kh_model_set_sampling; T <= 0 while the model is greedy)
-  const KhProcParams* proc;    // device copy (kh_model_set_penalties / kh_model_set_logit_bias)
-  const int32_t* bias_ids;
-  const float* bias;
-  int32_t* hist;               // [hist_cap] token fed at every position
-  int hist_cap;
-  int32_t* cnt;                // [vocab] counters, zero between launches
-  const int32_t* forced;
-  int n_forced;
-  int32_t* words;
-  int words_cap;
-  int32_t* d_next;
-  int32_t* d_token;
-  int32_t* d_pos;
-  const float* tok_emb;
-  float* x;
-  int dim, vocab;
-  int advance;
-};
-static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_proc(const KhSampleProcArgs a) {
-  __shared__ KhSampSmem s;
-  __shared__ int s_pos, s_forced;
-  if (threadIdx.x == 0) {
-    const int pos = *a.d_pos;
-    s_pos = pos;
-    s_forced = (a.forced && pos + 1 < a.n_forced && a.forced[pos + 1] >= 0) ? a.forced[pos + 1] : -1;
-  }
-  __syncthreads();
-  const int pos = s_pos, forced = s_forced;
-  int feed, reported;
-  if (forced >= 0) {
-    feed = forced;  // prompt phase: next = tokens[pos+1] (main.cpp:36-38)
-    reported = -1;
-  } else {
-    const KhProcParams pp = *a.proc;
-    kh_logit_process_core(a.logits, a.vocab, a.hist, pos, pp, a.bias_ids, a.bias, a.cnt);
-    float v = -INFINITY;
-    int idx = 0x7fffffff;
-    kh_samp_for_global(a.logits, a.vocab, [&](float l, int i) __attribute__((always_inline)) { amax_merge(v, idx, l, i); });
-    wave_amax(v, idx);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-      s.red[wave] = v;
-      s.red_i[wave] = idx;
-    }
-    __syncthreads();
-    v = s.red[0];
-    idx = s.red_i[0];
-    for (int w = 1; w < KH_SAMP_THREADS / KH_WAVE; ++w) amax_merge(v, idx, s.red[w], s.red_i[w]);
-    __syncthreads();  // s.red is the sampler core's too
-    const KhSampParams p = *a.params;
-    feed = reported = p.temperature > 0.f ? kh_sample_core(s, a.logits, a.vocab, v, p, (uint32_t)pos) : idx;
-  }
-  if (threadIdx.x == 0) {
-    *a.d_next = reported;
-    if (a.advance) {
-      if (a.words && pos < a.words_cap) a.words[pos] = feed;
-      if (pos + 1 < a.hist_cap) a.hist[pos + 1] = feed;
-      *a.d_token = feed;
-      *a.d_pos = pos + 1;
-    }
-  }
-  const int nxt = a.advance ? feed : -1;
-  if (nxt >= 0 && nxt < a.vocab) {
-    const f32x4* src = (const f32x4*)(a.tok_emb + (size_t)nxt * a.dim);
-    f32x4* dst = (f32x4*)a.x;
-    for (int i = threadIdx.x; i < (a.dim >> 2); i += KH_SAMP_THREADS) dst[i] = src[i];
-  }
+  kh_step_end(a.st, pos, forced, pick, nullptr, 0, KH_SAMP_THREADS);
 }

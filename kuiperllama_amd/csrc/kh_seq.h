@@ -12,8 +12,9 @@
 //                 what k_sample / k_sample_topp pick from the same logits
 // and, in place of k_seq_pick when a call states penalties, a logit bias or log-probs per sequence
 // (kh_model_seq_step_ex, kh_model_generate_batch_ex):
-//   k_seq_tail    one workgroup per lane: k_sample_lp's chain on the lane's row - the processing core on the slot's
-//                 parameters and history, the maximum, the greedy or sampled pick, the record of the lane's cache row
+//   k_seq_tail    one workgroup per lane: the step tails' pick chain (kh_logprobs.h: kh_tail_chain) on the lane's row -
+//                 the processing core on the slot's parameters and history, the maximum, the greedy or sampled pick,
+//                 the record of the lane's cache row
 // gfx950 only.
 #pragma once
 #include "kh_logprobs.h"
@@ -85,8 +86,8 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_pick(const KhSeq
   }
 }
 
-// The tail of a pass with per-sequence processors or log-probs: k_sample_lp's steps in its order (steps 1 - 4 are
-// kh_logprobs.h: kh_tail_chain, which kh_spec.h: k_spec_tail runs too), one workgroup per lane on per-slot state.
+// The tail of a pass with per-sequence processors or log-probs: steps 1 - 4 are kh_logprobs.h: kh_tail_chain, the one
+// chain of k_sample_proc, k_sample_lp and kh_spec.h: k_spec_tail, here one workgroup per lane on per-slot state.
 // Workgroup b, slot = slot[b], pos = pos[b], row = row[b]:
 //   1. proc[slot] says anything: kh_logit_process_core in place on row b of the logits, over the slot's history -
 //      hist is addressed by cache row like K/V, position p of the slot is hist[row - pos + p] - with the slot's bias
@@ -94,7 +95,7 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_pick(const KhSeq
 //   2. the first maximum of the processed row; 3. the pick: the sampler core (counter = pos) where the slot's
 //   temperature > 0, else that maximum;
 //   4. top_n >= 0: the record of cache row `row` - the pick, its log-prob and the top top_n of the logits the pick was
-//      made from; entries from top_n on are "none" (-1, NaN), as k_sample_lp leaves them;
+//      made from; entries from top_n on are "none" (kh_rec_none);
 //   5. tok[slot] = words[row] = pick, and hist[row + 1] = pick unless pos is the slot's last position (cap[b] = the
 //      positions the lane's slot holds; slots differ in length): row + 1 is then a row of the next slot.
 // LDS: KhSampSmem + KhLpSmem, as k_sample_lp.  No scratch, plain vector stores.
@@ -110,10 +111,7 @@ struct KhSeqTailArgs {
   int32_t cap[KH_PF_BMAX];     // positions the lane's slot holds
   int32_t* cnt;                // [KH_PF_BMAX][vocab] counters, zero between launches
   int top_n;                   // -1: no record
-  int32_t* rec_token;          // [cache_len]
-  float* rec_lp;               // [cache_len]
-  int32_t* rec_top_ids;        // [cache_len][KH_LOGPROBS_TOP]
-  float* rec_top_lp;           // [cache_len][KH_LOGPROBS_TOP]
+  KhTailRecs recs;             // [cache_len]
   int32_t* tok;                // [KH_SEQ_SLOTS_MAX]
   int32_t* words;              // [cache_len] or null
 };
@@ -124,8 +122,7 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_tail(const KhSeq
   const KhSampParams p = a.params[slot];
   const int pick = kh_tail_chain(a.logits + (size_t)b * (size_t)a.vstride, a.vocab, a.hist + (row - pos), pos, pp,
                                  a.bias_ids + (size_t)slot * KH_SEQ_BIAS_MAX, a.bias + (size_t)slot * KH_SEQ_BIAS_MAX,
-                                 a.cnt + (size_t)b * (size_t)a.vocab, p, a.top_n,
-                                 {a.rec_token, a.rec_lp, a.rec_top_ids, a.rec_top_lp}, row);
+                                 a.cnt + (size_t)b * (size_t)a.vocab, p, a.top_n, a.recs, row);
   if (threadIdx.x == 0) {
     a.tok[slot] = pick;
     if (a.words) a.words[row] = pick;

@@ -9,14 +9,15 @@
 // Under the model's settings (kh_model_verify_as_set, kh_model_generate_lookup_as_set: a sampler, penalties, a logit
 // bias or log-probs on) three launches take their place:
 //   k_spec_hist        the pass's fed tokens into the fed-token record, ahead of the rows that read them
-//   k_spec_tail        one workgroup per position: k_sample_lp's chain on its row (kh_logprobs.h: kh_tail_chain) - the
+//   k_spec_tail        one workgroup per position: the step tails' pick chain on its row (kh_logprobs.h: kh_tail_chain) - the
 //                      processors over the record up to its own position, the maximum, the greedy pick or the seeded
 //                      draw with counter = position, the log-prob record.  What a batch-1 step picks on the same logits.
 //   k_spec_accept_set  k_spec_accept's duties on those picks, the record entry the next step's window reads and "none"
-//                      over the log-prob records of the rejected positions
+//                      (kh_rec_none) over the log-prob records of the rejected positions
+// The accept gathers the next token's embedding row with the step tails' kh_embed_gather (kh_step_tail.h).
 // gfx950 only.
 #pragma once
-#include "kh_logprobs.h"  // kh_tail_chain
+#include "kh_logprobs.h"  // kh_tail_chain, KhTailRecs, kh_rec_none
 #include "kh_sample.h"    // KH_SAMP_THREADS, kh_samp_row_amax
 
 // pick[b] = first maximum of logits[b * stride .. + n), b = blockIdx.x (kh_samp_row_amax).  A row without a maximum
@@ -68,12 +69,7 @@ static __device__ __forceinline__ int kh_spec_accept_body(const KhSpecAcceptArgs
     s_next = nxt;
   }
   __syncthreads();
-  const int nxt = s_next;
-  if (nxt >= 0 && nxt < t.vocab) {
-    const f32x4* src = (const f32x4*)(t.tok_emb + (size_t)nxt * t.dim);
-    f32x4* dst = (f32x4*)t.x;
-    for (int i = threadIdx.x; i < (t.dim >> 2); i += KH_WG) dst[i] = src[i];
-  }
+  kh_embed_gather(t.tok_emb, t.x, t.dim, t.vocab, s_next, KH_WG);
   return a;
 }
 static __global__ __launch_bounds__(KH_WG) void k_spec_accept(const KhSpecAcceptArgs t) { kh_spec_accept_body(t); }
@@ -134,17 +130,9 @@ static __global__ __launch_bounds__(KH_WG) void k_spec_accept_set(const KhSpecAc
   __syncthreads();
   if (!s.recs.token) return;  // uniform
   const int n = s.t.n < KH_PF_BMAX ? s.t.n : KH_PF_BMAX;
-  const float none = __uint_as_float(0xffffffffu);
   for (int i = s_a + 1; i < n; ++i) {
     const int pos = s.t.pos0 + i;
     if (pos >= s.rec_cap) break;
-    if (threadIdx.x == 0) {
-      s.recs.token[pos] = -1;
-      s.recs.lp[pos] = none;
-    }
-    if (threadIdx.x < KH_LOGPROBS_TOP) {
-      s.recs.top_ids[(size_t)pos * KH_LOGPROBS_TOP + threadIdx.x] = -1;
-      s.recs.top_lp[(size_t)pos * KH_LOGPROBS_TOP + threadIdx.x] = none;
-    }
+    kh_rec_none(s.recs, pos, -1);
   }
 }
