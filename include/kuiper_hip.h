@@ -312,6 +312,17 @@ typedef struct kh_model_opts {
  * the passes, KH_W16_PASS and what still reads fp32 holds.  Hook KH_W16_F16=1 / 0 at creation overrides this bit;
  * KH_W16=0 still means no copy at all.  kh_model_w16_info slots 6 and 7 report. */
 #define KH_FLAG_W16_F16 32
+/* Q4: a 4-bit-exact int8 model runs its batch-1 decode GEMVs from a packed 4-bit copy of its matrices, bit for bit.  An
+ * int8 .bin whose quantised values all lie in [-8, 7] is a legal int8 checkpoint; with this flag the model keeps a
+ * second arena with the low nibbles of wq, wk, wv, wo, w1, w2, w3 of every layer and of wcls, two values per byte
+ * (half the int8 matrix bytes more HBM; the fp32 group scales are read where the image keeps them), and the decode
+ * GEMVs of the adopted launch classes (kh_plan_q4) stream it through kernels that run the int8 kernels' FMAs in their
+ * order.  The int8 image stays and everything else reads it: the B-token passes, the MFMA GEMM prefill, the wide pass,
+ * the operator level and the embedding gather.  Nothing is ever rounded: one value outside [-8, 7] and the copy is
+ * freed and the model behaves as if the flag were not set; likewise on fp32 images (KH_FLAG_W16* on an int8 image
+ * does nothing either).  Hooks at creation: KH_Q4=1 / 0 overrides the flag, KH_Q4_CLASSES=<mask> the adopted
+ * classes.  kh_model_q4_info reports. */
+#define KH_FLAG_Q4 64
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -378,6 +389,11 @@ int kh_model_cls_screen_info(kh_model* m, int64_t* out8);
  * that is not fp16-exact (0: fp16 was not tried, or every tensor passed).  With KH_FLAG_W16_F16 state -1 means exact
  * in neither format, and slot 4 keeps the first tensor that is not bf16-exact. */
 int kh_model_w16_info(kh_model* m, int64_t* out8);
+/* Q4 (KH_FLAG_Q4): out[8] = state (0 off or not applicable, 1 on, -1 a value lies outside [-8, 7], -2 the creation-time
+ * self-check failed - in both cases the model launches what it launches without the flag), bytes of the 4-bit copy,
+ * its build time in us, bit mask of the launch classes that run on it (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), index of
+ * the first inexact tensor (7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: wcls; -1 none); slots 5 - 7 are 0. */
+int kh_model_q4_info(kh_model* m, int64_t* out8);
 /* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
  * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave
  * every row.  out4 = screened token, full classifier's token, candidate rows re-scored, 1 if the step overflowed.
@@ -891,6 +907,11 @@ int kh_plan_decode_ring(int32_t dim, int32_t hidden_dim, int32_t vocab_size, int
  * geometry (kh_model_w16_info; 0: not applicable - int8, or dims that are no multiple of 4), bytes of the copy}. */
 int kh_plan_w16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t layer_num, int32_t is_quant,
                 int64_t* out2);
+/* kh_plan_q4: out2 = {bit mask of the decode launch classes that run on the 4-bit copy of KH_FLAG_Q4 for this geometry
+ * (kh_model_q4_info; 0: not applicable - fp32, or dims that are no multiple of the group size - or no class adopted),
+ * bytes of the copy (0: not applicable)}. */
+int kh_plan_q4(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t layer_num, int32_t is_quant,
+               int32_t group_size, int64_t* out2);
 /* kh_plan_attention: the decode-attention geometry of kh_mha_decode_f32 / the fused step for a cache of seq_len rows:
  * out8 = {time splits per head, splits per KV group (0: no group path), workspace slot stride, first pos + 1 of the
  * group path, path taken at `pos` (0 per-head, 1 group), active splits at `pos`, timesteps per split at `pos`,

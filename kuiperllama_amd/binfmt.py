@@ -401,5 +401,53 @@ def matrices_fp16_exact(image, spec: ModelSpec) -> bool:
     return bool(ents) and all(bool(_fp16_exact_words(_words(image, e)).all()) for e in ents)
 
 
+def q4_tensors(spec: ModelSpec) -> List[Tuple[TensorEntry, TensorEntry]]:
+    """The matrices the 4-bit weight copy of KH_FLAG_Q4 covers, each with its group scales: (int8 tensor, scales) of
+    wq, wk, wv, wo, w1, w2, w3 of every layer, in tensor-index order (7 * layer + index), then wcls.  [] for an fp32
+    image."""
+    if not spec.quant:
+        return []
+    by_name = {e.name: e for e in layout(spec)[0]}
+    names = [f"{n}.{l}" for l in range(spec.n_layers) for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")] + ["wcls"]
+    return [(by_name[n], by_name[n + ".scales"]) for n in names]
+
+
+def _torch_image(image) -> torch.Tensor:
+    return torch.from_numpy(image) if isinstance(image, np.ndarray) else image
+
+
+def matrices_q4_exact(image, spec: ModelSpec) -> bool:
+    """Does every quantised value of q4_tensors(spec) lie in [-8, 7], i.e. would KH_FLAG_Q4 adopt the image?"""
+    t = _torch_image(image)
+    ents = q4_tensors(spec)
+    for e, _ in ents:
+        q = t[e.offset: e.offset + e.nbytes].view(torch.int8)
+        if bool(((q < -8) | (q > 7)).any()):
+            return False
+    return bool(ents)
+
+
+def requantize_matrices_q4(image, spec: ModelSpec):
+    """Requantise the tensors of q4_tensors(spec) to 4 bits per value, in place, with the image's own tensor table,
+    layout and group size: the image stays an int8 checkpoint and becomes 4-bit-exact, what KH_FLAG_Q4 needs.  Per
+    group, in float32 as quantize_q80_torch does it: w = q * s, s' = max|w| / 7, q' = round(w / s') (half to even), so
+    q' lies in [-7, 7].  A group whose values are all zero keeps its scale and its zeros.  The library never does this
+    itself.  image: numpy uint8 array or torch uint8 tensor on any device.  Returns image."""
+    t = _torch_image(image)
+    gs = spec.group_size
+    for e, se in q4_tensors(spec):
+        q = t[e.offset: e.offset + e.nbytes].view(torch.int8)
+        s = t[se.offset: se.offset + se.nbytes].view(torch.float32)
+        w = q.reshape(-1, gs).float() * s[:, None]
+        wmax = w.abs().max(dim=1).values
+        s2 = wmax / 7.0
+        live = wmax > 0
+        q2 = torch.round(w / torch.where(live, s2, torch.ones_like(s2))[:, None]).to(torch.int8)
+        q.copy_(q2.reshape(-1))
+        s.copy_(torch.where(live, s2, s))
+        del w, q2
+    return image
+
+
 def spec_to_dict(spec: ModelSpec) -> dict:
     return dataclasses.asdict(spec)

@@ -16,6 +16,8 @@
 //   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge, the screen and W16
 //   kh_model_w16.hip      the 16-bit copy of a bf16-exact fp32 model's matrices and the decode GEMV launches that read
 //                         it (kh_w16.h kernels are instantiated here)
+//   kh_model_q4.hip       the 4-bit copy of a 4-bit-exact int8 model's matrices and the decode GEMV launches that read it
+//                         (kh_q4.h kernels are instantiated here)
 //   kh_model_h16.hip      the same launches for a copy in fp16 format (KH_FLAG_W16_F16; the _h16 kernels of kh_w16.h)
 //   kh_model_h16_pass.hip ... and its B-token passes (the _h16 kernels of kh_w16_pass.h)
 // gfx950 only.  No CPU fallback: every path launches HIP kernels.
@@ -323,6 +325,22 @@ struct kh_model {
     const void* cls = nullptr;
   };
   W16 w16;
+  // Q4 (kh_q4.h, kh_model_q4.hip; KH_FLAG_Q4 / hook KH_Q4): a second arena with the low nibbles of every int8 matrix value
+  // of a 4-bit-exact int8 model, two per byte, read by the batch-1 decode GEMVs of the adopted launch classes.  The
+  // group scales stay where they are; everything but those launches reads the int8 image.
+  struct Q4 {
+    int state = 0;          // 0 off or not applicable, 1 on, -1 some value lies outside [-8, 7], -2 the self-check failed
+    KhDev<char> alloc;      // the allocation; arena = its first 4-KiB boundary
+    char* arena = nullptr;
+    size_t bytes = 0;       // of the copy (every matrix padded to 256 bytes)
+    float build_us = 0.f;   // k_q4_build over all matrices
+    int classes = 0;        // KH_W16_* bits: launch classes that run on the copy (plan_q4, hook KH_Q4_CLASSES)
+    int first_inexact = -1; // tensor index 7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers = classifier
+    int nparts_image = 0;   // m->nparts of the int8 launches (the ring classifier's grid), for a copy that is given up
+    std::vector<W16::Layer> layers;
+    const void* cls = nullptr;
+  };
+  Q4 q4;
 };
 
 #define KH_GRAPH_STEPS 8
@@ -348,34 +366,40 @@ int configure_step_kernels(kh_model* m);  // >64 KiB dynamic-LDS opt-in of the h
 // variant (see kh_model::sg, step_variant): which attention / wo pair is launched; fenced: the form of the in-launch
 // split merge (m->attn_fenced, but for the self-test that compares the two)
 KhAttnArgs fill_attn(kh_model* m, int l, int variant, bool fenced);
-// w16: the launch reads the 16-bit copy (kh_model::w16; its kernel has the bits of the fp32 one); the forms without
-// the argument follow the model's plan
+// on: what the launch streams its matrices from - the image, the 16-bit copy (kh_model::w16) or the 4-bit copy
+// (kh_model::q4); a kernel on a copy has the bits of the one on the image.  The forms without the argument follow the
+// model's plan.  A launch on the 4-bit copy has no ring form: it takes the place of the ring launch.
+enum { KH_ON_IMAGE = 0, KH_ON_W16 = 1, KH_ON_Q4 = 2 };
 enum { KH_W16_QKV = 1, KH_W16_WO = 2, KH_W16_FFN13 = 4, KH_W16_W2 = 8, KH_W16_CLS = 16, KH_W16_ALL = 31 };
 // classes whose B-token pass reads the copy unless KH_W16_PASS says otherwise: the ones 3.1c's adoption rule keeps on
 // every geometry (profiles/w16_pass_ab.txt; qkv and wo fail it on Qwen2.5-0.5B, cls on TinyLlama)
 enum { KH_W16_PASS_DEFAULT = KH_W16_FFN13 | KH_W16_W2 };
 static inline bool w16_runs(const kh_model* m, int cls) { return (m->w16.classes & cls) != 0; }
+static inline bool q4_runs(const kh_model* m, int cls) { return (m->q4.classes & cls) != 0; }  // same class bits
+static inline int runs_on(const kh_model* m, int cls) {
+  return q4_runs(m, cls) ? KH_ON_Q4 : (w16_runs(m, cls) ? KH_ON_W16 : KH_ON_IMAGE);
+}
 // the B-token pass of the class (kh_model_prefill.hip: launch_pf_pass, pf_gemv_res, launch_pf_cls)
 static inline bool w16_pass_runs(const kh_model* m, int cls) { return (m->w16.pass_classes & cls) != 0; }
-void launch_qkv(kh_model* m, int l, bool w16);
+void launch_qkv(kh_model* m, int l, int on);
 void launch_attn(kh_model* m, int l, int variant, bool fenced);
-void launch_wo(kh_model* m, int l, int variant, bool w16);
+void launch_wo(kh_model* m, int l, int variant, int on);
 // ring: the LDS-DMA ring kernel (m->ring.ffn_r), else register tiles
-void launch_ffn13(kh_model* m, int l, bool ring, bool w16);
-void launch_w2(kh_model* m, int l, bool w16);
-static inline void launch_qkv(kh_model* m, int l) { launch_qkv(m, l, w16_runs(m, KH_W16_QKV)); }
-static inline void launch_wo(kh_model* m, int l, int variant) { launch_wo(m, l, variant, w16_runs(m, KH_W16_WO)); }
-static inline void launch_ffn13(kh_model* m, int l, bool ring) { launch_ffn13(m, l, ring, w16_runs(m, KH_W16_FFN13)); }
-static inline void launch_w2(kh_model* m, int l) { launch_w2(m, l, w16_runs(m, KH_W16_W2)); }
+void launch_ffn13(kh_model* m, int l, bool ring, int on);
+void launch_w2(kh_model* m, int l, int on);
+static inline void launch_qkv(kh_model* m, int l) { launch_qkv(m, l, runs_on(m, KH_W16_QKV)); }
+static inline void launch_wo(kh_model* m, int l, int variant) { launch_wo(m, l, variant, runs_on(m, KH_W16_WO)); }
+static inline void launch_ffn13(kh_model* m, int l, bool ring) { launch_ffn13(m, l, ring, runs_on(m, KH_W16_FFN13)); }
+static inline void launch_w2(kh_model* m, int l) { launch_w2(m, l, runs_on(m, KH_W16_W2)); }
 // what a classifier launch reads and writes; the model's own buffers and plan: launch_cls(m)
 struct ClsIo {
   const float* x;
   float *logits, *part_val;
   int32_t* part_idx;
 };
-void launch_cls(kh_model* m, const ClsIo& io, bool ring, bool w16);
+void launch_cls(kh_model* m, const ClsIo& io, bool ring, int on);
 static inline void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
-  launch_cls(m, io, ring, w16_runs(m, KH_W16_CLS));
+  launch_cls(m, io, ring, runs_on(m, KH_W16_CLS));
 }
 static inline void launch_cls(kh_model* m) {
   launch_cls(m, {m->x, m->logits, m->part_val, m->part_idx}, m->ring.cls_r == 2);
@@ -485,6 +509,20 @@ void h16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
 void h16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
 void h16_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
 void h16_launch_cls(kh_model* m, const KhClsArgs& a);
+// ---- kh_model_q4.hip ------------------------------------------------------------------------
+// Launch classes that run on the 4-bit copy for a geometry (KH_W16_* bits, 0: not applicable) and the copy's bytes
+// (host-only)
+int plan_q4(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, int layer_num, int group_size, size_t* bytes);
+// the copy, once the weights are resident and ahead of the self-tests (no-op unless KH_FLAG_Q4 / KH_Q4=1 asks)
+int q4_create(kh_model* m);
+void q4_release(kh_model* m);  // frees the copy; every class is back on what a model without the flag launches
+// the Q4 twins of the int8 launches: `a` as the int8 launch fills it, the matrices replaced by their copies here
+void q4_launch_qkv(kh_model* m, int l, const KhQkvArgs& a);
+void q4_launch_wo(kh_model* m, int l, const KhGemvResArgs& a);
+void q4_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
+void q4_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
+void q4_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
+void q4_launch_cls(kh_model* m, const KhClsArgs& a);
 // ---- kh_model_load.hip ----------------------------------------------------------------------
 // Make rows [0, rows) of the K / V cache usable before anything that touches them is enqueued: every layer, or one
 // (layer >= 0).  No-op for rows that are mapped already and for caches that are plainly allocated.  Newly mapped

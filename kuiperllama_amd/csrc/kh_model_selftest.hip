@@ -22,12 +22,16 @@
 //      of the same launch - layer 0 or the classifier, a real embedding row as the residual stream - outputs compared
 //      word for word.  A mismatch frees the copy and the model streams fp32 (kh_model_w16_info: state -2).  The
 //      launches go by the copy's format, so an fp16-format copy (KH_FLAG_W16_F16) is checked through its _h16 kernels.
+//  (f) Q4 (kh_q4.h, kh_model_q4.hip): every launch class that runs on the 4-bit copy, once against the int8 register-tile
+//      kernel of the same launch - layer 0 or the classifier, a real embedding row as the residual stream - outputs
+//      compared word for word.  A mismatch frees the copy and the model launches what it launches without the flag
+//      (kh_model_q4_info: state -2).
 //
 // Both run on scratch state the model owns at that moment (activation buffers, rows of layer 0 of the still
 // empty KV cache, which are zeroed again) in about a millisecond.  This is a tripwire for a part, a compiler or a
 // partition mode on which the suite never ran - a race that shows once in a million launches will not trip it.
 // Hooks (kh_debug_set / KH_* environment at load): KH_SELFTEST=0 skips both; KH_SELFTEST_FAIL="ring", "attn" or
-// "ring,attn" (also "screen", "w16") reports the named comparison as failed (fault injection: tests/test_model_gpu.py checks that the
+// "ring,attn" (also "screen", "w16", "q4") reports the named comparison as failed (fault injection: tests/test_model_gpu.py checks that the
 // fallbacks engage and that decode still matches the oracle).
 // Replaces nothing in the reference (it has neither path); cf. kuiper/source/op/kernels/cuda/matmul_kernel.cu:56-87,
 // mha_kernel.cu:47-130 for the kernels these paths stand in for.
@@ -80,7 +84,8 @@ static int ring_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
   hipStream_t s = m->stream;
   int rc = KH_OK;
   set_state(m, 1 % c.vocab_size, 0);  // x = a real embedding row
-  if (plan.ffn_r) {
+  // (a class on the 4-bit copy launches no ring kernel: kh_model_internal.h, KH_ON_Q4)
+  if (plan.ffn_r && !q4_runs(m, KH_W16_FFN13)) {
     launch_ffn13(m, 0, /*ring=*/true);  // -> h1
     KH_CHECK_HIP(hipMemcpyAsync(m->h3, m->h1, sizeof(float) * (size_t)c.hidden_dim, hipMemcpyDeviceToDevice, s));
     launch_ffn13(m, 0, /*ring=*/false);  // register tiles -> h1
@@ -91,7 +96,7 @@ static int ring_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
   // returns behind a launch follow a stream sync, and a device free waits for the device)
   KhDev<float> tmp_logits, tmp_pv;
   KhDev<int32_t> tmp_pi;
-  if (plan.cls_r) {
+  if (plan.cls_r && !q4_runs(m, KH_W16_CLS)) {
     const size_t np = (size_t)(m->sh_cls.grid > plan.cls_grid ? m->sh_cls.grid : plan.cls_grid);
     if ((rc = tmp_logits.alloc((size_t)c.vocab_size)) != KH_OK || (rc = tmp_pv.alloc(np)) != KH_OK ||
         (rc = tmp_pi.alloc(np)) != KH_OK)
@@ -264,6 +269,94 @@ static int w16_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) 
   return KH_OK;
 }
 
+// *result: 0 not applicable, 1 passed, -1 failed (the copy is freed, every class back on its int8 launch)
+static int q4_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
+  const kh_config& c = m->cfg;
+  *result = 0;
+  if (m->q4.state != 1) return KH_OK;
+  hipStream_t s = m->stream;
+  const size_t dim = (size_t)c.dim, kv = (size_t)c.kv_dim, hid = (size_t)c.hidden_dim, voc = (size_t)c.vocab_size;
+  const size_t np = (size_t)m->sh_cls.grid;  // both classifier launches below are register-tile launches
+  // scratch: x as the check found it | outputs of the Q4 launch (q, K row, V row | x | h | logits) | the int8 logits
+  size_t tmp_n = dim + 2 * kv;
+  if (hid > tmp_n) tmp_n = hid;
+  if (voc > tmp_n) tmp_n = voc;
+  KhDev<float> x0, tmp, ref, tmp_pv, ref_pv;
+  KhDev<int32_t> tmp_pi, ref_pi;
+  int rc = kv_ensure(m, 1, /*layer=*/0);  // the qkv launch writes row 0 of layer 0
+  if (rc != KH_OK || (rc = x0.alloc(dim)) != KH_OK || (rc = tmp.alloc(tmp_n)) != KH_OK) return rc;
+  if (q4_runs(m, KH_W16_CLS) &&
+      ((rc = ref.alloc(voc)) != KH_OK || (rc = tmp_pv.alloc(np)) != KH_OK || (rc = tmp_pi.alloc(np)) != KH_OK ||
+       (rc = ref_pv.alloc(np)) != KH_OK || (rc = ref_pi.alloc(np)) != KH_OK))
+    return rc;
+  auto diff = [&](const void* a, const void* b, size_t n) {  // words, whatever they hold
+    hipLaunchKernelGGL(k_st_diff, dim3(grid_for(n)), dim3(KH_WG), 0, s, (const uint32_t*)a, (const uint32_t*)b, n, d_flag);
+  };
+  auto copy = [&](float* dst, const float* src, size_t n) {
+    return hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, s);
+  };
+  set_state(m, 1 % c.vocab_size, 0);  // x = a real embedding row
+  hipError_t e = copy(x0, m->x, dim);
+  if (q4_runs(m, KH_W16_QKV) && e == hipSuccess) {
+    launch_qkv(m, 0, KH_ON_Q4);  // -> q, row 0 of layer 0's K and V
+    e = copy(tmp, m->q, dim);
+    if (e == hipSuccess) e = copy(tmp + dim, m->kcache, kv);
+    if (e == hipSuccess) e = copy(tmp + dim + kv, m->vcache, kv);
+    launch_qkv(m, 0, KH_ON_IMAGE);
+    diff(m->q, tmp, dim);
+    diff(m->kcache, tmp + dim, kv);
+    diff(m->vcache, tmp + dim + kv, kv);
+    if (e == hipSuccess) e = hipMemsetAsync(m->kcache, 0, sizeof(float) * kv, s);  // the cache is empty again
+    if (e == hipSuccess) e = hipMemsetAsync(m->vcache, 0, sizeof(float) * kv, s);
+  } else if (q4_runs(m, KH_W16_WO) && e == hipSuccess) {
+    launch_qkv(m, 0, KH_ON_IMAGE);  // wo's vector below
+    e = hipMemsetAsync(m->kcache, 0, sizeof(float) * kv, s);
+    if (e == hipSuccess) e = hipMemsetAsync(m->vcache, 0, sizeof(float) * kv, s);
+  }
+  if (q4_runs(m, KH_W16_WO) && e == hipSuccess) {  // x += wo . att, on the projected query as the vector
+    e = copy(m->att, m->q, dim);
+    launch_wo(m, 0, /*variant=*/0, KH_ON_Q4);
+    if (e == hipSuccess) e = copy(tmp, m->x, dim);
+    if (e == hipSuccess) e = copy(m->x, x0, dim);
+    launch_wo(m, 0, /*variant=*/0, KH_ON_IMAGE);
+    diff(m->x, tmp, dim);
+  }
+  if (q4_runs(m, KH_W16_FFN13) && e == hipSuccess) {
+    launch_ffn13(m, 0, /*ring=*/false, KH_ON_Q4);  // -> h1
+    e = copy(tmp, m->h1, hid);
+    launch_ffn13(m, 0, /*ring=*/false, KH_ON_IMAGE);
+    diff(m->h1, tmp, hid);
+  }
+  if (q4_runs(m, KH_W16_W2) && e == hipSuccess) {  // x += w2 . h1 (h1: what ffn13 left, or computed here)
+    if (!q4_runs(m, KH_W16_FFN13)) launch_ffn13(m, 0, /*ring=*/false, KH_ON_IMAGE);
+    e = copy(x0, m->x, dim);
+    launch_w2(m, 0, KH_ON_Q4);
+    if (e == hipSuccess) e = copy(tmp, m->x, dim);
+    if (e == hipSuccess) e = copy(m->x, x0, dim);
+    launch_w2(m, 0, KH_ON_IMAGE);
+    diff(m->x, tmp, dim);
+  }
+  if (q4_runs(m, KH_W16_CLS) && e == hipSuccess) {
+    launch_cls(m, {m->x, tmp, tmp_pv, tmp_pi}, /*ring=*/false, KH_ON_Q4);
+    launch_cls(m, {m->x, ref, ref_pv, ref_pi}, /*ring=*/false, KH_ON_IMAGE);
+    diff(ref, tmp, voc);
+    diff(ref_pv, tmp_pv, np);
+    diff(ref_pi, tmp_pi, np);
+  }
+  int32_t flag = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return (int)e;
+  if ((rc = kh_launch_status()) != KH_OK) return rc;
+  *result = 1;
+  if (!flag && !inject) return KH_OK;
+  *result = -1;
+  q4_release(m);
+  m->q4.state = -2;
+  fprintf(stderr, "[kh] Q4 self-check %s: the model streams its int8 matrices\n", inject ? "reported as failed (hook)" : "FAILED");
+  return KH_OK;
+}
+
 // -> KH_OK, or a HIP / KH error when a launch itself failed (the model is then not usable).  Results in
 // m->cfg.ring_selftest / attn_merge_selftest: 0 not applicable (or skipped), 1 passed, -1 failed -> fallback
 // engaged, 2 (attention only) the fenced form was requested.
@@ -275,11 +368,12 @@ int run_selftests(kh_model* m) {
   const char* inj = dbg("KH_SELFTEST_FAIL");
   KhDev<int32_t> d_flag;
   int rc;
-  if ((rc = d_flag.alloc(5)) != KH_OK) return rc;
-  int r = 0, a = 0, sc = 0, s8 = 0, w = 0;
-  KH_CHECK_HIP(hipMemsetAsync(d_flag, 0, 5 * sizeof(int32_t), m->stream));
+  if ((rc = d_flag.alloc(6)) != KH_OK) return rc;
+  int r = 0, a = 0, sc = 0, s8 = 0, w = 0, q4 = 0;
+  KH_CHECK_HIP(hipMemsetAsync(d_flag, 0, 6 * sizeof(int32_t), m->stream));
   // W16 first: the checks behind it then run on the kernels the model will launch
   if ((rc = w16_selftest(m, d_flag + 4, hook_has(inj, "w16"), &w)) != KH_OK) return rc;
+  if ((rc = q4_selftest(m, d_flag + 5, hook_has(inj, "q4"), &q4)) != KH_OK) return rc;
   if ((rc = ring_selftest(m, d_flag, hook_has(inj, "ring"), &r)) != KH_OK) return rc;
   if ((rc = attn_selftest(m, d_flag + 1, hook_has(inj, "attn"), &a)) != KH_OK) return rc;
   if ((rc = cls_screen_selftest(m, d_flag + 2, hook_has_screen(inj), &sc)) != KH_OK) return rc;
@@ -287,7 +381,7 @@ int run_selftests(kh_model* m) {
   m->cfg.ring_selftest = r;
   m->cfg.attn_merge_selftest = a;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
-    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d, classifier screen %d, its int8 tier %d, W16 %d (%.2f ms)\n", r, a, sc, s8, w,
+    fprintf(stderr, "[kh] self-tests: ring %d, attention merge %d, classifier screen %d, its int8 tier %d, W16 %d, Q4 %d (%.2f ms)\n", r, a, sc, s8, w, q4,
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return KH_OK;
 }

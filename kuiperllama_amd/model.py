@@ -344,6 +344,17 @@ class KuiperModel:
                 "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1],
                 "first_inexact": int(out[4])}
 
+    def q4_info(self) -> dict:
+        """The 4-bit weight copy of _ffi.KH_FLAG_Q4 (kh_model_q4_info): state (0 off or not applicable, 1 on, -1 some
+        int8 value lies outside [-8, 7], -2 the creation-time self-check failed), the copy's HBM bytes and build time,
+        the decode launch classes that stream it, and the first inexact tensor (7 * layer + index into wq, wk, wv, wo,
+        w1, w2, w3; 7 * n_layers: wcls; -1: none)."""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_q4_info(self._h, out), "kh_model_q4_info")
+        return {"state": int(out[0]), "bytes": int(out[1]), "build_us": int(out[2]),
+                "classes": [n for i, n in enumerate(_ffi.KH_Q4_CLASSES) if out[3] >> i & 1],
+                "first_inexact": int(out[4])}
+
     def w16_pass_info(self) -> dict:
         """The B-token passes of a KH_FLAG_W16 model (kh_model_w16_info, slot 5): {"classes": the launch classes whose
         passes - prefill, score, verify / generate_lookup, seq_* and generate_batch* - stream the 16-bit copy}, a

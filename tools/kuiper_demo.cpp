@@ -12,7 +12,7 @@
 //               [--theta 10000] [--eps 1e-5] [--steps 128] [--prompt 1,263] [--stop 2]
 //               [--exec graph|fused|unfused] [--max-seq-len N] [--device 0]
 //               [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json [--hf-spaces]] [--text "a"]
-//               [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16]
+//               [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16] [--q4]
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
@@ -26,6 +26,8 @@
 // not bf16-exact decodes as without the flag); prints kh_model_w16_info, the pass class mask included.
 // --w16-f16 = KH_FLAG_W16_F16: the same for an image that is bf16-exact OR fp16-exact (Llama-2's fp16 checkpoints); the
 // format of the copy is printed.
+// --q4 = KH_FLAG_Q4: decode an int8 image whose values all lie in [-8, 7] from a packed 4-bit copy of its matrices, bit
+// for bit (any other image decodes as without the flag); prints kh_model_q4_info.
 // --temperature / --top-k / --top-p / --seed: seeded sampling instead of the argmax (kh_model_set_sampling; the
 // reference's demo is greedy, which stays the default).
 // --repeat-penalty / --presence-penalty / --frequency-penalty over the last --repeat-last-n fed tokens (0: all of
@@ -98,6 +100,7 @@ static void usage() {
                "       [--theta F] [--eps F] [--steps N] [--prompt id,id,...] [--stop id,id] [--exec graph|fused|unfused]\n"
                "       [--max-seq-len N] [--device D] [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json\n"
                "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16]\n"
+               "       [--q4]\n"
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
@@ -157,6 +160,7 @@ int main(int argc, char** argv) {
     else if (a == "--fenced-merge") o.flags |= KH_FLAG_ATTN_MERGE_FENCED;
     else if (a == "--w16") o.flags |= KH_FLAG_W16;
     else if (a == "--w16-f16") o.flags |= KH_FLAG_W16_F16;
+    else if (a == "--q4") o.flags |= KH_FLAG_Q4;
     else if (a == "--temperature") samp.temperature = (float)std::atof(next());
     else if (a == "--top-k") samp.top_k = std::atoi(next());
     else if (a == "--top-p") samp.top_p = (float)std::atof(next());
@@ -293,6 +297,13 @@ int main(int argc, char** argv) {
                  "0x%llx, first inexact tensor %lld (bf16) %lld (fp16)\n",
                  (long long)w[0], w[0] != 1 ? "none" : (w[6] ? "fp16" : "bf16"), (double)w[1] / 1e9, (double)w[2] / 1e3,
                  (unsigned long long)w[3], (unsigned long long)w[5], (long long)w[4], (long long)w[7] - 1);
+  }
+  if (o.flags & KH_FLAG_Q4) {
+    int64_t w[8] = {0};
+    kh_model_q4_info(m, w);
+    // state: 0 not applicable (fp32), 1 on, -1 a value lies outside [-8, 7], -2 self-check failed (both: int8 decode)
+    std::fprintf(stderr, "Q4: state %lld, copy %.2f GB built in %.2f ms, launch classes 0x%llx, first inexact tensor %lld\n",
+                 (long long)w[0], (double)w[1] / 1e9, (double)w[2] / 1e3, (unsigned long long)w[3], (long long)w[4]);
   }
   rc = kh_model_set_sampling(m, &samp);
   if (rc != KH_OK) {
