@@ -1,5 +1,6 @@
 """Seeded sampling, CPU side: the fp64 reference of the semantics (tests/sampling_ref.py) on hand-made cases, the
-Philox4x32-10 known-answer vectors, the exported symbols and argument validation before any device call."""
+Philox4x32-10 known-answer vectors (scalar and vectorised), the integer statement of two-level rows against the fp64
+one, the exported symbols and argument validation before any device call."""
 import ctypes as C
 
 import numpy as np
@@ -84,6 +85,81 @@ def test_pick_walks_index_order_and_checker_tolerance():
     assert not ch.accepts(1.0, 0, 1.0, 9, range(32), [(p + 2) % 4 for p in picks]).any()
     # a token outside S is never accepted
     assert not R.Checker(np.array([5.0, 0.0, 0.0], np.float32)).accepts(1.0, 1, 1.0, 1, [0], [2]).any()
+
+
+def test_vectorised_philox_is_the_scalar_one():
+    rng = np.random.default_rng(1)
+    counters = np.concatenate([np.arange(3000), rng.integers(0, 2 ** 32, 1000), [2 ** 32 - 1, 2 ** 31, 2 ** 31 - 1]])
+    for seed in (0, 1, 0x1234_5678_9ABC, 1 << 32, 2 ** 64 - 1):
+        key = (seed & R.MASK, seed >> 32)
+        want = [R.philox4x32_10((int(c), 0, 0, 0), key)[0] >> 8 for c in counters]
+        got = R.philox_u24(seed, counters)
+        assert got.dtype == np.uint64 and got.tolist() == want
+        lo, hi = R.extreme_counters(seed, 3000)
+        assert (lo, hi) == (int(np.argmin(want[:3000])), int(np.argmax(want[:3000])))
+        assert R.uniform(seed, lo) == (want[lo] + 0.5) / 2 ** 24
+
+
+def _two_level_row(rng, V, nA, T, low_inf, third):
+    """(fp32 row, ascending indices of the maximum): the rest at 3 - 128 T (e = -128: weight zero on the device) or
+    -inf, and - `third` - up to three of them at 3 - 3 T instead (a weighted level)"""
+    A = np.sort(rng.choice(V, nA, replace=False))
+    lg = np.full(V, -np.inf if low_inf else 3.0 - 128.0 * T, np.float32)
+    lg[A] = 3.0
+    rest = np.setdiff1d(np.arange(V), A)
+    if third and rest.size:
+        lg[rng.choice(rest, min(3, rest.size), replace=False)] = 3.0 - 3.0 * T
+    return lg, A
+
+
+def test_two_level_pick_is_the_fp64_pick():
+    """The integer statement of a two-level row against the fp64 semantics on 400 small random rows.  Both are exact
+    here - fp64 sums of ones, P32 * n and u * m carry no rounding, and a weight of exp(-128) vanishes against Z >= 1 -
+    so any disagreement would have to come from a threshold within 1e-12 relative of a boundary: there is none."""
+    rng = np.random.default_rng(20241020)
+    n_rows = n_draws = 0
+    for r in range(400):
+        V = int(rng.integers(2, 601))
+        nA = int(rng.choice([1, 2, V, int(rng.integers(1, V + 1))]))
+        T = float(np.float32(rng.choice([1.0, 0.02, 50.0])))
+        K = int(rng.choice([0, 1, nA - 1, nA, nA + 1, V - 1, V, int(rng.integers(0, V + 2))]))
+        third = 0 < K <= nA and K < V and r % 3 == 0
+        lg, A = _two_level_row(rng, V, nA, T, bool(r % 2), third)
+        n = R.two_level_kept(nA, V, K, 1.0)[0]
+        P = float(np.float32(rng.choice([1.0, 0.5, 0.75, 0.999, 1e-6, (n - 1) / n if n > 1 else 0.25, rng.random()])))
+        seed = int(rng.integers(0, 2 ** 63))
+        for c in range(r, r + 6):
+            got, want = R.two_level_pick(A, V, K, P, seed, c), R.pick(lg, T, K, P, seed, c)
+            if got != want:  # how close the fp64 threshold is to a boundary of its walk
+                S, w, _ = R.kept_set(lg, T, K, P)
+                cum = np.cumsum(w[np.argsort(S, kind="stable")])
+                gap = np.abs(cum - R.uniform(seed, c) * cum[-1]).min() / cum[-1]
+                raise AssertionError((V, nA, T, K, P, seed, c, got, want, f"boundary distance {gap:.3e} of Z"))
+            n_draws += 1
+        n_rows += 1
+    assert (n_rows, n_draws) == (400, 2400)
+
+
+def test_predict_path_on_hand_made_rows():
+    def row(V, nA, low=-np.inf):
+        lg = np.full(V, low, np.float32)
+        lg[:nA] = 3.0
+        return lg
+    p = R.predict_path(row(4097, 4097), 1.0, 0, 1.0)  # no top-k, no top-p: the row itself is the candidate list
+    assert (p["mode"], p["ncand"], p["in_lds"], p["descents"], p["levels"]) == ("neither", 4097, False, ("pick",), 2)
+    assert R.predict_path(row(4096, 7), 1.0, 4096, 1.0)["in_lds"]  # K = V is off
+    p = R.predict_path(row(300, 100, -200.0), 1.0, 100, 1.0)  # m_key == ties: no index cut
+    assert (p["mode"], p["ncand"], p["descents"], p["m_key"], p["ties"]) == ("top-k only", 100, ("top-k key", "pick"), 100, 100)
+    p = R.predict_path(row(300, 100, -200.0), 1.0, 99, 0.5)  # cap = m_k = 99: m = 50 < ties
+    assert (p["mode"], p["descents"], p["m_key"]) == ("both", ("top-k key", "top-p key", "index cut", "pick"), 50)
+    p = R.predict_path(row(5000, 100), 0.02, 101, 1.0)  # K beyond the weighted tokens: every token is a candidate
+    assert (p["ncand"], p["in_lds"], p["m_key"], p["ties"], p["index_cut"]) == (5000, False, 1, 4900, True)
+    p = R.predict_path(row((1 << 19) + 19, 4097), 50.0, 0, 0.5)
+    assert (p["mode"], p["ncand"], p["in_lds"], p["m_key"], p["levels"]) == ("top-p only", 4097, False, 2049, 3)
+    assert R.predict_path(row(255, 3), 1.0, 2, 1.0)["levels"] == 1 and R.predict_path(row(256, 3), 1.0, 2, 1.0)["levels"] == 2
+    assert R.predict_path(row(1, 1), 1.0, 0, 1.0) == {"trivial": True}
+    with pytest.raises(AssertionError):  # a weighted third level that top-k does not cut off is no two-level row
+        R.predict_path(np.array([3.0, 3.0, 1.0, -np.inf], np.float32), 1.0, 0, 0.5)
 
 
 def test_sampling_symbols_are_exported(lib):
