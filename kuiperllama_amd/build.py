@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libkuiper_hip.so")
 SOURCES = ["kh_ops.hip", "kh_model_load.hip", "kh_model_step.hip", "kh_model_prefill.hip", "kh_model_gemm.hip", "kh_model_seq.hip", "kh_model_profile.hip", "kh_model_selftest.hip", "kh_model_screen.hip", "kh_model_w16.hip",
            "kh_model_h16.hip", "kh_model_h16_pass.hip", "kh_model_q4.hip",
            "kh_tokenizer.cpp", "kh_bpe.cpp", "kh_debug.cpp"]
-HEADERS = ["kh_common.h", "kh_gemv.h", "kh_attn.h", "kh_fused.h", "kh_q8ring.h", "kh_fused_ring.h", "kh_prefill.h", "kh_gemm.h", "kh_gemm_body.h", "kh_pattn.h", "kh_pattn_body.h", "kh_sample.h", "kh_step_tail.h", "kh_logit_proc.h", "kh_logprobs.h", "kh_cls_screen.h", "kh_w16.h", "kh_w16_pass.h", "kh_w16_launch.h", "kh_q4.h", "kh_pf_launch.h", "kh_unicode_tables.h",
+HEADERS = ["kh_common.h", "kh_gemv.h", "kh_attn.h", "kh_fused.h", "kh_q8ring.h", "kh_fused_ring.h", "kh_prefill.h", "kh_gemm.h", "kh_gemm_body.h", "kh_pattn.h", "kh_pattn_body.h", "kh_sample.h", "kh_step_tail.h", "kh_logit_proc.h", "kh_logprobs.h", "kh_cls_screen.h", "kh_w16.h", "kh_w16_pass.h", "kh_copy_launch.h", "kh_q4.h", "kh_pf_launch.h", "kh_unicode_tables.h",
            "kh_model_internal.h", "kh_buf.h", "kh_dispatch.h", "kh_score_plan.h", "kh_spec.h", "kh_lookup.h", "kh_seq.h", "kh_seq_plan.h", "kh_seq_gemm.h", "kh_seq_prefill.h",
            "../../include/kuiper_hip.h"]
 ARCH = "gfx950"
@@ -235,7 +235,7 @@ def ref_cpu_flavor(spec) -> str | None:
 
 def kernel_sources_sha1() -> str:
     """sha1 over the device-code headers of the decode / prefill kernels (csrc/kh_*.h except the host-only
-    kh_model_internal.h, kh_dispatch.h and kh_buf.h; kh_w16_launch.h and kh_pf_launch.h are host code too but decide which
+    kh_model_internal.h, kh_dispatch.h and kh_buf.h; kh_copy_launch.h and kh_pf_launch.h are host code too but decide which
     kernel instantiations exist, and are hashed), in name order.  profiles/pmc_traffic.json is stamped with it when the PMC passes are
     collected; bench.py recomputes it, so a kernel change after the collection shows in the record
     (roofline.traffic_source.kernel_sources_unchanged) instead of silently keeping a stale traffic ratio."""

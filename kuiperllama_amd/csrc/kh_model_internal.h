@@ -13,12 +13,14 @@
 //                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
 //   kh_model_screen.hip   the screened classifier of the greedy generate loop (kh_cls_screen.h kernels)
-//   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge, the screen and W16
-//   kh_model_w16.hip      the 16-bit copy of a bf16-exact fp32 model's matrices and the decode GEMV launches that read
-//                         it (kh_w16.h kernels are instantiated here)
-//   kh_model_q4.hip       the 4-bit copy of a 4-bit-exact int8 model's matrices and the decode GEMV launches that read it
-//                         (kh_q4.h kernels are instantiated here)
-//   kh_model_h16.hip      the same launches for a copy in fp16 format (KH_FLAG_W16_F16; the _h16 kernels of kh_w16.h)
+//   kh_model_selftest.hip creation-time checks of the ring kernels, the fence-free split merge, the screen and the
+//                         weight copies (one check for W16 and Q4)
+//   kh_model_w16.hip      the 16-bit copy of a bf16-exact fp32 model's matrices, and what every weight copy shares: its
+//                         bytes, its build, its release and the routing of the decode GEMV launches that read a copy
+//                         (kh_copy_launch.h: one launch text; the _w16 kernels of kh_w16.h are instantiated here)
+//   kh_model_q4.hip       the 4-bit copy of a 4-bit-exact int8 model's matrices (the same launch text; the kh_q4.h
+//                         kernels are instantiated here)
+//   kh_model_h16.hip      the same launch text for a 16-bit copy in fp16 format (KH_FLAG_W16_F16; the _h16 kernels of kh_w16.h)
 //   kh_model_h16_pass.hip ... and its B-token passes (the _h16 kernels of kh_w16_pass.h)
 // gfx950 only.  No CPU fallback: every path launches HIP kernels.
 //
@@ -304,19 +306,15 @@ struct kh_model {
     Q8 q8;
   };
   ClsScreen scr;
-  // W16 (kh_w16.h, kh_model_w16.hip; KH_FLAG_W16 / hook KH_W16): a second arena with the upper halves of every matrix
-  // word of a bf16-exact fp32 model, read by the batch-1 decode GEMVs and the B-token passes of the adopted launch classes.
-  // With KH_FLAG_W16_F16 / hook KH_W16_F16 an image that is not bf16-exact but fp16-exact gets the fp16 values instead.
-  struct W16 {
-    int state = 0;          // 0 off or not applicable, 1 on, -1 some matrix is not exact in a format asked for, -2 the self-check failed
-    int format = 0;         // of the live copy: KH_W16_BF16 (also: no copy) or KH_W16_F16 (kh_w16.h)
-    int first_inexact_f16 = -1;  // as first_inexact, for the fp16 format (-1: not tried, or every tensor passed)
+  // A narrow exact copy of the model's matrices (kh_model_w16.hip: copy_build, copy_release): a second
+  // arena that the batch-1 decode GEMVs of the adopted launch classes read instead of the image.  What W16 and Q4 share.
+  struct WCopy {
+    int state = 0;          // 0 off or not applicable, 1 on, -1 some matrix is not exact in the copy, -2 the self-check failed
     KhDev<char> alloc;      // the allocation; arena = its first 4-KiB boundary
     char* arena = nullptr;
     size_t bytes = 0;       // of the copy (every matrix padded to 256 bytes)
-    float build_us = 0.f;   // k_w16_build over all matrices
-    int classes = 0;        // KH_W16_* bits: launch classes that run on the copy (plan_w16)
-    int pass_classes = 0;   // ... whose B-token pass does too (kh_w16_pass.h; hook KH_W16_PASS): a subset of classes
+    float build_us = 0.f;   // the build kernel over all matrices
+    int classes = 0;        // KH_W16_* bits: launch classes that run on the copy
     int first_inexact = -1; // tensor index 7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers = classifier
     struct Layer {
       const void *wq, *wk, *wv, *wo, *w1, *w2, *w3;
@@ -324,21 +322,21 @@ struct kh_model {
     std::vector<Layer> layers;
     const void* cls = nullptr;
   };
+  // W16 (kh_w16.h, kh_model_w16.hip; KH_FLAG_W16 / hook KH_W16): the upper halves of every matrix word of a bf16-exact
+  // fp32 model (state -1: some matrix is not exact in a format asked for), read by the B-token passes of the adopted
+  // classes as well.  With KH_FLAG_W16_F16 / hook KH_W16_F16 an image that is not bf16-exact but fp16-exact gets the
+  // fp16 values instead.  classes: plan_w16.
+  struct W16 : WCopy {
+    int format = 0;         // of the live copy: KH_W16_BF16 (also: no copy) or KH_W16_F16 (kh_w16.h)
+    int first_inexact_f16 = -1;  // as first_inexact, for the fp16 format (-1: not tried, or every tensor passed)
+    int pass_classes = 0;   // classes whose B-token pass reads the copy too (kh_w16_pass.h; hook KH_W16_PASS): a subset of classes
+  };
   W16 w16;
-  // Q4 (kh_q4.h, kh_model_q4.hip; KH_FLAG_Q4 / hook KH_Q4): a second arena with the low nibbles of every int8 matrix value
-  // of a 4-bit-exact int8 model, two per byte, read by the batch-1 decode GEMVs of the adopted launch classes.  The
-  // group scales stay where they are; everything but those launches reads the int8 image.
-  struct Q4 {
-    int state = 0;          // 0 off or not applicable, 1 on, -1 some value lies outside [-8, 7], -2 the self-check failed
-    KhDev<char> alloc;      // the allocation; arena = its first 4-KiB boundary
-    char* arena = nullptr;
-    size_t bytes = 0;       // of the copy (every matrix padded to 256 bytes)
-    float build_us = 0.f;   // k_q4_build over all matrices
-    int classes = 0;        // KH_W16_* bits: launch classes that run on the copy (plan_q4, hook KH_Q4_CLASSES)
-    int first_inexact = -1; // tensor index 7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers = classifier
+  // Q4 (kh_q4.h, kh_model_q4.hip; KH_FLAG_Q4 / hook KH_Q4): the low nibbles of every int8 matrix value of a 4-bit-exact
+  // int8 model, two per byte (state -1: some value lies outside [-8, 7]).  The group scales stay where they are;
+  // everything but the decode launches reads the int8 image.  classes: plan_q4, hook KH_Q4_CLASSES.
+  struct Q4 : WCopy {
     int nparts_image = 0;   // m->nparts of the int8 launches (the ring classifier's grid), for a copy that is given up
-    std::vector<W16::Layer> layers;
-    const void* cls = nullptr;
   };
   Q4 q4;
 };
@@ -369,24 +367,25 @@ KhAttnArgs fill_attn(kh_model* m, int l, int variant, bool fenced);
 // on: what the launch streams its matrices from - the image, the 16-bit copy (kh_model::w16) or the 4-bit copy
 // (kh_model::q4); a kernel on a copy has the bits of the one on the image.  The forms without the argument follow the
 // model's plan.  A launch on the 4-bit copy has no ring form: it takes the place of the ring launch.
-enum { KH_ON_IMAGE = 0, KH_ON_W16 = 1, KH_ON_Q4 = 2 };
+// A type of its own: a bool or a class bit in its place does not compile.
+enum KhOn { KH_ON_IMAGE = 0, KH_ON_W16 = 1, KH_ON_Q4 = 2 };
 enum { KH_W16_QKV = 1, KH_W16_WO = 2, KH_W16_FFN13 = 4, KH_W16_W2 = 8, KH_W16_CLS = 16, KH_W16_ALL = 31 };
 // classes whose B-token pass reads the copy unless KH_W16_PASS says otherwise: the ones 3.1c's adoption rule keeps on
 // every geometry (profiles/w16_pass_ab.txt; qkv and wo fail it on Qwen2.5-0.5B, cls on TinyLlama)
 enum { KH_W16_PASS_DEFAULT = KH_W16_FFN13 | KH_W16_W2 };
 static inline bool w16_runs(const kh_model* m, int cls) { return (m->w16.classes & cls) != 0; }
 static inline bool q4_runs(const kh_model* m, int cls) { return (m->q4.classes & cls) != 0; }  // same class bits
-static inline int runs_on(const kh_model* m, int cls) {
+static inline KhOn runs_on(const kh_model* m, int cls) {
   return q4_runs(m, cls) ? KH_ON_Q4 : (w16_runs(m, cls) ? KH_ON_W16 : KH_ON_IMAGE);
 }
 // the B-token pass of the class (kh_model_prefill.hip: launch_pf_pass, pf_gemv_res, launch_pf_cls)
 static inline bool w16_pass_runs(const kh_model* m, int cls) { return (m->w16.pass_classes & cls) != 0; }
-void launch_qkv(kh_model* m, int l, int on);
+void launch_qkv(kh_model* m, int l, KhOn on);
 void launch_attn(kh_model* m, int l, int variant, bool fenced);
-void launch_wo(kh_model* m, int l, int variant, int on);
+void launch_wo(kh_model* m, int l, int variant, KhOn on);
 // ring: the LDS-DMA ring kernel (m->ring.ffn_r), else register tiles
-void launch_ffn13(kh_model* m, int l, bool ring, int on);
-void launch_w2(kh_model* m, int l, int on);
+void launch_ffn13(kh_model* m, int l, bool ring, KhOn on);
+void launch_w2(kh_model* m, int l, KhOn on);
 static inline void launch_qkv(kh_model* m, int l) { launch_qkv(m, l, runs_on(m, KH_W16_QKV)); }
 static inline void launch_wo(kh_model* m, int l, int variant) { launch_wo(m, l, variant, runs_on(m, KH_W16_WO)); }
 static inline void launch_ffn13(kh_model* m, int l, bool ring) { launch_ffn13(m, l, ring, runs_on(m, KH_W16_FFN13)); }
@@ -397,7 +396,7 @@ struct ClsIo {
   float *logits, *part_val;
   int32_t* part_idx;
 };
-void launch_cls(kh_model* m, const ClsIo& io, bool ring, int on);
+void launch_cls(kh_model* m, const ClsIo& io, bool ring, KhOn on);
 static inline void launch_cls(kh_model* m, const ClsIo& io, bool ring) {
   launch_cls(m, io, ring, runs_on(m, KH_W16_CLS));
 }
@@ -493,22 +492,15 @@ int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, in
 // the copy, once the weights are resident and ahead of the self-tests (no-op unless KH_FLAG_W16 / KH_W16=1 asks)
 int w16_create(kh_model* m);
 void w16_release(kh_model* m);  // frees the copy; no class runs on it afterwards
-// the W16 twins of the fp32 launches: `a` as the fp32 launch fills it, the matrices replaced by their copies here
-void w16_launch_qkv(kh_model* m, int l, const KhQkvArgs& a);
-void w16_launch_wo(kh_model* m, int l, const KhGemvResArgs& a);
-void w16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
-void w16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
-void w16_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
-void w16_launch_cls(kh_model* m, const KhClsArgs& a);
-// ---- kh_model_h16.hip: the same launches on an fp16-format copy (the w16_launch_* above hand over by w16.format;
-// one text, kh_w16_launch.h), the LDS opt-in of their w2 kernel ------------------------------------
-void h16_configure(const kh_model* m);
-void h16_launch_qkv(kh_model* m, int l, const KhQkvArgs& a);
-void h16_launch_wo(kh_model* m, int l, const KhGemvResArgs& a);
-void h16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
-void h16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
-void h16_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
-void h16_launch_cls(kh_model* m, const KhClsArgs& a);
+// The twins of the image's launches on a copy (on: KH_ON_W16 or KH_ON_Q4): `a` as the image's launch fills it, the
+// matrices replaced by their copies.  One text for every source (kh_copy_launch.h); routed here to the translation
+// unit that compiles the source's kernels - kh_model_w16.hip (bf16), kh_model_h16.hip (fp16), kh_model_q4.hip.
+void copy_launch_qkv(kh_model* m, int l, KhOn on, const KhQkvArgs& a);
+void copy_launch_wo(kh_model* m, int l, KhOn on, const KhGemvResArgs& a);
+void copy_launch_wo_comb(kh_model* m, int l, KhOn on, const KhWoCombArgs& a);
+void copy_launch_ffn13(kh_model* m, int l, KhOn on, const KhFfn13Args& a);
+void copy_launch_w2(kh_model* m, int l, KhOn on, const KhGemvResArgs& a);
+void copy_launch_cls(kh_model* m, KhOn on, const KhClsArgs& a);
 // ---- kh_model_q4.hip ------------------------------------------------------------------------
 // Launch classes that run on the 4-bit copy for a geometry (KH_W16_* bits, 0: not applicable) and the copy's bytes
 // (host-only)
@@ -516,13 +508,6 @@ int plan_q4(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, int
 // the copy, once the weights are resident and ahead of the self-tests (no-op unless KH_FLAG_Q4 / KH_Q4=1 asks)
 int q4_create(kh_model* m);
 void q4_release(kh_model* m);  // frees the copy; every class is back on what a model without the flag launches
-// the Q4 twins of the int8 launches: `a` as the int8 launch fills it, the matrices replaced by their copies here
-void q4_launch_qkv(kh_model* m, int l, const KhQkvArgs& a);
-void q4_launch_wo(kh_model* m, int l, const KhGemvResArgs& a);
-void q4_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& a);
-void q4_launch_ffn13(kh_model* m, int l, const KhFfn13Args& a);
-void q4_launch_w2(kh_model* m, int l, const KhGemvResArgs& a);
-void q4_launch_cls(kh_model* m, const KhClsArgs& a);
 // ---- kh_model_load.hip ----------------------------------------------------------------------
 // Make rows [0, rows) of the K / V cache usable before anything that touches them is enqueued: every layer, or one
 // (layer >= 0).  No-op for rows that are mapped already and for caches that are plainly allocated.  Newly mapped

@@ -25,7 +25,7 @@
 //  (f) Q4 (kh_q4.h, kh_model_q4.hip): every launch class that runs on the 4-bit copy, once against the int8 register-tile
 //      kernel of the same launch - layer 0 or the classifier, a real embedding row as the residual stream - outputs
 //      compared word for word.  A mismatch frees the copy and the model launches what it launches without the flag
-//      (kh_model_q4_info: state -2).
+//      (kh_model_q4_info: state -2).  (e) and (f) are one procedure, copy_selftest, told which copy to check.
 //
 // Both run on scratch state the model owns at that moment (activation buffers, rows of layer 0 of the still
 // empty KV cache, which are zeroed again) in about a millisecond.  This is a tripwire for a part, a compiler or a
@@ -183,101 +183,22 @@ static int attn_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result)
   return KH_OK;
 }
 
-// *result: 0 not applicable, 1 passed, -1 failed (the copy is freed, every class back on its fp32 kernel)
-static int w16_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
+// The weight copy `on` (KH_ON_W16 or KH_ON_Q4) against the image, class by class.
+// *result: 0 not applicable, 1 passed, -1 failed (the copy is freed, every class back on the image's launch)
+static int copy_selftest(kh_model* m, KhOn on, int32_t* d_flag, bool inject, int* result) {
   const kh_config& c = m->cfg;
+  const bool q4 = on == KH_ON_Q4;
+  kh_model::WCopy& w = q4 ? static_cast<kh_model::WCopy&>(m->q4) : m->w16;
   *result = 0;
-  if (m->w16.state != 1) return KH_OK;
+  if (w.state != 1) return KH_OK;
+  auto runs = [&](int cls) { return (w.classes & cls) != 0; };
   hipStream_t s = m->stream;
   const size_t dim = (size_t)c.dim, kv = (size_t)c.kv_dim, hid = (size_t)c.hidden_dim, voc = (size_t)c.vocab_size;
-  const size_t np = (size_t)m->nparts;
-  // scratch: x as the check found it | outputs of the W16 launch (q, K row, V row | x | h | logits)
-  size_t tmp_n = dim + 2 * kv;
-  if (hid > tmp_n) tmp_n = hid;
-  if (voc > tmp_n) tmp_n = voc;
-  KhDev<float> x0, tmp, tmp_pv;
-  KhDev<int32_t> tmp_pi;
-  int rc = kv_ensure(m, 1, /*layer=*/0);  // the qkv launch writes row 0 of layer 0
-  if (rc != KH_OK || (rc = x0.alloc(dim)) != KH_OK || (rc = tmp.alloc(tmp_n)) != KH_OK ||
-      (rc = tmp_pv.alloc(np)) != KH_OK || (rc = tmp_pi.alloc(np)) != KH_OK)
-    return rc;
-  auto diff = [&](const void* a, const void* b, size_t n) {  // words, whatever they hold
-    hipLaunchKernelGGL(k_st_diff, dim3(grid_for(n)), dim3(KH_WG), 0, s, (const uint32_t*)a, (const uint32_t*)b, n, d_flag);
-  };
-  auto copy = [&](float* dst, const float* src, size_t n) {
-    return hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, s);
-  };
-  hipError_t e = hipSuccess;
-  {
-    set_state(m, 1 % c.vocab_size, 0);  // x = a real embedding row
-    e = copy(x0, m->x, dim);
-    if (w16_runs(m, KH_W16_QKV) && e == hipSuccess) {
-      launch_qkv(m, 0, /*w16=*/true);  // -> q, row 0 of layer 0's K and V
-      e = copy(tmp, m->q, dim);
-      if (e == hipSuccess) e = copy(tmp + dim, m->kcache, kv);
-      if (e == hipSuccess) e = copy(tmp + dim + kv, m->vcache, kv);
-      launch_qkv(m, 0, /*w16=*/false);
-      diff(m->q, tmp, dim);
-      diff(m->kcache, tmp + dim, kv);
-      diff(m->vcache, tmp + dim + kv, kv);
-      if (e == hipSuccess) e = hipMemsetAsync(m->kcache, 0, sizeof(float) * kv, s);  // the cache is empty again
-      if (e == hipSuccess) e = hipMemsetAsync(m->vcache, 0, sizeof(float) * kv, s);
-    }
-    if (w16_runs(m, KH_W16_WO) && e == hipSuccess) {  // x += wo . att, on the projected query as the vector
-      e = copy(m->att, m->q, dim);
-      launch_wo(m, 0, /*variant=*/0, /*w16=*/true);
-      if (e == hipSuccess) e = copy(tmp, m->x, dim);
-      if (e == hipSuccess) e = copy(m->x, x0, dim);
-      launch_wo(m, 0, /*variant=*/0, /*w16=*/false);
-      diff(m->x, tmp, dim);
-    }
-    if (w16_runs(m, KH_W16_FFN13) && e == hipSuccess) {
-      launch_ffn13(m, 0, /*ring=*/false, /*w16=*/true);  // -> h1
-      e = copy(tmp, m->h1, hid);
-      launch_ffn13(m, 0, /*ring=*/false, /*w16=*/false);
-      diff(m->h1, tmp, hid);
-    }
-    if (w16_runs(m, KH_W16_W2) && e == hipSuccess) {  // x += w2 . h1 (h1: what ffn13 left, or an earlier check)
-      if (!w16_runs(m, KH_W16_FFN13)) launch_ffn13(m, 0, /*ring=*/false, /*w16=*/false);
-      e = copy(x0, m->x, dim);
-      launch_w2(m, 0, /*w16=*/true);
-      if (e == hipSuccess) e = copy(tmp, m->x, dim);
-      if (e == hipSuccess) e = copy(m->x, x0, dim);
-      launch_w2(m, 0, /*w16=*/false);
-      diff(m->x, tmp, dim);
-    }
-    if (w16_runs(m, KH_W16_CLS) && e == hipSuccess) {
-      launch_cls(m, {m->x, tmp, tmp_pv, tmp_pi}, /*ring=*/false, /*w16=*/true);
-      launch_cls(m, {m->x, m->logits, m->part_val, m->part_idx}, /*ring=*/false, /*w16=*/false);
-      diff(m->logits, tmp, voc);
-      diff(m->part_val, tmp_pv, np);
-      diff(m->part_idx, tmp_pi, np);
-    }
-  }
-  int32_t flag = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return (int)e;
-  if ((rc = kh_launch_status()) != KH_OK) return rc;
-  *result = 1;
-  if (!flag && !inject) return KH_OK;
-  *result = -1;
-  w16_release(m);
-  m->w16.state = -2;
-  m->w16.bytes = 0;
-  fprintf(stderr, "[kh] W16 self-check %s: the model streams its fp32 matrices\n", inject ? "reported as failed (hook)" : "FAILED");
-  return KH_OK;
-}
-
-// *result: 0 not applicable, 1 passed, -1 failed (the copy is freed, every class back on its int8 launch)
-static int q4_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
-  const kh_config& c = m->cfg;
-  *result = 0;
-  if (m->q4.state != 1) return KH_OK;
-  hipStream_t s = m->stream;
-  const size_t dim = (size_t)c.dim, kv = (size_t)c.kv_dim, hid = (size_t)c.hidden_dim, voc = (size_t)c.vocab_size;
-  const size_t np = (size_t)m->sh_cls.grid;  // both classifier launches below are register-tile launches
-  // scratch: x as the check found it | outputs of the Q4 launch (q, K row, V row | x | h | logits) | the int8 logits
+  // Both classifier launches below are register-tile launches.  (An fp32 model's m->nparts is this grid too: only a
+  // ring plan makes the two differ - kh_model_load.hip -, and plan_ring has none for fp32.)
+  const size_t np = (size_t)m->sh_cls.grid;
+  // scratch: x as the check found it | outputs of the copy's launch (q, K row, V row | x | h | logits) | the image's
+  // classifier outputs
   size_t tmp_n = dim + 2 * kv;
   if (hid > tmp_n) tmp_n = hid;
   if (voc > tmp_n) tmp_n = voc;
@@ -285,10 +206,14 @@ static int q4_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
   KhDev<int32_t> tmp_pi, ref_pi;
   int rc = kv_ensure(m, 1, /*layer=*/0);  // the qkv launch writes row 0 of layer 0
   if (rc != KH_OK || (rc = x0.alloc(dim)) != KH_OK || (rc = tmp.alloc(tmp_n)) != KH_OK) return rc;
-  if (q4_runs(m, KH_W16_CLS) &&
-      ((rc = ref.alloc(voc)) != KH_OK || (rc = tmp_pv.alloc(np)) != KH_OK || (rc = tmp_pi.alloc(np)) != KH_OK ||
-       (rc = ref_pv.alloc(np)) != KH_OK || (rc = ref_pi.alloc(np)) != KH_OK))
-    return rc;
+  if (runs(KH_W16_CLS) && ((rc = tmp_pv.alloc(np)) != KH_OK || (rc = tmp_pi.alloc(np)) != KH_OK)) return rc;
+  // The image's classifier launch of a W16 model writes the model's own buffers: they hold these logits until the first
+  // step (kh_model_get_logits of a fresh model).  A Q4 model's stay as they are.
+  ClsIo ref_io{m->x, m->logits, m->part_val, m->part_idx};
+  if (q4 && runs(KH_W16_CLS)) {
+    if ((rc = ref.alloc(voc)) != KH_OK || (rc = ref_pv.alloc(np)) != KH_OK || (rc = ref_pi.alloc(np)) != KH_OK) return rc;
+    ref_io = ClsIo{m->x, ref, ref_pv, ref_pi};
+  }
   auto diff = [&](const void* a, const void* b, size_t n) {  // words, whatever they hold
     hipLaunchKernelGGL(k_st_diff, dim3(grid_for(n)), dim3(KH_WG), 0, s, (const uint32_t*)a, (const uint32_t*)b, n, d_flag);
   };
@@ -297,8 +222,8 @@ static int q4_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
   };
   set_state(m, 1 % c.vocab_size, 0);  // x = a real embedding row
   hipError_t e = copy(x0, m->x, dim);
-  if (q4_runs(m, KH_W16_QKV) && e == hipSuccess) {
-    launch_qkv(m, 0, KH_ON_Q4);  // -> q, row 0 of layer 0's K and V
+  if (runs(KH_W16_QKV) && e == hipSuccess) {
+    launch_qkv(m, 0, on);  // -> q, row 0 of layer 0's K and V
     e = copy(tmp, m->q, dim);
     if (e == hipSuccess) e = copy(tmp + dim, m->kcache, kv);
     if (e == hipSuccess) e = copy(tmp + dim + kv, m->vcache, kv);
@@ -308,40 +233,40 @@ static int q4_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
     diff(m->vcache, tmp + dim + kv, kv);
     if (e == hipSuccess) e = hipMemsetAsync(m->kcache, 0, sizeof(float) * kv, s);  // the cache is empty again
     if (e == hipSuccess) e = hipMemsetAsync(m->vcache, 0, sizeof(float) * kv, s);
-  } else if (q4_runs(m, KH_W16_WO) && e == hipSuccess) {
+  } else if (runs(KH_W16_WO) && e == hipSuccess) {
     launch_qkv(m, 0, KH_ON_IMAGE);  // wo's vector below
     e = hipMemsetAsync(m->kcache, 0, sizeof(float) * kv, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->vcache, 0, sizeof(float) * kv, s);
   }
-  if (q4_runs(m, KH_W16_WO) && e == hipSuccess) {  // x += wo . att, on the projected query as the vector
+  if (runs(KH_W16_WO) && e == hipSuccess) {  // x += wo . att, on the projected query as the vector
     e = copy(m->att, m->q, dim);
-    launch_wo(m, 0, /*variant=*/0, KH_ON_Q4);
+    launch_wo(m, 0, /*variant=*/0, on);
     if (e == hipSuccess) e = copy(tmp, m->x, dim);
     if (e == hipSuccess) e = copy(m->x, x0, dim);
     launch_wo(m, 0, /*variant=*/0, KH_ON_IMAGE);
     diff(m->x, tmp, dim);
   }
-  if (q4_runs(m, KH_W16_FFN13) && e == hipSuccess) {
-    launch_ffn13(m, 0, /*ring=*/false, KH_ON_Q4);  // -> h1
+  if (runs(KH_W16_FFN13) && e == hipSuccess) {
+    launch_ffn13(m, 0, /*ring=*/false, on);  // -> h1
     e = copy(tmp, m->h1, hid);
     launch_ffn13(m, 0, /*ring=*/false, KH_ON_IMAGE);
     diff(m->h1, tmp, hid);
   }
-  if (q4_runs(m, KH_W16_W2) && e == hipSuccess) {  // x += w2 . h1 (h1: what ffn13 left, or computed here)
-    if (!q4_runs(m, KH_W16_FFN13)) launch_ffn13(m, 0, /*ring=*/false, KH_ON_IMAGE);
+  if (runs(KH_W16_W2) && e == hipSuccess) {  // x += w2 . h1 (h1: what ffn13 left, or computed here)
+    if (!runs(KH_W16_FFN13)) launch_ffn13(m, 0, /*ring=*/false, KH_ON_IMAGE);
     e = copy(x0, m->x, dim);
-    launch_w2(m, 0, KH_ON_Q4);
+    launch_w2(m, 0, on);
     if (e == hipSuccess) e = copy(tmp, m->x, dim);
     if (e == hipSuccess) e = copy(m->x, x0, dim);
     launch_w2(m, 0, KH_ON_IMAGE);
     diff(m->x, tmp, dim);
   }
-  if (q4_runs(m, KH_W16_CLS) && e == hipSuccess) {
-    launch_cls(m, {m->x, tmp, tmp_pv, tmp_pi}, /*ring=*/false, KH_ON_Q4);
-    launch_cls(m, {m->x, ref, ref_pv, ref_pi}, /*ring=*/false, KH_ON_IMAGE);
-    diff(ref, tmp, voc);
-    diff(ref_pv, tmp_pv, np);
-    diff(ref_pi, tmp_pi, np);
+  if (runs(KH_W16_CLS) && e == hipSuccess) {
+    launch_cls(m, {m->x, tmp, tmp_pv, tmp_pi}, /*ring=*/false, on);
+    launch_cls(m, ref_io, /*ring=*/false, KH_ON_IMAGE);
+    diff(ref_io.logits, tmp, voc);
+    diff(ref_io.part_val, tmp_pv, np);
+    diff(ref_io.part_idx, tmp_pi, np);
   }
   int32_t flag = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s);
@@ -351,9 +276,10 @@ static int q4_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result) {
   *result = 1;
   if (!flag && !inject) return KH_OK;
   *result = -1;
-  q4_release(m);
-  m->q4.state = -2;
-  fprintf(stderr, "[kh] Q4 self-check %s: the model streams its int8 matrices\n", inject ? "reported as failed (hook)" : "FAILED");
+  q4 ? q4_release(m) : w16_release(m);
+  w.state = -2;
+  fprintf(stderr, "[kh] %s self-check %s: the model streams its %s matrices\n", q4 ? "Q4" : "W16",
+          inject ? "reported as failed (hook)" : "FAILED", q4 ? "int8" : "fp32");
   return KH_OK;
 }
 
@@ -372,8 +298,8 @@ int run_selftests(kh_model* m) {
   int r = 0, a = 0, sc = 0, s8 = 0, w = 0, q4 = 0;
   KH_CHECK_HIP(hipMemsetAsync(d_flag, 0, 6 * sizeof(int32_t), m->stream));
   // W16 first: the checks behind it then run on the kernels the model will launch
-  if ((rc = w16_selftest(m, d_flag + 4, hook_has(inj, "w16"), &w)) != KH_OK) return rc;
-  if ((rc = q4_selftest(m, d_flag + 5, hook_has(inj, "q4"), &q4)) != KH_OK) return rc;
+  if ((rc = copy_selftest(m, KH_ON_W16, d_flag + 4, hook_has(inj, "w16"), &w)) != KH_OK) return rc;
+  if ((rc = copy_selftest(m, KH_ON_Q4, d_flag + 5, hook_has(inj, "q4"), &q4)) != KH_OK) return rc;
   if ((rc = ring_selftest(m, d_flag, hook_has(inj, "ring"), &r)) != KH_OK) return rc;
   if ((rc = attn_selftest(m, d_flag + 1, hook_has(inj, "attn"), &a)) != KH_OK) return rc;
   if ((rc = cls_screen_selftest(m, d_flag + 2, hook_has_screen(inj), &sc)) != KH_OK) return rc;

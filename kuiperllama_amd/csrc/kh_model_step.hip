@@ -140,11 +140,10 @@ KhQkvArgs fill_qkv(kh_model* m, int l) {
   a.eps = c.rms_eps;
   return a;
 }
-void launch_qkv(kh_model* m, int l, int on) {
+void launch_qkv(kh_model* m, int l, KhOn on) {
   const kh_config& c = m->cfg;
   const KhQkvArgs a = fill_qkv(m, l);
-  if (on == KH_ON_W16) return w16_launch_qkv(m, l, a);  // the same shape on the 16-bit copy (kh_model_w16.hip)
-  if (on == KH_ON_Q4) return q4_launch_qkv(m, l, a);    // ... on the 4-bit copy (kh_model_q4.hip)
+  if (on != KH_ON_IMAGE) return copy_launch_qkv(m, l, on, a);  // the same shape on a weight copy (kh_model_w16.hip)
   const kh_model::Shape& sh = m->sh_qkv;
   pick_fused<FusedU, FusedMV, QkvSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split,
                                      [&](auto Q, auto U, auto MV, auto SP) {
@@ -205,7 +204,7 @@ KhGemvResArgs fill_wo(kh_model* m, int l) {
   a.gshift = m->gshift;
   return a;
 }
-void launch_wo(kh_model* m, int l, int variant, int on) {
+void launch_wo(kh_model* m, int l, int variant, KhOn on) {
   const kh_config& c = m->cfg;
   const kh_model::Shape& sh = m->sh_wo;
   if (variant == 1) {  // behind a deferring attention launch: in-register staging of 2 or 4 float4
@@ -220,8 +219,7 @@ void launch_wo(kh_model* m, int l, int variant, int on) {
     a.cb.nsw = m->attn_ws_stride;
     a.cb.heads = c.head_num;
     a.cb.hs = c.head_size;
-    if (on == KH_ON_W16) return w16_launch_wo_comb(m, l, a);
-    if (on == KH_ON_Q4) return q4_launch_wo_comb(m, l, a);
+    if (on != KH_ON_IMAGE) return copy_launch_wo_comb(m, l, on, a);
     pick_fused<FusedU, WoCombMV, GemvResSP>(c.is_quant, sh.u, c.dim <= 2 * 4 * sh.wg ? 2 : 4, sh.split,
                                             [&](auto Q, auto U, auto MV, auto SP) {
       kh_launch(KH_KERNEL(k_wo_comb, Q, U, MV, SP), sh.grid, sh.wg, comb_lds_bytes(Q, c.dim, c.head_num), m->stream, a);
@@ -229,14 +227,13 @@ void launch_wo(kh_model* m, int l, int variant, int on) {
     return;
   }
   const KhGemvResArgs a = fill_wo(m, l);
-  if (on == KH_ON_W16) return w16_launch_wo(m, l, a);
-  if (on == KH_ON_Q4) return q4_launch_wo(m, l, a);
+  if (on != KH_ON_IMAGE) return copy_launch_wo(m, l, on, a);
   pick_fused<FusedU, FusedMV, GemvResSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), sh.split,
                                          [&](auto Q, auto U, auto MV, auto SP) {
     kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
   });
 }
-void launch_ffn13(kh_model* m, int l, bool ring, int on) {
+void launch_ffn13(kh_model* m, int l, bool ring, KhOn on) {
   const kh_config& c = m->cfg;
   const LayerW& W = m->layers[l];
   KhFfn13Args a;
@@ -249,20 +246,21 @@ void launch_ffn13(kh_model* m, int l, bool ring, int on) {
   a.hidden = c.hidden_dim;
   a.gshift = m->gshift;
   a.eps = c.rms_eps;
-  if (on == KH_ON_Q4) return q4_launch_ffn13(m, l, a);  // in the ring launch's place: the copy has no ring form
+  // Ahead of the ring branch: on the 4-bit copy the launch takes the ring launch's place (the copy has no ring form),
+  // and a model with a 16-bit copy is fp32 and never has a ring plan (plan_ring returns an empty one unless quant)
+  if (on != KH_ON_IMAGE) return copy_launch_ffn13(m, l, on, a);
   // the int8 LDS-DMA ring kernels (kh_fused_ring.h): 2 ring slots per wave, 4 float4 staged per thread, plain layout
   if (ring) {  // plan_ring: int8, dim a multiple of 256 floats and at most 16 per thread
     kh_launch(KH_KERNEL(k_ffn13_ring, 2, 4, false), m->ring.ffn_grid, KH_WG,
               ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
-  if (on == KH_ON_W16) return w16_launch_ffn13(m, l, a);
   const kh_model::Shape& sh = m->sh_ffn;
   pick_fused<FusedU, FusedMV, NoSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto Q, auto U, auto MV, auto) {
     kh_launch(KH_KERNEL(k_ffn13, Q, U, MV), sh.grid, sh.wg, fused_lds_bytes(Q, c.dim), m->stream, a);
   });
 }
-void launch_w2(kh_model* m, int l, int on) {
+void launch_w2(kh_model* m, int l, KhOn on) {
   const kh_config& c = m->cfg;
   KhGemvResArgs a;
   a.vec = m->h1;
@@ -271,15 +269,14 @@ void launch_w2(kh_model* m, int l, int on) {
   a.M = c.hidden_dim;
   a.K = c.dim;
   a.gshift = m->gshift;
-  if (on == KH_ON_W16) return w16_launch_w2(m, l, a);
-  if (on == KH_ON_Q4) return q4_launch_w2(m, l, a);
+  if (on != KH_ON_IMAGE) return copy_launch_w2(m, l, on, a);
   const kh_model::Shape& sh = m->sh_w2;  // int8 u 3: two exact tiles of three loads per row (pick_shape, u3)
   pick_fused<GemvResU, GemvResMV, GemvResSP>(c.is_quant, sh.u, kh_stage_maxv(c.hidden_dim, sh.wg), sh.split,
                                              [&](auto Q, auto U, auto MV, auto SP) {
     kh_launch(KH_KERNEL(k_gemv_res, Q, U, MV, SP), sh.grid, sh.wg, fused_lds_bytes(Q, c.hidden_dim), m->stream, a);
   });
 }
-void launch_cls(kh_model* m, const ClsIo& io, bool ring, int on) {
+void launch_cls(kh_model* m, const ClsIo& io, bool ring, KhOn on) {
   const kh_config& c = m->cfg;
   if (io.logits == m->logits) logits_fresh(m);  // (enqueue_steps has the last word behind captured steps)
   KhClsArgs a;
@@ -293,14 +290,14 @@ void launch_cls(kh_model* m, const ClsIo& io, bool ring, int on) {
   a.vocab = c.vocab_size;
   a.gshift = m->gshift;
   a.eps = c.rms_eps;
-  if (on == KH_ON_Q4) return q4_launch_cls(m, a);  // in the ring launch's place (m->nparts follows: q4_create)
+  // ahead of the ring branch, as in launch_ffn13 (on the 4-bit copy m->nparts follows the launch: q4_create)
+  if (on != KH_ON_IMAGE) return copy_launch_cls(m, on, a);
   // the classifier is int8 only when the model is quantised (untied; llama3.cpp:255-268)
   if (ring) {
     kh_launch(KH_KERNEL(k_cls_ring, 2, 4, false), m->ring.cls_grid, KH_WG,
               ring_lds_bytes(c.dim, false, KH_WAVES_PER_WG, 2), m->stream, a);
     return;
   }
-  if (on == KH_ON_W16) return w16_launch_cls(m, a);
   const kh_model::Shape& sh = m->sh_cls;
   pick_fused<FusedU, FusedMV, NoSP>(c.is_quant, sh.u, kh_stage_maxv(c.dim, sh.wg), 1, [&](auto Q, auto U, auto MV, auto) {
     kh_launch(KH_KERNEL(k_cls, Q, U, MV), sh.grid, sh.wg, cls_lds_bytes(Q, c.dim), m->stream, a);

@@ -1,22 +1,25 @@
 // kh_model_w16.hip — W16 at the model level: the 16-bit copy of a bf16-exact (or, with KH_FLAG_W16_F16, fp16-exact)
-// fp32 model's matrices (plan, build, exactness check, release, the class masks of decode and of the B-token passes),
-// the decode GEMV launches that read it and kh_model_w16_info (the passes' launches: kh_model_prefill.hip; the
-// launches of an fp16-format copy: kh_model_h16.hip, kh_model_h16_pass.hip).  The kernels are kh_w16.h's;
-// each launch is the fp32 launch of kh_model_step.hip with the same shape (split, u, grid, wg - a shape forced
-// through KH_SHAPE_* included) on the W16 twin of its kernel, so the bits do not change.
+// fp32 model's matrices (plan, exactness check, release, the class masks of decode and of the B-token passes) and
+// kh_model_w16_info - and what W16 shares with the 4-bit copy of an int8 model (kh_model_q4.hip): the bytes of a copy,
+// its build (arena, one build kernel over every matrix, per-tensor exactness flags), its release, and the routing of the
+// decode GEMV launches on a copy to the translation unit of their source (the launch text: kh_copy_launch.h; the
+// passes' launches: kh_model_prefill.hip, kh_model_h16_pass.hip).  The kernels here are kh_w16.h's _w16 ones; each
+// launch is the image's launch of kh_model_step.hip with the same shape (split, u, grid, wg - a shape forced through
+// KH_SHAPE_* included) on the twin of its kernel, so the bits do not change.
 // Replaces nothing in the reference (it streams fp32 weights: kuiper/source/op/kernels/cuda/matmul_kernel.cu:8-44).
 // gfx950 only.  No CPU fallback: every path below launches HIP kernels.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "kh_w16_launch.h"
+#include "kh_copy_launch.h"
 
 namespace khm {
 
+// ---- what every weight copy shares (W16 in both formats, Q4: kh_model_q4.hip) -----------------------------------
 namespace {
 inline size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
-// the matrices the copy covers, in tensor-index order: {rows K, columns M} of wq, wk, wv, wo, w1, w2, w3
+// the matrices a copy covers, in tensor-index order: {rows K, columns M} of wq, wk, wv, wo, w1, w2, w3
 inline void layer_dims(int dim, int hidden, int kv_dim, size_t (&K)[7], size_t (&M)[7]) {
   const size_t d = (size_t)dim, h = (size_t)hidden, kv = (size_t)kv_dim;
   const size_t k[7] = {d, kv, kv, d, h, d, h}, mm[7] = {d, d, d, d, d, h, d};
@@ -27,6 +30,73 @@ inline void layer_dims(int dim, int hidden, int kv_dim, size_t (&K)[7], size_t (
 }
 }  // namespace
 
+size_t copy_bytes(int dim, int hidden_dim, int kv_dim, int vocab_size, int layer_num, KhCopyMatBytes mat_bytes) {
+  size_t K[7], M[7], total = 0;
+  layer_dims(dim, hidden_dim, kv_dim, K, M);
+  for (int i = 0; i < 7; ++i) total += pad256(mat_bytes(K[i] * M[i]));
+  return total * (size_t)layer_num + pad256(mat_bytes((size_t)vocab_size * (size_t)dim));
+}
+
+void copy_release(kh_model::WCopy& w) {
+  w.alloc.reset();
+  w.arena = nullptr;
+  w.classes = 0;
+  w.bytes = 0;
+  w.layers.clear();
+  w.cls = nullptr;
+}
+
+int copy_build(kh_model* m, kh_model::WCopy& w, KhCopyBuildKernel kernel, KhCopyMatBytes mat_bytes, int per_item,
+               size_t bytes, int* first) {
+  const kh_config& c = m->cfg;
+  const int nt = 7 * c.layer_num + 1;
+  int rc;
+  if (!w.arena) {
+    if ((rc = w.alloc.alloc(bytes + 4096)) != KH_OK) return rc;
+    w.arena = (char*)(((uintptr_t)w.alloc.get() + 4095) & ~(uintptr_t)4095);
+    w.layers.resize((size_t)c.layer_num);
+  }
+  KhDev<uint32_t> d_flags;  // per tensor: some value is not exact in the copy being built
+  if ((rc = d_flags.alloc((size_t)nt)) != KH_OK) return rc;
+  hipStream_t s = m->stream;
+  size_t K[7], M[7], off = 0;
+  layer_dims(c.dim, c.hidden_dim, c.kv_dim, K, M);
+  hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * (size_t)nt, s);
+  if (e == hipSuccess) e = hipEventRecord(m->ev0, s);
+  auto build = [&](const void* src, size_t elems, int tensor) -> const void* {
+    char* dst = w.arena + off;
+    off += pad256(mat_bytes(elems));
+    const size_t n = elems / (size_t)per_item, need = (n + KH_WG - 1) / KH_WG;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(need < 4096 ? (need ? need : 1) : 4096)), dim3(KH_WG), 0, s,
+                       (const u32x4*)src, (u32x2*)dst, n, d_flags + tensor);
+    return dst;
+  };
+  for (int l = 0; l < c.layer_num && e == hipSuccess; ++l) {
+    const LayerW& W = m->layers[(size_t)l];
+    const void* src[7] = {W.wq.w, W.wk.w, W.wv.w, W.wo.w, W.w1.w, W.w2.w, W.w3.w};
+    const void* dst[7];
+    for (int i = 0; i < 7; ++i) dst[i] = build(src[i], K[i] * M[i], 7 * l + i);
+    w.layers[(size_t)l] = kh_model::WCopy::Layer{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5], dst[6]};
+  }
+  w.cls = build(m->cls.w, (size_t)c.vocab_size * (size_t)c.dim, nt - 1);  // tok_emb when the classifier is tied
+  std::vector<uint32_t> flags((size_t)nt, 0);
+  if (e == hipSuccess) e = hipEventRecord(m->ev1, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  rc = e == hipSuccess ? kh_launch_status() : (int)e;
+  if (rc == KH_OK && off != bytes) rc = KH_ERR_INTERNAL;
+  if (rc != KH_OK) return rc;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, m->ev0, m->ev1) == hipSuccess) w.build_us += ms * 1000.f;
+  *first = -1;
+  for (int t = 0; t < nt && *first < 0; ++t)
+    if (flags[(size_t)t]) *first = t;
+  return KH_OK;
+}
+
+// ---- W16 ------------------------------------------------------------------------------------------
+static size_t w16_mat_bytes(size_t elems) { return 2 * elems; }  // either format
+
 // Which launch classes run on the copy.  Every class does: in the same-box A/B (tools/w16_ab.py, profiles/w16_ab.txt)
 // each class's W16 median lies below its fp32 median by more than the range of the fp32 runs on all four geometries
 // (smallest margin: Qwen2.5-0.5B's qkv, 2.90 -> 2.85 us).  A class that one takes out here keeps its fp32 kernel and
@@ -35,24 +105,14 @@ int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, in
   if (bytes) *bytes = 0;
   if (quant || dim <= 0 || hidden_dim <= 0 || kv_dim <= 0 || vocab_size <= 0 || layer_num <= 0) return 0;
   if (dim % 4 != 0 || hidden_dim % 4 != 0) return 0;  // a lane's unit is four columns
-  size_t K[7], M[7], total = 0;
-  layer_dims(dim, hidden_dim, kv_dim, K, M);
-  for (int i = 0; i < 7; ++i) total += pad256(2 * K[i] * M[i]);
-  total *= (size_t)layer_num;
-  total += pad256(2 * (size_t)vocab_size * (size_t)dim);
-  if (bytes) *bytes = total;
+  if (bytes) *bytes = copy_bytes(dim, hidden_dim, kv_dim, vocab_size, layer_num, w16_mat_bytes);
   return KH_W16_ALL;
 }
 
 void w16_release(kh_model* m) {
-  kh_model::W16& w = m->w16;
-  w.alloc.reset();
-  w.arena = nullptr;
-  w.classes = 0;
-  w.pass_classes = 0;
-  w.format = KH_W16_BF16;
-  w.layers.clear();
-  w.cls = nullptr;
+  copy_release(m->w16);
+  m->w16.pass_classes = 0;
+  m->w16.format = KH_W16_BF16;
 }
 
 // Which classes run their B-token pass (kh_w16_pass.h) on the copy as well: those of KH_W16_PASS_DEFAULT that decode
@@ -78,58 +138,11 @@ int w16_create(kh_model* m) {
   size_t bytes = 0;
   const int classes = plan_w16(c.is_quant != 0, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size, c.layer_num, &bytes);
   if (!classes) return KH_OK;  // int8, or a geometry the view does not cover: nothing changes
-  const int nt = 7 * c.layer_num + 1;
-  KhDev<uint32_t> d_flags;  // per tensor: some word is not exact in the format being built
-  int rc;
-  if ((rc = w.alloc.alloc(bytes + 4096)) != KH_OK || (rc = d_flags.alloc((size_t)nt)) != KH_OK) {
-    w16_release(m);
-    return rc;
-  }
-  w.arena = (char*)(((uintptr_t)w.alloc.get() + 4095) & ~(uintptr_t)4095);
-  w.layers.resize((size_t)c.layer_num);
-  hipStream_t s = m->stream;
-  size_t K[7], M[7];
-  layer_dims(c.dim, c.hidden_dim, c.kv_dim, K, M);
-  // one pass of a build kernel over every matrix -> KH_OK and *first = the first inexact tensor (-1: none)
-  auto build_all = [&](auto kernel, int* first) -> int {
-    size_t off = 0;
-    hipError_t e = hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * (size_t)nt, s);
-    if (e == hipSuccess) e = hipEventRecord(m->ev0, s);
-    auto build = [&](const void* src, size_t elems, int tensor) -> const void* {
-      char* dst = w.arena + off;
-      off += pad256(2 * elems);
-      const size_t n4 = elems / 4, need = (n4 + KH_WG - 1) / KH_WG;
-      hipLaunchKernelGGL(kernel, dim3((unsigned)(need < 4096 ? (need ? need : 1) : 4096)), dim3(KH_WG), 0, s,
-                         (const u32x4*)src, (u32x2*)dst, n4, d_flags + tensor);
-      return dst;
-    };
-    for (int l = 0; l < c.layer_num && e == hipSuccess; ++l) {
-      const LayerW& W = m->layers[(size_t)l];
-      const void* src[7] = {W.wq.w, W.wk.w, W.wv.w, W.wo.w, W.w1.w, W.w2.w, W.w3.w};
-      const void* dst[7];
-      for (int i = 0; i < 7; ++i) dst[i] = build(src[i], K[i] * M[i], 7 * l + i);
-      w.layers[(size_t)l] = kh_model::W16::Layer{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5], dst[6]};
-    }
-    w.cls = build(m->cls.w, (size_t)c.vocab_size * (size_t)c.dim, nt - 1);  // tok_emb when the classifier is tied
-    std::vector<uint32_t> flags((size_t)nt, 0);
-    if (e == hipSuccess) e = hipEventRecord(m->ev1, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int r = e == hipSuccess ? kh_launch_status() : (int)e;
-    if (r == KH_OK && off != bytes) r = KH_ERR_INTERNAL;
-    if (r != KH_OK) return r;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, m->ev0, m->ev1) == hipSuccess) w.build_us += ms * 1000.f;
-    *first = -1;
-    for (int t = 0; t < nt && *first < 0; ++t)
-      if (flags[(size_t)t]) *first = t;
-    return KH_OK;
-  };
   int first = -1, first_f16 = -1, format = KH_W16_BF16;
-  rc = build_all(k_w16_build, &first);
+  int rc = copy_build(m, w, k_w16_build, w16_mat_bytes, 4, bytes, &first);
   if (rc == KH_OK && first >= 0 && try_f16) {
     format = KH_W16_F16;
-    rc = build_all(k_h16_build, &first_f16);
+    rc = copy_build(m, w, k_h16_build, w16_mat_bytes, 4, bytes, &first_f16);
   }
   if (rc != KH_OK) {
     w16_release(m);
@@ -144,42 +157,32 @@ int w16_create(kh_model* m) {
   }
   w.bytes = bytes;
   w.format = format;
-  if (format == KH_W16_F16)
-    h16_configure(m);
-  else
-    w16_configure_fmt<KH_W16_BF16>(m);
+  format == KH_W16_F16 ? copy_configure<KH_SRC_F16>(m) : copy_configure<KH_SRC_BF16>(m);
   w.classes = classes;
   w.pass_classes = classes & w16_pass_mask();
   w.state = 1;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
     fprintf(stderr, "[kh] W16: %.1f MiB %s copy of %d matrices in %.0f us, classes 0x%x, passes 0x%x\n",
-            (double)bytes / (1 << 20), format == KH_W16_F16 ? "fp16" : "bf16", nt, (double)w.build_us,
+            (double)bytes / (1 << 20), format == KH_W16_F16 ? "fp16" : "bf16", 7 * c.layer_num + 1, (double)w.build_us,
             (unsigned)classes, (unsigned)w.pass_classes);
   return KH_OK;
 }
 
-// ---- the launches (kh_w16_launch.h) ------------------------------------------------------------
-// This translation unit compiles the _w16 kernels; an fp16-format copy goes to kh_model_h16.hip, which compiles the
-// _h16 kernels from the same launch text.
-static inline bool f16_copy(const kh_model* m) { return m->w16.format == KH_W16_F16; }
-void w16_launch_qkv(kh_model* m, int l, const KhQkvArgs& fp32) {
-  f16_copy(m) ? h16_launch_qkv(m, l, fp32) : w16_qkv_fmt<KH_W16_BF16>(m, l, fp32);
-}
-void w16_launch_wo(kh_model* m, int l, const KhGemvResArgs& fp32) {
-  f16_copy(m) ? h16_launch_wo(m, l, fp32) : w16_wo_fmt<KH_W16_BF16>(m, l, fp32);
-}
-void w16_launch_wo_comb(kh_model* m, int l, const KhWoCombArgs& fp32) {
-  f16_copy(m) ? h16_launch_wo_comb(m, l, fp32) : w16_wo_comb_fmt<KH_W16_BF16>(m, l, fp32);
-}
-void w16_launch_ffn13(kh_model* m, int l, const KhFfn13Args& fp32) {
-  f16_copy(m) ? h16_launch_ffn13(m, l, fp32) : w16_ffn13_fmt<KH_W16_BF16>(m, l, fp32);
-}
-void w16_launch_w2(kh_model* m, int l, const KhGemvResArgs& fp32) {
-  f16_copy(m) ? h16_launch_w2(m, l, fp32) : w16_w2_fmt<KH_W16_BF16>(m, l, fp32);
-}
-void w16_launch_cls(kh_model* m, const KhClsArgs& fp32) {
-  f16_copy(m) ? h16_launch_cls(m, fp32) : w16_cls_fmt<KH_W16_BF16>(m, fp32);
-}
+// ---- the launches on a copy (kh_copy_launch.h) -------------------------------------------------------
+// This translation unit compiles the _w16 kernels; an fp16-format copy goes to kh_model_h16.hip and the 4-bit copy to
+// kh_model_q4.hip, which compile the _h16 and _q4 kernels from the same launch text.
+KH_COPY_LAUNCHES(, KH_SRC_BF16);
+// fn<source>(...): the 4-bit copy where the launch is on it, else the 16-bit copy in its format
+#define KH_COPY_ROUTE(fn, m, on, ...)                             \
+  ((on) == KH_ON_Q4                ? fn<KH_SRC_Q4>(__VA_ARGS__)   \
+   : (m)->w16.format == KH_W16_F16 ? fn<KH_SRC_F16>(__VA_ARGS__)  \
+                                   : fn<KH_SRC_BF16>(__VA_ARGS__))
+void copy_launch_qkv(kh_model* m, int l, KhOn on, const KhQkvArgs& a) { KH_COPY_ROUTE(copy_qkv, m, on, m, l, a); }
+void copy_launch_wo(kh_model* m, int l, KhOn on, const KhGemvResArgs& a) { KH_COPY_ROUTE(copy_wo, m, on, m, l, a); }
+void copy_launch_wo_comb(kh_model* m, int l, KhOn on, const KhWoCombArgs& a) { KH_COPY_ROUTE(copy_wo_comb, m, on, m, l, a); }
+void copy_launch_ffn13(kh_model* m, int l, KhOn on, const KhFfn13Args& a) { KH_COPY_ROUTE(copy_ffn13, m, on, m, l, a); }
+void copy_launch_w2(kh_model* m, int l, KhOn on, const KhGemvResArgs& a) { KH_COPY_ROUTE(copy_w2, m, on, m, l, a); }
+void copy_launch_cls(kh_model* m, KhOn on, const KhClsArgs& a) { KH_COPY_ROUTE(copy_cls, m, on, m, a); }
 
 }  // namespace khm
 using namespace khm;

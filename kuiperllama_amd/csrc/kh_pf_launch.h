@@ -8,7 +8,7 @@
 
 #include "kh_dispatch.h"
 #include "kh_model_internal.h"
-#include "kh_w16_launch.h"
+#include "kh_copy_launch.h"
 #include "kh_w16_pass.h"
 
 namespace khm {
@@ -75,7 +75,7 @@ void pick_pf(bool quant, int sp, int b, F&& f) {
 }
 // ---- the twins on the 16-bit copy (kh_w16_pass.h): `fp32` as the fp32 launch fills it, the matrices of layer l
 // replaced by their 16-bit copies, on the fp32 launch's shape, LDS bytes (the plain layout) and clipped grid - the fp32
-// lists without their int8 level, as pick_w16 of kh_w16_launch.h
+// lists without their int8 level, as pick_copy of kh_copy_launch.h
 template <class SPS, class BS, class F>
 void pick_pf_w16(int sp, int b, F&& f) {
   kh_pick(SPS{}, sp, [&](auto SP) { kh_pick_ge(BS{}, b, [&](auto B) { f(SP, B); }); });

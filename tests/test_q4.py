@@ -127,6 +127,9 @@ def test_plan_q4_bytes_and_classes():
     llama = binfmt.PRESETS["llama2-7b-int8"]
     p = _ffi.plan_q4(llama.dim, llama.hidden_dim, llama.kv_dim, llama.vocab_size, llama.n_layers, True, 64)
     assert p["bytes"] * 2 == sum(e.nbytes for e, _ in binfmt.q4_tensors(llama))  # half the int8 matrix bytes
+    # totals and the default classes of the library before W16 and Q4 shared their byte count (copy_bytes)
+    assert _ffi.plan_q4(64, 64, 64, 1, 1, True, 64) == {"classes": ["ffn13", "w2", "cls"], "bytes": 14592}
+    assert p == {"classes": ["ffn13", "w2", "cls"], "bytes": 3303538688}
     assert _ffi.plan_q4(72, 128, 72, 37, 2, True, 64) == {"classes": [], "bytes": 0}  # dim no multiple of the group
     assert _ffi.plan_q4(64, 128, 64, 37, 2, True, 8) == {"classes": [], "bytes": 0}   # a group below a lane's unit
     out = (_ffi._i64 * 2)()

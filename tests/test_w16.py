@@ -129,6 +129,16 @@ def test_plan_w16_bytes_and_classes():
         assert p["bytes"] == want, (name, p, want)  # every BASELINE matrix is a multiple of 256 bytes: no padding
         assert p["bytes"] * 2 == sum(e.nbytes for e in binfmt.w16_tensors(spec))  # half the matrix bytes
         assert set(p["classes"]) <= set(_ffi.KH_W16_CLASSES) and p["classes"], name
+    # matrices that are no multiple of 256 bytes: each is padded on its own (the copy's byte count is one function for
+    # W16 and Q4, kh_model_w16.hip::copy_bytes; the totals are those of the library before the two were merged)
+    def pad(n):
+        return (n + 255) & ~255
+    dim, hid, kv, voc = 132, 356, 68, 1001
+    want = 2 * pad(2 * dim * dim) + 2 * pad(2 * kv * dim) + 3 * pad(2 * hid * dim) + pad(2 * voc * dim)
+    assert want == 653568 != 2 * (2 * dim * dim + 2 * kv * dim + 3 * hid * dim + voc * dim)
+    assert _ffi.plan_w16(dim, hid, kv, voc, 1, False) == {"classes": list(_ffi.KH_W16_CLASSES), "bytes": want}
+    assert _ffi.plan_w16(64, 64, 64, 1, 1, False)["bytes"] == 57600
+    assert _ffi.plan_w16(256, 688, 128, 2048, 2, False)["bytes"] == 3948544
     assert _ffi.plan_w16(66, 96, 66, 37, 2, False) == {"classes": [], "bytes": 0}  # dim no multiple of 4
     out = (_ffi._i64 * 2)()
     assert _ffi.lib().kh_plan_w16(0, 96, 64, 37, 2, 0, out) == _ffi.KH_ERR_INVALID_ARG
