@@ -58,6 +58,13 @@ int kh_add_f32(const float* in1, const float* in2, float* out, int32_t n, void* 
 /* MatmulKernel (kernels_interface.h:9-10; cuda/matmul_kernel.cu:89-109,
  * cpu/matmul_kernel.cpp:5-41): y[K] = (W[K,M] . x[M]) * scale.
  * (The reference CUDA path ignores `scale`, the CPU path honours it; honoured here.) */
+/* y[t][0 .. M) = w16[M][K] . x[t][0 .. K) for t < T on the bf16 matrix cores, fp32-accurate (csrc/kh_gemm_w16.h: the
+ * K loop of KH_FLAG_GEMM16 under its STORE epilogue): w16 holds bf16 bits, row-major; every x splits exactly into
+ * three bf16 terms, products are exact, accumulation is fp32.  y has row stride ldy >= M.  M % 16 == 0, K % 32 == 0 and
+ * T <= 512, else KH_ERR_UNSUPPORTED; 16-byte aligned pointers, ldy % 4 == 0.  Allocates a staging copy of x and
+ * synchronises the stream. */
+int kh_gemm_w16_f32(const float* x, const uint16_t* w16, float* y, int32_t T, int32_t M, int32_t K, int32_t ldy,
+                    void* stream);
 int kh_matmul_f32(const float* x, const float* w, float* y, int32_t M, int32_t K, float scale,
                   void* stream);
 
@@ -297,7 +304,8 @@ typedef struct kh_model_opts {
  * of the pass mask: by default ffn13 and w2, the two that gain on every measured geometry; hook KH_W16_PASS at
  * creation: 0 none (the passes stream fp32), 0x1f all five, any other number a mask of the class bits below, 1 or
  * unset the default.  Still reading the fp32 image whatever the masks say: the MFMA GEMM prefill
- * (kh_model_prefill_gemm, long prompts of kh_model_generate without KH_FLAG_PREFILL_EXACT), the operator level, the
+ * (kh_model_prefill_gemm, long prompts of kh_model_generate without KH_FLAG_PREFILL_EXACT; KH_FLAG_GEMM16 below puts its
+ * GEMMs on the copy), the operator level, the
  * exact re-score of the screened greedy tails and the embedding gather.  Nothing is ever rounded: if one matrix word
  * of the image has a non-zero low half the copy is freed and the model behaves as if the flag were not set; likewise
  * on int8 images.  Hook KH_W16=1 / 0 at creation overrides the flag.  kh_model_w16_info reports. */
@@ -323,6 +331,18 @@ typedef struct kh_model_opts {
  * does nothing either).  Hooks at creation: KH_Q4=1 / 0 overrides the flag, KH_Q4_CLASSES=<mask> the adopted
  * classes.  kh_model_q4_info reports. */
 #define KH_FLAG_Q4 64
+/* GEMM16: the GEMM pass of a W16 model on the bf16 matrix cores, fp32-accurate (csrc/kh_gemm_w16.h).  Takes effect only
+ * where the model holds a live 16-bit copy in bf16 format (KH_FLAG_W16, or KH_FLAG_W16_F16 on a bf16-exact image) and
+ * the GEMM prefill runs on its geometry.  The GEMMs of kh_model_prefill_gemm (and the default prompt path of
+ * kh_model_generate), kh_model_seq_prefill_gemm, kh_model_seq_step_gemm and kh_model_generate_batch_gemm then read the
+ * bf16 weights of the copy and split every fp32 activation exactly into three bf16 terms (hi + mid + lo == x), so three
+ * v_mfma_f32_16x16x32_bf16 per 32 columns accumulate the fp32 dot product in fp32: kh_model_prefill_gemm's contract
+ * (fp32 round-off from another summation order), not the bits of the fp32 kernels.  Per launch class (1 qkv, 2 wo,
+ * 4 ffn13, 8 w2, 16 cls): a class whose contraction length is no multiple of 32, or that the adoption mask leaves out
+ * (kh_plan_gemm16; hook KH_GEMM16_CLASSES=<mask> at creation), keeps its fp32 kernel.  Inert - the launches and bits of
+ * the same model without the flag - on an fp16-format copy, an int8 model, an image that is not bf16-exact, and without
+ * a W16 flag.  Hook KH_GEMM16=1 / 0 at creation overrides the flag.  kh_model_gemm16_info reports. */
+#define KH_FLAG_GEMM16 128
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -394,6 +414,12 @@ int kh_model_w16_info(kh_model* m, int64_t* out8);
  * its build time in us, bit mask of the launch classes that run on it (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), index of
  * the first inexact tensor (7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: wcls; -1 none); slots 5 - 7 are 0. */
 int kh_model_q4_info(kh_model* m, int64_t* out8);
+/* GEMM16 (KH_FLAG_GEMM16): out[8] = state (1: some class of the GEMM pass runs on the bf16 matrix cores, 0: inert), bit
+ * mask of those classes (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), the reason where inert (0 none, 1 flag not set, 2 no W16
+ * flag, 3 int8 model, 4 image not bf16-exact, 5 the copy is in fp16 format, 6 geometry off the GEMM prefill or the W16
+ * view, 7 no class left by the mask and the K % 32 rule, 8 the copy's creation-time self-check failed), kh_plan_gemm16's
+ * mask for the geometry (0 where inert before the plan); slots 4 - 7 are 0. */
+int kh_model_gemm16_info(kh_model* m, int64_t* out8);
 /* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
  * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave
  * every row.  out4 = screened token, full classifier's token, candidate rows re-scored, 1 if the step overflowed.
@@ -916,6 +942,10 @@ int kh_plan_q4(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_si
  * out8 = {time splits per head, splits per KV group (0: no group path), workspace slot stride, first pos + 1 of the
  * group path, path taken at `pos` (0 per-head, 1 group), active splits at `pos`, timesteps per split at `pos`,
  * workgroups that own timesteps at `pos`} (KH_ATTN_TLONG, KH_ATTN_TS and KH_ATTN_WG honoured). */
+/* kh_plan_gemm16: out2 = {bit mask of the launch classes whose GEMMs of the GEMM pass run on the bf16 matrix cores under
+ * KH_FLAG_GEMM16 for this geometry (0: int8, or dims the GEMM prefill does not take): the adoption mask among the
+ * classes whose contraction length (dim; w2: hidden_dim) is a multiple of 32, columns of a K block (32)}. */
+int kh_plan_gemm16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t is_quant, int64_t* out2);
 int kh_plan_attention(int32_t head_num, int32_t kv_mul, int32_t head_size, int32_t seq_len, int32_t pos,
                       int32_t* out8);
 /* kh_plan_attention_launch: ONE decode-attention launch over the tokens at positions pos[0 .. n) of that geometry (a

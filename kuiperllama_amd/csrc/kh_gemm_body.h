@@ -1,7 +1,9 @@
 // kh_gemm_body.h — the statements of the GEMM kernel of kh_gemm.h, included INSIDE a kernel definition (no include
 // guard): ONE text for k_pg_gemm (kh_gemm.h: tokens of a run of consecutive positions) and k_sg_gemm (kh_seq_gemm.h:
-// lanes of different sequences).  The including kernel is a template <bool QUANT, int R, int NT, int EPI> and has in
-// scope
+// lanes of different sequences).  The including kernel is a template <bool QUANT, int R, int NT, int EPI> - or <int R, int NT,
+// EPI> with QUANT a constant - and has in scope
+//   constexpr bool KH_GEMM_W16   the K loop: false - pg_kloop_f32 / pg_kloop_q8 on the image; true - pg_kloop_w16
+//                           (kh_gemm_w16.h) on the 16-bit copy
 //   const KhPgGemmArgs a    its first kernel argument
 //   addr                    the token addressing of the QKV epilogue: addr.pos(tok) = the RoPE row, addr.row(tok) = the
 //                           cache row of token tok (PgRunAddr, SgLaneAddr)
@@ -49,7 +51,23 @@
   // (the K range depends on the wave index only: keep it in scalar registers so the block guards
   // of the K loop are scalar branches)
   PgBAddr B;
-  if (!QUANT) {
+  if constexpr (KH_GEMM_W16) {
+    // the 16-bit copy on the bf16 matrix cores (kh_gemm_w16.h): blocks of 32 columns; the activation slabs are the fp32
+    // loops' - the lane's eight columns 32b + 8h .. are half h & 1 of the tiled slab's 16-column block 2b + (h >> 1)
+    const int nb = K >> 5;
+    const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);
+    const int b0 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)kpart * (z1 - z0) / ks));
+    const int b1 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)(kpart + 1) * (z1 - z0) / ks));
+    const uint16_t* wrow[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) wrow[r] = (const uint16_t*)W.w + (size_t)(wr0 + rstep * r + i) * K + 8 * h;
+    if (a.b_tiled) {
+      B = PgBAddr{a.B + ((size_t)(h >> 1) * a.tcap + (size_t)(tok0 + i)) * 16 + 8 * (h & 1), 256, (size_t)a.tcap * 32, 0};
+    } else {
+      B = PgBAddr{a.B + (size_t)(tok0 + i) * K + 8 * h, (size_t)16 * K, 32, 0};
+    }
+    if (b1 > b0) pg_kloop_w16<R, NT>(wrow, B, b0, b1, acc);
+  } else if (!QUANT) {
     const int nb = K >> 4;
     const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);
     const int b0 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)kpart * (z1 - z0) / ks));

@@ -3,8 +3,9 @@
 // prompt prefill (kh_model_prefill_gemm: a run of positions), the prefill into sequence slots (kh_seq_prefill.h: a
 // tile table; kh_model_seq.hip checks the call and drives it) and the wide sequence pass (kh_seq_gemm.h: a lane table
 // at full depth; what kh_model_seq_step_gemm and kh_model_generate_batch_gemm enqueue) - with their slabs, the launch
-// plan of one GEMM (pg_shape, pg_plan) and the operator-level entry of the MFMA slice attention.  Always reads fp32
-// or int8 weights, never the 16-bit copy.  The reference feeds the prompt one token per forward pass
+// plan of one GEMM (pg_shape, pg_plan) and the operator-level entry of the MFMA slice attention.  Reads fp32 or int8
+// weights - and, under KH_FLAG_GEMM16, the 16-bit copy on the bf16 matrix cores (pg_gemm; the kernels are compiled in
+// kh_model_gemm_w16.hip).  The reference feeds the prompt one token per forward pass
 // (demo/main.cpp:20-22) and decodes one sequence per process (demo/main.cpp:16-50).
 // gfx950 only.
 #include <stdio.h>
@@ -125,7 +126,12 @@ struct PgShape {
 // hooks read per call (kh_debug_set takes effect on the next launch plan)
 inline bool pg_solo_on() { return !dbg_off("KH_PG_SOLO"); }
 inline bool pg_kz_on() { return !dbg_off("KH_PG_KZ"); }
-PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant, bool allow_kz) {
+//   * the loop on the 16-bit copy (kh_gemm_w16.h; allow_solo = false) spends VALU time on the activation split between
+//     its MFMAs, so - like int8 - it gains from a partner wave on the SIMD and `solo` only costs: 512-token prefill with
+//     KH_PG_SOLO=0 against the default, Llama-3.2-1B 6.14 vs 6.32 ms, Llama-2-7B 39.4 vs 41.1 ms, Qwen2.5-0.5B 4.82 vs
+//     6.29 ms (profiles/gemm16_shape_sweep.txt).  Everything else of the model is the fp32 fit, unchanged.
+PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant, bool allow_kz,
+                 bool allow_solo = true) {
   const int nt_all = (T + 15) / 16;
   const bool wide = nt_all > 8;  // a pass of more than 128 tokens
   PgShape best{1, 4, 1, (nt_all + 3) / 4, false, 1};
@@ -158,7 +164,7 @@ PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min
       cost *= 1.0 + (quant ? 0.15 : 0.05) * (double)(slices - 1);
       cost *= (double)(slices * NT) / (double)nt_all;
       bool solo = false;
-      if (!quant && (wide || R * NT >= 16) && pg_solo_on() && wgs > 256) {
+      if (allow_solo && !quant && (wide || R * NT >= 16) && pg_solo_on() && wgs > 256) {
         const long wg_wps = (nm * ks + 3) / 4;
         const double c1 = per_wave * (double)(((wgs + 255) / 256) * wg_wps) * (wg_wps <= 1 ? 1.0 : (wg_wps == 2 ? 1.6 : 1.8));
         if (c1 < per_wave * (double)(wps * rounds) * pen) {
@@ -174,7 +180,8 @@ PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min
   }
   return best;
 }
-bool pg_lds_opt_in(const void* kern, size_t lds) {
+}  // namespace
+bool khm::pg_lds_opt_in(const void* kern, size_t lds) {
   if (lds > 48 * 1024) {
     // the >48 KiB dynamic-LDS opt-in is per (device, kernel): set once, not on every launch of
     // the prefill hot path; a refusal is reported here, not as a generic launch error later
@@ -194,13 +201,17 @@ bool pg_lds_opt_in(const void* kern, size_t lds) {
   }
   return true;
 }
+namespace {
 // The launch shape of one GEMM of a pass: the cost model, the KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE> hook, KH_PG_DEBUG.
 // epi: KH_PG_*; STORE (the classifier GEMM of the wide sequence pass) plans as a residual GEMM without a K split
 // across workgroups.
-PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K) {
+// kcols: the columns of a K block of the loop that runs - 16 fp32, 64 int8, 32 on the 16-bit copy (kh_gemm_w16.h)
+PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K, int kcols) {
   const bool q = m->cfg.is_quant;
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
-  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / (q ? 64 : 16), q ? 4 : 16, q, EPI == KH_PG_RESID);
+  const bool w16 = kcols == 32;
+  // (min_blocks: the same 256 columns per wave as fp32's 16 blocks of 16)
+  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / kcols, q ? 4 : (w16 ? 8 : 16), q, EPI == KH_PG_RESID, !w16);
   {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE>="R,NT,ks[,kz]" overrides the heuristic
     static const char* const names[4] = {"KH_PG_SHAPE_QKV", "KH_PG_SHAPE_RESID", "KH_PG_SHAPE_SWIGLU",
                                          "KH_PG_SHAPE_STORE"};
@@ -213,7 +224,8 @@ PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, i
       {
         const int slices = ((T + 15) / 16 + NT - 1) / NT;
         sh = PgShape{R, NT, ks, slices,
-                     !q && (T > 128 || R * NT >= 16) && pg_solo_on() && (long)(rows_total / (16 * R)) * slices * kz > 256, kz};
+                     !q && !w16 && (T > 128 || R * NT >= 16) && pg_solo_on() &&
+                         (long)(rows_total / (16 * R)) * slices * kz > 256, kz};
       } else {
         // not a launch this GEMM has (e.g. R = 2 where 32 rows do not divide the matrices): say so rather than
         // let a test believe it forced a shape
@@ -288,10 +300,18 @@ inline int pg_lane_groups(const PgPass& p) { return (p.n + KH_PF_BMAX - 1) / KH_
 // One GEMM of a pass in its planned shape.  Returns, QKV: whether the epilogue rotates q / k itself (else the pass's
 // rope kernel has to follow); RESID: the number of K slices whose partial rows the next RMSNorm has to add (0 = the
 // epilogue added itself).  ok: cleared where the LDS opt-in of the shape is refused - that launch is skipped.
+// on16: the GEMM's launch class (KH_W16_*) and its matrices in the 16-bit copy.  Where the class runs on the bf16 matrix
+// cores (KH_FLAG_GEMM16: gemm16_runs) the same shape - planned in blocks of 32 columns - launches the _w16 stem
+// (kh_gemm_w16.h, compiled in kh_model_gemm_w16.hip) with the weight pointers swapped; everything else is untouched.
+struct PgOn16 {
+  int cls;
+  const void* w[3];
+};
 template <int EPI>
-int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmArgs a, bool* ok) {
+int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmArgs a, bool* ok, const PgOn16& on16) {
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
-  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K);
+  const bool w16 = gemm16_runs(m, on16.cls);
+  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K, w16 ? 32 : (m->cfg.is_quant ? 64 : 16));
   if (p.lanes && sh.NT > 4) {  // a hook asked for the 128-token tile
     sh.NT = 4;
     sh.slices = ((a.T + 15) / 16 + 3) / 4;
@@ -305,24 +325,32 @@ int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmAr
   auto opt_in = [&](auto kern, dim3&) { return pg_lds_opt_in((const void*)kern, lds); };
   const int tile = pg_tile(sh.R, sh.NT);  // one that is not listed runs as (2,2) where R is 2, else as (1,4)
   bool launched = false;
-  kh_pick_bool(m->cfg.is_quant, [&](auto Q) {
-    kh_pick(KhVals<0, 1, 2, 3>{}, tile >= 0 ? tile : (sh.R == 2 ? 2 : 3), [&](auto I) {
-      constexpr int R = kPgTiles[I][0], NT = kPgTiles[I][1];
-      if (p.lanes) {
-        if constexpr (NT <= 4)  // clamped above
-          launched = kh_launch_prep(opt_in, KH_KERNEL(k_sg_gemm, Q, R, NT, EPI), grid, wg, lds, m->stream, a, *p.lanes);
-        return;
-      }
-      if constexpr (EPI == KH_PG_QKV) {  // the other GEMMs do not care where a token sits
-        if (p.tiles) {
-          launched = kh_launch_prep(opt_in, KH_KERNEL(k_rg_gemm, Q, R, NT, EPI), grid, wg, lds, m->stream, a, *p.tiles);
+  if (w16) {
+    for (int j = 0; j < 3; ++j)
+      if (on16.w[j]) a.w[j].w = on16.w[j];
+    const int t = tile >= 0 ? tile : (sh.R == 2 ? 2 : 3);
+    launched = pg_gemm_w16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
+                                  p.lanes);
+  } else {
+    kh_pick_bool(m->cfg.is_quant, [&](auto Q) {
+      kh_pick(KhVals<0, 1, 2, 3>{}, tile >= 0 ? tile : (sh.R == 2 ? 2 : 3), [&](auto I) {
+        constexpr int R = kPgTiles[I][0], NT = kPgTiles[I][1];
+        if (p.lanes) {
+          if constexpr (NT <= 4)  // clamped above
+            launched = kh_launch_prep(opt_in, KH_KERNEL(k_sg_gemm, Q, R, NT, EPI), grid, wg, lds, m->stream, a, *p.lanes);
           return;
         }
-      }
-      if constexpr (EPI != KH_PG_STORE)  // the classifier epilogue is the lanes' alone
-        launched = kh_launch_prep(opt_in, KH_KERNEL(k_pg_gemm, Q, R, NT, EPI), grid, wg, lds, m->stream, a);
+        if constexpr (EPI == KH_PG_QKV) {  // the other GEMMs do not care where a token sits
+          if (p.tiles) {
+            launched = kh_launch_prep(opt_in, KH_KERNEL(k_rg_gemm, Q, R, NT, EPI), grid, wg, lds, m->stream, a, *p.tiles);
+            return;
+          }
+        }
+        if constexpr (EPI != KH_PG_STORE)  // the classifier epilogue is the lanes' alone
+          launched = kh_launch_prep(opt_in, KH_KERNEL(k_pg_gemm, Q, R, NT, EPI), grid, wg, lds, m->stream, a);
+      });
     });
-  });
+  }
   if (!launched) *ok = false;
   if (EPI == KH_PG_RESID) return sh.kz > 1 ? sh.kz : 0;
   return EPI == KH_PG_QKV && a.rope != KH_PG_ROPE_OFF;
@@ -372,6 +400,7 @@ bool launch_pg_pass(kh_model* m, const PgPass& p) {
   const bool rope_fuse_env = !dbg_off("KH_PG_ROPE_FUSE");
   for (int l = 0; l < c.layer_num; ++l) {
     const LayerW& W = m->layers[l];
+    const kh_model::WCopy::Layer C = m->w16.arena ? m->w16.layers[(size_t)l] : kh_model::WCopy::Layer{};  // (KH_FLAG_GEMM16)
     float* kc = m->kcache + (size_t)l * c.cache_len * c.kv_dim;
     float* vc = m->vcache + (size_t)l * c.cache_len * c.kv_dim;
     rmsnorm(W.att_norm);
@@ -386,7 +415,8 @@ bool launch_pg_pass(kh_model* m, const PgPass& p) {
       a.rope = !rope_fuse_env ? KH_PG_ROPE_OFF
                : (c.rope_mode == KH_ROPE_HALF ? (c.head_size % 32 == 0 ? KH_PG_ROPE_TILES : KH_PG_ROPE_OFF)
                                               : KH_PG_ROPE_PAIRS);
-      rope_fused = pg_gemm<KH_PG_QKV>(m, p, c.dim + 2 * c.kv_dim, c.dim % 32 == 0 && c.kv_dim % 32 == 0, a, &ok) != 0;
+      rope_fused = pg_gemm<KH_PG_QKV>(m, p, c.dim + 2 * c.kv_dim, c.dim % 32 == 0 && c.kv_dim % 32 == 0, a, &ok,
+                                          PgOn16{KH_W16_QKV, {C.wq, C.wk, C.wv}}) != 0;
     }
     if (!rope_fused && p.lanes) {
       launch_log("k_sg_rope");
@@ -433,25 +463,25 @@ bool launch_pg_pass(kh_model* m, const PgPass& p) {
       // the decode kernels leave row-major rows
       KhPgGemmArgs a = gemm_args(m->pg_att, mfma_attn ? 1 : 0, m->pg_x, c.dim, c.dim, c.dim);
       a.w[0] = W.wo; a.part = m->pg_part;
-      pending_kz = pg_gemm<KH_PG_RESID>(m, p, c.dim, c.dim % 32 == 0, a, &ok);
+      pending_kz = pg_gemm<KH_PG_RESID>(m, p, c.dim, c.dim % 32 == 0, a, &ok, PgOn16{KH_W16_WO, {C.wo}});
     }
     rmsnorm(W.ffn_norm);
     {
       KhPgGemmArgs a = gemm_args(m->pg_xn, 1, m->pg_h, c.hidden_dim, c.hidden_dim, c.dim);
       a.w[0] = W.w1; a.w[1] = W.w3;
-      pg_gemm<KH_PG_SWIGLU>(m, p, c.hidden_dim, c.hidden_dim % 32 == 0, a, &ok);
+      pg_gemm<KH_PG_SWIGLU>(m, p, c.hidden_dim, c.hidden_dim % 32 == 0, a, &ok, PgOn16{KH_W16_FFN13, {C.w1, C.w3}});
     }
     {
       KhPgGemmArgs a = gemm_args(m->pg_h, 1, m->pg_x, c.dim, c.dim, c.hidden_dim);
       a.w[0] = W.w2; a.part = m->pg_part;
-      pending_kz = pg_gemm<KH_PG_RESID>(m, p, c.dim, c.dim % 32 == 0, a, &ok);  // (the next RMSNorm adds them)
+      pending_kz = pg_gemm<KH_PG_RESID>(m, p, c.dim, c.dim % 32 == 0, a, &ok, PgOn16{KH_W16_W2, {C.w2}});  // (the next RMSNorm adds them)
     }
   }
   if (p.full_depth) {
     rmsnorm(m->final_norm);  // adds the last w2 GEMM's pending partials too
     KhPgGemmArgs a = gemm_args(m->pg_xn, 1, m->sg_logits, c.vocab_size, m->pf_vstride, c.dim);
     a.w[0] = m->cls;
-    pg_gemm<KH_PG_STORE>(m, p, c.vocab_size, c.vocab_size % 32 == 0, a, &ok);
+    pg_gemm<KH_PG_STORE>(m, p, c.vocab_size, c.vocab_size % 32 == 0, a, &ok, PgOn16{KH_W16_CLS, {m->w16.cls}});
   }
   return ok;
 }

@@ -1,5 +1,5 @@
 // kh_model_internal.h — state and cross-unit helpers of the model level of the C-ABI.
-// The model level is split into eleven translation units:
+// The model level is split into twelve translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
@@ -9,6 +9,7 @@
 //                         kernels on the 16-bit copy (kh_w16_pass.h)
 //   kh_model_gemm.hip     what runs on the GEMM slabs (kh_gemm.h, kh_pattn.h, kh_seq_prefill.h, kh_seq_gemm.h kernels):
 //                         the MFMA prompt prefill, its form into sequence slots and the wide sequence pass
+//   kh_model_gemm_w16.hip the same GEMMs on the bf16 matrix cores from the 16-bit copy (KH_FLAG_GEMM16; kh_gemm_w16.h kernels)
 //   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
 //                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
@@ -98,6 +99,9 @@ struct KhWoCombArgs;
 struct KhFfn13Args;
 struct KhClsArgs;
 struct KhProcParams;       // kh_logit_proc.h
+struct KhPgGemmArgs;       // kh_gemm.h
+struct KhRgTiles;          // kh_seq_prefill.h
+struct KhWideLanes;        // kh_seq_gemm.h
 struct kh_model {
   kh_config cfg{};
   kh_model_opts opts{};
@@ -330,6 +334,13 @@ struct kh_model {
     int format = 0;         // of the live copy: KH_W16_BF16 (also: no copy) or KH_W16_F16 (kh_w16.h)
     int first_inexact_f16 = -1;  // as first_inexact, for the fp16 format (-1: not tried, or every tensor passed)
     int pass_classes = 0;   // classes whose B-token pass reads the copy too (kh_w16_pass.h; hook KH_W16_PASS): a subset of classes
+    // KH_FLAG_GEMM16 / hook KH_GEMM16 (kh_gemm_w16.h): classes whose GEMMs of the GEMM pass (kh_model_gemm.hip:
+    // pg_gemm) run on the bf16 matrix cores from the copy - a live bf16-format copy, the GEMM prefill's geometry, K a
+    // multiple of 32 and the adoption mask (plan_gemm16, hook KH_GEMM16_CLASSES); 0 wherever the flag is inert, and
+    // gemm_reason says why (KH_GEMM16_*: kh_model_gemm16_info)
+    int gemm_classes = 0;
+    int gemm_reason = 0;
+    int gemm_plan = 0;      // plan_gemm16's mask for the geometry, whatever the hook says (0 unless the flag is live)
   };
   W16 w16;
   // Q4 (kh_q4.h, kh_model_q4.hip; KH_FLAG_Q4 / hook KH_Q4): the low nibbles of every int8 matrix value of a 4-bit-exact
@@ -378,6 +389,11 @@ static inline bool q4_runs(const kh_model* m, int cls) { return (m->q4.classes &
 static inline KhOn runs_on(const kh_model* m, int cls) {
   return q4_runs(m, cls) ? KH_ON_Q4 : (w16_runs(m, cls) ? KH_ON_W16 : KH_ON_IMAGE);
 }
+// the GEMM pass of the class on the bf16 matrix cores (kh_model_gemm.hip: pg_gemm)
+static inline bool gemm16_runs(const kh_model* m, int cls) { return m->w16.state == 1 && (m->w16.gemm_classes & cls) != 0; }
+// why KH_FLAG_GEMM16 does nothing on a model (kh_model_gemm16_info, slot 2); KH_GEMM16_ON: it does something
+enum { KH_GEMM16_ON = 0, KH_GEMM16_NO_FLAG = 1, KH_GEMM16_NO_W16 = 2, KH_GEMM16_QUANT = 3, KH_GEMM16_INEXACT = 4,
+       KH_GEMM16_FP16_COPY = 5, KH_GEMM16_GEOMETRY = 6, KH_GEMM16_NO_CLASS = 7, KH_GEMM16_SELFCHECK = 8 };
 // the B-token pass of the class (kh_model_prefill.hip: launch_pf_pass, pf_gemv_res, launch_pf_cls)
 static inline bool w16_pass_runs(const kh_model* m, int cls) { return (m->w16.pass_classes & cls) != 0; }
 void launch_qkv(kh_model* m, int l, KhOn on);
@@ -489,6 +505,10 @@ int cls_screen_selftest(kh_model* m, int32_t* d_flag, bool inject, int* result);
 // ---- kh_model_w16.hip -----------------------------------------------------------------------
 // Launch classes that run on the copy for a geometry (KH_W16_* bits, 0: not applicable) and the copy's bytes (host-only)
 int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, int layer_num, size_t* bytes);
+// Launch classes whose GEMM-pass GEMMs run on the bf16 matrix cores for a geometry (KH_W16_* bits; host-only): the
+// adoption mask among the classes whose contraction length is a multiple of 32; 0 for int8 and for geometries the
+// GEMM prefill does not run on
+int plan_gemm16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size);
 // the copy, once the weights are resident and ahead of the self-tests (no-op unless KH_FLAG_W16 / KH_W16=1 asks)
 int w16_create(kh_model* m);
 void w16_release(kh_model* m);  // frees the copy; no class runs on it afterwards
@@ -561,6 +581,19 @@ int seq_tail_enqueue(kh_model* m, float* logits, const KhSeqLanes& lanes, int n,
 KhAttnArgs attn_slice_args(kh_model* m, int l, const float* q, float* out, void* ws, size_t ws_tok_bytes);
 // ---- kh_model_gemm.hip ----------------------------------------------------------------------
 bool pg_supported(const kh_model* m);  // MFMA GEMM path
+// the >48 KiB dynamic-LDS opt-in of a GEMM-pass kernel, once per (device, kernel); false: refused
+bool pg_lds_opt_in(const void* kern, size_t lds);
+// ---- kh_model_gemm_w16.hip ------------------------------------------------------------------
+struct PgW16Launch {  // one GEMM of a pass as pg_gemm planned it, on the k_*_gemm_w16 kernels (kh_gemm_w16.h)
+  int epi, R, NT;     // KH_PG_*; a listed (R, NT) register tile
+  dim3 grid;
+  int wg;
+  size_t lds;
+};
+// a: the image launch's arguments with KhLin::w of every matrix pointing into the 16-bit copy.  tiles / lanes: the
+// token addressing (both null: a run).  false: the LDS opt-in was refused (nothing launched)
+bool pg_gemm_w16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemmArgs& a, const KhRgTiles* tiles,
+                        const KhWideLanes* lanes);
 // kh_model_prefill_gemm without the token record (hist_write); prefill_gemm_prepare: its slabs, made by the call
 // itself or ahead of it by whoever times it
 int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);

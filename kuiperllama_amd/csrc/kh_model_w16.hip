@@ -112,6 +112,8 @@ int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, in
 void w16_release(kh_model* m) {
   copy_release(m->w16);
   m->w16.pass_classes = 0;
+  if (m->w16.gemm_classes) m->w16.gemm_reason = KH_GEMM16_SELFCHECK;  // a live copy given up: the self-check's verdict
+  m->w16.gemm_classes = 0;
   m->w16.format = KH_W16_BF16;
 }
 
@@ -124,9 +126,54 @@ static int w16_pass_mask() {
   return (int)strtol(hook, nullptr, 0) & KH_W16_ALL;
 }
 
+// ---- KH_FLAG_GEMM16: the GEMM pass on the bf16 matrix cores (kh_gemm_w16.h) ------------------------------------
+// Classes that run their GEMMs of the GEMM pass on the copy unless KH_GEMM16_CLASSES says otherwise: 3.1e's adoption
+// rule - the class's time with the flag on lies below its flag-off time by more than the run-to-run range, at 512
+// tokens, on Llama-3.2-1B and on Llama-2-7B geometry (profiles/gemm16_ab.txt: qkv -2.4 / -8.1 %, wo -1.2 / -2.4 %,
+// ffn13 -14.3 / -13.1 %, w2 -4.9 / -6.0 % of the whole 512-token prefill; cls -3.2 % of a 64-lane batch on the 1B
+// geometry but -0.1 %, inside the range, on the 7B one: left out) - among the classes whose contraction length K is a multiple of the
+// 32-column block: qkv, wo, ffn13 and cls contract over dim, w2 over hidden_dim.
+enum { KH_GEMM16_DEFAULT = KH_W16_QKV | KH_W16_WO | KH_W16_FFN13 | KH_W16_W2 };
+static int gemm16_k32_classes(int dim, int hidden_dim) {
+  return (dim % 32 == 0 ? KH_W16_QKV | KH_W16_WO | KH_W16_FFN13 | KH_W16_CLS : 0) | (hidden_dim % 32 == 0 ? KH_W16_W2 : 0);
+}
+int plan_gemm16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size) {
+  if (quant || dim <= 0 || hidden_dim <= 0 || kv_dim <= 0 || vocab_size <= 0) return 0;
+  if (dim % 16 || hidden_dim % 16 || kv_dim % 16) return 0;  // pg_supported's granules of an fp32 model
+  return KH_GEMM16_DEFAULT & gemm16_k32_classes(dim, hidden_dim);
+}
+// Read at creation, behind the copy's build.  Hooks: KH_GEMM16=1 / 0 overrides the flag; KH_GEMM16_CLASSES=<number>
+// (strtol, base 0) replaces the adoption mask - the K % 32 rule still holds.
+static void gemm16_configure(kh_model* m, bool w16_wanted) {
+  const kh_config& c = m->cfg;
+  kh_model::W16& w = m->w16;
+  w.gemm_classes = w.gemm_plan = 0;
+  const char* hook = dbg("KH_GEMM16");
+  const bool want = hook ? hook[0] == '1' : (m->opts.flags & KH_FLAG_GEMM16) != 0;
+  if (!want) { w.gemm_reason = KH_GEMM16_NO_FLAG; return; }
+  if (c.is_quant) { w.gemm_reason = KH_GEMM16_QUANT; return; }
+  if (!w16_wanted) { w.gemm_reason = KH_GEMM16_NO_W16; return; }
+  if (w.state != 1) { w.gemm_reason = w.state == -1 ? KH_GEMM16_INEXACT : KH_GEMM16_GEOMETRY; return; }
+  if (w.format != KH_W16_BF16) { w.gemm_reason = KH_GEMM16_FP16_COPY; return; }
+  if (!pg_supported(m)) { w.gemm_reason = KH_GEMM16_GEOMETRY; return; }
+  w.gemm_plan = plan_gemm16(false, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size);
+  int mask = w.gemm_plan;
+  if (const char* cl = dbg("KH_GEMM16_CLASSES"))
+    mask = (int)strtol(cl, nullptr, 0) & gemm16_k32_classes(c.dim, c.hidden_dim);
+  w.gemm_classes = mask & w.classes;
+  w.gemm_reason = w.gemm_classes ? KH_GEMM16_ON : KH_GEMM16_NO_CLASS;
+}
+
 // The copy in the first format the image is exact in: bf16 (KH_FLAG_W16 or KH_FLAG_W16_F16), else fp16 (only
 // KH_FLAG_W16_F16; into the same arena - plan_w16's layout holds for both), else none.  All or nothing per format.
+static int w16_create_copy(kh_model* m, bool* wanted);
 int w16_create(kh_model* m) {
+  bool wanted = false;
+  const int rc = w16_create_copy(m, &wanted);
+  if (rc == KH_OK) gemm16_configure(m, wanted);
+  return rc;
+}
+static int w16_create_copy(kh_model* m, bool* wanted) {
   const kh_config& c = m->cfg;
   kh_model::W16& w = m->w16;
   w = kh_model::W16();
@@ -134,6 +181,7 @@ int w16_create(kh_model* m) {
   const char* hook_f16 = dbg("KH_W16_F16");
   const bool try_f16 = hook_f16 ? hook_f16[0] == '1' : (m->opts.flags & KH_FLAG_W16_F16) != 0;
   const bool want = hook ? hook[0] == '1' : (m->opts.flags & KH_FLAG_W16) != 0 || try_f16;
+  *wanted = want;
   if (!want) return KH_OK;
   size_t bytes = 0;
   const int classes = plan_w16(c.is_quant != 0, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size, c.layer_num, &bytes);
@@ -208,5 +256,26 @@ extern "C" int kh_model_w16_info(kh_model* m, int64_t* out) {
   out[5] = m->w16.pass_classes;
   out[6] = m->w16.format == KH_W16_F16;
   out[7] = m->w16.first_inexact_f16 + 1;
+  return KH_OK;
+}
+
+// out2 = {KH_W16_* bits of the launch classes whose GEMM-pass GEMMs run on the bf16 matrix cores under KH_FLAG_GEMM16
+// (0: not applicable), the columns of a K block}
+extern "C" int kh_plan_gemm16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t is_quant,
+                              int64_t* out2) {
+  if (!out2 || dim <= 0 || hidden_dim <= 0 || kv_dim <= 0 || vocab_size <= 0) return KH_ERR_INVALID_ARG;
+  out2[0] = plan_gemm16(is_quant != 0, dim, hidden_dim, kv_dim, vocab_size);
+  out2[1] = 32;
+  return KH_OK;
+}
+
+extern "C" int kh_model_gemm16_info(kh_model* m, int64_t* out) {
+  if (!m || !out) return KH_ERR_INVALID_ARG;
+  memset(out, 0, 8 * sizeof(int64_t));
+  const bool on = m->w16.state == 1 && m->w16.gemm_classes != 0;
+  out[0] = on;
+  out[1] = on ? m->w16.gemm_classes : 0;
+  out[2] = on ? KH_GEMM16_ON : m->w16.gemm_reason;
+  out[3] = m->w16.gemm_plan;
   return KH_OK;
 }

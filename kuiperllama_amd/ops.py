@@ -46,6 +46,20 @@ def matmul(x, w, out, scale: float = 1.0):
     return out
 
 
+def gemm_w16(x, w16, out=None):
+    """out[T, M] = x[T, K] @ w16[M, K]^T on the bf16 matrix cores, fp32-accurate (kh_gemm_w16_f32): w16 holds bf16 bits
+    (torch.bfloat16, or int16 / uint16 words); M % 16 == 0, K % 32 == 0, T <= 512."""
+    T, K = x.shape
+    M, K2 = w16.shape
+    if K2 != K or w16.element_size() != 2:
+        raise ValueError("gemm_w16: w16 must be [M, K] 16-bit words")
+    if out is None:
+        out = torch.empty((T, M), dtype=torch.float32, device=x.device)
+    _ffi.check(_ffi.lib().kh_gemm_w16_f32(_p(x, torch.float32), _p(w16), _p(out, torch.float32), T, M, K,
+                                          out.stride(0), _stream()), "kh_gemm_w16_f32")
+    return out
+
+
 def matmul_q8(x, w8, scales, group_size: int, out):
     K, M = w8.shape
     _ffi.check(_ffi.lib().kh_matmul_q8(_p(x, torch.float32), _p(w8, torch.int8),
