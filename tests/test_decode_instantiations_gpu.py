@@ -31,14 +31,15 @@ that geometry.  Per shape:
 While the steps run, the launch log (hook KH_LAUNCH_LOG) records the instantiations launched.  The coverage gates at
 the end compare it, per template, with the instantiations compiled into the library (read from its code objects):
 a new template argument fails here until it is tested, and a shape hook the plan refused shows up as a gap.
+The forced shapes, the teacher-forced step loop and the hooks are those of wcopy_cases.py, which the tests of the
+weight copies share.
 """
-import itertools
-
 import numpy as np
 import pytest
 import torch
 
 import code_objects as co
+import wcopy_cases as wc
 from kuiperllama_amd import _ffi, binfmt, build
 
 pytestmark = pytest.mark.gpu
@@ -46,18 +47,10 @@ pytestmark = pytest.mark.gpu
 LOGIT_ATOL_F32 = 2e-5  # test_model_gpu.py: LOGIT_ATOL_F32 / LOGIT_ATOL_Q8
 LOGIT_ATOL_Q8 = 5e-5
 KV_ATOL = 1e-5         # fused-path K/V bound of test_model_gpu.py::test_real_stride_deep_positions_vs_oracle
-CACHE = 1024
-DEEP_POS = 300         # 2 (head size 64) or 3 (128) attention time splits: k_wo_comb merges them where it can
+CACHE, DEEP_POS = wc.CACHE, wc.DEEP_POS  # 1024 rows; the deep step is at position 300
+L, Q2, HALF, INTER = wc.L, wc.Q2, wc.HALF, wc.INTER
+_spec = wc.spec
 
-
-def _spec(dim, hidden, heads, kv_heads, vocab, quant, group, rope, family, name):
-    theta = 1000000.0 if family == binfmt.FAMILY_QWEN2 else 10000.0
-    return binfmt.ModelSpec(dim, hidden, 2, heads, kv_heads, vocab, CACHE, False, family, quant, group, rope, theta,
-                            1e-6 if family == binfmt.FAMILY_QWEN2 else 1e-5, name)
-
-
-L, Q2 = binfmt.FAMILY_LLAMA, binfmt.FAMILY_QWEN2
-HALF, INTER = binfmt.ROPE_HALF, binfmt.ROPE_INTERLEAVED
 GEOMETRIES = {
     # fp32
     "f32-1152-h10368": _spec(1152, 10368, 18, 6, 1001, False, 64, HALF, L, "f32-1152"),       # hs 64, GQA 3:1
@@ -82,48 +75,10 @@ UNREACHABLE = {}
 _LAUNCHED = {}  # geometry -> instantiations its shapes launched (filled by test_geometry, read by the gates)
 
 
-def _pairs(spec):
-    """Work items (row pairs; ffn13: rows of w1/w3) of qkv, wo, ffn13, w2, cls: pick_shape's `pairs`."""
-    return {"QKV": (spec.dim + 2 * spec.kv_dim) // 2, "WO": spec.dim // 2, "FFN": spec.hidden_dim,
-            "W2": spec.dim // 2, "CLS": (spec.vocab_size + 1) // 2}
-
-
 def _shapes(spec):
-    """Forced shapes of one geometry: a list of {hook suffix: (split, u, grid, wg)}.  For each workgroup width, nine
-    shapes walk every (u, split) each kernel accepts (qkv: split <= 2, ffn13 / cls: 1, int8 w2 also u = 3).  Grid:
-    one pair per wave, at most 1024 workgroups.  Then two copies with only the grids changed, and for int8 one shape
-    without the ffn13 / cls hooks (the ring kernels take those launches)."""
-    us = (2, 4) if spec.quant else (2, 4, 8)
-    combos = {"QKV": list(itertools.product(us, (1, 2))), "WO": list(itertools.product(us, (1, 2, 4))),
-              "FFN": list(itertools.product(us, (1,))), "CLS": list(itertools.product(us, (1,))),
-              "W2": list(itertools.product((2, 3, 4) if spec.quant else us, (1, 2, 4)))}
-    pairs = _pairs(spec)
-    out = []
-    for wg in (256, 512):
-        for i in range(9):
-            sh = {}
-            for k, c in combos.items():
-                u, sp = c[i % len(c)]
-                ppw = (wg // 64) // sp
-                sh[k] = (sp, u, min(1024, -(-pairs[k] // ppw)), wg)
-            out.append(sh)
-    for base, grids in ((0, (3, 5, 2, 7, 1)), (13, (7, 61, 3, 13, 5))):
-        out.append({k: (s[0], s[1], g, s[3]) for (k, s), g in zip(out[base].items(), grids)})
-    if spec.quant:
-        out.append({k: v for k, v in out[4].items() if k not in ("FFN", "CLS")})
-    return out
-
-
-def _steps(spec, rng):
-    toks = [int(t) for t in rng.integers(0, spec.vocab_size, 4)]
-    return list(zip(toks, (0, 1, 2, DEEP_POS)))
-
-
-def _deep_rows(spec, rng):
-    kr = rng.standard_normal((spec.n_layers, DEEP_POS, spec.kv_dim), dtype=np.float32)
-    vr = rng.standard_normal((spec.n_layers, DEEP_POS, spec.kv_dim), dtype=np.float32)
-    kr[:, rng.integers(0, DEEP_POS, 8)] *= 6.0  # a few dominant keys: the splits' maxima differ
-    return kr, vr
+    """wcopy_cases.decode_shapes with a second odd-grid shape of its own and, for int8, the shape that leaves the
+    ffn13 / cls launches to the ring kernels"""
+    return wc.decode_shapes(spec, second_odd_grids=(7, 61, 3, 13, 5), ring_shape=spec.quant)
 
 
 def _gold(oracle, img_h, spec, steps, rows):
@@ -146,88 +101,70 @@ def _gold(oracle, img_h, spec, steps, rows):
     return out
 
 
-def _set_shape_hooks(sh):
-    for k in ("QKV", "WO", "FFN", "W2", "CLS"):
-        _ffi.debug_set(f"KH_SHAPE_{k}", ",".join(map(str, sh[k])) if k in sh else None)
-
-
-def _run_shape(m, spec, steps, rows, gold, floor, what):
-    """The teacher-forced steps on model m; checks against the gold, returns (logits, K rows, V rows) per step."""
-    nan = np.full((1, spec.kv_dim), np.nan, np.float32)
-    res = []
-    for (tok, pos), (lg, lo, kg, vg) in zip(steps, gold):
-        if pos == DEEP_POS:
-            for layer in range(spec.n_layers):
-                m.write_kv(layer, 0, rows[0][layer], rows[1][layer])
-        for layer in range(spec.n_layers):
-            m.write_kv(layer, pos, nan, nan)
-        nxt = m.predict(tok, pos, exec="fused")
-        got = m.logits()
+def _check_step(gold, floor, what):
+    """run_steps' check of one step against the gold: logits, the argmax where the gold's margin allows, K/V rows"""
+    def check(i, tok, pos, nxt, got, ks, vs):
+        lg, lo, kg, vg = gold[i]
         err = float(np.abs(got - lg).max())
         lim = max(floor, 3.0 * float(np.abs(lo - lg).max()))
         assert err <= lim, f"{what} pos {pos}: |logit - gold| {err:.3e} > {lim:.3e}"
         top2 = np.sort(lg)[-2:]
         if top2[1] - top2[0] > 2 * floor:
             assert nxt == int(np.argmax(lg)), f"{what} pos {pos}: argmax {nxt} vs gold {int(np.argmax(lg))}"
-        ks, vs = [], []
-        for layer in range(spec.n_layers):
-            k, v = m.read_kv(layer, pos, 1)
-            for name, a, b in (("K", k[0], kg[layer]), ("V", v[0], vg[layer])):
+        for layer in range(len(ks)):
+            for name, a, b in (("K", ks[layer], kg[layer]), ("V", vs[layer], vg[layer])):
                 e = np.abs(a - b)
                 assert np.all(e <= KV_ATOL), \
                     f"{what} pos {pos} layer {layer}: {name} row off by {np.nanmax(e) if np.isfinite(e).any() else e}" \
                     f" ({int(np.isnan(a).sum())} NaN)"
-            ks.append(k[0])
-            vs.append(v[0])
-        res.append((got, np.stack(ks), np.stack(vs)))
-    return res
+    return check
 
 
 @pytest.mark.parametrize("name", list(GEOMETRIES))
 def test_geometry(gpu, oracle, name):
     """All forced shapes of one geometry against its fp64 gold (module docstring), launch log recorded."""
-    from kuiperllama_amd.model import KuiperModel
     spec = GEOMETRIES[name]
     floor = LOGIT_ATOL_Q8 if spec.quant else LOGIT_ATOL_F32
     img_d = binfmt.synth_image(spec, seed=4242, device=gpu, final_norm_std=1.0)
     torch.cuda.synchronize()
     img_h = img_d.cpu().numpy()
     rng = np.random.default_rng(7)
-    steps = _steps(spec, rng)
-    rows = _deep_rows(spec, rng)
+    steps = wc.steps(spec, rng)
+    rows = wc.deep_rows(spec, rng)
     gold = _gold(oracle, img_h, spec, steps, rows)
+    shapes = _shapes(spec)
     launched = set()
     by_shape = {}  # (split, u, wg) of the five kernels -> results: grid invariance
     n_prefill = 0
     try:
-        for i, sh in enumerate(_shapes(spec)):
+        for i, sh in enumerate(shapes):
             what = f"{name} shape {i} {sh}"
-            _set_shape_hooks(sh)
-            m = KuiperModel.from_device_image(img_d, spec)
+            wc.set_shape_hooks(sh)
+            m = wc.model(img_d, spec)
             try:
-                _ffi.debug_set("KH_LAUNCH_LOG", "1")  # after creation: its self-tests are not checked launches
-                res = _run_shape(m, spec, steps, rows, gold, floor, what)
-                key = tuple((k, s[0], s[1], s[3]) for k, s in sorted(sh.items()))
-                if key in by_shape:
-                    for (la, ka, va), (lb, kb, vb) in zip(by_shape[key], res):
-                        assert np.array_equal(la, lb), f"{what}: logits depend on the grid"
-                        assert np.array_equal(ka, kb) and np.array_equal(va, vb), f"{what}: K/V depend on the grid"
-                by_shape.setdefault(key, res)
-                # B-token prefill of the three first tokens: the K/V rows of the token-by-token steps, bit for bit
-                toks = [t for t, _ in steps[:3]]
-                try:
-                    m.prefill(toks, 0)
-                except _ffi.KhError as e:
-                    assert e.code == -2, e  # KH_ERR_UNSUPPORTED: the shape is outside prefill_supported
-                else:
-                    n_prefill += 1
-                    for layer in range(spec.n_layers):
-                        k, v = m.read_kv(layer, 0, 3)
-                        kt = np.stack([r[1][layer] for r in res[:3]])
-                        vt = np.stack([r[2][layer] for r in res[:3]])
-                        assert np.array_equal(k, kt) and np.array_equal(v, vt), f"{what}: prefill K/V, layer {layer}"
-                launched |= _ffi.launch_log()
-                _ffi.debug_set("KH_LAUNCH_LOG", None)
+                with wc.launch_log() as read:  # after creation: its self-tests are not checked launches
+                    res = wc.run_steps(m, spec, steps, rows, _check_step(gold, floor, what))  # raw words
+                    key = tuple((k, s[0], s[1], s[3]) for k, s in sorted(sh.items()))
+                    if key in by_shape:
+                        for (la, ka, va, _), (lb, kb, vb, _) in zip(by_shape[key], res):
+                            assert np.array_equal(la, lb), f"{what}: logits depend on the grid"
+                            assert np.array_equal(ka, kb) and np.array_equal(va, vb), f"{what}: K/V depend on the grid"
+                    by_shape.setdefault(key, res)
+                    # B-token prefill of the three first tokens: the K/V rows of the token-by-token steps, bit for bit
+                    toks = [t for t, _ in steps[:3]]
+                    try:
+                        m.prefill(toks, 0)
+                    except _ffi.KhError as e:
+                        assert e.code == _ffi.KH_ERR_UNSUPPORTED, e  # the shape is outside prefill_supported
+                    else:
+                        n_prefill += 1
+                        for layer in range(spec.n_layers):
+                            k, v = m.read_kv(layer, 0, 3)
+                            kt = np.stack([r[1][layer] for r in res[:3]])
+                            vt = np.stack([r[2][layer] for r in res[:3]])
+                            assert np.array_equal(k.view(np.uint32), kt) and np.array_equal(v.view(np.uint32), vt), \
+                                f"{what}: prefill K/V, layer {layer}"
+                    launched |= read()
                 if i in (0, 13):
                     prompt = [t for t, _ in steps[:2]]
                     ga, _ = m.generate(prompt, 10, exec="graph")
@@ -236,11 +173,10 @@ def test_geometry(gpu, oracle, name):
             finally:
                 m.close()
     finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
-        _set_shape_hooks({})
+        wc.set_shape_hooks({})
     assert n_prefill > 0, f"{name}: no shape ran the B-token prefill"
     _LAUNCHED[name] = launched
-    print(f"{name}: {len(_shapes(spec))} shapes, {len(launched)} instantiations launched, {n_prefill} prefills")
+    print(f"{name}: {len(shapes)} shapes, {len(launched)} instantiations launched, {n_prefill} prefills")
 
 
 @pytest.fixture(scope="module")

@@ -10,10 +10,11 @@ import numpy as np
 import torch
 
 import code_objects as co
+import wcopy_cases as wc
 from kuiperllama_amd import _ffi, binfmt, build
 
 TINY = dict(dim=64, hidden_dim=128, n_layers=2, n_heads=4, n_kv_heads=2, vocab_size=37, seq_len=16)
-MATS = ("wq", "wk", "wv", "wo", "w1", "w2", "w3")
+MATS = wc.MATRICES
 
 
 def _spec(group=64, **kw):
@@ -151,11 +152,8 @@ def test_q4_symbols_are_in_the_abi():
     for hook in ("KH_Q4", "KH_Q4_CLASSES"):
         assert hook.startswith(_ffi._HOOK_PREFIXES)  # sync_env mirrors it from the environment
         assert _ffi.debug_get(hook) is None
-        try:
-            _ffi.debug_set(hook, "1")
+        with wc.hook(hook, "1"):
             assert _ffi.debug_get(hook) == "1"
-        finally:
-            _ffi.debug_set(hook, None)
     from kuiperllama_amd.model import KuiperModel
     assert callable(KuiperModel.q4_info)
     assert "kh_model_q4.hip" in build.SOURCES and "kh_q4.h" in build.HEADERS
@@ -175,11 +173,13 @@ def test_q4_kernels_in_the_code_objects():
         "k_ffn13": {f"k_ffn13<{q},{u},{mv}>" for q, us in Q for u in us for mv in (4, 2, 1, 0)},
         "k_cls": {f"k_cls<{q},{u},{mv}>" for q, us in Q for u in us for mv in (4, 2, 1, 0)},
     }
+    assert set(base) == wc.DECODE_F32
     counts = {"k_qkv": 16, "k_gemv_res": 45, "k_wo_comb": 12, "k_ffn13": 8, "k_cls": 8}
     total = 0
     for stem, want in base.items():
         assert co.instantiations(notes, {stem}) == want, stem  # fp32 and int8: unchanged
         for q, twin in (("true", "_q4"), ("false", "_w16"), ("false", "_h16")):
+            assert stem + twin in wc.DECODE[twin[1:]]
             w = {k.replace(f"{stem}<{q},", f"{stem}{twin}<") for k in want if k.startswith(f"{stem}<{q},")}
             got = co.instantiations(notes, {stem + twin})
             assert got == w and got, (stem + twin, sorted(got - w), sorted(w - got))
@@ -187,10 +187,10 @@ def test_q4_kernels_in_the_code_objects():
         assert n == counts[stem], (stem, n)
         total += n
     assert total == 89
-    for ring in ("k_ffn13_ring", "k_cls_ring"):  # no ring form on the copy, the int8 one as it was
+    for ring in sorted(wc.DECODE_INT8 - wc.DECODE_F32):  # no ring form on the copy, the int8 one as it was
         assert co.instantiations(notes, {ring}) == {ring + "<2,4,false>"}
         assert not co.instantiations(notes, {ring + "_q4"})
-    stems = {s + "_q4" for s in base}
+    stems = wc.DECODE["q4"]
     scratch = {co.template_name(k): v for k, v in co.kernel_scratch(notes).items()
                if (co.template_name(k) or "").split("<")[0] in stems}
     assert len(scratch) == 89, len(scratch)

@@ -4,7 +4,8 @@ bytes, never with a tolerance.
 
 Models: 2 layers, 1024 cache rows, synth_image(seed fixed, final_norm_std=1.0) requantised to 4 bits
 (binfmt.requantize_matrices_q4).  The two models of a comparison share one device image.  Where a test is about the
-kernels, every launch class runs on the copy (hook KH_Q4_CLASSES=0x1f), whatever the default plan adopts.
+kernels, every launch class runs on the copy (hook KH_Q4_CLASSES=0x1f), whatever the default plan adopts.  Shapes, the
+step loop and the comparisons are those of wcopy_cases.py.
 
   1. state: a requantised image -> state 1, the planned bytes and classes, the launch log of a step names the _q4 kernel
      of every adopted class and neither its int8 twin nor the ring kernel (the names are derived here from the planned
@@ -25,81 +26,40 @@ kernels, every launch class runs on the copy (hook KH_Q4_CLASSES=0x1f), whatever
   6. coverage gate: every compiled instantiation of the five _q4 stems was launched by (2); a launched name exists in
      the code objects.
 """
-import contextlib
-import itertools
-
 import numpy as np
 import pytest
 import torch
 
-import code_objects as co
-from kuiperllama_amd import _ffi, binfmt, build
+import wcopy_cases as wc
+from kuiperllama_amd import _ffi, binfmt
 
 pytestmark = pytest.mark.gpu
 
-CACHE = 1024
-DEEP_POS = 300
 EXACT = _ffi.KH_FLAG_PREFILL_EXACT
-HALF, INTER = binfmt.ROPE_HALF, binfmt.ROPE_INTERLEAVED
+HALF, INTER, L = wc.HALF, wc.INTER, wc.L
 INT8_ATOL = 1e-4  # tests/test_model_gpu.py: FULL_LOGIT_ATOL_Q8
 
-
-def _spec(dim, hidden, heads, kv_heads, vocab, rope, name, group=64, quant=True):
-    return binfmt.ModelSpec(dim, hidden, 2, heads, kv_heads, vocab, CACHE, False, binfmt.FAMILY_LLAMA, quant, group,
-                            rope, 10000.0, 1e-5, name)
-
-
 GEOMETRIES = {
-    "1152-h10368": _spec(1152, 10368, 18, 6, 1001, HALF, "q4-1152"),        # 72 units; w2 depth 6 / 0, SPLIT 4
-    "4224-h3072": _spec(4224, 3072, 33, 3, 777, INTER, "q4-4224"),          # hs 128 interleaved; depth 4 / 0
-    "960-g32-hs80": _spec(960, 1600, 12, 2, 1537, HALF, "q4-g32", group=32),  # group 32, 60 units, odd vocabulary
-    "448": _spec(448, 1216, 7, 7, 999, INTER, "q4-448"),                     # 28 units: masked lanes; planted nibbles
+    "1152-h10368": wc.spec(1152, 10368, 18, 6, 1001, True, 64, HALF, L, "q4-1152"),  # 72 units; w2 depth 6 / 0, SPLIT 4
+    "4224-h3072": wc.spec(4224, 3072, 33, 3, 777, True, 64, INTER, L, "q4-4224"),    # hs 128 interleaved; depth 4 / 0
+    "960-g32-hs80": wc.spec(960, 1600, 12, 2, 1537, True, 32, HALF, L, "q4-g32"),    # group 32, 60 units, odd vocabulary
+    "448": wc.spec(448, 1216, 7, 7, 999, True, 64, INTER, L, "q4-448"),              # 28 units: masked lanes; planted
 }
 SMALL = GEOMETRIES["448"]
-STEMS = {"k_qkv_q4", "k_gemv_res_q4", "k_wo_comb_q4", "k_ffn13_q4", "k_cls_q4"}
-INT8_STEMS = {"k_qkv", "k_gemv_res", "k_wo_comb", "k_ffn13", "k_cls", "k_ffn13_ring", "k_cls_ring"}
+STEMS = wc.DECODE["q4"]
+GEMV = STEMS | wc.DECODE_INT8  # the launches a logged step keeps
 
 _LAUNCHED = {}  # geometry -> _q4 instantiations its shapes launched (test_bit_identity -> test_coverage_gate)
-
-
-def _model(img, spec, flags=0):
-    from kuiperllama_amd.model import KuiperModel
-    return KuiperModel.from_device_image(img, spec, flags=flags)
-
-
-@contextlib.contextmanager
-def _hook(key, value):
-    _ffi.debug_set(key, value)
-    try:
-        yield
-    finally:
-        _ffi.debug_set(key, None)
+_model, _hook = wc.model, wc.hook
 
 
 def _q4_model(img, spec, flags=0):
     """flag on, every class on the copy"""
-    with _hook("KH_Q4_CLASSES", "0x1f"):
-        return _model(img, spec, flags | _ffi.KH_FLAG_Q4)
+    return wc.model(img, spec, flags | _ffi.KH_FLAG_Q4, q4_classes="0x1f")
 
 
-def _plant(img, spec):
-    """-8, 7 and -1 in low (even column) and high (odd column) nibbles of the first and the last 16-column unit of the
-    first two rows and the last row of every covered tensor"""
-    pat = torch.tensor([-8, 7, -1, -8, 7, -8, -1, 7, -1, -1, 7, 7, -8, -8, 7, -1], dtype=torch.int8, device=img.device)
-    for e, _ in binfmt.q4_tensors(spec):
-        q = binfmt.tensor_from_image(img, e)
-        for r in (0, 1, e.shape[0] - 1):
-            q[r, :16] = pat
-            q[r, -16:] = pat.flip(0)
-
-
-def _requantised(spec, gpu, seed=4242, plant=False):
-    img = binfmt.synth_image(spec, seed=seed, device=gpu, final_norm_std=1.0)
-    binfmt.requantize_matrices_q4(img, spec)
-    if plant:
-        _plant(img, spec)
-    torch.cuda.synchronize()
-    return img
+def _requantised(spec, gpu, plant=False):
+    return wc.exact_image("q4", spec, gpu, plant=plant)
 
 
 @pytest.fixture(scope="module")
@@ -107,19 +67,8 @@ def small_img(gpu):
     return _requantised(SMALL, gpu)
 
 
-def _gemv_log(log):
-    return {k for k in log if k.split("<")[0] in STEMS | INT8_STEMS}
-
-
-def _logged_step(m, tok=5, pos=0):
-    """(GEMV launches, logits) of one fused step"""
-    _ffi.debug_set("KH_LAUNCH_LOG", "1")
-    try:
-        m.predict(tok, pos, exec="fused")
-        lg = m.logits()
-        return _gemv_log(_ffi.launch_log()), lg
-    finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
+def _logged_step(m):
+    return wc.logged_step(m, GEMV)
 
 
 def _plan(spec):
@@ -216,7 +165,7 @@ def test_inexact_and_fp32_images_launch_what_they_launch_today(gpu):
         assert info["state"] == -1 and info["first_inexact"] == 7 * SMALL.n_layers, info
     finally:
         m.close()
-    f32 = _spec(448, 1216, 7, 7, 999, INTER, "q4-f32", quant=False)
+    f32 = wc.spec(448, 1216, 7, 7, 999, False, 64, INTER, L, "q4-f32")
     fimg = binfmt.synth_image(f32, seed=7, device=gpu)
     torch.cuda.synchronize()
     m0, m1 = _model(fimg, f32), _q4_model(fimg, f32)
@@ -267,96 +216,36 @@ def test_hooks_override_the_flag_and_the_plan(gpu, small_img):
 
 
 # ---- 2. bit identity under forced shapes ------------------------------------------------------
-def _shapes(spec):
-    """{hook suffix: (split, u, grid, wg)}: per workgroup width nine shapes that walk every (u, split) each int8 kernel
-    accepts (qkv: split <= 2, ffn13 / cls: 1; u 3 for w2 alone), grids of one pair per wave; then two of them with
-    small odd grids."""
-    us = (2, 4)
-    combos = {"QKV": list(itertools.product(us, (1, 2))), "WO": list(itertools.product(us, (1, 2, 4))),
-              "FFN": list(itertools.product(us, (1,))), "CLS": list(itertools.product(us, (1,))),
-              "W2": list(itertools.product((2, 3, 4), (1, 2, 4)))}
-    pairs = {"QKV": (spec.dim + 2 * spec.kv_dim) // 2, "WO": spec.dim // 2, "FFN": spec.hidden_dim,
-             "W2": spec.dim // 2, "CLS": (spec.vocab_size + 1) // 2}
-    out = []
-    for wg in (256, 512):
-        for i in range(9):
-            sh = {}
-            for k, c in combos.items():
-                u, sp = c[i % len(c)]
-                sh[k] = (sp, u, min(1024, -(-pairs[k] // ((wg // 64) // sp))), wg)
-            out.append(sh)
-    for base in (0, 13):
-        out.append({k: (s[0], s[1], g, s[3]) for (k, s), g in zip(out[base].items(), (3, 5, 2, 7, 1))})
-    return out
-
-
-def _set_shape_hooks(sh):
-    for k in ("QKV", "WO", "FFN", "W2", "CLS"):
-        _ffi.debug_set(f"KH_SHAPE_{k}", ",".join(map(str, sh[k])) if k in sh else None)
-
-
-def _run_steps(m, spec, steps, rows):
-    """teacher-forced steps into NaN rows -> [(logits, K rows [layers, kv], V rows, token)], floats as raw words"""
-    nan = np.full((1, spec.kv_dim), np.nan, np.float32)
-    res = []
-    for tok, pos in steps:
-        if pos == DEEP_POS:
-            for layer in range(spec.n_layers):
-                m.write_kv(layer, 0, rows[0][layer], rows[1][layer])
-        for layer in range(spec.n_layers):
-            m.write_kv(layer, pos, nan, nan)
-        nxt = m.predict(tok, pos, exec="fused")
-        lg = m.logits()
-        kv = [m.read_kv(layer, pos, 1) for layer in range(spec.n_layers)]
-        res.append((lg.view(np.uint32), np.stack([k[0] for k, _ in kv]).view(np.uint32),
-                    np.stack([v[0] for _, v in kv]).view(np.uint32), nxt))
-    return res
-
-
 @pytest.mark.parametrize("name", list(GEOMETRIES))
 def test_bit_identity_under_forced_shapes(gpu, name):
     spec = GEOMETRIES[name]
     img = _requantised(spec, gpu, plant=spec is SMALL)
     assert binfmt.matrices_q4_exact(img, spec)
     rng = np.random.default_rng(7)
-    steps = list(zip([int(t) for t in rng.integers(0, spec.vocab_size, 4)], (0, 1, 2, DEEP_POS)))
-    rows = (rng.standard_normal((spec.n_layers, DEEP_POS, spec.kv_dim), dtype=np.float32),
-            rng.standard_normal((spec.n_layers, DEEP_POS, spec.kv_dim), dtype=np.float32))
-    rows[0][:, rng.integers(0, DEEP_POS, 8)] *= 6.0  # a few dominant keys: the splits' maxima differ
+    steps = wc.steps(spec, rng)
+    rows = wc.deep_rows(spec, rng)
+    shapes = wc.decode_shapes(spec)
     launched = set()
     try:
-        for i, sh in enumerate(_shapes(spec)):
+        for i, sh in enumerate(shapes):
             what = f"{name} shape {i} {sh}"
-            _set_shape_hooks(sh)
+            wc.set_shape_hooks(sh)
             m0, m1 = _model(img, spec), _q4_model(img, spec)
             try:
                 info = m1.q4_info()
                 assert info["state"] == 1 and info["classes"] == list(_ffi.KH_Q4_CLASSES), (what, info)
-                want = _run_steps(m0, spec, steps, rows)
-                _ffi.debug_set("KH_LAUNCH_LOG", "1")  # after creation: the self-check's launches are not compared ones
-                got = _run_steps(m1, spec, steps, rows)
-                log = _gemv_log(_ffi.launch_log())
-                _ffi.debug_set("KH_LAUNCH_LOG", None)
-                assert log and all(k.split("<")[0] in STEMS for k in log), f"{what}: int8 GEMV launched: {sorted(log)}"
-                launched |= log
-                for (tok, pos), (la, ka, va, ta), (lb, kb, vb, tb) in zip(steps, want, got):
-                    assert not np.isnan(la.view(np.float32)).any(), f"{what} pos {pos}: NaN logits"
-                    assert np.array_equal(la, lb), f"{what} pos {pos}: logits differ in {int((la != lb).sum())} words"
-                    assert np.array_equal(ka, kb) and np.array_equal(va, vb), f"{what} pos {pos}: K/V rows differ"
-                    assert ta == tb, f"{what} pos {pos}: token {ta} vs {tb}"
+                launched |= wc.compare_steps(m0, m1, spec, steps, rows, what, STEMS, GEMV)[0]
             finally:
                 m0.close()
                 m1.close()
     finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
-        _set_shape_hooks({})
+        wc.set_shape_hooks({})
     _LAUNCHED[name] = launched
-    print(f"{name}: {len(_shapes(spec))} shapes, {len(launched)} Q4 instantiations launched")
+    print(f"{name}: {len(shapes)} shapes, {len(launched)} Q4 instantiations launched")
 
 
 # ---- 3. the copy is what is read --------------------------------------------------------------
 def test_the_copy_is_what_is_read(gpu):
-    layer1 = {f"{n}.1" for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")}
     for on in (True, False):
         img = _requantised(SMALL, gpu)
         assert (img.data_ptr() + SMALL.header_bytes()) % 16 == 0  # from_device_image uses the image in place
@@ -365,10 +254,7 @@ def test_the_copy_is_what_is_read(gpu):
             t0 = m.predict(5, 0, exec="fused")
             before = m.logits()
             assert np.isfinite(before).all()
-            for e, _ in binfmt.q4_tensors(SMALL):  # the int8 values of layer 1; the scales stay
-                if e.name in layer1:
-                    binfmt.tensor_from_image(img, e).fill_(0x55)
-            torch.cuda.synchronize()
+            wc.poison_layer1(img, SMALL, wc.LAYER1, 0x55)  # the int8 values of layer 1; the scales stay
             t1 = m.predict(5, 0, exec="fused")  # a batch-1 step: no B-token call follows the overwrite
             after = m.logits()
             if on:
@@ -381,40 +267,20 @@ def test_the_copy_is_what_is_read(gpu):
 
 # ---- 4. loops ---------------------------------------------------------------------------------
 def test_generate_loops_match(gpu, small_img):
-    rng = np.random.default_rng(11)
-    prompt = [int(t) for t in rng.integers(0, SMALL.vocab_size, 250)]  # sampled steps at positions 249 .. 270
-    total = 272
-    bias = {int(t): float(v) for t, v in zip(rng.integers(0, SMALL.vocab_size, 6), (-3.0, 2.5, -np.inf, 1.0, -1.5, 4.0))}
     res = {}
     for on in (False, True):
         m = _q4_model(small_img, SMALL, EXACT) if on else _model(small_img, SMALL, EXACT)
         try:
             assert m.q4_info()["state"] == (1 if on else 0)
-            r = {}
-            for ex in ("graph", "fused"):
-                r["greedy", ex] = m.generate(prompt, total, exec=ex)[0]
-            m.set_sampling(temperature=0.8, top_k=50, top_p=0.95, seed=17)
-            m.set_penalties(repetition=1.3, presence=0.2, frequency=0.1, last_n=64)
-            m.set_logit_bias(bias)
-            m.set_logprobs(5)
-            for ex in ("graph", "fused"):
-                r["sampled", ex] = m.generate(prompt, total, exec=ex)[0]
-                lp = m.logprobs(248, 24)
-                r["records", ex] = b"".join(lp[k].tobytes() for k in ("token", "logprob", "top_ids", "top_logprobs"))
-            res[on] = r
+            res[on] = wc.generate_loops(m)
         finally:
             m.close()
-    a, b = res[False], res[True]
-    assert len(a["greedy", "graph"]) > 256 and len(a["sampled", "graph"]) > 256  # the runs cross position 256
-    for key in a:
-        assert a[key] == b[key], f"{key}: flag off and on differ"
-    assert a["sampled", "graph"] == a["sampled", "fused"] and a["records", "graph"] == a["records", "fused"]
-    assert len(set(a["sampled", "graph"][-20:])) > 4  # the run wanders: equality is not that of one repeated token
+    wc.assert_loops_equal(res[False], res[True])
 
 
 def test_requantised_image_is_an_ordinary_int8_checkpoint(gpu, oracle, small_img):
     """anchor outside the library: the CPU oracle's int8 path on the requantised image, teacher-forced"""
-    om = oracle.OracleModel.from_spec(small_img.cpu().numpy(), SMALL, cache_len=CACHE)
+    om = oracle.OracleModel.from_spec(small_img.cpu().numpy(), SMALL, cache_len=wc.CACHE)
     m = _q4_model(small_img, SMALL)
     try:
         rng = np.random.default_rng(3)
@@ -443,7 +309,7 @@ def test_b_token_passes_are_the_int8_models(gpu, small_img):
             r["prefill"] = b"".join(k.tobytes() + v.tobytes() for k, v in kv)
             m.set_logprobs(3)
             sc = m.score(toks, 0)
-            r["score"] = b"".join(np.asarray(sc[k]).tobytes() for k in ("token", "logprob", "top_ids", "top_logprobs"))
+            r["score"] = wc.rec_bytes(sc)
             m.set_logprobs(None)
             slot_len = m.seq_slots(2)
             m.seq_prefill(0, toks[:3], 0)
@@ -479,15 +345,4 @@ def test_selfcheck_failure_falls_back_to_int8(gpu, small_img):
 
 # ---- 6. coverage gate -------------------------------------------------------------------------
 def test_coverage_gate(gpu):
-    assert co.tools_present(), "the LLVM tools of the ROCm install are needed to read the library's code objects"
-    build.build_lib()
-    compiled = co.instantiations(co.code_object_notes(_ffi.LIB_PATH), STEMS)
-    missing = [g for g in GEOMETRIES if g not in _LAUNCHED]
-    assert not missing, f"geometries that did not run to the end (run the whole module): {missing}"
-    seen = set().union(*_LAUNCHED.values())
-    for stem in sorted(STEMS):
-        assert any(k.split("<")[0] == stem for k in compiled), f"no {stem} instantiation in the library"
-    assert seen <= compiled, f"launched but not found in the code objects: {sorted(seen - compiled)}"
-    gap = compiled - seen
-    print(f"{len(seen)} of {len(compiled)} compiled Q4 instantiations launched and compared")
-    assert not gap, f"compiled and never launched: {sorted(gap)}"
+    wc.coverage_gate(STEMS, GEOMETRIES, _LAUNCHED, "Q4")

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import torch
 
+import wcopy_cases as wc
 from kuiperllama_amd import _ffi, binfmt, build
 
 TINY = dict(dim=64, hidden_dim=96, n_layers=2, n_heads=4, n_kv_heads=2, vocab_size=37, seq_len=16)
@@ -55,7 +56,7 @@ def _image_with_words(spec, rng):
 
 
 def test_covered_tensors_follow_the_classifier():
-    mats = {f"{n}.{l}" for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3") for l in range(2)}
+    mats = {f"{n}.{l}" for n in wc.MATRICES for l in range(2)}
     assert {e.name for e in binfmt.w16_tensors(_spec(True))} == mats | {"tok_emb"}
     assert {e.name for e in binfmt.w16_tensors(_spec(False))} == mats | {"wcls"}
     q = _spec(True, family=binfmt.FAMILY_QWEN2)  # biases are not matrices

@@ -11,13 +11,12 @@ import os
 import numpy as np
 
 import code_objects as co
-import test_w16_pass as pass_base
+import wcopy_cases as wc
 from kuiperllama_amd import _ffi, binfmt, build
 
 TINY = dict(dim=64, hidden_dim=96, n_layers=2, n_heads=4, n_kv_heads=2, vocab_size=37, seq_len=16)
 
-DECODE_W16 = ("k_qkv_w16", "k_gemv_res_w16", "k_wo_comb_w16", "k_ffn13_w16", "k_cls_w16")
-PASS_W16 = tuple(pass_base.W16_PASS)
+DECODE_W16, PASS_W16 = wc.DECODE["w16"], wc.PASS["w16"]
 
 
 def _spec(tied, **kw):
@@ -163,11 +162,8 @@ def test_flag_hook_and_entry_points():
     assert "#define KH_FLAG_W16_F16 32" in src and "#define KH_FLAG_W16 16" in src
     assert "KH_W16_F16".startswith(_ffi._HOOK_PREFIXES)  # sync_env mirrors it from the environment
     assert _ffi.debug_get("KH_W16_F16") is None
-    try:
-        _ffi.debug_set("KH_W16_F16", "1")
+    with wc.hook("KH_W16_F16", "1"):
         assert _ffi.debug_get("KH_W16_F16") == "1"
-    finally:
-        _ffi.debug_set("KH_W16_F16", None)
     assert _ffi.debug_get("KH_W16_F16") is None
     from kuiperllama_amd.model import KuiperModel
     assert callable(KuiperModel.w16_format)
@@ -181,7 +177,7 @@ def test_h16_kernels_in_the_code_objects():
     n = {}
     for stems, total in ((DECODE_W16, 111), (PASS_W16, 21)):
         n[total] = 0
-        for stem in stems:
+        for stem in sorted(stems):
             twin = stem[:-4] + "_h16"
             want = {k.replace(stem, twin) for k in co.instantiations(notes, {stem})}
             got = co.instantiations(notes, {twin})
@@ -189,11 +185,11 @@ def test_h16_kernels_in_the_code_objects():
             n[total] += len(got)
         assert n[total] == total, n
     # the _w16 pass sets and the fp32 / int8 sets are what they were
-    for table in (pass_base.W16_PASS, pass_base.EXISTING):
+    for table in (wc.PASS_W16_COMPILED, wc.PASS_COMPILED_BEFORE):
         for stem, want in table.items():
             got = co.instantiations(notes, {stem})
             assert got == want, (stem, sorted(got - want), sorted(want - got))
-    twins = {s[:-4] + "_h16" for s in DECODE_W16 + PASS_W16}
+    twins = wc.DECODE["h16"] | wc.PASS["h16"]
     scratch = {co.template_name(k): v for k, v in co.kernel_scratch(notes).items()
                if (co.template_name(k) or "").split("<")[0] in twins}
     assert len(scratch) == 132, len(scratch)

@@ -2,7 +2,7 @@
 fp16-exact image computes the BITS of the same image streamed as fp32 - logits, K/V rows, tokens and log-prob records,
 compared with np.array_equal / as bytes, never with a tolerance.
 
-Models and helpers are those of test_w16_gpu.py (2 layers, 1024 cache rows, its four geometries); the image is
+Models and helpers are those of wcopy_cases.py (2 layers, 1024 cache rows, its four fp32 geometries); the image is
 synth_image(seed fixed, final_norm_std=1.0) with its matrices rounded to fp16 (binfmt.round_matrices_fp16): 87 % of its
 matrix words are not bf16-exact and some thousand per geometry are fp16 subnormals.  The two models of a comparison
 share one device image.
@@ -26,50 +26,33 @@ import numpy as np
 import pytest
 import torch
 
-import code_objects as co
-import test_w16_gpu as base
-from kuiperllama_amd import _ffi, binfmt, build
+import wcopy_cases as wc
+from kuiperllama_amd import _ffi, binfmt
 
 pytestmark = pytest.mark.gpu
 
 W16 = _ffi.KH_FLAG_W16
 F16 = _ffi.KH_FLAG_W16_F16  # fails on a library without the feature
 EXACT = _ffi.KH_FLAG_PREFILL_EXACT
-GEOMETRIES, TIED, CACHE, DEEP_POS = base.GEOMETRIES, base.TIED, base.CACHE, base.DEEP_POS
-UNTIED = base._spec(448, 1216, 7, 7, 999, base.INTER, base.L, "h16-untied")  # tok_emb is not in the copy
-STEMS = {s.replace("_w16", "_h16") for s in base.STEMS}
-TIED_STEP_H16 = {k.replace("_w16", "_h16") for k in base.TIED_STEP_W16}
+GEOMETRIES, TIED = wc.GEOMETRIES_F32, wc.TIED
+UNTIED = wc.spec(448, 1216, 7, 7, 999, False, 64, wc.INTER, wc.L, "h16-untied")  # tok_emb is not in the copy
+STEMS = wc.DECODE["h16"]
+GEMV = STEMS | wc.DECODE["w16"] | wc.DECODE_F32  # the launches a logged step keeps
+# one fused step at position 0
+TIED_STEP_FP32, TIED_STEP_W16, TIED_STEP_H16 = wc.TIED_STEP_F32, wc.TIED_STEP["w16"], wc.TIED_STEP["h16"]
 NO_COPY = {"state": 0, "bytes": 0, "build_us": 0, "classes": [], "first_inexact": -1}
 
 _LAUNCHED = {}  # geometry -> _h16 instantiations its shapes launched (test_bit_identity -> test_coverage_gate)
-_model = base._model
-
-
-def _rounded(spec, gpu, seed=4242):
-    img = binfmt.synth_image(spec, seed=seed, device=gpu, final_norm_std=1.0)
-    binfmt.round_matrices_fp16(img, spec)
-    torch.cuda.synchronize()
-    return img
+_model = wc.model
 
 
 @pytest.fixture(scope="module")
 def tied_img(gpu):
-    return _rounded(TIED, gpu)
+    return wc.exact_image("h16", TIED, gpu)
 
 
-def _gemv_log(log):
-    return {k for k in log if k.split("<")[0] in STEMS | base.STEMS | base.FP32_STEMS}
-
-
-def _logged_step(m, tok=5, pos=0):
-    """(GEMV launches, logits) of one fused step"""
-    _ffi.debug_set("KH_LAUNCH_LOG", "1")
-    try:
-        m.predict(tok, pos, exec="fused")
-        lg = m.logits()
-        return _gemv_log(_ffi.launch_log()), lg
-    finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
+def _logged_step(m):
+    return wc.logged_step(m, GEMV)
 
 
 def _same_bits(a, b):
@@ -84,12 +67,12 @@ def test_state_and_launches(gpu, tied_img):
         assert m0.w16_info() == NO_COPY and m0.w16_format() == {"format": None, "first_inexact_fp16": -1}
         info = m1.w16_info()
         assert info["state"] == 1 and info["first_inexact"] == 0, info  # wq of layer 0 is not bf16-exact
-        assert info["bytes"] == base._planned_bytes(TIED) > 0, info
+        assert info["bytes"] == wc.planned_w16_bytes(TIED) > 0, info
         assert info["classes"] == list(_ffi.KH_W16_CLASSES), info
         assert m1.w16_format() == {"format": "fp16", "first_inexact_fp16": -1}
         log0, lg0 = _logged_step(m0)
         log1, lg1 = _logged_step(m1)
-        assert log0 == base.TIED_STEP_FP32, sorted(log0)
+        assert log0 == TIED_STEP_FP32, sorted(log0)
         assert log1 == TIED_STEP_H16, sorted(log1)
         assert np.isfinite(lg0).all() and _same_bits(lg0, lg1)
         # KH_FLAG_W16 alone stays bf16-only: what it reported and launched before the fp16 format existed
@@ -97,7 +80,7 @@ def test_state_and_launches(gpu, tied_img):
         assert info["state"] == -1 and info["bytes"] == 0 and info["classes"] == [] and info["first_inexact"] == 0, info
         assert mb.w16_format() == {"format": None, "first_inexact_fp16": -1}  # fp16 was not tried
         logb, lgb = _logged_step(mb)
-        assert logb == base.TIED_STEP_FP32 and _same_bits(lg0, lgb), sorted(logb)
+        assert logb == TIED_STEP_FP32 and _same_bits(lg0, lgb), sorted(logb)
     finally:
         m0.close()
         m1.close()
@@ -105,13 +88,13 @@ def test_state_and_launches(gpu, tied_img):
 
 
 def test_bf16_plain_and_int8_images(gpu):
-    img = base._rounded(TIED, gpu)  # bf16-exact: the bf16 format wins, the fp16 build never runs
+    img = wc.exact_image("w16", TIED, gpu)  # bf16-exact: the bf16 format wins, the fp16 build never runs
     m0, m1 = _model(img, TIED), _model(img, TIED, F16)
     try:
         assert m1.w16_info()["state"] == 1 and m1.w16_format() == {"format": "bf16", "first_inexact_fp16": -1}
         log0, lg0 = _logged_step(m0)
         log1, lg1 = _logged_step(m1)
-        assert log1 == base.TIED_STEP_W16 and _same_bits(lg0, lg1), sorted(log1)
+        assert log1 == TIED_STEP_W16 and _same_bits(lg0, lg1), sorted(log1)
     finally:
         m0.close()
         m1.close()
@@ -124,12 +107,12 @@ def test_bf16_plain_and_int8_images(gpu):
         assert m1.w16_format() == {"format": None, "first_inexact_fp16": 0}  # slot 7 = 1: wq of layer 0
         log0, lg0 = _logged_step(m0)
         log1, lg1 = _logged_step(m1)
-        assert log0 == log1 == base.TIED_STEP_FP32 and _same_bits(lg0, lg1), (sorted(log0), sorted(log1))
+        assert log0 == log1 == TIED_STEP_FP32 and _same_bits(lg0, lg1), (sorted(log0), sorted(log1))
     finally:
         m0.close()
         m1.close()
     # one mantissa bit too many in the LAST covered tensor (the tied classifier = tok_emb is tensor 7 * layers)
-    img = _rounded(TIED, gpu)
+    img = wc.exact_image("h16", TIED, gpu)
     e = [t for t in binfmt.layout(TIED)[0] if t.name == "tok_emb"][0]
     img[e.offset + e.nbytes - 4] |= 1
     torch.cuda.synchronize()
@@ -139,7 +122,7 @@ def test_bf16_plain_and_int8_images(gpu):
         assert m.w16_format() == {"format": None, "first_inexact_fp16": 7 * TIED.n_layers}
     finally:
         m.close()
-    q8 = base._spec(512, 1408, 8, 8, 501, base.INTER, base.L, "h16-q8", quant=True)
+    q8 = wc.spec(512, 1408, 8, 8, 501, True, 64, wc.INTER, wc.L, "h16-q8")
     qimg = binfmt.synth_image(q8, seed=7, device=gpu)
     torch.cuda.synchronize()
     m0, m1 = _model(qimg, q8), _model(qimg, q8, F16)
@@ -147,7 +130,7 @@ def test_bf16_plain_and_int8_images(gpu):
         assert m1.w16_info() == NO_COPY and m1.w16_format() == {"format": None, "first_inexact_fp16": -1}
         log0, lg0 = _logged_step(m0)
         log1, lg1 = _logged_step(m1)
-        assert log0 == log1 and log0 and not any(k.split("<")[0] in STEMS | base.STEMS for k in log1), sorted(log1)
+        assert log0 == log1 and log0 and not wc.stems(log1) & (STEMS | wc.DECODE["w16"]), sorted(log1)
         assert _same_bits(lg0, lg1)
     finally:
         m0.close()
@@ -155,8 +138,7 @@ def test_bf16_plain_and_int8_images(gpu):
 
 
 def test_hook_overrides_the_flag(gpu, tied_img):
-    try:
-        _ffi.debug_set("KH_W16_F16", "1")
+    with wc.hook("KH_W16_F16", "1"):
         for flags in (0, W16):  # the hook alone asks for a copy, as the flag alone does
             m = _model(tied_img, TIED, flags)
             try:
@@ -164,18 +146,17 @@ def test_hook_overrides_the_flag(gpu, tied_img):
                 assert _logged_step(m)[0] == TIED_STEP_H16
             finally:
                 m.close()
-        _ffi.debug_set("KH_W16", "0")  # no copy at all, whatever else is set
-        m = _model(tied_img, TIED, F16)
-        try:
-            assert m.w16_info() == NO_COPY and _logged_step(m)[0] == base.TIED_STEP_FP32
-        finally:
-            m.close()
-        _ffi.debug_set("KH_W16", None)
-        _ffi.debug_set("KH_W16_F16", "0")
+        with wc.hook("KH_W16", "0"):  # no copy at all, whatever else is set
+            m = _model(tied_img, TIED, F16)
+            try:
+                assert m.w16_info() == NO_COPY and _logged_step(m)[0] == TIED_STEP_FP32
+            finally:
+                m.close()
+    with wc.hook("KH_W16_F16", "0"):
         m = _model(tied_img, TIED, F16 | W16)  # bf16 only
         try:
             assert m.w16_info()["state"] == -1 and m.w16_format() == {"format": None, "first_inexact_fp16": -1}
-            assert _logged_step(m)[0] == base.TIED_STEP_FP32
+            assert _logged_step(m)[0] == TIED_STEP_FP32
         finally:
             m.close()
         m = _model(tied_img, TIED, F16)  # the bit is off and nothing else asks
@@ -183,70 +164,40 @@ def test_hook_overrides_the_flag(gpu, tied_img):
             assert m.w16_info() == NO_COPY
         finally:
             m.close()
-    finally:
-        _ffi.debug_set("KH_W16", None)
-        _ffi.debug_set("KH_W16_F16", None)
 
 
 # ---- 2. bit identity under forced shapes ------------------------------------------------------
-def _compare_steps(m0, m1, spec, steps, rows, what):
-    """teacher-forced steps on both models; -> the _h16 launches of the flag-on model, its results"""
-    want = base._run_steps(m0, spec, steps, rows)
-    _ffi.debug_set("KH_LAUNCH_LOG", "1")  # after creation: the self-check's launches are not compared ones
-    try:
-        got = base._run_steps(m1, spec, steps, rows)
-        log = _gemv_log(_ffi.launch_log())
-    finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
-    assert log and all(k.split("<")[0] in STEMS for k in log), f"{what}: fp32 or bf16 GEMV launched: {sorted(log)}"
-    for (tok, pos), (la, ka, va), (lb, kb, vb) in zip(steps, want, got):
-        assert np.array_equal(la, lb), f"{what} pos {pos}: logits differ in {int((la != lb).sum())} words"
-        assert np.array_equal(ka, kb) and np.array_equal(va, vb), f"{what} pos {pos}: K/V rows differ"
-    return log, want, got
-
-
 @pytest.mark.parametrize("name", list(GEOMETRIES))
 def test_bit_identity_under_forced_shapes(gpu, name):
     spec = GEOMETRIES[name]
-    img = _rounded(spec, gpu)
+    img = wc.exact_image("h16", spec, gpu)
     assert binfmt.matrices_fp16_exact(img, spec) and not binfmt.matrices_bf16_exact(img, spec)
     rng = np.random.default_rng(7)
-    steps = list(zip([int(t) for t in rng.integers(0, spec.vocab_size, 4)], (0, 1, 2, DEEP_POS)))
-    rows = (rng.standard_normal((spec.n_layers, DEEP_POS, spec.kv_dim), dtype=np.float32),
-            rng.standard_normal((spec.n_layers, DEEP_POS, spec.kv_dim), dtype=np.float32))
-    rows[0][:, rng.integers(0, DEEP_POS, 8)] *= 6.0  # a few dominant keys: the splits' maxima differ
+    steps = wc.steps(spec, rng)
+    rows = wc.deep_rows(spec, rng)
+    shapes = wc.decode_shapes(spec)
     launched = set()
     try:
-        for i, sh in enumerate(base._shapes(spec)):
+        for i, sh in enumerate(shapes):
             what = f"{name} shape {i} {sh}"
-            base._set_shape_hooks(sh)
+            wc.set_shape_hooks(sh)
             m0, m1 = _model(img, spec), _model(img, spec, F16)
             try:
                 assert m1.w16_info()["state"] == 1 and m1.w16_format()["format"] == "fp16", what
-                log, want, _ = _compare_steps(m0, m1, spec, steps, rows, what)
-                for (tok, pos), (la, _, _) in zip(steps, want):
-                    assert not np.isnan(la.view(np.float32)).any(), f"{what} pos {pos}: NaN logits"
-                launched |= log
+                launched |= wc.compare_steps(m0, m1, spec, steps, rows, what, STEMS, GEMV)[0]
             finally:
                 m0.close()
                 m1.close()
     finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
-        base._set_shape_hooks({})
+        wc.set_shape_hooks({})
     _LAUNCHED[name] = launched
-    print(f"{name}: {len(base._shapes(spec))} shapes, {len(launched)} _h16 instantiations launched")
+    print(f"{name}: {len(shapes)} shapes, {len(launched)} _h16 instantiations launched")
 
 
 # ---- 3. the copy is what is read --------------------------------------------------------------
 def test_the_copy_is_what_is_read(gpu):
-    def poison(img):
-        for e in binfmt.layout(TIED)[0]:
-            if e.name in {f"{n}.1" for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")}:
-                binfmt.tensor_from_image(img, e).fill_(float("nan"))
-        torch.cuda.synchronize()
-
     for flags in (F16, 0):
-        img = _rounded(TIED, gpu)
+        img = wc.exact_image("h16", TIED, gpu)
         assert (img.data_ptr() + TIED.header_bytes()) % 16 == 0  # from_device_image uses the image in place
         m = _model(img, TIED, flags)
         try:
@@ -254,7 +205,7 @@ def test_the_copy_is_what_is_read(gpu):
             t0 = m.predict(5, 0, exec="fused")
             before = m.logits()
             assert np.isfinite(before).all()
-            poison(img)
+            wc.poison_layer1(img, TIED, wc.LAYER1, float("nan"))
             t1 = m.predict(5, 0, exec="fused")
             after = m.logits()
             if flags:
@@ -273,7 +224,7 @@ def _subnormal_words(words):
 
 def test_edge_weights(gpu):
     """(a) every fp16 edge value as a weight: rows of one value each, then rows that hold all six"""
-    img = _rounded(TIED, gpu)
+    img = wc.exact_image("h16", TIED, gpu)
     vals = torch.tensor([2.0 ** -24, -2.0 ** -24, 1023 * 2.0 ** -24, 2.0 ** -14, 65504.0, -0.0], dtype=torch.float32)
     e = [t for t in binfmt.layout(TIED)[0] if t.name == "wk.0"][0]
     wk = binfmt.tensor_from_image(img, e)
@@ -289,7 +240,7 @@ def test_edge_weights(gpu):
     try:
         assert m1.w16_format()["format"] == "fp16"
         steps = [(5, 0), (17, 1), (900, 2)]
-        _, want, _ = _compare_steps(m0, m1, TIED, steps, None, "edge weights")
+        _, want, _ = wc.compare_steps(m0, m1, TIED, steps, None, "edge weights", STEMS, GEMV)
         assert np.isfinite(want[0][0].view(np.float32)).all()  # position 0: one key, whatever its size
         k0 = np.abs(want[0][1][0].view(np.float32))  # layer 0's K row is made of these weights: 2^-24 .. 65504 times a sum
         assert np.isfinite(k0).all() and (k0 > 1e3).any() and ((k0 > 0) & (k0 < 1e-3)).any(), (k0.min(), k0.max())
@@ -301,7 +252,7 @@ def test_edge_weights(gpu):
 def test_fp32_subnormal_products_and_sums(gpu):
     """(b) an embedding row so small that the norm leaves it tiny (x^2 underflows: x * rsqrt(eps)): layer 0's K row
     is a sum of fp32-subnormal products.  tok_emb is not in the copy of an untied model, so the image stays fp16-exact."""
-    img = _rounded(UNTIED, gpu)
+    img = wc.exact_image("h16", UNTIED, gpu)
     e = [t for t in binfmt.layout(UNTIED)[0] if t.name == "tok_emb"][0]
     # |emb| ~ 0.02, rsqrt(eps) = 316, a K entry ~ 0.02 sqrt(448) |x rsqrt(eps)|: 2^-130 puts it near 2^-129
     row = binfmt.tensor_from_image(img, e)[5]
@@ -314,7 +265,7 @@ def test_fp32_subnormal_products_and_sums(gpu):
     try:
         assert m1.w16_info()["state"] == 1 and m1.w16_format()["format"] == "fp16"
         steps = [(5, 0), (5, 1)]
-        _, want, got = _compare_steps(m0, m1, UNTIED, steps, None, "subnormal K row")
+        _, want, got = wc.compare_steps(m0, m1, UNTIED, steps, None, "subnormal K row", STEMS, GEMV)
         k0 = want[0][1][0]  # flag OFF: layer 0's K row at position 0
         n = _subnormal_words(k0)
         print(f"flag-off K row: {n} of {k0.size} words are non-zero fp32 subnormals")
@@ -327,39 +278,20 @@ def test_fp32_subnormal_products_and_sums(gpu):
 
 # ---- 5. loops ---------------------------------------------------------------------------------
 def test_generate_loops_match(gpu, oracle, tied_img):
-    rng = np.random.default_rng(11)
-    prompt = [int(t) for t in rng.integers(0, TIED.vocab_size, 250)]  # sampled steps at positions 249 .. 270
-    total = 272
-    bias = {int(t): float(v) for t, v in zip(rng.integers(0, TIED.vocab_size, 6), (-3.0, 2.5, -np.inf, 1.0, -1.5, 4.0))}
     res = {}
     for flags in (EXACT, EXACT | F16):
         m = _model(tied_img, TIED, flags)
         try:
             assert m.w16_format()["format"] == ("fp16" if flags & F16 else None)
-            r = {}
-            for ex in ("graph", "fused"):
-                r["greedy", ex] = m.generate(prompt, total, exec=ex)[0]  # the screened tail, as it is
-            r["greedy32"] = m.generate(prompt[:2], 32, exec="graph")[0]
-            m.set_sampling(temperature=0.8, top_k=50, top_p=0.95, seed=17)
-            m.set_penalties(repetition=1.3, presence=0.2, frequency=0.1, last_n=64)
-            m.set_logit_bias(bias)
-            m.set_logprobs(5)
-            for ex in ("graph", "fused"):
-                r["sampled", ex] = m.generate(prompt, total, exec=ex)[0]
-                lp = m.logprobs(248, 24)
-                r["records", ex] = b"".join(lp[k].tobytes() for k in ("token", "logprob", "top_ids", "top_logprobs"))
-            res[flags] = r
+            greedy32 = m.generate(wc.loop_prompt(TIED)[:2], 32, exec="graph")[0]
+            res[flags] = dict(wc.generate_loops(m), greedy32=greedy32)
         finally:
             m.close()
     a, b = res[EXACT], res[EXACT | F16]
-    assert len(a["greedy", "graph"]) > 256 and len(a["sampled", "graph"]) > 256  # the runs cross position 256
-    for key in a:
-        assert a[key] == b[key], f"{key}: flag off and on differ"
-    assert a["sampled", "graph"] == a["sampled", "fused"] and a["records", "graph"] == a["records", "fused"]
-    assert len(set(a["sampled", "graph"][-20:])) > 4  # the run wanders: equality is not that of one repeated token
+    wc.assert_loops_equal(a, b)
     # anchor outside the library: the CPU oracle on the fp16-rounded image
-    om = oracle.OracleModel.from_spec(tied_img.cpu().numpy(), TIED, cache_len=CACHE)
-    want = om.generate(prompt[:2], 32)
+    om = oracle.OracleModel.from_spec(tied_img.cpu().numpy(), TIED, cache_len=wc.CACHE)
+    want = om.generate(wc.loop_prompt(TIED)[:2], 32)
     om.close()
     assert b["greedy32"] == want, (b["greedy32"], want)
 
@@ -367,18 +299,15 @@ def test_generate_loops_match(gpu, oracle, tied_img):
 # ---- 6. self-check ----------------------------------------------------------------------------
 def test_selfcheck_failure_falls_back_to_fp32(gpu, tied_img):
     m0 = _model(tied_img, TIED)
-    try:
-        _ffi.debug_set("KH_SELFTEST_FAIL", "w16")
+    with wc.hook("KH_SELFTEST_FAIL", "w16"):
         m1 = _model(tied_img, TIED, F16)
-    finally:
-        _ffi.debug_set("KH_SELFTEST_FAIL", None)
     try:
         info = m1.w16_info()
         assert info["state"] == -2 and info["bytes"] == 0 and info["classes"] == [], info
         assert m1.w16_format()["format"] is None
         log0, lg0 = _logged_step(m0)
         log1, lg1 = _logged_step(m1)
-        assert log0 == log1 == base.TIED_STEP_FP32, sorted(log1)
+        assert log0 == log1 == TIED_STEP_FP32, sorted(log1)
         assert _same_bits(lg0, lg1)
     finally:
         m0.close()
@@ -387,15 +316,4 @@ def test_selfcheck_failure_falls_back_to_fp32(gpu, tied_img):
 
 # ---- 7. coverage gate -------------------------------------------------------------------------
 def test_coverage_gate(gpu):
-    assert co.tools_present(), "the LLVM tools of the ROCm install are needed to read the library's code objects"
-    build.build_lib()
-    compiled = co.instantiations(co.code_object_notes(_ffi.LIB_PATH), STEMS)
-    missing = [g for g in GEOMETRIES if g not in _LAUNCHED]
-    assert not missing, f"geometries that did not run to the end (run the whole module): {missing}"
-    seen = set().union(*_LAUNCHED.values())
-    for stem in sorted(STEMS):
-        assert any(k.split("<")[0] == stem for k in compiled), f"no {stem} instantiation in the library"
-    assert seen <= compiled, f"launched but not found in the code objects: {sorted(seen - compiled)}"
-    gap = compiled - seen
-    print(f"{len(seen)} of {len(compiled)} compiled _h16 instantiations launched and compared")
-    assert not gap, f"compiled and never launched: {sorted(gap)}"
+    wc.coverage_gate(STEMS, GEOMETRIES, _LAUNCHED, "_h16")

@@ -2,8 +2,8 @@
 and the sequence-slot calls stream the fp16-format 16-bit copy and leave the BITS of the same image streamed as fp32 -
 K/V rows, records, picks and words compared as raw words / bytes, never with a tolerance.
 
-Mirrors test_w16_pass_gpu.py (its geometries, widths, shapes and call sequence are used as they are) on images whose
-matrices are rounded to fp16 (binfmt.round_matrices_fp16).
+Mirrors test_w16_pass_gpu.py (the geometries, widths, shapes and call sequence of wcopy_cases.py, as there) on images
+whose matrices are rounded to fp16 (binfmt.round_matrices_fp16).
 
   1. state and launches: every class's pass on the copy (KH_W16_PASS=0x1f) -> only _h16 pass stems; the default mask
      and a class mask -> exactly their classes; 0 -> the fp32 stems while a predict logs the decode _h16 kernels.
@@ -17,56 +17,32 @@ matrices are rounded to fp16 (binfmt.round_matrices_fp16).
 """
 import numpy as np
 import pytest
-import torch
 
-import code_objects as co
-import test_w16_pass_gpu as base
-from kuiperllama_amd import _ffi, binfmt, build
+import wcopy_cases as wc
+from kuiperllama_amd import _ffi, binfmt
 
 pytestmark = pytest.mark.gpu
 
 F16 = _ffi.KH_FLAG_W16_F16  # fails on a library without the feature
 EXACT = _ffi.KH_FLAG_PREFILL_EXACT
-GEOMETRIES, WIDTH, TIED, QWEN = base.GEOMETRIES, base.WIDTH, base.TIED, base.QWEN
-ALL, DEFAULT, FP32_STEMS = base.ALL, base.DEFAULT, base.FP32_STEMS
-STEMS = {s.replace("_w16", "_h16") for s in base.STEMS}
-DECODE_H16 = {s.replace("_w16", "_h16") for s in base.DECODE_W16}
-DECODE_ANY = DECODE_H16 | base.DECODE_W16
+GEOMETRIES, WIDTH, TIED, QWEN = wc.GEOMETRIES_F32, wc.WIDTH, wc.TIED, wc.QWEN
+ALL = list(_ffi.KH_W16_CLASSES)
+DEFAULT = ["ffn13", "w2"]  # the classes whose pass reads the copy unless KH_W16_PASS says otherwise
+STEMS, W16_STEMS, FP32_STEMS = wc.PASS["h16"], wc.PASS["w16"], wc.PASS_F32
+DECODE_H16 = wc.DECODE["h16"]
+DECODE_ANY = DECODE_H16 | wc.DECODE["w16"]
 
 _LAUNCHED = {}  # geometry -> _h16 pass instantiations its shapes launched (test_bit_identity -> test_coverage_gate)
-_model = base._model
-
-
-def _rounded(spec, gpu, seed=4242):
-    img = binfmt.synth_image(spec, seed=seed, device=gpu, final_norm_std=1.0)
-    binfmt.round_matrices_fp16(img, spec)
-    torch.cuda.synchronize()
-    return img
+_model = wc.model
 
 
 @pytest.fixture(scope="module")
 def tied_img(gpu):
-    return _rounded(TIED, gpu)
+    return wc.exact_image("h16", TIED, gpu)
 
 
 def _logged_passes(m, spec):
-    """(stems of the pass launches of a prefill of 3 tokens, a score of 9 and a seq_step of 3 lanes - fp32, _w16 or
-    _h16; stems a predict launched)"""
-    toks = [int(t) for t in np.random.default_rng(3).integers(0, spec.vocab_size, 9)]
-    _ffi.debug_set("KH_LAUNCH_LOG", "1")
-    try:
-        m.prefill(toks[:3], 0)
-        m.set_logprobs(5)
-        m.score(toks, 0)
-        m.set_logprobs(None)
-        m.seq_slots(4)
-        m.seq_step([2, 0, 3], toks[:3], [0, 4, 1])
-        passes = base._stems(_ffi.launch_log()) & (STEMS | base.STEMS | FP32_STEMS)
-        _ffi.debug_set("KH_LAUNCH_LOG", "1")  # an empty log
-        m.predict(5, 0, exec="fused")
-        return passes, base._stems(_ffi.launch_log())
-    finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
+    return wc.logged_passes(m, spec, STEMS | W16_STEMS | FP32_STEMS)  # fp32, _w16 or _h16
 
 
 # ---- 1. state and launches --------------------------------------------------------------------
@@ -107,9 +83,9 @@ def test_state_and_launches(gpu, tied_img):
 @pytest.mark.parametrize("name", list(GEOMETRIES))
 def test_bit_identity_under_forced_shapes_and_masks(gpu, name):
     spec, width = GEOMETRIES[name], WIDTH[name]
-    img = _rounded(spec, gpu)
+    img = wc.exact_image("h16", spec, gpu)
     assert binfmt.matrices_fp16_exact(img, spec) and not binfmt.matrices_bf16_exact(img, spec)
-    shapes = base._shapes(spec)
+    shapes = wc.pass_shapes(spec)
     # (shape hooks, KH_W16_PASS, the classes it leaves): every forced shape with all five classes on the copy, then the
     # first of them that prefill_supported admits under the default mask and with the passes on fp32
     runs = [(sh, "0x1f", ALL) for sh in shapes]
@@ -119,7 +95,7 @@ def test_bit_identity_under_forced_shapes_and_masks(gpu, name):
             i += 1
             sh, passes, classes = runs[i]
             what = f"{name} run {i} {sh} KH_W16_PASS={passes}"
-            base._set_shape_hooks(sh)
+            wc.set_shape_hooks(sh)
             m0, m1 = _model(img, spec), _model(img, spec, F16, passes=passes)
             try:
                 assert m1.w16_info()["state"] == 1 and m1.w16_format()["format"] == "fp16", what
@@ -131,11 +107,10 @@ def test_bit_identity_under_forced_shapes_and_masks(gpu, name):
                     continue
                 if n_ran == 0:
                     runs += [(sh, None, DEFAULT), (sh, "0", [])]
-                _ffi.debug_set("KH_LAUNCH_LOG", "1")  # after creation; m0 logs into it too: only _h16 names are kept
-                base._run_shape(m0, m1, spec, width, what, 7 + i)
-                log = _ffi.launch_log()
-                _ffi.debug_set("KH_LAUNCH_LOG", None)
-                assert not any(k.split("<")[0] in base.STEMS for k in log), f"{what}: a bf16 twin was launched"
+                with wc.launch_log() as read:  # after creation; m0 logs into it too: only _h16 names are kept
+                    wc.run_pass_shape(m0, m1, spec, width, what, 7 + i)
+                    log = read()
+                assert not any(wc.stem(k) in W16_STEMS for k in log), f"{what}: a bf16 twin was launched"
                 mine = {k for k in log if k.split("<")[0] in STEMS}
                 assert bool(mine) == bool(classes), what
                 launched |= mine
@@ -144,8 +119,7 @@ def test_bit_identity_under_forced_shapes_and_masks(gpu, name):
                 m0.close()
                 m1.close()
     finally:
-        _ffi.debug_set("KH_LAUNCH_LOG", None)
-        base._set_shape_hooks({})
+        wc.set_shape_hooks({})
     assert n_ran >= 6, f"{name}: only {n_ran} runs reached the B-token pass"
     _LAUNCHED[name] = launched
     print(f"{name}: {n_ran} of {len(runs)} runs, {len(launched)} _h16 pass instantiations launched")
@@ -154,7 +128,7 @@ def test_bit_identity_under_forced_shapes_and_masks(gpu, name):
 def test_a_flag_on_pass_launches_no_fp32_twin_under_forced_shapes(gpu, tied_img):
     """the log of test 2 is shared by its two models; here the flag-on model runs alone"""
     try:
-        base._set_shape_hooks(base._shapes(TIED)[1])
+        wc.set_shape_hooks(wc.pass_shapes(TIED)[1])
         m = _model(tied_img, TIED, F16, passes="0x1f")
         try:
             p, _ = _logged_passes(m, TIED)
@@ -162,28 +136,17 @@ def test_a_flag_on_pass_launches_no_fp32_twin_under_forced_shapes(gpu, tied_img)
         finally:
             m.close()
     finally:
-        base._set_shape_hooks({})
+        wc.set_shape_hooks({})
 
 
 # ---- 3. the copy is what is read --------------------------------------------------------------
 def test_the_copy_is_what_is_read(gpu):
     spec = QWEN
-    names = {f"{n}.1" for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")} | {"wcls"}
-
-    def poison(img):
-        hit = 0
-        for e in binfmt.layout(spec)[0]:
-            if e.name in names:
-                binfmt.tensor_from_image(img, e).fill_(float("nan"))
-                hit += 1
-        assert hit == len(names)
-        torch.cuda.synchronize()
-
     rng = np.random.default_rng(5)
     toks = [int(t) for t in rng.integers(0, spec.vocab_size, 9)]
     prompts = [toks[:1], toks[2:5], toks[4:9]]
     for flags in (F16, 0):
-        img = _rounded(spec, gpu)
+        img = wc.exact_image("h16", spec, gpu)
         assert (img.data_ptr() + spec.header_bytes()) % 16 == 0  # from_device_image uses the image in place
         m = _model(img, spec, flags, passes="0x1f")
         try:
@@ -192,11 +155,11 @@ def test_the_copy_is_what_is_read(gpu):
             m.set_logprobs(5)
             r0 = m.score(toks, 0)
             assert np.isfinite(r0["logprob"][:-1]).all()
-            poison(img)
+            wc.poison_layer1(img, spec, wc.LAYER1 | {"wcls"}, float("nan"))
             r1 = m.score(toks, 0)
             if flags:
                 assert m.w16_format()["format"] == "fp16"
-                assert base._rec_bytes(r0) == base._rec_bytes(r1)
+                assert wc.rec_bytes(r0) == wc.rec_bytes(r1)
                 m.set_logprobs(None)
                 w1, _ = m.generate_batch(prompts, [12, 10, 14])
                 assert w0 == w1 and all(w0)
@@ -215,7 +178,7 @@ def test_loops_match(gpu, tied_img):
         try:
             assert m.w16_pass_info() == {"classes": ALL if flags & F16 else []}
             logs[flags] = set()
-            res[flags] = base._loops(m, width, logs[flags])  # generate_batch three ways, best_of(share=True)
+            res[flags] = wc.pass_loops(m, width, logs[flags])  # generate_batch three ways, best_of(share=True)
         finally:
             m.close()
     a, b = res[EXACT], res[EXACT | F16]
@@ -232,13 +195,12 @@ def test_loops_match(gpu, tied_img):
         m = _model(tied_img, TIED, flags, passes="0x1f")
         try:
             truth, _ = m.generate(prompt, total, exec="graph")
-            _ffi.debug_set("KH_LAUNCH_LOG", "1")
-            words, _, stats = m.generate_lookup(prompt, total, hint=truth)
-            log = base._stems(_ffi.launch_log())
-            _ffi.debug_set("KH_LAUNCH_LOG", None)
+            with wc.launch_log() as read:
+                words, _, stats = m.generate_lookup(prompt, total, hint=truth)
+                log = wc.stems(read())
             assert words == truth and stats["accepted"] > 0, stats
             if flags & F16:
-                assert log & (STEMS | base.STEMS | FP32_STEMS) == STEMS - {"k_seq_qkv_h16"}, sorted(log)
+                assert log & (STEMS | W16_STEMS | FP32_STEMS) == STEMS - {"k_seq_qkv_h16"}, sorted(log)
                 for s in (0, 2):
                     m.set_sampling(**a["samp"][s])
                     got, _ = m.generate(a["prompts"][s], a["totals"][s], exec="graph")
@@ -246,21 +208,11 @@ def test_loops_match(gpu, tied_img):
                 m.set_sampling()
             out[flags] = (words, stats)
         finally:
-            _ffi.debug_set("KH_LAUNCH_LOG", None)
             m.close()
     assert out[EXACT] == out[EXACT | F16]
 
 
 # ---- 5. coverage gate -------------------------------------------------------------------------
 def test_coverage_gate(gpu):
-    assert co.tools_present(), "the LLVM tools of the ROCm install are needed to read the library's code objects"
-    build.build_lib()
-    compiled = co.instantiations(co.code_object_notes(_ffi.LIB_PATH), STEMS)
+    compiled = wc.coverage_gate(STEMS, GEOMETRIES, _LAUNCHED, "_h16 pass")
     assert len(compiled) == 21, sorted(compiled)
-    missing = [g for g in GEOMETRIES if g not in _LAUNCHED]
-    assert not missing, f"geometries that did not run to the end (run the whole module): {missing}"
-    seen = set().union(*_LAUNCHED.values())
-    assert seen <= compiled, f"launched but not found in the code objects: {sorted(seen - compiled)}"
-    gap = compiled - seen
-    print(f"{len(seen)} of {len(compiled)} compiled _h16 pass instantiations launched and compared")
-    assert not gap, f"compiled and never launched: {sorted(gap)}"

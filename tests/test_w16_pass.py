@@ -3,40 +3,18 @@ the kernels in the library's gfx950 code objects - the five _w16 pass stems with
 (B in {8, 4}, gemv_res {8, 4, 2}; SPLIT {2, 1} for qkv, {4, 2, 1} for gemv_res), none with scratch, and the fp32 /
 int8 pass kernels with the sets they had before the twins existed.  CPU only."""
 import code_objects as co
+import wcopy_cases as wc
 from kuiperllama_amd import _ffi, build
 
-W16_PASS = {
-    "k_pf_qkv_w16": {f"k_pf_qkv_w16<{sp},{b}>" for sp in (2, 1) for b in (8, 4)},
-    "k_seq_qkv_w16": {f"k_seq_qkv_w16<{sp},{b}>" for sp in (2, 1) for b in (8, 4)},
-    "k_pf_ffn13_w16": {f"k_pf_ffn13_w16<{b}>" for b in (8, 4)},
-    "k_pf_gemv_res_w16": {f"k_pf_gemv_res_w16<{sp},{b}>" for sp in (4, 2, 1) for b in (8, 4, 2)},
-    "k_pf_cls_w16": {f"k_pf_cls_w16<{b}>" for b in (8, 4)},
-}
-# what the parent of the W16 passes compiled for the kernels whose bodies became templates over the matrix view
-EXISTING = {
-    "k_pf_qkv": {"k_pf_qkv<false,1,4>", "k_pf_qkv<false,1,8>", "k_pf_qkv<false,2,4>", "k_pf_qkv<false,2,8>",
-                 "k_pf_qkv<true,1,4>", "k_pf_qkv<true,2,4>"},
-    "k_seq_qkv": {"k_seq_qkv<false,1,4>", "k_seq_qkv<false,1,8>", "k_seq_qkv<false,2,4>", "k_seq_qkv<false,2,8>",
-                  "k_seq_qkv<true,1,4>", "k_seq_qkv<true,2,4>"},
-    "k_pf_ffn13": {"k_pf_ffn13<false,4>", "k_pf_ffn13<false,8>", "k_pf_ffn13<true,4>"},
-    "k_pf_gemv_res": {"k_pf_gemv_res<false,1,2>", "k_pf_gemv_res<false,1,4>", "k_pf_gemv_res<false,1,8>",
-                      "k_pf_gemv_res<false,2,2>", "k_pf_gemv_res<false,2,4>", "k_pf_gemv_res<false,2,8>",
-                      "k_pf_gemv_res<false,4,2>", "k_pf_gemv_res<false,4,4>", "k_pf_gemv_res<false,4,8>",
-                      "k_pf_gemv_res<true,1,2>", "k_pf_gemv_res<true,1,4>", "k_pf_gemv_res<true,2,2>",
-                      "k_pf_gemv_res<true,2,4>", "k_pf_gemv_res<true,4,2>", "k_pf_gemv_res<true,4,4>"},
-    "k_pf_cls": {"k_pf_cls<false,4>", "k_pf_cls<false,8>", "k_pf_cls<true,4>"},
-}
+W16_PASS, EXISTING = wc.PASS_W16_COMPILED, wc.PASS_COMPILED_BEFORE
 
 
 def test_hook_is_in_the_table():
     build.build_lib()
     assert "KH_W16_PASS".startswith(_ffi._HOOK_PREFIXES)  # sync_env mirrors it from the environment
     assert _ffi.debug_get("KH_W16_PASS") is None
-    try:
-        _ffi.debug_set("KH_W16_PASS", "0x5")
+    with wc.hook("KH_W16_PASS", "0x5"):
         assert _ffi.debug_get("KH_W16_PASS") == "0x5"
-    finally:
-        _ffi.debug_set("KH_W16_PASS", None)
     assert _ffi.debug_get("KH_W16_PASS") is None
 
 
@@ -53,6 +31,7 @@ def test_w16_info_abi():
 def test_pass_kernels_in_the_code_objects():
     assert co.tools_present(), "the LLVM tools of the ROCm install are needed to read the library's code objects"
     notes = co.code_object_notes(build.build_lib())
+    assert set(W16_PASS) == wc.PASS["w16"] and set(EXISTING) == wc.PASS_F32
     assert sum(len(v) for v in W16_PASS.values()) == 21
     for stem, want in W16_PASS.items():
         got = co.instantiations(notes, {stem})
