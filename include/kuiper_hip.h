@@ -325,11 +325,16 @@ typedef struct kh_model_opts {
  * second arena with the low nibbles of wq, wk, wv, wo, w1, w2, w3 of every layer and of wcls, two values per byte
  * (half the int8 matrix bytes more HBM; the fp32 group scales are read where the image keeps them), and the decode
  * GEMVs of the adopted launch classes (kh_plan_q4) stream it through kernels that run the int8 kernels' FMAs in their
- * order.  The int8 image stays and everything else reads it: the B-token passes, the MFMA GEMM prefill, the wide pass,
- * the operator level and the embedding gather.  Nothing is ever rounded: one value outside [-8, 7] and the copy is
+ * order.  The B-token passes (prefill, score, verify, the sequence-slot calls) of the classes in the pass mask stream
+ * the copy as well, through twins that leave the int8 pass's bits; the mask is KH_Q4_PASS's, independent of the decode
+ * classes, and by default w2 alone (the one class that passed the adoption rule on every measured geometry: DESIGN
+ * 3.1d).  The int8
+ * image stays and everything else reads it: the MFMA GEMM prefill, the wide pass, the operator level and the embedding
+ * gather.  Nothing is ever rounded: one value outside [-8, 7] and the copy is
  * freed and the model behaves as if the flag were not set; likewise on fp32 images (KH_FLAG_W16* on an int8 image
  * does nothing either).  Hooks at creation: KH_Q4=1 / 0 overrides the flag, KH_Q4_CLASSES=<mask> the adopted
- * classes.  kh_model_q4_info reports. */
+ * classes, KH_Q4_PASS=<mask> the classes whose B-token pass reads the copy (0x1f: all five; unset or 1: the default;
+ * no effect without a live copy).  kh_model_q4_info reports. */
 #define KH_FLAG_Q4 64
 /* GEMM16: the GEMM pass of a W16 model on the bf16 matrix cores, fp32-accurate (csrc/kh_gemm_w16.h).  Takes effect only
  * where the model holds a live 16-bit copy in bf16 format (KH_FLAG_W16, or KH_FLAG_W16_F16 on a bf16-exact image) and
@@ -412,7 +417,9 @@ int kh_model_w16_info(kh_model* m, int64_t* out8);
 /* Q4 (KH_FLAG_Q4): out[8] = state (0 off or not applicable, 1 on, -1 a value lies outside [-8, 7], -2 the creation-time
  * self-check failed - in both cases the model launches what it launches without the flag), bytes of the 4-bit copy,
  * its build time in us, bit mask of the launch classes that run on it (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), index of
- * the first inexact tensor (7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: wcls; -1 none); slots 5 - 7 are 0. */
+ * the first inexact tensor (7 * layer + {wq, wk, wv, wo, w1, w2, w3}, 7 * layers: wcls; -1 none), bit mask of the launch
+ * classes whose B-token passes (prefill, score, verify, sequence slots) run on the copy - hook KH_Q4_PASS, whatever the
+ * first mask says, 0 unless state is 1; slots 6 and 7 are 0. */
 int kh_model_q4_info(kh_model* m, int64_t* out8);
 /* GEMM16 (KH_FLAG_GEMM16): out[8] = state (1: some class of the GEMM pass runs on the bf16 matrix cores, 0: inert), bit
  * mask of those classes (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), the reason where inert (0 none, 1 flag not set, 2 no W16

@@ -11,8 +11,8 @@
 #include "kh_w16.h"
 #include "kh_model_internal.h"
 
-// The _q4 kernels by name only (kh_q4.h, which kh_model_q4.hip includes: a unit that includes it compiles its
-// k_q4_build, and only that unit is to)
+// The _q4 kernels by name only (kh_q4.h: a unit that includes it compiles its k_q4_build, and only the two units that
+// instantiate kernels on the view - kh_model_q4.hip, kh_model_q4_pass.hip - are to)
 template <int U, int MAXV, int SPLIT>
 __global__ __launch_bounds__(KH_WG_MAX, 4) void k_qkv_q4(const KhQkvArgs a);
 template <int U, int MAXV, int SPLIT>
@@ -53,7 +53,7 @@ void copy_release(kh_model::WCopy& w);  // frees the arena; no class runs on the
     else                                      \
       go(KH_KERNEL(K##_w16, __VA_ARGS__));    \
   } while (0)
-// ... or <stem>_q4, by the source (the B-token passes have no _q4 kernels: kh_pf_launch.h stays with KH_W16_TWIN)
+// ... or <stem>_q4, by the source (the decode launches below and the B-token pass launches of kh_pf_launch.h)
 #define KH_COPY_TWIN(SRC, go, K, ...)         \
   do {                                        \
     if constexpr (SRC == KH_SRC_Q4)           \

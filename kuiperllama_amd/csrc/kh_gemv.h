@@ -160,6 +160,7 @@ struct Gemv;
 template <int U>
 struct Gemv<false, U> {
   static constexpr int kU = U;
+  static constexpr bool kLayoutQ8 = false;  // the staged vector: plain fp32 (true: the four q8_slot planes)
   using Regs = RegsF32<U>;
   using Rows = RowsF32;
   int Mc;  // chunks per row in 16-byte units: M/4
@@ -189,6 +190,7 @@ struct Gemv<false, U> {
 template <int U>
 struct Gemv<true, U> {
   static constexpr int kU = U;
+  static constexpr bool kLayoutQ8 = true;
   using Regs = RegsQ8<U>;
   using Rows = RowsQ8;
   int Mc;  // M/16

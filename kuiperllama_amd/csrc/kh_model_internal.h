@@ -1,5 +1,5 @@
 // kh_model_internal.h — state and cross-unit helpers of the model level of the C-ABI.
-// The model level is split into twelve translation units:
+// The model level is split into fourteen translation units:
 //   kh_model_load.hip     .bin image -> HBM arena, weight table, buffers, create / destroy, cache I/O
 //   kh_model_step.hip     launch shapes, the fused and unfused decode step, hipGraph capture,
 //                         predict / generate (kh_fused.h kernels are instantiated here: one list of values per
@@ -21,6 +21,7 @@
 //                         (kh_copy_launch.h: one launch text; the _w16 kernels of kh_w16.h are instantiated here)
 //   kh_model_q4.hip       the 4-bit copy of a 4-bit-exact int8 model's matrices (the same launch text; the kh_q4.h
 //                         kernels are instantiated here)
+//   kh_model_q4_pass.hip  ... and its B-token passes (kh_pf_launch.h's launch text; the _q4 kernels of kh_q4_pass.h)
 //   kh_model_h16.hip      the same launch text for a 16-bit copy in fp16 format (KH_FLAG_W16_F16; the _h16 kernels of kh_w16.h)
 //   kh_model_h16_pass.hip ... and its B-token passes (the _h16 kernels of kh_w16_pass.h)
 // gfx950 only.  No CPU fallback: every path launches HIP kernels.
@@ -344,10 +345,14 @@ struct kh_model {
   };
   W16 w16;
   // Q4 (kh_q4.h, kh_model_q4.hip; KH_FLAG_Q4 / hook KH_Q4): the low nibbles of every int8 matrix value of a 4-bit-exact
-  // int8 model, two per byte (state -1: some value lies outside [-8, 7]).  The group scales stay where they are;
-  // everything but the decode launches reads the int8 image.  classes: plan_q4, hook KH_Q4_CLASSES.
+  // int8 model, two per byte (state -1: some value lies outside [-8, 7]).  The group scales stay where they are.  The
+  // decode launches of `classes` (plan_q4, hook KH_Q4_CLASSES) and the B-token passes of `pass_classes` read the copy;
+  // the GEMM passes and whatever is in neither mask read the int8 image.
   struct Q4 : WCopy {
     int nparts_image = 0;   // m->nparts of the int8 launches (the ring classifier's grid), for a copy that is given up
+    // classes whose B-token pass reads the copy (kh_q4_pass.h; hook KH_Q4_PASS): the copy holds every matrix, so the mask
+    // does not depend on `classes`; 0 unless the copy is live
+    int pass_classes = 0;
   };
   Q4 q4;
 };
@@ -396,6 +401,17 @@ enum { KH_GEMM16_ON = 0, KH_GEMM16_NO_FLAG = 1, KH_GEMM16_NO_W16 = 2, KH_GEMM16_
        KH_GEMM16_FP16_COPY = 5, KH_GEMM16_GEOMETRY = 6, KH_GEMM16_NO_CLASS = 7, KH_GEMM16_SELFCHECK = 8 };
 // the B-token pass of the class (kh_model_prefill.hip: launch_pf_pass, pf_gemv_res, launch_pf_cls)
 static inline bool w16_pass_runs(const kh_model* m, int cls) { return (m->w16.pass_classes & cls) != 0; }
+// classes whose B-token pass reads the 4-bit copy unless KH_Q4_PASS says otherwise: the ones 3.1c's adoption rule keeps
+// on both geometries of the same-box A/B (tools/q4_pass_ab.py, profiles/q4_pass_ab.txt).  w2 alone: in
+// both runs a prefill pass takes -0.8 % at Llama-2-7B int8 geometry (2.814 -> 2.791 ms) and -0.4 % at TinyLlama's
+// (0.825 -> 0.822 ms), each beyond the range of the int8 runs; wo and qkv pass at TinyLlama's in one run of two, ffn13
+// and cls in none (the pass is bound by its LDS reads and FMAs, not by the weight bytes)
+enum { KH_Q4_PASS_DEFAULT = KH_W16_W2 };
+static inline bool q4_pass_runs(const kh_model* m, int cls) { return (m->q4.pass_classes & cls) != 0; }
+// what the B-token pass of the class streams its matrices from (an image is fp32 or int8, so at most one copy is live)
+static inline KhOn pass_runs_on(const kh_model* m, int cls) {
+  return q4_pass_runs(m, cls) ? KH_ON_Q4 : (w16_pass_runs(m, cls) ? KH_ON_W16 : KH_ON_IMAGE);
+}
 void launch_qkv(kh_model* m, int l, KhOn on);
 void launch_attn(kh_model* m, int l, int variant, bool fenced);
 void launch_wo(kh_model* m, int l, int variant, KhOn on);

@@ -1,10 +1,10 @@
 // kh_model_prefill.hip — prompt phase of the model level: the B-token VALU pass (kh_prefill.h, bit-identical to
 // token-by-token; ONE layer driver, launch_pf_pass) and what runs on it - the prompt prefill, sequence scoring
 // (kh_model_score: k_pf_cls, k_score_lp), the verify pass of speculative decode (kh_model_verify[_as_set]: k_pf_cls,
-// kh_spec.h) and the pass over lanes of different sequences (kh_seq.h; kh_model_seq.hip drives it); for a W16 model
-// the launch classes of its pass mask run on the 16-bit copy (kh_w16_pass.h, the w16_pf_* launchers).  What runs on
-// the GEMM slabs lives in kh_model_gemm.hip.  The reference feeds the prompt one token per forward pass
-// (demo/main.cpp:20-22).
+// kh_spec.h) and the pass over lanes of different sequences (kh_seq.h; kh_model_seq.hip drives it); for a W16 or a Q4
+// model the launch classes of its pass mask run on the 16-bit / 4-bit copy (kh_w16_pass.h, kh_q4_pass.h; the
+// pf_*_on launchers below).  What runs on the GEMM slabs lives in kh_model_gemm.hip.  The reference feeds the prompt
+// one token per forward pass (demo/main.cpp:20-22).
 // gfx950 only.
 #include <stdio.h>
 #include <stdlib.h>
@@ -86,20 +86,26 @@ int ensure_prefill_buffers(kh_model* m) {
   m->pf_ws = std::move(ws);
   return KH_OK;
 }
-// ---- the twins on the 16-bit copy (kh_pf_launch.h): this translation unit compiles the _w16 kernels; an fp16-format
-// copy goes to kh_model_h16_pass.hip, which compiles the _h16 kernels from the same launch text
+// ---- the twins on a copy (kh_pf_launch.h; on: KH_ON_W16 or KH_ON_Q4, `img`: the image's arguments): this translation
+// unit compiles the _w16 kernels; an fp16-format copy goes to kh_model_h16_pass.hip and the 4-bit copy to
+// kh_model_q4_pass.hip, which compile the _h16 and the _q4 kernels from the same launch text
 inline bool f16_copy(const kh_model* m) { return m->w16.format == KH_W16_F16; }
-void w16_pf_qkv(kh_model* m, int l, const KhPfQkvArgs& fp32, const KhSeqLanes* lanes, int B) {
-  f16_copy(m) ? h16_pf_qkv(m, l, fp32, lanes, B) : w16_pf_qkv_fmt<KH_W16_BF16>(m, l, fp32, lanes, B);
+void pf_qkv_on(kh_model* m, KhOn on, int l, const KhPfQkvArgs& img, const KhSeqLanes* lanes, int B) {
+  if (on == KH_ON_Q4) return q4_pf_qkv(m, l, img, lanes, B);
+  f16_copy(m) ? h16_pf_qkv(m, l, img, lanes, B) : copy_pf_qkv<KH_SRC_BF16>(m, l, img, lanes, B);
 }
-void w16_pf_ffn13(kh_model* m, int l, const KhPfFfn13Args& fp32, int B) {
-  f16_copy(m) ? h16_pf_ffn13(m, l, fp32, B) : w16_pf_ffn13_fmt<KH_W16_BF16>(m, l, fp32, B);
+void pf_ffn13_on(kh_model* m, KhOn on, int l, const KhPfFfn13Args& img, int B) {
+  if (on == KH_ON_Q4) return q4_pf_ffn13(m, l, img, B);
+  f16_copy(m) ? h16_pf_ffn13(m, l, img, B) : copy_pf_ffn13<KH_SRC_BF16>(m, l, img, B);
 }
-void w16_pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& fp32, int bs) {
-  f16_copy(m) ? h16_pf_gemv_res(m, l, cls, sh, fp32, bs) : w16_pf_gemv_res_fmt<KH_W16_BF16>(m, l, cls, sh, fp32, bs);
+void pf_gemv_res_on(kh_model* m, KhOn on, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& img,
+                    int bs) {
+  if (on == KH_ON_Q4) return q4_pf_gemv_res(m, l, cls, sh, img, bs);
+  f16_copy(m) ? h16_pf_gemv_res(m, l, cls, sh, img, bs) : copy_pf_gemv_res<KH_SRC_BF16>(m, l, cls, sh, img, bs);
 }
-void w16_pf_cls(kh_model* m, const KhPfClsArgs& fp32, int B) {
-  f16_copy(m) ? h16_pf_cls(m, fp32, B) : w16_pf_cls_fmt<KH_W16_BF16>(m, fp32, B);
+void pf_cls_on(kh_model* m, KhOn on, const KhPfClsArgs& img, int B) {
+  if (on == KH_ON_Q4) return q4_pf_cls(m, img, B);
+  f16_copy(m) ? h16_pf_cls(m, img, B) : copy_pf_cls<KH_SRC_BF16>(m, img, B);
 }
 // y = W.v ; X += y for the nvalid tokens of the chunk, in sub-batches of the largest of 8/4/2
 // tokens (<= bmax) whose input vectors fit LDS.  w: layer l's wo (cls = KH_W16_WO) or w2 (KH_W16_W2)
@@ -113,12 +119,13 @@ void pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const K
   a.M = M;
   a.K = K;
   a.gshift = m->gshift;
+  const KhOn on = pass_runs_on(m, cls);  // the image, the 16-bit copy or the 4-bit copy
   for (int t0 = 0; t0 < nvalid; t0 += bs) {
     a.V = V + (size_t)t0 * M;
     a.X = X + (size_t)t0 * K;
     a.nvalid = nvalid - t0 < bs ? nvalid - t0 : bs;
-    if (w16_pass_runs(m, cls)) {  // the same shape on the 16-bit copy
-      w16_pf_gemv_res(m, l, cls, sh, a, bs);
+    if (on != KH_ON_IMAGE) {  // the same shape on the copy
+      pf_gemv_res_on(m, on, l, cls, sh, a, bs);
       continue;
     }
     pick_pf<PfGemvResB, PfGemvResSP>(q, sh.split, bs, [&](auto Q, auto SP, auto B) {
@@ -197,8 +204,8 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
   for (int l = 0; l < c.layer_num; ++l) {
     const LayerW& W = m->layers[l];
     // the instantiations of k_seq_qkv are k_pf_qkv's (PfB x PfQkvSP)
-    if (w16_pass_runs(m, KH_W16_QKV)) {  // the same shape on the 16-bit copy
-      w16_pf_qkv(m, l, pf_qkv_args(m, l, p), p.lanes, B);
+    if (const KhOn on = pass_runs_on(m, KH_W16_QKV); on != KH_ON_IMAGE) {  // the same shape on the copy
+      pf_qkv_on(m, on, l, pf_qkv_args(m, l, p), p.lanes, B);
     } else {
       pick_pf<PfB, PfQkvSP>(q, m->sh_qkv.split, B, [&](auto Q, auto SP, auto BB) {
         const size_t lds = pf_lds_bytes(Q, c.dim, BB);
@@ -246,8 +253,8 @@ void launch_pf_pass(kh_model* m, const PfPass& p) {
       a.gshift = m->gshift;
       a.nvalid = nvalid;
       a.eps = c.rms_eps;
-      if (w16_pass_runs(m, KH_W16_FFN13))
-        w16_pf_ffn13(m, l, a, B);
+      if (const KhOn on = pass_runs_on(m, KH_W16_FFN13); on != KH_ON_IMAGE)
+        pf_ffn13_on(m, on, l, a, B);
       else
         pick_pf<PfB, PfNoSP>(q, 1, B, [&](auto Q, auto, auto BB) {
           pf_launch(KH_KERNEL(k_pf_ffn13, Q, BB), m->sh_ffn, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
@@ -277,7 +284,7 @@ void launch_pf_cls(kh_model* m, int nvalid, int B) {
   a.gshift = m->gshift;
   a.nvalid = nvalid;
   a.eps = c.rms_eps;
-  if (w16_pass_runs(m, KH_W16_CLS)) return w16_pf_cls(m, a, B);
+  if (const KhOn on = pass_runs_on(m, KH_W16_CLS); on != KH_ON_IMAGE) return pf_cls_on(m, on, a, B);
   pick_pf<PfB, PfNoSP>(c.is_quant, 1, B, [&](auto Q, auto, auto BB) {
     pf_launch(KH_KERNEL(k_pf_cls, Q, BB), m->sh_cls, pf_lds_bytes(Q, c.dim, BB), m->stream, a);
   });

@@ -1,7 +1,8 @@
 // kh_model_q4.hip — Q4 at the model level: the packed 4-bit copy of a 4-bit-exact int8 model's matrices (plan, range
-// check, release, the class mask) and kh_model_q4_info.  The bytes, the build and the launch routing of a copy are
-// kh_model_w16.hip's, shared with W16; the launch text is kh_copy_launch.h's, instantiated here for KH_SRC_Q4, which
-// compiles the kh_q4.h kernels here and nowhere else.  Each launch is the int8 launch of kh_model_step.hip with the
+// check, release, the class masks of decode and of the B-token passes) and kh_model_q4_info.  The bytes, the build and
+// the launch routing of a copy are kh_model_w16.hip's, shared with W16; the launch text is kh_copy_launch.h's,
+// instantiated here for KH_SRC_Q4, which compiles the kh_q4.h kernels here and nowhere else (the pass kernels of
+// kh_q4_pass.h: kh_model_q4_pass.hip).  Each launch is the int8 launch of kh_model_step.hip with the
 // same shape (split, u, grid, wg - a shape forced through KH_SHAPE_* included) on the Q4 twin of its kernel, so the
 // bits do not change.
 // Replaces nothing in the reference (it streams int8 weights: kuiper/source/op/kernels/cuda/matmul_kernel.cu:56-87).
@@ -42,6 +43,7 @@ void q4_release(kh_model* m) {
   kh_model::Q4& q = m->q4;
   if (q.classes & KH_W16_CLS) m->nparts = q.nparts_image;  // the int8 classifier launch's partials again
   copy_release(q);
+  q.pass_classes = 0;
 }
 
 // Hook KH_Q4_CLASSES, read at creation: unset - the plan's classes; a number (strtol, base 0: 0x1f, 12, 0x1 for qkv
@@ -49,6 +51,16 @@ void q4_release(kh_model* m) {
 static int q4_class_mask(int planned) {
   const char* hook = dbg("KH_Q4_CLASSES");
   return hook ? (int)strtol(hook, nullptr, 0) & KH_W16_ALL : planned;
+}
+
+// Which classes run their B-token pass (kh_q4_pass.h) on the copy.  Hook KH_Q4_PASS, read at creation: unset or 1 -
+// KH_Q4_PASS_DEFAULT; 0 - none (the passes stream int8 while decode reads the copy); any other number (strtol, base 0:
+// 0x1f all, 0x1 qkv alone) - a mask of KH_W16_* bits.  Whatever KH_Q4_CLASSES says: the copy holds every matrix, and a
+// 4-token pass has another balance than the short decode launches that kept qkv and wo on int8.
+static int q4_pass_mask() {
+  const char* hook = dbg("KH_Q4_PASS");
+  if (!hook || strcmp(hook, "1") == 0) return KH_Q4_PASS_DEFAULT;
+  return (int)strtol(hook, nullptr, 0) & KH_W16_ALL;
 }
 
 // All or nothing: one value outside [-8, 7] anywhere and the model launches what it launches without the flag.
@@ -93,10 +105,11 @@ int q4_create(kh_model* m) {
   q.bytes = bytes;
   copy_configure<KH_SRC_Q4>(m);
   q.classes = classes;
+  q.pass_classes = q4_pass_mask();  // no launch here: the pass kernels' LDS opt-in is pf_clip_grid's, at their first launch
   q.state = 1;
   if (dbg("KH_LOAD_DEBUG") || dbg("KH_SHAPE_DEBUG"))
-    fprintf(stderr, "[kh] Q4: %.1f MiB 4-bit copy of %d matrices in %.0f us, classes 0x%x\n", (double)bytes / (1 << 20),
-            7 * c.layer_num + 1, (double)q.build_us, (unsigned)classes);
+    fprintf(stderr, "[kh] Q4: %.1f MiB 4-bit copy of %d matrices in %.0f us, classes 0x%x, pass classes 0x%x\n",
+            (double)bytes / (1 << 20), 7 * c.layer_num + 1, (double)q.build_us, (unsigned)classes, (unsigned)q.pass_classes);
   return KH_OK;
 }
 
@@ -113,7 +126,7 @@ extern "C" int kh_plan_q4(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32
   return KH_OK;
 }
 
-// out[0..4] = state, bytes, build us, class mask, first inexact tensor
+// out[0..5] = state, bytes, build us, class mask, first inexact tensor, class mask of the B-token passes
 extern "C" int kh_model_q4_info(kh_model* m, int64_t* out) {
   if (!m || !out) return KH_ERR_INVALID_ARG;
   memset(out, 0, 8 * sizeof(int64_t));
@@ -122,5 +135,6 @@ extern "C" int kh_model_q4_info(kh_model* m, int64_t* out) {
   out[2] = (int64_t)m->q4.build_us;
   out[3] = m->q4.classes;
   out[4] = m->q4.first_inexact;
+  out[5] = m->q4.pass_classes;
   return KH_OK;
 }

@@ -1,7 +1,8 @@
-// kh_pf_launch.h — how a B-token kernel (kh_prefill.h, kh_seq.h, kh_w16_pass.h) is launched: the grid clipped to one
-// resident round, the instantiation lists, and the launches of the twins on the 16-bit copy, written once for both
-// formats of the copy (kh_w16.h: KH_W16_BF16 -> the _w16 kernels, compiled by kh_model_prefill.hip; KH_W16_F16 -> the
-// _h16 kernels, compiled by kh_model_h16_pass.hip).  Host code only.
+// kh_pf_launch.h — how a B-token kernel (kh_prefill.h, kh_seq.h, kh_w16_pass.h, kh_q4_pass.h) is launched: the grid
+// clipped to one resident round, the instantiation lists, and the launches of the twins on a narrow exact copy, written
+// once over the source of kh_copy_launch.h (KH_SRC_BF16 -> the _w16 kernels, compiled by kh_model_prefill.hip;
+// KH_SRC_F16 -> the _h16 kernels, compiled by kh_model_h16_pass.hip; KH_SRC_Q4 -> the _q4 kernels of kh_q4_pass.h,
+// compiled by kh_model_q4_pass.hip).  Host code only.
 // Replaces nothing in the reference (it feeds the prompt one token per forward pass: demo/main.cpp:20-22).
 #pragma once
 #include <vector>
@@ -10,6 +11,18 @@
 #include "kh_model_internal.h"
 #include "kh_copy_launch.h"
 #include "kh_w16_pass.h"
+
+// The _q4 pass kernels by name only (kh_q4_pass.h, which kh_model_q4_pass.hip includes: the unit that compiles them)
+template <int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_qkv_q4(const KhPfQkvArgs a);
+template <int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_seq_qkv_q4(const KhSeqQkvArgs a);
+template <int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_ffn13_q4(const KhPfFfn13Args a);
+template <int SPLIT, int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_gemv_res_q4(const KhPfGemvResArgs a);
+template <int B>
+__global__ __launch_bounds__(KH_WG_MAX) void k_pf_cls_q4(const KhPfClsArgs a);
 
 namespace khm {
 
@@ -73,16 +86,17 @@ void pick_pf(bool quant, int sp, int b, F&& f) {
     kh_pick(SPS{}, sp, [&](auto SP) { kh_pick_ge(BS<decltype(Q)::value>{}, b, [&](auto B) { f(Q, SP, B); }); });
   });
 }
-// ---- the twins on the 16-bit copy (kh_w16_pass.h): `fp32` as the fp32 launch fills it, the matrices of layer l
-// replaced by their 16-bit copies, on the fp32 launch's shape, LDS bytes (the plain layout) and clipped grid - the fp32
-// lists without their int8 level, as pick_copy of kh_copy_launch.h
+// ---- the twins on a copy (kh_w16_pass.h, kh_q4_pass.h): `img` as the image's launch fills it, the matrices of layer l
+// replaced by their copies (copy_of<SRC>: the 16-bit or the 4-bit arena), on the image's launch shape, LDS bytes (the
+// layout of the image's kind: kh_src_quant<SRC>) and clipped grid - the lists at the ONE level of QUANT the source has,
+// as pick_copy of kh_copy_launch.h
 template <class SPS, class BS, class F>
-void pick_pf_w16(int sp, int b, F&& f) {
+void pick_pf_copy(int sp, int b, F&& f) {
   kh_pick(SPS{}, sp, [&](auto SP) { kh_pick_ge(BS{}, b, [&](auto B) { f(SP, B); }); });
 }
 // the logged, clipped launch of one twin
 template <class A>
-struct PfW16Go {
+struct PfCopyGo {
   const kh_model::Shape& sh;
   size_t lds;
   hipStream_t stream;
@@ -92,58 +106,68 @@ struct PfW16Go {
     pf_launch(kernel, stem, targs, sh, lds, stream, a);
   }
 };
-template <int FMT>
-void w16_pf_qkv_fmt(kh_model* m, int l, const KhPfQkvArgs& fp32, const KhSeqLanes* lanes, int B) {
-  KhPfQkvArgs a = fp32;
-  const kh_model::W16::Layer& W = m->w16.layers[(size_t)l];
+template <int SRC>
+void copy_pf_qkv(kh_model* m, int l, const KhPfQkvArgs& img, const KhSeqLanes* lanes, int B) {
+  constexpr bool Q = kh_src_quant<SRC>;
+  KhPfQkvArgs a = img;
+  const kh_model::WCopy::Layer& W = copy_of<SRC>(m).layers[(size_t)l];
   a.wq.w = W.wq;
   a.wk.w = W.wk;
   a.wv.w = W.wv;
-  pick_pf_w16<PfQkvSP, PfB<false>>(m->sh_qkv.split, B, [&](auto SP, auto BB) {
-    const size_t lds = pf_lds_bytes(false, a.dim, BB);
+  pick_pf_copy<PfQkvSP, PfB<Q>>(m->sh_qkv.split, B, [&](auto SP, auto BB) {
+    const size_t lds = pf_lds_bytes(Q, a.dim, BB);
     if (lanes) {
       const KhSeqQkvArgs sa{a, *lanes};
-      const PfW16Go<KhSeqQkvArgs> go{m->sh_qkv, lds, m->stream, sa};
-      KH_W16_TWIN(FMT, go, k_seq_qkv, SP, BB);
+      const PfCopyGo<KhSeqQkvArgs> go{m->sh_qkv, lds, m->stream, sa};
+      KH_COPY_TWIN(SRC, go, k_seq_qkv, SP, BB);
     } else {
-      const PfW16Go<KhPfQkvArgs> go{m->sh_qkv, lds, m->stream, a};
-      KH_W16_TWIN(FMT, go, k_pf_qkv, SP, BB);
+      const PfCopyGo<KhPfQkvArgs> go{m->sh_qkv, lds, m->stream, a};
+      KH_COPY_TWIN(SRC, go, k_pf_qkv, SP, BB);
     }
   });
 }
-template <int FMT>
-void w16_pf_ffn13_fmt(kh_model* m, int l, const KhPfFfn13Args& fp32, int B) {
-  KhPfFfn13Args a = fp32;
-  a.w1.w = m->w16.layers[(size_t)l].w1;
-  a.w3.w = m->w16.layers[(size_t)l].w3;
-  pick_pf_w16<PfNoSP, PfB<false>>(1, B, [&](auto, auto BB) {
-    const PfW16Go<KhPfFfn13Args> go{m->sh_ffn, pf_lds_bytes(false, a.dim, BB), m->stream, a};
-    KH_W16_TWIN(FMT, go, k_pf_ffn13, BB);
+template <int SRC>
+void copy_pf_ffn13(kh_model* m, int l, const KhPfFfn13Args& img, int B) {
+  constexpr bool Q = kh_src_quant<SRC>;
+  KhPfFfn13Args a = img;
+  a.w1.w = copy_of<SRC>(m).layers[(size_t)l].w1;
+  a.w3.w = copy_of<SRC>(m).layers[(size_t)l].w3;
+  pick_pf_copy<PfNoSP, PfB<Q>>(1, B, [&](auto, auto BB) {
+    const PfCopyGo<KhPfFfn13Args> go{m->sh_ffn, pf_lds_bytes(Q, a.dim, BB), m->stream, a};
+    KH_COPY_TWIN(SRC, go, k_pf_ffn13, BB);
   });
 }
 // cls: KH_W16_WO or KH_W16_W2; bs: the sub-batch pf_gemv_res chose
-template <int FMT>
-void w16_pf_gemv_res_fmt(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& fp32, int bs) {
-  KhPfGemvResArgs a = fp32;
-  a.w.w = cls == KH_W16_WO ? m->w16.layers[(size_t)l].wo : m->w16.layers[(size_t)l].w2;
-  pick_pf_w16<PfGemvResSP, PfGemvResB<false>>(sh.split, bs, [&](auto SP, auto B) {
-    const PfW16Go<KhPfGemvResArgs> go{sh, pf_lds_bytes(false, a.M, B), m->stream, a};
-    KH_W16_TWIN(FMT, go, k_pf_gemv_res, SP, B);
+template <int SRC>
+void copy_pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& img, int bs) {
+  constexpr bool Q = kh_src_quant<SRC>;
+  KhPfGemvResArgs a = img;
+  const kh_model::WCopy::Layer& W = copy_of<SRC>(m).layers[(size_t)l];
+  a.w.w = cls == KH_W16_WO ? W.wo : W.w2;
+  pick_pf_copy<PfGemvResSP, PfGemvResB<Q>>(sh.split, bs, [&](auto SP, auto B) {
+    const PfCopyGo<KhPfGemvResArgs> go{sh, pf_lds_bytes(Q, a.M, B), m->stream, a};
+    KH_COPY_TWIN(SRC, go, k_pf_gemv_res, SP, B);
   });
 }
-template <int FMT>
-void w16_pf_cls_fmt(kh_model* m, const KhPfClsArgs& fp32, int B) {
-  KhPfClsArgs a = fp32;
-  a.wcls.w = m->w16.cls;
-  pick_pf_w16<PfNoSP, PfB<false>>(1, B, [&](auto, auto BB) {
-    const PfW16Go<KhPfClsArgs> go{m->sh_cls, pf_lds_bytes(false, a.dim, BB), m->stream, a};
-    KH_W16_TWIN(FMT, go, k_pf_cls, BB);
+template <int SRC>
+void copy_pf_cls(kh_model* m, const KhPfClsArgs& img, int B) {
+  constexpr bool Q = kh_src_quant<SRC>;
+  KhPfClsArgs a = img;
+  a.wcls.w = copy_of<SRC>(m).cls;
+  pick_pf_copy<PfNoSP, PfB<Q>>(1, B, [&](auto, auto BB) {
+    const PfCopyGo<KhPfClsArgs> go{m->sh_cls, pf_lds_bytes(Q, a.dim, BB), m->stream, a};
+    KH_COPY_TWIN(SRC, go, k_pf_cls, BB);
   });
 }
-// kh_model_h16_pass.hip: the four above for KH_W16_F16
-void h16_pf_qkv(kh_model* m, int l, const KhPfQkvArgs& fp32, const KhSeqLanes* lanes, int B);
-void h16_pf_ffn13(kh_model* m, int l, const KhPfFfn13Args& fp32, int B);
-void h16_pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& fp32, int bs);
-void h16_pf_cls(kh_model* m, const KhPfClsArgs& fp32, int B);
+// kh_model_h16_pass.hip: the four above for KH_SRC_F16 ...
+void h16_pf_qkv(kh_model* m, int l, const KhPfQkvArgs& img, const KhSeqLanes* lanes, int B);
+void h16_pf_ffn13(kh_model* m, int l, const KhPfFfn13Args& img, int B);
+void h16_pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& img, int bs);
+void h16_pf_cls(kh_model* m, const KhPfClsArgs& img, int B);
+// ... and kh_model_q4_pass.hip: for KH_SRC_Q4
+void q4_pf_qkv(kh_model* m, int l, const KhPfQkvArgs& img, const KhSeqLanes* lanes, int B);
+void q4_pf_ffn13(kh_model* m, int l, const KhPfFfn13Args& img, int B);
+void q4_pf_gemv_res(kh_model* m, int l, int cls, const kh_model::Shape& sh, const KhPfGemvResArgs& img, int bs);
+void q4_pf_cls(kh_model* m, const KhPfClsArgs& img, int B);
 
 }  // namespace khm

@@ -32,10 +32,11 @@
 // chunk (16 floats per load), so its tile is kept to 2 loads per row
 #define KH_PF_U(QUANT) ((QUANT) ? 2 : 4)
 // The kernels below are written over the matrix view G (kh_gemv.h: Gemv<QUANT, U>; kh_w16_pass.h runs the same text
-// on GemvW16<U>).  Only the LDS layout of the staged vectors asks "int8 or not": every other view stages plain fp32.
+// on GemvW16<U>, kh_q4_pass.h on GemvQ4<U>).  The LDS layout of the staged vectors is the view's own statement
+// (kLayoutQ8: the four planes of the int8 view, which the 4-bit view reads too; else plain fp32).
 template <class G>
 constexpr bool pf_layout_q8() {
-  return std::is_same<typename G::Regs, RegsQ8<G::kU>>::value;
+  return G::kLayoutQ8;
 }
 
 // ---- B-token FMA of one register chunk --------------------------------------------------------
@@ -115,7 +116,7 @@ __device__ __forceinline__ void fma_chunk_b(const RegsQ8<U>& r, const f32x4* xs,
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-// the overload of the view's register tile (found at instantiation: kh_w16_pass.h adds RegsW16's)
+// the overload of the view's register tile (found at instantiation: kh_w16_pass.h adds RegsW16's, kh_q4_pass.h RegsQ4's)
 template <class G, int B>
 __device__ __forceinline__ void gemv_fma_b(const G& g, const typename G::Regs& r, const f32x4* xs, int xstride, int c0,
                                            int lim, int lane, float (&a0)[B], float (&a1)[B]) {

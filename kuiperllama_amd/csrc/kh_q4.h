@@ -74,6 +74,7 @@ static __device__ __forceinline__ float dot4_q4(uint32_t w, f32x4 x, float acc) 
 template <int U>
 struct GemvQ4 {
   static constexpr int kU = U;
+  static constexpr bool kLayoutQ8 = true;  // the int8 view's staged vector
   using Regs = RegsQ4<U>;
   using Rows = RowsQ4;
   int Mc;  // units per row: M/16

@@ -89,6 +89,7 @@ struct RowsW16 {
 template <int U, int FMT = KH_W16_BF16>
 struct GemvW16 {
   static constexpr int kU = U;
+  static constexpr bool kLayoutQ8 = false;
   using Regs = RegsW16<U, FMT>;
   using Rows = RowsW16;
   int Mc;  // units per row: M/4

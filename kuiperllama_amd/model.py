@@ -355,6 +355,15 @@ class KuiperModel:
                 "classes": [n for i, n in enumerate(_ffi.KH_Q4_CLASSES) if out[3] >> i & 1],
                 "first_inexact": int(out[4])}
 
+    def q4_pass_info(self) -> dict:
+        """The B-token passes of a KH_FLAG_Q4 model (kh_model_q4_info, slot 5): {"classes": the launch classes whose
+        passes - prefill, score, verify / generate_lookup, seq_* and generate_batch* - stream the 4-bit copy}.  The
+        mask is the hook KH_Q4_PASS's at creation, whatever q4_info()["classes"] says (the copy holds every matrix);
+        [] when the passes stream the int8 matrices, and always when the copy is not live."""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_q4_info(self._h, out), "kh_model_q4_info")
+        return {"classes": [n for i, n in enumerate(_ffi.KH_Q4_CLASSES) if out[5] >> i & 1]}
+
     def gemm16_info(self) -> dict:
         """_ffi.KH_FLAG_GEMM16 on this model (kh_model_gemm16_info): {"on": some launch class of the GEMM pass runs on
         the bf16 matrix cores, "classes": those classes, "reason": why the flag does nothing (one of

@@ -27,7 +27,7 @@
 // --w16-f16 = KH_FLAG_W16_F16: the same for an image that is bf16-exact OR fp16-exact (Llama-2's fp16 checkpoints); the
 // format of the copy is printed.
 // --q4 = KH_FLAG_Q4: decode an int8 image whose values all lie in [-8, 7] from a packed 4-bit copy of its matrices, bit
-// for bit (any other image decodes as without the flag); prints kh_model_q4_info.
+// for bit (any other image decodes as without the flag); prints kh_model_q4_info, the pass class mask included.
 // --gemm16 = KH_FLAG_GEMM16 (with --w16 or --w16-f16 on a bf16-exact image): the GEMM prompt phase and the wide batch
 // passes run on the bf16 matrix cores from the 16-bit copy, fp32-accurate (three exact bf16 terms per activation);
 // prints kh_model_gemm16_info.  Inert - and says why - on any other model.
@@ -306,8 +306,12 @@ int main(int argc, char** argv) {
     int64_t w[8] = {0};
     kh_model_q4_info(m, w);
     // state: 0 not applicable (fp32), 1 on, -1 a value lies outside [-8, 7], -2 self-check failed (both: int8 decode)
-    std::fprintf(stderr, "Q4: state %lld, copy %.2f GB built in %.2f ms, launch classes 0x%llx, first inexact tensor %lld\n",
-                 (long long)w[0], (double)w[1] / 1e9, (double)w[2] / 1e3, (unsigned long long)w[3], (long long)w[4]);
+    // pass classes: whose B-token passes (prefill, score, verify, sequence slots) read the copy too (hook KH_Q4_PASS)
+    std::fprintf(stderr,
+                 "Q4: state %lld, copy %.2f GB built in %.2f ms, launch classes 0x%llx, pass classes 0x%llx, first inexact "
+                 "tensor %lld\n",
+                 (long long)w[0], (double)w[1] / 1e9, (double)w[2] / 1e3, (unsigned long long)w[3], (unsigned long long)w[5],
+                 (long long)w[4]);
   }
   if (o.flags & KH_FLAG_GEMM16) {
     int64_t w[8] = {0};
