@@ -67,6 +67,14 @@ int kh_gemm_w16_f32(const float* x, const uint16_t* w16, float* y, int32_t T, in
                     void* stream);
 int kh_matmul_f32(const float* x, const float* w, float* y, int32_t M, int32_t K, float scale,
                   void* stream);
+/* y[t][0 .. M) = sum over groups g of scales[m][g] * (w8[m][64g .. 64g + 64) . x[t][64g .. 64g + 64)) for t < T, on the
+ * bf16 matrix cores, fp32-accurate (csrc/kh_gemm_q16.h: the K loop of KH_FLAG_GEMM16_Q8 under its STORE epilogue): w8 is
+ * int8, row-major [M][K], group size 64, scales[M][K / 64]; every int8 value is an exact bf16, every x splits exactly into
+ * three bf16 terms, products are exact, accumulation is fp32 and the group scale multiplies the group's partial sum.  y
+ * has row stride ldy >= M.  M % 16 == 0, K % 64 == 0 and T <= 512, else KH_ERR_UNSUPPORTED; 16-byte aligned pointers,
+ * ldy % 4 == 0.  Allocates a staging copy of x and synchronises the stream. */
+int kh_gemm_q8_bf16_f32(const float* x, const int8_t* w8, const float* scales, float* y, int32_t T, int32_t M, int32_t K,
+                        int32_t ldy, void* stream);
 
 /* MatmulKernelQuant (kernels_interface.h:12-14; cuda/matmul_kernel.cu:56-87,111-134):
  * y[p] = sum_i x[i] * scales[(p*M+i)/group_size] * float(w8[p*M+i]) */
@@ -348,6 +356,19 @@ typedef struct kh_model_opts {
  * the same model without the flag - on an fp16-format copy, an int8 model, an image that is not bf16-exact, and without
  * a W16 flag.  Hook KH_GEMM16=1 / 0 at creation overrides the flag.  kh_model_gemm16_info reports. */
 #define KH_FLAG_GEMM16 128
+/* GEMM16_Q8: the GEMM pass of an int8 group-64 model on the bf16 matrix cores, fp32-accurate, from the int8 image itself
+ * (csrc/kh_gemm_q16.h): no weight copy, no extra memory.  The GEMMs of kh_model_prefill_gemm (and the default prompt path
+ * of kh_model_generate), kh_model_seq_prefill_gemm, kh_model_seq_step_gemm and kh_model_generate_batch_gemm convert the
+ * int8 weights exactly to bf16 in registers, split every fp32 activation exactly into three bf16 terms and multiply the
+ * fp32 partial sum of each group of 64 columns by the group's scale: six v_mfma_f32_16x16x32_bf16 per group instead of
+ * sixteen v_mfma_f32_16x16x4_f32.  kh_model_prefill_gemm's int8 contract (exact products, fp32 accumulation) in another
+ * summation order and without the per-weight rounding of scale * q: not the bits of the int8 kernels.  Per launch class
+ * (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls): a class the adoption mask leaves out (kh_plan_gemm16_q8; hook
+ * KH_GEMM16_Q8_CLASSES=<mask> at creation) keeps its int8 kernel.  Inert - the launches and bits of the same model
+ * without the flag - on an fp32 model, a group size other than 64 and a geometry the GEMM prefill does not take.
+ * Independent of KH_FLAG_Q4 (the GEMM passes of a Q4 model read the int8 image) and of KH_FLAG_GEMM16 (inert on int8).
+ * Hook KH_GEMM16_Q8=1 / 0 at creation overrides the flag.  kh_model_gemm16_q8_info reports. */
+#define KH_FLAG_GEMM16_Q8 256
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -427,6 +448,11 @@ int kh_model_q4_info(kh_model* m, int64_t* out8);
  * view, 7 no class left by the mask and the K % 32 rule, 8 the copy's creation-time self-check failed), kh_plan_gemm16's
  * mask for the geometry (0 where inert before the plan); slots 4 - 7 are 0. */
 int kh_model_gemm16_info(kh_model* m, int64_t* out8);
+/* GEMM16_Q8 (KH_FLAG_GEMM16_Q8): out[8] = state (1: some class of the GEMM pass runs on the bf16 matrix cores from the
+ * int8 image, 0: inert), bit mask of those classes (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), the reason where inert (0 none,
+ * 1 flag not set, 2 fp32 model, 3 group size is not 64, 4 geometry off the GEMM prefill, 5 no class left by the mask),
+ * kh_plan_gemm16_q8's mask for the geometry (0 where inert before the plan); slots 4 - 7 are 0. */
+int kh_model_gemm16_q8_info(kh_model* m, int64_t* out8);
 /* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
  * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave
  * every row.  out4 = screened token, full classifier's token, candidate rows re-scored, 1 if the step overflowed.
@@ -953,6 +979,11 @@ int kh_plan_q4(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_si
  * KH_FLAG_GEMM16 for this geometry (0: int8, or dims the GEMM prefill does not take): the adoption mask among the
  * classes whose contraction length (dim; w2: hidden_dim) is a multiple of 32, columns of a K block (32)}. */
 int kh_plan_gemm16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t is_quant, int64_t* out2);
+/* kh_plan_gemm16_q8: out2 = {bit mask of the launch classes whose GEMMs of the GEMM pass run on the bf16 matrix cores
+ * from the int8 image under KH_FLAG_GEMM16_Q8 for this geometry by default (0: fp32, a group size other than 64, or dims
+ * the int8 GEMM prefill does not take), columns of a K block (64)}. */
+int kh_plan_gemm16_q8(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t is_quant,
+                      int32_t group_size, int64_t* out2);
 int kh_plan_attention(int32_t head_num, int32_t kv_mul, int32_t head_size, int32_t seq_len, int32_t pos,
                       int32_t* out8);
 /* kh_plan_attention_launch: ONE decode-attention launch over the tokens at positions pos[0 .. n) of that geometry (a

@@ -15,19 +15,19 @@ LIB_PATH = os.environ.get("KH_LIB") or os.path.join(_PKG, "lib", "libkuiper_hip.
 # every symbol include/kuiper_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "kh_error_string", "kh_version", "kh_device_count",
-    "kh_add_f32", "kh_matmul_f32", "kh_gemm_w16_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
+    "kh_add_f32", "kh_matmul_f32", "kh_gemm_w16_f32", "kh_gemm_q8_bf16_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
     "kh_mha_decode_workspace_bytes", "kh_argmax_f32", "kh_argmax_rows_f32",
     "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
-    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
+    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_gemm16_q8_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
     "kh_spm_create_from_file", "kh_spm_create_from_memory", "kh_spm_destroy", "kh_spm_vocab_size",
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
     "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_model_verify_as_set", "kh_model_generate_lookup_as_set", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
-    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_q4", "kh_plan_gemm16", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
+    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_q4", "kh_plan_gemm16", "kh_plan_gemm16_q8", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
     "kh_plan_seq_prefill_gemm", "kh_model_seq_prefill_gemm",
@@ -52,6 +52,9 @@ KH_FLAG_GEMM16 = 128  # the GEMM pass of a W16 model on the bf16 matrix cores, f
 # kh_model_gemm16_info, slot 2: why the flag does nothing on a model
 KH_GEMM16_REASONS = ("on", "flag not set", "no W16 flag", "int8 model", "image not bf16-exact", "fp16-format copy",
                      "geometry", "no class", "self-check failed")
+KH_FLAG_GEMM16_Q8 = 256  # the GEMM pass of an int8 group-64 model on the bf16 matrix cores (KuiperModel.gemm16_q8_info)
+# kh_model_gemm16_q8_info, slot 2: why the flag does nothing on a model
+KH_GEMM16_Q8_REASONS = ("on", "flag not set", "fp32 model", "group size not 64", "geometry", "no class")
 KH_Q4_CLASSES = KH_W16_CLASSES  # bit i of a class mask (kh_model_q4_info, kh_plan_q4, hook KH_Q4_CLASSES)
 KH_LOGPROBS_MAX_TOP = 20
 KH_SEQ_BIAS_MAX = 64
@@ -204,6 +207,9 @@ def lib() -> C.CDLL:
     L.kh_model_gemm16_info.argtypes = [_vp, C.POINTER(_i64)]
     L.kh_plan_gemm16.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
     L.kh_gemm_w16_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
+    L.kh_model_gemm16_q8_info.argtypes = [_vp, C.POINTER(_i64)]
+    L.kh_plan_gemm16_q8.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
+    L.kh_gemm_q8_bf16_f32.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
     L.kh_plan_q4.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
     L.kh_model_get_kv.argtypes = [_vp, C.POINTER(_vp), C.POINTER(_vp)]
     L.kh_model_kv_bytes.argtypes = [_vp, C.POINTER(_i64), C.POINTER(_i64)]
@@ -442,6 +448,17 @@ def plan_gemm16(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quant: 
     rc = lib().kh_plan_gemm16(dim, hidden_dim, kv_dim, vocab_size, int(quant), out)
     if rc != 0:
         raise KhError(rc, "kh_plan_gemm16")
+    return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
+
+
+def plan_gemm16_q8(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quant: bool, group_size: int = 64) -> dict:
+    """KH_FLAG_GEMM16_Q8 for a geometry (host-only, kh_plan_gemm16_q8): {"classes": the launch classes whose GEMMs of the
+    GEMM pass run on the bf16 matrix cores from the int8 image by default - [] for fp32, for a group size other than 64
+    and for dims the int8 GEMM prefill does not take -, "kblock": 64}."""
+    out = (_i64 * 2)()
+    rc = lib().kh_plan_gemm16_q8(dim, hidden_dim, kv_dim, vocab_size, int(quant), group_size, out)
+    if rc != 0:
+        raise KhError(rc, "kh_plan_gemm16_q8")
     return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
 
 

@@ -15,10 +15,10 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libkuiper_hip.so")
-SOURCES = ["kh_ops.hip", "kh_model_load.hip", "kh_model_step.hip", "kh_model_prefill.hip", "kh_model_gemm.hip", "kh_model_gemm_w16.hip", "kh_model_seq.hip", "kh_model_profile.hip", "kh_model_selftest.hip", "kh_model_screen.hip", "kh_model_w16.hip",
+SOURCES = ["kh_ops.hip", "kh_model_load.hip", "kh_model_step.hip", "kh_model_prefill.hip", "kh_model_gemm.hip", "kh_model_gemm_w16.hip", "kh_model_gemm_q16.hip", "kh_model_seq.hip", "kh_model_profile.hip", "kh_model_selftest.hip", "kh_model_screen.hip", "kh_model_w16.hip",
            "kh_model_h16.hip", "kh_model_h16_pass.hip", "kh_model_q4.hip", "kh_model_q4_pass.hip",
            "kh_tokenizer.cpp", "kh_bpe.cpp", "kh_debug.cpp"]
-HEADERS = ["kh_common.h", "kh_gemv.h", "kh_attn.h", "kh_fused.h", "kh_q8ring.h", "kh_fused_ring.h", "kh_prefill.h", "kh_gemm.h", "kh_gemm_body.h", "kh_gemm_w16.h", "kh_pattn.h", "kh_pattn_body.h", "kh_sample.h", "kh_step_tail.h", "kh_logit_proc.h", "kh_logprobs.h", "kh_cls_screen.h", "kh_w16.h", "kh_w16_pass.h", "kh_copy_launch.h", "kh_q4.h", "kh_q4_pass.h", "kh_pf_launch.h", "kh_unicode_tables.h",
+HEADERS = ["kh_common.h", "kh_gemv.h", "kh_attn.h", "kh_fused.h", "kh_q8ring.h", "kh_fused_ring.h", "kh_prefill.h", "kh_gemm.h", "kh_gemm_body.h", "kh_gemm_w16.h", "kh_gemm_q16.h", "kh_pattn.h", "kh_pattn_body.h", "kh_sample.h", "kh_step_tail.h", "kh_logit_proc.h", "kh_logprobs.h", "kh_cls_screen.h", "kh_w16.h", "kh_w16_pass.h", "kh_copy_launch.h", "kh_q4.h", "kh_q4_pass.h", "kh_pf_launch.h", "kh_unicode_tables.h",
            "kh_model_internal.h", "kh_buf.h", "kh_dispatch.h", "kh_score_plan.h", "kh_spec.h", "kh_lookup.h", "kh_seq.h", "kh_seq_plan.h", "kh_seq_gemm.h", "kh_seq_prefill.h",
            "../../include/kuiper_hip.h"]
 ARCH = "gfx950"

@@ -303,6 +303,10 @@ __device__ __forceinline__ void pg_kloop_q8(const int8_t* const (&wrow)[R],
 template <int R, int NT>
 __device__ __forceinline__ void pg_kloop_w16(const uint16_t* const (&wrow)[R], const PgBAddr& B, int b0, int b1,
                                              f32x4 (&acc)[R][NT]);
+// (the K loop of kh_gemm_q16.h on the int8 image, which the body names under KH_GEMM_Q16)
+template <int R, int NT>
+__device__ __forceinline__ void pg_kloop_q16(const int8_t* const (&wrow)[R], const float* const (&srow)[R],
+                                             const PgBAddr& B, int b0, int b1, f32x4 (&acc)[R][NT]);
 struct PgRunAddr {
   int pos0;
   __device__ __forceinline__ int pos(int tok) const { return pos0 + tok; }
@@ -312,7 +316,7 @@ template <bool QUANT, int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX(QUANT)) void k_pg_gemm(const KhPgGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI != KH_PG_STORE, "the classifier epilogue is the wide sequence pass's (k_sg_gemm)");
-  constexpr bool KH_GEMM_W16 = false;
+  constexpr bool KH_GEMM_W16 = false, KH_GEMM_Q16 = false;
   const PgRunAddr addr{a.pos0};
 #include "kh_gemm_body.h"
 }

@@ -4,6 +4,7 @@
 // EPI> with QUANT a constant - and has in scope
 //   constexpr bool KH_GEMM_W16   the K loop: false - pg_kloop_f32 / pg_kloop_q8 on the image; true - pg_kloop_w16
 //                           (kh_gemm_w16.h) on the 16-bit copy
+//   constexpr bool KH_GEMM_Q16   with QUANT: pg_kloop_q16 (kh_gemm_q16.h) on the int8 image in place of pg_kloop_q8
 //   const KhPgGemmArgs a    its first kernel argument
 //   addr                    the token addressing of the QKV epilogue: addr.pos(tok) = the RoPE row, addr.row(tok) = the
 //                           cache row of token tok (PgRunAddr, SgLaneAddr)
@@ -98,10 +99,13 @@
     const int b1 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)(kpart + 1) * (z1 - z0) / ks));
     const int8_t* wrow[R];
     const float* srow[R];
+    // the scale a lane loads: pg_kloop_q8 scales the weights of row i; pg_kloop_q16 (kh_gemm_q16.h) scales the partial
+    // sums, and the lane's quad shares the scales of the rows 4h .. 4h + 3 its accumulators hold
+    const int si = KH_GEMM_Q16 ? 4 * h + (i & 3) : i;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       wrow[r] = (const int8_t*)W.w + (size_t)(wr0 + rstep * r + i) * K + 16 * h;
-      srow[r] = W.scales + (size_t)(wr0 + rstep * r + i) * nb;
+      srow[r] = W.scales + (size_t)(wr0 + rstep * r + si) * nb;
     }
     if (a.b_tiled) {
       B = PgBAddr{a.B + (size_t)(tok0 + i) * 16 + 4 * h, 256, (size_t)4 * a.tcap * 16,
@@ -109,7 +113,11 @@
     } else {
       B = PgBAddr{a.B + (size_t)(tok0 + i) * K + 16 * h, (size_t)16 * K, 64, 4};
     }
-    if (b1 > b0) pg_kloop_q8<R, NT>(wrow, srow, B, b0, b1, acc);
+    if constexpr (KH_GEMM_Q16) {
+      if (b1 > b0) pg_kloop_q16<R, NT>(wrow, srow, B, b0, b1, acc);
+    } else {
+      if (b1 > b0) pg_kloop_q8<R, NT>(wrow, srow, B, b0, b1, acc);
+    }
   }
   // ---- combine the K slices (fixed order) and run the epilogue on float4 = 4 rows x 1 token,
   //      one 16-row tile at a time (the LDS area holds one tile row of partials) -------------------

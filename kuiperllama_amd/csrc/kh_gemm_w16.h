@@ -124,7 +124,7 @@ template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_pg_gemm_w16(const KhPgGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI != KH_PG_STORE, "the classifier epilogue is the wide sequence pass's (k_sg_gemm_w16)");
-  constexpr bool QUANT = false, KH_GEMM_W16 = true;
+  constexpr bool QUANT = false, KH_GEMM_W16 = true, KH_GEMM_Q16 = false;
   const PgRunAddr addr{a.pos0};
 #include "kh_gemm_body.h"
 }
@@ -132,14 +132,14 @@ template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_rg_gemm_w16(const KhPgGemmArgs a, const KhRgTiles tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI == KH_PG_QKV, "the other GEMMs of the pass are k_pg_gemm_w16's");
-  constexpr bool QUANT = false, KH_GEMM_W16 = true;
+  constexpr bool QUANT = false, KH_GEMM_W16 = true, KH_GEMM_Q16 = false;
   const RgTileAddr addr{tiles};
 #include "kh_gemm_body.h"
 }
 template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_sg_gemm_w16(const KhPgGemmArgs a, const KhWideLanes lanes) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  constexpr bool QUANT = false, KH_GEMM_W16 = true;
+  constexpr bool QUANT = false, KH_GEMM_W16 = true, KH_GEMM_Q16 = false;
   const SgLaneAddr addr{lanes};
 #include "kh_gemm_body.h"
 }

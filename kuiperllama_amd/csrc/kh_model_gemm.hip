@@ -130,8 +130,10 @@ inline bool pg_kz_on() { return !dbg_off("KH_PG_KZ"); }
 //     its MFMAs, so - like int8 - it gains from a partner wave on the SIMD and `solo` only costs: 512-token prefill with
 //     KH_PG_SOLO=0 against the default, Llama-3.2-1B 6.14 vs 6.32 ms, Llama-2-7B 39.4 vs 41.1 ms, Qwen2.5-0.5B 4.82 vs
 //     6.29 ms (profiles/gemm16_shape_sweep.txt).  Everything else of the model is the fp32 fit, unchanged.
+//   * the int8 loop on the bf16 matrix cores (kh_gemm_q16.h; tile28 = false) has no (2,8) register tile: the model picks
+//     among the other three, with the int8 fit otherwise unchanged.
 PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min_blocks, bool quant, bool allow_kz,
-                 bool allow_solo = true) {
+                 bool allow_solo = true, bool tile28 = true) {
   const int nt_all = (T + 15) / 16;
   const bool wide = nt_all > 8;  // a pass of more than 128 tokens
   PgShape best{1, 4, 1, (nt_all + 3) / 4, false, 1};
@@ -140,7 +142,7 @@ PgShape pg_shape(int T, int rows_total, bool r2_ok, int nm, int kblocks, int min
     const int R = c[0], NT = c[1], occ = c[2];
     if (R == 2 && !r2_ok) continue;
     if (R == 1 && quant && r2_ok) continue;  // int8: the 32-row tile measured better wherever it fits
-    if (NT > 4 && nt_all <= 4) continue;     // no 128-token tile for <= 64 tokens
+    if (NT > 4 && (nt_all <= 4 || !tile28)) continue;  // no 128-token tile for <= 64 tokens
     const int slices = (nt_all + NT - 1) / NT;
     for (int kz = 1; kz <= (allow_kz && pg_kz_on() ? KH_PG_KZ_MAX : 1); kz *= 2)
     for (int ks = 1; ks * nm * 64 <= KH_PG_WG_MAX(quant); ks *= 2) {
@@ -206,12 +208,14 @@ namespace {
 // epi: KH_PG_*; STORE (the classifier GEMM of the wide sequence pass) plans as a residual GEMM without a K split
 // across workgroups.
 // kcols: the columns of a K block of the loop that runs - 16 fp32, 64 int8, 32 on the 16-bit copy (kh_gemm_w16.h)
-PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K, int kcols) {
+// q16: the int8 loop on the bf16 matrix cores runs (kh_gemm_q16.h): no (2,8) tile - a hook that asks for it gets (2,4)
+PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K, int kcols, bool q16 = false) {
   const bool q = m->cfg.is_quant;
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
   const bool w16 = kcols == 32;
   // (min_blocks: the same 256 columns per wave as fp32's 16 blocks of 16)
-  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / kcols, q ? 4 : (w16 ? 8 : 16), q, EPI == KH_PG_RESID, !w16);
+  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / kcols, q ? 4 : (w16 ? 8 : 16), q, EPI == KH_PG_RESID, !w16 && !q16,
+                           !q16);
   {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE>="R,NT,ks[,kz]" overrides the heuristic
     static const char* const names[4] = {"KH_PG_SHAPE_QKV", "KH_PG_SHAPE_RESID", "KH_PG_SHAPE_SWIGLU",
                                          "KH_PG_SHAPE_STORE"};
@@ -222,6 +226,7 @@ PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, i
           (ks == 1 || ks == 2 || ks == 4 || ks == 8) && ks * nm * 64 <= KH_PG_WG_MAX(q) &&
           (kz == 1 || (EPI == KH_PG_RESID && (kz == 2 || kz == 4))))
       {
+        if (q16 && NT > 4) NT = 4;
         const int slices = ((T + 15) / 16 + NT - 1) / NT;
         sh = PgShape{R, NT, ks, slices,
                      !q && !w16 && (T > 128 || R * NT >= 16) && pg_solo_on() &&
@@ -303,6 +308,7 @@ inline int pg_lane_groups(const PgPass& p) { return (p.n + KH_PF_BMAX - 1) / KH_
 // on16: the GEMM's launch class (KH_W16_*) and its matrices in the 16-bit copy.  Where the class runs on the bf16 matrix
 // cores (KH_FLAG_GEMM16: gemm16_runs) the same shape - planned in blocks of 32 columns - launches the _w16 stem
 // (kh_gemm_w16.h, compiled in kh_model_gemm_w16.hip) with the weight pointers swapped; everything else is untouched.
+// An int8 group-64 model under KH_FLAG_GEMM16_Q8 (gemm16_q8_runs) launches the _q16 stem on the image's own pointers.
 struct PgOn16 {
   int cls;
   const void* w[3];
@@ -311,7 +317,8 @@ template <int EPI>
 int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmArgs a, bool* ok, const PgOn16& on16) {
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
   const bool w16 = gemm16_runs(m, on16.cls);
-  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K, w16 ? 32 : (m->cfg.is_quant ? 64 : 16));
+  const bool q16 = gemm16_q8_runs(m, on16.cls);  // (an int8 model: never both)
+  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K, w16 ? 32 : (m->cfg.is_quant ? 64 : 16), q16);
   if (p.lanes && sh.NT > 4) {  // a hook asked for the 128-token tile
     sh.NT = 4;
     sh.slices = ((a.T + 15) / 16 + 3) / 4;
@@ -330,6 +337,11 @@ int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmAr
       if (on16.w[j]) a.w[j].w = on16.w[j];
     const int t = tile >= 0 ? tile : (sh.R == 2 ? 2 : 3);
     launched = pg_gemm_w16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
+                                  p.lanes);
+  } else if (q16) {
+    // the int8 image's own weight and scale pointers, on the _q16 stem (kh_gemm_q16.h, compiled in kh_model_gemm_q16.hip)
+    const int t = tile >= 1 ? tile : (sh.R == 2 ? 2 : 3);
+    launched = pg_gemm_q16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
                                   p.lanes);
   } else {
     kh_pick_bool(m->cfg.is_quant, [&](auto Q) {

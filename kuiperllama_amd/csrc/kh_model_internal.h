@@ -10,6 +10,8 @@
 //   kh_model_gemm.hip     what runs on the GEMM slabs (kh_gemm.h, kh_pattn.h, kh_seq_prefill.h, kh_seq_gemm.h kernels):
 //                         the MFMA prompt prefill, its form into sequence slots and the wide sequence pass
 //   kh_model_gemm_w16.hip the same GEMMs on the bf16 matrix cores from the 16-bit copy (KH_FLAG_GEMM16; kh_gemm_w16.h kernels)
+//   kh_model_gemm_q16.hip the GEMMs of an int8 group-64 model on the bf16 matrix cores from the int8 image (KH_FLAG_GEMM16_Q8;
+//                         kh_gemm_q16.h kernels)
 //   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
 //                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
@@ -355,6 +357,16 @@ struct kh_model {
     int pass_classes = 0;
   };
   Q4 q4;
+  // KH_FLAG_GEMM16_Q8 / hook KH_GEMM16_Q8 (kh_gemm_q16.h, kh_model_gemm_q16.hip): classes whose GEMMs of the
+  // GEMM pass (kh_model_gemm.hip: pg_gemm) run on the bf16 matrix cores from the int8 image itself - an int8 group-64
+  // model on the GEMM prefill's geometry and the adoption mask (plan_gemm16_q8, hook KH_GEMM16_Q8_CLASSES); 0 wherever
+  // the flag is inert, and reason says why (KH_GEMM16_Q8_*: kh_model_gemm16_q8_info).  No copy, no memory.
+  struct Gemm16Q8 {
+    int classes = 0;
+    int reason = 0;
+    int plan = 0;           // plan_gemm16_q8's mask for the geometry, whatever the hook says (0 unless the flag is live)
+  };
+  Gemm16Q8 g16q8;
 };
 
 #define KH_GRAPH_STEPS 8
@@ -399,6 +411,11 @@ static inline bool gemm16_runs(const kh_model* m, int cls) { return m->w16.state
 // why KH_FLAG_GEMM16 does nothing on a model (kh_model_gemm16_info, slot 2); KH_GEMM16_ON: it does something
 enum { KH_GEMM16_ON = 0, KH_GEMM16_NO_FLAG = 1, KH_GEMM16_NO_W16 = 2, KH_GEMM16_QUANT = 3, KH_GEMM16_INEXACT = 4,
        KH_GEMM16_FP16_COPY = 5, KH_GEMM16_GEOMETRY = 6, KH_GEMM16_NO_CLASS = 7, KH_GEMM16_SELFCHECK = 8 };
+// the GEMM pass of the class on the bf16 matrix cores from the int8 image (KH_FLAG_GEMM16_Q8; kh_model_gemm.hip: pg_gemm)
+static inline bool gemm16_q8_runs(const kh_model* m, int cls) { return (m->g16q8.classes & cls) != 0; }
+// why KH_FLAG_GEMM16_Q8 does nothing on a model (kh_model_gemm16_q8_info, slot 2); KH_GEMM16_Q8_ON: it does something
+enum { KH_GEMM16_Q8_ON = 0, KH_GEMM16_Q8_NO_FLAG = 1, KH_GEMM16_Q8_FP32 = 2, KH_GEMM16_Q8_GROUP = 3,
+       KH_GEMM16_Q8_GEOMETRY = 4, KH_GEMM16_Q8_NO_CLASS = 5 };
 // the B-token pass of the class (kh_model_prefill.hip: launch_pf_pass, pf_gemv_res, launch_pf_cls)
 static inline bool w16_pass_runs(const kh_model* m, int cls) { return (m->w16.pass_classes & cls) != 0; }
 // classes whose B-token pass reads the 4-bit copy unless KH_Q4_PASS says otherwise: the ones 3.1c's adoption rule keeps
@@ -610,6 +627,14 @@ struct PgW16Launch {  // one GEMM of a pass as pg_gemm planned it, on the k_*_ge
 // token addressing (both null: a run).  false: the LDS opt-in was refused (nothing launched)
 bool pg_gemm_w16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemmArgs& a, const KhRgTiles* tiles,
                         const KhWideLanes* lanes);
+// ---- kh_model_gemm_q16.hip ------------------------------------------------------------------
+// the same launch on the k_*_gemm_q16 kernels (kh_gemm_q16.h): a is the int8 image launch's own.  The stem has no (2,8)
+// register tile: the caller plans without it
+bool pg_gemm_q16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemmArgs& a, const KhRgTiles* tiles,
+                        const KhWideLanes* lanes);
+// classes that run on it by default for a geometry (0: not an int8 group-64 model the GEMM prefill takes)
+int plan_gemm16_q8(bool quant, int group_size, int dim, int hidden_dim, int kv_dim, int vocab_size);
+void gemm16_q8_configure(kh_model* m);  // at creation
 // kh_model_prefill_gemm without the token record (hist_write); prefill_gemm_prepare: its slabs, made by the call
 // itself or ahead of it by whoever times it
 int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);

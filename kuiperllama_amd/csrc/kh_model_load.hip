@@ -677,6 +677,7 @@ static int create_from_device_weights_impl(const int32_t* h_header, const void* 
   rc = finish_create(m);
   if (rc == KH_OK) rc = w16_create(m);  // KH_FLAG_W16: the 16-bit copy of a bf16-exact model's matrices
   if (rc == KH_OK) rc = q4_create(m);   // KH_FLAG_Q4: the 4-bit copy of a 4-bit-exact int8 model's matrices
+  if (rc == KH_OK) gemm16_q8_configure(m);  // KH_FLAG_GEMM16_Q8: the GEMM passes of an int8 group-64 model on bf16 MFMAs
   if (rc == KH_OK) rc = cls_screen_create(m);
   if (rc == KH_OK) rc = run_selftests(m);  // the weights are resident: ring kernels / split merge against their fallbacks
   if (rc != KH_OK) {
@@ -756,6 +757,7 @@ static int create_from_host_image_impl(const void* h_image, size_t nbytes, const
   pc.lap("upload || buffers, joined");
   if (rc == KH_OK) rc = w16_create(m);  // the arena is resident: the 16-bit copy of a bf16-exact model's matrices (KH_FLAG_W16)
   if (rc == KH_OK) rc = q4_create(m);  // ... or the 4-bit copy of a 4-bit-exact int8 model's (KH_FLAG_Q4)
+  if (rc == KH_OK) gemm16_q8_configure(m);  // (KH_FLAG_GEMM16_Q8)
   pc.lap("W16 / Q4 copy");
   if (rc == KH_OK) rc = cls_screen_create(m);  // the arena is resident: bf16 copy of the classifier (fp32 models)
   pc.lap("bf16 classifier copy");

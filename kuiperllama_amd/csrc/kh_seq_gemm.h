@@ -31,7 +31,7 @@ struct SgLaneAddr {
 template <bool QUANT, int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX(QUANT)) void k_sg_gemm(const KhPgGemmArgs a, const KhWideLanes lanes) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  constexpr bool KH_GEMM_W16 = false;
+  constexpr bool KH_GEMM_W16 = false, KH_GEMM_Q16 = false;
   const SgLaneAddr addr{lanes};
 #include "kh_gemm_body.h"
 }

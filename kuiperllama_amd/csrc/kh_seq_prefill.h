@@ -48,7 +48,7 @@ template <bool QUANT, int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX(QUANT)) void k_rg_gemm(const KhPgGemmArgs a, const KhRgTiles tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI == KH_PG_QKV, "the other GEMMs of the pass are k_pg_gemm's");
-  constexpr bool KH_GEMM_W16 = false;
+  constexpr bool KH_GEMM_W16 = false, KH_GEMM_Q16 = false;
   const RgTileAddr addr{tiles};
 #include "kh_gemm_body.h"
 }

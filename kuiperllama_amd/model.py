@@ -375,6 +375,17 @@ class KuiperModel:
                 "reason": _ffi.KH_GEMM16_REASONS[out[2]],
                 "plan": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1]}
 
+    def gemm16_q8_info(self) -> dict:
+        """_ffi.KH_FLAG_GEMM16_Q8 on this model (kh_model_gemm16_q8_info): {"on": some launch class of the GEMM pass runs
+        on the bf16 matrix cores from the int8 image, "classes": those classes, "reason": why the flag does nothing (one
+        of _ffi.KH_GEMM16_Q8_REASONS; "on" where it does), "plan": the classes kh_plan_gemm16_q8 adopts for the geometry}."""
+        out = (_ffi._i64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_gemm16_q8_info(self._h, out), "kh_model_gemm16_q8_info")
+        return {"on": bool(out[0]),
+                "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[1] >> i & 1],
+                "reason": _ffi.KH_GEMM16_Q8_REASONS[out[2]],
+                "plan": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1]}
+
     def w16_pass_info(self) -> dict:
         """The B-token passes of a KH_FLAG_W16 model (kh_model_w16_info, slot 5): {"classes": the launch classes whose
         passes - prefill, score, verify / generate_lookup, seq_* and generate_batch* - stream the 16-bit copy}, a

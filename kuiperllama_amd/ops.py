@@ -60,6 +60,22 @@ def gemm_w16(x, w16, out=None):
     return out
 
 
+def gemm_q8_bf16(x, w8, scales, out=None):
+    """out[T, M] = x[T, K] @ (scales * w8)[M, K]^T on the bf16 matrix cores, fp32-accurate (kh_gemm_q8_bf16_f32): w8 is
+    int8 [M, K] in groups of 64 columns, scales fp32 [M, K / 64]; M % 16 == 0, K % 64 == 0, T <= 512.  out may be a
+    [T, ldy >= M] buffer: columns past M keep their bytes."""
+    T, K = x.shape
+    M, K2 = w8.shape
+    if K2 != K or tuple(scales.shape) != (M, K // 64):
+        raise ValueError("gemm_q8_bf16: w8 must be [M, K] int8 and scales [M, K / 64]")
+    if out is None:
+        out = torch.empty((T, M), dtype=torch.float32, device=x.device)
+    _ffi.check(_ffi.lib().kh_gemm_q8_bf16_f32(_p(x, torch.float32), _p(w8, torch.int8), _p(scales, torch.float32),
+                                              _p(out, torch.float32), T, M, K, out.stride(0), _stream()),
+               "kh_gemm_q8_bf16_f32")
+    return out
+
+
 def matmul_q8(x, w8, scales, group_size: int, out):
     K, M = w8.shape
     _ffi.check(_ffi.lib().kh_matmul_q8(_p(x, torch.float32), _p(w8, torch.int8),

@@ -12,7 +12,7 @@
 //               [--theta 10000] [--eps 1e-5] [--steps 128] [--prompt 1,263] [--stop 2]
 //               [--exec graph|fused|unfused] [--max-seq-len N] [--device 0]
 //               [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json [--hf-spaces]] [--text "a"]
-//               [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16] [--q4] [--gemm16]
+//               [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16] [--q4] [--gemm16] [--gemm16-q8]
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
@@ -31,6 +31,9 @@
 // --gemm16 = KH_FLAG_GEMM16 (with --w16 or --w16-f16 on a bf16-exact image): the GEMM prompt phase and the wide batch
 // passes run on the bf16 matrix cores from the 16-bit copy, fp32-accurate (three exact bf16 terms per activation);
 // prints kh_model_gemm16_info.  Inert - and says why - on any other model.
+// --gemm16-q8 = KH_FLAG_GEMM16_Q8 (an int8 group-64 image): the GEMM prompt phase and the wide batch passes run on the bf16
+// matrix cores from the int8 image itself, fp32-accurate; prints kh_model_gemm16_q8_info.  Inert - and says why - on any
+// other model.
 // --temperature / --top-k / --top-p / --seed: seeded sampling instead of the argmax (kh_model_set_sampling; the
 // reference's demo is greedy, which stays the default).
 // --repeat-penalty / --presence-penalty / --frequency-penalty over the last --repeat-last-n fed tokens (0: all of
@@ -103,7 +106,7 @@ static void usage() {
                "       [--theta F] [--eps F] [--steps N] [--prompt id,id,...] [--stop id,id] [--exec graph|fused|unfused]\n"
                "       [--max-seq-len N] [--device D] [--tokenizer tokenizer.model | --tokenizer-json tokenizer.json\n"
                "       [--hf-spaces]] [--text \"...\"] [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16]\n"
-               "       [--q4] [--gemm16]\n"
+               "       [--q4] [--gemm16] [--gemm16-q8]\n"
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
@@ -165,6 +168,7 @@ int main(int argc, char** argv) {
     else if (a == "--w16-f16") o.flags |= KH_FLAG_W16_F16;
     else if (a == "--q4") o.flags |= KH_FLAG_Q4;
     else if (a == "--gemm16") o.flags |= KH_FLAG_GEMM16;
+    else if (a == "--gemm16-q8") o.flags |= KH_FLAG_GEMM16_Q8;
     else if (a == "--temperature") samp.temperature = (float)std::atof(next());
     else if (a == "--top-k") samp.top_k = std::atoi(next());
     else if (a == "--top-p") samp.top_p = (float)std::atof(next());
@@ -319,6 +323,13 @@ int main(int argc, char** argv) {
     // reason: 0 on, 1 flag not set, 2 no W16 flag, 3 int8, 4 image not bf16-exact, 5 fp16-format copy, 6 geometry,
     // 7 no class, 8 self-check failed
     std::fprintf(stderr, "GEMM16: state %lld, classes on the bf16 matrix cores 0x%llx (plan 0x%llx), reason %lld\n",
+                 (long long)w[0], (unsigned long long)w[1], (unsigned long long)w[3], (long long)w[2]);
+  }
+  if (o.flags & KH_FLAG_GEMM16_Q8) {
+    int64_t w[8] = {0};
+    kh_model_gemm16_q8_info(m, w);
+    // reason: 0 on, 1 flag not set, 2 fp32 model, 3 group size not 64, 4 geometry, 5 no class
+    std::fprintf(stderr, "GEMM16_Q8: state %lld, classes on the bf16 matrix cores 0x%llx (plan 0x%llx), reason %lld\n",
                  (long long)w[0], (unsigned long long)w[1], (unsigned long long)w[3], (long long)w[2]);
   }
   rc = kh_model_set_sampling(m, &samp);
