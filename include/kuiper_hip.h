@@ -139,6 +139,27 @@ int kh_mha_prefill_f32(int32_t pos0, int32_t n_tokens, int32_t head_num, int32_t
                        int32_t seq_len, int32_t kv_dim, int32_t kv_mul, int32_t head_size,
                        float* mha_out, const float* q, const float* key_cache,
                        const float* value_cache, void* stream);
+/* The same launch in the output layout a model pass asks for: layout 0 / 1 = the tiled activation slab of an fp32 /
+ * int8 model that the wo GEMM reads (mha_out holds dim * tcap floats; element (token t, column k) of the fp32 slab
+ * sits at ((k / 16) * tcap + t) * 16 + k % 16), layout 2 = row-major as above.  n_tokens <= tcap <= 512 and
+ * tcap % 16 == 0, else KH_ERR_INVALID_ARG; tcap is not read for layout 2 but checked all the same.  Layout 1
+ * interleaves the quarters of 64-column blocks and needs dim % 64 == 0 (KH_ERR_INVALID_ARG). */
+int kh_mha_prefill_layout_f32(int32_t pos0, int32_t n_tokens, int32_t head_num, int32_t layer_index,
+                              int32_t seq_len, int32_t kv_dim, int32_t kv_mul, int32_t head_size,
+                              int32_t layout, int32_t tcap, float* mha_out, const float* q,
+                              const float* key_cache, const float* value_cache, void* stream);
+/* The attention of the prompt prefill into sequence slots (kh_model_seq_prefill_gemm) as an operator: n_tiles
+ * (1 .. 32) query tiles of 16 slab tokens, q is [16 * n_tiles][dim].  h_tiles is a HOST table of 5 x n_tiles int32:
+ * pos0[], nvalid[], base[], pfx_len[], pfx_row0[].  The tokens of tile k are positions pos0[k] .. pos0[k] +
+ * nvalid[k] - 1 (1 <= nvalid <= 16; the other columns of the tile repeat its last valid token and are stored too);
+ * position p of its sequence is cache row pfx_row0[k] + p for p < pfx_len[k] (0 <= pfx_len <= pos0) and row
+ * base[k] + p from there on (base may be negative).  Every such row up to position pos0 + nvalid - 1 must lie in
+ * [0, seq_len), else KH_ERR_RANGE; 16 * n_tiles <= tcap <= 512, tcap % 16 == 0.  Layouts as above (row-major:
+ * [16 * n_tiles][dim]). */
+int kh_mha_prefill_tiles_f32(int32_t n_tiles, const int32_t* h_tiles, int32_t head_num, int32_t layer_index,
+                             int32_t seq_len, int32_t kv_dim, int32_t kv_mul, int32_t head_size,
+                             int32_t layout, int32_t tcap, float* mha_out, const float* q,
+                             const float* key_cache, const float* value_cache, void* stream);
 
 /* The decode-path attention kernel with its long-context machinery.  Per-head path: the grid
  * carries ceil(seq_len/256) (<= 16) workgroups per head; positions < 256 use one of them, longer

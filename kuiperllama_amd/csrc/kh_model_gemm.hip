@@ -660,3 +660,77 @@ extern "C" int kh_mha_prefill_f32(int32_t pos0, int32_t n_tokens, int32_t head_n
   launch_pg_attn(a, head_size, (hipStream_t)stream);
   return kh_launch_status();
 }
+
+namespace {
+// What kh_mha_prefill_f32 checks of the head geometry, the caches and the pointers, for the two entries below; on
+// KH_OK `a` holds everything but the query columns (T, pos0), the layout and tcap.
+int pa_op_args(KhPgAttnArgs& a, int32_t head_num, int32_t layer_index, int32_t seq_len, int32_t kv_dim, int32_t kv_mul,
+               int32_t head_size, float* mha_out, const float* q, const float* key_cache, const float* value_cache) {
+  if (!mha_out || !q || !key_cache || !value_cache) return KH_ERR_INVALID_ARG;
+  if (head_num <= 0 || layer_index < 0 || seq_len <= 0 || kv_mul <= 0 || head_size <= 0 || kv_dim <= 0)
+    return KH_ERR_INVALID_ARG;
+  if (head_num % kv_mul || kv_dim != (head_num / kv_mul) * head_size) return KH_ERR_INVALID_ARG;
+  if (!pg_attn_supported(head_size)) return KH_ERR_UNSUPPORTED;
+  if (((uintptr_t)mha_out | (uintptr_t)q | (uintptr_t)key_cache | (uintptr_t)value_cache) & 15)
+    return KH_ERR_INVALID_ARG;  // 16-byte loads / stores
+  const size_t layer_off = (size_t)layer_index * seq_len * kv_dim;
+  a.q = q; a.kc = key_cache + layer_off; a.vc = value_cache + layer_off; a.out = mha_out;
+  a.dim = head_num * head_size; a.kv_dim = kv_dim; a.kv_heads = head_num / kv_mul; a.kv_mul = kv_mul;
+  return KH_OK;
+}
+bool pa_op_layout(int32_t layout, int32_t tcap, int32_t T, int dim) {
+  if (layout != KH_PA_TILED_F32 && layout != KH_PA_TILED_Q8 && layout != KH_PA_ROWS) return false;
+  // the int8 slab interleaves the quarters of 64-column blocks (pg_tiled_index): a partial block would reach past
+  // dim * tcap floats (an int8 model's dim is a multiple of its group size)
+  if (layout == KH_PA_TILED_Q8 && dim % 64) return false;
+  return T <= tcap && tcap <= KH_PG_TMAX && tcap % 16 == 0;
+}
+}  // namespace
+
+// kh_mha_prefill_f32 in the output layout a model pass asks for (kh_pattn.h: KH_PA_TILED_F32 / KH_PA_TILED_Q8 /
+// KH_PA_ROWS); the tiled layouts write a slab of dim x tcap floats (pg_tiled_index).
+extern "C" int kh_mha_prefill_layout_f32(int32_t pos0, int32_t n_tokens, int32_t head_num, int32_t layer_index,
+                                         int32_t seq_len, int32_t kv_dim, int32_t kv_mul, int32_t head_size,
+                                         int32_t layout, int32_t tcap, float* mha_out, const float* q,
+                                         const float* key_cache, const float* value_cache, void* stream) {
+  KhPgAttnArgs a{};
+  if (n_tokens <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
+  const int rc = pa_op_args(a, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size, mha_out, q, key_cache,
+                            value_cache);
+  if (rc != KH_OK) return rc;
+  if (!pa_op_layout(layout, tcap, n_tokens, a.dim)) return KH_ERR_INVALID_ARG;
+  if ((int64_t)pos0 + n_tokens > seq_len) return KH_ERR_RANGE;
+  a.T = n_tokens; a.pos0 = pos0; a.layout = layout; a.tcap = tcap;
+  launch_pg_attn(a, head_size, (hipStream_t)stream);
+  return kh_launch_status();
+}
+
+// Operator-level entry of the slot prefill's attention (kh_seq_prefill.h: k_rg_attn): n_tiles query tiles of 16 slab
+// tokens each, tile k described by h_tiles[0..5)[k] = pos0, nvalid, base, pfx_len, pfx_row0 (KhRgTiles).  Every cache
+// row a tile may read must lie in [0, seq_len).
+extern "C" int kh_mha_prefill_tiles_f32(int32_t n_tiles, const int32_t* h_tiles, int32_t head_num,
+                                        int32_t layer_index, int32_t seq_len, int32_t kv_dim, int32_t kv_mul,
+                                        int32_t head_size, int32_t layout, int32_t tcap, float* mha_out,
+                                        const float* q, const float* key_cache, const float* value_cache,
+                                        void* stream) {
+  KhPgAttnArgs a{};
+  if (!h_tiles || n_tiles < 1 || n_tiles > KH_RG_TILES) return KH_ERR_INVALID_ARG;
+  const int rc = pa_op_args(a, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size, mha_out, q, key_cache,
+                            value_cache);
+  if (rc != KH_OK) return rc;
+  if (!pa_op_layout(layout, tcap, 16 * n_tiles, a.dim)) return KH_ERR_INVALID_ARG;
+  KhRgTiles tiles;
+  for (int k = 0; k < KH_RG_TILES; ++k) {  // entries no slab token reads: the last tile's
+    const int s = k < n_tiles ? k : n_tiles - 1;
+    const int64_t pos0 = h_tiles[s], nv = h_tiles[n_tiles + s], base = h_tiles[2 * n_tiles + s];
+    const int64_t pfx = h_tiles[3 * n_tiles + s], prow = h_tiles[4 * n_tiles + s];
+    if (nv < 1 || nv > 16 || pos0 < 0 || pfx < 0 || pfx > pos0) return KH_ERR_INVALID_ARG;
+    if (pfx > 0 && (prow < 0 || prow + pfx > seq_len)) return KH_ERR_RANGE;  // rows pfx_row0 + [0, pfx_len)
+    if (base + pfx < 0 || base + pos0 + nv > seq_len) return KH_ERR_RANGE;   // rows base + [pfx_len, pos0 + nvalid)
+    tiles.pos0[k] = (int32_t)pos0; tiles.nvalid[k] = (int32_t)nv; tiles.base[k] = (int32_t)base;
+    tiles.pfx_len[k] = (int32_t)pfx; tiles.pfx_row0[k] = (int32_t)prow;
+  }
+  a.T = 16 * n_tiles; a.pos0 = 0; a.layout = layout; a.tcap = tcap;
+  launch_rg_attn(a, tiles, head_size, (hipStream_t)stream);
+  return kh_launch_status();
+}

@@ -155,6 +155,36 @@ def mha_prefill(pos0, n_tokens, head_num, layer_index, seq_len, kv_dim, kv_mul, 
     return mha_out
 
 
+PA_TILED_F32, PA_TILED_Q8, PA_ROWS = 0, 1, 2  # output layouts of the prompt-slice attention (csrc/kh_pattn.h)
+
+
+def mha_prefill_layout(pos0, n_tokens, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size, layout, tcap,
+                       mha_out, q, kcache, vcache):
+    """mha_prefill in the output layout of a model pass (kh_mha_prefill_layout_f32): PA_TILED_F32 / PA_TILED_Q8 write
+    the tiled slab of dim * tcap floats the wo GEMM reads, PA_ROWS row-major [n_tokens][dim]."""
+    _ffi.sync_env()  # KH_PG_ATTN_QT
+    _ffi.check(_ffi.lib().kh_mha_prefill_layout_f32(
+        int(pos0), int(n_tokens), head_num, layer_index, seq_len, kv_dim, kv_mul, head_size, int(layout), int(tcap),
+        _p(mha_out, torch.float32), _p(q, torch.float32), _p(kcache, torch.float32),
+        _p(vcache, torch.float32), _stream()), "kh_mha_prefill_layout_f32")
+    return mha_out
+
+
+def mha_prefill_tiles(tiles, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size, layout, tcap, mha_out, q,
+                      kcache, vcache):
+    """The slot prefill's attention (kh_mha_prefill_tiles_f32).  tiles: host int32 array [5][n_tiles] - pos0, nvalid,
+    base, pfx_len, pfx_row0 per 16-token query tile; q is [16 * n_tiles][dim]."""
+    import numpy as np
+    t = np.ascontiguousarray(tiles, dtype=np.int32)
+    if t.ndim != 2 or t.shape[0] != 5:
+        raise ValueError("mha_prefill_tiles: tiles must be [5][n_tiles]")
+    _ffi.check(_ffi.lib().kh_mha_prefill_tiles_f32(
+        t.shape[1], t.ctypes.data, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size, int(layout), int(tcap),
+        _p(mha_out, torch.float32), _p(q, torch.float32), _p(kcache, torch.float32),
+        _p(vcache, torch.float32), _stream()), "kh_mha_prefill_tiles_f32")
+    return mha_out
+
+
 def mha_decode_workspace(head_num: int, head_size: int, seq_len: int, device):
     """Zeroed workspace tensor for mha_decode (None when no time split is needed)."""
     _ffi.sync_env()  # KH_ATTN_TLONG

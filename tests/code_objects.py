@@ -3,7 +3,8 @@ the decode GEMV and GEMM-prefill kernels read straight from the Itanium-mangled 
 
 Reads the .hip_fatbin section with the LLVM tools of the ROCm install.  Used by test_code_objects.py (no kernel may
 use scratch), by the coverage gates (every compiled instantiation is launched: test_decode_instantiations_gpu.py,
-test_prefill_gemm_instantiations_gpu.py, test_attention_instantiations_gpu.py, test_cls_screen_instantiations_gpu.py,
+test_prefill_gemm_instantiations_gpu.py, test_attention_instantiations_gpu.py,
+test_prompt_attention_instantiations_gpu.py, test_cls_screen_instantiations_gpu.py,
 test_gemm16_gpu.py and, through wcopy_cases.coverage_gate, the five weight-copy modules), by the CPU modules that pin
 a feature's compiled kernel set (test_w16_pass.py, test_w16_f16.py, test_q4.py, test_gemm16.py, test_seq_gemm.py) and
 by the GPU modules that look a launched kernel up (test_seq_*_gpu.py, test_cls_screen_q8_gpu.py)."""
