@@ -271,6 +271,35 @@ int kh_logit_process_f32(float* logits, int64_t n, const int32_t* d_tokens, cons
 int kh_logprobs_f32(const float* logits, int64_t n, int32_t n_rows, const int32_t* d_ids, int32_t top_n, float* d_lse,
                     float* d_lp, int32_t* d_top_ids, float* d_top_lp, void* stream);
 
+/* Constrained decoding: a TOKEN AUTOMATON is a deterministic automaton over token ids in CSR form.  Row s =
+ * tokens[row_ptr[s] .. row_ptr[s + 1]) holds the ids allowed in state s, strictly ascending, and next[] the state behind
+ * each.  With a state s and a logit vector l[0..V):
+ *   1. every l[v] with v NOT in row s becomes -inf - a logit bias of -inf on exactly those ids;
+ *   2. with t the token picked from the masked vector, s = next(s, t).
+ * -inf stays -inf through all three steps of kh_logit_process_f32 and a bias may not be +inf, so masking AHEAD of the
+ * processors and biasing by -inf BEHIND them leave the same bits in every entry: a constrained step equals an
+ * unconstrained one whose bias list bans the ids outside the row.  The end of the output is part of the automaton:
+ * accepting states carry an edge on the stop token into a sink whose only edge is that token onto itself, so steps
+ * that run past a stop stay legal.
+ * kh_fsm_check, host only, the checks every call that takes an automaton makes before any device call:
+ * KH_ERR_INVALID_ARG for NULL arrays, n_states <= 0, start or any next outside [0, n_states), row_ptr not non-decreasing
+ * from 0, a row that is not strictly ascending, a row with NO edge (the sampler needs one finite logit); KH_ERR_RANGE
+ * for a token outside [0, vocab).
+ * kh_fsm_walk, host only: from `state`, follows tokens[0..n) as far as every token is in the row of the state reached;
+ * *out_state = the state behind the *n_ok tokens it could follow (the state behind words a model returned). */
+typedef struct kh_fsm {
+  int32_t n_states, start;
+  const int64_t* row_ptr;  /* [n_states + 1] */
+  const int32_t* tokens;   /* [n_edges] ascending and distinct within a row, in [0, vocab) */
+  const int32_t* next;     /* [n_edges] state after that token */
+} kh_fsm;
+int kh_fsm_check(const kh_fsm* a, int64_t vocab);
+int kh_fsm_walk(const kh_fsm* a, int32_t state, const int32_t* tokens, int64_t n, int32_t* out_state, int64_t* n_ok);
+/* The mask as an operator, in place: bit v & 31 of word v >> 5 of d_mask (DEVICE, ceil(n / 32) words) clear means
+ * logits[v] = -inf; every other entry keeps its bits; bits past n in the last word are ignored.  Asynchronous,
+ * graph-capturable, never allocates.  KH_ERR_INVALID_ARG for NULL pointers or n <= 0. */
+int kh_token_mask_f32(float* logits, int64_t n, const uint32_t* d_mask, void* stream);
+
 /* CPU-only helpers of the reference (kernels_interface.h:38-46), provided on device so the
  * op set is closed: softmax in place, x *= scale, out += sum_t scale[t]*value[t*stride..] */
 int kh_softmax_f32(float* x, int32_t n, void* stream);
@@ -638,6 +667,41 @@ int kh_model_set_logprobs(kh_model* m, int32_t top_n);
 int kh_model_get_logprobs_setting(const kh_model* m, int32_t* top_n);
 int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32_t* h_token, float* h_lp, int32_t* h_top_ids,
                           float* h_top_lp);
+
+/* The model's constraint (NULL = off, the default of every model): a token automaton (kh_fsm, above) inside the decode
+ * loop - "answer with one of these strings", "emit text that matches this pattern".  The model holds one automaton
+ * state s, a device word: kh_model_set_constraint sets it to `start`, so does the beginning of every kh_model_generate*
+ * call, and kh_model_set_constraint_state sets it to any state.  At every SAMPLED position of kh_model_predict (fused and
+ * unfused), kh_model_generate and kh_model_generate_until the logits outside row s become -inf ahead of the penalties,
+ * the bias, the pick and the log-prob record, and the pick t moves s to next(s, t); forced (prompt) steps and is_prompt
+ * predicts neither mask nor advance.  In every exec mode, with and without a sampler, penalties, a bias and log-probs, the
+ * tokens, logits and records are bit for bit those of a host loop of kh_model_predict on an unconstrained model whose
+ * logit bias is re-set at every step to -inf on the ids outside the row (see kh_fsm for why the order does not matter).
+ * Records come from the masked logits: a banned token has log-prob -inf; kh_model_get_logits and kh_model_first_sample
+ * report the masked logits.  The up to 16 steps kh_model_generate_until runs past a stop move s further: read the state
+ * behind returned words with kh_fsm_walk.
+ * While a constraint is set the step's last launch is k_sample_proc_fsm or, with log-probs on, k_sample_lp_fsm - the
+ * tails of the processors with the mask pass in front and the transition behind the pick: launches_per_token is
+ * unchanged, nothing returns to the host - and the screened classifier is not used; while off the model runs exactly
+ * the launches it runs without this feature.  The automaton lives in device buffers behind one descriptor that the
+ * captured launches read: a new automaton of any size needs no graph recapture.
+ * kh_model_set_constraint copies the automaton; before any device call it makes kh_fsm_check's checks against
+ * vocab_size and returns KH_ERR_INVALID_ARG where some row has every one of its tokens banned by a -inf entry of the
+ * model's logit bias; kh_model_set_logit_bias refuses such a list the same way while a constraint is set.
+ * Memory: beside the CSR arrays the model keeps one mask row of ceil(vocab_size / 32) words per state, on the device and
+ * while the call runs on the host - 16 KiB per state at a vocabulary of 128256; an automaton whose mask table would
+ * exceed KH_FSM_MAX_MASK_BYTES (256 MiB: 16743 states at that vocabulary) is refused with KH_ERR_UNSUPPORTED before any
+ * device call.
+ * kh_model_get_constraint_state synchronises the stream; both state calls return KH_ERR_UNSUPPORTED while the
+ * constraint is off, the setter KH_ERR_RANGE for a state outside [0, n_states).
+ * While a constraint is set kh_model_verify*, kh_model_generate_lookup*, every kh_model_seq_* call that launches
+ * (prefill, prefill_gemm, fork, step*) and kh_model_generate_batch* return KH_ERR_UNSUPPORTED before any launch (a row
+ * of a B-token pass would need the state behind the previous rows' picks).  kh_model_score and the prefills are
+ * untouched. */
+#define KH_FSM_MAX_MASK_BYTES (256 * 1024 * 1024)
+int kh_model_set_constraint(kh_model* m, const kh_fsm* a);
+int kh_model_get_constraint_state(kh_model* m, int32_t* state);
+int kh_model_set_constraint_state(kh_model* m, int32_t state);
 
 /* Sequence scoring: log P(token | prefix) at every FED position (perplexity, loglikelihood evaluation, reranking, the
  * "echo" log-probs of a prompt).  Feeds h_tokens[0..n) at positions pos0 .. pos0 + n - 1 - rows below pos0 must exist,

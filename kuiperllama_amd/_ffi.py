@@ -32,6 +32,7 @@ EXPORTS = [
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
     "kh_plan_seq_prefill_gemm", "kh_model_seq_prefill_gemm",
+    "kh_fsm_check", "kh_fsm_walk", "kh_token_mask_f32", "kh_model_set_constraint", "kh_model_get_constraint_state", "kh_model_set_constraint_state",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log", "kh_debug_alloc_stats",
 ]
 
@@ -102,6 +103,23 @@ class Penalties(C.Structure):
 
 def penalties(repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0, last_n: int = 0) -> Penalties:
     return Penalties(float(repetition), float(presence), float(frequency), int(last_n))
+
+
+class Fsm(C.Structure):
+    """kh_fsm: a token automaton in CSR form (row_ptr int64 [n_states + 1], tokens / next int32 [n_edges])."""
+    _fields_ = [("n_states", C.c_int32), ("start", C.c_int32), ("row_ptr", C.POINTER(C.c_int64)),
+                ("tokens", C.POINTER(C.c_int32)), ("next", C.POINTER(C.c_int32))]
+
+
+def fsm(start, row_ptr, tokens, nxt, n_states=None):
+    """(Fsm, keepalive) over numpy arrays; the arrays are converted to the struct's dtypes and must outlive the call."""
+    import numpy as np
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    tk = np.ascontiguousarray(tokens, dtype=np.int32)
+    nx = np.ascontiguousarray(nxt, dtype=np.int32)
+    ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a.size else C.POINTER(t)()
+    n = int(n_states) if n_states is not None else len(rp) - 1
+    return Fsm(n, int(start), ptr(rp, C.c_int64), ptr(tk, C.c_int32), ptr(nx, C.c_int32)), (rp, tk, nx)
 
 
 class SeqOpts(C.Structure):
@@ -317,6 +335,12 @@ def lib() -> C.CDLL:
     L.kh_debug_launch_log.argtypes = [C.c_char_p, _i64]
     L.kh_debug_launch_log.restype = _i64
     L.kh_debug_alloc_stats.argtypes = [C.POINTER(_i64)]
+    L.kh_fsm_check.argtypes = [C.POINTER(Fsm), _i64]
+    L.kh_fsm_walk.argtypes = [C.POINTER(Fsm), _i32, C.POINTER(_i32), _i64, C.POINTER(_i32), C.POINTER(_i64)]
+    L.kh_token_mask_f32.argtypes = [_vp, _i64, _vp, _vp]
+    L.kh_model_set_constraint.argtypes = [_vp, C.POINTER(Fsm)]
+    L.kh_model_get_constraint_state.argtypes = [_vp, C.POINTER(_i32)]
+    L.kh_model_set_constraint_state.argtypes = [_vp, _i32]
     for name in EXPORTS:  # fail at load time, not at first call, if a symbol is missing
         getattr(L, name)
     _lib = L

@@ -19,7 +19,7 @@ SOURCES = ["kh_ops.hip", "kh_model_load.hip", "kh_model_step.hip", "kh_model_pre
            "kh_model_h16.hip", "kh_model_h16_pass.hip", "kh_model_q4.hip", "kh_model_q4_pass.hip",
            "kh_tokenizer.cpp", "kh_bpe.cpp", "kh_debug.cpp"]
 HEADERS = ["kh_common.h", "kh_gemv.h", "kh_attn.h", "kh_fused.h", "kh_q8ring.h", "kh_fused_ring.h", "kh_prefill.h", "kh_gemm.h", "kh_gemm_body.h", "kh_gemm_w16.h", "kh_gemm_q16.h", "kh_pattn.h", "kh_pattn_body.h", "kh_sample.h", "kh_step_tail.h", "kh_logit_proc.h", "kh_logprobs.h", "kh_cls_screen.h", "kh_w16.h", "kh_w16_pass.h", "kh_copy_launch.h", "kh_q4.h", "kh_q4_pass.h", "kh_pf_launch.h", "kh_unicode_tables.h",
-           "kh_model_internal.h", "kh_buf.h", "kh_dispatch.h", "kh_score_plan.h", "kh_spec.h", "kh_lookup.h", "kh_seq.h", "kh_seq_plan.h", "kh_seq_gemm.h", "kh_seq_prefill.h",
+           "kh_model_internal.h", "kh_buf.h", "kh_dispatch.h", "kh_score_plan.h", "kh_spec.h", "kh_lookup.h", "kh_seq.h", "kh_seq_plan.h", "kh_seq_gemm.h", "kh_seq_prefill.h", "kh_fsm.h",
            "../../include/kuiper_hip.h"]
 ARCH = "gfx950"
 

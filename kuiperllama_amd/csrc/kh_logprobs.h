@@ -21,6 +21,7 @@
 // Also here: kh_tail_chain, the one chain process -> first maximum -> pick -> record, and the two step tails that run it
 // between kh_step_tail.h's begin and end (k_sample_proc, k_sample_lp); the rows of kh_seq.h and kh_spec.h run it too.
 #pragma once
+#include "kh_fsm.h"
 #include "kh_sample.h"
 
 #define KH_LOGPROBS_TOP KH_LOGPROBS_MAX_TOP  // (kuiper_hip.h) also the stride of a model's records
@@ -183,15 +184,27 @@ __device__ __forceinline__ void kh_logprobs_core(KhSampSmem& s, KhLpSmem& t, con
 //   3. the pick: the sampler core with counter pos where p.temperature > 0, else that maximum;
 //   4. top_n >= 0: the record at index `rec` of the record arrays - the pick, its log-prob and the top top_n of the
 //      logits the pick was made from (KhTailRecs, kh_step_tail.h); entries from top_n on are "none" (kh_rec_none).
+// With a constraint (fsm.desc non-null: the batch-1 tails k_sample_proc_fsm / k_sample_lp_fsm only; the argument is a
+// constant null in every other caller and the inlined chain is the one it was):
+//   0. kh_fsm_mask_core: the logits outside the row of the automaton state become -inf, ahead of step 1;
+//   5. kh_fsm_advance_core: the state behind the pick.
 // Returns the pick in every thread.  LDS: KhSampSmem + KhLpSmem.  Inlined, like the cores.
 __device__ __forceinline__ int kh_tail_chain(float* lg, int vocab, const int32_t* hist, int pos, const KhProcParams pp,
                                              const int32_t* bias_ids, const float* bias, int32_t* cnt,
                                              const KhSampParams p, int top_n, const KhTailRecs r, int rec,
-                                             KhAmaxParts parts = {nullptr, nullptr, 0}) {
+                                             KhAmaxParts parts = {nullptr, nullptr, 0},
+                                             const KhFsmRef fsm = {nullptr, nullptr}) {
   __shared__ KhSampSmem s;
   __shared__ KhLpSmem t;
   __shared__ float s_max;
   __shared__ int s_idx;
+  int fsm_s = -1;
+  if (fsm.desc) {  // uniform; every thread reads the state word ahead of the core's barrier, the write is step 5
+    fsm_s = *fsm.state;
+    if ((unsigned)fsm_s < (unsigned)fsm.desc->n_states)
+      kh_fsm_mask_core(lg, vocab, fsm.desc->mask + (size_t)fsm_s * (size_t)fsm.desc->stride);
+    parts.val = nullptr;  // the launch's maxima describe the raw row
+  }
   if (pp.repetition != 1.f || pp.presence != 0.f || pp.frequency != 0.f || pp.n_bias > 0) {  // uniform
     kh_logit_process_core(lg, vocab, hist, pos, pp, bias_ids, bias, cnt);
     parts.val = nullptr;
@@ -214,6 +227,7 @@ __device__ __forceinline__ int kh_tail_chain(float* lg, int vocab, const int32_t
     if (threadIdx.x == 0) r.token[rec] = pick;
     kh_rec_none(r, rec, top_n);
   }
+  if (fsm.desc) kh_fsm_advance_core(*fsm.desc, fsm_s, pick, fsm.state);
   return pick;
 }
 
@@ -286,6 +300,40 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_lp(const KhSa
   else if (rec)
     kh_rec_none(a.recs, pos, -1);
   kh_step_end(a.st, pos, forced, pick, a.hist, a.hist_cap, KH_SAMP_THREADS);
+}
+
+// ---- ... and while a constraint is set (kh_fsm.h, kh_model_set_constraint): twins of the two tails above whose chain
+// masks ahead of the processors and moves the automaton state behind the pick.  Twins, not an argument of the tails
+// above: the launches of a model without a constraint keep their code and their registers.  The descriptor and the state
+// word are the model's (allocated once): a new automaton needs no recapture.  proc / params / cnt exist (neutral / greedy
+// unless set), as for k_sample_lp.
+struct KhSampleProcFsmArgs {
+  KhFsmRef fsm;
+  KhSampleProcArgs t;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_proc_fsm(const KhSampleProcFsmArgs a) {
+  int pos, forced, pick = -1;
+  kh_step_begin(a.t.st, pos, forced);
+  if (forced < 0)
+    pick = kh_tail_chain(a.t.logits, a.t.st.vocab, a.t.hist, pos, *a.t.proc, a.t.bias_ids, a.t.bias, a.t.cnt, *a.t.params,
+                         /*top_n=*/-1, KhTailRecs{nullptr, nullptr, nullptr, nullptr}, 0, KhAmaxParts{nullptr, nullptr, 0},
+                         a.fsm);
+  kh_step_end(a.t.st, pos, forced, pick, a.t.hist, a.t.hist_cap, KH_SAMP_THREADS);
+}
+struct KhSampleLpFsmArgs {
+  KhFsmRef fsm;
+  KhSampleLpArgs t;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_sample_lp_fsm(const KhSampleLpFsmArgs a) {
+  int pos, forced, pick = -1;
+  kh_step_begin(a.t.st, pos, forced);
+  const bool rec = pos >= 0 && pos < a.t.rec_cap;
+  if (forced < 0)
+    pick = kh_tail_chain(a.t.logits, a.t.st.vocab, a.t.hist, pos, *a.t.proc, a.t.bias_ids, a.t.bias, a.t.cnt, *a.t.params,
+                         rec ? max(*a.t.top_n, 0) : -1, a.t.recs, pos, KhAmaxParts{nullptr, nullptr, 0}, a.fsm);
+  else if (rec)
+    kh_rec_none(a.t.recs, pos, -1);
+  kh_step_end(a.t.st, pos, forced, pick, a.t.hist, a.t.hist_cap, KH_SAMP_THREADS);
 }
 
 // ---- sequence scoring (kh_model_score): the records of the fed positions of one B-token pass.  One workgroup per

@@ -45,6 +45,7 @@
 #include "kh_attn.h"
 #include "kh_buf.h"
 #include "kh_common.h"
+#include "kh_fsm.h"
 #include "kh_seq_plan.h"
 #include "kh_step_tail.h"
 
@@ -245,7 +246,7 @@ struct kh_model {
     hipGraphExec_t e = nullptr;
   };
   // [StepTail][variant][log2 steps]: graphs of 1, 2, 4 and KH_GRAPH_STEPS = 8 steps per tail of the step
-  StepGraph sg[6][KH_STEP_VARIANTS][4];
+  StepGraph sg[8][KH_STEP_VARIANTS][4];
   // kh_model_set_sampling: the parameters (host copy), whether they sample (temperature > 0), and their device copy,
   // which the captured k_sample_topp launches read (a new seed or temperature needs no recapture)
   kh_sampling samp{0.f, 0, 1.f, 0};
@@ -278,6 +279,23 @@ struct kh_model {
   KhDev<float> d_lp_lp;
   KhDev<int32_t> d_lp_top_ids;
   KhDev<float> d_lp_top_lp;
+  // Constraint (kh_fsm.h, kh_model_set_constraint).  d_fsm: the descriptor the captured k_sample_*_fsm launches read,
+  // d_fsm_state: the automaton state - both allocated once, by the first "on", so that a new automaton rewrites the
+  // descriptor and swaps the buffers behind it without a recapture (the old buffers go once the stream has drained).
+  // Host copies of what the checks need: the CSR rows (a -inf bias may not empty a row) and the -inf ids of the bias.
+  struct Fsm {
+    KhDev<KhFsmDev> desc;
+    KhDev<int32_t> state;
+    KhDev<uint32_t> mask;
+    KhDev<int64_t> row_ptr;
+    KhDev<int32_t> tokens, next;
+    int n_states = 0, start = 0;
+    std::vector<int64_t> h_row_ptr;
+    std::vector<int32_t> h_tokens;
+  };
+  Fsm fsm;
+  bool fsm_on = false;
+  std::vector<int32_t> bias_banned;  // ascending ids of the bias list's -inf entries
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // Screened classifier of the greedy generate loop (kh_cls_screen.h, kh_model_screen.hip): fp32 models only
   struct ClsScreen {
@@ -459,14 +477,18 @@ static inline void logits_fresh(kh_model* m) { m->scr.stale = false; }
 // k_cls + k_sample_proc (penalties or a logit bias set: processing, then the greedy or sampled pick), or k_cls +
 // k_sample_lp (log-probs on: k_sample_proc's duties, then the record of the position).  kScreenQ8: the screened pair
 // behind its int8 tier, k_cls_screen_q8 + k_cls_screen (survivor mode) + k_sample_screen: 5L + 3 launches
-enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2, kProcess = 3, kLogprob = 4, kScreenQ8 = 5 };
+// kProcessFsm / kLogprobFsm: a constraint is set (kh_fsm.h) - k_cls + k_sample_proc_fsm / k_sample_lp_fsm, the two
+// tails above with the mask of the automaton state's row ahead of the chain and the transition behind the pick
+enum StepTail { kGreedy = 0, kSample = 1, kScreen = 2, kProcess = 3, kLogprob = 4, kScreenQ8 = 5, kProcessFsm = 6,
+                kLogprobFsm = 7 };
 static inline bool tail_screens(StepTail t) { return t == kScreen || t == kScreenQ8; }
 // log-probs, processing and sampling need every logit: they are stronger than a caller's wish to screen, and log-probs
 // are stronger than the rest.  process = false: a step whose pick is discarded (kh_model_predict at a prompt position)
 // leaves its logits as the classifier wrote them and writes no record
 // screen: 0 no, 1 the bf16 screen, 2 the bf16 screen behind its int8 tier (cls_screen_level)
 static inline StepTail step_tail(const kh_model* m, int screen, bool process = true) {
-  return m->lp_top_n >= 0 && process ? kLogprob
+  return m->fsm_on && process        ? (m->lp_top_n >= 0 ? kLogprobFsm : kProcessFsm)
+         : m->lp_top_n >= 0 && process ? kLogprob
          : m->proc_on && process     ? kProcess
          : m->samp_on                ? kSample
          : screen == 2               ? kScreenQ8

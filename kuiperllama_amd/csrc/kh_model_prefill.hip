@@ -568,7 +568,8 @@ static int verify_call(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t 
                        int32_t* n_accept, bool as_set) {
   if (!m || !h_tokens || !h_next || !n_accept || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
-  if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  // (a constraint: a row's mask would need the state behind the previous rows' picks)
+  if (m->fsm_on || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
   if (n > verify_width(m) || (int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
   if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));

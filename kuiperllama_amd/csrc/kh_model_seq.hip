@@ -266,7 +266,7 @@ extern "C" int kh_model_seq_prefill(kh_model* m, int32_t slot, const int32_t* h_
   if (slot < 0 || slot >= m->seq_slots || (int64_t)pos0 + n > cap(m, slot)) return KH_ERR_RANGE;
   if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   if (writes_shared(m, slot, pos0)) return KH_ERR_INVALID_ARG;  // a sharer below its shared length, a parent's shared rows
-  if (!prefill_supported(m)) return KH_ERR_UNSUPPORTED;
+  if (m->fsm_on || !prefill_supported(m)) return KH_ERR_UNSUPPORTED;  // (a constraint: the slots are not for it)
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
   const int row0 = own_base(m, slot);
@@ -318,6 +318,7 @@ extern "C" int kh_model_seq_prefill_gemm(kh_model* m, int32_t n_seq, const int32
     }
   }
   int rc;
+  if (m->fsm_on) return KH_ERR_UNSUPPORTED;
   if ((rc = seq_prefill_gemm_check(m)) != KH_OK) return rc;
   return kh_api_guard([&]() -> int {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
@@ -348,6 +349,7 @@ extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot
   if (src_slot < 0 || src_slot >= m->seq_slots || dst_slot < 0 || dst_slot >= m->seq_slots ||
       n_rows > slot_of(m, src_slot).len || n_rows > slot_of(m, dst_slot).len)
     return KH_ERR_RANGE;
+  if (m->fsm_on) return KH_ERR_UNSUPPORTED;
   if (slot_of(m, src_slot).pfx > 0 || slot_of(m, dst_slot).pfx > 0) return KH_ERR_UNSUPPORTED;  // a sharer's rows are not one run
   if (slot_of(m, dst_slot).pmax > 0) return KH_ERR_INVALID_ARG;  // a parent's shared rows are immutable
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
@@ -375,8 +377,8 @@ int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_
                  const kh_sampling* samplings, const kh_seq_opts* o, bool ex_call, int32_t* h_next, bool wide = false) {
   if (!m || !slots || !h_tokens || !pos || !h_next || n <= 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
-  if (wide ? !seq_gemm_supported(m) : (ex_call ? !full_depth_supported(m) : seq_unsupported(m)))
-    return KH_ERR_UNSUPPORTED;
+  if (m->fsm_on || (wide ? !seq_gemm_supported(m) : (ex_call ? !full_depth_supported(m) : seq_unsupported(m))))
+    return KH_ERR_UNSUPPORTED;  // (a constraint: one automaton state, no lane has its own)
   if (n > (wide ? KH_SEQ_SLOTS_MAX : verify_width(m))) return KH_ERR_RANGE;
   for (int i = 0; i < n; ++i) {
     if (slots[i] < 0 || slots[i] >= m->seq_slots || pos[i] < 0 || pos[i] >= cap(m, slots[i]) || h_tokens[i] < 0 ||
@@ -520,8 +522,8 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
     n_tok += (size_t)n_prompt[s];
   }
   if (!tokens_in_vocab(m, h_prompts, n_tok)) return KH_ERR_RANGE;
-  if (wide ? !seq_gemm_supported(m) : (ex_call ? !full_depth_supported(m) : seq_unsupported(m)))
-    return KH_ERR_UNSUPPORTED;
+  if (m->fsm_on || (wide ? !seq_gemm_supported(m) : (ex_call ? !full_depth_supported(m) : seq_unsupported(m))))
+    return KH_ERR_UNSUPPORTED;  // (a constraint: one automaton state, no lane has its own)
   SeqEx ex;
   {
     const int rc = seq_ex_parse(m, n_seq, o, &ex);

@@ -305,9 +305,10 @@ void launch_cls(kh_model* m, const ClsIo& io, bool ring, KhOn on) {
 }
 void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
   if (tail_screens(tail) && step_tail(m, 1) != kScreen) tail = step_tail(m, 1);  // processors or sampling on are stronger than "screen"
+  const KhFsmRef fsm{m->fsm.desc, m->fsm.state};  // (the _fsm tails: both exist while a constraint is set)
   if (tail_screens(tail)) {
     launch_sample_screen(m, advance, n_forced);
-  } else if (tail == kLogprob) {
+  } else if (tail == kLogprob || tail == kLogprobFsm) {
     KhSampleLpArgs t;
     t.logits = m->logits;
     t.part_val = m->part_val;
@@ -324,9 +325,15 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
     t.recs = lp_records(m);
     t.rec_cap = m->lp_cap;
     t.st = fill_step_tail(m, advance, n_forced);
+    if (tail == kLogprobFsm) {
+      launch_log("k_sample_lp_fsm");
+      const KhSampleLpFsmArgs tf{fsm, t};
+      hipLaunchKernelGGL(k_sample_lp_fsm, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, tf);
+      return;
+    }
     launch_log("k_sample_lp");
     hipLaunchKernelGGL(k_sample_lp, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
-  } else if (tail == kProcess) {
+  } else if (tail == kProcess || tail == kProcessFsm) {
     KhSampleProcArgs t;
     t.logits = m->logits;
     t.params = m->d_samp;
@@ -337,6 +344,12 @@ void launch_sample(kh_model* m, int advance, int n_forced, StepTail tail) {
     t.hist_cap = m->hist_cap;
     t.cnt = m->d_cnt;
     t.st = fill_step_tail(m, advance, n_forced);
+    if (tail == kProcessFsm) {
+      launch_log("k_sample_proc_fsm");
+      const KhSampleProcFsmArgs tf{fsm, t};
+      hipLaunchKernelGGL(k_sample_proc_fsm, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, tf);
+      return;
+    }
     launch_log("k_sample_proc");
     hipLaunchKernelGGL(k_sample_proc, dim3(1), dim3(KH_SAMP_THREADS), 0, m->stream, t);
   } else if (tail == kSample) {
@@ -448,6 +461,14 @@ int launch_step_unfused(kh_model* m, int pos, bool process) {
   KH_TRY(kh_rmsnorm_f32(m->x, m->final_norm, m->x, c.dim, c.rms_eps, s));
   KH_TRY(lin(m->cls, m->x, m->logits, c.dim, c.vocab_size));
   logits_fresh(m);
+  const bool fsm = process && m->fsm_on;
+  if (fsm) {  // the row of the automaton state, ahead of the processors: k_token_mask reads the state word itself
+    const int n4 = (c.vocab_size + 3) / 4, grid = (n4 + KH_WG - 1) / KH_WG;
+    launch_log("k_token_mask");
+    hipLaunchKernelGGL(k_token_mask, dim3(grid < 1024 ? grid : 1024), dim3(KH_WG), 0, m->stream, (float*)m->logits,
+                       c.vocab_size, (const uint32_t*)nullptr, (const KhFsmDev*)m->fsm.desc, (const int32_t*)m->fsm.state);
+    KH_TRY(kh_launch_status());
+  }
   if (process && m->proc_on)  // d_hist[pos] is this step's own token (set_state)
     KH_TRY(kh_logit_process_f32(m->logits, c.vocab_size, m->d_hist, nullptr, pos, &m->pen, m->d_bias_ids, m->d_bias,
                                 m->n_bias, m->d_cnt, s));
@@ -455,6 +476,12 @@ int launch_step_unfused(kh_model* m, int pos, bool process) {
     KH_TRY(kh_sample_f32(m->logits, c.vocab_size, &m->samp, pos, 1, m->d_next, s));
   } else {
     KH_TRY(kh_argmax_f32(m->logits, c.vocab_size, m->d_next, s));
+  }
+  if (fsm) {  // the state behind the pick
+    launch_log("k_fsm_advance");
+    hipLaunchKernelGGL(k_fsm_advance, dim3(1), dim3(KH_FSM_THREADS), 0, m->stream, (const KhFsmDev*)m->fsm.desc,
+                       (int32_t*)m->fsm.state, (const int32_t*)m->d_next);
+    KH_TRY(kh_launch_status());
   }
   if (process && m->lp_top_n >= 0) {  // the record of the position, from the logits the pick was made from
     KH_TRY(lp_none(m, pos, 1));       // (the entries behind top_n stay "none")
@@ -773,11 +800,25 @@ extern "C" int kh_model_get_sampling(const kh_model* m, kh_sampling* out) {
 
 // ---- logit processors (kh_logit_proc.h)
 namespace {
+// does the ascending list `banned` (the -inf ids of a bias list) hold every token of some row of a constraint?  Such a
+// state would leave the sampler no finite logit.
+bool fsm_row_emptied(const std::vector<int64_t>& row_ptr, const int32_t* tokens, const std::vector<int32_t>& banned) {
+  if (banned.empty()) return false;
+  for (size_t s = 0; s + 1 < row_ptr.size(); ++s) {
+    if (row_ptr[s + 1] - row_ptr[s] > (int64_t)banned.size()) continue;
+    bool all = true;
+    for (int64_t e = row_ptr[s]; e < row_ptr[s + 1] && all; ++e)
+      all = std::binary_search(banned.begin(), banned.end(), tokens[e]);
+    if (all) return true;
+  }
+  return false;
+}
 // after a change of m->pen / the bias list: whether anything is on, the buffers of the first "on", the device copy of
 // the parameters (on the model stream, behind whatever is queued)
 int proc_commit(kh_model* m) {
   const bool on = !kh_penalties_neutral(&m->pen) || m->n_bias > 0;
-  if (on || m->d_proc || m->lp_top_n >= 0) {  // (k_sample_lp reads the device copies while log-probs are on)
+  // (k_sample_lp reads the device copies while log-probs are on, k_sample_proc_fsm while a constraint is set)
+  if (on || m->d_proc || m->lp_top_n >= 0 || m->fsm_on) {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     if (!m->d_proc) {  // the first "on": d_proc and d_cnt together, and d_samp where no sampler call made it yet
       KhDev<KhProcParams> proc;
@@ -837,6 +878,12 @@ extern "C" int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const 
     int banned = 0;
     for (int i = 0; i < n; ++i) banned += h_bias[i] == -INFINITY;
     if (banned >= V) return KH_ERR_INVALID_ARG;  // (ids are distinct and in range) nothing left to pick
+    std::vector<int32_t> banned_ids;
+    for (int i = 0; i < n; ++i)
+      if (h_bias[i] == -INFINITY) banned_ids.push_back(h_ids[i]);
+    std::sort(banned_ids.begin(), banned_ids.end());
+    // ... nor in any state of the constraint
+    if (m->fsm_on && fsm_row_emptied(m->fsm.h_row_ptr, m->fsm.h_tokens.data(), banned_ids)) return KH_ERR_INVALID_ARG;
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
     if (n > (int)m->d_bias.size()) {
       // the captured k_sample_proc launches hold the old pointers: drain, drop the graphs (rebuilt on next use), then
@@ -857,8 +904,106 @@ extern "C" int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const 
       KH_CHECK_HIP(hipMemcpyAsync(m->d_bias, h_bias, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, m->stream));
     }
     m->n_bias = n;
+    m->bias_banned = std::move(banned_ids);
     return proc_commit(m);  // (its sync keeps the caller's arrays alive for the uploads)
   });
+}
+
+// ---- constraint (kh_fsm.h)
+extern "C" int kh_model_set_constraint(kh_model* m, const kh_fsm* a) {
+  if (!m) return KH_ERR_INVALID_ARG;
+  return kh_api_guard([&]() -> int {
+    if (!a) {  // off: the tails of the other settings again; the buffers stay for the next "on"
+      m->fsm_on = false;
+      return KH_OK;
+    }
+    // every check before any device call
+    int rc = kh_fsm_check_host(a, m->cfg.vocab_size);
+    if (rc != KH_OK) return rc;
+    const int64_t n_edges = a->row_ptr[a->n_states];
+    std::vector<int64_t> h_row_ptr(a->row_ptr, a->row_ptr + a->n_states + 1);
+    std::vector<int32_t> h_tokens(a->tokens, a->tokens + n_edges);
+    if (fsm_row_emptied(h_row_ptr, h_tokens.data(), m->bias_banned)) return KH_ERR_INVALID_ARG;
+    // the mask rows, on the host
+    const size_t stride = ((size_t)m->cfg.vocab_size + 31) / 32;
+    // one mask row per state, on the host and again on the device: bounded (16 KiB per state at V = 128256)
+    if (stride * sizeof(uint32_t) * (size_t)a->n_states > (size_t)KH_FSM_MAX_MASK_BYTES) return KH_ERR_UNSUPPORTED;
+    std::vector<uint32_t> h_mask(stride * (size_t)a->n_states, 0u);
+    for (int32_t s = 0; s < a->n_states; ++s)
+      for (int64_t e = a->row_ptr[s]; e < a->row_ptr[s + 1]; ++e)
+        h_mask[stride * (size_t)s + ((size_t)a->tokens[e] >> 5)] |= 1u << (a->tokens[e] & 31);
+    KH_CHECK_HIP(hipSetDevice(m->opts.device));
+    // new buffers first: a failed call leaves the model as it found it
+    KhDev<KhFsmDev> desc;
+    KhDev<int32_t> state, tokens, next;
+    KhDev<uint32_t> mask;
+    KhDev<int64_t> row_ptr;
+    const bool first = !m->fsm.desc;
+    if ((first && ((rc = desc.alloc(1)) != KH_OK || (rc = state.alloc(1)) != KH_OK)) ||
+        (rc = mask.alloc(h_mask.size())) != KH_OK || (rc = row_ptr.alloc(h_row_ptr.size())) != KH_OK ||
+        (rc = tokens.alloc((size_t)n_edges)) != KH_OK || (rc = next.alloc((size_t)n_edges)) != KH_OK)
+      return rc;
+    const bool was_on = m->fsm_on;
+    m->fsm_on = true;
+    rc = proc_commit(m);  // what the _fsm tails read beside the automaton: d_proc, d_cnt, d_samp
+    if (rc != KH_OK) {
+      m->fsm_on = was_on;
+      return rc;
+    }
+    if (first) {
+      m->fsm.desc = std::move(desc);
+      m->fsm.state = std::move(state);
+    }
+    // on the model stream, behind whatever is queued; the sync keeps the host copies alive for the uploads - and the
+    // stream has drained before the old buffers, which launches ahead of the new descriptor read, are released
+    const KhFsmDev d{mask, row_ptr, tokens, next, a->n_states, (int32_t)stride};
+    const int32_t start = a->start;
+    hipError_t e = hipMemcpyAsync(mask, h_mask.data(), sizeof(uint32_t) * h_mask.size(), hipMemcpyHostToDevice, m->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(row_ptr, h_row_ptr.data(), sizeof(int64_t) * h_row_ptr.size(), hipMemcpyHostToDevice, m->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(tokens, a->tokens, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, m->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(next, a->next, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, m->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->fsm.desc, &d, sizeof(d), hipMemcpyHostToDevice, m->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->fsm.state, &start, sizeof(start), hipMemcpyHostToDevice, m->stream);
+    const hipError_t es = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess || es != hipSuccess) {
+      // the descriptor may name the new buffers: keep them alive in the model, with the constraint off
+      m->fsm_on = false;
+      m->fsm.mask = std::move(mask);
+      m->fsm.row_ptr = std::move(row_ptr);
+      m->fsm.tokens = std::move(tokens);
+      m->fsm.next = std::move(next);
+      return e != hipSuccess ? (int)e : (int)es;
+    }
+    m->fsm.mask = std::move(mask);
+    m->fsm.row_ptr = std::move(row_ptr);
+    m->fsm.tokens = std::move(tokens);
+    m->fsm.next = std::move(next);
+    m->fsm.n_states = a->n_states;
+    m->fsm.start = a->start;
+    m->fsm.h_row_ptr = std::move(h_row_ptr);
+    m->fsm.h_tokens = std::move(h_tokens);
+    return KH_OK;
+  });
+}
+extern "C" int kh_model_get_constraint_state(kh_model* m, int32_t* state) {
+  if (!m || !state) return KH_ERR_INVALID_ARG;
+  if (!m->fsm_on) return KH_ERR_UNSUPPORTED;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemcpyAsync(state, m->fsm.state, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
+}
+extern "C" int kh_model_set_constraint_state(kh_model* m, int32_t state) {
+  if (!m) return KH_ERR_INVALID_ARG;
+  if (!m->fsm_on) return KH_ERR_UNSUPPORTED;
+  if (state < 0 || state >= m->fsm.n_states) return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemcpyAsync(m->fsm.state, &state, sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+  KH_CHECK_HIP(hipStreamSynchronize(m->stream));  // (keeps the host word alive for the upload)
+  return KH_OK;
 }
 
 // ---- log-probs (kh_logprobs.h)
@@ -911,6 +1056,12 @@ extern "C" int kh_model_generate(kh_model* m, const int32_t* h_prompt, int32_t n
 }
 
 namespace {
+// constraint on: the automaton state = start, on the model stream (a 32-bit fill: no host word to keep alive)
+int fsm_rearm(kh_model* m) {
+  if (!m->fsm_on) return KH_OK;
+  KH_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(int32_t*)m->fsm.state, m->fsm.start, 1, m->stream));
+  return KH_OK;
+}
 inline bool is_stop(int32_t t, const int32_t* stop, int n_stop) {
   for (int i = 0; i < n_stop; ++i)
     if (stop[i] == t) return true;
@@ -1007,6 +1158,9 @@ int generate_begin(kh_model* m, const int32_t* h_prompt, int n_prompt, int total
   // log-probs: the prompt positions are fed, not sampled (whatever path feeds them; the dry launches above wrote the
   // records of a throw-away continuation at positions 0 .. 7)
   if ((rc = lp_none(m, 0, n_prompt - 1)) != KH_OK) return rc;
+  // the constraint: every generate starts its automaton over (the dry launches above moved the state along a
+  // throw-away continuation)
+  if ((rc = fsm_rearm(m)) != KH_OK) return rc;
   KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
   if (n_prompt - 1 >= 2 && n_prompt - 1 < total_steps) {
     const char* e = dbg("KH_PREFILL");
@@ -1076,6 +1230,7 @@ extern "C" int kh_model_generate_until(kh_model* m, const int32_t* h_prompt, int
 
   if (exec == KH_EXEC_UNFUSED) {
     // the reference loop verbatim: host drives every step and reads `next` back each time
+    if ((rc = fsm_rearm(m)) != KH_OK) return rc;
     KH_CHECK_HIP(hipEventRecord(m->ev0, m->stream));
     int pos = 0, next = -1, nw = 0;
     while (pos < total_steps) {
@@ -1210,7 +1365,7 @@ static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_p
   if (!tokens_in_vocab(m, o.h_hint, o.n_hint)) return KH_ERR_RANGE;
   // only where the verify pass runs and, unless as_set, greedy on the raw logits only: no silent fallback to
   // generate_until
-  if (!full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  if (m->fsm_on || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;  // (a constraint: as kh_model_verify)
   if (!as_set && (m->samp_on || m->proc_on || m->lp_top_n >= 0)) return KH_ERR_UNSUPPORTED;
   return kh_api_guard([&]() -> int {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));

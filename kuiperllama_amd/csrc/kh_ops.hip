@@ -849,6 +849,33 @@ extern "C" int kh_logprobs_f32(const float* logits, int64_t n, int32_t n_rows, c
 }
 
 // =============================================================================================
+// constrained decoding (kh_fsm.h): the host checks and walk of a token automaton, and the mask as an operator
+extern "C" int kh_fsm_check(const kh_fsm* a, int64_t vocab) { return kh_fsm_check_host(a, vocab); }
+extern "C" int kh_fsm_walk(const kh_fsm* a, int32_t state, const int32_t* tokens, int64_t n, int32_t* out_state,
+                           int64_t* n_ok) {
+  if (!a || !a->row_ptr || !a->tokens || !a->next || a->n_states <= 0 || n < 0 || (n > 0 && !tokens) || !out_state ||
+      !n_ok)
+    return KH_ERR_INVALID_ARG;
+  if (state < 0 || state >= a->n_states) return KH_ERR_RANGE;
+  int64_t i = 0;
+  for (; i < n; ++i) {
+    const int64_t e = kh_fsm_edge_host(a, state, tokens[i]);
+    if (e < 0 || a->next[e] < 0 || a->next[e] >= a->n_states) break;
+    state = a->next[e];
+  }
+  *out_state = state;
+  *n_ok = i;
+  return KH_OK;
+}
+extern "C" int kh_token_mask_f32(float* logits, int64_t n, const uint32_t* d_mask, void* stream) {
+  if (!logits || !d_mask || n <= 0 || n > 0x7fffffffLL) return KH_ERR_INVALID_ARG;
+  const int64_t n4 = (n + 3) / 4, grid = (n4 + KH_WG - 1) / KH_WG;
+  hipLaunchKernelGGL(k_token_mask, dim3((unsigned)(grid < 1024 ? grid : 1024)), dim3(KH_WG), 0, (hipStream_t)stream, logits,
+                     (int)n, d_mask, (const KhFsmDev*)nullptr, (const int32_t*)nullptr);
+  return kh_launch_status();
+}
+
+// =============================================================================================
 extern "C" const char* kh_error_string(int code) {
   switch (code) {
     case KH_OK: return "success";

@@ -320,6 +320,28 @@ class KuiperModel:
                                                     out["top_logprobs"].ctypes.data), "kh_model_get_logprobs")
         return out
 
+    def set_constraint(self, automaton=None) -> None:
+        """Constrained decoding (kh_model_set_constraint): a constraint.TokenAutomaton - every sampled position of
+        predict / generate picks among the tokens its state allows and moves the state along the pick, inside the
+        graph loop.  None turns it off (the default).  The library copies the automaton."""
+        if automaton is None:
+            _ffi.check(_ffi.lib().kh_model_set_constraint(self._h, None), "kh_model_set_constraint")
+            return
+        a, keep = _ffi.fsm(automaton.start, automaton.row_ptr, automaton.tokens, automaton.next)
+        _ffi.check(_ffi.lib().kh_model_set_constraint(self._h, C.byref(a)), "kh_model_set_constraint")
+        del keep
+
+    @property
+    def constraint_state(self) -> int:
+        """The automaton state behind the last sampled step (kh_model_get_constraint_state; synchronises)."""
+        s = C.c_int32(-1)
+        _ffi.check(_ffi.lib().kh_model_get_constraint_state(self._h, C.byref(s)), "kh_model_get_constraint_state")
+        return int(s.value)
+
+    @constraint_state.setter
+    def constraint_state(self, state: int) -> None:
+        _ffi.check(_ffi.lib().kh_model_set_constraint_state(self._h, int(state)), "kh_model_set_constraint_state")
+
     def logits(self) -> np.ndarray:
         out = np.empty(self.cfg.vocab_size, np.float32)
         _ffi.check(_ffi.lib().kh_model_get_logits(self._h, out.ctypes.data), "kh_model_get_logits")

@@ -278,6 +278,18 @@ def logit_process(logits, tokens, pos, penalties=None, bias_ids=None, bias=None,
     return logits
 
 
+def token_mask(logits, mask):
+    """logits[v] = -inf in place wherever bit v & 31 of word v >> 5 of `mask` is clear (kh_token_mask_f32).  logits:
+    float32 GPU tensor [V]; mask: int32 GPU tensor of at least ceil(V / 32) words (the bits, whatever the sign); bits
+    past V are ignored."""
+    n = logits.numel()
+    if mask.numel() < (n + 31) // 32:
+        raise ValueError("mask needs ceil(V / 32) words")
+    _ffi.check(_ffi.lib().kh_token_mask_f32(_p(logits, torch.float32), n, _p(mask, torch.int32), _stream()),
+               "kh_token_mask_f32")
+    return logits
+
+
 def logprobs(logits, ids, top_n: int = 0) -> dict:
     """Log-probability of ids[r] under the softmax of logits[r] and the top_n alternatives of every row
     (kh_logprobs_f32).  logits: float32 GPU tensor [V] or [rows, V]; ids: int32 GPU tensor [rows] (an id outside [0, V)
