@@ -697,7 +697,9 @@ int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32_t* h_token
  * While a constraint is set kh_model_verify*, kh_model_generate_lookup*, every kh_model_seq_* call that launches
  * (prefill, prefill_gemm, fork, step*) and kh_model_generate_batch* return KH_ERR_UNSUPPORTED before any launch (a row
  * of a B-token pass would need the state behind the previous rows' picks).  kh_model_score and the prefills are
- * untouched. */
+ * untouched.  Sequences in slots are constrained by kh_model_seq_set_constraint ("Per-sequence constrained decoding"
+ * below), a setting of its own with one state per slot; one of the two is on at a time, and kh_model_set_constraint
+ * returns KH_ERR_UNSUPPORTED while that one is. */
 #define KH_FSM_MAX_MASK_BYTES (256 * 1024 * 1024)
 int kh_model_set_constraint(kh_model* m, const kh_fsm* a);
 int kh_model_get_constraint_state(kh_model* m, int32_t* state);
@@ -1006,6 +1008,52 @@ int kh_model_generate_batch_gemm(kh_model* m, int32_t n_seq, const int32_t* h_pr
 int kh_model_seq_gemm_logits(kh_model* m, int32_t lane, float* h_logits);
 int kh_plan_seq_batch_wide(int32_t n_seq, int32_t width, const int32_t* first_pos, const int32_t* total_steps,
                            int32_t* out_lanes, int32_t cap_passes, int32_t* n_passes);
+
+/* Per-sequence constrained decoding: the token automaton (kh_fsm, kh_model_set_constraint above) for sequences in slots -
+ * a server whose users each bring a schema, n constrained samples of a best-of-n, structured output from the wide pass.
+ * ONE automaton serves all slots and every slot has its own state word on the device.  Sequences with different
+ * constraints share a UNION: the automata laid side by side with their states renumbered, each sequence at its own
+ * start state (kuiperllama_amd.constraint.union builds it); KH_FSM_MAX_MASK_BYTES bounds the union as it bounds a
+ * single automaton.  A slot whose state is -1 is unconstrained: its row is not masked, nothing advances.
+ * At a lane's pass in kh_model_seq_step, _ex, _gemm and kh_model_generate_batch, _from, _ex, _gemm the row of the
+ * slot's state masks the lane's logits ahead of the penalties, the bias, the pick and the record, and the slot's state
+ * moves along the pick.  Fed-only positions (kh_model_seq_prefill, _prefill_gemm, the prompt part of generate_batch)
+ * neither mask nor advance: the caller moves a state along forced text with kh_fsm_walk and the setter.
+ * generate_batch* does not reset states; it samples from the state each slot holds.
+ * Contract: for sequence s with sub-automaton A_s the words, log-prob records, K/V rows and masked logits are bit for
+ * bit those of a batch-1 model under kh_model_set_constraint(A_s) with the same sampling, penalties, bias and log-probs
+ * through kh_model_generate; for the wide pass its own contract: every pick is exact on the pass's own logits, and
+ * kh_model_seq_gemm_logits returns the masked row.
+ * Launches: while some lane of a call sits in a slot whose state is >= 0 every pass of the call ends in k_seq_tail_fsm
+ * (csrc/kh_seq.h: k_seq_tail's twin with the automaton in its chain) for all its lanes, and a plain call runs as its
+ * _ex form with neutral options (the plain calls' refusals about the MODEL's own penalties, bias and log-probs stay).
+ * While no lane does - the constraint off, or every slot of the call at -1 - the calls launch exactly what they launch
+ * without this feature.  "Sits in" is decided on the host, by the state last SET for the slot (the device only moves
+ * a state >= 0 to another one).
+ * kh_model_seq_set_constraint (NULL: off) copies the automaton and sets every slot's state to -1.  Before any device
+ * call: kh_fsm_check's codes against vocab_size; KH_ERR_UNSUPPORTED while the model's batch-1 constraint is on
+ * (kh_model_set_constraint refuses the same way while this one is) and for a mask table above KH_FSM_MAX_MASK_BYTES.  The
+ * descriptor and the 64 state words (one per possible slot) are allocated once; a new automaton rewrites the descriptor.
+ * kh_model_seq_set_constraint_state / _get_constraint_state: state -1 or [0, n_states) of slot [0, n_slots), else
+ * KH_ERR_RANGE; KH_ERR_UNSUPPORTED while off.  The setter is stream-ordered; the getter synchronises.
+ * kh_model_seq_slots / _slots_var reset every state to -1, as they reset sharing.  kh_model_seq_fork copies the source
+ * slot's state to the destination on the stream (and the host's record of it): a fork in mid-generation continues
+ * under the same constraint.  kh_model_seq_share leaves states alone; a sharer may be constrained.
+ * A -inf bias may not leave a state without a token: a launching call returns KH_ERR_INVALID_ARG before any launch
+ * where the -inf entries of a lane's bias list hold every token of a row the lane's slot COULD reach - decided
+ * without a device read: the rows of the weakly connected component of the state last set for the slot.  Component
+ * labels and the rows of at most KH_SEQ_BIAS_MAX edges (no other row can be emptied) are computed once per automaton.
+ * kh_fsm_components / kh_fsm_bias_empties (host only, stateless) answer the two questions for any automaton:
+ * labels[s] = the smallest state of the weakly connected component of s; *emptied = 1 where the -inf entries of the
+ * list (n <= KH_SEQ_BIAS_MAX, else KH_ERR_RANGE) empty a row of state's component (state -1: never).  Both return
+ * kh_fsm_check's KH_ERR_INVALID_ARG codes for a malformed automaton.
+ * Speculative verify and lookup stay refused under the batch-1 constraint and do not read this one. */
+int kh_model_seq_set_constraint(kh_model* m, const kh_fsm* a);
+int kh_model_seq_set_constraint_state(kh_model* m, int32_t slot, int32_t state);
+int kh_model_seq_get_constraint_state(kh_model* m, int32_t slot, int32_t* state);
+int kh_fsm_components(const kh_fsm* a, int32_t* labels);
+int kh_fsm_bias_empties(const kh_fsm* a, int32_t state, const int32_t* h_ids, const float* h_bias, int32_t n,
+                        int32_t* emptied);
 
 /* MFMA prompt prefill into sequence slots: many prompts per weight pass (csrc/kh_seq_prefill.h).  kh_model_seq_prefill
  * is the bit-exact VALU pass, 8 (fp32) or 4 (int8) tokens per sweep of the weights; kh_model_prefill_gemm writes rows

@@ -33,6 +33,7 @@ EXPORTS = [
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
     "kh_plan_seq_prefill_gemm", "kh_model_seq_prefill_gemm",
     "kh_fsm_check", "kh_fsm_walk", "kh_token_mask_f32", "kh_model_set_constraint", "kh_model_get_constraint_state", "kh_model_set_constraint_state",
+    "kh_model_seq_set_constraint", "kh_model_seq_set_constraint_state", "kh_model_seq_get_constraint_state", "kh_fsm_components", "kh_fsm_bias_empties",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log", "kh_debug_alloc_stats",
 ]
 
@@ -341,6 +342,11 @@ def lib() -> C.CDLL:
     L.kh_model_set_constraint.argtypes = [_vp, C.POINTER(Fsm)]
     L.kh_model_get_constraint_state.argtypes = [_vp, C.POINTER(_i32)]
     L.kh_model_set_constraint_state.argtypes = [_vp, _i32]
+    L.kh_model_seq_set_constraint.argtypes = [_vp, C.POINTER(Fsm)]
+    L.kh_model_seq_set_constraint_state.argtypes = [_vp, _i32, _i32]
+    L.kh_model_seq_get_constraint_state.argtypes = [_vp, _i32, C.POINTER(_i32)]
+    L.kh_fsm_components.argtypes = [C.POINTER(Fsm), C.POINTER(_i32)]
+    L.kh_fsm_bias_empties.argtypes = [C.POINTER(Fsm), _i32, C.POINTER(_i32), C.POINTER(C.c_float), _i32, C.POINTER(_i32)]
     for name in EXPORTS:  # fail at load time, not at first call, if a symbol is missing
         getattr(L, name)
     _lib = L

@@ -7,6 +7,7 @@ automaton: accepting states carry an edge on `eos` into a sink whose only edge i
   from_choices(token_seqs, eos)          "answer with one of these": the trie of the sequences
   from_regex(pattern, vocab_bytes, eos)  "emit text that matches this pattern": full-match semantics over bytes
   vocab_bytes(tokenizer)                 the byte string of every token of a SpmTokenizer / BpeTokenizer
+  union(automata)                        one automaton for sequences with different constraints, and their start states
 
 Pure numpy; nothing here touches the GPU or the library.
 """
@@ -104,6 +105,33 @@ def from_choices(token_seqs: Sequence[Sequence[int]], eos: int) -> TokenAutomato
     for s in accepting:
         rows[s][int(eos)] = sink
     return _from_rows(0, rows)
+
+
+def union(automata: Sequence[Optional[TokenAutomaton]]) -> Tuple[TokenAutomaton, List[int]]:
+    """One automaton for sequences with different constraints (KuiperModel.seq_set_constraint): the given automata side
+    by side, the states of automata[i] renumbered by the number of states ahead of it.  Returns (the union, starts):
+    starts[i] is automata[i]'s start state in the union - the state to give sequence i's slot - and -1 where automata[i]
+    is None (an unconstrained sequence).  An object given more than once is laid down once and its entries share the
+    start (n samples under one constraint cost one copy).  The union's own `start` is that of the first automaton; the
+    union of one automaton is that automaton.  ValueError where there is no automaton at all."""
+    given = [a for a in automata if a is not None]
+    if not given:
+        raise ValueError("union: no automaton")
+    starts, state0, edge0, seen = [], 0, 0, {}
+    row_ptr, tokens, nxt = [np.zeros(1, np.int64)], [], []
+    for a in automata:
+        if a is None or id(a) in seen:
+            starts.append(-1 if a is None else seen[id(a)])
+            continue
+        starts.append(state0 + a.start)
+        seen[id(a)] = starts[-1]
+        row_ptr.append(a.row_ptr[1:] + edge0)
+        tokens.append(a.tokens)
+        nxt.append(a.next + np.int32(state0))
+        state0 += a.n_states
+        edge0 += a.n_edges
+    start = next(s for s in starts if s >= 0)
+    return TokenAutomaton(start, np.concatenate(row_ptr), np.concatenate(tokens), np.concatenate(nxt)), starts
 
 
 # ---- regular expressions over bytes --------------------------------------------------------------------------------

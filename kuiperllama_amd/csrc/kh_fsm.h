@@ -10,7 +10,9 @@
 // automaton of any size needs no graph recapture):
 //   mask     [n_states][stride] words, stride = ceil(V / 32): bit v & 31 of word v >> 5 of row s set = v is in row s;
 //   row_ptr / tokens / next   the CSR arrays as the caller gave them.
-// The state itself is one more device word beside d_pos and d_token.
+// The state itself is one more device word beside d_pos and d_token - or, for sequences in slots
+// (kh_model_seq_set_constraint, kh_seq.h: k_seq_tail_fsm), one word per slot of a table: one automaton serves all slots,
+// sequences with different constraints share a union and start at different states, -1 = unconstrained.
 //
 //   kh_fsm_mask_span    the mask pass of `nthr` threads over one vector: float4 q covers ids 4q .. 4q + 3, which are the
 //                       four bits (q & 7) * 4 .. of mask word q >> 3 - eight neighbouring lanes share a word, a wave
@@ -25,6 +27,9 @@
 // Plain C++, vector stores, no scratch, no inline assembly, no LDS.
 #pragma once
 #include <stdint.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "kh_common.h"
 
@@ -69,6 +74,49 @@ static inline int64_t kh_fsm_edge_host(const kh_fsm* a, int32_t s, int32_t t) {
     else hi = mid;
   }
   return lo < a->row_ptr[s + 1] && a->tokens[lo] == t ? lo : -1;
+}
+
+// ---- host: which rows a -inf bias list could empty, decided without a device read (kh_model_seq_set_constraint: one
+// automaton serves every slot and the device moves a slot's state, so the host knows the state it last SET, not the one
+// the slot is in).  A state can only reach states of its weakly connected component - label[s] = the smallest state of
+// the component of s -, and a list of at most max_edges ids can only empty a row of at most max_edges edges: `small`
+// holds those rows, ascending.  Built once per automaton.
+struct KhFsmReach {
+  std::vector<int32_t> label;  // [n_states]
+  std::vector<int32_t> small;  // states whose row has at most max_edges edges
+};
+static inline KhFsmReach kh_fsm_reach_host(const kh_fsm* a, int64_t max_edges) {
+  KhFsmReach r;
+  r.label.resize((size_t)a->n_states);
+  std::vector<int32_t>& p = r.label;  // union-find, the smaller root wins: a root is the smallest state of its set
+  for (int32_t s = 0; s < a->n_states; ++s) p[s] = s;
+  auto root = [&](int32_t s) {
+    while (p[s] != s) s = p[s] = p[p[s]];
+    return s;
+  };
+  for (int32_t s = 0; s < a->n_states; ++s) {
+    for (int64_t e = a->row_ptr[s]; e < a->row_ptr[s + 1]; ++e) {
+      const int32_t x = root(s), y = root(a->next[e]);
+      if (x < y) p[y] = x;
+      else p[x] = y;
+    }
+    if (a->row_ptr[s + 1] - a->row_ptr[s] <= max_edges) r.small.push_back(s);
+  }
+  for (int32_t s = 0; s < a->n_states; ++s) p[s] = root(s);
+  return r;
+}
+// does the ascending list `banned` hold every token of some small row in the component of `state`?
+static inline bool kh_fsm_reach_emptied_host(const int64_t* row_ptr, const int32_t* tokens, const KhFsmReach& r,
+                                             int32_t state, const std::vector<int32_t>& banned) {
+  if (banned.empty() || state < 0 || (size_t)state >= r.label.size()) return false;
+  for (const int32_t s : r.small) {
+    if (r.label[s] != r.label[state] || row_ptr[s + 1] - row_ptr[s] > (int64_t)banned.size()) continue;
+    bool all = true;
+    for (int64_t e = row_ptr[s]; e < row_ptr[s + 1] && all; ++e)
+      all = std::binary_search(banned.begin(), banned.end(), tokens[e]);
+    if (all) return true;
+  }
+  return false;
 }
 
 #if defined(__HIPCC__)

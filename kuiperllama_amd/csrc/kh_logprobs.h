@@ -184,8 +184,8 @@ __device__ __forceinline__ void kh_logprobs_core(KhSampSmem& s, KhLpSmem& t, con
 //   3. the pick: the sampler core with counter pos where p.temperature > 0, else that maximum;
 //   4. top_n >= 0: the record at index `rec` of the record arrays - the pick, its log-prob and the top top_n of the
 //      logits the pick was made from (KhTailRecs, kh_step_tail.h); entries from top_n on are "none" (kh_rec_none).
-// With a constraint (fsm.desc non-null: the batch-1 tails k_sample_proc_fsm / k_sample_lp_fsm only; the argument is a
-// constant null in every other caller and the inlined chain is the one it was):
+// With a constraint (fsm.desc non-null: the batch-1 tails k_sample_proc_fsm / k_sample_lp_fsm and, on a slot's state word,
+// kh_seq.h: k_seq_tail_fsm; the argument is a constant null in every other caller and the inlined chain is the one it was):
 //   0. kh_fsm_mask_core: the logits outside the row of the automaton state become -inf, ahead of step 1;
 //   5. kh_fsm_advance_core: the state behind the pick.
 // Returns the pick in every thread.  LDS: KhSampSmem + KhLpSmem.  Inlined, like the cores.

@@ -295,6 +295,15 @@ struct kh_model {
   };
   Fsm fsm;
   bool fsm_on = false;
+  // The sequence-level constraint (kh_model_seq_set_constraint; k_seq_tail_fsm): one automaton for all slots, the same
+  // buffers with a state table of KH_SEQ_SLOTS_MAX words, -1 = the slot is unconstrained.  One of the two constraints is
+  // on at a time.  seq_fsm_state: the state the host last set per slot - it decides whether a pass ends in
+  // k_seq_tail_fsm and which rows a lane's -inf bias is checked against (seq_fsm_reach; h_next is not kept: the host
+  // never walks).  The device moves the words; a word that was set >= 0 stays >= 0.
+  Fsm seq_fsm;
+  bool seq_fsm_on = false;
+  int32_t seq_fsm_state[KH_SEQ_SLOTS_MAX];
+  KhFsmReach seq_fsm_reach;
   std::vector<int32_t> bias_banned;  // ascending ids of the bias list's -inf entries
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // Screened classifier of the greedy generate loop (kh_cls_screen.h, kh_model_screen.hip): fp32 models only
@@ -621,7 +630,25 @@ struct KhSeqTail {
   const int32_t* bias_ids;   // [KH_SEQ_SLOTS_MAX][KH_SEQ_BIAS_MAX]
   const float* bias;
   int32_t* cnt;              // [KH_PF_BMAX][vocab]
+  KhFsmRef fsm;              // a lane's slot is constrained: the pass ends in k_seq_tail_fsm (else both null)
 };
+// The device form of an automaton (kh_model_set_constraint, kh_model_seq_set_constraint): the mask-size check and the
+// mask rows on the host, new buffers (and, the first time, the descriptor and n_state_words state words) - nothing of
+// the model is touched, a failure leaves it as it was.  fsm_install: the uploads and the descriptor on the model
+// stream, a sync, then the buffers replace f's; on an error they are kept alive in f too (the descriptor may name
+// them) and the caller turns its constraint off.  The state words are the caller's to write, ahead of fsm_install.
+struct FsmStage {
+  KhDev<KhFsmDev> desc;
+  KhDev<int32_t> state, tokens, next;
+  KhDev<uint32_t> mask;
+  KhDev<int64_t> row_ptr;
+  std::vector<uint32_t> h_mask;
+  std::vector<int64_t> h_row_ptr;
+  std::vector<int32_t> h_tokens;
+  size_t stride = 0;
+};
+int fsm_stage(kh_model* m, const kh_fsm* a, const kh_model::Fsm& f, size_t n_state_words, FsmStage* st);
+int fsm_install(kh_model* m, const kh_fsm* a, kh_model::Fsm& f, FsmStage& st);
 int seq_prepare(kh_model* m);
 int seq_prepare_ex(kh_model* m, bool records);  // behind seq_prepare: the tables of k_seq_tail, the record buffers
 int seq_prefill_enqueue(kh_model* m, int row0, const int32_t* toks, int n, int pos0, int pfx_len = 0, int pfx_row0 = 0);

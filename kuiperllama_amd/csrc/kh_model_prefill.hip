@@ -520,6 +520,7 @@ void khm::seq_attn_enqueue(kh_model* m, int l, const float* q, float* out, const
     launch_seq_attn(a, lanes, n, m->attn_wg, m->stream);
 }
 // the tail of lanes [0, n) on their logits rows [n][pf_vstride]: k_seq_pick, or k_seq_tail with a tail description
+// (k_seq_tail_fsm where the description names an automaton)
 int khm::seq_tail_enqueue(kh_model* m, float* logits, const KhSeqLanes& lanes, int n, bool words,
                           const KhSeqTail* tail) {
   const kh_config& c = m->cfg;
@@ -540,6 +541,12 @@ int khm::seq_tail_enqueue(kh_model* m, float* logits, const KhSeqLanes& lanes, i
     t.recs = lp_records(m);
     t.tok = m->d_seq_tok;
     t.words = words ? m->d_seq_words : nullptr;
+    if (tail->fsm.desc) {  // a lane's slot is constrained: the twin with the automaton, for all lanes of the pass
+      const KhSeqTailFsmArgs tf{tail->fsm, t};
+      launch_log("k_seq_tail_fsm");
+      hipLaunchKernelGGL(k_seq_tail_fsm, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, tf);
+      return kh_launch_status();
+    }
     launch_log("k_seq_tail");
     hipLaunchKernelGGL(k_seq_tail, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, t);
     return kh_launch_status();

@@ -2,7 +2,8 @@
 // of different sequences as an entry point (kh_model_seq_step) and the batched generate loop on top of it
 // (kh_model_generate_batch), and their _ex forms with per-sequence penalties, logit bias and log-probs (the pass then
 // ends in k_seq_tail), and their _gemm forms: the same host text over the wide pass of up to KH_SEQ_SLOTS_MAX lanes
-// (kh_model_gemm.hip: seq_pass_enqueue_gemm).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
+// (kh_model_gemm.hip: seq_pass_enqueue_gemm), and the sequence-level constraint (kh_model_seq_set_constraint: one
+// automaton, one state word per slot; the passes of a call with a constrained lane end in k_seq_tail_fsm).  Host side only: what is launched lives in kh_model_prefill.hip (seq_prefill_enqueue,
 // seq_pass_enqueue; kernels in kh_seq.h, kh_attn.h).  The reference decodes one sequence per process
 // (demo/main.cpp:16-50); n samples of a prompt are n runs of that loop there.
 // gfx950 only.
@@ -60,6 +61,28 @@ void set_layout(kh_model* m, int n, const int32_t* len, const int32_t* row0) {
     m->seq_tab[s].len = len[s];
   }
 }
+// the sequence-level constraint (kh_model_seq_set_constraint): every slot unconstrained again, on the model stream (a
+// 32-bit fill: no host word to keep alive)
+int seq_fsm_reset(kh_model* m) {
+  if (!m->seq_fsm_on) return KH_OK;
+  for (int s = 0; s < KH_SEQ_SLOTS_MAX; ++s) m->seq_fsm_state[s] = -1;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(int32_t*)m->seq_fsm.state, -1, KH_SEQ_SLOTS_MAX, m->stream));
+  return KH_OK;
+}
+// does a lane of the call sit in a constrained slot?  By the states the host last set (the device only moves a state
+// that is >= 0 to another that is): then the call's passes end in k_seq_tail_fsm
+bool seq_fsm_lanes(const kh_model* m, int n, const int32_t* slots) {
+  if (!m->seq_fsm_on) return false;
+  for (int i = 0; i < n; ++i)
+    if (m->seq_fsm_state[slots ? slots[i] : i] >= 0) return true;
+  return false;
+}
+// a plain call on constrained slots runs as the _ex call with these
+const kh_seq_opts* seq_neutral_opts(const kh_sampling* samplings, kh_seq_opts* store) {
+  *store = kh_seq_opts{samplings, nullptr, nullptr, nullptr, nullptr, -1};
+  return store;
+}
 bool penalties_on_sharer(const kh_model* m, const kh_seq_opts* o, int i, int s) {
   return o && o->penalties && m->seq_tab[s].pfx > 0 && !kh_penalties_neutral(&o->penalties[i]);
 }
@@ -94,7 +117,9 @@ struct SeqEx {
   int32_t off[KH_SEQ_SLOTS_MAX + 1] = {0};
 };
 // the checks of kh_model_set_penalties / kh_model_set_logit_bias / kh_model_set_logprobs per sequence; no device call
-int seq_ex_parse(const kh_model* m, int n, const kh_seq_opts* o, SeqEx* out) {
+// slot_of_i: the slots of the call's entries (null: entry i is slot i) - a -inf bias may not empty a row that the
+// entry's slot could reach under the sequence-level constraint (KhFsmReach)
+int seq_ex_parse(const kh_model* m, int n, const kh_seq_opts* o, SeqEx* out, const int32_t* slot_of_i) {
   out->o = o;
   if (!o) return KH_OK;
   const int V = m->cfg.vocab_size;
@@ -123,6 +148,15 @@ int seq_ex_parse(const kh_model* m, int n, const kh_seq_opts* o, SeqEx* out) {
       for (int k = 0; k < j; ++k)
         if (ids[k] == ids[j]) return KH_ERR_INVALID_ARG;
     if (nb > 0 && banned >= V) return KH_ERR_INVALID_ARG;  // nothing left to pick
+    const int st = m->seq_fsm_on ? m->seq_fsm_state[slot_of_i ? slot_of_i[i] : i] : -1;
+    if (banned > 0 && st >= 0) {
+      std::vector<int32_t> b;
+      for (int j = 0; j < nb; ++j)
+        if (bias[j] == -INFINITY) b.push_back(ids[j]);
+      std::sort(b.begin(), b.end());
+      if (kh_fsm_reach_emptied_host(m->seq_fsm.h_row_ptr.data(), m->seq_fsm.h_tokens.data(), m->seq_fsm_reach, st, b))
+        return KH_ERR_INVALID_ARG;
+    }
     out->off[i + 1] = out->off[i] + nb;
     out->on = out->on || nb > 0;
   }
@@ -209,7 +243,7 @@ extern "C" int kh_model_seq_slots(kh_model* m, int32_t n_slots, int32_t* slot_le
   }
   set_layout(m, n_slots, lens, row0);
   if (slot_len_out) *slot_len_out = len;
-  return KH_OK;
+  return seq_fsm_reset(m);
 }
 
 extern "C" int kh_model_seq_slots_var(kh_model* m, int32_t n_slots, const int32_t* h_len) {
@@ -217,7 +251,7 @@ extern "C" int kh_model_seq_slots_var(kh_model* m, int32_t n_slots, const int32_
   int32_t row0[KH_SEQ_SLOTS_MAX];
   if (!kh_seq_slots_var(m->cfg.cache_len, n_slots, h_len, row0)) return KH_ERR_INVALID_ARG;
   set_layout(m, n_slots, h_len, row0);
-  return KH_OK;
+  return seq_fsm_reset(m);
 }
 
 // Bookkeeping only: nothing is copied, nothing is launched.
@@ -366,6 +400,11 @@ extern "C" int kh_model_seq_fork(kh_model* m, int32_t src_slot, int32_t dst_slot
   }
   KH_CHECK_HIP(hipMemcpyAsync(m->d_hist + drow, m->d_hist + srow,
                               sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToDevice, m->stream));
+  if (m->seq_fsm_on) {  // the fork continues under the source's constraint, from the state the source is in
+    KH_CHECK_HIP(hipMemcpyAsync(m->seq_fsm.state + dst_slot, m->seq_fsm.state + src_slot, sizeof(int32_t),
+                                hipMemcpyDeviceToDevice, m->stream));
+    m->seq_fsm_state[dst_slot] = m->seq_fsm_state[src_slot];
+  }
   return KH_OK;
 }
 
@@ -388,9 +427,13 @@ int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_
       if (slots[j] == slots[i]) return KH_ERR_INVALID_ARG;  // two lanes of one sequence cannot share a pass
     if (samplings && !kh_sampling_valid(&samplings[i])) return KH_ERR_INVALID_ARG;
   }
+  const bool fsm = seq_fsm_lanes(m, n, slots);
+  kh_seq_opts neutral;
+  if (fsm && !o) o = seq_neutral_opts(samplings, &neutral);
   SeqEx ex;
   int rc;
-  if ((rc = seq_ex_parse(m, n, o, &ex)) != KH_OK) return rc;
+  if ((rc = seq_ex_parse(m, n, o, &ex, slots)) != KH_OK) return rc;
+  ex.on = ex.on || fsm;
   for (int i = 0; i < n; ++i) {
     if (writes_shared(m, slots[i], pos[i])) return KH_ERR_INVALID_ARG;
     if (penalties_on_sharer(m, o, i, slots[i])) return KH_ERR_UNSUPPORTED;  // its history lies in two row ranges
@@ -409,7 +452,8 @@ int seq_step_run(kh_model* m, int32_t n, const int32_t* slots, const int32_t* h_
     if (samplings && !kh_sampling_greedy(&samplings[i])) m->h_seq_samp_pin[slots[i]] = kh_samp_params(&samplings[i]);
   }
   rc = upload_slot_tables(m);
-  const KhSeqTail tail{ex.top_n, m->d_seq_proc, m->d_seq_bias_ids, m->d_seq_bias, m->d_seq_cnt};
+  const KhSeqTail tail{ex.top_n, m->d_seq_proc, m->d_seq_bias_ids, m->d_seq_bias, m->d_seq_cnt,
+                       fsm ? KhFsmRef{m->seq_fsm.desc, m->seq_fsm.state} : KhFsmRef{nullptr, nullptr}};
   if (rc == KH_OK && ex.on) {
     rc = upload_proc_tables(m, n, ex, [&](int i) { return slots[i]; });
     for (int i = 0; i < n && rc == KH_OK; ++i) {  // the lanes' fed tokens at their rows of the history
@@ -524,10 +568,14 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
   if (!tokens_in_vocab(m, h_prompts, n_tok)) return KH_ERR_RANGE;
   if (m->fsm_on || (wide ? !seq_gemm_supported(m) : (ex_call ? !full_depth_supported(m) : seq_unsupported(m))))
     return KH_ERR_UNSUPPORTED;  // (a constraint: one automaton state, no lane has its own)
+  const bool fsm = seq_fsm_lanes(m, n_seq, nullptr);
+  kh_seq_opts neutral;
+  if (fsm && !o) o = seq_neutral_opts(samplings, &neutral);
   SeqEx ex;
   {
-    const int rc = seq_ex_parse(m, n_seq, o, &ex);
+    const int rc = seq_ex_parse(m, n_seq, o, &ex, nullptr);
     if (rc != KH_OK) return rc;
+    ex.on = ex.on || fsm;
   }
   for (int s = 0; s < n_seq; ++s) {
     // the first position the call feeds: what is cached must cover a sharer's shared length and a parent's shared rows
@@ -544,7 +592,8 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
     if ((rc = seq_prepare(m)) != KH_OK) return rc;
     if (ex.on && (rc = seq_prepare_ex(m, ex.top_n >= 0)) != KH_OK) return rc;
     if (wide && (rc = seq_gemm_prepare(m)) != KH_OK) return rc;
-    const KhSeqTail tail{ex.top_n, m->d_seq_proc, m->d_seq_bias_ids, m->d_seq_bias, m->d_seq_cnt};
+    const KhSeqTail tail{ex.top_n, m->d_seq_proc, m->d_seq_bias_ids, m->d_seq_bias, m->d_seq_cnt,
+                         fsm ? KhFsmRef{m->seq_fsm.desc, m->seq_fsm.state} : KhFsmRef{nullptr, nullptr}};
     // every early return below may leave launches and copies into pinned memory in flight: drain first
     auto fail = [&](int code) -> int {
       (void)hipStreamSynchronize(m->stream);
@@ -670,6 +719,83 @@ int generate_batch_run(kh_model* m, int32_t n_seq, const int32_t* h_prompts, con
   });
 }
 }  // namespace
+
+// ---- the sequence-level constraint: one automaton, one state word per slot (kh_fsm.h, kh_seq.h: k_seq_tail_fsm)
+extern "C" int kh_model_seq_set_constraint(kh_model* m, const kh_fsm* a) {
+  if (!m) return KH_ERR_INVALID_ARG;
+  return kh_api_guard([&]() -> int {
+    if (!a) {  // off: k_seq_pick / k_seq_tail again; the buffers stay for the next "on"
+      m->seq_fsm_on = false;
+      return KH_OK;
+    }
+    // every check before any device call
+    int rc = kh_fsm_check_host(a, m->cfg.vocab_size);
+    if (rc != KH_OK) return rc;
+    if (m->fsm_on) return KH_ERR_UNSUPPORTED;  // one of the two constraints at a time
+    FsmStage st;
+    if ((rc = fsm_stage(m, a, m->seq_fsm, KH_SEQ_SLOTS_MAX, &st)) != KH_OK) return rc;
+    KhFsmReach reach = kh_fsm_reach_host(a, KH_SEQ_BIAS_MAX);
+    if (st.desc) {
+      m->seq_fsm.desc = std::move(st.desc);
+      m->seq_fsm.state = std::move(st.state);
+    }
+    m->seq_fsm_on = true;
+    rc = seq_fsm_reset(m);
+    const int rc2 = fsm_install(m, a, m->seq_fsm, st);
+    if (rc != KH_OK || rc2 != KH_OK) {
+      m->seq_fsm_on = false;
+      return rc != KH_OK ? rc : rc2;
+    }
+    m->seq_fsm_reach = std::move(reach);
+    return KH_OK;
+  });
+}
+extern "C" int kh_model_seq_set_constraint_state(kh_model* m, int32_t slot, int32_t state) {
+  if (!m) return KH_ERR_INVALID_ARG;
+  if (!m->seq_fsm_on) return KH_ERR_UNSUPPORTED;
+  if (slot < 0 || slot >= m->seq_slots || state < -1 || state >= m->seq_fsm.n_states) return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(m->seq_fsm.state + slot), state, 1, m->stream));
+  m->seq_fsm_state[slot] = state;
+  return KH_OK;
+}
+extern "C" int kh_model_seq_get_constraint_state(kh_model* m, int32_t slot, int32_t* state) {
+  if (!m || !state) return KH_ERR_INVALID_ARG;
+  if (!m->seq_fsm_on) return KH_ERR_UNSUPPORTED;
+  if (slot < 0 || slot >= m->seq_slots) return KH_ERR_RANGE;
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  KH_CHECK_HIP(hipMemcpyAsync(state, m->seq_fsm.state + slot, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+  KH_CHECK_HIP(hipStreamSynchronize(m->stream));
+  return KH_OK;
+}
+// host only, stateless: the two questions kh_model_seq_set_constraint and the launching calls ask of an automaton
+// (kh_fsm.h: KhFsmReach), as entry points of their own - a caller can ask them before it submits a bias list
+extern "C" int kh_fsm_components(const kh_fsm* a, int32_t* labels) {
+  if (!labels) return KH_ERR_INVALID_ARG;
+  const int rc = kh_fsm_check_host(a, INT64_MAX);
+  if (rc != KH_OK) return rc;
+  return kh_api_guard([&]() -> int {
+    const KhFsmReach r = kh_fsm_reach_host(a, 0);
+    memcpy(labels, r.label.data(), sizeof(int32_t) * r.label.size());
+    return KH_OK;
+  });
+}
+extern "C" int kh_fsm_bias_empties(const kh_fsm* a, int32_t state, const int32_t* h_ids, const float* h_bias, int32_t n,
+                                   int32_t* emptied) {
+  if (!emptied || n < 0 || (n > 0 && (!h_ids || !h_bias))) return KH_ERR_INVALID_ARG;
+  const int rc = kh_fsm_check_host(a, INT64_MAX);
+  if (rc != KH_OK) return rc;
+  if (state < -1 || state >= a->n_states || n > KH_SEQ_BIAS_MAX) return KH_ERR_RANGE;
+  return kh_api_guard([&]() -> int {
+    std::vector<int32_t> banned;
+    for (int i = 0; i < n; ++i)
+      if (h_bias[i] == -INFINITY) banned.push_back(h_ids[i]);
+    std::sort(banned.begin(), banned.end());
+    const KhFsmReach r = kh_fsm_reach_host(a, KH_SEQ_BIAS_MAX);
+    *emptied = kh_fsm_reach_emptied_host(a->row_ptr, a->tokens, r, state, banned) ? 1 : 0;
+    return KH_OK;
+  });
+}
 
 extern "C" int kh_model_seq_set_history(kh_model* m, int32_t slot, int32_t pos0, const int32_t* h_tokens, int32_t n) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;

@@ -910,6 +910,55 @@ extern "C" int kh_model_set_logit_bias(kh_model* m, const int32_t* h_ids, const 
 }
 
 // ---- constraint (kh_fsm.h)
+int khm::fsm_stage(kh_model* m, const kh_fsm* a, const kh_model::Fsm& f, size_t n_state_words, FsmStage* st) {
+  const int64_t n_edges = a->row_ptr[a->n_states];
+  // the mask rows, on the host
+  st->stride = ((size_t)m->cfg.vocab_size + 31) / 32;
+  // one mask row per state, on the host and again on the device: bounded (16 KiB per state at V = 128256)
+  if (st->stride * sizeof(uint32_t) * (size_t)a->n_states > (size_t)KH_FSM_MAX_MASK_BYTES) return KH_ERR_UNSUPPORTED;
+  st->h_row_ptr.assign(a->row_ptr, a->row_ptr + a->n_states + 1);
+  st->h_tokens.assign(a->tokens, a->tokens + n_edges);
+  st->h_mask.assign(st->stride * (size_t)a->n_states, 0u);
+  for (int32_t s = 0; s < a->n_states; ++s)
+    for (int64_t e = a->row_ptr[s]; e < a->row_ptr[s + 1]; ++e)
+      st->h_mask[st->stride * (size_t)s + ((size_t)a->tokens[e] >> 5)] |= 1u << (a->tokens[e] & 31);
+  KH_CHECK_HIP(hipSetDevice(m->opts.device));
+  // new buffers first: a failed call leaves the model as it found it
+  int rc;
+  if ((!f.desc && ((rc = st->desc.alloc(1)) != KH_OK || (rc = st->state.alloc(n_state_words)) != KH_OK)) ||
+      (rc = st->mask.alloc(st->h_mask.size())) != KH_OK || (rc = st->row_ptr.alloc(st->h_row_ptr.size())) != KH_OK ||
+      (rc = st->tokens.alloc((size_t)n_edges)) != KH_OK || (rc = st->next.alloc((size_t)n_edges)) != KH_OK)
+    return rc;
+  return KH_OK;
+}
+int khm::fsm_install(kh_model* m, const kh_fsm* a, kh_model::Fsm& f, FsmStage& st) {
+  const int64_t n_edges = a->row_ptr[a->n_states];
+  // on the model stream, behind whatever is queued; the sync keeps the host copies alive for the uploads - and the
+  // stream has drained before the old buffers, which launches ahead of the new descriptor read, are released
+  const KhFsmDev d{st.mask, st.row_ptr, st.tokens, st.next, a->n_states, (int32_t)st.stride};
+  hipError_t e =
+      hipMemcpyAsync(st.mask, st.h_mask.data(), sizeof(uint32_t) * st.h_mask.size(), hipMemcpyHostToDevice, m->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(st.row_ptr, st.h_row_ptr.data(), sizeof(int64_t) * st.h_row_ptr.size(), hipMemcpyHostToDevice,
+                       m->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(st.tokens, a->tokens, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, m->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(st.next, a->next, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, m->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(f.desc, &d, sizeof(d), hipMemcpyHostToDevice, m->stream);
+  const hipError_t es = hipStreamSynchronize(m->stream);
+  // (on an error the descriptor may name the new buffers: they are kept alive in the model all the same)
+  f.mask = std::move(st.mask);
+  f.row_ptr = std::move(st.row_ptr);
+  f.tokens = std::move(st.tokens);
+  f.next = std::move(st.next);
+  if (e != hipSuccess || es != hipSuccess) return e != hipSuccess ? (int)e : (int)es;
+  f.n_states = a->n_states;
+  f.start = a->start;
+  f.h_row_ptr = std::move(st.h_row_ptr);
+  f.h_tokens = std::move(st.h_tokens);
+  return KH_OK;
+}
 extern "C" int kh_model_set_constraint(kh_model* m, const kh_fsm* a) {
   if (!m) return KH_ERR_INVALID_ARG;
   return kh_api_guard([&]() -> int {
@@ -920,29 +969,13 @@ extern "C" int kh_model_set_constraint(kh_model* m, const kh_fsm* a) {
     // every check before any device call
     int rc = kh_fsm_check_host(a, m->cfg.vocab_size);
     if (rc != KH_OK) return rc;
-    const int64_t n_edges = a->row_ptr[a->n_states];
-    std::vector<int64_t> h_row_ptr(a->row_ptr, a->row_ptr + a->n_states + 1);
-    std::vector<int32_t> h_tokens(a->tokens, a->tokens + n_edges);
-    if (fsm_row_emptied(h_row_ptr, h_tokens.data(), m->bias_banned)) return KH_ERR_INVALID_ARG;
-    // the mask rows, on the host
-    const size_t stride = ((size_t)m->cfg.vocab_size + 31) / 32;
-    // one mask row per state, on the host and again on the device: bounded (16 KiB per state at V = 128256)
-    if (stride * sizeof(uint32_t) * (size_t)a->n_states > (size_t)KH_FSM_MAX_MASK_BYTES) return KH_ERR_UNSUPPORTED;
-    std::vector<uint32_t> h_mask(stride * (size_t)a->n_states, 0u);
-    for (int32_t s = 0; s < a->n_states; ++s)
-      for (int64_t e = a->row_ptr[s]; e < a->row_ptr[s + 1]; ++e)
-        h_mask[stride * (size_t)s + ((size_t)a->tokens[e] >> 5)] |= 1u << (a->tokens[e] & 31);
-    KH_CHECK_HIP(hipSetDevice(m->opts.device));
-    // new buffers first: a failed call leaves the model as it found it
-    KhDev<KhFsmDev> desc;
-    KhDev<int32_t> state, tokens, next;
-    KhDev<uint32_t> mask;
-    KhDev<int64_t> row_ptr;
-    const bool first = !m->fsm.desc;
-    if ((first && ((rc = desc.alloc(1)) != KH_OK || (rc = state.alloc(1)) != KH_OK)) ||
-        (rc = mask.alloc(h_mask.size())) != KH_OK || (rc = row_ptr.alloc(h_row_ptr.size())) != KH_OK ||
-        (rc = tokens.alloc((size_t)n_edges)) != KH_OK || (rc = next.alloc((size_t)n_edges)) != KH_OK)
-      return rc;
+    if (m->seq_fsm_on) return KH_ERR_UNSUPPORTED;  // one of the two constraints at a time
+    {
+      const std::vector<int64_t> h_row_ptr(a->row_ptr, a->row_ptr + a->n_states + 1);
+      if (fsm_row_emptied(h_row_ptr, a->tokens, m->bias_banned)) return KH_ERR_INVALID_ARG;
+    }
+    FsmStage st;
+    if ((rc = fsm_stage(m, a, m->fsm, 1, &st)) != KH_OK) return rc;
     const bool was_on = m->fsm_on;
     m->fsm_on = true;
     rc = proc_commit(m);  // what the _fsm tails read beside the automaton: d_proc, d_cnt, d_samp
@@ -950,41 +983,16 @@ extern "C" int kh_model_set_constraint(kh_model* m, const kh_fsm* a) {
       m->fsm_on = was_on;
       return rc;
     }
-    if (first) {
-      m->fsm.desc = std::move(desc);
-      m->fsm.state = std::move(state);
+    if (st.desc) {
+      m->fsm.desc = std::move(st.desc);
+      m->fsm.state = std::move(st.state);
     }
-    // on the model stream, behind whatever is queued; the sync keeps the host copies alive for the uploads - and the
-    // stream has drained before the old buffers, which launches ahead of the new descriptor read, are released
-    const KhFsmDev d{mask, row_ptr, tokens, next, a->n_states, (int32_t)stride};
-    const int32_t start = a->start;
-    hipError_t e = hipMemcpyAsync(mask, h_mask.data(), sizeof(uint32_t) * h_mask.size(), hipMemcpyHostToDevice, m->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(row_ptr, h_row_ptr.data(), sizeof(int64_t) * h_row_ptr.size(), hipMemcpyHostToDevice, m->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(tokens, a->tokens, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, m->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(next, a->next, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice, m->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->fsm.desc, &d, sizeof(d), hipMemcpyHostToDevice, m->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->fsm.state, &start, sizeof(start), hipMemcpyHostToDevice, m->stream);
-    const hipError_t es = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess || es != hipSuccess) {
-      // the descriptor may name the new buffers: keep them alive in the model, with the constraint off
+    rc = (int)hipMemsetD32Async((hipDeviceptr_t)(int32_t*)m->fsm.state, a->start, 1, m->stream);
+    const int rc2 = fsm_install(m, a, m->fsm, st);
+    if (rc != KH_OK || rc2 != KH_OK) {
       m->fsm_on = false;
-      m->fsm.mask = std::move(mask);
-      m->fsm.row_ptr = std::move(row_ptr);
-      m->fsm.tokens = std::move(tokens);
-      m->fsm.next = std::move(next);
-      return e != hipSuccess ? (int)e : (int)es;
+      return rc != KH_OK ? rc : rc2;
     }
-    m->fsm.mask = std::move(mask);
-    m->fsm.row_ptr = std::move(row_ptr);
-    m->fsm.tokens = std::move(tokens);
-    m->fsm.next = std::move(next);
-    m->fsm.n_states = a->n_states;
-    m->fsm.start = a->start;
-    m->fsm.h_row_ptr = std::move(h_row_ptr);
-    m->fsm.h_tokens = std::move(h_tokens);
     return KH_OK;
   });
 }

@@ -15,6 +15,12 @@
 //   k_seq_tail    one workgroup per lane: the step tails' pick chain (kh_logprobs.h: kh_tail_chain) on the lane's row -
 //                 the processing core on the slot's parameters and history, the maximum, the greedy or sampled pick,
 //                 the record of the lane's cache row
+// and, in place of either while the sequence-level constraint is set (kh_model_seq_set_constraint) and a lane of the
+// pass sits in a constrained slot:
+//   k_seq_tail_fsm  k_seq_tail's twin whose chain is given the automaton (kh_fsm.h) and the slot's word of the state
+//                 table: the row of the slot's state masks the lane's logits ahead of the processing core, the word
+//                 moves along the pick; a slot at -1 is neither masked nor moved.  A twin, not an argument: k_seq_tail
+//                 keeps its code and registers (both: 107 VGPR, 104 SGPR, 57928 B LDS, no scratch)
 // gfx950 only.
 #pragma once
 #include "kh_logprobs.h"
@@ -127,5 +133,33 @@ static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_tail(const KhSeq
     a.tok[slot] = pick;
     if (a.words) a.words[row] = pick;
     if (pos + 1 < a.cap[b]) a.hist[row + 1] = pick;
+  }
+}
+
+// ... and while the sequence-level constraint is set and a lane of the pass sits in a constrained slot
+// (kh_model_seq_set_constraint): a twin of k_seq_tail whose chain is given the automaton, so that k_seq_tail keeps its
+// code and registers - the rule of k_sample_proc_fsm.  One automaton serves every slot (sequences with different
+// constraints share a union, each from its own start state) and state[slot] is the slot's state word: the chain reads
+// it ahead of its first barrier, masks row b outside the state's row ahead of step 1 and moves the word along the pick
+// behind step 4.  A slot whose word is -1 (any word outside [0, n_states)) is unconstrained: the chain's out-of-range
+// path, no mask and no advance.  Lanes sit in distinct slots, so no two workgroups touch one word.
+struct KhSeqTailFsmArgs {
+  KhFsmRef fsm;  // the descriptor, and the state table [KH_SEQ_SLOTS_MAX]
+  KhSeqTailArgs t;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_seq_tail_fsm(const KhSeqTailFsmArgs a) {
+  const int b = blockIdx.x;
+  const int slot = a.t.lanes.slot[b], pos = a.t.lanes.pos[b], row = a.t.lanes.row[b];
+  const KhProcParams pp = a.t.proc[slot];
+  const KhSampParams p = a.t.params[slot];
+  const int pick =
+      kh_tail_chain(a.t.logits + (size_t)b * (size_t)a.t.vstride, a.t.vocab, a.t.hist + (row - pos), pos, pp,
+                    a.t.bias_ids + (size_t)slot * KH_SEQ_BIAS_MAX, a.t.bias + (size_t)slot * KH_SEQ_BIAS_MAX,
+                    a.t.cnt + (size_t)b * (size_t)a.t.vocab, p, a.t.top_n, a.t.recs, row,
+                    KhAmaxParts{nullptr, nullptr, 0}, KhFsmRef{a.fsm.desc, a.fsm.state + slot});
+  if (threadIdx.x == 0) {
+    a.t.tok[slot] = pick;
+    if (a.t.words) a.t.words[row] = pick;
+    if (pos + 1 < a.t.cap[b]) a.t.hist[row + 1] = pick;
   }
 }

@@ -703,6 +703,44 @@ class KuiperModel:
                    "kh_model_seq_fork")
         torch.cuda.synchronize()
 
+    def seq_set_constraint(self, automaton=None) -> None:
+        """Constrained decoding for sequences in slots (kh_model_seq_set_constraint): ONE constraint.TokenAutomaton for
+        all slots - constraint.union() lays different ones side by side - and one state per slot, all -1
+        (unconstrained) after this call.  seq_set_constraint_state(slot, s) puts a sequence under the constraint; from
+        then on every pass of seq_step / generate_batch / best_of masks that lane's logits to the row of its slot's
+        state ahead of penalties, bias, pick and record and moves the state along the pick, exactly as a batch-1 model
+        under set_constraint() does.  None turns it off.  One of this and set_constraint() is on at a time."""
+        if automaton is None:
+            _ffi.check(_ffi.lib().kh_model_seq_set_constraint(self._h, None), "kh_model_seq_set_constraint")
+            return
+        a, keep = _ffi.fsm(automaton.start, automaton.row_ptr, automaton.tokens, automaton.next)
+        _ffi.check(_ffi.lib().kh_model_seq_set_constraint(self._h, C.byref(a)), "kh_model_seq_set_constraint")
+        del keep
+        torch.cuda.synchronize()
+
+    def seq_constraint_state(self, slot: int) -> int:
+        """The automaton state of sequence slot `slot`, -1: unconstrained (kh_model_seq_get_constraint_state;
+        synchronises)."""
+        s = C.c_int32(0)
+        _ffi.check(_ffi.lib().kh_model_seq_get_constraint_state(self._h, int(slot), C.byref(s)),
+                   "kh_model_seq_get_constraint_state")
+        return int(s.value)
+
+    def seq_set_constraint_state(self, slot: int, state: int) -> None:
+        """Slot `slot` continues from `state` of the automaton (kh_model_seq_set_constraint_state); -1: unconstrained.
+        Fed-only positions do not move a state: walk forced text with TokenAutomaton.walk() and set the result."""
+        _ffi.check(_ffi.lib().kh_model_seq_set_constraint_state(self._h, int(slot), int(state)),
+                   "kh_model_seq_set_constraint_state")
+
+    def _seq_constrain(self, constraints) -> None:
+        """constraints= of generate_batch / best_of: the union of the given automata, set, every slot at its start."""
+        from . import constraint as _constraint
+        a, starts = _constraint.union(constraints)
+        self.seq_set_constraint(a)
+        for s, st in enumerate(starts):
+            if st >= 0:
+                self.seq_set_constraint_state(s, st)
+
     def seq_step(self, slots: Sequence[int], tokens: Sequence[int], pos: Sequence[int],
                  samplings: Optional[Sequence] = None, penalties: Optional[Sequence] = None,
                  logit_bias: Optional[Sequence] = None, logprobs: Optional[int] = None,
@@ -717,7 +755,8 @@ class KuiperModel:
         consulted.  With all three None this is the plain call.
         gemm=True: the wide pass on the matrix cores (kh_model_seq_step_gemm), up to seq_width(gemm=True) = 64 lanes.
         Not bit-identical to the batch-1 loop: logits and K/V rows agree to fp32 round-off, every pick is exact on the
-        pass's own logits (seq_gemm_logits)."""
+        pass's own logits (seq_gemm_logits).
+        Under seq_set_constraint() a lane whose slot holds a state >= 0 is masked to that state's row and moves it."""
         slots, tokens, pos = list(slots), list(tokens), list(pos)
         n = len(slots)
         if len(tokens) != n or len(pos) != n:
@@ -743,7 +782,8 @@ class KuiperModel:
                        stop: Sequence[int] = (), cached: Optional[Sequence[int]] = None,
                        penalties: Optional[Sequence] = None, logit_bias: Optional[Sequence] = None,
                        logprobs: Optional[int] = None, gemm: bool = False,
-                       gemm_prefill: bool = False) -> Tuple[List[List[int]], float]:
+                       gemm_prefill: bool = False,
+                       constraints: Optional[Sequence] = None) -> Tuple[List[List[int]], float]:
         """generate() for len(prompts) <= n_slots sequences at once, sequence s in slot s (kh_model_generate_batch):
         seq_width() sequences share every pass over the weights.  total_steps: one int for all or one per sequence;
         samplings: None (all greedy) or one entry per sequence (None | dict of temperature / top_k / top_p / seed).
@@ -759,7 +799,22 @@ class KuiperModel:
         near-ties, sampled words are the sampler's on the pass's own logits.
         gemm_prefill=True (orthogonal to gemm=): the fed-only part of every prompt that is not cached yet goes through
         one seq_prefill_many first - GEMM passes shared between the sequences instead of seq_prefill's passes per
-        sequence - and the call then runs with cached = len(prompt) - 1.  prefill_gemm()'s contract for those rows."""
+        sequence - and the call then runs with cached = len(prompt) - 1.  prefill_gemm()'s contract for those rows.
+        constraints: None, or one entry per sequence (None | constraint.TokenAutomaton): sequence s is sampled under
+        its automaton from the automaton's start state - constraint.union() of the entries is set with
+        seq_set_constraint(), every slot gets its start, and the constraint is turned off again behind the call.
+        Sequence s's words and records are then generate()'s of a batch-1 model under set_constraint(constraints[s]).
+        Without constraints= the call samples from whatever state seq_set_constraint_state() left in each slot."""
+        if constraints is not None and any(a is not None for a in constraints):
+            if len(constraints) != len(prompts):
+                raise ValueError(f"generate_batch: {len(constraints)} constraints for {len(prompts)} prompts")
+            self._seq_constrain(constraints)
+            try:
+                return self.generate_batch(prompts, total_steps, samplings, stop=stop, cached=cached,
+                                           penalties=penalties, logit_bias=logit_bias, logprobs=logprobs, gemm=gemm,
+                                           gemm_prefill=gemm_prefill)
+            finally:
+                self.seq_set_constraint(None)
         prompts = [list(p) for p in prompts]
         n = len(prompts)
         totals = [int(total_steps)] * n if isinstance(total_steps, (int, np.integer)) else [int(t) for t in total_steps]
@@ -827,7 +882,8 @@ class KuiperModel:
 
     def best_of(self, prompt: Sequence[int], n: int, total_steps: int, sampling: dict, stop: Sequence[int] = (),
                 penalties: Optional[dict] = None, logit_bias: Optional[dict] = None, top_n: int = 0,
-                share: bool = False, gemm: bool = False, gemm_prefill: bool = False) -> List[dict]:
+                share: bool = False, gemm: bool = False, gemm_prefill: bool = False,
+                constraints=None) -> List[dict]:
         """n samples of one prompt, best first: one seq_prefill of the prompt's fed-only part into slot 0, n - 1
         seq_forks, one generate_batch(cached=..) with seeds seed, seed + 1, .. of `sampling` (and the shared penalties
         / logit_bias), then seq_rank on the sampled positions' log-probs.  Returns [{"words", "mean_logprob", "seed"}]
@@ -838,7 +894,9 @@ class KuiperModel:
         n * (prompt + generated).  Same words and records; penalties are refused on sharing slots.
         gemm=True: the samples decode as wide passes (generate_batch(gemm=True)), up to 64 per pass over the weights;
         sample i is then the sampler's on the wide pass's logits, equal to generate()'s to fp32 round-off.
-        gemm_prefill=True: the one prefill is seq_prefill(.., gemm=True), the GEMM pass on the matrix cores."""
+        gemm_prefill=True: the one prefill is seq_prefill(.., gemm=True), the GEMM pass on the matrix cores.
+        constraints: None | one constraint.TokenAutomaton for all samples (generate_batch's constraints=, the same
+        entry n times): every sample is generate()'s of a batch-1 model under set_constraint() and its seed."""
         prompt, n, total_steps = [int(t) for t in prompt], int(n), int(total_steps)
         if n <= 0 or not prompt:
             raise ValueError("best_of: no sample, or an empty prompt")
@@ -860,7 +918,8 @@ class KuiperModel:
                     self.seq_fork(0, s, fed)
         words, _ = self.generate_batch([prompt] * n, total_steps, [dict(sampling, seed=seed0 + s) for s in range(n)],
                                        stop=stop, cached=[fed] * n, penalties=[penalties] * n,
-                                       logit_bias=[logit_bias] * n, logprobs=int(top_n), gemm=gemm)
+                                       logit_bias=[logit_bias] * n, logprobs=int(top_n), gemm=gemm,
+                                       constraints=None if constraints is None else [constraints] * n)
         rows = [self.seq_logprobs(s, 0, len(w))["logprob"] if w else np.empty(0, np.float32) for s, w in enumerate(words)]
         order, mean = seq_rank(rows, [min(fed, len(w)) for w in words], [len(w) for w in words])
         return [{"words": words[s], "mean_logprob": float(mean[s]), "seed": seed0 + s} for s in order]

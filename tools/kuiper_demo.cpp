@@ -74,6 +74,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -100,6 +101,52 @@ static int seq_feed_prompt(kh_model* m, const std::vector<int32_t>& prompt, int 
   return kh_model_seq_prefill_gemm(m, 1, &slot, prompt.data(), &n, &pos0);
 }
 
+// --choices "id,id,..;id,id,..": the token automaton of "answer with one of these" (kh_fsm) - the trie of the
+// sequences, each followed by `eos` into a sink whose only edge is `eos` onto itself (what the Python package's
+// constraint.from_choices builds).  State 0 is the root.  The arrays back the returned kh_fsm.
+struct ChoiceFsm {
+  std::vector<int64_t> row_ptr;
+  std::vector<int32_t> tokens, next;
+  kh_fsm a{0, 0, nullptr, nullptr, nullptr};
+};
+static bool build_choices(const std::vector<std::vector<int32_t>>& seqs, int32_t eos, ChoiceFsm* out) {
+  std::vector<std::map<int32_t, int32_t>> rows(1);
+  std::vector<int32_t> accepting;
+  for (const auto& seq : seqs) {
+    int32_t s = 0;
+    for (const int32_t t : seq) {
+      if (t == eos) return false;
+      auto it = rows[(size_t)s].find(t);
+      if (it == rows[(size_t)s].end()) {
+        rows.emplace_back();
+        it = rows[(size_t)s].emplace(t, (int32_t)rows.size() - 1).first;
+      }
+      s = it->second;
+    }
+    accepting.push_back(s);
+  }
+  const int32_t sink = (int32_t)rows.size();
+  rows.emplace_back();
+  rows[(size_t)sink][eos] = sink;
+  for (const int32_t s : accepting) rows[(size_t)s][eos] = sink;
+  out->row_ptr.assign(1, 0);
+  for (const auto& r : rows) {
+    for (const auto& e : r) {
+      out->tokens.push_back(e.first);
+      out->next.push_back(e.second);
+    }
+    out->row_ptr.push_back((int64_t)out->tokens.size());
+  }
+  out->a = kh_fsm{(int32_t)rows.size(), 0, out->row_ptr.data(), out->tokens.data(), out->next.data()};
+  return true;
+}
+// the sequence-level constraint of --parallel / --best-of: one automaton, every sample's slot at its start state
+static int seq_constrain(kh_model* m, const kh_fsm* a, int n) {
+  int rc = kh_model_seq_set_constraint(m, a);
+  for (int s = 0; s < n && rc == KH_OK; ++s) rc = kh_model_seq_set_constraint_state(m, s, a->start);
+  return rc;
+}
+
 static void usage() {
   std::fprintf(stderr,
                "usage: kuiper_demo model.bin [--family llama|qwen2] [--quant] [--rope interleaved|half]\n"
@@ -111,7 +158,9 @@ static void usage() {
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
                "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]\n"
-               "       [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]\n");
+               "       [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]\n"
+               "       [--choices \"id,id,..;id,id,..\"]  (answer with one of these, then the first --stop id; also\n"
+               "       beside --parallel / --best-of: every sample is constrained)\n");
 }
 
 int main(int argc, char** argv) {
@@ -136,6 +185,7 @@ int main(int argc, char** argv) {
   bool gemm_prefill = false;  // --gemm-prefill (kh_model_seq_prefill_gemm)
   int best_of = 0;   // --best-of N (kh_model_generate_batch_ex, kh_seq_rank)
   bool share_prefix = false;  // --share-prefix: the samples read the prompt's rows from slot 0 (kh_model_seq_share)
+  std::vector<std::vector<int32_t>> choices;  // --choices (kh_model_set_constraint / kh_model_seq_set_constraint)
   std::vector<int32_t> hint;  // --hint
   std::vector<int32_t> stop;  // is_sentence_ending ids (main.cpp:30): eos / <|eot_id|> / ...
   std::vector<int32_t> prompt{1, 263};  // BOS + "a": the reference demo's prompt (main.cpp:64)
@@ -198,6 +248,22 @@ int main(int argc, char** argv) {
       }
       bias_ids.push_back(std::atoi(e.substr(0, eq).c_str()));
       bias_vals.push_back(std::strtof(e.c_str() + eq + 1, nullptr));  // "-inf" parses
+    }
+    else if (a == "--choices") {
+      const std::string e = next();
+      choices.clear();
+      for (size_t p = 0; p <= e.size();) {  // sequences between ';', ids between ','
+        size_t q = e.find(';', p);
+        if (q == std::string::npos) q = e.size();
+        choices.emplace_back();
+        for (size_t i = p; i < q;) {
+          size_t j = e.find(',', i);
+          if (j == std::string::npos || j > q) j = q;
+          choices.back().push_back(std::atoi(e.substr(i, j - i).c_str()));
+          i = j + 1;
+        }
+        p = q + 1;
+      }
     }
     else if (a == "--text") {
       text = next();
@@ -356,6 +422,27 @@ int main(int argc, char** argv) {
     kh_model_destroy(m);
     return 1;
   }
+  ChoiceFsm cfsm;
+  if (!choices.empty()) {
+    // the end of an answer is the first stop id (is_sentence_ending): the runs below stop there
+    if (stop.empty() || !build_choices(choices, stop[0], &cfsm) || (rc = kh_fsm_check(&cfsm.a, c.vocab_size)) != KH_OK) {
+      std::fprintf(stderr, "--choices needs --stop (or a tokenizer), ids of the vocabulary and no stop id inside a choice\n");
+      kh_model_destroy(m);
+      return 2;
+    }
+    if (lookup || score) {
+      std::fprintf(stderr, "--choices does not go with --lookup or --score\n");
+      kh_model_destroy(m);
+      return 2;
+    }
+    // --parallel / --best-of constrain their slots below (kh_model_seq_set_constraint); one of the two at a time
+    if (parallel <= 0 && best_of <= 0 && (rc = kh_model_set_constraint(m, &cfsm.a)) != KH_OK) {
+      std::fprintf(stderr, "--choices failed: %d (%s)\n", rc, kh_error_string(rc));
+      kh_model_destroy(m);
+      return 1;
+    }
+    std::fprintf(stderr, "constraint: %zu choices, %d states, ends on token %d\n", choices.size(), cfsm.a.n_states, stop[0]);
+  }
   if (score) {
     if (logprobs < 0) {
       std::fprintf(stderr, "--score needs --logprobs N\n");
@@ -414,6 +501,7 @@ int main(int argc, char** argv) {
     std::printf("Generating...\n");
     const auto t0 = std::chrono::steady_clock::now();
     rc = seq_layout(m, N, have, steps, share_prefix, &slot_len);
+    if (rc == KH_OK && !choices.empty()) rc = seq_constrain(m, &cfsm.a, N);
     if (rc == KH_OK && have > 0) rc = seq_feed_prompt(m, prompt, have, gemm_prefill);
     for (int s = 1; s < N && rc == KH_OK && have > 0; ++s) rc = seq_attach(m, s, have, share_prefix);
     if (rc == KH_OK)
@@ -464,6 +552,7 @@ int main(int argc, char** argv) {
     std::printf("Generating...\n");
     const auto t0 = std::chrono::steady_clock::now();
     rc = seq_layout(m, parallel, have, steps, share_prefix, &slot_len);
+    if (rc == KH_OK && !choices.empty()) rc = seq_constrain(m, &cfsm.a, parallel);
     if (rc == KH_OK) rc = gemm_batch ? kh_model_seq_width_gemm(m, &width) : kh_model_seq_width(m, &width);
     if (rc == KH_OK && have > 0) rc = seq_feed_prompt(m, prompt, have, gemm_prefill);
     for (int s = 1; s < parallel && rc == KH_OK && have > 0; ++s) rc = seq_attach(m, s, have, share_prefix);
