@@ -694,10 +694,12 @@ int kh_model_get_logprobs(kh_model* m, int32_t pos0, int32_t n, int32_t* h_token
  * device call.
  * kh_model_get_constraint_state synchronises the stream; both state calls return KH_ERR_UNSUPPORTED while the
  * constraint is off, the setter KH_ERR_RANGE for a state outside [0, n_states).
- * While a constraint is set kh_model_verify*, kh_model_generate_lookup*, every kh_model_seq_* call that launches
- * (prefill, prefill_gemm, fork, step*) and kh_model_generate_batch* return KH_ERR_UNSUPPORTED before any launch (a row
- * of a B-token pass would need the state behind the previous rows' picks).  kh_model_score and the prefills are
- * untouched.  Sequences in slots are constrained by kh_model_seq_set_constraint ("Per-sequence constrained decoding"
+ * While a constraint is set kh_model_verify, kh_model_verify_as_set, kh_model_generate_lookup and
+ * kh_model_generate_lookup_as_set return KH_ERR_UNSUPPORTED before any launch: they know no automaton, and
+ * kh_model_verify_fsm / kh_model_generate_lookup_fsm ("Constrained lookup decode" below) are the calls that verify and
+ * draft under it.  Every kh_model_seq_* call that launches (prefill, prefill_gemm, fork, step*) and
+ * kh_model_generate_batch* refuse the same way (the slots have a constraint of their own).  kh_model_score and the
+ * prefills are untouched.  Sequences in slots are constrained by kh_model_seq_set_constraint ("Per-sequence constrained decoding"
  * below), a setting of its own with one state per slot; one of the two is on at a time, and kh_model_set_constraint
  * returns KH_ERR_UNSUPPORTED while that one is. */
 #define KH_FSM_MAX_MASK_BYTES (256 * 1024 * 1024)
@@ -746,7 +748,9 @@ int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0
  * log-prob settings are neither consulted nor touched.  Eager launches on the model stream (the pass, k_pf_cls,
  * k_spec_pick, k_spec_accept); synchronises.  A model that never calls this launches exactly what it launched before.
  * Before any launch: KH_ERR_INVALID_ARG for NULL pointers, n <= 0, pos0 < 0; KH_ERR_UNSUPPORTED for the geometries
- * kh_model_score refuses (the same predicate); KH_ERR_RANGE for n > width, pos0 + n > cache_len or a token outside
+ * kh_model_score refuses (the same predicate) and while kh_model_set_constraint is on - this call, kh_model_verify_as_set,
+ * kh_model_generate_lookup and kh_model_generate_lookup_as_set refuse there, kh_model_verify_fsm and
+ * kh_model_generate_lookup_fsm are the way; KH_ERR_RANGE for n > width, pos0 + n > cache_len or a token outside
  * [0, vocab_size). */
 int kh_model_verify_width(const kh_model* m, int32_t* width);
 int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next, int32_t* n_accept);
@@ -811,6 +815,44 @@ int kh_model_generate_lookup_as_set(kh_model* m, const int32_t* h_prompt, int32_
  * ngram_max 0 -> 4, ngram_min 0 -> 1. */
 int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t* hint, int32_t n_hint,
                     int32_t ngram_max, int32_t ngram_min, int32_t* out, int32_t cap);
+/* The drafter under a constraint (host only, stateless): the automaton drafts.  From `state` of `a`, until cap tokens
+ * are out or neither rule adds one: (a) while the row of the current state has exactly ONE edge, that token is emitted
+ * and the state moves along it - such a token is the pick under greedy and under every sampler, a raw logit of -inf or
+ * NaN aside; *n_forced (may be NULL) counts them; (b) otherwise kh_lookup_draft's proposal for seq + the tokens out so
+ * far, with the same hint and bounds and the remaining room, is cut to the longest prefix the automaton can follow from
+ * the current state, and the state moves along it; nothing kept: stop.  Every drafted token is followable: a loop built
+ * on this never feeds a token the mask would ban.  Returns the count, or before touching anything kh_fsm_check's codes
+ * for the automaton (any vocabulary), KH_ERR_RANGE for a state outside [0, n_states), kh_lookup_draft's
+ * KH_ERR_INVALID_ARG. */
+int kh_lookup_draft_fsm(const kh_fsm* a, int32_t state, const int32_t* seq, int32_t n_seq, const int32_t* hint,
+                        int32_t n_hint, int32_t ngram_max, int32_t ngram_min, int32_t* out, int32_t cap,
+                        int32_t* n_forced);
+
+/* Constrained lookup decode: the two _as_set calls under the model's constraint (kh_model_set_constraint).  A draft is
+ * accepted only where it equals the pick, so the only automaton state row b of a pass can be accepted in is the walk of
+ * the state word s over the fed tokens h_tokens[1..b] - known before the pass.  Row b is masked to the row of that state
+ * ahead of the penalties, the bias, the pick and the record, as a batch-1 step masks.
+ * kh_model_verify_fsm is kh_model_verify_as_set - its checks, its codes, its results - and runs while the constraint is
+ * on: h_next[i] = what a loop of kh_model_predict(.., KH_EXEC_FUSED) under the same constraint and settings returns at
+ * pos0 + i, from the state word as the call finds it; h_next[i] = -1 for every row behind a token h_tokens[k], 1 <= k
+ * <= i, that the automaton cannot follow (such a row cannot be accepted: the pick ahead of it lies in a row that does
+ * not hold the token).  Afterwards, beside what kh_model_verify_as_set leaves, the state word stands behind the last
+ * owned pick h_next[a] - kh_fsm_walk from the state at entry over h_next[0..a] - exactly where a batch-1 step leaves
+ * it: graph steps follow without a host-side reset.  Launches: k_spec_fsm_rows ahead of the pass (the state of every
+ * row; k_spec_hist's duty is part of it), the pass, k_pf_cls, k_spec_tail_fsm, k_spec_accept_fsm - with every
+ * combination of sampler, penalties, bias and log-probs, none included: the _as_set pass's launches plus at most one.
+ * With the constraint off it IS kh_model_verify_as_set.  The per-sequence constraint is not read.
+ * kh_model_generate_lookup_fsm is kh_model_generate_lookup_as_set with that pass and kh_lookup_draft_fsm as its
+ * drafter: the host tracks the state - `start`, then along every sampled word it reads - and drafts from it, forced
+ * tokens first; *n_forced (may be NULL) = drafted tokens that came from rule (a).  Words, *n_words, log-prob records
+ * and K/V rows are kh_model_generate_until's under the same constraint and settings.  After the call the state word
+ * stands behind the last pick the call owned, the stop token included where one ended it - unlike
+ * kh_model_generate_until, whose up to 16 steps past a stop move the state further. */
+int kh_model_verify_fsm(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
+                        int32_t* n_accept);
+int kh_model_generate_lookup_fsm(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
+                                 const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts, int32_t* h_words,
+                                 int32_t* n_words, float* h_elapsed_ms, kh_lookup_stats* stats, int32_t* n_forced);
 
 /* Sequence slots: several independent sequences in one model, decoded `width` per pass over the weights (best-of-n,
  * self-consistency, a handful of prompts at once).  The reference runs one sequence per process (demo/main.cpp).
@@ -1047,7 +1089,9 @@ int kh_plan_seq_batch_wide(int32_t n_seq, int32_t width, const int32_t* first_po
  * labels[s] = the smallest state of the weakly connected component of s; *emptied = 1 where the -inf entries of the
  * list (n <= KH_SEQ_BIAS_MAX, else KH_ERR_RANGE) empty a row of state's component (state -1: never).  Both return
  * kh_fsm_check's KH_ERR_INVALID_ARG codes for a malformed automaton.
- * Speculative verify and lookup stay refused under the batch-1 constraint and do not read this one. */
+ * Speculative verify and lookup do not read this constraint: kh_model_verify*, kh_model_generate_lookup* and the two
+ * _fsm calls run under it as they run without any.  Under the batch-1 constraint the four calls without _fsm refuse;
+ * kh_model_verify_fsm and kh_model_generate_lookup_fsm are the way. */
 int kh_model_seq_set_constraint(kh_model* m, const kh_fsm* a);
 int kh_model_seq_set_constraint_state(kh_model* m, int32_t slot, int32_t state);
 int kh_model_seq_get_constraint_state(kh_model* m, int32_t slot, int32_t* state);

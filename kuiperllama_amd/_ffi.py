@@ -27,7 +27,7 @@ EXPORTS = [
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
-    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_model_verify_as_set", "kh_model_generate_lookup_as_set", "kh_lookup_draft", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
+    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_model_verify_as_set", "kh_model_generate_lookup_as_set", "kh_lookup_draft", "kh_lookup_draft_fsm", "kh_model_verify_fsm", "kh_model_generate_lookup_fsm", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_q4", "kh_plan_gemm16", "kh_plan_gemm16_q8", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
@@ -288,6 +288,9 @@ def lib() -> C.CDLL:
     L.kh_model_verify_as_set.argtypes = L.kh_model_verify.argtypes
     L.kh_model_generate_lookup_as_set.argtypes = L.kh_model_generate_lookup.argtypes
     L.kh_lookup_draft.argtypes = [C.POINTER(_i32), _i32, C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32), _i32]
+    L.kh_lookup_draft_fsm.argtypes = [C.POINTER(Fsm), _i32] + L.kh_lookup_draft.argtypes + [C.POINTER(_i32)]
+    L.kh_model_verify_fsm.argtypes = L.kh_model_verify.argtypes
+    L.kh_model_generate_lookup_fsm.argtypes = L.kh_model_generate_lookup.argtypes + [C.POINTER(_i32)]
     L.kh_model_seq_slots.argtypes = [_vp, _i32, C.POINTER(_i32)]
     L.kh_plan_seq_slots.argtypes = [_i32, _i32, C.POINTER(_i32)]
     L.kh_model_seq_slots_var.argtypes = [_vp, _i32, C.POINTER(_i32)]

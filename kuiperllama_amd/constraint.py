@@ -71,6 +71,16 @@ class TokenAutomaton:
             s = nx
         return s, len(tokens)
 
+    def forced_run(self, state: int, cap: int) -> List[int]:
+        """The tokens that MUST follow from `state`, at most `cap`: while the row of the state holds exactly one id,
+        that id, and on along its edge (rule (a) of kh_lookup_draft_fsm; the sink's self-edge keeps a run going)."""
+        out, s = [], int(state)
+        while len(out) < cap and self.row_ptr[s + 1] - self.row_ptr[s] == 1:
+            e = int(self.row_ptr[s])
+            out.append(int(self.tokens[e]))
+            s = int(self.next[e])
+        return out
+
 
 def _from_rows(start: int, rows: List[dict]) -> TokenAutomaton:
     row_ptr, tokens, nxt = [0], [], []

@@ -31,7 +31,11 @@
 #include <algorithm>
 #include <vector>
 
+#if defined(__HIPCC__)
 #include "kh_common.h"
+#else
+#include "../../include/kuiper_hip.h"  // a plain host build (kh_lookup.h's drafter over an automaton): kh_fsm, KH_ERR_*
+#endif
 
 #define KH_FSM_THREADS 1024
 

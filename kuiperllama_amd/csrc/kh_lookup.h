@@ -10,6 +10,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "kh_fsm.h"  // (host part: kh_fsm, kh_fsm_edge_host - the drafter under a constraint, below)
+
 struct KhLookupCfg {
   int ngram_max, ngram_min, miss_steps;
 };
@@ -45,4 +47,43 @@ static inline int kh_lookup_draft_core(const int32_t* seq, int n_seq, const int3
       if (kh_lookup_match(seq + j, key, g)) return kh_lookup_copy(seq + j + g, n_seq - (j + g), out, cap);
   }
   return 0;
+}
+
+// ---- the drafter under a constraint (kh_model_generate_lookup_fsm, kh_lookup_draft_fsm): the automaton drafts.  From
+// `state`, until cap tokens are out or neither rule adds one:
+//   (a) while the row of the current state has exactly ONE edge: that token is the pick of every sampler (a raw logit
+//       of -inf or NaN aside) - emit it, move along it; *n_forced counts these;
+//   (b) otherwise kh_lookup_draft_core on seq + what is out so far, for the remaining room; of its proposal the longest
+//       prefix the automaton can follow from the current state is kept and followed; nothing kept: stop.
+// Every drafted token is followable, so a verify pass never feeds a token the mask would ban.  The automaton and the
+// state are checked by the caller (kh_fsm_check_host; 0 <= state < n_states), the bounds resolved.  `work` holds
+// n_seq + cap entries: seq, then the draft (rule (b) searches the text as it would stand).
+static inline int kh_lookup_draft_fsm_core(const kh_fsm* a, int32_t state, const int32_t* seq, int n_seq,
+                                           const int32_t* hint, int n_hint, int ngram_max, int ngram_min, int32_t* out,
+                                           int cap, int32_t* work, int32_t* n_forced) {
+  int n = 0, forced = 0;
+  for (int i = 0; i < n_seq; ++i) work[i] = seq[i];
+  while (n < cap) {
+    const int before = n;
+    while (n < cap && a->row_ptr[state + 1] - a->row_ptr[state] == 1) {  // (a)
+      const int64_t e = a->row_ptr[state];
+      out[n] = work[n_seq + n] = a->tokens[e];
+      state = a->next[e];
+      ++n;
+      ++forced;
+    }
+    if (n < cap) {  // (b)
+      const int d = kh_lookup_draft_core(work, n_seq + n, hint, n_hint, ngram_max, ngram_min, out + n, cap - n);
+      for (int i = 0; i < d; ++i) {
+        const int64_t e = kh_fsm_edge_host(a, state, out[n]);
+        if (e < 0) break;
+        work[n_seq + n] = out[n];
+        state = a->next[e];
+        ++n;
+      }
+    }
+    if (n == before) break;
+  }
+  if (n_forced) *n_forced = forced;
+  return n;
 }

@@ -175,6 +175,10 @@ struct kh_model {
   // ... under the model's settings (kh_model_verify_as_set; k_spec_tail): the processing core's counters per ROW of the
   // pass, [KH_PF_BMAX][vocab], zeroed once (the core re-arms them); made by the first such pass with processors on
   KhDev<int32_t> d_spec_cnt;
+  // ... and under its constraint (kh_model_verify_fsm; k_spec_fsm_rows): the automaton state of every row of the pass,
+  // [KH_PF_BMAX] - ahead of the row behind k_spec_fsm_rows, behind its pick behind k_spec_tail_fsm, -1: the row stands
+  // behind a fed token that cannot be followed; made by the first such pass
+  KhDev<int32_t> d_spec_fsm;
   // Sequence slots (kh_model_seq_slots, kh_model_seq.hip): the cache rows cut into seq_slots equal regions of
   // cache_len / seq_slots rows - bookkeeping, no kernel reads it.  Device tables with one entry per slot, one group
   // made by the first seq pass: the token the slot's sequence feeds next and its sampling parameters; the words of every
@@ -292,14 +296,15 @@ struct kh_model {
     int n_states = 0, start = 0;
     std::vector<int64_t> h_row_ptr;
     std::vector<int32_t> h_tokens;
+    std::vector<int32_t> h_next;  // (kh_model_generate_lookup_fsm walks the state on the host)
   };
   Fsm fsm;
   bool fsm_on = false;
   // The sequence-level constraint (kh_model_seq_set_constraint; k_seq_tail_fsm): one automaton for all slots, the same
   // buffers with a state table of KH_SEQ_SLOTS_MAX words, -1 = the slot is unconstrained.  One of the two constraints is
   // on at a time.  seq_fsm_state: the state the host last set per slot - it decides whether a pass ends in
-  // k_seq_tail_fsm and which rows a lane's -inf bias is checked against (seq_fsm_reach; h_next is not kept: the host
-  // never walks).  The device moves the words; a word that was set >= 0 stays >= 0.
+  // k_seq_tail_fsm and which rows a lane's -inf bias is checked against (seq_fsm_reach; the host never walks
+  // these).  The device moves the words; a word that was set >= 0 stays >= 0.
   Fsm seq_fsm;
   bool seq_fsm_on = false;
   int32_t seq_fsm_state[KH_SEQ_SLOTS_MAX];
@@ -610,13 +615,16 @@ bool full_depth_supported(const kh_model* m);
 int verify_width(const kh_model* m);
 // the buffers of a verify pass that reaches cache rows [0, rows): before the first verify_enqueue of a call.  as_set:
 // of a pass under the model's settings - the row counters too, where the settings need them
-int verify_prepare(kh_model* m, int rows, bool as_set = false);
+// fsm (with as_set, while the constraint is on): the rows' state words as well
+int verify_prepare(kh_model* m, int rows, bool as_set = false, bool fsm = false);
 // One verify pass of toks[0 .. n), 1 <= n <= verify_width, at positions pos0 ..: the full-depth pass, k_pf_cls,
 // k_spec_pick, k_spec_accept and the copy of the result block into m->h_spec_pin {a, pick[0 .. n)}, all enqueued on the
 // model stream; the caller synchronises before it reads the block.  Arguments are the caller's to check.
 // as_set: the picks are made under the model's sampler, penalties, logit bias and log-probs - where any of them is on,
 // k_spec_hist, k_spec_tail and k_spec_accept_set take the place of the last two launches; where none is, nothing changes.
-int verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool as_set = false);
+// fsm (with as_set, while the constraint is on): the pass under the constraint as well - k_spec_fsm_rows (k_spec_hist's
+// duty is part of it), k_spec_tail_fsm and k_spec_accept_fsm, whatever else is set; the model's state word follows.
+int verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool as_set = false, bool fsm = false);
 // Sequence slots (kh_model_seq.hip drives these; arguments are the caller's to check).  seq_prepare: the buffers of
 // a pass, before the first enqueue of a call.  seq_prefill_enqueue: kh_model_prefill's passes for n tokens at
 // positions pos0 .. of the sequence whose position 0 is cache row row0.  seq_pass_enqueue: one full-depth pass over

@@ -356,7 +356,7 @@ extern "C" int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, i
 
 // ---- speculative greedy decode: the verify pass (kh_spec.h) ---------------------------------------------------------
 int khm::verify_width(const kh_model* m) { return prefill_batch(m); }
-int khm::verify_prepare(kh_model* m, int rows, bool as_set) {
+int khm::verify_prepare(kh_model* m, int rows, bool as_set, bool fsm) {
   int rc;
   if ((rc = kv_ensure(m, rows)) != KH_OK) return rc;
   if ((rc = ensure_prefill_buffers(m)) != KH_OK) return rc;
@@ -368,6 +368,11 @@ int khm::verify_prepare(kh_model* m, int rows, bool as_set) {
     KH_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * n, m->stream));  // once: the core re-arms them
     m->d_spec_cnt = std::move(cnt);
   }
+  if (as_set && fsm && m->fsm_on && !m->d_spec_fsm) {
+    KhDev<int32_t> words;
+    if ((rc = words.alloc(KH_PF_BMAX)) != KH_OK) return rc;
+    m->d_spec_fsm = std::move(words);
+  }
   if (m->d_spec) return KH_OK;
   KhDev<int32_t> spec;
   KhPin<int32_t> pin;
@@ -376,18 +381,24 @@ int khm::verify_prepare(kh_model* m, int rows, bool as_set) {
   m->h_spec_pin = std::move(pin);
   return KH_OK;
 }
-int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool as_set) {
+int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool as_set, bool fsm) {
   const kh_config& c = m->cfg;
   const int B = prefill_batch(m);
+  // the constrained form: the tail's twins with the automaton, whatever else is set (the chain is the greedy pick then)
+  fsm = fsm && as_set && m->fsm_on;
   // the tail of the pass under the settings; with none of them on the greedy pair below is that tail
-  const bool tail = as_set && (m->samp_on || m->proc_on || m->lp_top_n >= 0);
+  const bool tail = fsm || (as_set && (m->samp_on || m->proc_on || m->lp_top_n >= 0));
   KhSpecAcceptArgs t;
   t.hist = m->d_hist;
   t.hist_cap = m->hist_cap;
   for (int b = 0; b < KH_PF_BMAX; ++b) t.fed[b] = b < n ? toks[b] : -1;
   t.pos0 = pos0;
   t.n = n;
-  if (tail && m->proc_on) {  // the record the rows' windows read, ahead of them on the stream
+  if (fsm) {  // the state ahead of every row - and the record, k_spec_hist's duty
+    launch_log("k_spec_fsm_rows");
+    hipLaunchKernelGGL(k_spec_fsm_rows, dim3(1), dim3(KH_FSM_THREADS), 0, m->stream, t, (const KhFsmDev*)m->fsm.desc,
+                       (const int32_t*)m->fsm.state, (int32_t*)m->d_spec_fsm);
+  } else if (tail && m->proc_on) {  // the record the rows' windows read, ahead of them on the stream
     launch_log("k_spec_hist");
     hipLaunchKernelGGL(k_spec_hist, dim3(1), dim3(KH_WAVE), 0, m->stream, t);
   }
@@ -410,8 +421,14 @@ int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool 
     a.top_n = records ? (const int32_t*)m->d_lp_top_n : nullptr;
     a.recs = recs;
     a.res = m->d_spec;
-    launch_log("k_spec_tail");
-    hipLaunchKernelGGL(k_spec_tail, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, a);
+    if (fsm) {
+      const KhSpecTailFsmArgs af{KhFsmRef{m->fsm.desc, m->d_spec_fsm}, a};
+      launch_log("k_spec_tail_fsm");
+      hipLaunchKernelGGL(k_spec_tail_fsm, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, af);
+    } else {
+      launch_log("k_spec_tail");
+      hipLaunchKernelGGL(k_spec_tail, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, a);
+    }
   } else {
     launch_log("k_spec_pick");
     hipLaunchKernelGGL(k_spec_pick, dim3(n), dim3(KH_SAMP_THREADS), 0, m->stream, (const float*)m->pf_logits,
@@ -428,9 +445,15 @@ int khm::verify_enqueue(kh_model* m, const int32_t* toks, int n, int pos0, bool 
   t.dim = c.dim;
   t.vocab = c.vocab_size;
   if (tail) {
-    launch_log("k_spec_accept_set");
-    hipLaunchKernelGGL(k_spec_accept_set, dim3(1), dim3(KH_WG), 0, m->stream,
-                       KhSpecAcceptSetArgs{t, records ? recs : KhTailRecs{nullptr, nullptr, nullptr, nullptr}, m->lp_cap});
+    const KhSpecAcceptSetArgs s{t, records ? recs : KhTailRecs{nullptr, nullptr, nullptr, nullptr}, m->lp_cap};
+    if (fsm) {
+      launch_log("k_spec_accept_fsm");
+      hipLaunchKernelGGL(k_spec_accept_fsm, dim3(1), dim3(KH_WG), 0, m->stream,
+                         KhSpecAcceptFsmArgs{s, (const int32_t*)m->d_spec_fsm, (int32_t*)m->fsm.state});
+    } else {
+      launch_log("k_spec_accept_set");
+      hipLaunchKernelGGL(k_spec_accept_set, dim3(1), dim3(KH_WG), 0, m->stream, s);
+    }
   } else {
     launch_log("k_spec_accept");
     hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(KH_WG), 0, m->stream, t);
@@ -572,17 +595,17 @@ extern "C" int kh_model_verify_width(const kh_model* m, int32_t* width) {
 }
 // One verify pass.  Eager launches on the model stream; every check before the first of them.
 static int verify_call(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
-                       int32_t* n_accept, bool as_set) {
+                       int32_t* n_accept, bool as_set, bool fsm = false) {
   if (!m || !h_tokens || !h_next || !n_accept || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
-  // (a constraint: a row's mask would need the state behind the previous rows' picks)
-  if (m->fsm_on || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
+  // (a constraint: kh_model_verify_fsm is the call for it - its rows take their states from k_spec_fsm_rows)
+  if ((m->fsm_on && !fsm) || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;
   if (n > verify_width(m) || (int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
   if (!tokens_in_vocab(m, h_tokens, n)) return KH_ERR_RANGE;
   KH_CHECK_HIP(hipSetDevice(m->opts.device));
   int rc;
-  if ((rc = verify_prepare(m, pos0 + n, as_set)) != KH_OK) return rc;
-  rc = verify_enqueue(m, h_tokens, n, pos0, as_set);
+  if ((rc = verify_prepare(m, pos0 + n, as_set, fsm)) != KH_OK) return rc;
+  rc = verify_enqueue(m, h_tokens, n, pos0, as_set, fsm);
   const hipError_t e = hipStreamSynchronize(m->stream);  // drained on every way out
   if (rc != KH_OK) return rc;
   if (e != hipSuccess) return (int)e;
@@ -597,6 +620,10 @@ extern "C" int kh_model_verify(kh_model* m, const int32_t* h_tokens, int32_t n, 
 extern "C" int kh_model_verify_as_set(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
                                       int32_t* n_accept) {
   return verify_call(m, h_tokens, n, pos0, h_next, n_accept, /*as_set=*/true);
+}
+extern "C" int kh_model_verify_fsm(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, int32_t* h_next,
+                                   int32_t* n_accept) {
+  return verify_call(m, h_tokens, n, pos0, h_next, n_accept, /*as_set=*/true, /*fsm=*/true);
 }
 
 // Time the prompt phase alone: n fed-only tokens at positions pos0.., HIP events on the model

@@ -957,6 +957,7 @@ int khm::fsm_install(kh_model* m, const kh_fsm* a, kh_model::Fsm& f, FsmStage& s
   f.start = a->start;
   f.h_row_ptr = std::move(st.h_row_ptr);
   f.h_tokens = std::move(st.h_tokens);
+  f.h_next.assign(a->next, a->next + n_edges);
   return KH_OK;
 }
 extern "C" int kh_model_set_constraint(kh_model* m, const kh_fsm* a) {
@@ -1350,6 +1351,23 @@ extern "C" int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t*
     return KH_ERR_INVALID_ARG;
   return kh_lookup_draft_core(seq, n_seq, hint, n_hint, cfg.ngram_max, cfg.ngram_min, out, cap);
 }
+extern "C" int kh_lookup_draft_fsm(const kh_fsm* a, int32_t state, const int32_t* seq, int32_t n_seq, const int32_t* hint,
+                                   int32_t n_hint, int32_t ngram_max, int32_t ngram_min, int32_t* out, int32_t cap,
+                                   int32_t* n_forced) {
+  KhLookupCfg cfg;
+  // every check before anything is touched: the automaton's (kh_fsm_check, any vocabulary), then the drafter's
+  const int rc = kh_fsm_check_host(a, INT64_MAX);
+  if (rc != KH_OK) return rc;
+  if (state < 0 || state >= a->n_states) return KH_ERR_RANGE;
+  if (n_seq < 0 || n_hint < 0 || cap < 0 || (n_seq > 0 && !seq) || (n_hint > 0 && !hint) || (cap > 0 && !out) ||
+      !kh_lookup_resolve(ngram_max, ngram_min, 0, &cfg))
+    return KH_ERR_INVALID_ARG;
+  return kh_api_guard([&]() -> int {
+    std::vector<int32_t> work((size_t)n_seq + (size_t)cap);
+    return kh_lookup_draft_fsm_core(a, state, seq, n_seq, hint, n_hint, cfg.ngram_max, cfg.ngram_min, out, cap,
+                                    work.data(), n_forced);
+  });
+}
 
 // kh_model_generate_until's graph form with the sampled part driven by draft + verify: at position p a draft of d >= 1
 // tokens costs one verify pass and yields a + 1 words, no draft costs miss_steps steps on the step graphs.  The host
@@ -1357,9 +1375,15 @@ extern "C" int kh_lookup_draft(const int32_t* seq, int32_t n_seq, const int32_t*
 // as_set = false: greedy on the raw logits, any setting is refused.  as_set = true: the pass picks under the model's
 // settings (verify_enqueue) as the plain steps do (step_tail); a draft is accepted where it EQUALS that pick - the
 // seeded draw depends on (seed, position) and the logits alone - so the words are generate_until's either way.
+// fsm (with as_set): the call that runs under the model's constraint.  The host tracks the automaton state - `start` as
+// generate_begin sets the device word, then along every sampled word it reads, on the model's host copy of the automaton -
+// and drafts from it with kh_lookup_draft_fsm_core: forced tokens first, n-gram proposals cut to what the automaton can
+// follow.  The passes are verify_enqueue's constrained form, the plain steps' tails are the _fsm ones already.  A stop
+// among the owned picks: the device word is set behind it (the pass or the steps moved it further).
 static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
                                const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts, int32_t* h_words,
-                               int32_t* n_words, float* h_elapsed_ms, kh_lookup_stats* stats, bool as_set) {
+                               int32_t* n_words, float* h_elapsed_ms, kh_lookup_stats* stats, bool as_set,
+                               bool fsm = false, int32_t* n_forced = nullptr) {
   if (!m || !h_prompt || n_prompt <= 0 || total_steps <= 0 || !h_words || !n_words || n_stop < 0 ||
       (n_stop > 0 && !h_stop))
     return KH_ERR_INVALID_ARG;
@@ -1373,7 +1397,7 @@ static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_p
   if (!tokens_in_vocab(m, o.h_hint, o.n_hint)) return KH_ERR_RANGE;
   // only where the verify pass runs and, unless as_set, greedy on the raw logits only: no silent fallback to
   // generate_until
-  if (m->fsm_on || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;  // (a constraint: as kh_model_verify)
+  if ((m->fsm_on && !fsm) || !full_depth_supported(m)) return KH_ERR_UNSUPPORTED;  // (a constraint: as kh_model_verify)
   if (!as_set && (m->samp_on || m->proc_on || m->lp_top_n >= 0)) return KH_ERR_UNSUPPORTED;
   return kh_api_guard([&]() -> int {
     KH_CHECK_HIP(hipSetDevice(m->opts.device));
@@ -1386,7 +1410,17 @@ static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_p
     };
     std::vector<int32_t> seq(h_prompt, h_prompt + n_prompt);  // seq[i] = the token of position i, as far as known
     seq.reserve((size_t)total_steps + KH_GRAPH_STEPS + 1);
-    if ((rc = verify_prepare(m, total_steps, as_set)) != KH_OK) return rc;
+    if ((rc = verify_prepare(m, total_steps, as_set, fsm)) != KH_OK) return rc;
+    // the constraint, as the host sees it
+    const bool fsm_run = fsm && m->fsm_on;
+    const kh_fsm A{m->fsm.n_states, m->fsm.start, m->fsm.h_row_ptr.data(), m->fsm.h_tokens.data(), m->fsm.h_next.data()};
+    int32_t hs = m->fsm.start;
+    auto fsm_move = [&](int32_t w) {  // (a word its row does not hold leaves the state, as kh_fsm_advance_core does)
+      const int64_t e = fsm_run ? kh_fsm_edge_host(&A, hs, w) : -1;
+      if (e >= 0) hs = A.next[e];
+    };
+    std::vector<int32_t> work(fsm_run ? (size_t)total_steps + KH_GRAPH_STEPS + 1 : 0);
+    int forced_total = 0;
     GenRun g;
     if ((rc = generate_begin(m, h_prompt, n_prompt, total_steps, KH_EXEC_GRAPH, &g)) != KH_OK) return fail(rc);
     const int width = verify_width(m);
@@ -1401,17 +1435,24 @@ static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_p
       int32_t fed[KH_GRAPH_STEPS];
       int d = 0;
       if (sampled && !first) {
-        const int room = total_steps - 1 - p;
-        d = kh_lookup_draft_core(seq.data(), p + 1, o.h_hint, o.n_hint, cfg.ngram_max, cfg.ngram_min, fed + 1,
-                                 width - 1 < room ? width - 1 : room);
+        const int room = total_steps - 1 - p, cap = width - 1 < room ? width - 1 : room;
+        if (fsm_run) {
+          int32_t forced = 0;
+          d = kh_lookup_draft_fsm_core(&A, hs, seq.data(), p + 1, o.h_hint, o.n_hint, cfg.ngram_max, cfg.ngram_min,
+                                       fed + 1, cap, work.data(), &forced);
+          forced_total += forced;
+        } else {
+          d = kh_lookup_draft_core(seq.data(), p + 1, o.h_hint, o.n_hint, cfg.ngram_max, cfg.ngram_min, fed + 1, cap);
+        }
       }
       if (d > 0) {
         fed[0] = seq[(size_t)p];
-        if ((rc = verify_enqueue(m, fed, d + 1, p, as_set)) != KH_OK) return fail(rc);
+        if ((rc = verify_enqueue(m, fed, d + 1, p, as_set, fsm)) != KH_OK) return fail(rc);
         if (hipStreamSynchronize(m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
         const int a = m->h_spec_pin[0];
         for (int i = 0; i <= a && stop_at < 0; ++i) {
           const int32_t w = m->h_spec_pin[1 + i];
+          fsm_move(w);
           if (is_stop(w, h_stop, n_stop)) {
             stop_at = p + i;
           } else {
@@ -1440,6 +1481,7 @@ static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_p
             hipStreamSynchronize(m->stream) != hipSuccess)
           return fail((int)hipErrorUnknown);
         for (int s = p; s < p + k && stop_at < 0; ++s) {
+          if (s >= n_prompt - 1) fsm_move(pin[s]);
           if (s >= n_prompt - 1 && is_stop(pin[s], h_stop, n_stop))
             stop_at = s;
           else if (s + 1 >= (int)seq.size())
@@ -1450,6 +1492,10 @@ static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_p
       }
     }
     if (hipEventRecord(m->ev1, m->stream) != hipSuccess) return fail((int)hipErrorUnknown);
+    // the state behind the stop: the pass or the steps that met it moved the device word past it
+    if (fsm_run && stop_at >= 0 &&
+        hipMemsetD32Async((hipDeviceptr_t)(int32_t*)m->fsm.state, hs, 1, m->stream) != hipSuccess)
+      return fail((int)hipErrorUnknown);
     if ((rc = kh_launch_status()) != KH_OK) return fail(rc);
     KH_CHECK_HIP(hipStreamSynchronize(m->stream));
     m->forced_in_flight = false;
@@ -1457,6 +1503,7 @@ static int generate_lookup_run(kh_model* m, const int32_t* h_prompt, int32_t n_p
     memcpy(h_words, pin, sizeof(int32_t) * (size_t)n_out);
     if (h_elapsed_ms) KH_CHECK_HIP(hipEventElapsedTime(h_elapsed_ms, m->ev0, m->ev1));
     if (stats) *stats = st;
+    if (n_forced) *n_forced = forced_total;
     *n_words = n_out;
     return KH_OK;
   });
@@ -1474,4 +1521,11 @@ extern "C" int kh_model_generate_lookup_as_set(kh_model* m, const int32_t* h_pro
                                                float* h_elapsed_ms, kh_lookup_stats* stats) {
   return generate_lookup_run(m, h_prompt, n_prompt, total_steps, h_stop, n_stop, opts, h_words, n_words, h_elapsed_ms,
                              stats, /*as_set=*/true);
+}
+extern "C" int kh_model_generate_lookup_fsm(kh_model* m, const int32_t* h_prompt, int32_t n_prompt, int32_t total_steps,
+                                            const int32_t* h_stop, int32_t n_stop, const kh_lookup_opts* opts,
+                                            int32_t* h_words, int32_t* n_words, float* h_elapsed_ms,
+                                            kh_lookup_stats* stats, int32_t* n_forced) {
+  return generate_lookup_run(m, h_prompt, n_prompt, total_steps, h_stop, n_stop, opts, h_words, n_words, h_elapsed_ms,
+                             stats, /*as_set=*/true, /*fsm=*/true, n_forced);
 }

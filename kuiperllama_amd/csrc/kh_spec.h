@@ -14,6 +14,16 @@
 //                      draw with counter = position, the log-prob record.  What a batch-1 step picks on the same logits.
 //   k_spec_accept_set  k_spec_accept's duties on those picks, the record entry the next step's window reads and "none"
 //                      (kh_rec_none) over the log-prob records of the rejected positions
+// Under the model's constraint (kh_model_verify_fsm, kh_model_generate_lookup_fsm; kh_fsm.h) the three have twins:
+//   k_spec_fsm_rows    k_spec_hist's duty, and the automaton state AHEAD of every row: rows[0] = the model's state word,
+//                      rows[b] = next(rows[b - 1], fed[b]), -1 from the first fed token its row does not hold.  A draft is
+//                      accepted only where it equals the pick, so the only state row b can be accepted in is the walk
+//                      of the state word over fed[1 .. b] - known before the pass.
+//   k_spec_tail_fsm    k_spec_tail with the chain given the automaton and rows[b]: mask ahead of the processors, the
+//                      transition behind the pick - rows[b] then holds the state BEHIND row b's pick.  A row at -1
+//                      cannot be accepted: it leaves at once with pick -1.
+//   k_spec_accept_fsm  k_spec_accept_set, and the model's state word = rows[a]: behind the last owned pick, where a
+//                      batch-1 step leaves it.
 // The accept gathers the next token's embedding row with the step tails' kh_embed_gather (kh_step_tail.h).
 // gfx950 only.
 #pragma once
@@ -125,6 +135,77 @@ static __global__ __launch_bounds__(KH_WG) void k_spec_accept_set(const KhSpecAc
   if (threadIdx.x == 0) {
     const int at = s.t.pos0 + a0 + 1;
     if (at < s.t.hist_cap) s.t.hist[at] = s.t.res[1 + a0];
+    s_a = a0;
+  }
+  __syncthreads();
+  if (!s.recs.token) return;  // uniform
+  const int n = s.t.n < KH_PF_BMAX ? s.t.n : KH_PF_BMAX;
+  for (int i = s_a + 1; i < n; ++i) {
+    const int pos = s.t.pos0 + i;
+    if (pos >= s.rec_cap) break;
+    kh_rec_none(s.recs, pos, -1);
+  }
+}
+
+// ---- the same pass under the model's settings AND its constraint (kh_fsm.h) ------------------------------------------
+// One workgroup of KH_FSM_THREADS, ahead of the pass: k_spec_hist's entries, then rows[b] = the state ahead of row b.
+// Each transition is kh_fsm_advance_core's strided search by the whole workgroup (no thread bisects: a row of V ids is
+// 128 compares per thread, all in flight), handed on through one LDS word with barriers between the steps.
+static __global__ __launch_bounds__(KH_FSM_THREADS) void k_spec_fsm_rows(const KhSpecAcceptArgs t, const KhFsmDev* desc,
+                                                                         const int32_t* state, int32_t* rows) {
+  __shared__ int32_t s_cur;
+  const int i = threadIdx.x, pos = t.pos0 + i;
+  const int n = t.n < KH_PF_BMAX ? t.n : KH_PF_BMAX;
+  if (i < n && pos >= 0 && pos < t.hist_cap) t.hist[pos] = t.fed[i];
+  if (i == 0) s_cur = *state;
+  for (int b = 0; b < KH_PF_BMAX; ++b) {  // uniform
+    __syncthreads();
+    const int cur = b < n ? s_cur : -1;
+    if (i == 0) rows[b] = cur;
+    if (b + 1 >= n) continue;
+    __syncthreads();  // every thread holds cur: the word may change
+    if (i == 0) s_cur = -1;
+    __syncthreads();
+    kh_fsm_advance_core(*desc, cur, t.fed[b + 1], &s_cur);  // (cur == -1: nothing; no edge: the word stays -1)
+  }
+}
+
+struct KhSpecTailFsmArgs {
+  KhFsmRef fsm;  // the descriptor, and rows [KH_PF_BMAX] (k_spec_fsm_rows)
+  KhSpecTailArgs t;
+};
+static __global__ __launch_bounds__(KH_SAMP_THREADS) void k_spec_tail_fsm(const KhSpecTailFsmArgs f) {
+  const KhSpecTailArgs& a = f.t;
+  const int b = blockIdx.x;
+  if (b >= KH_PF_BMAX) return;  // uniform
+  int32_t* const word = f.fsm.state + b;
+  if (*word < 0) {  // uniform: behind a fed token that cannot be followed
+    if (threadIdx.x == 0) a.res[1 + b] = -1;
+    return;
+  }
+  const int pos = a.pos0 + b;
+  const KhProcParams pp = a.proc ? *a.proc : KhProcParams{1.f, 0.f, 0.f, 0, 0};
+  const KhSampParams p = a.params ? *a.params : KhSampParams{};
+  const int top_n = a.top_n ? max(*a.top_n, 0) : -1;
+  const int pick = kh_tail_chain(a.logits + (size_t)b * (size_t)a.vstride, a.vocab, a.hist, pos, pp, a.bias_ids, a.bias,
+                                 a.cnt + (size_t)b * (size_t)a.vocab, p, top_n, a.recs, pos,
+                                 KhAmaxParts{nullptr, nullptr, 0}, KhFsmRef{f.fsm.desc, word});
+  if (threadIdx.x == 0) a.res[1 + b] = pick;
+}
+
+struct KhSpecAcceptFsmArgs {
+  KhSpecAcceptSetArgs s;
+  const int32_t* rows;  // [KH_PF_BMAX] behind k_spec_tail_fsm: the state behind every row's pick
+  int32_t* state;       // the model's state word
+};
+static __global__ __launch_bounds__(KH_WG) void k_spec_accept_fsm(const KhSpecAcceptFsmArgs f) {
+  const KhSpecAcceptSetArgs& s = f.s;
+  __shared__ int s_a;
+  const int a0 = kh_spec_accept_body(s.t);
+  if (threadIdx.x == 0) {
+    const int at = s.t.pos0 + a0 + 1;
+    if (at < s.t.hist_cap) s.t.hist[at] = s.t.res[1 + a0];
+    *f.state = f.rows[a0];
     s_a = a0;
   }
   __syncthreads();

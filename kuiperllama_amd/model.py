@@ -175,6 +175,23 @@ def lookup_draft(seq: Sequence[int], hint: Optional[Sequence[int]] = None, ngram
     return list(out[:n])
 
 
+def lookup_draft_fsm(automaton, state: int, seq: Sequence[int], hint: Optional[Sequence[int]] = None,
+                     ngram_max: int = 4, ngram_min: int = 1, cap: int = 7) -> Tuple[List[int], int]:
+    """The drafter of generate_lookup(constrained=True) (kh_lookup_draft_fsm; host only, no device): from `state` of
+    the constraint.TokenAutomaton, the tokens of single-edge rows - forced, whatever the model says - and, where a row
+    holds more, lookup_draft's proposal cut to what the automaton can follow.  Returns (tokens, n_forced)."""
+    seq, hint = list(seq), list(hint or [])
+    a, keep = _ffi.fsm(automaton.start, automaton.row_ptr, automaton.tokens, automaton.next)
+    out = (C.c_int32 * max(int(cap), 1))()
+    forced = C.c_int32(0)
+    n = _ffi.lib().kh_lookup_draft_fsm(C.byref(a), int(state), _i32_array(seq), len(seq), _i32_array(hint), len(hint),
+                                       int(ngram_max), int(ngram_min), out, int(cap), C.byref(forced))
+    del keep
+    if n < 0:
+        raise _ffi.KhError(n, "kh_lookup_draft_fsm")
+    return list(out[:n]), int(forced.value)
+
+
 class KuiperModel:
     """Owns a kh_model handle.  Construct with one of the from_* classmethods."""
 
@@ -583,17 +600,21 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_verify_width(self._h, C.byref(w)), "kh_model_verify_width")
         return int(w.value)
 
-    def verify(self, tokens: Sequence[int], pos0: int, as_set: bool = False) -> Tuple[np.ndarray, int]:
+    def verify(self, tokens: Sequence[int], pos0: int, as_set: bool = False,
+               constrained: bool = False) -> Tuple[np.ndarray, int]:
         """One verify pass (kh_model_verify): feeds tokens[0] - known - and the drafts tokens[1:] at positions pos0 ..
         in one sweep of the weights.  Returns (next, n_accept): next[i] is the greedy pick at position pos0 + i given
         tokens[:i + 1]; the caller owns next[:n_accept + 1], exactly the tokens a loop of predict() returns, and the
         decode state stands behind them.  as_set (kh_model_verify_as_set): the picks are made under the model's
         sampler, penalties, logit bias and log-probs - what a loop of predict() returns under the same settings -
-        and with log-probs on the records of the accepted positions are written."""
+        and with log-probs on the records of the accepted positions are written.  constrained (kh_model_verify_fsm):
+        as_set under set_constraint() as well - every row is masked to the row of the automaton state behind the fed
+        tokens ahead of it, next[i] is -1 behind a token the automaton cannot follow, and constraint_state stands
+        behind next[n_accept] afterwards."""
         n = len(tokens)
         nxt = np.full(max(n, 1), -1, np.int32)
         a = C.c_int32(-1)
-        name = "kh_model_verify_as_set" if as_set else "kh_model_verify"
+        name = "kh_model_verify_fsm" if constrained else "kh_model_verify_as_set" if as_set else "kh_model_verify"
         _ffi.check(getattr(_ffi.lib(), name)(self._h, _i32_array(tokens), n, int(pos0),
                                              nxt.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(a)), name)
         return nxt[:n], int(a.value)
@@ -601,13 +622,15 @@ class KuiperModel:
     def generate_lookup(self, prompt: Sequence[int], total_steps: int, stop: Sequence[int] = (), ngram_max: int = 4,
                         ngram_min: int = 1, miss_steps: int = 8,
                         hint: Optional[Sequence[int]] = None,
-                        as_set: bool = False) -> Tuple[List[int], float, dict]:
+                        as_set: bool = False, constrained: bool = False) -> Tuple[List[int], float, dict]:
         """generate(exec="graph") with the sampled part driven by draft + verify (kh_model_generate_lookup): the same
         words, several per sweep of the weights wherever lookup_draft's guess - from the text so far and the optional
         `hint`, the expected output - is right.  Greedy only, unless as_set (kh_model_generate_lookup_as_set): then the
         passes pick under the model's sampler, penalties, logit bias and log-probs, and the words and records are
         generate()'s under the same settings.  Returns (words, elapsed_ms, stats) with stats = {"passes", "drafted",
-        "accepted", "plain_steps"}."""
+        "accepted", "plain_steps"}.  constrained (kh_model_generate_lookup_fsm): as_set under set_constraint() as well -
+        the automaton drafts (lookup_draft_fsm: the tokens of single-edge rows first), the words are generate()'s under
+        the same constraint and settings, and stats gains "forced", the drafted tokens that were forced ones."""
         _ffi.sync_env()  # KH_PREFILL, KH_PG_*
         st, hn = list(stop or []), list(hint or [])
         hint_arr = _i32_array(hn)
@@ -617,10 +640,14 @@ class KuiperModel:
         n = C.c_int32(0)
         ms = C.c_float(0.0)
         stats = _ffi.LookupStats()
+        args = (self._h, _i32_array(prompt), len(prompt), total_steps, _i32_array(st), len(st), C.byref(opts), words,
+                C.byref(n), C.byref(ms), C.byref(stats))
+        if constrained:
+            forced = C.c_int32(0)
+            _ffi.check(_ffi.lib().kh_model_generate_lookup_fsm(*args, C.byref(forced)), "kh_model_generate_lookup_fsm")
+            return list(words[: n.value]), float(ms.value), dict(stats.as_dict(), forced=int(forced.value))
         name = "kh_model_generate_lookup_as_set" if as_set else "kh_model_generate_lookup"
-        _ffi.check(getattr(_ffi.lib(), name)(self._h, _i32_array(prompt), len(prompt), total_steps, _i32_array(st),
-                                             len(st), C.byref(opts), words, C.byref(n), C.byref(ms), C.byref(stats)),
-                   name)
+        _ffi.check(getattr(_ffi.lib(), name)(*args), name)
         return list(words[: n.value]), float(ms.value), stats.as_dict()
 
     # ---- sequence slots: several independent sequences per pass over the weights ---------------------------------

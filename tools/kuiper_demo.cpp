@@ -16,7 +16,7 @@
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
-//               [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]
+//               [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--lookup-constrained [ngram_max]] [--hint id,id,...]
 //               [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
@@ -51,6 +51,9 @@
 // --lookup-as-set [ngram_max]: the same loop under --temperature / --seed, the penalties, --logit-bias and --logprobs
 // (kh_model_generate_lookup_as_set): a draft is accepted where it equals the pick the settings make, so the words and
 // the log-prob lines are those of the same run without lookup.
+// --lookup-constrained [ngram_max]: that loop under --choices as well (kh_model_generate_lookup_fsm): the automaton
+// drafts - the tokens of a choice behind its branching prefix are forced - and the words are those of the same run
+// without lookup.  The stats line gains "forced F", the drafted tokens that were forced ones.
 // --parallel N: N samples of the one prompt, decoded together (kh_model_seq_slots / _seq_prefill / _seq_fork /
 // kh_model_generate_batch_from): the cache is cut into N slots, the prompt is prefilled once and forked, the seeds are
 // --seed, --seed + 1, ...; each sequence's ids are printed on a line of their own, then the aggregate "steps/s".
@@ -157,7 +160,7 @@ static void usage() {
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
-               "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--hint id,id,...]\n"
+               "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--lookup-constrained [ngram_max]] [--hint id,id,...]\n"
                "       [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]\n"
                "       [--choices \"id,id,..;id,id,..\"]  (answer with one of these, then the first --stop id; also\n"
                "       beside --parallel / --best-of: every sample is constrained)\n");
@@ -179,6 +182,7 @@ int main(int argc, char** argv) {
   bool score = false;  // --score (kh_model_score)
   bool lookup = false;  // --lookup [ngram_max] (kh_model_generate_lookup)
   bool lookup_as_set = false;  // --lookup-as-set [ngram_max] (kh_model_generate_lookup_as_set)
+  bool lookup_fsm = false;  // --lookup-constrained [ngram_max] (kh_model_generate_lookup_fsm)
   kh_lookup_opts lk{0, 0, 0, nullptr, 0};
   int parallel = 0;  // --parallel N (kh_model_generate_batch)
   bool gemm_batch = false;  // --gemm-batch (kh_model_generate_batch_gemm)
@@ -234,9 +238,10 @@ int main(int argc, char** argv) {
     else if (a == "--gemm-prefill") gemm_prefill = true;
     else if (a == "--best-of") best_of = std::atoi(next());
     else if (a == "--share-prefix") share_prefix = true;
-    else if (a == "--lookup" || a == "--lookup-as-set") {
+    else if (a == "--lookup" || a == "--lookup-as-set" || a == "--lookup-constrained") {
       lookup = true;
       if (a == "--lookup-as-set") lookup_as_set = true;
+      if (a == "--lookup-constrained") lookup_fsm = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') lk.ngram_max = std::atoi(argv[++i]);
     }
     else if (a == "--logit-bias") {
@@ -430,8 +435,8 @@ int main(int argc, char** argv) {
       kh_model_destroy(m);
       return 2;
     }
-    if (lookup || score) {
-      std::fprintf(stderr, "--choices does not go with --lookup or --score\n");
+    if ((lookup && !lookup_fsm) || score) {
+      std::fprintf(stderr, "--choices does not go with --lookup, --lookup-as-set or --score (--lookup-constrained is the one)\n");
       kh_model_destroy(m);
       return 2;
     }
@@ -593,9 +598,15 @@ int main(int argc, char** argv) {
   std::printf("Generating...\n");
   const auto t0 = std::chrono::steady_clock::now();  // timer excludes init (main.cpp:66)
   kh_lookup_stats lks{0, 0, 0, 0};
+  int32_t lk_forced = 0;
   if (lookup) {
     lk.h_hint = hint.empty() ? nullptr : hint.data();
     lk.n_hint = (int32_t)hint.size();
+  }
+  if (lookup_fsm) {
+    rc = kh_model_generate_lookup_fsm(m, prompt.data(), (int32_t)prompt.size(), steps, stop.data(), (int32_t)stop.size(),
+                                      &lk, words.data(), &n, &gpu_ms, &lks, &lk_forced);
+  } else if (lookup) {
     rc = (lookup_as_set ? kh_model_generate_lookup_as_set : kh_model_generate_lookup)(
         m, prompt.data(), (int32_t)prompt.size(), steps, stop.data(), (int32_t)stop.size(), &lk, words.data(), &n,
         &gpu_ms, &lks);
@@ -636,6 +647,7 @@ int main(int argc, char** argv) {
   if (lookup)
     std::printf("\nlookup: passes %d drafted %d accepted %d plain_steps %d", lks.passes, lks.drafted, lks.accepted,
                 lks.plain_steps);
+  if (lookup_fsm) std::printf(" forced %d", lk_forced);
   std::printf("\nsteps/s:%lf\n", (double)steps_done / dur);
   if (o.family == KH_FAMILY_QWEN2) std::printf("\nsteps:%d\n\nduration:%lf\n", steps_done, dur);  // main_qwen.cpp:73-74
   const int p0 = (int)prompt.size() - 1;
