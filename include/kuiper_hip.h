@@ -160,6 +160,19 @@ int kh_mha_prefill_tiles_f32(int32_t n_tiles, const int32_t* h_tiles, int32_t he
                              int32_t seq_len, int32_t kv_dim, int32_t kv_mul, int32_t head_size,
                              int32_t layout, int32_t tcap, float* mha_out, const float* q,
                              const float* key_cache, const float* value_cache, void* stream);
+/* The attention of the wide sequence pass under KH_FLAG_WIDE_ATTN as an operator (csrc/kh_seq_attn_wide.h): n_lanes
+ * (1 .. 64) query rows q[n][dim] of DIFFERENT sequences in one k_sg_attn launch plus k_sg_attn_merge.  h_lanes is a HOST
+ * table of 4 x n int32: pos[], base[], pfx_len[], pfx_row0[].  Lane i attends to positions 0 .. pos[i] of its sequence;
+ * position p is cache row pfx_row0[i] + p for p < pfx_len[i] (0 <= pfx_len <= pos) and row base[i] + p from there on
+ * (base = row - pos, may be negative).  Lanes with the same (pfx_row0, pfx_len) read those rows once for all their
+ * heads.  Rows outside the lanes' ranges are never loaded.  mha_out is [n][dim] row-major.  Within the fp32 tolerance
+ * of kh_mha_prefill_f32, not its bits.  Allocates a workspace, synchronises the stream and frees it.  Before any
+ * launch: KH_ERR_INVALID_ARG for NULL or misaligned pointers, a bad head geometry, n outside 1 .. 64, a negative
+ * pfx_len or pos < pfx_len; KH_ERR_RANGE for a row outside [0, seq_len); KH_ERR_UNSUPPORTED for a head size other than
+ * 48 / 64 / 128. */
+int kh_mha_decode_lanes_f32(int32_t n_lanes, const int32_t* h_lanes, int32_t head_num, int32_t layer_index,
+                            int32_t seq_len, int32_t kv_dim, int32_t kv_mul, int32_t head_size, float* mha_out,
+                            const float* q, const float* key_cache, const float* value_cache, void* stream);
 
 /* The decode-path attention kernel with its long-context machinery.  Per-head path: the grid
  * carries ceil(seq_len/256) (<= 16) workgroups per head; positions < 256 use one of them, longer
@@ -419,6 +432,15 @@ typedef struct kh_model_opts {
  * Independent of KH_FLAG_Q4 (the GEMM passes of a Q4 model read the int8 image) and of KH_FLAG_GEMM16 (inert on int8).
  * Hook KH_GEMM16_Q8=1 / 0 at creation overrides the flag.  kh_model_gemm16_q8_info reports. */
 #define KH_FLAG_GEMM16_Q8 256
+/* WIDE_ATTN: the attention of the wide sequence pass (kh_model_seq_step_gemm, kh_model_generate_batch_gemm) in ONE launch
+ * per layer for all lanes plus a small merge launch (csrc/kh_seq_attn_wide.h: k_sg_attn, k_sg_attn_merge on
+ * v_mfma_f32_16x16x4_f32) instead of k_seq_attn / k_seq_attn_pfx once per group of 8 lanes; lanes that share a prompt
+ * prefix (kh_model_seq_share) read its K/V rows once per 64 query columns (32 at head size 128), not once per lane.
+ * The wide pass's tolerance contract; everything else of the pass is untouched, and so are the 8-lane pass, the slot
+ * prefill and batch-1.  The first wide call allocates the partial workspace (64 x heads x 16 x (head_size + 4) floats).
+ * Inert - the launches of the same model without the flag - on a head size other than 48 / 64 / 128 and on a geometry
+ * the wide pass refuses.  Hook KH_WIDE_ATTN=1 / 0 at creation overrides the flag.  kh_model_wide_attn_info reports. */
+#define KH_FLAG_WIDE_ATTN 512
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -503,6 +525,11 @@ int kh_model_gemm16_info(kh_model* m, int64_t* out8);
  * 1 flag not set, 2 fp32 model, 3 group size is not 64, 4 geometry off the GEMM prefill, 5 no class left by the mask),
  * kh_plan_gemm16_q8's mask for the geometry (0 where inert before the plan); slots 4 - 7 are 0. */
 int kh_model_gemm16_q8_info(kh_model* m, int64_t* out8);
+/* WIDE_ATTN (KH_FLAG_WIDE_ATTN): out[8] = state (1: the wide pass launches k_sg_attn + k_sg_attn_merge per layer, 0:
+ * inert), the reason where inert (0 none, 1 flag not set, 2 head size other than 48 / 64 / 128, 3 a geometry the wide
+ * pass refuses), bytes of the partial workspace (0 before the first wide call under the flag), the most chunks an item
+ * is cut into, query columns per K/V row read; slots 5 - 7 are 0. */
+int kh_model_wide_attn_info(kh_model* m, int64_t* out8);
 /* tests: one screened step (k_cls_screen + k_sample_screen, as a generate launches them) and one full step (k_cls +
  * k_sample) on the residual vector h_x[dim], without advancing.  h_lb / h_ub [vocab]: the interval the screen gave
  * every row.  out4 = screened token, full classifier's token, candidate rows re-scored, 1 if the step overflowed.
@@ -1124,6 +1151,15 @@ int kh_fsm_bias_empties(const kh_fsm* a, int32_t state, const int32_t* h_ids, co
  * KH_PG_SHAPE_* hooks apply, KH_PG_CHUNK does not.  Synchronises. */
 int kh_plan_seq_prefill_gemm(int32_t n_seq, const int32_t* n_tokens, int32_t* out_runs, int32_t cap_runs,
                              int32_t* n_runs, int32_t* n_passes);
+/* kh_plan_wide_attn: host only - the item table of KH_FLAG_WIDE_ATTN's attention for a lane table (h_lanes as
+ * kh_mha_decode_lanes_f32's, with its argument codes; seq_len <= 0: no cache to check the rows against).  An item is a
+ * contiguous range of cache rows plus the lanes that attend to all of it: one share item per distinct (pfx_row0,
+ * pfx_len > 0), then lane i's own item (positions pfx_len .. pos) at index n_share + i.  out_items[8 * i ..] = {kind (0
+ * share, 1 own), first row, rows, chunks, 16-position tiles per chunk (all chunks but the last are whole), lanes, first
+ * index in out_lanes, work units per kv head}; out_lanes[<= 128]: the items' lanes, item after item.  *n_items = the
+ * items there are (KH_ERR_RANGE when cap_items holds fewer or an output is NULL: call with cap_items 0 to size). */
+int kh_plan_wide_attn(int32_t n_lanes, const int32_t* h_lanes, int32_t kv_mul, int32_t head_size, int32_t seq_len,
+                      int32_t* out_items, int32_t cap_items, int32_t* n_items, int32_t* out_lanes);
 int kh_model_seq_prefill_gemm(kh_model* m, int32_t n_seq, const int32_t* slots, const int32_t* h_tokens,
                               const int32_t* n_tokens, const int32_t* pos0);
 

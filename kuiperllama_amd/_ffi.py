@@ -17,12 +17,12 @@ EXPORTS = [
     "kh_error_string", "kh_version", "kh_device_count",
     "kh_add_f32", "kh_matmul_f32", "kh_gemm_w16_f32", "kh_gemm_q8_bf16_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
-    "kh_mha_prefill_layout_f32", "kh_mha_prefill_tiles_f32",
+    "kh_mha_prefill_layout_f32", "kh_mha_prefill_tiles_f32", "kh_mha_decode_lanes_f32",
     "kh_mha_decode_workspace_bytes", "kh_argmax_f32", "kh_argmax_rows_f32",
     "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
-    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_gemm16_q8_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
+    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_gemm16_q8_info", "kh_model_wide_attn_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
     "kh_spm_create_from_file", "kh_spm_create_from_memory", "kh_spm_destroy", "kh_spm_vocab_size",
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
@@ -31,7 +31,7 @@ EXPORTS = [
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_q4", "kh_plan_gemm16", "kh_plan_gemm16_q8", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
-    "kh_plan_seq_prefill_gemm", "kh_model_seq_prefill_gemm",
+    "kh_plan_seq_prefill_gemm", "kh_model_seq_prefill_gemm", "kh_plan_wide_attn",
     "kh_fsm_check", "kh_fsm_walk", "kh_token_mask_f32", "kh_model_set_constraint", "kh_model_get_constraint_state", "kh_model_set_constraint_state",
     "kh_model_seq_set_constraint", "kh_model_seq_set_constraint_state", "kh_model_seq_get_constraint_state", "kh_fsm_components", "kh_fsm_bias_empties",
     "kh_debug_set", "kh_debug_get", "kh_debug_list", "kh_debug_launch_log", "kh_debug_alloc_stats",
@@ -58,6 +58,9 @@ KH_GEMM16_REASONS = ("on", "flag not set", "no W16 flag", "int8 model", "image n
 KH_FLAG_GEMM16_Q8 = 256  # the GEMM pass of an int8 group-64 model on the bf16 matrix cores (KuiperModel.gemm16_q8_info)
 # kh_model_gemm16_q8_info, slot 2: why the flag does nothing on a model
 KH_GEMM16_Q8_REASONS = ("on", "flag not set", "fp32 model", "group size not 64", "geometry", "no class")
+KH_FLAG_WIDE_ATTN = 512  # the wide pass's attention in one launch per layer, shared prefixes read once (wide_attn_info)
+# kh_model_wide_attn_info, slot 1: why the flag does nothing on a model
+KH_WIDE_ATTN_REASONS = ("on", "flag not set", "head size", "geometry")
 KH_Q4_CLASSES = KH_W16_CLASSES  # bit i of a class mask (kh_model_q4_info, kh_plan_q4, hook KH_Q4_CLASSES)
 KH_LOGPROBS_MAX_TOP = 20
 KH_SEQ_BIAS_MAX = 64
@@ -230,6 +233,9 @@ def lib() -> C.CDLL:
     L.kh_plan_gemm16.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
     L.kh_gemm_w16_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
     L.kh_model_gemm16_q8_info.argtypes = [_vp, C.POINTER(_i64)]
+    L.kh_model_wide_attn_info.argtypes = [_vp, C.POINTER(_i64)]
+    L.kh_mha_decode_lanes_f32.argtypes = [_i32, _vp] + [_i32] * 6 + [_vp, _vp, _vp, _vp, _vp]
+    L.kh_plan_wide_attn.argtypes = [_i32, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32), C.POINTER(_i32)]
     L.kh_plan_gemm16_q8.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
     L.kh_gemm_q8_bf16_f32.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
     L.kh_plan_q4.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
@@ -496,6 +502,28 @@ def plan_gemm16_q8(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quan
     if rc != 0:
         raise KhError(rc, "kh_plan_gemm16_q8")
     return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
+
+
+def plan_wide_attn(lanes, kv_mul: int, head_size: int, seq_len: int = 0) -> list:
+    """The item table of KH_FLAG_WIDE_ATTN's attention for a lane table (host-only, kh_plan_wide_attn).  lanes: int32
+    [4][n] - pos, base (= row - pos), pfx_len, pfx_row0.  Per item, share items first and then lane i's own item:
+    {"kind": "share" / "own", "row0", "len", "chunks", "chunk_tiles" (16-position tiles per chunk), "lanes": the pass
+    lanes that attend to all of its rows, "units": work units per kv head}."""
+    import numpy as np
+    t = np.ascontiguousarray(lanes, dtype=np.int32)
+    if t.ndim != 2 or t.shape[0] != 4:
+        raise ValueError("plan_wide_attn: lanes must be [4][n]")
+    n = _i32(0)
+    rc = lib().kh_plan_wide_attn(t.shape[1], t.ctypes.data, kv_mul, head_size, seq_len, None, 0, C.byref(n), None)
+    if rc != KH_ERR_RANGE:
+        raise KhError(rc, "kh_plan_wide_attn")
+    items, who = (_i32 * (8 * n.value))(), (_i32 * 128)()
+    check(lib().kh_plan_wide_attn(t.shape[1], t.ctypes.data, kv_mul, head_size, seq_len, items, n.value, C.byref(n), who),
+          "kh_plan_wide_attn")
+    return [{"kind": ("share", "own")[items[8 * i]], "row0": items[8 * i + 1], "len": items[8 * i + 2],
+             "chunks": items[8 * i + 3], "chunk_tiles": items[8 * i + 4],
+             "lanes": [who[items[8 * i + 6] + k] for k in range(items[8 * i + 5])], "units": items[8 * i + 7]}
+            for i in range(n.value)]
 
 
 def plan_q4(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, n_layers: int, quant: bool,

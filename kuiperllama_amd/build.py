@@ -15,13 +15,16 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libkuiper_hip.so")
-SOURCES = ["kh_ops.hip", "kh_model_load.hip", "kh_model_step.hip", "kh_model_prefill.hip", "kh_model_gemm.hip", "kh_model_gemm_w16.hip", "kh_model_gemm_q16.hip", "kh_model_seq.hip", "kh_model_profile.hip", "kh_model_selftest.hip", "kh_model_screen.hip", "kh_model_w16.hip",
+SOURCES = ["kh_ops.hip", "kh_model_load.hip", "kh_model_step.hip", "kh_model_prefill.hip", "kh_model_gemm.hip", "kh_model_gemm_w16.hip", "kh_model_gemm_q16.hip", "kh_model_wide_attn.hip", "kh_model_seq.hip", "kh_model_profile.hip", "kh_model_selftest.hip", "kh_model_screen.hip", "kh_model_w16.hip",
            "kh_model_h16.hip", "kh_model_h16_pass.hip", "kh_model_q4.hip", "kh_model_q4_pass.hip",
            "kh_tokenizer.cpp", "kh_bpe.cpp", "kh_debug.cpp"]
 HEADERS = ["kh_common.h", "kh_gemv.h", "kh_attn.h", "kh_fused.h", "kh_q8ring.h", "kh_fused_ring.h", "kh_prefill.h", "kh_gemm.h", "kh_gemm_body.h", "kh_gemm_w16.h", "kh_gemm_q16.h", "kh_pattn.h", "kh_pattn_body.h", "kh_sample.h", "kh_step_tail.h", "kh_logit_proc.h", "kh_logprobs.h", "kh_cls_screen.h", "kh_w16.h", "kh_w16_pass.h", "kh_copy_launch.h", "kh_q4.h", "kh_q4_pass.h", "kh_pf_launch.h", "kh_unicode_tables.h",
-           "kh_model_internal.h", "kh_buf.h", "kh_dispatch.h", "kh_score_plan.h", "kh_spec.h", "kh_lookup.h", "kh_seq.h", "kh_seq_plan.h", "kh_seq_gemm.h", "kh_seq_prefill.h", "kh_fsm.h",
+           "kh_model_internal.h", "kh_buf.h", "kh_dispatch.h", "kh_score_plan.h", "kh_spec.h", "kh_lookup.h", "kh_seq.h", "kh_seq_plan.h", "kh_seq_gemm.h", "kh_seq_prefill.h", "kh_seq_attn_wide.h", "kh_wide_attn_plan.h", "kh_fsm.h",
            "../../include/kuiper_hip.h"]
 ARCH = "gfx950"
+# per-source compiler flags: kh_model_wide_attn.hip keeps the fp32 statements of its softmax and merges on scalar VALU ops
+# (the compiler forms no packed fp32 instructions from them)
+EXTRA_FLAGS = {"kh_model_wide_attn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -54,7 +57,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
                # inlined into (decode vs B-token prefill kernels are compared bit for bit) and the
                # CPU oracle is built the same way; explicit __builtin_fmaf calls stay FMAs
                "-ffp-contract=off",
-               "-Wno-unused-function", "-c", os.path.join(CSRC, src), "-o", obj]
+               "-Wno-unused-function"] + EXTRA_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((cmd, subprocess.Popen(cmd)))  # the translation units compile side by side
@@ -98,7 +101,7 @@ def build_variant(name: str, defines: list[str], commit: str | None = None) -> s
             continue
         obj = os.path.join(od, os.path.splitext(src)[0] + ".o")
         cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w"] + \
-              [f"-D{d}" for d in defines] + ["-c", os.path.join(CSRC, src), "-o", obj]
+              [f"-D{d}" for d in defines] + EXTRA_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         procs.append((cmd, subprocess.Popen(cmd)))
         objs.append(obj)
     for cmd, pr in procs:

@@ -19,6 +19,7 @@
 #include "kh_pattn.h"
 #include "kh_seq_gemm.h"
 #include "kh_seq_prefill.h"
+#include "kh_wide_attn_plan.h"
 
 using namespace khm;
 
@@ -258,8 +259,9 @@ PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, i
 //   RoPE where the          k_pg_rope                          k_rg_rope                    k_sg_rope
 //   epilogue cannot rotate
 //   attention               k_pg_attn, else the decode         k_rg_attn (the caller        seq_attn_enqueue per group of
-//                           kernel with pg_ws (KH_PG_ATTN=0,   checked: MFMA only)          KH_PF_BMAX lanes
-//                           odd head sizes)
+//                           kernel with pg_ws (KH_PG_ATTN=0,   checked: MFMA only)          KH_PF_BMAX lanes; under
+//                           odd head sizes)                                                 KH_FLAG_WIDE_ATTN k_sg_attn +
+//                                                                                           k_sg_attn_merge for all lanes
 //   wo's B operand          tiled iff MFMA attention ran       tiled                        row-major
 //   wo / SwiGLU / w2 GEMM   k_pg_gemm                          k_pg_gemm                    k_sg_gemm
 //   tile list               kPgTiles                           kPgTiles                     no (2,8): NT > 4 runs as NT = 4
@@ -410,6 +412,11 @@ bool launch_pg_pass(kh_model* m, const PgPass& p) {
   // attention of a run's or a tile table's slice: MFMA kernel (kh_pattn.h) unless KH_PG_ATTN=0 or an odd head size
   const bool mfma_attn = !p.lanes && pg_mfma_attn(m);
   const bool rope_fuse_env = !dbg_off("KH_PG_ROPE_FUSE");
+  // KH_FLAG_WIDE_ATTN (kh_seq_attn_wide.h): the lanes' attention in one launch per layer plus its merge; the item table
+  // is the same for every layer
+  const bool wide_attn = p.lanes && m->wattn.on;
+  KhWaTable wa_table;
+  if (wide_attn) wide_attn_table(m, *p.lanes, p.slots, p.n, &wa_table);
   for (int l = 0; l < c.layer_num; ++l) {
     const LayerW& W = m->layers[l];
     const kh_model::WCopy::Layer C = m->w16.arena ? m->w16.layers[(size_t)l] : kh_model::WCopy::Layer{};  // (KH_FLAG_GEMM16)
@@ -448,7 +455,9 @@ bool launch_pg_pass(kh_model* m, const PgPass& p) {
     // written, its attention, wo and FFN feed nothing (1/L of the pass minus one QKV GEMM) - unless the
     // classifier follows (full_depth)
     if (l == c.layer_num - 1 && !p.full_depth) break;
-    if (p.lanes) {
+    if (wide_attn) {
+      wide_attn_enqueue(m, l, m->pg_q, m->pg_att, wa_table);  // k_sg_attn + k_sg_attn_merge for all lanes
+    } else if (p.lanes) {
       for (int g = 0; g < pg_lane_groups(p); ++g) {
         int ng;
         const KhSeqLanes lg = pg_lane_group(m, p, g, &ng);
@@ -606,6 +615,7 @@ bool khm::seq_gemm_supported(const kh_model* m) {
 int khm::seq_gemm_prepare(kh_model* m) {
   int rc;
   if ((rc = ensure_pg_buffers(m)) != KH_OK) return rc;
+  if ((rc = wide_attn_prepare(m)) != KH_OK) return rc;  // (KH_FLAG_WIDE_ATTN: the partials of k_sg_attn)
   if (m->sg_logits) return KH_OK;
   KhDev<float> lg;
   const size_t n = (size_t)KH_SEQ_SLOTS_MAX * (size_t)m->pf_vstride;  // pf_vstride: seq_prepare ran

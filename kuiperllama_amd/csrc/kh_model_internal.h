@@ -12,6 +12,8 @@
 //   kh_model_gemm_w16.hip the same GEMMs on the bf16 matrix cores from the 16-bit copy (KH_FLAG_GEMM16; kh_gemm_w16.h kernels)
 //   kh_model_gemm_q16.hip the GEMMs of an int8 group-64 model on the bf16 matrix cores from the int8 image (KH_FLAG_GEMM16_Q8;
 //                         kh_gemm_q16.h kernels)
+//   kh_model_wide_attn.hip the wide pass's attention in one launch per layer (KH_FLAG_WIDE_ATTN; kh_seq_attn_wide.h kernels,
+//                         kh_wide_attn_plan.h) and its operator-level entry
 //   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
 //                         forms with per-sequence processors and log-probs (host side)
 //   kh_model_profile.hip  per-kernel / per-step timing entry points
@@ -106,6 +108,7 @@ struct KhProcParams;       // kh_logit_proc.h
 struct KhPgGemmArgs;       // kh_gemm.h
 struct KhRgTiles;          // kh_seq_prefill.h
 struct KhWideLanes;        // kh_seq_gemm.h
+struct KhWaTable;          // kh_wide_attn_plan.h
 struct kh_model {
   kh_config cfg{};
   kh_model_opts opts{};
@@ -399,6 +402,16 @@ struct kh_model {
     int plan = 0;           // plan_gemm16_q8's mask for the geometry, whatever the hook says (0 unless the flag is live)
   };
   Gemm16Q8 g16q8;
+  // KH_FLAG_WIDE_ATTN / hook KH_WIDE_ATTN (kh_seq_attn_wide.h, kh_model_wide_attn.hip): the wide pass's
+  // attention as k_sg_attn + k_sg_attn_merge per layer instead of the grouped launches; off wherever the flag is inert,
+  // and reason says why (KH_WIDE_ATTN_*: kh_model_wide_attn_info).  ws: the partials, made by the first wide call under
+  // the flag (seq_gemm_prepare)
+  struct WideAttn {
+    bool on = false;
+    int reason = 0;
+    KhDev<float> ws;
+  };
+  WideAttn wattn;
 };
 
 #define KH_GRAPH_STEPS 8
@@ -712,4 +725,13 @@ bool seq_gemm_supported(const kh_model* m);
 int seq_gemm_prepare(kh_model* m);
 int seq_pass_enqueue_gemm(kh_model* m, const int32_t* slots, const int32_t* pos, int n, bool words,
                           const KhSeqTail* tail = nullptr);
+// ---- kh_model_wide_attn.hip -----------------------------------------------------------------
+// why KH_FLAG_WIDE_ATTN does nothing on a model (kh_model_wide_attn_info, slot 1); KH_WIDE_ATTN_ON: it does something
+enum { KH_WIDE_ATTN_ON = 0, KH_WIDE_ATTN_NO_FLAG = 1, KH_WIDE_ATTN_HEAD_SIZE = 2, KH_WIDE_ATTN_GEOMETRY = 3 };
+void wide_attn_configure(kh_model* m);  // at creation
+int wide_attn_prepare(kh_model* m);     // the partial workspace, where the flag is live
+// The item table (kh_wide_attn_plan.h) of a wide pass's lanes: once per pass, the same for every layer.
+void wide_attn_table(const kh_model* m, const KhWideLanes& lanes, const int32_t* slots, int n, KhWaTable* t);
+// k_sg_attn + k_sg_attn_merge of layer l on q / out rows of dim floats per lane
+void wide_attn_enqueue(kh_model* m, int l, const float* q, float* out, const KhWaTable& t);
 }  // namespace khm

@@ -425,6 +425,16 @@ class KuiperModel:
                 "reason": _ffi.KH_GEMM16_Q8_REASONS[out[2]],
                 "plan": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1]}
 
+    def wide_attn_info(self) -> dict:
+        """_ffi.KH_FLAG_WIDE_ATTN on this model (kh_model_wide_attn_info): {"on": the wide pass launches k_sg_attn and
+        k_sg_attn_merge once per layer instead of k_seq_attn per group of 8 lanes, "reason": why the flag does nothing
+        (one of _ffi.KH_WIDE_ATTN_REASONS; "on" where it does), "workspace_bytes": the partials (0 before the first wide
+        call), "max_chunks": per item, "columns_per_read": query columns one K/V row read feeds}."""
+        out = (_ffi._i64 * 8)()
+        _ffi.check(_ffi.lib().kh_model_wide_attn_info(self._h, out), "kh_model_wide_attn_info")
+        return {"on": bool(out[0]), "reason": _ffi.KH_WIDE_ATTN_REASONS[out[1]], "workspace_bytes": int(out[2]),
+                "max_chunks": int(out[3]), "columns_per_read": int(out[4])}
+
     def w16_pass_info(self) -> dict:
         """The B-token passes of a KH_FLAG_W16 model (kh_model_w16_info, slot 5): {"classes": the launch classes whose
         passes - prefill, score, verify / generate_lookup, seq_* and generate_batch* - stream the 16-bit copy}, a

@@ -185,6 +185,20 @@ def mha_prefill_tiles(tiles, head_num, layer_index, seq_len, kv_dim, kv_mul, hea
     return mha_out
 
 
+def mha_decode_lanes(lanes, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size, mha_out, q, kcache, vcache):
+    """The wide pass's one-launch attention (kh_mha_decode_lanes_f32: k_sg_attn + k_sg_attn_merge).  lanes: host int32
+    array [4][n] - pos, base (= row - pos), pfx_len, pfx_row0 per lane; q and mha_out are [n][dim].  Synchronises."""
+    import numpy as np
+    t = np.ascontiguousarray(lanes, dtype=np.int32)
+    if t.ndim != 2 or t.shape[0] != 4:
+        raise ValueError("mha_decode_lanes: lanes must be [4][n]")
+    _ffi.check(_ffi.lib().kh_mha_decode_lanes_f32(
+        t.shape[1], t.ctypes.data, head_num, layer_index, seq_len, kv_dim, kv_mul, head_size,
+        _p(mha_out, torch.float32), _p(q, torch.float32), _p(kcache, torch.float32),
+        _p(vcache, torch.float32), _stream()), "kh_mha_decode_lanes_f32")
+    return mha_out
+
+
 def mha_decode_workspace(head_num: int, head_size: int, seq_len: int, device):
     """Zeroed workspace tensor for mha_decode (None when no time split is needed)."""
     _ffi.sync_env()  # KH_ATTN_TLONG

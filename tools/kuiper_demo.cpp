@@ -17,7 +17,7 @@
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
 //               [--logit-bias id=value]... [--logprobs N] [--score]
 //               [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--lookup-constrained [ngram_max]] [--hint id,id,...]
-//               [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]
+//               [--parallel N [--gemm-batch [--wide-attn]]] [--best-of N] [--share-prefix] [--gemm-prefill]
 //
 // --exact-prefill = KH_FLAG_PREFILL_EXACT: the prompt phase bit for bit the reference's one-token-per-pass prompt
 // phase (demo/main.cpp:20-22); without it prompts of 17+ tokens run as fp32-MFMA GEMMs (tolerance parity, 8-10 x the
@@ -61,6 +61,9 @@
 // --gemm-batch (beside --parallel): the samples decode as wide passes on the matrix cores, up to 64 per pass over the
 // weights (kh_model_seq_width_gemm / kh_model_generate_batch_gemm): equal to the plain run to fp32 round-off, greedy ids
 // can differ at near-ties.  Refused where the library refuses it; there is no fallback.
+// --wide-attn (beside --gemm-batch) = KH_FLAG_WIDE_ATTN: the wide passes' attention runs as one launch per layer for all
+// samples plus a merge, and samples that share the prompt (--share-prefix) read its rows once; prints
+// kh_model_wide_attn_info.  Inert - and says why - on a head size other than 48 / 64 / 128.
 // --best-of N: --parallel's N samples (seeds --seed, --seed + 1, ...) through kh_model_generate_batch_ex, which takes
 // the sampler, penalty, bias and --logprobs flags per sequence (the model's own settings are not consulted), ranked by
 // kh_seq_rank on the mean log-prob of each sample's generated tokens: one line per sample, best first,
@@ -161,7 +164,7 @@ static void usage() {
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
                "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
                "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--lookup-constrained [ngram_max]] [--hint id,id,...]\n"
-               "       [--parallel N [--gemm-batch]] [--best-of N] [--share-prefix] [--gemm-prefill]\n"
+               "       [--parallel N [--gemm-batch [--wide-attn]]] [--best-of N] [--share-prefix] [--gemm-prefill]\n"
                "       [--choices \"id,id,..;id,id,..\"]  (answer with one of these, then the first --stop id; also\n"
                "       beside --parallel / --best-of: every sample is constrained)\n");
 }
@@ -235,6 +238,7 @@ int main(int argc, char** argv) {
     else if (a == "--score") score = true;
     else if (a == "--parallel") parallel = std::atoi(next());
     else if (a == "--gemm-batch") gemm_batch = true;
+    else if (a == "--wide-attn") o.flags |= KH_FLAG_WIDE_ATTN;
     else if (a == "--gemm-prefill") gemm_prefill = true;
     else if (a == "--best-of") best_of = std::atoi(next());
     else if (a == "--share-prefix") share_prefix = true;
@@ -402,6 +406,13 @@ int main(int argc, char** argv) {
     // reason: 0 on, 1 flag not set, 2 fp32 model, 3 group size not 64, 4 geometry, 5 no class
     std::fprintf(stderr, "GEMM16_Q8: state %lld, classes on the bf16 matrix cores 0x%llx (plan 0x%llx), reason %lld\n",
                  (long long)w[0], (unsigned long long)w[1], (unsigned long long)w[3], (long long)w[2]);
+  }
+  if (o.flags & KH_FLAG_WIDE_ATTN) {
+    int64_t w[8] = {0};
+    kh_model_wide_attn_info(m, w);
+    // reason: 0 on, 1 flag not set, 2 head size other than 48 / 64 / 128, 3 a geometry the wide pass refuses
+    std::fprintf(stderr, "WIDE_ATTN: state %lld, reason %lld, %lld query columns per K/V row read\n", (long long)w[0],
+                 (long long)w[1], (long long)w[4]);
   }
   rc = kh_model_set_sampling(m, &samp);
   if (rc != KH_OK) {
