@@ -283,6 +283,21 @@ int kh_logit_process_f32(float* logits, int64_t n, const int32_t* d_tokens, cons
  * device call, for top_n < 0, top_n > KH_LOGPROBS_MAX_TOP, top_n > n, n_rows <= 0 or a NULL logits. */
 int kh_logprobs_f32(const float* logits, int64_t n, int32_t n_rows, const int32_t* d_ids, int32_t top_n, float* d_lse,
                     float* d_lp, int32_t* d_top_ids, float* d_top_lp, void* stream);
+/* The same statistics of the logits C[t][v] = W[v] . X[t] WITHOUT the logits: the classifier GEMM on the fp32 matrix
+ * cores with the log-softmax in its epilogue and a merge per token (csrc/kh_score_gemm.h: k_pg_cls_lse, k_pg_lse_merge;
+ * the tail of kh_model_score_gemm below).  W [vocab][dim] and X [T][dim] fp32 row-major, d_targets[T] int32 (NULL or an id
+ * outside [0, vocab): NaN) -> d_lse[T], d_lp[T], d_top_ids[T][top_n], d_top_lp[T][top_n], d_max[T] (the largest
+ * logit), d_target_logit[T] (all DEVICE; any of them may be NULL).  workspace: kh_cls_logprobs_workspace_bytes(T, vocab,
+ * dim) bytes of device memory, 16-byte aligned (the tiled copy of X and one partial record per 128 vocabulary rows and
+ * token).  Each logit is a k-ordered fp32 fmaf chain (kh_model_prefill_gemm's contract); on those logits the ids are
+ * exact and lse / lp are within the bound of kh_logprobs_f32 above.  Asynchronous, never allocates.  Before any device
+ * call: KH_ERR_INVALID_ARG for NULL W / X / workspace, T, vocab, dim <= 0, top_n outside [0, min(KH_LOGPROBS_MAX_TOP,
+ * vocab)], a pointer that is not 16-byte aligned or a workspace that is too small; KH_ERR_RANGE for T > 512;
+ * KH_ERR_UNSUPPORTED for vocab % 16 != 0 or dim % 16 != 0. */
+int64_t kh_cls_logprobs_workspace_bytes(int32_t T, int32_t vocab, int32_t dim);
+int kh_cls_logprobs_f32(const float* W, const float* X, int32_t T, int32_t vocab, int32_t dim, const int32_t* d_targets,
+                        int32_t top_n, float* d_lse, float* d_lp, int32_t* d_top_ids, float* d_top_lp, float* d_max,
+                        float* d_target_logit, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Constrained decoding: a TOKEN AUTOMATON is a deterministic automaton over token ids in CSR form.  Row s =
  * tokens[row_ptr[s] .. row_ptr[s + 1]) holds the ids allowed in state s, strictly ascending, and next[] the state behind
@@ -752,8 +767,24 @@ int kh_model_set_constraint_state(kh_model* m, int32_t state);
  * Before any launch: KH_ERR_INVALID_ARG for NULL pointers, n <= 0, pos0 < 0; KH_ERR_RANGE for pos0 + n > cache_len or
  * a token outside [0, vocab_size); KH_ERR_UNSUPPORTED while log-probs are off (kh_model_set_logprobs never called, or
  * -1) and for geometries outside the mirrored kernels (kh_model_prefill's limits; dim > 16 x the classifier's
- * workgroup width).  There is no token-by-token fallback and no MFMA variant. */
+ * workgroup width).  There is no token-by-token fallback; the MFMA variant is kh_model_score_gemm below. */
 int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
+/* kh_model_score on the matrix cores: the passes of kh_model_prefill_gemm (up to 512 tokens per sweep of the weights) at
+ * full depth, each ending in the classifier GEMM with the log-softmax in its epilogue (csrc/kh_score_gemm.h:
+ * k_pg_cls_lse + k_pg_lse_merge) - no logits row is written.  Same records as kh_model_score: position p holds the token
+ * that followed (across pass boundaries too), its log-prob under the RAW logits and the top_n; the last position token
+ * -1, NaN and a filled top list; entries from top_n on "none".  The K/V rows and the fed-token record are left as
+ * kh_model_prefill_gemm leaves them.
+ * Contract: kh_model_prefill_gemm's, NOT the bit-exact one of kh_model_score - the logits differ from the decode
+ * classifier's by fp32 round-off of another summation order.  On the pass's own logits the top ids are exact and lse /
+ * lp within kh_logprobs_f32's bound.  Reads the fp32 or int8 image, also under KH_FLAG_W16 / KH_FLAG_GEMM16* / KH_FLAG_Q4
+ * (the classifier never runs on a weight copy here).  Opt-in: no other call is rerouted to it.  The first call allocates
+ * its workspace (one partial record per 128 vocabulary rows and pass token, 176 bytes each); a model that never calls
+ * this allocates and launches nothing new.
+ * Before any launch: kh_model_score's argument and range codes; KH_ERR_UNSUPPORTED while log-probs are off, for the
+ * geometries kh_model_prefill_gemm refuses, for vocab_size % 16 != 0 and while kh_model_set_constraint is on.  There is
+ * no fallback to the VALU pass. */
+int kh_model_score_gemm(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
 
 /* Speculative greedy decode: up to `width` consecutive positions verified by ONE pass over the weights (llama.cpp's
  * lookup / --draft, vLLM's ngram speculator, the "predicted outputs" of hosted APIs, in their exact greedy form).

@@ -19,7 +19,7 @@ EXPORTS = [
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
     "kh_mha_prefill_layout_f32", "kh_mha_prefill_tiles_f32", "kh_mha_decode_lanes_f32",
     "kh_mha_decode_workspace_bytes", "kh_argmax_f32", "kh_argmax_rows_f32",
-    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
+    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_cls_logprobs_workspace_bytes", "kh_cls_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
     "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_gemm16_q8_info", "kh_model_wide_attn_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
@@ -27,7 +27,7 @@ EXPORTS = [
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
-    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_model_verify_as_set", "kh_model_generate_lookup_as_set", "kh_lookup_draft", "kh_lookup_draft_fsm", "kh_model_verify_fsm", "kh_model_generate_lookup_fsm", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
+    "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_score_gemm", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_model_verify_as_set", "kh_model_generate_lookup_as_set", "kh_lookup_draft", "kh_lookup_draft_fsm", "kh_model_verify_fsm", "kh_model_generate_lookup_fsm", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
     "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_q4", "kh_plan_gemm16", "kh_plan_gemm16_q8", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
@@ -286,6 +286,10 @@ def lib() -> C.CDLL:
                                 C.POINTER(C.c_int64)]
     L.kh_model_prefill.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
     L.kh_model_score.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
+    L.kh_model_score_gemm.argtypes = [_vp, C.POINTER(_i32), _i32, _i32]
+    L.kh_cls_logprobs_workspace_bytes.argtypes = [_i32, _i32, _i32]
+    L.kh_cls_logprobs_workspace_bytes.restype = _i64
+    L.kh_cls_logprobs_f32.argtypes = [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
     L.kh_model_verify_width.argtypes = [_vp, C.POINTER(_i32)]
     L.kh_model_verify.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]
     L.kh_model_generate_lookup.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), _i32,

@@ -270,6 +270,8 @@ PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, i
 //                           K/V rows                                                        k_pg_rmsnorm and the KH_PG_STORE
 //                                                                                           GEMM into sg_logits (the caller's
 //                                                                                           seq_tail_enqueue per group follows)
+// A scoring run (pg_score_run, kh_model_score_gemm) is a run at full depth: behind the final k_pg_rmsnorm it ends in
+// k_pg_cls_lse + k_pg_lse_merge (kh_score_gemm.h: the classifier GEMM with the log-softmax in its epilogue, no logits).
 struct PgPass {
   int T;
   const int32_t* toks;  // host ids of the T slab tokens; null: the lanes feed d_seq_tok
@@ -279,10 +281,15 @@ struct PgPass {
   const KhWideLanes* lanes;  // a lane table, with the call's slots[n] the 8-lane groups are cut from (T = n)
   const int32_t* slots;
   int n;
+  const int32_t* score_target;  // a scoring run (device, [T]: the token that followed slab token t); else null
 };
 PgPass pg_run(const int32_t* toks, int T, int pos0) { return PgPass{T, toks, false, pos0, nullptr, nullptr, nullptr, 0}; }
 PgPass pg_tiles(const int32_t* toks, int T, const KhRgTiles& tiles) {
   return PgPass{T, toks, false, 0, &tiles, nullptr, nullptr, 0};
+}
+// a run at full depth that ends in the fused classifier and log-softmax (kh_score_gemm.h) instead of logits rows
+PgPass pg_score_run(const int32_t* toks, int T, int pos0, const int32_t* d_target) {
+  return PgPass{T, toks, true, pos0, nullptr, nullptr, nullptr, 0, d_target};
 }
 PgPass pg_lanes(const KhWideLanes& lanes, const int32_t* slots, int n) {
   return PgPass{n, nullptr, true, 0, nullptr, &lanes, slots, n};
@@ -500,6 +507,10 @@ bool launch_pg_pass(kh_model* m, const PgPass& p) {
   }
   if (p.full_depth) {
     rmsnorm(m->final_norm);  // adds the last w2 GEMM's pending partials too
+    if (p.score_target) {
+      score_gemm_tail(m, T, p.pos0, p.score_target);  // k_pg_cls_lse + k_pg_lse_merge
+      return ok;
+    }
     KhPgGemmArgs a = gemm_args(m->pg_xn, 1, m->sg_logits, c.vocab_size, m->pf_vstride, c.dim);
     a.w[0] = m->cls;
     pg_gemm<KH_PG_STORE>(m, p, c.vocab_size, c.vocab_size % 32 == 0, a, &ok, PgOn16{KH_W16_CLS, {m->w16.cls}});
@@ -530,7 +541,7 @@ extern "C" int kh_model_prefill_gemm(kh_model* m, const int32_t* h_tokens, int32
   if (rc == KH_OK) rc = khm::lp_none(m, pos0, n);
   return rc == KH_OK ? khm::hist_write(m, h_tokens, n, pos0) : rc;
 }
-int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0) {
+int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, const int32_t* d_score_target) {
   if (!m || !h_tokens || n <= 0 || pos0 < 0) return KH_ERR_INVALID_ARG;
   const kh_config& c = m->cfg;
   if ((int64_t)pos0 + n > c.cache_len) return KH_ERR_RANGE;
@@ -547,8 +558,11 @@ int khm::prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32
     chunk = v < 16 ? 16 : (v > KH_PG_TMAX ? KH_PG_TMAX : v);
   }
   bool ok = true;
-  for (int t0 = 0; t0 < n; t0 += chunk)
-    ok &= launch_pg_pass(m, pg_run(h_tokens + t0, n - t0 < chunk ? n - t0 : chunk, pos0 + t0));
+  for (int t0 = 0; t0 < n; t0 += chunk) {
+    const int T = n - t0 < chunk ? n - t0 : chunk;
+    ok &= launch_pg_pass(m, d_score_target ? pg_score_run(h_tokens + t0, T, pos0 + t0, d_score_target + t0)
+                                           : pg_run(h_tokens + t0, T, pos0 + t0));
+  }
   if (!ok) return KH_ERR_UNSUPPORTED;  // a GEMM shape's LDS opt-in was refused
   return kh_launch_status();
 }

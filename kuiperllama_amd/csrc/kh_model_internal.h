@@ -220,6 +220,10 @@ struct kh_model {
   // the first wide call; sg_lanes: the lane count of the last wide pass (0: none yet)
   KhDev<float> sg_logits;
   int sg_lanes = 0;
+  // sequence scoring on the GEMM pass (kh_score_gemm.h): the partial records of one pass, [vocabulary blocks]
+  // [KH_PG_TMAX][KH_CL_STRIDE], and the targets of one call, [cache_len]; one group, made by the first kh_model_score_gemm
+  KhDev<float> cl_ws;
+  KhDev<int32_t> cl_target;
   KhPin<int32_t> h_words_pin;   // pinned mirror of d_words (stop-token check, final copy-out)
   KhPin<int32_t> h_forced_pin;  // pinned staging of d_forced [seq_cap + 1]: the upload needs no host sync
   int forced_hwm = 0;              // entries of d_forced that may differ from -1 (the last generate's upload)
@@ -707,7 +711,9 @@ int plan_gemm16_q8(bool quant, int group_size, int dim, int hidden_dim, int kv_d
 void gemm16_q8_configure(kh_model* m);  // at creation
 // kh_model_prefill_gemm without the token record (hist_write); prefill_gemm_prepare: its slabs, made by the call
 // itself or ahead of it by whoever times it
-int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0);
+// d_score_target (device, [n]: the token that followed token i, -1 behind the last): every pass runs at full depth and
+// ends in score_gemm_tail - the passes of kh_model_score_gemm
+int prefill_gemm_run(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0, const int32_t* d_score_target = nullptr);
 int prefill_gemm_prepare(kh_model* m);
 // The GEMM prefill into sequence slots (kh_seq_prefill.h; kh_model_seq_prefill_gemm).  _check: KH_OK where the pass
 // runs - the GEMM prefill's geometries with an MFMA attention instantiation for the head size and KH_PG_ATTN not 0 -,
@@ -725,6 +731,10 @@ bool seq_gemm_supported(const kh_model* m);
 int seq_gemm_prepare(kh_model* m);
 int seq_pass_enqueue_gemm(kh_model* m, const int32_t* slots, const int32_t* pos, int n, bool words,
                           const KhSeqTail* tail = nullptr);
+// ---- kh_model_score_gemm.hip ----------------------------------------------------------------
+// The tail of a scoring run's pass (kh_score_gemm.h): k_pg_cls_lse on pg_xn's T rows and k_pg_lse_merge into the
+// records of positions pos0 ..; cl_ws / cl_target are kh_model_score_gemm's to make
+void score_gemm_tail(kh_model* m, int T, int pos0, const int32_t* d_target);
 // ---- kh_model_wide_attn.hip -----------------------------------------------------------------
 // why KH_FLAG_WIDE_ATTN does nothing on a model (kh_model_wide_attn_info, slot 1); KH_WIDE_ATTN_ON: it does something
 enum { KH_WIDE_ATTN_ON = 0, KH_WIDE_ATTN_NO_FLAG = 1, KH_WIDE_ATTN_HEAD_SIZE = 2, KH_WIDE_ATTN_GEOMETRY = 3 };

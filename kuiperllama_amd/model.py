@@ -594,13 +594,20 @@ class KuiperModel:
         out["perplexity"] = float(np.exp(-total / len(lp))) if len(lp) else float("nan")
         return out
 
-    def score(self, tokens: Sequence[int], pos0: int = 0) -> dict:
+    def score(self, tokens: Sequence[int], pos0: int = 0, gemm: bool = False) -> dict:
         """log P(token | prefix) of given text (kh_model_score; needs set_logprobs(top_n)): feeds `tokens` at
         positions pos0.. like prefill() and returns the records of those n positions - "token": the token that
         followed (-1 at the last position), "logprob": its log-prob under the raw logits (NaN at the last),
         "top_ids" / "top_logprobs": [n, top_n] - plus "sum_logprob" and "perplexity" (score_totals).  Bit-identical
-        to ops.logprobs on the logits a loop of predict() leaves."""
+        to ops.logprobs on the logits a loop of predict() leaves.  gemm=True: the same records from the GEMM pass on
+        the matrix cores (kh_model_score_gemm: prefill_gemm's contract - fp32 round-off, not bit-exact -, the classifier
+        fused with the log-softmax, no logits written; refused where prefill_gemm is, for vocabularies that are no
+        multiple of 16 and under a constraint)."""
         t = (C.c_int32 * len(tokens))(*[int(x) for x in tokens])
+        if gemm:
+            _ffi.sync_env()
+            _ffi.check(_ffi.lib().kh_model_score_gemm(self._h, t, len(tokens), int(pos0)), "kh_model_score_gemm")
+            return self.score_totals(self.logprobs(int(pos0), len(tokens)))
         _ffi.check(_ffi.lib().kh_model_score(self._h, t, len(tokens), int(pos0)), "kh_model_score")
         return self.score_totals(self.logprobs(int(pos0), len(tokens)))
 

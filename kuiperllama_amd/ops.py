@@ -324,6 +324,28 @@ def logprobs(logits, ids, top_n: int = 0) -> dict:
     return out
 
 
+def cls_logprobs(w, x, targets=None, top_n: int = 0) -> dict:
+    """ops.logprobs of the logits x @ w.T without the logits (kh_cls_logprobs_f32: the classifier GEMM on the matrix
+    cores with the log-softmax in its epilogue, csrc/kh_score_gemm.h).  w: float32 GPU tensor [vocab, dim]; x: [T, dim],
+    T <= 512; targets: int32 GPU tensor [T] (None or an id outside [0, vocab): NaN).  Returns ops.logprobs' four keys
+    plus "max" (the largest logit of every token) and "target_logit", as GPU tensors."""
+    V, K = w.shape
+    T = x.shape[0]
+    if x.shape[1] != K or (targets is not None and targets.numel() != T):
+        raise ValueError("cls_logprobs: x must be [T, dim] and targets [T]")
+    dev, n = x.device, max(int(top_n), 0)
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"lse": f(T), "logprob": f(T), "top_ids": torch.empty((T, n), dtype=torch.int32, device=dev),
+           "top_logprobs": f(T, n), "max": f(T), "target_logit": f(T)}
+    L = _ffi.lib()
+    ws = torch.empty(max(int(L.kh_cls_logprobs_workspace_bytes(T, V, K)), 16), dtype=torch.uint8, device=dev)
+    _ffi.check(L.kh_cls_logprobs_f32(_p(w, torch.float32), _p(x, torch.float32), T, V, K, _p(targets, torch.int32),
+                                     int(top_n), _p(out["lse"]), _p(out["logprob"]), _p(out["top_ids"]),
+                                     _p(out["top_logprobs"]), _p(out["max"]), _p(out["target_logit"]), _p(ws),
+                                     ws.numel(), _stream()), "kh_cls_logprobs_f32")
+    return out
+
+
 def softmax_(x):
     _ffi.check(_ffi.lib().kh_softmax_f32(_p(x, torch.float32), x.numel(), _stream()),
                "kh_softmax_f32")

@@ -15,7 +15,7 @@
 //               [--exact-prefill] [--fenced-merge] [--w16] [--w16-f16] [--q4] [--gemm16] [--gemm16-q8]
 //               [--temperature T] [--top-k K] [--top-p P] [--seed S]
 //               [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]
-//               [--logit-bias id=value]... [--logprobs N] [--score]
+//               [--logit-bias id=value]... [--logprobs N] [--score [--gemm-score]]
 //               [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--lookup-constrained [ngram_max]] [--hint id,id,...]
 //               [--parallel N [--gemm-batch [--wide-attn]]] [--best-of N] [--share-prefix] [--gemm-prefill]
 //
@@ -44,6 +44,7 @@
 // --score (needs --logprobs N): scores the prompt instead of generating (kh_model_score): one line per prompt
 // position in the same form - the token is the one that FOLLOWED, "-1 nan" at the last position, whose list is the
 // next-token distribution - then "sum_logprob:" and "perplexity:" over the prompt's n - 1 predicted tokens.
+// --gemm-score (with --score): the same records from the GEMM pass on the matrix cores (kh_model_score_gemm).
 // --lookup [ngram_max]: speculative greedy decode (kh_model_generate_lookup): the same words, several per pass over
 // the weights wherever the text so far - or --hint id,id,..., the expected output - predicts the next tokens (n-grams
 // of up to ngram_max tokens, default 4).  Greedy only.  A line "lookup: passes P drafted D accepted A plain_steps S"
@@ -162,7 +163,7 @@ static void usage() {
                "       [--q4] [--gemm16] [--gemm16-q8]\n"
                "       [--temperature T] [--top-k K] [--top-p P] [--seed S]\n"
                "       [--repeat-penalty R] [--presence-penalty A] [--frequency-penalty B] [--repeat-last-n N]\n"
-               "       [--logit-bias id=value]... [--logprobs N] [--score]\n"
+               "       [--logit-bias id=value]... [--logprobs N] [--score [--gemm-score]]\n"
                "       [--lookup [ngram_max]] [--lookup-as-set [ngram_max]] [--lookup-constrained [ngram_max]] [--hint id,id,...]\n"
                "       [--parallel N [--gemm-batch [--wide-attn]]] [--best-of N] [--share-prefix] [--gemm-prefill]\n"
                "       [--choices \"id,id,..;id,id,..\"]  (answer with one of these, then the first --stop id; also\n"
@@ -183,6 +184,7 @@ int main(int argc, char** argv) {
   int steps = 128, exec = KH_EXEC_GRAPH;
   int logprobs = -1;  // --logprobs N (kh_model_set_logprobs)
   bool score = false;  // --score (kh_model_score)
+  bool gemm_score = false;  // --gemm-score (kh_model_score_gemm)
   bool lookup = false;  // --lookup [ngram_max] (kh_model_generate_lookup)
   bool lookup_as_set = false;  // --lookup-as-set [ngram_max] (kh_model_generate_lookup_as_set)
   bool lookup_fsm = false;  // --lookup-constrained [ngram_max] (kh_model_generate_lookup_fsm)
@@ -236,6 +238,7 @@ int main(int argc, char** argv) {
     else if (a == "--repeat-last-n") pen.last_n = std::atoi(next());
     else if (a == "--logprobs") logprobs = std::atoi(next());
     else if (a == "--score") score = true;
+    else if (a == "--gemm-score") gemm_score = true;
     else if (a == "--parallel") parallel = std::atoi(next());
     else if (a == "--gemm-batch") gemm_batch = true;
     else if (a == "--wide-attn") o.flags |= KH_FLAG_WIDE_ATTN;
@@ -466,8 +469,8 @@ int main(int argc, char** argv) {
       return 2;
     }
     const int cnt = (int)prompt.size();
-    if ((rc = kh_model_score(m, prompt.data(), cnt, 0)) != KH_OK) {
-      std::fprintf(stderr, "kh_model_score failed: %d (%s)\n", rc, kh_error_string(rc));
+    if ((rc = gemm_score ? kh_model_score_gemm(m, prompt.data(), cnt, 0) : kh_model_score(m, prompt.data(), cnt, 0)) != KH_OK) {
+      std::fprintf(stderr, "%s failed: %d (%s)\n", gemm_score ? "kh_model_score_gemm" : "kh_model_score", rc, kh_error_string(rc));
       kh_model_destroy(m);
       return 1;
     }
