@@ -65,6 +65,12 @@ int kh_add_f32(const float* in1, const float* in2, float* out, int32_t n, void* 
  * synchronises the stream. */
 int kh_gemm_w16_f32(const float* x, const uint16_t* w16, float* y, int32_t T, int32_t M, int32_t K, int32_t ldy,
                     void* stream);
+/* The same product from fp16 weights (csrc/kh_gemm_h16.h: the K loop of KH_FLAG_GEMM16_F16 under its STORE epilogue):
+ * w16 holds IEEE binary16 bits, row-major; every weight splits exactly into two bf16 terms (w_hi + w_lo == w), every x
+ * into three, all six products per column are exact and kept, accumulation is fp32.  The preconditions and return
+ * codes of kh_gemm_w16_f32. */
+int kh_gemm_h16_f32(const float* x, const uint16_t* w16, float* y, int32_t T, int32_t M, int32_t K, int32_t ldy,
+                    void* stream);
 int kh_matmul_f32(const float* x, const float* w, float* y, int32_t M, int32_t K, float scale,
                   void* stream);
 /* y[t][0 .. M) = sum over groups g of scales[m][g] * (w8[m][64g .. 64g + 64) . x[t][64g .. 64g + 64)) for t < T, on the
@@ -456,6 +462,21 @@ typedef struct kh_model_opts {
  * Inert - the launches of the same model without the flag - on a head size other than 48 / 64 / 128 and on a geometry
  * the wide pass refuses.  Hook KH_WIDE_ATTN=1 / 0 at creation overrides the flag.  kh_model_wide_attn_info reports. */
 #define KH_FLAG_WIDE_ATTN 512
+/* GEMM16_F16: the GEMM pass of an fp16-origin fp32 model on the bf16 matrix cores, fp32-accurate, from the 16-bit copy in
+ * its fp16 format (csrc/kh_gemm_h16.h): no second copy, no rounding.  Takes effect only where the model holds a live
+ * 16-bit copy in fp16 format (KH_FLAG_W16_F16 on an image that is fp16-exact and not bf16-exact) and the GEMM prefill
+ * runs on its geometry.  The GEMMs of kh_model_prefill_gemm (and the default prompt path of kh_model_generate),
+ * kh_model_seq_prefill_gemm, kh_model_seq_step_gemm and kh_model_generate_batch_gemm then split every fp16 weight of the
+ * copy exactly into two bf16 terms in registers (w_hi + w_lo == w) and every fp32 activation into three
+ * (hi + mid + lo == x), so six v_mfma_f32_16x16x32_bf16 per 32 columns accumulate the fp32 dot product in fp32, every
+ * product exact: kh_model_prefill_gemm's contract (fp32 round-off from another summation order), not the bits of the
+ * fp32 kernels.  Per launch class (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls): a class whose contraction length is no multiple
+ * of 32, or that the adoption mask leaves out (kh_plan_gemm16_f16; hook KH_GEMM16_F16_CLASSES=<mask> at creation), keeps
+ * its fp32 kernel.  Inert - the launches and bits of the same model without the flag - on a bf16-format copy (that is
+ * KH_FLAG_GEMM16's case: with both flags set a caller gets the matrix-core path whichever format the image is exact
+ * in), an int8 model, an image that is not fp16-exact, and without KH_FLAG_W16_F16.  Hook KH_GEMM16_F16=1 / 0 at
+ * creation overrides the flag.  kh_model_gemm16_f16_info reports. */
+#define KH_FLAG_GEMM16_F16 1024
 
 typedef struct kh_config {
   int32_t dim, hidden_dim, layer_num, head_num, kv_head_num, vocab_size, seq_len;
@@ -540,6 +561,13 @@ int kh_model_gemm16_info(kh_model* m, int64_t* out8);
  * 1 flag not set, 2 fp32 model, 3 group size is not 64, 4 geometry off the GEMM prefill, 5 no class left by the mask),
  * kh_plan_gemm16_q8's mask for the geometry (0 where inert before the plan); slots 4 - 7 are 0. */
 int kh_model_gemm16_q8_info(kh_model* m, int64_t* out8);
+/* GEMM16_F16 (KH_FLAG_GEMM16_F16): out[8] = state (1: some class of the GEMM pass runs on the bf16 matrix cores from the
+ * fp16-format copy, 0: inert), bit mask of those classes (1 qkv, 2 wo, 4 ffn13, 8 w2, 16 cls), the reason where inert
+ * (0 none, 1 flag not set, 2 no KH_FLAG_W16_F16, 3 int8 model, 4 image not fp16-exact, 5 the copy is in bf16 format, 6
+ * geometry off the GEMM prefill or the W16 view, 7 no class left by the mask and the K % 32 rule, 8 the copy's
+ * creation-time self-check failed), kh_plan_gemm16_f16's mask for the geometry (0 where inert before the plan); slots
+ * 4 - 7 are 0. */
+int kh_model_gemm16_f16_info(kh_model* m, int64_t* out8);
 /* WIDE_ATTN (KH_FLAG_WIDE_ATTN): out[8] = state (1: the wide pass launches k_sg_attn + k_sg_attn_merge per layer, 0:
  * inert), the reason where inert (0 none, 1 flag not set, 2 head size other than 48 / 64 / 128, 3 a geometry the wide
  * pass refuses), bytes of the partial workspace (0 before the first wide call under the flag), the most chunks an item
@@ -1228,6 +1256,12 @@ int kh_plan_gemm16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t voca
  * the int8 GEMM prefill does not take), columns of a K block (64)}. */
 int kh_plan_gemm16_q8(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t is_quant,
                       int32_t group_size, int64_t* out2);
+/* kh_plan_gemm16_f16: out2 = {bit mask of the launch classes whose GEMMs of the GEMM pass run on the bf16 matrix cores
+ * from the fp16-format copy under KH_FLAG_GEMM16_F16 for this geometry by default (0: int8, dims the GEMM prefill does
+ * not take, or no class adopted): the adoption mask among the classes whose contraction length (dim; w2: hidden_dim)
+ * is a multiple of 32, columns of a K block (32)}. */
+int kh_plan_gemm16_f16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t is_quant,
+                       int64_t* out2);
 int kh_plan_attention(int32_t head_num, int32_t kv_mul, int32_t head_size, int32_t seq_len, int32_t pos,
                       int32_t* out8);
 /* kh_plan_attention_launch: ONE decode-attention launch over the tokens at positions pos[0 .. n) of that geometry (a

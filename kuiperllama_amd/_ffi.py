@@ -15,20 +15,20 @@ LIB_PATH = os.environ.get("KH_LIB") or os.path.join(_PKG, "lib", "libkuiper_hip.
 # every symbol include/kuiper_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "kh_error_string", "kh_version", "kh_device_count",
-    "kh_add_f32", "kh_matmul_f32", "kh_gemm_w16_f32", "kh_gemm_q8_bf16_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
+    "kh_add_f32", "kh_matmul_f32", "kh_gemm_w16_f32", "kh_gemm_h16_f32", "kh_gemm_q8_bf16_f32", "kh_matmul_q8", "kh_embedding_f32", "kh_embedding_f32_host", "kh_swiglu_f32",
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
     "kh_mha_prefill_layout_f32", "kh_mha_prefill_tiles_f32", "kh_mha_decode_lanes_f32",
     "kh_mha_decode_workspace_bytes", "kh_argmax_f32", "kh_argmax_rows_f32",
     "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_cls_logprobs_workspace_bytes", "kh_cls_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
-    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_gemm16_q8_info", "kh_model_wide_attn_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
+    "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_gemm16_q8_info", "kh_model_gemm16_f16_info", "kh_model_wide_attn_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
     "kh_spm_create_from_file", "kh_spm_create_from_memory", "kh_spm_destroy", "kh_spm_vocab_size",
     "kh_spm_bos_id", "kh_spm_eos_id", "kh_spm_unk_id", "kh_spm_encode", "kh_spm_decode",
     "kh_bpe_create_from_file", "kh_bpe_create_from_memory", "kh_bpe_destroy", "kh_bpe_vocab_size",
     "kh_bpe_bos_id", "kh_bpe_eos_id", "kh_bpe_stop_id", "kh_bpe_encode", "kh_bpe_decode",
     "kh_model_generate", "kh_model_generate_until", "kh_model_first_sample", "kh_model_set_sampling", "kh_model_get_sampling", "kh_model_set_penalties", "kh_model_get_penalties", "kh_model_set_logit_bias", "kh_model_set_logprobs", "kh_model_get_logprobs_setting", "kh_model_get_logprobs", "kh_model_time_step", "kh_model_prefill", "kh_model_prefill_gemm", "kh_model_score", "kh_model_score_gemm", "kh_model_verify_width", "kh_model_verify", "kh_model_generate_lookup", "kh_model_verify_as_set", "kh_model_generate_lookup_as_set", "kh_lookup_draft", "kh_lookup_draft_fsm", "kh_model_verify_fsm", "kh_model_generate_lookup_fsm", "kh_model_seq_slots", "kh_model_seq_width", "kh_model_seq_prefill", "kh_model_seq_fork", "kh_model_seq_step", "kh_model_generate_batch", "kh_model_generate_batch_from", "kh_model_seq_step_ex", "kh_model_generate_batch_ex", "kh_model_seq_set_history", "kh_model_seq_get_logprobs", "kh_seq_rank", "kh_model_time_prefill", "kh_model_profile_kernel", "kh_model_profile_step", "kh_kclass_name",
-    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_q4", "kh_plan_gemm16", "kh_plan_gemm16_q8", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
+    "kh_plan_decode_shapes", "kh_plan_decode_ring", "kh_plan_w16", "kh_plan_q4", "kh_plan_gemm16", "kh_plan_gemm16_q8", "kh_plan_gemm16_f16", "kh_plan_prefill_shape", "kh_plan_attention", "kh_plan_attention_launch", "kh_plan_seq_slots", "kh_plan_seq_batch",
     "kh_model_seq_slots_var", "kh_plan_seq_slots_var", "kh_model_seq_share", "kh_model_seq_row",
     "kh_model_seq_width_gemm", "kh_model_seq_step_gemm", "kh_model_generate_batch_gemm", "kh_model_seq_gemm_logits", "kh_plan_seq_batch_wide",
     "kh_plan_seq_prefill_gemm", "kh_model_seq_prefill_gemm", "kh_plan_wide_attn",
@@ -61,6 +61,10 @@ KH_GEMM16_Q8_REASONS = ("on", "flag not set", "fp32 model", "group size not 64",
 KH_FLAG_WIDE_ATTN = 512  # the wide pass's attention in one launch per layer, shared prefixes read once (wide_attn_info)
 # kh_model_wide_attn_info, slot 1: why the flag does nothing on a model
 KH_WIDE_ATTN_REASONS = ("on", "flag not set", "head size", "geometry")
+KH_FLAG_GEMM16_F16 = 1024  # the GEMM pass on the fp16-format copy on the bf16 matrix cores (KuiperModel.gemm16_f16_info)
+# kh_model_gemm16_f16_info, slot 2: why the flag does nothing on a model
+KH_GEMM16_F16_REASONS = ("on", "flag not set", "no W16_F16 flag", "int8 model", "image not fp16-exact", "bf16-format copy",
+                         "geometry", "no class", "self-check failed")
 KH_Q4_CLASSES = KH_W16_CLASSES  # bit i of a class mask (kh_model_q4_info, kh_plan_q4, hook KH_Q4_CLASSES)
 KH_LOGPROBS_MAX_TOP = 20
 KH_SEQ_BIAS_MAX = 64
@@ -233,6 +237,9 @@ def lib() -> C.CDLL:
     L.kh_plan_gemm16.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
     L.kh_gemm_w16_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
     L.kh_model_gemm16_q8_info.argtypes = [_vp, C.POINTER(_i64)]
+    L.kh_model_gemm16_f16_info.argtypes = [_vp, C.POINTER(_i64)]
+    L.kh_plan_gemm16_f16.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]
+    L.kh_gemm_h16_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
     L.kh_model_wide_attn_info.argtypes = [_vp, C.POINTER(_i64)]
     L.kh_mha_decode_lanes_f32.argtypes = [_i32, _vp] + [_i32] * 6 + [_vp, _vp, _vp, _vp, _vp]
     L.kh_plan_wide_attn.argtypes = [_i32, _vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32), C.POINTER(_i32)]
@@ -505,6 +512,17 @@ def plan_gemm16_q8(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quan
     rc = lib().kh_plan_gemm16_q8(dim, hidden_dim, kv_dim, vocab_size, int(quant), group_size, out)
     if rc != 0:
         raise KhError(rc, "kh_plan_gemm16_q8")
+    return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
+
+
+def plan_gemm16_f16(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quant: bool) -> dict:
+    """KH_FLAG_GEMM16_F16 for a geometry (host-only, kh_plan_gemm16_f16): {"classes": the launch classes whose GEMMs of
+    the GEMM pass run on the bf16 matrix cores from the fp16-format copy by default - [] for int8, for dims the GEMM
+    prefill does not take and where no class is adopted -, "kblock": 32}."""
+    out = (_i64 * 2)()
+    rc = lib().kh_plan_gemm16_f16(dim, hidden_dim, kv_dim, vocab_size, int(quant), out)
+    if rc != 0:
+        raise KhError(rc, "kh_plan_gemm16_f16")
     return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
 
 

@@ -5,6 +5,7 @@
 //   constexpr bool KH_GEMM_W16   the K loop: false - pg_kloop_f32 / pg_kloop_q8 on the image; true - pg_kloop_w16
 //                           (kh_gemm_w16.h) on the 16-bit copy
 //   constexpr bool KH_GEMM_Q16   with QUANT: pg_kloop_q16 (kh_gemm_q16.h) on the int8 image in place of pg_kloop_q8
+//   constexpr bool KH_GEMM_H16   pg_kloop_h16 (kh_gemm_h16.h) on the 16-bit copy in its fp16 format (never with the two above)
 //   const KhPgGemmArgs a    its first kernel argument
 //   addr                    the token addressing of the QKV epilogue: addr.pos(tok) = the RoPE row, addr.row(tok) = the
 //                           cache row of token tok (PgRunAddr, SgLaneAddr)
@@ -52,8 +53,8 @@
   // (the K range depends on the wave index only: keep it in scalar registers so the block guards
   // of the K loop are scalar branches)
   PgBAddr B;
-  if constexpr (KH_GEMM_W16) {
-    // the 16-bit copy on the bf16 matrix cores (kh_gemm_w16.h): blocks of 32 columns; the activation slabs are the fp32
+  if constexpr (KH_GEMM_W16 || KH_GEMM_H16) {
+    // the 16-bit copy on the bf16 matrix cores (kh_gemm_w16.h; its fp16 format: kh_gemm_h16.h): blocks of 32 columns; the activation slabs are the fp32
     // loops' - the lane's eight columns 32b + 8h .. are half h & 1 of the tiled slab's 16-column block 2b + (h >> 1)
     const int nb = K >> 5;
     const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);
@@ -67,7 +68,11 @@
     } else {
       B = PgBAddr{a.B + (size_t)(tok0 + i) * K + 8 * h, (size_t)16 * K, 32, 0};
     }
-    if (b1 > b0) pg_kloop_w16<R, NT>(wrow, B, b0, b1, acc);
+    if constexpr (KH_GEMM_H16) {
+      if (b1 > b0) pg_kloop_h16<R, NT>(wrow, B, b0, b1, acc);
+    } else {
+      if (b1 > b0) pg_kloop_w16<R, NT>(wrow, B, b0, b1, acc);
+    }
   } else if (!QUANT) {
     const int nb = K >> 4;
     const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);

@@ -209,7 +209,8 @@ namespace {
 // epi: KH_PG_*; STORE (the classifier GEMM of the wide sequence pass) plans as a residual GEMM without a K split
 // across workgroups.
 // kcols: the columns of a K block of the loop that runs - 16 fp32, 64 int8, 32 on the 16-bit copy (kh_gemm_w16.h)
-// q16: the int8 loop on the bf16 matrix cores runs (kh_gemm_q16.h): no (2,8) tile - a hook that asks for it gets (2,4)
+// q16: the int8 loop on the bf16 matrix cores runs (kh_gemm_q16.h), or the fp16-format copy's (kh_gemm_h16.h, kcols 32):
+// no (2,8) tile - a hook that asks for it gets (2,4)
 PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K, int kcols, bool q16 = false) {
   const bool q = m->cfg.is_quant;
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
@@ -318,6 +319,8 @@ inline int pg_lane_groups(const PgPass& p) { return (p.n + KH_PF_BMAX - 1) / KH_
 // cores (KH_FLAG_GEMM16: gemm16_runs) the same shape - planned in blocks of 32 columns - launches the _w16 stem
 // (kh_gemm_w16.h, compiled in kh_model_gemm_w16.hip) with the weight pointers swapped; everything else is untouched.
 // An int8 group-64 model under KH_FLAG_GEMM16_Q8 (gemm16_q8_runs) launches the _q16 stem on the image's own pointers.
+// A copy in its fp16 format under KH_FLAG_GEMM16_F16 (gemm16_f16_runs) launches the _h16 stem (kh_gemm_h16.h) in the shape
+// the _w16 path plans - blocks of 32 columns, a minimum K range of 8 blocks, never solo - without the (2,8) tile.
 struct PgOn16 {
   int cls;
   const void* w[3];
@@ -327,7 +330,8 @@ int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmAr
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
   const bool w16 = gemm16_runs(m, on16.cls);
   const bool q16 = gemm16_q8_runs(m, on16.cls);  // (an int8 model: never both)
-  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K, w16 ? 32 : (m->cfg.is_quant ? 64 : 16), q16);
+  const bool h16 = gemm16_f16_runs(m, on16.cls);  // (the copy is in its fp16 format: never with w16)
+  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K, w16 || h16 ? 32 : (m->cfg.is_quant ? 64 : 16), q16 || h16);
   if (p.lanes && sh.NT > 4) {  // a hook asked for the 128-token tile
     sh.NT = 4;
     sh.slices = ((a.T + 15) / 16 + 3) / 4;
@@ -346,6 +350,13 @@ int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmAr
       if (on16.w[j]) a.w[j].w = on16.w[j];
     const int t = tile >= 0 ? tile : (sh.R == 2 ? 2 : 3);
     launched = pg_gemm_w16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
+                                  p.lanes);
+  } else if (h16) {
+    // the _w16 path's shape and weight pointers on the _h16 stem (kh_gemm_h16.h, compiled in kh_model_gemm_h16.hip)
+    for (int j = 0; j < 3; ++j)
+      if (on16.w[j]) a.w[j].w = on16.w[j];
+    const int t = tile >= 1 ? tile : (sh.R == 2 ? 2 : 3);
+    launched = pg_gemm_h16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
                                   p.lanes);
   } else if (q16) {
     // the int8 image's own weight and scale pointers, on the _q16 stem (kh_gemm_q16.h, compiled in kh_model_gemm_q16.hip)

@@ -12,6 +12,8 @@
 //   kh_model_gemm_w16.hip the same GEMMs on the bf16 matrix cores from the 16-bit copy (KH_FLAG_GEMM16; kh_gemm_w16.h kernels)
 //   kh_model_gemm_q16.hip the GEMMs of an int8 group-64 model on the bf16 matrix cores from the int8 image (KH_FLAG_GEMM16_Q8;
 //                         kh_gemm_q16.h kernels)
+//   kh_model_gemm_h16.hip the GEMMs of an fp16-origin fp32 model on the bf16 matrix cores from the fp16-format 16-bit copy
+//                         (KH_FLAG_GEMM16_F16; kh_gemm_h16.h kernels)
 //   kh_model_wide_attn.hip the wide pass's attention in one launch per layer (KH_FLAG_WIDE_ATTN; kh_seq_attn_wide.h kernels,
 //                         kh_wide_attn_plan.h) and its operator-level entry
 //   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
@@ -406,6 +408,17 @@ struct kh_model {
     int plan = 0;           // plan_gemm16_q8's mask for the geometry, whatever the hook says (0 unless the flag is live)
   };
   Gemm16Q8 g16q8;
+  // KH_FLAG_GEMM16_F16 / hook KH_GEMM16_F16 (kh_gemm_h16.h, kh_model_gemm_h16.hip): classes whose GEMMs of the
+  // GEMM pass (kh_model_gemm.hip: pg_gemm) run on the bf16 matrix cores from the 16-bit copy in its fp16 format - a live
+  // fp16-format copy (w16), the GEMM prefill's geometry, K a multiple of 32 and the adoption mask (plan_gemm16_f16, hook
+  // KH_GEMM16_F16_CLASSES); 0 wherever the flag is inert, and reason says why (KH_GEMM16_F16_*: kh_model_gemm16_f16_info).
+  // The copy is w16's: a copy its self-check gives up (w16.state -2) takes these launches with it (gemm16_f16_runs).
+  struct Gemm16F16 {
+    int classes = 0;
+    int reason = 0;
+    int plan = 0;           // plan_gemm16_f16's mask for the geometry, whatever the hook says (0 unless the flag is live)
+  };
+  Gemm16F16 g16f16;
   // KH_FLAG_WIDE_ATTN / hook KH_WIDE_ATTN (kh_seq_attn_wide.h, kh_model_wide_attn.hip): the wide pass's
   // attention as k_sg_attn + k_sg_attn_merge per layer instead of the grouped launches; off wherever the flag is inert,
   // and reason says why (KH_WIDE_ATTN_*: kh_model_wide_attn_info).  ws: the partials, made by the first wide call under
@@ -465,6 +478,14 @@ static inline bool gemm16_q8_runs(const kh_model* m, int cls) { return (m->g16q8
 // why KH_FLAG_GEMM16_Q8 does nothing on a model (kh_model_gemm16_q8_info, slot 2); KH_GEMM16_Q8_ON: it does something
 enum { KH_GEMM16_Q8_ON = 0, KH_GEMM16_Q8_NO_FLAG = 1, KH_GEMM16_Q8_FP32 = 2, KH_GEMM16_Q8_GROUP = 3,
        KH_GEMM16_Q8_GEOMETRY = 4, KH_GEMM16_Q8_NO_CLASS = 5 };
+// the GEMM pass of the class on the bf16 matrix cores from the fp16-format copy (KH_FLAG_GEMM16_F16; kh_model_gemm.hip: pg_gemm)
+static inline bool gemm16_f16_runs(const kh_model* m, int cls) {
+  return m->w16.state == 1 && m->w16.format == 1 /* KH_W16_F16 */ && (m->g16f16.classes & cls) != 0;
+}
+// why KH_FLAG_GEMM16_F16 does nothing on a model (kh_model_gemm16_f16_info, slot 2); KH_GEMM16_F16_ON: it does something
+enum { KH_GEMM16_F16_ON = 0, KH_GEMM16_F16_NO_FLAG = 1, KH_GEMM16_F16_NO_W16_F16 = 2, KH_GEMM16_F16_QUANT = 3,
+       KH_GEMM16_F16_INEXACT = 4, KH_GEMM16_F16_BF16_COPY = 5, KH_GEMM16_F16_GEOMETRY = 6, KH_GEMM16_F16_NO_CLASS = 7,
+       KH_GEMM16_F16_SELFCHECK = 8 };
 // the B-token pass of the class (kh_model_prefill.hip: launch_pf_pass, pf_gemv_res, launch_pf_cls)
 static inline bool w16_pass_runs(const kh_model* m, int cls) { return (m->w16.pass_classes & cls) != 0; }
 // classes whose B-token pass reads the 4-bit copy unless KH_Q4_PASS says otherwise: the ones 3.1c's adoption rule keeps
@@ -709,6 +730,14 @@ bool pg_gemm_q16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemm
 // classes that run on it by default for a geometry (0: not an int8 group-64 model the GEMM prefill takes)
 int plan_gemm16_q8(bool quant, int group_size, int dim, int hidden_dim, int kv_dim, int vocab_size);
 void gemm16_q8_configure(kh_model* m);  // at creation
+// ---- kh_model_gemm_h16.hip ------------------------------------------------------------------
+// the same launch on the k_*_gemm_h16 kernels (kh_gemm_h16.h): a as for pg_gemm_w16_launch, the copy in its fp16 format.
+// The stem has no (2,8) register tile: the caller plans without it
+bool pg_gemm_h16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemmArgs& a, const KhRgTiles* tiles,
+                        const KhWideLanes* lanes);
+// classes that run on it by default for a geometry (0: int8, dims the GEMM prefill does not take, or none adopted)
+int plan_gemm16_f16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size);
+void gemm16_f16_configure(kh_model* m);  // at creation, behind w16_create
 // kh_model_prefill_gemm without the token record (hist_write); prefill_gemm_prepare: its slabs, made by the call
 // itself or ahead of it by whoever times it
 // d_score_target (device, [n]: the token that followed token i, -1 behind the last): every pass runs at full depth and

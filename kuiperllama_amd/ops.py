@@ -60,6 +60,20 @@ def gemm_w16(x, w16, out=None):
     return out
 
 
+def gemm_h16(x, w16, out=None):
+    """out[T, M] = x[T, K] @ w16[M, K]^T on the bf16 matrix cores, fp32-accurate (kh_gemm_h16_f32): w16 holds fp16 bits
+    (torch.float16, or int16 / uint16 words); M % 16 == 0, K % 32 == 0, T <= 512.  out may be a [T, ldy >= M] buffer."""
+    T, K = x.shape
+    M, K2 = w16.shape
+    if K2 != K or w16.element_size() != 2:
+        raise ValueError("gemm_h16: w16 must be [M, K] 16-bit words")
+    if out is None:
+        out = torch.empty((T, M), dtype=torch.float32, device=x.device)
+    _ffi.check(_ffi.lib().kh_gemm_h16_f32(_p(x, torch.float32), _p(w16), _p(out, torch.float32), T, M, K,
+                                          out.stride(0), _stream()), "kh_gemm_h16_f32")
+    return out
+
+
 def gemm_q8_bf16(x, w8, scales, out=None):
     """out[T, M] = x[T, K] @ (scales * w8)[M, K]^T on the bf16 matrix cores, fp32-accurate (kh_gemm_q8_bf16_f32): w8 is
     int8 [M, K] in groups of 64 columns, scales fp32 [M, K / 64]; M % 16 == 0, K % 64 == 0, T <= 512.  out may be a
