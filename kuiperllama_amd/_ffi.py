@@ -494,36 +494,32 @@ def plan_w16(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, n_layers: 
     return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "bytes": int(out[1])}
 
 
+def _plan_gemm16(entry: str, *args) -> dict:
+    out = (_i64 * 2)()
+    rc = getattr(lib(), entry)(*args, out)
+    if rc != 0:
+        raise KhError(rc, entry)
+    return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
+
+
 def plan_gemm16(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quant: bool) -> dict:
     """KH_FLAG_GEMM16 for a geometry (host-only, kh_plan_gemm16): {"classes": the launch classes whose GEMMs of the GEMM
     pass run on the bf16 matrix cores - [] for int8 and for dims the GEMM prefill does not take -, "kblock": 32}."""
-    out = (_i64 * 2)()
-    rc = lib().kh_plan_gemm16(dim, hidden_dim, kv_dim, vocab_size, int(quant), out)
-    if rc != 0:
-        raise KhError(rc, "kh_plan_gemm16")
-    return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
+    return _plan_gemm16("kh_plan_gemm16", dim, hidden_dim, kv_dim, vocab_size, int(quant))
 
 
 def plan_gemm16_q8(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quant: bool, group_size: int = 64) -> dict:
     """KH_FLAG_GEMM16_Q8 for a geometry (host-only, kh_plan_gemm16_q8): {"classes": the launch classes whose GEMMs of the
     GEMM pass run on the bf16 matrix cores from the int8 image by default - [] for fp32, for a group size other than 64
     and for dims the int8 GEMM prefill does not take -, "kblock": 64}."""
-    out = (_i64 * 2)()
-    rc = lib().kh_plan_gemm16_q8(dim, hidden_dim, kv_dim, vocab_size, int(quant), group_size, out)
-    if rc != 0:
-        raise KhError(rc, "kh_plan_gemm16_q8")
-    return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
+    return _plan_gemm16("kh_plan_gemm16_q8", dim, hidden_dim, kv_dim, vocab_size, int(quant), group_size)
 
 
 def plan_gemm16_f16(dim: int, hidden_dim: int, kv_dim: int, vocab_size: int, quant: bool) -> dict:
     """KH_FLAG_GEMM16_F16 for a geometry (host-only, kh_plan_gemm16_f16): {"classes": the launch classes whose GEMMs of
     the GEMM pass run on the bf16 matrix cores from the fp16-format copy by default - [] for int8, for dims the GEMM
     prefill does not take and where no class is adopted -, "kblock": 32}."""
-    out = (_i64 * 2)()
-    rc = lib().kh_plan_gemm16_f16(dim, hidden_dim, kv_dim, vocab_size, int(quant), out)
-    if rc != 0:
-        raise KhError(rc, "kh_plan_gemm16_f16")
-    return {"classes": [n for i, n in enumerate(KH_W16_CLASSES) if out[0] >> i & 1], "kblock": int(out[1])}
+    return _plan_gemm16("kh_plan_gemm16_f16", dim, hidden_dim, kv_dim, vocab_size, int(quant))
 
 
 def plan_wide_attn(lanes, kv_mul: int, head_size: int, seq_len: int = 0) -> list:

@@ -45,6 +45,8 @@
 // fp32 tolerance against the oracle (tests/test_model_gpu.py::test_gemm_prefill_*).  The bit-exact
 // B-token path stays available (kh_model_prefill / KH_PREFILL=gemv).
 #pragma once
+#include <type_traits>
+
 #include "kh_fused.h"
 
 // Prompt tokens per weight pass.  128 tokens (8 MFMA token tiles) already put every GEMM above the
@@ -162,6 +164,28 @@ struct PgBAddr {           // activation operand addressing: base + nt*s_nt + bl
   const float* base;
   size_t s_nt, s_b, s_q;   // in floats
 };
+// The K loop a kernel stem runs - the ONE constant kh_gemm_body.h is steered by.  PG_F32 / PG_Q8: pg_kloop_f32 /
+// pg_kloop_q8 below, on the image.  On the bf16 matrix cores: PG_W16 the 16-bit copy in bf16 format (kh_gemm_w16.h),
+// PG_H16 the same copy in fp16 format (kh_gemm_h16.h), PG_Q16 the int8 image (kh_gemm_q16.h).
+enum PgCore { PG_F32, PG_Q8, PG_W16, PG_H16, PG_Q16 };
+template <PgCore CORE>
+struct PgCoreTraits {
+  static constexpr bool QUANT = CORE == PG_Q8 || CORE == PG_Q16;          // the image is int8 group-64
+  static constexpr int KSHIFT = CORE == PG_F32 ? 4 : (QUANT ? 6 : 5);      // log2 of the columns of a K block: 16 / 64 / 32
+  using W = std::conditional_t<QUANT, int8_t, std::conditional_t<CORE == PG_F32, float, uint16_t>>;  // a weight element
+};
+// PgKloop<CORE>::run<R, NT>(wrow, [srow,] B, b0, b1, acc): the loop of a core, stated beside it (KH_PG_KLOOP) - the body
+// names loops that the headers behind this one define
+template <PgCore CORE>
+struct PgKloop;
+#define KH_PG_KLOOP(CORE, FN)                                        \
+  template <>                                                        \
+  struct PgKloop<CORE> {                                             \
+    template <int R, int NT, class... A>                             \
+    static __device__ __forceinline__ void run(A&... operands) {     \
+      FN<R, NT>(operands...);                                        \
+    }                                                                \
+  }
 
 // fp32 weights: blocks of 16 columns; lane (i, h) owns W[i][16b + 4h .. +4] of each of its R tiles
 template <int R, int NT>
@@ -292,6 +316,7 @@ __device__ __forceinline__ void pg_kloop_q8(const int8_t* const (&wrow)[R],
   };
   pg_phases<RING, 4>(b0, b1, load_a, load_b, sub);
 }
+KH_PG_KLOOP(PG_Q8, pg_kloop_q8);
 
 // blockDim.x = NM * ks * 64 (NM = 2 for SWIGLU); blockIdx.x = (16*R)-row tile; blockIdx.y = slice of
 // 16*NT tokens.  LDS: [waves][NT][64] float4 partial tiles (skipped when one wave owns the whole K).
@@ -299,18 +324,6 @@ __device__ __forceinline__ void pg_kloop_q8(const int8_t* const (&wrow)[R],
 // The statements of the kernel live in kh_gemm_body.h, included by the two kernels that differ in the token addressing
 // of the QKV epilogue only: k_pg_gemm below addresses a run of consecutive positions of one sequence (PgRunAddr),
 // kh_seq_gemm.h: k_sg_gemm lanes of different sequences (a lane table).
-// (the K loop of kh_gemm_w16.h on the 16-bit copy, which the body names under KH_GEMM_W16)
-template <int R, int NT>
-__device__ __forceinline__ void pg_kloop_w16(const uint16_t* const (&wrow)[R], const PgBAddr& B, int b0, int b1,
-                                             f32x4 (&acc)[R][NT]);
-// (the K loop of kh_gemm_q16.h on the int8 image, which the body names under KH_GEMM_Q16)
-template <int R, int NT>
-__device__ __forceinline__ void pg_kloop_q16(const int8_t* const (&wrow)[R], const float* const (&srow)[R],
-                                             const PgBAddr& B, int b0, int b1, f32x4 (&acc)[R][NT]);
-// (the K loop of kh_gemm_h16.h on the fp16-format 16-bit copy, which the body names under KH_GEMM_H16)
-template <int R, int NT>
-__device__ __forceinline__ void pg_kloop_h16(const uint16_t* const (&wrow)[R], const PgBAddr& B, int b0, int b1,
-                                             f32x4 (&acc)[R][NT]);
 struct PgRunAddr {
   int pos0;
   __device__ __forceinline__ int pos(int tok) const { return pos0 + tok; }
@@ -320,7 +333,7 @@ template <bool QUANT, int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX(QUANT)) void k_pg_gemm(const KhPgGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI != KH_PG_STORE, "the classifier epilogue is the wide sequence pass's (k_sg_gemm)");
-  constexpr bool KH_GEMM_W16 = false, KH_GEMM_Q16 = false, KH_GEMM_H16 = false;
+  constexpr PgCore CORE = QUANT ? PG_Q8 : PG_F32;
   const PgRunAddr addr{a.pos0};
 #include "kh_gemm_body.h"
 }

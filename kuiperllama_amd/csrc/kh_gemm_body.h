@@ -1,14 +1,12 @@
 // kh_gemm_body.h — the statements of the GEMM kernel of kh_gemm.h, included INSIDE a kernel definition (no include
-// guard): ONE text for k_pg_gemm (kh_gemm.h: tokens of a run of consecutive positions) and k_sg_gemm (kh_seq_gemm.h:
-// lanes of different sequences).  The including kernel is a template <bool QUANT, int R, int NT, int EPI> - or <int R, int NT,
-// EPI> with QUANT a constant - and has in scope
-//   constexpr bool KH_GEMM_W16   the K loop: false - pg_kloop_f32 / pg_kloop_q8 on the image; true - pg_kloop_w16
-//                           (kh_gemm_w16.h) on the 16-bit copy
-//   constexpr bool KH_GEMM_Q16   with QUANT: pg_kloop_q16 (kh_gemm_q16.h) on the int8 image in place of pg_kloop_q8
-//   constexpr bool KH_GEMM_H16   pg_kloop_h16 (kh_gemm_h16.h) on the 16-bit copy in its fp16 format (never with the two above)
+// guard): ONE text for k_pg_gemm (kh_gemm.h: tokens of a run of consecutive positions), k_rg_gemm (kh_seq_prefill.h: a
+// tile table) and k_sg_gemm (kh_seq_gemm.h: lanes of different sequences), and for their twins on the bf16 matrix cores.
+// The including kernel is a template <int R, int NT, int EPI> (behind a bool QUANT in the fp32 / int8 stems) and has in
+// scope
+//   constexpr PgCore CORE   the K loop (kh_gemm.h: PgCore, PgCoreTraits) - all this text is steered by
 //   const KhPgGemmArgs a    its first kernel argument
 //   addr                    the token addressing of the QKV epilogue: addr.pos(tok) = the RoPE row, addr.row(tok) = the
-//                           cache row of token tok (PgRunAddr, SgLaneAddr)
+//                           cache row of token tok (PgRunAddr, RgTileAddr, SgLaneAddr)
 //   char smem_raw[]         the dynamic LDS
 // Textual, not a device function template (the way pf_qkv_body is): the arguments would reach a function through a
 // generic-address-space reference, the compiler then no longer reads them straight from the kernel-argument segment,
@@ -52,15 +50,16 @@
     for (int nt = 0; nt < NT; ++nt) acc[r][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
   // (the K range depends on the wave index only: keep it in scalar registers so the block guards
   // of the K loop are scalar branches)
+  using PgT = PgCoreTraits<CORE>;
+  const int nb = K >> PgT::KSHIFT;  // K blocks: of the workgroup's slice [z0, z1), of this wave [b0, b1)
+  const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);
+  const int b0 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)kpart * (z1 - z0) / ks));
+  const int b1 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)(kpart + 1) * (z1 - z0) / ks));
+  const typename PgT::W* wrow[R];
   PgBAddr B;
-  if constexpr (KH_GEMM_W16 || KH_GEMM_H16) {
+  if constexpr (CORE == PG_W16 || CORE == PG_H16) {
     // the 16-bit copy on the bf16 matrix cores (kh_gemm_w16.h; its fp16 format: kh_gemm_h16.h): blocks of 32 columns; the activation slabs are the fp32
     // loops' - the lane's eight columns 32b + 8h .. are half h & 1 of the tiled slab's 16-column block 2b + (h >> 1)
-    const int nb = K >> 5;
-    const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);
-    const int b0 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)kpart * (z1 - z0) / ks));
-    const int b1 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)(kpart + 1) * (z1 - z0) / ks));
-    const uint16_t* wrow[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) wrow[r] = (const uint16_t*)W.w + (size_t)(wr0 + rstep * r + i) * K + 8 * h;
     if (a.b_tiled) {
@@ -68,17 +67,8 @@
     } else {
       B = PgBAddr{a.B + (size_t)(tok0 + i) * K + 8 * h, (size_t)16 * K, 32, 0};
     }
-    if constexpr (KH_GEMM_H16) {
-      if (b1 > b0) pg_kloop_h16<R, NT>(wrow, B, b0, b1, acc);
-    } else {
-      if (b1 > b0) pg_kloop_w16<R, NT>(wrow, B, b0, b1, acc);
-    }
-  } else if (!QUANT) {
-    const int nb = K >> 4;
-    const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);
-    const int b0 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)kpart * (z1 - z0) / ks));
-    const int b1 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)(kpart + 1) * (z1 - z0) / ks));
-    const float* wrow[R];
+    if (b1 > b0) PgKloop<CORE>::template run<R, NT>(wrow, B, b0, b1, acc);
+  } else if constexpr (CORE == PG_F32) {
 #pragma unroll
     for (int r = 0; r < R; ++r) wrow[r] = (const float*)W.w + (size_t)(wr0 + rstep * r + i) * K + 4 * h;
     if (a.b_tiled) {
@@ -98,15 +88,10 @@
       pg_kloop_f32<R, NT>(wrow, B, b0, b1, acc);
     }
   } else {
-    const int nb = K >> 6;
-    const int z0 = (int)((long)blockIdx.z * nb / gridDim.z), z1 = (int)((long)(blockIdx.z + 1) * nb / gridDim.z);
-    const int b0 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)kpart * (z1 - z0) / ks));
-    const int b1 = __builtin_amdgcn_readfirstlane(z0 + (int)((long)(kpart + 1) * (z1 - z0) / ks));
-    const int8_t* wrow[R];
     const float* srow[R];
     // the scale a lane loads: pg_kloop_q8 scales the weights of row i; pg_kloop_q16 (kh_gemm_q16.h) scales the partial
     // sums, and the lane's quad shares the scales of the rows 4h .. 4h + 3 its accumulators hold
-    const int si = KH_GEMM_Q16 ? 4 * h + (i & 3) : i;
+    const int si = CORE == PG_Q16 ? 4 * h + (i & 3) : i;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       wrow[r] = (const int8_t*)W.w + (size_t)(wr0 + rstep * r + i) * K + 16 * h;
@@ -118,11 +103,7 @@
     } else {
       B = PgBAddr{a.B + (size_t)(tok0 + i) * K + 16 * h, (size_t)16 * K, 64, 4};
     }
-    if constexpr (KH_GEMM_Q16) {
-      if (b1 > b0) pg_kloop_q16<R, NT>(wrow, srow, B, b0, b1, acc);
-    } else {
-      if (b1 > b0) pg_kloop_q8<R, NT>(wrow, srow, B, b0, b1, acc);
-    }
+    if (b1 > b0) PgKloop<CORE>::template run<R, NT>(wrow, srow, B, b0, b1, acc);
   }
   // ---- combine the K slices (fixed order) and run the epilogue on float4 = 4 rows x 1 token,
   //      one 16-row tile at a time (the LDS area holds one tile row of partials) -------------------
@@ -235,7 +216,7 @@
         o.y = swiglu1(v0.y, v1.y);
         o.z = swiglu1(v0.z, v1.z);
         o.w = swiglu1(v0.w, v1.w);
-        *(f32x4*)(a.out + pg_tiled_index(QUANT, orow, tok, a.tcap)) = o;  // H feeds the w2 GEMM: tiled slab
+        *(f32x4*)(a.out + pg_tiled_index(PgT::QUANT, orow, tok, a.tcap)) = o;  // H feeds the w2 GEMM: tiled slab
       }
     }
   }

@@ -70,38 +70,23 @@ struct PgH16Ring {
   static constexpr int D = R * NT >= 8 ? 3 : 4;
 };
 
-// fp16 weights: blocks of 32 columns [b0, b1), b1 > b0; wrow / B as pg_kloop_w16's
+// fp16 weights: pg_kloop_w16's ring (pg_ring16); a slot splits the weights and issues six MFMAs on two accumulators
 template <int R, int NT>
 __device__ __forceinline__ void pg_kloop_h16(const uint16_t* const (&wrow)[R], const PgBAddr& B, int b0, int b1,
                                              f32x4 (&acc)[R][NT]) {
-  constexpr int D = PgH16Ring<R, NT>::D;
-  pg_u32x4 a[D][R];
-  f32x4 xb[D][NT][2];
-  const int last = b1 - 1;
-  auto load = [&](int slot, int bb) __attribute__((always_inline)) {
-    bb = bb < last ? bb : last;  // (wave-uniform)
-#pragma unroll
-    for (int r = 0; r < R; ++r) a[slot][r] = ld_nt((const pg_u32x4*)(wrow[r] + (size_t)bb * 32));
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const float* p = B.base + nt * B.s_nt + (size_t)bb * B.s_b;
-      xb[slot][nt][0] = *(const f32x4*)p;
-      xb[slot][nt][1] = *(const f32x4*)(p + 4);
-    }
-    __builtin_amdgcn_sched_barrier(0);  // slots stay in issue order (vmcnt retires in order)
-  };
   f32x4 accl[R][NT];  // the five small terms (see the head of the file)
 #pragma unroll
   for (int r = 0; r < R; ++r)
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) accl[r][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto mfma = [&](int slot) __attribute__((always_inline)) {
+  pg_ring16<PgH16Ring<R, NT>::D, R, NT>(wrow, B, b0, b1, [&](const pg_u32x4 (&a)[R], const f32x4 (&xb)[NT][2])
+                                                             __attribute__((always_inline)) {
     PgSplitH16 w[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) w[r] = pg_split_h16(a[slot][r]);
+    for (int r = 0; r < R; ++r) w[r] = pg_split_h16(a[r]);
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      const PgSplit3 x = pg_split3(xb[slot][nt][0], xb[slot][nt][1]);
+      const PgSplit3 x = pg_split3(xb[nt][0], xb[nt][1]);
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[r].hi, x.hi, acc[r][nt], 0, 0, 0);
@@ -118,18 +103,7 @@ __device__ __forceinline__ void pg_kloop_h16(const uint16_t* const (&wrow)[R], c
         accl[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[r].lo, x.lo, accl[r][nt], 0, 0, 0);
       }
     }
-  };
-#pragma unroll
-  for (int d = 0; d < D; ++d) load(d, b0 + d);
-  for (int b = b0; b < b1; b += D) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      if (b + d < b1) {  // wave-uniform (b0, b1 are scalars)
-        mfma(d);
-        if (b + d + D < b1) load(d, b + d + D);
-      }
-    }
-  }
+  });
 #pragma unroll
   for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -138,14 +112,15 @@ __device__ __forceinline__ void pg_kloop_h16(const uint16_t* const (&wrow)[R], c
       acc[r][nt].z += accl[r][nt].z; acc[r][nt].w += accl[r][nt].w;
     }
 }
+KH_PG_KLOOP(PG_H16, pg_kloop_h16);
 
-// The kernels: kh_gemm_body.h with the K loop above (KH_GEMM_H16), under the three token addressings of the GEMM pass.
+// The kernels: kh_gemm_body.h with the K loop above (CORE = PG_H16), under the three token addressings of the GEMM pass.
 // KhLin::w of every matrix points into the fp16-format copy.  Launch geometry, LDS and arguments are k_pg_gemm's.
 template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_pg_gemm_h16(const KhPgGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI != KH_PG_STORE, "the classifier epilogue is the wide sequence pass's (k_sg_gemm_h16)");
-  constexpr bool QUANT = false, KH_GEMM_W16 = false, KH_GEMM_Q16 = false, KH_GEMM_H16 = true;
+  constexpr PgCore CORE = PG_H16;
   const PgRunAddr addr{a.pos0};
 #include "kh_gemm_body.h"
 }
@@ -153,14 +128,14 @@ template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_rg_gemm_h16(const KhPgGemmArgs a, const KhRgTiles tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI == KH_PG_QKV, "the other GEMMs of the pass are k_pg_gemm_h16's");
-  constexpr bool QUANT = false, KH_GEMM_W16 = false, KH_GEMM_Q16 = false, KH_GEMM_H16 = true;
+  constexpr PgCore CORE = PG_H16;
   const RgTileAddr addr{tiles};
 #include "kh_gemm_body.h"
 }
 template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_sg_gemm_h16(const KhPgGemmArgs a, const KhWideLanes lanes) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  constexpr bool QUANT = false, KH_GEMM_W16 = false, KH_GEMM_Q16 = false, KH_GEMM_H16 = true;
+  constexpr PgCore CORE = PG_H16;
   const SgLaneAddr addr{lanes};
 #include "kh_gemm_body.h"
 }

@@ -156,14 +156,15 @@ __device__ __forceinline__ void pg_kloop_q16(const int8_t* const (&wrow)[R], con
     }
   }
 }
+KH_PG_KLOOP(PG_Q16, pg_kloop_q16);
 
-// The kernels: kh_gemm_body.h with the K loop above (KH_GEMM_Q16), under the three token addressings of the GEMM pass.
+// The kernels: kh_gemm_body.h with the K loop above (CORE = PG_Q16), under the three token addressings of the GEMM pass.
 // KhLin::w / scales of every matrix are the image's own.  Launch geometry, LDS and arguments are k_pg_gemm's.
 template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_Q8) void k_pg_gemm_q16(const KhPgGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI != KH_PG_STORE, "the classifier epilogue is the wide sequence pass's (k_sg_gemm_q16)");
-  constexpr bool QUANT = true, KH_GEMM_W16 = false, KH_GEMM_Q16 = true, KH_GEMM_H16 = false;
+  constexpr PgCore CORE = PG_Q16;
   const PgRunAddr addr{a.pos0};
 #include "kh_gemm_body.h"
 }
@@ -171,14 +172,14 @@ template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_Q8) void k_rg_gemm_q16(const KhPgGemmArgs a, const KhRgTiles tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI == KH_PG_QKV, "the other GEMMs of the pass are k_pg_gemm_q16's");
-  constexpr bool QUANT = true, KH_GEMM_W16 = false, KH_GEMM_Q16 = true, KH_GEMM_H16 = false;
+  constexpr PgCore CORE = PG_Q16;
   const RgTileAddr addr{tiles};
 #include "kh_gemm_body.h"
 }
 template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_Q8) void k_sg_gemm_q16(const KhPgGemmArgs a, const KhWideLanes lanes) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  constexpr bool QUANT = true, KH_GEMM_W16 = false, KH_GEMM_Q16 = true, KH_GEMM_H16 = false;
+  constexpr PgCore CORE = PG_Q16;
   const SgLaneAddr addr{lanes};
 #include "kh_gemm_body.h"
 }

@@ -70,40 +70,27 @@ struct PgW16Ring {
   static constexpr int D = R * NT >= 16 ? 2 : (R * NT >= 8 ? 3 : 4);
 };
 
-// bf16 weights: blocks of 32 columns [b0, b1), b1 > b0; lane (i, h) owns W16[i][32b + 8h .. +8] of each of its R tiles
-// (wrow[r] points at the lane's eight columns of block 0) and Xn[token][32b + 8h .. +8] of each of its NT token tiles
-// (B.base likewise; s_nt / s_b in floats per token tile / per block of 32)
-template <int R, int NT>
-__device__ __forceinline__ void pg_kloop_w16(const uint16_t* const (&wrow)[R], const PgBAddr& B, int b0, int b1,
-                                             f32x4 (&acc)[R][NT]) {
-  constexpr int D = PgW16Ring<R, NT>::D;
+// The ring of the two loops on the 16-bit copy (here and kh_gemm_h16.h), D slots deep: blocks of 32 columns [b0, b1),
+// b1 > b0; lane (i, h) owns W16[i][32b + 8h .. +8] of each of its R tiles (wrow[r] points at the lane's eight columns of
+// block 0) and Xn[token][32b + 8h .. +8] of each of its NT token tiles (B.base likewise; s_nt / s_b in floats per token
+// tile / per block of 32).  slot(a, xb): what a loop does with a block's operands - the R weight dwordx4 and the NT
+// pairs of activation float4.
+template <int D, int R, int NT, class Slot>
+__device__ __forceinline__ void pg_ring16(const uint16_t* const (&wrow)[R], const PgBAddr& B, int b0, int b1, Slot&& slot) {
   pg_u32x4 a[D][R];
   f32x4 xb[D][NT][2];
   const int last = b1 - 1;
-  auto load = [&](int slot, int bb) __attribute__((always_inline)) {
+  auto load = [&](int d, int bb) __attribute__((always_inline)) {
     bb = bb < last ? bb : last;  // (wave-uniform)
 #pragma unroll
-    for (int r = 0; r < R; ++r) a[slot][r] = ld_nt((const pg_u32x4*)(wrow[r] + (size_t)bb * 32));
+    for (int r = 0; r < R; ++r) a[d][r] = ld_nt((const pg_u32x4*)(wrow[r] + (size_t)bb * 32));
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const float* p = B.base + nt * B.s_nt + (size_t)bb * B.s_b;
-      xb[slot][nt][0] = *(const f32x4*)p;
-      xb[slot][nt][1] = *(const f32x4*)(p + 4);
+      xb[d][nt][0] = *(const f32x4*)p;
+      xb[d][nt][1] = *(const f32x4*)(p + 4);
     }
     __builtin_amdgcn_sched_barrier(0);  // slots stay in issue order (vmcnt retires in order)
-  };
-  auto mfma = [&](int slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const PgSplit3 x = pg_split3(xb[slot][nt][0], xb[slot][nt][1]);
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const bf16x8 w = __builtin_bit_cast(bf16x8, a[slot][r]);
-        acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x.hi, acc[r][nt], 0, 0, 0);
-        acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x.mid, acc[r][nt], 0, 0, 0);
-        acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x.lo, acc[r][nt], 0, 0, 0);
-      }
-    }
   };
 #pragma unroll
   for (int d = 0; d < D; ++d) load(d, b0 + d);
@@ -111,20 +98,41 @@ __device__ __forceinline__ void pg_kloop_w16(const uint16_t* const (&wrow)[R], c
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       if (b + d < b1) {  // wave-uniform (b0, b1 are scalars)
-        mfma(d);
+        slot(a[d], xb[d]);
         if (b + d + D < b1) load(d, b + d + D);
       }
     }
   }
 }
 
-// The kernels: kh_gemm_body.h with the K loop above (KH_GEMM_W16), under the three token addressings of the GEMM pass.
+// bf16 weights: three MFMAs per (row tile, token tile, block) on one accumulator
+template <int R, int NT>
+__device__ __forceinline__ void pg_kloop_w16(const uint16_t* const (&wrow)[R], const PgBAddr& B, int b0, int b1,
+                                             f32x4 (&acc)[R][NT]) {
+  pg_ring16<PgW16Ring<R, NT>::D, R, NT>(wrow, B, b0, b1, [&](const pg_u32x4 (&a)[R], const f32x4 (&xb)[NT][2])
+                                                             __attribute__((always_inline)) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const PgSplit3 x = pg_split3(xb[nt][0], xb[nt][1]);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const bf16x8 w = __builtin_bit_cast(bf16x8, a[r]);
+        acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x.hi, acc[r][nt], 0, 0, 0);
+        acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x.mid, acc[r][nt], 0, 0, 0);
+        acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x.lo, acc[r][nt], 0, 0, 0);
+      }
+    }
+  });
+}
+KH_PG_KLOOP(PG_W16, pg_kloop_w16);
+
+// The kernels: kh_gemm_body.h with the K loop above (CORE = PG_W16), under the three token addressings of the GEMM pass.
 // KhLin::w of every matrix points into the 16-bit copy.  Launch geometry, LDS and arguments are k_pg_gemm's.
 template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_pg_gemm_w16(const KhPgGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI != KH_PG_STORE, "the classifier epilogue is the wide sequence pass's (k_sg_gemm_w16)");
-  constexpr bool QUANT = false, KH_GEMM_W16 = true, KH_GEMM_Q16 = false, KH_GEMM_H16 = false;
+  constexpr PgCore CORE = PG_W16;
   const PgRunAddr addr{a.pos0};
 #include "kh_gemm_body.h"
 }
@@ -132,14 +140,14 @@ template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_rg_gemm_w16(const KhPgGemmArgs a, const KhRgTiles tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   static_assert(EPI == KH_PG_QKV, "the other GEMMs of the pass are k_pg_gemm_w16's");
-  constexpr bool QUANT = false, KH_GEMM_W16 = true, KH_GEMM_Q16 = false, KH_GEMM_H16 = false;
+  constexpr PgCore CORE = PG_W16;
   const RgTileAddr addr{tiles};
 #include "kh_gemm_body.h"
 }
 template <int R, int NT, int EPI>
 __global__ __launch_bounds__(KH_PG_WG_MAX_F32) void k_sg_gemm_w16(const KhPgGemmArgs a, const KhWideLanes lanes) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  constexpr bool QUANT = false, KH_GEMM_W16 = true, KH_GEMM_Q16 = false, KH_GEMM_H16 = false;
+  constexpr PgCore CORE = PG_W16;
   const SgLaneAddr addr{lanes};
 #include "kh_gemm_body.h"
 }

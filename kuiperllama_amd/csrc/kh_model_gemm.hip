@@ -4,8 +4,9 @@
 // tile table; kh_model_seq.hip checks the call and drives it) and the wide sequence pass (kh_seq_gemm.h: a lane table
 // at full depth; what kh_model_seq_step_gemm and kh_model_generate_batch_gemm enqueue) - with their slabs, the launch
 // plan of one GEMM (pg_shape, pg_plan) and the operator-level entry of the MFMA slice attention.  Reads fp32 or int8
-// weights - and, under KH_FLAG_GEMM16, the 16-bit copy on the bf16 matrix cores (pg_gemm; the kernels are compiled in
-// kh_model_gemm_w16.hip).  The reference feeds the prompt one token per forward pass
+// weights - and, under the KH_FLAG_GEMM16* flags, the 16-bit copy or the int8 image on the bf16 matrix cores (pg_gemm,
+// kh_gemm16_launch.h; the kernels are compiled in kh_model_gemm_w16.hip, _h16.hip and _q16.hip, whose operator-level
+// entries share gemm16_op below).  The reference feeds the prompt one token per forward pass
 // (demo/main.cpp:20-22) and decodes one sequence per process (demo/main.cpp:16-50).
 // gfx950 only.
 #include <stdio.h>
@@ -15,6 +16,7 @@
 
 #include "kh_dispatch.h"
 #include "kh_gemm.h"
+#include "kh_gemm16_launch.h"
 #include "kh_model_internal.h"
 #include "kh_pattn.h"
 #include "kh_seq_gemm.h"
@@ -208,16 +210,16 @@ namespace {
 // The launch shape of one GEMM of a pass: the cost model, the KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE> hook, KH_PG_DEBUG.
 // epi: KH_PG_*; STORE (the classifier GEMM of the wide sequence pass) plans as a residual GEMM without a K split
 // across workgroups.
-// kcols: the columns of a K block of the loop that runs - 16 fp32, 64 int8, 32 on the 16-bit copy (kh_gemm_w16.h)
-// q16: the int8 loop on the bf16 matrix cores runs (kh_gemm_q16.h), or the fp16-format copy's (kh_gemm_h16.h, kcols 32):
-// no (2,8) tile - a hook that asks for it gets (2,4)
-PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K, int kcols, bool q16 = false) {
+// core: the K loop that runs (pg_core_of).  Its K block has 16 (fp32), 64 (int8, PG_Q16) or 32 columns (the 16-bit copy:
+// PG_W16, PG_H16); the loops on the copy keep the same 256 columns per wave as fp32's 16 blocks of 16 and never go solo
+// (pg_shape); PG_H16 and PG_Q16 have no (2,8) tile (kh_gemm16_launch.h) - a hook that asks for it gets (2,4)
+PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, int K, PgCore core) {
   const bool q = m->cfg.is_quant;
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
-  const bool w16 = kcols == 32;
-  // (min_blocks: the same 256 columns per wave as fp32's 16 blocks of 16)
-  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / kcols, q ? 4 : (w16 ? 8 : 16), q, EPI == KH_PG_RESID, !w16 && !q16,
-                           !q16);
+  const bool w16 = core == PG_W16 || core == PG_H16;
+  const bool tile28 = core != PG_H16 && core != PG_Q16;
+  PgShape sh = pg_shape(T, rows_total, r2_ok, nm, K / (q ? 64 : (w16 ? 32 : 16)), q ? 4 : (w16 ? 8 : 16), q,
+                        EPI == KH_PG_RESID, !w16 && tile28, tile28);
   {  // tuning hook: KH_PG_SHAPE_<QKV|RESID|SWIGLU|STORE>="R,NT,ks[,kz]" overrides the heuristic
     static const char* const names[4] = {"KH_PG_SHAPE_QKV", "KH_PG_SHAPE_RESID", "KH_PG_SHAPE_SWIGLU",
                                          "KH_PG_SHAPE_STORE"};
@@ -228,7 +230,7 @@ PgShape pg_plan(const kh_model* m, int EPI, int T, int rows_total, bool r2_ok, i
           (ks == 1 || ks == 2 || ks == 4 || ks == 8) && ks * nm * 64 <= KH_PG_WG_MAX(q) &&
           (kz == 1 || (EPI == KH_PG_RESID && (kz == 2 || kz == 4))))
       {
-        if (q16 && NT > 4) NT = 4;
+        if (!tile28 && NT > 4) NT = 4;
         const int slices = ((T + 15) / 16 + NT - 1) / NT;
         sh = PgShape{R, NT, ks, slices,
                      !q && !w16 && (T > 128 || R * NT >= 16) && pg_solo_on() &&
@@ -316,11 +318,9 @@ inline int pg_lane_groups(const PgPass& p) { return (p.n + KH_PF_BMAX - 1) / KH_
 // rope kernel has to follow); RESID: the number of K slices whose partial rows the next RMSNorm has to add (0 = the
 // epilogue added itself).  ok: cleared where the LDS opt-in of the shape is refused - that launch is skipped.
 // on16: the GEMM's launch class (KH_W16_*) and its matrices in the 16-bit copy.  Where the class runs on the bf16 matrix
-// cores (KH_FLAG_GEMM16: gemm16_runs) the same shape - planned in blocks of 32 columns - launches the _w16 stem
-// (kh_gemm_w16.h, compiled in kh_model_gemm_w16.hip) with the weight pointers swapped; everything else is untouched.
-// An int8 group-64 model under KH_FLAG_GEMM16_Q8 (gemm16_q8_runs) launches the _q16 stem on the image's own pointers.
-// A copy in its fp16 format under KH_FLAG_GEMM16_F16 (gemm16_f16_runs) launches the _h16 stem (kh_gemm_h16.h) in the shape
-// the _w16 path plans - blocks of 32 columns, a minimum K range of 8 blocks, never solo - without the (2,8) tile.
+// cores (pg_core_of: a KH_FLAG_GEMM16* flag adopted it) the shape - planned for that core's K blocks and tiles - launches
+// the core's stem through kh_gemm16_launch.h: PG_W16 and PG_H16 with the weight pointers swapped for the copy's, PG_Q16 on
+// the int8 image's own; everything else is untouched.
 struct PgOn16 {
   int cls;
   const void* w[3];
@@ -328,10 +328,8 @@ struct PgOn16 {
 template <int EPI>
 int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmArgs a, bool* ok, const PgOn16& on16) {
   const int nm = EPI == KH_PG_SWIGLU ? 2 : 1;
-  const bool w16 = gemm16_runs(m, on16.cls);
-  const bool q16 = gemm16_q8_runs(m, on16.cls);  // (an int8 model: never both)
-  const bool h16 = gemm16_f16_runs(m, on16.cls);  // (the copy is in its fp16 format: never with w16)
-  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K, w16 || h16 ? 32 : (m->cfg.is_quant ? 64 : 16), q16 || h16);
+  const PgCore core = pg_core_of(m, on16.cls);
+  PgShape sh = pg_plan(m, EPI, a.T, rows_total, r2_ok, a.K, core);
   if (p.lanes && sh.NT > 4) {  // a hook asked for the 128-token tile
     sh.NT = 4;
     sh.slices = ((a.T + 15) / 16 + 3) / 4;
@@ -343,29 +341,20 @@ int pg_gemm(kh_model* m, const PgPass& p, int rows_total, bool r2_ok, KhPgGemmAr
   size_t lds = pg_lds_bytes(wg / 64, sh.NT);
   if (sh.solo && lds < KH_PG_SOLO_LDS) lds = KH_PG_SOLO_LDS;  // one workgroup per CU at a time
   auto opt_in = [&](auto kern, dim3&) { return pg_lds_opt_in((const void*)kern, lds); };
-  const int tile = pg_tile(sh.R, sh.NT);  // one that is not listed runs as (2,2) where R is 2, else as (1,4)
+  // the tile among those the core's stems are compiled for: one that is not listed runs as (2,2) where R is 2, else as (1,4)
+  const bool on16m = core != PG_F32 && core != PG_Q8;
+  int tile = on16m ? pg16_tile(core, sh.R, sh.NT) : pg_tile(sh.R, sh.NT);
+  if (tile < 0) tile = sh.R == 2 ? 2 : 3;
   bool launched = false;
-  if (w16) {
-    for (int j = 0; j < 3; ++j)
-      if (on16.w[j]) a.w[j].w = on16.w[j];
-    const int t = tile >= 0 ? tile : (sh.R == 2 ? 2 : 3);
-    launched = pg_gemm_w16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
-                                  p.lanes);
-  } else if (h16) {
-    // the _w16 path's shape and weight pointers on the _h16 stem (kh_gemm_h16.h, compiled in kh_model_gemm_h16.hip)
-    for (int j = 0; j < 3; ++j)
-      if (on16.w[j]) a.w[j].w = on16.w[j];
-    const int t = tile >= 1 ? tile : (sh.R == 2 ? 2 : 3);
-    launched = pg_gemm_h16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
-                                  p.lanes);
-  } else if (q16) {
-    // the int8 image's own weight and scale pointers, on the _q16 stem (kh_gemm_q16.h, compiled in kh_model_gemm_q16.hip)
-    const int t = tile >= 1 ? tile : (sh.R == 2 ? 2 : 3);
-    launched = pg_gemm_q16_launch(PgW16Launch{EPI, kPgTiles[t][0], kPgTiles[t][1], grid, wg, lds}, m->stream, a, p.tiles,
-                                  p.lanes);
+  if (on16m) {
+    if (core != PG_Q16)  // the loop reads the 16-bit copy
+      for (int j = 0; j < 3; ++j)
+        if (on16.w[j]) a.w[j].w = on16.w[j];
+    launched = pg_gemm16_launch_of(core)(PgGemm16Launch{EPI, kPg16Tiles[tile][0], kPg16Tiles[tile][1], grid, wg, lds},
+                                         m->stream, a, p.tiles, p.lanes);
   } else {
     kh_pick_bool(m->cfg.is_quant, [&](auto Q) {
-      kh_pick(KhVals<0, 1, 2, 3>{}, tile >= 0 ? tile : (sh.R == 2 ? 2 : 3), [&](auto I) {
+      kh_pick(KhVals<0, 1, 2, 3>{}, tile, [&](auto I) {
         constexpr int R = kPgTiles[I][0], NT = kPgTiles[I][1];
         if (p.lanes) {
           if constexpr (NT <= 4)  // clamped above
@@ -671,6 +660,30 @@ int khm::seq_pass_enqueue_gemm(kh_model* m, const int32_t* slots, const int32_t*
   }
   if (!ok) return KH_ERR_UNSUPPORTED;  // a GEMM shape's LDS opt-in was refused
   return kh_launch_status();
+}
+
+// ---- the operator-level GEMM on the bf16 matrix cores (kh_gemm16_launch.h: what the call does and which shapes) --------
+int khm::gemm16_op(PgGemm16LaunchFn launch, int kcols, const float* x, const void* w, const float* scales, int gshift,
+                   float* y, int T, int M, int K, int ldy, hipStream_t s) {
+  const int R = M % 32 == 0 ? 2 : 1, NT = R == 2 ? (T > 32 ? 4 : 2) : 4;
+  const int slices = ((T + 15) / 16 + NT - 1) / NT, rows = slices * NT * 16, nb = K / kcols;
+  const int ks = nb >= 32 ? 4 : (nb >= 8 ? 2 : 1);
+  KhDev<float> xs;  // [rows][K], the padding rows zero
+  int rc;
+  if ((rc = xs.alloc((size_t)rows * K)) != KH_OK) return rc;
+  KH_CHECK_HIP(hipMemsetAsync(xs, 0, (size_t)rows * K * sizeof(float), s));
+  KH_CHECK_HIP(hipMemcpyAsync(xs, x, (size_t)T * K * sizeof(float), hipMemcpyDeviceToDevice, s));
+  KhPgGemmArgs a{};
+  a.w[0].w = w;
+  a.w[0].scales = scales;
+  a.B = xs; a.b_tiled = 0; a.tcap = rows; a.out = y;
+  a.rows0 = M; a.ldo = ldy; a.K = K; a.T = T; a.gshift = gshift;
+  const KhWideLanes none{};  // (the STORE epilogue reads no lane)
+  const bool ok = launch(PgGemm16Launch{KH_PG_STORE, R, NT, dim3(M / (16 * R), slices, 1), ks * 64, pg_lds_bytes(ks, NT)}, s, a,
+                         nullptr, &none);
+  rc = ok ? kh_launch_status() : KH_ERR_UNSUPPORTED;
+  const hipError_t e = hipStreamSynchronize(s);  // xs is freed on return
+  return rc != KH_OK ? rc : (int)e;
 }
 
 // Operator-level entry of the MFMA slice attention (kh_pattn.h): the multi-token form of MHAKernel.

@@ -9,11 +9,10 @@
 //                         kernels on the 16-bit copy (kh_w16_pass.h)
 //   kh_model_gemm.hip     what runs on the GEMM slabs (kh_gemm.h, kh_pattn.h, kh_seq_prefill.h, kh_seq_gemm.h kernels):
 //                         the MFMA prompt prefill, its form into sequence slots and the wide sequence pass
-//   kh_model_gemm_w16.hip the same GEMMs on the bf16 matrix cores from the 16-bit copy (KH_FLAG_GEMM16; kh_gemm_w16.h kernels)
-//   kh_model_gemm_q16.hip the GEMMs of an int8 group-64 model on the bf16 matrix cores from the int8 image (KH_FLAG_GEMM16_Q8;
-//                         kh_gemm_q16.h kernels)
-//   kh_model_gemm_h16.hip the GEMMs of an fp16-origin fp32 model on the bf16 matrix cores from the fp16-format 16-bit copy
-//                         (KH_FLAG_GEMM16_F16; kh_gemm_h16.h kernels)
+//   kh_model_gemm_w16.hip the same GEMMs on the bf16 matrix cores, one launch text (kh_gemm16_launch.h) instantiated per
+//   kh_model_gemm_q16.hip core beside its kernels and its operator-level entry: from the 16-bit copy (KH_FLAG_GEMM16;
+//   kh_model_gemm_h16.hip kh_gemm_w16.h), from the int8 image of a group-64 model (KH_FLAG_GEMM16_Q8; kh_gemm_q16.h, with
+//                         the flag's configuration) and from the copy in fp16 format (KH_FLAG_GEMM16_F16; kh_gemm_h16.h)
 //   kh_model_wide_attn.hip the wide pass's attention in one launch per layer (KH_FLAG_WIDE_ATTN; kh_seq_attn_wide.h kernels,
 //                         kh_wide_attn_plan.h) and its operator-level entry
 //   kh_model_seq.hip      sequence slots of the K/V cache, kh_model_seq_step, kh_model_generate_batch and their _ex
@@ -24,7 +23,8 @@
 //                         weight copies (one check for W16 and Q4)
 //   kh_model_w16.hip      the 16-bit copy of a bf16-exact fp32 model's matrices, and what every weight copy shares: its
 //                         bytes, its build, its release and the routing of the decode GEMV launches that read a copy
-//                         (kh_copy_launch.h: one launch text; the _w16 kernels of kh_w16.h are instantiated here)
+//                         (kh_copy_launch.h: one launch text; the _w16 kernels of kh_w16.h are instantiated here); the
+//                         configuration of the two GEMM-pass flags that read the copy (KH_FLAG_GEMM16, KH_FLAG_GEMM16_F16)
 //   kh_model_q4.hip       the 4-bit copy of a 4-bit-exact int8 model's matrices (the same launch text; the kh_q4.h
 //                         kernels are instantiated here)
 //   kh_model_q4_pass.hip  ... and its B-token passes (kh_pf_launch.h's launch text; the _q4 kernels of kh_q4_pass.h)
@@ -378,13 +378,6 @@ struct kh_model {
     int format = 0;         // of the live copy: KH_W16_BF16 (also: no copy) or KH_W16_F16 (kh_w16.h)
     int first_inexact_f16 = -1;  // as first_inexact, for the fp16 format (-1: not tried, or every tensor passed)
     int pass_classes = 0;   // classes whose B-token pass reads the copy too (kh_w16_pass.h; hook KH_W16_PASS): a subset of classes
-    // KH_FLAG_GEMM16 / hook KH_GEMM16 (kh_gemm_w16.h): classes whose GEMMs of the GEMM pass (kh_model_gemm.hip:
-    // pg_gemm) run on the bf16 matrix cores from the copy - a live bf16-format copy, the GEMM prefill's geometry, K a
-    // multiple of 32 and the adoption mask (plan_gemm16, hook KH_GEMM16_CLASSES); 0 wherever the flag is inert, and
-    // gemm_reason says why (KH_GEMM16_*: kh_model_gemm16_info)
-    int gemm_classes = 0;
-    int gemm_reason = 0;
-    int gemm_plan = 0;      // plan_gemm16's mask for the geometry, whatever the hook says (0 unless the flag is live)
   };
   W16 w16;
   // Q4 (kh_q4.h, kh_model_q4.hip; KH_FLAG_Q4 / hook KH_Q4): the low nibbles of every int8 matrix value of a 4-bit-exact
@@ -398,27 +391,21 @@ struct kh_model {
     int pass_classes = 0;
   };
   Q4 q4;
-  // KH_FLAG_GEMM16_Q8 / hook KH_GEMM16_Q8 (kh_gemm_q16.h, kh_model_gemm_q16.hip): classes whose GEMMs of the
-  // GEMM pass (kh_model_gemm.hip: pg_gemm) run on the bf16 matrix cores from the int8 image itself - an int8 group-64
-  // model on the GEMM prefill's geometry and the adoption mask (plan_gemm16_q8, hook KH_GEMM16_Q8_CLASSES); 0 wherever
-  // the flag is inert, and reason says why (KH_GEMM16_Q8_*: kh_model_gemm16_q8_info).  No copy, no memory.
-  struct Gemm16Q8 {
+  // The GEMM pass (kh_model_gemm.hip: pg_gemm) on the bf16 matrix cores, per flag: classes whose GEMMs run there; 0
+  // wherever the flag is inert, and reason says why (the flag's KH_GEMM16*_ codes: its kh_model_gemm16*_info).
+  struct Gemm16 {
     int classes = 0;
     int reason = 0;
-    int plan = 0;           // plan_gemm16_q8's mask for the geometry, whatever the hook says (0 unless the flag is live)
+    int plan = 0;           // the flag's plan_gemm16* mask for the geometry, whatever the hook says (0 unless the flag is live)
   };
-  Gemm16Q8 g16q8;
-  // KH_FLAG_GEMM16_F16 / hook KH_GEMM16_F16 (kh_gemm_h16.h, kh_model_gemm_h16.hip): classes whose GEMMs of the
-  // GEMM pass (kh_model_gemm.hip: pg_gemm) run on the bf16 matrix cores from the 16-bit copy in its fp16 format - a live
-  // fp16-format copy (w16), the GEMM prefill's geometry, K a multiple of 32 and the adoption mask (plan_gemm16_f16, hook
-  // KH_GEMM16_F16_CLASSES); 0 wherever the flag is inert, and reason says why (KH_GEMM16_F16_*: kh_model_gemm16_f16_info).
-  // The copy is w16's: a copy its self-check gives up (w16.state -2) takes these launches with it (gemm16_f16_runs).
-  struct Gemm16F16 {
-    int classes = 0;
-    int reason = 0;
-    int plan = 0;           // plan_gemm16_f16's mask for the geometry, whatever the hook says (0 unless the flag is live)
-  };
-  Gemm16F16 g16f16;
+  // KH_FLAG_GEMM16 / hook KH_GEMM16 (kh_gemm_w16.h): from the 16-bit copy (w16) - a live bf16-format copy, the
+  // GEMM prefill's geometry, K a multiple of 32 and the adoption mask (plan_gemm16, hook KH_GEMM16_CLASSES).
+  // KH_FLAG_GEMM16_F16 / hook KH_GEMM16_F16 (kh_gemm_h16.h): the same on a live fp16-format copy
+  // (plan_gemm16_f16, hook KH_GEMM16_F16_CLASSES).  The copy is w16's: one its self-check gives up (w16.state -2) takes
+  // these launches with it (pg_core_of, kh_gemm16_launch.h) and the info calls answer KH_GEMM16*_SELFCHECK.
+  // KH_FLAG_GEMM16_Q8 / hook KH_GEMM16_Q8 (kh_gemm_q16.h): from the int8 image itself - an int8 group-64 model
+  // on the GEMM prefill's geometry and the adoption mask (plan_gemm16_q8, hook KH_GEMM16_Q8_CLASSES).  No copy, no memory.
+  Gemm16 g16, g16f16, g16q8;
   // KH_FLAG_WIDE_ATTN / hook KH_WIDE_ATTN (kh_seq_attn_wide.h, kh_model_wide_attn.hip): the wide pass's
   // attention as k_sg_attn + k_sg_attn_merge per layer instead of the grouped launches; off wherever the flag is inert,
   // and reason says why (KH_WIDE_ATTN_*: kh_model_wide_attn_info).  ws: the partials, made by the first wide call under
@@ -468,21 +455,14 @@ static inline bool q4_runs(const kh_model* m, int cls) { return (m->q4.classes &
 static inline KhOn runs_on(const kh_model* m, int cls) {
   return q4_runs(m, cls) ? KH_ON_Q4 : (w16_runs(m, cls) ? KH_ON_W16 : KH_ON_IMAGE);
 }
-// the GEMM pass of the class on the bf16 matrix cores (kh_model_gemm.hip: pg_gemm)
-static inline bool gemm16_runs(const kh_model* m, int cls) { return m->w16.state == 1 && (m->w16.gemm_classes & cls) != 0; }
 // why KH_FLAG_GEMM16 does nothing on a model (kh_model_gemm16_info, slot 2); KH_GEMM16_ON: it does something
 enum { KH_GEMM16_ON = 0, KH_GEMM16_NO_FLAG = 1, KH_GEMM16_NO_W16 = 2, KH_GEMM16_QUANT = 3, KH_GEMM16_INEXACT = 4,
        KH_GEMM16_FP16_COPY = 5, KH_GEMM16_GEOMETRY = 6, KH_GEMM16_NO_CLASS = 7, KH_GEMM16_SELFCHECK = 8 };
-// the GEMM pass of the class on the bf16 matrix cores from the int8 image (KH_FLAG_GEMM16_Q8; kh_model_gemm.hip: pg_gemm)
-static inline bool gemm16_q8_runs(const kh_model* m, int cls) { return (m->g16q8.classes & cls) != 0; }
 // why KH_FLAG_GEMM16_Q8 does nothing on a model (kh_model_gemm16_q8_info, slot 2); KH_GEMM16_Q8_ON: it does something
 enum { KH_GEMM16_Q8_ON = 0, KH_GEMM16_Q8_NO_FLAG = 1, KH_GEMM16_Q8_FP32 = 2, KH_GEMM16_Q8_GROUP = 3,
        KH_GEMM16_Q8_GEOMETRY = 4, KH_GEMM16_Q8_NO_CLASS = 5 };
-// the GEMM pass of the class on the bf16 matrix cores from the fp16-format copy (KH_FLAG_GEMM16_F16; kh_model_gemm.hip: pg_gemm)
-static inline bool gemm16_f16_runs(const kh_model* m, int cls) {
-  return m->w16.state == 1 && m->w16.format == 1 /* KH_W16_F16 */ && (m->g16f16.classes & cls) != 0;
-}
-// why KH_FLAG_GEMM16_F16 does nothing on a model (kh_model_gemm16_f16_info, slot 2); KH_GEMM16_F16_ON: it does something
+// why KH_FLAG_GEMM16_F16 does nothing on a model (kh_model_gemm16_f16_info, slot 2); KH_GEMM16_F16_ON: it does something.
+// Code for code KH_GEMM16_*'s: the two flags are configured by one function (kh_model_w16.hip: gemm16_copy_configure)
 enum { KH_GEMM16_F16_ON = 0, KH_GEMM16_F16_NO_FLAG = 1, KH_GEMM16_F16_NO_W16_F16 = 2, KH_GEMM16_F16_QUANT = 3,
        KH_GEMM16_F16_INEXACT = 4, KH_GEMM16_F16_BF16_COPY = 5, KH_GEMM16_F16_GEOMETRY = 6, KH_GEMM16_F16_NO_CLASS = 7,
        KH_GEMM16_F16_SELFCHECK = 8 };
@@ -616,6 +596,11 @@ int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, in
 // adoption mask among the classes whose contraction length is a multiple of 32; 0 for int8 and for geometries the
 // GEMM prefill does not run on
 int plan_gemm16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size);
+// the same under KH_FLAG_GEMM16_F16 (the fp16-format copy): 0 as well where the adoption rule keeps no class
+int plan_gemm16_f16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size);
+// the classes a GEMM16* flag acts on: `plan`, unless the flag's hook KH_GEMM16*_CLASSES=<number> is set (hook_value:
+// its dbg(), strtol base 0) and replaces it - within `allowed`
+int gemm16_hook_mask(const char* hook_value, int plan, int allowed);
 // the copy, once the weights are resident and ahead of the self-tests (no-op unless KH_FLAG_W16 / KH_W16=1 asks)
 int w16_create(kh_model* m);
 void w16_release(kh_model* m);  // frees the copy; no class runs on it afterwards
@@ -711,33 +696,11 @@ KhAttnArgs attn_slice_args(kh_model* m, int l, const float* q, float* out, void*
 bool pg_supported(const kh_model* m);  // MFMA GEMM path
 // the >48 KiB dynamic-LDS opt-in of a GEMM-pass kernel, once per (device, kernel); false: refused
 bool pg_lds_opt_in(const void* kern, size_t lds);
-// ---- kh_model_gemm_w16.hip ------------------------------------------------------------------
-struct PgW16Launch {  // one GEMM of a pass as pg_gemm planned it, on the k_*_gemm_w16 kernels (kh_gemm_w16.h)
-  int epi, R, NT;     // KH_PG_*; a listed (R, NT) register tile
-  dim3 grid;
-  int wg;
-  size_t lds;
-};
-// a: the image launch's arguments with KhLin::w of every matrix pointing into the 16-bit copy.  tiles / lanes: the
-// token addressing (both null: a run).  false: the LDS opt-in was refused (nothing launched)
-bool pg_gemm_w16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemmArgs& a, const KhRgTiles* tiles,
-                        const KhWideLanes* lanes);
-// ---- kh_model_gemm_q16.hip ------------------------------------------------------------------
-// the same launch on the k_*_gemm_q16 kernels (kh_gemm_q16.h): a is the int8 image launch's own.  The stem has no (2,8)
-// register tile: the caller plans without it
-bool pg_gemm_q16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemmArgs& a, const KhRgTiles* tiles,
-                        const KhWideLanes* lanes);
-// classes that run on it by default for a geometry (0: not an int8 group-64 model the GEMM prefill takes)
+// ---- kh_model_gemm_w16.hip, kh_model_gemm_q16.hip, kh_model_gemm_h16.hip: kh_gemm16_launch.h ------------------
+// classes that run on the int8 image's bf16-matrix-core stem by default for a geometry (0: not an int8 group-64 model the
+// GEMM prefill takes)
 int plan_gemm16_q8(bool quant, int group_size, int dim, int hidden_dim, int kv_dim, int vocab_size);
 void gemm16_q8_configure(kh_model* m);  // at creation
-// ---- kh_model_gemm_h16.hip ------------------------------------------------------------------
-// the same launch on the k_*_gemm_h16 kernels (kh_gemm_h16.h): a as for pg_gemm_w16_launch, the copy in its fp16 format.
-// The stem has no (2,8) register tile: the caller plans without it
-bool pg_gemm_h16_launch(const PgW16Launch& L, hipStream_t stream, const KhPgGemmArgs& a, const KhRgTiles* tiles,
-                        const KhWideLanes* lanes);
-// classes that run on it by default for a geometry (0: int8, dims the GEMM prefill does not take, or none adopted)
-int plan_gemm16_f16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size);
-void gemm16_f16_configure(kh_model* m);  // at creation, behind w16_create
 // kh_model_prefill_gemm without the token record (hist_write); prefill_gemm_prepare: its slabs, made by the call
 // itself or ahead of it by whoever times it
 // d_score_target (device, [n]: the token that followed token i, -1 behind the last): every pass runs at full depth and

@@ -675,10 +675,9 @@ static int create_from_device_weights_impl(const int32_t* h_header, const void* 
   m->arena_bytes = weight_nbytes;
   m->cfg.weight_bytes = (int64_t)expected_weight_bytes(m->cfg);
   rc = finish_create(m);
-  if (rc == KH_OK) rc = w16_create(m);  // KH_FLAG_W16: the 16-bit copy of a bf16-exact model's matrices
+  if (rc == KH_OK) rc = w16_create(m);  // KH_FLAG_W16: the 16-bit copy of a bf16-exact model's matrices (and KH_FLAG_GEMM16 / _F16 on it)
   if (rc == KH_OK) rc = q4_create(m);   // KH_FLAG_Q4: the 4-bit copy of a 4-bit-exact int8 model's matrices
   if (rc == KH_OK) gemm16_q8_configure(m);  // KH_FLAG_GEMM16_Q8: the GEMM passes of an int8 group-64 model on bf16 MFMAs
-  if (rc == KH_OK) gemm16_f16_configure(m);  // KH_FLAG_GEMM16_F16: the GEMM passes on the fp16-format copy on bf16 MFMAs
   if (rc == KH_OK) wide_attn_configure(m);  // KH_FLAG_WIDE_ATTN: the wide pass's attention in one launch per layer
   if (rc == KH_OK) rc = cls_screen_create(m);
   if (rc == KH_OK) rc = run_selftests(m);  // the weights are resident: ring kernels / split merge against their fallbacks
@@ -760,7 +759,6 @@ static int create_from_host_image_impl(const void* h_image, size_t nbytes, const
   if (rc == KH_OK) rc = w16_create(m);  // the arena is resident: the 16-bit copy of a bf16-exact model's matrices (KH_FLAG_W16)
   if (rc == KH_OK) rc = q4_create(m);  // ... or the 4-bit copy of a 4-bit-exact int8 model's (KH_FLAG_Q4)
   if (rc == KH_OK) gemm16_q8_configure(m);  // (KH_FLAG_GEMM16_Q8)
-  if (rc == KH_OK) gemm16_f16_configure(m);  // (KH_FLAG_GEMM16_F16)
   if (rc == KH_OK) wide_attn_configure(m);  // (KH_FLAG_WIDE_ATTN)
   pc.lap("W16 / Q4 copy");
   if (rc == KH_OK) rc = cls_screen_create(m);  // the arena is resident: bf16 copy of the classifier (fp32 models)

@@ -112,8 +112,6 @@ int plan_w16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size, in
 void w16_release(kh_model* m) {
   copy_release(m->w16);
   m->w16.pass_classes = 0;
-  if (m->w16.gemm_classes) m->w16.gemm_reason = KH_GEMM16_SELFCHECK;  // a live copy given up: the self-check's verdict
-  m->w16.gemm_classes = 0;
   m->w16.format = KH_W16_BF16;
 }
 
@@ -126,54 +124,90 @@ static int w16_pass_mask() {
   return (int)strtol(hook, nullptr, 0) & KH_W16_ALL;
 }
 
-// ---- KH_FLAG_GEMM16: the GEMM pass on the bf16 matrix cores (kh_gemm_w16.h) ------------------------------------
-// Classes that run their GEMMs of the GEMM pass on the copy unless KH_GEMM16_CLASSES says otherwise: 3.1e's adoption
-// rule - the class's time with the flag on lies below its flag-off time by more than the run-to-run range, at 512
+// ---- KH_FLAG_GEMM16, KH_FLAG_GEMM16_F16: the GEMM pass on the bf16 matrix cores from the copy (kh_gemm_w16.h, kh_gemm_h16.h)
+// Classes that run their GEMMs of the GEMM pass on the bf16-format copy unless KH_GEMM16_CLASSES says otherwise: 3.1e's
+// adoption rule - the class's time with the flag on lies below its flag-off time by more than the run-to-run range, at 512
 // tokens, on Llama-3.2-1B and on Llama-2-7B geometry (profiles/gemm16_ab.txt: qkv -2.4 / -8.1 %, wo -1.2 / -2.4 %,
 // ffn13 -14.3 / -13.1 %, w2 -4.9 / -6.0 % of the whole 512-token prefill; cls -3.2 % of a 64-lane batch on the 1B
 // geometry but -0.1 %, inside the range, on the 7B one: left out) - among the classes whose contraction length K is a multiple of the
 // 32-column block: qkv, wo, ffn13 and cls contract over dim, w2 over hidden_dim.
 enum { KH_GEMM16_DEFAULT = KH_W16_QKV | KH_W16_WO | KH_W16_FFN13 | KH_W16_W2 };
+// ... and on the fp16-format copy unless KH_GEMM16_F16_CLASSES says otherwise: the same rule, on both geometries at 512
+// tokens (profiles/gemm16_f16_ab.txt).  On the 1B geometry qkv, wo and w2 stay inside the range and ffn13 loses 18 %; cls
+// gains 2.7 % of a 64-sequence batch there but the 7B geometry is not measured.  The rule keeps nothing:
+// the flag acts only through the hook.
+enum { KH_GEMM16_F16_DEFAULT = 0 };
 static int gemm16_k32_classes(int dim, int hidden_dim) {
   return (dim % 32 == 0 ? KH_W16_QKV | KH_W16_WO | KH_W16_FFN13 | KH_W16_CLS : 0) | (hidden_dim % 32 == 0 ? KH_W16_W2 : 0);
 }
-int plan_gemm16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size) {
+static int plan_gemm16_copy(int adopted, bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size) {
   if (quant || dim <= 0 || hidden_dim <= 0 || kv_dim <= 0 || vocab_size <= 0) return 0;
   if (dim % 16 || hidden_dim % 16 || kv_dim % 16) return 0;  // pg_supported's granules of an fp32 model
-  return KH_GEMM16_DEFAULT & gemm16_k32_classes(dim, hidden_dim);
+  return adopted & gemm16_k32_classes(dim, hidden_dim);
 }
-// Read at creation, behind the copy's build.  Hooks: KH_GEMM16=1 / 0 overrides the flag; KH_GEMM16_CLASSES=<number>
-// (strtol, base 0) replaces the adoption mask - the K % 32 rule still holds.
-static void gemm16_configure(kh_model* m, bool w16_wanted) {
+int plan_gemm16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size) {
+  return plan_gemm16_copy(KH_GEMM16_DEFAULT, quant, dim, hidden_dim, kv_dim, vocab_size);
+}
+int plan_gemm16_f16(bool quant, int dim, int hidden_dim, int kv_dim, int vocab_size) {
+  return plan_gemm16_copy(KH_GEMM16_F16_DEFAULT, quant, dim, hidden_dim, kv_dim, vocab_size);
+}
+int gemm16_hook_mask(const char* hook_value, int plan, int allowed) {
+  return hook_value ? (int)strtol(hook_value, nullptr, 0) & allowed : plan;
+}
+// One of the two flags, read at creation behind the copy's build.  format: the copy's the flag runs on; hook = 1 / 0
+// overrides the flag; hook_classes replaces the adoption mask `adopted` (gemm16_hook_mask) - the K % 32 rule still holds;
+// copy_wanted: the flag or hook that asks for a copy in that format was set.  The reasons are KH_GEMM16_*, which
+// KH_GEMM16_F16_* repeat code for code (FP16_COPY / BF16_COPY: the live copy has the other format).
+static_assert(KH_GEMM16_F16_NO_FLAG == KH_GEMM16_NO_FLAG && KH_GEMM16_F16_NO_W16_F16 == KH_GEMM16_NO_W16 &&
+                  KH_GEMM16_F16_QUANT == KH_GEMM16_QUANT && KH_GEMM16_F16_INEXACT == KH_GEMM16_INEXACT &&
+                  KH_GEMM16_F16_BF16_COPY == KH_GEMM16_FP16_COPY && KH_GEMM16_F16_GEOMETRY == KH_GEMM16_GEOMETRY &&
+                  KH_GEMM16_F16_NO_CLASS == KH_GEMM16_NO_CLASS && KH_GEMM16_F16_SELFCHECK == KH_GEMM16_SELFCHECK &&
+                  KH_GEMM16_F16_ON == KH_GEMM16_ON,
+              "one configure, one info");
+static void gemm16_copy_configure(kh_model* m, kh_model::Gemm16& g, int format, unsigned flag, const char* hook_name,
+                                  const char* hook_classes, int adopted, bool copy_wanted) {
   const kh_config& c = m->cfg;
-  kh_model::W16& w = m->w16;
-  w.gemm_classes = w.gemm_plan = 0;
-  const char* hook = dbg("KH_GEMM16");
-  const bool want = hook ? hook[0] == '1' : (m->opts.flags & KH_FLAG_GEMM16) != 0;
-  if (!want) { w.gemm_reason = KH_GEMM16_NO_FLAG; return; }
-  if (c.is_quant) { w.gemm_reason = KH_GEMM16_QUANT; return; }
-  if (!w16_wanted) { w.gemm_reason = KH_GEMM16_NO_W16; return; }
-  if (w.state != 1) { w.gemm_reason = w.state == -1 ? KH_GEMM16_INEXACT : KH_GEMM16_GEOMETRY; return; }
-  if (w.format != KH_W16_BF16) { w.gemm_reason = KH_GEMM16_FP16_COPY; return; }
-  if (!pg_supported(m)) { w.gemm_reason = KH_GEMM16_GEOMETRY; return; }
-  w.gemm_plan = plan_gemm16(false, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size);
-  int mask = w.gemm_plan;
-  if (const char* cl = dbg("KH_GEMM16_CLASSES"))
-    mask = (int)strtol(cl, nullptr, 0) & gemm16_k32_classes(c.dim, c.hidden_dim);
-  w.gemm_classes = mask & w.classes;
-  w.gemm_reason = w.gemm_classes ? KH_GEMM16_ON : KH_GEMM16_NO_CLASS;
+  const kh_model::W16& w = m->w16;
+  g = kh_model::Gemm16();
+  const char* hook = dbg(hook_name);
+  const bool want = hook ? hook[0] == '1' : (m->opts.flags & flag) != 0;
+  if (!want) { g.reason = KH_GEMM16_NO_FLAG; return; }
+  if (c.is_quant) { g.reason = KH_GEMM16_QUANT; return; }
+  if (!copy_wanted) { g.reason = KH_GEMM16_NO_W16; return; }
+  if (w.state != 1) { g.reason = w.state == -1 ? KH_GEMM16_INEXACT : KH_GEMM16_GEOMETRY; return; }
+  if (w.format != format) { g.reason = KH_GEMM16_FP16_COPY; return; }
+  if (!pg_supported(m)) { g.reason = KH_GEMM16_GEOMETRY; return; }
+  g.plan = plan_gemm16_copy(adopted, false, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size);
+  g.classes = gemm16_hook_mask(dbg(hook_classes), g.plan, gemm16_k32_classes(c.dim, c.hidden_dim)) & w.classes;
+  g.reason = g.classes ? KH_GEMM16_ON : KH_GEMM16_NO_CLASS;
+}
+// kh_model_gemm16_info / kh_model_gemm16_f16_info.  A copy its self-check gave up (w16.state -2) is no longer live: the
+// classes the flag had adopted say so.
+static int gemm16_copy_info(const kh_model* m, kh_model::Gemm16 kh_model::*flag, int format, int64_t* out) {
+  if (!m || !out) return KH_ERR_INVALID_ARG;
+  memset(out, 0, 8 * sizeof(int64_t));
+  const kh_model::Gemm16& g = m->*flag;
+  const bool on = m->w16.state == 1 && m->w16.format == format && g.classes != 0;
+  out[0] = on;
+  out[1] = on ? g.classes : 0;
+  out[2] = on ? KH_GEMM16_ON : (g.classes ? KH_GEMM16_SELFCHECK : g.reason);
+  out[3] = g.plan;
+  return KH_OK;
 }
 
 // The copy in the first format the image is exact in: bf16 (KH_FLAG_W16 or KH_FLAG_W16_F16), else fp16 (only
 // KH_FLAG_W16_F16; into the same arena - plan_w16's layout holds for both), else none.  All or nothing per format.
-static int w16_create_copy(kh_model* m, bool* wanted);
+static int w16_create_copy(kh_model* m, bool* wanted, bool* wanted_f16);
 int w16_create(kh_model* m) {
-  bool wanted = false;
-  const int rc = w16_create_copy(m, &wanted);
-  if (rc == KH_OK) gemm16_configure(m, wanted);
+  bool wanted = false, wanted_f16 = false;
+  const int rc = w16_create_copy(m, &wanted, &wanted_f16);
+  if (rc != KH_OK) return rc;
+  gemm16_copy_configure(m, m->g16, KH_W16_BF16, KH_FLAG_GEMM16, "KH_GEMM16", "KH_GEMM16_CLASSES", KH_GEMM16_DEFAULT, wanted);
+  gemm16_copy_configure(m, m->g16f16, KH_W16_F16, KH_FLAG_GEMM16_F16, "KH_GEMM16_F16", "KH_GEMM16_F16_CLASSES",
+                        KH_GEMM16_F16_DEFAULT, wanted_f16);
   return rc;
 }
-static int w16_create_copy(kh_model* m, bool* wanted) {
+static int w16_create_copy(kh_model* m, bool* wanted, bool* wanted_f16) {
   const kh_config& c = m->cfg;
   kh_model::W16& w = m->w16;
   w = kh_model::W16();
@@ -182,6 +216,7 @@ static int w16_create_copy(kh_model* m, bool* wanted) {
   const bool try_f16 = hook_f16 ? hook_f16[0] == '1' : (m->opts.flags & KH_FLAG_W16_F16) != 0;
   const bool want = hook ? hook[0] == '1' : (m->opts.flags & KH_FLAG_W16) != 0 || try_f16;
   *wanted = want;
+  *wanted_f16 = try_f16;
   if (!want) return KH_OK;
   size_t bytes = 0;
   const int classes = plan_w16(c.is_quant != 0, c.dim, c.hidden_dim, c.kv_dim, c.vocab_size, c.layer_num, &bytes);
@@ -269,13 +304,18 @@ extern "C" int kh_plan_gemm16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, i
   return KH_OK;
 }
 
-extern "C" int kh_model_gemm16_info(kh_model* m, int64_t* out) {
-  if (!m || !out) return KH_ERR_INVALID_ARG;
-  memset(out, 0, 8 * sizeof(int64_t));
-  const bool on = m->w16.state == 1 && m->w16.gemm_classes != 0;
-  out[0] = on;
-  out[1] = on ? m->w16.gemm_classes : 0;
-  out[2] = on ? KH_GEMM16_ON : m->w16.gemm_reason;
-  out[3] = m->w16.gemm_plan;
+extern "C" int kh_model_gemm16_info(kh_model* m, int64_t* out) { return gemm16_copy_info(m, &kh_model::g16, KH_W16_BF16, out); }
+
+// out2 = {KH_W16_* bits of the launch classes whose GEMM-pass GEMMs run on the bf16 matrix cores under
+// KH_FLAG_GEMM16_F16 by default (0: not applicable, or the adoption rule keeps none), the columns of a K block}
+extern "C" int kh_plan_gemm16_f16(int32_t dim, int32_t hidden_dim, int32_t kv_dim, int32_t vocab_size, int32_t is_quant,
+                                  int64_t* out2) {
+  if (!out2 || dim <= 0 || hidden_dim <= 0 || kv_dim <= 0 || vocab_size <= 0) return KH_ERR_INVALID_ARG;
+  out2[0] = plan_gemm16_f16(is_quant != 0, dim, hidden_dim, kv_dim, vocab_size);
+  out2[1] = 32;
   return KH_OK;
+}
+
+extern "C" int kh_model_gemm16_f16_info(kh_model* m, int64_t* out) {
+  return gemm16_copy_info(m, &kh_model::g16f16, KH_W16_F16, out);
 }

@@ -403,39 +403,32 @@ class KuiperModel:
         _ffi.check(_ffi.lib().kh_model_q4_info(self._h, out), "kh_model_q4_info")
         return {"classes": [n for i, n in enumerate(_ffi.KH_Q4_CLASSES) if out[5] >> i & 1]}
 
+    def _gemm16_info(self, entry: str, reasons) -> dict:
+        out = (_ffi._i64 * 8)()
+        _ffi.check(getattr(_ffi.lib(), entry)(self._h, out), entry)
+        return {"on": bool(out[0]),
+                "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[1] >> i & 1],
+                "reason": reasons[out[2]],
+                "plan": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1]}
+
     def gemm16_info(self) -> dict:
         """_ffi.KH_FLAG_GEMM16 on this model (kh_model_gemm16_info): {"on": some launch class of the GEMM pass runs on
         the bf16 matrix cores, "classes": those classes, "reason": why the flag does nothing (one of
         _ffi.KH_GEMM16_REASONS; "on" where it does), "plan": the classes kh_plan_gemm16 adopts for the geometry}."""
-        out = (_ffi._i64 * 8)()
-        _ffi.check(_ffi.lib().kh_model_gemm16_info(self._h, out), "kh_model_gemm16_info")
-        return {"on": bool(out[0]),
-                "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[1] >> i & 1],
-                "reason": _ffi.KH_GEMM16_REASONS[out[2]],
-                "plan": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1]}
+        return self._gemm16_info("kh_model_gemm16_info", _ffi.KH_GEMM16_REASONS)
 
     def gemm16_q8_info(self) -> dict:
         """_ffi.KH_FLAG_GEMM16_Q8 on this model (kh_model_gemm16_q8_info): {"on": some launch class of the GEMM pass runs
         on the bf16 matrix cores from the int8 image, "classes": those classes, "reason": why the flag does nothing (one
         of _ffi.KH_GEMM16_Q8_REASONS; "on" where it does), "plan": the classes kh_plan_gemm16_q8 adopts for the geometry}."""
-        out = (_ffi._i64 * 8)()
-        _ffi.check(_ffi.lib().kh_model_gemm16_q8_info(self._h, out), "kh_model_gemm16_q8_info")
-        return {"on": bool(out[0]),
-                "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[1] >> i & 1],
-                "reason": _ffi.KH_GEMM16_Q8_REASONS[out[2]],
-                "plan": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1]}
+        return self._gemm16_info("kh_model_gemm16_q8_info", _ffi.KH_GEMM16_Q8_REASONS)
 
     def gemm16_f16_info(self) -> dict:
         """_ffi.KH_FLAG_GEMM16_F16 on this model (kh_model_gemm16_f16_info): {"on": some launch class of the GEMM pass
         runs on the bf16 matrix cores from the fp16-format copy, "classes": those classes, "reason": why the flag does
         nothing (one of _ffi.KH_GEMM16_F16_REASONS; "on" where it does), "plan": the classes kh_plan_gemm16_f16 adopts for
         the geometry}."""
-        out = (_ffi._i64 * 8)()
-        _ffi.check(_ffi.lib().kh_model_gemm16_f16_info(self._h, out), "kh_model_gemm16_f16_info")
-        return {"on": bool(out[0]),
-                "classes": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[1] >> i & 1],
-                "reason": _ffi.KH_GEMM16_F16_REASONS[out[2]],
-                "plan": [n for i, n in enumerate(_ffi.KH_W16_CLASSES) if out[3] >> i & 1]}
+        return self._gemm16_info("kh_model_gemm16_f16_info", _ffi.KH_GEMM16_F16_REASONS)
 
     def wide_attn_info(self) -> dict:
         """_ffi.KH_FLAG_WIDE_ATTN on this model (kh_model_wide_attn_info): {"on": the wide pass launches k_sg_attn and

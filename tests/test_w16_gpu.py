@@ -217,10 +217,12 @@ def test_generate_loops_match(gpu, oracle, tied_img):
 def test_selfcheck_failure_falls_back_to_fp32(gpu, tied_img):
     m0 = _model(tied_img, TIED)
     with wc.hook("KH_SELFTEST_FAIL", "w16"):
-        m1 = _model(tied_img, TIED, W16)
+        m1 = _model(tied_img, TIED, W16 | _ffi.KH_FLAG_GEMM16)
     try:
         info = m1.w16_info()
         assert info["state"] == -2 and info["bytes"] == 0 and info["classes"] == [], info
+        g16 = m1.gemm16_info()  # the GEMM pass loses the copy with decode, and says why
+        assert not g16["on"] and g16["classes"] == [] and g16["reason"] == "self-check failed", g16
         log0, lg0 = _logged_step(m0)
         log1, lg1 = _logged_step(m1)
         assert log0 == log1 == TIED_STEP_FP32, sorted(log1)

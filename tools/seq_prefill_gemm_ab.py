@@ -4,7 +4,7 @@ weights, on the matrix cores) against the parent commit's seq_prefill loop.  Out
 
     python -m kuiperllama_amd.build --variant-at <parent commit> parent      # the baseline library, where git is
     python tools/seq_prefill_gemm_ab.py ab --baseline-lib kuiperllama_amd/lib/parent.so [--out FILE] [--cases a,b]
-    python tools/seq_prefill_gemm_ab.py prefill --baseline-lib kuiperllama_amd/lib/parent.so
+    python tools/seq_prefill_gemm_ab.py prefill --baseline-lib kuiperllama_amd/lib/parent.so [--tokens N] [--flags a,b]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/seq_prefill_gemm_ab.py pass
     python tools/seq_prefill_gemm_ab.py table DIR/.../*_kernel_stats.csv
     python tools/seq_prefill_gemm_ab.py symbols --baseline-lib kuiperllama_amd/lib/parent.so     # no GPU
@@ -17,8 +17,11 @@ ab:      per geometry (synthetic image), both libraries on ONE device image in o
          (ii)  64 prompts of 32 tokens into 64 slots: 64 kh_model_seq_prefill calls against one seq_prefill_many;
          (iii) 8 prompts of 300 tokens into 8 slots, likewise.
          Prompt tok/s = fed tokens / time; "pad" = the share of a call's slab tokens that are padding.
-prefill: kh_model_time_prefill of a 128-token prefill_gemm, baseline library against this tree, alternating (the
-         statements of k_pg_attn moved into csrc/kh_pattn_body.h; no other existing kernel changed).
+prefill: kh_model_time_prefill of a `--tokens`-token (128) prefill_gemm, alternating in one process: two models of the
+         baseline library - the baseline against itself, whose runs give its own run-to-run range - and one of this tree,
+         all on one device image.  `--flags`: per entry one such comparison - none, or gemm16 / gemm16_f16 / gemm16_q8:
+         the flag with every launch class adopted (its class hook 0x1f) on an image rounded to the format the flag needs
+         (a flag that does not apply to a preset is skipped).  Verdict per line: is the tree's median inside that range.
 pass:    one 512-token prompt on Llama-3.2-1B geometry fed nine times each way, alternating - seq_prefill(1, tokens,
          gemm=True) and the batch-1 prefill_gemm(tokens) - for a kernel trace; table: the k_rg_* / k_pg_* rows of its
          kernel statistics.
@@ -47,7 +50,7 @@ def _i32(v):
 class Baseline:
     """another build of the library on the same device image (ctypes): its seq_prefill and the GEMM prefill's timer"""
 
-    def __init__(self, lib_path, image, spec, max_seq_len):
+    def __init__(self, lib_path, image, spec, max_seq_len, flags=0, hooks=None):
         from kuiperllama_amd import _ffi
         self.L = L = C.CDLL(lib_path)
         i32, p32 = C.c_int32, C.POINTER(C.c_int32)
@@ -58,10 +61,13 @@ class Baseline:
         L.kh_model_time_prefill.argtypes = [C.c_void_p, p32, i32, i32, i32, C.POINTER(C.c_float)]
         L.kh_model_destroy.argtypes = [C.c_void_p]
         L.kh_model_destroy.restype = None
+        L.kh_debug_set.argtypes = [C.c_char_p, C.c_char_p]
+        for k, v in (hooks or {}).items():  # read at creation; the library keeps them, as every model of the process wants
+            assert L.kh_debug_set(k.encode(), v.encode()) == 0
         weights = image[spec.header_bytes():]
         assert weights.data_ptr() % 16 == 0
         header = np.frombuffer(image[:32].cpu().numpy().tobytes(), dtype=np.int32)
-        o = _ffi.ModelOpts(spec.family, int(spec.quant), spec.rope_mode, spec.rope_theta, spec.rms_eps, max_seq_len, 0, 0)
+        o = _ffi.ModelOpts(spec.family, int(spec.quant), spec.rope_mode, spec.rope_theta, spec.rms_eps, max_seq_len, 0, flags)
         self.h = C.c_void_p()
         rc = L.kh_model_create_from_device_weights(_i32(header.tolist()[:8]), weights.data_ptr(), weights.numel(),
                                                    C.byref(o), C.byref(self.h))
@@ -159,26 +165,56 @@ def ab(args):
     _write(args.out, [""], end="")
 
 
+# prefill --flags: name -> (the binding's flag names, the class hook, applies to int8 presets, the image's rounding)
+PREFILL_FLAGS = {"none": ((), None, None, None),
+                 "gemm16": (("KH_FLAG_W16", "KH_FLAG_GEMM16"), "KH_GEMM16_CLASSES", False, "round_matrices_bf16"),
+                 "gemm16_f16": (("KH_FLAG_W16_F16", "KH_FLAG_GEMM16_F16"), "KH_GEMM16_F16_CLASSES", False, "round_matrices_fp16"),
+                 "gemm16_q8": (("KH_FLAG_GEMM16_Q8",), "KH_GEMM16_Q8_CLASSES", True, None)}
+
+
 def prefill(args):
+    from kuiperllama_amd import _ffi, binfmt
     from kuiperllama_amd.model import KuiperModel
-    lines = ["# tools/seq_prefill_gemm_ab.py prefill: kh_model_time_prefill, 128-token prefill_gemm, baseline library vs "
-             "this tree, alternating, ms (min / median / max of 9)"]
+    n = args.tokens
+    lines = [f"# tools/seq_prefill_gemm_ab.py prefill: kh_model_time_prefill, {n}-token prefill_gemm, two models of the baseline "
+             "library and one of this tree, alternating, ms (min / median / max of 9); range: over both baseline models"]
     for name in args.cases.split(","):
-        spec, img = _image(name)
-        new = KuiperModel.from_device_image(img, spec, max_seq_len=512)
-        old = Baseline(args.baseline_lib, img, spec, 512)
-        toks = [int(t) for t in np.random.default_rng(1).integers(0, spec.vocab_size, 128)]
-        a, b = [], []
-        for rep in range(10):
-            x, y = old.time_prefill(toks), new.time_prefill(toks, 0, "gemm")
-            if rep:
-                a.append(x)
-                b.append(y)
-        lines.append(f"{name:16s} baseline {min(a):.3f} / {np.median(a):.3f} / {max(a):.3f}   this tree {min(b):.3f} / "
-                     f"{np.median(b):.3f} / {max(b):.3f}")
-        print(lines[-1], flush=True)
-        new.close()
-        old.close()
+        for flag in args.flags.split(","):
+            names, hook, quant, rounding = PREFILL_FLAGS[flag]
+            spec, img = _image(name)
+            if quant is not None and bool(spec.quant) != quant:
+                continue
+            if rounding:
+                img = getattr(binfmt, rounding)(img, spec)
+            flags = 0
+            for f in names:
+                flags |= getattr(_ffi, f)
+            hooks = {hook: "0x1f"} if hook else {}
+            for k, v in hooks.items():
+                _ffi.debug_set(k, v)
+            new = KuiperModel.from_device_image(img, spec, max_seq_len=max(512, n), flags=flags)
+            for k in hooks:
+                _ffi.debug_set(k, None)
+            old = [Baseline(args.baseline_lib, img, spec, max(512, n), flags, hooks) for _ in range(2)]
+            toks = [int(t) for t in np.random.default_rng(1).integers(0, spec.vocab_size, n)]
+            a, a2, b = [], [], []
+            for rep in range(10):
+                x, x2, y = old[0].time_prefill(toks), old[1].time_prefill(toks), new.time_prefill(toks, 0, "gemm")
+                if rep:
+                    a.append(x)
+                    a2.append(x2)
+                    b.append(y)
+            lo, hi = min(a + a2), max(a + a2)
+            on = {"gemm16": new.gemm16_info, "gemm16_f16": new.gemm16_f16_info, "gemm16_q8": new.gemm16_q8_info}
+            lines.append(f"{name:16s} {flag:10s} {('classes ' + ','.join(on[flag]()['classes'])) if flag in on else '':32s} "
+                         f"baseline {min(a):.3f} / {np.median(a):.3f} / {max(a):.3f}   baseline again {min(a2):.3f} / "
+                         f"{np.median(a2):.3f} / {max(a2):.3f}   this tree {min(b):.3f} / {np.median(b):.3f} / {max(b):.3f}   "
+                         f"range {lo:.3f} .. {hi:.3f}: tree median {'inside' if lo <= np.median(b) <= hi else 'OUTSIDE'}")
+            print(lines[-1], flush=True)
+            new.close()
+            for o in old:
+                o.close()
+            del img
     _write(args.out, lines)
 
 
@@ -265,6 +301,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seq_prefill_gemm_ab.txt"))
     ap.add_argument("--cases", default=",".join(PRESETS))
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--tokens", type=int, default=128, help="prefill: tokens of the timed prompt")
+    ap.add_argument("--flags", default="none", help="prefill: comma list of " + ", ".join(PREFILL_FLAGS))
     args = ap.parse_args()
     if args.mode in ("ab", "prefill", "symbols") and not args.baseline_lib:
         ap.error(f"{args.mode} needs --baseline-lib")
