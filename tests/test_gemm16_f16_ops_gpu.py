@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from kuiperllama_amd import _ffi, ops
-from test_gemm16_ops_gpu import _x_values
+import gemm16_cases as g16
+from kuiperllama_amd import ops
 
 pytestmark = pytest.mark.gpu
 
@@ -24,27 +24,13 @@ def _run(gpu, x, w):
     return y.cpu().numpy()
 
 
-def _one_hot(gpu, x, wv, K, what):
-    M = len(wv)
-    col = np.arange(M) % K
-    w = np.zeros((M, K), np.float32)
-    w[np.arange(M), col] = wv
-    got = _run(gpu, x, w)
-    p64 = x[:, col].astype(np.float64) * wv[None, :].astype(np.float64)
-    want = np.float32(0) + p64.astype(np.float32)  # added to +0
-    assert np.isfinite(want).all() and np.array_equal(want.astype(np.float64), p64 + 0.0)  # the product is an fp32 value
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert not len(bad), f"{what}: {len(bad)} of {got.size} differ, first (token, row) {bad[0]}: " \
-                         f"{got[tuple(bad[0])]!r} vs {want[tuple(bad[0])]!r}"
-
-
 @pytest.mark.parametrize("K,M", SHAPES)
 @pytest.mark.parametrize("T", TOKENS)
 @pytest.mark.parametrize("kind", ["powers of two", "full significands"])
 def test_one_hot_rows_are_bit_exact(gpu, kind, K, M, T):
     rng = np.random.default_rng(1000 * K + 10 * M + T)
     if kind == "powers of two":  # +-2^e over fp16's whole range (w_lo = 0) against full 24-bit x
-        x = _x_values(rng, T, K)  # +-0 and +-FLT_MAX in columns 0 .. 3
+        x = g16.x_values(rng, T, K)  # +-0 and +-FLT_MAX in columns 0 .. 3
         m = np.ones(M)
         e = (np.arange(M) * 7 + T) % 40 - 24  # -24 .. 15, subnormals included; every value where M >= 40
         big = np.isin(np.arange(M) % K, (2, 3))
@@ -55,7 +41,7 @@ def test_one_hot_rows_are_bit_exact(gpu, kind, K, M, T):
         x[0::2, 0], x[1::2, 1] = np.float32(0.0), np.float32(-0.0)
         m = (rng.integers(512, 1024, M) * 2 + 1).astype(np.float64)
         e = (np.arange(M) * 7 + T) % 30 - 24  # -24 .. 5: fp16's normal range for an 11-bit significand
-    _one_hot(gpu, x, (rng.choice([-1.0, 1.0], M) * m * np.exp2(e)).astype(np.float32), K, f"{kind} K {K} M {M} T {T}")
+    g16.one_hot(_run, gpu, x, (rng.choice([-1.0, 1.0], M) * m * np.exp2(e)).astype(np.float32), K, f"{kind} K {K} M {M} T {T}")
 
 
 @pytest.mark.parametrize("M", [64, 80])
@@ -71,31 +57,8 @@ def test_integers_equal_the_int64_product(gpu, M):
 
 
 def test_general_within_twice_the_fp32_gemv_error(gpu):
-    rng = np.random.default_rng(99)
-    T, K, M = 64, 1024, 128
-    w = (rng.standard_normal((M, K), dtype=np.float32) * np.float32(0.05)).astype(np.float16).astype(np.float32)
-    x = rng.standard_normal((T, K), dtype=np.float32)
-    y64 = x.astype(np.float64) @ w.astype(np.float64).T
-    got = _run(gpu, x, w)
-    xd, wd = torch.from_numpy(x).to(gpu), torch.from_numpy(w).to(gpu)
-    y32 = torch.empty((T, M), dtype=torch.float32, device=gpu)
-    for t in range(T):  # the fp32 yardstick: the GEMV kernel of kh_matmul_f32, one row of x at a time
-        ops.matmul(xd[t], wd, y32[t])
-    torch.cuda.synchronize()
-    e16 = float(np.abs(got - y64).max())
-    e32 = float(np.abs(y32.cpu().numpy() - y64).max())
-    ulp = float(np.spacing(np.float32(np.abs(y64).max())))
-    print(f"gemm_h16 vs fp64: {e16:.3e}; kh_matmul_f32 vs fp64: {e32:.3e}; 1 ulp of max |y|: {ulp:.3e}")
-    assert e16 <= 2.0 * e32 + ulp
+    g16.general_case(g16.H16, _run, gpu, lambda w: w.astype(np.float16).astype(np.float32))
 
 
 def test_preconditions(gpu):
-    def rc(T, M, K):
-        x = torch.zeros((T, K), dtype=torch.float32, device=gpu)
-        w = torch.zeros((M, K), dtype=torch.int16, device=gpu)
-        y = torch.zeros((T, (M + 3) // 4 * 4), dtype=torch.float32, device=gpu)
-        return _ffi.lib().kh_gemm_h16_f32(x.data_ptr(), w.data_ptr(), y.data_ptr(), T, M, K, y.stride(0), None)
-    assert rc(4, 24, 32) == _ffi.KH_ERR_UNSUPPORTED   # M % 16
-    assert rc(4, 16, 48) == _ffi.KH_ERR_UNSUPPORTED   # K % 32
-    assert rc(513, 16, 32) == _ffi.KH_ERR_UNSUPPORTED  # T > 512
-    assert rc(512, 16, 32) == 0
+    g16.preconditions(g16.H16, gpu)

@@ -19,22 +19,11 @@ import numpy as np
 import pytest
 import torch
 
+import gemm16_cases as g16
 import split3_ref as s3
-from kuiperllama_amd import _ffi, ops
+from kuiperllama_amd import ops
 
 pytestmark = pytest.mark.gpu
-
-FMAX = np.finfo(np.float32).max
-SPECIAL = {0: 0.0, 1: -0.0, 2: FMAX, 3: -FMAX}  # column -> value, on every other token
-
-
-def _x_values(rng, T, K):
-    m = rng.integers(1 << 23, 1 << 24, (T, K)).astype(np.float64)  # full 24-bit significands
-    e = rng.integers(-30, 31, (T, K)).astype(np.float64)
-    x = (rng.choice([-1.0, 1.0], (T, K)) * m * np.exp2(e - 23)).astype(np.float32)
-    for c, v in SPECIAL.items():
-        x[(c & 1)::2, c] = np.float32(v)
-    return x
 
 
 def _run(gpu, x, w):
@@ -48,19 +37,11 @@ def _run(gpu, x, w):
 @pytest.mark.parametrize("T", [1, 16, 17, 100])
 def test_one_hot_rows_are_bit_exact(gpu, K, M, T):
     rng = np.random.default_rng(1000 * K + 10 * M + T)
-    x = _x_values(rng, T, K)
+    x = g16.x_values(rng, T, K)
     col = np.arange(M) % K
     e = rng.integers(-8, 9, M)
     e[np.isin(col, (2, 3))] = -np.abs(e[np.isin(col, (2, 3))])  # the largest finite value stays finite
-    wv = (rng.choice([-1.0, 1.0], M) * np.exp2(e)).astype(np.float32)
-    w = np.zeros((M, K), np.float32)
-    w[np.arange(M), col] = wv
-    got = _run(gpu, x, w)
-    want = np.float32(0) + x[:, col] * wv[None, :]  # one exact product per element, added to +0
-    assert np.isfinite(want).all()
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert not len(bad), f"K {K} M {M} T {T}: {len(bad)} of {got.size} differ, first (token, row) {bad[0]}: " \
-                         f"{got[tuple(bad[0])]!r} vs {want[tuple(bad[0])]!r}"
+    g16.one_hot(_run, gpu, x, (rng.choice([-1.0, 1.0], M) * np.exp2(e)).astype(np.float32), K, f"K {K} M {M} T {T}")
 
 
 @pytest.mark.parametrize("M", [64, 80])
@@ -76,31 +57,8 @@ def test_integers_equal_the_int64_product(gpu, M):
 
 
 def test_general_within_twice_the_fp32_gemv_error(gpu):
-    rng = np.random.default_rng(99)
-    T, K, M = 64, 1024, 128
-    w = s3.trunc16(rng.standard_normal((M, K), dtype=np.float32) * np.float32(0.05))
-    x = rng.standard_normal((T, K), dtype=np.float32)
-    y64 = x.astype(np.float64) @ w.astype(np.float64).T
-    got = _run(gpu, x, w)
-    xd, wd = torch.from_numpy(x).to(gpu), torch.from_numpy(w).to(gpu)
-    y32 = torch.empty((T, M), dtype=torch.float32, device=gpu)
-    for t in range(T):  # the fp32 yardstick: the GEMV kernel of kh_matmul_f32, one row of x at a time
-        ops.matmul(xd[t], wd, y32[t])
-    torch.cuda.synchronize()
-    e16 = float(np.abs(got - y64).max())
-    e32 = float(np.abs(y32.cpu().numpy() - y64).max())
-    ulp = float(np.spacing(np.float32(np.abs(y64).max())))
-    print(f"gemm_w16 vs fp64: {e16:.3e}; kh_matmul_f32 vs fp64: {e32:.3e}; 1 ulp of max |y|: {ulp:.3e}")
-    assert e16 <= 2.0 * e32 + ulp
+    g16.general_case(g16.W16, _run, gpu, s3.trunc16)
 
 
 def test_preconditions(gpu):
-    def rc(T, M, K):
-        x = torch.zeros((T, K), dtype=torch.float32, device=gpu)
-        w = torch.zeros((M, K), dtype=torch.int16, device=gpu)
-        y = torch.zeros((T, (M + 3) // 4 * 4), dtype=torch.float32, device=gpu)
-        return _ffi.lib().kh_gemm_w16_f32(x.data_ptr(), w.data_ptr(), y.data_ptr(), T, M, K, y.stride(0), None)
-    assert rc(4, 24, 32) == _ffi.KH_ERR_UNSUPPORTED   # M % 16
-    assert rc(4, 16, 48) == _ffi.KH_ERR_UNSUPPORTED   # K % 32
-    assert rc(513, 16, 32) == _ffi.KH_ERR_UNSUPPORTED  # T > 512
-    assert rc(512, 16, 32) == 0
+    g16.preconditions(g16.W16, gpu)

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-import code_objects as co
+import gemm16_cases as g16
 import gemm_q16_ref as ref
 import split3_ref as s3
 from kuiperllama_amd import _ffi, build
@@ -77,51 +77,14 @@ def test_plan_gemm16_q8_masks():
 
 
 def test_gemm16_q8_symbols_are_in_the_abi():
-    build.build_lib()
-    L = _ffi.lib()
-    for n in ("kh_model_gemm16_q8_info", "kh_plan_gemm16_q8", "kh_gemm_q8_bf16_f32"):
-        assert n in _ffi.EXPORTS and hasattr(L, n)
-    assert _ffi.KH_FLAG_GEMM16_Q8 == 256
-    others = [v for k, v in vars(_ffi).items() if k.startswith("KH_FLAG_") and k != "KH_FLAG_GEMM16_Q8"]
-    assert len(others) >= 8 and not any(_ffi.KH_FLAG_GEMM16_Q8 & v for v in others), others
-    src = open(os.path.join(build.CSRC, "..", "..", "include", "kuiper_hip.h")).read()
-    assert "#define KH_FLAG_GEMM16_Q8 256" in src
-    for decl in ("int kh_model_gemm16_q8_info(", "int kh_plan_gemm16_q8(", "int kh_gemm_q8_bf16_f32("):
-        assert decl in src, decl
-    assert L.kh_model_gemm16_q8_info(None, None) == _ffi.KH_ERR_INVALID_ARG
-    assert L.kh_gemm_q8_bf16_f32(None, None, None, None, 1, 16, 64, 16, None) == _ffi.KH_ERR_INVALID_ARG
-    for hook in ("KH_GEMM16_Q8", "KH_GEMM16_Q8_CLASSES"):
-        assert hook.startswith(_ffi._HOOK_PREFIXES)  # sync_env mirrors it from the environment
-        assert _ffi.debug_get(hook) is None
-        try:
-            _ffi.debug_set(hook, "1")
-            assert _ffi.debug_get(hook) == "1"
-        finally:
-            _ffi.debug_set(hook, None)
+    g16.check_abi(g16.Q16, 256, 6)
+    assert _ffi.lib().kh_gemm_q8_bf16_f32(None, None, None, None, 1, 16, 64, 16, None) == _ffi.KH_ERR_INVALID_ARG
     lib_src = open(os.path.join(build.CSRC, "kh_model_gemm_q16.hip")).read()
     assert 'dbg("KH_GEMM16_Q8")' in lib_src and 'dbg("KH_GEMM16_Q8_CLASSES")' in lib_src
-    from kuiperllama_amd import ops
-    from kuiperllama_amd.model import KuiperModel
-    assert callable(KuiperModel.gemm16_q8_info) and callable(ops.gemm_q8_bf16)
-    assert len(_ffi.KH_GEMM16_Q8_REASONS) == 6 and len(_ffi.KH_GEMM16_REASONS) == 9
-    assert "kh_model_gemm_q16.hip" in build.SOURCES and "kh_gemm_q16.h" in build.HEADERS
+    assert len(_ffi.KH_GEMM16_REASONS) == 9
 
 
 def test_gemm16_q8_kernels_in_the_code_objects():
     """The three stems are compiled for the register tiles they take - the int8 stem's without (2,8) - and the
     epilogues of the stems they stand in for, and none of them uses scratch."""
-    if not co.tools_present():
-        import pytest
-        pytest.skip("LLVM tools of the ROCm install not found")
-    notes = co.code_object_notes(build.build_lib())
-    tiles = ((2, 4), (2, 2), (1, 4))
-    want = {
-        "k_pg_gemm_q16": {f"k_pg_gemm_q16<{r},{nt},{e}>" for r, nt in tiles for e in (0, 1, 2)},
-        "k_rg_gemm_q16": {f"k_rg_gemm_q16<{r},{nt},0>" for r, nt in tiles},
-        "k_sg_gemm_q16": {f"k_sg_gemm_q16<{r},{nt},{e}>" for r, nt in tiles for e in (0, 1, 2, 3)},
-    }
-    for stem, w in want.items():
-        got = co.instantiations(notes, {stem})
-        assert got == w, (stem, sorted(got - w), sorted(w - got))
-    scratch = {k: v for k, v in co.kernel_scratch(notes).items() if "_gemm_q16" in k and v}
-    assert not scratch, scratch
+    g16.check_code_objects(g16.Q16)

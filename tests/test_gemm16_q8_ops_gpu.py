@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+import gemm16_cases as g16
 import gemm_q16_ref as ref
 from kuiperllama_amd import _ffi, ops
 
@@ -83,9 +84,7 @@ def test_integers_and_power_of_two_scales_are_bit_exact(gpu, M, K, T):
     got = _run(gpu, x, q, s)
     want = g64.astype(np.float32)
     assert np.array_equal(want.astype(np.float64), g64)
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    assert not len(bad), f"M {M} K {K} T {T}: {len(bad)} of {got.size} differ, first (token, row) {bad[0]}: " \
-                         f"{got[tuple(bad[0])]!r} vs {want[tuple(bad[0])]!r}"
+    g16.assert_same_bits(got, want, f"M {M} K {K} T {T}")
 
 
 @pytest.mark.parametrize("M,K,T", SHAPES)

@@ -1,24 +1,31 @@
-"""Same-box A/B of KH_FLAG_GEMM16 (csrc/kh_gemm_w16.h): the GEMM pass of a W16 model on the bf16 matrix cores against the
-same model on the fp32 matrix cores.
+"""Same-box A/B of the GEMM pass on the bf16 matrix cores against the same model on the fp32 matrix cores, one core per
+run: w16 - KH_FLAG_GEMM16 (csrc/kh_gemm_w16.h), a W16 model from its bf16-format copy; h16 - KH_FLAG_GEMM16_F16
+(csrc/kh_gemm_h16.h), an fp16-origin fp32 model from its fp16-format copy; q16 - KH_FLAG_GEMM16_Q8 (csrc/kh_gemm_q16.h),
+an int8 group-64 model from its int8 image.
 
-    python tools/gemm16_ab.py [--models llama3.2-1b,tinyllama-1.1b,qwen2.5-0.5b,llama2-7b]
-                              [--tree LABEL=PATH ...] [--out profiles/gemm16_ab.txt]
+    python tools/gemm16_ab.py [--core w16|h16|q16] [--models NAME,...] [--tree LABEL=PATH ...] [--out FILE]
 
-One process per model (this script re-invoked with --model) on a synthetic image of the BASELINE geometry whose
-matrices were rounded to bf16; every model of the process has KH_FLAG_W16 on and shares the device image.  Settings:
-flag off; flag on with every class (hook KH_GEMM16_CLASSES=0x1f); flag on with the default mask; and each single class
-(0x1 qkv, 0x2 wo, 0x4 ffn13, 0x8 w2, 0x10 cls), alternated ROUNDS times behind one warm-up round.  Figures, median and
-range over the rounds:
+--models and --out default per core (CORES below): the BASELINE geometries the core was measured on, and
+profiles/gemm16_ab.txt, profiles/gemm16_f16_ab.txt, profiles/gemm16_q8_ab.txt.  A q16 model name ending in -int8 that is
+no preset is that preset's geometry, quantised.
+
+One process per model (this script re-invoked with --model) on a synthetic image of the geometry made exact for the core
+(matrices rounded to bf16 / to fp16 / int8 as synthesised); every model of the process has the copy's flag on (w16:
+KH_FLAG_W16, h16: KH_FLAG_W16_F16) and shares the device image.  Settings: flag off; flag on with every class (the core's
+class-mask hook = 0x1f); flag on with the default mask; and each single class (0x1 qkv, 0x2 wo, 0x4 ffn13, 0x8 w2,
+0x10 cls), alternated ROUNDS times behind one warm-up round.  Figures, median and range over the rounds:
   * kh_model_time_prefill (mode gemm) of 128 and of 512 prompt tokens, as prompt tok/s and ms;
   * seq_prefill_many of 64 x 32 tokens (wall clock around the call and a device synchronise);
   * generate_batch(gemm=True) of 16 and of 64 sequences, 24 sampled steps: the call's own elapsed_ms.
 Per-class times: a single-class model differs from the flag-off model in that class's GEMMs alone, so the difference
 of their 512-token prefill times (cls: of their 64-sequence batches; a prefill runs no classifier) is the class's.
-Adoption rule: a class joins the default mask if its single-class median lies below the flag-off median
-by more than the range of the flag-off runs, on llama3.2-1b and on llama2-7b.
+Adoption rule (3.1g for h16, 3.1f for q16): a class joins the default mask if its single-class median lies
+below the flag-off median by more than the range of the flag-off runs, on every geometry measured (w16: on llama3.2-1b
+and on llama2-7b).
 --tree (repeatable): another checkout of the project to measure beside this one, e.g. the parent commit with its own
 library built; a tree without the flag measures the flag-off row only.  That row of this tree must match it."""
 import argparse
+import dataclasses
 import os
 import statistics
 import subprocess
@@ -31,36 +38,61 @@ SETTINGS = ((None, "off"), ("0x1f", "all"), ("default", "default"), ("0x1", "qkv
 ROUNDS = 5
 FIGURES = ("prefill128 ms", "prefill512 ms", "slots 64x32 ms", "batch16 ms", "batch64 ms")
 STEPS = 24
+# core -> what differs: the flag and the copy's flag beside it (names in _ffi), how the image is made exact (binfmt), the
+# class-mask hook, the info method, the default --models and --out, the header's two phrases, and three phrases of the lines
+CORES = {
+    "w16": dict(flag="KH_FLAG_GEMM16", copy_flag="KH_FLAG_W16", make_exact="round_matrices_bf16", hook="KH_GEMM16_CLASSES",
+                info="gemm16_info", models="llama3.2-1b,tinyllama-1.1b,qwen2.5-0.5b,llama2-7b", out="gemm16_ab.txt",
+                header=("W16 models", "bf16-rounded synthetic images"), ran="classes with K % 32 == 0",
+                keeps="keeps its fp32 kernel on this geometry (K % 32)"),
+    "h16": dict(flag="KH_FLAG_GEMM16_F16", copy_flag="KH_FLAG_W16_F16", make_exact="round_matrices_fp16",
+                hook="KH_GEMM16_F16_CLASSES", info="gemm16_f16_info", models="llama3.2-1b,tinyllama-1.1b,llama2-7b",
+                out="gemm16_f16_ab.txt", header=("fp16-origin models", "fp16-rounded synthetic images"),
+                ran="classes with K % 32 == 0", keeps="keeps its fp32 kernel on this geometry (K % 32)"),
+    "q16": dict(flag="KH_FLAG_GEMM16_Q8", copy_flag=None, make_exact=None, hook="KH_GEMM16_Q8_CLASSES",
+                info="gemm16_q8_info", models="llama2-7b-int8,tinyllama-1.1b-int8", out="gemm16_q8_ab.txt",
+                header=("int8 group-64 models", "synthetic int8 images"), ran="under 0x1f",
+                keeps="keeps its int8 kernel on this geometry"),
+}
 
 
 def _med_range(v):
     return statistics.median(v), max(v) - min(v)
 
 
-def one_model(name, tree):
+def one_model(core, name, tree):
     import torch
     sys.path.insert(0, tree)
     from kuiperllama_amd import _ffi, binfmt
     from kuiperllama_amd.model import KuiperModel
-    has_flag = hasattr(_ffi, "KH_FLAG_GEMM16")
-    spec = binfmt.PRESETS[name]
+    c = CORES[core]
+    has_flag = hasattr(_ffi, c["flag"])
+    spec = binfmt.PRESETS.get(name)
+    if core == "q16":
+        spec = spec or dataclasses.replace(binfmt.PRESETS[name[:-len("-int8")]], quant=True, group_size=64, name=name)
+        assert spec.quant and spec.group_size == 64, spec
     dev = torch.device("cuda:0")
     img = binfmt.synth_image(spec, seed=1234, device=dev)
-    binfmt.round_matrices_bf16(img, spec)
+    if c["make_exact"]:
+        img = getattr(binfmt, c["make_exact"])(img, spec)
     torch.cuda.synchronize()
     m = {}
     for hook, label in SETTINGS if has_flag else SETTINGS[:1]:
-        flags = _ffi.KH_FLAG_W16
+        flags = getattr(_ffi, c["copy_flag"]) if c["copy_flag"] else 0
         if hook is not None:
-            flags |= _ffi.KH_FLAG_GEMM16
-            _ffi.debug_set("KH_GEMM16_CLASSES", None if hook == "default" else hook)
+            flags |= getattr(_ffi, c["flag"])
+            _ffi.debug_set(c["hook"], None if hook == "default" else hook)
         m[label] = KuiperModel.from_device_image(img, spec, max_seq_len=2048, flags=flags)
     if has_flag:
-        _ffi.debug_set("KH_GEMM16_CLASSES", None)
-    assert m["off"].w16_info()["state"] == 1, m["off"].w16_info()
+        _ffi.debug_set(c["hook"], None)
+    if core == "w16":
+        assert m["off"].w16_info()["state"] == 1, m["off"].w16_info()
+    if core == "h16":
+        assert m["off"].w16_format()["format"] == "fp16", m["off"].w16_format()
+    info = {label: getattr(mm, c["info"]) for label, mm in m.items()} if has_flag else {}
     print(f"## {name}: dim {spec.dim} hidden {spec.hidden_dim} layers {spec.n_layers} vocab {spec.vocab_size}"
-          + (f"; default mask {','.join(m['default'].gemm16_info()['classes']) or 'none'}; classes with K % 32 == 0: "
-             f"{','.join(m['all'].gemm16_info()['classes'])}" if has_flag else "; this tree has no KH_FLAG_GEMM16"))
+          + (f"; default mask {','.join(info['default']()['classes']) or 'none'}; {c['ran']}: "
+             f"{','.join(info['all']()['classes'])}" if has_flag else f"; this tree has no {c['flag']}"))
     toks = [1] + [(263 + 7 * i) % spec.vocab_size for i in range(511)]
     segs = [[(11 + 5 * s + 3 * i) % spec.vocab_size for i in range(32)] for s in range(64)]
     prompts = [[1, 263 + s] for s in range(64)]
@@ -93,14 +125,14 @@ def one_model(name, tree):
         print(f"{f}: off / all {off / statistics.median(t['all'][f]):.2f} x, off / default "
               f"{off / statistics.median(t['default'][f]):.2f} x")
     print("per-class time with the flag off -> on (difference to the flag-off model), and the adoption rule:")
-    ran = m["all"].gemm16_info()["classes"]
-    for c in ("qkv", "wo", "ffn13", "w2", "cls"):
-        f = "batch64 ms" if c == "cls" else "prefill512 ms"
-        (m0, r0), (m1, r1) = _med_range(t["off"][f]), _med_range(t[c][f])
-        if c not in ran:
-            print(f"{c:6s} keeps its fp32 kernel on this geometry (K % 32)")
+    ran = info["all"]()["classes"]
+    for cl in ("qkv", "wo", "ffn13", "w2", "cls"):
+        f = "batch64 ms" if cl == "cls" else "prefill512 ms"
+        (m0, r0), (m1, r1) = _med_range(t["off"][f]), _med_range(t[cl][f])
+        if cl not in ran:
+            print(f"{cl:6s} {c['keeps']}")
             continue
-        print(f"{c:6s} {f}: off {m0:.3f} (range {r0:.3f})  class on {m1:.3f} (range {r1:.3f})  {m1 - m0:+.3f} ms "
+        print(f"{cl:6s} {f}: off {m0:.3f} (range {r0:.3f})  class on {m1:.3f} (range {r1:.3f})  {m1 - m0:+.3f} ms "
               f"({(m1 / m0 - 1) * 100:+.1f} %)  {'passes' if m1 < m0 - r0 else 'FAILS (not below flag-off by more than its range)'}")
     for mm in m.values():
         mm.close()
@@ -109,15 +141,19 @@ def one_model(name, tree):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", help="(internal) measure one model in this process and print its lines")
-    ap.add_argument("--models", default="llama3.2-1b,tinyllama-1.1b,qwen2.5-0.5b,llama2-7b")
+    ap.add_argument("--core", choices=sorted(CORES), default="w16")
+    ap.add_argument("--models", help="default: the core's (CORES)")
     ap.add_argument("--tree", action="append", default=[], help="LABEL=PATH of another checkout to measure too")
     ap.add_argument("--this-tree", default=ROOT, help="(internal) the checkout --model measures")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gemm16_ab.txt"))
+    ap.add_argument("--out", help="default: the core's file under profiles/ (CORES)")
     a = ap.parse_args()
     if a.model:
-        return one_model(a.model, a.this_tree)
-    lines = ["# tools/gemm16_ab.py: the GEMM pass of W16 models on the bf16 matrix cores (KH_FLAG_GEMM16) against the "
-             "fp32 matrix cores, bf16-rounded synthetic images, one MI355X, one process per model and tree", ""]
+        return one_model(a.core, a.model, a.this_tree)
+    c = CORES[a.core]
+    a.models = a.models if a.models is not None else c["models"]
+    a.out = a.out or os.path.join(ROOT, "profiles", c["out"])
+    lines = [f"# tools/gemm16_ab.py --core {a.core}: the GEMM pass of {c['header'][0]} on the bf16 matrix cores ({c['flag']}) "
+             f"against the fp32 matrix cores, {c['header'][1]}, one MI355X, one process per model and tree", ""]
 
     def emit(s):
         lines.append(s)
@@ -129,7 +165,7 @@ def main():
     for name in [n for n in a.models.split(",") if n]:
         for label, path in trees:
             emit(f"# ---- {label}")
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--model", name, "--this-tree",
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--core", a.core, "--model", name, "--this-tree",
                                 os.path.abspath(path)], capture_output=True, text=True, timeout=900,
                                cwd=os.path.abspath(path))
             for s in p.stdout.splitlines():
