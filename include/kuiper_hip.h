@@ -304,6 +304,16 @@ int64_t kh_cls_logprobs_workspace_bytes(int32_t T, int32_t vocab, int32_t dim);
 int kh_cls_logprobs_f32(const float* W, const float* X, int32_t T, int32_t vocab, int32_t dim, const int32_t* d_targets,
                         int32_t top_n, float* d_lse, float* d_lp, int32_t* d_top_ids, float* d_top_lp, float* d_max,
                         float* d_target_logit, void* workspace, int64_t workspace_bytes, void* stream);
+/* kh_cls_logprobs_f32 on the bf16 matrix cores (csrc/kh_score_gemm_w16.h: k_pg_cls_lse_w16, then k_pg_lse_merge): W16
+ * [vocab][dim] holds the bf16 bits of the weights, row-major; X stays fp32 and is split exactly into three bf16 terms,
+ * so each logit is the fp32 dot product in another summation order (kh_gemm_w16_f32's numerics).  The weights must be
+ * FINITE: an infinite weight times a zero term of the split is NaN.  The other arguments, the workspace
+ * (kh_cls_logprobs_workspace_bytes) and the codes are kh_cls_logprobs_f32's, with KH_ERR_UNSUPPORTED for vocab % 16 != 0
+ * or dim % 32 != 0. */
+int kh_cls_logprobs_w16_f32(const uint16_t* W16, const float* X, int32_t T, int32_t vocab, int32_t dim,
+                            const int32_t* d_targets, int32_t top_n, float* d_lse, float* d_lp, int32_t* d_top_ids,
+                            float* d_top_lp, float* d_max, float* d_target_logit, void* workspace, int64_t workspace_bytes,
+                            void* stream);
 
 /* Constrained decoding: a TOKEN AUTOMATON is a deterministic automaton over token ids in CSR form.  Row s =
  * tokens[row_ptr[s] .. row_ptr[s + 1]) holds the ids allowed in state s, strictly ascending, and next[] the state behind
@@ -805,8 +815,12 @@ int kh_model_score(kh_model* m, const int32_t* h_tokens, int32_t n, int32_t pos0
  * kh_model_prefill_gemm leaves them.
  * Contract: kh_model_prefill_gemm's, NOT the bit-exact one of kh_model_score - the logits differ from the decode
  * classifier's by fp32 round-off of another summation order.  On the pass's own logits the top ids are exact and lse /
- * lp within kh_logprobs_f32's bound.  Reads the fp32 or int8 image, also under KH_FLAG_W16 / KH_FLAG_GEMM16* / KH_FLAG_Q4
- * (the classifier never runs on a weight copy here).  Opt-in: no other call is rerouted to it.  The first call allocates
+ * lp within kh_logprobs_f32's bound.  The layer GEMMs are kh_model_prefill_gemm's, KH_FLAG_GEMM16* included.  The
+ * classifier reads the fp32 or int8 image, also under KH_FLAG_W16 / KH_FLAG_GEMM16_F16 / KH_FLAG_GEMM16_Q8 / KH_FLAG_Q4,
+ * with ONE exception: where KH_FLAG_GEMM16 is live on a bf16-format copy and the cls class is in the model's mask (not
+ * by default: hook KH_GEMM16_CLASSES=0x1f at creation) it runs on the bf16 matrix cores from the copy
+ * (csrc/kh_score_gemm_w16.h: k_pg_cls_lse_w16, the activations split into three bf16 terms once per workgroup) - the
+ * same contract, the logits in yet another summation order.  Opt-in: no other call is rerouted to it.  The first call allocates
  * its workspace (one partial record per 128 vocabulary rows and pass token, 176 bytes each); a model that never calls
  * this allocates and launches nothing new.
  * Before any launch: kh_model_score's argument and range codes; KH_ERR_UNSUPPORTED while log-probs are off, for the

@@ -19,7 +19,7 @@ EXPORTS = [
     "kh_rmsnorm_f32", "kh_rope_f32", "kh_sincos_cache_f32", "kh_mha_f32", "kh_mha_decode_f32", "kh_mha_prefill_f32",
     "kh_mha_prefill_layout_f32", "kh_mha_prefill_tiles_f32", "kh_mha_decode_lanes_f32",
     "kh_mha_decode_workspace_bytes", "kh_argmax_f32", "kh_argmax_rows_f32",
-    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_cls_logprobs_workspace_bytes", "kh_cls_logprobs_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
+    "kh_argmax_f32_host", "kh_sample_f32", "kh_sample_f32_host", "kh_logit_process_workspace_bytes", "kh_logit_process_f32", "kh_logprobs_f32", "kh_cls_logprobs_workspace_bytes", "kh_cls_logprobs_f32", "kh_cls_logprobs_w16_f32", "kh_softmax_f32", "kh_scale_f32", "kh_scale_sum_f32",
     "kh_model_create_from_file", "kh_model_create_from_host_image",
     "kh_model_create_from_device_weights", "kh_model_destroy", "kh_model_get_config",
     "kh_model_stream", "kh_model_get_load_ms", "kh_model_predict", "kh_model_get_logits", "kh_model_cls_screen_info", "kh_model_cls_screen_probe", "kh_model_cls_screen_read", "kh_model_cls_screen_q8_info", "kh_model_cls_screen_q8_probe", "kh_model_cls_screen_q8_read", "kh_model_w16_info", "kh_model_q4_info", "kh_model_gemm16_info", "kh_model_gemm16_q8_info", "kh_model_gemm16_f16_info", "kh_model_wide_attn_info", "kh_model_get_kv", "kh_model_kv_bytes", "kh_model_read_kv", "kh_model_write_kv",
@@ -297,6 +297,7 @@ def lib() -> C.CDLL:
     L.kh_cls_logprobs_workspace_bytes.argtypes = [_i32, _i32, _i32]
     L.kh_cls_logprobs_workspace_bytes.restype = _i64
     L.kh_cls_logprobs_f32.argtypes = [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.kh_cls_logprobs_w16_f32.argtypes = L.kh_cls_logprobs_f32.argtypes
     L.kh_model_verify_width.argtypes = [_vp, C.POINTER(_i32)]
     L.kh_model_verify.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]
     L.kh_model_generate_lookup.argtypes = [_vp, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), _i32,

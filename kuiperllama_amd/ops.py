@@ -337,9 +337,11 @@ def logprobs(logits, ids, top_n: int = 0) -> dict:
 
 def cls_logprobs(w, x, targets=None, top_n: int = 0) -> dict:
     """ops.logprobs of the logits x @ w.T without the logits (kh_cls_logprobs_f32: the classifier GEMM on the matrix
-    cores with the log-softmax in its epilogue, csrc/kh_score_gemm.h).  w: float32 GPU tensor [vocab, dim]; x: [T, dim],
-    T <= 512; targets: int32 GPU tensor [T] (None or an id outside [0, vocab): NaN).  Returns ops.logprobs' four keys
-    plus "max" (the largest logit of every token) and "target_logit", as GPU tensors."""
+    cores with the log-softmax in its epilogue, csrc/kh_score_gemm.h).  w: float32 GPU tensor [vocab, dim], or a
+    bfloat16 one of finite values with dim % 32 == 0 (kh_cls_logprobs_w16_f32: the bf16 matrix cores,
+    csrc/kh_score_gemm_w16.h); x: float32 [T, dim], T <= 512; targets: int32 GPU tensor [T] (None or an id outside
+    [0, vocab): NaN).  Returns ops.logprobs' four keys plus "max" (the largest logit of every token) and
+    "target_logit", as GPU tensors."""
     V, K = w.shape
     T = x.shape[0]
     if x.shape[1] != K or (targets is not None and targets.numel() != T):
@@ -350,10 +352,12 @@ def cls_logprobs(w, x, targets=None, top_n: int = 0) -> dict:
            "top_logprobs": f(T, n), "max": f(T), "target_logit": f(T)}
     L = _ffi.lib()
     ws = torch.empty(max(int(L.kh_cls_logprobs_workspace_bytes(T, V, K)), 16), dtype=torch.uint8, device=dev)
-    _ffi.check(L.kh_cls_logprobs_f32(_p(w, torch.float32), _p(x, torch.float32), T, V, K, _p(targets, torch.int32),
-                                     int(top_n), _p(out["lse"]), _p(out["logprob"]), _p(out["top_ids"]),
-                                     _p(out["top_logprobs"]), _p(out["max"]), _p(out["target_logit"]), _p(ws),
-                                     ws.numel(), _stream()), "kh_cls_logprobs_f32")
+    entry = "kh_cls_logprobs_w16_f32" if w.dtype == torch.bfloat16 else "kh_cls_logprobs_f32"
+    wp = _p(w, torch.bfloat16 if w.dtype == torch.bfloat16 else torch.float32)
+    _ffi.check(getattr(L, entry)(wp, _p(x, torch.float32), T, V, K, _p(targets, torch.int32),
+                                 int(top_n), _p(out["lse"]), _p(out["logprob"]), _p(out["top_ids"]),
+                                 _p(out["top_logprobs"]), _p(out["max"]), _p(out["target_logit"]), _p(ws),
+                                 ws.numel(), _stream()), entry)
     return out
 
 
